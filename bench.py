@@ -35,8 +35,8 @@ import torch.distributed as dist
 ROOT = Path(__file__).resolve().parent
 sys.path.insert(0, str(ROOT))
 
-PEAK_FP32_MFMA_TFLOPS = 157.3     # /opt/skills/guides/MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, 256 CUs x 4 SIMD x 64 FLOP/clk x 2.4 GHz
-PEAK_BF16_MFMA_TFLOPS = 2500.0    # same guide: dense bf16 MFMA (the headline 5 PFLOP/s figure includes 2:1 sparsity)
+PEAK_FP32_MFMA_TFLOPS = 157.3     # MI355X microarchitecture: v_mfma_f32_32x32x2_f32, 256 CUs x 4 SIMD x 64 FLOP/clk x 2.4 GHz
+PEAK_BF16_MFMA_TFLOPS = 2500.0    # same source: dense bf16 MFMA (the headline 5 PFLOP/s figure includes 2:1 sparsity)
 PEAK_HBM_GBPS = 8000.0            # HBM3E spec
 FWD_GFLOP_PER_IMG = 45.15         # conv layers only, 512x512, M+N+4 = 7
 TRAIN_GFLOP_PER_IMG = 135.5
@@ -186,6 +186,35 @@ def pmc_traffic(kind):
     return round(row["hbm_bytes_per_launch"]), src
 
 
+DUMP_SAMPLE = 4 << 20            # floats per sampled array: 16 MB each, ~33 MB in all
+DUMP_SEED = 20251015
+
+
+def dump_outputs(directory, net, loss):
+    """What the last timed step computed, as a caller of TrainStep sees it, written as float32 .npy files for comparing builds:
+      * loss.npy         [total, heatmap, offset, embedding] -- TrainStep's return value;
+      * params.npy       the updated weights after Adam, flattened in state_dict order and logical (OIHW) layout,
+                         sampled at DUMP_SAMPLE positions: sorted(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False));
+      * grads.npy        the gradients of the same step at the same positions;
+      * bn_running.npy   every BatchNorm running_mean then running_var, in named_buffers order (all of them).
+    The inputs of a bench run are seeded, so two runs with the same arguments dump comparable arrays."""
+    params = list(net.parameters())
+    with torch.no_grad():
+        w = torch.cat([p.detach().reshape(-1) for p in params])
+        g = torch.cat([net.grad_of(p).reshape(-1) for p in params])
+        bn = [b for name, b in net.named_buffers() if name.endswith("running_mean")] + \
+             [b for name, b in net.named_buffers() if name.endswith("running_var")]
+        bn = torch.cat([b.detach().reshape(-1).float() for b in bn])
+    n = w.numel()
+    k = min(n, DUMP_SAMPLE)
+    idx = torch.from_numpy(np.sort(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False))).to(w.device)
+    arrays = {"loss": loss, "params": w[idx], "grads": g[idx], "bn_running": bn}
+    directory.mkdir(parents=True, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(directory / f"{name}.npy", t.detach().float().cpu().numpy())
+    print(f"bench.py: wrote {', '.join(arrays)} (.npy) to {directory}", file=sys.stderr, flush=True)
+
+
 def self_launch(n, argv):
     """Spawn `python -m torch.distributed.run --nnodes=1 --nproc-per-node n ... bench.py <argv>` (the driver's own launch line),
     wait, and return the child's exit code.  No torch.cuda call happens in this (parent) process."""
@@ -235,7 +264,12 @@ def main():
                     help="skip the north-star side figures measured AFTER the timed region (eval forward bs=B / bs=1, bf16 forward, "
                          "configs[4] stress forward + decode): use it under rocprofv3 --stats so that the per-kernel averages "
                          "describe the timed training steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (rank 0): the loss vector, a fixed "
+                         "sample of the updated weights and of the gradients, the BatchNorm running statistics (see dump_outputs)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves, as a CHILD `torch.distributed.run`, BEFORE
@@ -350,6 +384,8 @@ def main():
     net._engine.prof = None
     barrier()
     dt = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:                     # before anything else runs a step on these weights
+        dump_outputs(Path(a.dump_outputs), net, loss)
     prof, prof_steps = events, sampled
     if not prof:                                         # --no-conv-events: the per-kernel figures come from three extra (untimed) steps
         net._engine.prof = prof = []
