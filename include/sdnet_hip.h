@@ -502,10 +502,17 @@ int sd_maxpool_bn_relu_bwd(const float* dpool, const uint8_t* idx, const float* 
 int sd_upsample2x_bwd(const float* dy, const float* add, float* dx, int B, int H, int W, int C, sd_stream_t stream);
 
 /* Head (network.py:22-29): 1x1 conv C -> Co with bias; NHWC in, NCHW out (the layout the decoder
- * and the loss consume).  Co <= 32.  C = 128 (the default FPN depth), Co <= 16, HW % 16 == 0 and 16-byte aligned pointers take the
- * MFMA kernels (forward: wave-private LDS-DMA ring + v_mfma_f32_16x16x4_f32; backward: weight-gradient partials likewise, one partial
- * row per wave, before the data gradient); other shapes the generic kernels.  Same arithmetic either way (fp32 products and sums;
- * the order of the sums differs). */
+ * and the loss consume).  1 <= Co <= SD_HEAD_MAX_CO, i.e. up to 252 labels + parts.
+ *   Co <= 32: C = 128 (the default FPN depth), Co <= 16, HW % 16 == 0 and 16-byte aligned pointers take the MFMA kernels (forward:
+ *     wave-private LDS-DMA ring + v_mfma_f32_16x16x4_f32; backward: weight-gradient partials likewise, one partial row per wave, before
+ *     the data gradient); other shapes the generic kernels (C % 4 == 0, C <= 512 forward; C in {64, 128, 256} backward).
+ *   33 <= Co <= 256: C in {64, 128, 256} and B * HW < 2^31, else SD_ERR_INVALID; the forwards need x 16-byte aligned (SD_ERR_ALIGN).
+ *     Every pass is a GEMM over the pixels on the MFMA (sd_head_wide.hip): fp32 forward, data gradient and weight-gradient partials on
+ *     v_mfma_f32_32x32x2_f32, the bf16 forward on v_mfma_f32_32x32x16_bf16 with the fp32 weights split into two bf16 terms.  Any HW
+ *     (ragged tiles are masked).  The workspace holds a fixed number of partial rows that depends on the shape only (at most
+ *     about 17 MB; repeated calls give the same bits).
+ * Same arithmetic on every path (fp32 products and sums; the order of the sums differs). */
+#define SD_HEAD_MAX_CO 256
 int sd_head_fwd(const float* x_nhwc, const float* w, const float* bias, float* y_nchw, int B, int HW, int C, int Co,
                 sd_stream_t stream);
 size_t sd_head_bwd_workspace_bytes(int B, int HW, int C, int Co);

@@ -72,6 +72,17 @@ __device__ __forceinline__ void st4(uint16_t* p, int64_t i, const float4 v) {
     reinterpret_cast<uint2*>(p)[i] = pk;
 }
 
+// Head (1x1 conv C -> Co): Co <= HEAD_NARROW_MAX_CO takes the kernels of sd_nn.hip; wider heads (up to SD_HEAD_MAX_CO, C in {64, 128, 256})
+// the GEMM kernels of sd_head_wide.hip, reached through the sd_head_* entry points of sd_nn.hip.
+constexpr int HEAD_NARROW_MAX_CO = 32;
+int head_wide_check(const char* fn, int64_t P, int C, int Co);                       // 0, or SD_ERR_INVALID with the message set
+int head_wide_fwd(const float* x, const float* w, const float* bias, float* y, int B, int HW, int C, int Co, hipStream_t st);
+int head_wide_fwd_bf16(const void* x, const float* w, const float* bias, float* y, int B, int HW, int C, int Co, hipStream_t st);
+size_t head_wide_bwd_workspace_bytes(int64_t P, int C, int Co);
+// weight / bias gradient partial rows (rows x (Co * C + Co) floats, finished by the caller in a fixed order), and the data gradient
+int head_wide_wgrad(const float* dy, const float* x, float* partial, int B, int HW, int C, int Co, hipStream_t st, int& rows);
+int head_wide_dgrad(const float* dy, const float* w, float* dx, int B, int HW, int C, int Co, hipStream_t st);
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);

@@ -696,8 +696,6 @@ __global__ __launch_bounds__(256) void k_up2_bwd(const T* __restrict__ dy, const
 // 4-float row pad (ds_read_b128 conflict-free), then thread (pixel, group) accumulates its
 // outputs with wave-uniform (broadcast) weight reads.  HBM-bound: AI ~ 3 flop/B.
 // ------------------------------------------------------------------------------------------
-constexpr int HEAD_MAX_CO = 32;
-
 __global__ __launch_bounds__(256) void k_head_fwd(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
                                                    float* __restrict__ y, int64_t M, int HW, int C, int Co) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -715,13 +713,13 @@ __global__ __launch_bounds__(256) void k_head_fwd(const float* __restrict__ x, c
     for (int i = threadIdx.x; i < Co * C; i += 256) ws[i] = w[i];
     __syncthreads();
     const int px = threadIdx.x & 63, grp = threadIdx.x >> 6;
-    float acc[HEAD_MAX_CO / 4];
+    float acc[HEAD_NARROW_MAX_CO / 4];
 #pragma unroll
-    for (int j = 0; j < HEAD_MAX_CO / 4; ++j) acc[j] = 0.f;
+    for (int j = 0; j < HEAD_NARROW_MAX_CO / 4; ++j) acc[j] = 0.f;
     for (int c = 0; c < C; c += 4) {
         const float4 v = *reinterpret_cast<const float4*>(xs + px * LD + c);
 #pragma unroll
-        for (int j = 0; j < HEAD_MAX_CO / 4; ++j) {
+        for (int j = 0; j < HEAD_NARROW_MAX_CO / 4; ++j) {
             const int co = grp + 4 * j;
             if (co < Co) {
                 const float4 ww = *reinterpret_cast<const float4*>(ws + co * C + c);
@@ -733,7 +731,7 @@ __global__ __launch_bounds__(256) void k_head_fwd(const float* __restrict__ x, c
     if (m < M) {
         const int64_t b = m / HW, pix = m - b * HW;
 #pragma unroll
-        for (int j = 0; j < HEAD_MAX_CO / 4; ++j) {
+        for (int j = 0; j < HEAD_NARROW_MAX_CO / 4; ++j) {
             const int co = grp + 4 * j;
             if (co < Co) y[(b * Co + co) * HW + pix] = acc[j] + bias[co];
         }
@@ -815,7 +813,7 @@ constexpr int HEAD_WG_PIX = 1024;   // pixels per block of the head weight-gradi
 template <typename T>      // T = float, or uint16_t: dx is stored as bf16 (mixed-precision training)
 __global__ __launch_bounds__(256) void k_head_dgrad(const float* __restrict__ dy, const float* __restrict__ w, T* __restrict__ dx,
                                                      int64_t M, int HW, int C, int Co) {
-    __shared__ float gs[HEAD_MAX_CO][64];
+    __shared__ float gs[HEAD_NARROW_MAX_CO][64];
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* ws = lds;                 // [Co][C]
     const int64_t m0 = (int64_t)blockIdx.x * 64;
@@ -934,15 +932,15 @@ __global__ __launch_bounds__(256) void k_head_wgrad_bf16(const float* __restrict
 // accumulates Co sums over its half of every chunk (all 256 threads busy when C == 128), 8 loads in flight.
 __global__ __launch_bounds__(256) void k_head_wgrad(const float* __restrict__ dy, const float* __restrict__ x, float* __restrict__ partial,
                                                      int64_t M, int HW, int C, int Co) {
-    __shared__ float gs[HEAD_MAX_CO][64];
-    __shared__ float comb[HEAD_MAX_CO][256];
+    __shared__ float gs[HEAD_NARROW_MAX_CO][64];
+    __shared__ float comb[HEAD_NARROW_MAX_CO][256];
     const int64_t mb = (int64_t)blockIdx.x * HEAD_WG_PIX;
     const int halves = max(1, 256 / C);                 // pixel sub-ranges handled in parallel
     const int c = threadIdx.x % C, hf = threadIdx.x / C;
     const int span = 64 / halves;
-    float acc[HEAD_MAX_CO];
+    float acc[HEAD_NARROW_MAX_CO];
 #pragma unroll
-    for (int j = 0; j < HEAD_MAX_CO; ++j) acc[j] = 0.f;
+    for (int j = 0; j < HEAD_NARROW_MAX_CO; ++j) acc[j] = 0.f;
     float bsum = 0.f;                                   // thread co < Co also accumulates the bias gradient
     for (int64_t m0 = mb; m0 < min(mb + HEAD_WG_PIX, M); m0 += 64) {
         __syncthreads();
@@ -967,7 +965,7 @@ __global__ __launch_bounds__(256) void k_head_wgrad(const float* __restrict__ dy
 #pragma unroll
                 for (int u = 0; u < 8; ++u)
 #pragma unroll
-                    for (int j = 0; j < HEAD_MAX_CO; ++j)
+                    for (int j = 0; j < HEAD_NARROW_MAX_CO; ++j)
                         if (j < Co) acc[j] += gs[j][p0 + pb + u] * xv[u];
             }
         }
@@ -1189,13 +1187,13 @@ __global__ __launch_bounds__(256) void k_head_fwd_bf16(const uint16_t* __restric
     for (int i = threadIdx.x; i < Co * C; i += 256) ws[i] = w[i];
     __syncthreads();
     const int px = threadIdx.x & 63, grp = threadIdx.x >> 6;
-    float acc[HEAD_MAX_CO / 4];
+    float acc[HEAD_NARROW_MAX_CO / 4];
 #pragma unroll
-    for (int j = 0; j < HEAD_MAX_CO / 4; ++j) acc[j] = 0.f;
+    for (int j = 0; j < HEAD_NARROW_MAX_CO / 4; ++j) acc[j] = 0.f;
     for (int c = 0; c < C; c += 4) {
         const float4 v = *reinterpret_cast<const float4*>(xs + px * LD + c);
 #pragma unroll
-        for (int j = 0; j < HEAD_MAX_CO / 4; ++j) {
+        for (int j = 0; j < HEAD_NARROW_MAX_CO / 4; ++j) {
             const int co = grp + 4 * j;
             if (co < Co) {
                 const float4 ww = *reinterpret_cast<const float4*>(ws + co * C + c);
@@ -1207,7 +1205,7 @@ __global__ __launch_bounds__(256) void k_head_fwd_bf16(const uint16_t* __restric
     if (m < M) {
         const int64_t b = m / HW, pix = m - b * HW;
 #pragma unroll
-        for (int j = 0; j < HEAD_MAX_CO / 4; ++j) {
+        for (int j = 0; j < HEAD_NARROW_MAX_CO / 4; ++j) {
             const int co = grp + 4 * j;
             if (co < Co) y[(b * Co + co) * HW + pix] = acc[j] + bias[co];
         }
@@ -1893,7 +1891,8 @@ int sd_maxpool3x3s2_fwd_bf16(const void* x, void* y, int B, int Hi, int Wi, int 
 
 int sd_head_fwd_bf16(const void* x, const float* w, const float* bias, float* y, int B, int HW, int C, int Co, sd_stream_t stream) {
     SD_REQUIRE(x && w && bias && y && B > 0 && HW > 0, SD_ERR_INVALID, "sd_head_fwd_bf16: bad arguments");
-    SD_REQUIRE(C % 8 == 0 && C <= 512 && Co > 0 && Co <= HEAD_MAX_CO, SD_ERR_INVALID, "sd_head_fwd_bf16: needs C %% 8 == 0, C <= 512, Co <= %d", HEAD_MAX_CO);
+    if (Co > HEAD_NARROW_MAX_CO) return head_wide_fwd_bf16(x, w, bias, y, B, HW, C, Co, (hipStream_t)stream);    // sd_head_wide.hip
+    SD_REQUIRE(C % 8 == 0 && C <= 512 && Co > 0 && Co <= HEAD_NARROW_MAX_CO, SD_ERR_INVALID, "sd_head_fwd_bf16: needs C %% 8 == 0, C <= 512, Co <= %d", HEAD_NARROW_MAX_CO);
     const int64_t M = (int64_t)B * HW;
     if (C == 128 && HW % 4 == 0 && aligned16(x) && aligned16(y)) {       // wave-private LDS-DMA + bf16 MFMA pipeline (the default FPN depth)
         const int ntiles = (int)cdiv(M, 64), blocks = std::max(1, std::min(cdiv(ntiles, 4), 1024));
@@ -1910,7 +1909,8 @@ int sd_head_fwd_bf16(const void* x, const float* w, const float* bias, float* y,
 
 int sd_head_fwd(const float* x, const float* w, const float* bias, float* y, int B, int HW, int C, int Co, sd_stream_t stream) {
     SD_REQUIRE(x && w && bias && y && B > 0 && HW > 0, SD_ERR_INVALID, "sd_head_fwd: bad arguments");
-    SD_REQUIRE(C % 4 == 0 && C <= 512 && Co > 0 && Co <= HEAD_MAX_CO, SD_ERR_INVALID, "sd_head_fwd: needs C %% 4 == 0, C <= 512, Co <= %d", HEAD_MAX_CO);
+    if (Co > HEAD_NARROW_MAX_CO) return head_wide_fwd(x, w, bias, y, B, HW, C, Co, (hipStream_t)stream);              // sd_head_wide.hip
+    SD_REQUIRE(C % 4 == 0 && C <= 512 && Co > 0 && Co <= HEAD_NARROW_MAX_CO, SD_ERR_INVALID, "sd_head_fwd: needs C %% 4 == 0, C <= 512, Co <= %d", HEAD_NARROW_MAX_CO);
     const int64_t M = (int64_t)B * HW;
     if (C == 128 && Co <= 16 && HW % 16 == 0 && M < (1ll << 31) && aligned16(x) && aligned16(w) && aligned16(y)) {
         const int ntiles = (int)(M / 16);
@@ -1932,14 +1932,27 @@ int sd_head_fwd(const float* x, const float* w, const float* bias, float* y, int
 static int head_wgrad_wave_rows(int64_t M) { return (int)std::min<int64_t>(1024, (cdiv(M, 16) + 3) / 4 * 4); }
 size_t sd_head_bwd_workspace_bytes(int B, int HW, int C, int Co) {
     const int64_t M = (int64_t)B * HW;
+    if (Co > HEAD_NARROW_MAX_CO) return head_wide_bwd_workspace_bytes(M, C, Co);
     return align_up((size_t)std::max<int64_t>(cdiv(M, HEAD_WG_PIX), head_wgrad_wave_rows(M)) * (Co * C + Co) * sizeof(float), 256);
 }
 
 int sd_head_bwd(const float* dy, const float* x, const float* w, float* dx, float* dw, float* dbias, int B, int HW, int C, int Co,
                 int accumulate, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
     SD_REQUIRE(dy && x && w && dx && dw && dbias && workspace && B > 0 && HW > 0, SD_ERR_INVALID, "sd_head_bwd: bad arguments");
-    SD_REQUIRE(C % 4 == 0 && C <= 256 && (256 % C == 0) && (64 % (256 / C) == 0) && ((64 / (256 / C)) % 8 == 0) && Co > 0 && Co <= HEAD_MAX_CO,
-               SD_ERR_INVALID, "sd_head_bwd: needs C in {64, 128, 256} and Co <= %d", HEAD_MAX_CO);
+    if (Co > HEAD_NARROW_MAX_CO) {                                             // GEMM kernels of sd_head_wide.hip
+        const int64_t P = (int64_t)B * HW;
+        if (int e = head_wide_check("sd_head_bwd", P, C, Co)) return e;
+        SD_REQUIRE(workspace_bytes >= sd_head_bwd_workspace_bytes(B, HW, C, Co), SD_ERR_WORKSPACE, "sd_head_bwd: workspace too small");
+        hipStream_t st = (hipStream_t)stream;
+        int rows = 0;
+        if (int e = head_wide_wgrad(dy, x, (float*)workspace, B, HW, C, Co, st, rows)) return e;
+        const int n = Co * C + Co;
+        hipLaunchKernelGGL(k_head_wgrad_fin, dim3(cdiv(n, 8)), dim3(256), 0, st, (const float*)workspace, rows, n, dw, dbias, Co * C, accumulate);
+        SD_LAUNCH_CHECK();
+        return head_wide_dgrad(dy, w, dx, B, HW, C, Co, st);
+    }
+    SD_REQUIRE(C % 4 == 0 && C <= 256 && (256 % C == 0) && (64 % (256 / C) == 0) && ((64 / (256 / C)) % 8 == 0) && Co > 0 && Co <= HEAD_NARROW_MAX_CO,
+               SD_ERR_INVALID, "sd_head_bwd: needs C in {64, 128, 256} and Co <= %d", HEAD_NARROW_MAX_CO);
     SD_REQUIRE(workspace_bytes >= sd_head_bwd_workspace_bytes(B, HW, C, Co), SD_ERR_WORKSPACE, "sd_head_bwd: workspace too small");
     const int64_t M = (int64_t)B * HW;
     hipStream_t st = (hipStream_t)stream;
