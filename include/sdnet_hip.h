@@ -199,6 +199,20 @@ int sd_preprocess_images_jitter(const uint8_t* images, int B, int Hin, int Win, 
                                 const float* jitter_factors, const float* mean3, const float* std3, float* out, void* workspace,
                                 size_t workspace_bytes, sd_stream_t stream);
 
+/* The same two pipelines over B images that are not packed together (a device-resident cache of decoded images): images is a DEVICE
+ * array of B device pointers, each to one (Hin, Win, 3) u8 image, any byte alignment, duplicates allowed.  Every other argument, the
+ * workspace sizes (sd_preprocess_workspace_bytes / sd_preprocess_jitter_workspace_bytes) and the output bytes are those of
+ * sd_preprocess_images / sd_preprocess_images_jitter on the same image bytes.  The horizontal pass stages source rows in LDS:
+ * Win <= 21834 (SD_ERR_INVALID beyond). */
+int sd_preprocess_images_list(const uint8_t* const* images, int B, int Hin, int Win, int Hout, int Wout,
+                              const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize,
+                              const uint8_t* flips, const float* mean3, const float* std3, float* out,
+                              void* workspace, size_t workspace_bytes, sd_stream_t stream);
+int sd_preprocess_images_list_jitter(const uint8_t* const* images, int B, int Hin, int Win, int Hout, int Wout, const int* h_bounds,
+                                     const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips,
+                                     const int* jitter_order, const float* jitter_factors, const float* mean3, const float* std3, float* out,
+                                     void* workspace, size_t workspace_bytes, sd_stream_t stream);
+
 /* ---- loss: src/sdnet/model/loss.py:17-64,91-117 ------------------------------------------- */
 
 #define SD_HM_MSE   0

@@ -43,6 +43,82 @@ __global__ __launch_bounds__(256) void k_resample_h(const uint8_t* __restrict__ 
     dst[0] = clip8(s0); dst[1] = clip8(s1); dst[2] = clip8(s2);
 }
 
+// horizontal pass from a device table of image pointers (sd_preprocess_images_list*): the bytes of k_resample_h, built for large
+// sources read straight from HBM (a decoded-image cache).  A block owns `rpb` (<= HL_ROWS) consecutive source rows of one image -- rows of
+// one image are contiguous -- and stages them into LDS with 16-byte global loads (the bytes before the first and after the last 16-byte
+// boundary one by one: any byte offset works and nothing outside the image is read), then evaluates the taps from LDS, every thread
+// owning output columns and reading each of its weights once for all the block's rows, four taps (12 bytes) at a time as four aligned
+// dwords + v_alignbyte (integer sums: the order of the taps does not change a bit); the 8-bit intermediate is written row by row,
+// consecutive threads on consecutive pixels.  Dynamic LDS: rpb * Win * 3 + 32 bytes (the offset mod 16 + the last window's overhang;
+// bytes there are multiplied by zero weights).
+constexpr int HL_ROWS = 4;
+constexpr int HL_LDS_BYTES = 65536;
+__global__ __launch_bounds__(256) void k_resample_h_list(const uint8_t* const* __restrict__ images, uint8_t* __restrict__ out, int Hin, int Win,
+                                                          int Wout, const int* __restrict__ bounds, const int* __restrict__ kk, int ksize, int rpb,
+                                                          int blocks_per_image) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const int b = blockIdx.x / blocks_per_image;
+    const int r0 = (blockIdx.x - b * blocks_per_image) * rpb;
+    const int nr = min(rpb, Hin - r0);
+    const int L = Win * 3;                                               // row bytes (rpb * L + 32 <= HL_LDS_BYTES: checked by the host)
+    const uint8_t* src = images[b] + (int64_t)r0 * L;
+    const int span = nr * L;
+    const int off = (int)(reinterpret_cast<uintptr_t>(src) & 15);      // LDS keeps the source's offset mod 16: 16-byte LDS stores stay aligned
+    const int head = min((16 - off) & 15, span);
+    const int nvec = (span - head) >> 4, tail = head + (nvec << 4);
+    const uint4* vsrc = reinterpret_cast<const uint4*>(src + head);
+    uint4* vdst = reinterpret_cast<uint4*>(lds + off + head);
+    for (int base = 0; base < nvec; base += 8 * 256) {                  // 8 loads in flight per thread before the LDS stores
+        uint4 v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int i = base + k * 256 + threadIdx.x;
+            v[k] = i < nvec ? vsrc[i] : make_uint4(0, 0, 0, 0);
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int i = base + k * 256 + threadIdx.x;
+            if (i < nvec) vdst[i] = v[k];
+        }
+    }
+    if ((int)threadIdx.x < head) lds[off + threadIdx.x] = src[threadIdx.x];
+    if ((int)threadIdx.x < span - tail) lds[off + tail + threadIdx.x] = src[tail + threadIdx.x];
+    __syncthreads();
+    for (int x = threadIdx.x; x < Wout; x += 256) {
+        const int xmin = bounds[2 * x], n = bounds[2 * x + 1];
+        const int* k = kk + (int64_t)x * ksize;
+        int s[HL_ROWS][3];
+#pragma unroll
+        for (int r = 0; r < HL_ROWS; ++r) s[r][0] = s[r][1] = s[r][2] = 1 << (PRECISION_BITS - 1);
+        for (int t0 = 0; t0 < n; t0 += 4) {                              // four taps = 12 source bytes per row: 4 dword LDS reads
+            int w[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) w[j] = t0 + j < n ? k[t0 + j] : 0;
+#pragma unroll
+            for (int r = 0; r < HL_ROWS; ++r) {
+                if (r < nr) {
+                    const int q = off + r * L + (xmin + t0) * 3;           // first byte of the four pixels (reads stop 13 bytes past the rows)
+                    const uint32_t* d = reinterpret_cast<const uint32_t*>(lds + (q & ~3));
+                    const int sh = q & 3;
+                    const uint32_t d0 = d[0], d1 = d[1], d2 = d[2], d3 = d[3];
+                    const uint32_t a0 = __builtin_amdgcn_alignbyte(d1, d0, sh), a1 = __builtin_amdgcn_alignbyte(d2, d1, sh),
+                                   a2 = __builtin_amdgcn_alignbyte(d3, d2, sh);   // bytes r0 g0 b0 r1 | g1 b1 r2 g2 | b2 r3 g3 b3
+                    s[r][0] += (int)(a0 & 255) * w[0] + (int)(a0 >> 24) * w[1] + (int)((a1 >> 16) & 255) * w[2] + (int)((a2 >> 8) & 255) * w[3];
+                    s[r][1] += (int)((a0 >> 8) & 255) * w[0] + (int)(a1 & 255) * w[1] + (int)(a1 >> 24) * w[2] + (int)((a2 >> 16) & 255) * w[3];
+                    s[r][2] += (int)((a0 >> 16) & 255) * w[0] + (int)((a1 >> 8) & 255) * w[1] + (int)(a2 & 255) * w[2] + (int)(a2 >> 24) * w[3];
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < HL_ROWS; ++r) {
+            if (r < nr) {
+                uint8_t* dst = out + (((int64_t)b * Hin + r0 + r) * Wout + x) * 3;
+                dst[0] = clip8(s[r][0]); dst[1] = clip8(s[r][1]); dst[2] = clip8(s[r][2]);
+            }
+        }
+    }
+}
+
 // vertical pass + flips + to_tensor + Normalize: tmp (B, Hin, Wout, 3) u8 -> out (B, 3, Hout, Wout) fp32 NCHW
 __global__ __launch_bounds__(256) void k_resample_v_norm(const uint8_t* __restrict__ in, float* __restrict__ out, int Hin, int Hout, int Wout,
                                                           const int* __restrict__ bounds, const int* __restrict__ kk, int ksize,
@@ -227,6 +303,31 @@ static int preprocess_check(const char* what, const uint8_t* images, int B, int 
     return 0;
 }
 
+// the launches after the horizontal pass (tmp = its 8-bit intermediate at the start of the workspace), shared by the packed and the list forms
+static int preprocess_tail(int B, int Hin, int Hout, int Wout, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips,
+                           const float* mean3, const float* std3, float* out, uint8_t* tmp, hipStream_t st) {
+    hipLaunchKernelGGL(k_resample_v_norm, dim3(cdiv((int64_t)B * Hout * Wout, 256)), dim3(256), 0, st, tmp, out, Hin, Hout, Wout, v_bounds, v_kk,
+                       v_ksize, flips, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], B);
+    SD_LAUNCH_CHECK();
+    return 0;
+}
+
+static int preprocess_jitter_tail(int B, int Hin, int Win, int Hout, int Wout, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips,
+                                  const int* jitter_order, const float* jitter_factors, const float* mean3, const float* std3, float* out,
+                                  uint8_t* tmp, hipStream_t st) {
+    uint8_t* img = tmp + sd_preprocess_workspace_bytes(B, Hin, Win, Wout);
+    unsigned long long* lsum = reinterpret_cast<unsigned long long*>(img + align_up((size_t)B * Hout * Wout * 3, 256));
+    const int64_t npix = (int64_t)Hout * Wout;
+    hipLaunchKernelGGL(k_resample_v_u8, dim3(cdiv((int64_t)B * npix, 256)), dim3(256), 0, st, tmp, img, Hin, Hout, Wout, v_bounds, v_kk, v_ksize, B);
+    SD_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_jitter_lsum, dim3(std::min<int64_t>(cdiv(npix, 256), 64), B), dim3(256), 0, st, img, npix, jitter_order, jitter_factors, lsum);
+    SD_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_jitter_norm, dim3(cdiv((int64_t)B * npix, 256)), dim3(256), 0, st, img, out, Hout, Wout, jitter_order, jitter_factors, lsum,
+                       flips, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], B);
+    SD_LAUNCH_CHECK();
+    return 0;
+}
+
 int sd_preprocess_images(const uint8_t* images, int B, int Hin, int Win, int Hout, int Wout, const int* h_bounds, const int* h_kk,
                          int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips, const float* mean3,
                          const float* std3, float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
@@ -239,10 +340,7 @@ int sd_preprocess_images(const uint8_t* images, int B, int Hin, int Win, int Hou
     const int64_t rows = (int64_t)B * Hin;
     hipLaunchKernelGGL(k_resample_h, dim3(cdiv(rows * Wout, 256)), dim3(256), 0, st, images, tmp, Hin, Win, Wout, h_bounds, h_kk, h_ksize, rows);
     SD_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_resample_v_norm, dim3(cdiv((int64_t)B * Hout * Wout, 256)), dim3(256), 0, st, tmp, out, Hin, Hout, Wout, v_bounds, v_kk,
-                       v_ksize, flips, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], B);
-    SD_LAUNCH_CHECK();
-    return 0;
+    return preprocess_tail(B, Hin, Hout, Wout, v_bounds, v_kk, v_ksize, flips, mean3, std3, out, tmp, st);
 }
 
 int sd_preprocess_images_jitter(const uint8_t* images, int B, int Hin, int Win, int Hout, int Wout, const int* h_bounds, const int* h_kk,
@@ -258,19 +356,67 @@ int sd_preprocess_images_jitter(const uint8_t* images, int B, int Hin, int Win, 
     hipStream_t st = (hipStream_t)stream;
     uint8_t* tmp = reinterpret_cast<uint8_t*>(workspace);
     uint8_t* img = tmp + sd_preprocess_workspace_bytes(B, Hin, Win, Wout);
-    unsigned long long* lsum = reinterpret_cast<unsigned long long*>(img + align_up((size_t)B * Hout * Wout * 3, 256));
-    SD_HIP(hipMemsetAsync(lsum, 0, (size_t)B * 8, st));
-    const int64_t rows = (int64_t)B * Hin, npix = (int64_t)Hout * Wout;
+    SD_HIP(hipMemsetAsync(img + align_up((size_t)B * Hout * Wout * 3, 256), 0, (size_t)B * 8, st));        // lsum
+    const int64_t rows = (int64_t)B * Hin;
     hipLaunchKernelGGL(k_resample_h, dim3(cdiv(rows * Wout, 256)), dim3(256), 0, st, images, tmp, Hin, Win, Wout, h_bounds, h_kk, h_ksize, rows);
     SD_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_resample_v_u8, dim3(cdiv((int64_t)B * npix, 256)), dim3(256), 0, st, tmp, img, Hin, Hout, Wout, v_bounds, v_kk, v_ksize, B);
-    SD_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_jitter_lsum, dim3(std::min<int64_t>(cdiv(npix, 256), 64), B), dim3(256), 0, st, img, npix, jitter_order, jitter_factors, lsum);
-    SD_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_jitter_norm, dim3(cdiv((int64_t)B * npix, 256)), dim3(256), 0, st, img, out, Hout, Wout, jitter_order, jitter_factors, lsum,
-                       flips, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], B);
+    return preprocess_jitter_tail(B, Hin, Win, Hout, Wout, v_bounds, v_kk, v_ksize, flips, jitter_order, jitter_factors, mean3, std3, out, tmp, st);
+}
+
+// ---- the same from a device table of B image pointers (k_resample_h_list for the horizontal pass) ----
+static int preprocess_list_check(const char* what, const uint8_t* const* images, int B, int Hin, int Win, int Hout, int Wout, const int* h_bounds,
+                                 const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const float* mean3,
+                                 const float* std3, float* out, void* workspace, int* rpb, int* blocks_per_image) {
+    if (int e = preprocess_check(what, reinterpret_cast<const uint8_t*>(images), B, Hin, Win, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk,
+                                 v_ksize, mean3, std3, out, workspace)) return e;
+    SD_REQUIRE((int64_t)Win * 3 + 32 <= HL_LDS_BYTES, SD_ERR_INVALID, "%s: source rows of %d pixels exceed the LDS staging buffer (at most %d)",
+               what, Win, (HL_LDS_BYTES - 32) / 3);
+    *rpb = (int)std::min<int64_t>(HL_ROWS, (HL_LDS_BYTES - 32) / ((int64_t)Win * 3));
+    *blocks_per_image = cdiv(Hin, *rpb);
+    SD_REQUIRE((int64_t)B * *blocks_per_image < (1ll << 31), SD_ERR_INVALID, "%s: batch too large", what);
+    return 0;
+}
+
+static int resample_h_list(const uint8_t* const* images, uint8_t* tmp, int B, int Hin, int Win, int Wout, const int* h_bounds, const int* h_kk,
+                           int h_ksize, int rpb, int blocks_per_image, hipStream_t st) {
+    const size_t lds = (size_t)rpb * Win * 3 + 32;
+    hipLaunchKernelGGL(k_resample_h_list, dim3((unsigned)((int64_t)B * blocks_per_image)), dim3(256), lds, st, images, tmp, Hin, Win, Wout, h_bounds,
+                       h_kk, h_ksize, rpb, blocks_per_image);
     SD_LAUNCH_CHECK();
     return 0;
+}
+
+int sd_preprocess_images_list(const uint8_t* const* images, int B, int Hin, int Win, int Hout, int Wout, const int* h_bounds, const int* h_kk,
+                              int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips, const float* mean3,
+                              const float* std3, float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
+    int rpb = 0, bpi = 0;
+    if (int e = preprocess_list_check("sd_preprocess_images_list", images, B, Hin, Win, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
+                                      mean3, std3, out, workspace, &rpb, &bpi)) return e;
+    SD_REQUIRE(workspace_bytes >= sd_preprocess_workspace_bytes(B, Hin, Win, Wout), SD_ERR_WORKSPACE, "sd_preprocess_images_list: workspace %zu < %zu",
+               workspace_bytes, sd_preprocess_workspace_bytes(B, Hin, Win, Wout));
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t* tmp = reinterpret_cast<uint8_t*>(workspace);
+    if (int e = resample_h_list(images, tmp, B, Hin, Win, Wout, h_bounds, h_kk, h_ksize, rpb, bpi, st)) return e;
+    return preprocess_tail(B, Hin, Hout, Wout, v_bounds, v_kk, v_ksize, flips, mean3, std3, out, tmp, st);
+}
+
+int sd_preprocess_images_list_jitter(const uint8_t* const* images, int B, int Hin, int Win, int Hout, int Wout, const int* h_bounds, const int* h_kk,
+                                     int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips, const int* jitter_order,
+                                     const float* jitter_factors, const float* mean3, const float* std3, float* out, void* workspace,
+                                     size_t workspace_bytes, sd_stream_t stream) {
+    int rpb = 0, bpi = 0;
+    if (int e = preprocess_list_check("sd_preprocess_images_list_jitter", images, B, Hin, Win, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk,
+                                      v_ksize, mean3, std3, out, workspace, &rpb, &bpi)) return e;
+    SD_REQUIRE(jitter_order && jitter_factors, SD_ERR_INVALID, "sd_preprocess_images_list_jitter: null jitter parameters");
+    SD_REQUIRE(B <= 65535, SD_ERR_INVALID, "sd_preprocess_images_list_jitter: batch %d > 65535", B);
+    SD_REQUIRE(workspace_bytes >= sd_preprocess_jitter_workspace_bytes(B, Hin, Win, Hout, Wout), SD_ERR_WORKSPACE,
+               "sd_preprocess_images_list_jitter: workspace %zu < %zu", workspace_bytes, sd_preprocess_jitter_workspace_bytes(B, Hin, Win, Hout, Wout));
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t* tmp = reinterpret_cast<uint8_t*>(workspace);
+    uint8_t* img = tmp + sd_preprocess_workspace_bytes(B, Hin, Win, Wout);
+    SD_HIP(hipMemsetAsync(img + align_up((size_t)B * Hout * Wout * 3, 256), 0, (size_t)B * 8, st));        // lsum
+    if (int e = resample_h_list(images, tmp, B, Hin, Win, Wout, h_bounds, h_kk, h_ksize, rpb, bpi, st)) return e;
+    return preprocess_jitter_tail(B, Hin, Win, Hout, Wout, v_bounds, v_kk, v_ksize, flips, jitter_order, jitter_factors, mean3, std3, out, tmp, st);
 }
 
 }  // extern "C"

@@ -123,6 +123,44 @@ def preprocess_images(images: torch.Tensor, out_size, flips=None, mean=_MEAN, st
     return out
 
 
+def preprocess_image_list(pointers: torch.Tensor, hin: int, win: int, out_size, flips=None, mean=_MEAN, std=_STD, jitter=None) -> torch.Tensor:
+    """`preprocess_images` over B images that are not packed together: pointers is a (B,) int64 DEVICE tensor of the device addresses of
+    B (hin, win, 3) uint8 images (any byte alignment; the caller keeps them alive until the work on the current stream is done), e.g. entries
+    of data/image_cache.py's DeviceImageCache.  Same arguments otherwise, same output bytes as `preprocess_images` on the stacked images."""
+    L.require_cuda(pointers)
+    if pointers.dtype != torch.int64 or pointers.dim() != 1 or pointers.numel() == 0:
+        raise L.SdError(f"preprocess_image_list expects a non-empty (B,) int64 pointer table, got {tuple(pointers.shape)} {pointers.dtype}")
+    pointers = pointers.contiguous()
+    dev = pointers.device
+    B, Hin, Win = pointers.numel(), int(hin), int(win)
+    Wout, Hout = int(out_size[0]), int(out_size[1])
+    hb, hk, hks = _tables.get(Win, Wout, dev)
+    vb, vk, vks = _tables.get(Hin, Hout, dev)
+    out = torch.empty((B, 3, Hout, Wout), dtype=torch.float32, device=dev)
+    lib = L.lib()
+    fl = None
+    if flips is not None:
+        fl = torch.as_tensor(flips, dtype=torch.uint8).to(dev, non_blocking=True)
+        if fl.numel() != B:
+            raise L.SdError("flips must have one entry per image")
+    m3, s3 = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
+    if jitter is not None:
+        order = torch.as_tensor(jitter[0], dtype=torch.int32).to(dev, non_blocking=True)
+        factors = torch.as_tensor(jitter[1], dtype=torch.float32).reshape(-1, 3).contiguous().to(dev, non_blocking=True)
+        if order.numel() != B or factors.shape[0] != B:
+            raise L.SdError("jitter parameters must have one row per image")
+        ws = L.workspace(lib.sd_preprocess_jitter_workspace_bytes(B, Hin, Win, Hout, Wout), dev)
+        L.check(lib.sd_preprocess_images_list_jitter(pointers.data_ptr(), B, Hin, Win, Hout, Wout, hb.data_ptr(), hk.data_ptr(), hks, vb.data_ptr(),
+                                                     vk.data_ptr(), vks, fl.data_ptr() if fl is not None else 0, order.data_ptr(), factors.data_ptr(),
+                                                     m3, s3, out.data_ptr(), ws.data_ptr(), ws.numel(), L.stream()), "sd_preprocess_images_list_jitter")
+        return out
+    ws = L.workspace(lib.sd_preprocess_workspace_bytes(B, Hin, Win, Wout), dev)
+    L.check(lib.sd_preprocess_images_list(pointers.data_ptr(), B, Hin, Win, Hout, Wout, hb.data_ptr(), hk.data_ptr(), hks, vb.data_ptr(),
+                                          vk.data_ptr(), vks, fl.data_ptr() if fl is not None else 0, m3, s3, out.data_ptr(), ws.data_ptr(),
+                                          ws.numel(), L.stream()), "sd_preprocess_images_list")
+    return out
+
+
 def jitter_words(order, brightness, contrast, saturation, hue):
     """One image's ColorJitter parameters in the form `sd_preprocess_images_jitter` takes: the op order (a permutation of
     0 brightness, 1 contrast, 2 saturation, 3 hue) packed two bits each, the hue shift byte `uint8(hue * 255)` torchvision's adjust_hue
@@ -164,7 +202,10 @@ class ValidationAugmentation:
         for (hin, win), (idx, stack) in groups.items():
             f = None if flips is None else [flips[i] for i in idx]
             j = None if jitter is None else ([jitter[0][i] for i in idx], [jitter[1][i] for i in idx])
-            res = preprocess_images(stack.to(dev, non_blocking=True), (W, H), f, jitter=j)
+            if hasattr(stack, "pointers"):                           # data/image_cache.py ImageList: cached / uploaded images by address
+                res = preprocess_image_list(stack.pointers, hin, win, (W, H), f, jitter=j)
+            else:
+                res = preprocess_images(stack.to(dev, non_blocking=True), (W, H), f, jitter=j)
             if len(groups) == 1:
                 out = res
             else:

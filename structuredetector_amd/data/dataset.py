@@ -39,6 +39,23 @@ class CropDataset:
     def __len__(self):
         return len(self.files)
 
+    # ---- the pieces of __getitem__ a cache of decoded images (data/image_cache.py) needs without decoding ----
+    def annotation_key(self, index):
+        """(path, st_mtime_ns, st_size) of sample `index`'s JSON file: what its parsed annotation is cached under."""
+        import os
+        st = os.stat(self.files[index])
+        return str(self.files[index]), st.st_mtime_ns, st.st_size
+
+    def image_file(self, index, ann):
+        """The image file sample `index`'s annotation names, found the way __getitem__ finds it."""
+        return ann.image_path if ann.image_path.is_absolute() else self.files[index].parent / ann.image_path.name
+
+    def read_annotation(self, index):
+        """Sample `index`'s annotation parsed from its JSON (ORIGINAL pixels, img_size as recorded), and its image file: no decode."""
+        from ..utils.types import ImageAnnotation
+        ann = ImageAnnotation.from_json(self.files[index], self.args.anchor_name)
+        return ann, self.image_file(index, ann)
+
     def __getitem__(self, index):
         import numpy as np
         from PIL import Image

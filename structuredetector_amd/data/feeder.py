@@ -17,7 +17,7 @@ from __future__ import annotations
 import os
 import queue
 import threading
-from concurrent.futures import ThreadPoolExecutor
+from concurrent.futures import Future, ThreadPoolExecutor
 
 import torch
 
@@ -79,6 +79,7 @@ def prefetch_items(dataset, workers=None, depth=None):
 
 class GroupedBatch:
     """One batch as the GPU pipeline wants it: `groups` = {(height, width): (sample positions, (n, height, width, 3) uint8 DEVICE tensor)},
+    or, when the feeder has a DeviceImageCache, {(height, width): (sample positions, data/image_cache.py ImageList of n device addresses)};
     `annotations` in sample order (ORIGINAL image pixels), `ready` = event after which the device tensors are complete."""
 
     def __init__(self, groups, annotations, ready, keep):
@@ -89,9 +90,11 @@ class GroupedBatch:
 
 
 class BatchFeeder:
-    def __init__(self, dataset, index_batches, device, workers=None, depth=3):
+    def __init__(self, dataset, index_batches, device, workers=None, depth=3, cache=None):
         """dataset: CropDataset(raw=True) -- items ((H, W, 3) uint8 CPU tensor, annotation); index_batches: the epoch's batches of sample
-        indices (trainer.shard_indices); workers: decode threads (default: default_decode_workers()); depth: batches in flight ahead of the consumer."""
+        indices (trainer.shard_indices); workers: decode threads (default: default_decode_workers()); depth: batches in flight ahead of the consumer;
+        cache: a data/image_cache.py DeviceImageCache or None -- with one, a cached sample is neither decoded nor staged (its group carries
+        its device address), a miss is decoded and uploaded as without one and then cached if it fits."""
         self.dataset, self.batches, self.device = dataset, [list(int(j) for j in b) for b in index_batches], torch.device(device)
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
@@ -99,6 +102,7 @@ class BatchFeeder:
         self.depth = max(1, int(depth))
         self._pinned = {}             # (n, h, w) -> list of [buffer, event of the upload that last read it]
         self._stop = threading.Event()
+        self.cache = cache
 
     # ---- staging buffers: `depth + 2` pinned buffers per shape in rotation; a buffer is rewritten only after the upload that read it is done
     def _staging(self, n, h, w):
@@ -123,30 +127,16 @@ class BatchFeeder:
                 def submit_more():
                     nonlocal nxt
                     while nxt < len(self.batches) and len(pending) <= self.depth:
-                        pending.append([pool.submit(self.dataset.__getitem__, j) for j in self.batches[nxt]])
+                        if self.cache is None:
+                            pending.append([pool.submit(self.dataset.__getitem__, j) for j in self.batches[nxt]])
+                        else:                                  # a hit: (entry, annotation) now; a miss: decoded on the pool
+                            pending.append([self.cache.lookup(self.dataset, j) or pool.submit(self._read_keyed, j) for j in self.batches[nxt]])
                         nxt += 1
                 submit_more()
                 while pending and not self._stop.is_set():
-                    items = [f.result() for f in pending.pop(0)]
+                    got = [f.result() if isinstance(f, Future) else f for f in pending.pop(0)]
                     submit_more()
-                    by_size = {}
-                    for pos, (im, _) in enumerate(items):
-                        by_size.setdefault((int(im.shape[0]), int(im.shape[1])), []).append(pos)
-                    groups, keep = {}, []
-                    with torch.cuda.stream(side):
-                        for (h, w), idx in by_size.items():
-                            slot = self._staging(len(idx), h, w)
-                            for k, pos in enumerate(idx):
-                                slot[0][k].copy_(items[pos][0])                  # pageable -> pinned (releases the GIL)
-                            dev = slot[0].to(self.device, non_blocking=True)     # asynchronous: pinned source, side stream
-                            ev = torch.cuda.Event()
-                            ev.record(side)
-                            slot[1] = ev
-                            groups[(h, w)] = (idx, dev)
-                            keep.append(slot)
-                        ready = torch.cuda.Event()
-                        ready.record(side)
-                    batch = GroupedBatch(groups, [a for _, a in items], ready, keep)
+                    batch = self._assemble(got, side) if self.cache is None else self._assemble_cached(got, side)
                     while not self._stop.is_set():
                         try:
                             out.put(batch, timeout=0.2)
@@ -155,10 +145,89 @@ class BatchFeeder:
                             continue
                 for fs in pending:                              # consumer stopped early
                     for f in fs:
-                        f.cancel()
+                        if isinstance(f, Future):
+                            f.cancel()
             out.put(None)
         except BaseException as err:                            # hand the failure to the consumer instead of dying silently
             out.put(err)
+
+    def _assemble(self, items, side):
+        """items: per sample ((h, w, 3) uint8 CPU tensor, annotation).  Grouped by size, staged in pinned memory and uploaded on the side stream."""
+        by_size = {}
+        for pos, (im, _) in enumerate(items):
+            by_size.setdefault((int(im.shape[0]), int(im.shape[1])), []).append(pos)
+        groups, keep = {}, []
+        with torch.cuda.stream(side):
+            for (h, w), idx in by_size.items():
+                slot = self._staging(len(idx), h, w)
+                for k, pos in enumerate(idx):
+                    slot[0][k].copy_(items[pos][0])                  # pageable -> pinned (releases the GIL)
+                dev = slot[0].to(self.device, non_blocking=True)     # asynchronous: pinned source, side stream
+                ev = torch.cuda.Event()
+                ev.record(side)
+                slot[1] = ev
+                groups[(h, w)] = (idx, dev)
+                keep.append(slot)
+            ready = torch.cuda.Event()
+            ready.record(side)
+        return GroupedBatch(groups, [a for _, a in items], ready, keep)
+
+    # ---- with a DeviceImageCache ----
+    def _read_keyed(self, j):
+        """A miss: the cache keys of sample j (taken before the decode: a file rewritten meanwhile misses again), then the decode."""
+        try:
+            keys = self.cache.keys(self.dataset, j)
+        except OSError:
+            keys = None
+        return keys, self.dataset[j]
+
+    def _assemble_cached(self, got, side):
+        """got: per sample, a hit ((address, h, w), annotation) or a miss (keys, ((h, w, 3) uint8 CPU tensor, annotation)).  Misses are staged,
+        uploaded and inserted into the cache on the side stream; every size group becomes an ImageList of device addresses."""
+        from .image_cache import ImageList
+        by_size, anns, misses = {}, [], {}
+        for pos, (a, b) in enumerate(got):
+            if isinstance(b, tuple):                            # miss: (keys, (image, annotation))
+                im, ann = b
+                misses[pos] = (a, im)
+                hw = (int(im.shape[0]), int(im.shape[1]))
+            else:                                               # hit: ((address, h, w), annotation)
+                ann, hw = b, (a[1], a[2])
+            by_size.setdefault(hw, []).append(pos)
+            anns.append(ann)
+        groups, keep, inserted = {}, [], False
+        with torch.cuda.stream(side):
+            if self.cache.fence is not None:
+                side.wait_event(self.cache.fence)               # entries another stream wrote
+            for (h, w), idx in by_size.items():
+                miss = [pos for pos in idx if pos in misses]
+                dev = None
+                if miss:
+                    slot = self._staging(len(miss), h, w)
+                    for k, pos in enumerate(miss):
+                        slot[0][k].copy_(misses[pos][1])                     # pageable -> pinned (releases the GIL)
+                    dev = slot[0].to(self.device, non_blocking=True)         # asynchronous: pinned source, side stream
+                    ev = torch.cuda.Event()
+                    ev.record(side)
+                    slot[1] = ev
+                    keep.append(slot)
+                    for k, pos in enumerate(miss):
+                        if misses[pos][0] is not None:
+                            inserted |= self.cache.insert(misses[pos][0], anns[pos], dev[k])
+                addrs, k = [], 0
+                for pos in idx:
+                    if pos in misses:
+                        addrs.append(dev.data_ptr() + k * h * w * 3)
+                        k += 1
+                    else:
+                        addrs.append(got[pos][0][0])
+                table = torch.tensor(addrs, dtype=torch.int64).pin_memory().to(self.device, non_blocking=True)
+                groups[(h, w)] = (idx, ImageList(table, h, w, [dev] if dev is not None else []))
+            if inserted:
+                self.cache.mark_written(side)
+            ready = torch.cuda.Event()
+            ready.record(side)
+        return GroupedBatch(groups, anns, ready, keep)
 
     def __iter__(self):
         out = queue.Queue(maxsize=self.depth)
@@ -175,7 +244,7 @@ class BatchFeeder:
                 cur = torch.cuda.current_stream(self.device)
                 cur.wait_event(item.ready)                      # device-side wait: the host does not block
                 for _, dev in item.groups.values():
-                    dev.record_stream(cur)                      # allocated on the side stream, consumed on this one
+                    dev.record_stream(cur)                      # allocated on the side stream, consumed on this one (ImageList: its table + uploads)
                 yield item
         finally:
             self._stop.set()

@@ -22,11 +22,12 @@ def index_batches(n, batch):
     return [list(range(lo, min(lo + batch, n))) for lo in range(0, n, batch)]
 
 
-def batched_outputs(net, decoder, dataset, args, batch=None, workers=None, with_raw_parts=True, keep_output=False, depth=2):
+def batched_outputs(net, decoder, dataset, args, batch=None, workers=None, with_raw_parts=True, keep_output=False, depth=2, cache=None):
     """dataset: `CropDataset(args, dir, raw=True)` or `PredictionDataset(dir, args, raw=True)` -- items ((H, W, 3) uint8 tensor,
     ImageAnnotation in ORIGINAL pixels with img_size).  Yields, per image and in dataset order,
     (prediction ImageAnnotation in network-input pixels, ground-truth annotation in network-input pixels (resized + clipped like
-    Resize + Encode do, transforms.py:47-60,154), raw_parts or None, this image's output dict of (1, C, h, w) views when keep_output else None)."""
+    Resize + Encode do, transforms.py:47-60,154), raw_parts or None, this image's output dict of (1, C, h, w) views when keep_output else None).
+    cache: a data/image_cache.py DeviceImageCache the feed reads cached images from (CropDataset only), or None."""
     from ..data.augment import ValidationAugmentation
     from ..data.feeder import BatchFeeder, default_decode_workers
     batch = int(batch or getattr(args, "eval_batch", 16) or 16)
@@ -43,7 +44,7 @@ def batched_outputs(net, decoder, dataset, args, batch=None, workers=None, with_
     threads = torch.get_num_threads()
     torch.set_num_threads(1)                       # the loop's host work is tiny tensor ops; torch's pool would spin against the decode threads
     try:
-        for group in BatchFeeder(dataset, index_batches(len(dataset), batch), args.device, workers=workers, depth=depth):
+        for group in BatchFeeder(dataset, index_batches(len(dataset), batch), args.device, workers=workers, depth=depth, cache=cache):
             with torch.no_grad():
                 images, anns = prepare(group, group.annotations)
                 out = net(images)

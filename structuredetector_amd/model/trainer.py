@@ -365,6 +365,9 @@ class Trainer:
         from .loss import Loss
         self.decoder, self.evaluator, self.loss = Decoder(args), Evaluator(args), Loss(args)
         self.valid_set = None if args.synthetic or not args.valid_dir else CropDataset(args, args.valid_dir, raw=True)
+        # --cache_images GB: decoded images kept in device memory across epochs, one cache for both sets, filled before epoch 1
+        from ..data.image_cache import from_args
+        self.cache = None if args.synthetic else from_args(args)
         self.start_epoch = 0
         self.global_step = 0                      # trainer.py:35,129: images seen, the x axis of every scalar
         self._writer = None
@@ -393,7 +396,7 @@ class Trainer:
             threads = torch.get_num_threads()
             torch.set_num_threads(1)
             try:
-                for batch in BatchFeeder(self.dataset, shards, a.device, workers=workers, depth=getattr(a, "prefetch", 3)):
+                for batch in BatchFeeder(self.dataset, shards, a.device, workers=workers, depth=getattr(a, "prefetch", 3), cache=self.cache):
                     images, anns = self.augment(batch, batch.annotations)
                     yield images, self.encode.batch(self.augment.size, anns, a.device)
             finally:
@@ -405,7 +408,7 @@ class Trainer:
         if self.valid_set is not None:
             # decode threads -> GPU Resize + Normalize -> forward + decoder at --eval_batch images per launch (model/predictor.py)
             from .predictor import batched_outputs
-            yield from batched_outputs(self.net, self.decoder, self.valid_set, a, keep_output=True)
+            yield from batched_outputs(self.net, self.decoder, self.valid_set, a, keep_output=True, cache=self.cache)
             return
         from ..data.synthetic import synthetic_samples
         for image, annotation in synthetic_samples(a, min(max(a.synthetic, 1), 16), seed=20261003):
@@ -498,8 +501,24 @@ class Trainer:
                 self._writer.close()
                 self._writer = None
 
+    def prefill_cache(self):
+        """Decode every training and validation image once into the device cache (each rank the whole set: its shard changes every epoch)."""
+        from ..data.feeder import default_decode_workers
+        from ..data.image_cache import GB
+        a = self.args
+        workers = getattr(a, "decode_workers", 0) or default_decode_workers(self.step.world)
+        for ds in (self.dataset, self.valid_set):
+            if ds is not None:
+                self.cache.prefill(ds, workers)
+        st = self.cache.stats()
+        if self.rank == 0:
+            print(f"image cache: {st['images']} images, {st['bytes_used'] / GB:.2f} GB in {st['prefill_seconds']:.1f} s, "
+                  f"{st['refused']} left on the host path (budget {a.cache_images:g} GB)", flush=True)
+
     def _train(self):
         steps = 0
+        if self.cache is not None:
+            self.prefill_cache()
         for epoch in range(self.start_epoch, self.args.epochs):
             self.epoch = epoch
             per_step = []

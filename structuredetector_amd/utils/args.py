@@ -56,6 +56,8 @@ _FLAGS = [
                                    "the trunk: what the reference downloads for pretrained=True (default: $SDNET_BACKBONE_WEIGHTS, then the torch hub cache).")),
     (("--log_dir",), dict(type=str, default=None, help="Directory for the training scalars (default: the run's save directory).")),
     (("--eval_batch",), dict(type=int, default=16, help="Images per forward + decode launch in evaluate / validation / detect.")),
+    (("--cache_images",), dict(type=float, default=0.0, help="GB of device memory for decoded training / validation images, kept across "
+                               "epochs (decoded once before epoch 1; images beyond the budget are decoded every epoch; 0 = off).")),
 ]
 
 _POSITIVE = ["in_channels", "fpn_depth", "batch_size", "epochs", "learning_rate", "down_ratio", "max_objects", "max_parts"]
@@ -83,6 +85,7 @@ def finalize(args):
     for k in _UNIT:
         assert 0 <= getattr(args, k) <= 1, f"'{k}' should be in [0.0, 1.0]"
     assert 0 < args.sigma_gauss <= 1, "'sigma_gauss' should be in ]0.0, 1.0]"
+    assert getattr(args, "cache_images", 0) >= 0, "'cache_images' should be greater than or equal to 0"
 
     args.lr_step = int(args.epochs / args.lr_step) if args.lr_step != 0 else args.epochs
     for k in ("train_dir", "valid_dir", "pretrained_model"):
