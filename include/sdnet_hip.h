@@ -245,6 +245,12 @@ typedef struct sd_loss_desc {
 size_t sd_loss_workspace_bytes(int B, int M, int N, int h, int w);
 int sd_loss_fwd(const sd_loss_desc* d, float* out8, void* workspace, size_t workspace_bytes, sd_stream_t stream);
 
+/* Loss.forward of every image of the batch on its own (validation: per-image losses, then the mean over
+ * images, trainer.py:160-168).  out: (B,8) device floats, row b = sd_loss_fwd's out8 of image b alone and
+ * bit-identical to a separate B = 1 sd_loss_fwd call.  Same descriptor and workspace
+ * (sd_loss_workspace_bytes) as sd_loss_fwd; two launches for the whole batch. */
+int sd_loss_fwd_per_image(const sd_loss_desc* d, float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream);
+
 /* d total / d head for all M+N+4 channels.  grad_out: device scalar (upstream gradient).
  * dhead: (B,M+N+4,h,w) contiguous, fully overwritten. */
 int sd_loss_bwd(const sd_loss_desc* d, const float* out8, const float* grad_out, float* dhead, sd_stream_t stream);

@@ -84,6 +84,7 @@ _SIGNATURES = {
     "sd_render_targets": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_float, c_vp, c_vp]),
     "sd_loss_workspace_bytes": (c_size, [c_int] * 5),
     "sd_loss_fwd": (c_int, [C.POINTER(LossDesc), c_vp, c_vp, c_size, c_vp]),
+    "sd_loss_fwd_per_image": (c_int, [C.POINTER(LossDesc), c_vp, c_vp, c_size, c_vp]),
     "sd_loss_bwd": (c_int, [C.POINTER(LossDesc), c_vp, c_vp, c_vp, c_vp]),
     "sd_conv2d_fwd_workspace_bytes": (c_size, [C.POINTER(ConvDesc)]),
     "sd_conv2d_fwd": (c_int, [c_vp, c_vp, c_vp, C.POINTER(ConvDesc), c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_size, c_vp]),

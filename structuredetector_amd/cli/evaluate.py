@@ -2,17 +2,36 @@
 validation directory (or `--synthetic N` seeded scenes); prints the reference's five metric tables and optionally writes the
 keypoint CSV (`--save_csv_eval`).  The reference decodes one image per call (:34-45); here the directory is read by decode threads,
 resized + normalised on the GPU and pushed through forward + decoder `--eval_batch` images at a time (model/predictor.py), while
-`Evaluator.accumulate` still sees one image after the other in the reference's order -- counters and accuracy lists are identical."""
+`Evaluator.accumulate` still sees one image after the other in the reference's order -- counters and accuracy lists are identical.
+
+Multi-GPU: `python -m torch.distributed.run --nproc-per-node N -m structuredetector_amd.cli.evaluate ...` (or an already
+initialised process group).  Each rank evaluates its contiguous shard of the images; the per-rank Evaluators are merged in rank
+order (utils/distributed.py), which is dataset order, so every rank returns the one-process result and rank 0 prints it and
+writes the CSV."""
+from itertools import islice
+
 import torch
+import torch.distributed as dist
 
 from ..data import CropDataset, Decoder
 from ..model import Evaluator, Network
 from ..utils import Arguments
+from ..utils.distributed import gather_evaluator, init_from_env, shard_range, world_info
 
 
 def main(argv=None):
+    created = init_from_env()
+    try:
+        return _evaluate(argv)
+    finally:
+        if created:
+            dist.destroy_process_group()
+
+
+def _evaluate(argv):
     args = Arguments().parse(argv)
     assert args.synthetic or args.valid_dir, "Path to a directory with validation samples must be specified."
+    rank, world = world_info()
     evaluator = Evaluator(args)
     decoder = Decoder(args)
     # evaluate.py:30-31 builds Network(args) (ImageNet trunk) and then overwrites every tensor from the checkpoint: the ImageNet file is
@@ -23,7 +42,8 @@ def main(argv=None):
     net = net.eval().to(args.device)
     if args.synthetic:
         from ..data.synthetic import synthetic_samples
-        for image, annotation in synthetic_samples(args, args.synthetic):
+        lo, hi = shard_range(args.synthetic, rank, world)
+        for image, annotation in islice(synthetic_samples(args, args.synthetic), lo, hi):
             with torch.no_grad():
                 output = net(image[None].to(args.device))
             data = decoder(output, return_metadata=True, metadata_fields=("annotation", "raw_parts"))
@@ -31,12 +51,15 @@ def main(argv=None):
     else:
         from ..model.predictor import batched_outputs
         dataset = CropDataset(args, args.valid_dir, raw=True)               # decode only; Resize + Normalize run on the GPU per batch
-        for prediction, annotation, raw_parts, _ in batched_outputs(net, decoder, dataset, args):
+        shard = shard_range(len(dataset), rank, world)
+        for prediction, annotation, raw_parts, _ in batched_outputs(net, decoder, dataset, args, index_range=shard):
             # the annotation was resized to the network input and clipped (Resize + Encode's clip); the Evaluator maps both sides back to img_size
             evaluator.accumulate(prediction, annotation, raw_parts, True, True)
-    evaluator.pretty_print()
-    if args.csv_path is not None:
-        evaluator.save_kps_csv(args.csv_path)
+    evaluator = gather_evaluator(evaluator)
+    if rank == 0:
+        evaluator.pretty_print()
+        if args.csv_path is not None:
+            evaluator.save_kps_csv(args.csv_path)
     return evaluator
 
 

@@ -145,6 +145,65 @@ __global__ __launch_bounds__(256) void k_loss_finalize(const float* __restrict__
     }
 }
 
+// sum |pred - target| * mask  and  #mask over the n entries of image b alone: l1_term's loop at B = 1 on image b's rows, so the
+// result has the bits of a separate B = 1 call.
+__device__ void l1_term_image(const RegView& r, int b, int64_t hw, double* red, double& sum, double& cnt) {
+    double s = 0.0, c = 0.0;
+    const int64_t row = (int64_t)b * r.n;
+    for (int i = threadIdx.x; i < r.n; i += 256) {
+        if (!r.mask[row + i]) continue;
+        int64_t id = r.inds[row + i];
+        id = id < 0 ? 0 : (id >= hw ? hw - 1 : id);
+        const float* f = r.f + (int64_t)b * r.sb + id;
+        s += (double)fabsf(f[0] - r.tgt[2 * (row + i)]) + (double)fabsf(f[r.sc] - r.tgt[2 * (row + i) + 1]);
+        c += 1.0;
+    }
+    sum = block_sum_d(s, red);
+    cnt = block_sum_d(c, red);
+}
+
+// Per-image finalize, grid = B: block b reduces image b's C*chunks partials and its three masked-L1 terms in k_loss_finalize's
+// order at B = 1 and writes out[b*8 + 0..7] -- each row is bit-identical to a separate B = 1 sd_loss_fwd.
+__global__ __launch_bounds__(256) void k_loss_finalize_per_image(const float* __restrict__ partial, int M, int N, int hw, int chunks,
+                                                                  int focal, float hm_w, float off_w, float emb_w, RegView ra, RegView rp,
+                                                                  RegView re, float* __restrict__ out) {
+    __shared__ double red[4];
+    const int b = blockIdx.x;
+    const int C = M + N;
+    const float* part = partial + (int64_t)b * C * chunks * 3;
+    double acc[2][3] = {{0, 0, 0}, {0, 0, 0}};
+    for (int i = threadIdx.x; i < C * chunks; i += 256) {
+        const int c = i / chunks;
+        const int g = (c < M) ? 0 : 1;
+        acc[g][0] += part[3 * (int64_t)i + 0];
+        acc[g][1] += part[3 * (int64_t)i + 1];
+        acc[g][2] += part[3 * (int64_t)i + 2];
+    }
+    double tot[2][3];
+    for (int g = 0; g < 2; ++g)
+        for (int j = 0; j < 3; ++j) tot[g][j] = block_sum_d(acc[g][j], red);
+    double la, ca, lp, cp, le, ce;
+    l1_term_image(ra, b, hw, red, la, ca);
+    l1_term_image(rp, b, hw, red, lp, cp);
+    l1_term_image(re, b, hw, red, le, ce);
+    if (threadIdx.x == 0) {
+        double hm = 0.0;
+        for (int g = 0; g < 2; ++g) {
+            const double n_el = (double)(g ? N : M) * hw;                 // B = 1
+            if (!focal) hm += tot[g][0] / n_el;
+            else hm += (tot[g][2] == 0.0) ? -tot[g][0] : -(tot[g][1] + tot[g][0]) / tot[g][2];
+        }
+        hm *= hm_w;
+        const double off = off_w * ((ca > 0 ? la / ca : 0.0) + (cp > 0 ? lp / cp : 0.0));
+        const double emb = emb_w * (ce > 0 ? le / ce : 0.0);
+        float* o = out + (int64_t)b * 8;
+        o[0] = (float)(hm + off + emb);
+        o[1] = (float)hm; o[2] = (float)off; o[3] = (float)emb;
+        o[4] = (float)tot[0][2]; o[5] = (float)tot[1][2];
+        o[6] = (float)ca; o[7] = (float)cp;
+    }
+}
+
 // d total / d logits for the heatmap channels; zero for the 4 regression channels (filled in by
 // k_loss_bwd_scatter afterwards).  grid (chunks, M+N+4, B).
 __global__ __launch_bounds__(256) void k_loss_bwd_dense(HmView a, HmView p, int B, int M, int N, int hw, int focal, float hm_w,
@@ -301,6 +360,28 @@ int sd_loss_fwd(const sd_loss_desc* d, float* out8, void* workspace, size_t work
     RegView re{d->embeddings, d->e_sb, d->e_sc, d->t_embeddings, d->part_inds, d->part_mask, d->P};
     hipLaunchKernelGGL(k_loss_finalize, dim3(1), dim3(256), 0, st, (const float*)workspace, d->B, d->M, d->N, hw, chunks, focal,
                        d->hm_weight, d->offset_weight, d->embedding_weight, ra, rp, re, out8);
+    SD_LAUNCH_CHECK();
+    return 0;
+}
+
+int sd_loss_fwd_per_image(const sd_loss_desc* d, float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
+    if (int e = check_desc(d)) return e;
+    SD_REQUIRE(out && workspace, SD_ERR_INVALID, "sd_loss_fwd_per_image: null pointer");
+    SD_REQUIRE(workspace_bytes >= sd_loss_workspace_bytes(d->B, d->M, d->N, d->h, d->w), SD_ERR_WORKSPACE,
+               "sd_loss_fwd_per_image: workspace too small");
+    const int hw = d->h * d->w, chunks = cdiv(hw, LOSS_CHUNK);
+    const int focal = d->hm_loss_fn == SD_HM_FOCAL;
+    HmView a{d->anchor_hm, d->a_sb, d->a_sc, d->t_anchor_hm, d->ta_sb, d->ta_sc};
+    HmView p{d->part_hm, d->p_sb, d->p_sc, d->t_part_hm, d->tp_sb, d->tp_sc};
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_loss_hm_partial, dim3(chunks, d->M + d->N, d->B), dim3(256), 0, st, a, p, d->M, hw, chunks, focal,
+                       (float*)workspace);
+    SD_LAUNCH_CHECK();
+    RegView ra{d->offsets, d->o_sb, d->o_sc, d->anchor_offsets, d->anchor_inds, d->anchor_mask, d->K};
+    RegView rp{d->offsets, d->o_sb, d->o_sc, d->part_offsets, d->part_inds, d->part_mask, d->P};
+    RegView re{d->embeddings, d->e_sb, d->e_sc, d->t_embeddings, d->part_inds, d->part_mask, d->P};
+    hipLaunchKernelGGL(k_loss_finalize_per_image, dim3(d->B), dim3(256), 0, st, (const float*)workspace, d->M, d->N, hw, chunks, focal,
+                       d->hm_weight, d->offset_weight, d->embedding_weight, ra, rp, re, out);
     SD_LAUNCH_CHECK();
     return 0;
 }

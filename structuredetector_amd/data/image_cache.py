@@ -149,13 +149,14 @@ class DeviceImageCache:
         ev.record(stream or torch.cuda.current_stream(self.device))
         self.fence = ev
 
-    def prefill(self, dataset, workers=None):
+    def prefill(self, dataset, workers=None, indices=None):
         """Decode every sample of a CropDataset(raw=True) not cached yet on a pool of threads (data/feeder.py: prefetch_items), upload each
-        from pinned memory on a side stream into the arenas, and fence with an event (waited for here).  Returns the number decoded."""
+        from pinned memory on a side stream into the arenas, and fence with an event (waited for here).  indices: the samples to consider
+        (default: all).  Returns the number decoded."""
         from .feeder import prefetch_items
         t0 = time.perf_counter()
         todo = []
-        for j in range(len(dataset)):
+        for j in (range(len(dataset)) if indices is None else indices):
             if not self.contains(dataset, j):
                 todo.append(j)
         torch.cuda.set_device(self.device)

@@ -1,9 +1,9 @@
 """`Loss`: heatmap (MSE or CornerNet focal) + masked-L1 offset / embedding loss.
 
 Mirrors src/sdnet/model/loss.py:8-64,91-165 (`Loss`, `LossStats`; `FocalLoss` / `L1Loss` exist
-as the fused HIP kernels `sd_loss_fwd` / `sd_loss_bwd`).  Differences in mechanism, not in
-result: one fused forward pass + one finalize block instead of ~40 launches, and the
-reference's host branches (`numel == 0`, `num_pos == 0`) run on the device, so a training step
+as the fused HIP kernels `sd_loss_fwd` / `sd_loss_bwd`, and `sd_loss_fwd_per_image` gives validation its
+per-image losses for a whole batch).  Differences in mechanism, not in result: one fused forward
+pass + one finalize block instead of ~40 launches, and the reference's host branches (`numel == 0`, `num_pos == 0`) run on the device, so a training step
 never synchronises with the host.
 """
 from __future__ import annotations
@@ -35,9 +35,8 @@ def _common_base(views):
     return base if c0 == Cb else None
 
 
-def loss_forward(head, tgt, cfg):
-    """sd_loss_fwd on the raw head tensor (B, M+N+4, h, w).  Returns (desc, keep-alive list, out8) where
-    out8 = [total, hm, offset, embedding, num_pos_a, num_pos_p, n_valid_a, n_valid_p] on the device."""
+def loss_desc(head, tgt, cfg):
+    """The sd_loss_desc of the raw head tensor (B, M+N+4, h, w) and the targets.  Returns (desc, keep-alive list)."""
     (M, N, K, P, fn, hm_w, off_w, emb_w) = cfg
     B, Cc, h, w = head.shape
     keep = [head]
@@ -81,11 +80,28 @@ def loss_forward(head, tgt, cfg):
     d.B, d.M, d.N, d.h, d.w, d.K, d.P = B, M, N, h, w, K, P
     d.hm_loss_fn = fn
     d.hm_weight, d.offset_weight, d.embedding_weight = hm_w, off_w, emb_w
+    return d, keep
+
+
+def loss_forward(head, tgt, cfg):
+    """sd_loss_fwd on the raw head tensor (B, M+N+4, h, w).  Returns (desc, keep-alive list, out8) where
+    out8 = [total, hm, offset, embedding, num_pos_a, num_pos_p, n_valid_a, n_valid_p] on the device."""
+    d, keep = loss_desc(head, tgt, cfg)
     out8 = torch.empty(8, dtype=torch.float32, device=head.device)
     lib = L.lib()
-    ws = L.workspace(lib.sd_loss_workspace_bytes(B, M, N, h, w), head.device)
+    ws = L.workspace(lib.sd_loss_workspace_bytes(d.B, d.M, d.N, d.h, d.w), head.device)
     L.check(lib.sd_loss_fwd(C.byref(d), out8.data_ptr(), ws.data_ptr(), ws.numel(), L.stream()), "sd_loss_fwd")
     return d, keep, out8
+
+
+def loss_forward_per_image(head, tgt, cfg):
+    """sd_loss_fwd_per_image: (B, 8) device tensor, row b = loss_forward's out8 of image b alone (the same bits)."""
+    d, keep = loss_desc(head, tgt, cfg)
+    out = torch.empty((d.B, 8), dtype=torch.float32, device=head.device)
+    lib = L.lib()
+    ws = L.workspace(lib.sd_loss_workspace_bytes(d.B, d.M, d.N, d.h, d.w), head.device)
+    L.check(lib.sd_loss_fwd_per_image(C.byref(d), out.data_ptr(), ws.data_ptr(), ws.numel(), L.stream()), "sd_loss_fwd_per_image")
+    return out
 
 
 def loss_backward(desc, out8, grad_out, shape):
@@ -133,6 +149,20 @@ class Loss(torch.nn.Module):
         total, out8 = _SdLoss.apply(head, target, cfg)
         self.stats.update(out8[1], out8[2], out8[3])
         return total
+
+    def per_image(self, input, target):
+        """The loss of every image of the batch on its own, in one launch pair: (B, 8) device tensor whose row b is `forward`'s
+        out8 for image b alone -- [total, hm, offset, embedding, num_pos_a, num_pos_p, n_valid_a, n_valid_p], the bits of a B = 1
+        call.  No autograd, no host sync; `stats` is left alone."""
+        views = [input["anchor_hm"], input["part_hm"], input["offsets"], input["embeddings"]]
+        L.require_cuda(*views)
+        M, N = views[0].shape[1], views[1].shape[1]
+        with torch.no_grad():
+            head = _common_base(views)
+            if head is None:
+                head = torch.cat([v.float() for v in views], dim=1)
+            cfg = loss_config(self.args, M, N, target["anchor_inds"].shape[1], target["part_inds"].shape[1])
+            return loss_forward_per_image(head, target, cfg)
 
 
 class LossStats:

@@ -18,47 +18,59 @@ from __future__ import annotations
 import torch
 
 
-def index_batches(n, batch):
-    return [list(range(lo, min(lo + batch, n))) for lo in range(0, n, batch)]
+def index_batches(n, batch, lo=0):
+    return [list(range(i, min(i + batch, n))) for i in range(lo, n, batch)]
 
 
-def batched_outputs(net, decoder, dataset, args, batch=None, workers=None, with_raw_parts=True, keep_output=False, depth=2, cache=None):
+def batched_decodes(net, decoder, dataset, args, batch=None, workers=None, with_raw_parts=True, depth=2, cache=None, index_range=None):
     """dataset: `CropDataset(args, dir, raw=True)` or `PredictionDataset(dir, args, raw=True)` -- items ((H, W, 3) uint8 tensor,
-    ImageAnnotation in ORIGINAL pixels with img_size).  Yields, per image and in dataset order,
-    (prediction ImageAnnotation in network-input pixels, ground-truth annotation in network-input pixels (resized + clipped like
-    Resize + Encode do, transforms.py:47-60,154), raw_parts or None, this image's output dict of (1, C, h, w) views when keep_output else None).
+    ImageAnnotation in ORIGINAL pixels with img_size).  Yields, per decoded batch and in dataset order,
+    (list of prediction ImageAnnotations in network-input pixels, list of ground-truth annotations in network-input pixels (resized +
+    clipped like Resize + Encode do, transforms.py:47-60,154), list of raw_parts or None, the batch's output dict of (B, C, h, w) views).
+    index_range: (lo, hi), the items to run (a rank's shard, utils/distributed.shard_range); batches are cut inside it.  Default: all.
     cache: a data/image_cache.py DeviceImageCache the feed reads cached images from (CropDataset only), or None."""
     from ..data.augment import ValidationAugmentation
     from ..data.feeder import BatchFeeder, default_decode_workers
     batch = int(batch or getattr(args, "eval_batch", 16) or 16)
     workers = workers or getattr(args, "decode_workers", 0) or default_decode_workers()
+    lo, hi = index_range if index_range is not None else (0, len(dataset))
+    if hi <= lo:                                   # an empty shard (more ranks than images)
+        return
     prepare = ValidationAugmentation(args)
     pending = None
 
     def finish(p):
         handle, anns, out = p
         preds, raws = handle.result()
-        for i, (pred, ann) in enumerate(zip(preds, anns)):
-            yield pred, ann, (raws[i] if raws is not None else None), (None if out is None else {k: v[i:i + 1] for k, v in out.items()})
+        return list(preds), list(anns), (list(raws) if raws is not None else None), out
 
     threads = torch.get_num_threads()
     torch.set_num_threads(1)                       # the loop's host work is tiny tensor ops; torch's pool would spin against the decode threads
     try:
-        for group in BatchFeeder(dataset, index_batches(len(dataset), batch), args.device, workers=workers, depth=depth, cache=cache):
+        for group in BatchFeeder(dataset, index_batches(hi, batch, lo), args.device, workers=workers, depth=depth, cache=cache):
             with torch.no_grad():
                 images, anns = prepare(group, group.annotations)
                 out = net(images)
                 if isinstance(out, torch.Tensor):  # Network(raw_output=True)
                     out = split_head(net, out)
                 handle = decoder.submit(out, with_raw_parts=with_raw_parts)
-            cur = (handle, anns, out if keep_output else None)
+            cur = (handle, anns, out)
             if pending is not None:
-                yield from finish(pending)
+                yield finish(pending)
             pending = cur
         if pending is not None:
-            yield from finish(pending)
+            yield finish(pending)
     finally:
         torch.set_num_threads(threads)
+
+
+def batched_outputs(net, decoder, dataset, args, batch=None, workers=None, with_raw_parts=True, keep_output=False, depth=2, cache=None,
+                    index_range=None):
+    """`batched_decodes` one image at a time: yields, per image and in dataset order, (prediction, ground-truth annotation, raw_parts or
+    None, this image's output dict of (1, C, h, w) views when keep_output else None)."""
+    for preds, anns, raws, out in batched_decodes(net, decoder, dataset, args, batch, workers, with_raw_parts, depth, cache, index_range):
+        for i, (pred, ann) in enumerate(zip(preds, anns)):
+            yield pred, ann, (raws[i] if raws is not None else None), ({k: v[i:i + 1] for k, v in out.items()} if keep_output else None)
 
 
 def split_head(net, out):

@@ -402,41 +402,90 @@ class Trainer:
             finally:
                 torch.set_num_threads(threads)
 
-    def valid_samples(self):
-        """Per image, in order: (prediction, annotation in network-input pixels, raw_parts, this image's head views)."""
-        a = self.args
+    def valid_batches(self):
+        """Per batch of this rank's contiguous shard of the validation set, in order: (predictions, annotations in network-input pixels,
+        raw_parts, the batch's head views).  Directory: `--eval_batch` images per forward + decoder launch (model/predictor.py);
+        synthetic: one forward per image, as always, grouped `--eval_batch` at a time for the loss."""
+        from itertools import islice
+
+        from ..utils.distributed import shard_range
+        a, world = self.args, self.step.world
         if self.valid_set is not None:
             # decode threads -> GPU Resize + Normalize -> forward + decoder at --eval_batch images per launch (model/predictor.py)
-            from .predictor import batched_outputs
-            yield from batched_outputs(self.net, self.decoder, self.valid_set, a, keep_output=True, cache=self.cache)
+            from .predictor import batched_decodes
+            yield from batched_decodes(self.net, self.decoder, self.valid_set, a, cache=self.cache,
+                                       index_range=shard_range(len(self.valid_set), self.rank, world))
             return
         from ..data.synthetic import synthetic_samples
-        for image, annotation in synthetic_samples(a, min(max(a.synthetic, 1), 16), seed=20261003):
+        n = min(max(a.synthetic, 1), 16)
+        lo, hi = shard_range(n, self.rank, world)
+        batch = int(getattr(a, "eval_batch", 16) or 16)
+        group = []
+
+        def collate(group):
+            preds, anns, raws, outs = zip(*group)
+            return list(preds), list(anns), list(raws), {k: torch.cat([o[k] for o in outs]) for k in outs[0]}
+
+        for image, annotation in islice(synthetic_samples(a, n, seed=20261003), lo, hi):
             with torch.no_grad():
                 output = self.net(image[None].to(a.device))
                 data = self.decoder(output, return_metadata=True, metadata_fields=("annotation", "raw_parts"))
-            yield data["annotation"][0], annotation, data["raw_parts"][0], output
+            group.append((data["annotation"][0], annotation, data["raw_parts"][0], output))
+            if len(group) == batch:
+                yield collate(group)
+                group = []
+        if group:
+            yield collate(group)
+
+    def _take_rank0_buffers(self):
+        """Data-parallel validation scores rank 0's model (the one reported and saved): every rank keeps a copy of its own BatchNorm
+        running statistics (rank-local, no SyncBN) and takes rank 0's by broadcast.  Returns the copies for `_restore_buffers`."""
+        own = [b.detach().clone() for b in self.net.buffers()]
+        for b in self.net.buffers():
+            dist.broadcast(b, 0, group=self.step.pg)
+        self.net.invalidate_folded()                                 # the eval forward caches folded BatchNorm affines
+        return own
+
+    def _restore_buffers(self, own):
+        with torch.no_grad():
+            for b, o in zip(self.net.buffers(), own):
+                b.copy_(o)
+        self.net.invalidate_folded()
 
     def valid(self):
         """Validation pass of the reference (src/sdnet/model/trainer.py:137-237): eval-mode forward, Decoder + Evaluator + Loss PER IMAGE
         (the loss statistics are means over images of per-image losses, :160-168), then the four `model_best_*.pth` checkpoints
-        (rank 0 only).  Forward and decoder run batched; the per-image loss is taken on that image's slice of the batch output."""
+        (rank 0 only).  Forward and decoder run batched; the per-image losses of a batch come from one Encode and one
+        `Loss.per_image` launch pair (bit-identical to one loss call per image).
+        Data-parallel: each rank runs its contiguous shard (utils/distributed.py) with rank 0's BatchNorm buffers; per-image loss rows
+        and Evaluators are gathered in rank order, so every rank returns the stats of one pass over the whole set in sample order
+        and keeps the same best-so-far values; afterwards each rank has its own buffers back."""
+        from ..utils.distributed import gather_evaluator, gather_rows
         a = self.args
+        world = self.step.world
+        own = self._take_rank0_buffers() if world > 1 else None
         self.net.eval()
         self.evaluator.reset()
-        stats, n, per_image = LossStats(), 0, []
-        for prediction, annotation, raw_parts, output in self.valid_samples():
-            with torch.no_grad():
-                self.evaluator.accumulate(prediction, annotation, raw_parts, eval_csi=True, eval_classif=True)
-                # the annotation is in network-input pixels (resized + clipped / the synthetic generator): encode it as the target
-                target = self.encode.batch((a.width, a.height), [annotation], a.device)
-                self.loss(output, target)
-            per_image.append(torch.stack([self.loss.stats.hm_loss, self.loss.stats.offset_loss, self.loss.stats.embedding_loss]))
-            n += 1
-        if n:                                                      # one host sync for the whole pass (it was three `.item()` per image)
-            stats = LossStats(*(torch.stack(per_image).double().sum(0).tolist()))
-        self.net.train()
-        if n:
+        rows = []
+        try:
+            for predictions, annotations, raw_parts, output in self.valid_batches():
+                with torch.no_grad():
+                    # the Evaluator sees each annotation before Encode clips it in place, as in the reference's per-image loop
+                    self.evaluator.accumulate_batch(predictions, annotations, raw_parts, eval_csi=True, eval_classif=True)
+                    # the annotations are in network-input pixels (resized + clipped / the synthetic generator): encode them as the targets
+                    target = self.encode.batch((a.width, a.height), annotations, a.device)
+                    rows.append(self.loss.per_image(output, target)[:, 1:4])         # hm, offset, embedding per image
+        finally:
+            if own is not None:
+                self._restore_buffers(own)
+            self.net.train()
+        rows = torch.cat(rows) if rows else torch.zeros((0, 3), dtype=torch.float32, device=a.device)
+        rows = gather_rows(rows, self.step.pg)                     # every image of the set, in sample order
+        self.evaluator = gather_evaluator(self.evaluator, self.step.pg)
+        n = rows.shape[0]
+        stats = LossStats()
+        if n:                                                      # one host sync for the whole pass
+            stats = LossStats(*(rows.double().sum(0).tolist()))
             stats /= n
         f1_csi = self.evaluator.csi_eval.reduce().f1_score
         f1_classif = self.evaluator.classification_eval.reduce().f1_score
@@ -451,10 +500,11 @@ class Trainer:
                 writer.add_scalars(tag, values, self.global_step)
             writer.flush()
             print(f"validation ({n} images): loss {stats.total_loss:.5f} | kp F1 {f1_kp:.2%} | CSI F1 {f1_csi:.2%} | classification F1 {f1_classif:.2%}", flush=True)
-            for value, attr, name, better in ((stats.total_loss, "best_loss", "loss", lambda v, b: v < b), (f1_csi, "best_csi", "csi", lambda v, b: v > b),
-                                              (f1_classif, "best_classif", "classif", lambda v, b: v > b), (f1_kp, "best_kp_reg", "kp_reg", lambda v, b: v > b)):
-                if better(value, getattr(self, attr)):
-                    setattr(self, attr, value)
+        for value, attr, name, better in ((stats.total_loss, "best_loss", "loss", lambda v, b: v < b), (f1_csi, "best_csi", "csi", lambda v, b: v > b),
+                                          (f1_classif, "best_classif", "classif", lambda v, b: v > b), (f1_kp, "best_kp_reg", "kp_reg", lambda v, b: v > b)):
+            if better(value, getattr(self, attr)):
+                setattr(self, attr, value)                         # on every rank: all ranks see the same merged numbers
+                if self.rank == 0:
                     self.net.save(self.save_dir / f"model_best_{name}.pth")
         return stats
 
@@ -502,14 +552,17 @@ class Trainer:
                 self._writer = None
 
     def prefill_cache(self):
-        """Decode every training and validation image once into the device cache (each rank the whole set: its shard changes every epoch)."""
+        """Decode every training image and this rank's validation shard once into the device cache (each rank the whole training set: its
+        training shard changes every epoch; the validation shard does not)."""
         from ..data.feeder import default_decode_workers
         from ..data.image_cache import GB
+        from ..utils.distributed import shard_range
         a = self.args
         workers = getattr(a, "decode_workers", 0) or default_decode_workers(self.step.world)
-        for ds in (self.dataset, self.valid_set):
-            if ds is not None:
-                self.cache.prefill(ds, workers)
+        if self.dataset is not None:
+            self.cache.prefill(self.dataset, workers)
+        if self.valid_set is not None:
+            self.cache.prefill(self.valid_set, workers, indices=range(*shard_range(len(self.valid_set), self.rank, self.step.world)))
         st = self.cache.stats()
         if self.rank == 0:
             print(f"image cache: {st['images']} images, {st['bytes_used'] / GB:.2f} GB in {st['prefill_seconds']:.1f} s, "
