@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark of the SDNet hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 A step = one training pass over one synthetic batch (BASELINE.json configs[2]: bs=64/GPU, 512x512 fp32,
@@ -12,9 +12,13 @@ JSON line; `value` = images/sec over all ranks (weak scaling).  The same line ca
   * `roofline`: the MFMA roofline of the dominant kernel, measured live with stream events around every conv launch
     of the timed region (+ every conv kernel and the fwd / dgrad / wgrad phases);
   * `rccl`: self-evidence of the gradient exchange -- before the timed region every rank puts rank+1 through the
-    SAME buckets / binding / streams the step uses and the sum must be N(N+1)/2 on every rank; after it, the isolated
-    duration of each bucket's all-reduce and `exposed_comm_ms` = step time with the exchange - step time without;
-  * `north_star` (N=1, after the timed region; `--no-extras` skips it): eval forward bs=64 fp32 vs the fp32 MFMA peak
+    SAME buckets / binding / streams the step uses and the sum must be N(N+1)/2 on every rank.
+A plain run stops there: set-up, warm-up, the timed steps, `--dump-outputs`, the line.  `--full` also measures,
+after the timed region (each in runs of its own):
+  * `rccl` (N>1): the isolated duration of each bucket's all-reduce and `exposed_comm_ms` = step time with the
+    exchange - step time without;
+  * `roofline` under `--no-conv-events`, from three extra steps;
+  * `north_star` (N=1; `--no-extras` skips it): eval forward bs=64 fp32 vs the fp32 MFMA peak
     (the north-star's >= 60 % target), bs=1 forward + decode + objects (configs[1]), bf16 forward bs=64 vs the bf16
     MFMA peak, and configs[4] (1024x1024, 8 labels / 8 parts, K=128, P=512, bs=16: bf16 forward + fp32 decode);
   * `decode`: HIP decoder us/img (bs=64 on the device, bs=1 end to end) and its fraction of the HBM roofline;
@@ -238,14 +242,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=64, help="images per GPU")
     ap.add_argument("--size", type=int, default=512)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure everything beyond the headline: the CPU baseline, the north-star side "
+                         "figures, the decoder, and (N > 1) each bucket's all-reduce and the exposed communication time")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--overlap-wgrad", action="store_true",
                     help="experiment: run the weight-gradient GEMMs on a side stream (measured in round 2: fp32 step 6 %% SLOWER, mixed "
                          "precision -0.3 %%: both streams are MFMA-bound and share the power budget; per-kernel durations then overlap)")
     ap.add_argument("--exchange", choices=("torch", "rccl"), default=None,
                     help="gradient all-reduce binding for --gpus > 1: torch.distributed's RCCL (default) or the C-ABI sd_allreduce_*")
     ap.add_argument("--no-comm-sim", dest="comm_sim", action="store_false", default=True,
-                    help="skip `north_star.comm_sim` (single-GPU runs): the training step with a simulated all-reduce beside its backward")
+                    help="skip `north_star.comm_sim` (single-GPU --full runs): the training step with a simulated all-reduce beside its backward")
     ap.add_argument("--comm-sim-wgs", type=int, default=32, help="workgroups of the simulated collective (RCCL: one or two per channel)")
     ap.add_argument("--comm-sim-gbps", type=float, default=200.0,
                     help="modelled bus bandwidth of the 8-rank all-reduce over xGMI (7 links x ~50 GB/s per direction: 150-300 GB/s for 1-50 MB buckets)")
@@ -259,11 +266,11 @@ def main():
                     help="experiment: all-zero images (every activation is then zero): same kernels at lower MFMA power -> DVFS headroom")
     ap.add_argument("--no-conv-events", action="store_true",
                     help="A/B of the measurement itself: no stream events around the conv launches of the timed region (the per-kernel "
-                         "figures then come from three extra steps; DESIGN.md records the difference: events on every step cost 1 %%)")
+                         "figures then come from three extra steps under --full, a plain run reports roofline null; DESIGN.md records "
+                         "the difference: events on every step cost 1 %%)")
     ap.add_argument("--no-extras", dest="extras", action="store_false", default=True,
-                    help="skip the north-star side figures measured AFTER the timed region (eval forward bs=B / bs=1, bf16 forward, "
-                         "configs[4] stress forward + decode): use it under rocprofv3 --stats so that the per-kernel averages "
-                         "describe the timed training steps only")
+                    help="--full without the north-star side figures measured AFTER the timed region (eval forward bs=B / bs=1, bf16 "
+                         "forward, configs[4] stress forward + decode)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed to DIR/<name>.npy (rank 0): the loss vector, a fixed "
                          "sample of the updated weights and of the gradients, the BatchNorm running statistics (see dump_outputs)")
@@ -387,7 +394,7 @@ def main():
     if a.dump_outputs and rank == 0:                     # before anything else runs a step on these weights
         dump_outputs(Path(a.dump_outputs), net, loss)
     prof, prof_steps = events, sampled
-    if not prof:                                         # --no-conv-events: the per-kernel figures come from three extra (untimed) steps
+    if not prof and a.full:                              # --no-conv-events: the per-kernel figures come from three extra (untimed) steps
         net._engine.prof = prof = []
         prof_steps = 3
         for i in range(prof_steps):
@@ -404,7 +411,7 @@ def main():
         rccl["ms_per_step_per_rank_max"] = round(max(float(v.item()) for v in per_rank) / a.steps * 1e3, 3)
     loss_host = [float(v) for v in loss.cpu()]
     assert all(np.isfinite(loss_host)), f"non-finite loss {loss_host}"
-    if world > 1:
+    if world > 1 and a.full:
         # exposed communication = step time with the exchange - step time without it (same schedule, all-reduce skipped),
         # and the isolated duration of each bucket's all-reduce (what the overlap has to hide)
         rccl["buckets_isolated"] = step.time_buckets()
@@ -424,30 +431,32 @@ def main():
         rccl["allreduce_bytes_per_step"] = int(net.flat_grads.numel()) * 4
 
     # ---- roofline of the dominant kernel (live, from the timed region)
-    per, phases = {}, {}
-    for kind, flops, e0, e1, phase in prof:
-        t = e0.elapsed_time(e1) * 1e-3
-        d = per.setdefault(kind, [0, 0.0, 0.0])
-        d[0] += 1; d[1] += flops; d[2] += t
-        q = phases.setdefault(phase, [0.0, 0.0])
-        q[0] += flops; q[1] += t
-    kernels = {k: {"launches_per_step": v[0] // max(prof_steps, 1), "avg_launch_us": round(v[2] / v[0] * 1e6, 2),
-                   "gflop_per_launch": round(v[1] / v[0] / 1e9, 3), "tflops": round(v[1] / v[2] / 1e12, 2)} for k, v in per.items()}
-    dom = max(per, key=lambda k: per[k][2])
-    ach = per[dom][1] / per[dom][2] / 1e12
-    # (`--amp`: the engine labels its bf16 launches "bf16:<kernel the fp32 dispatcher would pick>"; their roofline is the bf16 MFMA peak)
-    peak_dom = PEAK_BF16_MFMA_TFLOPS if dom.startswith("bf16:") else PEAK_FP32_MFMA_TFLOPS
-    conv_time_frac = sum(v[2] for v in per.values()) / prof_steps / max(dt / a.steps, 1e-9)
-    traffic, traffic_src = pmc_traffic(dom) if (B, img) == (64, 512) and not a.amp else (None, None)
-    roofline = {"bound": "mfma", "kernel": dom, "achieved": round(ach, 2), "peak": peak_dom, "unit": "TFLOP/s",
-                "frac": round(ach / peak_dom, 4), "traffic": traffic, "traffic_source": traffic_src,
-                "flops_per_launch": round(per[dom][1] / per[dom][0], 1), "avg_launch_us": kernels[dom]["avg_launch_us"],
-                "launches_per_step": kernels[dom]["launches_per_step"], "all_conv_kernels": kernels,
-                "conv_phases": {ph: {"ms_per_step": round(v[1] / prof_steps * 1e3, 3), "tflops": round(v[0] / v[1] / 1e12, 2),
-                                     "frac_of_peak": round(v[0] / v[1] / 1e12 / peak_dom, 4)} for ph, v in phases.items()},
-                "conv_share_of_step_time": round(conv_time_frac, 3)}
+    roofline = None                                      # (a plain --no-conv-events run has no events to read)
+    if prof:
+        per, phases = {}, {}
+        for kind, flops, e0, e1, phase in prof:
+            t = e0.elapsed_time(e1) * 1e-3
+            d = per.setdefault(kind, [0, 0.0, 0.0])
+            d[0] += 1; d[1] += flops; d[2] += t
+            q = phases.setdefault(phase, [0.0, 0.0])
+            q[0] += flops; q[1] += t
+        kernels = {k: {"launches_per_step": v[0] // max(prof_steps, 1), "avg_launch_us": round(v[2] / v[0] * 1e6, 2),
+                       "gflop_per_launch": round(v[1] / v[0] / 1e9, 3), "tflops": round(v[1] / v[2] / 1e12, 2)} for k, v in per.items()}
+        dom = max(per, key=lambda k: per[k][2])
+        ach = per[dom][1] / per[dom][2] / 1e12
+        # (`--amp`: the engine labels its bf16 launches "bf16:<kernel the fp32 dispatcher would pick>"; their roofline is the bf16 MFMA peak)
+        peak_dom = PEAK_BF16_MFMA_TFLOPS if dom.startswith("bf16:") else PEAK_FP32_MFMA_TFLOPS
+        conv_time_frac = sum(v[2] for v in per.values()) / prof_steps / max(dt / a.steps, 1e-9)
+        traffic, traffic_src = pmc_traffic(dom) if (B, img) == (64, 512) and not a.amp else (None, None)
+        roofline = {"bound": "mfma", "kernel": dom, "achieved": round(ach, 2), "peak": peak_dom, "unit": "TFLOP/s",
+                    "frac": round(ach / peak_dom, 4), "traffic": traffic, "traffic_source": traffic_src,
+                    "flops_per_launch": round(per[dom][1] / per[dom][0], 1), "avg_launch_us": kernels[dom]["avg_launch_us"],
+                    "launches_per_step": kernels[dom]["launches_per_step"], "all_conv_kernels": kernels,
+                    "conv_phases": {ph: {"ms_per_step": round(v[1] / prof_steps * 1e3, 3), "tflops": round(v[0] / v[1] / 1e12, 2),
+                                         "frac_of_peak": round(v[0] / v[1] / 1e12 / peak_dom, 4)} for ph, v in phases.items()},
+                    "conv_share_of_step_time": round(conv_time_frac, 3)}
 
-    # ---- north-star side figures (same process, AFTER the timed region; rank 0, single-GPU runs only)
+    # ---- --full: north-star side figures (same process, AFTER the timed region; rank 0, single-GPU runs only)
     extra = {}
 
     def timed(fn, n, warm=2):
@@ -487,7 +496,7 @@ def main():
         except Exception as err:
             ns[key] = {"error": repr(err)[:300]}
 
-    if rank == 0 and a.extras and world == 1:
+    if a.full and rank == 0 and a.extras and world == 1:
         ns = {}
 
         def fig_fwd_fp32():
@@ -683,7 +692,7 @@ def main():
         if (B, img) == (64, 512):
             guarded(ns, "directory_feed", fig_directory_feed)
         extra["north_star"] = ns
-    if rank == 0:
+    if a.full and rank == 0:
         try:
             dec = Decoder(args)
             tgt = enc.render_device(plans[0])
@@ -734,7 +743,7 @@ def main():
             "rccl": rccl,
         }
         line.update(extra)
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline(M, N, K, P, img)
             except Exception as err:

@@ -114,7 +114,8 @@ def test_bench_two_ranks_rehearsal_over_gloo(launcher):
     """bench.py's multi-rank path as the driver launches it (torch.distributed.run, one process per rank, barrier + max-over-ranks
     timing, rank 0 prints the one JSON line) with two ranks sharing the test GPU and gloo standing in for RCCL -- and the same run
     started as plain `python bench.py --gpus 2` (no launcher, WORLD_SIZE unset): bench.py then spawns its ranks itself before
-    any GPU call and relays rank 0's line and the child's exit code."""
+    any GPU call and relays rank 0's line and the child's exit code.  Under `--full`, the line also carries each bucket's isolated
+    all-reduce and the exposed communication time."""
     import json
     import subprocess
     import sys
@@ -123,7 +124,7 @@ def test_bench_two_ranks_rehearsal_over_gloo(launcher):
     env = dict(os.environ, SDNET_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR"):
         env.pop(k, None)
-    tail = [str(root / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4", "--size", "128"]
+    tail = [str(root / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4", "--size", "128", "--full"]
     if launcher == "torchrun":
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                "--master-port", str(_free_port())] + tail
@@ -142,6 +143,33 @@ def test_bench_two_ranks_rehearsal_over_gloo(launcher):
     assert set(r["buckets_isolated"]) == {"fpn_head", "down4", "down3", "down2", "down1_stem"}
     assert sum(b["floats"] for b in r["buckets_isolated"].values()) * 4 == r["allreduce_bytes_per_step"] > 87_000_000
     assert "exposed_comm_ms" in r and r["ms_per_step_without_exchange"] > 0
+
+
+def test_bench_plain_run_is_the_headline_only(tmp_path):
+    """`python bench.py --gpus 1` without `--full`: the headline line (with the roofline read from the timed region's events) and
+    the dumped outputs of the last timed step, and none of the side figures that take runs of their own."""
+    import json
+    import subprocess
+    import sys
+    from pathlib import Path
+    root = Path(__file__).resolve().parent.parent
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    cmd = [sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "4", "--size", "128",
+           "--dump-outputs", str(tmp_path)]
+    out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    rec = json.loads(lines[0])
+    assert rec["metric"] == "images/sec (train fwd+bwd) and decode us/img at 512x512" and rec["unit"] == "images/sec"
+    assert rec["higher_is_better"] is True and rec["dtype"] == "f32" and (rec["steps"], rec["warmup"]) == (2, 1)
+    assert rec["value"] == pytest.approx(4 * 1e3 / rec["ms_per_step"], rel=1e-3)
+    assert rec["roofline"]["kernel"] and rec["roofline"]["launches_per_step"] > 0
+    assert rec["rccl"]["check"].startswith("single rank")
+    assert not {"north_star", "decode", "cpu_baseline"} & set(rec)
+    assert np.load(tmp_path / "loss.npy").tolist() == pytest.approx(rec["loss"], abs=1e-6)
+    for name in ("params", "grads", "bn_running"):
+        assert np.isfinite(np.load(tmp_path / f"{name}.npy")).all()
 
 
 def test_verify_exchange_detects_a_missing_rank(monkeypatch):

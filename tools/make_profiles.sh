@@ -16,8 +16,8 @@ stats() {   # stats <name> <python script + args>: rocprofv3 --kernel-trace --st
 # 1. the default bench command's timed region under rocprofv3 (side figures and CPU baseline off: per-kernel averages = training steps)
 stats bench_no_extras bench.py --no-extras --no-cpu-baseline
 grep '^{' $OUT/${TAG}_bench_no_extras.stdout > $OUT/${TAG}_bench_under_rocprof.json
-# 2. the default bench line itself (no profiler)
-python3 bench.py > $OUT/${TAG}_bench_default_run.json 2> gpurun_out/mp_bench.err
+# 2. the bench line with every side figure (no profiler)
+python3 bench.py --full > $OUT/${TAG}_bench_default_run.json
 # 3. training steps only: fp32 and mixed precision; bf16 eval forward
 stats train_fp32 tools/prof_train.py 4
 stats train_amp tools/prof_train.py 4 amp
