@@ -575,6 +575,74 @@ int sd_comm_sim_copy(const void* src, void* dst, size_t src_bytes, size_t move_b
 double sd_mfma_bf16_stream_flops(int iters);
 int    sd_mfma_bf16_stream(const void* operands64k, float* out, int iters, sd_stream_t stream);
 
+/* ---- synchronized BatchNorm (data-parallel training: statistics over the whole global batch) ----
+ * Every batch-statistics finish above is one launch that reduces partial rows to per-channel sums in double, in a fixed order, and
+ * turns them into outputs.  The split forms below stop after the first half and hand the sums to the caller in ONE fp64 vector
+ *     sums = [S0 (C), S1 (C), n]      forward:  S0 = sum x,  S1 = sum x^2;   backward: S0 = sum g,  S1 = sum g * xhat
+ * (n = the element count M of this call, C + C + 1 doubles, 8-byte aligned), so that the caller can all-reduce it (sum) across ranks;
+ * the second half then turns the (global) sums into outputs.  Summation order and arithmetic are those of the one-launch finish: with
+ * no exchange in between, split == fused bit for bit.  The backward's phase 1 writes dgamma / dbeta (+= when accumulate) from the
+ * LOCAL sums (they reach the other ranks through the gradient all-reduce).  Workspaces are those of the fused forms.
+ * These are contract changes (results depend on what the caller does with `sums`), hence explicit entry points, not sd_set_option. */
+/* phase 2, forward: mean = S0/n, invstd = 1/sqrt(S1/n - mean^2 + eps), running stats with momentum and the unbiased var
+ * (var * n/(n-1)); running_mean / running_var both given or both null.  Phase 2, backward: means_out = [S0/n (C), S1/n (C)] as
+ * sd_bn_bwd_apply / sd_bn_bwd_apply_bf16 / sd_maxpool_bn_relu_bwd_apply* consume them. */
+int sd_bn_stats_from_sums(const double* sums, int C, float eps, float momentum, float* running_mean, float* running_var, float* mean,
+                          float* invstd, sd_stream_t stream);
+int sd_bn_bwd_means_from_sums(const double* sums, int C, float* means_out, sd_stream_t stream);
+/* phase 1 of sd_bn_finalize_stats / sd_bn_bwd_finalize on caller-provided partial rows (same rows, scratch and order) */
+int sd_bn_stats_sums(const float* partial, int rows, int64_t M, int C, double* sums, float* scratch, sd_stream_t stream);
+int sd_bn_bwd_sums(const float* partial, int rows, int64_t M, int C, float* dgamma, float* dbeta, int accumulate, double* sums,
+                   float* scratch, sd_stream_t stream);
+/* sd_bn_train_stats[_bf16] stopping after phase 1 */
+int sd_bn_train_sums(const float* x, int64_t M, int C, double* sums, void* workspace, size_t workspace_bytes, sd_stream_t stream);
+int sd_bn_train_sums_bf16(const void* x, int64_t M, int C, double* sums, void* workspace, size_t workspace_bytes, sd_stream_t stream);
+/* the fused conv forwards stopping after phase 1 (the statistics still come from the conv epilogue: no extra pass over y).
+ * sd_conv2d_fwd_bn_stats_rows: partial rows the epilogue of that forward writes (bf16 = 0: fp32 kernels, 1: bf16 kernels);
+ * 0 = the split-K two-pass form (conv, then sd_bn_train_stats); -1 = unsupported geometry.  Host arithmetic only. */
+int sd_conv2d_fwd_bn_stats_rows(const sd_conv_desc* d, int bf16);
+int sd_conv2d_fwd_bn_sums(const float* x, const float* w, float* y, const sd_conv_desc* d, double* sums, void* workspace,
+                          size_t workspace_bytes, sd_stream_t stream);
+int sd_conv2d_fwd_bf16_bn_sums(const void* x, const void* w, void* y, const sd_conv_desc* d, double* sums, void* workspace,
+                               size_t workspace_bytes, sd_stream_t stream);
+int sd_conv2d_stem_fwd_bn_sums(const float* x_nchw, const float* w, float* y, const sd_conv_desc* d, double* sums, void* workspace,
+                               size_t workspace_bytes, sd_stream_t stream);
+int sd_conv2d_stem_fwd_bn_sums_bf16mm(const float* x_nchw, const float* w, float* y, const sd_conv_desc* d, double* sums, void* workspace,
+                                      size_t workspace_bytes, sd_stream_t stream);
+int sd_conv2d_stem_fwd_bn_sums_bf16(const float* x_nchw, const float* w, void* y_bf16, const sd_conv_desc* d, double* sums, void* workspace,
+                                    size_t workspace_bytes, sd_stream_t stream);
+/* the fused data-gradient + BatchNorm-backward reduction stopping after phase 1 (dgamma / dbeta += local sums) */
+int sd_conv2d_dgrad_bn_reduce_sums(const float* dy, const float* w_t, float* dx, const sd_conv_desc* d, const float* residual,
+                                   const float* bn_x, const float* bn_y, int relu, const float* mean, const float* invstd,
+                                   const float* gamma, const float* beta, float* dgamma, float* dbeta, int accumulate,
+                                   double* sums, void* workspace, size_t workspace_bytes, sd_stream_t stream);
+/* the reduce half of sd_bn_bwd[_bf16] (relu as there); the apply half is sd_bn_bwd_apply / sd_bn_bwd_apply_bf16 (the bf16 forms
+ * choose their 8-wide kernels from 16-byte alignment as sd_bn_bwd_bf16 does: buffers of one allocator make the same choice) */
+int sd_bn_bwd_reduce(const float* dy, const float* x, const float* y, int relu, int64_t M, int C, const float* mean, const float* invstd,
+                     const float* gamma, const float* beta, float* dgamma, float* dbeta, int accumulate, double* sums, void* workspace,
+                     size_t workspace_bytes, sd_stream_t stream);
+int sd_bn_bwd_reduce_bf16(const void* dy, const void* x, const void* y, int relu, int64_t M, int C, const float* mean, const float* invstd,
+                          const float* gamma, const float* beta, float* dgamma, float* dbeta, int accumulate, double* sums, void* workspace,
+                          size_t workspace_bytes, sd_stream_t stream);
+int sd_bn_bwd_apply_bf16(const void* dy, const void* x, const void* y, int relu, int64_t M, int C, const float* mean, const float* invstd,
+                         const float* gamma, const float* beta, const float* means, void* dx, void* g_out, sd_stream_t stream);
+/* the stem tail's backward in two halves: reduce (sd_maxpool_bn_relu_bwd's reduction + phase 1; fp32, or bf16 dpool / x) and apply
+ * from the means of sd_bn_bwd_means_from_sums (fp32; bf16 in, fp32 dx; bf16 in, bf16 dx).  Workspace as sd_maxpool_bn_relu_bwd. */
+int sd_maxpool_bn_relu_bwd_reduce(const float* dpool, const uint8_t* idx, const float* x, int B, int Hi, int Wi, int C, const float* mean,
+                                  const float* invstd, const float* gamma, const float* beta, float* dgamma, float* dbeta, int accumulate,
+                                  double* sums, void* workspace, size_t workspace_bytes, sd_stream_t stream);
+int sd_maxpool_bn_relu_bwd_reduce_bf16(const void* dpool_bf16, const uint8_t* idx, const void* x_bf16, int B, int Hi, int Wi, int C,
+                                       const float* mean, const float* invstd, const float* gamma, const float* beta, float* dgamma,
+                                       float* dbeta, int accumulate, double* sums, void* workspace, size_t workspace_bytes, sd_stream_t stream);
+int sd_maxpool_bn_relu_bwd_apply(const float* dpool, const uint8_t* idx, const float* x, int B, int Hi, int Wi, int C, const float* mean,
+                                 const float* invstd, const float* gamma, const float* beta, const float* means, float* dx, sd_stream_t stream);
+int sd_maxpool_bn_relu_bwd_apply_bf16(const void* dpool_bf16, const uint8_t* idx, const void* x_bf16, int B, int Hi, int Wi, int C,
+                                      const float* mean, const float* invstd, const float* gamma, const float* beta, const float* means, float* dx,
+                                      sd_stream_t stream);
+int sd_maxpool_bn_relu_bwd_apply_bf16_dx16(const void* dpool_bf16, const uint8_t* idx, const void* x_bf16, int B, int Hi, int Wi, int C,
+                                           const float* mean, const float* invstd, const float* gamma, const float* beta, const float* means,
+                                           void* dx_bf16, sd_stream_t stream);
+
 /* ---- profiler ranges (no reference counterpart: SURVEY.md section 5 lists tracing as absent from the reference) ----
  * roctx ranges on the calling thread, for `rocprofv3 --marker-trace`.  Active only when the environment holds SDNET_ROCTX=1 at the
  * first call AND a marker library (librocprofiler-sdk-roctx / libroctx64) can be dlopen'ed; otherwise every call is a no-op returning 0.

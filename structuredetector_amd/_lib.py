@@ -160,6 +160,28 @@ _SIGNATURES = {
     "sd_bn_bwd_apply": (c_int, [c_vp, c_vp, c_vp, c_int, c_i64, c_int] + [c_vp] * 8),
     "sd_bn_finalize_scratch_rows": (c_int, [c_int]),
     "sd_bn_finalize_stats": (c_int, [c_vp, c_int, c_i64, c_int, c_float, c_float, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    # synchronized BatchNorm: split statistics finish (phase 1 -> fp64 [S0, S1, n], phase 2 from the sums)
+    "sd_bn_stats_from_sums": (c_int, [c_vp, c_int, c_float, c_float, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "sd_bn_bwd_means_from_sums": (c_int, [c_vp, c_int, c_vp, c_vp]),
+    "sd_bn_stats_sums": (c_int, [c_vp, c_int, c_i64, c_int, c_vp, c_vp, c_vp]),
+    "sd_bn_bwd_sums": (c_int, [c_vp, c_int, c_i64, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_vp]),
+    "sd_bn_train_sums": (c_int, [c_vp, c_i64, c_int, c_vp, c_vp, c_size, c_vp]),
+    "sd_bn_train_sums_bf16": (c_int, [c_vp, c_i64, c_int, c_vp, c_vp, c_size, c_vp]),
+    "sd_conv2d_fwd_bn_stats_rows": (c_int, [c_vp, c_int]),
+    "sd_conv2d_fwd_bn_sums": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),
+    "sd_conv2d_fwd_bf16_bn_sums": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),
+    "sd_conv2d_stem_fwd_bn_sums": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),
+    "sd_conv2d_stem_fwd_bn_sums_bf16mm": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),
+    "sd_conv2d_stem_fwd_bn_sums_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),
+    "sd_conv2d_dgrad_bn_reduce_sums": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int] + [c_vp] * 6 + [c_int, c_vp, c_vp, c_size, c_vp]),
+    "sd_bn_bwd_reduce": (c_int, [c_vp, c_vp, c_vp, c_int, c_i64, c_int] + [c_vp] * 6 + [c_int, c_vp, c_vp, c_size, c_vp]),
+    "sd_bn_bwd_reduce_bf16": (c_int, [c_vp, c_vp, c_vp, c_int, c_i64, c_int] + [c_vp] * 6 + [c_int, c_vp, c_vp, c_size, c_vp]),
+    "sd_bn_bwd_apply_bf16": (c_int, [c_vp, c_vp, c_vp, c_int, c_i64, c_int] + [c_vp] * 8),
+    "sd_maxpool_bn_relu_bwd_reduce": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int] + [c_vp] * 6 + [c_int, c_vp, c_vp, c_size, c_vp]),
+    "sd_maxpool_bn_relu_bwd_reduce_bf16": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int] + [c_vp] * 6 + [c_int, c_vp, c_vp, c_size, c_vp]),
+    "sd_maxpool_bn_relu_bwd_apply": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int] + [c_vp] * 7),
+    "sd_maxpool_bn_relu_bwd_apply_bf16": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int] + [c_vp] * 7),
+    "sd_maxpool_bn_relu_bwd_apply_bf16_dx16": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int] + [c_vp] * 7),
     "sd_allreduce_unique_id": (c_int, [c_vp]),
     "sd_allreduce_init": (c_int, [c_vp, c_int, c_int, C.POINTER(c_vp)]),
     "sd_allreduce_run": (c_int, [c_vp, c_vp, c_i64, c_vp]),

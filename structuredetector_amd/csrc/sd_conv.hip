@@ -5432,6 +5432,21 @@ static int fwd_stat_rows(const sd_conv_desc* d, bool bf16 = false) {
     return (patch_tile_bn(t, BN, 0, bf16) || ((!bf16 || (g_igemm_big_bf16 && BN == 128)) && igemm_big_tiles(a, BN, 0))) ? cdiv(a.M, BMB) : cdiv(a.M, BM);
 }
 
+// finish of the statistics a conv epilogue left in partial rows: today's one-launch finalize, or (sums != nullptr, synchronized
+// BatchNorm) phase 1 of the split finish into the caller's fp64 [S0, S1, n]
+static int bn_stats_finish(const float* partial, int rows, int64_t M, int C, float eps, float momentum, float* running_mean, float* running_var,
+                           float* mean, float* invstd, double* sums, float* scratch, sd_stream_t stream) {
+    if (sums) return sd_bn_stats_sums(partial, rows, M, C, sums, scratch, stream);
+    return sd_bn_finalize_stats(partial, rows, M, C, eps, momentum, running_mean, running_var, mean, invstd, scratch, stream);
+}
+
+static bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
+
+int sd_conv2d_fwd_bn_stats_rows(const sd_conv_desc* d, int bf16) {
+    if (!d || d->B <= 0 || d->Cout % 64 || d->Cin % (bf16 ? 64 : 32)) return -1;
+    return fwd_stat_rows(d, bf16 != 0);
+}
+
 size_t sd_conv2d_fwd_bn_stats_workspace_bytes(const sd_conv_desc* d) {
     if (!d || d->Cin % 32 || d->Cout % 64) return 0;
     const int rows = fwd_stat_rows(d);
@@ -5440,19 +5455,21 @@ size_t sd_conv2d_fwd_bn_stats_workspace_bytes(const sd_conv_desc* d) {
     return std::max(fused, split);
 }
 
-int sd_conv2d_fwd_bn_stats(const float* x, const float* w, float* y, const sd_conv_desc* d, float eps, float momentum, float* running_mean,
-                           float* running_var, float* mean, float* invstd, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
-    if (int e = check_conv("sd_conv2d_fwd_bn_stats", d)) return e;
-    SD_REQUIRE(x && w && y && mean && invstd && workspace, SD_ERR_INVALID, "sd_conv2d_fwd_bn_stats: null pointer");
-    SD_REQUIRE(d->Cin % 32 == 0 && d->Cout % 64 == 0, SD_ERR_INVALID, "sd_conv2d_fwd_bn_stats: needs Cin %% 32 == 0 and Cout %% 64 == 0 (got %d, %d)",
-               d->Cin, d->Cout);
-    SD_REQUIRE(aligned16(x) && aligned16(w) && aligned16(y), SD_ERR_ALIGN, "sd_conv2d_fwd_bn_stats: pointers must be 16-byte aligned");
-    SD_REQUIRE(workspace_bytes >= sd_conv2d_fwd_bn_stats_workspace_bytes(d), SD_ERR_WORKSPACE, "sd_conv2d_fwd_bn_stats: workspace too small");
+static int conv_fwd_bn_stats_any(const char* what, const float* x, const float* w, float* y, const sd_conv_desc* d, float eps, float momentum,
+                                 float* running_mean, float* running_var, float* mean, float* invstd, double* sums, void* workspace,
+                                 size_t workspace_bytes, sd_stream_t stream) {
+    if (int e = check_conv(what, d)) return e;
+    SD_REQUIRE(x && w && y && (sums || (mean && invstd)) && workspace, SD_ERR_INVALID, "%s: null pointer", what);
+    SD_REQUIRE(d->Cin % 32 == 0 && d->Cout % 64 == 0, SD_ERR_INVALID, "%s: needs Cin %% 32 == 0 and Cout %% 64 == 0 (got %d, %d)",
+               what, d->Cin, d->Cout);
+    SD_REQUIRE(aligned16(x) && aligned16(w) && aligned16(y) && aligned8(sums), SD_ERR_ALIGN, "%s: pointers must be 16-byte aligned (sums: 8-byte)", what);
+    SD_REQUIRE(workspace_bytes >= sd_conv2d_fwd_bn_stats_workspace_bytes(d), SD_ERR_WORKSPACE, "%s: workspace too small", what);
     const int64_t M = (int64_t)d->B * d->Ho * d->Wo;
     const int rows = fwd_stat_rows(d);
     if (rows == 0) {        // small batch (split-K): plain conv, then the separate statistics pass
         const size_t cw = sd_conv2d_fwd_workspace_bytes(d);
         if (int e = sd_conv2d_fwd(x, w, y, d, nullptr, nullptr, nullptr, 0, 0, workspace, cw, stream)) return e;
+        if (sums) return sd_bn_train_sums(y, M, d->Cout, sums, (char*)workspace + cw, workspace_bytes - cw, stream);
         return sd_bn_train_stats(y, M, d->Cout, eps, momentum, running_mean, running_var, mean, invstd, (char*)workspace + cw,
                                  workspace_bytes - cw, stream);
     }
@@ -5460,8 +5477,23 @@ int sd_conv2d_fwd_bn_stats(const float* x, const float* w, float* y, const sd_co
     fill_fwd(a, d);
     a.x = x; a.w = w; a.y = y; a.stat = (float*)workspace;
     if (int e = launch_igemm(a, false, (hipStream_t)stream)) return e;
-    return sd_bn_finalize_stats((const float*)workspace, rows, M, d->Cout, eps, momentum, running_mean, running_var, mean, invstd,
-                                (float*)workspace + (size_t)rows * 2 * d->Cout, stream);
+    return bn_stats_finish((const float*)workspace, rows, M, d->Cout, eps, momentum, running_mean, running_var, mean, invstd, sums,
+                           (float*)workspace + (size_t)rows * 2 * d->Cout, stream);
+}
+
+int sd_conv2d_fwd_bn_stats(const float* x, const float* w, float* y, const sd_conv_desc* d, float eps, float momentum, float* running_mean,
+                           float* running_var, float* mean, float* invstd, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
+    return conv_fwd_bn_stats_any("sd_conv2d_fwd_bn_stats", x, w, y, d, eps, momentum, running_mean, running_var, mean, invstd, nullptr, workspace,
+                                 workspace_bytes, stream);
+}
+
+// synchronized BatchNorm: the same launch stopping after phase 1 of the statistics finish ([S0, S1, n] fp64 into `sums`; workspace as
+// sd_conv2d_fwd_bn_stats_workspace_bytes)
+int sd_conv2d_fwd_bn_sums(const float* x, const float* w, float* y, const sd_conv_desc* d, double* sums, void* workspace, size_t workspace_bytes,
+                          sd_stream_t stream) {
+    SD_REQUIRE(sums, SD_ERR_INVALID, "sd_conv2d_fwd_bn_sums: null pointer");
+    return conv_fwd_bn_stats_any("sd_conv2d_fwd_bn_sums", x, w, y, d, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr, sums, workspace, workspace_bytes,
+                                 stream);
 }
 
 static void stem_args(StemArgs& a, const sd_conv_desc* d) {
@@ -5567,19 +5599,21 @@ size_t sd_conv2d_fwd_bf16_bn_stats_workspace_bytes(const sd_conv_desc* d) {
     return std::max(std::max(fused, split), (size_t)256);
 }
 
-int sd_conv2d_fwd_bf16_bn_stats(const void* x, const void* w, void* y, const sd_conv_desc* d, float eps, float momentum, float* running_mean,
-                                float* running_var, float* mean, float* invstd, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
-    if (int e = check_conv("sd_conv2d_fwd_bf16_bn_stats", d)) return e;
-    SD_REQUIRE(x && w && y && mean && invstd && workspace, SD_ERR_INVALID, "sd_conv2d_fwd_bf16_bn_stats: null pointer");
-    SD_REQUIRE(d->Cin % 64 == 0 && d->Cout % 64 == 0, SD_ERR_INVALID, "sd_conv2d_fwd_bf16_bn_stats: needs Cin %% 64 == 0 and Cout %% 64 == 0 (got %d, %d)",
-               d->Cin, d->Cout);
-    SD_REQUIRE(aligned16(x) && aligned16(w) && aligned16(y), SD_ERR_ALIGN, "sd_conv2d_fwd_bf16_bn_stats: pointers must be 16-byte aligned");
-    SD_REQUIRE(workspace_bytes >= sd_conv2d_fwd_bf16_bn_stats_workspace_bytes(d), SD_ERR_WORKSPACE, "sd_conv2d_fwd_bf16_bn_stats: workspace too small");
+static int conv_fwd_bf16_bn_stats_any(const char* what, const void* x, const void* w, void* y, const sd_conv_desc* d, float eps, float momentum,
+                                      float* running_mean, float* running_var, float* mean, float* invstd, double* sums, void* workspace,
+                                      size_t workspace_bytes, sd_stream_t stream) {
+    if (int e = check_conv(what, d)) return e;
+    SD_REQUIRE(x && w && y && (sums || (mean && invstd)) && workspace, SD_ERR_INVALID, "%s: null pointer", what);
+    SD_REQUIRE(d->Cin % 64 == 0 && d->Cout % 64 == 0, SD_ERR_INVALID, "%s: needs Cin %% 64 == 0 and Cout %% 64 == 0 (got %d, %d)",
+               what, d->Cin, d->Cout);
+    SD_REQUIRE(aligned16(x) && aligned16(w) && aligned16(y) && aligned8(sums), SD_ERR_ALIGN, "%s: pointers must be 16-byte aligned (sums: 8-byte)", what);
+    SD_REQUIRE(workspace_bytes >= sd_conv2d_fwd_bf16_bn_stats_workspace_bytes(d), SD_ERR_WORKSPACE, "%s: workspace too small", what);
     const int rows = fwd_stat_rows(d, true);
     const int64_t M = (int64_t)d->B * d->Ho * d->Wo;
     if (rows == 0) {        // small batch (split-K): plain conv, then the separate statistics pass over the bf16 output
         const size_t cw = sd_conv2d_fwd_bf16_workspace_bytes(d);
         if (int e = sd_conv2d_fwd_bf16(x, w, y, d, nullptr, nullptr, nullptr, 0, 0, workspace, cw, stream)) return e;
+        if (sums) return sd_bn_train_sums_bf16(y, M, d->Cout, sums, (char*)workspace + cw, workspace_bytes - cw, stream);
         return sd_bn_train_stats_bf16(y, M, d->Cout, eps, momentum, running_mean, running_var, mean, invstd, (char*)workspace + cw,
                                       workspace_bytes - cw, stream);
     }
@@ -5589,8 +5623,22 @@ int sd_conv2d_fwd_bf16_bn_stats(const void* x, const void* w, void* y, const sd_
     a.mul = d->stride; a.div = 1; a.off = -d->pad; a.rsign = 1;
     a.M = d->B * d->Ho * d->Wo; a.kchunks = d->Cin / 64; a.nk = d->R * d->S * a.kchunks; a.splits = 1;
     if (int e = launch_igemm(a, false, (hipStream_t)stream, true)) return e;
-    return sd_bn_finalize_stats((const float*)workspace, rows, M, d->Cout, eps, momentum, running_mean, running_var, mean, invstd,
-                                (float*)workspace + (size_t)rows * 2 * d->Cout, stream);
+    return bn_stats_finish((const float*)workspace, rows, M, d->Cout, eps, momentum, running_mean, running_var, mean, invstd, sums,
+                           (float*)workspace + (size_t)rows * 2 * d->Cout, stream);
+}
+
+int sd_conv2d_fwd_bf16_bn_stats(const void* x, const void* w, void* y, const sd_conv_desc* d, float eps, float momentum, float* running_mean,
+                                float* running_var, float* mean, float* invstd, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
+    return conv_fwd_bf16_bn_stats_any("sd_conv2d_fwd_bf16_bn_stats", x, w, y, d, eps, momentum, running_mean, running_var, mean, invstd, nullptr,
+                                      workspace, workspace_bytes, stream);
+}
+
+// synchronized BatchNorm: sd_conv2d_fwd_bf16_bn_stats stopping after phase 1 of the statistics finish ([S0, S1, n] fp64 into `sums`)
+int sd_conv2d_fwd_bf16_bn_sums(const void* x, const void* w, void* y, const sd_conv_desc* d, double* sums, void* workspace, size_t workspace_bytes,
+                               sd_stream_t stream) {
+    SD_REQUIRE(sums, SD_ERR_INVALID, "sd_conv2d_fwd_bf16_bn_sums: null pointer");
+    return conv_fwd_bf16_bn_stats_any("sd_conv2d_fwd_bf16_bn_sums", x, w, y, d, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr, sums, workspace,
+                                      workspace_bytes, stream);
 }
 
 // data-gradient with bf16 dy / transposed weights / dx (+ bf16 residual: res_mode 0 none, 1 same size, 2 half-size map added at even pixels)
@@ -5651,13 +5699,14 @@ size_t sd_conv2d_stem_fwd_bn_stats_workspace_bytes(const sd_conv_desc* d) {
     return wt + (size_t)(a.ntiles + sd_bn_finalize_scratch_rows(a.ntiles)) * 2 * 64 * sizeof(float);
 }
 
-int sd_conv2d_stem_fwd_bn_stats(const float* x_nchw, const float* w, float* y, const sd_conv_desc* d, float eps, float momentum,
-                                float* running_mean, float* running_var, float* mean, float* invstd, void* workspace, size_t workspace_bytes,
-                                sd_stream_t stream) {
-    if (int e = check_conv("sd_conv2d_stem_fwd_bn_stats", d)) return e;
-    SD_REQUIRE(x_nchw && w && y && mean && invstd && workspace, SD_ERR_INVALID, "sd_conv2d_stem_fwd_bn_stats: null pointer");
-    SD_REQUIRE(stem_is_7x7s2(d), SD_ERR_INVALID, "sd_conv2d_stem_fwd_bn_stats: the stem is a 7x7 / stride 2 / pad 3 conv, 3 -> 64 channels");
-    SD_REQUIRE(workspace_bytes >= sd_conv2d_stem_fwd_bn_stats_workspace_bytes(d), SD_ERR_WORKSPACE, "sd_conv2d_stem_fwd_bn_stats: workspace too small");
+static int stem_fwd_bn_stats_f32(const char* what, const float* x_nchw, const float* w, float* y, const sd_conv_desc* d, float eps, float momentum,
+                                 float* running_mean, float* running_var, float* mean, float* invstd, double* sums, void* workspace,
+                                 size_t workspace_bytes, sd_stream_t stream) {
+    if (int e = check_conv(what, d)) return e;
+    SD_REQUIRE(x_nchw && w && y && (sums || (mean && invstd)) && workspace, SD_ERR_INVALID, "%s: null pointer", what);
+    SD_REQUIRE(aligned8(sums), SD_ERR_ALIGN, "%s: the fp64 sums must be 8-byte aligned", what);
+    SD_REQUIRE(stem_is_7x7s2(d), SD_ERR_INVALID, "%s: the stem is a 7x7 / stride 2 / pad 3 conv, 3 -> 64 channels", what);
+    SD_REQUIRE(workspace_bytes >= sd_conv2d_stem_fwd_bn_stats_workspace_bytes(d), SD_ERR_WORKSPACE, "%s: workspace too small", what);
     hipStream_t st = (hipStream_t)stream;
     float* wt = (float*)workspace;
     float* partial = (float*)((char*)workspace + align_up((size_t)STEM_K * 64 * sizeof(float), 256));
@@ -5672,26 +5721,27 @@ int sd_conv2d_stem_fwd_bn_stats(const float* x_nchw, const float* w, float* y, c
         (void)attr_once;
         hipLaunchKernelGGL(k_stem_fwd<false>, dim3(std::min(a.ntiles, 512)), dim3(256), lds, st, a);
         SD_LAUNCH_CHECK();
-        return sd_bn_finalize_stats(partial, a.ntiles, (int64_t)d->B * d->Ho * d->Wo, 64, eps, momentum, running_mean, running_var, mean, invstd,
+        return bn_stats_finish(partial, a.ntiles, (int64_t)d->B * d->Ho * d->Wo, 64, eps, momentum, running_mean, running_var, mean, invstd, sums,
                                     partial + (size_t)a.ntiles * 128, stream);
     }
     // k_stem_fwd_dma: one partial statistics row per BLOCK (the workspace holds one per tile: more than enough)
     const int blocks = std::min(a.ntiles, std::max(1, g_stem_fwd_blocks));
     hipLaunchKernelGGL(k_stem_fwd_dma<true>, dim3(blocks), dim3(256), (size_t)STEM_KPAD * 64 * sizeof(float), st, a);
     SD_LAUNCH_CHECK();
-    return sd_bn_finalize_stats(partial, blocks, (int64_t)d->B * d->Ho * d->Wo, 64, eps, momentum, running_mean, running_var, mean, invstd,
+    return bn_stats_finish(partial, blocks, (int64_t)d->B * d->Ho * d->Wo, 64, eps, momentum, running_mean, running_var, mean, invstd, sums,
                                 partial + (size_t)a.ntiles * 128, stream);
 }
 
 // the same stem launch with the product on the bf16 MFMA (image patch and weights rounded to bf16 on the way into the operands, fp32
 // accumulation, fp32 output + statistics): the mixed-precision training step (under autocast the reference's conv1 runs in bf16 too)
-int sd_conv2d_stem_fwd_bn_stats_bf16mm(const float* x_nchw, const float* w, float* y, const sd_conv_desc* d, float eps, float momentum,
-                                       float* running_mean, float* running_var, float* mean, float* invstd, void* workspace,
-                                       size_t workspace_bytes, sd_stream_t stream) {
-    if (int e = check_conv("sd_conv2d_stem_fwd_bn_stats_bf16mm", d)) return e;
-    SD_REQUIRE(x_nchw && w && y && mean && invstd && workspace, SD_ERR_INVALID, "sd_conv2d_stem_fwd_bn_stats_bf16mm: null pointer");
-    SD_REQUIRE(stem_is_7x7s2(d), SD_ERR_INVALID, "sd_conv2d_stem_fwd_bn_stats_bf16mm: the stem is a 7x7 / stride 2 / pad 3 conv, 3 -> 64 channels");
-    SD_REQUIRE(workspace_bytes >= sd_conv2d_stem_fwd_bn_stats_workspace_bytes(d), SD_ERR_WORKSPACE, "sd_conv2d_stem_fwd_bn_stats_bf16mm: workspace too small");
+static int stem_fwd_bn_stats_bf16mm(const char* what, const float* x_nchw, const float* w, float* y, const sd_conv_desc* d, float eps, float momentum,
+                                    float* running_mean, float* running_var, float* mean, float* invstd, double* sums, void* workspace,
+                                    size_t workspace_bytes, sd_stream_t stream) {
+    if (int e = check_conv(what, d)) return e;
+    SD_REQUIRE(x_nchw && w && y && (sums || (mean && invstd)) && workspace, SD_ERR_INVALID, "%s: null pointer", what);
+    SD_REQUIRE(aligned8(sums), SD_ERR_ALIGN, "%s: the fp64 sums must be 8-byte aligned", what);
+    SD_REQUIRE(stem_is_7x7s2(d), SD_ERR_INVALID, "%s: the stem is a 7x7 / stride 2 / pad 3 conv, 3 -> 64 channels", what);
+    SD_REQUIRE(workspace_bytes >= sd_conv2d_stem_fwd_bn_stats_workspace_bytes(d), SD_ERR_WORKSPACE, "%s: workspace too small", what);
     hipStream_t st = (hipStream_t)stream;
     float* partial = (float*)((char*)workspace + align_up((size_t)STEM_K * 64 * sizeof(float), 256));
     StemArgs a{};
@@ -5702,18 +5752,19 @@ int sd_conv2d_stem_fwd_bn_stats_bf16mm(const float* x_nchw, const float* w, floa
     (void)attr_once;
     hipLaunchKernelGGL(k_stem_fwd<true>, dim3(std::min(a.ntiles, 512)), dim3(256), lds, st, a);
     SD_LAUNCH_CHECK();
-    return sd_bn_finalize_stats(partial, a.ntiles, (int64_t)d->B * d->Ho * d->Wo, 64, eps, momentum, running_mean, running_var, mean, invstd,
+    return bn_stats_finish(partial, a.ntiles, (int64_t)d->B * d->Ho * d->Wo, 64, eps, momentum, running_mean, running_var, mean, invstd, sums,
                                 partial + (size_t)a.ntiles * 128, stream);
 }
 
 // the same with a bf16 NHWC output (mixed-precision training: the conv output is read twice more by the stem tail, 1 GB in fp32 at bs=64)
-int sd_conv2d_stem_fwd_bn_stats_bf16(const float* x_nchw, const float* w, void* y_bf16, const sd_conv_desc* d, float eps, float momentum,
-                                     float* running_mean, float* running_var, float* mean, float* invstd, void* workspace,
-                                     size_t workspace_bytes, sd_stream_t stream) {
-    if (int e = check_conv("sd_conv2d_stem_fwd_bn_stats_bf16", d)) return e;
-    SD_REQUIRE(x_nchw && w && y_bf16 && mean && invstd && workspace, SD_ERR_INVALID, "sd_conv2d_stem_fwd_bn_stats_bf16: null pointer");
-    SD_REQUIRE(stem_is_7x7s2(d), SD_ERR_INVALID, "sd_conv2d_stem_fwd_bn_stats_bf16: the stem is a 7x7 / stride 2 / pad 3 conv, 3 -> 64 channels");
-    SD_REQUIRE(workspace_bytes >= sd_conv2d_stem_fwd_bn_stats_workspace_bytes(d), SD_ERR_WORKSPACE, "sd_conv2d_stem_fwd_bn_stats_bf16: workspace too small");
+static int stem_fwd_bn_stats_bf16(const char* what, const float* x_nchw, const float* w, void* y_bf16, const sd_conv_desc* d, float eps, float momentum,
+                                  float* running_mean, float* running_var, float* mean, float* invstd, double* sums, void* workspace,
+                                  size_t workspace_bytes, sd_stream_t stream) {
+    if (int e = check_conv(what, d)) return e;
+    SD_REQUIRE(x_nchw && w && y_bf16 && (sums || (mean && invstd)) && workspace, SD_ERR_INVALID, "%s: null pointer", what);
+    SD_REQUIRE(aligned8(sums), SD_ERR_ALIGN, "%s: the fp64 sums must be 8-byte aligned", what);
+    SD_REQUIRE(stem_is_7x7s2(d), SD_ERR_INVALID, "%s: the stem is a 7x7 / stride 2 / pad 3 conv, 3 -> 64 channels", what);
+    SD_REQUIRE(workspace_bytes >= sd_conv2d_stem_fwd_bn_stats_workspace_bytes(d), SD_ERR_WORKSPACE, "%s: workspace too small", what);
     hipStream_t st = (hipStream_t)stream;
     float* partial = (float*)((char*)workspace + align_up((size_t)STEM_K * 64 * sizeof(float), 256));
     StemArgs a{};
@@ -5728,7 +5779,7 @@ int sd_conv2d_stem_fwd_bn_stats_bf16(const float* x_nchw, const float* w, void* 
         (void)attr_ring;
         hipLaunchKernelGGL(k_stem_fwd_bf16_ring, dim3(blocks), dim3(512), SF_LDS_BYTES, st, a);
         SD_LAUNCH_CHECK();
-        return sd_bn_finalize_stats(partial, blocks, (int64_t)d->B * d->Ho * d->Wo, 64, eps, momentum, running_mean, running_var, mean, invstd,
+        return bn_stats_finish(partial, blocks, (int64_t)d->B * d->Ho * d->Wo, 64, eps, momentum, running_mean, running_var, mean, invstd, sums,
                                     partial + (size_t)a.ntiles * 128, stream);
     }
     const size_t lds = STEM_FWD_LDS_BYTES;
@@ -5736,8 +5787,51 @@ int sd_conv2d_stem_fwd_bn_stats_bf16(const float* x_nchw, const float* w, void* 
     (void)attr_once;
     hipLaunchKernelGGL(k_stem_fwd<true>, dim3(std::min(a.ntiles, 512)), dim3(256), lds, st, a);
     SD_LAUNCH_CHECK();
-    return sd_bn_finalize_stats(partial, a.ntiles, (int64_t)d->B * d->Ho * d->Wo, 64, eps, momentum, running_mean, running_var, mean, invstd,
+    return bn_stats_finish(partial, a.ntiles, (int64_t)d->B * d->Ho * d->Wo, 64, eps, momentum, running_mean, running_var, mean, invstd, sums,
                                 partial + (size_t)a.ntiles * 128, stream);
+}
+
+int sd_conv2d_stem_fwd_bn_stats(const float* x_nchw, const float* w, float* y, const sd_conv_desc* d, float eps, float momentum,
+                                float* running_mean, float* running_var, float* mean, float* invstd, void* workspace, size_t workspace_bytes,
+                                sd_stream_t stream) {
+    return stem_fwd_bn_stats_f32("sd_conv2d_stem_fwd_bn_stats", x_nchw, w, y, d, eps, momentum, running_mean, running_var, mean, invstd, nullptr,
+                                 workspace, workspace_bytes, stream);
+}
+
+int sd_conv2d_stem_fwd_bn_stats_bf16mm(const float* x_nchw, const float* w, float* y, const sd_conv_desc* d, float eps, float momentum,
+                                       float* running_mean, float* running_var, float* mean, float* invstd, void* workspace,
+                                       size_t workspace_bytes, sd_stream_t stream) {
+    return stem_fwd_bn_stats_bf16mm("sd_conv2d_stem_fwd_bn_stats_bf16mm", x_nchw, w, y, d, eps, momentum, running_mean, running_var, mean, invstd,
+                                    nullptr, workspace, workspace_bytes, stream);
+}
+
+int sd_conv2d_stem_fwd_bn_stats_bf16(const float* x_nchw, const float* w, void* y_bf16, const sd_conv_desc* d, float eps, float momentum,
+                                     float* running_mean, float* running_var, float* mean, float* invstd, void* workspace,
+                                     size_t workspace_bytes, sd_stream_t stream) {
+    return stem_fwd_bn_stats_bf16("sd_conv2d_stem_fwd_bn_stats_bf16", x_nchw, w, y_bf16, d, eps, momentum, running_mean, running_var, mean, invstd,
+                                  nullptr, workspace, workspace_bytes, stream);
+}
+
+// synchronized BatchNorm: the three stem launches stopping after phase 1 of the statistics finish ([S0, S1, n] fp64 into `sums`)
+int sd_conv2d_stem_fwd_bn_sums(const float* x_nchw, const float* w, float* y, const sd_conv_desc* d, double* sums, void* workspace,
+                               size_t workspace_bytes, sd_stream_t stream) {
+    SD_REQUIRE(sums, SD_ERR_INVALID, "sd_conv2d_stem_fwd_bn_sums: null pointer");
+    return stem_fwd_bn_stats_f32("sd_conv2d_stem_fwd_bn_sums", x_nchw, w, y, d, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr, sums, workspace,
+                                 workspace_bytes, stream);
+}
+
+int sd_conv2d_stem_fwd_bn_sums_bf16mm(const float* x_nchw, const float* w, float* y, const sd_conv_desc* d, double* sums, void* workspace,
+                                      size_t workspace_bytes, sd_stream_t stream) {
+    SD_REQUIRE(sums, SD_ERR_INVALID, "sd_conv2d_stem_fwd_bn_sums_bf16mm: null pointer");
+    return stem_fwd_bn_stats_bf16mm("sd_conv2d_stem_fwd_bn_sums_bf16mm", x_nchw, w, y, d, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr, sums,
+                                    workspace, workspace_bytes, stream);
+}
+
+int sd_conv2d_stem_fwd_bn_sums_bf16(const float* x_nchw, const float* w, void* y_bf16, const sd_conv_desc* d, double* sums, void* workspace,
+                                    size_t workspace_bytes, sd_stream_t stream) {
+    SD_REQUIRE(sums, SD_ERR_INVALID, "sd_conv2d_stem_fwd_bn_sums_bf16: null pointer");
+    return stem_fwd_bn_stats_bf16("sd_conv2d_stem_fwd_bn_sums_bf16", x_nchw, w, y_bf16, d, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr, sums,
+                                  workspace, workspace_bytes, stream);
 }
 
 int sd_conv2d_dgrad_half_res(const float* dy, const float* w_t, float* dx, const sd_conv_desc* d, const float* residual_half,
@@ -6086,19 +6180,19 @@ size_t sd_conv2d_dgrad_bn_reduce_workspace_bytes(const sd_conv_desc* d) {
     return (size_t)(rows + sd_bn_finalize_scratch_rows(rows)) * 2 * d->Cin * sizeof(float);
 }
 
-int sd_conv2d_dgrad_bn_reduce(const float* dy, const float* w_t, float* dx, const sd_conv_desc* d, const float* residual, const float* bn_x,
-                              const float* bn_y, int relu, const float* mean, const float* invstd, const float* gamma, const float* beta,
-                              float* dgamma, float* dbeta, int accumulate, float* means_out, void* workspace, size_t workspace_bytes,
-                              sd_stream_t stream) {
-    if (int e = check_conv("sd_conv2d_dgrad_bn_reduce", d)) return e;
-    SD_REQUIRE(dy && w_t && dx && bn_x && mean && invstd && gamma && dgamma && dbeta && means_out && workspace, SD_ERR_INVALID,
-               "sd_conv2d_dgrad_bn_reduce: null pointer");
+static int conv_dgrad_bn_reduce_any(const char* what, const float* dy, const float* w_t, float* dx, const sd_conv_desc* d, const float* residual,
+                                    const float* bn_x, const float* bn_y, int relu, const float* mean, const float* invstd, const float* gamma,
+                                    const float* beta, float* dgamma, float* dbeta, int accumulate, float* means_out, double* sums, void* workspace,
+                                    size_t workspace_bytes, sd_stream_t stream) {
+    if (int e = check_conv(what, d)) return e;
+    SD_REQUIRE(dy && w_t && dx && bn_x && mean && invstd && gamma && dgamma && dbeta && (means_out || sums) && workspace, SD_ERR_INVALID,
+               "%s: null pointer", what);
     SD_REQUIRE(relu >= 0 && relu <= 3 && ((relu != 1 && relu != 3) || bn_y) && (relu != 2 || beta), SD_ERR_INVALID,
-               "sd_conv2d_dgrad_bn_reduce: relu must be 0, 1 / 3 (need bn_y) or 2 (needs beta)");
-    SD_REQUIRE(d->Cout % 32 == 0 && d->Cin % 64 == 0, SD_ERR_INVALID, "sd_conv2d_dgrad_bn_reduce: needs Cout %% 32 == 0 and Cin %% 64 == 0");
+               "%s: relu must be 0, 1 / 3 (need bn_y) or 2 (needs beta)", what);
+    SD_REQUIRE(d->Cout % 32 == 0 && d->Cin % 64 == 0, SD_ERR_INVALID, "%s: needs Cout %% 32 == 0 and Cin %% 64 == 0", what);
     SD_REQUIRE(aligned16(dy) && aligned16(w_t) && aligned16(dx) && aligned16(residual) && aligned16(bn_x) && aligned16(bn_y) && aligned16(mean) &&
-               aligned16(invstd) && aligned16(gamma) && aligned16(beta), SD_ERR_ALIGN, "sd_conv2d_dgrad_bn_reduce: pointers must be 16-byte aligned");
-    SD_REQUIRE(workspace_bytes >= sd_conv2d_dgrad_bn_reduce_workspace_bytes(d), SD_ERR_WORKSPACE, "sd_conv2d_dgrad_bn_reduce: workspace too small");
+               aligned16(invstd) && aligned16(gamma) && aligned16(beta) && aligned8(sums), SD_ERR_ALIGN, "%s: pointers must be 16-byte aligned", what);
+    SD_REQUIRE(workspace_bytes >= sd_conv2d_dgrad_bn_reduce_workspace_bytes(d), SD_ERR_WORKSPACE, "%s: workspace too small", what);
     ConvArgs a{};
     fill_dgrad(a, d);
     a.x = dy; a.w = w_t; a.y = dx; a.res = residual;
@@ -6106,8 +6200,30 @@ int sd_conv2d_dgrad_bn_reduce(const float* dy, const float* w_t, float* dx, cons
     a.stat = (float*)workspace;
     if (int e = launch_igemm(a, false, (hipStream_t)stream)) return e;
     const int rows = dgrad_stat_rows(d);
+    if (sums) return sd_bn_bwd_sums((const float*)workspace, rows, (int64_t)a.M, d->Cin, dgamma, dbeta, accumulate, sums,
+                                    (float*)workspace + (size_t)rows * 2 * d->Cin, stream);
     return sd_bn_bwd_finalize((const float*)workspace, rows, (int64_t)a.M, d->Cin, dgamma, dbeta, accumulate, means_out,
                               (float*)workspace + (size_t)rows * 2 * d->Cin, stream);
+}
+
+int sd_conv2d_dgrad_bn_reduce(const float* dy, const float* w_t, float* dx, const sd_conv_desc* d, const float* residual, const float* bn_x,
+                              const float* bn_y, int relu, const float* mean, const float* invstd, const float* gamma, const float* beta,
+                              float* dgamma, float* dbeta, int accumulate, float* means_out, void* workspace, size_t workspace_bytes,
+                              sd_stream_t stream) {
+    SD_REQUIRE(means_out, SD_ERR_INVALID, "sd_conv2d_dgrad_bn_reduce: null pointer");
+    return conv_dgrad_bn_reduce_any("sd_conv2d_dgrad_bn_reduce", dy, w_t, dx, d, residual, bn_x, bn_y, relu, mean, invstd, gamma, beta, dgamma, dbeta,
+                                    accumulate, means_out, nullptr, workspace, workspace_bytes, stream);
+}
+
+// synchronized BatchNorm: the same launch stopping after phase 1 of the backward finish (dgamma / dbeta += local sums,
+// [sum g, sum g * xhat, n] fp64 into `sums`; the means then come from sd_bn_bwd_means_from_sums)
+int sd_conv2d_dgrad_bn_reduce_sums(const float* dy, const float* w_t, float* dx, const sd_conv_desc* d, const float* residual, const float* bn_x,
+                                   const float* bn_y, int relu, const float* mean, const float* invstd, const float* gamma, const float* beta,
+                                   float* dgamma, float* dbeta, int accumulate, double* sums, void* workspace, size_t workspace_bytes,
+                                   sd_stream_t stream) {
+    SD_REQUIRE(sums, SD_ERR_INVALID, "sd_conv2d_dgrad_bn_reduce_sums: null pointer");
+    return conv_dgrad_bn_reduce_any("sd_conv2d_dgrad_bn_reduce_sums", dy, w_t, dx, d, residual, bn_x, bn_y, relu, mean, invstd, gamma, beta, dgamma,
+                                    dbeta, accumulate, nullptr, sums, workspace, workspace_bytes, stream);
 }
 
 #ifdef SD_PP_TRACE

@@ -104,20 +104,17 @@ __global__ __launch_bounds__(256) void k_rows_fold(const float* __restrict__ in,
     }
 }
 
-// FIN 0: BN statistics -> mean, invstd, running stats (momentum, unbiased running var)
-// FIN 1: BN backward   -> dgamma (+=), dbeta (+=), and the two means needed by the apply pass
-// FIN 2: bias gradient -> out0 (+=)
-template <int FIN>
-__global__ __launch_bounds__(256) void k_col_finalize(const float* __restrict__ partial, int nblocks, int C, double M, float eps,
-                                                       float momentum, float* __restrict__ out0, float* __restrict__ out1,
-                                                       float* __restrict__ run_mean, float* __restrict__ run_var,
-                                                       float* __restrict__ aux0, float* __restrict__ aux1, int accumulate) {
+// The per-channel double sums of the partial rows, in ONE fixed order (8-way lane tree, xor-shuffle over the 16 lanes of a wave that
+// share a channel, the 4 waves through LDS): k_col_finalize and the split finish (k_col_sums + k_*_from_sums, synchronized BatchNorm)
+// both reduce through it, so a split finish with no exchange in between gives today's bits.  Returns false for the lanes that own no
+// result (every thread of the block must call it: it holds a barrier).
+__device__ __forceinline__ bool col_pair_sums(const float* __restrict__ partial, int nblocks, int C, double (&r0)[4][4], double (&r1)[4][4],
+                                              double& s0, double& s1) {
     // 4 channels x 64 lanes over the partial rows per workgroup, 8 loads in flight per lane (the pass is latency-bound: up to
     // 8192 partial rows of a few KB each); fixed order -> deterministic
-    __shared__ double r0[4][4], r1[4][4];
     const int lc = threadIdx.x & 3, lr = threadIdx.x >> 2;
     const int c = blockIdx.x * 4 + lc;
-    double s0 = 0.0, s1 = 0.0;
+    s0 = 0.0; s1 = 0.0;
     if (c < C) {
         double t0[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t1[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         // eight rows in flight per lane and trip, the last trip's missing rows read row 0 and add nothing (no serial tail: with 128-512 partial
@@ -145,19 +142,40 @@ __global__ __launch_bounds__(256) void k_col_finalize(const float* __restrict__ 
     for (int o = 4; o < 64; o <<= 1) { s0 += __shfl_xor(s0, o); s1 += __shfl_xor(s1, o); }
     if ((threadIdx.x & 63) < 4) { r0[threadIdx.x >> 6][lc] = s0; r1[threadIdx.x >> 6][lc] = s1; }
     __syncthreads();
-    if (lr != 0 || c >= C) return;
+    if (lr != 0 || c >= C) return false;
     s0 = (r0[0][lc] + r0[1][lc]) + (r0[2][lc] + r0[3][lc]);
     s1 = (r1[0][lc] + r1[1][lc]) + (r1[2][lc] + r1[3][lc]);
+    return true;
+}
+
+// BN statistics of channel c from its sums over M elements: mean, invstd, running stats (momentum, unbiased running var)
+__device__ __forceinline__ void bn_stats_tail(double s0, double s1, double M, float eps, float momentum, int c, float* __restrict__ mean_out,
+                                              float* __restrict__ invstd_out, float* __restrict__ run_mean, float* __restrict__ run_var) {
+    const double mean = s0 / M;
+    const double var = fmax(s1 / M - mean * mean, 0.0);             // biased variance (normalisation)
+    mean_out[c] = (float)mean;
+    invstd_out[c] = (float)(1.0 / sqrt(var + (double)eps));
+    if (run_mean) {
+        const double unb = M > 1.0 ? var * M / (M - 1.0) : var;     // torch: running_var uses the unbiased estimate
+        run_mean[c] = (float)((1.0 - momentum) * run_mean[c] + momentum * mean);
+        run_var[c] = (float)((1.0 - momentum) * run_var[c] + momentum * unb);
+    }
+}
+
+// FIN 0: BN statistics -> mean, invstd, running stats (momentum, unbiased running var)
+// FIN 1: BN backward   -> dgamma (+=), dbeta (+=), and the two means needed by the apply pass
+// FIN 2: bias gradient -> out0 (+=)
+template <int FIN>
+__global__ __launch_bounds__(256) void k_col_finalize(const float* __restrict__ partial, int nblocks, int C, double M, float eps,
+                                                       float momentum, float* __restrict__ out0, float* __restrict__ out1,
+                                                       float* __restrict__ run_mean, float* __restrict__ run_var,
+                                                       float* __restrict__ aux0, float* __restrict__ aux1, int accumulate) {
+    __shared__ double r0[4][4], r1[4][4];
+    double s0, s1;
+    if (!col_pair_sums(partial, nblocks, C, r0, r1, s0, s1)) return;
+    const int c = blockIdx.x * 4 + (threadIdx.x & 3);
     if (FIN == 0) {
-        const double mean = s0 / M;
-        const double var = fmax(s1 / M - mean * mean, 0.0);             // biased variance (normalisation)
-        out0[c] = (float)mean;
-        out1[c] = (float)(1.0 / sqrt(var + (double)eps));
-        if (run_mean) {
-            const double unb = M > 1.0 ? var * M / (M - 1.0) : var;     // torch: running_var uses the unbiased estimate
-            run_mean[c] = (float)((1.0 - momentum) * run_mean[c] + momentum * mean);
-            run_var[c] = (float)((1.0 - momentum) * run_var[c] + momentum * unb);
-        }
+        bn_stats_tail(s0, s1, M, eps, momentum, c, out0, out1, run_mean, run_var);
     } else if (FIN == 1) {
         out0[c] = (accumulate ? out0[c] : 0.f) + (float)s1;             // dgamma = sum g * xhat
         out1[c] = (accumulate ? out1[c] : 0.f) + (float)s0;             // dbeta  = sum g
@@ -166,6 +184,43 @@ __global__ __launch_bounds__(256) void k_col_finalize(const float* __restrict__ 
     } else {
         out0[c] = (accumulate ? out0[c] : 0.f) + (float)s0;
     }
+}
+
+// Split finish, phase 1 (synchronized BatchNorm): the per-channel sums of k_col_finalize, in its order, into
+// sums = [S0 (C), S1 (C), n] (fp64; n = M, written by channel 0's lane).  FIN 1 also writes dgamma / dbeta from these LOCAL sums.
+template <int FIN>
+__global__ __launch_bounds__(256) void k_col_sums(const float* __restrict__ partial, int nblocks, int C, double M, float* __restrict__ dgamma,
+                                                   float* __restrict__ dbeta, int accumulate, double* __restrict__ sums) {
+    __shared__ double r0[4][4], r1[4][4];
+    double s0, s1;
+    if (!col_pair_sums(partial, nblocks, C, r0, r1, s0, s1)) return;
+    const int c = blockIdx.x * 4 + (threadIdx.x & 3);
+    sums[c] = s0;
+    sums[C + c] = s1;
+    if (c == 0) sums[2 * C] = M;
+    if (FIN == 1) {
+        dgamma[c] = (accumulate ? dgamma[c] : 0.f) + (float)s1;
+        dbeta[c] = (accumulate ? dbeta[c] : 0.f) + (float)s0;
+    }
+}
+
+// Split finish, phase 2 of the forward: mean, invstd and the running statistics from (possibly all-reduced) sums -- the tail of
+// k_col_finalize<0> with n = sums[2C]
+__global__ __launch_bounds__(256) void k_bn_stats_from_sums(const double* __restrict__ sums, int C, float eps, float momentum,
+                                                             float* __restrict__ mean, float* __restrict__ invstd,
+                                                             float* __restrict__ run_mean, float* __restrict__ run_var) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    bn_stats_tail(sums[c], sums[C + c], sums[2 * C], eps, momentum, c, mean, invstd, run_mean, run_var);
+}
+
+// Split finish, phase 2 of the backward: means = [mean(g) (C), mean(g * xhat) (C)] for the apply pass, n = sums[2C]
+__global__ __launch_bounds__(256) void k_bn_bwd_means_from_sums(const double* __restrict__ sums, int C, float* __restrict__ means) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    const double M = sums[2 * C];
+    means[c] = (float)(sums[c] / M);
+    means[C + c] = (float)(sums[C + c] / M);
 }
 
 // y = [relu]( (x - mean) * invstd * gamma + beta [+ res] )
@@ -1525,40 +1580,119 @@ static int check_mc(const char* what, int64_t M, int C) {
     return 0;
 }
 
-int sd_bn_train_stats(const float* x, int64_t M, int C, float eps, float momentum, float* running_mean, float* running_var,
-                      float* mean, float* invstd, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
-    if (int e = check_mc("sd_bn_train_stats", M, C)) return e;
-    SD_REQUIRE(x && mean && invstd && workspace, SD_ERR_INVALID, "sd_bn_train_stats: null pointer");
-    SD_REQUIRE(workspace_bytes >= sd_col_reduce_workspace_bytes(M, C), SD_ERR_WORKSPACE, "sd_bn_train_stats: workspace too small");
+}  // extern "C"
+
+// the forward finish of partial rows [rows][2][C]: k_col_finalize<0> (one launch), or with `sums` phase 1 of the split finish only
+// (k_col_sums<0>: [S0, S1, n] in fp64; mean / invstd / running statistics then come from sd_bn_stats_from_sums)
+static void bn_stats_finish(const float* fin, int rows, int64_t M, int C, float eps, float momentum, float* running_mean, float* running_var,
+                            float* mean, float* invstd, double* sums, hipStream_t st) {
+    if (sums)
+        hipLaunchKernelGGL(k_col_sums<0>, dim3(cdiv(C, 4)), dim3(256), 0, st, fin, rows, C, (double)M, (float*)nullptr, (float*)nullptr, 0, sums);
+    else
+        hipLaunchKernelGGL(k_col_finalize<0>, dim3(cdiv(C, 4)), dim3(256), 0, st, fin, rows, C, (double)M, eps, momentum,
+                           mean, invstd, running_mean, running_var, (float*)nullptr, (float*)nullptr, 0);
+}
+
+// the backward finish: k_col_finalize<1> (dgamma / dbeta and the two means), or with `sums` phase 1 only (dgamma / dbeta from the local
+// sums + [S0, S1, n]; the means then come from sd_bn_bwd_means_from_sums)
+static void bn_bwd_finish(const float* fin, int rows, int64_t M, int C, float* dgamma, float* dbeta, int accumulate, float* mg, float* mgx,
+                          double* sums, hipStream_t st) {
+    if (sums)
+        hipLaunchKernelGGL(k_col_sums<1>, dim3(cdiv(C, 4)), dim3(256), 0, st, fin, rows, C, (double)M, dgamma, dbeta, accumulate, sums);
+    else
+        hipLaunchKernelGGL(k_col_finalize<1>, dim3(cdiv(C, 4)), dim3(256), 0, st, fin, rows, C, (double)M, 0.f, 0.f, dgamma, dbeta,
+                           (float*)nullptr, (float*)nullptr, mg, mgx, accumulate);
+}
+
+static bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
+
+template <typename T>
+static int bn_train_stats_any(const char* what, const T* x, int64_t M, int C, float eps, float momentum, float* running_mean, float* running_var,
+                              float* mean, float* invstd, double* sums, void* workspace, size_t workspace_bytes, hipStream_t st) {
+    if (int e = check_mc(what, M, C)) return e;
+    SD_REQUIRE(x && (sums || (mean && invstd)) && workspace, SD_ERR_INVALID, "%s: null pointer", what);
+    SD_REQUIRE(aligned8(sums), SD_ERR_ALIGN, "%s: the fp64 sums must be 8-byte aligned", what);
+    SD_REQUIRE(workspace_bytes >= sd_col_reduce_workspace_bytes(M, C), SD_ERR_WORKSPACE, "%s: workspace too small", what);
     const int rpb = red_rows(M), nb = cdiv(M, rpb);
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_col_reduce<0>, dim3(nb), dim3(256), 0, st, x, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr,
+    hipLaunchKernelGGL((k_col_reduce<0, T>), dim3(nb), dim3(256), 0, st, x, (const T*)nullptr, (const T*)nullptr, (const float*)nullptr,
                        (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, 0, M, C, (float*)workspace, rpb);
     SD_LAUNCH_CHECK();
     int rows = nb;
     const float* fin = fold_partials((const float*)workspace, rows, C, (float*)workspace + ((size_t)nb + 1) * 2 * C, st);
-    hipLaunchKernelGGL(k_col_finalize<0>, dim3(cdiv(C, 4)), dim3(256), 0, st, fin, rows, C, (double)M, eps, momentum,
-                       mean, invstd, running_mean, running_var, (float*)nullptr, (float*)nullptr, 0);
+    bn_stats_finish(fin, rows, M, C, eps, momentum, running_mean, running_var, mean, invstd, sums, st);
     SD_LAUNCH_CHECK();
     return 0;
 }
 
-int sd_bn_train_stats_bf16(const void* x, int64_t M, int C, float eps, float momentum, float* running_mean, float* running_var,
-                           float* mean, float* invstd, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
-    if (int e = check_mc("sd_bn_train_stats_bf16", M, C)) return e;
-    SD_REQUIRE(x && mean && invstd && workspace, SD_ERR_INVALID, "sd_bn_train_stats_bf16: null pointer");
-    SD_REQUIRE(workspace_bytes >= sd_col_reduce_workspace_bytes(M, C), SD_ERR_WORKSPACE, "sd_bn_train_stats_bf16: workspace too small");
+// the reduction half of sd_bn_bwd[_bf16]: partial rows of (sum g, sum g * xhat) into the workspace, then the finish (the two means at
+// workspace + nb * 2C, or with `sums` phase 1 into the caller's fp64 buffer).  `wide`: the bf16 x8 kernels (the caller's choice, so
+// that the fused and the split forms reduce in the same order).
+template <typename T>
+static int bn_bwd_reduce_any(const char* what, const T* dy, const T* x, const void* y, int relu, int64_t M, int C, const float* mean,
+                             const float* invstd, const float* gamma, const float* beta, float* dgamma, float* dbeta, int accumulate,
+                             double* sums, bool wide, void* workspace, size_t workspace_bytes, hipStream_t st) {
+    if (int e = check_mc(what, M, C)) return e;
+    SD_REQUIRE(relu >= 0 && relu <= 3, SD_ERR_INVALID, "%s: relu must be 0 (none), 1 (mask from y), 2 (mask recomputed from x) or 3 (mask bytes)", what);
+    SD_REQUIRE(dy && x && mean && invstd && gamma && dgamma && dbeta && workspace && ((relu != 1 && relu != 3) || y) && (relu != 2 || beta),
+               SD_ERR_INVALID, "%s: null pointer", what);
+    SD_REQUIRE(aligned8(sums), SD_ERR_ALIGN, "%s: the fp64 sums must be 8-byte aligned", what);
+    SD_REQUIRE(workspace_bytes >= sd_col_reduce_workspace_bytes(M, C), SD_ERR_WORKSPACE, "%s: workspace too small", what);
     const int rpb = red_rows(M), nb = cdiv(M, rpb);
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL((k_col_reduce<0, uint16_t>), dim3(nb), dim3(256), 0, st, (const uint16_t*)x, (const uint16_t*)nullptr, (const uint16_t*)nullptr,
-                       (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, 0, M, C, (float*)workspace, rpb);
+    float* partial = (float*)workspace;
+    float* mg = partial + (size_t)nb * 2 * C;
+    float* mgx = mg + C;
+    if constexpr (std::is_same<T, uint16_t>::value) {
+        if (wide) hipLaunchKernelGGL(k_col_reduce_bwd_bf16x8, dim3(nb), dim3(256), 0, st, dy, x, (const uint8_t*)y, mean, invstd, gamma, beta, relu,
+                                     M, C, partial, rpb);
+        else hipLaunchKernelGGL((k_col_reduce<1, uint16_t>), dim3(nb), dim3(256), 0, st, dy, x, (const uint16_t*)y, mean, invstd, gamma, beta,
+                                relu, M, C, partial, rpb);
+    } else {
+        hipLaunchKernelGGL(k_col_reduce<1>, dim3(nb), dim3(256), 0, st, dy, x, (const float*)y, mean, invstd, gamma, beta, relu, M, C, partial, rpb);
+    }
     SD_LAUNCH_CHECK();
     int rows = nb;
-    const float* fin = fold_partials((const float*)workspace, rows, C, (float*)workspace + ((size_t)nb + 1) * 2 * C, st);
-    hipLaunchKernelGGL(k_col_finalize<0>, dim3(cdiv(C, 4)), dim3(256), 0, st, fin, rows, C, (double)M, eps, momentum,
-                       mean, invstd, running_mean, running_var, (float*)nullptr, (float*)nullptr, 0);
+    const float* fin = fold_partials(partial, rows, C, mgx + C, st);
+    bn_bwd_finish(fin, rows, M, C, dgamma, dbeta, accumulate, mg, mgx, sums, st);
     SD_LAUNCH_CHECK();
     return 0;
+}
+
+// the apply pass of sd_bn_bwd_bf16 (means = [mean(g) (C), mean(g * xhat) (C)])
+static int bn_bwd_apply_bf16(const void* dy, const void* x, const void* y, int relu, int64_t M, int C, const float* mean, const float* invstd,
+                             const float* gamma, const float* beta, const float* means, void* dx, void* g_out, bool wide, hipStream_t st) {
+    const int64_t n4 = M * C / 4;
+    if (wide) hipLaunchKernelGGL(k_bn_bwd_apply_bf16x8, dim3(ew_grid(n4 / 2)), dim3(256), 0, st, (const uint16_t*)dy, (const uint16_t*)x, (const uint8_t*)y,
+                                 relu, n4 / 2, C, mean, invstd, gamma, beta, means, means + C, (uint16_t*)dx, (uint16_t*)g_out);
+    else hipLaunchKernelGGL(k_bn_bwd_apply<uint16_t>, dim3(ew_grid(n4)), dim3(256), 0, st, (const uint16_t*)dy, (const uint16_t*)x, (const uint16_t*)y,
+                            relu, n4, C, mean, invstd, gamma, beta, means, means + C, (uint16_t*)dx, (uint16_t*)g_out);
+    SD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" {
+
+int sd_bn_train_stats(const float* x, int64_t M, int C, float eps, float momentum, float* running_mean, float* running_var,
+                      float* mean, float* invstd, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
+    return bn_train_stats_any<float>("sd_bn_train_stats", x, M, C, eps, momentum, running_mean, running_var, mean, invstd, nullptr, workspace,
+                                     workspace_bytes, (hipStream_t)stream);
+}
+
+int sd_bn_train_stats_bf16(const void* x, int64_t M, int C, float eps, float momentum, float* running_mean, float* running_var,
+                           float* mean, float* invstd, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
+    return bn_train_stats_any<uint16_t>("sd_bn_train_stats_bf16", (const uint16_t*)x, M, C, eps, momentum, running_mean, running_var, mean, invstd,
+                                        nullptr, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int sd_bn_train_sums(const float* x, int64_t M, int C, double* sums, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
+    SD_REQUIRE(sums, SD_ERR_INVALID, "sd_bn_train_sums: null sums");
+    return bn_train_stats_any<float>("sd_bn_train_sums", x, M, C, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr, sums, workspace, workspace_bytes,
+                                     (hipStream_t)stream);
+}
+
+int sd_bn_train_sums_bf16(const void* x, int64_t M, int C, double* sums, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
+    SD_REQUIRE(sums, SD_ERR_INVALID, "sd_bn_train_sums_bf16: null sums");
+    return bn_train_stats_any<uint16_t>("sd_bn_train_sums_bf16", (const uint16_t*)x, M, C, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr, sums,
+                                        workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 // rows of `scratch` the two-level finish of `rows` partial rows needs (0 = single level)
@@ -1573,8 +1707,34 @@ int sd_bn_finalize_stats(const float* partial, int rows, int64_t M, int C, float
     // the rows are first folded in coalesced slabs (full 2C-float rows per block), then the few slab sums are finished.
     partial = fold_partials(partial, rows, C, scratch, st);
     SD_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_col_finalize<0>, dim3(cdiv(C, 4)), dim3(256), 0, st, partial, rows, C, (double)M, eps, momentum,
-                       mean, invstd, running_mean, running_var, (float*)nullptr, (float*)nullptr, 0);
+    bn_stats_finish(partial, rows, M, C, eps, momentum, running_mean, running_var, mean, invstd, nullptr, st);
+    SD_LAUNCH_CHECK();
+    return 0;
+}
+
+// synchronized BatchNorm, forward: phase 1 of sd_bn_finalize_stats (same partial rows, same scratch, same summation order) into
+// sums = [S0 = sum x (C), S1 = sum x^2 (C), n = M] in fp64; after any all-reduce of `sums`, sd_bn_stats_from_sums finishes
+int sd_bn_stats_sums(const float* partial, int rows, int64_t M, int C, double* sums, float* scratch, sd_stream_t stream) {
+    if (int e = check_mc("sd_bn_stats_sums", M, C)) return e;
+    SD_REQUIRE(partial && sums && rows > 0, SD_ERR_INVALID, "sd_bn_stats_sums: bad arguments (null pointer or rows <= 0)");
+    SD_REQUIRE(aligned8(sums), SD_ERR_ALIGN, "sd_bn_stats_sums: the fp64 sums must be 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    partial = fold_partials(partial, rows, C, scratch, st);
+    SD_LAUNCH_CHECK();
+    bn_stats_finish(partial, rows, M, C, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr, sums, st);
+    SD_LAUNCH_CHECK();
+    return 0;
+}
+
+// phase 2: mean, invstd (biased variance) and the running statistics (unbiased with n = sums[2C]) from [S0, S1, n]
+int sd_bn_stats_from_sums(const double* sums, int C, float eps, float momentum, float* running_mean, float* running_var, float* mean,
+                          float* invstd, sd_stream_t stream) {
+    if (int e = check_mc("sd_bn_stats_from_sums", 1, C)) return e;
+    SD_REQUIRE(sums && mean && invstd && (running_mean != nullptr) == (running_var != nullptr), SD_ERR_INVALID,
+               "sd_bn_stats_from_sums: null pointer (running_mean and running_var are both given or both null)");
+    SD_REQUIRE(aligned8(sums), SD_ERR_ALIGN, "sd_bn_stats_from_sums: the fp64 sums must be 8-byte aligned");
+    hipLaunchKernelGGL(k_bn_stats_from_sums, dim3(cdiv(C, 256)), dim3(256), 0, (hipStream_t)stream, sums, C, eps, momentum, mean, invstd,
+                       running_mean, running_var);
     SD_LAUNCH_CHECK();
     return 0;
 }
@@ -1601,28 +1761,26 @@ int sd_bn_fold(const float* gamma, const float* beta, const float* running_mean,
 int sd_bn_bwd(const float* dy, const float* x, const float* y, int relu, int64_t M, int C, const float* mean, const float* invstd,
               const float* gamma, const float* beta, float* dx, float* g_out, float* dgamma, float* dbeta, int accumulate, void* workspace,
               size_t workspace_bytes, sd_stream_t stream) {
-    if (int e = check_mc("sd_bn_bwd", M, C)) return e;
-    SD_REQUIRE(relu >= 0 && relu <= 3, SD_ERR_INVALID, "sd_bn_bwd: relu must be 0 (none), 1 (mask from y), 2 (mask recomputed from x) or 3 (mask bytes)");
-    SD_REQUIRE(dy && x && mean && invstd && gamma && dx && dgamma && dbeta && workspace && ((relu != 1 && relu != 3) || y) && (relu != 2 || beta),
-               SD_ERR_INVALID, "sd_bn_bwd: null pointer");
-    SD_REQUIRE(workspace_bytes >= sd_col_reduce_workspace_bytes(M, C), SD_ERR_WORKSPACE, "sd_bn_bwd: workspace too small");
-    const int rpb = red_rows(M), nb = cdiv(M, rpb);
-    hipStream_t st = (hipStream_t)stream;
-    float* partial = (float*)workspace;
-    float* mg = partial + (size_t)nb * 2 * C;
-    float* mgx = mg + C;
-    hipLaunchKernelGGL(k_col_reduce<1>, dim3(nb), dim3(256), 0, st, dy, x, y, mean, invstd, gamma, beta, relu, M, C, partial, rpb);
-    SD_LAUNCH_CHECK();
-    int rows = nb;
-    const float* fin = fold_partials(partial, rows, C, mgx + C, st);
-    hipLaunchKernelGGL(k_col_finalize<1>, dim3(cdiv(C, 4)), dim3(256), 0, st, fin, rows, C, (double)M, 0.f, 0.f, dgamma, dbeta,
-                       (float*)nullptr, (float*)nullptr, mg, mgx, accumulate);
-    SD_LAUNCH_CHECK();
+    SD_REQUIRE(dx, SD_ERR_INVALID, "sd_bn_bwd: null pointer");
+    if (int e = bn_bwd_reduce_any<float>("sd_bn_bwd", dy, x, y, relu, M, C, mean, invstd, gamma, beta, dgamma, dbeta, accumulate, nullptr, false,
+                                         workspace, workspace_bytes, (hipStream_t)stream)) return e;
+    const int nb = cdiv(M, red_rows(M));
+    const float* mg = (const float*)workspace + (size_t)nb * 2 * C;
     const int64_t n4 = M * C / 4;
-    hipLaunchKernelGGL(k_bn_bwd_apply<float>, dim3(ew_grid(n4)), dim3(256), 0, st, dy, x, y, relu, n4, C, mean, invstd, gamma, beta,
-                       (const float*)mg, (const float*)mgx, dx, g_out);
+    hipLaunchKernelGGL(k_bn_bwd_apply<float>, dim3(ew_grid(n4)), dim3(256), 0, (hipStream_t)stream, dy, x, y, relu, n4, C, mean, invstd, gamma, beta,
+                       mg, mg + C, dx, g_out);
     SD_LAUNCH_CHECK();
     return 0;
+}
+
+// synchronized BatchNorm, backward: the reduce half of sd_bn_bwd alone -- dgamma / dbeta (+=) from the local sums and
+// sums = [sum g (C), sum g * xhat (C), n = M] in fp64; after any all-reduce of `sums`, sd_bn_bwd_means_from_sums + sd_bn_bwd_apply
+int sd_bn_bwd_reduce(const float* dy, const float* x, const float* y, int relu, int64_t M, int C, const float* mean, const float* invstd,
+                     const float* gamma, const float* beta, float* dgamma, float* dbeta, int accumulate, double* sums, void* workspace,
+                     size_t workspace_bytes, sd_stream_t stream) {
+    SD_REQUIRE(sums, SD_ERR_INVALID, "sd_bn_bwd_reduce: null pointer");
+    return bn_bwd_reduce_any<float>("sd_bn_bwd_reduce", dy, x, y, relu, M, C, mean, invstd, gamma, beta, dgamma, dbeta, accumulate, sums, false,
+                                    workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 // second half of the reduction of sd_bn_bwd on caller-provided partial rows [rows][2][C] (sum g, sum g * xhat):
@@ -1634,8 +1792,32 @@ int sd_bn_bwd_finalize(const float* partial, int rows, int64_t M, int C, float* 
     hipStream_t st = (hipStream_t)stream;
     const float* fin = fold_partials(partial, rows, C, scratch, st);
     SD_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_col_finalize<1>, dim3(cdiv(C, 4)), dim3(256), 0, st, fin, rows, C, (double)M, 0.f, 0.f, dgamma, dbeta,
-                       (float*)nullptr, (float*)nullptr, means_out, means_out + C, accumulate);
+    bn_bwd_finish(fin, rows, M, C, dgamma, dbeta, accumulate, means_out, means_out + C, nullptr, st);
+    SD_LAUNCH_CHECK();
+    return 0;
+}
+
+// synchronized BatchNorm, backward: phase 1 of sd_bn_bwd_finalize -- dgamma / dbeta (+=) from the local sums and
+// sums = [sum g (C), sum g * xhat (C), n = M] in fp64 (same partial rows, scratch and summation order)
+int sd_bn_bwd_sums(const float* partial, int rows, int64_t M, int C, float* dgamma, float* dbeta, int accumulate, double* sums, float* scratch,
+                   sd_stream_t stream) {
+    if (int e = check_mc("sd_bn_bwd_sums", M, C)) return e;
+    SD_REQUIRE(partial && dgamma && dbeta && sums && rows > 0, SD_ERR_INVALID, "sd_bn_bwd_sums: bad arguments (null pointer or rows <= 0)");
+    SD_REQUIRE(aligned8(sums), SD_ERR_ALIGN, "sd_bn_bwd_sums: the fp64 sums must be 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const float* fin = fold_partials(partial, rows, C, scratch, st);
+    SD_LAUNCH_CHECK();
+    bn_bwd_finish(fin, rows, M, C, dgamma, dbeta, accumulate, nullptr, nullptr, sums, st);
+    SD_LAUNCH_CHECK();
+    return 0;
+}
+
+// phase 2: means_out = [S0 / n (C), S1 / n (C)] with n = sums[2C], what sd_bn_bwd_apply[_bf16] / sd_maxpool_bn_relu_bwd_apply* consume
+int sd_bn_bwd_means_from_sums(const double* sums, int C, float* means_out, sd_stream_t stream) {
+    if (int e = check_mc("sd_bn_bwd_means_from_sums", 1, C)) return e;
+    SD_REQUIRE(sums && means_out, SD_ERR_INVALID, "sd_bn_bwd_means_from_sums: null pointer");
+    SD_REQUIRE(aligned8(sums), SD_ERR_ALIGN, "sd_bn_bwd_means_from_sums: the fp64 sums must be 8-byte aligned");
+    hipLaunchKernelGGL(k_bn_bwd_means_from_sums, dim3(cdiv(C, 256)), dim3(256), 0, (hipStream_t)stream, sums, C, means_out);
     SD_LAUNCH_CHECK();
     return 0;
 }
@@ -1722,38 +1904,68 @@ int sd_bn_relu_maxpool_fwd_bf16(const void* x_bf16, int B, int Hi, int Wi, int C
 }
 
 extern "C++" {
-template <typename XT, typename PT, typename DT = float>
-static int maxpool_bn_relu_bwd_any(const char* what, const PT* dpool, const uint8_t* idx, const XT* x, int B, int Hi, int Wi, int C, const float* mean,
-                                   const float* invstd, const float* gamma, const float* beta, DT* dx, float* dgamma, float* dbeta, int accumulate,
-                                   void* workspace, size_t workspace_bytes, sd_stream_t stream) {
+// The stem tail's backward (max-pool -> ReLU -> BatchNorm): reduce, finish, apply.  Split forms for synchronized BatchNorm:
+// `sums` -> stop after phase 1 (dgamma / dbeta from the local sums, [S0, S1, n] in fp64); `means` -> the apply pass alone.
+template <typename XT, typename PT>
+static int maxpool_bn_relu_bwd_reduce_any(const char* what, const PT* dpool, const uint8_t* idx, const XT* x, int B, int Hi, int Wi, int C,
+                                          const float* mean, const float* invstd, const float* gamma, const float* beta, float* dgamma,
+                                          float* dbeta, int accumulate, double* sums, void* workspace, size_t workspace_bytes, hipStream_t st) {
     const int64_t M = (int64_t)B * Hi * Wi;
     if (int e = check_mc(what, M, C)) return e;
-    SD_REQUIRE(dpool && idx && x && mean && invstd && gamma && beta && dx && dgamma && dbeta && workspace, SD_ERR_INVALID, "%s: null pointer", what);
+    SD_REQUIRE(dpool && idx && x && mean && invstd && gamma && beta && dgamma && dbeta && workspace, SD_ERR_INVALID, "%s: null pointer", what);
+    SD_REQUIRE(aligned8(sums), SD_ERR_ALIGN, "%s: the fp64 sums must be 8-byte aligned", what);
     SD_REQUIRE(workspace_bytes >= sd_col_reduce_workspace_bytes(M, C), SD_ERR_WORKSPACE, "%s: workspace too small", what);
     const int Ho = (Hi + 2 - 3) / 2 + 1, Wo = (Wi + 2 - 3) / 2 + 1;
     const int nb = cdiv(M, RED_ROWS_PER_BLOCK);
-    hipStream_t st = (hipStream_t)stream;
     float* partial = (float*)workspace;
     float* mg = partial + (size_t)nb * 2 * C;
     float* mgx = mg + C;
     const bool quad = Hi % 2 == 0 && Wi % 2 == 0;        // even maps: 2x2 quads share their four windows
-    constexpr bool F32 = std::is_same<XT, float>::value && std::is_same<PT, float>::value && std::is_same<DT, float>::value;
+    constexpr bool F32 = std::is_same<XT, float>::value && std::is_same<PT, float>::value;
     SD_REQUIRE(quad || F32, SD_ERR_INVALID, "%s: the bf16 form needs even Hi, Wi", what);
     if (quad) hipLaunchKernelGGL((k_pool_bn_bwd_reduce_quad<XT, PT>), dim3(nb), dim3(256), 0, st, dpool, idx, x, mean, invstd, gamma, beta, Hi, Wi, Ho, Wo, M / 4, C, partial);
     else if constexpr (F32) hipLaunchKernelGGL(k_pool_bn_bwd_reduce, dim3(nb), dim3(256), 0, st, dpool, idx, x, mean, invstd, gamma, beta, Hi, Wi, Ho, Wo, M, C, partial);
     SD_LAUNCH_CHECK();
     int rows = nb;
     const float* fin = fold_partials(partial, rows, C, mgx + C, st);
-    hipLaunchKernelGGL(k_col_finalize<1>, dim3(cdiv(C, 4)), dim3(256), 0, st, fin, rows, C, (double)M, 0.f, 0.f, dgamma, dbeta,
-                       (float*)nullptr, (float*)nullptr, mg, mgx, accumulate);
-    SD_LAUNCH_CHECK();
-    const int64_t n4 = M * C / 4;
-    if (quad) hipLaunchKernelGGL((k_pool_bn_bwd_apply_quad<XT, PT, DT>), dim3(cdiv(n4 / 4, 256)), dim3(256), 0, st, dpool, idx, x, mean, invstd, gamma, beta,
-                                 (const float*)mg, (const float*)mgx, Hi, Wi, Ho, Wo, n4 / 4, C, dx);
-    else if constexpr (F32) hipLaunchKernelGGL(k_pool_bn_bwd_apply, dim3(cdiv(n4, 256)), dim3(256), 0, st, dpool, idx, x, mean, invstd, gamma, beta, (const float*)mg,
-                                               (const float*)mgx, Hi, Wi, Ho, Wo, n4, C, dx);
+    bn_bwd_finish(fin, rows, M, C, dgamma, dbeta, accumulate, mg, mgx, sums, st);
     SD_LAUNCH_CHECK();
     return 0;
+}
+
+template <typename XT, typename PT, typename DT>
+static int maxpool_bn_relu_bwd_apply_any(const char* what, const PT* dpool, const uint8_t* idx, const XT* x, int B, int Hi, int Wi, int C,
+                                         const float* mean, const float* invstd, const float* gamma, const float* beta, const float* means, DT* dx,
+                                         hipStream_t st) {
+    const int64_t M = (int64_t)B * Hi * Wi;
+    if (int e = check_mc(what, M, C)) return e;
+    SD_REQUIRE(dpool && idx && x && mean && invstd && gamma && beta && means && dx, SD_ERR_INVALID, "%s: null pointer", what);
+    const int Ho = (Hi + 2 - 3) / 2 + 1, Wo = (Wi + 2 - 3) / 2 + 1;
+    const bool quad = Hi % 2 == 0 && Wi % 2 == 0;
+    constexpr bool F32 = std::is_same<XT, float>::value && std::is_same<PT, float>::value && std::is_same<DT, float>::value;
+    SD_REQUIRE(quad || F32, SD_ERR_INVALID, "%s: the bf16 form needs even Hi, Wi", what);
+    const int64_t n4 = M * C / 4;
+    if (quad) hipLaunchKernelGGL((k_pool_bn_bwd_apply_quad<XT, PT, DT>), dim3(cdiv(n4 / 4, 256)), dim3(256), 0, st, dpool, idx, x, mean, invstd, gamma, beta,
+                                 means, means + C, Hi, Wi, Ho, Wo, n4 / 4, C, dx);
+    else if constexpr (F32) hipLaunchKernelGGL(k_pool_bn_bwd_apply, dim3(cdiv(n4, 256)), dim3(256), 0, st, dpool, idx, x, mean, invstd, gamma, beta, means,
+                                               means + C, Hi, Wi, Ho, Wo, n4, C, dx);
+    SD_LAUNCH_CHECK();
+    return 0;
+}
+
+template <typename XT, typename PT, typename DT = float>
+static int maxpool_bn_relu_bwd_any(const char* what, const PT* dpool, const uint8_t* idx, const XT* x, int B, int Hi, int Wi, int C, const float* mean,
+                                   const float* invstd, const float* gamma, const float* beta, DT* dx, float* dgamma, float* dbeta, int accumulate,
+                                   void* workspace, size_t workspace_bytes, sd_stream_t stream) {
+    SD_REQUIRE(dx, SD_ERR_INVALID, "%s: null pointer", what);
+    constexpr bool F32 = std::is_same<XT, float>::value && std::is_same<PT, float>::value && std::is_same<DT, float>::value;
+    SD_REQUIRE((Hi % 2 == 0 && Wi % 2 == 0) || F32, SD_ERR_INVALID, "%s: the bf16 form needs even Hi, Wi", what);
+    hipStream_t st = (hipStream_t)stream;
+    if (int e = maxpool_bn_relu_bwd_reduce_any<XT, PT>(what, dpool, idx, x, B, Hi, Wi, C, mean, invstd, gamma, beta, dgamma, dbeta, accumulate, nullptr,
+                                                       workspace, workspace_bytes, st)) return e;
+    const int nb = cdiv((int64_t)B * Hi * Wi, RED_ROWS_PER_BLOCK);
+    const float* mg = (const float*)workspace + (size_t)nb * 2 * C;
+    return maxpool_bn_relu_bwd_apply_any<XT, PT, DT>(what, dpool, idx, x, B, Hi, Wi, C, mean, invstd, gamma, beta, mg, dx, st);
 }
 }  // extern "C++"
 
@@ -1778,6 +1990,47 @@ int sd_maxpool_bn_relu_bwd_bf16_dx16(const void* dpool_bf16, const uint8_t* idx,
     return maxpool_bn_relu_bwd_any<uint16_t, uint16_t, uint16_t>("sd_maxpool_bn_relu_bwd_bf16_dx16", (const uint16_t*)dpool_bf16, idx, (const uint16_t*)x_bf16,
                                                                  B, Hi, Wi, C, mean, invstd, gamma, beta, (uint16_t*)dx_bf16, dgamma, dbeta, accumulate,
                                                                  workspace, workspace_bytes, stream);
+}
+
+// synchronized BatchNorm: the reduce half of sd_maxpool_bn_relu_bwd (dgamma / dbeta += local sums; [S0, S1, n] fp64 into `sums`) ...
+int sd_maxpool_bn_relu_bwd_reduce(const float* dpool, const uint8_t* idx, const float* x, int B, int Hi, int Wi, int C, const float* mean,
+                                  const float* invstd, const float* gamma, const float* beta, float* dgamma, float* dbeta, int accumulate, double* sums,
+                                  void* workspace, size_t workspace_bytes, sd_stream_t stream) {
+    SD_REQUIRE(sums, SD_ERR_INVALID, "sd_maxpool_bn_relu_bwd_reduce: null pointer");
+    return maxpool_bn_relu_bwd_reduce_any<float, float>("sd_maxpool_bn_relu_bwd_reduce", dpool, idx, x, B, Hi, Wi, C, mean, invstd, gamma, beta, dgamma,
+                                                        dbeta, accumulate, sums, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+// ... of its two bf16 forms (bf16 pooled gradient and conv output) ...
+int sd_maxpool_bn_relu_bwd_reduce_bf16(const void* dpool_bf16, const uint8_t* idx, const void* x_bf16, int B, int Hi, int Wi, int C, const float* mean,
+                                       const float* invstd, const float* gamma, const float* beta, float* dgamma, float* dbeta, int accumulate,
+                                       double* sums, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
+    SD_REQUIRE(sums, SD_ERR_INVALID, "sd_maxpool_bn_relu_bwd_reduce_bf16: null pointer");
+    return maxpool_bn_relu_bwd_reduce_any<uint16_t, uint16_t>("sd_maxpool_bn_relu_bwd_reduce_bf16", (const uint16_t*)dpool_bf16, idx, (const uint16_t*)x_bf16,
+                                                              B, Hi, Wi, C, mean, invstd, gamma, beta, dgamma, dbeta, accumulate, sums, workspace,
+                                                              workspace_bytes, (hipStream_t)stream);
+}
+
+// ... and the apply pass from the two means of sd_bn_bwd_means_from_sums: fp32, bf16 in / fp32 dx, bf16 in / bf16 dx
+int sd_maxpool_bn_relu_bwd_apply(const float* dpool, const uint8_t* idx, const float* x, int B, int Hi, int Wi, int C, const float* mean,
+                                 const float* invstd, const float* gamma, const float* beta, const float* means, float* dx, sd_stream_t stream) {
+    return maxpool_bn_relu_bwd_apply_any<float, float, float>("sd_maxpool_bn_relu_bwd_apply", dpool, idx, x, B, Hi, Wi, C, mean, invstd, gamma, beta,
+                                                              means, dx, (hipStream_t)stream);
+}
+
+int sd_maxpool_bn_relu_bwd_apply_bf16(const void* dpool_bf16, const uint8_t* idx, const void* x_bf16, int B, int Hi, int Wi, int C, const float* mean,
+                                      const float* invstd, const float* gamma, const float* beta, const float* means, float* dx, sd_stream_t stream) {
+    return maxpool_bn_relu_bwd_apply_any<uint16_t, uint16_t, float>("sd_maxpool_bn_relu_bwd_apply_bf16", (const uint16_t*)dpool_bf16, idx,
+                                                                    (const uint16_t*)x_bf16, B, Hi, Wi, C, mean, invstd, gamma, beta, means, dx,
+                                                                    (hipStream_t)stream);
+}
+
+int sd_maxpool_bn_relu_bwd_apply_bf16_dx16(const void* dpool_bf16, const uint8_t* idx, const void* x_bf16, int B, int Hi, int Wi, int C,
+                                           const float* mean, const float* invstd, const float* gamma, const float* beta, const float* means,
+                                           void* dx_bf16, sd_stream_t stream) {
+    return maxpool_bn_relu_bwd_apply_any<uint16_t, uint16_t, uint16_t>("sd_maxpool_bn_relu_bwd_apply_bf16_dx16", (const uint16_t*)dpool_bf16, idx,
+                                                                       (const uint16_t*)x_bf16, B, Hi, Wi, C, mean, invstd, gamma, beta, means,
+                                                                       (uint16_t*)dx_bf16, (hipStream_t)stream);
 }
 
 int sd_upsample2x_bwd(const float* dy, const float* add, float* dx, int B, int H, int W, int C, sd_stream_t stream) {
@@ -1824,34 +2077,36 @@ int sd_bn_apply_bf16(const void* x, void* y, int64_t M, int C, const float* mean
 int sd_bn_bwd_bf16(const void* dy, const void* x, const void* y, int relu, int64_t M, int C, const float* mean, const float* invstd,
                    const float* gamma, const float* beta, void* dx, void* g_out, float* dgamma, float* dbeta, int accumulate, void* workspace,
                    size_t workspace_bytes, sd_stream_t stream) {
-    if (int e = check_mc("sd_bn_bwd_bf16", M, C)) return e;
-    SD_REQUIRE(relu >= 0 && relu <= 3, SD_ERR_INVALID, "sd_bn_bwd_bf16: relu must be 0 (none), 1 (mask from y), 2 (mask recomputed from x) or 3 (mask bytes)");
-    SD_REQUIRE(dy && x && mean && invstd && gamma && dx && dgamma && dbeta && workspace && ((relu != 1 && relu != 3) || y) && (relu != 2 || beta),
-               SD_ERR_INVALID, "sd_bn_bwd_bf16: null pointer");
-    SD_REQUIRE(workspace_bytes >= sd_col_reduce_workspace_bytes(M, C), SD_ERR_WORKSPACE, "sd_bn_bwd_bf16: workspace too small");
-    const int rpb = red_rows(M), nb = cdiv(M, rpb);
+    SD_REQUIRE(dx, SD_ERR_INVALID, "sd_bn_bwd_bf16: null pointer");
     hipStream_t st = (hipStream_t)stream;
-    float* partial = (float*)workspace;
-    float* mg = partial + (size_t)nb * 2 * C;
-    float* mgx = mg + C;
     const bool wide = C % 8 == 0 && relu != 1 && aligned16(dy) && aligned16(x) && aligned16(dx) && aligned16(g_out);
-    if (wide) hipLaunchKernelGGL(k_col_reduce_bwd_bf16x8, dim3(nb), dim3(256), 0, st, (const uint16_t*)dy, (const uint16_t*)x, (const uint8_t*)y, mean,
-                                 invstd, gamma, beta, relu, M, C, partial, rpb);
-    else hipLaunchKernelGGL((k_col_reduce<1, uint16_t>), dim3(nb), dim3(256), 0, st, (const uint16_t*)dy, (const uint16_t*)x, (const uint16_t*)y, mean,
-                            invstd, gamma, beta, relu, M, C, partial, rpb);
-    SD_LAUNCH_CHECK();
-    int rows = nb;
-    const float* fin = fold_partials(partial, rows, C, mgx + C, st);
-    hipLaunchKernelGGL(k_col_finalize<1>, dim3(cdiv(C, 4)), dim3(256), 0, st, fin, rows, C, (double)M, 0.f, 0.f, dgamma, dbeta,
-                       (float*)nullptr, (float*)nullptr, mg, mgx, accumulate);
-    SD_LAUNCH_CHECK();
-    const int64_t n4 = M * C / 4;
-    if (wide) hipLaunchKernelGGL(k_bn_bwd_apply_bf16x8, dim3(ew_grid(n4 / 2)), dim3(256), 0, st, (const uint16_t*)dy, (const uint16_t*)x, (const uint8_t*)y,
-                                 relu, n4 / 2, C, mean, invstd, gamma, beta, (const float*)mg, (const float*)mgx, (uint16_t*)dx, (uint16_t*)g_out);
-    else hipLaunchKernelGGL(k_bn_bwd_apply<uint16_t>, dim3(ew_grid(n4)), dim3(256), 0, st, (const uint16_t*)dy, (const uint16_t*)x, (const uint16_t*)y,
-                       relu, n4, C, mean, invstd, gamma, beta, (const float*)mg, (const float*)mgx, (uint16_t*)dx, (uint16_t*)g_out);
-    SD_LAUNCH_CHECK();
-    return 0;
+    if (int e = bn_bwd_reduce_any<uint16_t>("sd_bn_bwd_bf16", (const uint16_t*)dy, (const uint16_t*)x, y, relu, M, C, mean, invstd, gamma, beta,
+                                            dgamma, dbeta, accumulate, nullptr, wide, workspace, workspace_bytes, st)) return e;
+    const int nb = cdiv(M, red_rows(M));
+    const float* mg = (const float*)workspace + (size_t)nb * 2 * C;
+    return bn_bwd_apply_bf16(dy, x, y, relu, M, C, mean, invstd, gamma, beta, mg, dx, g_out, wide, st);
+}
+
+// the reduce half of sd_bn_bwd_bf16 (see sd_bn_bwd_reduce); the x8 kernel is chosen from dy / x alone (sd_bn_bwd_bf16 also asks for
+// 16-byte aligned dx / g_out: buffers from one allocator make the same choice in both forms)
+int sd_bn_bwd_reduce_bf16(const void* dy, const void* x, const void* y, int relu, int64_t M, int C, const float* mean, const float* invstd,
+                          const float* gamma, const float* beta, float* dgamma, float* dbeta, int accumulate, double* sums, void* workspace,
+                          size_t workspace_bytes, sd_stream_t stream) {
+    SD_REQUIRE(sums, SD_ERR_INVALID, "sd_bn_bwd_reduce_bf16: null pointer");
+    const bool wide = C % 8 == 0 && relu != 1 && aligned16(dy) && aligned16(x);
+    return bn_bwd_reduce_any<uint16_t>("sd_bn_bwd_reduce_bf16", (const uint16_t*)dy, (const uint16_t*)x, y, relu, M, C, mean, invstd, gamma, beta,
+                                       dgamma, dbeta, accumulate, sums, wide, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+// apply pass of sd_bn_bwd_bf16 with the two per-channel means known (sd_bn_bwd_means_from_sums)
+int sd_bn_bwd_apply_bf16(const void* dy, const void* x, const void* y, int relu, int64_t M, int C, const float* mean, const float* invstd,
+                         const float* gamma, const float* beta, const float* means, void* dx, void* g_out, sd_stream_t stream) {
+    if (int e = check_mc("sd_bn_bwd_apply_bf16", M, C)) return e;
+    SD_REQUIRE(relu >= 0 && relu <= 3, SD_ERR_INVALID, "sd_bn_bwd_apply_bf16: relu must be 0 (none), 1 (mask from y), 2 (mask recomputed from x) or 3 (mask bytes)");
+    SD_REQUIRE(dy && x && mean && invstd && gamma && means && dx && ((relu != 1 && relu != 3) || y) && (relu != 2 || beta), SD_ERR_INVALID,
+               "sd_bn_bwd_apply_bf16: null pointer");
+    const bool wide = C % 8 == 0 && relu != 1 && aligned16(dy) && aligned16(x) && aligned16(dx) && aligned16(g_out);
+    return bn_bwd_apply_bf16(dy, x, y, relu, M, C, mean, invstd, gamma, beta, means, dx, g_out, wide, (hipStream_t)stream);
 }
 
 int sd_col_sum_bf16(const void* x, int64_t M, int C, float* out, int accumulate, void* workspace, size_t workspace_bytes, sd_stream_t stream) {

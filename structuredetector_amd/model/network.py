@@ -241,14 +241,32 @@ class _Engine:
             "sd_conv2d_fwd"))
         return y, d
 
-    def conv_stats(self, x, conv, B, Hi, Wi, bn: BNParams, update_running=True, amp=False):
+    def conv_stats(self, x, conv, B, Hi, Wi, bn: BNParams, update_running=True, amp=False, sync=None):
         """Training forward of conv -> BatchNorm: the conv launch also produces the batch statistics of its output
-        (sd_conv2d_fwd_bn_stats), so bn_train(..., stats=...) only has the apply pass left."""
+        (sd_conv2d_fwd_bn_stats), so bn_train(..., stats=...) only has the apply pass left.  `sync` (a BnStatsExchange): the same
+        launch stops after the first half of the statistics finish, the fp64 sums are exchanged, the second half finishes."""
         d = _desc(B, Hi, Wi, conv)
         y = torch.empty((B, d.Ho, d.Wo, conv.cout), dtype=torch.bfloat16 if amp else torch.float32, device=x.device)
         mean = torch.empty(conv.cout, dtype=torch.float32, device=x.device)
         invstd = torch.empty_like(mean)
         flops = 2.0 * B * d.Ho * d.Wo * conv.cout * conv.cin * conv.k * conv.k
+        if sync is not None:
+            sums = sync.take(conv.cout)
+            if sync.log is not None:
+                fused = self.lib.sd_conv2d_fwd_bn_stats_rows(C.byref(d), int(amp)) > 0
+                sync.log.append(("sd_conv2d_fwd_bf16_bn_sums" if amp else "sd_conv2d_fwd_bn_sums") + ("" if fused else ":two-pass"))
+            if amp:
+                ws = self._ws(self.lib.sd_conv2d_fwd_bf16_bn_stats_workspace_bytes(C.byref(d)), x.device)
+                self._timed("bf16:" + self._kname(d, 16), flops, lambda: L.check(
+                    self.lib.sd_conv2d_fwd_bf16_bn_sums(x.data_ptr(), self._w16(conv).data_ptr(), y.data_ptr(), C.byref(d), sums.data_ptr(),
+                                                        ws.data_ptr(), ws.numel(), L.stream()), "sd_conv2d_fwd_bf16_bn_sums"))
+            else:
+                ws = self._ws(self.lib.sd_conv2d_fwd_bn_stats_workspace_bytes(C.byref(d)), x.device)
+                self._timed(self._kname(d, 0), flops, lambda: L.check(
+                    self.lib.sd_conv2d_fwd_bn_sums(x.data_ptr(), conv.weight.data_ptr(), y.data_ptr(), C.byref(d), sums.data_ptr(),
+                                                   ws.data_ptr(), ws.numel(), L.stream()), "sd_conv2d_fwd_bn_sums"))
+            self._stats_from_sums(sync, sums, bn, mean, invstd, update_running)
+            return y, d, (mean, invstd)
         if amp:
             ws = self._ws(self.lib.sd_conv2d_fwd_bf16_bn_stats_workspace_bytes(C.byref(d)), x.device)
             self._timed("bf16:" + self._kname(d, 16), flops, lambda: L.check(
@@ -267,10 +285,34 @@ class _Engine:
             "sd_conv2d_fwd_bn_stats"))
         return y, d, (mean, invstd)
 
-    def bn_train(self, x, bn: BNParams, res=None, relu=True, update_running=True, stats=None, want_mask=False):
+    def _stats_from_sums(self, sync, sums, bn: BNParams, mean, invstd, update_running=True):
+        """Synchronized BatchNorm, forward: all-reduce the layer's fp64 [S0, S1, n], then mean / invstd / running statistics from it."""
+        sync.reduce(sums)
+        L.check(self.lib.sd_bn_stats_from_sums(sums.data_ptr(), bn.c, BN_EPS, BN_MOMENTUM,
+                                               bn.running_mean.data_ptr() if update_running else 0,
+                                               bn.running_var.data_ptr() if update_running else 0,
+                                               mean.data_ptr(), invstd.data_ptr(), L.stream()), "sd_bn_stats_from_sums")
+
+    def _means_from_sums(self, sync, sums, Cc, device):
+        """Synchronized BatchNorm, backward: all-reduce [sum g, sum g * xhat, n], then the two per-channel means of the apply pass."""
+        sync.reduce(sums)
+        means = torch.empty(2 * Cc, dtype=torch.float32, device=device)
+        L.check(self.lib.sd_bn_bwd_means_from_sums(sums.data_ptr(), Cc, means.data_ptr(), L.stream()), "sd_bn_bwd_means_from_sums")
+        return means
+
+    def bn_train(self, x, bn: BNParams, res=None, relu=True, update_running=True, stats=None, want_mask=False, sync=None):
         Mrows, Cc = x.numel() // x.shape[-1], x.shape[-1]
         if stats is not None:
             mean, invstd = stats
+        elif sync is not None:
+            mean = torch.empty(Cc, dtype=torch.float32, device=x.device)
+            invstd = torch.empty_like(mean)
+            sums = sync.take(Cc)
+            sync.record("sd_bn_train_sums")
+            ws = self._ws(self.lib.sd_col_reduce_workspace_bytes(Mrows, Cc), x.device)
+            train_sums = self.lib.sd_bn_train_sums_bf16 if x.dtype == torch.bfloat16 else self.lib.sd_bn_train_sums
+            L.check(train_sums(x.data_ptr(), Mrows, Cc, sums.data_ptr(), ws.data_ptr(), ws.numel(), L.stream()), "sd_bn_train_sums")
+            self._stats_from_sums(sync, sums, bn, mean, invstd, update_running)
         else:
             mean = torch.empty(Cc, dtype=torch.float32, device=x.device)
             invstd = torch.empty_like(mean)
@@ -315,6 +357,10 @@ class _Engine:
         if H % 32 or W % 32:
             raise L.SdError("input height/width must be multiples of 32 (args.py:181-186)")
         rec = tape is not None
+        # synchronized BatchNorm (TrainStep(sync_bn=True)): every batch-statistics finish goes through the exchange on the tape
+        sx = tape.get("bn_sync") if (rec and training) else None
+        if sx is not None:
+            sx.begin("fwd")
 
         # stem: conv7x7/2 + BN + ReLU + maxpool3x3/2 (network.py:43-45)
         T.push("fwd:stem")
@@ -334,11 +380,20 @@ class _Engine:
             m0 = torch.empty(64, dtype=torch.float32, device=x.device)
             i0 = torch.empty_like(m0)
             ws = self._ws(lib.sd_conv2d_stem_fwd_bn_stats_workspace_bytes(C.byref(d0)), x.device)
-            stem_fwd = (lib.sd_conv2d_stem_fwd_bn_stats_bf16 if amp_stem else lib.sd_conv2d_stem_fwd_bn_stats_bf16mm) if amp \
-                else lib.sd_conv2d_stem_fwd_bn_stats                                                           # amp: product on the bf16 MFMA
-            L.check(stem_fwd(x.data_ptr(), stem.weight.data_ptr(), s0.data_ptr(), C.byref(d0), BN_EPS, BN_MOMENTUM,
-                             bn0.running_mean.data_ptr(), bn0.running_var.data_ptr(), m0.data_ptr(), i0.data_ptr(),
-                             ws.data_ptr(), ws.numel(), L.stream()), "sd_conv2d_stem_fwd_bn_stats")
+            if sx is None:
+                stem_fwd = (lib.sd_conv2d_stem_fwd_bn_stats_bf16 if amp_stem else lib.sd_conv2d_stem_fwd_bn_stats_bf16mm) if amp \
+                    else lib.sd_conv2d_stem_fwd_bn_stats                                                           # amp: product on the bf16 MFMA
+                L.check(stem_fwd(x.data_ptr(), stem.weight.data_ptr(), s0.data_ptr(), C.byref(d0), BN_EPS, BN_MOMENTUM,
+                                 bn0.running_mean.data_ptr(), bn0.running_var.data_ptr(), m0.data_ptr(), i0.data_ptr(),
+                                 ws.data_ptr(), ws.numel(), L.stream()), "sd_conv2d_stem_fwd_bn_stats")
+            else:
+                sums = sx.take(64)
+                stem_sums = (lib.sd_conv2d_stem_fwd_bn_sums_bf16 if amp_stem else lib.sd_conv2d_stem_fwd_bn_sums_bf16mm) if amp \
+                    else lib.sd_conv2d_stem_fwd_bn_sums
+                sx.record("sd_conv2d_stem_fwd_bn_sums")
+                L.check(stem_sums(x.data_ptr(), stem.weight.data_ptr(), s0.data_ptr(), C.byref(d0), sums.data_ptr(), ws.data_ptr(), ws.numel(),
+                                  L.stream()), "sd_conv2d_stem_fwd_bn_sums")
+                self._stats_from_sums(sx, sums, bn0, m0, i0)
             self._nbt.append(bn0.num_batches_tracked)
             pool_fwd = lib.sd_bn_relu_maxpool_fwd_bf16 if amp_stem else lib.sd_bn_relu_maxpool_fwd
             L.check(pool_fwd(s0.data_ptr(), B, d0.Ho, d0.Wo, 64, m0.data_ptr(), i0.data_ptr(), bn0.weight.data_ptr(),
@@ -362,11 +417,11 @@ class _Engine:
             T.push(f"fwd:down{li}")
             for blk in layer:
                 if training:
-                    c1, d1, st1 = self.conv_stats(cur, blk.conv1, B, Hc, Wc, blk.bn1, amp=amp)
+                    c1, d1, st1 = self.conv_stats(cur, blk.conv1, B, Hc, Wc, blk.bn1, amp=amp, sync=sx)
                     a1, m1, i1 = self.bn_train(c1, blk.bn1, stats=st1)
-                    c2, d2, st2 = self.conv_stats(a1, blk.conv2, B, d1.Ho, d1.Wo, blk.bn2, amp=amp)
+                    c2, d2, st2 = self.conv_stats(a1, blk.conv2, B, d1.Ho, d1.Wo, blk.bn2, amp=amp, sync=sx)
                     if blk.downsample is not None:
-                        cd, dd, std_ = self.conv_stats(cur, blk.downsample[0], B, Hc, Wc, blk.downsample[1], amp=amp)
+                        cd, dd, std_ = self.conv_stats(cur, blk.downsample[0], B, Hc, Wc, blk.downsample[1], amp=amp, sync=sx)
                         idt, md, idd = self.bn_train(cd, blk.downsample[1], relu=False, stats=std_)
                     else:
                         cd = dd = md = idd = None
@@ -396,7 +451,7 @@ class _Engine:
         for fpn, (sc_t, Hs, Ws) in ((net.up2, (p4, H4, W4)), (net.up3, (p3, H3, W3)), (net.up4, (p2, H2, W2))):
             t, dl = self.conv(sc_t, fpn.lateral, B, Hs, Ws, shift=fpn.lateral.bias, res=f, res_up2=True, amp=amp, sb=not training)
             if training:
-                c, dc, stf = self.conv_stats(t, fpn.conv[0], B, Hs, Ws, fpn.conv[1], amp=amp)
+                c, dc, stf = self.conv_stats(t, fpn.conv[0], B, Hs, Ws, fpn.conv[1], amp=amp, sync=sx)
                 fn, mf, if_ = self.bn_train(c, fpn.conv[1], stats=stf)
                 if rec:
                     fpn_tape.append((fpn, sc_t, (Hs, Ws), dl, t, dc, c, mf, if_, fn))
@@ -562,7 +617,7 @@ class _Engine:
         L.check(transpose(conv.weight.data_ptr(), wt.data_ptr(), conv.cout, conv.k * conv.k, conv.cin, L.stream()), "transpose_weights")
         return wt
 
-    def _dgrad(self, dy, conv, d, res=None, bn_next=None, res_half=False):
+    def _dgrad(self, dy, conv, d, res=None, bn_next=None, res_half=False, sync=None):
         """dx = dgrad(dy) [+ res].  bn_next = (x, y, relu, bn, mean, invstd) of the BatchNorm whose output gradient dx is:
         the launch then also does that BatchNorm's backward reduction (sd_conv2d_dgrad_bn_reduce) and the per-channel means
         come back for _bn_bwd(..., means=...), which only has the apply pass left."""
@@ -588,8 +643,18 @@ class _Engine:
             return dx
         assert not res_half
         x, y, relu, bn, mean, invstd = bn_next
-        means = torch.empty(2 * conv.cin, dtype=torch.float32, device=dy.device)
         ws = self._ws(self.lib.sd_conv2d_dgrad_bn_reduce_workspace_bytes(C.byref(d)), dy.device)
+        if sync is not None:            # synchronized BatchNorm: the epilogue's sums are exchanged before the means are formed
+            sums = sync.take(conv.cin)
+            sync.record("sd_conv2d_dgrad_bn_reduce_sums")
+            self._timed(self._kname(d, 1), flops, lambda: L.check(
+                self.lib.sd_conv2d_dgrad_bn_reduce_sums(dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), C.byref(d), _ptr(res), x.data_ptr(),
+                                                        _ptr(y) if int(relu) in (1, 3) else 0, int(relu), mean.data_ptr(), invstd.data_ptr(),
+                                                        bn.weight.data_ptr(), bn.bias.data_ptr(), self.net.grad_of(bn.weight).data_ptr(),
+                                                        self.net.grad_of(bn.bias).data_ptr(), 0, sums.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                        L.stream()), "sd_conv2d_dgrad_bn_reduce_sums"), phase="dgrad")
+            return dx, self._means_from_sums(sync, sums, conv.cin, dy.device)
+        means = torch.empty(2 * conv.cin, dtype=torch.float32, device=dy.device)
         self._timed(self._kname(d, 1), flops, lambda: L.check(
             self.lib.sd_conv2d_dgrad_bn_reduce(dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), C.byref(d), _ptr(res), x.data_ptr(),
                                                _ptr(y) if int(relu) in (1, 3) else 0, int(relu), mean.data_ptr(), invstd.data_ptr(),
@@ -642,10 +707,26 @@ class _Engine:
         L.check(col_sum(dy.data_ptr(), Mrows, Cc, self.net.grad_of(conv.bias).data_ptr(), 0, ws.data_ptr(), ws.numel(), L.stream()),
                 "sd_col_sum")
 
-    def _bn_bwd(self, dy, x, y, relu, bn, mean, invstd, want_g=False, means=None):
+    def _bn_bwd(self, dy, x, y, relu, bn, mean, invstd, want_g=False, means=None, sync=None):
         Mrows, Cc = x.numel() // x.shape[-1], x.shape[-1]
         dx = torch.empty_like(x)
         g = torch.empty_like(x) if want_g else None
+        if means is None and sync is not None:
+            # synchronized BatchNorm: the reduce half (dgamma / dbeta from the local sums), the exchange, the means, then the apply half
+            sums = sync.take(Cc)
+            bf16 = x.dtype == torch.bfloat16
+            sync.record("sd_bn_bwd_reduce_bf16" if bf16 else "sd_bn_bwd_reduce")
+            ws = self._ws(self.lib.sd_col_reduce_workspace_bytes(Mrows, Cc), x.device)
+            reduce = self.lib.sd_bn_bwd_reduce_bf16 if bf16 else self.lib.sd_bn_bwd_reduce
+            L.check(reduce(dy.data_ptr(), x.data_ptr(), _ptr(y) if int(relu) in (1, 3) else 0, int(relu), Mrows, Cc, mean.data_ptr(),
+                           invstd.data_ptr(), bn.weight.data_ptr(), bn.bias.data_ptr(), self.net.grad_of(bn.weight).data_ptr(),
+                           self.net.grad_of(bn.bias).data_ptr(), 0, sums.data_ptr(), ws.data_ptr(), ws.numel(), L.stream()), "sd_bn_bwd_reduce")
+            means = self._means_from_sums(sync, sums, Cc, x.device)
+            apply = self.lib.sd_bn_bwd_apply_bf16 if bf16 else self.lib.sd_bn_bwd_apply
+            L.check(apply(dy.data_ptr(), x.data_ptr(), _ptr(y) if int(relu) in (1, 3) else 0, int(relu), Mrows, Cc, mean.data_ptr(),
+                          invstd.data_ptr(), bn.weight.data_ptr(), bn.bias.data_ptr(), means.data_ptr(), dx.data_ptr(), _ptr(g), L.stream()),
+                    "sd_bn_bwd_apply")
+            return dx, g
         if means is not None:       # reduction (and dgamma / dbeta) already done by the data-gradient launch that produced dy
             L.check(self.lib.sd_bn_bwd_apply(dy.data_ptr(), x.data_ptr(), _ptr(y) if int(relu) in (1, 3) else 0, int(relu), Mrows, Cc,
                                              mean.data_ptr(), invstd.data_ptr(), bn.weight.data_ptr(), bn.bias.data_ptr(), means.data_ptr(),
@@ -672,6 +753,9 @@ class _Engine:
         amp = bool(tape.get("amp"))
         if amp and self.fuse_bn_bwd:
             raise L.SdError("fuse_bn_bwd is an fp32-path experiment; switch it off for mixed-precision training")
+        sx = tape.get("bn_sync")             # synchronized BatchNorm (see forward)
+        if sx is not None:
+            sx.begin("bwd")
         T.push("bwd:fpn_head")
         self._transpose_all(amp)
         ws = self._ws(lib.sd_head_bwd_workspace_bytes(B, H2 * W2, hc.cin, hc.cout), dhead.device)
@@ -695,7 +779,7 @@ class _Engine:
         # gradient for that tensor exists, so the sum of the two is the dgrad kernel's residual epilogue.
         lateral_grad = {}
         for (fpn, sc_t, (Hs, Ws), dl, t, dc, c, mf, if_, fn) in reversed(tape["fpn"]):
-            dcv, _ = self._bn_bwd(df, c, fn, 2, fpn.conv[1], mf, if_)
+            dcv, _ = self._bn_bwd(df, c, fn, 2, fpn.conv[1], mf, if_, sync=sx)
             dt = self._dgrad(dcv, fpn.conv[0], dc)
             self._wgrad(dcv, t, fpn.conv[0], dc)
             self._wgrad(dt, sc_t, fpn.lateral, dl)
@@ -722,7 +806,7 @@ class _Engine:
         last = len(blocks) - 1
         has_lateral = blocks[last][12].data_ptr() in lateral_grad
         nxt = None if has_lateral else bn2_of(last)
-        r = self._dgrad(df, net.up1, d5, bn_next=nxt)
+        r = self._dgrad(df, net.up1, d5, bn_next=nxt, sync=sx)
         dcur, mcur = r if nxt is not None else (r, None)
         T.pop()
         if on_stage:
@@ -737,17 +821,17 @@ class _Engine:
             extra = lateral_grad.pop(out.data_ptr(), None)
             if extra is not None:                       # `out` also feeds an FPN lateral conv: this launch completes d(out)
                 nxt = bn2_of(bi)
-                r = self._dgrad(extra[0], extra[1], extra[2], res=dcur, bn_next=nxt)
+                r = self._dgrad(extra[0], extra[1], extra[2], res=dcur, bn_next=nxt, sync=sx)
                 dcur, mcur = r if nxt is not None else (r, None)
-            dc2, g = self._bn_bwd(dcur, c2, msk, 3, blk.bn2, m2, i2, want_g=True, means=mcur)
+            dc2, g = self._bn_bwd(dcur, c2, msk, 3, blk.bn2, m2, i2, want_g=True, means=mcur, sync=sx)
             nxt = (c1, None, 2, blk.bn1, m1, i1) if self.fuse_bn_bwd else None
-            r = self._dgrad(dc2, blk.conv2, d2, bn_next=nxt)
+            r = self._dgrad(dc2, blk.conv2, d2, bn_next=nxt, sync=sx)
             da1, ma1 = r if nxt is not None else (r, None)
             self._wgrad(dc2, a1, blk.conv2, d2)
-            dc1, _ = self._bn_bwd(da1, c1, a1, 2, blk.bn1, m1, i1, means=ma1)
+            dc1, _ = self._bn_bwd(da1, c1, a1, 2, blk.bn1, m1, i1, means=ma1, sync=sx)
             half = False
             if blk.downsample is not None:
-                dcd, _ = self._bn_bwd(g, cd, None, False, blk.downsample[1], md, idd)
+                dcd, _ = self._bn_bwd(g, cd, None, False, blk.downsample[1], md, idd, sync=sx)
                 ds = blk.downsample[0]
                 half = ds.k == 1 and ds.stride == 2 and ds.pad == 0 and Hc % 2 == 0 and Wc % 2 == 0 and not self.fuse_bn_bwd
                 if half:
@@ -765,7 +849,7 @@ class _Engine:
             # d(xin) = d(out of the previous block), complete unless that tensor also feeds an FPN lateral (handled above)
             prev_lateral = bi > 0 and blocks[bi - 1][12].data_ptr() in lateral_grad
             nxt = None if (bi == 0 or prev_lateral) else bn2_of(bi - 1)
-            r = self._dgrad(dc1, blk.conv1, d1, res=skip, bn_next=nxt, res_half=half)
+            r = self._dgrad(dc1, blk.conv1, d1, res=skip, bn_next=nxt, res_half=half, sync=sx)
             dcur, mcur = r if nxt is not None else (r, None)
             self._wgrad(dc1, xin, blk.conv1, d1)
             if id(blk) in first_of:                                         # the first block of a layer closes that layer's range
@@ -784,10 +868,23 @@ class _Engine:
         ring = amp_stem and self.stem_ring and d0.Wi % 4 == 0          # the row-ring weight gradient fetches the image in aligned groups of four columns
         ds0 = torch.empty(s0.shape, dtype=torch.bfloat16 if ring else torch.float32, device=s0.device)
         ws = self._ws(lib.sd_col_reduce_workspace_bytes(B * d0.Ho * d0.Wo, 64), s0.device)
-        pool_bwd = lib.sd_maxpool_bn_relu_bwd_bf16_dx16 if ring else (lib.sd_maxpool_bn_relu_bwd_bf16 if amp_stem else lib.sd_maxpool_bn_relu_bwd)
-        L.check(pool_bwd(dcur.data_ptr(), pidx.data_ptr(), s0.data_ptr(), B, d0.Ho, d0.Wo, 64, m0.data_ptr(), i0.data_ptr(),
-                         bn0.weight.data_ptr(), bn0.bias.data_ptr(), ds0.data_ptr(), net.grad_of(bn0.weight).data_ptr(),
-                         net.grad_of(bn0.bias).data_ptr(), 0, ws.data_ptr(), ws.numel(), L.stream()), "sd_maxpool_bn_relu_bwd")
+        if sx is None:
+            pool_bwd = lib.sd_maxpool_bn_relu_bwd_bf16_dx16 if ring else (lib.sd_maxpool_bn_relu_bwd_bf16 if amp_stem else lib.sd_maxpool_bn_relu_bwd)
+            L.check(pool_bwd(dcur.data_ptr(), pidx.data_ptr(), s0.data_ptr(), B, d0.Ho, d0.Wo, 64, m0.data_ptr(), i0.data_ptr(),
+                             bn0.weight.data_ptr(), bn0.bias.data_ptr(), ds0.data_ptr(), net.grad_of(bn0.weight).data_ptr(),
+                             net.grad_of(bn0.bias).data_ptr(), 0, ws.data_ptr(), ws.numel(), L.stream()), "sd_maxpool_bn_relu_bwd")
+        else:                                         # synchronized BatchNorm: reduce half, exchange, means, apply half
+            sums = sx.take(64)
+            sx.record("sd_maxpool_bn_relu_bwd_reduce")
+            pool_reduce = lib.sd_maxpool_bn_relu_bwd_reduce_bf16 if amp_stem else lib.sd_maxpool_bn_relu_bwd_reduce
+            L.check(pool_reduce(dcur.data_ptr(), pidx.data_ptr(), s0.data_ptr(), B, d0.Ho, d0.Wo, 64, m0.data_ptr(), i0.data_ptr(),
+                                bn0.weight.data_ptr(), bn0.bias.data_ptr(), net.grad_of(bn0.weight).data_ptr(), net.grad_of(bn0.bias).data_ptr(), 0,
+                                sums.data_ptr(), ws.data_ptr(), ws.numel(), L.stream()), "sd_maxpool_bn_relu_bwd_reduce")
+            means = self._means_from_sums(sx, sums, 64, s0.device)
+            pool_apply = lib.sd_maxpool_bn_relu_bwd_apply_bf16_dx16 if ring else (lib.sd_maxpool_bn_relu_bwd_apply_bf16 if amp_stem
+                                                                                  else lib.sd_maxpool_bn_relu_bwd_apply)
+            L.check(pool_apply(dcur.data_ptr(), pidx.data_ptr(), s0.data_ptr(), B, d0.Ho, d0.Wo, 64, m0.data_ptr(), i0.data_ptr(),
+                               bn0.weight.data_ptr(), bn0.bias.data_ptr(), means.data_ptr(), ds0.data_ptr(), L.stream()), "sd_maxpool_bn_relu_bwd_apply")
         stem = net.adpater[0]
         ws = self._ws(lib.sd_conv2d_stem_wgrad_workspace_bytes(C.byref(d0)), ds0.device)
         # amp: product on the bf16 MFMA (autocast: conv1 in bf16); a bf16 stem gives a bf16 gradient (row-ring kernel)
@@ -1026,10 +1123,12 @@ class Network(nn.Module):
         return run
 
     # ---- explicit (autograd-free) training path used by the trainer / bench ----------------
-    def forward_train(self, x, amp=False):
+    def forward_train(self, x, amp=False, bn_sync=None):
         """Forward in training mode recording the tape; returns (head tensor, tape).  amp=True: the mixed-precision step of the
-        reference's `--amp` (trainer.py:115-121) -- bf16 activations and conv weights, fp32 accumulation, statistics and master weights."""
-        tape = {}
+        reference's `--amp` (trainer.py:115-121) -- bf16 activations and conv weights, fp32 accumulation, statistics and master weights.
+        bn_sync (a `sync_bn.BnStatsExchange`): synchronized BatchNorm -- every BatchNorm of this forward and of `backward_from(tape, ...)`
+        finishes its batch statistics through the exchange (global statistics over the ranks of its process group).  None: today's launches."""
+        tape = {} if bn_sync is None else {"bn_sync": bn_sync}
         return self._engine.forward(x, True, tape, amp=amp), tape
 
     def backward_from(self, tape, dhead, on_stage=None):

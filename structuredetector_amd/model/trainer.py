@@ -7,7 +7,8 @@ what the reference lacks: pure data-parallel training, one process per GPU, grad
 RCCL (`torch.distributed` backend "nccl") in five buckets that follow the backward pass
 (FPN+head, down4, down3, down2, down1+stem), so the 87 MB exchange hides behind the remaining
 backward kernels; the mean is applied inside the fused Adam launch (grad_scale = 1/world).
-BatchNorm statistics stay rank-local (the reference has no SyncBN to match).
+BatchNorm statistics are rank-local by default; `sync_bn=True` (`train --sync_bn`) computes them over the global batch
+(model/sync_bn.py) through the same process group as the gradient buckets.
 """
 from __future__ import annotations
 
@@ -87,7 +88,7 @@ class SimExchange:
 
 
 class TrainStep:
-    def __init__(self, net, args, lr=None, betas=(0.9, 0.999), eps=1e-8, process_group=None, exchange=None):
+    def __init__(self, net, args, lr=None, betas=(0.9, 0.999), eps=1e-8, process_group=None, exchange=None, sync_bn=False):
         if net.flat_params is None:
             raise L.SdError("move the Network to the GPU before building TrainStep")
         self.net, self.args = net, args
@@ -102,6 +103,11 @@ class TrainStep:
         want_sim = exchange == "sim"
         if exchange not in ("torch", "rccl", "sim"):
             raise ValueError(f"exchange must be 'torch', 'rccl' or 'sim', got {exchange!r}")
+        if sync_bn and exchange == "rccl":
+            # the statistics would need a second communicator beside the C-ABI one: two communicators whose collectives can run in
+            # different orders on different ranks can deadlock the GPUs
+            raise L.SdError("sync_bn needs the torch.distributed exchange: its statistics all-reduces must share the gradient buckets' "
+                            "process group (one communicator, one order on every rank); exchange='rccl' is a communicator of its own")
         self.rccl = RcclExchange(net.flat_params.device, process_group) if (exchange == "rccl" and self.world > 1) else None
         self.ranges = net.stage_ranges()
         self.sim = None                  # SimExchange: the collective's footprint on one GPU (attach_sim)
@@ -111,6 +117,13 @@ class TrainStep:
         self.stats = LossStats()
         self.amp = bool(getattr(args, "use_amp", False))      # mixed-precision step (trainer.py:115-121)
         self.exchange_enabled = True     # False: skip the all-reduce (bench.py measures the exposed communication time with it)
+        # synchronized BatchNorm: per-layer fp64 statistics all-reduced over `process_group` (the gradient buckets' group); with one
+        # rank the split finish runs without a collective (bit-identical to the default step)
+        self.sync_bn = bool(sync_bn)
+        self.bn_sync = None
+        if self.sync_bn:
+            from .sync_bn import BnStatsExchange
+            self.bn_sync = BnStatsExchange.for_network(net, process_group, self.world)
 
     # ---- true resume: the reference saves weights only (trainer.py:226-237), so a run cannot continue --------
     def state_dict(self):
@@ -257,7 +270,10 @@ class TrainStep:
         net = self.net
         T.push("step")
         T.push("forward")
-        head, tape = net.forward_train(images, amp=self.amp)
+        if self.bn_sync is None:
+            head, tape = net.forward_train(images, amp=self.amp)
+        else:
+            head, tape = net.forward_train(images, amp=self.amp, bn_sync=self.bn_sync)
         T.pop()
         T.push("loss")
         M, N = net.label_count, net.part_count
@@ -288,6 +304,11 @@ class TrainStep:
         T.pop()
         self.stats.update(out8[1], out8[2], out8[3])
         return out8[:4]
+
+
+def train_step_kwargs(args):
+    """Keyword arguments `Trainer` builds its `TrainStep` with from the parsed command line."""
+    return dict(lr=args.learning_rate, sync_bn=bool(getattr(args, "sync_bn", False)))
 
 
 class StepLR:
@@ -348,7 +369,7 @@ class Trainer:
         if args.pretrained_model:
             self.net.load_state_dict(torch.load(args.pretrained_model, map_location="cpu", weights_only=True))
         self.net.to(args.device).train()
-        self.step = TrainStep(self.net, args, lr=args.learning_rate)
+        self.step = TrainStep(self.net, args, **train_step_kwargs(args))
         self.step.sync_parameters()
         self.scheduler = StepLR(self.step, args.lr_step)
         self.encode = Encode(args)
@@ -439,7 +460,7 @@ class Trainer:
 
     def _take_rank0_buffers(self):
         """Data-parallel validation scores rank 0's model (the one reported and saved): every rank keeps a copy of its own BatchNorm
-        running statistics (rank-local, no SyncBN) and takes rank 0's by broadcast.  Returns the copies for `_restore_buffers`."""
+        running statistics (rank-local unless the step runs synchronized BatchNorm) and takes rank 0's by broadcast.  Returns the copies for `_restore_buffers`."""
         own = [b.detach().clone() for b in self.net.buffers()]
         for b in self.net.buffers():
             dist.broadcast(b, 0, group=self.step.pg)
@@ -570,6 +591,8 @@ class Trainer:
 
     def _train(self):
         steps = 0
+        if self.rank == 0 and self.step.sync_bn:
+            print(f"synchronized BatchNorm: on (statistics over the global batch of {self.step.world} rank(s) x {self.args.batch_size})", flush=True)
         if self.cache is not None:
             self.prefill_cache()
         for epoch in range(self.start_epoch, self.args.epochs):

@@ -56,6 +56,8 @@ _FLAGS = [
                                    "the trunk: what the reference downloads for pretrained=True (default: $SDNET_BACKBONE_WEIGHTS, then the torch hub cache).")),
     (("--log_dir",), dict(type=str, default=None, help="Directory for the training scalars (default: the run's save directory).")),
     (("--eval_batch",), dict(type=int, default=16, help="Images per forward + decode launch in evaluate / validation / detect.")),
+    (("--sync_bn",), dict(action="store_true", help="Synchronized BatchNorm: data-parallel ranks normalise with the statistics of the "
+                          "global batch (one fp64 all-reduce per BatchNorm and direction).")),
     (("--cache_images",), dict(type=float, default=0.0, help="GB of device memory for decoded training / validation images, kept across "
                                "epochs (decoded once before epoch 1; images beyond the budget are decoded every epoch; 0 = off).")),
 ]
