@@ -364,7 +364,9 @@ int sd_set_option(const char* name, int value);
 
 /* Name of the device kernel the launchers pick for this geometry (pass 0 = sd_conv2d_fwd, 1 = sd_conv2d_dgrad,
  * 2 = sd_conv2d_wgrad; 16 = sd_conv2d_fwd_bf16, 17 = sd_conv2d_dgrad_bf16), as rocprofv3 prints it without the sd:: namespace -- lets a profiler label its event timings
- * with the same names as the kernel trace.  Thread-local storage, valid until the next call on the thread. */
+ * with the same names as the kernel trace.  Passes 0 / 1 / 16 / 17 name the kernel of the dispatch plan (plan_conv in csrc/sd_conv.hip, the
+ * same function the launchers run) of a launch WITHOUT epilogue operands: a launch with a scale, fused statistics or a half-size residual can
+ * take another kernel (a 1x1 conv named k_conv1x1_stream_bf16 runs k_conv_igemm then).  Thread-local storage, valid until the next call on the thread. */
 const char* sd_conv2d_kernel_name(const sd_conv_desc* d, int pass);
 
 /* bf16 backbone (inference; BASELINE stress config "bf16 backbone + fp32 decode"): activations and weights bf16

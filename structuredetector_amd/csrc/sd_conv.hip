@@ -5097,8 +5097,8 @@ static thread_local int g_patch_bn64 = 0;            // 64-channel layers: the p
 static thread_local int g_patch_min_tiles = 512;     // two resident blocks per CU; sd_set_option("conv_patch_min_tiles", n) (tests: 1; off: 1 << 30)
 
 // k_conv3x3_patch applies: unit-stride 3x3 with pad 1 (fwd: rsign +1, off -1; dgrad: rsign -1, off +1), map width 16..128 (power
-// of two), images that are whole 256-pixel tiles, no split-K, and a grid that fills the chip.  Fills the geometry fields.
-static bool conv_patch_geometry(ConvArgs& a, int BN, int mode, bool bf16 = false, bool allow64 = false) {
+// of two), images that are whole 256-pixel tiles, no split-K, and a grid of at least `min_tiles` blocks.  Fills the geometry fields.
+static bool conv_patch_geometry(ConvArgs& a, int BN, int mode, bool bf16, bool allow64, int min_tiles) {
     // (64-channel tiles: on for bf16, where they gain 2 %; opt-in for fp32)
     if (!SD_CONV_PATCH || (BN == 64 && !g_patch_bn64 && !bf16 && !allow64) || mode != 0 || a.R != 3 || a.S != 3 || a.mul != 1 || a.div != 1 || a.splits > 1) return false;
     if (!((a.rsign == 1 && a.off == -1) || (a.rsign == -1 && a.off == 1))) return false;
@@ -5106,7 +5106,7 @@ static bool conv_patch_geometry(ConvArgs& a, int BN, int mode, bool bf16 = false
     int l2 = 0;
     while ((1 << l2) < a.Wo) ++l2;
     if ((1 << l2) != a.Wo || a.Wo < 16 || a.Wo > 128 || (a.Ho * a.Wo) % BMB) return false;
-    if ((a.M / BMB) * (a.Nn / BN) < g_patch_min_tiles) return false;
+    if ((a.M / BMB) * (a.Nn / BN) < min_tiles) return false;
     const int th = BMB / a.Wo;
     a.pt_tw_log2 = l2;
     a.pt_rolling = a.Wo == 128;
@@ -5122,10 +5122,10 @@ static bool conv_patch_geometry(ConvArgs& a, int BN, int mode, bool bf16 = false
 static thread_local int g_patch_narrow = 2;            // 1: fp32 only, 2: bf16 too.  Same-box A/B (tools/ab_option.py): fp32 step -0.4 % (layer4: k_conv_igemm<128> -> k_conv3x3_patch<64>), bf16 eval forward -1.6 %, mixed-precision step -0.7 %
 static int patch_tile_bn(ConvArgs& a, int BN, int mode, bool bf16) {
     ConvArgs t = a;
-    if (conv_patch_geometry(t, BN, mode, bf16)) { a = t; return BN; }
+    if (conv_patch_geometry(t, BN, mode, bf16, false, g_patch_min_tiles)) { a = t; return BN; }
     if (BN == 128 && (bf16 ? g_patch_narrow >= 2 : g_patch_narrow >= 1)) {
         t = a;
-        if (conv_patch_geometry(t, 64, mode, bf16, true)) { a = t; return 64; }
+        if (conv_patch_geometry(t, 64, mode, bf16, true, g_patch_min_tiles)) { a = t; return 64; }
     }
     return 0;
 }
@@ -5180,11 +5180,11 @@ static bool conv_rowsf32_geometry(const ConvArgs& a, int mode, RowsArgsF& r) {
 }
 
 // k_conv3x3_bf16_pp applies: bf16, 128-channel output tiles, the double-buffered patch geometry (maps up to 64 pixels wide as whole
-// rows, wider ones as 64-pixel column strips), whole 512-pixel tiles and a grid of at least g_pp_min_tiles blocks (one 512-thread block per CU).  Fills the geometry fields.
+// rows, wider ones as 64-pixel column strips), whole 512-pixel tiles and a grid of at least `min_tiles` blocks (one 512-thread block per CU).  Fills the geometry fields.
 static thread_local int g_pp_min_tiles = 200;        // sd_set_option("conv_pp_min_tiles", n) (tests: 1; off: 1 << 30)
 static thread_local int g_pp_strips = 1;             // sd_set_option("conv_pp_strips", 0): maps of 128 pixels and wider stay on k_conv3x3_patch (A/B)
-static bool conv_pp_geometry(ConvArgs& a, int mode) {
-    if (a.Nn % 128 || a.M % PP_BM || (a.M / PP_BM) * (a.Nn / 128) < g_pp_min_tiles || a.res_up2) return false;   // (a half-size residual map: k_conv3x3_patch)
+static bool conv_pp_geometry(ConvArgs& a, int mode, int min_tiles) {
+    if (a.Nn % 128 || a.M % PP_BM || (a.M / PP_BM) * (a.Nn / 128) < min_tiles || a.res_up2) return false;   // (a half-size residual map: k_conv3x3_patch)
     a.pt_strip_log2 = 0;
     int l2 = 0;
     while ((1 << l2) < a.Wo) ++l2;
@@ -5197,11 +5197,7 @@ static bool conv_pp_geometry(ConvArgs& a, int mode) {
         a.pt_tw_log2 = 6; a.pt_strip_log2 = l2 - 6; a.pt_rolling = 0; a.pt_pw = 66; a.pt_pieces = cdiv(6 * 66, 16); a.pt_flip = a.rsign < 0;
         return true;
     }
-    const int keep = g_patch_min_tiles;
-    g_patch_min_tiles = 1;
-    const bool ok = conv_patch_geometry(a, 128, mode, true);
-    g_patch_min_tiles = keep;
-    return ok && !a.pt_rolling;
+    return conv_patch_geometry(a, 128, mode, true, false, 1) && !a.pt_rolling;      // (the grid was measured against min_tiles above)
 }
 
 static thread_local int g_stem_fwd_ring = 1;         // sd_set_option("stem_fwd_ring", 0): the mixed-precision stem forward on k_stem_fwd<true> (A/B)
@@ -5219,134 +5215,198 @@ static int igemm_big_tiles(const ConvArgs& a, int BN, int mode) {
     return (big_tiles >= 512 && (mode != 2 || m_per % BMB == 0)) ? big_tiles : 0;
 }
 
+// ---- how a conv is dispatched ------------------------------------------------------------------------------------------------------
+// plan_conv() is the ONE place that decides which kernel takes a forward / data-gradient launch, with what tile, grid and LDS, and how
+// many partial-statistics rows its epilogue writes.  The launch (launch_plan), the name query (sd_conv2d_kernel_name), the statistics-row
+// and workspace queries and sd_conv2d_fwd_bf16_head_supported all read a ConvPlan; none of them asks a conv_*_geometry predicate itself.
+enum ConvFamily {
+    CONV_STREAM1X1,      // k_conv1x1_stream_bf16<Ck, P>
+    CONV_ROWS16,         // k_conv3x3_c64_rows16_bf16 (sd_conv_rows16.hip)
+    CONV_ROWS_BF16,      // k_conv3x3_c64_rows_bf16
+    CONV_ROWS_F32,       // k_conv3x3_c64_rows_f32
+    CONV_PP,             // k_conv3x3_bf16_pp
+    CONV_PP_HEAD,        // k_conv3x3_bf16_pp_head
+    CONV_PATCH,          // k_conv3x3_patch<BN, BF16>
+    CONV_PATCH_ROLL,     // k_conv3x3_patch_roll<BN, BF16>
+    CONV_IGEMM_BIG,      // k_conv_igemm_big<BN, MODE, BF16>
+    CONV_IGEMM,          // k_conv_igemm<BN, MODE, BF16> (+ k_splitk_reduce when a.splits > 1)
+};
+
+struct ConvPlan {
+    ConvFamily family;
+    bool bf16;
+    int BN, mode;            // output-channel tile; MODE of the tile kernels (0 unit div, 1 stem, 2 stride-2 parity classes, 3 generic strided)
+    int grid_x, grid_y, block;
+    size_t lds;              // dynamic LDS bytes (0: the kernel's tiles are static __shared__ objects)
+    int stat_rows;           // partial-statistics rows this kernel's epilogue writes when a.stat is set (0: it fuses none -- split-K, 1x1 stream)
+    ConvArgs a;              // the launch arguments, pt_* geometry filled for the patch families
+    RowsArgs ra;             // CONV_ROWS16 / CONV_ROWS_BF16
+    RowsArgsF rf;            // CONV_ROWS_F32
+};
+
+// `a` carries the geometry AND the operand facts the choice depends on: scale, stat, bn_x, res_up2, splits, head_y (set or not).  A size
+// query plans with stand-in operands (plan_query); the options are read here, at call time (they are thread-local).
+static ConvPlan plan_conv(const ConvArgs& a, bool bf16, bool stem = false) {
+    ConvPlan p{};
+    p.bf16 = bf16;
+    p.a = a;
+    p.BN = (a.Nn % 128 == 0) ? 128 : 64;
+    p.mode = stem ? 1 : (a.par ? 2 : (a.div > 1 ? 3 : 0));
+    p.grid_y = 1; p.block = 256;
+    if (!stem && bf16) {
+        if (conv1x1_stream_geometry(a, p.mode) && conv1x1_stream_args(a)) {
+            p.family = CONV_STREAM1X1;
+            p.grid_x = std::min(512, cdiv(a.M / (a.Ck == 64 ? 32 : 16), 4));
+            return p;
+        }
+        if (conv_rows64_geometry(a, p.mode, p.ra)) {
+            p.family = conv_rows16_args(p.ra) ? CONV_ROWS16 : CONV_ROWS_BF16;
+            p.grid_x = std::min(p.ra.nunits, 256); p.lds = RS_LDS_BYTES; p.stat_rows = p.ra.nunits;
+            return p;
+        }
+        ConvArgs t = a;
+        if (conv_pp_geometry(t, p.mode, g_pp_min_tiles)) {
+            p.a = t;
+            p.family = a.head_y ? CONV_PP_HEAD : CONV_PP;
+            p.BN = 128; p.grid_x = (a.M / PP_BM) * (a.Nn / 128); p.block = 512; p.lds = PP_LDS_FLOATS * sizeof(float); p.stat_rows = a.M / PP_BM;
+            return p;
+        }
+    }
+    if (!stem && !bf16 && conv_rowsf32_geometry(a, p.mode, p.rf)) {
+        p.family = CONV_ROWS_F32;
+        p.grid_x = std::min(p.rf.nunits, 256); p.lds = RF_LDS_BYTES; p.stat_rows = p.rf.nunits;
+        return p;
+    }
+    if (!stem) {
+        if (const int PBN = patch_tile_bn(p.a, p.BN, p.mode, bf16)) {
+            p.family = p.a.pt_rolling ? CONV_PATCH_ROLL : CONV_PATCH;
+            p.BN = PBN; p.grid_x = (a.M / BMB) * (a.Nn / PBN); p.stat_rows = cdiv(a.M, BMB);
+            return p;
+        }
+    }
+    // bf16: the 256-row tiles only on request, and only with 128-channel tiles
+    if (const int big_tiles = (!bf16 || (g_igemm_big_bf16 && p.BN == 128)) ? igemm_big_tiles(a, p.BN, p.mode) : 0) {
+        p.family = CONV_IGEMM_BIG;
+        p.grid_x = big_tiles; p.stat_rows = cdiv(a.M, BMB);
+        return p;
+    }
+    p.family = CONV_IGEMM;
+    p.grid_x = cdiv(a.M, BM) * (a.Nn / p.BN); p.grid_y = a.splits > 1 ? a.splits : 1; p.stat_rows = a.splits > 1 ? 0 : cdiv(a.M, BM);
+    return p;
+}
+
+// the kernel of a plan as rocprofv3 prints it (without the sd:: namespace); `buf` is used by the templated families
+static const char* conv_plan_name(const ConvPlan& p, char* buf, size_t n) {
+    const char* tf = p.bf16 ? "true" : "false";
+    switch (p.family) {
+    case CONV_STREAM1X1: return p.a.Ck == 64 ? "k_conv1x1_stream_bf16<64, 2>" : "k_conv1x1_stream_bf16<128, 1>";
+    case CONV_ROWS16: return "k_conv3x3_c64_rows16_bf16";
+    case CONV_ROWS_BF16: return "k_conv3x3_c64_rows_bf16";
+    case CONV_ROWS_F32: return "k_conv3x3_c64_rows_f32";
+    case CONV_PP: return "k_conv3x3_bf16_pp";
+    case CONV_PP_HEAD: return "k_conv3x3_bf16_pp_head";
+    case CONV_PATCH: snprintf(buf, n, "k_conv3x3_patch<%d, %s>", p.BN, tf); return buf;
+    case CONV_PATCH_ROLL: snprintf(buf, n, "k_conv3x3_patch_roll<%d, %s>", p.BN, tf); return buf;
+    case CONV_IGEMM_BIG: snprintf(buf, n, "k_conv_igemm_big<%d, %d, %s>", p.BN, p.mode, tf); return buf;
+    case CONV_IGEMM: snprintf(buf, n, "k_conv_igemm<%d, %d, %s>", p.BN, p.mode, tf); return buf;
+    }
+    return "";
+}
+
+// kernels that ask for more dynamic LDS than the default limit: raise the kernel's limit once per host thread (cheap, idempotent)
+template <auto KERNEL>
+static int raise_dynamic_lds(size_t bytes) {
+    static thread_local bool raised = false;
+    if (!raised) {
+        SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        raised = true;
+    }
+    return 0;
+}
+
+// the tile kernels of a plan (the tiles are static __shared__ objects: 65 KB for BN = 128, 49 KB for BN = 64).  k_conv_igemm_big exists
+// for the (BN, MODE) pairs igemm_big_tiles() admits; plan_conv names it for no other
 template <int BN, int MODE, bool BF16 = false>
-static void launch_one(const ConvArgs& a, int tiles, size_t lds, hipStream_t st) {
-    (void)lds;                             // the tiles are static __shared__ objects (65 KB for BN = 128, 49 KB for BN = 64)
+static void launch_tiles(const ConvPlan& p, hipStream_t st) {
     if constexpr ((BN == 128 || (!BF16 && (SD_IGEMM_BIG64 || (SD_IGEMM_BIG64_S2 && MODE == 2)))) && (MODE == 0 || MODE == 2)) {
-        if (const int big_tiles = (!BF16 || g_igemm_big_bf16) ? igemm_big_tiles(a, BN, MODE) : 0) {
-            hipLaunchKernelGGL((k_conv_igemm_big<BN, MODE, BF16>), dim3(big_tiles), dim3(256), 0, st, a);
+        if (p.family == CONV_IGEMM_BIG) {
+            hipLaunchKernelGGL((k_conv_igemm_big<BN, MODE, BF16>), dim3(p.grid_x), dim3(256), 0, st, p.a);
             return;
         }
     }
-    hipLaunchKernelGGL((k_conv_igemm<BN, MODE, BF16>), dim3(tiles, a.splits > 1 ? a.splits : 1), dim3(256), 0, st, a);
+    hipLaunchKernelGGL((k_conv_igemm<BN, MODE, BF16>), dim3(p.grid_x, p.grid_y), dim3(256), 0, st, p.a);
+}
+template <int BN, bool BF16>
+static void launch_tiles_mode(const ConvPlan& p, hipStream_t st) {
+    if (p.mode == 0) launch_tiles<BN, 0, BF16>(p, st);
+    else if (p.mode == 2) launch_tiles<BN, 2, BF16>(p, st);
+    else launch_tiles<BN, 3, BF16>(p, st);
+}
+template <bool BF16>
+static void launch_patch(const ConvPlan& p, hipStream_t st) {
+    if (p.family == CONV_PATCH_ROLL) {
+        if (p.BN == 128) hipLaunchKernelGGL((k_conv3x3_patch_roll<128, BF16>), dim3(p.grid_x), dim3(256), 0, st, p.a);
+        else hipLaunchKernelGGL((k_conv3x3_patch_roll<64, BF16>), dim3(p.grid_x), dim3(256), 0, st, p.a);
+    } else if (p.BN == 128) hipLaunchKernelGGL((k_conv3x3_patch<128, BF16>), dim3(p.grid_x), dim3(256), 0, st, p.a);
+    else hipLaunchKernelGGL((k_conv3x3_patch<64, BF16>), dim3(p.grid_x), dim3(256), 0, st, p.a);
 }
 
-static int launch_igemm(const ConvArgs& a, bool stem, hipStream_t st, bool bf16 = false) {
-    const int BN = (a.Nn % 128 == 0) ? 128 : 64;
-    const int tiles = cdiv(a.M, BM) * (a.Nn / BN);
-    const size_t lds = (size_t)NBUF * (BM + BN) * LDK * sizeof(float) + BM * sizeof(int);
-    const int mode = stem ? 1 : (a.par ? 2 : (a.div > 1 ? 3 : 0));
-    if (!stem && bf16) {
-        if (conv1x1_stream_geometry(a, mode) && conv1x1_stream_args(a)) {
-            if (a.Ck == 64) { const int nt = a.M / 32; hipLaunchKernelGGL((k_conv1x1_stream_bf16<64, 2>), dim3(std::min(512, cdiv(nt, 4))), dim3(256), 0, st, a, nt); }
-            else { const int nt = a.M / 16; hipLaunchKernelGGL((k_conv1x1_stream_bf16<128, 1>), dim3(std::min(512, cdiv(nt, 4))), dim3(256), 0, st, a, nt); }
-            SD_LAUNCH_CHECK();
-            return 0;
-        }
-        RowsArgs ra;
-        if (conv_rows64_geometry(a, mode, ra)) {
-            static thread_local bool raised64 = false;
-            if (!raised64) {
-                SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv3x3_c64_rows_bf16), hipFuncAttributeMaxDynamicSharedMemorySize, RS_LDS_BYTES));
-                raised64 = true;
-            }
-            if (conv_rows16_args(ra)) {
-                if (int e = launch_rows16_bf16(ra, st)) return e;
-            } else hipLaunchKernelGGL(k_conv3x3_c64_rows_bf16, dim3(std::min(ra.nunits, 256)), dim3(256), RS_LDS_BYTES, st, ra);
-            SD_LAUNCH_CHECK();
-            return 0;
-        }
-        ConvArgs pa = a;
-        if (conv_pp_geometry(pa, mode)) {
-            static thread_local bool raised = false;      // per host thread: cheap, idempotent
-            if (!raised) {
-                SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv3x3_bf16_pp), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           PP_LDS_FLOATS * (int)sizeof(float)));
-                raised = true;
-            }
-            if (pa.head_y) {
-                static thread_local bool raised_h = false;
-                if (!raised_h) {
-                    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv3x3_bf16_pp_head), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               PP_LDS_FLOATS * (int)sizeof(float)));
-                    raised_h = true;
-                }
-                hipLaunchKernelGGL(k_conv3x3_bf16_pp_head, dim3((pa.M / PP_BM) * (pa.Nn / 128)), dim3(512), PP_LDS_FLOATS * sizeof(float), st, pa);
-            } else {
-                hipLaunchKernelGGL(k_conv3x3_bf16_pp, dim3((pa.M / PP_BM) * (pa.Nn / 128)), dim3(512), PP_LDS_FLOATS * sizeof(float), st, pa);
-            }
-            SD_LAUNCH_CHECK();
-            return 0;
-        }
-        SD_REQUIRE(!a.head_y, SD_ERR_INVALID, "sd_conv2d_fwd_bf16_head: this geometry does not take the two-group kernel (ask sd_conv2d_fwd_bf16_head_supported)");
-    }
-    if (!stem && !bf16) {
-        RowsArgsF rf;
-        if (conv_rowsf32_geometry(a, mode, rf)) {
-            static thread_local bool raisedf = false;
-            if (!raisedf) {
-                SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv3x3_c64_rows_f32), hipFuncAttributeMaxDynamicSharedMemorySize, RF_LDS_BYTES));
-                raisedf = true;
-            }
-            hipLaunchKernelGGL(k_conv3x3_c64_rows_f32, dim3(std::min(rf.nunits, 256)), dim3(256), RF_LDS_BYTES, st, rf);
-            SD_LAUNCH_CHECK();
-            return 0;
-        }
-    }
-    if (!stem) {
-        ConvArgs pa = a;
-        if (const int PBN = patch_tile_bn(pa, BN, mode, bf16)) {
-            const int pt_tiles = (pa.M / BMB) * (pa.Nn / PBN);
-            if (bf16) {
-                if (pa.pt_rolling) {
-                    if (PBN == 128) hipLaunchKernelGGL((k_conv3x3_patch_roll<128, true>), dim3(pt_tiles), dim3(256), 0, st, pa);
-                    else hipLaunchKernelGGL((k_conv3x3_patch_roll<64, true>), dim3(pt_tiles), dim3(256), 0, st, pa);
-                } else if (PBN == 128) hipLaunchKernelGGL((k_conv3x3_patch<128, true>), dim3(pt_tiles), dim3(256), 0, st, pa);
-                else hipLaunchKernelGGL((k_conv3x3_patch<64, true>), dim3(pt_tiles), dim3(256), 0, st, pa);
-            } else {
-                if (pa.pt_rolling) {
-                    if (PBN == 128) hipLaunchKernelGGL((k_conv3x3_patch_roll<128, false>), dim3(pt_tiles), dim3(256), 0, st, pa);
-                    else hipLaunchKernelGGL((k_conv3x3_patch_roll<64, false>), dim3(pt_tiles), dim3(256), 0, st, pa);
-                } else if (PBN == 128) hipLaunchKernelGGL((k_conv3x3_patch<128, false>), dim3(pt_tiles), dim3(256), 0, st, pa);
-                else hipLaunchKernelGGL((k_conv3x3_patch<64, false>), dim3(pt_tiles), dim3(256), 0, st, pa);
-            }
-            SD_LAUNCH_CHECK();
-            return 0;
-        }
-    }
-    if (bf16) {                            // forward (MODE 0) and, for mixed-precision training, the data-gradient modes
-        if (BN == 128) {
-            if (mode == 0) launch_one<128, 0, true>(a, tiles, lds, st);
-            else if (mode == 2) launch_one<128, 2, true>(a, tiles, lds, st);
-            else launch_one<128, 3, true>(a, tiles, lds, st);
-        } else {
-            if (mode == 0) launch_one<64, 0, true>(a, tiles, lds, st);
-            else if (mode == 2) launch_one<64, 2, true>(a, tiles, lds, st);
-            else launch_one<64, 3, true>(a, tiles, lds, st);
-        }
-    } else
-    if (mode == 1) launch_one<64, 1>(a, tiles, lds, st);
-    else if (BN == 128) {
-        if (mode == 0) launch_one<128, 0>(a, tiles, lds, st);
-        else if (mode == 2) launch_one<128, 2>(a, tiles, lds, st);
-        else launch_one<128, 3>(a, tiles, lds, st);
-    } else {
-        if (mode == 0) launch_one<64, 0>(a, tiles, lds, st);
-        else if (mode == 2) launch_one<64, 2>(a, tiles, lds, st);
-        else launch_one<64, 3>(a, tiles, lds, st);
+static int launch_plan(const ConvPlan& p, hipStream_t st) {
+    const ConvArgs& a = p.a;
+    SD_REQUIRE(!a.head_y || p.family == CONV_PP_HEAD, SD_ERR_INVALID,
+               "sd_conv2d_fwd_bf16_head: this geometry does not take the two-group kernel (ask sd_conv2d_fwd_bf16_head_supported)");
+    const dim3 grid(p.grid_x, p.grid_y), block(p.block);
+    switch (p.family) {
+    case CONV_STREAM1X1:
+        if (a.Ck == 64) hipLaunchKernelGGL((k_conv1x1_stream_bf16<64, 2>), grid, block, 0, st, a, a.M / 32);
+        else hipLaunchKernelGGL((k_conv1x1_stream_bf16<128, 1>), grid, block, 0, st, a, a.M / 16);
+        break;
+    case CONV_ROWS16:
+    case CONV_ROWS_BF16:
+        if (int e = raise_dynamic_lds<k_conv3x3_c64_rows_bf16>(p.lds)) return e;
+        if (p.family == CONV_ROWS16) {
+            if (int e = launch_rows16_bf16(p.ra, st)) return e;
+        } else hipLaunchKernelGGL(k_conv3x3_c64_rows_bf16, grid, block, p.lds, st, p.ra);
+        break;
+    case CONV_ROWS_F32:
+        if (int e = raise_dynamic_lds<k_conv3x3_c64_rows_f32>(p.lds)) return e;
+        hipLaunchKernelGGL(k_conv3x3_c64_rows_f32, grid, block, p.lds, st, p.rf);
+        break;
+    case CONV_PP:
+        if (int e = raise_dynamic_lds<k_conv3x3_bf16_pp>(p.lds)) return e;
+        hipLaunchKernelGGL(k_conv3x3_bf16_pp, grid, block, p.lds, st, a);
+        break;
+    case CONV_PP_HEAD:
+        if (int e = raise_dynamic_lds<k_conv3x3_bf16_pp_head>(p.lds)) return e;
+        hipLaunchKernelGGL(k_conv3x3_bf16_pp_head, grid, block, p.lds, st, a);
+        break;
+    case CONV_PATCH:
+    case CONV_PATCH_ROLL:
+        if (p.bf16) launch_patch<true>(p, st); else launch_patch<false>(p, st);
+        break;
+    case CONV_IGEMM_BIG:
+    case CONV_IGEMM:
+        if (p.bf16) {                      // forward (MODE 0) and, for mixed-precision training, the data-gradient modes
+            if (p.BN == 128) launch_tiles_mode<128, true>(p, st); else launch_tiles_mode<64, true>(p, st);
+        } else if (p.mode == 1) launch_tiles<64, 1>(p, st);
+        else if (p.BN == 128) launch_tiles_mode<128, false>(p, st);
+        else launch_tiles_mode<64, false>(p, st);
+        break;
     }
     SD_LAUNCH_CHECK();
-    if (a.splits > 1) {
-        if (bf16) hipLaunchKernelGGL(k_splitk_reduce<true>, dim3(cdiv((int64_t)a.M * a.Nn / 4, 256)), dim3(256), 0, st, a);
+    if (p.family == CONV_IGEMM && a.splits > 1) {
+        if (p.bf16) hipLaunchKernelGGL(k_splitk_reduce<true>, dim3(cdiv((int64_t)a.M * a.Nn / 4, 256)), dim3(256), 0, st, a);
         else hipLaunchKernelGGL(k_splitk_reduce<false>, dim3(cdiv((int64_t)a.M * a.Nn / 4, 256)), dim3(256), 0, st, a);
         SD_LAUNCH_CHECK();
     }
     return 0;
 }
 
+static int launch_igemm(const ConvArgs& a, bool stem, hipStream_t st, bool bf16 = false) { return launch_plan(plan_conv(a, bf16, stem), st); }
+
 // Split-K factor of the forward conv: only when the tile grid cannot fill the chip (small batch).
 static thread_local int g_fwd_split_k = 1;           // sd_set_option("conv_fwd_split_k", 0): small grids keep the single-pass kernels (tests of those kernels)
-static int fwd_splits(const sd_conv_desc* d, int ke = BK) {
+static int fwd_splits(const sd_conv_desc* d, int ke) {
     if (!g_fwd_split_k) return 1;
     const int M = d->B * d->Ho * d->Wo;
     const int BN = (d->Cout % 128 == 0) ? 128 : 64;
@@ -5357,18 +5417,32 @@ static int fwd_splits(const sd_conv_desc* d, int ke = BK) {
     return std::max(1, std::min(s, 64));
 }
 
-// geometry part of the kernel arguments (shared by the launchers and sd_conv2d_kernel_name)
-static void fill_fwd(ConvArgs& a, const sd_conv_desc* d) {
-    a.B = d->B; a.Hi = d->Hi; a.Wi = d->Wi; a.Ck = d->Cin; a.Ho = d->Ho; a.Wo = d->Wo; a.Nn = d->Cout; a.R = d->R; a.S = d->S;
-    a.mul = d->stride; a.div = 1; a.off = -d->pad; a.rsign = 1;
-    a.M = d->B * d->Ho * d->Wo; a.kchunks = d->Cin / BK; a.nk = d->R * d->S * a.kchunks;
-    a.splits = fwd_splits(d);
+// Descriptor -> geometry part of the kernel arguments.  pass 0: forward (with its split-K factor), 1: data-gradient (the conv seen from
+// its output: taps reversed, stride as a divisor).  K chunks are 128-byte lines: 32 fp32 or 64 bf16 channels.
+static ConvArgs conv_args(const sd_conv_desc* d, int pass, bool bf16) {
+    ConvArgs a{};
+    const int ke = bf16 ? 64 : BK;
+    a.B = d->B; a.R = d->R; a.S = d->S;
+    if (pass == 0) {
+        a.Hi = d->Hi; a.Wi = d->Wi; a.Ck = d->Cin; a.Ho = d->Ho; a.Wo = d->Wo; a.Nn = d->Cout;
+        a.mul = d->stride; a.div = 1; a.off = -d->pad; a.rsign = 1;
+        a.splits = fwd_splits(d, ke);
+    } else {
+        a.Hi = d->Ho; a.Wi = d->Wo; a.Ck = d->Cout; a.Ho = d->Hi; a.Wo = d->Wi; a.Nn = d->Cin;
+        a.mul = 1; a.div = d->stride; a.off = d->pad; a.rsign = -1;
+    }
+    a.M = a.B * a.Ho * a.Wo; a.kchunks = a.Ck / ke; a.nk = a.R * a.S * a.kchunks;
+    if (pass == 1) a.par = (d->stride == 2 && d->Hi % 2 == 0 && d->Wi % 2 == 0 && (a.M / 4) % BM == 0) ? 1 : 0;
+    return a;
 }
-static void fill_dgrad(ConvArgs& a, const sd_conv_desc* d) {
-    a.B = d->B; a.Hi = d->Ho; a.Wi = d->Wo; a.Ck = d->Cout; a.Ho = d->Hi; a.Wo = d->Wi; a.Nn = d->Cin; a.R = d->R; a.S = d->S;
-    a.mul = 1; a.div = d->stride; a.off = d->pad; a.rsign = -1;
-    a.M = d->B * d->Hi * d->Wi; a.kchunks = d->Cout / BK; a.nk = d->R * d->S * a.kchunks;
-    a.par = (d->stride == 2 && d->Hi % 2 == 0 && d->Wi % 2 == 0 && (a.M / 4) % BM == 0) ? 1 : 0;
+
+// Plan of the launch an entry point would make for this descriptor, for the queries that launch nothing.  `stats`: the launch with the
+// fused statistics epilogue (forward: stat; data-gradient: stat + bn_x) -- the operands are stand-ins that only say "set".
+static float g_query_operand;
+static ConvPlan plan_query(const sd_conv_desc* d, int pass, bool bf16, bool stats) {
+    ConvArgs a = conv_args(d, pass, bf16);
+    if (stats) { a.stat = &g_query_operand; if (pass == 1) a.bn_x = &g_query_operand; }
+    return plan_conv(a, bf16);
 }
 
 static int check_conv(const char* what, const sd_conv_desc* d) {
@@ -5390,7 +5464,7 @@ extern "C" {
 
 size_t sd_conv2d_fwd_workspace_bytes(const sd_conv_desc* d) {
     if (!d || d->Cin % 32 || d->Cout % 64) return 0;
-    const int s = fwd_splits(d);
+    const int s = conv_args(d, 0, false).splits;
     return s > 1 ? (size_t)s * d->B * d->Ho * d->Wo * d->Cout * sizeof(float) : 0;
 }
 
@@ -5403,8 +5477,7 @@ int sd_conv2d_fwd(const float* x, const float* w, float* y, const sd_conv_desc* 
     SD_REQUIRE(aligned16(x) && aligned16(w) && aligned16(y) && aligned16(scale) && aligned16(shift) && aligned16(residual), SD_ERR_ALIGN,
                "sd_conv2d_fwd: pointers must be 16-byte aligned");
     SD_REQUIRE(!res_up2 || (d->Ho % 2 == 0 && d->Wo % 2 == 0), SD_ERR_INVALID, "sd_conv2d_fwd: res_up2 needs even Ho, Wo");
-    ConvArgs a{};
-    fill_fwd(a, d);
+    ConvArgs a = conv_args(d, 0, false);
     a.x = x; a.w = w; a.y = y; a.scale = scale; a.shift = shift; a.res = residual;
     a.relu = relu; a.res_up2 = res_up2;
     if (a.splits > 1) {
@@ -5413,23 +5486,6 @@ int sd_conv2d_fwd(const float* x, const float* w, float* y, const sd_conv_desc* 
         else a.splits = 1;
     }
     return launch_igemm(a, false, (hipStream_t)stream);
-}
-
-// rows of the statistics partial buffer the forward kernel of this geometry writes (0 = the split-K path: no fused statistics)
-static int fwd_stat_rows(const sd_conv_desc* d, bool bf16 = false) {
-    ConvArgs a{};
-    fill_fwd(a, d);
-    if (bf16) { a.kchunks = d->Cin / 64; a.nk = d->R * d->S * a.kchunks; a.splits = fwd_splits(d, 64); }
-    if (a.splits > 1) return 0;
-    const int BN = (a.Nn % 128 == 0) ? 128 : 64;
-    ConvArgs t = a;
-    RowsArgs ra;
-    if (bf16 && conv_rows64_geometry(a, 0, ra)) return ra.nunits;
-    RowsArgsF rf;
-    if (!bf16 && conv_rowsf32_geometry(a, 0, rf)) return rf.nunits;
-    if (bf16 && conv_pp_geometry(t, 0)) return a.M / PP_BM;
-    t = a;
-    return (patch_tile_bn(t, BN, 0, bf16) || ((!bf16 || (g_igemm_big_bf16 && BN == 128)) && igemm_big_tiles(a, BN, 0))) ? cdiv(a.M, BMB) : cdiv(a.M, BM);
 }
 
 // finish of the statistics a conv epilogue left in partial rows: today's one-launch finalize, or (sums != nullptr, synchronized
@@ -5444,46 +5500,55 @@ static bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7
 
 int sd_conv2d_fwd_bn_stats_rows(const sd_conv_desc* d, int bf16) {
     if (!d || d->B <= 0 || d->Cout % 64 || d->Cin % (bf16 ? 64 : 32)) return -1;
-    return fwd_stat_rows(d, bf16 != 0);
+    return plan_query(d, 0, bf16 != 0, true).stat_rows;        // (0 = the split-K path: no fused statistics)
 }
 
 size_t sd_conv2d_fwd_bn_stats_workspace_bytes(const sd_conv_desc* d) {
     if (!d || d->Cin % 32 || d->Cout % 64) return 0;
-    const int rows = fwd_stat_rows(d);
+    const int rows = plan_query(d, 0, false, true).stat_rows;
     const size_t fused = (size_t)(rows + sd_bn_finalize_scratch_rows(rows)) * 2 * d->Cout * sizeof(float);
     const size_t split = sd_conv2d_fwd_workspace_bytes(d) + sd_col_reduce_workspace_bytes((int64_t)d->B * d->Ho * d->Wo, d->Cout);
     return std::max(fused, split);
 }
 
-static int conv_fwd_bn_stats_any(const char* what, const float* x, const float* w, float* y, const sd_conv_desc* d, float eps, float momentum,
+// Forward conv + training BatchNorm statistics, fp32 or bf16 operands.  The statistics come out of the conv's epilogue, in the partial rows
+// its plan names; a split-K plan (small batch) fuses none: plain conv, then the separate statistics pass over the output.
+static int conv_fwd_bn_stats_any(const char* what, bool bf16, const void* x, const void* w, void* y, const sd_conv_desc* d, float eps, float momentum,
                                  float* running_mean, float* running_var, float* mean, float* invstd, double* sums, void* workspace,
                                  size_t workspace_bytes, sd_stream_t stream) {
     if (int e = check_conv(what, d)) return e;
     SD_REQUIRE(x && w && y && (sums || (mean && invstd)) && workspace, SD_ERR_INVALID, "%s: null pointer", what);
-    SD_REQUIRE(d->Cin % 32 == 0 && d->Cout % 64 == 0, SD_ERR_INVALID, "%s: needs Cin %% 32 == 0 and Cout %% 64 == 0 (got %d, %d)",
-               what, d->Cin, d->Cout);
+    const int cm = bf16 ? 64 : 32;
+    SD_REQUIRE(d->Cin % cm == 0 && d->Cout % 64 == 0, SD_ERR_INVALID, "%s: needs Cin %% %d == 0 and Cout %% 64 == 0 (got %d, %d)",
+               what, cm, d->Cin, d->Cout);
     SD_REQUIRE(aligned16(x) && aligned16(w) && aligned16(y) && aligned8(sums), SD_ERR_ALIGN, "%s: pointers must be 16-byte aligned (sums: 8-byte)", what);
-    SD_REQUIRE(workspace_bytes >= sd_conv2d_fwd_bn_stats_workspace_bytes(d), SD_ERR_WORKSPACE, "%s: workspace too small", what);
+    SD_REQUIRE(workspace_bytes >= (bf16 ? sd_conv2d_fwd_bf16_bn_stats_workspace_bytes(d) : sd_conv2d_fwd_bn_stats_workspace_bytes(d)),
+               SD_ERR_WORKSPACE, "%s: workspace too small", what);
     const int64_t M = (int64_t)d->B * d->Ho * d->Wo;
-    const int rows = fwd_stat_rows(d);
-    if (rows == 0) {        // small batch (split-K): plain conv, then the separate statistics pass
-        const size_t cw = sd_conv2d_fwd_workspace_bytes(d);
-        if (int e = sd_conv2d_fwd(x, w, y, d, nullptr, nullptr, nullptr, 0, 0, workspace, cw, stream)) return e;
-        if (sums) return sd_bn_train_sums(y, M, d->Cout, sums, (char*)workspace + cw, workspace_bytes - cw, stream);
-        return sd_bn_train_stats(y, M, d->Cout, eps, momentum, running_mean, running_var, mean, invstd, (char*)workspace + cw,
-                                 workspace_bytes - cw, stream);
-    }
-    ConvArgs a{};
-    fill_fwd(a, d);
+    ConvArgs a = conv_args(d, 0, bf16);
     a.x = x; a.w = w; a.y = y; a.stat = (float*)workspace;
-    if (int e = launch_igemm(a, false, (hipStream_t)stream)) return e;
+    const ConvPlan p = plan_conv(a, bf16);
+    const int rows = p.stat_rows;
+    if (rows == 0) {
+        const size_t cw = bf16 ? sd_conv2d_fwd_bf16_workspace_bytes(d) : sd_conv2d_fwd_workspace_bytes(d);
+        void* rest = (char*)workspace + cw;
+        if (bf16) {
+            if (int e = sd_conv2d_fwd_bf16(x, w, y, d, nullptr, nullptr, nullptr, 0, 0, workspace, cw, stream)) return e;
+            if (sums) return sd_bn_train_sums_bf16(y, M, d->Cout, sums, rest, workspace_bytes - cw, stream);
+            return sd_bn_train_stats_bf16(y, M, d->Cout, eps, momentum, running_mean, running_var, mean, invstd, rest, workspace_bytes - cw, stream);
+        }
+        if (int e = sd_conv2d_fwd((const float*)x, (const float*)w, (float*)y, d, nullptr, nullptr, nullptr, 0, 0, workspace, cw, stream)) return e;
+        if (sums) return sd_bn_train_sums((const float*)y, M, d->Cout, sums, rest, workspace_bytes - cw, stream);
+        return sd_bn_train_stats((const float*)y, M, d->Cout, eps, momentum, running_mean, running_var, mean, invstd, rest, workspace_bytes - cw, stream);
+    }
+    if (int e = launch_plan(p, (hipStream_t)stream)) return e;
     return bn_stats_finish((const float*)workspace, rows, M, d->Cout, eps, momentum, running_mean, running_var, mean, invstd, sums,
                            (float*)workspace + (size_t)rows * 2 * d->Cout, stream);
 }
 
 int sd_conv2d_fwd_bn_stats(const float* x, const float* w, float* y, const sd_conv_desc* d, float eps, float momentum, float* running_mean,
                            float* running_var, float* mean, float* invstd, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
-    return conv_fwd_bn_stats_any("sd_conv2d_fwd_bn_stats", x, w, y, d, eps, momentum, running_mean, running_var, mean, invstd, nullptr, workspace,
+    return conv_fwd_bn_stats_any("sd_conv2d_fwd_bn_stats", false, x, w, y, d, eps, momentum, running_mean, running_var, mean, invstd, nullptr, workspace,
                                  workspace_bytes, stream);
 }
 
@@ -5492,7 +5557,7 @@ int sd_conv2d_fwd_bn_stats(const float* x, const float* w, float* y, const sd_co
 int sd_conv2d_fwd_bn_sums(const float* x, const float* w, float* y, const sd_conv_desc* d, double* sums, void* workspace, size_t workspace_bytes,
                           sd_stream_t stream) {
     SD_REQUIRE(sums, SD_ERR_INVALID, "sd_conv2d_fwd_bn_sums: null pointer");
-    return conv_fwd_bn_stats_any("sd_conv2d_fwd_bn_sums", x, w, y, d, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr, sums, workspace, workspace_bytes,
+    return conv_fwd_bn_stats_any("sd_conv2d_fwd_bn_sums", false, x, w, y, d, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr, sums, workspace, workspace_bytes,
                                  stream);
 }
 
@@ -5509,7 +5574,7 @@ size_t sd_conv2d_stem_fwd_workspace_bytes(const sd_conv_desc* d) { (void)d; retu
 
 size_t sd_conv2d_fwd_bf16_workspace_bytes(const sd_conv_desc* d) {
     if (!d || d->Cin % 64 || d->Cout % 64) return 0;
-    const int s = fwd_splits(d, 64);
+    const int s = conv_args(d, 0, true).splits;
     return s > 1 ? (size_t)s * d->B * d->Ho * d->Wo * d->Cout * sizeof(float) : 0;
 }
 
@@ -5522,13 +5587,9 @@ int sd_conv2d_fwd_bf16(const void* x, const void* w, void* y, const sd_conv_desc
     SD_REQUIRE(aligned16(x) && aligned16(w) && aligned16(y) && aligned16(scale) && aligned16(shift) && aligned16(residual), SD_ERR_ALIGN,
                "sd_conv2d_fwd_bf16: pointers must be 16-byte aligned");
     SD_REQUIRE(!res_up2 || (d->Ho % 2 == 0 && d->Wo % 2 == 0), SD_ERR_INVALID, "sd_conv2d_fwd_bf16: res_up2 needs even Ho, Wo");
-    ConvArgs a{};
+    ConvArgs a = conv_args(d, 0, true);
     a.x = x; a.w = w; a.y = y; a.scale = scale; a.shift = shift; a.res = residual;
-    a.B = d->B; a.Hi = d->Hi; a.Wi = d->Wi; a.Ck = d->Cin; a.Ho = d->Ho; a.Wo = d->Wo; a.Nn = d->Cout; a.R = d->R; a.S = d->S;
-    a.mul = d->stride; a.div = 1; a.off = -d->pad; a.rsign = 1;
     a.relu = relu; a.res_up2 = res_up2;
-    a.M = d->B * d->Ho * d->Wo; a.kchunks = d->Cin / 64; a.nk = d->R * d->S * a.kchunks;
-    a.splits = fwd_splits(d, 64);
     if (a.splits > 1) {
         if (workspace && workspace_bytes >= sd_conv2d_fwd_bf16_workspace_bytes(d)) a.part = (float*)workspace;
         else a.splits = 1;
@@ -5551,12 +5612,9 @@ __global__ __launch_bounds__(256) void k_head_split_bf16(const float* __restrict
 
 int sd_conv2d_fwd_bf16_head_supported(const sd_conv_desc* d, int head_co) {
     if (!d || d->Cout != 128 || d->Cin % 64 || head_co < 1 || head_co > 32 || d->Wo % 4) return 0;
-    ConvArgs a{};
-    a.B = d->B; a.Hi = d->Hi; a.Wi = d->Wi; a.Ck = d->Cin; a.Ho = d->Ho; a.Wo = d->Wo; a.Nn = d->Cout; a.R = d->R; a.S = d->S;
-    a.mul = d->stride; a.div = 1; a.off = -d->pad; a.rsign = 1;
-    a.M = d->B * d->Ho * d->Wo; a.kchunks = d->Cin / 64; a.nk = d->R * d->S * a.kchunks;
-    a.splits = fwd_splits(d, 64);
-    return (a.splits <= 1 && conv_pp_geometry(a, 0)) ? 1 : 0;
+    ConvArgs a = conv_args(d, 0, true);
+    a.head_y = &g_query_operand;          // (stands for the head's output: a query launches nothing)
+    return plan_conv(a, true).family == CONV_PP_HEAD ? 1 : 0;
 }
 
 size_t sd_head_split_bf16_bytes(void) { return (size_t)2 * 32 * 128 * sizeof(uint16_t) + 32 * sizeof(float); }
@@ -5578,13 +5636,9 @@ int sd_conv2d_fwd_bf16_head(const void* x, const void* w, const sd_conv_desc* d,
                "sd_conv2d_fwd_bf16_head: needs a 3x3 / stride 1 conv onto 128 channels that takes k_conv3x3_bf16_pp and 1 <= head_co <= 32");
     SD_REQUIRE(aligned16(x) && aligned16(w) && aligned16(scale) && aligned16(shift) && aligned16(head_prepared) && aligned16(head_y), SD_ERR_ALIGN,
                "sd_conv2d_fwd_bf16_head: pointers must be 16-byte aligned");
-    ConvArgs a{};
+    ConvArgs a = conv_args(d, 0, true);     // (sd_conv2d_fwd_bf16_head_supported: no split-K for this descriptor)
     a.x = x; a.w = w; a.y = nullptr; a.scale = scale; a.shift = shift;
-    a.B = d->B; a.Hi = d->Hi; a.Wi = d->Wi; a.Ck = d->Cin; a.Ho = d->Ho; a.Wo = d->Wo; a.Nn = d->Cout; a.R = d->R; a.S = d->S;
-    a.mul = d->stride; a.div = 1; a.off = -d->pad; a.rsign = 1;
     a.relu = relu;
-    a.M = d->B * d->Ho * d->Wo; a.kchunks = d->Cin / 64; a.nk = d->R * d->S * a.kchunks;
-    a.splits = 1;
     a.head_w = (const uint16_t*)head_prepared; a.head_b = (const float*)((const uint16_t*)head_prepared + 2 * 32 * 128);
     a.head_y = head_y; a.head_co = head_co;
     return launch_igemm(a, false, (hipStream_t)stream, true);
@@ -5593,43 +5647,15 @@ int sd_conv2d_fwd_bf16_head(const void* x, const void* w, const sd_conv_desc* d,
 // ---- mixed-precision training (bf16 activations and weights, fp32 accumulation; trainer.py:115-121 autocast) -----------------
 size_t sd_conv2d_fwd_bf16_bn_stats_workspace_bytes(const sd_conv_desc* d) {
     if (!d || d->Cin % 64 || d->Cout % 64) return 0;
-    const int rows = fwd_stat_rows(d, true);
+    const int rows = plan_query(d, 0, true, true).stat_rows;
     const size_t fused = (size_t)(rows + sd_bn_finalize_scratch_rows(rows)) * 2 * d->Cout * sizeof(float);
     const size_t split = sd_conv2d_fwd_bf16_workspace_bytes(d) + sd_col_reduce_workspace_bytes((int64_t)d->B * d->Ho * d->Wo, d->Cout);
     return std::max(std::max(fused, split), (size_t)256);
 }
 
-static int conv_fwd_bf16_bn_stats_any(const char* what, const void* x, const void* w, void* y, const sd_conv_desc* d, float eps, float momentum,
-                                      float* running_mean, float* running_var, float* mean, float* invstd, double* sums, void* workspace,
-                                      size_t workspace_bytes, sd_stream_t stream) {
-    if (int e = check_conv(what, d)) return e;
-    SD_REQUIRE(x && w && y && (sums || (mean && invstd)) && workspace, SD_ERR_INVALID, "%s: null pointer", what);
-    SD_REQUIRE(d->Cin % 64 == 0 && d->Cout % 64 == 0, SD_ERR_INVALID, "%s: needs Cin %% 64 == 0 and Cout %% 64 == 0 (got %d, %d)",
-               what, d->Cin, d->Cout);
-    SD_REQUIRE(aligned16(x) && aligned16(w) && aligned16(y) && aligned8(sums), SD_ERR_ALIGN, "%s: pointers must be 16-byte aligned (sums: 8-byte)", what);
-    SD_REQUIRE(workspace_bytes >= sd_conv2d_fwd_bf16_bn_stats_workspace_bytes(d), SD_ERR_WORKSPACE, "%s: workspace too small", what);
-    const int rows = fwd_stat_rows(d, true);
-    const int64_t M = (int64_t)d->B * d->Ho * d->Wo;
-    if (rows == 0) {        // small batch (split-K): plain conv, then the separate statistics pass over the bf16 output
-        const size_t cw = sd_conv2d_fwd_bf16_workspace_bytes(d);
-        if (int e = sd_conv2d_fwd_bf16(x, w, y, d, nullptr, nullptr, nullptr, 0, 0, workspace, cw, stream)) return e;
-        if (sums) return sd_bn_train_sums_bf16(y, M, d->Cout, sums, (char*)workspace + cw, workspace_bytes - cw, stream);
-        return sd_bn_train_stats_bf16(y, M, d->Cout, eps, momentum, running_mean, running_var, mean, invstd, (char*)workspace + cw,
-                                      workspace_bytes - cw, stream);
-    }
-    ConvArgs a{};
-    a.x = x; a.w = w; a.y = y; a.stat = (float*)workspace;
-    a.B = d->B; a.Hi = d->Hi; a.Wi = d->Wi; a.Ck = d->Cin; a.Ho = d->Ho; a.Wo = d->Wo; a.Nn = d->Cout; a.R = d->R; a.S = d->S;
-    a.mul = d->stride; a.div = 1; a.off = -d->pad; a.rsign = 1;
-    a.M = d->B * d->Ho * d->Wo; a.kchunks = d->Cin / 64; a.nk = d->R * d->S * a.kchunks; a.splits = 1;
-    if (int e = launch_igemm(a, false, (hipStream_t)stream, true)) return e;
-    return bn_stats_finish((const float*)workspace, rows, M, d->Cout, eps, momentum, running_mean, running_var, mean, invstd, sums,
-                           (float*)workspace + (size_t)rows * 2 * d->Cout, stream);
-}
-
 int sd_conv2d_fwd_bf16_bn_stats(const void* x, const void* w, void* y, const sd_conv_desc* d, float eps, float momentum, float* running_mean,
                                 float* running_var, float* mean, float* invstd, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
-    return conv_fwd_bf16_bn_stats_any("sd_conv2d_fwd_bf16_bn_stats", x, w, y, d, eps, momentum, running_mean, running_var, mean, invstd, nullptr,
+    return conv_fwd_bn_stats_any("sd_conv2d_fwd_bf16_bn_stats", true, x, w, y, d, eps, momentum, running_mean, running_var, mean, invstd, nullptr,
                                       workspace, workspace_bytes, stream);
 }
 
@@ -5637,7 +5663,7 @@ int sd_conv2d_fwd_bf16_bn_stats(const void* x, const void* w, void* y, const sd_
 int sd_conv2d_fwd_bf16_bn_sums(const void* x, const void* w, void* y, const sd_conv_desc* d, double* sums, void* workspace, size_t workspace_bytes,
                                sd_stream_t stream) {
     SD_REQUIRE(sums, SD_ERR_INVALID, "sd_conv2d_fwd_bf16_bn_sums: null pointer");
-    return conv_fwd_bf16_bn_stats_any("sd_conv2d_fwd_bf16_bn_sums", x, w, y, d, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr, sums, workspace,
+    return conv_fwd_bn_stats_any("sd_conv2d_fwd_bf16_bn_sums", true, x, w, y, d, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr, sums, workspace,
                                       workspace_bytes, stream);
 }
 
@@ -5649,9 +5675,7 @@ int sd_conv2d_dgrad_bf16(const void* dy, const void* w_t, void* dx, const sd_con
     SD_REQUIRE(d->Cout % 64 == 0 && d->Cin % 64 == 0, SD_ERR_INVALID, "sd_conv2d_dgrad_bf16: needs Cout %% 64 == 0 and Cin %% 64 == 0");
     SD_REQUIRE(res_mode != 2 || (d->Hi % 2 == 0 && d->Wi % 2 == 0), SD_ERR_INVALID, "sd_conv2d_dgrad_bf16: a half-size residual needs even Hi, Wi");
     SD_REQUIRE(aligned16(dy) && aligned16(w_t) && aligned16(dx) && aligned16(residual), SD_ERR_ALIGN, "sd_conv2d_dgrad_bf16: pointers must be 16-byte aligned");
-    ConvArgs a{};
-    fill_dgrad(a, d);
-    a.kchunks = d->Cout / 64; a.nk = d->R * d->S * a.kchunks;
+    ConvArgs a = conv_args(d, 1, true);
     a.x = dy; a.w = w_t; a.y = dx; a.res = res_mode ? residual : nullptr; a.res_up2 = res_mode == 2 ? 2 : 0;
     return launch_igemm(a, false, (hipStream_t)stream, true);
 }
@@ -5683,11 +5707,9 @@ int sd_conv2d_stem_fwd(const float* x_nchw, const float* w, void* y, const sd_co
         return 0;
     }
     SD_REQUIRE(!out_bf16, SD_ERR_INVALID, "sd_conv2d_stem_fwd: bf16 output needs the 7x7/2 geometry and a workspace");
-    ConvArgs a{};
+    ConvArgs a = conv_args(d, 0, false);      // (Ck = 3, Nn = 64: required above)
     a.x = x_nchw; a.w = w; a.y = y; a.scale = scale; a.shift = shift; a.relu = relu;
-    a.B = d->B; a.Hi = d->Hi; a.Wi = d->Wi; a.Ck = 3; a.Ho = d->Ho; a.Wo = d->Wo; a.Nn = 64; a.R = d->R; a.S = d->S;
-    a.mul = d->stride; a.div = 1; a.off = -d->pad; a.rsign = 1;
-    a.M = d->B * d->Ho * d->Wo; a.kchunks = 1; a.nk = cdiv(d->R * d->S * 3, BK);
+    a.kchunks = 1; a.nk = cdiv(d->R * d->S * 3, BK); a.splits = 0;      // MODE 1: K = all taps x 3 channels, in 32-element chunks
     return launch_igemm(a, true, st);
 }
 
@@ -5842,8 +5864,7 @@ int sd_conv2d_dgrad_half_res(const float* dy, const float* w_t, float* dx, const
     SD_REQUIRE(d->Hi % 2 == 0 && d->Wi % 2 == 0, SD_ERR_INVALID, "sd_conv2d_dgrad_half_res: needs even Hi, Wi");
     SD_REQUIRE(aligned16(dy) && aligned16(w_t) && aligned16(dx) && aligned16(residual_half), SD_ERR_ALIGN,
                "sd_conv2d_dgrad_half_res: pointers must be 16-byte aligned");
-    ConvArgs a{};
-    fill_dgrad(a, d);
+    ConvArgs a = conv_args(d, 1, false);
     a.x = dy; a.w = w_t; a.y = dx; a.res = residual_half; a.res_up2 = 2;
     return launch_igemm(a, false, (hipStream_t)stream);
 }
@@ -5853,8 +5874,7 @@ int sd_conv2d_dgrad(const float* dy, const float* w_t, float* dx, const sd_conv_
     SD_REQUIRE(dy && w_t && dx, SD_ERR_INVALID, "sd_conv2d_dgrad: null pointer");
     SD_REQUIRE(d->Cout % 32 == 0 && d->Cin % 64 == 0, SD_ERR_INVALID, "sd_conv2d_dgrad: needs Cout %% 32 == 0 and Cin %% 64 == 0");
     SD_REQUIRE(aligned16(dy) && aligned16(w_t) && aligned16(dx) && aligned16(residual), SD_ERR_ALIGN, "sd_conv2d_dgrad: pointers must be 16-byte aligned");
-    ConvArgs a{};
-    fill_dgrad(a, d);
+    ConvArgs a = conv_args(d, 1, false);
     a.x = dy; a.w = w_t; a.y = dx; a.res = residual;
     return launch_igemm(a, false, (hipStream_t)stream);
 }
@@ -5891,11 +5911,8 @@ static bool wgrad_all_taps(const sd_conv_desc* d) {
 
 static thread_local int g_wgrad_f32_ring = 2;        // sd_set_option("wgrad_f32_ring", n): 2 = k_wgrad3x3_ring2 (two groups per 512-thread block), 1 = k_wgrad3x3_ring, 0 = k_wgrad3x3<32> (A/B, tests)
 static thread_local int g_wgrad_bf16_ring = 5;       // sd_set_option("wgrad_bf16_ring", n): 5 (default) = k_wgrad3x3_bf16_ring2 (two groups per 512-thread block); 2 .. 4 = k_wgrad3x3_bf16_ring with that prefetch distance; 0 = k_wgrad3x3_bf16<32> (A/B, tests)
-static int wgrad_splits(const sd_conv_desc* d, int tiles) {
-    if (wgrad_all_taps(d)) {
-        const int chunks = d->B * d->Ho * d->Wo / 32;
-        return std::max(1, std::min(cdiv(512, tiles), chunks / 8));      // two resident blocks per CU, >= 8 chunks each
-    }
+// split count of the tap-per-block kernels
+static int wgrad_tile_splits(const sd_conv_desc* d, int tiles) {
     // Pick the split count so that tiles*splits fills whole "rounds" of the chip (256 CUs x 2 resident 128x128
     // blocks, x4 for the 64x64 tile): a last round that is mostly empty costs as much as a full one.
     const int M = d->B * d->Ho * d->Wo;
@@ -5913,11 +5930,104 @@ static int wgrad_splits(const sd_conv_desc* d, int tiles) {
     return best_s;
 }
 
+// ---- how a weight gradient is dispatched: plan_wgrad() decides kernel, tile, grid, splits and workspace for sd_conv2d_wgrad /
+// sd_conv2d_wgrad_bf16, their size queries and pass 2 of sd_conv2d_kernel_name ----------------------------------------------------------
+enum WgradFamily {
+    WGRAD_TAPS_RING2,    // k_wgrad3x3_ring2 / k_wgrad3x3_bf16_ring2
+    WGRAD_TAPS_RING,     // k_wgrad3x3_ring / k_wgrad3x3_bf16_ring<ring_d>
+    WGRAD_TAPS,          // k_wgrad3x3<roww> / k_wgrad3x3_bf16<roww>
+    WGRAD_TILE,          // k_conv_wgrad<TN, TC>
+    WGRAD_TAP_BF16,      // k_wgrad_tap_bf16<TC>
+    WGRAD_WIDEN,         // bf16 operands widened to fp32 in the workspace, then the fp32 plan (Cout not a multiple of 128: no such layer in SDNet)
+};
+
+struct WgradPlan {
+    WgradFamily family;
+    int TN, TC, tiles;       // (Cout, Cin) tile and their count (x taps for the one-tap-per-block kernels)
+    int roww, ring_d;        // WGRAD_TAPS: chunk row width 32 / 16; bf16 WGRAD_TAPS_RING: prefetch distance
+    int splits;              // pixel splits the kernel is LAUNCHED with = partial tensors the reduce pass reads
+    int m_per_split;         // pixels per split (the kernels that split by pixel index)
+    int strips, chunks_total, chunks_per_split;       // ring kernels: they split by chunk
+    size_t part_bytes;       // the partial tensors at the start of the workspace: room for `splits` or a bound that is not smaller
+    size_t workspace_bytes;
+};
+
+static WgradPlan plan_wgrad(const sd_conv_desc* d, bool bf16) {
+    WgradPlan p{};
+    const size_t dw_bytes = (size_t)d->Cout * d->R * d->S * d->Cin * sizeof(float);
+    const int M = d->B * d->Ho * d->Wo;
+    if (wgrad_all_taps(d)) {
+        p.TN = p.TC = 64; p.tiles = (d->Cout / 64) * (d->Cin / 64);
+        const int chunks = M / 32;
+        const int bound = std::max(1, std::min(cdiv(512, p.tiles), chunks / 8));      // two resident blocks per CU, >= 8 chunks each
+        const int ring = bf16 ? g_wgrad_bf16_ring : g_wgrad_f32_ring;
+        p.splits = bound;
+        p.m_per_split = cdiv(cdiv(M, p.splits), 32) * 32;
+        if (d->Wo % 32 == 0 && ring) {
+            p.strips = d->Wo / 32; p.chunks_total = d->B * p.strips * d->Ho;           // (= chunks)
+            if (ring >= (bf16 ? 5 : 2)) {
+                // one 512-thread block per CU, two groups half a chunk apart: half as many (twice as long) splits, and none of them empty.
+                // min(cdiv(256, tiles), chunks / 16) <= min(cdiv(512, tiles), chunks / 8) = bound, and the second line only lowers it
+                p.family = WGRAD_TAPS_RING2;
+                p.splits = std::max(1, std::min(cdiv(256, p.tiles), p.chunks_total / 16));
+                p.chunks_per_split = cdiv(p.chunks_total, p.splits);
+                p.splits = cdiv(p.chunks_total, p.chunks_per_split);
+            } else {
+                p.family = WGRAD_TAPS_RING;
+                p.ring_d = ring == 2 ? 2 : (ring >= 4 ? 4 : 3);
+                p.chunks_per_split = cdiv(p.chunks_total, p.splits);
+            }
+        } else {
+            p.family = WGRAD_TAPS;
+            p.roww = d->Wo % 32 == 0 ? 32 : 16;
+        }
+        p.part_bytes = (size_t)bound * dw_bytes;          // (every option setting fits: the caller may size once and switch kernels)
+        p.workspace_bytes = bf16 ? align_up(p.part_bytes, 256) : p.part_bytes;
+        return p;
+    }
+    if (bf16 && d->Cout % 128 == 0 && d->Cin % 64 == 0) {
+        p.family = WGRAD_TAP_BF16;
+        p.TN = 128; p.TC = d->Cin % 128 == 0 ? 128 : 64; p.tiles = d->R * d->S * (d->Cout / p.TN) * (d->Cin / p.TC);
+        p.splits = std::max(1, std::min(cdiv(1024, p.tiles), M / 256));      // fill two blocks per CU (512 slots) with whole rounds, at least 8 chunks (256 pixels) per split
+        p.m_per_split = cdiv(cdiv(M, p.splits), 32) * 32;
+        p.part_bytes = p.workspace_bytes = align_up((size_t)p.splits * dw_bytes, 256);
+        return p;
+    }
+    p.family = WGRAD_TILE;
+    p.TN = d->Cout % 128 == 0 ? 128 : 64; p.TC = d->Cin % 128 == 0 ? 128 : 64; p.tiles = d->R * d->S * (d->Cout / p.TN) * (d->Cin / p.TC);
+    p.splits = p.tiles ? wgrad_tile_splits(d, p.tiles) : 1;      // (no tiles: channel counts the launcher refuses; the name query still gets its tile)
+    p.m_per_split = cdiv(cdiv(M, p.splits), 32) * 32;
+    p.part_bytes = p.workspace_bytes = (size_t)p.splits * dw_bytes;
+    if (bf16) {
+        p.family = WGRAD_WIDEN;
+        p.part_bytes = align_up(p.part_bytes, 256);
+        p.workspace_bytes = p.part_bytes + align_up((size_t)M * d->Cout * 4, 256) + align_up((size_t)d->B * d->Hi * d->Wi * d->Cin * 4, 256);
+    }
+    return p;
+}
+
+// descriptor + plan -> the fields the weight-gradient argument structs share
+extern "C++" template <typename A>
+static void wgrad_args(A& a, const sd_conv_desc* d, const WgradPlan& p) {
+    a.B = d->B; a.Hi = d->Hi; a.Wi = d->Wi; a.Ck = d->Cin; a.Ho = d->Ho; a.Wo = d->Wo; a.Nn = d->Cout;
+    a.M = d->B * d->Ho * d->Wo; a.splits = p.splits; a.m_per_split = p.m_per_split;
+    if constexpr (!std::is_same_v<A, WgradArgs16>) { a.R = d->R; a.S = d->S; a.stride = d->stride; a.pad = d->pad; }
+    if constexpr (!std::is_same_v<A, WgradArgs16t>) { a.strips = p.strips; a.chunks_total = p.chunks_total; a.chunks_per_split = p.chunks_per_split; }
+}
+
+// deterministic sum of the plan's partial tensors into dw
+static int wgrad_reduce(const WgradPlan& p, const sd_conv_desc* d, const void* workspace, float* dw, int accumulate, hipStream_t st) {
+    const int64_t n4 = (int64_t)d->Cout * d->R * d->S * d->Cin / 4;
+    const bool taps = p.family == WGRAD_TAPS_RING2 || p.family == WGRAD_TAPS_RING || p.family == WGRAD_TAPS;
+    if (taps || p.splits >= 16) hipLaunchKernelGGL(k_wgrad_reduce_par, dim3(cdiv(n4, 32)), dim3(256), 0, st, (const float*)workspace, dw, n4, p.splits, accumulate);
+    else hipLaunchKernelGGL(k_wgrad_reduce, dim3(cdiv(n4, 256)), dim3(256), 0, st, (const float*)workspace, dw, n4, p.splits, accumulate);
+    SD_LAUNCH_CHECK();
+    return 0;
+}
+
 size_t sd_conv2d_wgrad_workspace_bytes(const sd_conv_desc* d) {
     if (!d || d->Cin % 64 || d->Cout % 64) return 0;
-    const int TN = d->Cout % 128 == 0 ? 128 : 64, TC = d->Cin % 128 == 0 ? 128 : 64;
-    const int tiles = wgrad_all_taps(d) ? (d->Cout / 64) * (d->Cin / 64) : d->R * d->S * (d->Cout / TN) * (d->Cin / TC);
-    return (size_t)wgrad_splits(d, tiles) * d->Cout * d->R * d->S * d->Cin * sizeof(float);
+    return plan_wgrad(d, false).workspace_bytes;
 }
 
 int sd_conv2d_wgrad(const float* dy, const float* x, float* dw, const sd_conv_desc* d, int accumulate, void* workspace,
@@ -5925,68 +6035,42 @@ int sd_conv2d_wgrad(const float* dy, const float* x, float* dw, const sd_conv_de
     if (int e = check_conv("sd_conv2d_wgrad", d)) return e;
     SD_REQUIRE(dy && x && dw && workspace, SD_ERR_INVALID, "sd_conv2d_wgrad: null pointer");
     SD_REQUIRE(d->Cin % 64 == 0 && d->Cout % 64 == 0, SD_ERR_INVALID, "sd_conv2d_wgrad: needs Cin, Cout %% 64 == 0");
-    SD_REQUIRE(workspace_bytes >= sd_conv2d_wgrad_workspace_bytes(d), SD_ERR_WORKSPACE, "sd_conv2d_wgrad: workspace too small");
-    const int TN = d->Cout % 128 == 0 ? 128 : 64, TC = d->Cin % 128 == 0 ? 128 : 64;
-    const int tiles = wgrad_all_taps(d) ? (d->Cout / 64) * (d->Cin / 64) : d->R * d->S * (d->Cout / TN) * (d->Cin / TC);
+    const WgradPlan p = plan_wgrad(d, false);
+    SD_REQUIRE(workspace_bytes >= p.workspace_bytes, SD_ERR_WORKSPACE, "sd_conv2d_wgrad: workspace too small");
     WgradArgs a{};
     a.dy = dy; a.x = x; a.part = (float*)workspace;
-    a.B = d->B; a.Hi = d->Hi; a.Wi = d->Wi; a.Ck = d->Cin; a.Ho = d->Ho; a.Wo = d->Wo; a.Nn = d->Cout; a.R = d->R; a.S = d->S;
-    a.stride = d->stride; a.pad = d->pad;
-    a.M = d->B * d->Ho * d->Wo;
-    a.splits = wgrad_splits(d, tiles);
-    a.m_per_split = cdiv(cdiv(a.M, a.splits), 32) * 32;
+    wgrad_args(a, d, p);
     hipStream_t st = (hipStream_t)stream;
-    const int64_t n4 = (int64_t)d->Cout * d->R * d->S * d->Cin / 4;
-    if (wgrad_all_taps(d)) {
-        if (d->Wo % 32 == 0 && g_wgrad_f32_ring >= 2) {
-            a.strips = d->Wo / 32; a.chunks_total = d->B * a.strips * d->Ho;
-            a.splits = std::max(1, std::min(cdiv(256, tiles), a.chunks_total / 16));
-            a.chunks_per_split = cdiv(a.chunks_total, a.splits);
-            a.splits = cdiv(a.chunks_total, a.chunks_per_split);
-            hipLaunchKernelGGL(k_wgrad3x3_ring2, dim3(a.splits, tiles), dim3(512), 0, st, a);
-        } else if (d->Wo % 32 == 0 && g_wgrad_f32_ring) {
-            a.strips = d->Wo / 32; a.chunks_total = d->B * a.strips * d->Ho; a.chunks_per_split = cdiv(a.chunks_total, a.splits);
-            hipLaunchKernelGGL(k_wgrad3x3_ring, dim3(a.splits, tiles), dim3(256), 0, st, a);
-        } else if (d->Wo % 32 == 0) hipLaunchKernelGGL(k_wgrad3x3<32>, dim3(a.splits, tiles), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL(k_wgrad3x3<16>, dim3(a.splits, tiles), dim3(256), 0, st, a);
-        SD_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_wgrad_reduce_par, dim3(cdiv(n4, 32)), dim3(256), 0, st, (const float*)workspace, dw, n4, a.splits, accumulate);
-        SD_LAUNCH_CHECK();
-        return 0;
+    const dim3 taps_grid(p.splits, p.tiles);
+    switch (p.family) {
+    case WGRAD_TAPS_RING2: hipLaunchKernelGGL(k_wgrad3x3_ring2, taps_grid, dim3(512), 0, st, a); break;
+    case WGRAD_TAPS_RING: hipLaunchKernelGGL(k_wgrad3x3_ring, taps_grid, dim3(256), 0, st, a); break;
+    case WGRAD_TAPS:
+        if (p.roww == 32) hipLaunchKernelGGL(k_wgrad3x3<32>, taps_grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(k_wgrad3x3<16>, taps_grid, dim3(256), 0, st, a);
+        break;
+    default: {
+        const size_t lds = (size_t)2 * 32 * (p.TN + 4 + p.TC + 4) * sizeof(float);
+        const dim3 grid(p.tiles, p.splits);
+        static const hipError_t attr_once = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_wgrad<128, 128>),
+                                                                hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 32 * (128 + 4 + 128 + 4) * 4);
+        (void)attr_once;
+        if (p.TN == 128 && p.TC == 128) hipLaunchKernelGGL((k_conv_wgrad<128, 128>), grid, dim3(256), lds, st, a);
+        else if (p.TN == 128) hipLaunchKernelGGL((k_conv_wgrad<128, 64>), grid, dim3(256), lds, st, a);
+        else if (p.TC == 128) hipLaunchKernelGGL((k_conv_wgrad<64, 128>), grid, dim3(256), lds, st, a);
+        else hipLaunchKernelGGL((k_conv_wgrad<64, 64>), grid, dim3(256), lds, st, a);
     }
-    const size_t lds = (size_t)2 * 32 * (TN + 4 + TC + 4) * sizeof(float);
-    dim3 grid(tiles, a.splits);
-    static const hipError_t attr_once = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_wgrad<128, 128>),
-                                                            hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 32 * (128 + 4 + 128 + 4) * 4);
-    (void)attr_once;
-    if (TN == 128 && TC == 128) hipLaunchKernelGGL((k_conv_wgrad<128, 128>), grid, dim3(256), lds, st, a);
-    else if (TN == 128) hipLaunchKernelGGL((k_conv_wgrad<128, 64>), grid, dim3(256), lds, st, a);
-    else if (TC == 128) hipLaunchKernelGGL((k_conv_wgrad<64, 128>), grid, dim3(256), lds, st, a);
-    else hipLaunchKernelGGL((k_conv_wgrad<64, 64>), grid, dim3(256), lds, st, a);
+    }
     SD_LAUNCH_CHECK();
-    if (a.splits >= 16) hipLaunchKernelGGL(k_wgrad_reduce_par, dim3(cdiv(n4, 32)), dim3(256), 0, st, (const float*)workspace, dw, n4, a.splits, accumulate);
-    else hipLaunchKernelGGL(k_wgrad_reduce, dim3(cdiv(n4, 256)), dim3(256), 0, st, (const float*)workspace, dw, n4, a.splits, accumulate);
-    SD_LAUNCH_CHECK();
-    return 0;
+    return wgrad_reduce(p, d, workspace, dw, accumulate, st);
 }
 
 // ---- mixed-precision weight gradient: dY and X bf16, dW fp32.  3x3 / stride 1 layers (32 of the 42 weight-gradient launches of a
-// step, 97 % of the flops) run k_wgrad3x3_bf16; the strided and 1x1 convs widen their operands to fp32 in the workspace and take
-// the fp32 kernels (exact: a bf16 value is an fp32 value).
-static bool wgrad_tap_bf16(const sd_conv_desc* d) { return !wgrad_all_taps(d) && d->Cout % 128 == 0 && d->Cin % 64 == 0; }
-static int wgrad_tap_bf16_tiles(const sd_conv_desc* d) { return d->R * d->S * (d->Cout / 128) * (d->Cin / (d->Cin % 128 == 0 ? 128 : 64)); }
-static int wgrad_tap_bf16_splits(const sd_conv_desc* d) {
-    // fill two blocks per CU (512 slots) with whole rounds, at least 8 chunks (256 pixels) per split
-    const int tiles = wgrad_tap_bf16_tiles(d), M = d->B * d->Ho * d->Wo;
-    return std::max(1, std::min(cdiv(1024, tiles), M / 256));
-}
-
+// step, 97 % of the flops) run k_wgrad3x3_bf16; the strided and 1x1 convs onto multiples of 128 channels run k_wgrad_tap_bf16; the rest
+// widen their operands to fp32 in the workspace and take the fp32 kernels (exact: a bf16 value is an fp32 value).
 size_t sd_conv2d_wgrad_bf16_workspace_bytes(const sd_conv_desc* d) {
     if (!d || d->Cin % 64 || d->Cout % 64) return 0;
-    const size_t base = align_up(sd_conv2d_wgrad_workspace_bytes(d), 256);
-    if (wgrad_all_taps(d)) return base;
-    if (wgrad_tap_bf16(d)) return align_up((size_t)wgrad_tap_bf16_splits(d) * d->Cout * d->R * d->S * d->Cin * sizeof(float), 256);
-    return base + align_up((size_t)d->B * d->Ho * d->Wo * d->Cout * 4, 256) + align_up((size_t)d->B * d->Hi * d->Wi * d->Cin * 4, 256);
+    return plan_wgrad(d, true).workspace_bytes;
 }
 
 int sd_conv2d_wgrad_bf16(const void* dy, const void* x, float* dw, const sd_conv_desc* d, int accumulate, void* workspace,
@@ -5995,62 +6079,40 @@ int sd_conv2d_wgrad_bf16(const void* dy, const void* x, float* dw, const sd_conv
     SD_REQUIRE(dy && x && dw && workspace, SD_ERR_INVALID, "sd_conv2d_wgrad_bf16: null pointer");
     SD_REQUIRE(d->Cin % 64 == 0 && d->Cout % 64 == 0, SD_ERR_INVALID, "sd_conv2d_wgrad_bf16: needs Cin, Cout %% 64 == 0");
     SD_REQUIRE(aligned16(dy) && aligned16(x), SD_ERR_ALIGN, "sd_conv2d_wgrad_bf16: pointers must be 16-byte aligned");
-    SD_REQUIRE(workspace_bytes >= sd_conv2d_wgrad_bf16_workspace_bytes(d), SD_ERR_WORKSPACE, "sd_conv2d_wgrad_bf16: workspace too small");
+    const WgradPlan p = plan_wgrad(d, true);
+    SD_REQUIRE(workspace_bytes >= p.workspace_bytes, SD_ERR_WORKSPACE, "sd_conv2d_wgrad_bf16: workspace too small");
     hipStream_t st = (hipStream_t)stream;
-    if (wgrad_tap_bf16(d)) {
-        WgradArgs16t a{};
-        a.dy = (const uint16_t*)dy; a.x = (const uint16_t*)x; a.part = (float*)workspace;
-        a.B = d->B; a.Hi = d->Hi; a.Wi = d->Wi; a.Ck = d->Cin; a.Ho = d->Ho; a.Wo = d->Wo; a.Nn = d->Cout; a.R = d->R; a.S = d->S;
-        a.stride = d->stride; a.pad = d->pad;
-        a.M = d->B * d->Ho * d->Wo;
-        a.splits = wgrad_tap_bf16_splits(d);
-        a.m_per_split = cdiv(cdiv(a.M, a.splits), 32) * 32;
-        const dim3 grid(a.splits, wgrad_tap_bf16_tiles(d));
-        if (d->Cin % 128 == 0) hipLaunchKernelGGL(k_wgrad_tap_bf16<128>, grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL(k_wgrad_tap_bf16<64>, grid, dim3(256), 0, st, a);
-        SD_LAUNCH_CHECK();
-        const int64_t n4 = (int64_t)d->Cout * d->R * d->S * d->Cin / 4;
-        if (a.splits >= 16) hipLaunchKernelGGL(k_wgrad_reduce_par, dim3(cdiv(n4, 32)), dim3(256), 0, st, (const float*)workspace, dw, n4, a.splits, accumulate);
-        else hipLaunchKernelGGL(k_wgrad_reduce, dim3(cdiv(n4, 256)), dim3(256), 0, st, (const float*)workspace, dw, n4, a.splits, accumulate);
-        SD_LAUNCH_CHECK();
-        return 0;
-    }
-    if (!wgrad_all_taps(d)) {       // (Cout not a multiple of 128: no such layer in SDNet) widen to fp32 in the workspace, fp32 kernels
-        const size_t base = align_up(sd_conv2d_wgrad_workspace_bytes(d), 256);
+    if (p.family == WGRAD_WIDEN) {
         const int64_t ndy = (int64_t)d->B * d->Ho * d->Wo * d->Cout, nx = (int64_t)d->B * d->Hi * d->Wi * d->Cin;
-        float* dy32 = reinterpret_cast<float*>((char*)workspace + base);
-        float* x32 = reinterpret_cast<float*>((char*)workspace + base + align_up((size_t)ndy * 4, 256));
+        float* dy32 = reinterpret_cast<float*>((char*)workspace + p.part_bytes);
+        float* x32 = reinterpret_cast<float*>((char*)workspace + p.part_bytes + align_up((size_t)ndy * 4, 256));
         if (int e = sd_cast_bf16_to_f32(dy, dy32, ndy, stream)) return e;
         if (int e = sd_cast_bf16_to_f32(x, x32, nx, stream)) return e;
-        return sd_conv2d_wgrad(dy32, x32, dw, d, accumulate, workspace, base, stream);
+        return sd_conv2d_wgrad(dy32, x32, dw, d, accumulate, workspace, p.part_bytes, stream);
     }
-    const int tiles = (d->Cout / 64) * (d->Cin / 64);
+    if (p.family == WGRAD_TAP_BF16) {
+        WgradArgs16t a{};
+        a.dy = (const uint16_t*)dy; a.x = (const uint16_t*)x; a.part = (float*)workspace;
+        wgrad_args(a, d, p);
+        const dim3 grid(p.splits, p.tiles);
+        if (p.TC == 128) hipLaunchKernelGGL(k_wgrad_tap_bf16<128>, grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(k_wgrad_tap_bf16<64>, grid, dim3(256), 0, st, a);
+        SD_LAUNCH_CHECK();
+        return wgrad_reduce(p, d, workspace, dw, accumulate, st);
+    }
     WgradArgs16 a{};
     a.dy = (const uint16_t*)dy; a.x = (const uint16_t*)x; a.part = (float*)workspace;
-    a.B = d->B; a.Hi = d->Hi; a.Wi = d->Wi; a.Ck = d->Cin; a.Ho = d->Ho; a.Wo = d->Wo; a.Nn = d->Cout;
-    a.M = d->B * d->Ho * d->Wo;
-    a.splits = wgrad_splits(d, tiles);
-    a.m_per_split = cdiv(cdiv(a.M, a.splits), 32) * 32;
-    const int64_t n4 = (int64_t)d->Cout * 9 * d->Cin / 4;
-    if (d->Wo % 32 == 0 && g_wgrad_bf16_ring >= 5) {
-        // one 512-thread block per CU, two groups half a chunk apart: half as many (twice as long) splits
-        a.strips = d->Wo / 32; a.chunks_total = d->B * a.strips * d->Ho;
-        a.splits = std::max(1, std::min(cdiv(256, tiles), a.chunks_total / 16));
-        a.chunks_per_split = cdiv(a.chunks_total, a.splits);
-        a.splits = cdiv(a.chunks_total, a.chunks_per_split);
-        hipLaunchKernelGGL(k_wgrad3x3_bf16_ring2, dim3(a.splits, tiles), dim3(512), 0, st, a);
-    } else if (d->Wo % 32 == 0 && g_wgrad_bf16_ring) {
-        a.strips = d->Wo / 32; a.chunks_total = d->B * a.strips * d->Ho; a.chunks_per_split = cdiv(a.chunks_total, a.splits);
-        if (g_wgrad_bf16_ring == 2) hipLaunchKernelGGL(k_wgrad3x3_bf16_ring<2>, dim3(a.splits, tiles), dim3(256), 0, st, a);
-        else if (g_wgrad_bf16_ring == 3) hipLaunchKernelGGL(k_wgrad3x3_bf16_ring<3>, dim3(a.splits, tiles), dim3(256), 0, st, a);
-        else if (g_wgrad_bf16_ring >= 4) hipLaunchKernelGGL(k_wgrad3x3_bf16_ring<4>, dim3(a.splits, tiles), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL(k_wgrad3x3_bf16_ring<3>, dim3(a.splits, tiles), dim3(256), 0, st, a);
-    } else if (d->Wo % 32 == 0) hipLaunchKernelGGL(k_wgrad3x3_bf16<32>, dim3(a.splits, tiles), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(k_wgrad3x3_bf16<16>, dim3(a.splits, tiles), dim3(256), 0, st, a);
+    wgrad_args(a, d, p);
+    const dim3 grid(p.splits, p.tiles);
+    if (p.family == WGRAD_TAPS_RING2) hipLaunchKernelGGL(k_wgrad3x3_bf16_ring2, grid, dim3(512), 0, st, a);
+    else if (p.family == WGRAD_TAPS_RING) {
+        if (p.ring_d == 2) hipLaunchKernelGGL(k_wgrad3x3_bf16_ring<2>, grid, dim3(256), 0, st, a);
+        else if (p.ring_d == 3) hipLaunchKernelGGL(k_wgrad3x3_bf16_ring<3>, grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(k_wgrad3x3_bf16_ring<4>, grid, dim3(256), 0, st, a);
+    } else if (p.roww == 32) hipLaunchKernelGGL(k_wgrad3x3_bf16<32>, grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_wgrad3x3_bf16<16>, grid, dim3(256), 0, st, a);
     SD_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_wgrad_reduce_par, dim3(cdiv(n4, 32)), dim3(256), 0, st, (const float*)workspace, dw, n4, a.splits, accumulate);
-    SD_LAUNCH_CHECK();
-    return 0;
+    return wgrad_reduce(p, d, workspace, dw, accumulate, st);
 }
 
 int sd_stem_bn_relu_maxpool_fwd_bf16(const float* x_nchw, const float* w, const float* scale, const float* shift, void* y, const sd_conv_desc* d,
@@ -6164,19 +6226,9 @@ int sd_conv2d_stem_wgrad_bf16(const void* dy_bf16, const float* x_nchw, float* d
     return 0;
 }
 
-// partial rows the data-gradient kernel of this geometry writes for the fused BatchNorm-backward reduction
-static int dgrad_stat_rows(const sd_conv_desc* d) {
-    ConvArgs a{};
-    fill_dgrad(a, d);
-    const int BN = (a.Nn % 128 == 0) ? 128 : 64;
-    const int mode = a.par ? 2 : (a.div > 1 ? 3 : 0);
-    ConvArgs t = a;
-    return (patch_tile_bn(t, BN, mode, false) || igemm_big_tiles(a, BN, mode)) ? cdiv(a.M, BMB) : cdiv(a.M, BM);
-}
-
 size_t sd_conv2d_dgrad_bn_reduce_workspace_bytes(const sd_conv_desc* d) {
     if (!d || d->Cin % 64 || d->Cout % 32) return 0;
-    const int rows = dgrad_stat_rows(d);
+    const int rows = plan_query(d, 1, false, true).stat_rows;
     return (size_t)(rows + sd_bn_finalize_scratch_rows(rows)) * 2 * d->Cin * sizeof(float);
 }
 
@@ -6193,13 +6245,13 @@ static int conv_dgrad_bn_reduce_any(const char* what, const float* dy, const flo
     SD_REQUIRE(aligned16(dy) && aligned16(w_t) && aligned16(dx) && aligned16(residual) && aligned16(bn_x) && aligned16(bn_y) && aligned16(mean) &&
                aligned16(invstd) && aligned16(gamma) && aligned16(beta) && aligned8(sums), SD_ERR_ALIGN, "%s: pointers must be 16-byte aligned", what);
     SD_REQUIRE(workspace_bytes >= sd_conv2d_dgrad_bn_reduce_workspace_bytes(d), SD_ERR_WORKSPACE, "%s: workspace too small", what);
-    ConvArgs a{};
-    fill_dgrad(a, d);
+    ConvArgs a = conv_args(d, 1, false);
     a.x = dy; a.w = w_t; a.y = dx; a.res = residual;
     a.bn_x = bn_x; a.bn_y = bn_y; a.bn_relu = relu; a.bn_mean = mean; a.bn_invstd = invstd; a.bn_gamma = gamma; a.bn_beta = beta;
     a.stat = (float*)workspace;
-    if (int e = launch_igemm(a, false, (hipStream_t)stream)) return e;
-    const int rows = dgrad_stat_rows(d);
+    const ConvPlan p = plan_conv(a, false);
+    if (int e = launch_plan(p, (hipStream_t)stream)) return e;
+    const int rows = p.stat_rows;
     if (sums) return sd_bn_bwd_sums((const float*)workspace, rows, (int64_t)a.M, d->Cin, dgamma, dbeta, accumulate, sums,
                                     (float*)workspace + (size_t)rows * 2 * d->Cin, stream);
     return sd_bn_bwd_finalize((const float*)workspace, rows, (int64_t)a.M, d->Cin, dgamma, dbeta, accumulate, means_out,
@@ -6259,37 +6311,15 @@ const char* sd_conv2d_kernel_name(const sd_conv_desc* d, int pass) {
     static thread_local char name[64];
     if (!d || d->Cin <= 0 || d->Cout <= 0) return "";
     if (pass == 2) {
-        if (wgrad_all_taps(d)) return d->Wo % 32 == 0 ? (g_wgrad_f32_ring >= 2 ? "k_wgrad3x3_ring2" : g_wgrad_f32_ring ? "k_wgrad3x3_ring" : "k_wgrad3x3<32>") : "k_wgrad3x3<16>";
-        snprintf(name, sizeof(name), "k_conv_wgrad<%d, %d>", d->Cout % 128 == 0 ? 128 : 64, d->Cin % 128 == 0 ? 128 : 64);
-        return name;
+        const WgradPlan p = plan_wgrad(d, false);
+        switch (p.family) {
+        case WGRAD_TAPS_RING2: return "k_wgrad3x3_ring2";
+        case WGRAD_TAPS_RING: return "k_wgrad3x3_ring";
+        case WGRAD_TAPS: return p.roww == 32 ? "k_wgrad3x3<32>" : "k_wgrad3x3<16>";
+        default: snprintf(name, sizeof(name), "k_conv_wgrad<%d, %d>", p.TN, p.TC); return name;
+        }
     }
-    ConvArgs a{};
-    const bool bf16 = (pass & 16) != 0;
-    pass &= 15;
-    if (pass == 0) fill_fwd(a, d); else fill_dgrad(a, d);
-    const int BN = (a.Nn % 128 == 0) ? 128 : 64;
-    const int mode = a.par ? 2 : (a.div > 1 ? 3 : 0);
-    ConvArgs t = a;
-    if (bf16) {          // the bf16 dispatch of launch_igemm (chunks of 64 channels; forward: split-K for small grids)
-        a.kchunks = a.Ck / 64; a.nk = a.R * a.S * a.kchunks;
-        a.splits = pass == 0 ? fwd_splits(d, 64) : 1;
-        t = a;
-        if (conv1x1_stream_geometry(a, mode)) return a.Ck == 64 ? "k_conv1x1_stream_bf16<64, 2>" : "k_conv1x1_stream_bf16<128, 1>";   // (launches with a scale or statistics: k_conv_igemm)
-        RowsArgs ra;
-        if (conv_rows64_geometry(a, mode, ra)) return conv_rows16_args(ra) ? "k_conv3x3_c64_rows16_bf16" : "k_conv3x3_c64_rows_bf16";
-        if (conv_pp_geometry(t, mode)) return "k_conv3x3_bf16_pp";
-        t = a;
-        if (const int PBN = patch_tile_bn(t, BN, mode, true)) snprintf(name, sizeof(name), "k_conv3x3_patch%s<%d, true>", t.pt_rolling ? "_roll" : "", PBN);
-        else if (g_igemm_big_bf16 && BN == 128 && igemm_big_tiles(a, BN, mode)) snprintf(name, sizeof(name), "k_conv_igemm_big<%d, %d, true>", BN, mode);
-        else snprintf(name, sizeof(name), "k_conv_igemm<%d, %d, true>", BN, mode);
-        return name;
-    }
-    RowsArgsF rf;
-    if (conv_rowsf32_geometry(a, mode, rf)) return "k_conv3x3_c64_rows_f32";
-    if (const int PBN = patch_tile_bn(t, BN, mode, false)) snprintf(name, sizeof(name), "k_conv3x3_patch%s<%d, false>", t.pt_rolling ? "_roll" : "", PBN);
-    else if (igemm_big_tiles(a, BN, mode)) snprintf(name, sizeof(name), "k_conv_igemm_big<%d, %d, false>", BN, mode);
-    else snprintf(name, sizeof(name), "k_conv_igemm<%d, %d, false>", BN, mode);
-    return name;
+    return conv_plan_name(plan_query(d, pass & 15, (pass & 16) != 0, false), name, sizeof(name));
 }
 
 }  // extern "C"

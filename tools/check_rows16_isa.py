@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Static check of the instantiations of k_conv3x3_c64_rows16_bf16 that launch_igemm dispatches (KIND 0 / 1, with and without a residual).
+"""Static check of the instantiations of k_conv3x3_c64_rows16_bf16 that plan_conv dispatches (KIND 0 / 1, with and without a residual).
 
 Its MFMAs are inline asm (the weight fragments are pinned to AGPRs / VGPRs by constraint), so hipcc's hazard recogniser does not see them.
 That is safe only while the register allocator keeps every weight fragment where it was pinned: a fragment it parks elsewhere is copied into
