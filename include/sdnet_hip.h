@@ -126,22 +126,39 @@ int sd_decode_fused(const float* anchor_hm, int64_t a_sb, int64_t a_sc,
                     const float* embeddings, int64_t e_sb, int64_t e_sc,
                     int B, int M, int N, int h, int w, int K, int P, float conf, float dist_px, int exact_topk,
                     void* packed, void* state, size_t state_bytes, void* workspace, size_t workspace_bytes, sd_stream_t stream);
-/* Tuning knob of sd_decode_fused (not a result-changing setting; THREAD-LOCAL: it applies to calls made by the host thread that set
- * it, every thread starts from the default, so two engines in two threads of one process cannot disturb each other):
- * "tall_tiles_from" = number of 64x16-pixel tile blocks of a launch (B x (M+N) x tiles) from which the NMS runs on 64x32 tiles instead
- * (default 2688: batches of 56 and more at 128x128 maps; 1 = always, 1 << 30 = never).  The sizes returned by sd_decode_state_bytes /
- * _workspace_bytes cover both.
- * Knobs of sd_decode (same rules): "map_parallel_from" = number of 64x16-pixel tile blocks of a call from which sd_decode takes its
- * map-parallel path -- tile pass without global atomics, one selector block per (image, map), one merge + association block per image;
- * bit-identical results -- instead of the launch pair with one selector block per image (default, value -1: by geometry and mode -- on maps up to 128
- * columns wide sd_decode always takes it, and the one-launch kernel is recommended below 960 tile blocks without the exact top-k only;
- * wider maps from 2560; always for images of 1024+ tile blocks such as
- * 1024x1024 inputs with 8 + 8 maps; sd_decode_fused_recommended follows the same rule; a value >= 0 holds for every geometry: 1 = always,
- * 1 << 30 = never); "map_tile_height" = 16 / 32 / 0 (by size) rows per NMS tile there;
- * "map_scalar_nms" = 1 keeps the per-pixel-sigmoid tile kernel where the logit-domain one (w % 4 == 0, aligned planes) applies;
- * "map_rows11" = bands of 128-row maps: 1 (default) 8-row bands with two bands per wave on launches of < 1024 maps, else 11-row bands; 0 = 16-row bands;
- * 8 / 11 = forced. */
+/* A/B and test switches of the two decoders (none changes a result; THREAD-LOCAL: a value applies to calls made by the host thread
+ * that set it, every thread starts from the defaults, so two engines in two threads of one process cannot disturb each other).
+ * Unknown names: SD_ERR_INVALID.  The keys, in the order of the table in csrc/sd_decode.hip (INTEGRATION.md has the same list):
+ *   "tall_tiles_from" (2688)   sd_decode_fused: number of 64x16-pixel tile blocks of a launch (B x (M+N) x tiles) from which the NMS runs
+ *                              on 64x32 tiles instead (batches of 56 and more at 128x128 maps; 1 = always, 1 << 30 = never).  The sizes
+ *                              returned by sd_decode_state_bytes / _workspace_bytes cover both.
+ *   "map_parallel_from" (-1)   sd_decode: number of 64x16-pixel tile blocks of a call from which it takes its map-parallel path -- tile
+ *                              pass without global atomics, one selector block per (image, map) or part of a map, one merge + association
+ *                              block per image; bit-identical results -- instead of the launch pair with one selector block per image.
+ *                              -1 = by geometry and mode: on maps up to 128 columns wide sd_decode always takes it, and the one-launch
+ *                              kernel is recommended below 960 tile blocks without the exact top-k only; wider maps from 2560; always for
+ *                              images of 1024+ tile blocks such as 1024x1024 inputs with 8 + 8 maps; sd_decode_fused_recommended follows
+ *                              the same rule.  A value >= 0 holds for every geometry and mode: 1 = always, 1 << 30 = never.
+ *   "map_rows11" (1)           bands of 128-row maps in k_map_stream_select: 1 = 8-row bands with two bands per wave on launches of
+ *                              fewer than 1024 maps, else 11-row bands; 0 = 16-row bands; 8 / 11 = forced.
+ *   "map_stream" (1)           0 = tile kernel + k_select_map instead of k_map_stream_select inside the map-parallel path.
+ *   "map_tile_height" (0)      rows per NMS tile of that tile kernel: 16 / 32 / 0 (by size).
+ *   "map_scalar_nms" (0)       1 = the per-pixel-sigmoid tile kernel also where the logit-domain one (w % 4 == 0, aligned planes) applies.
+ *   "map_split" (0)            blocks of k_map_stream_select per map: 0 = by size, 1 .. 4 = forced.
+ *   "map_half" (1)             0 = one band per wave also on maps up to 128 columns wide (1: two bands per wave there).
+ *   "map_waves3" (1)           parts of three wave-iterations of work on 192-thread blocks: 1 = from 1024 blocks per launch when a score
+ *                              threshold keeps the selections short, 0 = never, 2 = always.
+ *   "map_rank_group" (1)       ranks + gathers + association of an image: 1 = by size (k_rank_group_small, k_rank_group<256>, else
+ *                              k_rank_maps + k_group_wide), 0 = always the pair, 2 = the one-block kernel wherever its lists fit LDS. */
 int sd_decode_set_option(const char* name, int value);
+/* What a decode would launch, for the CALLING thread's options (host arithmetic only, no HIP call; profiling labels and dispatch tables:
+ * tools/decode_dispatch_table.py).  flags bit 0: the heat-map planes are vector-loadable (16-byte aligned base pointers, strides that are
+ * multiples of 4 floats); bit 1: describe sd_decode_fused (exact_topk with its override bit) instead of sd_decode (annotations-only is
+ * planned with a positive confidence threshold).  One line: each launch as "<kernel as rocprofv3 prints it, without sd::> grid=XxYxZ
+ * block=T lds=<dynamic LDS bytes>", launches in order, separated by "; "; the counter memset of the launch pair is listed as "memset";
+ * "refused: <message>" where sd_decode_fused would return an error; "" for a non-positive argument.  Thread-local storage, valid until
+ * the next call on the thread. */
+const char* sd_decode_kernel_names(int B, int M, int N, int h, int w, int K, int P, int exact_topk, int flags);
 
 /* Device self-check of the two properties the logit-domain NMS tile pass of sd_decode rests on, over ALL 2^32 fp32 bit patterns:
  * out3[0] = violations of "clamped sigmoid is monotone non-decreasing", out3[1] = violations of the near-tie margin table

@@ -7,6 +7,7 @@
 #pragma clang fp contract(off)
 #include "sd_common.h"
 #include <atomic>
+#include <cstdarg>
 #include <cstring>
 
 namespace sd {
@@ -2427,7 +2428,56 @@ int sd_decode_peaks(const float* logits, int64_t sb, int64_t sc, int B, int C, i
     return 0;
 }
 
-// ---- map-parallel path of sd_decode (k_nms_slots -> k_select_map -> k_rank_maps -> k_group_wide) ----
+}  // extern "C"
+
+namespace sd {
+
+// ---- decoder options ----------------------------------------------------------------------------------------------------------------
+// sd_decode_set_option(name, value): A/B and test switches, one instance per host thread (every thread starts from the defaults, like the
+// conv dispatch options).  DECODE_OPTION_KEYS is the one list of keys and defaults; include/sdnet_hip.h documents them in this order.
+struct DecodeOptionKey;
+struct DecodeOptions {
+    int tall_tiles_from = 0, map_parallel_from = 0, map_rows11 = 0, map_stream = 0, map_tile_height = 0, map_scalar_nms = 0, map_split = 0,
+        map_half = 0, map_waves3 = 0, map_rank_group = 0;       // (set from DECODE_OPTION_KEYS by the constructor)
+    int map_from_user = 0;      // 1: "map_parallel_from" was set by the caller and holds for every geometry and mode (tests, A/B)
+    constexpr DecodeOptions();
+};
+struct DecodeOptionKey { const char* name; int DecodeOptions::*member; int def; };
+constexpr DecodeOptionKey DECODE_OPTION_KEYS[] = {
+    {"tall_tiles_from", &DecodeOptions::tall_tiles_from, 2688},  // sd_decode_fused: 64x32 NMS tiles from this many 64x16 tile blocks per launch (fused_tile_height)
+    {"map_parallel_from", &DecodeOptions::map_parallel_from, 2560},  // tile blocks (at 64x16) from which sd_decode takes the map-parallel path; < 0: back to the built-in rule (map_path_from)
+    {"map_rows11", &DecodeOptions::map_rows11, 1},          // bands of maps with 9-16 units of 11 rows: 1 = 8 or 11 rows by size, 0 = 16 rows, 8 / 11 = forced (A/B, tests)
+    {"map_stream", &DecodeOptions::map_stream, 1},          // 0: tile kernel + k_select_map instead of k_map_stream_select (A/B, tests)
+    {"map_tile_height", &DecodeOptions::map_tile_height, 0},  // tile rows of that tile kernel: 16, 32, 0 = by size
+    {"map_scalar_nms", &DecodeOptions::map_scalar_nms, 0},  // 1: the per-pixel-sigmoid tile kernel also where the logit-domain one applies (A/B, tests)
+    {"map_split", &DecodeOptions::map_split, 0},            // parts per map in k_map_stream_select: 0 = by geometry, 1 .. MAP_SPLIT_MAX = forced (A/B, tests)
+    {"map_half", &DecodeOptions::map_half, 1},              // 0: one band per wave also on maps up to 128 columns wide (A/B, tests)
+    {"map_waves3", &DecodeOptions::map_waves3, 1},          // parts of three wave-iterations on 192-thread blocks: 1 = from 1024 blocks with a score threshold, 0 never, 2 always (A/B, tests)
+    {"map_rank_group", &DecodeOptions::map_rank_group, 1},  // 0: k_rank_maps + k_group_wide instead of the one-launch k_rank_group; 2: the generic one-block kernel wherever its lists fit LDS (A/B, tests)
+};
+constexpr DecodeOptions::DecodeOptions() {
+    for (const DecodeOptionKey& k : DECODE_OPTION_KEYS) this->*k.member = k.def;
+}
+static thread_local DecodeOptions g_decode_options;
+
+static int set_decode_option(const char* name, int value) {
+    for (const DecodeOptionKey& k : DECODE_OPTION_KEYS) {
+        if (!name || strcmp(name, k.name)) continue;
+        if (k.member == &DecodeOptions::map_parallel_from) {         // a value >= 0 holds for every geometry, a negative one returns to the built-in rule
+            g_decode_options.map_from_user = value >= 0;
+            if (value < 0) value = k.def;
+        }
+        g_decode_options.*k.member = value;
+        return 0;
+    }
+    set_error("sd_decode_set_option: unknown option '%s'", name ? name : "(null)");
+    return SD_ERR_INVALID;
+}
+
+// ---- how a decode is dispatched -----------------------------------------------------------------------------------------------------
+// plan_decode() and plan_decode_fused() are the ONE place that decides what sd_decode / sd_decode_fused launch: path, kernels, template
+// arguments, grids, blocks, dynamic LDS and workspace.  The launchers, sd_decode_fused_supported / _recommended and sd_decode_kernel_names
+// read a plan; the predicates below are called from the plan functions only (map_path_possible also sizes the workspace).  No HIP call.
 struct MapWs {
     uint64_t* cand;       // B * C * tiles * (TW * th) keys
     int* tile_cnt;        // B * C * tiles
@@ -2452,48 +2502,314 @@ static MapWs carve_map(void* ws, int B, int C, int h, int w, int th, int K, int 
     r.bytes = off;
     return r;
 }
-// Tile blocks (at 64x16) from which sd_decode takes the map-parallel path, and its tile height (0 = by size); per host thread.
-// sd_decode_set_option("map_parallel_from" / "map_tile_height", n).
-static thread_local int g_map_parallel_from = 2560;
-static thread_local int g_map_from_user = 0;        // 1: "map_parallel_from" was set by the caller and holds for every geometry and mode (tests, A/B)
-static thread_local int g_map_tile_height = 0;
-static thread_local int g_map_stream = 1;           // 0: tile kernel + k_select_map instead of k_map_stream_select (A/B, tests)
-static thread_local int g_map_rows11 = 1;           // bands of maps with 9-16 units of 11 rows: 1 = 8 or 11 rows by size, 0 = 16 rows, 8 / 11 = forced (A/B, tests)
-static thread_local int g_map_scalar_nms = 0;       // 1: the per-pixel-sigmoid tile kernel also where the logit-domain one applies (A/B, tests)
-static thread_local int g_map_waves3 = 1;           // parts of three wave-iterations on 192-thread blocks: 1 = from 1024 blocks with a score threshold, 0 never, 2 always (A/B, tests)
-static thread_local int g_map_half = 1;             // 0: one band per wave also on maps up to 128 columns wide (A/B, tests)
-// 64 x 16 tile blocks per call from which sd_decode takes the map-parallel path (and the one-launch kernel is no longer recommended).  On maps
-// up to 128 columns wide -- two bands per wave, two parts per map, one rank + association launch -- measured at the cfg shape after the early
-// score cut (`profiles/r05_decode_small_batches.txt`): annotations-only 16.7 us at bs = 16 .. 20 against 16.6 .. 17.7 for k_decode_fused and
-// 19.8 for the launch pair (bs = 32: 15.7 / 19.2; bs = 8: 16.3 / 15.9 / 20.3): from 960 tile blocks (bs = 20); with the exact top-k 19.7 us
-// at bs = 1 against 26.5 for k_decode_fused: always.  Wider maps keep the round-4 threshold.
-static int64_t map_from(int w, bool exact) {
-    if (g_map_from_user) return g_map_parallel_from;
-    const bool fast = g_map_half && g_map_stream && w <= 128 && w % 4 == 0;
-    return fast ? (exact ? 1 : 960) : g_map_parallel_from;
-}
-// ... and inside sd_decode, where the alternative is the launch pair (19.8-21.6 us at bs = 1 .. 16 against 14.8-16.8): always on those maps
-static int64_t map_from_pair(int w) {
-    if (g_map_from_user) return g_map_parallel_from;
-    return (g_map_half && g_map_stream && w <= 128 && w % 4 == 0) ? 1 : g_map_parallel_from;
-}
-static thread_local int g_map_split = 0;            // parts per map in k_map_stream_select: 0 = by geometry, 1 .. MAP_SPLIT_MAX = forced (A/B, tests)
-static thread_local int g_map_rank_group = 1;       // 0: k_rank_maps + k_group_wide instead of the one-launch k_rank_group (A/B, tests)
 constexpr size_t RANK_GROUP_LDS_MAX = 96 * 1024;    // dynamic LDS of k_rank_group (beside its 37 KB of static arrays)
-static int map_tile_height(int64_t blocks16) {
-    if (g_map_tile_height == 16 || g_map_tile_height == 32) return g_map_tile_height;
-    return blocks16 >= 8192 ? 32 : 16;
-}
+constexpr int FUSED_LDS_LIMIT = 96 * 1024;          // dynamic LDS sd_decode_fused asks for at most (gfx950: 160 KB per CU)
+
+// 64 x 16 tile blocks of one image's C maps (the unit of every dispatch threshold; a call has B times as many)
+static int64_t image_tiles16(int C, int h, int w) { return (int64_t)C * cdiv(w, TW) * cdiv(h, 16); }
+static int64_t fused_tiles(int h, int w, int th) { return (int64_t)cdiv(w, TW) * cdiv(h, th); }
 static bool map_path_possible(int M, int N, int h, int w, int K, int P) {
-    return M <= 64 && N <= 64 && (int64_t)cdiv(w, TW) * cdiv(h, 16) <= MAP_TILES_MAX && K <= SD_MAX_TOPK && P <= SD_MAX_TOPK &&
+    return M <= 64 && N <= 64 && image_tiles16(1, h, w) <= MAP_TILES_MAX && K <= SD_MAX_TOPK && P <= SD_MAX_TOPK &&
            (int64_t)M * K <= RANK_KEYS_MAX && (int64_t)N * P <= RANK_KEYS_MAX;
 }
+// a map the fast streaming form serves: two bands per wave, two parts per map, one rank + association launch
+static bool fast_map(const DecodeOptions& o, int w) { return o.map_half && o.map_stream && w <= 128 && w % 4 == 0; }
+// Tile blocks per call from which the map-parallel path is the one to take: `fast_from` on the maps fast_map() serves, else the round-4
+// threshold; "map_parallel_from" set by the caller holds for every geometry and mode.
+static int64_t map_path_from(const DecodeOptions& o, int w, int64_t fast_from) {
+    if (o.map_from_user) return o.map_parallel_from;
+    return fast_map(o, w) ? fast_from : o.map_parallel_from;
+}
+static int map_tile_height(const DecodeOptions& o, int64_t blocks16) {
+    if (o.map_tile_height == 16 || o.map_tile_height == 32) return o.map_tile_height;
+    return blocks16 >= 8192 ? 32 : 16;
+}
+// Tile height of one fused launch.  64x16 tiles give a small batch the most workgroups (bs=1: 32 + 1); once the launch holds more
+// tile blocks than the chip keeps resident at once (about 1200 with the selector's LDS block), they run in rounds and 64x32 tiles --
+// half the blocks, half the records the selectors wait for, 36 halo rows per 32 instead of 20 per 16 -- finish sooner.  Measured
+// (tools/decode_tile_sweep.py, 3 maps of 128x128, us per launch 64x16 / 64x32): bs=1 12.8 / 14.0, bs=16 14.6 / 15.2, bs=32 16.6 / 16.7,
+// bs=48 18.7 / 18.9, bs=64 21.1 / 20.1, bs=96 25.3 / 23.6, bs=128 29.6 / 27.1: the switch sits at 2688 blocks (bs=56).  sd_decode_set_option("tall_tiles_from", n) moves the switch.
+static int fused_tile_height(const DecodeOptions& o, int64_t blocks16) { return blocks16 >= o.tall_tiles_from ? 32 : 16; }
 
+struct LaunchDims { dim3 grid; unsigned block; size_t lds; };      // lds: DYNAMIC bytes (a kernel's static arrays come on top)
+enum DecodePath { DECODE_MAP, DECODE_PAIR };
+enum Stage1Form { STAGE1_STREAM, STAGE1_SLOTS_V, STAGE1_SLOTS };
+enum RankForm { RANK_GROUP_SMALL, RANK_GROUP_256, RANK_GROUP_1024, RANK_MAPS_GROUP_WIDE };
+struct DecodePlan {
+    DecodePath path;
+    size_t ws_bytes;             // workspace this plan needs
+    // DECODE_PAIR: memset, k_nms_tile<1> (stage1_l), k_select_group (rank_l)
+    // DECODE_MAP, stage 1: k_map_stream_select<threads, rows, half> (stage1_l), or k_nms_slots_v<th> / k_nms_slots<th> (stage1_l) + k_select_map (select_l)
+    Stage1Form stage1;
+    int th, tiles_x, tiles;      // tile height of the tile kernels and of the workspace layout; tiles per map
+    int rows, splits, threads;   // k_map_stream_select: band rows (8 / 11 / 16), parts per map (= stage-1 lists per map), block threads
+    bool half;                   //                      two bands per wave
+    LaunchDims stage1_l, select_l;
+    // DECODE_MAP, ranks + association: one of the one-block kernels (rank_l), or k_rank_maps (rank_l) + k_group_wide (group_l)
+    RankForm rank;
+    int LM, LN;                  // lists per group (a part of a split map is one more sorted list of its group)
+    LaunchDims rank_l, group_l;
+};
+
+// score_cut: stage 1 drops peaks below a positive score (annotations-only with conf > 0; the exact top-k keeps every peak).
+// vec_ok: the heat-map planes allow 16-byte loads (base pointers and strides; the width is asked here).
+static DecodePlan plan_decode(int B, int M, int N, int h, int w, int K, int P, bool score_cut, bool vec_ok, const DecodeOptions& o) {
+    DecodePlan p{};
+    const int C = M + N;
+    const int64_t tiles_img16 = image_tiles16(C, h, w), blocks16 = B * tiles_img16;
+    // measured (tools/decode_path_sweep.py): the launch pair costs ~20 us + what ONE block per image needs for its lists (1024x1024, 8 + 8
+    // maps: 64 us at bs = 1), the map-parallel chain 25-35 us + the tile pass; they cross at ~2500 tile blocks, and images of 1024 and
+    // more tile blocks are better off on the map-parallel path at any batch size.  On the maps fast_map() serves, where the alternative
+    // is the launch pair (19.8-21.6 us at bs = 1 .. 16 against 14.8-16.8): always
+    const bool want_map = blocks16 >= map_path_from(o, w, 1) || (o.map_parallel_from < (1 << 30) && tiles_img16 >= 1024);
+    if (!(map_path_possible(M, N, h, w, K, P) && want_map && blocks16 < (1ll << 30))) {
+        p.path = DECODE_PAIR;
+        p.ws_bytes = carve(nullptr, B, M, N, h, w).bytes;
+        p.stage1_l = {dim3(cdiv(w, TW) * cdiv(h, TH), C, B), 256, 0};
+        p.rank_l = {dim3(B), 2 * SEL_THREADS, 0};
+        return p;
+    }
+    p.path = DECODE_MAP;
+    p.th = map_tile_height(o, blocks16);
+    p.tiles_x = cdiv(w, TW); p.tiles = p.tiles_x * cdiv(h, p.th);
+    p.ws_bytes = carve_map(nullptr, B, C, h, w, p.th, K, P).bytes;
+    const bool vec = o.map_scalar_nms == 0 && w % 4 == 0 && vec_ok;
+    p.splits = 1;
+    if (vec && o.map_stream) {
+        // tile pass + per-map selection in one kernel (candidate list `cand`: h * w slots per map, only touched by overflowing maps)
+        p.stage1 = STAGE1_STREAM;
+        const int strips = cdiv(w, 256);
+        // 16 waves per map where 16-row bands give 16+ units of work (strip x band; 256 x 256 maps: 40.9 -> 36.5 us per batch of 16 x 16
+        // maps; 128 x 128 maps, 8 units, stay at 8 waves: 14.4 us, 14.9 with 16); maps of 9 .. 15 such units (128 x 128: 8) take 11-row
+        // bands: every wave walks 15 rows instead of 20 -- and, round 5, such a map is SPLIT over ceil(bands / 4) blocks of four waves, one
+        // band per wave (bs = 64, 3 maps of 128 x 128: 576 blocks of 4 waves on every CU of the chip instead of 192 blocks with 12 busy
+        // waves of 16)
+        const int units16 = strips * cdiv(h, 16), units11 = strips * cdiv(h, 11);
+        // maps up to 128 columns wide: two bands per wave (lanes 0-31 / 32-63), half the waves (sd_decode_set_option("map_half", 0): off)
+        p.half = o.map_half && strips == 1 && w <= 128;
+        // ... and 8-row bands (12 rows per wave, all requested at once) with two bands per wave while the launch is small enough for its
+        // latency to matter more than the halo rows it re-reads (measured at 128 x 128 maps, two parts per map: bs = 64 17.3 -> 16.6 us,
+        // bs = 128 19.2 -> 18.2, exact top-k 24.6 -> 23.3; bs = 512 36.5 -> 38.1: from 1024 maps the 11-row bands stay)
+        const bool short_ok = units11 > 8 && units11 <= 16;
+        p.rows = units16 >= 16 ? 16 : (!short_ok || o.map_rows11 == 0) ? 16
+               : (o.map_rows11 == 8 || (o.map_rows11 == 1 && p.half && (int64_t)B * C < 1024)) ? (p.half ? 8 : 11) : 11;
+        const int bands = cdiv(h, p.rows);
+        // (measured, `profiles/r05_decode_split_sweep.txt`: at bs = 64 -- 192 maps -- one block per map and three parts per map stream in the
+        // same 14 us, the kernel is bound by the start-up spread of its ~2500 waves and their first round trips, and the rank kernel pays for
+        // three times the lists; at bs = 512 the parts stream in 53 instead of 74 us: five 27 KB blocks per CU instead of one of 86 KB)
+        //  With two bands per wave (maps up to 128 columns) two parts per map pay from ~100 maps: bs = 64 21.4 -> 20.5 us, bs = 512 72.8 -> 53.6.)
+        int want = o.map_split;
+        if (want <= 0) want = ((p.rows == 11 || p.rows == 8) && strips == 1) ? (p.half ? ((int64_t)B * C >= 96 ? 2 : 1) : ((int64_t)B * C >= 384 ? cdiv(bands, 4) : 1)) : 1;
+        p.splits = std::max(1, std::min({want, MAP_SPLIT_MAX, bands}));
+        if ((int64_t)M * p.splits * K > RANK_KEYS_MAX || (int64_t)N * p.splits * P > RANK_KEYS_MAX) p.splits = 1;
+        const int per_block = strips * cdiv(bands, p.splits);            // units of work of the largest part
+        const int per_wave = p.half ? cdiv(per_block, 2) : per_block;    // wave-iterations of work of the largest part
+        const unsigned grid = (unsigned)(B * C * p.splits);
+        // (three band pairs per part -- the cfg shape in two parts -- on three waves where several blocks share a CU and a score
+        //  threshold keeps the selections short: bs = 512 32.1 -> 28.7 us; at bs = 64, 384 blocks, the idle fourth wave costs nothing
+        //  -- 9.6 vs 10.1 us: the start-up spread of a launch goes by its blocks, not its waves -- and the exact top-k's radix select over
+        //  ~1000 keys wants the fourth wave: 16.3 vs 21.0 us)
+        const bool waves3 = o.map_waves3 == 2 || (o.map_waves3 == 1 && grid >= 1024u && score_cut);
+        if (p.half)            p.threads = per_wave > 8 ? 1024 : per_wave > 4 ? 512 : (p.rows == 11 && per_wave == 3 && waves3) ? 192 : 256;
+        else if (p.rows == 16) p.threads = (p.splits == 1 && units16 >= 16) ? 1024 : (per_block > 4 || p.splits == 1) ? 512 : 256;
+        else                   p.threads = (per_block > 8 || p.splits == 1) ? 1024 : per_block > 4 ? 512 : (per_block == 3 && waves3) ? 192 : 256;
+        p.stage1_l = {dim3(grid), (unsigned)p.threads, 0};
+    } else {
+        p.stage1 = vec ? STAGE1_SLOTS_V : STAGE1_SLOTS;
+        p.stage1_l = {dim3((unsigned)((int64_t)B * C * p.tiles)), 256, 0};
+        p.select_l = {dim3(B * C), SEL_THREADS, 0};
+    }
+    p.LM = M * p.splits; p.LN = N * p.splits;
+    // ranks + gathers + association of an image in ONE block (two dependent launches less) where an image's lists are short: the
+    // ranking is serial per image there (stress, 16 lists of 128 / 512 keys in one 1024-thread block: 75 us against 8.6 + 7.4 for
+    // k_rank_maps + k_group_wide -- `profiles/r05_decode_split_sweep.txt`), so large selections keep the map-parallel pair.
+    // map_rank_group: 0 never, 1 by size (default), 2 the generic one-block kernel wherever its lists fit LDS (tests)
+    const int64_t n_keys = (int64_t)p.LM * K + (int64_t)p.LN * P;
+    const size_t rg_lds = ((size_t)n_keys + K + P) * 8;
+    const bool small = K <= RGS_K && P <= RGS_K && p.LM * K <= RGS_KEYS && p.LN * P <= RGS_KEYS && n_keys <= RGS_THREADS * RGS_KPT && h * w >= RGS_K;
+    const bool fits256 = n_keys <= 1024 && K <= 256 && P <= 256;
+    if (o.map_rank_group == 1 && small) {
+        p.rank = RANK_GROUP_SMALL;
+        p.rank_l = {dim3(B), RGS_THREADS, 0};
+    } else if (rg_lds <= RANK_GROUP_LDS_MAX && (o.map_rank_group == 2 || (o.map_rank_group == 1 && fits256))) {
+        p.rank = fits256 ? RANK_GROUP_256 : RANK_GROUP_1024;
+        p.rank_l = {dim3(B), fits256 ? 256u : 1024u, rg_lds};
+    } else {
+        p.rank = RANK_MAPS_GROUP_WIDE;
+        p.rank_l = {dim3(B * C * p.splits), SEL_THREADS, (size_t)std::max((int64_t)p.LM * K, (int64_t)p.LN * P) * 8};
+        p.group_l = {dim3(B, cdiv(P, GROUP_PARTS)), GROUP_THREADS, (size_t)K * 8 + (size_t)P * 8 + (size_t)((K + 3) & ~3) * 8 + (size_t)(K + P) * 4};
+    }
+    return p;
+}
+
+// the 17 instantiations of k_map_stream_select, by (block threads, band rows, two bands per wave)
+using StreamKernel = void (*)(Group, Group, int, int, float, float, int, int, uint64_t*, uint64_t*, int);
+struct StreamInst { int threads, rows; bool half; StreamKernel kernel; };
+static const StreamInst STREAM_KERNELS[] = {
+    {1024, 8, true, k_map_stream_select<1024, 8, true>},    {512, 8, true, k_map_stream_select<512, 8, true>},
+    {256, 8, true, k_map_stream_select<256, 8, true>},
+    {1024, 16, true, k_map_stream_select<1024, 16, true>},  {512, 16, true, k_map_stream_select<512, 16, true>},
+    {256, 16, true, k_map_stream_select<256, 16, true>},
+    {1024, 11, true, k_map_stream_select<1024, 11, true>},  {512, 11, true, k_map_stream_select<512, 11, true>},
+    {192, 11, true, k_map_stream_select<192, 11, true>},    {256, 11, true, k_map_stream_select<256, 11, true>},
+    {1024, 16, false, k_map_stream_select<1024, 16, false>}, {512, 16, false, k_map_stream_select<512, 16, false>},
+    {256, 16, false, k_map_stream_select<256, 16, false>},
+    {1024, 11, false, k_map_stream_select<1024, 11, false>}, {512, 11, false, k_map_stream_select<512, 11, false>},
+    {192, 11, false, k_map_stream_select<192, 11, false>},  {256, 11, false, k_map_stream_select<256, 11, false>},
+};
+static StreamKernel stream_kernel(const DecodePlan& p) {
+    for (const StreamInst& s : STREAM_KERNELS)
+        if (s.threads == p.threads && s.rows == p.rows && s.half == p.half) return s.kernel;
+    return nullptr;
+}
+
+struct FusedPlan {
+    bool supported;              // sd_decode_fused can compute this geometry in either mode and with either tile height
+    bool recommended;            // ... and is the faster decoder for it
+    int err;                     // 0: THIS launch (mode, tile height by the options) can run; else the code sd_decode_fused returns ...
+    char reason[320];            // ... and its message
+    int th, tiles_x, tiles, sort_cap;
+    FusedLds lds;
+    unsigned grid;
+};
+static const char* const FUSED_RANGE_MSG = "sd_decode_fused: %s=%d out of range (1..%d; use sd_decode beyond)";
+
+__attribute__((format(printf, 3, 4))) static bool refuse(char* why, size_t n, const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(why, n, fmt, ap);
+    va_end(ap);
+    return false;
+}
+// What a launch of k_decode_fused needs -- `tiles` tiles per map, a tile pass of th-row tiles, a sort buffer of at least `cap_floor` keys
+// per team -- in the order sd_decode_fused reports it; `why` gets the message of the first requirement that fails.  gate_tiles16: the
+// 64x16 tile blocks of an image where geometries beyond 256 of them are to be refused (sd_decode is the faster decoder there), else 0.
+static bool fused_fits(int B, int C, int K, int P, int64_t tiles, int th, int cap_floor, int64_t gate_tiles16, int& sort_cap, FusedLds& lds,
+                       char* why, size_t n) {
+    const int64_t nti = C * tiles;
+    if (K > FUSED_MAX_TOPK) return refuse(why, n, FUSED_RANGE_MSG, "max_objects", K, FUSED_MAX_TOPK);
+    if (P > FUSED_MAX_TOPK) return refuse(why, n, FUSED_RANGE_MSG, "max_parts", P, FUSED_MAX_TOPK);
+    // at most B selector blocks wait inside the grid: keep them far below the resident block slots of the chip (256 CUs x >= 2)
+    if (B > 256) return refuse(why, n, "sd_decode_fused: batch %d > 256 (selector blocks must stay resident); use sd_decode", B);
+    if (gate_tiles16 > 256)
+        return refuse(why, n, "sd_decode_fused: %lld tile blocks per image (> 256): sd_decode is several times faster for this geometry "
+                  "(sd_decode_fused_recommended() == 0); pass exact_topk | 2 to run it here anyway", (long long)gate_tiles16);
+    if (nti > 32 * FUSED_THREADS) return refuse(why, n, "sd_decode_fused: %lld tiles per image > %d; use sd_decode", (long long)nti, 32 * FUSED_THREADS);
+    if ((int64_t)B * nti + B >= (1ll << 31)) return refuse(why, n, "sd_decode_fused: grid too large");
+    // rank sort needs 2 * np2 <= cap with np2 >= max(K, P): never below 2 * next_pow2(max(K, P))
+    sort_cap = cap_floor;
+    while (sort_cap < 2 * std::max(K, P)) sort_cap *= 2;
+    lds = fused_lds(K, P, (int)nti, sort_cap, th);
+    if (lds.total > FUSED_LDS_LIMIT)
+        return refuse(why, n, "sd_decode_fused: %d maps x %d tiles need %d bytes of LDS (> %d); use sd_decode", C, (int)tiles, lds.total, FUSED_LDS_LIMIT);
+    return true;
+}
+
+// exact_topk: bit 0 = exact top-k, bit 1 (value 2) = accept geometries where sd_decode is the faster decoder (tests of this kernel)
+static FusedPlan plan_decode_fused(int B, int M, int N, int h, int w, int K, int P, int exact_topk, const DecodeOptions& o) {
+    FusedPlan p{};
+    p.err = SD_ERR_INVALID;
+    if (B <= 0 || M <= 0 || N <= 0 || h <= 0 || w <= 0 || K <= 0 || P <= 0) {
+        snprintf(p.reason, sizeof(p.reason), "sd_decode_fused: bad shape");
+        return p;
+    }
+    const bool exact = (exact_topk & 1) != 0, force = (exact_topk & 2) != 0;
+    const int C = M + N;
+    const int64_t tiles_img16 = image_tiles16(C, h, w), blocks16 = B * tiles_img16;
+    // supported: judged on the 64x16 tiling (more tiles, more LDS for their counts), the tile pass of 64x32 tiles and the exact top-k's
+    // sort buffer: what fits there fits in either mode and with either tile height, whatever "tall_tiles_from" says at launch
+    p.supported = fused_fits(B, C, K, P, fused_tiles(h, w, 16), 32, FUSED_CAP_EXACT, 0, p.sort_cap, p.lds, p.reason, sizeof(p.reason));
+    // Where ONE launch is the faster decoder (measured: profiles/r02_decode_variants.txt): image geometries of at most 256 tile blocks
+    // (512x512 with 2 + 1 maps = 48; the selector's LDS is paid by every tile block of the grid, and with ~1000 tiles per image -- 1024x1024,
+    // 8 + 8 maps -- it halves the occupancy of the 16 k tile blocks: 451 us vs 116 us for sd_decode at K = 128, P = 512), and for the exact
+    // top-k only small batches (bs = 64: 39.0 vs 31.3 us, its two 2048-key sort buffers cost the tile blocks occupancy).
+    p.recommended = p.supported && tiles_img16 <= 256 && (!exact || B <= 8);
+    // ... and not from the batch where sd_decode's map-parallel path on the maps fast_map() serves is faster.  Measured at the cfg shape
+    // after the early score cut (`profiles/r05_decode_small_batches.txt`): annotations-only 16.7 us at bs = 16 .. 20 against 16.6 .. 17.7 for
+    // k_decode_fused and 19.8 for the launch pair (bs = 32: 15.7 / 19.2; bs = 8: 16.3 / 15.9 / 20.3): from 960 tile blocks (bs = 20); with
+    // the exact top-k 19.7 us at bs = 1 against 26.5 for k_decode_fused: always; bs = 64: 20.5 us against 23.5
+    // (`profiles/r05_decode_split_sweep.txt`).  Wider maps keep the round-4 threshold.
+    if (blocks16 >= map_path_from(o, w, exact ? 1 : 960) && fast_map(o, w) && map_path_possible(M, N, h, w, K, P)) p.recommended = false;
+    p.th = fused_tile_height(o, blocks16);
+    const int64_t tiles = fused_tiles(h, w, p.th);
+    if (!fused_fits(B, C, K, P, tiles, p.th, exact ? FUSED_CAP_EXACT : FUSED_CAP_FAST, force ? 0 : tiles_img16, p.sort_cap, p.lds, p.reason, sizeof(p.reason)))
+        return p;
+    p.err = 0; p.reason[0] = 0;
+    p.tiles_x = cdiv(w, TW); p.tiles = (int)tiles;
+    p.grid = (unsigned)(B * C * tiles + B);
+    return p;
+}
+
+// "<kernel as rocprofv3 prints it, without sd::> grid=XxYxZ block=T lds=<dynamic bytes>", launches separated by "; "
+static int append_launch(char* buf, size_t n, int at, const char* name, const LaunchDims* l) {
+    if (at < 0 || (size_t)at >= n) return at;
+    const char* sep = at ? "; " : "";
+    if (!l) return at + snprintf(buf + at, n - at, "%s%s", sep, name);
+    return at + snprintf(buf + at, n - at, "%s%s grid=%ux%ux%u block=%u lds=%zu", sep, name, l->grid.x, l->grid.y, l->grid.z, l->block, l->lds);
+}
+static void decode_plan_names(const DecodePlan& p, char* buf, size_t n) {
+    char name[64];
+    int at = 0;
+    if (p.path == DECODE_PAIR) {
+        at = append_launch(buf, n, at, "memset", nullptr);
+        at = append_launch(buf, n, at, "k_nms_tile<1>", &p.stage1_l);
+        append_launch(buf, n, at, "k_select_group", &p.rank_l);
+        return;
+    }
+    switch (p.stage1) {
+    case STAGE1_STREAM: snprintf(name, sizeof(name), "k_map_stream_select<%d, %d, %s>", p.threads, p.rows, p.half ? "true" : "false"); break;
+    case STAGE1_SLOTS_V: snprintf(name, sizeof(name), "k_nms_slots_v<%d>", p.th); break;
+    case STAGE1_SLOTS: snprintf(name, sizeof(name), "k_nms_slots<%d>", p.th); break;
+    }
+    at = append_launch(buf, n, at, name, &p.stage1_l);
+    if (p.stage1 != STAGE1_STREAM) at = append_launch(buf, n, at, "k_select_map", &p.select_l);
+    switch (p.rank) {
+    case RANK_GROUP_SMALL: append_launch(buf, n, at, "k_rank_group_small", &p.rank_l); break;
+    case RANK_GROUP_256: append_launch(buf, n, at, "k_rank_group<256>", &p.rank_l); break;
+    case RANK_GROUP_1024: append_launch(buf, n, at, "k_rank_group<1024>", &p.rank_l); break;
+    case RANK_MAPS_GROUP_WIDE:
+        at = append_launch(buf, n, at, "k_rank_maps", &p.rank_l);
+        append_launch(buf, n, at, "k_group_wide", &p.group_l);
+        break;
+    }
+}
+
+// kernels that ask for more dynamic LDS than the default limit: raise the kernel's limit once per host thread (cheap, idempotent)
+template <auto KERNEL>
+static int raise_dynamic_lds(int bytes) {
+    static thread_local bool raised = false;
+    if (!raised) {
+        SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+        raised = true;
+    }
+    return 0;
+}
+
+}  // namespace sd
+
+extern "C" {
+
+// ---- sd_decode: the launch pair (k_nms_tile -> k_select_group) or the map-parallel path (k_map_stream_select, or k_nms_slots ->
+// k_select_map; then k_rank_group, or k_rank_maps -> k_group_wide), as plan_decode says ----
+int sd_decode_set_option(const char* name, int value) { return set_decode_option(name, value); }
+
+// The size queries of both decoders cover EITHER tile height (an option may change between sizing and launch) and, for sd_decode,
+// either path; a launch checks its buffers against what its own plan needs, which is never more.
 size_t sd_decode_workspace_bytes(int B, int M, int N, int h, int w, int K, int P) {
     size_t need = carve(nullptr, B, M, N, h, w).bytes;
-    if (map_path_possible(M, N, h, w, K, P))           // either tile height (the option may change between sizing and launch)
+    if (map_path_possible(M, N, h, w, K, P))
         need = std::max({need, carve_map(nullptr, B, M + N, h, w, 16, K, P).bytes, carve_map(nullptr, B, M + N, h, w, 32, K, P).bytes});
     return need;
+}
+
+size_t sd_decode_state_bytes(int B, int M, int N, int h, int w) {
+    return align_up((size_t)std::max(B, 1) * (M + N) * fused_tiles(h, w, 16) * REC_WORDS * sizeof(unsigned), 256);
+}
+
+size_t sd_decode_fused_workspace_bytes(int B, int M, int N, int h, int w, int K, int P) {
+    (void)K; (void)P;
+    const size_t t = std::max(fused_tiles(h, w, 16) * TW * 16, fused_tiles(h, w, 32) * TW * 32);
+    return align_up((size_t)B * (M + N) * t * 8, 256);
 }
 
 size_t sd_decode_packed_words(int B, int K, int P) { return (size_t)B * (6 * (size_t)K + 11 * (size_t)P + 1); }
@@ -2509,186 +2825,74 @@ int sd_decode(const float* anchor_hm, int64_t a_sb, int64_t a_sc, const float* p
     SD_REQUIRE(K > 0 && K <= SD_MAX_TOPK && (int64_t)K <= (int64_t)M * h * w, SD_ERR_INVALID, "sd_decode: max_objects=%d out of range", K);
     SD_REQUIRE(P > 0 && P <= SD_MAX_TOPK && (int64_t)P <= (int64_t)N * h * w, SD_ERR_INVALID, "sd_decode: max_parts=%d out of range", P);
     SD_REQUIRE(packed && workspace, SD_ERR_INVALID, "sd_decode: null pointer");
+    const float min_score = exact_topk ? 0.f : conf;
+    const bool vec_ok = aligned16(anchor_hm) && aligned16(part_hm) && a_sb % 4 == 0 && a_sc % 4 == 0 && p_sb % 4 == 0 && p_sc % 4 == 0;
+    const DecodePlan p = plan_decode(B, M, N, h, w, K, P, min_score > 0.f, vec_ok, g_decode_options);
+    SD_REQUIRE(workspace_bytes >= p.ws_bytes, SD_ERR_WORKSPACE, "sd_decode: workspace %zu < %zu", workspace_bytes, p.ws_bytes);
     hipStream_t st = (hipStream_t)stream;
     Group g0{anchor_hm, a_sb, a_sc, M}, g1{part_hm, p_sb, p_sc, N};
-    const int64_t blocks16 = (int64_t)B * (M + N) * cdiv(w, TW) * cdiv(h, 16);
-    // measured (tools/decode_path_sweep.py): the launch pair costs ~20 us + what ONE block per image needs for its lists (1024x1024, 8 + 8
-    // maps: 64 us at bs = 1), the map-parallel chain 25-35 us + the tile pass; they cross at ~2500 tile blocks, and images of 1024 and
-    // more tile blocks are better off on the map-parallel path at any batch size
-    const int64_t tiles_img16 = (int64_t)(M + N) * cdiv(w, TW) * cdiv(h, 16);
-    const bool want_map = blocks16 >= map_from_pair(w) || (g_map_parallel_from < (1 << 30) && tiles_img16 >= 1024);
-    if (map_path_possible(M, N, h, w, K, P) && want_map && blocks16 < (1ll << 30)) {
-        const int th = map_tile_height(blocks16);
-        const MapWs mw = carve_map(workspace, B, M + N, h, w, th, K, P);
-        SD_REQUIRE(workspace_bytes >= mw.bytes, SD_ERR_WORKSPACE, "sd_decode: workspace %zu < %zu", workspace_bytes, mw.bytes);
-        const int tiles_x = cdiv(w, TW), tiles = tiles_x * cdiv(h, th), C = M + N;
-        const float min_score = exact_topk ? 0.f : conf;
-        const bool vec = g_map_scalar_nms == 0 && w % 4 == 0 && aligned16(anchor_hm) && aligned16(part_hm) && a_sb % 4 == 0 && a_sc % 4 == 0 &&
-                         p_sb % 4 == 0 && p_sc % 4 == 0;
-        int splits = 1;                                              // stage-1 lists per map (parts of a split map)
-        if (vec && g_map_scalar_nms == 0 && g_map_stream) {
-            // tile pass + per-map selection in one kernel (candidate list `cand`: h * w slots per map, only touched by overflowing maps)
-            // 16 waves per map where a map has 16+ units of work (strip x 16-row band): 256 x 256 maps 40.9 -> 36.4 us per batch of 16 x 16 maps;
-            // 128 x 128 maps (8 units) stay at 8 waves (14.4 us; 14.9 with 16)
-            const int strips = cdiv(w, 256);
-            // 16 waves per map where 16-row bands give 16+ units of work (256 x 256 maps: 40.9 -> 36.5 us per batch of 16 x 16 maps); maps of
-            // 9 .. 15 such units (128 x 128: 8) take 11-row bands: every wave walks 15 rows instead of 20 -- and, round 5, such a map is SPLIT
-            // over ceil(bands / 4) blocks of four waves, one band per wave (bs = 64, 3 maps of 128 x 128: 576 blocks of 4 waves on every CU of
-            // the chip instead of 192 blocks with 12 busy waves of 16)
-            const int units16 = strips * cdiv(h, 16), units11 = strips * cdiv(h, 11);
-            // ... and 8-row bands (12 rows per wave, all requested at once) with two bands per wave while the launch is small enough for its
-            // latency to matter more than the halo rows it re-reads (measured at 128 x 128 maps, two parts per map: bs = 64 17.3 -> 16.6 us,
-            // bs = 128 19.2 -> 18.2, exact top-k 24.6 -> 23.3; bs = 512 36.5 -> 38.1: from 1024 maps the 11-row bands stay)
-            const bool half_ok = g_map_half && strips == 1 && w <= 128;
-            const bool short_ok = units11 > 8 && units11 <= 16;
-            const int rows = units16 >= 16 ? 16 : (!short_ok || g_map_rows11 == 0) ? 16
-                           : (g_map_rows11 == 8 || (g_map_rows11 == 1 && half_ok && (int64_t)B * C < 1024)) ? (half_ok ? 8 : 11) : 11;
-            const int bands = cdiv(h, rows);
-            // maps up to 128 columns wide: two bands per wave (lanes 0-31 / 32-63), half the waves (sd_decode_set_option("map_half", 0): off)
-            const bool half = g_map_half && strips == 1 && w <= 128;
-            int want = g_map_split;
-            // (measured, `profiles/r05_decode_split_sweep.txt`: at bs = 64 -- 192 maps -- one block per map and three parts per map stream in the
-            // same 14 us, the kernel is bound by the start-up spread of its ~2500 waves and their first round trips, and the rank kernel pays for
-            // three times the lists; at bs = 512 the parts stream in 53 instead of 74 us: five 27 KB blocks per CU instead of one of 86 KB)
-            //  With two bands per wave (maps up to 128 columns) two parts per map pay from ~100 maps: bs = 64 21.4 -> 20.5 us, bs = 512 72.8 -> 53.6.)
-            if (want <= 0) want = ((rows == 11 || rows == 8) && strips == 1) ? (half ? ((int64_t)B * C >= 96 ? 2 : 1) : ((int64_t)B * C >= 384 ? cdiv(bands, 4) : 1)) : 1;
-            splits = std::max(1, std::min({want, MAP_SPLIT_MAX, bands}));
-            if ((int64_t)M * splits * K > RANK_KEYS_MAX || (int64_t)N * splits * P > RANK_KEYS_MAX) splits = 1;
-            const int per_block = strips * cdiv(bands, splits);            // units of work of the largest part
-            const int per_wave = half ? cdiv(per_block, 2) : per_block;    // wave-iterations of work of the largest part
-            const unsigned grid = (unsigned)(B * C * splits);
-            const float min_logit = conservative_min_logit(min_score);
-            const bool waves3 = g_map_waves3 == 2 || (g_map_waves3 == 1 && grid >= 1024u && min_score > 0.f);
-#define SD_STREAM(NT_, ROWS_, HALF_) hipLaunchKernelGGL((k_map_stream_select<NT_, ROWS_, HALF_>), dim3(grid), dim3(NT_), 0, st, g0, g1, h, w, min_score, min_logit, K, P, mw.cand, mw.stage1, splits)
-            if (half) {
-                if (rows == 8) { if (per_wave > 8) SD_STREAM(1024, 8, true); else if (per_wave > 4) SD_STREAM(512, 8, true); else SD_STREAM(256, 8, true); }
-                else if (rows == 16) { if (per_wave > 8) SD_STREAM(1024, 16, true); else if (per_wave > 4) SD_STREAM(512, 16, true); else SD_STREAM(256, 16, true); }
-                // (three band pairs per part -- the cfg shape in two parts -- on three waves where several blocks share a CU and a score
-                //  threshold keeps the selections short: bs = 512 32.1 -> 28.7 us; at bs = 64, 384 blocks, the idle fourth wave costs nothing
-                //  -- 9.6 vs 10.1 us: the start-up spread of a launch goes by its blocks, not its waves -- and the exact top-k's radix select over
-                //  ~1000 keys wants the fourth wave: 16.3 vs 21.0 us)
-                else            { if (per_wave > 8) SD_STREAM(1024, 11, true); else if (per_wave > 4) SD_STREAM(512, 11, true); else if (per_wave == 3 && waves3) SD_STREAM(192, 11, true); else SD_STREAM(256, 11, true); }
-            } else if (rows == 16) {
-                if (splits == 1 && units16 >= 16) SD_STREAM(1024, 16, false);
-                else if (per_block > 4 || splits == 1) SD_STREAM(512, 16, false);
-                else SD_STREAM(256, 16, false);
-            } else {
-                if (per_block > 8 || splits == 1) SD_STREAM(1024, 11, false);
-                else if (per_block > 4) SD_STREAM(512, 11, false);
-                else if (per_block == 3 && waves3) SD_STREAM(192, 11, false);
-                else SD_STREAM(256, 11, false);
-            }
-#undef SD_STREAM
-            SD_LAUNCH_CHECK();
-        } else {
-            const dim3 tgrid((unsigned)((int64_t)B * C * tiles));
-            if (vec && th == 32) hipLaunchKernelGGL(k_nms_slots_v<32>, tgrid, dim3(256), 0, st, g0, g1, h, w, tiles_x, tiles, min_score, mw.cand, mw.tile_cnt);
-            else if (vec)        hipLaunchKernelGGL(k_nms_slots_v<16>, tgrid, dim3(256), 0, st, g0, g1, h, w, tiles_x, tiles, min_score, mw.cand, mw.tile_cnt);
-            else if (th == 32)   hipLaunchKernelGGL(k_nms_slots<32>, tgrid, dim3(256), 0, st, g0, g1, h, w, tiles_x, tiles, min_score, mw.cand, mw.tile_cnt);
-            else                 hipLaunchKernelGGL(k_nms_slots<16>, tgrid, dim3(256), 0, st, g0, g1, h, w, tiles_x, tiles, min_score, mw.cand, mw.tile_cnt);
-            SD_LAUNCH_CHECK();
-            hipLaunchKernelGGL(k_select_map, dim3(B * C), dim3(SEL_THREADS), 0, st, mw.cand, mw.tile_cnt, tiles, TW * th, M, N, K, P, mw.stage1);
-            SD_LAUNCH_CHECK();
-        }
-        RegMaps rm{offsets, o_sb, o_sc, embeddings, e_sb, e_sc};
-        const int LM = M * splits, LN = N * splits;                  // lists per group
-        const size_t rg_lds = ((size_t)LM * K + (size_t)LN * P + K + P) * 8;
-        // ranks + gathers + association of an image in ONE block (two dependent launches less) where an image's lists are short: the
-        // ranking is serial per image there (stress, 16 lists of 128 / 512 keys in one 1024-thread block: 75 us against 8.6 + 7.4 for
-        // k_rank_maps + k_group_wide -- `profiles/r05_decode_split_sweep.txt`), so large selections keep the map-parallel pair.
-        // map_rank_group: 0 never, 1 by size (default), 2 the generic one-block kernel wherever its lists fit LDS (tests)
-        const int64_t n_keys = (int64_t)LM * K + (int64_t)LN * P;
-        const bool small = K <= RGS_K && P <= RGS_K && LM * K <= RGS_KEYS && LN * P <= RGS_KEYS && n_keys <= RGS_THREADS * RGS_KPT && h * w >= RGS_K;
-        if (g_map_rank_group == 1 && small) {
-            hipLaunchKernelGGL(k_rank_group_small, dim3(B), dim3(RGS_THREADS), 0, st, mw.stage1, LM, LN, h, w, K, P, conf, dist_px, rm, packed, B);
-            SD_LAUNCH_CHECK();
-            return 0;
-        }
-        if (rg_lds <= RANK_GROUP_LDS_MAX && (g_map_rank_group == 2 || (g_map_rank_group == 1 && n_keys <= 1024 && K <= 256 && P <= 256))) {
-            static thread_local bool raised_rg = false;             // per host thread: cheap, idempotent
-            if (!raised_rg) {
-                SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_rank_group<256>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)RANK_GROUP_LDS_MAX));
-                SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_rank_group<1024>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)RANK_GROUP_LDS_MAX));
-                raised_rg = true;
-            }
-            if (n_keys <= 1024 && K <= 256 && P <= 256)
-                hipLaunchKernelGGL(k_rank_group<256>, dim3(B), dim3(256), rg_lds, st, mw.stage1, LM, LN, h, w, K, P, conf, dist_px, rm, packed, B);
-            else
-                hipLaunchKernelGGL(k_rank_group<1024>, dim3(B), dim3(1024), rg_lds, st, mw.stage1, LM, LN, h, w, K, P, conf, dist_px, rm, packed, B);
-            SD_LAUNCH_CHECK();
-            return 0;
-        }
-        const size_t rank_lds = (size_t)std::max((int64_t)LM * K, (int64_t)LN * P) * 8;
-        if (rank_lds > 48 * 1024) {
-            static thread_local bool raised = false;               // per host thread: cheap, idempotent
-            if (!raised) {
-                SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_rank_maps), hipFuncAttributeMaxDynamicSharedMemorySize, RANK_KEYS_MAX * 8));
-                raised = true;
-            }
-        }
-        // (a part of a split map is one more sorted list of its group: k_rank_maps sees M * splits and N * splits lists)
-        hipLaunchKernelGGL(k_rank_maps, dim3(B * C * splits), dim3(SEL_THREADS), rank_lds, st, mw.stage1, LM, LN, K, P, mw.final_keys);
+    RegMaps rm{offsets, o_sb, o_sc, embeddings, e_sb, e_sc};
+    if (p.path == DECODE_PAIR) {
+        const PeaksWs ws = carve(workspace, B, M, N, h, w);
+        SD_HIP(hipMemsetAsync(ws.counters, 0, (size_t)B * 2 * CNT_STRIDE * sizeof(int), st));
+        hipLaunchKernelGGL(k_nms_tile<1>, p.stage1_l.grid, dim3(p.stage1_l.block), 0, st, g0, g1, h, w, cdiv(w, TW), 1, min_score, (float*)nullptr,
+                           ws.cand0, ws.cand1, ws.counters);
         SD_LAUNCH_CHECK();
-        const size_t group_lds = (size_t)K * 8 + (size_t)P * 8 + (size_t)((K + 3) & ~3) * 8 + (size_t)(K + P) * 4;
-        hipLaunchKernelGGL(k_group_wide, dim3(B, cdiv(P, GROUP_PARTS)), dim3(GROUP_THREADS), group_lds, st, mw.final_keys, h, w, K, P,
-                           conf, dist_px, rm, packed, B);
+        hipLaunchKernelGGL(k_select_group, p.rank_l.grid, dim3(p.rank_l.block), 0, st, ws.cand0, ws.cand1, ws.counters, M, N, h, w, K, P, conf,
+                           dist_px, rm, packed, B);
         SD_LAUNCH_CHECK();
         return 0;
     }
-    const PeaksWs ws = carve(workspace, B, M, N, h, w);
-    SD_REQUIRE(workspace_bytes >= ws.bytes, SD_ERR_WORKSPACE, "sd_decode: workspace %zu < %zu", workspace_bytes, ws.bytes);
-    SD_HIP(hipMemsetAsync(ws.counters, 0, (size_t)B * 2 * CNT_STRIDE * sizeof(int), st));
-    const int tiles_x = cdiv(w, TW), tiles_y = cdiv(h, TH);
-    hipLaunchKernelGGL(k_nms_tile<1>, dim3(tiles_x * tiles_y, M + N, B), dim3(256), 0, st, g0, g1, h, w, tiles_x, 1, exact_topk ? 0.f : conf, (float*)nullptr,
-                       ws.cand0, ws.cand1, ws.counters);
+    const MapWs mw = carve_map(workspace, B, M + N, h, w, p.th, K, P);
+    const LaunchDims& s1 = p.stage1_l;
+    switch (p.stage1) {
+    case STAGE1_STREAM: {
+        const StreamKernel kernel = stream_kernel(p);
+        SD_REQUIRE(kernel != nullptr, SD_ERR_INVALID, "sd_decode: no k_map_stream_select<%d, %d, %d>", p.threads, p.rows, (int)p.half);
+        hipLaunchKernelGGL(kernel, s1.grid, dim3(s1.block), 0, st, g0, g1, h, w, min_score, conservative_min_logit(min_score), K, P, mw.cand, mw.stage1, p.splits);
+        break;
+    }
+    case STAGE1_SLOTS_V:
+        if (p.th == 32) hipLaunchKernelGGL(k_nms_slots_v<32>, s1.grid, dim3(s1.block), 0, st, g0, g1, h, w, p.tiles_x, p.tiles, min_score, mw.cand, mw.tile_cnt);
+        else            hipLaunchKernelGGL(k_nms_slots_v<16>, s1.grid, dim3(s1.block), 0, st, g0, g1, h, w, p.tiles_x, p.tiles, min_score, mw.cand, mw.tile_cnt);
+        break;
+    case STAGE1_SLOTS:
+        if (p.th == 32) hipLaunchKernelGGL(k_nms_slots<32>, s1.grid, dim3(s1.block), 0, st, g0, g1, h, w, p.tiles_x, p.tiles, min_score, mw.cand, mw.tile_cnt);
+        else            hipLaunchKernelGGL(k_nms_slots<16>, s1.grid, dim3(s1.block), 0, st, g0, g1, h, w, p.tiles_x, p.tiles, min_score, mw.cand, mw.tile_cnt);
+        break;
+    }
     SD_LAUNCH_CHECK();
-    RegMaps rm{offsets, o_sb, o_sc, embeddings, e_sb, e_sc};
-    hipLaunchKernelGGL(k_select_group, dim3(B), dim3(2 * SEL_THREADS), 0, st, ws.cand0, ws.cand1, ws.counters, M, N, h, w, K, P, conf,
-                       dist_px, rm, packed, B);
+    if (p.stage1 != STAGE1_STREAM) {
+        hipLaunchKernelGGL(k_select_map, p.select_l.grid, dim3(p.select_l.block), 0, st, mw.cand, mw.tile_cnt, p.tiles, TW * p.th, M, N, K, P, mw.stage1);
+        SD_LAUNCH_CHECK();
+    }
+    const LaunchDims& r = p.rank_l;
+    switch (p.rank) {
+    case RANK_GROUP_SMALL:
+        hipLaunchKernelGGL(k_rank_group_small, r.grid, dim3(r.block), 0, st, mw.stage1, p.LM, p.LN, h, w, K, P, conf, dist_px, rm, packed, B);
+        break;
+    case RANK_GROUP_256:
+    case RANK_GROUP_1024:
+        if (int e = raise_dynamic_lds<k_rank_group<256>>((int)RANK_GROUP_LDS_MAX)) return e;
+        if (int e = raise_dynamic_lds<k_rank_group<1024>>((int)RANK_GROUP_LDS_MAX)) return e;
+        if (p.rank == RANK_GROUP_256)
+            hipLaunchKernelGGL(k_rank_group<256>, r.grid, dim3(r.block), r.lds, st, mw.stage1, p.LM, p.LN, h, w, K, P, conf, dist_px, rm, packed, B);
+        else
+            hipLaunchKernelGGL(k_rank_group<1024>, r.grid, dim3(r.block), r.lds, st, mw.stage1, p.LM, p.LN, h, w, K, P, conf, dist_px, rm, packed, B);
+        break;
+    case RANK_MAPS_GROUP_WIDE:
+        if (r.lds > 48 * 1024)
+            if (int e = raise_dynamic_lds<k_rank_maps>(RANK_KEYS_MAX * 8)) return e;
+        hipLaunchKernelGGL(k_rank_maps, r.grid, dim3(r.block), r.lds, st, mw.stage1, p.LM, p.LN, K, P, mw.final_keys);
+        SD_LAUNCH_CHECK();
+        hipLaunchKernelGGL(k_group_wide, p.group_l.grid, dim3(p.group_l.block), p.group_l.lds, st, mw.final_keys, h, w, K, P, conf, dist_px, rm,
+                           packed, B);
+        break;
+    }
     SD_LAUNCH_CHECK();
     return 0;
 }
 
-constexpr int FUSED_LDS_LIMIT = 96 * 1024;    // dynamic LDS the launcher asks for at most (gfx950: 160 KB per CU)
-static int next_pow2_host(int v) { int p = 1; while (p < v) p <<= 1; return p; }
-// Tile height of one fused launch.  64x16 tiles give a small batch the most workgroups (bs=1: 32 + 1); once the launch holds more
-// tile blocks than the chip keeps resident at once (about 1200 with the selector's LDS block), they run in rounds and 64x32 tiles --
-// half the blocks, half the records the selectors wait for, 36 halo rows per 32 instead of 20 per 16 -- finish sooner.  Measured
-// (tools/decode_tile_sweep.py, 3 maps of 128x128, us per launch 64x16 / 64x32): bs=1 12.8 / 14.0, bs=16 14.6 / 15.2, bs=32 16.6 / 16.7,
-// bs=48 18.7 / 18.9, bs=64 21.1 / 20.1, bs=96 25.3 / 23.6, bs=128 29.6 / 27.1: the switch sits at 2688 blocks (bs=56).  sd_decode_set_option("tall_tiles_from", n) moves the switch.
-static thread_local int g_tall_tiles_from = 2688;      // per host thread, like the conv dispatch thresholds
-int sd_decode_set_option(const char* name, int value) {
-    if (name && !strcmp(name, "tall_tiles_from")) { g_tall_tiles_from = value; return 0; }
-    if (name && !strcmp(name, "map_parallel_from")) {            // < 0: back to the built-in rule (map_from)
-        g_map_from_user = value >= 0; g_map_parallel_from = value >= 0 ? value : 2560; return 0;
-    }
-    if (name && !strcmp(name, "map_tile_height")) { g_map_tile_height = value; return 0; }
-    if (name && !strcmp(name, "map_scalar_nms")) { g_map_scalar_nms = value; return 0; }
-    if (name && !strcmp(name, "map_rows11")) { g_map_rows11 = value; return 0; }
-    if (name && !strcmp(name, "map_stream")) { g_map_stream = value; return 0; }
-    if (name && !strcmp(name, "map_split")) { g_map_split = value; return 0; }
-    if (name && !strcmp(name, "map_half")) { g_map_half = value; return 0; }
-    if (name && !strcmp(name, "map_waves3")) { g_map_waves3 = value; return 0; }
-    if (name && !strcmp(name, "map_rank_group")) { g_map_rank_group = value; return 0; }
-    sd::set_error("sd_decode_set_option: unknown option '%s'", name ? name : "(null)");
-    return SD_ERR_INVALID;
-}
-static int fused_tile_height(int B, int M, int N, int h, int w) {
-    const int64_t blocks16 = (int64_t)std::max(B, 1) * (M + N) * cdiv(w, TW) * cdiv(h, 16);
-    return blocks16 >= g_tall_tiles_from ? 32 : 16;
-}
-static size_t fused_tiles(int h, int w, int th) { return (size_t)cdiv(w, TW) * cdiv(h, th); }
-
-// both sizes cover EITHER tile height (the option may change between sizing and launch)
-size_t sd_decode_state_bytes(int B, int M, int N, int h, int w) {
-    return align_up((size_t)std::max(B, 1) * (M + N) * fused_tiles(h, w, 16) * REC_WORDS * sizeof(unsigned), 256);
-}
-
-size_t sd_decode_fused_workspace_bytes(int B, int M, int N, int h, int w, int K, int P) {
-    (void)K; (void)P;
-    const size_t t = std::max(fused_tiles(h, w, 16) * TW * 16, fused_tiles(h, w, 32) * TW * 32);
-    return align_up((size_t)B * (M + N) * t * 8, 256);
-}
 
 #ifdef SD_DECODE_TRACE
 int sd_debug_read_trace(unsigned long long* out, int n) {
@@ -2712,25 +2916,11 @@ int sd_stream_synchronize(sd_stream_t stream) {
 }
 
 int sd_decode_fused_supported(int B, int M, int N, int h, int w, int K, int P) {
-    if (B <= 0 || M <= 0 || N <= 0 || h <= 0 || w <= 0 || K <= 0 || P <= 0) return 0;
-    // judged on the 64x16 tiling (more tiles, more LDS for their counts): what fits there fits with 64x32 tiles
-    const int64_t nti = (int64_t)(M + N) * fused_tiles(h, w, 16);
-    return K <= FUSED_MAX_TOPK && P <= FUSED_MAX_TOPK && B <= 256 && nti <= 32 * FUSED_THREADS && (int64_t)B * nti + B < (1ll << 31) &&
-           fused_lds(K, P, (int)nti, std::max(FUSED_CAP_EXACT, 2 * next_pow2_host(std::max(K, P))), 32).total <= FUSED_LDS_LIMIT;
+    return plan_decode_fused(B, M, N, h, w, K, P, 0, g_decode_options).supported;
 }
 
-// Where ONE launch is the faster decoder (measured: profiles/r02_decode_variants.txt): image geometries of at most 256 tile blocks
-// (512x512 with 2 + 1 maps = 48; the selector's LDS is paid by every tile block of the grid, and with ~1000 tiles per image -- 1024x1024,
-// 8 + 8 maps -- it halves the occupancy of the 16 k tile blocks: 451 us vs 116 us for sd_decode at K = 128, P = 512), and for the exact
-// top-k only small batches (bs = 64: 39.0 vs 31.3 us, its two 2048-key sort buffers cost the tile blocks occupancy).
-static int64_t fused_image_tiles(int M, int N, int h, int w) { return (int64_t)(M + N) * fused_tiles(h, w, 16); }
 int sd_decode_fused_recommended(int B, int M, int N, int h, int w, int K, int P, int exact_topk) {
-    // round 5: from the batch where sd_decode takes its map-parallel path (2560 tile blocks per call: bs >= 54 at the cfg shape) that path is
-    // the faster one on maps up to 128 columns wide -- two bands per wave, two parts per map, ranks + association in one launch: 20.5 us per
-    // bs = 64 batch against 23.5 for the one-launch kernel (`profiles/r05_decode_split_sweep.txt`)
-    const int64_t blocks16 = (int64_t)B * (M + N) * cdiv(w, TW) * cdiv(h, 16);
-    if (blocks16 >= map_from(w, (exact_topk & 1) != 0) && g_map_half && g_map_stream && w <= 128 && w % 4 == 0 && map_path_possible(M, N, h, w, K, P)) return 0;
-    return sd_decode_fused_supported(B, M, N, h, w, K, P) && fused_image_tiles(M, N, h, w) <= 256 && (!(exact_topk & 1) || B <= 8);
+    return plan_decode_fused(B, M, N, h, w, K, P, exact_topk, g_decode_options).recommended;
 }
 
 int sd_decode_fused(const float* anchor_hm, int64_t a_sb, int64_t a_sc, const float* part_hm, int64_t p_sb, int64_t p_sc,
@@ -2741,52 +2931,42 @@ int sd_decode_fused(const float* anchor_hm, int64_t a_sb, int64_t a_sc, const fl
     if (int e = check_map("sd_decode_fused(part_hm)", part_hm, p_sb, p_sc, B, N, h, w)) return e;
     if (int e = check_map("sd_decode_fused(offsets)", offsets, o_sb, o_sc, B, 2, h, w)) return e;
     if (int e = check_map("sd_decode_fused(embeddings)", embeddings, e_sb, e_sc, B, 2, h, w)) return e;
-    SD_REQUIRE(K > 0 && K <= FUSED_MAX_TOPK && (int64_t)K <= (int64_t)M * h * w, SD_ERR_INVALID,
-               "sd_decode_fused: max_objects=%d out of range (1..%d; use sd_decode beyond)", K, FUSED_MAX_TOPK);
-    SD_REQUIRE(P > 0 && P <= FUSED_MAX_TOPK && (int64_t)P <= (int64_t)N * h * w, SD_ERR_INVALID,
-               "sd_decode_fused: max_parts=%d out of range (1..%d; use sd_decode beyond)", P, FUSED_MAX_TOPK);
-    // at most B selector blocks wait inside the grid: keep them far below the resident block slots of the chip (256 CUs x >= 2)
-    SD_REQUIRE(B <= 256, SD_ERR_INVALID, "sd_decode_fused: batch %d > 256 (selector blocks must stay resident); use sd_decode", B);
+    SD_REQUIRE(K > 0 && (int64_t)K <= (int64_t)M * h * w, SD_ERR_INVALID, FUSED_RANGE_MSG, "max_objects", K, FUSED_MAX_TOPK);
+    SD_REQUIRE(P > 0 && (int64_t)P <= (int64_t)N * h * w, SD_ERR_INVALID, FUSED_RANGE_MSG, "max_parts", P, FUSED_MAX_TOPK);
     SD_REQUIRE(packed && workspace && state, SD_ERR_INVALID, "sd_decode_fused: null pointer");
-    // exact_topk bit 1 (value 2): accept geometries where the two-launch sd_decode is the faster decoder (tests of this kernel)
-    const bool force = (exact_topk & 2) != 0;
-    exact_topk &= 1;
-    SD_REQUIRE(force || (M > 0 && N > 0 && fused_image_tiles(M, N, h, w) <= 256), SD_ERR_INVALID,
-               "sd_decode_fused: %lld tile blocks per image (> 256): sd_decode is several times faster for this geometry "
-               "(sd_decode_fused_recommended() == 0); pass exact_topk | 2 to run it here anyway", (long long)fused_image_tiles(std::max(M, 1), std::max(N, 1), h, w));
-    const int th = fused_tile_height(B, M, N, h, w);
-    const int tiles_x = cdiv(w, TW), tiles_y = cdiv(h, th);
-    const int tiles = tiles_x * tiles_y;
-    const int64_t nti = (int64_t)(M + N) * tiles;
-    SD_REQUIRE(nti <= 32 * FUSED_THREADS, SD_ERR_INVALID, "sd_decode_fused: %lld tiles per image > %d; use sd_decode", (long long)nti,
-               32 * FUSED_THREADS);
-    SD_REQUIRE((int64_t)B * nti + B < (1ll << 31), SD_ERR_INVALID, "sd_decode_fused: grid too large");
+    const FusedPlan p = plan_decode_fused(B, M, N, h, w, K, P, exact_topk, g_decode_options);
+    SD_REQUIRE(p.err == 0, p.err, "%s", p.reason);
     SD_REQUIRE(state_bytes >= sd_decode_state_bytes(B, M, N, h, w), SD_ERR_WORKSPACE, "sd_decode_fused: state %zu < %zu bytes", state_bytes,
                sd_decode_state_bytes(B, M, N, h, w));
     const size_t need = sd_decode_fused_workspace_bytes(B, M, N, h, w, K, P);
     SD_REQUIRE(workspace_bytes >= need, SD_ERR_WORKSPACE, "sd_decode_fused: workspace %zu < %zu", workspace_bytes, need);
-    // rank sort needs 2 * np2 <= cap with np2 >= max(K, P): never below 2 * next_pow2(max(K, P))
-    int sort_cap = exact_topk ? FUSED_CAP_EXACT : FUSED_CAP_FAST;
-    while (sort_cap < 2 * std::max(K, P)) sort_cap *= 2;
-    const FusedLds lds = fused_lds(K, P, (int)nti, sort_cap, th);
-    SD_REQUIRE(lds.total <= FUSED_LDS_LIMIT, SD_ERR_INVALID, "sd_decode_fused: %d maps x %d tiles need %d bytes of LDS (> %d); use sd_decode",
-               M + N, tiles, lds.total, FUSED_LDS_LIMIT);
-    auto kern = th == 32 ? k_decode_fused<32> : k_decode_fused<16>;
-    if (lds.total > 48 * 1024) {
-        static thread_local bool raised[2] = {false, false};      // per host thread: cheap, idempotent
-        if (!raised[th == 32]) {
-            SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, FUSED_LDS_LIMIT));
-            raised[th == 32] = true;
-        }
-    }
+    if (p.lds.total > 48 * 1024)
+        if (int e = p.th == 32 ? raise_dynamic_lds<k_decode_fused<32>>(FUSED_LDS_LIMIT) : raise_dynamic_lds<k_decode_fused<16>>(FUSED_LDS_LIMIT)) return e;
     Group g0{anchor_hm, a_sb, a_sc, M}, g1{part_hm, p_sb, p_sc, N};
     RegMaps rm{offsets, o_sb, o_sc, embeddings, e_sb, e_sc};
-    hipLaunchKernelGGL(kern, dim3((unsigned)(B * nti + B)), dim3(FUSED_THREADS), (size_t)lds.total, (hipStream_t)stream, g0, g1,
-                       h, w, tiles_x, tiles, exact_topk ? 0.f : conf, reinterpret_cast<uint64_t*>(workspace),
-                       reinterpret_cast<unsigned*>(state), K, P, sort_cap, conf, dist_px, rm, packed, B);
+    hipLaunchKernelGGL(p.th == 32 ? k_decode_fused<32> : k_decode_fused<16>, dim3(p.grid), dim3(FUSED_THREADS), (size_t)p.lds.total,
+                       (hipStream_t)stream, g0, g1, h, w, p.tiles_x, p.tiles, (exact_topk & 1) ? 0.f : conf, reinterpret_cast<uint64_t*>(workspace),
+                       reinterpret_cast<unsigned*>(state), K, P, p.sort_cap, conf, dist_px, rm, packed, B);
     SD_LAUNCH_CHECK();
     return 0;
 }
+
+const char* sd_decode_kernel_names(int B, int M, int N, int h, int w, int K, int P, int exact_topk, int flags) {
+    static thread_local char line[384];
+    line[0] = 0;
+    if (B <= 0 || M <= 0 || N <= 0 || h <= 0 || w <= 0 || K <= 0 || P <= 0) return line;
+    if (flags & 2) {
+        const FusedPlan p = plan_decode_fused(B, M, N, h, w, K, P, exact_topk, g_decode_options);
+        if (p.err) { snprintf(line, sizeof(line), "refused: %s", p.reason); return line; }
+        const LaunchDims l{dim3(p.grid), FUSED_THREADS, (size_t)p.lds.total};
+        append_launch(line, sizeof(line), 0, p.th == 32 ? "k_decode_fused<32>" : "k_decode_fused<16>", &l);
+        return line;
+    }
+    // (annotations-only is planned with a positive confidence threshold: what every caller passes)
+    decode_plan_names(plan_decode(B, M, N, h, w, K, P, !exact_topk, (flags & 1) != 0, g_decode_options), line, sizeof(line));
+    return line;
+}
+
 
 int sd_decode_group(const float* a_score, const int64_t* a_ind, const float* a_cls, const float* p_score, const int64_t* p_ind,
                     const float* p_cls, const float* offsets, int64_t o_sb, int64_t o_sc, const float* embeddings, int64_t e_sb,

@@ -196,6 +196,34 @@ def test_set_option_is_host_only_and_rejects_unknown_names():
     assert lib.sd_decode_fused_workspace_bytes(64, 2, 1, 132, 128, 20, 40) == ws >= 64 * 3 * 2 * 5 * 2048 * 8
     assert lib.sd_decode_set_option(b"tall_tiles_from", 2688) == 0
     assert lib.sd_decode_set_option(b"nope", 1) == -1 and b"nope" in lib.sd_last_error()
+    # what a decode launches is host arithmetic too (plan_decode / plan_decode_fused); flags bit 0 = vector-loadable planes, bit 1 = fused.
+    # Expectations read off the dispatch code of the commit before the plan functions, by hand.
+    names = lambda *a: lib.sd_decode_kernel_names(*a).decode()
+    cfg = (64, 2, 1, 128, 128, 20, 40)
+    # cfg shape at bs = 64: 8-row bands, two bands per wave, two parts per map (64 x 3 x 2 blocks of 4 waves), ranks + association in one launch
+    assert names(*cfg, 0, 1) == ("k_map_stream_select<256, 8, true> grid=384x1x1 block=256 lds=0; "
+                                 "k_rank_group_small grid=64x1x1 block=256 lds=0")
+    assert lib.sd_decode_set_option(b"map_parallel_from", 1 << 30) == 0
+    assert names(*cfg, 0, 1) == "memset; k_nms_tile<1> grid=16x3x64 block=256 lds=0; k_select_group grid=64x1x1 block=1024 lds=0"
+    assert lib.sd_decode_set_option(b"map_parallel_from", 1) == 0
+    # 66 columns are not a multiple of four: the scalar tile kernel + per-map selection
+    assert names(3, 3, 2, 66, 66, 12, 24, 0, 1) == ("k_nms_slots<16> grid=150x1x1 block=256 lds=0; k_select_map grid=15x1x1 block=512 lds=0; "
+                                                    "k_rank_group_small grid=3x1x1 block=256 lds=0")
+    assert lib.sd_decode_set_option(b"map_parallel_from", -1) == 0
+    # stress shape: 16 waves per map on 16-row bands; 16 lists of 128 / 512 keys keep the map-parallel ranks + the wide association
+    assert names(16, 8, 8, 256, 256, 128, 512, 0, 1) == ("k_map_stream_select<1024, 16, false> grid=256x1x1 block=1024 lds=0; "
+                                                         "k_rank_maps grid=256x1x1 block=512 lds=32768; k_group_wide grid=16x8x1 block=256 lds=8704")
+    # bs = 1: the one-launch kernel on 64x16 tiles, 3 x 16 tile blocks + 1 selector
+    assert names(1, 2, 1, 128, 128, 20, 40, 0, 2).startswith("k_decode_fused<16> grid=49x1x1 block=256 lds=")
+    assert names(300, 2, 1, 128, 128, 20, 40, 0, 2).startswith("refused: sd_decode_fused: batch 300 > 256")
+    assert names(0, 2, 1, 128, 128, 20, 40, 0, 0) == ""
+    # every documented key is accepted (set to its default here), an unknown one refused
+    for key, default in (("tall_tiles_from", 2688), ("map_parallel_from", -1), ("map_rows11", 1), ("map_stream", 1), ("map_tile_height", 0),
+                         ("map_scalar_nms", 0), ("map_split", 0), ("map_half", 1), ("map_waves3", 1), ("map_rank_group", 1)):
+        assert lib.sd_decode_set_option(key.encode(), default) == 0, key
+        assert key in (ROOT / "include" / "sdnet_hip.h").read_text() and key in (ROOT / "INTEGRATION.md").read_text(), key
+    assert names(*cfg, 0, 1).startswith("k_map_stream_select<256, 8, true> grid=384x1x1")
+    assert lib.sd_decode_set_option(b"map_parallel", 1) == -1 and b"map_parallel" in lib.sd_last_error()
     # kernel choice is host arithmetic on the descriptor: a 3x3 / 1 / 1 conv with a chip-filling grid takes the patch kernel,
     # a strided one the 256-row tile kernel, a small one the 128-row tiles
     d = L.ConvDesc()
