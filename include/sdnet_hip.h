@@ -567,6 +567,33 @@ int sd_head_bwd_bf16(const float* dy, const void* x_bf16, const float* w, void* 
 int sd_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, int step,
                  float lr, float beta1, float beta2, float eps, float grad_scale, sd_stream_t stream);
 
+/* The same step with the large-batch options (no reference counterpart; the reference's optimizer is plain Adam): decoupled weight decay as
+ * in torch.optim.AdamW, global-norm clipping as in torch.nn.utils.clip_grad_norm_, and an exponential moving average of the weights -- one
+ * reduction launch (only for clipping) plus one fused update, no host synchronisation.
+ *   sd_grad_sumsq: fp64 partial sums of squares of grad[0..n) into the workspace (sd_grad_sumsq_workspace_bytes(n) bytes = one double per
+ *     block, 8-byte aligned; every one is written, earlier contents do not matter).  Fixed reduction order: the same gradients give the same
+ *     bits on every run and on every rank.
+ *   sd_optim_step: sd_adam_step's arguments, then
+ *     weight_decay >= 0 and decay_mask: p *= 1 - lr * weight_decay before the Adam update where decay_mask[i / 4] != 0 (one byte per group of
+ *       four floats; NULL: everywhere);
+ *     max_norm >= 0 (0: no clipping), partials / npartials: the workspace sd_grad_sumsq has just filled and its count of doubles.  Every
+ *       block finishes the partials itself in fp64 in a fixed order: norm = |grad_scale| * sqrt(sum) is the norm of the gradient after
+ *       grad_scale, the gradient is multiplied by min(1, max_norm / (norm + 1e-6)).  A norm that is not finite (an inf or nan gradient) skips
+ *       the step: parameters, moments and EMA are not written;
+ *     ema (NULL: none) and ema_decay in [0, 1): ema = ema_decay * ema + (1 - ema_decay) * p_new, from the registers holding the new parameter;
+ *     status (SD_OPTIM_STATUS_BYTES, 4-byte aligned; needed and written only when max_norm > 0): [0] float norm, [1] float coefficient applied
+ *       (0 for a skipped step), [2] int32 count of skipped steps (incremented, never reset), [3] reserved.
+ *   Options that are off are compiled out (one kernel per combination); with all three off the launch is sd_adam_step's own kernel.
+ * Errors (text in sd_last_error()): SD_ERR_INVALID for n % 4 != 0, step < 1, negative weight_decay / max_norm, ema_decay outside [0, 1),
+ * max_norm > 0 without partials or status; SD_ERR_ALIGN for misaligned pointers; SD_ERR_WORKSPACE for a workspace that is too small. */
+#define SD_OPTIM_STATUS_BYTES 16
+size_t sd_grad_sumsq_workspace_bytes(int64_t n);
+int sd_grad_sumsq(const float* grad, int64_t n, void* workspace, size_t workspace_bytes, sd_stream_t stream);
+int sd_optim_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, int step,
+                  float lr, float beta1, float beta2, float eps, float grad_scale, float weight_decay,
+                  const uint8_t* decay_mask, float max_norm, const void* partials, int npartials, float* ema,
+                  float ema_decay, void* status, sd_stream_t stream);
+
 /* ---- gradient exchange (the reference's step, trainer.py:113-124, is single-device) -------------------
  * Thin wrapper over RCCL, one communicator per process (= per GPU).  librccl.so.1 is dlopen()ed on first use (the copy a
  * PyTorch-ROCm process has already loaded is reused), so libsdnet_hip.so has no link-time dependency on it.

@@ -1167,6 +1167,95 @@ __global__ __launch_bounds__(256) void k_adam(float* __restrict__ p, const float
 }
 
 // ------------------------------------------------------------------------------------------
+// Optimizer step with options (sd_optim_step): decoupled weight decay (torch.optim.AdamW), global-norm
+// clipping (torch.nn.utils.clip_grad_norm_) and a weight EMA, fused into k_adam's one pass.  The norm
+// needs every gradient before the first update: k_grad_sumsq leaves one fp64 partial per block and
+// every block of k_optim finishes them itself (at most 4 KB from L2) -- no third launch, no host trip.
+// Both reductions run in a fixed order (per thread in index order, 64 lanes by shuffle, 4 waves in
+// order): the same gradients give the same bits on every run and every rank.  No atomics.
+// ------------------------------------------------------------------------------------------
+constexpr int SUMSQ_MAX_BLOCKS = 512;         // partials: 2 blocks per CU, eight 16-byte loads in flight per thread
+
+__device__ __forceinline__ double sumsq4(const float4 a) {
+    return ((double)a.x * a.x + (double)a.y * a.y) + ((double)a.z * a.z + (double)a.w * a.w);
+}
+
+// sum of 256 per-thread doubles, the same value in every thread
+__device__ __forceinline__ double block_sum_256(double s, double* red4) {
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) red4[threadIdx.x >> 6] = s;
+    __syncthreads();
+    return ((red4[0] + red4[1]) + red4[2]) + red4[3];
+}
+
+// (plain loads, not non-temporal ones: the update kernel that follows re-reads the same 87 MB, which may then still be in the last-level cache)
+__global__ __launch_bounds__(256) void k_grad_sumsq(const float* __restrict__ g, int64_t n4, double* __restrict__ partial) {
+    __shared__ double red[4];
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    const float4* G = reinterpret_cast<const float4*>(g);
+    double s = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += 8 * stride) {
+        float4 a[8];                                       // eight loads in flight; past the end: the last group re-read, counted as zero
+#pragma unroll
+        for (int k = 0; k < 8; ++k) a[k] = G[min(i + k * stride, n4 - 1)];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) s += i + k * stride < n4 ? sumsq4(a[k]) : 0.0;
+    }
+    s = block_sum_256(s, red);
+    if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+// status block (SD_OPTIM_STATUS_BYTES): [0] float global norm, [1] float clip coefficient, [2] int32 skipped steps, [3] reserved
+template <bool DECAY, bool CLIP, bool EMA>
+__global__ __launch_bounds__(256) void k_optim(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                float* __restrict__ v, int64_t n4, float lr, float b1, float b2, float eps, float bc1,
+                                                float bc2_sqrt, float gscale, float decay_mul, const uint8_t* __restrict__ mask,
+                                                float max_norm, const double* __restrict__ partial, int npartial,
+                                                float* __restrict__ ema, float ema_decay, uint32_t* __restrict__ status) {
+    float coef = 1.f;
+    if (CLIP) {
+        __shared__ double red[4];
+        double s = 0.0;
+        for (int k = threadIdx.x; k < npartial; k += 256) s += partial[k];
+        s = block_sum_256(s, red);
+        const float norm = (float)(fabs((double)gscale) * sqrt(s));            // of the gradient after grad_scale
+        const bool finite = (__float_as_uint(norm) & 0x7f800000u) != 0x7f800000u;
+        coef = finite ? fminf(1.f, max_norm / (norm + 1e-6f)) : 0.f;           // clip_grad_norm_: max_norm / (total_norm + 1e-6), clamped to 1
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            status[0] = __float_as_uint(norm);
+            status[1] = __float_as_uint(coef);
+            if (!finite) status[2] = status[2] + 1u;
+        }
+        if (!finite) return;                                                   // an inf / nan gradient: the step is skipped, nothing is written
+    }
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+        float4 pp = reinterpret_cast<float4*>(p)[i];
+        const float4 gg = reinterpret_cast<const float4*>(g)[i];
+        float4 mm = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
+        float4 ee = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (EMA) ee = reinterpret_cast<float4*>(ema)[i];
+        const bool decay = DECAY && (mask == nullptr || mask[i] != 0);
+        float* P = &pp.x; const float* G = &gg.x; float* Mo = &mm.x; float* V = &vv.x; float* E = &ee.x;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float gr = G[j] * gscale;
+            if (CLIP) gr *= coef;
+            if (decay) P[j] *= decay_mul;                            // AdamW: param.mul_(1 - lr * weight_decay)
+            Mo[j] = b1 * Mo[j] + (1.f - b1) * gr;                     // from here on: k_adam, same operation order
+            V[j] = b2 * V[j] + (1.f - b2) * gr * gr;
+            const float denom = sqrtf(V[j]) / bc2_sqrt + eps;
+            P[j] -= (lr / bc1) * (Mo[j] / denom);
+            if (EMA) E[j] = ema_decay * E[j] + (1.f - ema_decay) * P[j];
+        }
+        reinterpret_cast<float4*>(p)[i] = pp;
+        reinterpret_cast<float4*>(m)[i] = mm;
+        reinterpret_cast<float4*>(v)[i] = vv;
+        if (EMA) reinterpret_cast<float4*>(ema)[i] = ee;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // bf16 backbone (inference): weight cast, max-pool and head reading bf16 NHWC activations
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ float bf2f_(uint16_t v) { return __uint_as_float((uint32_t)v << 16); }
@@ -2259,6 +2348,59 @@ int sd_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg
     const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
     hipLaunchKernelGGL(k_adam, dim3(ew_grid(n / 4)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n / 4, lr, beta1, beta2, eps,
                        (float)bc1, (float)sqrt(bc2), grad_scale);
+    SD_LAUNCH_CHECK();
+    return 0;
+}
+
+static inline int sumsq_blocks(int64_t n) { return n > 0 ? (int)std::min<int64_t>(cdiv(n / 4, 256), SUMSQ_MAX_BLOCKS) : 0; }
+
+size_t sd_grad_sumsq_workspace_bytes(int64_t n) { return (size_t)sumsq_blocks(n) * sizeof(double); }
+
+int sd_grad_sumsq(const float* grad, int64_t n, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
+    SD_REQUIRE(grad && workspace && n > 0 && n % 4 == 0, SD_ERR_INVALID, "sd_grad_sumsq: bad arguments (n %% 4 == 0)");
+    SD_REQUIRE(aligned16(grad) && (reinterpret_cast<uintptr_t>(workspace) & 7u) == 0, SD_ERR_ALIGN,
+               "sd_grad_sumsq: grad must be 16-byte aligned, the workspace 8-byte aligned");
+    SD_REQUIRE(workspace_bytes >= sd_grad_sumsq_workspace_bytes(n), SD_ERR_WORKSPACE, "sd_grad_sumsq: workspace too small");
+    hipLaunchKernelGGL(k_grad_sumsq, dim3(sumsq_blocks(n)), dim3(256), 0, (hipStream_t)stream, grad, n / 4, (double*)workspace);
+    SD_LAUNCH_CHECK();
+    return 0;
+}
+
+int sd_optim_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, int step, float lr, float beta1, float beta2,
+                  float eps, float grad_scale, float weight_decay, const uint8_t* decay_mask, float max_norm, const void* partials,
+                  int npartials, float* ema, float ema_decay, void* status, sd_stream_t stream) {
+    SD_REQUIRE(param && grad && exp_avg && exp_avg_sq && n > 0 && n % 4 == 0 && step >= 1, SD_ERR_INVALID, "sd_optim_step: bad arguments (n %% 4 == 0, step >= 1)");
+    SD_REQUIRE(aligned16(param) && aligned16(grad) && aligned16(exp_avg) && aligned16(exp_avg_sq) && aligned16(ema), SD_ERR_ALIGN,
+               "sd_optim_step: pointers must be 16-byte aligned");
+    SD_REQUIRE(weight_decay >= 0.f, SD_ERR_INVALID, "sd_optim_step: weight_decay must be >= 0 (got %g)", (double)weight_decay);
+    SD_REQUIRE(max_norm >= 0.f, SD_ERR_INVALID, "sd_optim_step: max_norm must be >= 0 (got %g; 0 = no clipping)", (double)max_norm);
+    SD_REQUIRE(ema_decay >= 0.f && ema_decay < 1.f, SD_ERR_INVALID, "sd_optim_step: ema_decay must be in [0, 1) (got %g)", (double)ema_decay);
+    const bool decay = weight_decay > 0.f, clip = max_norm > 0.f, avg = ema != nullptr;
+    if (clip) {
+        SD_REQUIRE(partials && npartials > 0 && status, SD_ERR_INVALID,
+                   "sd_optim_step: max_norm > 0 needs the partials of sd_grad_sumsq (pointer and count) and the status block");
+        SD_REQUIRE(npartials == sumsq_blocks(n), SD_ERR_INVALID, "sd_optim_step: %d partials, sd_grad_sumsq writes %d for n = %lld "
+                   "(sd_grad_sumsq_workspace_bytes(n) / 8)", npartials, sumsq_blocks(n), (long long)n);
+        SD_REQUIRE((reinterpret_cast<uintptr_t>(partials) & 7u) == 0 && (reinterpret_cast<uintptr_t>(status) & 3u) == 0, SD_ERR_ALIGN,
+                   "sd_optim_step: partials must be 8-byte aligned, the status block 4-byte aligned");
+    }
+    const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
+    const int64_t n4 = n / 4;
+    hipStream_t st = (hipStream_t)stream;
+    if (!decay && !clip && !avg) {                                             // every option off: sd_adam_step's own launch
+        hipLaunchKernelGGL(k_adam, dim3(ew_grid(n4)), dim3(256), 0, st, param, grad, exp_avg, exp_avg_sq, n4, lr, beta1, beta2, eps, (float)bc1,
+                           (float)sqrt(bc2), grad_scale);
+        SD_LAUNCH_CHECK();
+        return 0;
+    }
+    using kernel_t = decltype(&k_optim<true, true, true>);
+    static const kernel_t variants[8] = {nullptr,                      k_optim<true, false, false>, k_optim<false, true, false>,
+                                         k_optim<true, true, false>,   k_optim<false, false, true>, k_optim<true, false, true>,
+                                         k_optim<false, true, true>,   k_optim<true, true, true>};
+    const float decay_mul = (float)(1.0 - (double)lr * (double)weight_decay);
+    hipLaunchKernelGGL(variants[(int)decay | (int)clip << 1 | (int)avg << 2], dim3(ew_grid(n4)), dim3(256), 0, st, param, grad, exp_avg, exp_avg_sq, n4,
+                       lr, beta1, beta2, eps, (float)bc1, (float)sqrt(bc2), grad_scale, decay_mul, decay_mask, max_norm, (const double*)partials,
+                       npartials, ema, ema_decay, (uint32_t*)status);
     SD_LAUNCH_CHECK();
     return 0;
 }

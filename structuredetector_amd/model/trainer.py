@@ -13,6 +13,7 @@ BatchNorm statistics are rank-local by default; `sync_bn=True` (`train --sync_bn
 from __future__ import annotations
 
 import os
+from contextlib import contextmanager
 
 import torch
 import torch.distributed as dist
@@ -88,9 +89,13 @@ class SimExchange:
 
 
 class TrainStep:
-    def __init__(self, net, args, lr=None, betas=(0.9, 0.999), eps=1e-8, process_group=None, exchange=None, sync_bn=False):
+    def __init__(self, net, args, lr=None, betas=(0.9, 0.999), eps=1e-8, process_group=None, exchange=None, sync_bn=False,
+                 weight_decay=0.0, clip_grad_norm=0.0, ema_decay=0.0):
         if net.flat_params is None:
             raise L.SdError("move the Network to the GPU before building TrainStep")
+        if weight_decay < 0 or clip_grad_norm < 0 or not 0 <= ema_decay < 1:
+            raise ValueError(f"weight_decay and clip_grad_norm must be >= 0 and ema_decay in [0, 1), got {weight_decay!r}, {clip_grad_norm!r}, "
+                             f"{ema_decay!r}")
         self.net, self.args = net, args
         self.lr = float(lr if lr is not None else getattr(args, "learning_rate", 1e-3))
         self.betas, self.eps = betas, eps
@@ -124,14 +129,110 @@ class TrainStep:
         if self.sync_bn:
             from .sync_bn import BnStatsExchange
             self.bn_sync = BnStatsExchange.for_network(net, process_group, self.world)
+        # large-batch options of the optimizer (sd_optim_step): all zero = the plain sd_adam_step launch.  The status block
+        # ([0] float norm, [1] float clip coefficient, [2] int32 skipped steps) lives on the device and is never read by the step.
+        self.weight_decay, self.clip_grad_norm, self.ema_decay = float(weight_decay), float(clip_grad_norm), float(ema_decay)
+        self.decay_mask = self.ema = self._partials = None
+        self._status = torch.zeros(4, dtype=torch.int32, device=net.flat_params.device)
+        self._status.view(torch.float32)[1] = 1.0
+        self._configure_optim()
+
+    # ---- AdamW decay / global-norm clipping / weight EMA ----------------------------------------------------------------------
+    def _configure_optim(self):
+        """Buffers of the options that are on: the decay mask, the partials of the norm, the EMA copy (kept if it already exists)."""
+        net = self.net
+        if self.weight_decay > 0 and self.decay_mask is None:
+            self.decay_mask = self.build_decay_mask(net)
+        if self.clip_grad_norm > 0 and self._partials is None:
+            self._partials = torch.empty(L.lib().sd_grad_sumsq_workspace_bytes(net.flat_grads.numel()) // 8, dtype=torch.float64,
+                                         device=net.flat_params.device)
+        if self.ema_decay > 0 and self.ema is None:
+            self.ema = net.flat_params.detach().clone()
+        if self.ema_decay == 0:
+            self.ema = None
+
+    @staticmethod
+    def build_decay_mask(net):
+        """One byte per group of four floats of the flat buffer: 1 inside the slots of the 4-D tensors (convolution weights), 0 for
+        biases and BatchNorm weight / bias.  Slots are 32-byte aligned and a conv weight has a multiple of four elements, so a group
+        never straddles two tensors."""
+        mask = torch.zeros(net.flat_params.numel() // 4, dtype=torch.uint8)
+        for p in net._flat_order:
+            off, n = net._flat_off[id(p)]
+            if p.dim() == 4:
+                assert off % 4 == 0 and n % 4 == 0, "a convolution weight must fill whole 16-byte groups"
+                mask[off // 4:(off + n) // 4] = 1
+        return mask.to(net.flat_params.device)
+
+    @property
+    def plain_adam(self):
+        return self.weight_decay == 0 and self.clip_grad_norm == 0 and self.ema_decay == 0
+
+    @property
+    def grad_norm(self):
+        """Global norm of the last step's (averaged) gradient before clipping, as a device tensor; 0 until a step with clipping ran."""
+        return self._status.view(torch.float32)[0]
+
+    @property
+    def clip_coef(self):
+        """Coefficient the last step multiplied its gradient by (1 = not clipped, 0 = step skipped), as a device tensor."""
+        return self._status.view(torch.float32)[1]
+
+    @property
+    def skipped_steps(self):
+        """Steps skipped so far because the gradient norm was not finite, as a device tensor (int32)."""
+        return self._status[2]
+
+    def ema_decay_at(self, t):
+        """Decay of update number t (1-based): min(ema_decay, (1 + t) / (10 + t)) -- the average follows the weights closely at first."""
+        return min(self.ema_decay, (1.0 + t) / (10.0 + t))
+
+    def _optim_step(self):
+        """sd_grad_sumsq (only with clipping) + sd_optim_step on the step's stream; nothing is read back."""
+        net, lib, st = self.net, L.lib(), L.stream()
+        n = net.flat_params.numel()
+        clip = self.clip_grad_norm > 0
+        if clip:
+            L.check(lib.sd_grad_sumsq(net.flat_grads.data_ptr(), n, self._partials.data_ptr(), self._partials.numel() * 8, st), "sd_grad_sumsq")
+        L.check(lib.sd_optim_step(net.flat_params.data_ptr(), net.flat_grads.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), n,
+                                  self.step_count, self.lr, self.betas[0], self.betas[1], self.eps, 1.0 / self.world, self.weight_decay,
+                                  self.decay_mask.data_ptr() if self.decay_mask is not None else None, self.clip_grad_norm,
+                                  self._partials.data_ptr() if clip else None, self._partials.numel() if clip else 0,
+                                  self.ema.data_ptr() if self.ema is not None else None,
+                                  self.ema_decay_at(self.step_count) if self.ema is not None else 0.0, self._status.data_ptr(), st), "sd_optim_step")
+
+    @contextmanager
+    def ema_weights(self):
+        """Run the body on the averaged weights: the contents of `flat_params` and the EMA buffer are exchanged on entry and exchanged
+        back, bit for bit, on exit (every parameter of the network is a view of `flat_params`).  BatchNorm running statistics are
+        shared, not averaged.  Without an EMA (`ema_decay == 0`) the body runs on the weights as they are."""
+        if self.ema is None:
+            yield
+            return
+        self._swap_ema()
+        try:
+            yield
+        finally:
+            self._swap_ema()
+
+    def _swap_ema(self):
+        with torch.no_grad():
+            held = self.net.flat_params.clone()
+            self.net.flat_params.copy_(self.ema)
+            self.ema.copy_(held)
+        self.net.invalidate_folded()                 # the eval forward caches folded BatchNorm affines and bf16 weight copies
 
     # ---- true resume (SURVEY.md 8f-3): the reference saves weights only (trainer.py:226-237), so a run cannot continue --------
     def state_dict(self):
         """Optimizer state of the flat-buffer Adam: both moment buffers, the step count (bias correction) and the learning rate.
         Tensors are copies on the host; `Network.state_dict()` carries the weights and BatchNorm buffers."""
-        return {"exp_avg": self.exp_avg.detach().cpu().clone(), "exp_avg_sq": self.exp_avg_sq.detach().cpu().clone(),
-                "step_count": int(self.step_count), "lr": float(self.lr), "betas": tuple(self.betas), "eps": float(self.eps),
-                "flat_numel": int(self.net.flat_params.numel())}
+        state = {"exp_avg": self.exp_avg.detach().cpu().clone(), "exp_avg_sq": self.exp_avg_sq.detach().cpu().clone(),
+                 "step_count": int(self.step_count), "lr": float(self.lr), "betas": tuple(self.betas), "eps": float(self.eps),
+                 "flat_numel": int(self.net.flat_params.numel())}
+        if not self.plain_adam:          # (one host read of the skip counter: state_dict is a checkpoint, not the step)
+            state.update(weight_decay=self.weight_decay, clip_grad_norm=self.clip_grad_norm, ema_decay=self.ema_decay,
+                         skipped_steps=int(self.skipped_steps), ema=None if self.ema is None else self.ema.detach().cpu().clone())
+        return state
 
     def load_state_dict(self, state):
         if int(state["flat_numel"]) != self.net.flat_params.numel():
@@ -141,6 +242,13 @@ class TrainStep:
         self.exp_avg_sq.copy_(state["exp_avg_sq"])
         self.step_count, self.lr = int(state["step_count"]), float(state["lr"])
         self.betas, self.eps = tuple(state["betas"]), float(state["eps"])
+        # the options travel with the run; a file written without them (or before they existed) loads with all three off
+        self.weight_decay, self.clip_grad_norm = float(state.get("weight_decay", 0.0)), float(state.get("clip_grad_norm", 0.0))
+        self.ema_decay = float(state.get("ema_decay", 0.0))
+        self._configure_optim()
+        if self.ema is not None:
+            self.ema.copy_(state["ema"] if state.get("ema") is not None else self.net.flat_params)
+        self._status[2] = int(state.get("skipped_steps", 0))
 
     def sync_parameters(self):
         """Identical initial weights on every rank (rank 0's)."""
@@ -148,6 +256,8 @@ class TrainStep:
             dist.broadcast(self.net.flat_params, 0, group=self.pg)
             for b in self.net.buffers():
                 dist.broadcast(b, 0, group=self.pg)
+            if self.ema is not None and self.step_count == 0:       # the average starts from the weights every rank now holds
+                self.ema.copy_(self.net.flat_params)
 
     # Bucket plans: which stages travel together.  A group is launched when its LAST stage completes; the stages of a group are adjacent in
     # the flat buffer (parameters are laid out in registration order: stem, down1 .. down4, FPN, head -- the backward completes them from
@@ -297,9 +407,12 @@ class TrainStep:
         T.pop()
         self.step_count += 1
         T.push("adam")
-        L.check(L.lib().sd_adam_step(net.flat_params.data_ptr(), net.flat_grads.data_ptr(), self.exp_avg.data_ptr(),
-                                     self.exp_avg_sq.data_ptr(), net.flat_params.numel(), self.step_count, self.lr, self.betas[0],
-                                     self.betas[1], self.eps, 1.0 / self.world, L.stream()), "sd_adam_step")
+        if self.plain_adam:
+            L.check(L.lib().sd_adam_step(net.flat_params.data_ptr(), net.flat_grads.data_ptr(), self.exp_avg.data_ptr(),
+                                         self.exp_avg_sq.data_ptr(), net.flat_params.numel(), self.step_count, self.lr, self.betas[0],
+                                         self.betas[1], self.eps, 1.0 / self.world, L.stream()), "sd_adam_step")
+        else:
+            self._optim_step()
         T.pop()
         T.pop()
         self.stats.update(out8[1], out8[2], out8[3])
@@ -308,7 +421,11 @@ class TrainStep:
 
 def train_step_kwargs(args):
     """Keyword arguments `Trainer` builds its `TrainStep` with from the parsed command line."""
-    return dict(lr=args.learning_rate, sync_bn=bool(getattr(args, "sync_bn", False)))
+    kw = dict(lr=args.learning_rate, sync_bn=bool(getattr(args, "sync_bn", False)))
+    for name in ("weight_decay", "clip_grad_norm", "ema_decay"):          # optimizer options: passed when set (TrainStep's defaults are "off")
+        if getattr(args, name, 0.0):
+            kw[name] = float(getattr(args, name))
+    return kw
 
 
 class StepLR:
@@ -480,7 +597,13 @@ class Trainer:
         `Loss.per_image` launch pair (bit-identical to one loss call per image).
         Data-parallel: each rank runs its contiguous shard (utils/distributed.py) with rank 0's BatchNorm buffers; per-image loss rows
         and Evaluators are gathered in rank order, so every rank returns the stats of one pass over the whole set in sample order
-        and keeps the same best-so-far values; afterwards each rank has its own buffers back."""
+        and keeps the same best-so-far values; afterwards each rank has its own buffers back.
+        With `--ema_decay` the pass, the best-model selection and the `model_best_*.pth` files use the averaged weights
+        (`TrainStep.ema_weights()`); the raw weights are back in place when it returns."""
+        with self.step.ema_weights():
+            return self._valid()
+
+    def _valid(self):
         from ..utils.distributed import gather_evaluator, gather_rows
         a = self.args
         world = self.step.world
@@ -545,7 +668,12 @@ class Trainer:
         from pathlib import Path
         state = torch.load(path, map_location="cpu", weights_only=True)
         self.net.load_state_dict(state["model"])
+        asked = (self.step.weight_decay, self.step.clip_grad_norm, self.step.ema_decay)
         self.step.load_state_dict(state["optimizer"])
+        kept = (self.step.weight_decay, self.step.clip_grad_norm, self.step.ema_decay)
+        if kept != asked and self.rank == 0:            # the options belong to the run: the file's win over the command line's, and say so
+            print("resume: optimizer options come from the checkpoint -- weight_decay %g, clip_grad_norm %g, ema_decay %g (the command line "
+                  "asked for %g, %g, %g); a checkpoint written without them continues with all three off" % (kept + asked), flush=True)
         self.scheduler.load_state_dict(state["scheduler"])
         self.start_epoch = int(state["epoch"]) + 1
         for k, v in state["best"].items():
@@ -591,29 +719,41 @@ class Trainer:
 
     def _train(self):
         steps = 0
+        if self.rank == 0 and not self.step.plain_adam:
+            print(f"optimizer: weight decay {self.step.weight_decay:g} (convolution weights), gradient clipping at norm "
+                  f"{self.step.clip_grad_norm:g}, weight EMA {self.step.ema_decay:g} (0 = off)", flush=True)
         if self.rank == 0 and self.step.sync_bn:
             print(f"synchronized BatchNorm: on (statistics over the global batch of {self.step.world} rank(s) x {self.args.batch_size})", flush=True)
         if self.cache is not None:
             self.prefill_cache()
         for epoch in range(self.start_epoch, self.args.epochs):
             self.epoch = epoch
-            per_step = []
+            per_step, norms = [], []
+            clipping = self.step.clip_grad_norm > 0
             for images, targets in self.batches():
                 per_step.append(self.step(images, targets).clone())    # (total, hm, offset, embedding) on the device: no host sync in the loop
+                if clipping:
+                    norms.append(self.step.grad_norm.clone())          # the status block's norm of this step, read with the losses below
                 steps += 1
                 if self.args.steps and steps >= self.args.steps:
                     break
             n = len(per_step)
             rows = torch.stack(per_step).tolist() if n else []         # one host sync per epoch
+            norms = torch.stack(norms).tolist() if norms else []
+            skipped = int(self.step.skipped_steps) if clipping else 0
             mean = [sum(r[k] for r in rows) / max(n, 1) for k in range(4)]
             if self.rank == 0:
                 # trainer.py:126-133: "Loss/Train" per optimizer step at global_step (+= batch_size per step), "Learning rate" per epoch;
                 # the reference's writer forces a device sync per step -- the same scalars are written here from the epoch's one copy
                 writer = self.scalar_writer()
-                for r in rows:
+                for k, r in enumerate(rows):
                     writer.add_scalars("Loss/Train", dict(hm_loss=r[1], offset_loss=r[2], embedding_loss=r[3]), self.global_step)
+                    if clipping:
+                        writer.add_scalar("Gradient norm", norms[k], self.global_step)
                     self.global_step += self.args.batch_size
                 writer.add_scalar("Learning rate", self.step.lr, self.global_step)
+                if clipping:
+                    writer.add_scalar("Skipped steps", skipped, self.global_step)
                 writer.flush()
                 print(f"epoch {epoch}: total {mean[0]:.5f} hm {mean[1]:.5f} offset {mean[2]:.5f} embedding {mean[3]:.5f} "
                       f"lr {self.step.lr:g} ({n} steps)", flush=True)
@@ -624,5 +764,7 @@ class Trainer:
             if self.rank == 0:                                         # state at the END of the epoch: --resume continues with epoch + 1
                 self.save_dir.mkdir(parents=True, exist_ok=True)
                 self.save_resume(self.save_dir / "resume.pth")
+                if self.step.ema is not None:                          # model_best_* hold the averaged weights: the raw ones go here
+                    self.net.save(self.save_dir / "last_model.pth")
             if self.args.steps and steps >= self.args.steps:
                 break

@@ -60,6 +60,12 @@ _FLAGS = [
                           "global batch (one fp64 all-reduce per BatchNorm and direction).")),
     (("--cache_images",), dict(type=float, default=0.0, help="GB of device memory for decoded training / validation images, kept across "
                                "epochs (decoded once before epoch 1; images beyond the budget are decoded every epoch; 0 = off).")),
+    (("--weight_decay",), dict(type=float, default=0.0, help="Decoupled weight decay (torch.optim.AdamW) on the convolution weights; biases "
+                               "and BatchNorm parameters are not decayed (0 = off: plain Adam).")),
+    (("--clip_grad_norm",), dict(type=float, default=0.0, help="Clip the global norm of the (averaged) gradient to this value "
+                                 "(torch.nn.utils.clip_grad_norm_); a step whose gradient norm is not finite is skipped -- this guard against inf / nan gradients (--amp) exists only with clipping on (0 = off).")),
+    (("--ema_decay",), dict(type=float, default=0.0, help="Exponential moving average of the weights with this decay, warmed up as "
+                            "min(decay, (1 + t) / (10 + t)); validation and model_best_*.pth use the average (0 = off).")),
 ]
 
 _POSITIVE = ["in_channels", "fpn_depth", "batch_size", "epochs", "learning_rate", "down_ratio", "max_objects", "max_parts"]
@@ -88,6 +94,9 @@ def finalize(args):
         assert 0 <= getattr(args, k) <= 1, f"'{k}' should be in [0.0, 1.0]"
     assert 0 < args.sigma_gauss <= 1, "'sigma_gauss' should be in ]0.0, 1.0]"
     assert getattr(args, "cache_images", 0) >= 0, "'cache_images' should be greater than or equal to 0"
+    for k in ("weight_decay", "clip_grad_norm", "ema_decay"):
+        assert getattr(args, k, 0.0) >= 0, f"'{k}' should be greater than or equal to 0"
+    assert getattr(args, "ema_decay", 0.0) < 1, "'ema_decay' should be less than 1"
 
     args.lr_step = int(args.epochs / args.lr_step) if args.lr_step != 0 else args.epochs
     for k in ("train_dir", "valid_dir", "pretrained_model"):

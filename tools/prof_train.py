@@ -12,9 +12,11 @@ from structuredetector_amd.model import Network
 from structuredetector_amd.model.trainer import TrainStep
 dev = torch.device("cuda")
 args = make_args(dev)
-args.use_amp = len(sys.argv) > 2 and sys.argv[2] == "amp"      # prof_train.py <steps> amp: the mixed-precision step
+args.use_amp = "amp" in sys.argv[2:]                            # prof_train.py <steps> amp: the mixed-precision step
+# prof_train.py <steps> [amp] options: AdamW decay + global-norm clipping + weight EMA (k_grad_sumsq + k_optim instead of k_adam)
+options = dict(weight_decay=0.05, clip_grad_norm=1.0, ema_decay=0.999) if "options" in sys.argv[2:] else {}
 net = Network(args, pretrained=False).to(dev).train()
-step = TrainStep(net, args)
+step = TrainStep(net, args, **options)
 enc = Encode(args)
 B, img, STEPS = 64, 512, int(sys.argv[1]) if len(sys.argv) > 1 else 4
 x = torch.randn(B, 3, img, img, device=dev)
