@@ -180,6 +180,27 @@ int sd_decode_group(const float* a_score, const int64_t* a_ind, const float* a_c
                     int B, int h, int w, int K, int P, float conf, float dist_px,
                     void* packed, sd_stream_t stream);
 
+/* ---- flip test-time augmentation (no reference counterpart: the reference decodes one forward of the unflipped image) ----
+ * `view_flips_host` is a HOST array of V bytes, one per view: bit 0 = horizontal, bit 1 = vertical flip (the encoding of
+ * sd_preprocess_images' `flips`).  V is 2 or 4 and view 0 must be the unflipped image (byte 0); anything else is SD_ERR_INVALID.
+ * Both functions are one launch each, use no workspace and no atomics, and are deterministic.
+ *
+ * sd_tta_views: x (B,3,H,W) fp32 NCHW contiguous -> out (V*B,3,H,W); view v of image b is image v*B + b of `out`:
+ *   out[v*B + b, c, y, x] = x[b, c, fy(y), fx(x)],  fy(y) = H-1-y if bit 1 of view v else y,  fx(x) = W-1-x if bit 0 else x.
+ *   The input is read once; every view -- mirrored rows too -- is written as contiguous spans.
+ *
+ * sd_tta_merge_nms: `hm` = the heatmap logits of a head output of V*B images ordered as above, a strided (sb, sc) channel-slice view
+ *   like every other map argument; out (B,C,h,w) contiguous.  For every pixel
+ *       m(y, x) = (s_0 + s_1 [+ s_2 + s_3]) * (1/V),   s_v = clamped_sigmoid(hm[v*B + b, c, fy_v(y), fx_v(x)])
+ *   -- the device function behind sd_clamped_sigmoid, the terms added in view order v = 0 .. V-1 in fp32, each add and the final multiply
+ *   rounded separately (no FMA contraction) -- and out = m where m equals the maximum of m over the 5x5 window, else 0; padding (-inf)
+ *   and ties exactly as sd_nms5.  Equal, bit for bit, to sd_nms5 of that sum formed from sd_clamped_sigmoid outputs.  Every view's logits
+ *   are read once and the output is written once; 16-byte loads when w % 4 == 0 and planes / strides are 16-byte aligned, 4-byte loads
+ *   otherwise. */
+int sd_tta_views(const float* x, float* out, int B, int H, int W, int V, const unsigned char* view_flips_host, sd_stream_t stream);
+int sd_tta_merge_nms(const float* hm, int64_t sb, int64_t sc, float* out, int B, int C, int h, int w, int V,
+                     const unsigned char* view_flips_host, sd_stream_t stream);
+
 /* ---- target rendering: src/sdnet/data/transforms.py:130-205 (Encode) ---------------------- */
 
 /* Heatmaps of a batch (transforms.py:143,160-161,173-174; utils.py:418-419): for every pixel of

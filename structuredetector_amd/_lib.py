@@ -71,6 +71,9 @@ _SIGNATURES = {
     "sd_decode_fused_workspace_bytes": (c_size, [c_int] * 7),
     "sd_decode_fused": (c_int, _MAP * 4 + [c_int] * 7 + [c_float, c_float, c_int, c_vp, c_vp, c_size, c_vp, c_size, c_vp]),
     "sd_decode_group": (c_int, [c_vp] * 6 + _MAP * 2 + [c_int] * 5 + [c_float, c_float, c_vp, c_vp]),
+    # flip test-time augmentation: ..., V, view_flips (HOST array of V bytes), stream
+    "sd_tta_views": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]),
+    "sd_tta_merge_nms": (c_int, _MAP + [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp]),
     "sd_preprocess_workspace_bytes": (c_size, [c_int] * 4),
     "sd_preprocess_images": (c_int, [c_vp] + [c_int] * 5 + [c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp, C.POINTER(c_float), C.POINTER(c_float),
                                                 c_vp, c_vp, c_size, c_vp]),

@@ -40,6 +40,9 @@ def _evaluate(argv):
     if args.pretrained_model:
         net.load_state_dict(torch.load(args.pretrained_model, map_location="cpu", weights_only=True))
     net = net.eval().to(args.device)
+    if getattr(args, "tta", "none") != "none":      # --tta: the mirrored views, one forward over all of them and the merge sit inside the per-batch step
+        from ..model.tta import with_tta
+        net, decoder = with_tta(net, decoder, args)
     if args.synthetic:
         from ..data.synthetic import synthetic_samples
         lo, hi = shard_range(args.synthetic, rank, world)

@@ -1,0 +1,247 @@
+// Flip test-time augmentation for gfx950: the mirrored input batch (sd_tta_views) and the merge of the V head outputs into ONE
+// suppressed probability map (sd_tta_merge_nms).  No reference counterpart (the reference has no test-time augmentation).
+// The merged value decides which pixels survive the NMS and is compared bit for bit with the library's own primitives
+// (sd_clamped_sigmoid, sd_nms5): separately rounded adds and one multiply -- floating-point contraction is OFF in this file.
+#pragma clang fp contract(off)
+#include "sd_common.h"
+
+namespace sd {
+
+struct ViewFlips {
+    unsigned char f[4];          // bit 0 = horizontal, bit 1 = vertical (the encoding of sd_preprocess_images' `flips`)
+};
+
+// ---------------------------------------------------------------------------------------------
+// Views.  One thread per group of four input pixels of a row (VEC) or per pixel: the input is read ONCE, as contiguous spans, and every
+// view is written from registers.  A mirrored row leaves as one contiguous span too -- lane i of a wave writes the group W4-1-i with
+// its four components swapped, so a wave's 1 KiB of a row stays 1 KiB of the mirrored row, only in descending lane order.
+// ---------------------------------------------------------------------------------------------
+template <int V, bool VEC>
+__global__ __launch_bounds__(256) void k_tta_views(const float* __restrict__ x, float* __restrict__ out, int64_t planes, int H, int W,
+                                                   ViewFlips vf) {
+    const int wg = VEC ? W >> 2 : W;                                   // groups per row
+    const int64_t n = planes * H * wg;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int64_t row = i / wg;
+    const int g = (int)(i - row * wg);
+    const int64_t plane = row / H;
+    const int y = (int)(row - plane * H);
+    if (VEC) {
+        const float4 v = reinterpret_cast<const float4*>(x)[i];
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            const bool hf = vf.f[k] & 1;
+            const int dy = (vf.f[k] & 2) ? H - 1 - y : y;
+            const int dg = hf ? wg - 1 - g : g;
+            reinterpret_cast<float4*>(out)[(((int64_t)k * planes + plane) * H + dy) * wg + dg] =
+                make_float4(hf ? v.w : v.x, hf ? v.z : v.y, hf ? v.y : v.z, hf ? v.x : v.w);
+        }
+    } else {
+        const float v = x[i];
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            const int dy = (vf.f[k] & 2) ? H - 1 - y : y;
+            const int dg = (vf.f[k] & 1) ? W - 1 - g : g;
+            out[(((int64_t)k * planes + plane) * H + dy) * W + dg] = v;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Merge + NMS.  One 256-thread block per 64x16 output tile of one merged map (the tile of sd_nms5).  The tile and its 2-pixel halo are
+// staged in LDS as m = (s_0 + s_1 [+ s_2 + s_3]) * (1/V), s_v = clamped_sigmoid(view v's logit at the mirrored coordinate); the 5-max
+// is separable (row pass into a second LDS array, column pass in registers); out = (m == max5x5(m)) ? m : 0 with -inf padding.
+// Every view's logits are read once (+ the halo re-reads, served by L2), the output is written once.
+//   VEC: w % 4 == 0 and 16-byte aligned planes.  The staged span of a row is widened to the enclosing aligned groups
+//        [tx0-4, tx0+68): 18 16-byte loads per row and view; a mirrored view reads the group w-4-x and swaps its components,
+//        so its span is contiguous as well.  A group lies entirely inside or entirely outside the map.
+//   else: one 4-byte load per staged cell, [tx0-2, tx0+66).
+// LDS column of map column x: x - tx0 + OFF (OFF = 4) in both variants.
+// ---------------------------------------------------------------------------------------------
+constexpr int TW = 64, TH = 16, HALO = 2, OFF = 4;
+constexpr int LH = TH + 2 * HALO;        // 20 staged rows
+constexpr int LWV = TW + 2 * OFF;        // 72 staged columns (VEC); the scalar variant fills columns OFF-HALO .. OFF+TW+HALO-1
+constexpr int LWS = TW + 2 * HALO;       // 68 cells per row loaded by the scalar variant
+
+template <int V, bool VEC>
+__global__ __launch_bounds__(256) void k_tta_merge_nms(const float* __restrict__ hm, int64_t sb, int64_t sc, int B, int C, int h, int w,
+                                                       int tiles_x, ViewFlips vf, float* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) float S[LH][LWV];
+    __shared__ __attribute__((aligned(16))) float Hm[LH][TW];
+    constexpr float inv = 1.0f / V;                                    // 0.5, 0.25: exact
+    const int tid = threadIdx.x;
+    const int b = blockIdx.z, c = blockIdx.y;
+    const int tx0 = (blockIdx.x % tiles_x) * TW;
+    const int ty0 = (blockIdx.x / tiles_x) * TH;
+    const float* plane[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) plane[v] = hm + ((int64_t)v * B + b) * sb + (int64_t)c * sc;
+
+    // all loads of the thread are issued before the first use; cells outside the map read element 0 and become -inf
+    if (VEC) {
+        constexpr int GR = LWV / 4, NG = LH * GR;                      // 18 groups per row, 360 per tile
+        constexpr int NLD = (NG + 255) / 256;
+        float4 ld[NLD][V];
+#pragma unroll
+        for (int j = 0; j < NLD; ++j) {
+            const int i = tid + j * 256;
+            const int r = i / GR, q = i - r * GR;
+            const int y = ty0 + r - HALO, x = tx0 - OFF + 4 * q;
+            const bool ok = i < NG && y >= 0 && y < h && x >= 0 && x < w;
+#pragma unroll
+            for (int v = 0; v < V; ++v) {
+                const int sy = (vf.f[v] & 2) ? h - 1 - y : y;
+                const int sx = (vf.f[v] & 1) ? w - 4 - x : x;
+                ld[j][v] = *reinterpret_cast<const float4*>(plane[v] + (ok ? (int64_t)sy * w + sx : 0));
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < NLD; ++j) {
+            const int i = tid + j * 256;
+            const int r = i / GR, q = i - r * GR;
+            const int y = ty0 + r - HALO, x = tx0 - OFF + 4 * q;
+            const bool ok = y >= 0 && y < h && x >= 0 && x < w;
+            float4 m;
+#pragma unroll
+            for (int v = 0; v < V; ++v) {
+                const float4 t = ld[j][v];
+                const bool hf = vf.f[v] & 1;
+                const float4 s = make_float4(clamped_sigmoid(hf ? t.w : t.x), clamped_sigmoid(hf ? t.z : t.y),
+                                             clamped_sigmoid(hf ? t.y : t.z), clamped_sigmoid(hf ? t.x : t.w));
+                if (v == 0) m = s;
+                else { m.x = m.x + s.x; m.y = m.y + s.y; m.z = m.z + s.z; m.w = m.w + s.w; }
+            }
+            m.x = m.x * inv; m.y = m.y * inv; m.z = m.z * inv; m.w = m.w * inv;
+            if (!ok) m = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+            if (i < NG) *reinterpret_cast<float4*>(&S[r][4 * q]) = m;
+        }
+    } else {
+        constexpr int NC = LH * LWS;
+        constexpr int NLD = (NC + 255) / 256;
+        float ld[NLD][V];
+#pragma unroll
+        for (int j = 0; j < NLD; ++j) {
+            const int i = tid + j * 256;
+            const int r = i / LWS, cc = i - r * LWS;
+            const int y = ty0 + r - HALO, x = tx0 + cc - HALO;
+            const bool ok = i < NC && y >= 0 && y < h && x >= 0 && x < w;
+#pragma unroll
+            for (int v = 0; v < V; ++v) {
+                const int sy = (vf.f[v] & 2) ? h - 1 - y : y;
+                const int sx = (vf.f[v] & 1) ? w - 1 - x : x;
+                ld[j][v] = plane[v][ok ? (int64_t)sy * w + sx : 0];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < NLD; ++j) {
+            const int i = tid + j * 256;
+            const int r = i / LWS, cc = i - r * LWS;
+            const int y = ty0 + r - HALO, x = tx0 + cc - HALO;
+            const bool ok = y >= 0 && y < h && x >= 0 && x < w;
+            float m = clamped_sigmoid(ld[j][0]);
+#pragma unroll
+            for (int v = 1; v < V; ++v) m = m + clamped_sigmoid(ld[j][v]);
+            m = m * inv;
+            if (i < NC) S[r][cc + OFF - HALO] = ok ? m : -INFINITY;
+        }
+    }
+    __syncthreads();
+    // row pass: Hm[r][cc] = max over map columns tx0+cc-2 .. tx0+cc+2
+    for (int i = tid; i < LH * TW; i += 256) {
+        const int r = i / TW, cc = i - r * TW;
+        const float* s = &S[r][cc + OFF - HALO];
+        Hm[r][cc] = fmaxf(fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3])), s[4]);
+    }
+    __syncthreads();
+    // column pass + output: four adjacent pixels of one row per thread
+    const int r = tid / (TW / 4), c4 = (tid - r * (TW / 4)) * 4;
+    const int y = ty0 + r, x = tx0 + c4;
+    if (y >= h) return;
+    float mx[4], val[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float m = fmaxf(fmaxf(Hm[r][c4 + k], Hm[r + 1][c4 + k]), fmaxf(Hm[r + 2][c4 + k], Hm[r + 3][c4 + k]));
+        mx[k] = fmaxf(m, Hm[r + 4][c4 + k]);
+        const float v = S[r + HALO][c4 + k + OFF];
+        val[k] = (v == mx[k]) ? v : 0.0f;
+    }
+    float* dst = out + (((int64_t)b * C + c) * h + y) * w + x;
+    if (VEC) {
+        if (x < w) *reinterpret_cast<float4*>(dst) = make_float4(val[0], val[1], val[2], val[3]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (x + k < w) dst[k] = val[k];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------
+static int check_views(const char* fn, int V, const unsigned char* view_flips, ViewFlips* vf) {
+    SD_REQUIRE(V == 2 || V == 4, SD_ERR_INVALID, "%s: V=%d views (2 or 4 are supported)", fn, V);
+    SD_REQUIRE(view_flips != nullptr, SD_ERR_INVALID, "%s: null view_flips", fn);
+    *vf = ViewFlips{{0, 0, 0, 0}};
+    for (int v = 0; v < V; ++v) {
+        SD_REQUIRE(view_flips[v] < 4, SD_ERR_INVALID, "%s: view_flips[%d]=%d (bit 0 = horizontal, bit 1 = vertical)", fn, v, (int)view_flips[v]);
+        vf->f[v] = view_flips[v];
+    }
+    SD_REQUIRE(view_flips[0] == 0, SD_ERR_INVALID, "%s: view 0 must be the unflipped image (view_flips[0]=%d)", fn, (int)view_flips[0]);
+    return 0;
+}
+
+}  // namespace sd
+
+using namespace sd;
+
+extern "C" {
+
+int sd_tta_views(const float* x, float* out, int B, int H, int W, int V, const unsigned char* view_flips, sd_stream_t stream) {
+    SD_REQUIRE(x != nullptr && out != nullptr, SD_ERR_INVALID, "sd_tta_views: null pointer");
+    SD_REQUIRE(B > 0 && H > 0 && W > 0, SD_ERR_INVALID, "sd_tta_views: bad shape (%d,3,%d,%d)", B, H, W);
+    ViewFlips vf;
+    if (int e = check_views("sd_tta_views", V, view_flips, &vf)) return e;
+    const int64_t planes = (int64_t)B * 3;
+    const bool vec = (W % 4 == 0) && aligned16(x) && aligned16(out);
+    const int64_t blocks = (planes * H * (vec ? W / 4 : W) + 255) / 256;
+    SD_REQUIRE(blocks < (1ll << 31), SD_ERR_INVALID, "sd_tta_views: %lld blocks exceed the grid", (long long)blocks);
+    const dim3 grid((unsigned)blocks), block(256);
+    const hipStream_t st = (hipStream_t)stream;
+    if (V == 2) {
+        if (vec) hipLaunchKernelGGL((k_tta_views<2, true>), grid, block, 0, st, x, out, planes, H, W, vf);
+        else     hipLaunchKernelGGL((k_tta_views<2, false>), grid, block, 0, st, x, out, planes, H, W, vf);
+    } else {
+        if (vec) hipLaunchKernelGGL((k_tta_views<4, true>), grid, block, 0, st, x, out, planes, H, W, vf);
+        else     hipLaunchKernelGGL((k_tta_views<4, false>), grid, block, 0, st, x, out, planes, H, W, vf);
+    }
+    SD_LAUNCH_CHECK();
+    return 0;
+}
+
+int sd_tta_merge_nms(const float* hm, int64_t sb, int64_t sc, float* out, int B, int C, int h, int w, int V,
+                     const unsigned char* view_flips, sd_stream_t stream) {
+    SD_REQUIRE(hm != nullptr && out != nullptr, SD_ERR_INVALID, "sd_tta_merge_nms: null pointer");
+    SD_REQUIRE(B > 0 && C > 0 && h > 0 && w > 0, SD_ERR_INVALID, "sd_tta_merge_nms: bad shape (%d,%d,%d,%d)", B, C, h, w);
+    ViewFlips vf;
+    if (int e = check_views("sd_tta_merge_nms", V, view_flips, &vf)) return e;
+    SD_REQUIRE((int64_t)C * h * w < (1ll << 31), SD_ERR_INVALID, "sd_tta_merge_nms: C*h*w must be < 2^31");
+    SD_REQUIRE(sc >= (int64_t)h * w && sb >= (int64_t)h * w, SD_ERR_INVALID, "sd_tta_merge_nms: bad strides sb=%lld sc=%lld",
+               (long long)sb, (long long)sc);
+    SD_REQUIRE(C <= 65535 && B <= 65535, SD_ERR_INVALID, "sd_tta_merge_nms: B=%d, C=%d exceed the grid (65535)", B, C);
+    const int tiles_x = cdiv(w, TW), tiles_y = cdiv(h, TH);
+    const bool vec = (w % 4 == 0) && aligned16(hm) && aligned16(out) && sb % 4 == 0 && sc % 4 == 0;
+    const dim3 grid(tiles_x * tiles_y, C, B), block(256);
+    const hipStream_t st = (hipStream_t)stream;
+    if (V == 2) {
+        if (vec) hipLaunchKernelGGL((k_tta_merge_nms<2, true>), grid, block, 0, st, hm, sb, sc, B, C, h, w, tiles_x, vf, out);
+        else     hipLaunchKernelGGL((k_tta_merge_nms<2, false>), grid, block, 0, st, hm, sb, sc, B, C, h, w, tiles_x, vf, out);
+    } else {
+        if (vec) hipLaunchKernelGGL((k_tta_merge_nms<4, true>), grid, block, 0, st, hm, sb, sc, B, C, h, w, tiles_x, vf, out);
+        else     hipLaunchKernelGGL((k_tta_merge_nms<4, false>), grid, block, 0, st, hm, sb, sc, B, C, h, w, tiles_x, vf, out);
+    }
+    SD_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // extern "C"

@@ -375,3 +375,17 @@ class FusedOutputDecoder(Decoder):
 
     def _call_low_latency(self, outputs, conf_thresh, dist_thresh):
         return None                                   # (the one-launch kernel starts from logits; this class starts from NMS'ed maps)
+
+    def __call__(self, outputs, conf_thresh=None, dist_thresh=None, return_metadata=False, metadata_fields=None):
+        # the inherited full-metadata dict applies the sigmoid to `anchor_hm` / `part_hm`; a TtaOutput holds probabilities already
+        if return_metadata and isinstance(outputs, TtaOutput) and not (
+                metadata_fields is not None and set(metadata_fields) <= {"annotation", "raw_parts"}):
+            raise L.SdError("FusedOutputDecoder: the full metadata of a test-time-augmentation output is not defined (its heatmaps are "
+                            "merged probabilities, not logits); ask for metadata_fields within ('annotation', 'raw_parts')")
+        return super().__call__(outputs, conf_thresh, dist_thresh, return_metadata, metadata_fields)
+
+
+class TtaOutput(dict):
+    """The four-key output of `model/tta.FlipTta`: `anchor_hm` / `part_hm` are merged, already suppressed PROBABILITY maps (the mean
+    over the mirrored views, after the 5x5 NMS), `offsets` / `embeddings` the unflipped view's.  A plain dict otherwise; the type is
+    the mark `FusedOutputDecoder` checks before it hands out metadata."""

@@ -93,6 +93,10 @@ class Predictor(torch.nn.Module):
         self.model.load_state_dict(torch.load(args.pretrained_model, map_location="cpu", weights_only=True), strict=True)
         self.model.eval().to(args.device)
         self.decoder = Decoder(args)
+        self.tta = None
+        if getattr(args, "tta", "none") != "none":                                # --tta: mirrored views + merged heatmaps (model/tta.py)
+            from .tta import FlipTta, tta_decoder
+            self.tta, self.decoder = FlipTta(self.model, args, args.tta), tta_decoder(args)
 
     def forward(self, image):
         import numpy as np
@@ -101,4 +105,4 @@ class Predictor(torch.nn.Module):
         arr = torch.from_numpy(np.asarray(image.convert("RGB"), np.uint8).copy())[None].to(self.args.device)
         with torch.no_grad():
             x = preprocess_images(arr, (self.args.width, self.args.height))
-            return self.decoder(self.model(x))[0]
+            return self.decoder((self.tta or self.model)(x))[0]

@@ -66,6 +66,10 @@ _FLAGS = [
                                  "(torch.nn.utils.clip_grad_norm_); a step whose gradient norm is not finite is skipped -- this guard against inf / nan gradients (--amp) exists only with clipping on (0 = off).")),
     (("--ema_decay",), dict(type=float, default=0.0, help="Exponential moving average of the weights with this decay, warmed up as "
                             "min(decay, (1 + t) / (10 + t)); validation and model_best_*.pth use the average (0 = off).")),
+    (("--tta",), dict(type=str, default="none", choices=["none", "hflip", "vflip", "hvflip"], help="Flip test-time augmentation in evaluate / "
+                      "detect / Predictor: the network also runs on the mirrored image(s) (2 views for hflip and vflip, 4 for hvflip: the "
+                      "forward sees that many times --eval_batch images), the heatmaps are averaged and decoded once. Not consulted by "
+                      "train: its validation pass computes the loss from the plain head output.")),
 ]
 
 _POSITIVE = ["in_channels", "fpn_depth", "batch_size", "epochs", "learning_rate", "down_ratio", "max_objects", "max_parts"]
