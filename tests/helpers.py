@@ -165,3 +165,452 @@ def oracle_conv_trace(ref, x, dhead_of, device, skip=()):
         for h in handles:
             h.remove()
     return head.detach(), trace
+
+
+# ---------------------------------------------------------------------------------------------
+# bit-exact conv / head tests (tests/test_exact_cases_cpu.py, tests/test_gpu_exact.py)
+#
+# Integer operands make every product and every partial sum of a conv an integer.  While the sum of the ABSOLUTE products stays below
+# 2^24, every partial sum -- in any order, with or without FMA, for any tile, split, ring or reduce pass -- is an integer below 2^24 and
+# therefore exact in fp32: an fp32 kernel must reproduce the fp64 reference bit for bit, a bf16 kernel its nearest-even rounding.
+# Epilogues add half-integer shifts and scales of 0.5 / 1 / 2: multiples of 0.5 are exact in fp32 below 2^23, the limit used there.
+# ---------------------------------------------------------------------------------------------
+EXACT_LIMIT = float(2 ** 24)
+EXACT_LIMIT_HALVES = float(2 ** 23)
+MAX_REFERENCE_MACS = 2 ** 31
+
+# library defaults of the thread-local dispatch options the cases change (include/sdnet_hip.h, sd_set_option)
+OPTION_DEFAULTS = {"conv_patch_min_tiles": 512, "conv_pp_min_tiles": 200, "conv_rows64_min_units": 192, "conv_rows_f32_min_units": 192,
+                   "conv_fwd_split_k": 1, "conv_patch_narrow": 2, "conv_pp_strips": 1, "conv_rows16": 1, "igemm_big_bf16": 0,
+                   "conv1x1_stream_min_pixels": 32 * 2048, "conv_patch_bn64": 0, "wgrad_f32_ring": 2, "wgrad_bf16_ring": 5}
+
+
+class dispatch_options:
+    """with dispatch_options(lib, {...}): sets the thread-local options and restores the defaults on the way out."""
+
+    def __init__(self, lib, opts):
+        self.lib, self.opts = lib, dict(opts)
+
+    def __enter__(self):
+        for k, v in self.opts.items():
+            assert self.lib.sd_set_option(k.encode(), int(v)) == 0, k
+        return self
+
+    def __exit__(self, *exc):
+        for k in self.opts:
+            assert self.lib.sd_set_option(k.encode(), OPTION_DEFAULTS[k]) == 0, k
+        return False
+
+
+def conv_desc(L, geom):
+    B, H, W, cin, cout, k, stride, pad = geom
+    d = L.ConvDesc()
+    d.B, d.Hi, d.Wi, d.Cin, d.Cout, d.R, d.S, d.stride, d.pad = B, H, W, cin, cout, k, k, stride, pad
+    d.Ho, d.Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    return d
+
+
+def conv_macs(geom):
+    B, H, W, cin, cout, k, stride, pad = geom
+    return B * ((H + 2 * pad - k) // stride + 1) * ((W + 2 * pad - k) // stride + 1) * cin * cout * k * k
+
+
+# (geometry (B, H, W, Cin, Cout, k, stride, pad), options, {sd_conv2d_kernel_name pass: kernel the case must reach}).  Passes 0 / 1 / 2 =
+# fp32 forward / data-gradient / weight gradient, 16 / 17 = bf16 forward / data-gradient.  The geometries are those of the tolerance tests
+# (CONV_CASES, PATCH_CASES, the row-stream, two-group and 1x1-stream cases of tests/test_gpu_network.py and tests/test_gpu_amp.py) without
+# the ones whose reference costs more than 2^31 multiply-adds, kernels behind size thresholds reached through the options.
+# k_conv_igemm_big has no threshold option: its plan needs 512 tiles of 256 x 128 outputs and a reduction of at least 512, i.e. 2^33
+# multiply-adds for the unit-stride form -- the one 1x1 case (a plain GEMM for the reference) that reaches it is the exception to the limit.
+BIG_TILE_CASE = (8, 64, 64, 512, 512, 1, 1, 0)
+EXACT_CONV_CASES = [
+    ((2, 16, 24, 64, 64, 3, 1, 1), {}, {0: 'k_conv_igemm<64, 0, false>', 1: 'k_conv_igemm<64, 0, false>', 2: 'k_conv_wgrad<64, 64>', 16: 'k_conv_igemm<64, 0, true>', 17: 'k_conv_igemm<64, 0, true>'}),
+    ((1, 20, 12, 64, 128, 3, 2, 1), {}, {0: 'k_conv_igemm<128, 0, false>', 1: 'k_conv_igemm<64, 3, false>', 2: 'k_conv_wgrad<128, 64>', 16: 'k_conv_igemm<128, 0, true>', 17: 'k_conv_igemm<64, 3, true>'}),
+    ((3, 8, 8, 128, 128, 3, 1, 1), {}, {0: 'k_conv_igemm<128, 0, false>', 1: 'k_conv_igemm<128, 0, false>', 2: 'k_conv_wgrad<128, 128>', 16: 'k_conv_igemm<128, 0, true>', 17: 'k_conv_igemm<128, 0, true>'}),
+    ((2, 12, 12, 64, 128, 1, 2, 0), {}, {0: 'k_conv_igemm<128, 0, false>', 1: 'k_conv_igemm<64, 3, false>', 2: 'k_conv_wgrad<128, 64>', 16: 'k_conv_igemm<128, 0, true>', 17: 'k_conv_igemm<64, 3, true>'}),
+    ((1, 6, 10, 512, 128, 1, 1, 0), {}, {0: 'k_conv_igemm<128, 0, false>', 1: 'k_conv_igemm<128, 0, false>', 2: 'k_conv_wgrad<128, 128>', 16: 'k_conv_igemm<128, 0, true>', 17: 'k_conv_igemm<128, 0, true>'}),
+    ((2, 9, 7, 256, 256, 3, 1, 1), {}, {0: 'k_conv_igemm<128, 0, false>', 1: 'k_conv_igemm<128, 0, false>', 2: 'k_conv_wgrad<128, 128>', 16: 'k_conv_igemm<128, 0, true>', 17: 'k_conv_igemm<128, 0, true>'}),
+    ((2, 32, 32, 64, 128, 3, 2, 1), {}, {0: 'k_conv_igemm<128, 0, false>', 1: 'k_conv_igemm<64, 2, false>', 2: 'k_conv_wgrad<128, 64>', 16: 'k_conv_igemm<128, 0, true>', 17: 'k_conv_igemm<64, 2, true>'}),
+    ((2, 32, 32, 64, 128, 1, 2, 0), {}, {0: 'k_conv_igemm<128, 0, false>', 1: 'k_conv_igemm<64, 2, false>', 2: 'k_conv_wgrad<128, 64>', 16: 'k_conv_igemm<128, 0, true>', 17: 'k_conv_igemm<64, 2, true>'}),
+    ((2, 16, 32, 64, 64, 3, 1, 1), {}, {0: 'k_conv_igemm<64, 0, false>', 1: 'k_conv_igemm<64, 0, false>', 2: 'k_wgrad3x3_ring2', 16: 'k_conv_igemm<64, 0, true>', 17: 'k_conv_igemm<64, 0, true>'}),
+    ((1, 7, 96, 64, 64, 3, 1, 1), {}, {0: 'k_conv_igemm<64, 0, false>', 1: 'k_conv_igemm<64, 0, false>', 2: 'k_wgrad3x3_ring2', 16: 'k_conv_igemm<64, 0, true>', 17: 'k_conv_igemm<64, 0, true>'}),
+    ((3, 40, 64, 64, 64, 3, 1, 1), {}, {0: 'k_conv_igemm<64, 0, false>', 1: 'k_conv_igemm<64, 0, false>', 2: 'k_wgrad3x3_ring2', 16: 'k_conv_igemm<64, 0, true>', 17: 'k_conv_igemm<64, 0, true>'}),
+    ((2, 8, 32, 128, 128, 3, 1, 1), {}, {0: 'k_conv_igemm<128, 0, false>', 1: 'k_conv_igemm<128, 0, false>', 2: 'k_wgrad3x3_ring2', 16: 'k_conv_igemm<128, 0, true>', 17: 'k_conv_igemm<128, 0, true>'}),
+    ((1, 5, 64, 192, 64, 3, 1, 1), {}, {0: 'k_conv_igemm<64, 0, false>', 1: 'k_conv_igemm<64, 0, false>', 2: 'k_wgrad3x3_ring2', 16: 'k_conv_igemm<64, 0, true>', 17: 'k_conv_igemm<64, 0, true>'}),
+    ((3, 16, 16, 128, 64, 3, 1, 1), {}, {0: 'k_conv_igemm<64, 0, false>', 1: 'k_conv_igemm<128, 0, false>', 2: 'k_wgrad3x3<16>', 16: 'k_conv_igemm<64, 0, true>', 17: 'k_conv_igemm<128, 0, true>'}),
+    ((2, 6, 16, 64, 64, 3, 1, 1), {}, {0: 'k_conv_igemm<64, 0, false>', 1: 'k_conv_igemm<64, 0, false>', 2: 'k_wgrad3x3<16>', 16: 'k_conv_igemm<64, 0, true>', 17: 'k_conv_igemm<64, 0, true>'}),
+    ((20, 4, 32, 64, 64, 3, 1, 1), {}, {0: 'k_conv_igemm<64, 0, false>', 1: 'k_conv_igemm<64, 0, false>', 2: 'k_wgrad3x3_ring2', 16: 'k_conv_igemm<64, 0, true>', 17: 'k_conv_igemm<64, 0, true>'}),
+    ((5, 12, 32, 64, 128, 3, 1, 1), {}, {0: 'k_conv_igemm<128, 0, false>', 1: 'k_conv_igemm<64, 0, false>', 2: 'k_wgrad3x3_ring2', 16: 'k_conv_igemm<128, 0, true>', 17: 'k_conv_igemm<64, 0, true>'}),
+    ((9, 1, 64, 64, 64, 3, 1, 1), {}, {0: 'k_conv_igemm<64, 0, false>', 1: 'k_conv_igemm<64, 0, false>', 2: 'k_wgrad3x3_ring2', 16: 'k_conv_igemm<64, 0, true>', 17: 'k_conv_igemm<64, 0, true>'}),
+    ((1, 16, 16, 512, 512, 3, 1, 1), {}, {0: 'k_conv_igemm<128, 0, false>', 1: 'k_conv_igemm<128, 0, false>', 2: 'k_wgrad3x3<16>', 16: 'k_conv_igemm<128, 0, true>', 17: 'k_conv_igemm<128, 0, true>'}),
+    ((2, 16, 16, 256, 512, 3, 2, 1), {}, {0: 'k_conv_igemm<128, 0, false>', 1: 'k_conv_igemm<128, 2, false>', 2: 'k_conv_wgrad<128, 128>', 16: 'k_conv_igemm<128, 0, true>', 17: 'k_conv_igemm<128, 2, true>'}),
+    ((1, 17, 9, 128, 256, 1, 2, 0), {}, {0: 'k_conv_igemm<128, 0, false>', 1: 'k_conv_igemm<128, 3, false>', 2: 'k_conv_wgrad<128, 128>', 16: 'k_conv_igemm<128, 0, true>', 17: 'k_conv_igemm<128, 3, true>'}),
+    ((2, 8, 8, 128, 128, 1, 1, 0), {}, {0: 'k_conv_igemm<128, 0, false>', 1: 'k_conv_igemm<128, 0, false>', 2: 'k_conv_wgrad<128, 128>', 16: 'k_conv_igemm<128, 0, true>', 17: 'k_conv_igemm<128, 0, true>'}),
+    ((2, 12, 12, 128, 64, 3, 2, 1), {}, {0: 'k_conv_igemm<64, 0, false>', 1: 'k_conv_igemm<128, 3, false>', 2: 'k_conv_wgrad<64, 128>', 16: 'k_conv_igemm<64, 0, true>', 17: 'k_conv_igemm<128, 3, true>'}),
+    ((2, 16, 16, 128, 64, 3, 2, 1), {}, {0: 'k_conv_igemm<64, 0, false>', 1: 'k_conv_igemm<128, 2, false>', 2: 'k_conv_wgrad<64, 128>', 16: 'k_conv_igemm<64, 0, true>', 17: 'k_conv_igemm<128, 2, true>'}),
+    ((2, 16, 32, 64, 64, 3, 1, 1), {'wgrad_f32_ring': 0}, {2: 'k_wgrad3x3<32>'}),
+    ((2, 16, 32, 64, 64, 3, 1, 1), {'wgrad_f32_ring': 1}, {2: 'k_wgrad3x3_ring'}),
+    ((1, 7, 96, 64, 64, 3, 1, 1), {'wgrad_f32_ring': 0}, {2: 'k_wgrad3x3<32>'}),
+    ((1, 7, 96, 64, 64, 3, 1, 1), {'wgrad_f32_ring': 1}, {2: 'k_wgrad3x3_ring'}),
+    ((3, 40, 64, 64, 64, 3, 1, 1), {'wgrad_f32_ring': 0}, {2: 'k_wgrad3x3<32>'}),
+    ((3, 40, 64, 64, 64, 3, 1, 1), {'wgrad_f32_ring': 1}, {2: 'k_wgrad3x3_ring'}),
+    ((2, 8, 32, 128, 128, 3, 1, 1), {'wgrad_f32_ring': 0}, {2: 'k_wgrad3x3<32>'}),
+    ((2, 8, 32, 128, 128, 3, 1, 1), {'wgrad_f32_ring': 1}, {2: 'k_wgrad3x3_ring'}),
+    ((1, 5, 64, 192, 64, 3, 1, 1), {'wgrad_f32_ring': 0}, {2: 'k_wgrad3x3<32>'}),
+    ((1, 5, 64, 192, 64, 3, 1, 1), {'wgrad_f32_ring': 1}, {2: 'k_wgrad3x3_ring'}),
+    ((20, 4, 32, 64, 64, 3, 1, 1), {'wgrad_f32_ring': 0}, {2: 'k_wgrad3x3<32>'}),
+    ((20, 4, 32, 64, 64, 3, 1, 1), {'wgrad_f32_ring': 1}, {2: 'k_wgrad3x3_ring'}),
+    ((5, 12, 32, 64, 128, 3, 1, 1), {'wgrad_f32_ring': 0}, {2: 'k_wgrad3x3<32>'}),
+    ((5, 12, 32, 64, 128, 3, 1, 1), {'wgrad_f32_ring': 1}, {2: 'k_wgrad3x3_ring'}),
+    ((9, 1, 64, 64, 64, 3, 1, 1), {'wgrad_f32_ring': 0}, {2: 'k_wgrad3x3<32>'}),
+    ((9, 1, 64, 64, 64, 3, 1, 1), {'wgrad_f32_ring': 1}, {2: 'k_wgrad3x3_ring'}),
+    ((3, 16, 16, 64, 64, 3, 1, 1), {'conv_patch_min_tiles': 1, 'conv_fwd_split_k': 0, 'conv_patch_bn64': 1}, {0: 'k_conv3x3_patch<64, false>', 1: 'k_conv3x3_patch<64, false>'}),
+    ((3, 16, 16, 64, 64, 3, 1, 1), {'conv_patch_min_tiles': 1, 'conv_fwd_split_k': 0}, {16: 'k_conv3x3_patch<64, true>', 17: 'k_conv3x3_patch<64, true>'}),
+    ((2, 32, 32, 128, 128, 3, 1, 1), {'conv_patch_min_tiles': 1, 'conv_fwd_split_k': 0, 'conv_patch_bn64': 1}, {0: 'k_conv3x3_patch<128, false>', 1: 'k_conv3x3_patch<128, false>'}),
+    ((2, 32, 32, 128, 128, 3, 1, 1), {'conv_patch_min_tiles': 1, 'conv_fwd_split_k': 0}, {16: 'k_conv3x3_patch<128, true>', 17: 'k_conv3x3_patch<128, true>'}),
+    ((1, 64, 64, 64, 128, 3, 1, 1), {'conv_patch_min_tiles': 1, 'conv_fwd_split_k': 0, 'conv_patch_bn64': 1}, {0: 'k_conv3x3_patch<128, false>', 1: 'k_conv3x3_patch<64, false>'}),
+    ((1, 64, 64, 64, 128, 3, 1, 1), {'conv_patch_min_tiles': 1, 'conv_fwd_split_k': 0}, {16: 'k_conv3x3_patch<128, true>', 17: 'k_conv3x3_patch<64, true>'}),
+    ((1, 8, 128, 64, 64, 3, 1, 1), {'conv_patch_min_tiles': 1, 'conv_fwd_split_k': 0, 'conv_patch_bn64': 1}, {0: 'k_conv3x3_patch_roll<64, false>', 1: 'k_conv3x3_patch_roll<64, false>'}),
+    ((1, 8, 128, 64, 64, 3, 1, 1), {'conv_patch_min_tiles': 1, 'conv_fwd_split_k': 0}, {16: 'k_conv3x3_patch_roll<64, true>', 17: 'k_conv3x3_patch_roll<64, true>'}),
+    ((1, 4, 128, 128, 256, 3, 1, 1), {'conv_patch_min_tiles': 1, 'conv_fwd_split_k': 0, 'conv_patch_bn64': 1}, {0: 'k_conv3x3_patch_roll<128, false>', 1: 'k_conv3x3_patch_roll<128, false>'}),
+    ((1, 4, 128, 128, 256, 3, 1, 1), {'conv_patch_min_tiles': 1, 'conv_fwd_split_k': 0}, {16: 'k_conv3x3_patch_roll<128, true>', 17: 'k_conv3x3_patch_roll<128, true>'}),
+    ((5, 16, 16, 256, 128, 3, 1, 1), {'conv_patch_min_tiles': 1, 'conv_fwd_split_k': 0, 'conv_patch_bn64': 1}, {0: 'k_conv3x3_patch<128, false>', 1: 'k_conv3x3_patch<128, false>'}),
+    ((5, 16, 16, 256, 128, 3, 1, 1), {'conv_patch_min_tiles': 1, 'conv_fwd_split_k': 0}, {16: 'k_conv3x3_patch<128, true>', 17: 'k_conv3x3_patch<128, true>'}),
+    ((2, 6, 128, 128, 128, 3, 1, 1), {'conv_patch_min_tiles': 1, 'conv_fwd_split_k': 0, 'conv_patch_bn64': 1}, {0: 'k_conv3x3_patch_roll<128, false>', 1: 'k_conv3x3_patch_roll<128, false>'}),
+    ((2, 6, 128, 128, 128, 3, 1, 1), {'conv_patch_min_tiles': 1, 'conv_fwd_split_k': 0}, {16: 'k_conv3x3_patch_roll<128, true>', 17: 'k_conv3x3_patch_roll<128, true>'}),
+    ((4, 16, 16, 256, 256, 3, 1, 1), {'conv_patch_min_tiles': 12, 'conv_patch_narrow': 1, 'conv_fwd_split_k': 0}, {0: 'k_conv3x3_patch<64, false>', 1: 'k_conv3x3_patch<64, false>', 16: 'k_conv_igemm<128, 0, true>', 17: 'k_conv_igemm<128, 0, true>'}),
+    ((4, 16, 16, 256, 256, 3, 1, 1), {'conv_patch_min_tiles': 12, 'conv_patch_narrow': 0, 'conv_fwd_split_k': 0}, {0: 'k_conv_igemm<128, 0, false>', 1: 'k_conv_igemm<128, 0, false>'}),
+    ((4, 16, 16, 256, 256, 3, 1, 1), {'conv_patch_min_tiles': 12, 'conv_patch_narrow': 2, 'conv_fwd_split_k': 0}, {16: 'k_conv3x3_patch<64, true>', 17: 'k_conv3x3_patch<64, true>'}),
+    ((2, 16, 64, 64, 64, 3, 1, 1), {'conv_rows_f32_min_units': 1, 'conv_fwd_split_k': 0}, {0: 'k_conv3x3_c64_rows_f32', 1: 'k_conv3x3_c64_rows_f32'}),
+    ((1, 21, 128, 64, 64, 3, 1, 1), {'conv_rows_f32_min_units': 1, 'conv_fwd_split_k': 0}, {0: 'k_conv3x3_c64_rows_f32', 1: 'k_conv3x3_c64_rows_f32'}),
+    ((3, 9, 192, 64, 64, 3, 1, 1), {'conv_rows_f32_min_units': 1, 'conv_fwd_split_k': 0}, {0: 'k_conv3x3_c64_rows_f32', 1: 'k_conv3x3_c64_rows_f32'}),
+    ((2, 40, 64, 64, 64, 3, 1, 1), {'conv_rows_f32_min_units': 1, 'conv_fwd_split_k': 0}, {0: 'k_conv3x3_c64_rows_f32', 1: 'k_conv3x3_c64_rows_f32'}),
+    ((2, 16, 128, 64, 64, 3, 1, 1), {'conv_rows64_min_units': 1, 'conv_fwd_split_k': 0, 'conv_rows16': 1}, {16: 'k_conv3x3_c64_rows16_bf16', 17: 'k_conv3x3_c64_rows16_bf16'}),
+    ((2, 16, 128, 64, 64, 3, 1, 1), {'conv_rows64_min_units': 1, 'conv_fwd_split_k': 0, 'conv_rows16': 0}, {16: 'k_conv3x3_c64_rows_bf16', 17: 'k_conv3x3_c64_rows_bf16'}),
+    ((1, 24, 256, 64, 64, 3, 1, 1), {'conv_rows64_min_units': 1, 'conv_fwd_split_k': 0, 'conv_rows16': 1}, {16: 'k_conv3x3_c64_rows16_bf16', 17: 'k_conv3x3_c64_rows16_bf16'}),
+    ((1, 24, 256, 64, 64, 3, 1, 1), {'conv_rows64_min_units': 1, 'conv_fwd_split_k': 0, 'conv_rows16': 0}, {16: 'k_conv3x3_c64_rows_bf16', 17: 'k_conv3x3_c64_rows_bf16'}),
+    ((3, 9, 128, 64, 64, 3, 1, 1), {'conv_rows64_min_units': 1, 'conv_fwd_split_k': 0, 'conv_rows16': 1}, {16: 'k_conv3x3_c64_rows16_bf16', 17: 'k_conv3x3_c64_rows16_bf16'}),
+    ((3, 9, 128, 64, 64, 3, 1, 1), {'conv_rows64_min_units': 1, 'conv_fwd_split_k': 0, 'conv_rows16': 0}, {16: 'k_conv3x3_c64_rows_bf16', 17: 'k_conv3x3_c64_rows_bf16'}),
+    ((2, 1, 128, 64, 64, 3, 1, 1), {'conv_rows64_min_units': 1, 'conv_fwd_split_k': 0, 'conv_rows16': 1}, {16: 'k_conv3x3_c64_rows16_bf16', 17: 'k_conv3x3_c64_rows16_bf16'}),
+    ((2, 1, 128, 64, 64, 3, 1, 1), {'conv_rows64_min_units': 1, 'conv_fwd_split_k': 0, 'conv_rows16': 0}, {16: 'k_conv3x3_c64_rows_bf16', 17: 'k_conv3x3_c64_rows_bf16'}),
+    ((1, 2, 128, 64, 64, 3, 1, 1), {'conv_rows64_min_units': 1, 'conv_fwd_split_k': 0, 'conv_rows16': 1}, {16: 'k_conv3x3_c64_rows16_bf16', 17: 'k_conv3x3_c64_rows16_bf16'}),
+    ((1, 2, 128, 64, 64, 3, 1, 1), {'conv_rows64_min_units': 1, 'conv_fwd_split_k': 0, 'conv_rows16': 0}, {16: 'k_conv3x3_c64_rows_bf16', 17: 'k_conv3x3_c64_rows_bf16'}),
+    ((4, 32, 32, 128, 128, 3, 1, 1), {'conv_pp_min_tiles': 1, 'conv_fwd_split_k': 0}, {16: 'k_conv3x3_bf16_pp', 17: 'k_conv3x3_bf16_pp'}),
+    ((2, 16, 16, 256, 256, 3, 1, 1), {'conv_pp_min_tiles': 1, 'conv_fwd_split_k': 0}, {16: 'k_conv3x3_bf16_pp', 17: 'k_conv3x3_bf16_pp'}),
+    ((6, 16, 16, 128, 128, 3, 1, 1), {'conv_pp_min_tiles': 1, 'conv_fwd_split_k': 0}, {16: 'k_conv3x3_bf16_pp', 17: 'k_conv3x3_bf16_pp'}),
+    ((1, 8, 128, 128, 128, 3, 1, 1), {'conv_pp_min_tiles': 1, 'conv_fwd_split_k': 0}, {16: 'k_conv3x3_bf16_pp', 17: 'k_conv3x3_bf16_pp'}),
+    ((1, 8, 128, 128, 128, 3, 1, 1), {'conv_pp_min_tiles': 1, 'conv_fwd_split_k': 0, 'conv_pp_strips': 0, 'conv_patch_min_tiles': 1}, {16: 'k_conv3x3_patch_roll<128, true>', 17: 'k_conv3x3_patch_roll<128, true>'}),
+    ((1, 4, 256, 128, 128, 3, 1, 1), {'conv_pp_min_tiles': 1, 'conv_fwd_split_k': 0}, {16: 'k_conv3x3_bf16_pp', 17: 'k_conv3x3_bf16_pp'}),
+    ((2, 12, 128, 128, 256, 3, 1, 1), {'conv_pp_min_tiles': 1, 'conv_fwd_split_k': 0}, {16: 'k_conv3x3_bf16_pp', 17: 'k_conv3x3_bf16_pp'}),
+    ((2, 12, 128, 128, 256, 3, 1, 1), {'conv_pp_min_tiles': 1, 'conv_fwd_split_k': 0, 'conv_pp_strips': 0, 'conv_patch_min_tiles': 1}, {16: 'k_conv3x3_patch_roll<128, true>', 17: 'k_conv3x3_patch_roll<128, true>'}),
+    ((2, 16, 16, 64, 128, 1, 1, 0), {'conv1x1_stream_min_pixels': 32}, {16: 'k_conv1x1_stream_bf16<64, 2>', 17: 'k_conv_igemm<64, 0, true>'}),
+    ((1, 8, 20, 64, 128, 1, 1, 0), {'conv1x1_stream_min_pixels': 32}, {16: 'k_conv1x1_stream_bf16<64, 2>', 17: 'k_conv_igemm<64, 0, true>'}),
+    ((3, 12, 8, 128, 128, 1, 1, 0), {'conv1x1_stream_min_pixels': 32}, {16: 'k_conv1x1_stream_bf16<128, 1>', 17: 'k_conv1x1_stream_bf16<128, 1>'}),
+    ((2, 32, 32, 128, 128, 1, 1, 0), {'conv1x1_stream_min_pixels': 32}, {16: 'k_conv1x1_stream_bf16<128, 1>', 17: 'k_conv1x1_stream_bf16<128, 1>'}),
+    ((8, 64, 64, 512, 512, 1, 1, 0), {}, {0: 'k_conv_igemm_big<128, 0, false>'}),
+    ((8, 64, 64, 512, 512, 1, 1, 0), {'igemm_big_bf16': 1}, {16: 'k_conv_igemm_big<128, 0, true>'}),
+    ((4, 128, 128, 256, 512, 1, 2, 0), {}, {1: 'k_conv_igemm_big<128, 2, false>'}),
+    ((4, 128, 128, 256, 512, 1, 2, 0), {'igemm_big_bf16': 1}, {17: 'k_conv_igemm_big<128, 2, true>'}),
+]
+
+EXACT_SB_CASES = [  # sd_conv2d_fwd_sb: SB_CASES of tests/test_gpu_network.py
+    (1, 128, 128, 64, 64, 3, 1, 1), (1, 64, 64, 128, 128, 3, 1, 1), (1, 32, 32, 256, 256, 3, 1, 1), (1, 16, 16, 512, 512, 3, 1, 1),
+    (1, 128, 128, 64, 128, 3, 2, 1), (1, 128, 128, 64, 128, 1, 2, 0), (1, 16, 16, 512, 128, 1, 1, 0), (1, 32, 32, 256, 128, 1, 1, 0),
+    (2, 9, 7, 256, 256, 3, 1, 1), (3, 20, 12, 64, 64, 3, 1, 1), (1, 24, 40, 64, 64, 5, 1, 2), (2, 32, 32, 64, 128, 7, 2, 3)]
+EXACT_STEM_SHAPES = [(2, 64, 96), (5, 32, 32), (2, 136, 520)]
+# sd_conv2d_wgrad_bf16: 3x3 / 1 ring forms (Wo % 32 == 0), the 16-wide form, k_wgrad_tap_bf16 (Cout % 128 == 0) and the widened fp32 path
+EXACT_WGRAD_BF16_CASES = [(2, 32, 32, 64, 64, 3, 1, 1), (1, 16, 16, 128, 64, 3, 1, 1), (3, 32, 64, 64, 128, 3, 1, 1), (2, 20, 12, 64, 128, 3, 2, 1),
+                          (4, 12, 12, 64, 128, 1, 2, 0), (2, 8, 8, 128, 128, 1, 1, 0), (1, 17, 9, 128, 256, 1, 2, 0), (20, 4, 32, 64, 64, 3, 1, 1),
+                          (5, 12, 32, 64, 128, 3, 1, 1), (3, 7, 96, 128, 64, 3, 1, 1), (9, 1, 64, 64, 64, 3, 1, 1), (2, 12, 12, 128, 64, 3, 2, 1)]
+WGRAD_BF16_RINGS = (0, 2, 3, 4, 5)
+# statistics regime: (geometry, options, pass 0 / 16 kernel): tile kernels, ragged last tile, patch and row-stream epilogues
+EXACT_STATS_CASES = [
+    ((2, 16, 24, 64, 64, 3, 1, 1), {"conv_fwd_split_k": 0}, {0: "k_conv_igemm<64, 0, false>", 16: "k_conv_igemm<64, 0, true>"}),
+    ((2, 9, 7, 256, 256, 3, 1, 1), {"conv_fwd_split_k": 0}, {0: "k_conv_igemm<128, 0, false>", 16: "k_conv_igemm<128, 0, true>"}),
+    ((1, 16, 16, 512, 512, 3, 1, 1), {}, {0: "k_conv_igemm<128, 0, false>", 16: "k_conv_igemm<128, 0, true>"}),      # split-K: two-pass form
+    ((2, 12, 12, 64, 128, 1, 2, 0), {"conv_fwd_split_k": 0}, {0: "k_conv_igemm<128, 0, false>", 16: "k_conv_igemm<128, 0, true>"}),
+    ((2, 32, 32, 128, 128, 3, 1, 1), {"conv_patch_min_tiles": 1, "conv_fwd_split_k": 0}, {0: "k_conv3x3_patch<128, false>", 16: "k_conv3x3_patch<128, true>"}),
+    ((1, 8, 128, 64, 64, 3, 1, 1), {"conv_patch_min_tiles": 1, "conv_fwd_split_k": 0, "conv_patch_bn64": 1},
+     {0: "k_conv3x3_patch_roll<64, false>", 16: "k_conv3x3_patch_roll<64, true>"}),
+    ((3, 9, 192, 64, 64, 3, 1, 1), {"conv_rows_f32_min_units": 1, "conv_fwd_split_k": 0}, {0: "k_conv3x3_c64_rows_f32"}),
+    ((3, 9, 128, 64, 64, 3, 1, 1), {"conv_rows64_min_units": 1, "conv_fwd_split_k": 0, "conv_rows16": 0}, {16: "k_conv3x3_c64_rows_bf16"}),
+    ((4, 32, 32, 128, 128, 3, 1, 1), {"conv_pp_min_tiles": 1, "conv_fwd_split_k": 0}, {16: "k_conv3x3_bf16_pp"}),
+]
+# sd_conv2d_dgrad_bn_reduce_sums: (geometry, options, pass 1 kernel)
+EXACT_BNRED_CASES = [
+    ((2, 16, 24, 64, 64, 3, 1, 1), {}, "k_conv_igemm<64, 0, false>"),
+    ((2, 9, 7, 256, 256, 3, 1, 1), {}, "k_conv_igemm<128, 0, false>"),
+    ((2, 32, 32, 64, 128, 3, 2, 1), {}, "k_conv_igemm<64, 2, false>"),
+    ((2, 32, 32, 128, 128, 3, 1, 1), {"conv_patch_min_tiles": 1}, "k_conv3x3_patch<128, false>"),
+    ((1, 8, 128, 64, 64, 3, 1, 1), {"conv_patch_min_tiles": 1, "conv_patch_bn64": 1}, "k_conv3x3_patch_roll<64, false>"),
+]
+# heads (B, H, W, C, Co): generic path (HW % 16 != 0, C != 128, 16 < Co <= 32), the C = 128 / Co <= 16 MFMA path, the wide path (Co > 32:
+# one Co that is no multiple of 16 and one that is; ragged pixel tiles)
+EXACT_HEAD_CASES = [(2, 6, 10, 128, 7), (2, 16, 16, 64, 5), (1, 12, 12, 128, 20), (2, 48, 48, 128, 7), (3, 16, 20, 128, 16),
+                    (2, 24, 24, 128, 33), (1, 45, 37, 64, 100), (2, 16, 16, 256, 64)]
+EXACT_HEAD_BF16_BWD_CASES = [(2, 6, 10, 128, 7), (3, 32, 40, 128, 8), (2, 16, 16, 64, 5)]
+# fused FPN conv + head (k_conv3x3_bf16_pp_head): (B, H, W, Cin, head channels)
+EXACT_FUSED_HEAD_CASES = [(4, 32, 32, 128, 7), (1, 8, 128, 128, 20), (2, 16, 16, 256, 32)]
+
+
+def case_id(entry):
+    geom, opts = entry[0], entry[1]
+    return "x".join(str(v) for v in geom) + "".join(f"-{k.replace('conv_', '')}{v}" for k, v in opts.items())
+
+
+# -- operand regimes: seeded generators of integer-valued fp32 tensors -----------------------------
+def int_uniform(g, shape, a):
+    import torch
+    return torch.randint(-a, a + 1, tuple(shape), generator=g).float()
+
+
+def half_integers(g, shape, a):
+    """multiples of 0.5 in [-a, a]"""
+    import torch
+    return torch.randint(-2 * a, 2 * a + 1, tuple(shape), generator=g).float() / 2
+
+
+def pow2_scales(g, n):
+    import torch
+    return torch.tensor([0.5, 1.0, 2.0])[torch.randint(0, 3, (n,), generator=g)]
+
+
+def ternary(g, shape, density):
+    import torch
+    sign = torch.randint(0, 2, tuple(shape), generator=g).float() * 2 - 1
+    return sign * (torch.rand(tuple(shape), generator=g) < density).float()
+
+
+# amplitude pairs of the rounding regime, widest first: integers up to 15 are exact in bf16
+_AMPLITUDES = [(15, 15), (15, 11), (15, 7), (11, 7), (8, 6), (8, 4), (6, 4), (4, 4), (4, 3), (3, 3), (3, 2), (2, 2), (2, 1), (1, 1)]
+
+
+def rounding_amplitudes(K, target=900.0):
+    """Amplitudes (a, b) of the two operands of a K-term reduction whose sums have a standard deviation near `target`: a uniform integer in
+    [-a, a] has variance a (a + 1) / 3.  Around 900 the outputs straddle the bf16 binades with an ulp of 2 .. 16 (256 .. 4096), where an
+    integer needs rounding with probability 1 - 1/ulp and is a tie with probability 1/ulp; much larger sums have almost no ties, much smaller
+    ones need no rounding (the [-3, 3] x [-2, 2] range of a 576-term conv rounds nothing)."""
+    import math
+    best = min(_AMPLITUDES, key=lambda ab: abs(math.log(math.sqrt(K * ab[0] * (ab[0] + 1) * ab[1] * (ab[1] + 1) / 9.0) / target)))
+    return best
+
+
+def rounding_pair(g, shape_a, shape_b, K):
+    a, b = rounding_amplitudes(K)
+    return int_uniform(g, shape_a, a), int_uniform(g, shape_b, b)
+
+
+def wide_pair(g, shape_a, shape_b, K, wide_first):
+    """one operand with 12 significant bits (integers in [-2047, 2047]), the other in {-1, 0, 1}, thinned so that a K-term sum of absolute
+    products stays near 3000 * 1024 (below 2^22)"""
+    density = min(2.0 / 3.0, 3000.0 / K)
+    if wide_first:
+        return int_uniform(g, shape_a, 2047), ternary(g, shape_b, density)
+    return ternary(g, shape_a, density), int_uniform(g, shape_b, 2047)
+
+
+def stats_pair(g, shape_a, shape_b, K, pixels):
+    """statistics regime: the widest of the small ranges for which pixels * E[y^2] = pixels * K * var(a) * var(b) stays below 2^22 (the
+    asserted bound is on the actual sums)"""
+    for a, b in ((3, 2), (2, 2), (2, 1), (1, 1)):
+        if pixels * K * (a * (a + 1) / 3.0) * (b * (b + 1) / 3.0) < 2 ** 22:
+            break
+    return int_uniform(g, shape_a, a), int_uniform(g, shape_b, b)
+
+
+# -- bf16 rounding on fp32 bit patterns (independent of torch's conversion) ---------------------------
+def _bits(t):
+    import torch
+    return t.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+
+
+def _from_bits(b):
+    import torch
+    b = b & 0xFFFFFFFF
+    b = torch.where(b >= 2 ** 31, b - 2 ** 32, b)
+    return b.to(torch.int32).view(torch.float32)
+
+
+def bf16_rne(t32):
+    """fp32 tensor -> fp32 tensor holding round-to-nearest-even bf16 values (finite inputs)"""
+    b = _bits(t32)
+    return _from_bits((b + 0x7FFF + ((b >> 16) & 1)) & 0xFFFF0000)
+
+
+def bf16_trunc(t32):
+    return _from_bits(_bits(t32) & 0xFFFF0000)
+
+
+def rounding_shares(ref32):
+    """(share not representable in bf16, share of exact ties, share where truncation differs from nearest-even)"""
+    low = _bits(ref32) & 0xFFFF
+    return (float((low != 0).double().mean()), float((low == 0x8000).double().mean()),
+            float((bf16_rne(ref32) != bf16_trunc(ref32)).double().mean()))
+
+
+ROUNDING_SHARES_MIN = (0.20, 0.05, 0.05)
+
+
+def assert_rounding_coverage(ref32, what=""):
+    s = rounding_shares(ref32)
+    assert all(v >= m for v, m in zip(s, ROUNDING_SHARES_MIN)), f"{what}: inexact / ties / truncation-differs shares {s} below {ROUNDING_SHARES_MIN}"
+    return s
+
+
+# -- fp64 references and their worst-case bounds ------------------------------------------------------
+def conv_ref(x, w, stride, pad):
+    import torch.nn.functional as F
+    return F.conv2d(x.double(), w.double(), None, stride, pad)
+
+
+def dgrad_ref(dy, w, x_shape, stride, pad):
+    import torch
+    return torch.nn.grad.conv2d_input(tuple(x_shape), w.double(), dy.double(), stride, pad)
+
+
+def wgrad_ref(dy, x, w_shape, stride, pad):
+    import torch
+    return torch.nn.grad.conv2d_weight(x.double(), tuple(w_shape), dy.double(), stride, pad)
+
+
+def epilogue_ref(conv64, scale=None, shift=None, res=None, relu=False):
+    y = conv64
+    if scale is not None:
+        y = y * scale.double().view(1, -1, 1, 1)
+    if shift is not None:
+        y = y + shift.double().view(1, -1, 1, 1)
+    if res is not None:
+        y = y + res.double()
+    return y.clamp_min(0) if relu else y
+
+
+def assert_exact_reference(ref64, bound64, limit=EXACT_LIMIT, what=""):
+    """the conditions on the inputs: worst-case bound below the limit everywhere, and the fp64 reference equal to its own fp32 rounding"""
+    import torch
+    assert float(bound64.max()) < limit, f"{what}: worst-case bound {float(bound64.max()):.0f} >= {limit:.0f}"
+    assert float(ref64.abs().max()) <= float(bound64.max())
+    assert torch.equal(ref64.float().double(), ref64), f"{what}: the reference is not exact in fp32"
+    return ref64.float()
+
+
+def assert_equal_report(got, ref, what="", layout="bhwc"):
+    """torch.equal with a report: count of mismatches and the first few with their position (named by `layout`) and both values.
+    NaN in `got` (an element the kernel never wrote) is a mismatch."""
+    import torch
+    got, ref = got.detach().cpu(), ref.detach().cpu()
+    assert got.shape == ref.shape and got.dtype == ref.dtype, (what, got.shape, ref.shape, got.dtype, ref.dtype)
+    if torch.equal(got, ref):
+        return
+    bad = (got != ref) | torch.isnan(got)
+    idx = bad.nonzero()
+    lines = [f"{what}: {int(bad.sum())} of {bad.numel()} elements differ (shape {tuple(got.shape)}, position = {layout})"]
+    for i in idx[:8].tolist():
+        lines.append(f"  {tuple(i)}: got {float(got[tuple(i)])!r}, want {float(ref[tuple(i)])!r}")
+    raise AssertionError("\n".join(lines))
+
+
+# -- the problems the CPU and the GPU module share (cached: a reference is computed once and never modified) --------
+def _seed(geom, salt):
+    return (sum((i + 3) * 7919 * int(v) for i, v in enumerate(geom)) + 104729 * salt) % (2 ** 31)
+
+
+def _pair(g, regime, shape_a, shape_b, K, pixels):
+    if regime == "round":
+        return rounding_pair(g, shape_a, shape_b, K)
+    if regime == "stats":
+        return stats_pair(g, shape_a, shape_b, K, pixels)
+    return wide_pair(g, shape_a, shape_b, K, regime == "wide_a")
+
+
+import functools  # noqa: E402
+
+
+@functools.lru_cache(maxsize=None)
+def fwd_problem(geom, regime="round"):
+    """x (B, Cin, H, W), w (Cout, Cin, k, k) and the fp64 conv with its worst-case bound conv(|x|, |w|); regime: round / wide_a (x wide) /
+    wide_b (w wide) / stats"""
+    import torch
+    B, H, W, cin, cout, k, stride, pad = geom
+    g = torch.Generator().manual_seed(_seed(geom, {"round": 1, "wide_a": 2, "wide_b": 3, "stats": 4}[regime]))
+    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    x, w = _pair(g, regime, (B, cin, H, W), (cout, cin, k, k), cin * k * k, B * Ho * Wo)
+    ref, bound = conv_ref(x, w, stride, pad), conv_ref(x.abs(), w.abs(), stride, pad)
+    return {"x": x, "w": w, "ref": ref, "bound": bound}
+
+
+@functools.lru_cache(maxsize=None)
+def dgrad_problem(geom, regime="round"):
+    """dy (B, Cout, Ho, Wo), w and the fp64 data gradient with its bound; wide_a: dy wide, wide_b: w wide"""
+    import torch
+    B, H, W, cin, cout, k, stride, pad = geom
+    g = torch.Generator().manual_seed(_seed(geom, {"round": 5, "wide_a": 6, "wide_b": 7, "stats": 8}[regime]))
+    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    K = cout * (-(-k // stride)) ** 2                    # taps that reach one input pixel
+    dy, w = _pair(g, regime, (B, cout, Ho, Wo), (cout, cin, k, k), K, B * H * W)
+    ref = dgrad_ref(dy, w, (B, cin, H, W), stride, pad)
+    bound = dgrad_ref(dy.abs(), w.abs(), (B, cin, H, W), stride, pad)
+    return {"dy": dy, "w": w, "ref": ref, "bound": bound}
+
+
+@functools.lru_cache(maxsize=None)
+def wgrad_problem(geom, regime="round"):
+    """dy, x and the fp64 weight gradient (Cout, Cin, k, k) with its bound sum |dy| |x|; wide_a: dy wide, wide_b: x wide"""
+    import torch
+    B, H, W, cin, cout, k, stride, pad = geom
+    g = torch.Generator().manual_seed(_seed(geom, {"round": 9, "wide_a": 10, "wide_b": 11}[regime]))
+    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    if regime == "round":      # no bf16 output here: the widest bf16-exact integers the pixel count allows
+        a = 15 if B * Ho * Wo * 225 < EXACT_LIMIT else 8
+        dy, x = int_uniform(g, (B, cout, Ho, Wo), a), int_uniform(g, (B, cin, H, W), a)
+    else:
+        dy, x = wide_pair(g, (B, cout, Ho, Wo), (B, cin, H, W), B * Ho * Wo, regime == "wide_a")
+    ref = wgrad_ref(dy, x, (cout, cin, k, k), stride, pad)
+    bound = wgrad_ref(dy.abs(), x.abs(), (cout, cin, k, k), stride, pad)
+    return {"dy": dy, "x": x, "ref": ref, "bound": bound}
+
+
+def epilogue_operands(geom_or_seed, channels, res_shape, salt=0, wide=False):
+    """scale in {0.5, 1, 2}, half-integer shift, integer residual (12 significant bits in the wide regime)"""
+    import torch
+    g = torch.Generator().manual_seed(_seed(tuple(geom_or_seed), 20 + salt))
+    return pow2_scales(g, channels), half_integers(g, (channels,), 32), int_uniform(g, res_shape, 2047 if wide else 63)
+
+
+def epilogue_bound(bound64, scale=None, shift=None, res=None):
+    b = bound64
+    if scale is not None:
+        b = b * scale.double().abs().view(1, -1, 1, 1)
+    if shift is not None:
+        b = b + shift.double().abs().view(1, -1, 1, 1)
+    if res is not None:
+        b = b + res.double().abs()
+    return b
+
+
+@functools.lru_cache(maxsize=None)
+def stem_problem(shape, regime="round"):
+    """image (B, 3, H, W), weights (64, 3, 7, 7), fp64 conv 7x7 / 2 / 3 and its bound"""
+    B, H, W = shape
+    return fwd_problem((B, H, W, 3, 64, 7, 2, 3), regime)
+
+
+@functools.lru_cache(maxsize=None)
+def head_problem(case, regime="round"):
+    """x (B, C, H, W), w (Co, C), bias (Co), dy (B, Co, H, W) integers; fp64 forward, dx, dw, dbias and their bounds"""
+    import torch
+    B, H, W, Cc, Co = case
+    g = torch.Generator().manual_seed(_seed(case, {"round": 12, "wide_a": 13, "wide_b": 14}[regime]))
+    if regime == "round":
+        x, w = int_uniform(g, (B, Cc, H, W), 15), int_uniform(g, (Co, Cc), 63)      # (w is fp32 on every path; |w| <= 256 is exact in bf16 too)
+        dy = int_uniform(g, (B, Co, H, W), 15 if B * H * W * 225 < EXACT_LIMIT else 8)
+    else:
+        x, w = wide_pair(g, (B, Cc, H, W), (Co, Cc), Cc, regime == "wide_a")
+        dy = ternary(g, (B, Co, H, W), min(2.0 / 3.0, 3000.0 / (B * H * W)))
+    bias = int_uniform(g, (Co,), 63)
+    xd, wd, dyd = x.double(), w.double(), dy.double()
+    out = {"x": x, "w": w, "bias": bias, "dy": dy,
+           "y": torch.einsum("bchw,oc->bohw", xd, wd) + bias.double().view(1, -1, 1, 1),
+           "y_bound": torch.einsum("bchw,oc->bohw", xd.abs(), wd.abs()) + bias.double().abs().view(1, -1, 1, 1),
+           "dx": torch.einsum("bohw,oc->bchw", dyd, wd), "dx_bound": torch.einsum("bohw,oc->bchw", dyd.abs(), wd.abs()),
+           "dw": torch.einsum("bohw,bchw->oc", dyd, xd), "dw_bound": torch.einsum("bohw,bchw->oc", dyd.abs(), xd.abs()),
+           "db": dyd.sum((0, 2, 3)), "db_bound": dyd.abs().sum((0, 2, 3))}
+    return out
