@@ -251,6 +251,25 @@ int sd_preprocess_images_list_jitter(const uint8_t* const* images, int B, int Hi
                                      const int* jitter_order, const float* jitter_factors, const float* mean3, const float* std3, float* out,
                                      void* workspace, size_t workspace_bytes, sd_stream_t stream);
 
+/* Both pipelines with a random affine warp (rotate, scale, shift: torchvision RandomAffine on the RESIZED PIL image, in front of the
+ * ColorJitter) applied per image on the device, byte for byte Pillow's Image.transform(size, AFFINE, matrix, BILINEAR, fillcolor):
+ * affine (B, 6) fp64 on the DEVICE = per image the inverse matrix [m0 .. m5] that maps an output pixel centre (x + 0.5, y + 0.5) to the
+ * source position (m0 x + m1 y + m2, m3 x + m4 y + m5), both in pixels of the resized (Hout, Wout) image; any finite matrix is legal, an
+ * output pixel whose source position is outside the image takes fill3 (HOST pointer to three bytes, RGB).  jitter_order / jitter_factors
+ * as in sd_preprocess_images_jitter, or BOTH null for the chain without ColorJitter (one of the two alone: SD_ERR_INVALID); the contrast
+ * op's grey mean is taken over the warped image, fill pixels included.  workspace: sd_preprocess_affine_workspace_bytes() bytes in
+ * either case.  The list form takes the pointer table of sd_preprocess_images_list (same Win limit). */
+size_t sd_preprocess_affine_workspace_bytes(int B, int Hin, int Win, int Hout, int Wout);
+int sd_preprocess_images_affine(const uint8_t* images, int B, int Hin, int Win, int Hout, int Wout, const int* h_bounds, const int* h_kk,
+                                int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips, const int* jitter_order,
+                                const float* jitter_factors, const double* affine, const uint8_t fill3[3], const float* mean3,
+                                const float* std3, float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream);
+int sd_preprocess_images_list_affine(const uint8_t* const* images, int B, int Hin, int Win, int Hout, int Wout, const int* h_bounds,
+                                     const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips,
+                                     const int* jitter_order, const float* jitter_factors, const double* affine, const uint8_t fill3[3],
+                                     const float* mean3, const float* std3, float* out, void* workspace, size_t workspace_bytes,
+                                     sd_stream_t stream);
+
 /* ---- loss: src/sdnet/model/loss.py:17-64,91-117 ------------------------------------------- */
 
 #define SD_HM_MSE   0

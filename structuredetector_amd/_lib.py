@@ -84,6 +84,13 @@ _SIGNATURES = {
                                                      c_vp, c_vp, c_size, c_vp]),
     "sd_preprocess_images_list_jitter": (c_int, [c_vp] + [c_int] * 5 + [c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, C.POINTER(c_float),
                                                             C.POINTER(c_float), c_vp, c_vp, c_size, c_vp]),
+    # random affine warp between the resize and the jitter: ..., flips, jitter_order, jitter_factors (both null: no jitter), affine (B, 6)
+    # fp64 device, fill3 (HOST, 3 bytes), mean3, std3, out, workspace, bytes, stream
+    "sd_preprocess_affine_workspace_bytes": (c_size, [c_int] * 5),
+    "sd_preprocess_images_affine": (c_int, [c_vp] + [c_int] * 5 + [c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, C.POINTER(C.c_ubyte),
+                                            C.POINTER(c_float), C.POINTER(c_float), c_vp, c_vp, c_size, c_vp]),
+    "sd_preprocess_images_list_affine": (c_int, [c_vp] + [c_int] * 5 + [c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, C.POINTER(C.c_ubyte),
+                                                 C.POINTER(c_float), C.POINTER(c_float), c_vp, c_vp, c_size, c_vp]),
     "sd_render_targets": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_float, c_vp, c_vp]),
     "sd_loss_workspace_bytes": (c_size, [c_int] * 5),
     "sd_loss_fwd": (c_int, [C.POINTER(LossDesc), c_vp, c_vp, c_size, c_vp]),

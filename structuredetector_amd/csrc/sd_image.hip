@@ -281,6 +281,132 @@ __global__ __launch_bounds__(256) void k_jitter_norm(const uint8_t* __restrict__
     o[2 * plane] = ((float)c.b / 255.0f - m2) / d2;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// RandomAffine (rotate, scale, shift; no shear) on the RESIZED 8-bit image, in front of the jitter: torchvision's RandomAffine on a PIL
+// image = Image.transform(size, AFFINE, inverse matrix, BILINEAR, fillcolor) = Pillow's generic transform (libImaging/Geometry.c:
+// affine_transform + bilinear_filter32RGB), plain double arithmetic evaluated left to right and TRUNCATED to a byte -- a result one ulp
+// below an integer changes the byte, so everything below is fp64 with contraction off (this file's pragma).  The host hands one inverse
+// matrix (6 doubles, output pixel centre -> source position) per image; any finite matrix is legal, what maps outside the source is fill.
+// A gather: a block owns a 64 x 16 tile of one image's output (a rotated footprint of about 64 x 64 source pixels at most: compact in L2),
+// a thread four consecutive output pixels (whole-dword / 16-byte stores when the width is a multiple of 4).  The two horizontal neighbours
+// of a tap are adjacent bytes: one 8-byte read per source row where three pixels remain in the row, byte reads at the right border.
+// ---------------------------------------------------------------------------------------------------------------------------------
+constexpr int AF_TX = 16, AF_TY = 16, AF_PX = 4;                         // threads per tile row, tile rows, pixels per thread
+
+struct Affine6 { double m0, m1, m2, m3, m4, m5; };
+
+__device__ __forceinline__ void affine_row(const uint8_t* __restrict__ row, int x0, int x1, bool wide, int* a, int* b) {
+    if (wide) {                                                          // x1 == x0 + 1 and pixel x0 + 2 is in the row: 8 bytes stay inside it
+        uint64_t v;
+        __builtin_memcpy(&v, row + 3 * x0, 8);
+        a[0] = (int)(v & 255); a[1] = (int)((v >> 8) & 255); a[2] = (int)((v >> 16) & 255);
+        b[0] = (int)((v >> 24) & 255); b[1] = (int)((v >> 32) & 255); b[2] = (int)((v >> 40) & 255);
+    } else {
+        const uint8_t* p = row + 3 * x0;
+        const uint8_t* q = row + 3 * x1;
+        a[0] = p[0]; a[1] = p[1]; a[2] = p[2];
+        b[0] = q[0]; b[1] = q[1]; b[2] = q[2];
+    }
+}
+
+// one output pixel (x, y) of an (H, W, 3) image: Pillow's affine_transform + bilinear_filter32RGB
+__device__ __forceinline__ Rgb8 affine_pixel(const uint8_t* __restrict__ src, int H, int W, const Affine6& m, int x, int y, const Rgb8& fill) {
+    const double xc = (double)x + 0.5, yc5 = (double)y + 0.5;
+    double xin = m.m0 * xc + m.m1 * yc5 + m.m2;
+    double yin = m.m3 * xc + m.m4 * yc5 + m.m5;
+    if (!(xin >= 0.0 && xin < (double)W && yin >= 0.0 && yin < (double)H)) return fill;       // (a NaN is outside too)
+    xin -= 0.5; yin -= 0.5;
+    const double fx = floor(xin), fy = floor(yin);
+    const double dx = xin - fx, dy = yin - fy;
+    const int X = (int)fx, Y = (int)fy;                                  // -1 .. W - 1, -1 .. H - 1
+    const int x0 = min(max(X, 0), W - 1), x1 = min(max(X + 1, 0), W - 1);
+    const int y0 = min(max(Y, 0), H - 1), y1 = min(max(Y + 1, 0), H - 1);   // Y + 1 == H: Pillow sets v2 = v1, which row y0 read twice gives too
+    const bool wide = X >= 0 && X + 2 < W;
+    int a0[3], b0[3], a1[3], b1[3];
+    affine_row(src + (int64_t)y0 * W * 3, x0, x1, wide, a0, b0);
+    affine_row(src + (int64_t)y1 * W * 3, x0, x1, wide, a1, b1);
+    int o[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const double v1 = (double)a0[c] + (double)(b0[c] - a0[c]) * dx;
+        const double v2 = (double)a1[c] + (double)(b1[c] - a1[c]) * dx;
+        o[c] = (int)(v1 + (v2 - v1) * dy) & 255;                         // (UINT8) of a value in [0, 255]
+    }
+    return Rgb8{o[0], o[1], o[2]};
+}
+
+__device__ __forceinline__ Affine6 affine_of(const double* __restrict__ affine, int b) {
+    const double* m = affine + 6 * (int64_t)b;
+    return Affine6{m[0], m[1], m[2], m[3], m[4], m[5]};
+}
+
+// img (B, H, W, 3) u8 -> out (B, H, W, 3) u8.  grid (cdiv(W, 64), cdiv(H, 16), B)
+__global__ __launch_bounds__(256) void k_affine_u8(const uint8_t* __restrict__ img, uint8_t* __restrict__ out, int H, int W,
+                                                    const double* __restrict__ affine, int f0, int f1, int f2) {
+    const int b = blockIdx.z;
+    const int x = (blockIdx.x * AF_TX + (threadIdx.x % AF_TX)) * AF_PX, y = blockIdx.y * AF_TY + threadIdx.x / AF_TX;
+    if (x >= W || y >= H) return;
+    const Affine6 m = affine_of(affine, b);
+    const Rgb8 fill{f0, f1, f2};
+    const uint8_t* src = img + (int64_t)b * H * W * 3;
+    uint8_t* dst = out + (((int64_t)b * H + y) * W + x) * 3;
+    if ((W & 3) == 0) {                                                  // four pixels = three aligned dwords
+        Rgb8 c[AF_PX];
+#pragma unroll
+        for (int k = 0; k < AF_PX; ++k) c[k] = affine_pixel(src, H, W, m, x + k, y, fill);
+        uint32_t* d = reinterpret_cast<uint32_t*>(dst);
+        d[0] = (uint32_t)c[0].r | (uint32_t)c[0].g << 8 | (uint32_t)c[0].b << 16 | (uint32_t)c[1].r << 24;
+        d[1] = (uint32_t)c[1].g | (uint32_t)c[1].b << 8 | (uint32_t)c[2].r << 16 | (uint32_t)c[2].g << 24;
+        d[2] = (uint32_t)c[2].b | (uint32_t)c[3].r << 8 | (uint32_t)c[3].g << 16 | (uint32_t)c[3].b << 24;
+    } else {
+        for (int k = 0; k < AF_PX && x + k < W; ++k) {
+            const Rgb8 c = affine_pixel(src, H, W, m, x + k, y, fill);
+            dst[3 * k] = (uint8_t)c.r; dst[3 * k + 1] = (uint8_t)c.g; dst[3 * k + 2] = (uint8_t)c.b;
+        }
+    }
+}
+
+// the same gather + flips + to_tensor + Normalize: img (B, H, W, 3) u8 -> out (B, 3, H, W) fp32 NCHW = k_affine_u8, then the flip and
+// normalise arithmetic of k_resample_v_norm.  A thread owns four pixels of the WARPED image; a horizontal flip reverses them in the store.
+__global__ __launch_bounds__(256) void k_affine_norm(const uint8_t* __restrict__ img, float* __restrict__ out, int H, int W,
+                                                      const double* __restrict__ affine, int f0, int f1, int f2,
+                                                      const uint8_t* __restrict__ flips, float m0, float m1, float m2, float d0, float d1,
+                                                      float d2) {
+    const int b = blockIdx.z;
+    const int x = (blockIdx.x * AF_TX + (threadIdx.x % AF_TX)) * AF_PX, y = blockIdx.y * AF_TY + threadIdx.x / AF_TX;
+    if (x >= W || y >= H) return;
+    const Affine6 m = affine_of(affine, b);
+    const Rgb8 fill{f0, f1, f2};
+    const uint8_t* src = img + (int64_t)b * H * W * 3;
+    const int f = flips ? flips[b] : 0;
+    const int oy = (f & 2) ? H - 1 - y : y;
+    const int64_t plane = (int64_t)H * W;
+    float* o = out + (int64_t)b * 3 * plane + (int64_t)oy * W;
+    if ((W & 3) == 0) {
+        float r[AF_PX], g[AF_PX], bl[AF_PX];
+#pragma unroll
+        for (int k = 0; k < AF_PX; ++k) {
+            const Rgb8 c = affine_pixel(src, H, W, m, x + k, y, fill);
+            const int j = (f & 1) ? AF_PX - 1 - k : k;
+            r[j] = ((float)c.r / 255.0f - m0) / d0;
+            g[j] = ((float)c.g / 255.0f - m1) / d1;
+            bl[j] = ((float)c.b / 255.0f - m2) / d2;
+        }
+        const int ox = (f & 1) ? W - AF_PX - x : x;
+        *reinterpret_cast<float4*>(o + ox) = make_float4(r[0], r[1], r[2], r[3]);
+        *reinterpret_cast<float4*>(o + plane + ox) = make_float4(g[0], g[1], g[2], g[3]);
+        *reinterpret_cast<float4*>(o + 2 * plane + ox) = make_float4(bl[0], bl[1], bl[2], bl[3]);
+    } else {
+        for (int k = 0; k < AF_PX && x + k < W; ++k) {
+            const Rgb8 c = affine_pixel(src, H, W, m, x + k, y, fill);
+            const int ox = (f & 1) ? W - 1 - (x + k) : x + k;
+            o[ox] = ((float)c.r / 255.0f - m0) / d0;
+            o[plane + ox] = ((float)c.g / 255.0f - m1) / d1;
+            o[2 * plane + ox] = ((float)c.b / 255.0f - m2) / d2;
+        }
+    }
+}
+
 }  // namespace sd
 
 using namespace sd;
@@ -312,20 +438,33 @@ static int preprocess_tail(int B, int Hin, int Hout, int Wout, const int* v_boun
     return 0;
 }
 
-static int preprocess_jitter_tail(int B, int Hin, int Win, int Hout, int Wout, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips,
-                                  const int* jitter_order, const float* jitter_factors, const float* mean3, const float* std3, float* out,
-                                  uint8_t* tmp, hipStream_t st) {
-    uint8_t* img = tmp + sd_preprocess_workspace_bytes(B, Hin, Win, Wout);
-    unsigned long long* lsum = reinterpret_cast<unsigned long long*>(img + align_up((size_t)B * Hout * Wout * 3, 256));
-    const int64_t npix = (int64_t)Hout * Wout;
-    hipLaunchKernelGGL(k_resample_v_u8, dim3(cdiv((int64_t)B * npix, 256)), dim3(256), 0, st, tmp, img, Hin, Hout, Wout, v_bounds, v_kk, v_ksize, B);
+// vertical pass into an 8-bit image, and the two jitter launches on an 8-bit image: the halves of the jitter tail, shared with the affine forms
+static int resample_v_u8(int B, int Hin, int Hout, int Wout, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* tmp, uint8_t* img,
+                         hipStream_t st) {
+    hipLaunchKernelGGL(k_resample_v_u8, dim3(cdiv((int64_t)B * Hout * Wout, 256)), dim3(256), 0, st, tmp, img, Hin, Hout, Wout, v_bounds, v_kk,
+                       v_ksize, B);
     SD_LAUNCH_CHECK();
+    return 0;
+}
+
+static int jitter_norm(int B, int Hout, int Wout, const uint8_t* flips, const int* jitter_order, const float* jitter_factors, const float* mean3,
+                       const float* std3, float* out, const uint8_t* img, unsigned long long* lsum, hipStream_t st) {
+    const int64_t npix = (int64_t)Hout * Wout;
     hipLaunchKernelGGL(k_jitter_lsum, dim3(std::min<int64_t>(cdiv(npix, 256), 64), B), dim3(256), 0, st, img, npix, jitter_order, jitter_factors, lsum);
     SD_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_jitter_norm, dim3(cdiv((int64_t)B * npix, 256)), dim3(256), 0, st, img, out, Hout, Wout, jitter_order, jitter_factors, lsum,
                        flips, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], B);
     SD_LAUNCH_CHECK();
     return 0;
+}
+
+static int preprocess_jitter_tail(int B, int Hin, int Win, int Hout, int Wout, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips,
+                                  const int* jitter_order, const float* jitter_factors, const float* mean3, const float* std3, float* out,
+                                  uint8_t* tmp, hipStream_t st) {
+    uint8_t* img = tmp + sd_preprocess_workspace_bytes(B, Hin, Win, Wout);
+    unsigned long long* lsum = reinterpret_cast<unsigned long long*>(img + align_up((size_t)B * Hout * Wout * 3, 256));
+    if (int e = resample_v_u8(B, Hin, Hout, Wout, v_bounds, v_kk, v_ksize, tmp, img, st)) return e;
+    return jitter_norm(B, Hout, Wout, flips, jitter_order, jitter_factors, mean3, std3, out, img, lsum, st);
 }
 
 int sd_preprocess_images(const uint8_t* images, int B, int Hin, int Win, int Hout, int Wout, const int* h_bounds, const int* h_kk,
@@ -417,6 +556,86 @@ int sd_preprocess_images_list_jitter(const uint8_t* const* images, int B, int Hi
     SD_HIP(hipMemsetAsync(img + align_up((size_t)B * Hout * Wout * 3, 256), 0, (size_t)B * 8, st));        // lsum
     if (int e = resample_h_list(images, tmp, B, Hin, Win, Wout, h_bounds, h_kk, h_ksize, rpb, bpi, st)) return e;
     return preprocess_jitter_tail(B, Hin, Win, Hout, Wout, v_bounds, v_kk, v_ksize, flips, jitter_order, jitter_factors, mean3, std3, out, tmp, st);
+}
+
+// ---- RandomAffine between the resize and the jitter / normalise (k_affine_u8, k_affine_norm) ----
+// workspace: the jitter forms' [horizontal intermediate | 8-bit image | grey sums] + a second 8-bit image.  The vertical pass writes the
+// second image, the warp reads it: with jitter into the first (where the jitter launches expect their input), without straight to `out`.
+size_t sd_preprocess_affine_workspace_bytes(int B, int Hin, int Win, int Hout, int Wout) {
+    return sd_preprocess_jitter_workspace_bytes(B, Hin, Win, Hout, Wout) + align_up((size_t)B * Hout * Wout * 3, 256);
+}
+
+static int affine_check(const char* what, int B, int Hin, int Win, int Hout, int Wout, const int* jitter_order, const float* jitter_factors,
+                        const double* affine, const uint8_t* fill3, size_t workspace_bytes) {
+    SD_REQUIRE(affine && fill3, SD_ERR_INVALID, "%s: null affine matrices or fill colour", what);
+    SD_REQUIRE((jitter_order == nullptr) == (jitter_factors == nullptr), SD_ERR_INVALID,
+               "%s: jitter_order and jitter_factors go together (both null = no jitter)", what);
+    SD_REQUIRE(B <= 65535, SD_ERR_INVALID, "%s: batch %d > 65535", what, B);
+    SD_REQUIRE(workspace_bytes >= sd_preprocess_affine_workspace_bytes(B, Hin, Win, Hout, Wout), SD_ERR_WORKSPACE, "%s: workspace %zu < %zu", what,
+               workspace_bytes, sd_preprocess_affine_workspace_bytes(B, Hin, Win, Hout, Wout));
+    return 0;
+}
+
+// the launches after the horizontal pass
+static int preprocess_affine_tail(int B, int Hin, int Win, int Hout, int Wout, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips,
+                                  const int* jitter_order, const float* jitter_factors, const double* affine, const uint8_t* fill3,
+                                  const float* mean3, const float* std3, float* out, uint8_t* tmp, hipStream_t st) {
+    uint8_t* img = tmp + sd_preprocess_workspace_bytes(B, Hin, Win, Wout);
+    unsigned long long* lsum = reinterpret_cast<unsigned long long*>(img + align_up((size_t)B * Hout * Wout * 3, 256));
+    uint8_t* resized = tmp + sd_preprocess_jitter_workspace_bytes(B, Hin, Win, Hout, Wout);
+    if (int e = resample_v_u8(B, Hin, Hout, Wout, v_bounds, v_kk, v_ksize, tmp, resized, st)) return e;
+    const dim3 grid(cdiv(Wout, AF_TX * AF_PX), cdiv(Hout, AF_TY), B);
+    if (!jitter_order) {
+        hipLaunchKernelGGL(k_affine_norm, grid, dim3(256), 0, st, resized, out, Hout, Wout, affine, (int)fill3[0], (int)fill3[1], (int)fill3[2], flips,
+                           mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
+        SD_LAUNCH_CHECK();
+        return 0;
+    }
+    hipLaunchKernelGGL(k_affine_u8, grid, dim3(256), 0, st, resized, img, Hout, Wout, affine, (int)fill3[0], (int)fill3[1], (int)fill3[2]);
+    SD_LAUNCH_CHECK();
+    return jitter_norm(B, Hout, Wout, flips, jitter_order, jitter_factors, mean3, std3, out, img, lsum, st);
+}
+
+int sd_preprocess_images_affine(const uint8_t* images, int B, int Hin, int Win, int Hout, int Wout, const int* h_bounds, const int* h_kk,
+                                int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips, const int* jitter_order,
+                                const float* jitter_factors, const double* affine, const uint8_t* fill3, const float* mean3, const float* std3,
+                                float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
+    if (int e = preprocess_check("sd_preprocess_images_affine", images, B, Hin, Win, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, mean3,
+                                 std3, out, workspace)) return e;
+    if (int e = affine_check("sd_preprocess_images_affine", B, Hin, Win, Hout, Wout, jitter_order, jitter_factors, affine, fill3, workspace_bytes))
+        return e;
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t* tmp = reinterpret_cast<uint8_t*>(workspace);
+    if (jitter_order) {
+        uint8_t* img = tmp + sd_preprocess_workspace_bytes(B, Hin, Win, Wout);
+        SD_HIP(hipMemsetAsync(img + align_up((size_t)B * Hout * Wout * 3, 256), 0, (size_t)B * 8, st));    // lsum
+    }
+    const int64_t rows = (int64_t)B * Hin;
+    hipLaunchKernelGGL(k_resample_h, dim3(cdiv(rows * Wout, 256)), dim3(256), 0, st, images, tmp, Hin, Win, Wout, h_bounds, h_kk, h_ksize, rows);
+    SD_LAUNCH_CHECK();
+    return preprocess_affine_tail(B, Hin, Win, Hout, Wout, v_bounds, v_kk, v_ksize, flips, jitter_order, jitter_factors, affine, fill3, mean3, std3,
+                                  out, tmp, st);
+}
+
+int sd_preprocess_images_list_affine(const uint8_t* const* images, int B, int Hin, int Win, int Hout, int Wout, const int* h_bounds,
+                                     const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips,
+                                     const int* jitter_order, const float* jitter_factors, const double* affine, const uint8_t* fill3,
+                                     const float* mean3, const float* std3, float* out, void* workspace, size_t workspace_bytes,
+                                     sd_stream_t stream) {
+    int rpb = 0, bpi = 0;
+    if (int e = preprocess_list_check("sd_preprocess_images_list_affine", images, B, Hin, Win, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk,
+                                      v_ksize, mean3, std3, out, workspace, &rpb, &bpi)) return e;
+    if (int e = affine_check("sd_preprocess_images_list_affine", B, Hin, Win, Hout, Wout, jitter_order, jitter_factors, affine, fill3,
+                             workspace_bytes)) return e;
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t* tmp = reinterpret_cast<uint8_t*>(workspace);
+    if (jitter_order) {
+        uint8_t* img = tmp + sd_preprocess_workspace_bytes(B, Hin, Win, Wout);
+        SD_HIP(hipMemsetAsync(img + align_up((size_t)B * Hout * Wout * 3, 256), 0, (size_t)B * 8, st));    // lsum
+    }
+    if (int e = resample_h_list(images, tmp, B, Hin, Win, Wout, h_bounds, h_kk, h_ksize, rpb, bpi, st)) return e;
+    return preprocess_affine_tail(B, Hin, Win, Hout, Wout, v_bounds, v_kk, v_ksize, flips, jitter_order, jitter_factors, affine, fill3, mean3, std3,
+                                  out, tmp, st);
 }
 
 }  // extern "C"

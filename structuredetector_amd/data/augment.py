@@ -11,6 +11,10 @@ Color plus an HSV round trip for the hue, in a random order; `sd_preprocess_imag
 resized image (oracle/pil_photometric.py is the restatement, pinned against Pillow over all 2^24 colours; torchvision itself is absent
 here, its PIL code path is restated from the published 0.20.1 source), so with the same random draws the normalised tensor equals the
 reference's bit for bit.  The random draws come from torch's global generator on the host (TrainAugmentation.draws_for).
+Random affine (`--aug_rotate / --aug_scale / --aug_translate`; not in the reference): where torchvision's RandomAffine would sit, between
+Resize and ColorJitter, as Pillow's `Image.transform(size, AFFINE, matrix, BILINEAR, fillcolor=_FILL)` byte for byte
+(`sd_preprocess_images_affine`); the matrices are built on the host (`affine_inverse_matrix`), the annotations follow with
+`utils.misc.affine_annotation`, which drops what leaves the frame.
 """
 from __future__ import annotations
 
@@ -21,11 +25,12 @@ import numpy as np
 import torch
 
 from .. import _lib as L
-from ..utils.misc import clip_annotation, hflip_annotation, vflip_annotation
+from ..utils.misc import affine_annotation, clip_annotation, hflip_annotation, vflip_annotation
 
 PRECISION_BITS = 32 - 8 - 2
 _MEAN = (0.485, 0.456, 0.406)
 _STD = (0.229, 0.224, 0.225)
+_FILL = (124, 116, 104)          # what the affine warp leaves uncovered: the ImageNet mean in bytes (about 0 after Normalize)
 
 
 def pil_bilinear_coeffs(in_size: int, out_size: int):
@@ -86,10 +91,46 @@ class _Tables:
 _tables = _Tables()
 
 
-def preprocess_images(images: torch.Tensor, out_size, flips=None, mean=_MEAN, std=_STD, jitter=None) -> torch.Tensor:
+def affine_inverse_matrix(size, angle, scale, translate):
+    """torchvision's `_get_inverse_affine_matrix` with shear 0 about the image centre, in plain Python floats (C doubles): the six
+    coefficients Pillow's `Image.transform(size, AFFINE, m, ...)` takes, mapping an OUTPUT pixel centre to its source position.
+    size = (width, height), angle in degrees, translate = (tx, ty) in pixels.  Angle 0, scale 1, no shift: exactly [1, 0, 0, 0, 1, 0]."""
+    w, h = size
+    tx, ty = translate
+    rot = math.radians(angle)
+    cx, cy = w * 0.5, h * 0.5
+    a, b, c, d = math.cos(rot), -math.sin(rot), math.sin(rot), math.cos(rot)
+    m = [d / scale, -b / scale, 0.0, -c / scale, a / scale, 0.0]
+    m[2] += m[0] * (-cx - tx) + m[1] * (-cy - ty)
+    m[5] += m[3] * (-cx - tx) + m[4] * (-cy - ty)
+    m[2] += cx
+    m[5] += cy
+    return m
+
+
+def affine_forward_matrix(size, angle, scale, translate):
+    """The forward twin of `affine_inverse_matrix` (source position -> output position, both as pixel centres): what the annotations
+    follow (`affine_annotation`).  out = scale * R(angle) * (in - centre) + centre + translate."""
+    w, h = size
+    tx, ty = translate
+    rot = math.radians(angle)
+    cx, cy = w * 0.5, h * 0.5
+    a, b, c, d = scale * math.cos(rot), -scale * math.sin(rot), scale * math.sin(rot), scale * math.cos(rot)
+    return [a, b, cx + tx - (a * cx + b * cy), c, d, cy + ty - (c * cx + d * cy)]
+
+
+def _affine_rows(affine, B, device):
+    rows = torch.as_tensor(np.asarray(affine, dtype=np.float64)).reshape(-1, 6).contiguous()
+    if rows.shape[0] != B:
+        raise L.SdError("affine must have one row of 6 coefficients per image")
+    return rows.to(device, non_blocking=True)
+
+
+def preprocess_images(images: torch.Tensor, out_size, flips=None, mean=_MEAN, std=_STD, jitter=None, affine=None) -> torch.Tensor:
     """images: (B, Hin, Win, 3) uint8 on the GPU; out_size = (width, height); flips: (B,) uint8 (bit 0 horizontal, bit 1 vertical)
-    or None; jitter: None or (order words (B,) int32, factors (B, 3) fp32) as `jitter_words` makes them.
-    Returns (B, 3, height, width) fp32 = Normalize(to_tensor(flip(jitter(resize(image))))) of transforms.py:217-226."""
+    or None; jitter: None or (order words (B,) int32, factors (B, 3) fp32) as `jitter_words` makes them; affine: None or B rows of the 6
+    coefficients of `affine_inverse_matrix` at out_size (the warp runs on the resized image, in front of the jitter, fill `_FILL`).
+    Returns (B, 3, height, width) fp32 = Normalize(to_tensor(flip(jitter(affine(resize(image)))))) of transforms.py:217-226."""
     L.require_cuda(images)
     if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3:
         raise L.SdError(f"preprocess_images expects (B, H, W, 3) uint8, got {tuple(images.shape)} {images.dtype}")
@@ -106,11 +147,22 @@ def preprocess_images(images: torch.Tensor, out_size, flips=None, mean=_MEAN, st
         if fl.numel() != B:
             raise L.SdError("flips must have one entry per image")
     m3, s3 = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
+    order = factors = None
     if jitter is not None:
         order = torch.as_tensor(jitter[0], dtype=torch.int32).to(images.device, non_blocking=True)
         factors = torch.as_tensor(jitter[1], dtype=torch.float32).reshape(-1, 3).contiguous().to(images.device, non_blocking=True)
         if order.numel() != B or factors.shape[0] != B:
             raise L.SdError("jitter parameters must have one row per image")
+    if affine is not None:
+        rows = _affine_rows(affine, B, images.device)
+        ws = L.workspace(lib.sd_preprocess_affine_workspace_bytes(B, Hin, Win, Hout, Wout), images.device)
+        L.check(lib.sd_preprocess_images_affine(images.data_ptr(), B, Hin, Win, Hout, Wout, hb.data_ptr(), hk.data_ptr(), hks, vb.data_ptr(),
+                                                vk.data_ptr(), vks, fl.data_ptr() if fl is not None else 0,
+                                                order.data_ptr() if order is not None else 0, factors.data_ptr() if factors is not None else 0,
+                                                rows.data_ptr(), (C.c_ubyte * 3)(*_FILL), m3, s3, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                L.stream()), "sd_preprocess_images_affine")
+        return out
+    if jitter is not None:
         ws = L.workspace(lib.sd_preprocess_jitter_workspace_bytes(B, Hin, Win, Hout, Wout), images.device)
         L.check(lib.sd_preprocess_images_jitter(images.data_ptr(), B, Hin, Win, Hout, Wout, hb.data_ptr(), hk.data_ptr(), hks, vb.data_ptr(),
                                                 vk.data_ptr(), vks, fl.data_ptr() if fl is not None else 0, order.data_ptr(), factors.data_ptr(),
@@ -123,7 +175,8 @@ def preprocess_images(images: torch.Tensor, out_size, flips=None, mean=_MEAN, st
     return out
 
 
-def preprocess_image_list(pointers: torch.Tensor, hin: int, win: int, out_size, flips=None, mean=_MEAN, std=_STD, jitter=None) -> torch.Tensor:
+def preprocess_image_list(pointers: torch.Tensor, hin: int, win: int, out_size, flips=None, mean=_MEAN, std=_STD, jitter=None,
+                          affine=None) -> torch.Tensor:
     """`preprocess_images` over B images that are not packed together: pointers is a (B,) int64 DEVICE tensor of the device addresses of
     B (hin, win, 3) uint8 images (any byte alignment; the caller keeps them alive until the work on the current stream is done), e.g. entries
     of data/image_cache.py's DeviceImageCache.  Same arguments otherwise, same output bytes as `preprocess_images` on the stacked images."""
@@ -144,11 +197,23 @@ def preprocess_image_list(pointers: torch.Tensor, hin: int, win: int, out_size, 
         if fl.numel() != B:
             raise L.SdError("flips must have one entry per image")
     m3, s3 = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
+    order = factors = None
     if jitter is not None:
         order = torch.as_tensor(jitter[0], dtype=torch.int32).to(dev, non_blocking=True)
         factors = torch.as_tensor(jitter[1], dtype=torch.float32).reshape(-1, 3).contiguous().to(dev, non_blocking=True)
         if order.numel() != B or factors.shape[0] != B:
             raise L.SdError("jitter parameters must have one row per image")
+    if affine is not None:
+        rows = _affine_rows(affine, B, dev)
+        ws = L.workspace(lib.sd_preprocess_affine_workspace_bytes(B, Hin, Win, Hout, Wout), dev)
+        L.check(lib.sd_preprocess_images_list_affine(pointers.data_ptr(), B, Hin, Win, Hout, Wout, hb.data_ptr(), hk.data_ptr(), hks, vb.data_ptr(),
+                                                     vk.data_ptr(), vks, fl.data_ptr() if fl is not None else 0,
+                                                     order.data_ptr() if order is not None else 0,
+                                                     factors.data_ptr() if factors is not None else 0, rows.data_ptr(),
+                                                     (C.c_ubyte * 3)(*_FILL), m3, s3, out.data_ptr(), ws.data_ptr(), ws.numel(), L.stream()),
+                "sd_preprocess_images_list_affine")
+        return out
+    if jitter is not None:
         ws = L.workspace(lib.sd_preprocess_jitter_workspace_bytes(B, Hin, Win, Hout, Wout), dev)
         L.check(lib.sd_preprocess_images_list_jitter(pointers.data_ptr(), B, Hin, Win, Hout, Wout, hb.data_ptr(), hk.data_ptr(), hks, vb.data_ptr(),
                                                      vk.data_ptr(), vks, fl.data_ptr() if fl is not None else 0, order.data_ptr(), factors.data_ptr(),
@@ -180,6 +245,10 @@ class ValidationAugmentation:
         """(flips, jitter) for n samples: validation draws nothing."""
         return None, None
 
+    def affine_draws_for(self, n):
+        """(angle, scale, tx, ty) per sample, or None: validation never warps and never draws."""
+        return None
+
     def __call__(self, images, annotations):
         """images: list of (H, W, 3) uint8 arrays / tensors (any sizes) or one (B, H, W, 3) tensor; annotations: list of
         ImageAnnotation in ORIGINAL image pixels (modified in place like the reference's Resize / flips / Encode clip do on their
@@ -198,14 +267,17 @@ class ValidationAugmentation:
             groups = {k: ([i for i, _ in v], torch.stack([t for _, t in v])) for k, v in by_size.items()}
         n = sum(len(idx) for idx, _ in groups.values())
         flips, jitter = self.draws_for(n)
+        warps = self.affine_draws_for(n)
+        inverse = None if warps is None else [affine_inverse_matrix((W, H), a, s, (tx, ty)) for a, s, tx, ty in warps]
         out = torch.empty((n, 3, H, W), dtype=torch.float32, device=dev)
         for (hin, win), (idx, stack) in groups.items():
             f = None if flips is None else [flips[i] for i in idx]
             j = None if jitter is None else ([jitter[0][i] for i in idx], [jitter[1][i] for i in idx])
+            m = None if inverse is None else [inverse[i] for i in idx]
             if hasattr(stack, "pointers"):                           # data/image_cache.py ImageList: cached / uploaded images by address
-                res = preprocess_image_list(stack.pointers, hin, win, (W, H), f, jitter=j)
+                res = preprocess_image_list(stack.pointers, hin, win, (W, H), f, jitter=j, affine=m)
             else:
-                res = preprocess_images(stack.to(dev, non_blocking=True), (W, H), f, jitter=j)
+                res = preprocess_images(stack.to(dev, non_blocking=True), (W, H), f, jitter=j, affine=m)
             if len(groups) == 1:
                 out = res
             else:
@@ -214,6 +286,9 @@ class ValidationAugmentation:
                 ann = annotations[i]
                 ann.img_size = ann.img_size or (win, hin)
                 ann.resize((win, hin), (W, H))                       # transforms.py:58
+                if warps is not None:                                # on the resized image, before the flips: drops what leaves the frame
+                    a, s, tx, ty = warps[i]
+                    affine_annotation(ann, affine_forward_matrix((W, H), a, s, (tx, ty)), (W, H))
                 if flips is not None and flips[i] & 1:
                     hflip_annotation(ann, (W, H))                    # transforms.py:15 (on the resized image)
                 if flips is not None and flips[i] & 2:
@@ -237,6 +312,9 @@ class TrainAugmentation(ValidationAugmentation):
     def __init__(self, args, prob=0.5):
         super().__init__(args)
         self.prob = prob
+        self.rotate = float(getattr(args, "aug_rotate", 0.0))              # degrees: angle uniform in [-rotate, rotate]
+        self.scale = float(getattr(args, "aug_scale", 0.0))                # scale uniform in [1 - scale, 1 + scale]
+        self.translate = float(getattr(args, "aug_translate", 0.0))        # shift uniform in [-translate, translate] * (width, height)
 
     def draws_for(self, n):
         """(flips, jitter) of n samples from torch's global generator, in THREE vectorised draws per batch: per-sample tiny tensor ops
@@ -258,6 +336,18 @@ class TrainAugmentation(ValidationAugmentation):
             w, f3 = jitter_words(order, b, c, s_, h)
             words.append(w); factors.append(f3)
         return flip_bits, (words, factors)
+
+    def affine_draws_for(self, n):
+        """(angle, scale, tx, ty) of n samples (torchvision RandomAffine.get_params' distributions, the shift left unrounded) from ONE more
+        draw on torch's global generator, made after those of `draws_for`; None, and no draw at all, when the three ranges are 0 or
+        augmentation is off.  The shift range follows the current multi-scale size."""
+        if self.args.no_augmentation or (self.rotate == 0 and self.scale == 0 and self.translate == 0):
+            return None
+        W, H = self.size
+        u = torch.rand(n, 4, dtype=torch.float64)
+        lo = torch.tensor([-self.rotate, 1 - self.scale, -self.translate * W, -self.translate * H], dtype=torch.float64)
+        hi = torch.tensor([self.rotate, 1 + self.scale, self.translate * W, self.translate * H], dtype=torch.float64)
+        return [tuple(r) for r in (lo + (hi - lo) * u).tolist()]
 
     def trigger_random_resize(self):
         if self.args.no_augmentation:

@@ -70,6 +70,13 @@ _FLAGS = [
                       "detect / Predictor: the network also runs on the mirrored image(s) (2 views for hflip and vflip, 4 for hvflip: the "
                       "forward sees that many times --eval_batch images), the heatmaps are averaged and decoded once. Not consulted by "
                       "train: its validation pass computes the loss from the plain head output.")),
+    (("--aug_rotate",), dict(type=float, default=0.0, metavar="DEG", help="Training augmentation: rotate every image about its centre by an "
+                             "angle uniform in [-DEG, DEG] (0 .. 180; what leaves the frame is dropped from the annotation, what the image does "
+                             "not cover is filled with the ImageNet mean; 0 = off). Not consulted by evaluate / detect.")),
+    (("--aug_scale",), dict(type=float, default=0.0, metavar="S", help="Training augmentation: zoom every image about its centre by a factor "
+                            "uniform in [1 - S, 1 + S] (0 <= S < 1; 0 = off). Not consulted by evaluate / detect.")),
+    (("--aug_translate",), dict(type=float, default=0.0, metavar="T", help="Training augmentation: shift every image by a fraction of its width "
+                                "and height uniform in [-T, T] (0 .. 0.5; 0 = off). Not consulted by evaluate / detect.")),
 ]
 
 _POSITIVE = ["in_channels", "fpn_depth", "batch_size", "epochs", "learning_rate", "down_ratio", "max_objects", "max_parts"]
@@ -101,6 +108,9 @@ def finalize(args):
     for k in ("weight_decay", "clip_grad_norm", "ema_decay"):
         assert getattr(args, k, 0.0) >= 0, f"'{k}' should be greater than or equal to 0"
     assert getattr(args, "ema_decay", 0.0) < 1, "'ema_decay' should be less than 1"
+    assert 0 <= getattr(args, "aug_rotate", 0.0) <= 180, "'aug_rotate' should be in [0, 180]"
+    assert 0 <= getattr(args, "aug_scale", 0.0) < 1, "'aug_scale' should be in [0, 1["
+    assert 0 <= getattr(args, "aug_translate", 0.0) <= 0.5, "'aug_translate' should be in [0, 0.5]"
 
     args.lr_step = int(args.epochs / args.lr_step) if args.lr_step != 0 else args.epochs
     for k in ("train_dir", "valid_dir", "pretrained_model"):

@@ -55,6 +55,42 @@ def vflip_annotation(annotation, img_size):
     return annotation
 
 
+def affine_annotation(annotation, forward_matrix, img_size):
+    """Follow an affine warp of the image (data/augment.py: affine_forward_matrix), in place.  A pixel index p is the pixel centre p + 0.5
+    -- the convention under which hflip_annotation's w - x - 1 holds -- so p' + 0.5 = F (p + 0.5); coordinates stay floats.  Unlike a flip, a
+    warp can move points out of the frame, where clip_annotation would pin them to the border as false keypoints: they are dropped, by
+    the warp's own inside test 0 <= x' + 0.5 < w and 0 <= y' + 0.5 < h.  An object whose anchor leaves goes with all its parts; a part that
+    leaves is removed from its object; a box becomes the axis-aligned hull of its four corners (clip_annotation clips it later)."""
+    w, h = img_size
+    f0, f1, f2, f3, f4, f5 = forward_matrix
+
+    def move(x, y):
+        xc, yc = x + 0.5, y + 0.5
+        return f0 * xc + f1 * yc + f2 - 0.5, f3 * xc + f4 * yc + f5 - 0.5
+
+    def inside(x, y):
+        return 0 <= x + 0.5 < w and 0 <= y + 0.5 < h
+
+    kept = []
+    for obj in annotation.objects:
+        obj.x, obj.y = move(obj.x, obj.y)
+        if not inside(obj.x, obj.y):
+            continue
+        parts = []
+        for p in obj.parts:
+            p.x, p.y = move(p.x, p.y)
+            if inside(p.x, p.y):
+                parts.append(p)
+        obj.parts = parts
+        if obj.box is not None:
+            b = obj.box
+            xs, ys = zip(*(move(x, y) for x in (b.x_min, b.x_max) for y in (b.y_min, b.y_max)))
+            b.x_min, b.x_max, b.y_min, b.y_max = min(xs), max(xs), min(ys), max(ys)
+        kept.append(obj)
+    annotation.objects = kept
+    return annotation
+
+
 def get_unique_color_map(labels):
     """utils.py:476-479: a stable RGB triple per name (first three bytes of its xxh64 digest)."""
     from xxhash import xxh64_digest
