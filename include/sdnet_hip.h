@@ -270,6 +270,27 @@ int sd_preprocess_images_list_affine(const uint8_t* const* images, int B, int Hi
                                      const float* mean3, const float* std3, float* out, void* workspace, size_t workspace_bytes,
                                      sd_stream_t stream);
 
+/* Both pipelines with a mosaic (four images of the batch per sample) composed on the device from the RESIZED images, in front of the
+ * warp: Resize -> Mosaic -> [RandomAffine] -> [ColorJitter] -> flips -> Normalize.  mosaic_geom (B, 6) int32 on the DEVICE = per image
+ * cx, cy, s0, s1, s2, s3: output pixel (x, y) lies in quadrant q = (x >= cx) + 2 (y >= cy) and takes, byte for byte,
+ * Image.transform((Wout, Hout), AFFINE, m_q, BILINEAR, fillcolor = fill3) of resized image s_q at (x, y); mosaic_affine (B, 4, 6) fp64
+ * on the DEVICE = the four inverse matrices m_0 .. m_3 per image, in the convention of `affine` above.  Any matrices and any centre in
+ * [0, Wout] x [0, Hout] are legal; the tables cannot be checked without a sync, so the kernels clamp cx, cy to that range and s_q to
+ * [0, B): any table is memory-safe.  A row (Wout, Hout, b, -, -, -) with m_0 the identity copies image b.  affine: as above, or null
+ * for no warp; jitter_order / jitter_factors: both set or both null (one alone, a null table or fill3: SD_ERR_INVALID).  The contrast
+ * op's grey mean is taken over the composed (and warped) image.  workspace: sd_preprocess_mosaic_workspace_bytes() bytes in every case. */
+size_t sd_preprocess_mosaic_workspace_bytes(int B, int Hin, int Win, int Hout, int Wout);
+int sd_preprocess_images_mosaic(const uint8_t* images, int B, int Hin, int Win, int Hout, int Wout, const int* h_bounds, const int* h_kk,
+                                int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips, const int* jitter_order,
+                                const float* jitter_factors, const double* affine, const int* mosaic_geom, const double* mosaic_affine,
+                                const uint8_t fill3[3], const float* mean3, const float* std3, float* out, void* workspace,
+                                size_t workspace_bytes, sd_stream_t stream);
+int sd_preprocess_images_list_mosaic(const uint8_t* const* images, int B, int Hin, int Win, int Hout, int Wout, const int* h_bounds,
+                                     const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips,
+                                     const int* jitter_order, const float* jitter_factors, const double* affine, const int* mosaic_geom,
+                                     const double* mosaic_affine, const uint8_t fill3[3], const float* mean3, const float* std3, float* out,
+                                     void* workspace, size_t workspace_bytes, sd_stream_t stream);
+
 /* ---- loss: src/sdnet/model/loss.py:17-64,91-117 ------------------------------------------- */
 
 #define SD_HM_MSE   0

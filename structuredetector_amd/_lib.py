@@ -91,6 +91,13 @@ _SIGNATURES = {
                                             C.POINTER(c_float), C.POINTER(c_float), c_vp, c_vp, c_size, c_vp]),
     "sd_preprocess_images_list_affine": (c_int, [c_vp] + [c_int] * 5 + [c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, C.POINTER(C.c_ubyte),
                                                  C.POINTER(c_float), C.POINTER(c_float), c_vp, c_vp, c_size, c_vp]),
+    # mosaic in front of the warp: ..., jitter_factors, affine (null: no warp), mosaic_geom (B, 6) int32 device, mosaic_affine (B, 4, 6) fp64
+    # device, fill3 (HOST), mean3, std3, out, workspace, bytes, stream
+    "sd_preprocess_mosaic_workspace_bytes": (c_size, [c_int] * 5),
+    "sd_preprocess_images_mosaic": (c_int, [c_vp] + [c_int] * 5 + [c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                            C.POINTER(C.c_ubyte), C.POINTER(c_float), C.POINTER(c_float), c_vp, c_vp, c_size, c_vp]),
+    "sd_preprocess_images_list_mosaic": (c_int, [c_vp] + [c_int] * 5 + [c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                 C.POINTER(C.c_ubyte), C.POINTER(c_float), C.POINTER(c_float), c_vp, c_vp, c_size, c_vp]),
     "sd_render_targets": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_float, c_vp, c_vp]),
     "sd_loss_workspace_bytes": (c_size, [c_int] * 5),
     "sd_loss_fwd": (c_int, [C.POINTER(LossDesc), c_vp, c_vp, c_size, c_vp]),

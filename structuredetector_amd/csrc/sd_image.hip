@@ -407,6 +407,117 @@ __global__ __launch_bounds__(256) void k_affine_norm(const uint8_t* __restrict__
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Mosaic (four images per sample) on the RESIZED 8-bit images, in front of the warp: the canvas of image b is cut at a centre (cx, cy)
+// into four quadrants q = (x >= cx) + 2 (y >= cy), and quadrant q shows image s_q of the same batch under its own inverse matrix m_q --
+// per pixel exactly Image.transform((W, H), AFFINE, m_q, BILINEAR, fillcolor) of resized[s_q] read at (x, y), i.e. affine_pixel on the
+// canvas pixel centre.  geom (B, 6) int32 = cx, cy, s_0 .. s_3 and maffine (B, 4, 6) fp64 live on the device and cannot be checked by the
+// host without a sync: cx, cy are clamped to [0, W], [0, H] and s_q to [0, B), so any table is memory-safe.  The launch shape of the
+// affine kernels; a block whose 64 x 16 tile lies inside one quadrant (all but the one row and one column of blocks the centre cuts)
+// loads its one matrix once and runs the affine kernels' loop, a straddling block selects source and matrix per pixel.  The sources are
+// other images of the batch: never in place.
+// ---------------------------------------------------------------------------------------------------------------------------------
+struct MosaicGeom { int cx, cy, s0, s1, s2, s3; };
+
+__device__ __forceinline__ MosaicGeom mosaic_geom_of(const int* __restrict__ geom, int b, int B, int H, int W) {
+    const int* g = geom + 6 * (int64_t)b;
+    return MosaicGeom{min(max(g[0], 0), W), min(max(g[1], 0), H), min(max(g[2], 0), B - 1), min(max(g[3], 0), B - 1),
+                      min(max(g[4], 0), B - 1), min(max(g[5], 0), B - 1)};
+}
+__device__ __forceinline__ int mosaic_source(const MosaicGeom& g, int q) { return q == 0 ? g.s0 : (q == 1 ? g.s1 : (q == 2 ? g.s2 : g.s3)); }
+
+// what a block needs to produce pixels: `uniform` = its whole tile lies in quadrant q0 (src / m are that quadrant's), else per pixel
+struct MosaicTile {
+    MosaicGeom g;
+    bool uniform;
+    const uint8_t* src;
+    Affine6 m;
+};
+
+__device__ __forceinline__ MosaicTile mosaic_tile(const uint8_t* __restrict__ img, const int* __restrict__ geom,
+                                                  const double* __restrict__ maffine, int b, int B, int H, int W) {
+    MosaicTile t;
+    t.g = mosaic_geom_of(geom, b, B, H, W);
+    const int bx0 = blockIdx.x * AF_TX * AF_PX, by0 = blockIdx.y * AF_TY;
+    t.uniform = (t.g.cx <= bx0 || t.g.cx >= bx0 + AF_TX * AF_PX) && (t.g.cy <= by0 || t.g.cy >= by0 + AF_TY);
+    const int q0 = (bx0 >= t.g.cx ? 1 : 0) + (by0 >= t.g.cy ? 2 : 0);     // the quadrant of the tile's first pixel (the tile's, when uniform)
+    t.src = img + (int64_t)mosaic_source(t.g, q0) * H * W * 3;
+    t.m = affine_of(maffine, 4 * b + q0);
+    return t;
+}
+
+__device__ __forceinline__ Rgb8 mosaic_pixel(const MosaicTile& t, const uint8_t* __restrict__ img, const double* __restrict__ maffine, int b,
+                                             int H, int W, int x, int y, const Rgb8& fill) {
+    if (t.uniform) return affine_pixel(t.src, H, W, t.m, x, y, fill);
+    const int q = (x >= t.g.cx ? 1 : 0) + (y >= t.g.cy ? 2 : 0);
+    return affine_pixel(img + (int64_t)mosaic_source(t.g, q) * H * W * 3, H, W, affine_of(maffine, 4 * b + q), x, y, fill);
+}
+
+// img (B, H, W, 3) u8 -> out (B, H, W, 3) u8 (another buffer).  grid (cdiv(W, 64), cdiv(H, 16), B)
+__global__ __launch_bounds__(256) void k_mosaic_u8(const uint8_t* __restrict__ img, uint8_t* __restrict__ out, int H, int W,
+                                                    const int* __restrict__ geom, const double* __restrict__ maffine, int f0, int f1, int f2) {
+    const int b = blockIdx.z, B = gridDim.z;
+    const int x = (blockIdx.x * AF_TX + (threadIdx.x % AF_TX)) * AF_PX, y = blockIdx.y * AF_TY + threadIdx.x / AF_TX;
+    if (x >= W || y >= H) return;
+    const MosaicTile t = mosaic_tile(img, geom, maffine, b, B, H, W);
+    const Rgb8 fill{f0, f1, f2};
+    uint8_t* dst = out + (((int64_t)b * H + y) * W + x) * 3;
+    if ((W & 3) == 0) {                                                  // four pixels = three aligned dwords
+        Rgb8 c[AF_PX];
+#pragma unroll
+        for (int k = 0; k < AF_PX; ++k) c[k] = mosaic_pixel(t, img, maffine, b, H, W, x + k, y, fill);
+        uint32_t* d = reinterpret_cast<uint32_t*>(dst);
+        d[0] = (uint32_t)c[0].r | (uint32_t)c[0].g << 8 | (uint32_t)c[0].b << 16 | (uint32_t)c[1].r << 24;
+        d[1] = (uint32_t)c[1].g | (uint32_t)c[1].b << 8 | (uint32_t)c[2].r << 16 | (uint32_t)c[2].g << 24;
+        d[2] = (uint32_t)c[2].b | (uint32_t)c[3].r << 8 | (uint32_t)c[3].g << 16 | (uint32_t)c[3].b << 24;
+    } else {
+        for (int k = 0; k < AF_PX && x + k < W; ++k) {
+            const Rgb8 c = mosaic_pixel(t, img, maffine, b, H, W, x + k, y, fill);
+            dst[3 * k] = (uint8_t)c.r; dst[3 * k + 1] = (uint8_t)c.g; dst[3 * k + 2] = (uint8_t)c.b;
+        }
+    }
+}
+
+// the same gather + flips + to_tensor + Normalize: img (B, H, W, 3) u8 -> out (B, 3, H, W) fp32 NCHW (the chain with neither warp nor jitter);
+// the store of k_affine_norm
+__global__ __launch_bounds__(256) void k_mosaic_norm(const uint8_t* __restrict__ img, float* __restrict__ out, int H, int W,
+                                                      const int* __restrict__ geom, const double* __restrict__ maffine, int f0, int f1, int f2,
+                                                      const uint8_t* __restrict__ flips, float m0, float m1, float m2, float d0, float d1,
+                                                      float d2) {
+    const int b = blockIdx.z, B = gridDim.z;
+    const int x = (blockIdx.x * AF_TX + (threadIdx.x % AF_TX)) * AF_PX, y = blockIdx.y * AF_TY + threadIdx.x / AF_TX;
+    if (x >= W || y >= H) return;
+    const MosaicTile t = mosaic_tile(img, geom, maffine, b, B, H, W);
+    const Rgb8 fill{f0, f1, f2};
+    const int f = flips ? flips[b] : 0;
+    const int oy = (f & 2) ? H - 1 - y : y;
+    const int64_t plane = (int64_t)H * W;
+    float* o = out + (int64_t)b * 3 * plane + (int64_t)oy * W;
+    if ((W & 3) == 0) {
+        float r[AF_PX], g[AF_PX], bl[AF_PX];
+#pragma unroll
+        for (int k = 0; k < AF_PX; ++k) {
+            const Rgb8 c = mosaic_pixel(t, img, maffine, b, H, W, x + k, y, fill);
+            const int j = (f & 1) ? AF_PX - 1 - k : k;
+            r[j] = ((float)c.r / 255.0f - m0) / d0;
+            g[j] = ((float)c.g / 255.0f - m1) / d1;
+            bl[j] = ((float)c.b / 255.0f - m2) / d2;
+        }
+        const int ox = (f & 1) ? W - AF_PX - x : x;
+        *reinterpret_cast<float4*>(o + ox) = make_float4(r[0], r[1], r[2], r[3]);
+        *reinterpret_cast<float4*>(o + plane + ox) = make_float4(g[0], g[1], g[2], g[3]);
+        *reinterpret_cast<float4*>(o + 2 * plane + ox) = make_float4(bl[0], bl[1], bl[2], bl[3]);
+    } else {
+        for (int k = 0; k < AF_PX && x + k < W; ++k) {
+            const Rgb8 c = mosaic_pixel(t, img, maffine, b, H, W, x + k, y, fill);
+            const int ox = (f & 1) ? W - 1 - (x + k) : x + k;
+            o[ox] = ((float)c.r / 255.0f - m0) / d0;
+            o[plane + ox] = ((float)c.g / 255.0f - m1) / d1;
+            o[2 * plane + ox] = ((float)c.b / 255.0f - m2) / d2;
+        }
+    }
+}
+
 }  // namespace sd
 
 using namespace sd;
@@ -636,6 +747,102 @@ int sd_preprocess_images_list_affine(const uint8_t* const* images, int B, int Hi
     if (int e = resample_h_list(images, tmp, B, Hin, Win, Wout, h_bounds, h_kk, h_ksize, rpb, bpi, st)) return e;
     return preprocess_affine_tail(B, Hin, Win, Hout, Wout, v_bounds, v_kk, v_ksize, flips, jitter_order, jitter_factors, affine, fill3, mean3, std3,
                                   out, tmp, st);
+}
+
+// ---- Mosaic between the resize and the warp / jitter / normalise (k_mosaic_u8, k_mosaic_norm) ----
+// workspace: that of the affine forms, [horizontal intermediate | 8-bit image A | grey sums | 8-bit image B].  The jitter launches read A, so
+// the 8-bit stages are laid out backwards from there: without a warp the vertical pass writes B and the mosaic A (or `out`, fused); with a
+// warp the vertical pass writes A, the mosaic B, and the warp A again (or `out`, fused) -- A's resized bytes are dead by then.
+size_t sd_preprocess_mosaic_workspace_bytes(int B, int Hin, int Win, int Hout, int Wout) {
+    return sd_preprocess_affine_workspace_bytes(B, Hin, Win, Hout, Wout);
+}
+
+static int mosaic_check(const char* what, int B, int Hin, int Win, int Hout, int Wout, const int* jitter_order, const float* jitter_factors,
+                        const int* mosaic_geom, const double* mosaic_affine, const uint8_t* fill3, size_t workspace_bytes) {
+    SD_REQUIRE(mosaic_geom && mosaic_affine && fill3, SD_ERR_INVALID, "%s: null mosaic tables or fill colour", what);
+    SD_REQUIRE((jitter_order == nullptr) == (jitter_factors == nullptr), SD_ERR_INVALID,
+               "%s: jitter_order and jitter_factors go together (both null = no jitter)", what);
+    SD_REQUIRE(B <= 65535, SD_ERR_INVALID, "%s: batch %d > 65535", what, B);
+    SD_REQUIRE(workspace_bytes >= sd_preprocess_mosaic_workspace_bytes(B, Hin, Win, Hout, Wout), SD_ERR_WORKSPACE, "%s: workspace %zu < %zu", what,
+               workspace_bytes, sd_preprocess_mosaic_workspace_bytes(B, Hin, Win, Hout, Wout));
+    return 0;
+}
+
+// the launches after the horizontal pass
+static int preprocess_mosaic_tail(int B, int Hin, int Win, int Hout, int Wout, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips,
+                                  const int* jitter_order, const float* jitter_factors, const double* affine, const int* mosaic_geom,
+                                  const double* mosaic_affine, const uint8_t* fill3, const float* mean3, const float* std3, float* out,
+                                  uint8_t* tmp, hipStream_t st) {
+    uint8_t* img_a = tmp + sd_preprocess_workspace_bytes(B, Hin, Win, Wout);
+    unsigned long long* lsum = reinterpret_cast<unsigned long long*>(img_a + align_up((size_t)B * Hout * Wout * 3, 256));
+    uint8_t* img_b = tmp + sd_preprocess_jitter_workspace_bytes(B, Hin, Win, Hout, Wout);
+    uint8_t* resized = affine ? img_a : img_b;
+    uint8_t* mosaic = affine ? img_b : img_a;
+    const int f0 = fill3[0], f1 = fill3[1], f2 = fill3[2];
+    if (int e = resample_v_u8(B, Hin, Hout, Wout, v_bounds, v_kk, v_ksize, tmp, resized, st)) return e;
+    const dim3 grid(cdiv(Wout, AF_TX * AF_PX), cdiv(Hout, AF_TY), B);
+    if (!affine && !jitter_order) {
+        hipLaunchKernelGGL(k_mosaic_norm, grid, dim3(256), 0, st, resized, out, Hout, Wout, mosaic_geom, mosaic_affine, f0, f1, f2, flips, mean3[0],
+                           mean3[1], mean3[2], std3[0], std3[1], std3[2]);
+        SD_LAUNCH_CHECK();
+        return 0;
+    }
+    hipLaunchKernelGGL(k_mosaic_u8, grid, dim3(256), 0, st, resized, mosaic, Hout, Wout, mosaic_geom, mosaic_affine, f0, f1, f2);
+    SD_LAUNCH_CHECK();
+    if (affine && !jitter_order) {
+        hipLaunchKernelGGL(k_affine_norm, grid, dim3(256), 0, st, mosaic, out, Hout, Wout, affine, f0, f1, f2, flips, mean3[0], mean3[1], mean3[2],
+                           std3[0], std3[1], std3[2]);
+        SD_LAUNCH_CHECK();
+        return 0;
+    }
+    if (affine) {
+        hipLaunchKernelGGL(k_affine_u8, grid, dim3(256), 0, st, mosaic, img_a, Hout, Wout, affine, f0, f1, f2);
+        SD_LAUNCH_CHECK();
+    }
+    return jitter_norm(B, Hout, Wout, flips, jitter_order, jitter_factors, mean3, std3, out, img_a, lsum, st);
+}
+
+int sd_preprocess_images_mosaic(const uint8_t* images, int B, int Hin, int Win, int Hout, int Wout, const int* h_bounds, const int* h_kk,
+                                int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips, const int* jitter_order,
+                                const float* jitter_factors, const double* affine, const int* mosaic_geom, const double* mosaic_affine,
+                                const uint8_t* fill3, const float* mean3, const float* std3, float* out, void* workspace, size_t workspace_bytes,
+                                sd_stream_t stream) {
+    if (int e = preprocess_check("sd_preprocess_images_mosaic", images, B, Hin, Win, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, mean3,
+                                 std3, out, workspace)) return e;
+    if (int e = mosaic_check("sd_preprocess_images_mosaic", B, Hin, Win, Hout, Wout, jitter_order, jitter_factors, mosaic_geom, mosaic_affine, fill3,
+                             workspace_bytes)) return e;
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t* tmp = reinterpret_cast<uint8_t*>(workspace);
+    if (jitter_order) {
+        uint8_t* img = tmp + sd_preprocess_workspace_bytes(B, Hin, Win, Wout);
+        SD_HIP(hipMemsetAsync(img + align_up((size_t)B * Hout * Wout * 3, 256), 0, (size_t)B * 8, st));    // lsum
+    }
+    const int64_t rows = (int64_t)B * Hin;
+    hipLaunchKernelGGL(k_resample_h, dim3(cdiv(rows * Wout, 256)), dim3(256), 0, st, images, tmp, Hin, Win, Wout, h_bounds, h_kk, h_ksize, rows);
+    SD_LAUNCH_CHECK();
+    return preprocess_mosaic_tail(B, Hin, Win, Hout, Wout, v_bounds, v_kk, v_ksize, flips, jitter_order, jitter_factors, affine, mosaic_geom,
+                                  mosaic_affine, fill3, mean3, std3, out, tmp, st);
+}
+
+int sd_preprocess_images_list_mosaic(const uint8_t* const* images, int B, int Hin, int Win, int Hout, int Wout, const int* h_bounds,
+                                     const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips,
+                                     const int* jitter_order, const float* jitter_factors, const double* affine, const int* mosaic_geom,
+                                     const double* mosaic_affine, const uint8_t* fill3, const float* mean3, const float* std3, float* out,
+                                     void* workspace, size_t workspace_bytes, sd_stream_t stream) {
+    int rpb = 0, bpi = 0;
+    if (int e = preprocess_list_check("sd_preprocess_images_list_mosaic", images, B, Hin, Win, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk,
+                                      v_ksize, mean3, std3, out, workspace, &rpb, &bpi)) return e;
+    if (int e = mosaic_check("sd_preprocess_images_list_mosaic", B, Hin, Win, Hout, Wout, jitter_order, jitter_factors, mosaic_geom, mosaic_affine,
+                             fill3, workspace_bytes)) return e;
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t* tmp = reinterpret_cast<uint8_t*>(workspace);
+    if (jitter_order) {
+        uint8_t* img = tmp + sd_preprocess_workspace_bytes(B, Hin, Win, Wout);
+        SD_HIP(hipMemsetAsync(img + align_up((size_t)B * Hout * Wout * 3, 256), 0, (size_t)B * 8, st));    // lsum
+    }
+    if (int e = resample_h_list(images, tmp, B, Hin, Win, Wout, h_bounds, h_kk, h_ksize, rpb, bpi, st)) return e;
+    return preprocess_mosaic_tail(B, Hin, Win, Hout, Wout, v_bounds, v_kk, v_ksize, flips, jitter_order, jitter_factors, affine, mosaic_geom,
+                                  mosaic_affine, fill3, mean3, std3, out, tmp, st);
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 from .dataset import CropDataset, PredictionDataset, collate_fn
 from .decoders import Decoder, FusedOutputDecoder, RawDecoder
 from .transforms import Encode
-from .augment import (TrainAugmentation, ValidationAugmentation, affine_forward_matrix, affine_inverse_matrix, pil_bilinear_coeffs,
+from .augment import (TrainAugmentation, ValidationAugmentation, affine_forward_matrix, affine_inverse_matrix, mosaic_tiles, pil_bilinear_coeffs,
                       preprocess_image_list, preprocess_images)
 from .feeder import BatchFeeder, GroupedBatch
 from .image_cache import DeviceImageCache, ImageList

@@ -15,6 +15,9 @@ Random affine (`--aug_rotate / --aug_scale / --aug_translate`; not in the refere
 Resize and ColorJitter, as Pillow's `Image.transform(size, AFFINE, matrix, BILINEAR, fillcolor=_FILL)` byte for byte
 (`sd_preprocess_images_affine`); the matrices are built on the host (`affine_inverse_matrix`), the annotations follow with
 `utils.misc.affine_annotation`, which drops what leaves the frame.
+Mosaic (`--aug_mosaic P`; not in the reference): between Resize and the warp, a selected image becomes four images of its size group at
+half scale around a random centre (`mosaic_tiles`), each quadrant Pillow's `Image.transform` of its source byte for byte
+(`sd_preprocess_images_mosaic`); `utils.misc.mosaic_annotation` gathers the four annotations and keeps what each tile shows.
 """
 from __future__ import annotations
 
@@ -25,7 +28,7 @@ import numpy as np
 import torch
 
 from .. import _lib as L
-from ..utils.misc import affine_annotation, clip_annotation, hflip_annotation, vflip_annotation
+from ..utils.misc import affine_annotation, clip_annotation, hflip_annotation, mosaic_annotation, vflip_annotation
 
 PRECISION_BITS = 32 - 8 - 2
 _MEAN = (0.485, 0.456, 0.406)
@@ -119,6 +122,42 @@ def affine_forward_matrix(size, angle, scale, translate):
     return [a, b, cx + tx - (a * cx + b * cy), c, d, cy + ty - (c * cx + d * cy)]
 
 
+def mosaic_tiles(size, i, draw):
+    """One image's mosaic from (W, H) = size and draw = (cx, cy, (p1, p2, p3)) -- an integer centre and the three partner images -- or
+    draw = None for an image that is not selected.  Returns (geom, inverse, forward, rects):
+    geom    [cx, cy, s0, s1, s2, s3], the row of `sd_preprocess_images_mosaic`'s mosaic_geom: tile q = (x >= cx) + 2 (y >= cy) shows image s_q, s0 = i;
+    inverse the four matrices m_q (canvas pixel centre -> source position) of its mosaic_affine;
+    forward their twins (source -> canvas), what `mosaic_annotation` moves the points by;
+    rects   (x0, y0, x1, y1) per tile: the canvas pixels x0 <= x < x1, y0 <= y < y1 that show the tile's source.
+    Policy: every source at zoom 1/2 with a corner on the centre, so tile q's half image has its origin at ox = cx - W/2 (q = 0, 2) or cx
+    (q = 1, 3), oy likewise with cy and H/2, m_q = [2, 0, -2 ox, 0, 2, -2 oy] (exact in double; every tap is a 2 x 2 block mean) and its
+    rectangle is the half image cropped by the quadrant and the canvas; what the half image leaves of its quadrant is fill.  Not
+    selected: the centre (W, H) makes tile 0 the whole canvas and the identity copies image i."""
+    W, H = size
+    if draw is None:
+        ident = [1.0, 0.0, 0.0, 0.0, 1.0, 0.0]
+        return [W, H, i, i, i, i], [list(ident) for _ in range(4)], [list(ident) for _ in range(4)], [(0, 0, W, H), (W, 0, W, H), (0, H, W, H), (W, H, W, H)]
+    cx, cy, partners = draw
+    inverse, forward, rects = [], [], []
+    for q in range(4):
+        ox = cx - W // 2 if q in (0, 2) else cx
+        oy = cy - H // 2 if q < 2 else cy
+        inverse.append([2.0, 0.0, -2.0 * ox, 0.0, 2.0, -2.0 * oy])
+        forward.append([0.5, 0.0, float(ox), 0.0, 0.5, float(oy)])
+        x0, x1 = (max(ox, 0), cx) if q in (0, 2) else (cx, min(ox + W // 2, W))
+        y0, y1 = (max(oy, 0), cy) if q < 2 else (cy, min(oy + H // 2, H))
+        rects.append((x0, y0, x1, y1))
+    return [cx, cy, i, *partners], inverse, forward, rects
+
+
+def _mosaic_tables(mosaic, B, device):
+    geom = torch.as_tensor(np.asarray(mosaic[0], dtype=np.int32)).reshape(-1, 6).contiguous()
+    mats = torch.as_tensor(np.asarray(mosaic[1], dtype=np.float64)).reshape(-1, 24).contiguous()
+    if geom.shape[0] != B or mats.shape[0] != B:
+        raise L.SdError("mosaic must have one geometry row of 6 integers and four matrices of 6 coefficients per image")
+    return geom.to(device, non_blocking=True), mats.to(device, non_blocking=True)
+
+
 def _affine_rows(affine, B, device):
     rows = torch.as_tensor(np.asarray(affine, dtype=np.float64)).reshape(-1, 6).contiguous()
     if rows.shape[0] != B:
@@ -126,11 +165,13 @@ def _affine_rows(affine, B, device):
     return rows.to(device, non_blocking=True)
 
 
-def preprocess_images(images: torch.Tensor, out_size, flips=None, mean=_MEAN, std=_STD, jitter=None, affine=None) -> torch.Tensor:
+def preprocess_images(images: torch.Tensor, out_size, flips=None, mean=_MEAN, std=_STD, jitter=None, affine=None, mosaic=None) -> torch.Tensor:
     """images: (B, Hin, Win, 3) uint8 on the GPU; out_size = (width, height); flips: (B,) uint8 (bit 0 horizontal, bit 1 vertical)
     or None; jitter: None or (order words (B,) int32, factors (B, 3) fp32) as `jitter_words` makes them; affine: None or B rows of the 6
-    coefficients of `affine_inverse_matrix` at out_size (the warp runs on the resized image, in front of the jitter, fill `_FILL`).
-    Returns (B, 3, height, width) fp32 = Normalize(to_tensor(flip(jitter(affine(resize(image)))))) of transforms.py:217-226."""
+    coefficients of `affine_inverse_matrix` at out_size (the warp runs on the resized image, in front of the jitter, fill `_FILL`); mosaic:
+    None or (geom: B rows [cx, cy, s0 .. s3], matrices: B x 4 x 6) as `mosaic_tiles` makes them, the sources s_q indexing THIS batch
+    (the composite is built from the resized images, in front of the warp).
+    Returns (B, 3, height, width) fp32 = Normalize(to_tensor(flip(jitter(affine(mosaic(resize(image))))))) of transforms.py:217-226."""
     L.require_cuda(images)
     if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3:
         raise L.SdError(f"preprocess_images expects (B, H, W, 3) uint8, got {tuple(images.shape)} {images.dtype}")
@@ -153,6 +194,17 @@ def preprocess_images(images: torch.Tensor, out_size, flips=None, mean=_MEAN, st
         factors = torch.as_tensor(jitter[1], dtype=torch.float32).reshape(-1, 3).contiguous().to(images.device, non_blocking=True)
         if order.numel() != B or factors.shape[0] != B:
             raise L.SdError("jitter parameters must have one row per image")
+    if mosaic is not None:
+        geom, mats = _mosaic_tables(mosaic, B, images.device)
+        rows = None if affine is None else _affine_rows(affine, B, images.device)
+        ws = L.workspace(lib.sd_preprocess_mosaic_workspace_bytes(B, Hin, Win, Hout, Wout), images.device)
+        L.check(lib.sd_preprocess_images_mosaic(images.data_ptr(), B, Hin, Win, Hout, Wout, hb.data_ptr(), hk.data_ptr(), hks, vb.data_ptr(),
+                                                vk.data_ptr(), vks, fl.data_ptr() if fl is not None else 0,
+                                                order.data_ptr() if order is not None else 0, factors.data_ptr() if factors is not None else 0,
+                                                rows.data_ptr() if rows is not None else 0, geom.data_ptr(), mats.data_ptr(),
+                                                (C.c_ubyte * 3)(*_FILL), m3, s3, out.data_ptr(), ws.data_ptr(), ws.numel(), L.stream()),
+                "sd_preprocess_images_mosaic")
+        return out
     if affine is not None:
         rows = _affine_rows(affine, B, images.device)
         ws = L.workspace(lib.sd_preprocess_affine_workspace_bytes(B, Hin, Win, Hout, Wout), images.device)
@@ -176,7 +228,7 @@ def preprocess_images(images: torch.Tensor, out_size, flips=None, mean=_MEAN, st
 
 
 def preprocess_image_list(pointers: torch.Tensor, hin: int, win: int, out_size, flips=None, mean=_MEAN, std=_STD, jitter=None,
-                          affine=None) -> torch.Tensor:
+                          affine=None, mosaic=None) -> torch.Tensor:
     """`preprocess_images` over B images that are not packed together: pointers is a (B,) int64 DEVICE tensor of the device addresses of
     B (hin, win, 3) uint8 images (any byte alignment; the caller keeps them alive until the work on the current stream is done), e.g. entries
     of data/image_cache.py's DeviceImageCache.  Same arguments otherwise, same output bytes as `preprocess_images` on the stacked images."""
@@ -203,6 +255,18 @@ def preprocess_image_list(pointers: torch.Tensor, hin: int, win: int, out_size, 
         factors = torch.as_tensor(jitter[1], dtype=torch.float32).reshape(-1, 3).contiguous().to(dev, non_blocking=True)
         if order.numel() != B or factors.shape[0] != B:
             raise L.SdError("jitter parameters must have one row per image")
+    if mosaic is not None:
+        geom, mats = _mosaic_tables(mosaic, B, dev)
+        rows = None if affine is None else _affine_rows(affine, B, dev)
+        ws = L.workspace(lib.sd_preprocess_mosaic_workspace_bytes(B, Hin, Win, Hout, Wout), dev)
+        L.check(lib.sd_preprocess_images_list_mosaic(pointers.data_ptr(), B, Hin, Win, Hout, Wout, hb.data_ptr(), hk.data_ptr(), hks, vb.data_ptr(),
+                                                     vk.data_ptr(), vks, fl.data_ptr() if fl is not None else 0,
+                                                     order.data_ptr() if order is not None else 0,
+                                                     factors.data_ptr() if factors is not None else 0,
+                                                     rows.data_ptr() if rows is not None else 0, geom.data_ptr(), mats.data_ptr(),
+                                                     (C.c_ubyte * 3)(*_FILL), m3, s3, out.data_ptr(), ws.data_ptr(), ws.numel(), L.stream()),
+                "sd_preprocess_images_list_mosaic")
+        return out
     if affine is not None:
         rows = _affine_rows(affine, B, dev)
         ws = L.workspace(lib.sd_preprocess_affine_workspace_bytes(B, Hin, Win, Hout, Wout), dev)
@@ -234,6 +298,13 @@ def jitter_words(order, brightness, contrast, saturation, hue):
     return word, (float(brightness), float(contrast), float(saturation))
 
 
+class _Objects:
+    """The object list an annotation had at some point (mosaic_annotation reads `objects` only)."""
+
+    def __init__(self, objects):
+        self.objects = list(objects)
+
+
 class ValidationAugmentation:
     """transforms.py:255-261 for a batch: Resize((width, height)) + Normalize (+ the clip Encode applies, transforms.py:154)."""
 
@@ -247,6 +318,10 @@ class ValidationAugmentation:
 
     def affine_draws_for(self, n):
         """(angle, scale, tx, ty) per sample, or None: validation never warps and never draws."""
+        return None
+
+    def mosaic_draws_for(self, n, groups):
+        """Per sample None or (cx, cy, partners), or None for the batch: validation never composes and never draws."""
         return None
 
     def __call__(self, images, annotations):
@@ -269,15 +344,21 @@ class ValidationAugmentation:
         flips, jitter = self.draws_for(n)
         warps = self.affine_draws_for(n)
         inverse = None if warps is None else [affine_inverse_matrix((W, H), a, s, (tx, ty)) for a, s, tx, ty in warps]
+        mosaics = self.mosaic_draws_for(n, [idx for idx, _ in groups.values()])
         out = torch.empty((n, 3, H, W), dtype=torch.float32, device=dev)
         for (hin, win), (idx, stack) in groups.items():
             f = None if flips is None else [flips[i] for i in idx]
             j = None if jitter is None else ([jitter[0][i] for i in idx], [jitter[1][i] for i in idx])
             m = None if inverse is None else [inverse[i] for i in idx]
+            kw = {}
+            if mosaics is not None:                                  # the kernel's sources index this group's stack: partners come from the group
+                where = {i: k for k, i in enumerate(idx)}
+                tiles = {i: mosaic_tiles((W, H), i, mosaics[i]) for i in idx}
+                kw["mosaic"] = ([[*tiles[i][0][:2], *(where[s] for s in tiles[i][0][2:])] for i in idx], [tiles[i][1] for i in idx])
             if hasattr(stack, "pointers"):                           # data/image_cache.py ImageList: cached / uploaded images by address
-                res = preprocess_image_list(stack.pointers, hin, win, (W, H), f, jitter=j, affine=m)
+                res = preprocess_image_list(stack.pointers, hin, win, (W, H), f, jitter=j, affine=m, **kw)
             else:
-                res = preprocess_images(stack.to(dev, non_blocking=True), (W, H), f, jitter=j, affine=m)
+                res = preprocess_images(stack.to(dev, non_blocking=True), (W, H), f, jitter=j, affine=m, **kw)
             if len(groups) == 1:
                 out = res
             else:
@@ -286,6 +367,14 @@ class ValidationAugmentation:
                 ann = annotations[i]
                 ann.img_size = ann.img_size or (win, hin)
                 ann.resize((win, hin), (W, H))                       # transforms.py:58
+            if mosaics is not None:                                  # an image is itself and maybe someone's partner: compose from the
+                resized = {i: _Objects(annotations[i].objects) for i in idx}      # resized objects of the whole group, as they were
+                for i in idx:
+                    if mosaics[i] is not None:
+                        geom, _, forward, rects = tiles[i]
+                        mosaic_annotation(annotations[i], [resized[s] for s in geom[2:]], forward, rects)
+            for i in idx:
+                ann = annotations[i]
                 if warps is not None:                                # on the resized image, before the flips: drops what leaves the frame
                     a, s, tx, ty = warps[i]
                     affine_annotation(ann, affine_forward_matrix((W, H), a, s, (tx, ty)), (W, H))
@@ -315,6 +404,7 @@ class TrainAugmentation(ValidationAugmentation):
         self.rotate = float(getattr(args, "aug_rotate", 0.0))              # degrees: angle uniform in [-rotate, rotate]
         self.scale = float(getattr(args, "aug_scale", 0.0))                # scale uniform in [1 - scale, 1 + scale]
         self.translate = float(getattr(args, "aug_translate", 0.0))        # shift uniform in [-translate, translate] * (width, height)
+        self.mosaic = float(getattr(args, "aug_mosaic", 0.0))              # per-image probability of becoming a mosaic of four
 
     def draws_for(self, n):
         """(flips, jitter) of n samples from torch's global generator, in THREE vectorised draws per batch: per-sample tiny tensor ops
@@ -348,6 +438,24 @@ class TrainAugmentation(ValidationAugmentation):
         lo = torch.tensor([-self.rotate, 1 - self.scale, -self.translate * W, -self.translate * H], dtype=torch.float64)
         hi = torch.tensor([self.rotate, 1 + self.scale, self.translate * W, self.translate * H], dtype=torch.float64)
         return [tuple(r) for r in (lo + (hi - lo) * u).tolist()]
+
+    def mosaic_draws_for(self, n, groups):
+        """Per sample None (not selected) or (cx, cy, (p1, p2, p3)) from ONE more draw on torch's global generator, `rand(n, 6)` in float64,
+        made after that of `affine_draws_for`: columns select (u < P), cx uniform over the integers of [W/4, 3W/4], cy over [H/4, 3H/4],
+        and three partners.  groups = the index lists of the batch's size groups: partner k of image i is `idx[int(u * len(idx))]` of its
+        own group idx (with replacement, i itself allowed: the device composes from the resized images of one group).  None, and no draw
+        at all, with `--aug_mosaic 0` or augmentation off.  The centre follows the current multi-scale size."""
+        if self.args.no_augmentation or self.mosaic == 0:
+            return None
+        W, H = self.size
+        u = torch.rand(n, 6, dtype=torch.float64).tolist()
+        draws = [None] * n
+        for idx in groups:
+            for i in idx:
+                sel, ux, uy, *up = u[i]
+                if sel < self.mosaic:
+                    draws[i] = (W // 4 + int(ux * (W // 2 + 1)), H // 4 + int(uy * (H // 2 + 1)), tuple(idx[int(v * len(idx))] for v in up))
+        return draws
 
     def trigger_random_resize(self):
         if self.args.no_augmentation:

@@ -77,6 +77,10 @@ _FLAGS = [
                             "uniform in [1 - S, 1 + S] (0 <= S < 1; 0 = off). Not consulted by evaluate / detect.")),
     (("--aug_translate",), dict(type=float, default=0.0, metavar="T", help="Training augmentation: shift every image by a fraction of its width "
                                 "and height uniform in [-T, T] (0 .. 0.5; 0 = off). Not consulted by evaluate / detect.")),
+    (("--aug_mosaic",), dict(type=float, default=0.0, metavar="P", help="Training augmentation: with probability P (0 .. 1; 0 = off) an image "
+                             "becomes a mosaic of itself and three other images of its batch at half scale around a random centre. A mosaic "
+                             "carries up to four images' objects: raise --max_objects / --max_parts accordingly (what exceeds them is "
+                             "truncated by the target encoder as always). Not consulted by evaluate / detect.")),
 ]
 
 _POSITIVE = ["in_channels", "fpn_depth", "batch_size", "epochs", "learning_rate", "down_ratio", "max_objects", "max_parts"]
@@ -111,6 +115,7 @@ def finalize(args):
     assert 0 <= getattr(args, "aug_rotate", 0.0) <= 180, "'aug_rotate' should be in [0, 180]"
     assert 0 <= getattr(args, "aug_scale", 0.0) < 1, "'aug_scale' should be in [0, 1["
     assert 0 <= getattr(args, "aug_translate", 0.0) <= 0.5, "'aug_translate' should be in [0, 0.5]"
+    assert 0 <= getattr(args, "aug_mosaic", 0.0) <= 1, "'aug_mosaic' should be in [0, 1]"
 
     args.lr_step = int(args.epochs / args.lr_step) if args.lr_step != 0 else args.epochs
     for k in ("train_dir", "valid_dir", "pretrained_model"):

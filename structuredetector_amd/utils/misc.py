@@ -91,6 +91,46 @@ def affine_annotation(annotation, forward_matrix, img_size):
     return annotation
 
 
+def mosaic_annotation(annotation, sources, forward_matrices, rects):
+    """Follow a mosaic of the image (data/augment.py: mosaic_tiles): `annotation` gets, in place, the objects of the four `sources` (the
+    RESIZED annotations of the images shown in tiles 0 .. 3; they are read, never modified: every object is cloned first, so an image can
+    be itself, its own partner and someone else's) moved by each tile's forward matrix, p' + 0.5 = F_q (p + 0.5) as in affine_annotation, and
+    kept iff the point lies inside the tile's rectangle (x0, y0, x1, y1): x0 <= x' + 0.5 < x1 and y0 <= y' + 0.5 < y1 -- the pixels of the
+    composite that tile owns.  An object whose anchor fails goes with all its parts; a failing part is removed from its object; a box
+    becomes the hull of its corners (clip_annotation clips it later).  Objects are concatenated in tile order; image_path / img_size stay."""
+    objects = []
+    for source, (f0, f1, f2, f3, f4, f5), (x0, y0, x1, y1) in zip(sources, forward_matrices, rects):
+        if x0 >= x1 or y0 >= y1:
+            continue
+
+        def move(x, y):
+            xc, yc = x + 0.5, y + 0.5
+            return f0 * xc + f1 * yc + f2 - 0.5, f3 * xc + f4 * yc + f5 - 0.5
+
+        def inside(x, y):
+            return x0 <= x + 0.5 < x1 and y0 <= y + 0.5 < y1
+
+        for obj in source.objects:
+            x, y = move(obj.x, obj.y)
+            if not inside(x, y):
+                continue
+            obj = obj.clone()
+            obj.x, obj.y = x, y
+            parts = []
+            for p in obj.parts:
+                p.x, p.y = move(p.x, p.y)
+                if inside(p.x, p.y):
+                    parts.append(p)
+            obj.parts = parts
+            if obj.box is not None:
+                b = obj.box
+                xs, ys = zip(*(move(bx, by) for bx in (b.x_min, b.x_max) for by in (b.y_min, b.y_max)))
+                b.x_min, b.x_max, b.y_min, b.y_max = min(xs), max(xs), min(ys), max(ys)
+            objects.append(obj)
+    annotation.objects = objects
+    return annotation
+
+
 def get_unique_color_map(labels):
     """utils.py:476-479: a stable RGB triple per name (first three bytes of its xxh64 digest)."""
     from xxhash import xxh64_digest

@@ -2,7 +2,7 @@
 """`train --train_dir` throughput (VERDICT r2 task 4): N synthetic PNG + JSON samples on disk (schema of the
 reference's README.md:40-71), decoded by the thread-pool feed, resized / jittered / flipped / normalised and encoded on the GPU, through
 the real TrainStep -- images/s next to the synthetic-tensor step of the same batch (what bench.py times).
-usage: feed_bench.py [--n 512] [--batch 64] [--steps 24] [--workers 0] [--amp] [--no_augmentation] [--dir /tmp/sd_feed]"""
+usage: feed_bench.py [--n 512] [--batch 64] [--steps 24] [--workers 0] [--amp] [--no_augmentation] [--aug_mosaic P] [--dir /tmp/sd_feed]"""
 import argparse
 import json
 import sys
@@ -41,7 +41,8 @@ def write_samples(directory, n, size, seed=7):
     return directory.parent / "feed_labels.json"
 
 
-def run(n=512, batch=64, size=512, steps=24, workers=0, amp=False, no_augmentation=False, directory="/tmp/sd_feed", breakdown=True, synthetic=True):
+def run(n=512, batch=64, size=512, steps=24, workers=0, amp=False, no_augmentation=False, directory="/tmp/sd_feed", breakdown=True, synthetic=True,
+        aug_mosaic=0.0):
     """Returns the figures as a dict (bench.py's `directory_feed` extra calls this with breakdown / synthetic off)."""
     import os
     from concurrent.futures import ThreadPoolExecutor
@@ -59,8 +60,10 @@ def run(n=512, batch=64, size=512, steps=24, workers=0, amp=False, no_augmentati
     t_write = time.perf_counter() - t0
     png_mb = sum(f.stat().st_size for f in (root / "train").glob("*.png")) / n / 1e6
     common = ["--labels", str(labels), "-s", "stem", "-b", str(batch), "-W", str(size), "-H", str(size), "-e", "1000"] + (["--amp"] if amp else []) + \
-             (["-a"] if no_augmentation else [])
+             (["-a"] if no_augmentation else []) + (["--aug_mosaic", str(aug_mosaic)] if aug_mosaic else [])
     out = {"samples": n, "png_mb_each": round(png_mb, 3), "write_s": round(t_write, 1), "batch": batch, "amp": amp, "augmentation": not no_augmentation}
+    if aug_mosaic:
+        out["aug_mosaic"] = aug_mosaic
     threads_before = torch.get_num_threads()
 
     def rate(argv, label):
@@ -134,9 +137,9 @@ def main():
     ap.add_argument("--n", type=int, default=512); ap.add_argument("--batch", type=int, default=64); ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--steps", type=int, default=24); ap.add_argument("--workers", type=int, default=0)
     ap.add_argument("--amp", action="store_true"); ap.add_argument("--no_augmentation", action="store_true")
-    ap.add_argument("--dir", default="/tmp/sd_feed")
+    ap.add_argument("--dir", default="/tmp/sd_feed"); ap.add_argument("--aug_mosaic", type=float, default=0.0)
     a = ap.parse_args()
-    print(json.dumps(run(a.n, a.batch, a.size, a.steps, a.workers, a.amp, a.no_augmentation, a.dir)))
+    print(json.dumps(run(a.n, a.batch, a.size, a.steps, a.workers, a.amp, a.no_augmentation, a.dir, aug_mosaic=a.aug_mosaic)))
 
 
 if __name__ == "__main__":
