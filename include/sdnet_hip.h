@@ -201,6 +201,28 @@ int sd_tta_views(const float* x, float* out, int B, int H, int W, int V, const u
 int sd_tta_merge_nms(const float* hm, int64_t sb, int64_t sc, float* out, int B, int C, int h, int w, int V,
                      const unsigned char* view_flips_host, sd_stream_t stream);
 
+/* ---- multi-scale test-time augmentation (no reference counterpart) ----
+ * sd_tta_scale_merge_nms: the heatmap logits of S forwards at S input sizes, each over V mirrored views, merged on the base grid:
+ *   scale s is a (V*B, C, hs[s], ws[s]) strided (sb[s], sc[s]) channel-slice view at hm_host[s] (device pointers; the five arrays
+ *   `*_host` are HOST arrays of S entries), view v of image b is image v*B + b as in sd_tta_views; out (B,C,h,w) contiguous.
+ *   1 <= S <= 5, V in {1, 2, 4}, view 0 unflipped, 1 <= hs[s] <= 2h and 1 <= ws[s] <= 2w (the bound that fits the source footprint
+ *   of a 64x16 tile and its halo, <= 138 x 42 cells, into LDS); anything else is SD_ERR_INVALID.  Scale 0 need not be the base size.
+ *   One launch, no workspace, no atomics, no host synchronisation, deterministic.  For base cell (y, x), with all coordinate
+ *   arithmetic in double and every fp32 operation rounded separately (no contraction):
+ *       rx = (double)ws / (double)w;  sx = max((x + 0.5) * rx - 0.5, 0);  x0 = min((int)floor(sx), ws-1);  x1 = min(x0 + 1, ws-1);
+ *       lx = sx - x0;  wx1 = (float)lx;  wx0 = (float)(1.0 - lx)        (the vertical axis alike: torch's bilinear, align_corners=False)
+ *       p_v(yy, xx) = clamped_sigmoid(hm_s[v*B + b, c, fy_v(yy), fx_v(xx)]),  fx_v(xx) = ws-1-xx if bit 0 of view v else xx, fy_v alike
+ *       top = wx0 * p_v(y0, x0) + wx1 * p_v(y0, x1);  bot = wx0 * p_v(y1, x0) + wx1 * p_v(y1, x1);  r_{s,v} = wy0 * top + wy1 * bot
+ *       m = (sum of r_{s,v}, scale-major, view-minor, from r_{0,0}) * inv,   inv = the fp32 nearest to the double 1.0 / (S * V)
+ *   and out = m where m equals the maximum of m over the 5x5 window, else 0; padding and ties exactly as sd_nms5.  Equal sizes give
+ *   x0 = x, wx0 = 1, wx1 = 0: with S = 1 at the base size the function equals sd_tta_merge_nms bit for bit (and runs its kernel), and
+ *   with V = 1 as well sd_nms5(apply_sigmoid = 1).  Every source cell's sigmoid is computed once per block; every view is read once
+ *   (+ halo re-reads), the output written once; 16-byte loads per scale when ws % 4 == 0 and planes / strides are 16-byte aligned,
+ *   4-byte loads otherwise. */
+int sd_tta_scale_merge_nms(const float* const* hm_host, const int64_t* sb_host, const int64_t* sc_host, const int* hs_host,
+                           const int* ws_host, float* out, int B, int C, int h, int w, int S, int V,
+                           const unsigned char* view_flips_host, sd_stream_t stream);
+
 /* ---- target rendering: src/sdnet/data/transforms.py:130-205 (Encode) ---------------------- */
 
 /* Heatmaps of a batch (transforms.py:143,160-161,173-174; utils.py:418-419): for every pixel of

@@ -74,6 +74,8 @@ _SIGNATURES = {
     # flip test-time augmentation: ..., V, view_flips (HOST array of V bytes), stream
     "sd_tta_views": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]),
     "sd_tta_merge_nms": (c_int, _MAP + [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp]),
+    # multi-scale: hm / sb / sc / hs / ws (HOST arrays of S entries), out, B, C, h, w, S, V, view_flips, stream
+    "sd_tta_scale_merge_nms": (c_int, [c_vp] * 6 + [c_int] * 6 + [c_vp, c_vp]),
     "sd_preprocess_workspace_bytes": (c_size, [c_int] * 4),
     "sd_preprocess_images": (c_int, [c_vp] + [c_int] * 5 + [c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp, C.POINTER(c_float), C.POINTER(c_float),
                                                 c_vp, c_vp, c_size, c_vp]),

@@ -40,7 +40,10 @@ def _evaluate(argv):
     if args.pretrained_model:
         net.load_state_dict(torch.load(args.pretrained_model, map_location="cpu", weights_only=True))
     net = net.eval().to(args.device)
-    if getattr(args, "tta", "none") != "none":      # --tta: the mirrored views, one forward over all of them and the merge sit inside the per-batch step
+    if args.synthetic and getattr(args, "tta_scales", ()):
+        raise SystemExit("--tta_scales resamples every input size from the source images; --synthetic renders its samples as network-input "
+                         "tensors and has no source image to resample: evaluate a directory (--valid_dir) or drop --tta_scales")
+    if getattr(args, "tta", "none") != "none" or getattr(args, "tta_scales", ()):      # --tta / --tta_scales: the views, the forwards and the merge sit inside the per-batch step
         from ..model.tta import with_tta
         net, decoder = with_tta(net, decoder, args)
     if args.synthetic:

@@ -1,7 +1,9 @@
 // Flip test-time augmentation for gfx950: the mirrored input batch (sd_tta_views) and the merge of the V head outputs into ONE
-// suppressed probability map (sd_tta_merge_nms).  No reference counterpart (the reference has no test-time augmentation).
-// The merged value decides which pixels survive the NMS and is compared bit for bit with the library's own primitives
-// (sd_clamped_sigmoid, sd_nms5): separately rounded adds and one multiply -- floating-point contraction is OFF in this file.
+// suppressed probability map (sd_tta_merge_nms), and the multi-scale merge (sd_tta_scale_merge_nms): the S x V head outputs of S input
+// sizes resampled to the base grid, averaged and suppressed in one launch.  No reference counterpart (the reference has no test-time
+// augmentation).  The merged value decides which pixels survive the NMS and is compared bit for bit with the library's own primitives
+// (sd_clamped_sigmoid, sd_nms5): separately rounded multiplies and adds, resampling coordinates in double -- floating-point contraction
+// is OFF in this file.
 #pragma clang fp contract(off)
 #include "sd_common.h"
 
@@ -177,10 +179,164 @@ __global__ __launch_bounds__(256) void k_tta_merge_nms(const float* __restrict__
 }
 
 // ---------------------------------------------------------------------------------------------
+// Scale merge + NMS (multi-scale test-time augmentation).  The block and its tile are those of k_tta_merge_nms; the S x V head tensors
+// have sizes of their own and are resampled to the base grid (bilinear, half-pixel centres: F.interpolate's align_corners=False).
+// Per scale the block computes the 68 + 20 per-axis entries (x0, x1, wx0, wx1) of its tile + halo once, in double (scale_axis); per
+// (scale, view) it stages clamped_sigmoid of the source footprint of the tile in LDS ONCE per source cell (F, in MEMORY coordinates:
+// a mirrored view is mirrored when F is indexed, so the staged span of a row is contiguous either way) and every base cell adds its
+// interpolated sample to a register accumulator -- scale-major, view-minor, each product and add rounded separately.  The mean then
+// goes through the separable 5-max of k_tta_merge_nms.
+//   footprint: hs <= 2h, ws <= 2w (checked on the host) bound it to 138 x 42 source cells for the 68 x 20 base cells; the 16-byte
+//   variant widens a row's span to whole aligned groups (<= 36 groups = FW columns).  The staging loops are clamped to F's extent.
+//   16-byte loads per scale when ws % 4 == 0 and the planes / strides are 16-byte aligned (a group is then entirely inside a row),
+//   4-byte loads otherwise.
+// ---------------------------------------------------------------------------------------------
+constexpr int MAX_SCALES = 5;
+constexpr int FH = 42, FW = 144;
+
+struct ScaleArgs {
+    const float* hm[MAX_SCALES];
+    int64_t sb[MAX_SCALES], sc[MAX_SCALES];
+    double rx[MAX_SCALES], ry[MAX_SCALES];          // (double)ws / (double)w, (double)hs / (double)h
+    int hs[MAX_SCALES], ws[MAX_SCALES];
+    unsigned char vec[MAX_SCALES];
+};
+
+// one axis entry of the resampling: source cells i0, i1 and their weights for base cell `i` (n_in source cells, ratio = n_in / n_out)
+__device__ __forceinline__ void scale_axis(int i, double ratio, int n_in, int* i0, int* i1, float* w0, float* w1) {
+    const double t = ((double)i + 0.5) * ratio;
+    const double s = fmax(t - 0.5, 0.0);
+    const int a = min((int)floor(s), n_in - 1);
+    const double lam = s - (double)a;
+    *i0 = a;
+    *i1 = min(a + 1, n_in - 1);
+    *w1 = (float)lam;
+    *w0 = (float)(1.0 - lam);
+}
+
+template <int V>
+__global__ __launch_bounds__(256) void k_tta_scale_merge_nms(ScaleArgs sa, int S, float inv, int B, int C, int h, int w, int tiles_x,
+                                                             ViewFlips vf, int out_vec, float* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) float F[FH][FW];
+    __shared__ __attribute__((aligned(16))) float Sm[LH][LWV];
+    __shared__ __attribute__((aligned(16))) float Hm[LH][TW];
+    __shared__ int X0[LWS], X1[LWS], Y0[LH], Y1[LH];
+    __shared__ float WX0[LWS], WX1[LWS], WY0[LH], WY1[LH];
+    constexpr int NC = LH * LWS;                                       // 1360 base cells (tile + halo)
+    constexpr int NA = (NC + 255) / 256;
+    const int tid = threadIdx.x;
+    const int b = blockIdx.z, c = blockIdx.y;
+    const int tx0 = (blockIdx.x % tiles_x) * TW;
+    const int ty0 = (blockIdx.x / tiles_x) * TH;
+    float acc[NA];
+#pragma unroll
+    for (int j = 0; j < NA; ++j) acc[j] = 0.0f;
+
+    for (int s = 0; s < S; ++s) {
+        const int hs = sa.hs[s], ws = sa.ws[s];
+        // axis tables of this scale; cells of the halo outside the map take the entry of the nearest cell inside (never sampled, but the
+        // first and the last entry bound the footprint)
+        if (tid < LWS) {
+            scale_axis(min(max(tx0 + tid - HALO, 0), w - 1), sa.rx[s], ws, &X0[tid], &X1[tid], &WX0[tid], &WX1[tid]);
+        } else if (tid < LWS + LH) {
+            const int r = tid - LWS;
+            scale_axis(min(max(ty0 + r - HALO, 0), h - 1), sa.ry[s], hs, &Y0[r], &Y1[r], &WY0[r], &WY1[r]);
+        }
+        __syncthreads();
+        const int xa = X0[0], xb = X1[LWS - 1], ya = Y0[0], yb = Y1[LH - 1];      // the footprint in view coordinates (monotone tables)
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            const bool hf = vf.f[v] & 1, vfl = vf.f[v] & 2;
+            const float* plane = sa.hm[s] + ((int64_t)v * B + b) * sa.sb[s] + (int64_t)c * sa.sc[s];
+            const int mya = vfl ? hs - 1 - yb : ya;                    // the footprint in memory coordinates
+            const int rows = min(yb - ya + 1, FH);
+            int mxa = hf ? ws - 1 - xb : xa;
+            if (sa.vec[s]) {
+                mxa &= ~3;
+                const int mxb = hf ? ws - 1 - xa : xb;
+                const int groups = min((mxb >> 2) - (mxa >> 2) + 1, FW / 4);
+                const int n = rows * groups;
+                for (int i = tid; i < n; i += 256) {
+                    const int r = i / groups, q = i - r * groups;
+                    const float4 t = *reinterpret_cast<const float4*>(plane + (int64_t)(mya + r) * ws + mxa + 4 * q);
+                    *reinterpret_cast<float4*>(&F[r][4 * q]) =
+                        make_float4(clamped_sigmoid(t.x), clamped_sigmoid(t.y), clamped_sigmoid(t.z), clamped_sigmoid(t.w));
+                }
+            } else {
+                const int cols = min(xb - xa + 1, FW);
+                const int n = rows * cols;
+                for (int i = tid; i < n; i += 256) {
+                    const int r = i / cols, q = i - r * cols;
+                    F[r][q] = clamped_sigmoid(plane[(int64_t)(mya + r) * ws + mxa + q]);
+                }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int j = 0; j < NA; ++j) {
+                const int i = tid + j * 256;
+                const int r = i / LWS, cc = i - r * LWS;
+                const int y = ty0 + r - HALO, x = tx0 + cc - HALO;
+                if (i < NC && y >= 0 && y < h && x >= 0 && x < w) {
+                    const int fx0 = (hf ? ws - 1 - X0[cc] : X0[cc]) - mxa, fx1 = (hf ? ws - 1 - X1[cc] : X1[cc]) - mxa;
+                    const int fy0 = (vfl ? hs - 1 - Y0[r] : Y0[r]) - mya, fy1 = (vfl ? hs - 1 - Y1[r] : Y1[r]) - mya;
+                    const float wx0 = WX0[cc], wx1 = WX1[cc], wy0 = WY0[r], wy1 = WY1[r];
+                    const float top = wx0 * F[fy0][fx0] + wx1 * F[fy0][fx1];
+                    const float bot = wx0 * F[fy1][fx0] + wx1 * F[fy1][fx1];
+                    const float rv = wy0 * top + wy1 * bot;
+                    acc[j] = acc[j] + rv;                              // 0 + r_{0,0} is r_{0,0}
+                }
+            }
+            __syncthreads();                                           // F and the tables are rewritten by the next view / scale
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < NA; ++j) {
+        const int i = tid + j * 256;
+        const int r = i / LWS, cc = i - r * LWS;
+        const int y = ty0 + r - HALO, x = tx0 + cc - HALO;
+        if (i < NC) Sm[r][cc + OFF - HALO] = (y >= 0 && y < h && x >= 0 && x < w) ? acc[j] * inv : -INFINITY;
+    }
+    __syncthreads();
+    for (int i = tid; i < LH * TW; i += 256) {
+        const int r = i / TW, cc = i - r * TW;
+        const float* p = &Sm[r][cc + OFF - HALO];
+        Hm[r][cc] = fmaxf(fmaxf(fmaxf(p[0], p[1]), fmaxf(p[2], p[3])), p[4]);
+    }
+    __syncthreads();
+    const int r = tid / (TW / 4), c4 = (tid - r * (TW / 4)) * 4;
+    const int y = ty0 + r, x = tx0 + c4;
+    if (y >= h) return;
+    float val[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float m = fmaxf(fmaxf(Hm[r][c4 + k], Hm[r + 1][c4 + k]), fmaxf(Hm[r + 2][c4 + k], Hm[r + 3][c4 + k]));
+        const float mx = fmaxf(m, Hm[r + 4][c4 + k]);
+        const float v = Sm[r + HALO][c4 + k + OFF];
+        val[k] = (v == mx) ? v : 0.0f;
+    }
+    float* dst = out + (((int64_t)b * C + c) * h + y) * w + x;
+    if (out_vec) {
+        if (x < w) *reinterpret_cast<float4*>(dst) = make_float4(val[0], val[1], val[2], val[3]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (x + k < w) dst[k] = val[k];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-static int check_views(const char* fn, int V, const unsigned char* view_flips, ViewFlips* vf) {
-    SD_REQUIRE(V == 2 || V == 4, SD_ERR_INVALID, "%s: V=%d views (2 or 4 are supported)", fn, V);
+template <int V>
+static void launch_merge_nms(bool vec, dim3 grid, hipStream_t st, const float* hm, int64_t sb, int64_t sc, int B, int C, int h, int w,
+                             int tiles_x, ViewFlips vf, float* out) {
+    if (vec) hipLaunchKernelGGL((k_tta_merge_nms<V, true>), grid, dim3(256), 0, st, hm, sb, sc, B, C, h, w, tiles_x, vf, out);
+    else     hipLaunchKernelGGL((k_tta_merge_nms<V, false>), grid, dim3(256), 0, st, hm, sb, sc, B, C, h, w, tiles_x, vf, out);
+}
+
+static int check_views(const char* fn, int V, const unsigned char* view_flips, ViewFlips* vf, bool single_view = false) {
+    SD_REQUIRE(V == 2 || V == 4 || (single_view && V == 1), SD_ERR_INVALID, "%s: V=%d views (%s are supported)", fn, V,
+               single_view ? "1, 2 or 4" : "2 or 4");
     SD_REQUIRE(view_flips != nullptr, SD_ERR_INVALID, "%s: null view_flips", fn);
     *vf = ViewFlips{{0, 0, 0, 0}};
     for (int v = 0; v < V; ++v) {
@@ -231,15 +387,62 @@ int sd_tta_merge_nms(const float* hm, int64_t sb, int64_t sc, float* out, int B,
     SD_REQUIRE(C <= 65535 && B <= 65535, SD_ERR_INVALID, "sd_tta_merge_nms: B=%d, C=%d exceed the grid (65535)", B, C);
     const int tiles_x = cdiv(w, TW), tiles_y = cdiv(h, TH);
     const bool vec = (w % 4 == 0) && aligned16(hm) && aligned16(out) && sb % 4 == 0 && sc % 4 == 0;
+    const dim3 grid(tiles_x * tiles_y, C, B);
+    const hipStream_t st = (hipStream_t)stream;
+    if (V == 2) launch_merge_nms<2>(vec, grid, st, hm, sb, sc, B, C, h, w, tiles_x, vf, out);
+    else        launch_merge_nms<4>(vec, grid, st, hm, sb, sc, B, C, h, w, tiles_x, vf, out);
+    SD_LAUNCH_CHECK();
+    return 0;
+}
+
+int sd_tta_scale_merge_nms(const float* const* hm_host, const int64_t* sb_host, const int64_t* sc_host, const int* hs_host,
+                           const int* ws_host, float* out, int B, int C, int h, int w, int S, int V,
+                           const unsigned char* view_flips_host, sd_stream_t stream) {
+    const char* fn = "sd_tta_scale_merge_nms";
+    SD_REQUIRE(hm_host != nullptr && sb_host != nullptr && sc_host != nullptr && hs_host != nullptr && ws_host != nullptr && out != nullptr,
+               SD_ERR_INVALID, "%s: null pointer", fn);
+    SD_REQUIRE(S >= 1 && S <= MAX_SCALES, SD_ERR_INVALID, "%s: S=%d scales (1 .. %d are supported)", fn, S, MAX_SCALES);
+    SD_REQUIRE(B > 0 && C > 0 && h > 0 && w > 0, SD_ERR_INVALID, "%s: bad shape (%d,%d,%d,%d)", fn, B, C, h, w);
+    ViewFlips vf;
+    if (int e = check_views(fn, V, view_flips_host, &vf, true)) return e;
+    SD_REQUIRE((int64_t)C * h * w < (1ll << 31), SD_ERR_INVALID, "%s: C*h*w must be < 2^31", fn);
+    SD_REQUIRE(C <= 65535 && B <= 65535, SD_ERR_INVALID, "%s: B=%d, C=%d exceed the grid (65535)", fn, B, C);
+    ScaleArgs sa{};
+    for (int s = 0; s < S; ++s) {
+        const int hs = hs_host[s], ws = ws_host[s];
+        SD_REQUIRE(hm_host[s] != nullptr, SD_ERR_INVALID, "%s: null pointer (scale %d)", fn, s);
+        SD_REQUIRE(hs >= 1 && ws >= 1, SD_ERR_INVALID, "%s: scale %d has an empty map (%d,%d)", fn, s, hs, ws);
+        // the bound that fits a tile's source footprint into LDS
+        SD_REQUIRE(hs <= 2 * (int64_t)h && ws <= 2 * (int64_t)w, SD_ERR_INVALID,
+                   "%s: scale %d map (%d,%d) is more than twice the base grid (%d,%d)", fn, s, hs, ws, h, w);
+        SD_REQUIRE(sc_host[s] >= (int64_t)hs * ws && sb_host[s] >= (int64_t)hs * ws, SD_ERR_INVALID,
+                   "%s: bad strides sb=%lld sc=%lld (scale %d)", fn, (long long)sb_host[s], (long long)sc_host[s], s);
+        sa.hm[s] = hm_host[s];
+        sa.sb[s] = sb_host[s];
+        sa.sc[s] = sc_host[s];
+        sa.hs[s] = hs;
+        sa.ws[s] = ws;
+        sa.rx[s] = (double)ws / (double)w;
+        sa.ry[s] = (double)hs / (double)h;
+        sa.vec[s] = (ws % 4 == 0) && aligned16(hm_host[s]) && sb_host[s] % 4 == 0 && sc_host[s] % 4 == 0;
+    }
+    const int tiles_x = cdiv(w, TW), tiles_y = cdiv(h, TH);
+    const bool out_vec = (w % 4 == 0) && aligned16(out);
     const dim3 grid(tiles_x * tiles_y, C, B), block(256);
     const hipStream_t st = (hipStream_t)stream;
-    if (V == 2) {
-        if (vec) hipLaunchKernelGGL((k_tta_merge_nms<2, true>), grid, block, 0, st, hm, sb, sc, B, C, h, w, tiles_x, vf, out);
-        else     hipLaunchKernelGGL((k_tta_merge_nms<2, false>), grid, block, 0, st, hm, sb, sc, B, C, h, w, tiles_x, vf, out);
-    } else {
-        if (vec) hipLaunchKernelGGL((k_tta_merge_nms<4, true>), grid, block, 0, st, hm, sb, sc, B, C, h, w, tiles_x, vf, out);
-        else     hipLaunchKernelGGL((k_tta_merge_nms<4, false>), grid, block, 0, st, hm, sb, sc, B, C, h, w, tiles_x, vf, out);
+    if (S == 1 && sa.hs[0] == h && sa.ws[0] == w) {
+        // nothing to resample (x0 = x, weights 1 and 0: the same values): the flip merge's kernel, whose sum stays in registers
+        const bool vec = out_vec && sa.vec[0];
+        if (V == 1)      launch_merge_nms<1>(vec, grid, st, sa.hm[0], sa.sb[0], sa.sc[0], B, C, h, w, tiles_x, vf, out);
+        else if (V == 2) launch_merge_nms<2>(vec, grid, st, sa.hm[0], sa.sb[0], sa.sc[0], B, C, h, w, tiles_x, vf, out);
+        else             launch_merge_nms<4>(vec, grid, st, sa.hm[0], sa.sb[0], sa.sc[0], B, C, h, w, tiles_x, vf, out);
+        SD_LAUNCH_CHECK();
+        return 0;
     }
+    const float inv = (float)(1.0 / (double)(S * V));
+    if (V == 1)      hipLaunchKernelGGL((k_tta_scale_merge_nms<1>), grid, block, 0, st, sa, S, inv, B, C, h, w, tiles_x, vf, (int)out_vec, out);
+    else if (V == 2) hipLaunchKernelGGL((k_tta_scale_merge_nms<2>), grid, block, 0, st, sa, S, inv, B, C, h, w, tiles_x, vf, (int)out_vec, out);
+    else             hipLaunchKernelGGL((k_tta_scale_merge_nms<4>), grid, block, 0, st, sa, S, inv, B, C, h, w, tiles_x, vf, (int)out_vec, out);
     SD_LAUNCH_CHECK();
     return 0;
 }

@@ -324,22 +324,46 @@ class ValidationAugmentation:
         """Per sample None or (cx, cy, partners), or None for the batch: validation never composes and never draws."""
         return None
 
+    @staticmethod
+    def size_groups(images):
+        """{(hin, win): (indices into the batch, stack of those images)} of what `__call__` accepts as `images`."""
+        if hasattr(images, "groups"):                                # data/feeder.py GroupedBatch: grouped by size and uploaded already
+            return images.groups
+        if isinstance(images, torch.Tensor) and images.dim() == 4:
+            return {tuple(images.shape[1:3]): (list(range(images.shape[0])), images)}
+        by_size = {}
+        for i, im in enumerate(images):
+            t = im if isinstance(im, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(im))
+            by_size.setdefault(tuple(t.shape[:2]), []).append((i, t))
+        return {k: ([i for i, _ in v], torch.stack([t for _, t in v])) for k, v in by_size.items()}
+
+    def images_at(self, images, size):
+        """The Resize + Normalize of `__call__` at another `size` = (width, height), from the same SOURCE images: the
+        (B, 3, height, width) tensor only.  No annotation is touched (`__call__` edits them in place, once) and nothing is drawn: this
+        is the plain validation transform, what the multi-scale test (model/tta.py ScaleTta) runs at its extra sizes."""
+        dev = self.args.device
+        W, H = size
+        groups = self.size_groups(images)
+        out = None
+        for (hin, win), (idx, stack) in groups.items():
+            if hasattr(stack, "pointers"):
+                res = preprocess_image_list(stack.pointers, hin, win, (W, H))
+            else:
+                res = preprocess_images(stack.to(dev, non_blocking=True), (W, H))
+            if len(groups) == 1:
+                return res
+            if out is None:
+                out = torch.empty((sum(len(i) for i, _ in groups.values()), 3, H, W), dtype=torch.float32, device=dev)
+            out[torch.as_tensor(idx, device=dev)] = res
+        return out
+
     def __call__(self, images, annotations):
         """images: list of (H, W, 3) uint8 arrays / tensors (any sizes) or one (B, H, W, 3) tensor; annotations: list of
         ImageAnnotation in ORIGINAL image pixels (modified in place like the reference's Resize / flips / Encode clip do on their
         copies).  Returns ((B, 3, height, width) fp32 device tensor, annotations in network-input pixels)."""
         dev = self.args.device
         W, H = self.size
-        if hasattr(images, "groups"):                                # data/feeder.py GroupedBatch: grouped by size and uploaded already
-            groups = images.groups
-        elif isinstance(images, torch.Tensor) and images.dim() == 4:
-            groups = {tuple(images.shape[1:3]): (list(range(images.shape[0])), images)}
-        else:
-            by_size = {}
-            for i, im in enumerate(images):
-                t = im if isinstance(im, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(im))
-                by_size.setdefault(tuple(t.shape[:2]), []).append((i, t))
-            groups = {k: ([i for i, _ in v], torch.stack([t for _, t in v])) for k, v in by_size.items()}
+        groups = self.size_groups(images)
         n = sum(len(idx) for idx, _ in groups.values())
         flips, jitter = self.draws_for(n)
         warps = self.affine_draws_for(n)

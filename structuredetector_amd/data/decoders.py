@@ -386,6 +386,6 @@ class FusedOutputDecoder(Decoder):
 
 
 class TtaOutput(dict):
-    """The four-key output of `model/tta.FlipTta`: `anchor_hm` / `part_hm` are merged, already suppressed PROBABILITY maps (the mean
+    """The four-key output of `model/tta.FlipTta` / `ScaleTta`: `anchor_hm` / `part_hm` are merged, already suppressed PROBABILITY maps (the mean
     over the mirrored views, after the 5x5 NMS), `offsets` / `embeddings` the unflipped view's.  A plain dict otherwise; the type is
     the mark `FusedOutputDecoder` checks before it hands out metadata."""

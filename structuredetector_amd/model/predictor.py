@@ -50,7 +50,10 @@ def batched_decodes(net, decoder, dataset, args, batch=None, workers=None, with_
         for group in BatchFeeder(dataset, index_batches(hi, batch, lo), args.device, workers=workers, depth=depth, cache=cache):
             with torch.no_grad():
                 images, anns = prepare(group, group.annotations)
-                out = net(images)
+                if getattr(net, "needs_sources", False):           # model/tta.py ScaleTta: its other sizes are resampled from the source images
+                    out = net(images, at_size=lambda size: prepare.images_at(group, size))
+                else:
+                    out = net(images)
                 if isinstance(out, torch.Tensor):  # Network(raw_output=True)
                     out = split_head(net, out)
                 handle = decoder.submit(out, with_raw_parts=with_raw_parts)
@@ -94,9 +97,10 @@ class Predictor(torch.nn.Module):
         self.model.eval().to(args.device)
         self.decoder = Decoder(args)
         self.tta = None
-        if getattr(args, "tta", "none") != "none":                                # --tta: mirrored views + merged heatmaps (model/tta.py)
-            from .tta import FlipTta, tta_decoder
-            self.tta, self.decoder = FlipTta(self.model, args, args.tta), tta_decoder(args)
+        if getattr(args, "tta", "none") != "none" or getattr(args, "tta_scales", ()):     # --tta / --tta_scales: views, sizes + merged heatmaps (model/tta.py)
+            from .tta import with_tta
+            net, self.decoder = with_tta(self.model, self.decoder, args)
+            self.tta = net if net is not self.model else None
 
     def forward(self, image):
         import numpy as np
@@ -105,4 +109,6 @@ class Predictor(torch.nn.Module):
         arr = torch.from_numpy(np.asarray(image.convert("RGB"), np.uint8).copy())[None].to(self.args.device)
         with torch.no_grad():
             x = preprocess_images(arr, (self.args.width, self.args.height))
+            if getattr(self.tta, "needs_sources", False):
+                return self.decoder(self.tta(x, at_size=lambda size: preprocess_images(arr, size)))[0]
             return self.decoder((self.tta or self.model)(x))[0]

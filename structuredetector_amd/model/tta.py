@@ -14,7 +14,14 @@ its data.  Per batch of B images:
      peak are not trustworthy (CenterNet's flip test makes the same choice).
 
 The merged maps are probabilities, already suppressed: they are decoded by `FusedOutputDecoder` (`tta_decoder`), never pushed back into
-the logit domain."""
+the logit domain.
+
+Multi-scale test (`--tta_scales`, `ScaleTta`): training draws its input size per epoch from the ratios 0.75 .. 1.25 rounded down to
+multiples of 32 (`TrainAugmentation.trigger_random_resize`), so a trained model has seen those sizes too.  Per batch the SOURCE images are
+resized + normalised to every size (each from the original pixels, like training; never from an already resized tensor), each size goes
+through steps 1 and 2, and ONE launch (`sd_tta_scale_merge_nms`) resamples the S x V heatmaps to the base grid (bilinear, half-pixel
+centres), averages them as probabilities and suppresses.  Offsets and embeddings are the base size's view 0: an embedding is in cells of
+its own scale."""
 from __future__ import annotations
 
 import ctypes as C
@@ -57,6 +64,106 @@ def tta_merge_nms(logits: torch.Tensor, flips) -> torch.Tensor:
     return out
 
 
+MAX_SCALES = 5                      # sd_tta_scale_merge_nms takes up to 5 sizes
+
+
+def scale_sizes(args, ratios):
+    """The (width, height) input sizes of the multi-scale test, the base size first: every ratio r gives (int(r*W/32)*32, int(r*H/32)*32)
+    -- `TrainAugmentation.trigger_random_resize`'s rule -- in the order given; sizes equal to the base or to an earlier one are dropped."""
+    W, H = int(args.width), int(args.height)
+    sizes = [(W, H)]
+    for r in ratios:
+        size = (int(r * W / 32) * 32, int(r * H / 32) * 32)
+        if min(size) < 32:
+            raise L.SdError(f"tta_scales: ratio {r} of {W} x {H} rounds to {size[0]} x {size[1]} (every side must be at least 32)")
+        if size not in sizes:
+            sizes.append(size)
+    if len(sizes) > MAX_SCALES:
+        raise L.SdError(f"tta_scales: {len(sizes)} distinct input sizes ({', '.join(f'{w} x {h}' for w, h in sizes)}); at most {MAX_SCALES} "
+                        "(the base size included) are supported")
+    return sizes
+
+
+def tta_scale_merge_nms(logits, flips, base_hw) -> torch.Tensor:
+    """S heatmap-logit tensors (V*B, C, hs, ws), one per scale (channel-slice views pass without a copy) -> (B, C, h, w) on the base grid
+    `base_hw` = (h, w): nms(mean over scales and views of the bilinearly resampled clamped sigmoid), one launch
+    (`sd_tta_scale_merge_nms`).  flips: the views of every scale (`VIEW_FLIPS[mode]`, or (0,) for one view)."""
+    L.require_cuda(*logits)
+    S, V = len(logits), len(flips)
+    h, w = base_hw
+    views = [L.map_view(t) for t in logits]
+    VB, Cc = views[0][0].shape[:2]
+    if VB % V:
+        raise L.SdError(f"tta_scale_merge_nms: {VB} images are not {V} views of a batch")
+    for t, *_ in views:
+        if t.shape[:2] != (VB, Cc) or t.device != views[0][0].device:
+            raise L.SdError(f"tta_scale_merge_nms: scales disagree: {[tuple(v[0].shape) for v in views]}")
+    out = torch.empty((VB // V, Cc, h, w), dtype=torch.float32, device=views[0][0].device)
+    L.check(L.lib().sd_tta_scale_merge_nms((C.c_void_p * S)(*[v[1] for v in views]), (C.c_int64 * S)(*[v[2] for v in views]),
+                                           (C.c_int64 * S)(*[v[3] for v in views]), (C.c_int * S)(*[v[0].shape[2] for v in views]),
+                                           (C.c_int * S)(*[v[0].shape[3] for v in views]), out.data_ptr(), VB // V, Cc, h, w, S, V,
+                                           (C.c_ubyte * V)(*flips), L.stream()), "sd_tta_scale_merge_nms")
+    return out
+
+
+def head_parts(out, M, nb):
+    """A forward's output -> ([heatmap tensors to merge], offsets, embeddings): the M + N heatmap channels as ONE (no-copy) tensor when
+    they are adjacent slices of one head tensor, else [anchor_hm, part_hm]."""
+    if isinstance(out, torch.Tensor):                                  # Network(raw_output=True)
+        return [out[:, :nb]], out[:, nb:nb + 2], out[:, nb + 2:nb + 4]
+    a, p = out["anchor_hm"], out["part_hm"]
+    if (a.dtype == p.dtype and a.stride() == p.stride() and a.shape[1] == M
+            and p.data_ptr() == a.data_ptr() + M * a.stride(1) * a.element_size()):
+        return [a.as_strided((a.shape[0], nb, a.shape[2], a.shape[3]), a.stride())], out["offsets"], out["embeddings"]
+    return [a, p], out["offsets"], out["embeddings"]
+
+
+class ScaleTta:
+    """`net` behind the multi-scale test, combined with the flip views of `mode` ("none": one view):
+    `ScaleTta(net, args, sizes, mode)(images, at_size=f)` -- `images` the batch at the base size `sizes[0]`, `f((width, height))` the same
+    source images resized + normalised to another size -- returns a `TtaOutput` like `FlipTta`: S forwards of V*B images, one merge
+    launch, the base size's view-0 offsets / embeddings (no copy).  `needs_sources` tells the callers to pass `at_size`."""
+
+    needs_sources = True
+
+    def __init__(self, net, args, sizes, mode="none"):
+        if mode != "none" and mode not in VIEW_FLIPS:
+            raise L.SdError(f"unknown test-time augmentation mode {mode!r} (one of {', '.join(MODES)})")
+        sizes = [tuple(int(v) for v in s) for s in sizes]
+        if not 1 <= len(sizes) <= MAX_SCALES or len(set(sizes)) != len(sizes) or any(v < 32 or v % 32 for s in sizes for v in s):
+            raise L.SdError(f"ScaleTta: 1 to {MAX_SCALES} distinct (width, height) sizes, multiples of 32, base first; got {sizes}")
+        self.net, self.args, self.sizes, self.mode = net, args, sizes, mode
+        self.flips = VIEW_FLIPS.get(mode, (0,))
+        self.label_count, self.part_count = len(args.labels), len(args.parts)
+
+    def __call__(self, images, at_size=None):
+        if at_size is None and len(self.sizes) > 1:
+            raise L.SdError("ScaleTta resamples every size from the source images: call it with at_size=(a callable (width, height) -> "
+                            "the preprocessed batch at that size); a preprocessed tensor alone is not enough")
+        B = images.shape[0]
+        W0, H0 = self.sizes[0]
+        if tuple(images.shape[2:]) != (H0, W0):
+            raise L.SdError(f"ScaleTta: the batch is {images.shape[3]} x {images.shape[2]}, the base size {W0} x {H0}")
+        M, nb = self.label_count, self.label_count + self.part_count
+        heat, offsets, embeddings = [], None, None
+        for i, size in enumerate(self.sizes):
+            x = images if i == 0 else at_size(size)
+            if tuple(x.shape) != (B, 3, size[1], size[0]):
+                raise L.SdError(f"ScaleTta: at_size({size}) returned {tuple(x.shape)}, expected {(B, 3, size[1], size[0])}")
+            hm, off, emb = head_parts(self.net(tta_views(x, self.flips) if len(self.flips) > 1 else x), M, nb)
+            heat.append(hm)
+            if i == 0:
+                offsets, embeddings = off[:B], emb[:B]
+        base_hw = tuple(heat[0][0].shape[2:])
+        if all(len(hm) == 1 for hm in heat):
+            merged = tta_scale_merge_nms([hm[0] for hm in heat], self.flips, base_hw)
+            anchor_hm, part_hm = merged[:, :M], merged[:, M:]
+        else:
+            heat = [hm if len(hm) == 2 else [hm[0][:, :M], hm[0][:, M:]] for hm in heat]
+            anchor_hm, part_hm = (tta_scale_merge_nms([hm[k] for hm in heat], self.flips, base_hw) for k in (0, 1))
+        return TtaOutput(anchor_hm=anchor_hm, part_hm=part_hm, offsets=offsets, embeddings=embeddings)
+
+
 class FlipTta:
     """`net` behind flip test-time augmentation: `FlipTta(net, args, mode)(images)` returns the usual four-key output (a `TtaOutput`):
     `anchor_hm` / `part_hm` are the merged, suppressed PROBABILITY maps, `offsets` / `embeddings` view 0's (no copy).  Decode it with
@@ -72,21 +179,12 @@ class FlipTta:
     def __call__(self, images):
         B = images.shape[0]
         M, nb = self.label_count, self.label_count + self.part_count
-        out = self.net(tta_views(images, self.flips))
-        if isinstance(out, torch.Tensor):                              # Network(raw_output=True)
-            hm, offsets, embeddings = out[:, :nb], out[:, nb:nb + 2], out[:, nb + 2:nb + 4]
-        else:
-            a, p, offsets, embeddings = out["anchor_hm"], out["part_hm"], out["offsets"], out["embeddings"]
-            if (a.dtype == p.dtype and a.stride() == p.stride() and a.shape[1] == M
-                    and p.data_ptr() == a.data_ptr() + M * a.stride(1) * a.element_size()):
-                hm = a.as_strided((a.shape[0], nb, a.shape[2], a.shape[3]), a.stride())      # adjacent slices of one head tensor: one launch
-            else:
-                hm = None
-        if hm is not None:
-            merged = tta_merge_nms(hm, self.flips)
+        heat, offsets, embeddings = head_parts(self.net(tta_views(images, self.flips)), M, nb)
+        if len(heat) == 1:                                             # adjacent slices of one head tensor: one launch
+            merged = tta_merge_nms(heat[0], self.flips)
             anchor_hm, part_hm = merged[:, :M], merged[:, M:]
         else:
-            anchor_hm, part_hm = tta_merge_nms(a, self.flips), tta_merge_nms(p, self.flips)
+            anchor_hm, part_hm = tta_merge_nms(heat[0], self.flips), tta_merge_nms(heat[1], self.flips)
         return TtaOutput(anchor_hm=anchor_hm, part_hm=part_hm, offsets=offsets[:B], embeddings=embeddings[:B])
 
 
@@ -96,8 +194,17 @@ def tta_decoder(args) -> FusedOutputDecoder:
 
 
 def with_tta(net, decoder, args):
-    """(net, decoder) as they are for `--tta none` (or no such attribute); otherwise `net` behind `FlipTta` and its decoder."""
+    """(net, decoder) as they are for `--tta none` and no `--tta_scales` (or no such attributes); `net` behind `FlipTta` for a flip mode
+    alone; `net` behind `ScaleTta` when `--tta_scales` adds at least one input size.  Both come with `tta_decoder(args)`."""
+    from ..utils.args import parse_tta_scales
     mode = getattr(args, "tta", "none") or "none"
+    ratios = parse_tta_scales(getattr(args, "tta_scales", "") or "")
+    if ratios:
+        sizes = scale_sizes(args, ratios)
+        if len(sizes) > 1:
+            return ScaleTta(net, args, sizes, mode), tta_decoder(args)
+        print(f"tta_scales: every ratio of {', '.join(f'{r:g}' for r in ratios)} rounds to the base size {sizes[0][0]} x {sizes[0][1]}: "
+              "single-scale inference")
     if mode == "none":
         return net, decoder
     return FlipTta(net, args, mode), tta_decoder(args)

@@ -70,6 +70,11 @@ _FLAGS = [
                       "detect / Predictor: the network also runs on the mirrored image(s) (2 views for hflip and vflip, 4 for hvflip: the "
                       "forward sees that many times --eval_batch images), the heatmaps are averaged and decoded once. Not consulted by "
                       "train: its validation pass computes the loss from the plain head output.")),
+    (("--tta_scales",), dict(type=str, default="", metavar="R[,R...]", help="Multi-scale test-time augmentation in evaluate / detect / "
+                             "Predictor: comma-separated input-size ratios in [0.5, 2] (e.g. 0.75,1.25; the ratio 1 is implied). The network "
+                             "also runs at int(R*W/32)*32 x int(R*H/32)*32 -- training's multi-scale rule, each size resampled from the source "
+                             "image, at most 5 sizes -- the heatmaps are resampled to the base grid, averaged and decoded once. Combines "
+                             "with --tta. Not consulted by train. Empty = off.")),
     (("--aug_rotate",), dict(type=float, default=0.0, metavar="DEG", help="Training augmentation: rotate every image about its centre by an "
                              "angle uniform in [-DEG, DEG] (0 .. 180; what leaves the frame is dropped from the annotation, what the image does "
                              "not cover is filled with the ImageNet mean; 0 = off). Not consulted by evaluate / detect.")),
@@ -96,6 +101,21 @@ def _name_map(value):
     return {value: 0}
 
 
+def parse_tta_scales(text):
+    """`--tta_scales`: "0.75,1.25" (or an already parsed sequence) -> the tuple of ratios, each in [0.5, 2]; "" -> ()."""
+    if not isinstance(text, str):
+        ratios = tuple(float(r) for r in text)
+    else:
+        try:
+            ratios = tuple(float(t) for t in text.split(",")) if text.strip() else ()
+        except ValueError:
+            raise ValueError(f"'tta_scales' should be a comma-separated list of ratios (e.g. 0.75,1.25), not {text!r}") from None
+    for r in ratios:
+        if not 0.5 <= r <= 2:                       # (also false for nan)
+            raise ValueError(f"'tta_scales' ratios should be in [0.5, 2], not {r}")
+    return ratios
+
+
 def finalize(args):
     """Validation + derived fields (args.py:178-269) on an already parsed namespace."""
     for side in ("width", "height"):
@@ -116,6 +136,7 @@ def finalize(args):
     assert 0 <= getattr(args, "aug_scale", 0.0) < 1, "'aug_scale' should be in [0, 1["
     assert 0 <= getattr(args, "aug_translate", 0.0) <= 0.5, "'aug_translate' should be in [0, 0.5]"
     assert 0 <= getattr(args, "aug_mosaic", 0.0) <= 1, "'aug_mosaic' should be in [0, 1]"
+    args.tta_scales = parse_tta_scales(getattr(args, "tta_scales", ""))
 
     args.lr_step = int(args.epochs / args.lr_step) if args.lr_step != 0 else args.epochs
     for k in ("train_dir", "valid_dir", "pretrained_model"):
