@@ -223,6 +223,37 @@ int sd_tta_scale_merge_nms(const float* const* hm_host, const int64_t* sb_host, 
                            const int* ws_host, float* out, int B, int C, int h, int w, int S, int V,
                            const unsigned char* view_flips_host, sd_stream_t stream);
 
+/* ---- tiled inference (no reference counterpart: the reference resizes the whole image to one network input) ----
+ * A canvas of Wc = Tx*W - (Tx-1)*O by Hc = Ty*H - (Ty-1)*O pixels is cut into Ty x Tx overlapping tiles of the network's own input size
+ * W x H; tile (j, i) starts at pixel (j*(H-O), i*(W-O)); tile t = j*Tx + i of image b is image t*B + b (the ordering of sd_tta_views).
+ * 1 <= Tx, Ty <= 8 and 0 <= 2*O <= min(H, W) (at most two tiles cover a cell along an axis); all geometry is validated on the host
+ * before any HIP call, anything else is SD_ERR_INVALID.  Both functions are one launch each, use no workspace, no atomics and no host
+ * synchronisation, and are deterministic.
+ *
+ * sd_tile_views: canvas (B,3,Hc,Wc) fp32 NCHW contiguous -> out (Ty*Tx*B,3,H,W):
+ *       out[t*B + b, c, y, x] = canvas[b, c, j*(H-O) + y, i*(W-O) + x].
+ *   Requires Wc == Tx*W - (Tx-1)*O and Hc == Ty*H - (Ty-1)*O.  16-byte accesses when W, O and Wc are multiples of 4 and the pointers
+ *   are 16-byte aligned, 4-byte accesses otherwise.
+ *
+ * sd_tile_merge_nms: all sizes in cells.  `hm` = the heatmap logits of the T*B tile forwards, a strided (sb, sc) (T*B, C, h, w)
+ *   channel-slice view; `reg` a strided (r_sb, r_sc) (T*B, R, h, w) view of the regression channels (offsets + embeddings; R = 0 with
+ *   null pointers is allowed).  out_hm (B,C,hc,wc) and out_reg (B,R,hc,wc) contiguous, wc = Tx*w - (Tx-1)*o, hc = Ty*h - (Ty-1)*o.
+ *   Per axis, shown for x (y alike): for canvas column X, i_hi = min(X / (w-o), Tx-1) and l = X - i_hi*(w-o).  If i_hi > 0 and l < o two
+ *   tiles cover the column: tile i_hi-1 at local column l + (w-o) with weight w_lo = (float)((double)(o-l) / (double)(o+1)), and tile
+ *   i_hi at local column l with weight w_hi = (float)((double)(l+1) / (double)(o+1)).  Otherwise only tile i_hi covers it, weight 1.0f.
+ *   Heatmaps: for every covering tile in ascending t order (row-major)  p = clamped_sigmoid(logit) -- the device function behind
+ *   sd_clamped_sigmoid --, wt = wy * wx, c = wt * p; m = the sum of the c in that order, every fp32 operation rounded separately;
+ *   out_hm = m where m equals the 5x5 maximum of m over the canvas, else 0: seams get no special treatment, padding (-inf) and ties
+ *   exactly as sd_nms5.  Regressions: out_reg is a bit copy from the owner tile; per axis the owner is the covering tile with the
+ *   larger weight, the lower-index tile on a tie (o odd, l = (o-1)/2).  Offsets are sub-cell and embeddings displacements in cells:
+ *   both are translation-invariant and need no correction.
+ *   Consequences: Tx = Ty = 1 equals sd_nms5(apply_sigmoid = 1) bit for bit; o = 0 equals sd_nms5 of the concatenated tile maps; every
+ *   cell covered by a single tile keeps its probability unchanged.  16-byte loads when w and o are multiples of 4 and planes / strides
+ *   are 16-byte aligned, 4-byte loads otherwise. */
+int sd_tile_views(const float* canvas, float* out, int B, int Hc, int Wc, int H, int W, int Ty, int Tx, int O, sd_stream_t stream);
+int sd_tile_merge_nms(const float* hm, int64_t sb, int64_t sc, int C, const float* reg, int64_t r_sb, int64_t r_sc, int R,
+                      float* out_hm, float* out_reg, int B, int h, int w, int Ty, int Tx, int o, sd_stream_t stream);
+
 /* ---- target rendering: src/sdnet/data/transforms.py:130-205 (Encode) ---------------------- */
 
 /* Heatmaps of a batch (transforms.py:143,160-161,173-174; utils.py:418-419): for every pixel of

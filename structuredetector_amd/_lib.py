@@ -76,6 +76,9 @@ _SIGNATURES = {
     "sd_tta_merge_nms": (c_int, _MAP + [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp]),
     # multi-scale: hm / sb / sc / hs / ws (HOST arrays of S entries), out, B, C, h, w, S, V, view_flips, stream
     "sd_tta_scale_merge_nms": (c_int, [c_vp] * 6 + [c_int] * 6 + [c_vp, c_vp]),
+    # tiled inference: canvas, out, B, Hc, Wc, H, W, Ty, Tx, O, stream / hm map, C, reg map, R, out_hm, out_reg, B, h, w, Ty, Tx, o, stream
+    "sd_tile_views": (c_int, [c_vp, c_vp] + [c_int] * 8 + [c_vp]),
+    "sd_tile_merge_nms": (c_int, _MAP + [c_int] + _MAP + [c_int, c_vp, c_vp] + [c_int] * 6 + [c_vp]),
     "sd_preprocess_workspace_bytes": (c_size, [c_int] * 4),
     "sd_preprocess_images": (c_int, [c_vp] + [c_int] * 5 + [c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp, C.POINTER(c_float), C.POINTER(c_float),
                                                 c_vp, c_vp, c_size, c_vp]),

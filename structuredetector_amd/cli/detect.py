@@ -38,7 +38,7 @@ def _detect(argv):
     if args.pretrained_model:
         net.load_state_dict(torch.load(args.pretrained_model, map_location="cpu", weights_only=True))
     net = net.eval().to(args.device)
-    if getattr(args, "tta", "none") != "none" or getattr(args, "tta_scales", ()):
+    if getattr(args, "tta", "none") != "none" or getattr(args, "tta_scales", ()) or getattr(args, "tiles", ()):
         from ..model.tta import with_tta
         net, decoder = with_tta(net, decoder, args)
     out_dir = Path("predictions")

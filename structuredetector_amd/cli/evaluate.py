@@ -28,6 +28,16 @@ def main(argv=None):
             dist.destroy_process_group()
 
 
+def refuse_synthetic_resampling(args):
+    """`--synthetic` renders network-input tensors: the options that resample the SOURCE image at another size have nothing to resample."""
+    if args.synthetic and getattr(args, "tta_scales", ()):
+        raise SystemExit("--tta_scales resamples every input size from the source images; --synthetic renders its samples as network-input "
+                         "tensors and has no source image to resample: evaluate a directory (--valid_dir) or drop --tta_scales")
+    if args.synthetic and getattr(args, "tiles", ()):
+        raise SystemExit("--tiles resamples its canvas from the source images; --synthetic renders its samples as network-input tensors and "
+                         "has no source image to resample: evaluate a directory (--valid_dir) or drop --tiles")
+
+
 def _evaluate(argv):
     args = Arguments().parse(argv)
     assert args.synthetic or args.valid_dir, "Path to a directory with validation samples must be specified."
@@ -40,10 +50,8 @@ def _evaluate(argv):
     if args.pretrained_model:
         net.load_state_dict(torch.load(args.pretrained_model, map_location="cpu", weights_only=True))
     net = net.eval().to(args.device)
-    if args.synthetic and getattr(args, "tta_scales", ()):
-        raise SystemExit("--tta_scales resamples every input size from the source images; --synthetic renders its samples as network-input "
-                         "tensors and has no source image to resample: evaluate a directory (--valid_dir) or drop --tta_scales")
-    if getattr(args, "tta", "none") != "none" or getattr(args, "tta_scales", ()):      # --tta / --tta_scales: the views, the forwards and the merge sit inside the per-batch step
+    refuse_synthetic_resampling(args)
+    if getattr(args, "tta", "none") != "none" or getattr(args, "tta_scales", ()) or getattr(args, "tiles", ()):      # --tta / --tta_scales: the views, the forwards and the merge sit inside the per-batch step
         from ..model.tta import with_tta
         net, decoder = with_tta(net, decoder, args)
     if args.synthetic:

@@ -1,5 +1,5 @@
 from .dataset import CropDataset, PredictionDataset, collate_fn
-from .decoders import Decoder, FusedOutputDecoder, RawDecoder
+from .decoders import Decoder, FusedOutputDecoder, RawDecoder, TiledOutputDecoder
 from .transforms import Encode
 from .augment import (TrainAugmentation, ValidationAugmentation, affine_forward_matrix, affine_inverse_matrix, mosaic_tiles, pil_bilinear_coeffs,
                       preprocess_image_list, preprocess_images)

@@ -222,7 +222,7 @@ class Decoder:
     def _assemble(self, host, B, out_h, out_w, conf_thresh, want_raw):
         """decoders.py:103-159 on the host copy of the packed result: (annotations, raw_parts or None).  Values leave numpy ONCE
         (`tolist()`: float(np.float32) == tensor.item()); the per-image loops run on plain Python lists."""
-        in_h, in_w = int(self.down_ratio * out_h), int(self.down_ratio * out_w)       # decoders.py:41
+        in_h, in_w = self._input_size(out_h, out_w)                                    # decoders.py:41
         sx, sy = in_w / out_w, in_h / out_h                                            # utils.py:19-26
         anchor_all, part_all, assign_all = host["anchor_out"].tolist(), host["part_out"].tolist(), host["assign"].tolist()
         label_map, part_map, anchor_name = self.label_map, self.part_map, self.anchor_name
@@ -244,6 +244,10 @@ class Decoder:
             if want_raw:                                                               # decoders.py:142-159: skip score < conf
                 raw_parts.append([Keypoint(part_map[int(pt[3])], pt[0] * sx, pt[1] * sy, pt[2]) for pt in parts_b if not pt[2] < conf_thresh])
         return annotations, raw_parts
+
+    def _input_size(self, out_h, out_w):
+        """(rows, columns) of the network input the annotations are reported in, for an (out_h, out_w) output map."""
+        return int(self.down_ratio * out_h), int(self.down_ratio * out_w)
 
     def submit(self, outputs, conf_thresh=None, dist_thresh=None, with_raw_parts=False):
         """The device stage of `__call__` WITHOUT the host wait: launches the decoder, starts the copy of the packed result into a pinned
@@ -370,8 +374,13 @@ class FusedOutputDecoder(Decoder):
         packed = torch.empty(lib.sd_decode_packed_words(B, K, P), dtype=torch.int32, device=o.device)
         L.check(lib.sd_decode_group(a_s.data_ptr(), a_i.data_ptr(), a_c.data_ptr(), p_s.data_ptr(), p_i.data_ptr(), p_c.data_ptr(),
                                     o_p, o_sb, o_sc, e_p, e_sb, e_sc, B, h, w, K, P, float(np.float32(conf_thresh)),
-                                    float(np.float32(dist_thresh * min(w, h))), packed.data_ptr(), L.stream()), "sd_decode_group")
+                                    float(np.float32(dist_thresh * self._linkage_side(h, w))), packed.data_ptr(), L.stream()),
+                "sd_decode_group")
         return packed, (B, K, P, h, w)
+
+    def _linkage_side(self, h, w):
+        """The side (in cells) the linkage radius `decoder_dist_thresh` is a fraction of: the smaller side of the decoded map."""
+        return min(w, h)
 
     def _call_low_latency(self, outputs, conf_thresh, dist_thresh):
         return None                                   # (the one-launch kernel starts from logits; this class starts from NMS'ed maps)
@@ -383,6 +392,33 @@ class FusedOutputDecoder(Decoder):
             raise L.SdError("FusedOutputDecoder: the full metadata of a test-time-augmentation output is not defined (its heatmaps are "
                             "merged probabilities, not logits); ask for metadata_fields within ('annotation', 'raw_parts')")
         return super().__call__(outputs, conf_thresh, dist_thresh, return_metadata, metadata_fields)
+
+
+class TiledOutputDecoder(FusedOutputDecoder):
+    """The decoder of `model/tiles.TiledNet`'s output: maps on the CANVAS grid (hc, wc) of `grid` = (Tx, Ty) tiles that overlap by
+    `overlap_cells`.  Objects are at the tile's scale, so the linkage radius is `decoder_dist_thresh * min(w, h)` of the TILE map; the
+    annotations come back in network-input pixels (W x H) like every other path -- cell * W / wc, cell * H / hc -- so `Evaluator`,
+    `detect`'s resize back to the original image and the rank sharding stay as they are."""
+
+    def __init__(self, args, grid, overlap_cells):
+        super().__init__(args)
+        self.grid = tuple(int(v) for v in grid)
+        self.overlap_cells = int(overlap_cells)
+
+    def tile_map(self, hc, wc):
+        """(h, w) of one tile's map for a canvas map (hc, wc)."""
+        tx, ty = self.grid
+        h, w = (hc + (ty - 1) * self.overlap_cells) // ty, (wc + (tx - 1) * self.overlap_cells) // tx
+        if (ty * h - (ty - 1) * self.overlap_cells, tx * w - (tx - 1) * self.overlap_cells) != (hc, wc):
+            raise L.SdError(f"TiledOutputDecoder: a {wc} x {hc} map is not {tx} x {ty} tiles with an overlap of {self.overlap_cells} cells")
+        return h, w
+
+    def _linkage_side(self, hc, wc):
+        return min(self.tile_map(hc, wc))
+
+    def _input_size(self, out_h, out_w):
+        h, w = self.tile_map(out_h, out_w)
+        return int(self.down_ratio * h), int(self.down_ratio * w)
 
 
 class TtaOutput(dict):

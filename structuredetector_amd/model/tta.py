@@ -194,11 +194,19 @@ def tta_decoder(args) -> FusedOutputDecoder:
 
 
 def with_tta(net, decoder, args):
-    """(net, decoder) as they are for `--tta none` and no `--tta_scales` (or no such attributes); `net` behind `FlipTta` for a flip mode
-    alone; `net` behind `ScaleTta` when `--tta_scales` adds at least one input size.  Both come with `tta_decoder(args)`."""
-    from ..utils.args import parse_tta_scales
+    """(net, decoder) as they are for `--tta none`, no `--tta_scales` and no `--tiles` (or no such attributes); `net` behind `FlipTta` for
+    a flip mode alone; `net` behind `ScaleTta` when `--tta_scales` adds at least one input size.  Both come with `tta_decoder(args)`.
+    `--tiles` (model/tiles.py) puts `net` behind `TiledNet` with its `tiled_decoder`, and is refused together with the other two."""
+    from ..utils.args import parse_tiles, parse_tta_scales
     mode = getattr(args, "tta", "none") or "none"
     ratios = parse_tta_scales(getattr(args, "tta_scales", "") or "")
+    grid = parse_tiles(getattr(args, "tiles", "") or "")
+    if grid:
+        if mode != "none" or ratios:
+            raise L.SdError("--tiles does not combine with --tta / --tta_scales: the tile outputs are stitched as they are; drop one of them")
+        from .tiles import TiledNet, tiled_decoder
+        overlap = getattr(args, "tile_overlap", 64)
+        return TiledNet(net, args, grid, overlap), tiled_decoder(args, grid, overlap)
     if ratios:
         sizes = scale_sizes(args, ratios)
         if len(sizes) > 1:

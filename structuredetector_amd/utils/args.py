@@ -75,6 +75,14 @@ _FLAGS = [
                              "also runs at int(R*W/32)*32 x int(R*H/32)*32 -- training's multi-scale rule, each size resampled from the source "
                              "image, at most 5 sizes -- the heatmaps are resampled to the base grid, averaged and decoded once. Combines "
                              "with --tta. Not consulted by train. Empty = off.")),
+    (("--tiles",), dict(type=str, default="", metavar="CxR", help="Tiled inference in evaluate / detect / Predictor: columns x rows of "
+                        "overlapping tiles (e.g. 2x2 or 3x2, each 1 .. 8). The source image is resized to a canvas of C*W - (C-1)*O by "
+                        "R*H - (R-1)*O pixels (O = --tile_overlap), the network runs on every W x H tile -- the forward sees C*R times "
+                        "--eval_batch images; --eval_batch keeps counting images -- and the tile heatmaps are stitched, blended over the "
+                        "seams and decoded once. The canvas holds C*R times the area: raise --max_objects / --max_parts with it. Does not "
+                        "combine with --tta / --tta_scales. Not consulted by train. Empty or 1x1 = off.")),
+    (("--tile_overlap",), dict(type=int, default=64, metavar="PX", help="Pixels two neighbouring tiles of --tiles share: a multiple of 32 "
+                               "in [0, min(W, H) / 2].")),
     (("--aug_rotate",), dict(type=float, default=0.0, metavar="DEG", help="Training augmentation: rotate every image about its centre by an "
                              "angle uniform in [-DEG, DEG] (0 .. 180; what leaves the frame is dropped from the annotation, what the image does "
                              "not cover is filled with the ImageNet mean; 0 = off). Not consulted by evaluate / detect.")),
@@ -116,6 +124,51 @@ def parse_tta_scales(text):
     return ratios
 
 
+MAX_TILES = 8                       # tiles per axis (sd_tile_views / sd_tile_merge_nms)
+
+
+def parse_tiles(text):
+    """`--tiles`: "3x2" (columns x rows; or an already parsed pair) -> (Tx, Ty), each in 1 .. 8; "" and "1x1" -> () (off)."""
+    if not isinstance(text, str):
+        grid = tuple(text)
+        if len(grid) not in (0, 2) or any(int(v) != v for v in grid):
+            raise ValueError(f"'tiles' should be COLUMNSxROWS (e.g. 2x2), not {text!r}")
+        grid = tuple(int(v) for v in grid)
+    else:
+        fields = text.strip().lower().split("x") if text.strip() else []
+        try:
+            grid = tuple(int(f) for f in fields)
+        except ValueError:
+            grid = None
+        if grid is None or len(grid) not in (0, 2):
+            raise ValueError(f"'tiles' should be COLUMNSxROWS (e.g. 2x2), not {text!r}")
+    for v in grid:
+        if not 1 <= v <= MAX_TILES:
+            raise ValueError(f"'tiles' should have 1 to {MAX_TILES} tiles per axis, not {v}")
+    return () if grid == (1, 1) else grid
+
+
+def check_tile_overlap(overlap, width, height):
+    """`--tile_overlap` against the network input: a multiple of 32 in [0, min(W, H) / 2]; returns it as an int."""
+    if int(overlap) != overlap or overlap % 32:
+        raise ValueError(f"'tile_overlap' should be a multiple of 32, not {overlap}")
+    if not 0 <= 2 * overlap <= min(width, height):
+        raise ValueError(f"'tile_overlap' should be in [0, {min(width, height) // 2}] (half the smaller side of {width} x {height}), not {overlap}")
+    return int(overlap)
+
+
+def tile_canvas(width, height, grid, overlap):
+    """(Wc, Hc) = (Tx*W - (Tx-1)*O, Ty*H - (Ty-1)*O): the canvas Tx x Ty tiles of W x H with overlap O cover."""
+    tx, ty = grid
+    return tx * width - (tx - 1) * overlap, ty * height - (ty - 1) * overlap
+
+
+def tile_origins(width, height, grid, overlap):
+    """The (row, column) pixel at which tile t = j*Tx + i starts: (j*(H-O), i*(W-O)), in t order."""
+    tx, ty = grid
+    return [(j * (height - overlap), i * (width - overlap)) for j in range(ty) for i in range(tx)]
+
+
 def finalize(args):
     """Validation + derived fields (args.py:178-269) on an already parsed namespace."""
     for side in ("width", "height"):
@@ -137,6 +190,9 @@ def finalize(args):
     assert 0 <= getattr(args, "aug_translate", 0.0) <= 0.5, "'aug_translate' should be in [0, 0.5]"
     assert 0 <= getattr(args, "aug_mosaic", 0.0) <= 1, "'aug_mosaic' should be in [0, 1]"
     args.tta_scales = parse_tta_scales(getattr(args, "tta_scales", ""))
+    args.tiles = parse_tiles(getattr(args, "tiles", ""))
+    args.tile_overlap = check_tile_overlap(getattr(args, "tile_overlap", 64), args.width, args.height) if args.tiles \
+        else getattr(args, "tile_overlap", 64)
 
     args.lr_step = int(args.epochs / args.lr_step) if args.lr_step != 0 else args.epochs
     for k in ("train_dir", "valid_dir", "pretrained_model"):
