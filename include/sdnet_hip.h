@@ -344,6 +344,31 @@ int sd_preprocess_images_list_mosaic(const uint8_t* const* images, int B, int Hi
                                      const double* mosaic_affine, const uint8_t fill3[3], const float* mean3, const float* std3, float* out,
                                      void* workspace, size_t workspace_bytes, sd_stream_t stream);
 
+/* Every pipeline above on a WINDOW of the resized image (crop training at the tile scale, `train --train_tiles`): image b's resize target is
+ * a (Hc, Wc) canvas of which only the (Hout, Wout) window at (x0_b, y0_b) is produced -- byte for byte
+ * Image.resize((Wc, Hc), BILINEAR).crop((x0, y0, x0 + Wout, y0 + Hout)) -- and everything after the resize works on that window:
+ * Window -> [Mosaic] -> [RandomAffine] -> [ColorJitter] -> flips -> Normalize at (Hout, Wout).  h_bounds / h_kk and v_bounds / v_kk are
+ * the tables of Win -> Wc and Hin -> Hc.  window (B, 2) int32 on the DEVICE = x0, y0 per image; it cannot be checked without a sync, so
+ * the kernels clamp x0 to [0, Wc - Wout] and y0 to [0, Hc - Hout]: any table is memory-safe.  max_rows / max_cols: HOST upper bounds of
+ * any window's source row span (v_bounds[y0 + Hout - 1].first + count - v_bounds[y0].first) and column span (h_bounds likewise), from the
+ * host's copy of the tables (data/augment.py window_extents); only those rows and columns of the source are read, and spans are clamped
+ * to them.  Every stage is optional: flips, jitter_order + jitter_factors, affine, mosaic_geom + mosaic_affine may be null (all null:
+ * window + Normalize); fill3 is needed with a warp or a mosaic.  One half of a pair alone, a null window, a window larger than the
+ * canvas or max_rows / max_cols outside the source: SD_ERR_INVALID.  The list form stages max_cols source pixels per row in LDS:
+ * max_cols <= 21834 (SD_ERR_INVALID beyond), whatever Win is.  workspace: sd_preprocess_window_workspace_bytes() bytes in every case. */
+size_t sd_preprocess_window_workspace_bytes(int B, int max_rows, int Hout, int Wout);
+int sd_preprocess_images_window(const uint8_t* images, int B, int Hin, int Win, int Hc, int Wc, int Hout, int Wout, const int* h_bounds,
+                                const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const int* window, int max_rows,
+                                int max_cols, const uint8_t* flips, const int* jitter_order, const float* jitter_factors, const double* affine,
+                                const int* mosaic_geom, const double* mosaic_affine, const uint8_t fill3[3], const float* mean3, const float* std3,
+                                float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream);
+int sd_preprocess_images_list_window(const uint8_t* const* images, int B, int Hin, int Win, int Hc, int Wc, int Hout, int Wout, const int* h_bounds,
+                                     const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const int* window,
+                                     int max_rows, int max_cols, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
+                                     const double* affine, const int* mosaic_geom, const double* mosaic_affine, const uint8_t fill3[3],
+                                     const float* mean3, const float* std3, float* out, void* workspace, size_t workspace_bytes,
+                                     sd_stream_t stream);
+
 /* ---- loss: src/sdnet/model/loss.py:17-64,91-117 ------------------------------------------- */
 
 #define SD_HM_MSE   0

@@ -103,6 +103,13 @@ _SIGNATURES = {
                                             C.POINTER(C.c_ubyte), C.POINTER(c_float), C.POINTER(c_float), c_vp, c_vp, c_size, c_vp]),
     "sd_preprocess_images_list_mosaic": (c_int, [c_vp] + [c_int] * 5 + [c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                                  C.POINTER(C.c_ubyte), C.POINTER(c_float), C.POINTER(c_float), c_vp, c_vp, c_size, c_vp]),
+    # windowed resize in front of every chain: images, B, Hin, Win, Hc, Wc, Hout, Wout, tables, window (B, 2) int32 device, max_rows, max_cols,
+    # flips, jitter_order, jitter_factors, affine, mosaic_geom, mosaic_affine (each stage null: off), fill3 (HOST), mean3, std3, out, ...
+    "sd_preprocess_window_workspace_bytes": (c_size, [c_int] * 4),
+    "sd_preprocess_images_window": (c_int, [c_vp] + [c_int] * 7 + [c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_int, c_int] + [c_vp] * 6 +
+                                    [C.POINTER(C.c_ubyte), C.POINTER(c_float), C.POINTER(c_float), c_vp, c_vp, c_size, c_vp]),
+    "sd_preprocess_images_list_window": (c_int, [c_vp] + [c_int] * 7 + [c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_int, c_int] + [c_vp] * 6 +
+                                         [C.POINTER(C.c_ubyte), C.POINTER(c_float), C.POINTER(c_float), c_vp, c_vp, c_size, c_vp]),
     "sd_render_targets": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_float, c_vp, c_vp]),
     "sd_loss_workspace_bytes": (c_size, [c_int] * 5),
     "sd_loss_fwd": (c_int, [C.POINTER(LossDesc), c_vp, c_vp, c_size, c_vp]),

@@ -518,6 +518,203 @@ __global__ __launch_bounds__(256) void k_mosaic_norm(const uint8_t* __restrict__
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Windowed resize (crop training at the tile scale, `train --train_tiles`; not in the reference): image b's output is the Wout x Hout
+// window at (x0_b, y0_b) of its resize to a Wc x Hc canvas -- byte for byte Image.resize((Wc, Hc), BILINEAR).crop((x0, y0, x0 + Wout,
+// y0 + Hout)) -- without resampling the rest of the canvas: the tables are the canvas tables read at x0 + x and y0 + y, the horizontal
+// pass covers only the source rows [rlo, rhi) under the window's rows (rlo = v_bounds[y0].first, rhi = v_bounds[y0 + Hout - 1].first +
+// count) and the window's columns, and the intermediate is (B, max_rows, Wout, 3), image b's row r being source row rlo_b + r.
+// window (B, 2) int32 = x0, y0 lives on the device and cannot be checked by the host without a sync: x0, y0 are clamped to [0, Wc - Wout],
+// [0, Hc - Hout] and the row / column spans to the host's max_rows / max_cols, so any window table is memory-safe (the mosaic rule).
+// ---------------------------------------------------------------------------------------------------------------------------------
+struct Window { int x0, y0, rlo, nrows; };
+
+__device__ __forceinline__ Window window_of(const int* __restrict__ window, const int* __restrict__ v_bounds, int b, int Hc, int Wc, int Hout,
+                                            int Wout, int max_rows) {
+    const int x0 = min(max(window[2 * b], 0), Wc - Wout), y0 = min(max(window[2 * b + 1], 0), Hc - Hout);
+    const int last = y0 + Hout - 1;
+    const int rlo = v_bounds[2 * y0], rhi = v_bounds[2 * last] + v_bounds[2 * last + 1];
+    return Window{x0, y0, rlo, min(max(rhi - rlo, 1), max_rows)};
+}
+
+// horizontal pass, packed: in (B, Hin, Win, 3) u8 -> tmp (B, max_rows, Wout, 3) u8, one thread per intermediate pixel (k_resample_h's sum)
+__global__ __launch_bounds__(256) void k_window_h(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int Hin, int Win, int Hc, int Wc,
+                                                   int Hout, int Wout, const int* __restrict__ bounds, const int* __restrict__ kk, int ksize,
+                                                   const int* __restrict__ v_bounds, const int* __restrict__ window, int max_rows, int B) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t)B * max_rows * Wout) return;
+    const int x = (int)(i % Wout);
+    const int64_t t = i / Wout;
+    const int r = (int)(t % max_rows), b = (int)(t / max_rows);
+    const Window wd = window_of(window, v_bounds, b, Hc, Wc, Hout, Wout, max_rows);
+    if (r >= wd.nrows) return;                                           // rows past this window's span are never read
+    const int cx = wd.x0 + x;
+    const int xmin = bounds[2 * cx], n = bounds[2 * cx + 1];
+    const int* k = kk + (int64_t)cx * ksize;
+    const uint8_t* src = in + (((int64_t)b * Hin + wd.rlo + r) * Win + xmin) * 3;
+    int s0 = 1 << (PRECISION_BITS - 1), s1 = s0, s2 = s0;
+    for (int t = 0; t < n; ++t) {
+        const int w = k[t];
+        s0 += src[3 * t + 0] * w; s1 += src[3 * t + 1] * w; s2 += src[3 * t + 2] * w;
+    }
+    uint8_t* dst = out + i * 3;
+    dst[0] = clip8(s0); dst[1] = clip8(s1); dst[2] = clip8(s2);
+}
+
+// horizontal pass from a device table of image pointers: the block shape and the tap loop of k_resample_h_list -- a block owns `rpb`
+// (<= HL_ROWS) consecutive rows of one window's span -- but it stages only the bytes of source columns [clo, chi) of each row (clo =
+// bounds[x0].first, chi = bounds[x0 + Wout - 1].first + count).  Those pieces are not contiguous in memory: every row is staged on its
+// own, with 16-byte global loads between its first and last 16-byte boundary and byte loads outside them (any byte offset works and
+// nothing outside the image is read).  In LDS the rows lie S = 3 ncols + (0 .. 3) bytes apart, S = the source pitch mod 4, the first at the
+// source's offset mod 4: every row keeps its address mod 4, so a 16-byte load is stored as four aligned dwords.  Dynamic LDS: rpb *
+// max_cols * 3 + 32 bytes (offset <= 3, pitch padding <= 9, the last tap group's overhang 13; bytes there are multiplied by zero weights).
+__global__ __launch_bounds__(256) void k_window_h_list(const uint8_t* const* __restrict__ images, uint8_t* __restrict__ out, int Win, int Hc, int Wc,
+                                                        int Hout, int Wout, const int* __restrict__ bounds, const int* __restrict__ kk, int ksize,
+                                                        const int* __restrict__ v_bounds, const int* __restrict__ window, int max_rows,
+                                                        int max_cols, int rpb, int blocks_per_image) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const int b = blockIdx.x / blocks_per_image;
+    const int r0 = (blockIdx.x - b * blocks_per_image) * rpb;
+    const Window wd = window_of(window, v_bounds, b, Hc, Wc, Hout, Wout, max_rows);
+    const int nr = min(rpb, wd.nrows - r0);
+    if (nr <= 0) return;                                                 // (the whole block: nobody waits at the barrier)
+    const int lastc = wd.x0 + Wout - 1;
+    const int clo = bounds[2 * wd.x0];
+    const int ncols = min(max(bounds[2 * lastc] + bounds[2 * lastc + 1] - clo, 1), max_cols);
+    const int L = ncols * 3;                                             // staged bytes per row (rpb * L + 32 <= HL_LDS_BYTES: checked by the host)
+    const int64_t pitch = (int64_t)Win * 3;
+    const uint8_t* src0 = images[b] + ((int64_t)(wd.rlo + r0) * Win + clo) * 3;
+    const int off = (int)(reinterpret_cast<uintptr_t>(src0) & 3);
+    const int S = L + (int)((pitch - L) & 3);
+    const uint8_t* rs[HL_ROWS];
+    int hd[HL_ROWS], nv[HL_ROWS], maxv = 0;
+#pragma unroll
+    for (int r = 0; r < HL_ROWS; ++r) {
+        rs[r] = src0 + (int64_t)min(r, nr - 1) * pitch;
+        hd[r] = min((16 - (int)(reinterpret_cast<uintptr_t>(rs[r]) & 15)) & 15, L);
+        nv[r] = r < nr ? (L - hd[r]) >> 4 : 0;
+        maxv = max(maxv, nv[r]);
+    }
+    for (int base = 0; base < maxv; base += 2 * 256) {                  // up to 8 loads in flight per thread before the LDS stores
+        uint4 v[HL_ROWS][2];
+#pragma unroll
+        for (int r = 0; r < HL_ROWS; ++r) {
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const int i = base + k * 256 + threadIdx.x;
+                v[r][k] = i < nv[r] ? reinterpret_cast<const uint4*>(rs[r] + hd[r])[i] : make_uint4(0, 0, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < HL_ROWS; ++r) {
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const int i = base + k * 256 + threadIdx.x;
+                if (i < nv[r]) {
+                    uint32_t* d = reinterpret_cast<uint32_t*>(lds + off + r * S + hd[r]) + 4 * i;
+                    d[0] = v[r][k].x; d[1] = v[r][k].y; d[2] = v[r][k].z; d[3] = v[r][k].w;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < HL_ROWS; ++r) {
+        if (r < nr) {
+            const int tail = hd[r] + (nv[r] << 4);
+            if ((int)threadIdx.x < hd[r]) lds[off + r * S + threadIdx.x] = rs[r][threadIdx.x];
+            if ((int)threadIdx.x < L - tail) lds[off + r * S + tail + threadIdx.x] = rs[r][tail + threadIdx.x];
+        }
+    }
+    __syncthreads();
+    for (int x = threadIdx.x; x < Wout; x += 256) {
+        const int cx = wd.x0 + x;
+        const int xmin = bounds[2 * cx] - clo, n = bounds[2 * cx + 1];
+        const int* k = kk + (int64_t)cx * ksize;
+        int s[HL_ROWS][3];
+#pragma unroll
+        for (int r = 0; r < HL_ROWS; ++r) s[r][0] = s[r][1] = s[r][2] = 1 << (PRECISION_BITS - 1);
+        for (int t0 = 0; t0 < n; t0 += 4) {
+            int w[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) w[j] = t0 + j < n ? k[t0 + j] : 0;
+            const int p = min(max(xmin + t0, 0), ncols - 1);           // a staged column whatever the tables say (inside already when they agree)
+#pragma unroll
+            for (int r = 0; r < HL_ROWS; ++r) {
+                if (r < nr) {
+                    const int q = off + r * S + p * 3;                   // first byte of the four pixels (reads stop 13 bytes past the row)
+                    const uint32_t* d = reinterpret_cast<const uint32_t*>(lds + (q & ~3));
+                    const int sh = q & 3;
+                    const uint32_t d0 = d[0], d1 = d[1], d2 = d[2], d3 = d[3];
+                    const uint32_t a0 = __builtin_amdgcn_alignbyte(d1, d0, sh), a1 = __builtin_amdgcn_alignbyte(d2, d1, sh),
+                                   a2 = __builtin_amdgcn_alignbyte(d3, d2, sh);   // bytes r0 g0 b0 r1 | g1 b1 r2 g2 | b2 r3 g3 b3
+                    s[r][0] += (int)(a0 & 255) * w[0] + (int)(a0 >> 24) * w[1] + (int)((a1 >> 16) & 255) * w[2] + (int)((a2 >> 8) & 255) * w[3];
+                    s[r][1] += (int)((a0 >> 8) & 255) * w[0] + (int)(a1 & 255) * w[1] + (int)(a1 >> 24) * w[2] + (int)((a2 >> 16) & 255) * w[3];
+                    s[r][2] += (int)((a0 >> 16) & 255) * w[0] + (int)((a1 >> 8) & 255) * w[1] + (int)(a2 & 255) * w[2] + (int)(a2 >> 24) * w[3];
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < HL_ROWS; ++r) {
+            if (r < nr) {
+                uint8_t* dst = out + (((int64_t)b * max_rows + r0 + r) * Wout + x) * 3;
+                dst[0] = clip8(s[r][0]); dst[1] = clip8(s[r][1]); dst[2] = clip8(s[r][2]);
+            }
+        }
+    }
+}
+
+// one output pixel of the vertical pass on a window: table row y0 + y, intermediate rows relative to rlo (kept inside the span)
+__device__ __forceinline__ Rgb8 window_v_pixel(const uint8_t* __restrict__ in, int Wout, const int* __restrict__ bounds, const int* __restrict__ kk,
+                                               int ksize, const Window& wd, int max_rows, int b, int x, int y) {
+    const int ty = wd.y0 + y;
+    const int ymin = bounds[2 * ty] - wd.rlo, n = bounds[2 * ty + 1];
+    const int* k = kk + (int64_t)ty * ksize;
+    const uint8_t* src = in + ((int64_t)b * max_rows * Wout + x) * 3;
+    int s0 = 1 << (PRECISION_BITS - 1), s1 = s0, s2 = s0;
+    for (int r = 0; r < n; ++r) {
+        const int w = k[r];
+        const uint8_t* px = src + (int64_t)min(max(ymin + r, 0), wd.nrows - 1) * Wout * 3;
+        s0 += px[0] * w; s1 += px[1] * w; s2 += px[2] * w;
+    }
+    return Rgb8{clip8(s0), clip8(s1), clip8(s2)};
+}
+
+// vertical pass + flips + to_tensor + Normalize on a window: tmp (B, max_rows, Wout, 3) u8 -> out (B, 3, Hout, Wout) fp32 NCHW (k_resample_v_norm)
+__global__ __launch_bounds__(256) void k_window_v_norm(const uint8_t* __restrict__ in, float* __restrict__ out, int Hc, int Wc, int Hout, int Wout,
+                                                        const int* __restrict__ bounds, const int* __restrict__ kk, int ksize,
+                                                        const int* __restrict__ window, int max_rows, const uint8_t* __restrict__ flips, float m0,
+                                                        float m1, float m2, float d0, float d1, float d2, int B) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t)B * Hout * Wout) return;
+    const int x = (int)(i % Wout);
+    const int64_t t = i / Wout;
+    const int y = (int)(t % Hout), b = (int)(t / Hout);
+    const int f = flips ? flips[b] : 0;                                  // the flips act on the WINDOW, after the resize
+    const int sx = (f & 1) ? Wout - 1 - x : x, sy = (f & 2) ? Hout - 1 - y : y;
+    const Window wd = window_of(window, bounds, b, Hc, Wc, Hout, Wout, max_rows);
+    const Rgb8 c = window_v_pixel(in, Wout, bounds, kk, ksize, wd, max_rows, b, sx, sy);
+    const int64_t plane = (int64_t)Hout * Wout;
+    float* o = out + (int64_t)b * 3 * plane + (int64_t)y * Wout + x;
+    o[0] = ((float)c.r / 255.0f - m0) / d0;
+    o[plane] = ((float)c.g / 255.0f - m1) / d1;
+    o[2 * plane] = ((float)c.b / 255.0f - m2) / d2;
+}
+
+// vertical pass only on a window: tmp (B, max_rows, Wout, 3) u8 -> img (B, Hout, Wout, 3) u8, what the mosaic / warp / jitter stages work on
+__global__ __launch_bounds__(256) void k_window_v_u8(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int Hc, int Wc, int Hout, int Wout,
+                                                      const int* __restrict__ bounds, const int* __restrict__ kk, int ksize,
+                                                      const int* __restrict__ window, int max_rows, int B) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t)B * Hout * Wout) return;
+    const int x = (int)(i % Wout);
+    const int64_t t = i / Wout;
+    const int y = (int)(t % Hout), b = (int)(t / Hout);
+    const Window wd = window_of(window, bounds, b, Hc, Wc, Hout, Wout, max_rows);
+    const Rgb8 c = window_v_pixel(in, Wout, bounds, kk, ksize, wd, max_rows, b, x, y);
+    uint8_t* dst = out + i * 3;
+    dst[0] = (uint8_t)c.r; dst[1] = (uint8_t)c.g; dst[2] = (uint8_t)c.b;
+}
+
 }  // namespace sd
 
 using namespace sd;
@@ -687,14 +884,10 @@ static int affine_check(const char* what, int B, int Hin, int Win, int Hout, int
     return 0;
 }
 
-// the launches after the horizontal pass
-static int preprocess_affine_tail(int B, int Hin, int Win, int Hout, int Wout, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips,
-                                  const int* jitter_order, const float* jitter_factors, const double* affine, const uint8_t* fill3,
-                                  const float* mean3, const float* std3, float* out, uint8_t* tmp, hipStream_t st) {
-    uint8_t* img = tmp + sd_preprocess_workspace_bytes(B, Hin, Win, Wout);
-    unsigned long long* lsum = reinterpret_cast<unsigned long long*>(img + align_up((size_t)B * Hout * Wout * 3, 256));
-    uint8_t* resized = tmp + sd_preprocess_jitter_workspace_bytes(B, Hin, Win, Hout, Wout);
-    if (int e = resample_v_u8(B, Hin, Hout, Wout, v_bounds, v_kk, v_ksize, tmp, resized, st)) return e;
+// the launches after the vertical pass (`resized` = the 8-bit resized image), shared with the window forms
+static int affine_stages(int B, int Hout, int Wout, const uint8_t* flips, const int* jitter_order, const float* jitter_factors, const double* affine,
+                         const uint8_t* fill3, const float* mean3, const float* std3, float* out, const uint8_t* resized, uint8_t* img,
+                         unsigned long long* lsum, hipStream_t st) {
     const dim3 grid(cdiv(Wout, AF_TX * AF_PX), cdiv(Hout, AF_TY), B);
     if (!jitter_order) {
         hipLaunchKernelGGL(k_affine_norm, grid, dim3(256), 0, st, resized, out, Hout, Wout, affine, (int)fill3[0], (int)fill3[1], (int)fill3[2], flips,
@@ -705,6 +898,17 @@ static int preprocess_affine_tail(int B, int Hin, int Win, int Hout, int Wout, c
     hipLaunchKernelGGL(k_affine_u8, grid, dim3(256), 0, st, resized, img, Hout, Wout, affine, (int)fill3[0], (int)fill3[1], (int)fill3[2]);
     SD_LAUNCH_CHECK();
     return jitter_norm(B, Hout, Wout, flips, jitter_order, jitter_factors, mean3, std3, out, img, lsum, st);
+}
+
+// the launches after the horizontal pass
+static int preprocess_affine_tail(int B, int Hin, int Win, int Hout, int Wout, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips,
+                                  const int* jitter_order, const float* jitter_factors, const double* affine, const uint8_t* fill3,
+                                  const float* mean3, const float* std3, float* out, uint8_t* tmp, hipStream_t st) {
+    uint8_t* img = tmp + sd_preprocess_workspace_bytes(B, Hin, Win, Wout);
+    unsigned long long* lsum = reinterpret_cast<unsigned long long*>(img + align_up((size_t)B * Hout * Wout * 3, 256));
+    uint8_t* resized = tmp + sd_preprocess_jitter_workspace_bytes(B, Hin, Win, Hout, Wout);
+    if (int e = resample_v_u8(B, Hin, Hout, Wout, v_bounds, v_kk, v_ksize, tmp, resized, st)) return e;
+    return affine_stages(B, Hout, Wout, flips, jitter_order, jitter_factors, affine, fill3, mean3, std3, out, resized, img, lsum, st);
 }
 
 int sd_preprocess_images_affine(const uint8_t* images, int B, int Hin, int Win, int Hout, int Wout, const int* h_bounds, const int* h_kk,
@@ -768,18 +972,13 @@ static int mosaic_check(const char* what, int B, int Hin, int Win, int Hout, int
     return 0;
 }
 
-// the launches after the horizontal pass
-static int preprocess_mosaic_tail(int B, int Hin, int Win, int Hout, int Wout, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips,
-                                  const int* jitter_order, const float* jitter_factors, const double* affine, const int* mosaic_geom,
-                                  const double* mosaic_affine, const uint8_t* fill3, const float* mean3, const float* std3, float* out,
-                                  uint8_t* tmp, hipStream_t st) {
-    uint8_t* img_a = tmp + sd_preprocess_workspace_bytes(B, Hin, Win, Wout);
-    unsigned long long* lsum = reinterpret_cast<unsigned long long*>(img_a + align_up((size_t)B * Hout * Wout * 3, 256));
-    uint8_t* img_b = tmp + sd_preprocess_jitter_workspace_bytes(B, Hin, Win, Hout, Wout);
+// the launches after the vertical pass, shared with the window forms: the resized image is in A with a warp, in B without (see above)
+static int mosaic_stages(int B, int Hout, int Wout, const uint8_t* flips, const int* jitter_order, const float* jitter_factors, const double* affine,
+                         const int* mosaic_geom, const double* mosaic_affine, const uint8_t* fill3, const float* mean3, const float* std3, float* out,
+                         uint8_t* img_a, uint8_t* img_b, unsigned long long* lsum, hipStream_t st) {
     uint8_t* resized = affine ? img_a : img_b;
     uint8_t* mosaic = affine ? img_b : img_a;
     const int f0 = fill3[0], f1 = fill3[1], f2 = fill3[2];
-    if (int e = resample_v_u8(B, Hin, Hout, Wout, v_bounds, v_kk, v_ksize, tmp, resized, st)) return e;
     const dim3 grid(cdiv(Wout, AF_TX * AF_PX), cdiv(Hout, AF_TY), B);
     if (!affine && !jitter_order) {
         hipLaunchKernelGGL(k_mosaic_norm, grid, dim3(256), 0, st, resized, out, Hout, Wout, mosaic_geom, mosaic_affine, f0, f1, f2, flips, mean3[0],
@@ -800,6 +999,19 @@ static int preprocess_mosaic_tail(int B, int Hin, int Win, int Hout, int Wout, c
         SD_LAUNCH_CHECK();
     }
     return jitter_norm(B, Hout, Wout, flips, jitter_order, jitter_factors, mean3, std3, out, img_a, lsum, st);
+}
+
+// the launches after the horizontal pass
+static int preprocess_mosaic_tail(int B, int Hin, int Win, int Hout, int Wout, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips,
+                                  const int* jitter_order, const float* jitter_factors, const double* affine, const int* mosaic_geom,
+                                  const double* mosaic_affine, const uint8_t* fill3, const float* mean3, const float* std3, float* out,
+                                  uint8_t* tmp, hipStream_t st) {
+    uint8_t* img_a = tmp + sd_preprocess_workspace_bytes(B, Hin, Win, Wout);
+    unsigned long long* lsum = reinterpret_cast<unsigned long long*>(img_a + align_up((size_t)B * Hout * Wout * 3, 256));
+    uint8_t* img_b = tmp + sd_preprocess_jitter_workspace_bytes(B, Hin, Win, Hout, Wout);
+    if (int e = resample_v_u8(B, Hin, Hout, Wout, v_bounds, v_kk, v_ksize, tmp, affine ? img_a : img_b, st)) return e;
+    return mosaic_stages(B, Hout, Wout, flips, jitter_order, jitter_factors, affine, mosaic_geom, mosaic_affine, fill3, mean3, std3, out, img_a, img_b,
+                         lsum, st);
 }
 
 int sd_preprocess_images_mosaic(const uint8_t* images, int B, int Hin, int Win, int Hout, int Wout, const int* h_bounds, const int* h_kk,
@@ -843,6 +1055,112 @@ int sd_preprocess_images_list_mosaic(const uint8_t* const* images, int B, int Hi
     if (int e = resample_h_list(images, tmp, B, Hin, Win, Wout, h_bounds, h_kk, h_ksize, rpb, bpi, st)) return e;
     return preprocess_mosaic_tail(B, Hin, Win, Hout, Wout, v_bounds, v_kk, v_ksize, flips, jitter_order, jitter_factors, affine, mosaic_geom,
                                   mosaic_affine, fill3, mean3, std3, out, tmp, st);
+}
+
+// ---- Windowed resize in front of every chain above (k_window_h / k_window_h_list, k_window_v_norm / k_window_v_u8) ----
+// workspace: that of the mosaic forms with max_rows in the place of Hin, [horizontal intermediate (B, max_rows, Wout, 3) | 8-bit image A |
+// grey sums | 8-bit image B]: the windowed vertical pass writes the 8-bit window where the stage that follows expects the resized image.
+size_t sd_preprocess_window_workspace_bytes(int B, int max_rows, int Hout, int Wout) {
+    return sd_preprocess_mosaic_workspace_bytes(B, max_rows, 0, Hout, Wout);
+}
+
+static int window_check(const char* what, const uint8_t* images, int B, int Hin, int Win, int Hc, int Wc, int Hout, int Wout, const int* h_bounds,
+                        const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const int* window, int max_rows, int max_cols,
+                        const int* jitter_order, const float* jitter_factors, const double* affine, const int* mosaic_geom,
+                        const double* mosaic_affine, const uint8_t* fill3, const float* mean3, const float* std3, float* out, void* workspace,
+                        size_t workspace_bytes) {
+    if (int e = preprocess_check(what, images, B, Hin, Win, Hc, Wc, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, mean3, std3, out, workspace))
+        return e;
+    SD_REQUIRE(window, SD_ERR_INVALID, "%s: null window table", what);
+    SD_REQUIRE(Hout > 0 && Wout > 0 && Hout <= Hc && Wout <= Wc, SD_ERR_INVALID, "%s: a %d x %d window does not fit a %d x %d canvas", what, Wout, Hout,
+               Wc, Hc);
+    SD_REQUIRE(max_rows > 0 && max_rows <= Hin && max_cols > 0 && max_cols <= Win, SD_ERR_INVALID,
+               "%s: max_rows %d / max_cols %d should be in [1, %d] / [1, %d] (the source)", what, max_rows, max_cols, Hin, Win);
+    SD_REQUIRE((jitter_order == nullptr) == (jitter_factors == nullptr), SD_ERR_INVALID,
+               "%s: jitter_order and jitter_factors go together (both null = no jitter)", what);
+    SD_REQUIRE((mosaic_geom == nullptr) == (mosaic_affine == nullptr), SD_ERR_INVALID,
+               "%s: mosaic_geom and mosaic_affine go together (both null = no mosaic)", what);
+    SD_REQUIRE(fill3 || !(affine || mosaic_geom), SD_ERR_INVALID, "%s: a warp or a mosaic needs a fill colour", what);
+    SD_REQUIRE(B <= 65535 || !(jitter_order || affine || mosaic_geom), SD_ERR_INVALID, "%s: batch %d > 65535", what, B);
+    SD_REQUIRE(workspace_bytes >= sd_preprocess_window_workspace_bytes(B, max_rows, Hout, Wout), SD_ERR_WORKSPACE, "%s: workspace %zu < %zu", what,
+               workspace_bytes, sd_preprocess_window_workspace_bytes(B, max_rows, Hout, Wout));
+    return 0;
+}
+
+// the launches after the horizontal pass: the windowed vertical pass, fused with Normalize when no stage follows, else into the 8-bit
+// image the existing tails resample into, and then their launches (jitter_norm, affine_stages, mosaic_stages)
+static int window_tail(int B, int Hc, int Wc, int Hout, int Wout, const int* v_bounds, const int* v_kk, int v_ksize, const int* window, int max_rows,
+                       const uint8_t* flips, const int* jitter_order, const float* jitter_factors, const double* affine, const int* mosaic_geom,
+                       const double* mosaic_affine, const uint8_t* fill3, const float* mean3, const float* std3, float* out, uint8_t* tmp,
+                       hipStream_t st) {
+    const dim3 grid(cdiv((int64_t)B * Hout * Wout, 256));
+    if (!jitter_order && !affine && !mosaic_geom) {
+        hipLaunchKernelGGL(k_window_v_norm, grid, dim3(256), 0, st, tmp, out, Hc, Wc, Hout, Wout, v_bounds, v_kk, v_ksize, window, max_rows, flips,
+                           mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], B);
+        SD_LAUNCH_CHECK();
+        return 0;
+    }
+    uint8_t* img_a = tmp + sd_preprocess_workspace_bytes(B, max_rows, 0, Wout);
+    unsigned long long* lsum = reinterpret_cast<unsigned long long*>(img_a + align_up((size_t)B * Hout * Wout * 3, 256));
+    uint8_t* img_b = tmp + sd_preprocess_jitter_workspace_bytes(B, max_rows, 0, Hout, Wout);
+    uint8_t* resized = (mosaic_geom != nullptr) == (affine != nullptr) ? img_a : img_b;    // jitter reads A, the warp B, the mosaic A with a warp, else B
+    hipLaunchKernelGGL(k_window_v_u8, grid, dim3(256), 0, st, tmp, resized, Hc, Wc, Hout, Wout, v_bounds, v_kk, v_ksize, window, max_rows, B);
+    SD_LAUNCH_CHECK();
+    if (mosaic_geom)
+        return mosaic_stages(B, Hout, Wout, flips, jitter_order, jitter_factors, affine, mosaic_geom, mosaic_affine, fill3, mean3, std3, out, img_a,
+                             img_b, lsum, st);
+    if (affine)
+        return affine_stages(B, Hout, Wout, flips, jitter_order, jitter_factors, affine, fill3, mean3, std3, out, resized, img_a, lsum, st);
+    return jitter_norm(B, Hout, Wout, flips, jitter_order, jitter_factors, mean3, std3, out, img_a, lsum, st);
+}
+
+int sd_preprocess_images_window(const uint8_t* images, int B, int Hin, int Win, int Hc, int Wc, int Hout, int Wout, const int* h_bounds,
+                                const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const int* window, int max_rows,
+                                int max_cols, const uint8_t* flips, const int* jitter_order, const float* jitter_factors, const double* affine,
+                                const int* mosaic_geom, const double* mosaic_affine, const uint8_t* fill3, const float* mean3, const float* std3,
+                                float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
+    if (int e = window_check("sd_preprocess_images_window", images, B, Hin, Win, Hc, Wc, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
+                             window, max_rows, max_cols, jitter_order, jitter_factors, affine, mosaic_geom, mosaic_affine, fill3, mean3, std3, out,
+                             workspace, workspace_bytes)) return e;
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t* tmp = reinterpret_cast<uint8_t*>(workspace);
+    if (jitter_order) {
+        uint8_t* img = tmp + sd_preprocess_workspace_bytes(B, max_rows, 0, Wout);
+        SD_HIP(hipMemsetAsync(img + align_up((size_t)B * Hout * Wout * 3, 256), 0, (size_t)B * 8, st));    // lsum
+    }
+    hipLaunchKernelGGL(k_window_h, dim3(cdiv((int64_t)B * max_rows * Wout, 256)), dim3(256), 0, st, images, tmp, Hin, Win, Hc, Wc, Hout, Wout, h_bounds,
+                       h_kk, h_ksize, v_bounds, window, max_rows, B);
+    SD_LAUNCH_CHECK();
+    return window_tail(B, Hc, Wc, Hout, Wout, v_bounds, v_kk, v_ksize, window, max_rows, flips, jitter_order, jitter_factors, affine, mosaic_geom,
+                       mosaic_affine, fill3, mean3, std3, out, tmp, st);
+}
+
+int sd_preprocess_images_list_window(const uint8_t* const* images, int B, int Hin, int Win, int Hc, int Wc, int Hout, int Wout, const int* h_bounds,
+                                     const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const int* window,
+                                     int max_rows, int max_cols, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
+                                     const double* affine, const int* mosaic_geom, const double* mosaic_affine, const uint8_t* fill3,
+                                     const float* mean3, const float* std3, float* out, void* workspace, size_t workspace_bytes,
+                                     sd_stream_t stream) {
+    const char* what = "sd_preprocess_images_list_window";
+    if (int e = window_check(what, reinterpret_cast<const uint8_t*>(images), B, Hin, Win, Hc, Wc, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk,
+                             v_ksize, window, max_rows, max_cols, jitter_order, jitter_factors, affine, mosaic_geom, mosaic_affine, fill3, mean3, std3,
+                             out, workspace, workspace_bytes)) return e;
+    SD_REQUIRE((int64_t)max_cols * 3 + 32 <= HL_LDS_BYTES, SD_ERR_INVALID,
+               "%s: a column span of %d source pixels exceeds the LDS staging buffer (at most %d)", what, max_cols, (HL_LDS_BYTES - 32) / 3);
+    const int rpb = (int)std::min<int64_t>(HL_ROWS, (HL_LDS_BYTES - 32) / ((int64_t)max_cols * 3));
+    const int bpi = cdiv(max_rows, rpb);
+    SD_REQUIRE((int64_t)B * bpi < (1ll << 31), SD_ERR_INVALID, "%s: batch too large", what);
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t* tmp = reinterpret_cast<uint8_t*>(workspace);
+    if (jitter_order) {
+        uint8_t* img = tmp + sd_preprocess_workspace_bytes(B, max_rows, 0, Wout);
+        SD_HIP(hipMemsetAsync(img + align_up((size_t)B * Hout * Wout * 3, 256), 0, (size_t)B * 8, st));    // lsum
+    }
+    hipLaunchKernelGGL(k_window_h_list, dim3((unsigned)((int64_t)B * bpi)), dim3(256), (size_t)rpb * max_cols * 3 + 32, st, images, tmp, Win, Hc, Wc,
+                       Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, window, max_rows, max_cols, rpb, bpi);
+    SD_LAUNCH_CHECK();
+    return window_tail(B, Hc, Wc, Hout, Wout, v_bounds, v_kk, v_ksize, window, max_rows, flips, jitter_order, jitter_factors, affine, mosaic_geom,
+                       mosaic_affine, fill3, mean3, std3, out, tmp, st);
 }
 
 }  // extern "C"

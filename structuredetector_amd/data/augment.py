@@ -18,6 +18,10 @@ Resize and ColorJitter, as Pillow's `Image.transform(size, AFFINE, matrix, BILIN
 Mosaic (`--aug_mosaic P`; not in the reference): between Resize and the warp, a selected image becomes four images of its size group at
 half scale around a random centre (`mosaic_tiles`), each quadrant Pillow's `Image.transform` of its source byte for byte
 (`sd_preprocess_images_mosaic`); `utils.misc.mosaic_annotation` gathers the four annotations and keeps what each tile shows.
+Window (`--train_tiles CxR`; not in the reference): the Resize itself targets the canvas tiled inference shows the network (`tile_canvas`) and
+only a W x H window of it at a random origin is produced, `Image.resize(canvas, BILINEAR).crop(window)` byte for byte
+(`sd_preprocess_images_window`: the source rows and columns under the window are all that is read); every later stage works on the window,
+the annotations follow with `ann.resize` to the canvas and `affine_annotation` by the shift.
 """
 from __future__ import annotations
 
@@ -28,6 +32,7 @@ import numpy as np
 import torch
 
 from .. import _lib as L
+from ..utils.args import parse_tiles, tile_canvas
 from ..utils.misc import affine_annotation, clip_annotation, hflip_annotation, mosaic_annotation, vflip_annotation
 
 PRECISION_BITS = 32 - 8 - 2
@@ -76,22 +81,50 @@ def pil_bilinear_coeffs(in_size: int, out_size: int):
 
 
 class _Tables:
-    """Device-resident coefficient tables, one entry per (in_size, out_size) pair seen (a handful per run)."""
+    """Coefficient tables, one entry per (in_size, out_size) pair seen (a handful per run): the host copy, the device-resident copy, and
+    the window extents read off the host copy."""
 
     def __init__(self):
         self.cache = {}
+        self.host_cache = {}
+        self.extents = {}
+
+    def host(self, in_size, out_size):
+        t = self.host_cache.get((in_size, out_size))
+        if t is None:
+            t = self.host_cache[(in_size, out_size)] = pil_bilinear_coeffs(in_size, out_size)
+        return t
 
     def get(self, in_size, out_size, device):
         key = (in_size, out_size, device.index)
         t = self.cache.get(key)
         if t is None:
-            bounds, kk, ksize = pil_bilinear_coeffs(in_size, out_size)
+            bounds, kk, ksize = self.host(in_size, out_size)
             t = (torch.from_numpy(bounds).to(device), torch.from_numpy(kk).to(device), ksize)
             self.cache[key] = t
         return t
 
+    def extent(self, in_size, canvas_size, out_size):
+        key = (in_size, canvas_size, out_size)
+        e = self.extents.get(key)
+        if e is None:
+            bounds = self.host(in_size, canvas_size)[0]
+            first, end = bounds[:, 0].tolist(), bounds.sum(1).tolist()                  # first source index, one past the last
+            e = self.extents[key] = max(end[o + out_size - 1] - first[o] for o in range(canvas_size - out_size + 1))
+        return e
+
 
 _tables = _Tables()
+
+
+def window_extents(in_size: int, canvas_size: int, out_size: int) -> int:
+    """The largest source span, along one axis, of any `out_size` window of a resize in_size -> canvas_size: the maximum over the origins
+    o in [0, canvas_size - out_size] of bounds[o + out_size - 1].first + count - bounds[o].first on `pil_bilinear_coeffs`' table.  What
+    `sd_preprocess_images_window` takes as max_cols (width axis) and max_rows (height axis); cached with the tables."""
+    in_size, canvas_size, out_size = int(in_size), int(canvas_size), int(out_size)
+    if not 0 < out_size <= canvas_size:
+        raise ValueError(f"a window of {out_size} does not fit a canvas of {canvas_size}")
+    return _tables.extent(in_size, canvas_size, out_size)
 
 
 def affine_inverse_matrix(size, angle, scale, translate):
@@ -165,18 +198,64 @@ def _affine_rows(affine, B, device):
     return rows.to(device, non_blocking=True)
 
 
-def preprocess_images(images: torch.Tensor, out_size, flips=None, mean=_MEAN, std=_STD, jitter=None, affine=None, mosaic=None) -> torch.Tensor:
+def _preprocess_window(fn_name, source, B, Hin, Win, out_size, flips, mean, std, jitter, affine, mosaic, window, dev):
+    """The window forms of `preprocess_images` / `preprocess_image_list`: source = the address of the packed images or of the pointer
+    table; window = ((Wc, Hc), B origins (x0, y0))."""
+    (Wc, Hc), origins = window
+    Wc, Hc = int(Wc), int(Hc)
+    Wout, Hout = int(out_size[0]), int(out_size[1])
+    if not (0 < Wout <= Wc and 0 < Hout <= Hc):
+        raise L.SdError(f"window: {Wout} x {Hout} does not fit the canvas {Wc} x {Hc}")
+    org = torch.as_tensor(np.asarray(origins, dtype=np.int32)).reshape(-1, 2).contiguous()
+    if org.shape[0] != B:
+        raise L.SdError("window must have one origin (x0, y0) per image")
+    org = org.to(dev, non_blocking=True)
+    hb, hk, hks = _tables.get(Win, Wc, dev)
+    vb, vk, vks = _tables.get(Hin, Hc, dev)
+    max_cols, max_rows = window_extents(Win, Wc, Wout), window_extents(Hin, Hc, Hout)
+    out = torch.empty((B, 3, Hout, Wout), dtype=torch.float32, device=dev)
+    fl = order = factors = rows = geom = mats = None
+    if flips is not None:
+        fl = torch.as_tensor(flips, dtype=torch.uint8).to(dev, non_blocking=True)
+        if fl.numel() != B:
+            raise L.SdError("flips must have one entry per image")
+    if jitter is not None:
+        order = torch.as_tensor(jitter[0], dtype=torch.int32).to(dev, non_blocking=True)
+        factors = torch.as_tensor(jitter[1], dtype=torch.float32).reshape(-1, 3).contiguous().to(dev, non_blocking=True)
+        if order.numel() != B or factors.shape[0] != B:
+            raise L.SdError("jitter parameters must have one row per image")
+    if affine is not None:
+        rows = _affine_rows(affine, B, dev)
+    if mosaic is not None:
+        geom, mats = _mosaic_tables(mosaic, B, dev)
+    ptr = lambda t: t.data_ptr() if t is not None else 0
+    lib = L.lib()
+    ws = L.workspace(lib.sd_preprocess_window_workspace_bytes(B, max_rows, Hout, Wout), dev)
+    L.check(getattr(lib, fn_name)(source, B, Hin, Win, Hc, Wc, Hout, Wout, hb.data_ptr(), hk.data_ptr(), hks, vb.data_ptr(), vk.data_ptr(), vks,
+                                  org.data_ptr(), max_rows, max_cols, ptr(fl), ptr(order), ptr(factors), ptr(rows), ptr(geom), ptr(mats),
+                                  (C.c_ubyte * 3)(*_FILL), (C.c_float * 3)(*mean), (C.c_float * 3)(*std), out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                  L.stream()), fn_name)
+    return out
+
+
+def preprocess_images(images: torch.Tensor, out_size, flips=None, mean=_MEAN, std=_STD, jitter=None, affine=None, mosaic=None,
+                      window=None) -> torch.Tensor:
     """images: (B, Hin, Win, 3) uint8 on the GPU; out_size = (width, height); flips: (B,) uint8 (bit 0 horizontal, bit 1 vertical)
     or None; jitter: None or (order words (B,) int32, factors (B, 3) fp32) as `jitter_words` makes them; affine: None or B rows of the 6
     coefficients of `affine_inverse_matrix` at out_size (the warp runs on the resized image, in front of the jitter, fill `_FILL`); mosaic:
     None or (geom: B rows [cx, cy, s0 .. s3], matrices: B x 4 x 6) as `mosaic_tiles` makes them, the sources s_q indexing THIS batch
-    (the composite is built from the resized images, in front of the warp).
+    (the composite is built from the resized images, in front of the warp); window: None or ((canvas width, canvas height), B origins
+    (x0, y0)): the resize targets the canvas and only its out_size window at the origin is produced (`sd_preprocess_images_window`;
+    origins are clamped into the canvas on the device), every later stage works on that window.
     Returns (B, 3, height, width) fp32 = Normalize(to_tensor(flip(jitter(affine(mosaic(resize(image))))))) of transforms.py:217-226."""
     L.require_cuda(images)
     if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3:
         raise L.SdError(f"preprocess_images expects (B, H, W, 3) uint8, got {tuple(images.shape)} {images.dtype}")
     images = images.contiguous()
     B, Hin, Win, _ = images.shape
+    if window is not None:
+        return _preprocess_window("sd_preprocess_images_window", images.data_ptr(), B, Hin, Win, out_size, flips, mean, std, jitter, affine, mosaic,
+                                  window, images.device)
     Wout, Hout = int(out_size[0]), int(out_size[1])
     hb, hk, hks = _tables.get(Win, Wout, images.device)
     vb, vk, vks = _tables.get(Hin, Hout, images.device)
@@ -228,7 +307,7 @@ def preprocess_images(images: torch.Tensor, out_size, flips=None, mean=_MEAN, st
 
 
 def preprocess_image_list(pointers: torch.Tensor, hin: int, win: int, out_size, flips=None, mean=_MEAN, std=_STD, jitter=None,
-                          affine=None, mosaic=None) -> torch.Tensor:
+                          affine=None, mosaic=None, window=None) -> torch.Tensor:
     """`preprocess_images` over B images that are not packed together: pointers is a (B,) int64 DEVICE tensor of the device addresses of
     B (hin, win, 3) uint8 images (any byte alignment; the caller keeps them alive until the work on the current stream is done), e.g. entries
     of data/image_cache.py's DeviceImageCache.  Same arguments otherwise, same output bytes as `preprocess_images` on the stacked images."""
@@ -238,6 +317,9 @@ def preprocess_image_list(pointers: torch.Tensor, hin: int, win: int, out_size, 
     pointers = pointers.contiguous()
     dev = pointers.device
     B, Hin, Win = pointers.numel(), int(hin), int(win)
+    if window is not None:                                           # (the LDS limit of the list form then binds the window's column span)
+        return _preprocess_window("sd_preprocess_images_list_window", pointers.data_ptr(), B, Hin, Win, out_size, flips, mean, std, jitter, affine,
+                                  mosaic, window, dev)
     Wout, Hout = int(out_size[0]), int(out_size[1])
     hb, hk, hks = _tables.get(Win, Wout, dev)
     vb, vk, vks = _tables.get(Hin, Hout, dev)
@@ -324,6 +406,10 @@ class ValidationAugmentation:
         """Per sample None or (cx, cy, partners), or None for the batch: validation never composes and never draws."""
         return None
 
+    def window_draws_for(self, n):
+        """((Wc, Hc), n origins (x0, y0)) or None: validation always shows the whole frame and never draws."""
+        return None
+
     @staticmethod
     def size_groups(images):
         """{(hin, win): (indices into the batch, stack of those images)} of what `__call__` accepts as `images`."""
@@ -369,6 +455,7 @@ class ValidationAugmentation:
         warps = self.affine_draws_for(n)
         inverse = None if warps is None else [affine_inverse_matrix((W, H), a, s, (tx, ty)) for a, s, tx, ty in warps]
         mosaics = self.mosaic_draws_for(n, [idx for idx, _ in groups.values()])
+        windows = self.window_draws_for(n)
         out = torch.empty((n, 3, H, W), dtype=torch.float32, device=dev)
         for (hin, win), (idx, stack) in groups.items():
             f = None if flips is None else [flips[i] for i in idx]
@@ -379,6 +466,8 @@ class ValidationAugmentation:
                 where = {i: k for k, i in enumerate(idx)}
                 tiles = {i: mosaic_tiles((W, H), i, mosaics[i]) for i in idx}
                 kw["mosaic"] = ([[*tiles[i][0][:2], *(where[s] for s in tiles[i][0][2:])] for i in idx], [tiles[i][1] for i in idx])
+            if windows is not None:
+                kw["window"] = (windows[0], [windows[1][i] for i in idx])
             if hasattr(stack, "pointers"):                           # data/image_cache.py ImageList: cached / uploaded images by address
                 res = preprocess_image_list(stack.pointers, hin, win, (W, H), f, jitter=j, affine=m, **kw)
             else:
@@ -390,7 +479,12 @@ class ValidationAugmentation:
             for i in idx:
                 ann = annotations[i]
                 ann.img_size = ann.img_size or (win, hin)
-                ann.resize((win, hin), (W, H))                       # transforms.py:58
+                if windows is None:
+                    ann.resize((win, hin), (W, H))                   # transforms.py:58
+                else:                                                # to the canvas, then into the window: what leaves it is dropped
+                    x0, y0 = windows[1][i]
+                    ann.resize((win, hin), windows[0])
+                    affine_annotation(ann, [1.0, 0.0, -float(x0), 0.0, 1.0, -float(y0)], (W, H))
             if mosaics is not None:                                  # an image is itself and maybe someone's partner: compose from the
                 resized = {i: _Objects(annotations[i].objects) for i in idx}      # resized objects of the whole group, as they were
                 for i in idx:
@@ -429,6 +523,8 @@ class TrainAugmentation(ValidationAugmentation):
         self.scale = float(getattr(args, "aug_scale", 0.0))                # scale uniform in [1 - scale, 1 + scale]
         self.translate = float(getattr(args, "aug_translate", 0.0))        # shift uniform in [-translate, translate] * (width, height)
         self.mosaic = float(getattr(args, "aug_mosaic", 0.0))              # per-image probability of becoming a mosaic of four
+        self.train_tiles = parse_tiles(getattr(args, "train_tiles", ""), "train_tiles")   # (Tx, Ty) of the canvas the windows are cut from, () = off
+        self.tile_overlap = int(getattr(args, "tile_overlap", 64))
 
     def draws_for(self, n):
         """(flips, jitter) of n samples from torch's global generator, in THREE vectorised draws per batch: per-sample tiny tensor ops
@@ -480,6 +576,19 @@ class TrainAugmentation(ValidationAugmentation):
                 if sel < self.mosaic:
                     draws[i] = (W // 4 + int(ux * (W // 2 + 1)), H // 4 + int(uy * (H // 2 + 1)), tuple(idx[int(v * len(idx))] for v in up))
         return draws
+
+    def window_draws_for(self, n):
+        """((Wc, Hc), n origins (x0, y0)) with `--train_tiles`: the canvas `tile_canvas` gives for the current multi-scale size and, from ONE
+        more draw on torch's global generator, `rand(n, 2)` in float64, made after that of `mosaic_draws_for`, x0 = int(u (Wc - W + 1)) and
+        y0 = int(u (Hc - H + 1)): uniform over the windows of the canvas.  None, and no draw at all, with the flag off.  The flag selects
+        the pixel scale the network is trained at, not a perturbation of a sample, and a fixed window would hide most of every frame for
+        good: the windows are drawn under `--no_augmentation` too."""
+        if not self.train_tiles:
+            return None
+        W, H = self.size
+        Wc, Hc = tile_canvas(W, H, self.train_tiles, self.tile_overlap)
+        u = torch.rand(n, 2, dtype=torch.float64).tolist()
+        return (Wc, Hc), [(int(ux * (Wc - W + 1)), int(uy * (Hc - H + 1))) for ux, uy in u]
 
     def trigger_random_resize(self):
         if self.args.no_augmentation:

@@ -17,7 +17,7 @@ pixels (o = O / down_ratio cells):
 
 The result is a `TtaOutput` whose four maps are on the canvas grid; `TiledOutputDecoder` decodes it with the TILE's linkage radius and
 reports network-input pixels (W x H).  Tiling shows objects at a larger pixel scale than whole-frame training did: train for it with
-`--aug_scale` or on crops.  No accuracy figure is claimed."""
+`train --train_tiles` (windows of the same canvas; data/augment.py).  No accuracy figure is claimed."""
 from __future__ import annotations
 
 import torch

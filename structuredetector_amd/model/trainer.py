@@ -463,7 +463,8 @@ class Trainer:
     """Epoch loop around TrainStep with the reference's knobs (src/sdnet/model/trainer.py:23-237): Adam(lr),
     StepLR(step_size=args.lr_step), validation every second epoch with the Decoder + Evaluator + Loss and the four
     `model_best_{loss,csi,classif,kp_reg}.pth` checkpoints in trainings/<timestamp>/.  Data: a directory of JSON+image
-    samples (no augmentation) or `--synthetic N` seeded scenes rendered on the GPU.  TensorBoard logging and the PIL
+    samples (no augmentation) or `--synthetic N` seeded scenes rendered on the GPU.  `--train_tiles` trains on windows of the directory's
+    images at the tile scale of `evaluate --tiles`; the validation pass here always shows whole frames.  TensorBoard logging and the PIL
     augmentations are outside the hot path."""
 
     def __init__(self, args):
@@ -473,8 +474,10 @@ class Trainer:
         import numpy as np
 
         from ..data import CropDataset, Encode
+        from ..utils.args import check_train_tiles
         from .network import Network
         self.args = args
+        check_train_tiles(args)                                        # --train_tiles: refused with --synthetic, overlap against the smallest size
         if getattr(args, "use_amp", False) and not BF16_TRAINING:
             # the reference autocasts the training forward under --amp (trainer.py:115-121); silently training in fp32 under the
             # same flag would be a different experiment with the same name
@@ -724,6 +727,10 @@ class Trainer:
                   f"{self.step.clip_grad_norm:g}, weight EMA {self.step.ema_decay:g} (0 = off)", flush=True)
         if self.rank == 0 and self.step.sync_bn:
             print(f"synchronized BatchNorm: on (statistics over the global batch of {self.step.world} rank(s) x {self.args.batch_size})", flush=True)
+        if self.rank == 0 and self.augment.train_tiles:
+            tx, ty = self.augment.train_tiles
+            print(f"train tiles: every sample is a random window of the {tx}x{ty} tile canvas (overlap {self.augment.tile_overlap}); this run's "
+                  "validation shows whole frames -- measure tiled deployment with evaluate --tiles", flush=True)
         if self.cache is not None:
             self.prefill_cache()
         for epoch in range(self.start_epoch, self.args.epochs):

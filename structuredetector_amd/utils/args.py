@@ -83,6 +83,13 @@ _FLAGS = [
                         "combine with --tta / --tta_scales. Not consulted by train. Empty or 1x1 = off.")),
     (("--tile_overlap",), dict(type=int, default=64, metavar="PX", help="Pixels two neighbouring tiles of --tiles share: a multiple of 32 "
                                "in [0, min(W, H) / 2].")),
+    (("--train_tiles",), dict(type=str, default="", metavar="CxR", help="Crop training at the scale of tiled inference: every training sample "
+                              "is a W x H window, at a uniformly random position, of the source image resized to the canvas that --tiles CxR "
+                              "with --tile_overlap would show the network (C*W - (C-1)*O by R*H - (R-1)*O pixels, following the per-epoch "
+                              "multi-scale size); the other augmentations work on the window, objects whose anchor lies outside it are dropped. "
+                              "Windows are drawn under --no_augmentation too. Needs a directory (not --synthetic). The validation pass of train "
+                              "still shows whole frames: measure tiled deployment with evaluate --tiles. Not consulted by evaluate / detect. "
+                              "Empty or 1x1 = off.")),
     (("--aug_rotate",), dict(type=float, default=0.0, metavar="DEG", help="Training augmentation: rotate every image about its centre by an "
                              "angle uniform in [-DEG, DEG] (0 .. 180; what leaves the frame is dropped from the annotation, what the image does "
                              "not cover is filled with the ImageNet mean; 0 = off). Not consulted by evaluate / detect.")),
@@ -127,12 +134,12 @@ def parse_tta_scales(text):
 MAX_TILES = 8                       # tiles per axis (sd_tile_views / sd_tile_merge_nms)
 
 
-def parse_tiles(text):
-    """`--tiles`: "3x2" (columns x rows; or an already parsed pair) -> (Tx, Ty), each in 1 .. 8; "" and "1x1" -> () (off)."""
+def parse_tiles(text, name="tiles"):
+    """`--tiles` (or `--train_tiles`: `name`): "3x2" (columns x rows; or an already parsed pair) -> (Tx, Ty), each in 1 .. 8; "" and "1x1" -> () (off)."""
     if not isinstance(text, str):
         grid = tuple(text)
         if len(grid) not in (0, 2) or any(int(v) != v for v in grid):
-            raise ValueError(f"'tiles' should be COLUMNSxROWS (e.g. 2x2), not {text!r}")
+            raise ValueError(f"'{name}' should be COLUMNSxROWS (e.g. 2x2), not {text!r}")
         grid = tuple(int(v) for v in grid)
     else:
         fields = text.strip().lower().split("x") if text.strip() else []
@@ -141,10 +148,10 @@ def parse_tiles(text):
         except ValueError:
             grid = None
         if grid is None or len(grid) not in (0, 2):
-            raise ValueError(f"'tiles' should be COLUMNSxROWS (e.g. 2x2), not {text!r}")
+            raise ValueError(f"'{name}' should be COLUMNSxROWS (e.g. 2x2), not {text!r}")
     for v in grid:
         if not 1 <= v <= MAX_TILES:
-            raise ValueError(f"'tiles' should have 1 to {MAX_TILES} tiles per axis, not {v}")
+            raise ValueError(f"'{name}' should have 1 to {MAX_TILES} tiles per axis, not {v}")
     return () if grid == (1, 1) else grid
 
 
@@ -167,6 +174,24 @@ def tile_origins(width, height, grid, overlap):
     """The (row, column) pixel at which tile t = j*Tx + i starts: (j*(H-O), i*(W-O)), in t order."""
     tx, ty = grid
     return [(j * (height - overlap), i * (width - overlap)) for j in range(ty) for i in range(tx)]
+
+
+def check_train_tiles(args):
+    """`--train_tiles` on a parsed namespace -> (Tx, Ty) or () (off), as `train` checks it (model/trainer.py; `evaluate` and `detect` never
+    look at the flag).  When it is on: `--synthetic` is refused (a rendered scene has no source
+    image to cut a window from) and `--tile_overlap` must hold for the SMALLEST size the per-epoch multi-scale rule can produce,
+    int(0.75 * side / 32) * 32 (the side itself under --no_augmentation): the canvas follows that size every epoch."""
+    grid = parse_tiles(getattr(args, "train_tiles", ""), "train_tiles")
+    if not grid:
+        return grid
+    if getattr(args, "synthetic", 0):
+        raise ValueError("'train_tiles' cuts windows from source images: it needs --train_dir, not --synthetic")
+    ratio = 1.0 if getattr(args, "no_augmentation", False) else 0.75
+    width, height = int(ratio * args.width / 32) * 32, int(ratio * args.height / 32) * 32
+    if min(width, height) < 32:
+        raise ValueError(f"'train_tiles' needs a network input whose smallest multi-scale size is at least 32 x 32, not {width} x {height}")
+    check_tile_overlap(getattr(args, "tile_overlap", 64), width, height)
+    return grid
 
 
 def finalize(args):
@@ -193,6 +218,7 @@ def finalize(args):
     args.tiles = parse_tiles(getattr(args, "tiles", ""))
     args.tile_overlap = check_tile_overlap(getattr(args, "tile_overlap", 64), args.width, args.height) if args.tiles \
         else getattr(args, "tile_overlap", 64)
+    args.train_tiles = parse_tiles(getattr(args, "train_tiles", ""), "train_tiles")      # checked by `train` (check_train_tiles); ignored by the others
 
     args.lr_step = int(args.epochs / args.lr_step) if args.lr_step != 0 else args.epochs
     for k in ("train_dir", "valid_dir", "pretrained_model"):
