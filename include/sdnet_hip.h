@@ -223,6 +223,35 @@ int sd_tta_scale_merge_nms(const float* const* hm_host, const int64_t* sb_host, 
                            const int* ws_host, float* out, int B, int C, int h, int w, int S, int V,
                            const unsigned char* view_flips_host, sd_stream_t stream);
 
+/* ---- transposed views (no reference counterpart): the four symmetries of the grid that the flips do not reach ----
+ * `view_flips_host` is a HOST array of Vf bytes in the encoding of sd_tta_views, Vf in {1, 2, 4}, byte 0 must be 0 and every byte < 4.
+ * All three functions validate every argument on the host before any launch (anything else is SD_ERR_INVALID), are one launch each, use no
+ * workspace, no atomics and no host synchronisation, and are deterministic.  Every transposed plane is staged through LDS tiles of an odd
+ * dword pitch, so global loads and stores both run along the fast axis; 16-byte accesses where pointer and row length allow, 4-byte ones
+ * otherwise.
+ *
+ * sd_d4_views: x (B,3,H,W) fp32 NCHW contiguous -> out (Vf*B,3,H,W) and out_t (Vf*B,3,W,H); view v of image b is image v*B + b of both:
+ *       out  [v*B + b, c, y, x] = x[b, c, fy(y), fx(x)]          -- exactly what sd_tta_views writes
+ *       out_t[v*B + b, c, r, s] = xT[b, c, fy'(r), fx'(s)],  xT[b, c, r, s] = x[b, c, s, r]   -- transpose FIRST, then flip the transposed image:
+ *   fy'(r) = W-1-r if bit 1 of view v else r, fx'(s) = H-1-s if bit 0 else s.  With H == W, out_t = out + Vf*B*3*H*W makes the two one
+ *   batch of 2*Vf*B images.  The input is read once.
+ *
+ * sd_d4_merge_nms: `hm` = heatmap logits of the plain views, a strided (sb, sc) channel-slice view of (Vf*B, C, h, w); `hm_t` = those of
+ *   the transposed views, (Vf*B, C, w, h) with strides (sb_t, sc_t); out (B,C,h,w) contiguous.  With s_v(y, x) = clamped_sigmoid(hm[v*B + b, c,
+ *   fy_v(y), fx_v(x)]) as in sd_tta_merge_nms and t_v(y, x) = clamped_sigmoid(hm_t[v*B + b, c, fy'_v(x), fx'_v(y)]) (the flipped transposed map,
+ *   transposed back),
+ *       m = ((s_0 [+ s_1 [+ s_2 + s_3]]) + (t_0 [+ t_1 [+ t_2 + t_3]])) * (1 / (2 Vf))
+ *   -- each sum from its view 0 in view order, then the two sums added, in fp32, every add and the multiply rounded separately -- and out = m
+ *   where m equals the maximum of m over the 5x5 window, else 0; padding and ties exactly as sd_nms5.
+ *
+ * sd_transpose_select: x, out (B,P,S,S) fp32 contiguous, not overlapping (refused); `sel_dev` a DEVICE table of B bytes: image b of out is
+ *   the transpose of image b of x where sel_dev[b] & 1, a copy otherwise (the other bits are masked). */
+int sd_d4_views(const float* x, float* out, float* out_t, int B, int H, int W, int Vf, const unsigned char* view_flips_host,
+                sd_stream_t stream);
+int sd_d4_merge_nms(const float* hm, int64_t sb, int64_t sc, const float* hm_t, int64_t sb_t, int64_t sc_t, float* out, int B, int C, int h,
+                    int w, int Vf, const unsigned char* view_flips_host, sd_stream_t stream);
+int sd_transpose_select(const float* x, float* out, int B, int P, int S, const unsigned char* sel_dev, sd_stream_t stream);
+
 /* ---- tiled inference (no reference counterpart: the reference resizes the whole image to one network input) ----
  * A canvas of Wc = Tx*W - (Tx-1)*O by Hc = Ty*H - (Ty-1)*O pixels is cut into Ty x Tx overlapping tiles of the network's own input size
  * W x H; tile (j, i) starts at pixel (j*(H-O), i*(W-O)); tile t = j*Tx + i of image b is image t*B + b (the ordering of sd_tta_views).

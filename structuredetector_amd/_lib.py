@@ -76,6 +76,11 @@ _SIGNATURES = {
     "sd_tta_merge_nms": (c_int, _MAP + [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp]),
     # multi-scale: hm / sb / sc / hs / ws (HOST arrays of S entries), out, B, C, h, w, S, V, view_flips, stream
     "sd_tta_scale_merge_nms": (c_int, [c_vp] * 6 + [c_int] * 6 + [c_vp, c_vp]),
+    # transposed views: x, out, out_t, B, H, W, Vf, view_flips, stream / hm map, hm_t map, out, B, C, h, w, Vf, view_flips, stream /
+    # x, out, B, P, S, sel (DEVICE bytes), stream
+    "sd_d4_views": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]),
+    "sd_d4_merge_nms": (c_int, _MAP + _MAP + [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp]),
+    "sd_transpose_select": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp]),
     # tiled inference: canvas, out, B, Hc, Wc, H, W, Ty, Tx, O, stream / hm map, C, reg map, R, out_hm, out_reg, B, h, w, Ty, Tx, o, stream
     "sd_tile_views": (c_int, [c_vp, c_vp] + [c_int] * 8 + [c_vp]),
     "sd_tile_merge_nms": (c_int, _MAP + [c_int] + _MAP + [c_int, c_vp, c_vp] + [c_int] * 6 + [c_vp]),

@@ -38,7 +38,8 @@ def _detect(argv):
     if args.pretrained_model:
         net.load_state_dict(torch.load(args.pretrained_model, map_location="cpu", weights_only=True))
     net = net.eval().to(args.device)
-    if getattr(args, "tta", "none") != "none" or getattr(args, "tta_scales", ()) or getattr(args, "tiles", ()):
+    if (getattr(args, "tta", "none") != "none" or getattr(args, "tta_scales", ()) or getattr(args, "tiles", ())
+            or getattr(args, "tta_transpose", False)):
         from ..model.tta import with_tta
         net, decoder = with_tta(net, decoder, args)
     out_dir = Path("predictions")

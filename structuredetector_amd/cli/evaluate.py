@@ -51,7 +51,8 @@ def _evaluate(argv):
         net.load_state_dict(torch.load(args.pretrained_model, map_location="cpu", weights_only=True))
     net = net.eval().to(args.device)
     refuse_synthetic_resampling(args)
-    if getattr(args, "tta", "none") != "none" or getattr(args, "tta_scales", ()) or getattr(args, "tiles", ()):      # --tta / --tta_scales: the views, the forwards and the merge sit inside the per-batch step
+    if (getattr(args, "tta", "none") != "none" or getattr(args, "tta_scales", ()) or getattr(args, "tiles", ())
+            or getattr(args, "tta_transpose", False)):      # --tta / --tta_scales: the views, the forwards and the merge sit inside the per-batch step
         from ..model.tta import with_tta
         net, decoder = with_tta(net, decoder, args)
     if args.synthetic:

@@ -5,13 +5,9 @@
 // (sd_clamped_sigmoid, sd_nms5): separately rounded multiplies and adds, resampling coordinates in double -- floating-point contraction
 // is OFF in this file.
 #pragma clang fp contract(off)
-#include "sd_common.h"
+#include "sd_views.h"
 
 namespace sd {
-
-struct ViewFlips {
-    unsigned char f[4];          // bit 0 = horizontal, bit 1 = vertical (the encoding of sd_preprocess_images' `flips`)
-};
 
 // ---------------------------------------------------------------------------------------------
 // Views.  One thread per group of four input pixels of a row (VEC) or per pixel: the input is read ONCE, as contiguous spans, and every
@@ -59,12 +55,8 @@ __global__ __launch_bounds__(256) void k_tta_views(const float* __restrict__ x, 
 //        [tx0-4, tx0+68): 18 16-byte loads per row and view; a mirrored view reads the group w-4-x and swaps its components,
 //        so its span is contiguous as well.  A group lies entirely inside or entirely outside the map.
 //   else: one 4-byte load per staged cell, [tx0-2, tx0+66).
-// LDS column of map column x: x - tx0 + OFF (OFF = 4) in both variants.
+// LDS column of map column x: x - tx0 + OFF (OFF = 4) in both variants (the tile constants: sd_views.h).
 // ---------------------------------------------------------------------------------------------
-constexpr int TW = 64, TH = 16, HALO = 2, OFF = 4;
-constexpr int LH = TH + 2 * HALO;        // 20 staged rows
-constexpr int LWV = TW + 2 * OFF;        // 72 staged columns (VEC); the scalar variant fills columns OFF-HALO .. OFF+TW+HALO-1
-constexpr int LWS = TW + 2 * HALO;       // 68 cells per row loaded by the scalar variant
 
 template <int V, bool VEC>
 __global__ __launch_bounds__(256) void k_tta_merge_nms(const float* __restrict__ hm, int64_t sb, int64_t sc, int B, int C, int h, int w,
@@ -332,19 +324,6 @@ static void launch_merge_nms(bool vec, dim3 grid, hipStream_t st, const float* h
                              int tiles_x, ViewFlips vf, float* out) {
     if (vec) hipLaunchKernelGGL((k_tta_merge_nms<V, true>), grid, dim3(256), 0, st, hm, sb, sc, B, C, h, w, tiles_x, vf, out);
     else     hipLaunchKernelGGL((k_tta_merge_nms<V, false>), grid, dim3(256), 0, st, hm, sb, sc, B, C, h, w, tiles_x, vf, out);
-}
-
-static int check_views(const char* fn, int V, const unsigned char* view_flips, ViewFlips* vf, bool single_view = false) {
-    SD_REQUIRE(V == 2 || V == 4 || (single_view && V == 1), SD_ERR_INVALID, "%s: V=%d views (%s are supported)", fn, V,
-               single_view ? "1, 2 or 4" : "2 or 4");
-    SD_REQUIRE(view_flips != nullptr, SD_ERR_INVALID, "%s: null view_flips", fn);
-    *vf = ViewFlips{{0, 0, 0, 0}};
-    for (int v = 0; v < V; ++v) {
-        SD_REQUIRE(view_flips[v] < 4, SD_ERR_INVALID, "%s: view_flips[%d]=%d (bit 0 = horizontal, bit 1 = vertical)", fn, v, (int)view_flips[v]);
-        vf->f[v] = view_flips[v];
-    }
-    SD_REQUIRE(view_flips[0] == 0, SD_ERR_INVALID, "%s: view 0 must be the unflipped image (view_flips[0]=%d)", fn, (int)view_flips[0]);
-    return 0;
 }
 
 }  // namespace sd

@@ -22,6 +22,9 @@ Window (`--train_tiles CxR`; not in the reference): the Resize itself targets th
 only a W x H window of it at a random origin is produced, `Image.resize(canvas, BILINEAR).crop(window)` byte for byte
 (`sd_preprocess_images_window`: the source rows and columns under the window are all that is read); every later stage works on the window,
 the annotations follow with `ann.resize` to the canvas and `affine_annotation` by the shift.
+Transpose (`--aug_transpose P`; not in the reference): last, after the flips, a selected image of the assembled (square) batch has its x and
+y swapped (`sd_transpose_select`, one launch: lossless, with the flips the eight symmetries of the grid); the annotations follow with
+`utils.misc.transpose_annotation`.
 """
 from __future__ import annotations
 
@@ -33,7 +36,7 @@ import torch
 
 from .. import _lib as L
 from ..utils.args import parse_tiles, tile_canvas
-from ..utils.misc import affine_annotation, clip_annotation, hflip_annotation, mosaic_annotation, vflip_annotation
+from ..utils.misc import affine_annotation, clip_annotation, hflip_annotation, mosaic_annotation, transpose_annotation, vflip_annotation
 
 PRECISION_BITS = 32 - 8 - 2
 _MEAN = (0.485, 0.456, 0.406)
@@ -372,6 +375,22 @@ def preprocess_image_list(pointers: torch.Tensor, hin: int, win: int, out_size, 
     return out
 
 
+def transpose_select(batch: torch.Tensor, select) -> torch.Tensor:
+    """(B, P, S, S) fp32 on the GPU -> a new tensor: image b transposed (x and y swapped) where `select[b] & 1`, copied otherwise
+    (`sd_transpose_select`, one launch).  select: B flags (a sequence, or a uint8 tensor on either side)."""
+    L.require_cuda(batch)
+    x = batch.contiguous().float()
+    if x.dim() != 4 or x.shape[2] != x.shape[3]:
+        raise L.SdError(f"transpose_select expects a (B, P, S, S) batch of square images, got {tuple(x.shape)}")
+    B, P, S, _ = x.shape
+    sel = torch.as_tensor(select, dtype=torch.uint8).to(x.device, non_blocking=True)
+    if sel.numel() != B:
+        raise L.SdError("select must have one entry per image")
+    out = torch.empty_like(x)
+    L.check(L.lib().sd_transpose_select(x.data_ptr(), out.data_ptr(), B, P, S, sel.data_ptr(), L.stream()), "sd_transpose_select")
+    return out
+
+
 def jitter_words(order, brightness, contrast, saturation, hue):
     """One image's ColorJitter parameters in the form `sd_preprocess_images_jitter` takes: the op order (a permutation of
     0 brightness, 1 contrast, 2 saturation, 3 hue) packed two bits each, the hue shift byte `uint8(hue * 255)` torchvision's adjust_hue
@@ -408,6 +427,10 @@ class ValidationAugmentation:
 
     def window_draws_for(self, n):
         """((Wc, Hc), n origins (x0, y0)) or None: validation always shows the whole frame and never draws."""
+        return None
+
+    def transpose_draws_for(self, n):
+        """n flags (1 = the sample is transposed) or None: validation never transposes and never draws."""
         return None
 
     @staticmethod
@@ -456,6 +479,9 @@ class ValidationAugmentation:
         inverse = None if warps is None else [affine_inverse_matrix((W, H), a, s, (tx, ty)) for a, s, tx, ty in warps]
         mosaics = self.mosaic_draws_for(n, [idx for idx, _ in groups.values()])
         windows = self.window_draws_for(n)
+        transposes = self.transpose_draws_for(n)
+        if transposes is not None and W != H:
+            raise L.SdError(f"aug_transpose: a transposed sample needs a square batch, not {W} x {H}")
         out = torch.empty((n, 3, H, W), dtype=torch.float32, device=dev)
         for (hin, win), (idx, stack) in groups.items():
             f = None if flips is None else [flips[i] for i in idx]
@@ -500,7 +526,11 @@ class ValidationAugmentation:
                     hflip_annotation(ann, (W, H))                    # transforms.py:15 (on the resized image)
                 if flips is not None and flips[i] & 2:
                     vflip_annotation(ann, (W, H))                    # transforms.py:28
+                if transposes is not None and transposes[i]:
+                    transpose_annotation(ann, (W, H))                # last, like the image's
                 clip_annotation(ann, (W, H))                         # transforms.py:154
+        if transposes is not None:                                   # one launch over the assembled batch, after the flips
+            out = transpose_select(out, transposes)
         return out, annotations
 
 
@@ -523,6 +553,7 @@ class TrainAugmentation(ValidationAugmentation):
         self.scale = float(getattr(args, "aug_scale", 0.0))                # scale uniform in [1 - scale, 1 + scale]
         self.translate = float(getattr(args, "aug_translate", 0.0))        # shift uniform in [-translate, translate] * (width, height)
         self.mosaic = float(getattr(args, "aug_mosaic", 0.0))              # per-image probability of becoming a mosaic of four
+        self.transpose = float(getattr(args, "aug_transpose", 0.0))        # per-image probability of being transposed (square sizes only)
         self.train_tiles = parse_tiles(getattr(args, "train_tiles", ""), "train_tiles")   # (Tx, Ty) of the canvas the windows are cut from, () = off
         self.tile_overlap = int(getattr(args, "tile_overlap", 64))
 
@@ -589,6 +620,13 @@ class TrainAugmentation(ValidationAugmentation):
         Wc, Hc = tile_canvas(W, H, self.train_tiles, self.tile_overlap)
         u = torch.rand(n, 2, dtype=torch.float64).tolist()
         return (Wc, Hc), [(int(ux * (Wc - W + 1)), int(uy * (Hc - H + 1))) for ux, uy in u]
+
+    def transpose_draws_for(self, n):
+        """n flags (1 where u < P) from ONE more draw on torch's global generator, `rand(n)` in float64, made after that of
+        `window_draws_for`; None, and no draw at all, with `--aug_transpose 0` or augmentation off."""
+        if self.args.no_augmentation or self.transpose == 0:
+            return None
+        return (torch.rand(n, dtype=torch.float64) < self.transpose).to(torch.uint8).tolist()
 
     def trigger_random_resize(self):
         if self.args.no_augmentation:

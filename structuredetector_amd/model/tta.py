@@ -21,7 +21,13 @@ multiples of 32 (`TrainAugmentation.trigger_random_resize`), so a trained model 
 resized + normalised to every size (each from the original pixels, like training; never from an already resized tensor), each size goes
 through steps 1 and 2, and ONE launch (`sd_tta_scale_merge_nms`) resamples the S x V heatmaps to the base grid (bilinear, half-pixel
 centres), averages them as probabilities and suppresses.  Offsets and embeddings are the base size's view 0: an embedding is in cells of
-its own scale."""
+its own scale.
+
+Transposed views (`--tta_transpose`, `TransposeTta`): the flips are four of the eight symmetries of the grid; the other four are the
+transposes (quarter turns and diagonal mirrors), lossless like the flips.  `sd_d4_views` writes, for every flip view, the view and the same
+flip of the TRANSPOSED image; a square input is one forward over 2*Vf*B images, any other two forwards (H x W and W x H);
+`sd_d4_merge_nms` flips and transposes the heatmaps back, averages the 2*Vf probability maps and suppresses, in one launch.  Offsets and
+embeddings are view 0's, as above."""
 from __future__ import annotations
 
 import ctypes as C
@@ -61,6 +67,41 @@ def tta_merge_nms(logits: torch.Tensor, flips) -> torch.Tensor:
     out = torch.empty((VB // V, Cc, h, w), dtype=torch.float32, device=t.device)
     L.check(L.lib().sd_tta_merge_nms(p, sb, sc, out.data_ptr(), VB // V, Cc, h, w, V, (C.c_ubyte * V)(*flips), L.stream()),
             "sd_tta_merge_nms")
+    return out
+
+
+def d4_views(images: torch.Tensor, flips, joint=False):
+    """(B, 3, H, W) fp32 -> (plain views (Vf*B, 3, H, W), transposed views (Vf*B, 3, W, H)), view v of image b at index v*B + b of both:
+    `flip_f(x)` and `flip_f(x.transpose(-1, -2))` (`sd_d4_views`, one launch).  flips: `VIEW_FLIPS[mode]`, or (0,) for one view.
+    joint=True (H == W only): ONE (2*Vf*B, 3, H, W) batch, the plain views first."""
+    L.require_cuda(images)
+    x = images.contiguous().float()
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise L.SdError(f"d4_views expects a (B, 3, H, W) batch, got {tuple(x.shape)}")
+    B, _, H, W = x.shape
+    if joint and H != W:
+        raise L.SdError(f"d4_views: one joint batch needs a square input, got {W} x {H}")
+    Vf = len(flips)
+    buf = torch.empty((2 * Vf * B, 3, H, W), dtype=torch.float32, device=x.device)
+    out, out_t = buf[:Vf * B], buf[Vf * B:].view(Vf * B, 3, W, H)
+    L.check(L.lib().sd_d4_views(x.data_ptr(), out.data_ptr(), out_t.data_ptr(), B, H, W, Vf, (C.c_ubyte * Vf)(*flips), L.stream()), "sd_d4_views")
+    return buf if joint else (out, out_t)
+
+
+def d4_merge_nms(logits: torch.Tensor, logits_t: torch.Tensor, flips) -> torch.Tensor:
+    """Heatmap logits of the plain views (Vf*B, C, h, w) and of the transposed views (Vf*B, C, w, h) (channel-slice views pass without a
+    copy) -> (B, C, h, w): nms((sum_v flip_v(sigmoid(plain_v)) + sum_v flip_v(sigmoid(transposed_v)).transpose(-1, -2)) / (2 Vf)), one
+    launch (`sd_d4_merge_nms`)."""
+    L.require_cuda(logits, logits_t)
+    Vf = len(flips)
+    t, p, sb, sc = L.map_view(logits)
+    tt, pt, sbt, sct = L.map_view(logits_t)
+    VB, Cc, h, w = t.shape
+    if VB % Vf or tuple(tt.shape) != (VB, Cc, w, h) or tt.device != t.device:
+        raise L.SdError(f"d4_merge_nms: {tuple(t.shape)} and {tuple(tt.shape)} are not {Vf} views of a batch and their transposes")
+    out = torch.empty((VB // Vf, Cc, h, w), dtype=torch.float32, device=t.device)
+    L.check(L.lib().sd_d4_merge_nms(p, sb, sc, pt, sbt, sct, out.data_ptr(), VB // Vf, Cc, h, w, Vf, (C.c_ubyte * Vf)(*flips), L.stream()),
+            "sd_d4_merge_nms")
     return out
 
 
@@ -188,6 +229,39 @@ class FlipTta:
         return TtaOutput(anchor_hm=anchor_hm, part_hm=part_hm, offsets=offsets[:B], embeddings=embeddings[:B])
 
 
+class TransposeTta:
+    """`net` behind the transposed-view test, combined with the flip views of `mode` ("none": the image and its transpose):
+    `TransposeTta(net, args, mode)(images)` returns a `TtaOutput` like `FlipTta`: the merged, suppressed PROBABILITY maps of 2*Vf views and
+    view 0's offsets / embeddings (no copy).  A square batch is one forward over 2*Vf*B images, any other two forwards of Vf*B images, at
+    H x W and at W x H.  Decode it with `tta_decoder(args)`."""
+
+    def __init__(self, net, args, mode="none"):
+        if mode != "none" and mode not in VIEW_FLIPS:
+            raise L.SdError(f"unknown test-time augmentation mode {mode!r} (one of {', '.join(MODES)})")
+        self.net, self.args, self.mode = net, args, mode
+        self.flips = VIEW_FLIPS.get(mode, (0,))
+        self.label_count, self.part_count = len(args.labels), len(args.parts)
+
+    def __call__(self, images):
+        B, n = images.shape[0], len(self.flips) * images.shape[0]
+        M, nb = self.label_count, self.label_count + self.part_count
+        if images.shape[2] == images.shape[3]:
+            heat, offsets, embeddings = head_parts(self.net(d4_views(images, self.flips, joint=True)), M, nb)
+            heat_t = [hm[n:] for hm in heat]
+            heat = [hm[:n] for hm in heat]
+        else:
+            plain, transposed = d4_views(images, self.flips)
+            heat, offsets, embeddings = head_parts(self.net(plain), M, nb)
+            heat_t, _, _ = head_parts(self.net(transposed), M, nb)
+        if len(heat) == 1 and len(heat_t) == 1:                        # adjacent slices of one head tensor: one launch
+            merged = d4_merge_nms(heat[0], heat_t[0], self.flips)
+            anchor_hm, part_hm = merged[:, :M], merged[:, M:]
+        else:
+            heat, heat_t = ([hm[0][:, :M], hm[0][:, M:]] if len(hm) == 1 else hm for hm in (heat, heat_t))
+            anchor_hm, part_hm = (d4_merge_nms(heat[k], heat_t[k], self.flips) for k in (0, 1))
+        return TtaOutput(anchor_hm=anchor_hm, part_hm=part_hm, offsets=offsets[:B], embeddings=embeddings[:B])
+
+
 def tta_decoder(args) -> FusedOutputDecoder:
     """The decoder that belongs with `FlipTta`: top-k directly on the merged, suppressed maps."""
     return FusedOutputDecoder(args)
@@ -196,11 +270,17 @@ def tta_decoder(args) -> FusedOutputDecoder:
 def with_tta(net, decoder, args):
     """(net, decoder) as they are for `--tta none`, no `--tta_scales` and no `--tiles` (or no such attributes); `net` behind `FlipTta` for
     a flip mode alone; `net` behind `ScaleTta` when `--tta_scales` adds at least one input size.  Both come with `tta_decoder(args)`.
-    `--tiles` (model/tiles.py) puts `net` behind `TiledNet` with its `tiled_decoder`, and is refused together with the other two."""
+    `--tiles` (model/tiles.py) puts `net` behind `TiledNet` with its `tiled_decoder`, and is refused together with the other two.
+    `--tta_transpose`, alone or with a flip mode, puts `net` behind `TransposeTta`; with `--tta_scales` or `--tiles` it is refused."""
     from ..utils.args import parse_tiles, parse_tta_scales
     mode = getattr(args, "tta", "none") or "none"
     ratios = parse_tta_scales(getattr(args, "tta_scales", "") or "")
     grid = parse_tiles(getattr(args, "tiles", "") or "")
+    if getattr(args, "tta_transpose", False):
+        if ratios or grid:
+            raise L.SdError("--tta_transpose does not combine with --tta_scales / --tiles: the transposed views are merged on one grid at one "
+                            "input size; drop one of them")
+        return TransposeTta(net, args, mode), tta_decoder(args)
     if grid:
         if mode != "none" or ratios:
             raise L.SdError("--tiles does not combine with --tta / --tta_scales: the tile outputs are stitched as they are; drop one of them")

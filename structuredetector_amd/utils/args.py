@@ -75,6 +75,11 @@ _FLAGS = [
                              "also runs at int(R*W/32)*32 x int(R*H/32)*32 -- training's multi-scale rule, each size resampled from the source "
                              "image, at most 5 sizes -- the heatmaps are resampled to the base grid, averaged and decoded once. Combines "
                              "with --tta. Not consulted by train. Empty = off.")),
+    (("--tta_transpose",), dict(action="store_true", help="Transposed-view test-time augmentation in evaluate / detect / Predictor: the "
+                                "network also runs on the transposed image for every flip view, so the forward sees 2x the views (2 alone, "
+                                "4 with --tta hflip or vflip, 8 with --tta hvflip: the eight symmetries of the grid; a non-square input takes "
+                                "two forwards), the heatmaps are turned back, averaged and decoded once. Combines with --tta; does not "
+                                "combine with --tta_scales / --tiles. Not consulted by train.")),
     (("--tiles",), dict(type=str, default="", metavar="CxR", help="Tiled inference in evaluate / detect / Predictor: columns x rows of "
                         "overlapping tiles (e.g. 2x2 or 3x2, each 1 .. 8). The source image is resized to a canvas of C*W - (C-1)*O by "
                         "R*H - (R-1)*O pixels (O = --tile_overlap), the network runs on every W x H tile -- the forward sees C*R times "
@@ -101,6 +106,10 @@ _FLAGS = [
                              "becomes a mosaic of itself and three other images of its batch at half scale around a random centre. A mosaic "
                              "carries up to four images' objects: raise --max_objects / --max_parts accordingly (what exceeds them is "
                              "truncated by the target encoder as always). Not consulted by evaluate / detect.")),
+    (("--aug_transpose",), dict(type=float, default=0.0, metavar="P", help="Training augmentation: with probability P (0 .. 1; 0 = off) an "
+                                "image is transposed (x and y swapped: a lossless quarter turn with the flips, no resampling and no fill), "
+                                "after the flips. Needs a square network input (--width equal to --height). Not consulted by evaluate / "
+                                "detect.")),
 ]
 
 _POSITIVE = ["in_channels", "fpn_depth", "batch_size", "epochs", "learning_rate", "down_ratio", "max_objects", "max_parts"]
@@ -194,6 +203,16 @@ def check_train_tiles(args):
     return grid
 
 
+def check_aug_transpose(args):
+    """`--aug_transpose` on a parsed namespace -> P, as `train` checks it (model/trainer.py): a batch has ONE shape, so a transposed sample
+    needs width == height (the per-epoch multi-scale rule and the `--train_tiles` windows keep a square square)."""
+    p = float(getattr(args, "aug_transpose", 0.0) or 0.0)
+    if p > 0 and args.width != args.height:
+        raise ValueError(f"'aug_transpose' transposes samples inside a batch of one shape: it needs a square network input, not "
+                         f"{args.width} x {args.height}")
+    return p
+
+
 def finalize(args):
     """Validation + derived fields (args.py:178-269) on an already parsed namespace."""
     for side in ("width", "height"):
@@ -214,6 +233,7 @@ def finalize(args):
     assert 0 <= getattr(args, "aug_scale", 0.0) < 1, "'aug_scale' should be in [0, 1["
     assert 0 <= getattr(args, "aug_translate", 0.0) <= 0.5, "'aug_translate' should be in [0, 0.5]"
     assert 0 <= getattr(args, "aug_mosaic", 0.0) <= 1, "'aug_mosaic' should be in [0, 1]"
+    assert 0 <= getattr(args, "aug_transpose", 0.0) <= 1, "'aug_transpose' should be in [0, 1]"
     args.tta_scales = parse_tta_scales(getattr(args, "tta_scales", ""))
     args.tiles = parse_tiles(getattr(args, "tiles", ""))
     args.tile_overlap = check_tile_overlap(getattr(args, "tile_overlap", 64), args.width, args.height) if args.tiles \

@@ -55,6 +55,20 @@ def vflip_annotation(annotation, img_size):
     return annotation
 
 
+def transpose_annotation(annotation, img_size):
+    """Follow a transpose of the image (x and y swapped), in place; img_size = (W, H) of the image BEFORE the transpose (the result lives in
+    an H x W frame).  Every keypoint and box swaps its axes; nothing leaves the frame.  An involution, and transpose o hflip = vflip o
+    transpose."""
+    for obj in annotation.objects:
+        obj.x, obj.y = obj.y, obj.x
+        for p in obj.parts:
+            p.x, p.y = p.y, p.x
+        if obj.box is not None:
+            b = obj.box
+            b.x_min, b.x_max, b.y_min, b.y_max = b.y_min, b.y_max, b.x_min, b.x_max
+    return annotation
+
+
 def affine_annotation(annotation, forward_matrix, img_size):
     """Follow an affine warp of the image (data/augment.py: affine_forward_matrix), in place.  A pixel index p is the pixel centre p + 0.5
     -- the convention under which hflip_annotation's w - x - 1 holds -- so p' + 0.5 = F (p + 0.5); coordinates stay floats.  Unlike a flip, a
