@@ -252,6 +252,30 @@ int sd_d4_merge_nms(const float* hm, int64_t sb, int64_t sc, const float* hm_t, 
                     int w, int Vf, const unsigned char* view_flips_host, sd_stream_t stream);
 int sd_transpose_select(const float* x, float* out, int B, int P, int S, const unsigned char* sel_dev, sd_stream_t stream);
 
+/* ---- evaluation matching (no reference counterpart: the reference matches on the host, at one confidence threshold) ----
+ * Labels EVERY top-k slot of a decoded batch a hit or a miss against the ground truth, the way the Evaluator matches anchors and raw parts
+ * (greedy by descending score; a prediction only ever tries its nearest ground truth of its class).  Whether slot i is a hit depends only
+ * on the slots ranked above it, so the counters at ANY confidence threshold are prefix counts over the slots the threshold keeps.
+ *   a_list (B,K,4) fp32, words x, y, score, class: the anchor_out part of sd_decode's `packed`;  p_list (B,P,6) fp32, same first four words:
+ *   its part_out part.  1 <= K, P <= SD_MAX_TOPK.  Both lists are in score-descending order, as sd_decode writes them (not checked).
+ *   gt_xy (G,2) fp64: every ground-truth point of the batch in SOURCE-IMAGE pixels;  gt_cls (G) int32: their classes (negative: matches
+ *   nothing);  gt_off (2B+1) int32: segment b = [gt_off[b], gt_off[b+1]) holds the anchors of image b, segment B + b its parts (device
+ *   data: the kernel clamps every offset into [0, G], so any table is memory-safe);  G >= 0 (the pointers are needed even then).
+ *   img (B,3) fp64: per image fx, fy, thr;  sx, sy: cell -> network-input pixel scale.
+ *   match, dist: (B, K+P) int32 / fp64; row b holds the K anchor slots, then the P part slots.
+ * For slot i of a list with segment S, in fp64 with every operation rounded separately (no contraction):
+ *       X = ((double)x * sx) * fx;   Y = ((double)y * sy) * fy;   d_j = hypot(X - gx_j, Y - gy_j)  over the j of S with gt_cls[j] == (int)class
+ *       j* = the first minimum (lowest j on equal distance);  dist = d_j*, or +inf when S has no ground truth of that class
+ *       match = j* - gt_off[S]  when d_j* < thr (strictly) AND i is the lowest slot index of its list with that j* and a distance below thr,
+ *               else -1 (a prediction gets no second choice).
+ * All slots are matched whatever their score: a filler slot has a higher index than every real one and cannot displace it.
+ * One launch (one 256-thread block per image and list; the ground truths pass through LDS SD_EVAL_GT_CHUNK at a time), no workspace, no
+ * host synchronisation, integer LDS atomics only: deterministic.  Null pointers, non-positive B / K / P, K or P beyond SD_MAX_TOPK and a
+ * negative G: SD_ERR_INVALID; a_list / gt_xy not 16-byte, p_list / img / dist not 8-byte, the int32 tables not 4-byte aligned: SD_ERR_ALIGN. */
+#define SD_EVAL_GT_CHUNK 1024
+int sd_eval_match(const float* a_list, const float* p_list, int B, int K, int P, const double* gt_xy, const int* gt_cls, const int* gt_off,
+                  int G, const double* img, double sx, double sy, int* match, double* dist, sd_stream_t stream);
+
 /* ---- tiled inference (no reference counterpart: the reference resizes the whole image to one network input) ----
  * A canvas of Wc = Tx*W - (Tx-1)*O by Hc = Ty*H - (Ty-1)*O pixels is cut into Ty x Tx overlapping tiles of the network's own input size
  * W x H; tile (j, i) starts at pixel (j*(H-O), i*(W-O)); tile t = j*Tx + i of image b is image t*B + b (the ordering of sd_tta_views).

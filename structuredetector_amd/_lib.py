@@ -81,6 +81,8 @@ _SIGNATURES = {
     "sd_d4_views": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]),
     "sd_d4_merge_nms": (c_int, _MAP + _MAP + [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp]),
     "sd_transpose_select": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp]),
+    # evaluation matching: a_list, p_list, B, K, P, gt_xy, gt_cls, gt_off, G, img, sx, sy, match, dist, stream
+    "sd_eval_match": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_vp, C.c_double, C.c_double, c_vp, c_vp, c_vp]),
     # tiled inference: canvas, out, B, Hc, Wc, H, W, Ty, Tx, O, stream / hm map, C, reg map, R, out_hm, out_reg, B, h, w, Ty, Tx, o, stream
     "sd_tile_views": (c_int, [c_vp, c_vp] + [c_int] * 8 + [c_vp]),
     "sd_tile_merge_nms": (c_int, _MAP + [c_int] + _MAP + [c_int, c_vp, c_vp] + [c_int] * 6 + [c_vp]),

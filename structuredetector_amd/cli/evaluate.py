@@ -16,7 +16,7 @@ import torch.distributed as dist
 from ..data import CropDataset, Decoder
 from ..model import Evaluator, Network
 from ..utils import Arguments
-from ..utils.distributed import gather_evaluator, init_from_env, shard_range, world_info
+from ..utils.distributed import gather_evaluator, gather_pr_curve, init_from_env, shard_range, world_info
 
 
 def main(argv=None):
@@ -55,6 +55,10 @@ def _evaluate(argv):
             or getattr(args, "tta_transpose", False)):      # --tta / --tta_scales: the views, the forwards and the merge sit inside the per-batch step
         from ..model.tta import with_tta
         net, decoder = with_tta(net, decoder, args)
+    curve = None
+    if getattr(args, "pr_curve", False):                   # --pr_curve: every threshold of the grid from one matching pass (model/pr_curve.py)
+        from ..model.pr_curve import PrCurve
+        curve = PrCurve(args)
     if args.synthetic:
         from ..data.synthetic import synthetic_samples
         lo, hi = shard_range(args.synthetic, rank, world)
@@ -63,18 +67,27 @@ def _evaluate(argv):
                 output = net(image[None].to(args.device))
             data = decoder(output, return_metadata=True, metadata_fields=("annotation", "raw_parts"))
             evaluator.accumulate(data["annotation"][0], annotation, data["raw_parts"][0], True, True)
+            if curve is not None:
+                curve.submit(decoder, output, [annotation]).result()
     else:
         from ..model.predictor import batched_outputs
         dataset = CropDataset(args, args.valid_dir, raw=True)               # decode only; Resize + Normalize run on the GPU per batch
         shard = shard_range(len(dataset), rank, world)
-        for prediction, annotation, raw_parts, _ in batched_outputs(net, decoder, dataset, args, index_range=shard):
+        for prediction, annotation, raw_parts, _ in batched_outputs(net, decoder, dataset, args, index_range=shard, pr_curve=curve):
             # the annotation was resized to the network input and clipped (Resize + Encode's clip); the Evaluator maps both sides back to img_size
             evaluator.accumulate(prediction, annotation, raw_parts, True, True)
     evaluator = gather_evaluator(evaluator)
+    if curve is not None:
+        curve = gather_pr_curve(curve)
+        evaluator.pr_curve = curve
     if rank == 0:
         evaluator.pretty_print()
         if args.csv_path is not None:
             evaluator.save_kps_csv(args.csv_path)
+        if curve is not None:
+            curve.pretty_print()
+            if getattr(args, "csv_pr_path", None) is not None:
+                curve.save_csv(args.csv_pr_path)
     return evaluator
 
 

@@ -22,13 +22,16 @@ def index_batches(n, batch, lo=0):
     return [list(range(i, min(i + batch, n))) for i in range(lo, n, batch)]
 
 
-def batched_decodes(net, decoder, dataset, args, batch=None, workers=None, with_raw_parts=True, depth=2, cache=None, index_range=None):
+def batched_decodes(net, decoder, dataset, args, batch=None, workers=None, with_raw_parts=True, depth=2, cache=None, index_range=None,
+                    pr_curve=None):
     """dataset: `CropDataset(args, dir, raw=True)` or `PredictionDataset(dir, args, raw=True)` -- items ((H, W, 3) uint8 tensor,
     ImageAnnotation in ORIGINAL pixels with img_size).  Yields, per decoded batch and in dataset order,
     (list of prediction ImageAnnotations in network-input pixels, list of ground-truth annotations in network-input pixels (resized +
     clipped like Resize + Encode do, transforms.py:47-60,154), list of raw_parts or None, the batch's output dict of (B, C, h, w) views).
     index_range: (lo, hi), the items to run (a rank's shard, utils/distributed.shard_range); batches are cut inside it.  Default: all.
-    cache: a data/image_cache.py DeviceImageCache the feed reads cached images from (CropDataset only), or None."""
+    cache: a data/image_cache.py DeviceImageCache the feed reads cached images from (CropDataset only), or None.
+    pr_curve: a model/pr_curve.py PrCurve fed with every batch (queued right behind the decode, on its packed result when that holds the
+    exact top-k; finished alongside the decode's result, so the queue-ahead overlap is kept), or None: nothing is launched."""
     from ..data.augment import ValidationAugmentation
     from ..data.feeder import BatchFeeder, default_decode_workers
     batch = int(batch or getattr(args, "eval_batch", 16) or 16)
@@ -40,8 +43,10 @@ def batched_decodes(net, decoder, dataset, args, batch=None, workers=None, with_
     pending = None
 
     def finish(p):
-        handle, anns, out = p
+        handle, anns, out, matching = p
         preds, raws = handle.result()
+        if matching is not None:
+            matching.result()
         return list(preds), list(anns), (list(raws) if raws is not None else None), out
 
     threads = torch.get_num_threads()
@@ -57,7 +62,8 @@ def batched_decodes(net, decoder, dataset, args, batch=None, workers=None, with_
                 if isinstance(out, torch.Tensor):  # Network(raw_output=True)
                     out = split_head(net, out)
                 handle = decoder.submit(out, with_raw_parts=with_raw_parts)
-            cur = (handle, anns, out)
+                matching = None if pr_curve is None else pr_curve.submit(decoder, out, anns, packed=handle.packed if with_raw_parts else None)
+            cur = (handle, anns, out, matching)
             if pending is not None:
                 yield finish(pending)
             pending = cur
@@ -68,10 +74,11 @@ def batched_decodes(net, decoder, dataset, args, batch=None, workers=None, with_
 
 
 def batched_outputs(net, decoder, dataset, args, batch=None, workers=None, with_raw_parts=True, keep_output=False, depth=2, cache=None,
-                    index_range=None):
+                    index_range=None, pr_curve=None):
     """`batched_decodes` one image at a time: yields, per image and in dataset order, (prediction, ground-truth annotation, raw_parts or
     None, this image's output dict of (1, C, h, w) views when keep_output else None)."""
-    for preds, anns, raws, out in batched_decodes(net, decoder, dataset, args, batch, workers, with_raw_parts, depth, cache, index_range):
+    for preds, anns, raws, out in batched_decodes(net, decoder, dataset, args, batch, workers, with_raw_parts, depth, cache, index_range,
+                                                  pr_curve):
         for i, (pred, ann) in enumerate(zip(preds, anns)):
             yield pred, ann, (raws[i] if raws is not None else None), ({k: v[i:i + 1] for k, v in out.items()} if keep_output else None)
 

@@ -95,6 +95,14 @@ _FLAGS = [
                               "Windows are drawn under --no_augmentation too. Needs a directory (not --synthetic). The validation pass of train "
                               "still shows whole frames: measure tiled deployment with evaluate --tiles. Not consulted by evaluate / detect. "
                               "Empty or 1x1 = off.")),
+    (("--pr_curve",), dict(action="store_true", help="evaluate: also sweep the anchor-location and part-location metrics over the "
+                           "confidence thresholds 0.01 .. 0.99 (and --conf_threshold) from ONE matching pass on the GPU, and print per "
+                           "group the average precision (area under the precision envelope over recall), the best F1 with its threshold "
+                           "and the operating point at --conf_threshold. CSI and classification stay at --conf_threshold. Only the "
+                           "decoder's top-k slots are seen, which bounds the detections at low thresholds: raise --max_objects / "
+                           "--max_parts. Not consulted by train / detect.")),
+    (("--save_csv_pr",), dict(dest="csv_pr_path", type=Path, default=None, metavar="PATH", help="evaluate --pr_curve: write the curves here, "
+                              "one row per group, label and threshold: tp, ndet, npos, precision, recall, F1, mean accuracy.")),
     (("--aug_rotate",), dict(type=float, default=0.0, metavar="DEG", help="Training augmentation: rotate every image about its centre by an "
                              "angle uniform in [-DEG, DEG] (0 .. 180; what leaves the frame is dropped from the annotation, what the image does "
                              "not cover is filled with the ImageNet mean; 0 = off). Not consulted by evaluate / detect.")),

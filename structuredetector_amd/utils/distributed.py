@@ -48,6 +48,22 @@ def gather_evaluator(evaluator, group=None):
     return merged
 
 
+def gather_pr_curve(curve, group=None):
+    """Every rank's PrCurve tables, merged in rank order into a fresh PrCurve (`PrCurve.merge`); every rank returns the same merged
+    object.  Without a process group (or at world 1) the curve itself is returned."""
+    from ..model.pr_curve import PrCurve
+    _, world = world_info(group)
+    if world == 1:
+        return curve
+    parts = _gather_objects((curve.tables, curve.images, curve.redone), group)
+    merged = PrCurve(curve.args, curve.thresholds)
+    for tables, images, redone in parts:
+        other = PrCurve(curve.args, curve.thresholds)
+        other.tables, other.images, other.redone = tables, images, redone
+        merged.merge(other)
+    return merged
+
+
 def gather_objects(items, group=None):
     """Every rank's list concatenated in rank order (on every rank); `items` itself at world 1."""
     _, world = world_info(group)
