@@ -28,8 +28,6 @@ __device__ __forceinline__ void vec_cell(int i, int* r, int* q) {
     *q = (i & 7) | (((i >> 5) & 1) << 3);
 }
 
-__device__ __forceinline__ float4 reversed(const float4 v) { return make_float4(v.w, v.z, v.y, v.x); }
-
 // ---------------------------------------------------------------------------------------------
 // Views.  One block per 64 x 64 tile of one input plane: the tile is read ONCE (contiguous spans), every plain view is written from
 // registers as k_tta_views writes it, and every transposed view from the LDS tile: view k of the transposed (W, H) plane has
@@ -287,131 +285,42 @@ __global__ __launch_bounds__(256) void k_d4_merge_nms(const float* __restrict__ 
         }
     }
 
-    // ---- plain views (k_tta_merge_nms's staging); their loads are in flight across the barrier
+    // ---- plain views (k_tta_merge_nms's staging, sd_views.h); their loads are in flight across the barrier
     if (VEC) {
-        constexpr int GR = LWV / 4, NG = LH * GR;
-        constexpr int NLD = (NG + 255) / 256;
-        float4 ld[NLD][V];
-#pragma unroll
-        for (int j = 0; j < NLD; ++j) {
-            const int i = tid + j * 256;
-            const int r = i / GR, q = i - r * GR;
-            const int y = ty0 + r - HALO, x = tx0 - OFF + 4 * q;
-            const bool ok = i < NG && y >= 0 && y < h && x >= 0 && x < w;
-#pragma unroll
-            for (int v = 0; v < V; ++v) {
-                const int sy = (vf.f[v] & 2) ? h - 1 - y : y;
-                const int sx = (vf.f[v] & 1) ? w - 4 - x : x;
-                ld[j][v] = *reinterpret_cast<const float4*>(plane[v] + (ok ? (int64_t)sy * w + sx : 0));
-            }
-        }
+        float4 ld[NLDV][V];
+        plain_load_vec(ld, plane, vf, tid, ty0, tx0, h, w);
         __syncthreads();
 #pragma unroll
-        for (int j = 0; j < NLD; ++j) {
-            const int i = tid + j * 256;
-            const int r = i / GR, q = i - r * GR;
-            const int y = ty0 + r - HALO, x = tx0 - OFF + 4 * q;
-            const bool ok = i < NG && y >= 0 && y < h && x >= 0 && x < w;
-            float4 m;
-#pragma unroll
-            for (int v = 0; v < V; ++v) {
-                const float4 t = (vf.f[v] & 1) ? reversed(ld[j][v]) : ld[j][v];
-                const float4 s = make_float4(clamped_sigmoid(t.x), clamped_sigmoid(t.y), clamped_sigmoid(t.z), clamped_sigmoid(t.w));
-                if (v == 0) m = s;
-                else { m.x = m.x + s.x; m.y = m.y + s.y; m.z = m.z + s.z; m.w = m.w + s.w; }
-            }
-            if (ok) {
-                const int ry = r + OFF - HALO;
-                m.x = (m.x + Tt[4 * q][ry]) * inv; m.y = (m.y + Tt[4 * q + 1][ry]) * inv;
-                m.z = (m.z + Tt[4 * q + 2][ry]) * inv; m.w = (m.w + Tt[4 * q + 3][ry]) * inv;
+        for (int j = 0; j < NLDV; ++j) {
+            const TileCell t = plain_cell_vec(tid + j * 256, ty0, tx0, h, w);
+            float4 m = plain_sum_vec(ld[j], vf);
+            if (t.ok) {
+                const int ry = t.r + OFF - HALO;
+                m.x = (m.x + Tt[t.c][ry]) * inv; m.y = (m.y + Tt[t.c + 1][ry]) * inv;
+                m.z = (m.z + Tt[t.c + 2][ry]) * inv; m.w = (m.w + Tt[t.c + 3][ry]) * inv;
             } else {
                 m = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
             }
-            if (i < NG) *reinterpret_cast<float4*>(&S[r][4 * q]) = m;
+            if (t.in) *reinterpret_cast<float4*>(&S[t.r][t.c]) = m;
         }
     } else {
-        constexpr int NC = LH * LWS;
-        constexpr int NLD = (NC + 255) / 256;
-        float ld[NLD][V];
-#pragma unroll
-        for (int j = 0; j < NLD; ++j) {
-            const int i = tid + j * 256;
-            const int r = i / LWS, cc = i - r * LWS;
-            const int y = ty0 + r - HALO, x = tx0 + cc - HALO;
-            const bool ok = i < NC && y >= 0 && y < h && x >= 0 && x < w;
-#pragma unroll
-            for (int v = 0; v < V; ++v) {
-                const int sy = (vf.f[v] & 2) ? h - 1 - y : y;
-                const int sx = (vf.f[v] & 1) ? w - 1 - x : x;
-                ld[j][v] = plane[v][ok ? (int64_t)sy * w + sx : 0];
-            }
-        }
+        float ld[NLDS][V];
+        plain_load_scalar(ld, plane, vf, tid, ty0, tx0, h, w);
         __syncthreads();
 #pragma unroll
-        for (int j = 0; j < NLD; ++j) {
-            const int i = tid + j * 256;
-            const int r = i / LWS, cc = i - r * LWS;
-            const int y = ty0 + r - HALO, x = tx0 + cc - HALO;
-            const bool ok = i < NC && y >= 0 && y < h && x >= 0 && x < w;
-            float m = clamped_sigmoid(ld[j][0]);
-#pragma unroll
-            for (int v = 1; v < V; ++v) m = m + clamped_sigmoid(ld[j][v]);
-            if (i < NC) S[r][cc + OFF - HALO] = ok ? (m + Tt[cc + OFF - HALO][r + OFF - HALO]) * inv : -INFINITY;
+        for (int j = 0; j < NLDS; ++j) {
+            const TileCell t = plain_cell_scalar(tid + j * 256, ty0, tx0, h, w);
+            const float m = plain_sum_scalar(ld[j]);
+            if (t.in) S[t.r][t.c] = t.ok ? (m + Tt[t.c][t.r + OFF - HALO]) * inv : -INFINITY;
         }
     }
     __syncthreads();
-    // row pass: Hm[r][cc] = max over map columns tx0+cc-2 .. tx0+cc+2
-    for (int i = tid; i < LH * TW; i += 256) {
-        const int r = i / TW, cc = i - r * TW;
-        const float* s = &S[r][cc + OFF - HALO];
-        Hm[r][cc] = fmaxf(fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3])), s[4]);
-    }
-    __syncthreads();
-    // column pass + output: four adjacent pixels of one row per thread
-    const int r = tid / (TW / 4), c4 = (tid - r * (TW / 4)) * 4;
-    const int y = ty0 + r, x = tx0 + c4;
-    if (y >= h) return;
-    float val[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const float m = fmaxf(fmaxf(Hm[r][c4 + k], Hm[r + 1][c4 + k]), fmaxf(Hm[r + 2][c4 + k], Hm[r + 3][c4 + k]));
-        const float mx = fmaxf(m, Hm[r + 4][c4 + k]);
-        const float v = S[r + HALO][c4 + k + OFF];
-        val[k] = (v == mx) ? v : 0.0f;
-    }
-    float* dst = out + (((int64_t)b * C + c) * h + y) * w + x;
-    if (VEC) {
-        if (x < w) *reinterpret_cast<float4*>(dst) = make_float4(val[0], val[1], val[2], val[3]);
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (x + k < w) dst[k] = val[k];
-    }
+    nms5_tile_store(S, Hm, tid, ty0, tx0, h, w, out + ((int64_t)b * C + c) * h * w, VEC);
 }
 
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-template <int V>
-static void launch_d4_views(bool vec, bool vect, dim3 grid, hipStream_t st, const float* x, float* out, float* out_t, int64_t planes, int H,
-                            int W, int tiles_x, int tiles, ViewFlips vf) {
-    const dim3 block(256);
-    if (vec && vect)  hipLaunchKernelGGL((k_d4_views<V, true, true>), grid, block, 0, st, x, out, out_t, planes, H, W, tiles_x, tiles, vf);
-    else if (vec)     hipLaunchKernelGGL((k_d4_views<V, true, false>), grid, block, 0, st, x, out, out_t, planes, H, W, tiles_x, tiles, vf);
-    else if (vect)    hipLaunchKernelGGL((k_d4_views<V, false, true>), grid, block, 0, st, x, out, out_t, planes, H, W, tiles_x, tiles, vf);
-    else              hipLaunchKernelGGL((k_d4_views<V, false, false>), grid, block, 0, st, x, out, out_t, planes, H, W, tiles_x, tiles, vf);
-}
-
-template <int V>
-static void launch_d4_merge(bool vec, bool vect, dim3 grid, hipStream_t st, const float* hm, int64_t sb, int64_t sc, const float* hm_t,
-                            int64_t sbt, int64_t sct, int B, int C, int h, int w, int tiles_x, ViewFlips vf, float* out) {
-    const dim3 block(256);
-    if (vec && vect)  hipLaunchKernelGGL((k_d4_merge_nms<V, true, true>), grid, block, 0, st, hm, sb, sc, hm_t, sbt, sct, B, C, h, w, tiles_x, vf, out);
-    else if (vec)     hipLaunchKernelGGL((k_d4_merge_nms<V, true, false>), grid, block, 0, st, hm, sb, sc, hm_t, sbt, sct, B, C, h, w, tiles_x, vf, out);
-    else if (vect)    hipLaunchKernelGGL((k_d4_merge_nms<V, false, true>), grid, block, 0, st, hm, sb, sc, hm_t, sbt, sct, B, C, h, w, tiles_x, vf, out);
-    else              hipLaunchKernelGGL((k_d4_merge_nms<V, false, false>), grid, block, 0, st, hm, sb, sc, hm_t, sbt, sct, B, C, h, w, tiles_x, vf, out);
-}
-
 static bool ranges_overlap(const float* a, const float* b, int64_t n) {
     const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b), bytes = (uintptr_t)n * sizeof(float);
     return pa < pb + bytes && pb < pa + bytes;
@@ -437,11 +346,16 @@ int sd_d4_views(const float* x, float* out, float* out_t, int B, int H, int W, i
     SD_REQUIRE(blocks < (1ll << 31), SD_ERR_INVALID, "%s: %lld blocks exceed the grid", fn, (long long)blocks);
     const bool vec = (W % 4 == 0) && aligned16(x) && aligned16(out);
     const bool vect = (H % 4 == 0) && aligned16(out_t);
-    const dim3 grid((unsigned)blocks);
+    const dim3 grid((unsigned)blocks), block(256);
     const hipStream_t st = (hipStream_t)stream;
-    if (Vf == 1)      launch_d4_views<1>(vec, vect, grid, st, x, out, out_t, planes, H, W, tiles_x, tiles, vf);
-    else if (Vf == 2) launch_d4_views<2>(vec, vect, grid, st, x, out, out_t, planes, H, W, tiles_x, tiles, vf);
-    else              launch_d4_views<4>(vec, vect, grid, st, x, out, out_t, planes, H, W, tiles_x, tiles, vf);
+    with_views<true>(Vf, [&](auto v) {
+        with_flag(vec, [&](auto vc) {
+            with_flag(vect, [&](auto vt) {
+                hipLaunchKernelGGL((k_d4_views<decltype(v)::value, decltype(vc)::value, decltype(vt)::value>), grid, block, 0, st, x, out, out_t,
+                                   planes, H, W, tiles_x, tiles, vf);
+            });
+        });
+    });
     SD_LAUNCH_CHECK();
     return 0;
 }
@@ -450,10 +364,8 @@ int sd_d4_merge_nms(const float* hm, int64_t sb, int64_t sc, const float* hm_t, 
                     int w, int Vf, const unsigned char* view_flips_host, sd_stream_t stream) {
     const char* fn = "sd_d4_merge_nms";
     SD_REQUIRE(hm != nullptr && hm_t != nullptr && out != nullptr, SD_ERR_INVALID, "%s: null pointer", fn);
-    SD_REQUIRE(B > 0 && C > 0 && h > 0 && w > 0, SD_ERR_INVALID, "%s: bad shape (%d,%d,%d,%d)", fn, B, C, h, w);
     ViewFlips vf;
-    if (int e = check_views(fn, Vf, view_flips_host, &vf, true)) return e;
-    SD_REQUIRE((int64_t)C * h * w < (1ll << 31), SD_ERR_INVALID, "%s: C*h*w must be < 2^31", fn);
+    if (int e = check_merge_args(fn, B, C, h, w, Vf, view_flips_host, &vf, true)) return e;
     SD_REQUIRE(sc >= (int64_t)h * w && sb >= (int64_t)h * w, SD_ERR_INVALID, "%s: bad strides sb=%lld sc=%lld", fn, (long long)sb, (long long)sc);
     SD_REQUIRE(sc_t >= (int64_t)h * w && sb_t >= (int64_t)h * w, SD_ERR_INVALID, "%s: bad strides sb_t=%lld sc_t=%lld", fn, (long long)sb_t,
                (long long)sc_t);
@@ -461,11 +373,16 @@ int sd_d4_merge_nms(const float* hm, int64_t sb, int64_t sc, const float* hm_t, 
     const int tiles_x = cdiv(w, TW), tiles_y = cdiv(h, TH);
     const bool vec = (w % 4 == 0) && aligned16(hm) && aligned16(out) && sb % 4 == 0 && sc % 4 == 0;
     const bool vect = (h % 4 == 0) && aligned16(hm_t) && sb_t % 4 == 0 && sc_t % 4 == 0;
-    const dim3 grid(tiles_x * tiles_y, C, B);
+    const dim3 grid(tiles_x * tiles_y, C, B), block(256);
     const hipStream_t st = (hipStream_t)stream;
-    if (Vf == 1)      launch_d4_merge<1>(vec, vect, grid, st, hm, sb, sc, hm_t, sb_t, sc_t, B, C, h, w, tiles_x, vf, out);
-    else if (Vf == 2) launch_d4_merge<2>(vec, vect, grid, st, hm, sb, sc, hm_t, sb_t, sc_t, B, C, h, w, tiles_x, vf, out);
-    else              launch_d4_merge<4>(vec, vect, grid, st, hm, sb, sc, hm_t, sb_t, sc_t, B, C, h, w, tiles_x, vf, out);
+    with_views<true>(Vf, [&](auto v) {
+        with_flag(vec, [&](auto vc) {
+            with_flag(vect, [&](auto vt) {
+                hipLaunchKernelGGL((k_d4_merge_nms<decltype(v)::value, decltype(vc)::value, decltype(vt)::value>), grid, block, 0, st, hm, sb, sc,
+                                   hm_t, sb_t, sc_t, B, C, h, w, tiles_x, vf, out);
+            });
+        });
+    });
     SD_LAUNCH_CHECK();
     return 0;
 }

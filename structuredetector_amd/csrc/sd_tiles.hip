@@ -4,7 +4,7 @@
 // decides which cells survive the NMS and is compared bit for bit with the library's own primitives (sd_clamped_sigmoid, sd_nms5):
 // separately rounded multiplies and adds, ramp weights in double -- floating-point contraction is OFF in this file.
 #pragma clang fp contract(off)
-#include "sd_common.h"
+#include "sd_views.h"
 
 namespace sd {
 
@@ -43,14 +43,10 @@ __global__ __launch_bounds__(256) void k_tile_views(const float* __restrict__ ca
 //        group of four canvas columns is an aligned group of every tile that covers it, entirely inside or entirely outside an overlap.
 //        The staged span of a row is [tx0-4, tx0+68): 18 groups, each <= 4 16-byte loads (contiguous spans of the source tiles' rows).
 //   else: <= 4 4-byte loads per staged cell, [tx0-2, tx0+66).
-// LDS column of canvas column x: x - tx0 + OFF (OFF = 4) in both variants; LDS row of canvas row y: y - ty0 + HALO.
+// LDS column of canvas column x: x - tx0 + OFF (OFF = 4) in both variants; LDS row of canvas row y: y - ty0 + HALO (the tile constants
+// and the NMS tail: sd_views.h).
 // Blocks with blockIdx.y >= C copy regression plane blockIdx.y - C of the same canvas tile from the owner tiles, unstaged.
 // ---------------------------------------------------------------------------------------------
-constexpr int TW = 64, TH = 16, HALO = 2, OFF = 4;
-constexpr int LH = TH + 2 * HALO;        // 20 staged rows
-constexpr int LWV = TW + 2 * OFF;        // 72 table / staged columns
-constexpr int LWS = TW + 2 * HALO;       // 68 cells per row loaded by the scalar variant
-
 struct AxisEntry {
     int hi;          // the upper covering tile (-1: the cell is outside the canvas)
     int l;           // local coordinate in tile `hi`; tile hi-1 covers the cell at l + (n - o) when `two`
@@ -206,33 +202,7 @@ __global__ __launch_bounds__(256) void k_tile_merge_nms(const float* __restrict_
         }
     }
     __syncthreads();
-    // row pass: Hm[r][cc] = max over canvas columns tx0+cc-2 .. tx0+cc+2
-    for (int i = tid; i < LH * TW; i += 256) {
-        const int r = i / TW, cc = i - r * TW;
-        const float* s = &S[r][cc + OFF - HALO];
-        Hm[r][cc] = fmaxf(fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3])), s[4]);
-    }
-    __syncthreads();
-    // column pass + output: four adjacent cells of one row per thread
-    const int r = tid / (TW / 4), c4 = (tid - r * (TW / 4)) * 4;
-    const int y = ty0 + r, x = tx0 + c4;
-    if (y >= hc) return;
-    float val[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const float m = fmaxf(fmaxf(Hm[r][c4 + k], Hm[r + 1][c4 + k]), fmaxf(Hm[r + 2][c4 + k], Hm[r + 3][c4 + k]));
-        const float mx = fmaxf(m, Hm[r + 4][c4 + k]);
-        const float v = S[r + HALO][c4 + k + OFF];
-        val[k] = (v == mx) ? v : 0.0f;
-    }
-    float* dst = out_hm + (((int64_t)b * C + c) * hc + y) * wc + x;
-    if (VEC) {
-        if (x < wc) *reinterpret_cast<float4*>(dst) = make_float4(val[0], val[1], val[2], val[3]);
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (x + k < wc) dst[k] = val[k];
-    }
+    nms5_tile_store(S, Hm, tid, ty0, tx0, hc, wc, out_hm + ((int64_t)b * C + c) * hc * wc, VEC);
 }
 
 // the geometry both entry points share: T tiles of n with overlap o along an axis
@@ -289,12 +259,10 @@ int sd_tile_merge_nms(const float* hm, int64_t sb, int64_t sc, int C, const floa
     const int reg_vec = R > 0 && wc % 4 == 0 && aligned16(out_reg);
     const dim3 grid(blocks_x * blocks_y, C + R, B), block(256);
     const hipStream_t st = (hipStream_t)stream;
-    if (vec)
-        hipLaunchKernelGGL((k_tile_merge_nms<true>), grid, block, 0, st, hm, sb, sc, C, reg, r_sb, r_sc, out_hm, out_reg, B, h, w, Ty, Tx, o,
-                           (int)hc, (int)wc, blocks_x, reg_vec);
-    else
-        hipLaunchKernelGGL((k_tile_merge_nms<false>), grid, block, 0, st, hm, sb, sc, C, reg, r_sb, r_sc, out_hm, out_reg, B, h, w, Ty, Tx, o,
-                           (int)hc, (int)wc, blocks_x, reg_vec);
+    with_flag(vec, [&](auto vc) {
+        hipLaunchKernelGGL((k_tile_merge_nms<decltype(vc)::value>), grid, block, 0, st, hm, sb, sc, C, reg, r_sb, r_sc, out_hm, out_reg, B, h, w,
+                           Ty, Tx, o, (int)hc, (int)wc, blocks_x, reg_vec);
+    });
     SD_LAUNCH_CHECK();
     return 0;
 }

@@ -33,7 +33,7 @@ __global__ __launch_bounds__(256) void k_tta_views(const float* __restrict__ x, 
             const int dy = (vf.f[k] & 2) ? H - 1 - y : y;
             const int dg = hf ? wg - 1 - g : g;
             reinterpret_cast<float4*>(out)[(((int64_t)k * planes + plane) * H + dy) * wg + dg] =
-                make_float4(hf ? v.w : v.x, hf ? v.z : v.y, hf ? v.y : v.z, hf ? v.x : v.w);
+                hf ? reversed(v) : v;
         }
     } else {
         const float v = x[i];
@@ -50,12 +50,9 @@ __global__ __launch_bounds__(256) void k_tta_views(const float* __restrict__ x, 
 // Merge + NMS.  One 256-thread block per 64x16 output tile of one merged map (the tile of sd_nms5).  The tile and its 2-pixel halo are
 // staged in LDS as m = (s_0 + s_1 [+ s_2 + s_3]) * (1/V), s_v = clamped_sigmoid(view v's logit at the mirrored coordinate); the 5-max
 // is separable (row pass into a second LDS array, column pass in registers); out = (m == max5x5(m)) ? m : 0 with -inf padding.
-// Every view's logits are read once (+ the halo re-reads, served by L2), the output is written once.
-//   VEC: w % 4 == 0 and 16-byte aligned planes.  The staged span of a row is widened to the enclosing aligned groups
-//        [tx0-4, tx0+68): 18 16-byte loads per row and view; a mirrored view reads the group w-4-x and swaps its components,
-//        so its span is contiguous as well.  A group lies entirely inside or entirely outside the map.
-//   else: one 4-byte load per staged cell, [tx0-2, tx0+66).
-// LDS column of map column x: x - tx0 + OFF (OFF = 4) in both variants (the tile constants: sd_views.h).
+// Every view's logits are read once (+ the halo re-reads, served by L2), the output is written once.  The tile constants, the staging
+// (plain_load_* / plain_sum_*; VEC: 16-byte loads, w % 4 == 0 and 16-byte aligned planes) and the NMS tail (nms5_tile_store) are
+// sd_views.h's, shared with k_d4_merge_nms and k_tile_merge_nms.
 // ---------------------------------------------------------------------------------------------
 
 template <int V, bool VEC>
@@ -74,100 +71,28 @@ __global__ __launch_bounds__(256) void k_tta_merge_nms(const float* __restrict__
 
     // all loads of the thread are issued before the first use; cells outside the map read element 0 and become -inf
     if (VEC) {
-        constexpr int GR = LWV / 4, NG = LH * GR;                      // 18 groups per row, 360 per tile
-        constexpr int NLD = (NG + 255) / 256;
-        float4 ld[NLD][V];
+        float4 ld[NLDV][V];
+        plain_load_vec(ld, plane, vf, tid, ty0, tx0, h, w);
 #pragma unroll
-        for (int j = 0; j < NLD; ++j) {
-            const int i = tid + j * 256;
-            const int r = i / GR, q = i - r * GR;
-            const int y = ty0 + r - HALO, x = tx0 - OFF + 4 * q;
-            const bool ok = i < NG && y >= 0 && y < h && x >= 0 && x < w;
-#pragma unroll
-            for (int v = 0; v < V; ++v) {
-                const int sy = (vf.f[v] & 2) ? h - 1 - y : y;
-                const int sx = (vf.f[v] & 1) ? w - 4 - x : x;
-                ld[j][v] = *reinterpret_cast<const float4*>(plane[v] + (ok ? (int64_t)sy * w + sx : 0));
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < NLD; ++j) {
-            const int i = tid + j * 256;
-            const int r = i / GR, q = i - r * GR;
-            const int y = ty0 + r - HALO, x = tx0 - OFF + 4 * q;
-            const bool ok = y >= 0 && y < h && x >= 0 && x < w;
-            float4 m;
-#pragma unroll
-            for (int v = 0; v < V; ++v) {
-                const float4 t = ld[j][v];
-                const bool hf = vf.f[v] & 1;
-                const float4 s = make_float4(clamped_sigmoid(hf ? t.w : t.x), clamped_sigmoid(hf ? t.z : t.y),
-                                             clamped_sigmoid(hf ? t.y : t.z), clamped_sigmoid(hf ? t.x : t.w));
-                if (v == 0) m = s;
-                else { m.x = m.x + s.x; m.y = m.y + s.y; m.z = m.z + s.z; m.w = m.w + s.w; }
-            }
+        for (int j = 0; j < NLDV; ++j) {
+            const TileCell t = plain_cell_vec(tid + j * 256, ty0, tx0, h, w);
+            float4 m = plain_sum_vec(ld[j], vf);
             m.x = m.x * inv; m.y = m.y * inv; m.z = m.z * inv; m.w = m.w * inv;
-            if (!ok) m = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-            if (i < NG) *reinterpret_cast<float4*>(&S[r][4 * q]) = m;
+            if (!t.ok) m = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+            if (t.in) *reinterpret_cast<float4*>(&S[t.r][t.c]) = m;
         }
     } else {
-        constexpr int NC = LH * LWS;
-        constexpr int NLD = (NC + 255) / 256;
-        float ld[NLD][V];
+        float ld[NLDS][V];
+        plain_load_scalar(ld, plane, vf, tid, ty0, tx0, h, w);
 #pragma unroll
-        for (int j = 0; j < NLD; ++j) {
-            const int i = tid + j * 256;
-            const int r = i / LWS, cc = i - r * LWS;
-            const int y = ty0 + r - HALO, x = tx0 + cc - HALO;
-            const bool ok = i < NC && y >= 0 && y < h && x >= 0 && x < w;
-#pragma unroll
-            for (int v = 0; v < V; ++v) {
-                const int sy = (vf.f[v] & 2) ? h - 1 - y : y;
-                const int sx = (vf.f[v] & 1) ? w - 1 - x : x;
-                ld[j][v] = plane[v][ok ? (int64_t)sy * w + sx : 0];
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < NLD; ++j) {
-            const int i = tid + j * 256;
-            const int r = i / LWS, cc = i - r * LWS;
-            const int y = ty0 + r - HALO, x = tx0 + cc - HALO;
-            const bool ok = y >= 0 && y < h && x >= 0 && x < w;
-            float m = clamped_sigmoid(ld[j][0]);
-#pragma unroll
-            for (int v = 1; v < V; ++v) m = m + clamped_sigmoid(ld[j][v]);
-            m = m * inv;
-            if (i < NC) S[r][cc + OFF - HALO] = ok ? m : -INFINITY;
+        for (int j = 0; j < NLDS; ++j) {
+            const TileCell t = plain_cell_scalar(tid + j * 256, ty0, tx0, h, w);
+            const float m = plain_sum_scalar(ld[j]) * inv;
+            if (t.in) S[t.r][t.c] = t.ok ? m : -INFINITY;
         }
     }
     __syncthreads();
-    // row pass: Hm[r][cc] = max over map columns tx0+cc-2 .. tx0+cc+2
-    for (int i = tid; i < LH * TW; i += 256) {
-        const int r = i / TW, cc = i - r * TW;
-        const float* s = &S[r][cc + OFF - HALO];
-        Hm[r][cc] = fmaxf(fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3])), s[4]);
-    }
-    __syncthreads();
-    // column pass + output: four adjacent pixels of one row per thread
-    const int r = tid / (TW / 4), c4 = (tid - r * (TW / 4)) * 4;
-    const int y = ty0 + r, x = tx0 + c4;
-    if (y >= h) return;
-    float mx[4], val[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const float m = fmaxf(fmaxf(Hm[r][c4 + k], Hm[r + 1][c4 + k]), fmaxf(Hm[r + 2][c4 + k], Hm[r + 3][c4 + k]));
-        mx[k] = fmaxf(m, Hm[r + 4][c4 + k]);
-        const float v = S[r + HALO][c4 + k + OFF];
-        val[k] = (v == mx[k]) ? v : 0.0f;
-    }
-    float* dst = out + (((int64_t)b * C + c) * h + y) * w + x;
-    if (VEC) {
-        if (x < w) *reinterpret_cast<float4*>(dst) = make_float4(val[0], val[1], val[2], val[3]);
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (x + k < w) dst[k] = val[k];
-    }
+    nms5_tile_store(S, Hm, tid, ty0, tx0, h, w, out + ((int64_t)b * C + c) * h * w, VEC);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -289,41 +214,20 @@ __global__ __launch_bounds__(256) void k_tta_scale_merge_nms(ScaleArgs sa, int S
         if (i < NC) Sm[r][cc + OFF - HALO] = (y >= 0 && y < h && x >= 0 && x < w) ? acc[j] * inv : -INFINITY;
     }
     __syncthreads();
-    for (int i = tid; i < LH * TW; i += 256) {
-        const int r = i / TW, cc = i - r * TW;
-        const float* p = &Sm[r][cc + OFF - HALO];
-        Hm[r][cc] = fmaxf(fmaxf(fmaxf(p[0], p[1]), fmaxf(p[2], p[3])), p[4]);
-    }
-    __syncthreads();
-    const int r = tid / (TW / 4), c4 = (tid - r * (TW / 4)) * 4;
-    const int y = ty0 + r, x = tx0 + c4;
-    if (y >= h) return;
-    float val[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const float m = fmaxf(fmaxf(Hm[r][c4 + k], Hm[r + 1][c4 + k]), fmaxf(Hm[r + 2][c4 + k], Hm[r + 3][c4 + k]));
-        const float mx = fmaxf(m, Hm[r + 4][c4 + k]);
-        const float v = Sm[r + HALO][c4 + k + OFF];
-        val[k] = (v == mx) ? v : 0.0f;
-    }
-    float* dst = out + (((int64_t)b * C + c) * h + y) * w + x;
-    if (out_vec) {
-        if (x < w) *reinterpret_cast<float4*>(dst) = make_float4(val[0], val[1], val[2], val[3]);
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (x + k < w) dst[k] = val[k];
-    }
+    nms5_tile_store(Sm, Hm, tid, ty0, tx0, h, w, out + ((int64_t)b * C + c) * h * w, out_vec != 0);
 }
 
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-template <int V>
-static void launch_merge_nms(bool vec, dim3 grid, hipStream_t st, const float* hm, int64_t sb, int64_t sc, int B, int C, int h, int w,
+static void launch_merge_nms(int V, bool vec, dim3 grid, hipStream_t st, const float* hm, int64_t sb, int64_t sc, int B, int C, int h, int w,
                              int tiles_x, ViewFlips vf, float* out) {
-    if (vec) hipLaunchKernelGGL((k_tta_merge_nms<V, true>), grid, dim3(256), 0, st, hm, sb, sc, B, C, h, w, tiles_x, vf, out);
-    else     hipLaunchKernelGGL((k_tta_merge_nms<V, false>), grid, dim3(256), 0, st, hm, sb, sc, B, C, h, w, tiles_x, vf, out);
+    with_views<true>(V, [&](auto v) {
+        with_flag(vec, [&](auto vc) {
+            hipLaunchKernelGGL((k_tta_merge_nms<decltype(v)::value, decltype(vc)::value>), grid, dim3(256), 0, st, hm, sb, sc, B, C, h, w,
+                               tiles_x, vf, out);
+        });
+    });
 }
 
 }  // namespace sd
@@ -343,33 +247,28 @@ int sd_tta_views(const float* x, float* out, int B, int H, int W, int V, const u
     SD_REQUIRE(blocks < (1ll << 31), SD_ERR_INVALID, "sd_tta_views: %lld blocks exceed the grid", (long long)blocks);
     const dim3 grid((unsigned)blocks), block(256);
     const hipStream_t st = (hipStream_t)stream;
-    if (V == 2) {
-        if (vec) hipLaunchKernelGGL((k_tta_views<2, true>), grid, block, 0, st, x, out, planes, H, W, vf);
-        else     hipLaunchKernelGGL((k_tta_views<2, false>), grid, block, 0, st, x, out, planes, H, W, vf);
-    } else {
-        if (vec) hipLaunchKernelGGL((k_tta_views<4, true>), grid, block, 0, st, x, out, planes, H, W, vf);
-        else     hipLaunchKernelGGL((k_tta_views<4, false>), grid, block, 0, st, x, out, planes, H, W, vf);
-    }
+    with_views<false>(V, [&](auto v) {
+        with_flag(vec, [&](auto vc) {
+            hipLaunchKernelGGL((k_tta_views<decltype(v)::value, decltype(vc)::value>), grid, block, 0, st, x, out, planes, H, W, vf);
+        });
+    });
     SD_LAUNCH_CHECK();
     return 0;
 }
 
 int sd_tta_merge_nms(const float* hm, int64_t sb, int64_t sc, float* out, int B, int C, int h, int w, int V,
                      const unsigned char* view_flips, sd_stream_t stream) {
-    SD_REQUIRE(hm != nullptr && out != nullptr, SD_ERR_INVALID, "sd_tta_merge_nms: null pointer");
-    SD_REQUIRE(B > 0 && C > 0 && h > 0 && w > 0, SD_ERR_INVALID, "sd_tta_merge_nms: bad shape (%d,%d,%d,%d)", B, C, h, w);
+    const char* fn = "sd_tta_merge_nms";
+    SD_REQUIRE(hm != nullptr && out != nullptr, SD_ERR_INVALID, "%s: null pointer", fn);
     ViewFlips vf;
-    if (int e = check_views("sd_tta_merge_nms", V, view_flips, &vf)) return e;
-    SD_REQUIRE((int64_t)C * h * w < (1ll << 31), SD_ERR_INVALID, "sd_tta_merge_nms: C*h*w must be < 2^31");
-    SD_REQUIRE(sc >= (int64_t)h * w && sb >= (int64_t)h * w, SD_ERR_INVALID, "sd_tta_merge_nms: bad strides sb=%lld sc=%lld",
-               (long long)sb, (long long)sc);
-    SD_REQUIRE(C <= 65535 && B <= 65535, SD_ERR_INVALID, "sd_tta_merge_nms: B=%d, C=%d exceed the grid (65535)", B, C);
+    if (int e = check_merge_args(fn, B, C, h, w, V, view_flips, &vf, false)) return e;
+    SD_REQUIRE(sc >= (int64_t)h * w && sb >= (int64_t)h * w, SD_ERR_INVALID, "%s: bad strides sb=%lld sc=%lld", fn, (long long)sb, (long long)sc);
+    SD_REQUIRE(C <= 65535 && B <= 65535, SD_ERR_INVALID, "%s: B=%d, C=%d exceed the grid (65535)", fn, B, C);
     const int tiles_x = cdiv(w, TW), tiles_y = cdiv(h, TH);
     const bool vec = (w % 4 == 0) && aligned16(hm) && aligned16(out) && sb % 4 == 0 && sc % 4 == 0;
     const dim3 grid(tiles_x * tiles_y, C, B);
     const hipStream_t st = (hipStream_t)stream;
-    if (V == 2) launch_merge_nms<2>(vec, grid, st, hm, sb, sc, B, C, h, w, tiles_x, vf, out);
-    else        launch_merge_nms<4>(vec, grid, st, hm, sb, sc, B, C, h, w, tiles_x, vf, out);
+    launch_merge_nms(V, vec, grid, st, hm, sb, sc, B, C, h, w, tiles_x, vf, out);
     SD_LAUNCH_CHECK();
     return 0;
 }
@@ -381,10 +280,8 @@ int sd_tta_scale_merge_nms(const float* const* hm_host, const int64_t* sb_host, 
     SD_REQUIRE(hm_host != nullptr && sb_host != nullptr && sc_host != nullptr && hs_host != nullptr && ws_host != nullptr && out != nullptr,
                SD_ERR_INVALID, "%s: null pointer", fn);
     SD_REQUIRE(S >= 1 && S <= MAX_SCALES, SD_ERR_INVALID, "%s: S=%d scales (1 .. %d are supported)", fn, S, MAX_SCALES);
-    SD_REQUIRE(B > 0 && C > 0 && h > 0 && w > 0, SD_ERR_INVALID, "%s: bad shape (%d,%d,%d,%d)", fn, B, C, h, w);
     ViewFlips vf;
-    if (int e = check_views(fn, V, view_flips_host, &vf, true)) return e;
-    SD_REQUIRE((int64_t)C * h * w < (1ll << 31), SD_ERR_INVALID, "%s: C*h*w must be < 2^31", fn);
+    if (int e = check_merge_args(fn, B, C, h, w, V, view_flips_host, &vf, true)) return e;
     SD_REQUIRE(C <= 65535 && B <= 65535, SD_ERR_INVALID, "%s: B=%d, C=%d exceed the grid (65535)", fn, B, C);
     ScaleArgs sa{};
     for (int s = 0; s < S; ++s) {
@@ -411,17 +308,14 @@ int sd_tta_scale_merge_nms(const float* const* hm_host, const int64_t* sb_host, 
     const hipStream_t st = (hipStream_t)stream;
     if (S == 1 && sa.hs[0] == h && sa.ws[0] == w) {
         // nothing to resample (x0 = x, weights 1 and 0: the same values): the flip merge's kernel, whose sum stays in registers
-        const bool vec = out_vec && sa.vec[0];
-        if (V == 1)      launch_merge_nms<1>(vec, grid, st, sa.hm[0], sa.sb[0], sa.sc[0], B, C, h, w, tiles_x, vf, out);
-        else if (V == 2) launch_merge_nms<2>(vec, grid, st, sa.hm[0], sa.sb[0], sa.sc[0], B, C, h, w, tiles_x, vf, out);
-        else             launch_merge_nms<4>(vec, grid, st, sa.hm[0], sa.sb[0], sa.sc[0], B, C, h, w, tiles_x, vf, out);
+        launch_merge_nms(V, out_vec && sa.vec[0], grid, st, sa.hm[0], sa.sb[0], sa.sc[0], B, C, h, w, tiles_x, vf, out);
         SD_LAUNCH_CHECK();
         return 0;
     }
     const float inv = (float)(1.0 / (double)(S * V));
-    if (V == 1)      hipLaunchKernelGGL((k_tta_scale_merge_nms<1>), grid, block, 0, st, sa, S, inv, B, C, h, w, tiles_x, vf, (int)out_vec, out);
-    else if (V == 2) hipLaunchKernelGGL((k_tta_scale_merge_nms<2>), grid, block, 0, st, sa, S, inv, B, C, h, w, tiles_x, vf, (int)out_vec, out);
-    else             hipLaunchKernelGGL((k_tta_scale_merge_nms<4>), grid, block, 0, st, sa, S, inv, B, C, h, w, tiles_x, vf, (int)out_vec, out);
+    with_views<true>(V, [&](auto v) {
+        hipLaunchKernelGGL((k_tta_scale_merge_nms<decltype(v)::value>), grid, block, 0, st, sa, S, inv, B, C, h, w, tiles_x, vf, (int)out_vec, out);
+    });
     SD_LAUNCH_CHECK();
     return 0;
 }

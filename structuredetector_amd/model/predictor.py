@@ -22,6 +22,12 @@ def index_batches(n, batch, lo=0):
     return [list(range(i, min(i + batch, n))) for i in range(lo, n, batch)]
 
 
+def call_net(net, images, at_size):
+    """`net(images)`; a wrapper that `needs_sources` (model/tta.py ScaleTta, model/tiles.py TiledNet: their other sizes are resampled from
+    the source images) also gets `at_size`, a callable (width, height) -> the same images preprocessed at that size."""
+    return net(images, at_size=at_size) if getattr(net, "needs_sources", False) else net(images)
+
+
 def batched_decodes(net, decoder, dataset, args, batch=None, workers=None, with_raw_parts=True, depth=2, cache=None, index_range=None,
                     pr_curve=None):
     """dataset: `CropDataset(args, dir, raw=True)` or `PredictionDataset(dir, args, raw=True)` -- items ((H, W, 3) uint8 tensor,
@@ -55,10 +61,7 @@ def batched_decodes(net, decoder, dataset, args, batch=None, workers=None, with_
         for group in BatchFeeder(dataset, index_batches(hi, batch, lo), args.device, workers=workers, depth=depth, cache=cache):
             with torch.no_grad():
                 images, anns = prepare(group, group.annotations)
-                if getattr(net, "needs_sources", False):           # model/tta.py ScaleTta: its other sizes are resampled from the source images
-                    out = net(images, at_size=lambda size: prepare.images_at(group, size))
-                else:
-                    out = net(images)
+                out = call_net(net, images, lambda size: prepare.images_at(group, size))
                 if isinstance(out, torch.Tensor):  # Network(raw_output=True)
                     out = split_head(net, out)
                 handle = decoder.submit(out, with_raw_parts=with_raw_parts)
@@ -117,6 +120,4 @@ class Predictor(torch.nn.Module):
         arr = torch.from_numpy(np.asarray(image.convert("RGB"), np.uint8).copy())[None].to(self.args.device)
         with torch.no_grad():
             x = preprocess_images(arr, (self.args.width, self.args.height))
-            if getattr(self.tta, "needs_sources", False):
-                return self.decoder(self.tta(x, at_size=lambda size: preprocess_images(arr, size)))[0]
-            return self.decoder((self.tta or self.model)(x))[0]
+            return self.decoder(call_net(self.tta or self.model, x, lambda size: preprocess_images(arr, size)))[0]

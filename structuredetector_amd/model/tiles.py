@@ -25,7 +25,7 @@ import torch
 from .. import _lib as L
 from ..data.decoders import TiledOutputDecoder, TtaOutput
 from ..utils.args import MAX_TILES, check_tile_overlap, tile_canvas
-from .tta import head_parts
+from .tta import _ViewNet
 
 CHUNK = 64                          # images per forward of the tile batch, when the batch itself is not larger
 
@@ -90,7 +90,7 @@ def _regressions(offsets, embeddings):
     return torch.cat([o, e], 1)
 
 
-class TiledNet:
+class TiledNet(_ViewNet):
     """`net` behind tiled inference: `TiledNet(net, args, grid, overlap)(images, at_size=f)` -- `images` the batch at the network input
     size (it only supplies B), `f((width, height))` the same source images resized + normalised to another size -- returns a `TtaOutput`
     whose four maps are on the canvas grid.  grid = (Tx, Ty), overlap in pixels.  `needs_sources` tells the callers to pass `at_size`.
@@ -106,10 +106,9 @@ class TiledNet:
         except ValueError as e:
             raise L.SdError(str(e)) from None
         self.overlap_cells = int(self.overlap // args.down_ratio)
-        self.net, self.args = net, args
+        super().__init__(net, args)
         self.size = (W, H)
         self.canvas = tile_canvas(W, H, self.grid, self.overlap)
-        self.label_count, self.part_count = len(args.labels), len(args.parts)
 
     def __call__(self, images, at_size=None):
         if at_size is None:
@@ -121,22 +120,23 @@ class TiledNet:
         if tuple(canvas.shape) != (B, 3, Hc, Wc):
             raise L.SdError(f"TiledNet: at_size({(Wc, Hc)}) returned {tuple(canvas.shape)}, expected {(B, 3, Hc, Wc)}")
         tiles = tile_views(canvas, self.grid, self.overlap)
-        M, nb = self.label_count, self.label_count + self.part_count
         chunk = max(B, CHUNK)
-        parts = [head_parts(self.net(tiles[i:i + chunk]), M, nb) for i in range(0, tiles.shape[0], chunk)]
+        parts = [self.head_parts(tiles[i:i + chunk]) for i in range(0, tiles.shape[0], chunk)]
         if len(parts) == 1:
             heat, offsets, embeddings = parts[0]
             reg = _regressions(offsets, embeddings)
         else:                                                          # head tensors are small: the chunks are concatenated
             heat = [torch.cat([torch.cat(p[0], 1) for p in parts])]
             reg = torch.cat([torch.cat([p[1], p[2]], 1) for p in parts])
-        if len(heat) == 1:                                             # adjacent slices of one head tensor: one launch
-            merged, reg_out = tile_merge_nms(heat[0], reg, self.grid, self.overlap_cells)
-            anchor_hm, part_hm = merged[:, :M], merged[:, M:]
-        else:
-            anchor_hm, reg_out = tile_merge_nms(heat[0], reg, self.grid, self.overlap_cells)
-            part_hm, _ = tile_merge_nms(heat[1], None, self.grid, self.overlap_cells)
-        return TtaOutput(anchor_hm=anchor_hm, part_hm=part_hm, offsets=reg_out[:, :2], embeddings=reg_out[:, 2:4])
+        reg_out = []
+
+        def merge(hms):                                                # the regressions ride with the first launch
+            hm, r = tile_merge_nms(hms[0], None if reg_out else reg, self.grid, self.overlap_cells)
+            reg_out.append(r)
+            return hm
+
+        anchor_hm, part_hm = self.merged([heat], merge)
+        return TtaOutput(anchor_hm=anchor_hm, part_hm=part_hm, offsets=reg_out[0][:, :2], embeddings=reg_out[0][:, 2:4])
 
 
 def tiled_decoder(args, grid, overlap) -> TiledOutputDecoder:

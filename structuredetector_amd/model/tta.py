@@ -159,7 +159,36 @@ def head_parts(out, M, nb):
     return [a, p], out["offsets"], out["embeddings"]
 
 
-class ScaleTta:
+class _ViewNet:
+    """What the wrappers around `net` share (`FlipTta`, `ScaleTta`, `TransposeTta`, `TiledNet` in model/tiles.py): the mode check, the flips
+    of the views, the label / part counts, and the step from the forwards' heatmaps to the two merged maps."""
+
+    modes = MODES                   # the modes the wrapper takes
+
+    def __init__(self, net, args, mode="none"):
+        if mode not in self.modes:
+            raise L.SdError(f"unknown test-time augmentation mode {mode!r} (one of {', '.join(self.modes)})")
+        self.net, self.args, self.mode = net, args, mode
+        self.flips = VIEW_FLIPS.get(mode, (0,))
+        self.label_count, self.part_count = len(args.labels), len(args.parts)
+
+    def head_parts(self, x):
+        """`head_parts` of the forward over `x`."""
+        return head_parts(self.net(x), self.label_count, self.label_count + self.part_count)
+
+    def merged(self, heat, merge):
+        """heat: per forward (or per half of one), the heatmap list of `head_parts`; merge([one tensor of each]) -> the merged map.
+        Returns (anchor_hm, part_hm): ONE launch over the M + N channels when every entry is one tensor (adjacent slices of a head
+        tensor), else two, anchors first, entries that are one tensor split into their channel-slice views."""
+        M = self.label_count
+        if all(len(hm) == 1 for hm in heat):
+            out = merge([hm[0] for hm in heat])
+            return out[:, :M], out[:, M:]
+        heat = [hm if len(hm) == 2 else [hm[0][:, :M], hm[0][:, M:]] for hm in heat]
+        return merge([hm[0] for hm in heat]), merge([hm[1] for hm in heat])
+
+
+class ScaleTta(_ViewNet):
     """`net` behind the multi-scale test, combined with the flip views of `mode` ("none": one view):
     `ScaleTta(net, args, sizes, mode)(images, at_size=f)` -- `images` the batch at the base size `sizes[0]`, `f((width, height))` the same
     source images resized + normalised to another size -- returns a `TtaOutput` like `FlipTta`: S forwards of V*B images, one merge
@@ -168,14 +197,11 @@ class ScaleTta:
     needs_sources = True
 
     def __init__(self, net, args, sizes, mode="none"):
-        if mode != "none" and mode not in VIEW_FLIPS:
-            raise L.SdError(f"unknown test-time augmentation mode {mode!r} (one of {', '.join(MODES)})")
+        super().__init__(net, args, mode)
         sizes = [tuple(int(v) for v in s) for s in sizes]
         if not 1 <= len(sizes) <= MAX_SCALES or len(set(sizes)) != len(sizes) or any(v < 32 or v % 32 for s in sizes for v in s):
             raise L.SdError(f"ScaleTta: 1 to {MAX_SCALES} distinct (width, height) sizes, multiples of 32, base first; got {sizes}")
-        self.net, self.args, self.sizes, self.mode = net, args, sizes, mode
-        self.flips = VIEW_FLIPS.get(mode, (0,))
-        self.label_count, self.part_count = len(args.labels), len(args.parts)
+        self.sizes = sizes
 
     def __call__(self, images, at_size=None):
         if at_size is None and len(self.sizes) > 1:
@@ -185,80 +211,53 @@ class ScaleTta:
         W0, H0 = self.sizes[0]
         if tuple(images.shape[2:]) != (H0, W0):
             raise L.SdError(f"ScaleTta: the batch is {images.shape[3]} x {images.shape[2]}, the base size {W0} x {H0}")
-        M, nb = self.label_count, self.label_count + self.part_count
         heat, offsets, embeddings = [], None, None
         for i, size in enumerate(self.sizes):
             x = images if i == 0 else at_size(size)
             if tuple(x.shape) != (B, 3, size[1], size[0]):
                 raise L.SdError(f"ScaleTta: at_size({size}) returned {tuple(x.shape)}, expected {(B, 3, size[1], size[0])}")
-            hm, off, emb = head_parts(self.net(tta_views(x, self.flips) if len(self.flips) > 1 else x), M, nb)
+            hm, off, emb = self.head_parts(tta_views(x, self.flips) if len(self.flips) > 1 else x)
             heat.append(hm)
             if i == 0:
                 offsets, embeddings = off[:B], emb[:B]
         base_hw = tuple(heat[0][0].shape[2:])
-        if all(len(hm) == 1 for hm in heat):
-            merged = tta_scale_merge_nms([hm[0] for hm in heat], self.flips, base_hw)
-            anchor_hm, part_hm = merged[:, :M], merged[:, M:]
-        else:
-            heat = [hm if len(hm) == 2 else [hm[0][:, :M], hm[0][:, M:]] for hm in heat]
-            anchor_hm, part_hm = (tta_scale_merge_nms([hm[k] for hm in heat], self.flips, base_hw) for k in (0, 1))
+        anchor_hm, part_hm = self.merged(heat, lambda hms: tta_scale_merge_nms(hms, self.flips, base_hw))
         return TtaOutput(anchor_hm=anchor_hm, part_hm=part_hm, offsets=offsets, embeddings=embeddings)
 
 
-class FlipTta:
+class FlipTta(_ViewNet):
     """`net` behind flip test-time augmentation: `FlipTta(net, args, mode)(images)` returns the usual four-key output (a `TtaOutput`):
     `anchor_hm` / `part_hm` are the merged, suppressed PROBABILITY maps, `offsets` / `embeddings` view 0's (no copy).  Decode it with
     `tta_decoder(args)`."""
 
+    modes = tuple(VIEW_FLIPS)
+
     def __init__(self, net, args, mode):
-        if mode not in VIEW_FLIPS:
-            raise L.SdError(f"unknown test-time augmentation mode {mode!r} (one of {', '.join(VIEW_FLIPS)})")
-        self.net, self.args, self.mode = net, args, mode
-        self.flips = VIEW_FLIPS[mode]
-        self.label_count, self.part_count = len(args.labels), len(args.parts)
+        super().__init__(net, args, mode)
 
     def __call__(self, images):
         B = images.shape[0]
-        M, nb = self.label_count, self.label_count + self.part_count
-        heat, offsets, embeddings = head_parts(self.net(tta_views(images, self.flips)), M, nb)
-        if len(heat) == 1:                                             # adjacent slices of one head tensor: one launch
-            merged = tta_merge_nms(heat[0], self.flips)
-            anchor_hm, part_hm = merged[:, :M], merged[:, M:]
-        else:
-            anchor_hm, part_hm = tta_merge_nms(heat[0], self.flips), tta_merge_nms(heat[1], self.flips)
+        heat, offsets, embeddings = self.head_parts(tta_views(images, self.flips))
+        anchor_hm, part_hm = self.merged([heat], lambda hms: tta_merge_nms(hms[0], self.flips))
         return TtaOutput(anchor_hm=anchor_hm, part_hm=part_hm, offsets=offsets[:B], embeddings=embeddings[:B])
 
 
-class TransposeTta:
+class TransposeTta(_ViewNet):
     """`net` behind the transposed-view test, combined with the flip views of `mode` ("none": the image and its transpose):
     `TransposeTta(net, args, mode)(images)` returns a `TtaOutput` like `FlipTta`: the merged, suppressed PROBABILITY maps of 2*Vf views and
     view 0's offsets / embeddings (no copy).  A square batch is one forward over 2*Vf*B images, any other two forwards of Vf*B images, at
     H x W and at W x H.  Decode it with `tta_decoder(args)`."""
 
-    def __init__(self, net, args, mode="none"):
-        if mode != "none" and mode not in VIEW_FLIPS:
-            raise L.SdError(f"unknown test-time augmentation mode {mode!r} (one of {', '.join(MODES)})")
-        self.net, self.args, self.mode = net, args, mode
-        self.flips = VIEW_FLIPS.get(mode, (0,))
-        self.label_count, self.part_count = len(args.labels), len(args.parts)
-
     def __call__(self, images):
         B, n = images.shape[0], len(self.flips) * images.shape[0]
-        M, nb = self.label_count, self.label_count + self.part_count
         if images.shape[2] == images.shape[3]:
-            heat, offsets, embeddings = head_parts(self.net(d4_views(images, self.flips, joint=True)), M, nb)
-            heat_t = [hm[n:] for hm in heat]
-            heat = [hm[:n] for hm in heat]
+            heat, offsets, embeddings = self.head_parts(d4_views(images, self.flips, joint=True))
+            heat, heat_t = [hm[:n] for hm in heat], [hm[n:] for hm in heat]
         else:
             plain, transposed = d4_views(images, self.flips)
-            heat, offsets, embeddings = head_parts(self.net(plain), M, nb)
-            heat_t, _, _ = head_parts(self.net(transposed), M, nb)
-        if len(heat) == 1 and len(heat_t) == 1:                        # adjacent slices of one head tensor: one launch
-            merged = d4_merge_nms(heat[0], heat_t[0], self.flips)
-            anchor_hm, part_hm = merged[:, :M], merged[:, M:]
-        else:
-            heat, heat_t = ([hm[0][:, :M], hm[0][:, M:]] if len(hm) == 1 else hm for hm in (heat, heat_t))
-            anchor_hm, part_hm = (d4_merge_nms(heat[k], heat_t[k], self.flips) for k in (0, 1))
+            heat, offsets, embeddings = self.head_parts(plain)
+            heat_t, _, _ = self.head_parts(transposed)
+        anchor_hm, part_hm = self.merged([heat, heat_t], lambda hms: d4_merge_nms(hms[0], hms[1], self.flips))
         return TtaOutput(anchor_hm=anchor_hm, part_hm=part_hm, offsets=offsets[:B], embeddings=embeddings[:B])
 
 
