@@ -307,6 +307,22 @@ int sd_tile_views(const float* canvas, float* out, int B, int Hc, int Wc, int H,
 int sd_tile_merge_nms(const float* hm, int64_t sb, int64_t sc, int C, const float* reg, int64_t r_sb, int64_t r_sc, int R,
                       float* out_hm, float* out_reg, int B, int h, int w, int Ty, int Tx, int o, sd_stream_t stream);
 
+/* ---- cross-label anchor suppression (no reference counterpart: the reference suppresses per heatmap channel only) ----
+ * sd_label_nms: `p` = P, the per-label suppressed probability maps (what sd_nms5(apply_sigmoid = 1) or a merge kernel writes), a strided
+ *   (sb, sc) (B,M,h,w) view (for example the anchor slice of a merge kernel's output); out (B,M,h,w) contiguous; R = the radius in cells.
+ *   Per image:
+ *       best(y, x)  = max over c < M of P[c, y, x];      first(y, x) = the lowest c with P[c, y, x] == best(y, x)
+ *       win(y, x)   = max of best over |dy| <= R, |dx| <= R; cells outside the map do not count (-inf padding)
+ *       out[c, y, x] = P[c, y, x] if P[c, y, x] == win(y, x) and c == first(y, x), else 0
+ *   Only max and ==: equal values at different cells inside a window both survive (as in sd_nms5), a tie of labels at one cell goes to the
+ *   lowest label, and the rule is one max-pool, not a greedy loop: a peak suppressed by a neighbour still suppresses.  With M = 1 and
+ *   R <= 2 the output equals the input; with R > 2 peaks of one label closer than R are thinned as well.
+ *   1 <= R <= 8, 1 <= M <= 256, B <= 65535, M*h*w < 2^31, sb and sc >= h*w, no null pointer; anything else is SD_ERR_INVALID.  One launch,
+ *   no workspace, no atomics, no host synchronisation, deterministic.  One block per 64x16 tile and image walks the M label planes, each
+ *   read once (+ halo re-reads), and writes every label plane of its tile from registers; 16-byte accesses when w % 4 == 0 and pointers /
+ *   strides are 16-byte aligned, 4-byte accesses otherwise, same result. */
+int sd_label_nms(const float* p, int64_t sb, int64_t sc, float* out, int B, int M, int h, int w, int R, sd_stream_t stream);
+
 /* ---- target rendering: src/sdnet/data/transforms.py:130-205 (Encode) ---------------------- */
 
 /* Heatmaps of a batch (transforms.py:143,160-161,173-174; utils.py:418-419): for every pixel of

@@ -86,6 +86,8 @@ _SIGNATURES = {
     # tiled inference: canvas, out, B, Hc, Wc, H, W, Ty, Tx, O, stream / hm map, C, reg map, R, out_hm, out_reg, B, h, w, Ty, Tx, o, stream
     "sd_tile_views": (c_int, [c_vp, c_vp] + [c_int] * 8 + [c_vp]),
     "sd_tile_merge_nms": (c_int, _MAP + [c_int] + _MAP + [c_int, c_vp, c_vp] + [c_int] * 6 + [c_vp]),
+    # cross-label anchor suppression: map, out, B, M, h, w, R, stream
+    "sd_label_nms": (c_int, _MAP + [c_vp] + [c_int] * 5 + [c_vp]),
     "sd_preprocess_workspace_bytes": (c_size, [c_int] * 4),
     "sd_preprocess_images": (c_int, [c_vp] + [c_int] * 5 + [c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp, C.POINTER(c_float), C.POINTER(c_float),
                                                 c_vp, c_vp, c_size, c_vp]),

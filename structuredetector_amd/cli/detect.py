@@ -39,7 +39,7 @@ def _detect(argv):
         net.load_state_dict(torch.load(args.pretrained_model, map_location="cpu", weights_only=True))
     net = net.eval().to(args.device)
     if (getattr(args, "tta", "none") != "none" or getattr(args, "tta_scales", ()) or getattr(args, "tiles", ())
-            or getattr(args, "tta_transpose", False)):
+            or getattr(args, "tta_transpose", False) or getattr(args, "label_nms", 0)):
         from ..model.tta import with_tta
         net, decoder = with_tta(net, decoder, args)
     out_dir = Path("predictions")

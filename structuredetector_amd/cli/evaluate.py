@@ -52,9 +52,11 @@ def _evaluate(argv):
     net = net.eval().to(args.device)
     refuse_synthetic_resampling(args)
     if (getattr(args, "tta", "none") != "none" or getattr(args, "tta_scales", ()) or getattr(args, "tiles", ())
-            or getattr(args, "tta_transpose", False)):      # --tta / --tta_scales: the views, the forwards and the merge sit inside the per-batch step
+            or getattr(args, "tta_transpose", False) or getattr(args, "label_nms", 0)):      # --tta / --tta_scales: the views, the forwards and the merge sit inside the per-batch step
         from ..model.tta import with_tta
         net, decoder = with_tta(net, decoder, args)
+    if getattr(args, "label_nms", 0) and rank == 0:
+        print(f"label_nms: anchor peaks are suppressed across the {len(args.labels)} label maps within {args.label_nms} cells")
     curve = None
     if getattr(args, "pr_curve", False):                   # --pr_curve: every threshold of the grid from one matching pass (model/pr_curve.py)
         from ..model.pr_curve import PrCurve

@@ -108,7 +108,7 @@ class Predictor(torch.nn.Module):
         self.decoder = Decoder(args)
         self.tta = None
         if (getattr(args, "tta", "none") != "none" or getattr(args, "tta_scales", ()) or getattr(args, "tiles", ())
-                or getattr(args, "tta_transpose", False)):     # --tta / --tta_scales: views, sizes + merged heatmaps (model/tta.py)
+                or getattr(args, "tta_transpose", False) or getattr(args, "label_nms", 0)):     # --tta / --tta_scales: views, sizes + merged heatmaps (model/tta.py)
             from .tta import with_tta
             net, self.decoder = with_tta(self.model, self.decoder, args)
             self.tta = net if net is not self.model else None

@@ -270,7 +270,19 @@ def with_tta(net, decoder, args):
     """(net, decoder) as they are for `--tta none`, no `--tta_scales` and no `--tiles` (or no such attributes); `net` behind `FlipTta` for
     a flip mode alone; `net` behind `ScaleTta` when `--tta_scales` adds at least one input size.  Both come with `tta_decoder(args)`.
     `--tiles` (model/tiles.py) puts `net` behind `TiledNet` with its `tiled_decoder`, and is refused together with the other two.
-    `--tta_transpose`, alone or with a flip mode, puts `net` behind `TransposeTta`; with `--tta_scales` or `--tiles` it is refused."""
+    `--tta_transpose`, alone or with a flip mode, puts `net` behind `TransposeTta`; with `--tta_scales` or `--tiles` it is refused.
+    `--label_nms R` (model/label_nms.py) comes last, around whatever the rules above gave: a wrapper keeps its decoder, the bare `net`
+    gets `tta_decoder(args)` (a `LabelNms` output holds suppressed probabilities).  R = 0, or no such attribute: nothing is added."""
+    inner, inner_decoder = _with_views(net, decoder, args)
+    R = int(getattr(args, "label_nms", 0) or 0)
+    if R == 0:
+        return inner, inner_decoder
+    from .label_nms import LabelNms
+    return LabelNms(inner, args, R), (tta_decoder(args) if inner is net else inner_decoder)
+
+
+def _with_views(net, decoder, args):
+    """`with_tta` without `--label_nms`."""
     from ..utils.args import parse_tiles, parse_tta_scales
     mode = getattr(args, "tta", "none") or "none"
     ratios = parse_tta_scales(getattr(args, "tta_scales", "") or "")

@@ -80,6 +80,12 @@ _FLAGS = [
                                 "4 with --tta hflip or vflip, 8 with --tta hvflip: the eight symmetries of the grid; a non-square input takes "
                                 "two forwards), the heatmaps are turned back, averaged and decoded once. Combines with --tta; does not "
                                 "combine with --tta_scales / --tiles. Not consulted by train.")),
+    (("--label_nms",), dict(type=int, default=0, metavar="R", help="Cross-label anchor suppression in evaluate / detect / Predictor: after "
+                            "the per-label 5x5 NMS an anchor peak survives only where it equals the maximum over ALL label maps within R "
+                            "output cells (1 .. 8), so an object that peaks under two labels at the same place or a cell apart is decoded "
+                            "once, under the stronger label (the lower one on a tie). One max-pool, not a greedy loop; with R > 2 peaks of "
+                            "one label closer than R are thinned too (the wider window for --tiles scale). Part maps are untouched. Combines "
+                            "with --tta / --tta_scales / --tta_transpose / --tiles. Not consulted by train. 0 = off.")),
     (("--tiles",), dict(type=str, default="", metavar="CxR", help="Tiled inference in evaluate / detect / Predictor: columns x rows of "
                         "overlapping tiles (e.g. 2x2 or 3x2, each 1 .. 8). The source image is resized to a canvas of C*W - (C-1)*O by "
                         "R*H - (R-1)*O pixels (O = --tile_overlap), the network runs on every W x H tile -- the forward sees C*R times "
@@ -211,6 +217,18 @@ def check_train_tiles(args):
     return grid
 
 
+MAX_LABEL_NMS = 8                   # radius in cells (sd_label_nms / sd_nms5_labels)
+
+
+def check_label_nms(radius):
+    """`--label_nms`: an integer radius in output cells, 0 (off) .. 8; returns it as an int."""
+    if isinstance(radius, bool) or int(radius) != radius:
+        raise ValueError(f"'label_nms' should be an integer number of cells, not {radius!r}")
+    if not 0 <= radius <= MAX_LABEL_NMS:
+        raise ValueError(f"'label_nms' should be in [0, {MAX_LABEL_NMS}] (0 = off), not {radius}")
+    return int(radius)
+
+
 def check_aug_transpose(args):
     """`--aug_transpose` on a parsed namespace -> P, as `train` checks it (model/trainer.py): a batch has ONE shape, so a transposed sample
     needs width == height (the per-epoch multi-scale rule and the `--train_tiles` windows keep a square square)."""
@@ -242,6 +260,7 @@ def finalize(args):
     assert 0 <= getattr(args, "aug_translate", 0.0) <= 0.5, "'aug_translate' should be in [0, 0.5]"
     assert 0 <= getattr(args, "aug_mosaic", 0.0) <= 1, "'aug_mosaic' should be in [0, 1]"
     assert 0 <= getattr(args, "aug_transpose", 0.0) <= 1, "'aug_transpose' should be in [0, 1]"
+    args.label_nms = check_label_nms(getattr(args, "label_nms", 0))
     args.tta_scales = parse_tta_scales(getattr(args, "tta_scales", ""))
     args.tiles = parse_tiles(getattr(args, "tiles", ""))
     args.tile_overlap = check_tile_overlap(getattr(args, "tile_overlap", 64), args.width, args.height) if args.tiles \
