@@ -438,6 +438,29 @@ int sd_preprocess_images_list_window(const uint8_t* const* images, int B, int Hi
                                      const float* mean3, const float* std3, float* out, void* workspace, size_t workspace_bytes,
                                      sd_stream_t stream);
 
+/* Every pipeline above behind a LETTERBOX (aspect-preserving input, `--keep_aspect`): the source is resized to (Hi, Wi) -- the largest size
+ * of its aspect ratio that fits the frame, data/augment.py letterbox_geometry -- and pasted at (x0, y0) into a (Hout, Wout) frame of fill3,
+ * byte for byte Image.new("RGB", (Wout, Hout), fill3).paste(Image.resize((Wi, Hi), BILINEAR), (x0, y0)), and everything after the resize
+ * works on that frame: Letterbox -> [Mosaic] -> [RandomAffine] -> [ColorJitter] -> flips -> Normalize at (Hout, Wout); the contrast op's
+ * grey mean is taken over the frame, bars included.  h_bounds / h_kk and v_bounds / v_kk are the tables of Win -> Wi and Hin -> Hi.  The
+ * geometry is the same for the whole batch and is checked here: x0 < 0, y0 < 0, x0 + Wi > Wout or y0 + Hi > Hout is SD_ERR_INVALID.
+ * Every stage is optional: flips, jitter_order + jitter_factors, affine, mosaic_geom + mosaic_affine may be null (all null: letterbox +
+ * Normalize, two launches; a bar pixel is ((float)fill / 255 - mean) / std, the expressions of an image pixel); fill3 is always needed.
+ * One half of a pair alone or a null fill3: SD_ERR_INVALID.  With Wi == Wout and Hi == Hout the output is that of the entry points above
+ * bit for bit.  The list form takes the pointer table of sd_preprocess_images_list (same Win limit).
+ * workspace: sd_preprocess_letterbox_workspace_bytes() bytes in every case. */
+size_t sd_preprocess_letterbox_workspace_bytes(int B, int Hin, int Wi, int Hout, int Wout);
+int sd_preprocess_images_letterbox(const uint8_t* images, int B, int Hin, int Win, int Hi, int Wi, int Hout, int Wout, int y0, int x0,
+                                   const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize,
+                                   const uint8_t* flips, const int* jitter_order, const float* jitter_factors, const double* affine,
+                                   const int* mosaic_geom, const double* mosaic_affine, const uint8_t fill3[3], const float* mean3,
+                                   const float* std3, float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream);
+int sd_preprocess_images_list_letterbox(const uint8_t* const* images, int B, int Hin, int Win, int Hi, int Wi, int Hout, int Wout, int y0, int x0,
+                                        const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize,
+                                        const uint8_t* flips, const int* jitter_order, const float* jitter_factors, const double* affine,
+                                        const int* mosaic_geom, const double* mosaic_affine, const uint8_t fill3[3], const float* mean3,
+                                        const float* std3, float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream);
+
 /* ---- loss: src/sdnet/model/loss.py:17-64,91-117 ------------------------------------------- */
 
 #define SD_HM_MSE   0

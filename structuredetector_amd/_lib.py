@@ -119,6 +119,13 @@ _SIGNATURES = {
                                     [C.POINTER(C.c_ubyte), C.POINTER(c_float), C.POINTER(c_float), c_vp, c_vp, c_size, c_vp]),
     "sd_preprocess_images_list_window": (c_int, [c_vp] + [c_int] * 7 + [c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_int, c_int] + [c_vp] * 6 +
                                          [C.POINTER(C.c_ubyte), C.POINTER(c_float), C.POINTER(c_float), c_vp, c_vp, c_size, c_vp]),
+    # letterbox in front of every chain: images, B, Hin, Win, Hi, Wi, Hout, Wout, y0, x0, tables, flips, jitter_order, jitter_factors, affine,
+    # mosaic_geom, mosaic_affine (each stage null: off), fill3 (HOST, always needed), mean3, std3, out, workspace, bytes, stream
+    "sd_preprocess_letterbox_workspace_bytes": (c_size, [c_int] * 5),
+    "sd_preprocess_images_letterbox": (c_int, [c_vp] + [c_int] * 9 + [c_vp, c_vp, c_int, c_vp, c_vp, c_int] + [c_vp] * 6 +
+                                       [C.POINTER(C.c_ubyte), C.POINTER(c_float), C.POINTER(c_float), c_vp, c_vp, c_size, c_vp]),
+    "sd_preprocess_images_list_letterbox": (c_int, [c_vp] + [c_int] * 9 + [c_vp, c_vp, c_int, c_vp, c_vp, c_int] + [c_vp] * 6 +
+                                            [C.POINTER(C.c_ubyte), C.POINTER(c_float), C.POINTER(c_float), c_vp, c_vp, c_size, c_vp]),
     "sd_render_targets": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_float, c_vp, c_vp]),
     "sd_loss_workspace_bytes": (c_size, [c_int] * 5),
     "sd_loss_fwd": (c_int, [C.POINTER(LossDesc), c_vp, c_vp, c_size, c_vp]),

@@ -16,6 +16,8 @@ from ..data import Decoder
 from ..data.dataset import PredictionDataset
 from ..model import Network
 from ..utils import Arguments, draw
+from ..utils.args import check_keep_aspect
+from ..utils.misc import unletterbox_annotation
 from ..utils.distributed import gather_objects, init_from_env, shard_range, world_info
 
 
@@ -31,6 +33,7 @@ def main(argv=None):
 def _detect(argv):
     args = Arguments().parse(argv)
     assert args.valid_dir, "Path to a directory with the images to process must be specified (--valid_dir)."
+    keep_aspect = check_keep_aspect(args)                  # --keep_aspect: refused with --tiles / --tta_scales
     rank, world = world_info()
     dataset = PredictionDataset(args.valid_dir, args, raw=True)
     decoder = Decoder(args)
@@ -49,7 +52,10 @@ def _detect(argv):
     shard = shard_range(len(dataset), rank, world)
     for annotation, source, _, _ in batched_outputs(net, decoder, dataset, args, with_raw_parts=False, index_range=shard):
         img_size, image_path = source.img_size, source.image_path
-        annotation.resize((args.width, args.height), img_size)          # back to the pixels of the original image
+        if keep_aspect:                                                 # back to the pixels of the original image: out of the frame, then the scale
+            unletterbox_annotation(annotation, img_size, (args.width, args.height))
+        else:
+            annotation.resize((args.width, args.height), img_size)
         annotation.img_size = img_size
         annotation.image_path = image_path
         image = draw(Image.open(image_path).convert("RGB"), annotation, args)

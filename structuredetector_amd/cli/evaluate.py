@@ -16,6 +16,7 @@ import torch.distributed as dist
 from ..data import CropDataset, Decoder
 from ..model import Evaluator, Network
 from ..utils import Arguments
+from ..utils.args import check_keep_aspect
 from ..utils.distributed import gather_evaluator, gather_pr_curve, init_from_env, shard_range, world_info
 
 
@@ -41,6 +42,7 @@ def refuse_synthetic_resampling(args):
 def _evaluate(argv):
     args = Arguments().parse(argv)
     assert args.synthetic or args.valid_dir, "Path to a directory with validation samples must be specified."
+    check_keep_aspect(args)                                # --keep_aspect: refused with --tiles / --tta_scales / --synthetic
     rank, world = world_info()
     evaluator = Evaluator(args)
     decoder = Decoder(args)

@@ -715,6 +715,67 @@ __global__ __launch_bounds__(256) void k_window_v_u8(const uint8_t* __restrict__
     dst[0] = (uint8_t)c.r; dst[1] = (uint8_t)c.g; dst[2] = (uint8_t)c.b;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Letterbox (`--keep_aspect`; not in the reference): the Resize targets the largest Wi x Hi of the source's aspect ratio that fits the
+// Wout x Hout frame (data/augment.py letterbox_geometry) and the resized image is pasted at (x0, y0) into a frame of fill3 -- byte for
+// byte Image.new("RGB", (Wout, Hout), fill).paste(Image.resize((Wi, Hi), BILINEAR), (x0, y0)).  The horizontal pass is the plain one at
+// Wout = Wi (k_resample_h / k_resample_h_list); the vertical pass below produces the frame, one thread per FRAME pixel: inside the
+// placed rectangle k_resample_v_*'s sum on table row y - y0 and intermediate column x - x0, outside it the fill colour -- a bar pixel
+// reads neither the tables nor the intermediate.  The geometry is uniform over the batch (batches are grouped by source size) and
+// checked by the host half: host integers, no table, no clamp.
+// ---------------------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ Rgb8 letterbox_pixel(const uint8_t* __restrict__ in, int Hin, int Hi, int Wi, int y0, int x0,
+                                                const int* __restrict__ bounds, const int* __restrict__ kk, int ksize, int b, int x, int y,
+                                                const Rgb8& fill) {
+    const int ix = x - x0, iy = y - y0;
+    if (ix < 0 || ix >= Wi || iy < 0 || iy >= Hi) return fill;
+    const int ymin = bounds[2 * iy], n = bounds[2 * iy + 1];
+    const int* k = kk + (int64_t)iy * ksize;
+    const uint8_t* src = in + (((int64_t)b * Hin + ymin) * Wi + ix) * 3;
+    int s0 = 1 << (PRECISION_BITS - 1), s1 = s0, s2 = s0;
+    for (int r = 0; r < n; ++r) {
+        const int w = k[r];
+        const uint8_t* px = src + (int64_t)r * Wi * 3;
+        s0 += px[0] * w; s1 += px[1] * w; s2 += px[2] * w;
+    }
+    return Rgb8{clip8(s0), clip8(s1), clip8(s2)};
+}
+
+// vertical pass + paste + flips + to_tensor + Normalize: tmp (B, Hin, Wi, 3) u8 -> out (B, 3, Hout, Wout) fp32 NCHW.  The flips act on the
+// FRAME; a bar pixel goes through the same float expressions as an image pixel (bit-identical to normalising a fill byte).
+__global__ __launch_bounds__(256) void k_letterbox_v_norm(const uint8_t* __restrict__ in, float* __restrict__ out, int Hin, int Hi, int Wi, int Hout,
+                                                           int Wout, int y0, int x0, const int* __restrict__ bounds, const int* __restrict__ kk,
+                                                           int ksize, const uint8_t* __restrict__ flips, int f0, int f1, int f2, float m0, float m1,
+                                                           float m2, float d0, float d1, float d2, int B) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;          // one frame pixel (three planes) per thread
+    if (i >= (int64_t)B * Hout * Wout) return;
+    const int x = (int)(i % Wout);
+    const int64_t t = i / Wout;
+    const int y = (int)(t % Hout), b = (int)(t / Hout);
+    const int f = flips ? flips[b] : 0;
+    const int sx = (f & 1) ? Wout - 1 - x : x, sy = (f & 2) ? Hout - 1 - y : y;
+    const Rgb8 c = letterbox_pixel(in, Hin, Hi, Wi, y0, x0, bounds, kk, ksize, b, sx, sy, Rgb8{f0, f1, f2});
+    const int64_t plane = (int64_t)Hout * Wout;
+    float* o = out + (int64_t)b * 3 * plane + (int64_t)y * Wout + x;
+    o[0] = ((float)c.r / 255.0f - m0) / d0;
+    o[plane] = ((float)c.g / 255.0f - m1) / d1;
+    o[2 * plane] = ((float)c.b / 255.0f - m2) / d2;
+}
+
+// vertical pass + paste only: tmp (B, Hin, Wi, 3) u8 -> img (B, Hout, Wout, 3) u8, the frame the mosaic / warp / jitter stages work on
+__global__ __launch_bounds__(256) void k_letterbox_v_u8(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int Hin, int Hi, int Wi, int Hout,
+                                                         int Wout, int y0, int x0, const int* __restrict__ bounds, const int* __restrict__ kk,
+                                                         int ksize, int f0, int f1, int f2, int B) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t)B * Hout * Wout) return;
+    const int x = (int)(i % Wout);
+    const int64_t t = i / Wout;
+    const int y = (int)(t % Hout), b = (int)(t / Hout);
+    const Rgb8 c = letterbox_pixel(in, Hin, Hi, Wi, y0, x0, bounds, kk, ksize, b, x, y, Rgb8{f0, f1, f2});
+    uint8_t* dst = out + i * 3;
+    dst[0] = (uint8_t)c.r; dst[1] = (uint8_t)c.g; dst[2] = (uint8_t)c.b;
+}
+
 }  // namespace sd
 
 using namespace sd;
@@ -1161,6 +1222,111 @@ int sd_preprocess_images_list_window(const uint8_t* const* images, int B, int Hi
     SD_LAUNCH_CHECK();
     return window_tail(B, Hc, Wc, Hout, Wout, v_bounds, v_kk, v_ksize, window, max_rows, flips, jitter_order, jitter_factors, affine, mosaic_geom,
                        mosaic_affine, fill3, mean3, std3, out, tmp, st);
+}
+
+// ---- Letterbox in front of every chain above (k_resample_h / k_resample_h_list at Wout = Wi, k_letterbox_v_norm / k_letterbox_v_u8) ----
+// workspace: [horizontal intermediate (B, Hin, Wi, 3) | 8-bit frame A | grey sums | 8-bit frame B], the layout of the mosaic forms with
+// the intermediate at the inner width and the 8-bit images at the frame's size.
+size_t sd_preprocess_letterbox_workspace_bytes(int B, int Hin, int Wi, int Hout, int Wout) {
+    return align_up((size_t)B * Hin * Wi * 3, 256) + 2 * align_up((size_t)B * Hout * Wout * 3, 256) + align_up((size_t)B * 8, 256);
+}
+
+static int letterbox_check(const char* what, const uint8_t* images, int B, int Hin, int Win, int Hi, int Wi, int Hout, int Wout, int y0, int x0,
+                           const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize,
+                           const int* jitter_order, const float* jitter_factors, const double* affine, const int* mosaic_geom,
+                           const double* mosaic_affine, const uint8_t* fill3, const float* mean3, const float* std3, float* out, void* workspace,
+                           size_t workspace_bytes) {
+    if (int e = preprocess_check(what, images, B, Hin, Win, Hi, Wi, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, mean3, std3, out, workspace))
+        return e;
+    SD_REQUIRE(fill3, SD_ERR_INVALID, "%s: null fill colour", what);
+    SD_REQUIRE(Hout > 0 && Wout > 0 && (int64_t)B * Hout * Wout * 3 < (1ll << 40), SD_ERR_INVALID, "%s: bad frame %d x %d", what, Wout, Hout);
+    SD_REQUIRE(x0 >= 0 && y0 >= 0 && (int64_t)x0 + Wi <= Wout && (int64_t)y0 + Hi <= Hout, SD_ERR_INVALID,
+               "%s: a %d x %d image at (%d, %d) does not lie inside the %d x %d frame", what, Wi, Hi, x0, y0, Wout, Hout);
+    SD_REQUIRE((jitter_order == nullptr) == (jitter_factors == nullptr), SD_ERR_INVALID,
+               "%s: jitter_order and jitter_factors go together (both null = no jitter)", what);
+    SD_REQUIRE((mosaic_geom == nullptr) == (mosaic_affine == nullptr), SD_ERR_INVALID,
+               "%s: mosaic_geom and mosaic_affine go together (both null = no mosaic)", what);
+    SD_REQUIRE(B <= 65535 || !(jitter_order || affine || mosaic_geom), SD_ERR_INVALID, "%s: batch %d > 65535", what, B);
+    SD_REQUIRE(workspace_bytes >= sd_preprocess_letterbox_workspace_bytes(B, Hin, Wi, Hout, Wout), SD_ERR_WORKSPACE, "%s: workspace %zu < %zu", what,
+               workspace_bytes, sd_preprocess_letterbox_workspace_bytes(B, Hin, Wi, Hout, Wout));
+    return 0;
+}
+
+// the launches after the horizontal pass: the letterbox vertical pass, fused with Normalize when no stage follows, else into the 8-bit
+// frame the existing tails resample into, and then their launches (jitter_norm, affine_stages, mosaic_stages) at the frame's size
+static int letterbox_tail(int B, int Hin, int Hi, int Wi, int Hout, int Wout, int y0, int x0, const int* v_bounds, const int* v_kk, int v_ksize,
+                          const uint8_t* flips, const int* jitter_order, const float* jitter_factors, const double* affine, const int* mosaic_geom,
+                          const double* mosaic_affine, const uint8_t* fill3, const float* mean3, const float* std3, float* out, uint8_t* tmp,
+                          hipStream_t st) {
+    const dim3 grid(cdiv((int64_t)B * Hout * Wout, 256));
+    const int f0 = fill3[0], f1 = fill3[1], f2 = fill3[2];
+    if (!jitter_order && !affine && !mosaic_geom) {
+        hipLaunchKernelGGL(k_letterbox_v_norm, grid, dim3(256), 0, st, tmp, out, Hin, Hi, Wi, Hout, Wout, y0, x0, v_bounds, v_kk, v_ksize, flips, f0,
+                           f1, f2, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], B);
+        SD_LAUNCH_CHECK();
+        return 0;
+    }
+    const size_t frame = align_up((size_t)B * Hout * Wout * 3, 256);
+    uint8_t* img_a = tmp + align_up((size_t)B * Hin * Wi * 3, 256);
+    unsigned long long* lsum = reinterpret_cast<unsigned long long*>(img_a + frame);
+    uint8_t* img_b = img_a + frame + align_up((size_t)B * 8, 256);
+    uint8_t* framed = (mosaic_geom != nullptr) == (affine != nullptr) ? img_a : img_b;     // jitter reads A, the warp B, the mosaic A with a warp, else B
+    hipLaunchKernelGGL(k_letterbox_v_u8, grid, dim3(256), 0, st, tmp, framed, Hin, Hi, Wi, Hout, Wout, y0, x0, v_bounds, v_kk, v_ksize, f0, f1, f2, B);
+    SD_LAUNCH_CHECK();
+    if (mosaic_geom)
+        return mosaic_stages(B, Hout, Wout, flips, jitter_order, jitter_factors, affine, mosaic_geom, mosaic_affine, fill3, mean3, std3, out, img_a,
+                             img_b, lsum, st);
+    if (affine)
+        return affine_stages(B, Hout, Wout, flips, jitter_order, jitter_factors, affine, fill3, mean3, std3, out, framed, img_a, lsum, st);
+    return jitter_norm(B, Hout, Wout, flips, jitter_order, jitter_factors, mean3, std3, out, img_a, lsum, st);
+}
+
+static int letterbox_zero_lsum(int B, int Hin, int Wi, int Hout, int Wout, uint8_t* tmp, hipStream_t st) {
+    uint8_t* lsum = tmp + align_up((size_t)B * Hin * Wi * 3, 256) + align_up((size_t)B * Hout * Wout * 3, 256);
+    SD_HIP(hipMemsetAsync(lsum, 0, (size_t)B * 8, st));
+    return 0;
+}
+
+int sd_preprocess_images_letterbox(const uint8_t* images, int B, int Hin, int Win, int Hi, int Wi, int Hout, int Wout, int y0, int x0,
+                                   const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize,
+                                   const uint8_t* flips, const int* jitter_order, const float* jitter_factors, const double* affine,
+                                   const int* mosaic_geom, const double* mosaic_affine, const uint8_t* fill3, const float* mean3, const float* std3,
+                                   float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
+    if (int e = letterbox_check("sd_preprocess_images_letterbox", images, B, Hin, Win, Hi, Wi, Hout, Wout, y0, x0, h_bounds, h_kk, h_ksize, v_bounds,
+                                v_kk, v_ksize, jitter_order, jitter_factors, affine, mosaic_geom, mosaic_affine, fill3, mean3, std3, out, workspace,
+                                workspace_bytes)) return e;
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t* tmp = reinterpret_cast<uint8_t*>(workspace);
+    if (jitter_order)
+        if (int e = letterbox_zero_lsum(B, Hin, Wi, Hout, Wout, tmp, st)) return e;
+    const int64_t rows = (int64_t)B * Hin;
+    hipLaunchKernelGGL(k_resample_h, dim3(cdiv(rows * Wi, 256)), dim3(256), 0, st, images, tmp, Hin, Win, Wi, h_bounds, h_kk, h_ksize, rows);
+    SD_LAUNCH_CHECK();
+    return letterbox_tail(B, Hin, Hi, Wi, Hout, Wout, y0, x0, v_bounds, v_kk, v_ksize, flips, jitter_order, jitter_factors, affine, mosaic_geom,
+                          mosaic_affine, fill3, mean3, std3, out, tmp, st);
+}
+
+int sd_preprocess_images_list_letterbox(const uint8_t* const* images, int B, int Hin, int Win, int Hi, int Wi, int Hout, int Wout, int y0, int x0,
+                                        const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize,
+                                        const uint8_t* flips, const int* jitter_order, const float* jitter_factors, const double* affine,
+                                        const int* mosaic_geom, const double* mosaic_affine, const uint8_t* fill3, const float* mean3,
+                                        const float* std3, float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
+    const char* what = "sd_preprocess_images_list_letterbox";
+    if (int e = letterbox_check(what, reinterpret_cast<const uint8_t*>(images), B, Hin, Win, Hi, Wi, Hout, Wout, y0, x0, h_bounds, h_kk, h_ksize,
+                                v_bounds, v_kk, v_ksize, jitter_order, jitter_factors, affine, mosaic_geom, mosaic_affine, fill3, mean3, std3, out,
+                                workspace, workspace_bytes)) return e;
+    SD_REQUIRE((int64_t)Win * 3 + 32 <= HL_LDS_BYTES, SD_ERR_INVALID, "%s: source rows of %d pixels exceed the LDS staging buffer (at most %d)",
+               what, Win, (HL_LDS_BYTES - 32) / 3);
+    const int rpb = (int)std::min<int64_t>(HL_ROWS, (HL_LDS_BYTES - 32) / ((int64_t)Win * 3));
+    const int bpi = cdiv(Hin, rpb);
+    SD_REQUIRE((int64_t)B * bpi < (1ll << 31), SD_ERR_INVALID, "%s: batch too large", what);
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t* tmp = reinterpret_cast<uint8_t*>(workspace);
+    if (jitter_order)
+        if (int e = letterbox_zero_lsum(B, Hin, Wi, Hout, Wout, tmp, st)) return e;
+    if (int e = resample_h_list(images, tmp, B, Hin, Win, Wi, h_bounds, h_kk, h_ksize, rpb, bpi, st)) return e;
+    return letterbox_tail(B, Hin, Hi, Wi, Hout, Wout, y0, x0, v_bounds, v_kk, v_ksize, flips, jitter_order, jitter_factors, affine, mosaic_geom,
+                          mosaic_affine, fill3, mean3, std3, out, tmp, st);
 }
 
 }  // extern "C"

@@ -22,6 +22,12 @@ Window (`--train_tiles CxR`; not in the reference): the Resize itself targets th
 only a W x H window of it at a random origin is produced, `Image.resize(canvas, BILINEAR).crop(window)` byte for byte
 (`sd_preprocess_images_window`: the source rows and columns under the window are all that is read); every later stage works on the window,
 the annotations follow with `ann.resize` to the canvas and `affine_annotation` by the shift.
+Letterbox (`--keep_aspect`; not in the reference): the Resize keeps the source's aspect ratio -- the largest wi x hi that fits W x H
+(`letterbox_geometry`, integers only) -- and the resized image sits centred in a W x H frame of `_FILL`, byte for byte
+`Image.new("RGB", (W, H), _FILL).paste(Image.resize((wi, hi), BILINEAR), (px, py))` (`sd_preprocess_images_letterbox`: the plain horizontal
+pass at width wi, then one vertical pass that writes image and bars); every later stage works on the frame, the annotations follow with
+`ann.resize` to the inner image and a shift by (px, py) that drops nothing (`utils.misc.letterbox_annotation`'s rule);
+`utils.misc.unletterbox_annotation` is the way back.
 Transpose (`--aug_transpose P`; not in the reference): last, after the flips, a selected image of the assembled (square) batch has its x and
 y swapped (`sd_transpose_select`, one launch: lossless, with the flips the eight symmetries of the grid); the annotations follow with
 `utils.misc.transpose_annotation`.
@@ -36,7 +42,8 @@ import torch
 
 from .. import _lib as L
 from ..utils.args import parse_tiles, tile_canvas
-from ..utils.misc import affine_annotation, clip_annotation, hflip_annotation, mosaic_annotation, transpose_annotation, vflip_annotation
+from ..utils.misc import (affine_annotation, clip_annotation, hflip_annotation, letterbox_annotation, letterbox_geometry, mosaic_annotation,
+                          transpose_annotation, vflip_annotation)
 
 PRECISION_BITS = 32 - 8 - 2
 _MEAN = (0.485, 0.456, 0.406)
@@ -201,6 +208,26 @@ def _affine_rows(affine, B, device):
     return rows.to(device, non_blocking=True)
 
 
+def _stage_tables(B, flips, jitter, affine, mosaic, dev):
+    """The device tables of the optional stages, each None when its stage is off: flips (B,) uint8, jitter order (B,) int32 and factors
+    (B, 3) fp32, affine rows (B, 6) fp64, mosaic geometry (B, 6) int32 and matrices (B, 24) fp64."""
+    fl = order = factors = rows = geom = mats = None
+    if flips is not None:
+        fl = torch.as_tensor(flips, dtype=torch.uint8).to(dev, non_blocking=True)
+        if fl.numel() != B:
+            raise L.SdError("flips must have one entry per image")
+    if jitter is not None:
+        order = torch.as_tensor(jitter[0], dtype=torch.int32).to(dev, non_blocking=True)
+        factors = torch.as_tensor(jitter[1], dtype=torch.float32).reshape(-1, 3).contiguous().to(dev, non_blocking=True)
+        if order.numel() != B or factors.shape[0] != B:
+            raise L.SdError("jitter parameters must have one row per image")
+    if affine is not None:
+        rows = _affine_rows(affine, B, dev)
+    if mosaic is not None:
+        geom, mats = _mosaic_tables(mosaic, B, dev)
+    return fl, order, factors, rows, geom, mats
+
+
 def _preprocess_window(fn_name, source, B, Hin, Win, out_size, flips, mean, std, jitter, affine, mosaic, window, dev):
     """The window forms of `preprocess_images` / `preprocess_image_list`: source = the address of the packed images or of the pointer
     table; window = ((Wc, Hc), B origins (x0, y0))."""
@@ -217,20 +244,7 @@ def _preprocess_window(fn_name, source, B, Hin, Win, out_size, flips, mean, std,
     vb, vk, vks = _tables.get(Hin, Hc, dev)
     max_cols, max_rows = window_extents(Win, Wc, Wout), window_extents(Hin, Hc, Hout)
     out = torch.empty((B, 3, Hout, Wout), dtype=torch.float32, device=dev)
-    fl = order = factors = rows = geom = mats = None
-    if flips is not None:
-        fl = torch.as_tensor(flips, dtype=torch.uint8).to(dev, non_blocking=True)
-        if fl.numel() != B:
-            raise L.SdError("flips must have one entry per image")
-    if jitter is not None:
-        order = torch.as_tensor(jitter[0], dtype=torch.int32).to(dev, non_blocking=True)
-        factors = torch.as_tensor(jitter[1], dtype=torch.float32).reshape(-1, 3).contiguous().to(dev, non_blocking=True)
-        if order.numel() != B or factors.shape[0] != B:
-            raise L.SdError("jitter parameters must have one row per image")
-    if affine is not None:
-        rows = _affine_rows(affine, B, dev)
-    if mosaic is not None:
-        geom, mats = _mosaic_tables(mosaic, B, dev)
+    fl, order, factors, rows, geom, mats = _stage_tables(B, flips, jitter, affine, mosaic, dev)
     ptr = lambda t: t.data_ptr() if t is not None else 0
     lib = L.lib()
     ws = L.workspace(lib.sd_preprocess_window_workspace_bytes(B, max_rows, Hout, Wout), dev)
@@ -241,21 +255,48 @@ def _preprocess_window(fn_name, source, B, Hin, Win, out_size, flips, mean, std,
     return out
 
 
+def _preprocess_letterbox(fn_name, source, B, Hin, Win, out_size, flips, mean, std, jitter, affine, mosaic, letterbox, dev):
+    """The letterbox forms of `preprocess_images` / `preprocess_image_list`: source = the address of the packed images or of the pointer
+    table; letterbox = (wi, hi, px, py) as `letterbox_geometry` gives them (the library checks that the image lies inside the frame)."""
+    wi, hi, px, py = (int(v) for v in letterbox)
+    Wout, Hout = int(out_size[0]), int(out_size[1])
+    if wi <= 0 or hi <= 0:
+        raise L.SdError(f"letterbox: the inner image should be at least 1 x 1, not {wi} x {hi}")
+    hb, hk, hks = _tables.get(Win, wi, dev)
+    vb, vk, vks = _tables.get(Hin, hi, dev)
+    out = torch.empty((B, 3, Hout, Wout), dtype=torch.float32, device=dev)
+    fl, order, factors, rows, geom, mats = _stage_tables(B, flips, jitter, affine, mosaic, dev)
+    ptr = lambda t: t.data_ptr() if t is not None else 0
+    lib = L.lib()
+    ws = L.workspace(lib.sd_preprocess_letterbox_workspace_bytes(B, Hin, wi, Hout, Wout), dev)
+    L.check(getattr(lib, fn_name)(source, B, Hin, Win, hi, wi, Hout, Wout, py, px, hb.data_ptr(), hk.data_ptr(), hks, vb.data_ptr(), vk.data_ptr(),
+                                  vks, ptr(fl), ptr(order), ptr(factors), ptr(rows), ptr(geom), ptr(mats), (C.c_ubyte * 3)(*_FILL),
+                                  (C.c_float * 3)(*mean), (C.c_float * 3)(*std), out.data_ptr(), ws.data_ptr(), ws.numel(), L.stream()), fn_name)
+    return out
+
+
 def preprocess_images(images: torch.Tensor, out_size, flips=None, mean=_MEAN, std=_STD, jitter=None, affine=None, mosaic=None,
-                      window=None) -> torch.Tensor:
+                      window=None, letterbox=None) -> torch.Tensor:
     """images: (B, Hin, Win, 3) uint8 on the GPU; out_size = (width, height); flips: (B,) uint8 (bit 0 horizontal, bit 1 vertical)
     or None; jitter: None or (order words (B,) int32, factors (B, 3) fp32) as `jitter_words` makes them; affine: None or B rows of the 6
     coefficients of `affine_inverse_matrix` at out_size (the warp runs on the resized image, in front of the jitter, fill `_FILL`); mosaic:
     None or (geom: B rows [cx, cy, s0 .. s3], matrices: B x 4 x 6) as `mosaic_tiles` makes them, the sources s_q indexing THIS batch
     (the composite is built from the resized images, in front of the warp); window: None or ((canvas width, canvas height), B origins
     (x0, y0)): the resize targets the canvas and only its out_size window at the origin is produced (`sd_preprocess_images_window`;
-    origins are clamped into the canvas on the device), every later stage works on that window.
+    origins are clamped into the canvas on the device), every later stage works on that window; letterbox: None or (wi, hi, px, py) as
+    `letterbox_geometry` gives them: the resize targets wi x hi and the result is pasted at (px, py) into an out_size frame of `_FILL`
+    (`sd_preprocess_images_letterbox`), every later stage works on that frame (not together with `window`).
     Returns (B, 3, height, width) fp32 = Normalize(to_tensor(flip(jitter(affine(mosaic(resize(image))))))) of transforms.py:217-226."""
     L.require_cuda(images)
     if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3:
         raise L.SdError(f"preprocess_images expects (B, H, W, 3) uint8, got {tuple(images.shape)} {images.dtype}")
     images = images.contiguous()
     B, Hin, Win, _ = images.shape
+    if letterbox is not None:
+        if window is not None:
+            raise L.SdError("preprocess_images: a letterbox and a window do not combine")
+        return _preprocess_letterbox("sd_preprocess_images_letterbox", images.data_ptr(), B, Hin, Win, out_size, flips, mean, std, jitter, affine,
+                                     mosaic, letterbox, images.device)
     if window is not None:
         return _preprocess_window("sd_preprocess_images_window", images.data_ptr(), B, Hin, Win, out_size, flips, mean, std, jitter, affine, mosaic,
                                   window, images.device)
@@ -310,7 +351,7 @@ def preprocess_images(images: torch.Tensor, out_size, flips=None, mean=_MEAN, st
 
 
 def preprocess_image_list(pointers: torch.Tensor, hin: int, win: int, out_size, flips=None, mean=_MEAN, std=_STD, jitter=None,
-                          affine=None, mosaic=None, window=None) -> torch.Tensor:
+                          affine=None, mosaic=None, window=None, letterbox=None) -> torch.Tensor:
     """`preprocess_images` over B images that are not packed together: pointers is a (B,) int64 DEVICE tensor of the device addresses of
     B (hin, win, 3) uint8 images (any byte alignment; the caller keeps them alive until the work on the current stream is done), e.g. entries
     of data/image_cache.py's DeviceImageCache.  Same arguments otherwise, same output bytes as `preprocess_images` on the stacked images."""
@@ -320,6 +361,11 @@ def preprocess_image_list(pointers: torch.Tensor, hin: int, win: int, out_size, 
     pointers = pointers.contiguous()
     dev = pointers.device
     B, Hin, Win = pointers.numel(), int(hin), int(win)
+    if letterbox is not None:
+        if window is not None:
+            raise L.SdError("preprocess_image_list: a letterbox and a window do not combine")
+        return _preprocess_letterbox("sd_preprocess_images_list_letterbox", pointers.data_ptr(), B, Hin, Win, out_size, flips, mean, std, jitter,
+                                     affine, mosaic, letterbox, dev)
     if window is not None:                                           # (the LDS limit of the list form then binds the window's column span)
         return _preprocess_window("sd_preprocess_images_list_window", pointers.data_ptr(), B, Hin, Win, out_size, flips, mean, std, jitter, affine,
                                   mosaic, window, dev)
@@ -407,11 +453,13 @@ class _Objects:
 
 
 class ValidationAugmentation:
-    """transforms.py:255-261 for a batch: Resize((width, height)) + Normalize (+ the clip Encode applies, transforms.py:154)."""
+    """transforms.py:255-261 for a batch: Resize((width, height)) + Normalize (+ the clip Encode applies, transforms.py:154).  With
+    `--keep_aspect` the Resize is a letterbox, its geometry computed per size group at the current size (`letterbox_geometry`)."""
 
     def __init__(self, args):
         self.args = args
         self.size = (args.width, args.height)
+        self.keep_aspect = bool(getattr(args, "keep_aspect", False))
 
     def draws_for(self, n):
         """(flips, jitter) for n samples: validation draws nothing."""
@@ -455,10 +503,11 @@ class ValidationAugmentation:
         groups = self.size_groups(images)
         out = None
         for (hin, win), (idx, stack) in groups.items():
+            box = letterbox_geometry((win, hin), (W, H)) if self.keep_aspect else None
             if hasattr(stack, "pointers"):
-                res = preprocess_image_list(stack.pointers, hin, win, (W, H))
+                res = preprocess_image_list(stack.pointers, hin, win, (W, H), letterbox=box)
             else:
-                res = preprocess_images(stack.to(dev, non_blocking=True), (W, H))
+                res = preprocess_images(stack.to(dev, non_blocking=True), (W, H), letterbox=box)
             if len(groups) == 1:
                 return res
             if out is None:
@@ -482,6 +531,8 @@ class ValidationAugmentation:
         transposes = self.transpose_draws_for(n)
         if transposes is not None and W != H:
             raise L.SdError(f"aug_transpose: a transposed sample needs a square batch, not {W} x {H}")
+        if windows is not None and self.keep_aspect:
+            raise L.SdError("keep_aspect does not combine with train_tiles: a window is cut from the stretched canvas")
         out = torch.empty((n, 3, H, W), dtype=torch.float32, device=dev)
         for (hin, win), (idx, stack) in groups.items():
             f = None if flips is None else [flips[i] for i in idx]
@@ -494,6 +545,9 @@ class ValidationAugmentation:
                 kw["mosaic"] = ([[*tiles[i][0][:2], *(where[s] for s in tiles[i][0][2:])] for i in idx], [tiles[i][1] for i in idx])
             if windows is not None:
                 kw["window"] = (windows[0], [windows[1][i] for i in idx])
+            box = None
+            if self.keep_aspect:                                     # one geometry per size group, at the current (multi-scale) size
+                box = kw["letterbox"] = letterbox_geometry((win, hin), (W, H))
             if hasattr(stack, "pointers"):                           # data/image_cache.py ImageList: cached / uploaded images by address
                 res = preprocess_image_list(stack.pointers, hin, win, (W, H), f, jitter=j, affine=m, **kw)
             else:
@@ -505,7 +559,9 @@ class ValidationAugmentation:
             for i in idx:
                 ann = annotations[i]
                 ann.img_size = ann.img_size or (win, hin)
-                if windows is None:
+                if box is not None:                                  # to the inner image, then to its place in the frame: nothing leaves it
+                    letterbox_annotation(ann, (win, hin), (W, H))
+                elif windows is None:
                     ann.resize((win, hin), (W, H))                   # transforms.py:58
                 else:                                                # to the canvas, then into the window: what leaves it is dropped
                     x0, y0 = windows[1][i]

@@ -94,13 +94,16 @@ def split_head(net, out):
 
 class Predictor(torch.nn.Module):
     """src/sdnet/model/predictor.py:8-37: network (weights from `args.pretrained_model`) + Decoder behind one call;
-    `forward(image)` takes a PIL image (any size) and returns its ImageAnnotation in network-input pixels."""
+    `forward(image)` takes a PIL image (any size) and returns its ImageAnnotation in network-input pixels -- with `--keep_aspect` the
+    pixels of the letterbox frame; `to_source(annotation, image.size)` maps either to the pixels of the image."""
 
     def __init__(self, args):
         super().__init__()
         from ..data import Decoder
         from .network import Network
         self.args = args
+        from ..utils.args import check_keep_aspect
+        self.keep_aspect = check_keep_aspect(args)                              # --keep_aspect: refused with --tiles / --tta_scales
         assert getattr(args, "pretrained_model", None), "No pretrained model specified. Use the option '--load_model <model_path>'."   # cli/evaluate.py:14-16
         self.model = Network(args, pretrained=False, init_weights=False)          # every tensor comes from the checkpoint (predictor.py:13-16)
         self.model.load_state_dict(torch.load(args.pretrained_model, map_location="cpu", weights_only=True), strict=True)
@@ -116,8 +119,19 @@ class Predictor(torch.nn.Module):
     def forward(self, image):
         import numpy as np
 
-        from ..data.augment import preprocess_images
+        from ..data.augment import letterbox_geometry, preprocess_images
         arr = torch.from_numpy(np.asarray(image.convert("RGB"), np.uint8).copy())[None].to(self.args.device)
+        size = (self.args.width, self.args.height)
+        box = letterbox_geometry((arr.shape[2], arr.shape[1]), size) if self.keep_aspect else None
         with torch.no_grad():
-            x = preprocess_images(arr, (self.args.width, self.args.height))
+            x = preprocess_images(arr, size, letterbox=box)
             return self.decoder(call_net(self.tta or self.model, x, lambda size: preprocess_images(arr, size)))[0]
+
+    def to_source(self, annotation, image_size):
+        """`forward`'s annotation (network-input pixels) in the pixels of the image it came from, image_size = (width, height) = PIL's
+        `image.size`, in place: out of the letterbox frame with `--keep_aspect`, the plain rescale otherwise."""
+        from ..utils.misc import unletterbox_annotation
+        size = (self.args.width, self.args.height)
+        if self.keep_aspect:
+            return unletterbox_annotation(annotation, tuple(image_size), size)
+        return annotation.resize(size, tuple(image_size))

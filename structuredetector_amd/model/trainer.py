@@ -474,10 +474,11 @@ class Trainer:
         import numpy as np
 
         from ..data import CropDataset, Encode
-        from ..utils.args import check_aug_transpose, check_train_tiles
+        from ..utils.args import check_aug_transpose, check_keep_aspect, check_train_tiles
         from .network import Network
         self.args = args
         check_train_tiles(args)                                        # --train_tiles: refused with --synthetic, overlap against the smallest size
+        check_keep_aspect(args, training=True)                         # --keep_aspect: refused with --train_tiles / --synthetic
         check_aug_transpose(args)                                      # --aug_transpose: square network inputs only
         if getattr(args, "use_amp", False) and not BF16_TRAINING:
             # the reference autocasts the training forward under --amp (trainer.py:115-121); silently training in fp32 under the

@@ -120,6 +120,13 @@ _FLAGS = [
                              "becomes a mosaic of itself and three other images of its batch at half scale around a random centre. A mosaic "
                              "carries up to four images' objects: raise --max_objects / --max_parts accordingly (what exceeds them is "
                              "truncated by the target encoder as always). Not consulted by evaluate / detect.")),
+    (("--keep_aspect",), dict(action="store_true", help="Aspect-preserving network input in train (training and validation feeds) / evaluate / "
+                              "detect / Predictor: the source image is resized, aspect ratio kept, to the largest size that fits "
+                              "--width x --height and placed centred in a frame filled with the ImageNet mean (a letterbox), instead of "
+                              "being stretched onto the frame; every augmentation and test-time view works on the frame; detect writes "
+                              "original-image pixels. Train and evaluate a model with the same setting. Does not combine with --tiles / "
+                              "--tta_scales / --train_tiles (their other sizes would letterbox with different roundings) or --synthetic. "
+                              "Off = the stretched input.")),
     (("--aug_transpose",), dict(type=float, default=0.0, metavar="P", help="Training augmentation: with probability P (0 .. 1; 0 = off) an "
                                 "image is transposed (x and y swapped: a lossless quarter turn with the flips, no resampling and no fill), "
                                 "after the flips. Needs a square network input (--width equal to --height). Not consulted by evaluate / "
@@ -215,6 +222,29 @@ def check_train_tiles(args):
         raise ValueError(f"'train_tiles' needs a network input whose smallest multi-scale size is at least 32 x 32, not {width} x {height}")
     check_tile_overlap(getattr(args, "tile_overlap", 64), width, height)
     return grid
+
+
+def check_keep_aspect(args, training=False):
+    """`--keep_aspect` on a parsed namespace -> bool, as `train` (training=True), `evaluate`, `detect` and `Predictor` check it before any
+    GPU work.  When it is on, the options whose other input sizes would letterbox with different integer roundings -- their grids would
+    no longer align exactly -- are refused: `--train_tiles` by train, `--tiles` and `--tta_scales` by the others (train never consults
+    those two); and `--synthetic`, which renders network-input tensors and has no source image to letterbox."""
+    if not getattr(args, "keep_aspect", False):
+        return False
+    if training:
+        if parse_tiles(getattr(args, "train_tiles", ""), "train_tiles"):
+            raise ValueError("'keep_aspect' does not combine with --train_tiles: the canvas a window is cut from would letterbox with other "
+                             "roundings than the frame; drop one of them")
+    else:
+        if parse_tiles(getattr(args, "tiles", "")):
+            raise ValueError("'keep_aspect' does not combine with --tiles: the canvas would letterbox with other roundings than the frame and "
+                             "the tile grids would not align; drop one of them")
+        if parse_tta_scales(getattr(args, "tta_scales", "")):
+            raise ValueError("'keep_aspect' does not combine with --tta_scales: every other input size would letterbox with its own roundings "
+                             "and the heatmap grids would not align; drop one of them")
+    if getattr(args, "synthetic", 0):
+        raise ValueError("'keep_aspect' letterboxes source images: it needs a directory (--train_dir / --valid_dir), not --synthetic")
+    return True
 
 
 MAX_LABEL_NMS = 8                   # radius in cells (sd_label_nms / sd_nms5_labels)

@@ -145,6 +145,53 @@ def mosaic_annotation(annotation, sources, forward_matrices, rects):
     return annotation
 
 
+def letterbox_geometry(in_size, out_size):
+    """The aspect-preserving resize of `--keep_aspect`: a (win, hin) = in_size source in a (W, H) = out_size frame -> (wi, hi, px, py), the
+    size of the resized image -- the largest of the source's aspect ratio that fits the frame, the free side rounded to the nearest
+    integer -- and where its top-left corner is pasted (centred, the odd pixel of a bar after it).  Integer arithmetic only:
+    width binds when W * hin <= H * win: wi = W, hi = min(H, max(1, (hin * W + win // 2) // win)); otherwise hi = H and wi likewise."""
+    (win, hin), (W, H) = (int(v) for v in in_size), (int(v) for v in out_size)
+    if min(win, hin, W, H) <= 0:
+        raise ValueError(f"letterbox_geometry: sizes should be positive, not {win} x {hin} in {W} x {H}")
+    if W * hin <= H * win:
+        wi, hi = W, min(H, max(1, (hin * W + win // 2) // win))
+    else:
+        wi, hi = min(W, max(1, (win * H + hin // 2) // hin)), H
+    return wi, hi, (W - wi) // 2, (H - hi) // 2
+
+
+def shift_annotation(annotation, dx, dy):
+    """Move every keypoint and box by (dx, dy), in place.  Nothing is dropped and nothing is clipped: a shift by (0, 0) leaves every
+    coordinate bit for bit as it was."""
+    for obj in annotation.objects:
+        obj.x, obj.y = obj.x + dx, obj.y + dy
+        for p in obj.parts:
+            p.x, p.y = p.x + dx, p.y + dy
+        if obj.box is not None:
+            b = obj.box
+            b.x_min, b.x_max, b.y_min, b.y_max = b.x_min + dx, b.x_max + dx, b.y_min + dy, b.y_max + dy
+    return annotation
+
+
+def letterbox_annotation(annotation, in_size, out_size):
+    """Follow the letterbox of an image (in place): ORIGINAL pixels of a (win, hin) = in_size source -> pixels of the (W, H) = out_size
+    frame: `resize` to the inner image, then the shift by its corner.  The inner image lies inside the frame, so nothing leaves it and
+    nothing is dropped: `resize` is the plain scale x * wi / win (transforms.py:58), under which a point in the last source pixel lands
+    up to a pixel past wi - 1 and is pinned by clip_annotation afterwards, exactly as on the stretched path -- with no bars (px = py = 0)
+    the result is the stretched path's bit for bit."""
+    wi, hi, px, py = letterbox_geometry(in_size, out_size)
+    annotation.resize(tuple(in_size), (wi, hi))
+    return shift_annotation(annotation, px, py)
+
+
+def unletterbox_annotation(annotation, in_size, out_size):
+    """The way back from `letterbox_annotation` (in place): pixels of the (W, H) = out_size frame -> ORIGINAL pixels of the (win, hin) =
+    in_size source: the shift by (-px, -py), then `resize` (wi, hi) -> (win, hin).  Nothing is dropped: a prediction inside a bar lands
+    outside the source, where the caller can see it."""
+    wi, hi, px, py = letterbox_geometry(in_size, out_size)
+    return shift_annotation(annotation, -px, -py).resize((wi, hi), tuple(in_size))
+
+
 def get_unique_color_map(labels):
     """utils.py:476-479: a stable RGB triple per name (first three bytes of its xxh64 digest)."""
     from xxhash import xxh64_digest
