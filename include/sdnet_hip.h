@@ -461,6 +461,50 @@ int sd_preprocess_images_list_letterbox(const uint8_t* const* images, int B, int
                                         const int* mosaic_geom, const double* mosaic_affine, const uint8_t fill3[3], const float* mean3,
                                         const float* std3, float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream);
 
+/* Gaussian blur of 8-bit images (training augmentation, `train --aug_blur`): image b becomes Image.filter(ImageFilter.GaussianBlur(r_b))
+ * byte for byte -- Pillow's three box-blur passes along the rows, then three along the columns, each rounded to bytes.  blur (B, 3) int32
+ * on the DEVICE = R, ww, fw per image, the whole box radius and the two 24-bit weights of one pass
+ *     out[x] = (ww * sum_{i = -R .. R} in[c(x + i)] + fw * (in[c(x - R - 1)] + in[c(x + R + 1)]) + 2^23) >> 24,  c = clamp to the line,
+ * computed on the host from r (data/augment.py blur_box_params; float32 arithmetic).  A row with R == 0 and fw == 0 (r = 0) copies its
+ * image.  The table cannot be checked without a sync, so the kernels clamp R to [0, SD_BLUR_MAX_RADIUS]: any table is memory-safe (the
+ * weights of a row that blurs are below 2^24 and enter as 24-bit factors; what a row outside the definition computes is unspecified).
+ * SD_BLUR_MAX_RADIUS is the box radius of r = 8, the largest `--aug_blur` (sigma^2 = 64 / 3, l = floor((sqrt(257) - 1) / 2) = 7, box
+ * radius 7.47).  in and out are (B, H, W, 3) uint8 and must not overlap (in place: SD_ERR_INVALID); workspace: sd_blur_workspace_bytes()
+ * bytes (the image between the two directions). */
+#define SD_BLUR_MAX_RADIUS 7
+size_t sd_blur_workspace_bytes(int B, int H, int W);
+int sd_blur_u8(const uint8_t* in, uint8_t* out, int B, int H, int W, const int* blur, void* workspace, size_t workspace_bytes,
+               sd_stream_t stream);
+
+/* Every pipeline above with the blur between the warp and the jitter:
+ *     Resize | Window | Letterbox -> [Mosaic] -> [RandomAffine] -> Blur -> [ColorJitter] -> flips -> Normalize;
+ * the contrast op's grey mean is taken over the blurred image.  One entry point per source form, the geometry chosen by `geometry`:
+ *     SD_GEOM_STRETCH    the plain resize to (Hout, Wout); Hg, Wg, g0, g1 are not read and window is null;
+ *     SD_GEOM_WINDOW     sd_preprocess_images_window:    (Hg, Wg) = the canvas (Hc, Wc), g0 = max_rows, g1 = max_cols, window (B, 2);
+ *     SD_GEOM_LETTERBOX  sd_preprocess_images_letterbox: (Hg, Wg) = the inner image (Hi, Wi), g0 = y0, g1 = x0, window is null;
+ * tables, limits and errors are those of the entry point of that geometry.  Every stage is optional (null = off), pairs go together, and
+ * fill3 is needed where that entry point needs it.  blur: as sd_blur_u8's.  With blur null the call IS the existing entry point of
+ * that geometry and those stages (its output bit for bit); with blur set and no jitter the blurred bytes go through flips + Normalize
+ * alone.  workspace: sd_preprocess_blur_workspace_bytes() bytes in every case -- [horizontal intermediate | 8-bit image A | grey sums |
+ * 8-bit image B], the layout of the mosaic / window / letterbox forms: the 8-bit stages alternate between A and B so that the blur's
+ * horizontal direction writes B and its vertical direction A, where the jitter reads. */
+#define SD_GEOM_STRETCH   0
+#define SD_GEOM_WINDOW    1
+#define SD_GEOM_LETTERBOX 2
+size_t sd_preprocess_blur_workspace_bytes(int geometry, int B, int Hin, int Win, int Wg, int Hout, int Wout, int g0);
+int sd_preprocess_images_blur(const uint8_t* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout, int g0, int g1,
+                              const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize,
+                              const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
+                              const double* affine, const int* mosaic_geom, const double* mosaic_affine, const int* blur,
+                              const uint8_t fill3[3], const float* mean3, const float* std3, float* out, void* workspace,
+                              size_t workspace_bytes, sd_stream_t stream);
+int sd_preprocess_images_list_blur(const uint8_t* const* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout,
+                                   int g0, int g1, const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk,
+                                   int v_ksize, const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
+                                   const double* affine, const int* mosaic_geom, const double* mosaic_affine, const int* blur,
+                                   const uint8_t fill3[3], const float* mean3, const float* std3, float* out, void* workspace,
+                                   size_t workspace_bytes, sd_stream_t stream);
+
 /* ---- loss: src/sdnet/model/loss.py:17-64,91-117 ------------------------------------------- */
 
 #define SD_HM_MSE   0

@@ -126,6 +126,16 @@ _SIGNATURES = {
                                        [C.POINTER(C.c_ubyte), C.POINTER(c_float), C.POINTER(c_float), c_vp, c_vp, c_size, c_vp]),
     "sd_preprocess_images_list_letterbox": (c_int, [c_vp] + [c_int] * 9 + [c_vp, c_vp, c_int, c_vp, c_vp, c_int] + [c_vp] * 6 +
                                             [C.POINTER(C.c_ubyte), C.POINTER(c_float), C.POINTER(c_float), c_vp, c_vp, c_size, c_vp]),
+    # gaussian blur of 8-bit images: in, out, B, H, W, blur (B, 3) int32 device = R, ww, fw, workspace, bytes, stream
+    "sd_blur_workspace_bytes": (c_size, [c_int] * 3),
+    "sd_blur_u8": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_size, c_vp]),
+    # every chain with the blur in front of the jitter: images, geometry (0 stretch, 1 window, 2 letterbox), B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1,
+    # tables, window, flips, jitter_order, jitter_factors, affine, mosaic_geom, mosaic_affine, blur (each null: off), fill3 (HOST), mean3, std3, out, ...
+    "sd_preprocess_blur_workspace_bytes": (c_size, [c_int] * 8),
+    "sd_preprocess_images_blur": (c_int, [c_vp] + [c_int] * 10 + [c_vp, c_vp, c_int, c_vp, c_vp, c_int] + [c_vp] * 8 +
+                                  [C.POINTER(C.c_ubyte), C.POINTER(c_float), C.POINTER(c_float), c_vp, c_vp, c_size, c_vp]),
+    "sd_preprocess_images_list_blur": (c_int, [c_vp] + [c_int] * 10 + [c_vp, c_vp, c_int, c_vp, c_vp, c_int] + [c_vp] * 8 +
+                                       [C.POINTER(C.c_ubyte), C.POINTER(c_float), C.POINTER(c_float), c_vp, c_vp, c_size, c_vp]),
     "sd_render_targets": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_float, c_vp, c_vp]),
     "sd_loss_workspace_bytes": (c_size, [c_int] * 5),
     "sd_loss_fwd": (c_int, [C.POINTER(LossDesc), c_vp, c_vp, c_size, c_vp]),

@@ -83,6 +83,10 @@ size_t head_wide_bwd_workspace_bytes(int64_t P, int C, int Co);
 int head_wide_wgrad(const float* dy, const float* x, float* partial, int B, int HW, int C, int Co, hipStream_t st, int& rows);
 int head_wide_dgrad(const float* dy, const float* w, float* dx, int B, int HW, int C, int Co, hipStream_t st);
 
+// Gaussian blur stage (sd_blur.hip): in -> mid -> out, each (B, H, W, 3) u8; mid differs from in and out, out may be in.  blur (B, 3)
+// int32 on the device.  Shapes are the caller's to check (B and cdiv(H, 64) are grid dimensions: <= 65535).
+int blur_stage(const uint8_t* in, uint8_t* mid, uint8_t* out, int B, int H, int W, const int* blur, hipStream_t st);
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);

@@ -776,6 +776,27 @@ __global__ __launch_bounds__(256) void k_letterbox_v_u8(const uint8_t* __restric
     dst[0] = (uint8_t)c.r; dst[1] = (uint8_t)c.g; dst[2] = (uint8_t)c.b;
 }
 
+// flips + to_tensor + Normalize of an 8-bit image: img (B, Hout, Wout, 3) u8 -> out (B, 3, Hout, Wout) fp32 NCHW.  The tail of the blur forms
+// without jitter (k_jitter_norm with neutral factors is not the identity on bytes: its float blends truncate); the expressions of
+// k_resample_v_norm on the byte.
+__global__ __launch_bounds__(256) void k_u8_norm(const uint8_t* __restrict__ img, float* __restrict__ out, int Hout, int Wout,
+                                                  const uint8_t* __restrict__ flips, float m0, float m1, float m2, float d0, float d1, float d2,
+                                                  int B) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t)B * Hout * Wout) return;
+    const int x = (int)(i % Wout);
+    const int64_t t = i / Wout;
+    const int y = (int)(t % Hout), b = (int)(t / Hout);
+    const int f = flips ? flips[b] : 0;
+    const int sx = (f & 1) ? Wout - 1 - x : x, sy = (f & 2) ? Hout - 1 - y : y;
+    const uint8_t* px = img + (((int64_t)b * Hout + sy) * Wout + sx) * 3;
+    const int64_t plane = (int64_t)Hout * Wout;
+    float* o = out + (int64_t)b * 3 * plane + (int64_t)y * Wout + x;
+    o[0] = ((float)px[0] / 255.0f - m0) / d0;
+    o[plane] = ((float)px[1] / 255.0f - m1) / d1;
+    o[2 * plane] = ((float)px[2] / 255.0f - m2) / d2;
+}
+
 }  // namespace sd
 
 using namespace sd;
@@ -1327,6 +1348,203 @@ int sd_preprocess_images_list_letterbox(const uint8_t* const* images, int B, int
     if (int e = resample_h_list(images, tmp, B, Hin, Win, Wi, h_bounds, h_kk, h_ksize, rpb, bpi, st)) return e;
     return letterbox_tail(B, Hin, Hi, Wi, Hout, Wout, y0, x0, v_bounds, v_kk, v_ksize, flips, jitter_order, jitter_factors, affine, mosaic_geom,
                           mosaic_affine, fill3, mean3, std3, out, tmp, st);
+}
+
+// ---- Gaussian blur between the warp and the jitter, behind any geometry (sd_blur.hip: blur_stage; k_u8_norm) ----
+// workspace: [horizontal intermediate | 8-bit image A | grey sums | 8-bit image B] with the intermediate of the geometry, i.e. the layout of
+// the mosaic, window and letterbox forms.  The 8-bit stages in front of the blur -- vertical pass [, mosaic] [, warp] -- alternate between
+// A and B so that the last of them writes A: the blur's horizontal direction then writes B and its vertical direction A, where the jitter
+// launches (and k_u8_norm) read.  No stage runs in place.
+size_t sd_preprocess_blur_workspace_bytes(int geometry, int B, int Hin, int Win, int Wg, int Hout, int Wout, int g0) {
+    if (geometry == SD_GEOM_WINDOW) return sd_preprocess_window_workspace_bytes(B, g0, Hout, Wout);
+    if (geometry == SD_GEOM_LETTERBOX) return sd_preprocess_letterbox_workspace_bytes(B, Hin, Wg, Hout, Wout);
+    return sd_preprocess_mosaic_workspace_bytes(B, Hin, Win, Hout, Wout);
+}
+
+// the blur forms proper (blur set): the checks of the geometry's entry point, its horizontal pass, its vertical pass into an 8-bit image,
+// the 8-bit stages, the blur, and the jitter or plain tail
+static int preprocess_blur(const char* what, bool list, const void* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout,
+                           int g0, int g1, const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize,
+                           const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors, const double* affine,
+                           const int* mosaic_geom, const double* mosaic_affine, const int* blur, const uint8_t* fill3, const float* mean3,
+                           const float* std3, float* out, void* workspace, size_t workspace_bytes, hipStream_t st) {
+    const uint8_t* packed = reinterpret_cast<const uint8_t*>(images);
+    const uint8_t* const* table = reinterpret_cast<const uint8_t* const*>(images);
+    int rpb = 0, bpi = 0;
+    size_t tmp_bytes = 0;
+    if (geometry == SD_GEOM_STRETCH) {
+        if (list) {
+            if (int e = preprocess_list_check(what, table, B, Hin, Win, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, mean3, std3, out,
+                                              workspace, &rpb, &bpi)) return e;
+        } else if (int e = preprocess_check(what, packed, B, Hin, Win, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, mean3, std3, out,
+                                            workspace)) return e;
+        SD_REQUIRE(!window, SD_ERR_INVALID, "%s: a window table needs SD_GEOM_WINDOW", what);
+        SD_REQUIRE((jitter_order == nullptr) == (jitter_factors == nullptr), SD_ERR_INVALID,
+                   "%s: jitter_order and jitter_factors go together (both null = no jitter)", what);
+        SD_REQUIRE((mosaic_geom == nullptr) == (mosaic_affine == nullptr), SD_ERR_INVALID,
+                   "%s: mosaic_geom and mosaic_affine go together (both null = no mosaic)", what);
+        SD_REQUIRE(fill3 || !(affine || mosaic_geom), SD_ERR_INVALID, "%s: a warp or a mosaic needs a fill colour", what);
+        SD_REQUIRE(workspace_bytes >= sd_preprocess_mosaic_workspace_bytes(B, Hin, Win, Hout, Wout), SD_ERR_WORKSPACE, "%s: workspace %zu < %zu", what,
+                   workspace_bytes, sd_preprocess_mosaic_workspace_bytes(B, Hin, Win, Hout, Wout));
+        tmp_bytes = sd_preprocess_workspace_bytes(B, Hin, Win, Wout);
+    } else if (geometry == SD_GEOM_WINDOW) {
+        if (int e = window_check(what, packed, B, Hin, Win, Hg, Wg, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, window, g0, g1,
+                                 jitter_order, jitter_factors, affine, mosaic_geom, mosaic_affine, fill3, mean3, std3, out, workspace, workspace_bytes))
+            return e;
+        if (list) {
+            SD_REQUIRE((int64_t)g1 * 3 + 32 <= HL_LDS_BYTES, SD_ERR_INVALID,
+                       "%s: a column span of %d source pixels exceeds the LDS staging buffer (at most %d)", what, g1, (HL_LDS_BYTES - 32) / 3);
+            rpb = (int)std::min<int64_t>(HL_ROWS, (HL_LDS_BYTES - 32) / ((int64_t)g1 * 3));
+            bpi = cdiv(g0, rpb);
+            SD_REQUIRE((int64_t)B * bpi < (1ll << 31), SD_ERR_INVALID, "%s: batch too large", what);
+        }
+        tmp_bytes = sd_preprocess_workspace_bytes(B, g0, 0, Wout);
+    } else if (geometry == SD_GEOM_LETTERBOX) {
+        SD_REQUIRE(!window, SD_ERR_INVALID, "%s: a window table needs SD_GEOM_WINDOW", what);
+        if (int e = letterbox_check(what, packed, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, jitter_order,
+                                    jitter_factors, affine, mosaic_geom, mosaic_affine, fill3, mean3, std3, out, workspace, workspace_bytes)) return e;
+        if (list) {
+            SD_REQUIRE((int64_t)Win * 3 + 32 <= HL_LDS_BYTES, SD_ERR_INVALID, "%s: source rows of %d pixels exceed the LDS staging buffer (at most %d)",
+                       what, Win, (HL_LDS_BYTES - 32) / 3);
+            rpb = (int)std::min<int64_t>(HL_ROWS, (HL_LDS_BYTES - 32) / ((int64_t)Win * 3));
+            bpi = cdiv(Hin, rpb);
+            SD_REQUIRE((int64_t)B * bpi < (1ll << 31), SD_ERR_INVALID, "%s: batch too large", what);
+        }
+        tmp_bytes = align_up((size_t)B * Hin * Wg * 3, 256);
+    } else {
+        SD_REQUIRE(false, SD_ERR_INVALID, "%s: unknown geometry %d", what, geometry);
+    }
+    SD_REQUIRE(B <= 65535 && Hout <= 65535 * 64, SD_ERR_INVALID, "%s: batch %d > 65535 or frame too tall", what, B);
+
+    uint8_t* tmp = reinterpret_cast<uint8_t*>(workspace);
+    const size_t frame = align_up((size_t)B * Hout * Wout * 3, 256);
+    uint8_t* img_a = tmp + tmp_bytes;
+    unsigned long long* lsum = reinterpret_cast<unsigned long long*>(img_a + frame);
+    uint8_t* img_b = img_a + frame + align_up((size_t)B * 8, 256);
+    if (jitter_order) SD_HIP(hipMemsetAsync(lsum, 0, (size_t)B * 8, st));
+    const int before = 1 + (mosaic_geom ? 1 : 0) + (affine ? 1 : 0);     // 8-bit images written in front of the blur; the last one is A
+    int k = 0;
+    auto next = [&]() { return ((before - 1 - k++) & 1) ? img_b : img_a; };
+    uint8_t* cur = next();
+    const dim3 flat(cdiv((int64_t)B * Hout * Wout, 256));
+    const int f0 = fill3 ? fill3[0] : 0, f1 = fill3 ? fill3[1] : 0, f2 = fill3 ? fill3[2] : 0;
+    if (geometry == SD_GEOM_STRETCH) {
+        if (list) {
+            if (int e = resample_h_list(table, tmp, B, Hin, Win, Wout, h_bounds, h_kk, h_ksize, rpb, bpi, st)) return e;
+        } else {
+            const int64_t rows = (int64_t)B * Hin;
+            hipLaunchKernelGGL(k_resample_h, dim3(cdiv(rows * Wout, 256)), dim3(256), 0, st, packed, tmp, Hin, Win, Wout, h_bounds, h_kk, h_ksize, rows);
+            SD_LAUNCH_CHECK();
+        }
+        if (int e = resample_v_u8(B, Hin, Hout, Wout, v_bounds, v_kk, v_ksize, tmp, cur, st)) return e;
+    } else if (geometry == SD_GEOM_WINDOW) {
+        if (list)
+            hipLaunchKernelGGL(k_window_h_list, dim3((unsigned)((int64_t)B * bpi)), dim3(256), (size_t)rpb * g1 * 3 + 32, st, table, tmp, Win, Hg, Wg, Hout,
+                               Wout, h_bounds, h_kk, h_ksize, v_bounds, window, g0, g1, rpb, bpi);
+        else
+            hipLaunchKernelGGL(k_window_h, dim3(cdiv((int64_t)B * g0 * Wout, 256)), dim3(256), 0, st, packed, tmp, Hin, Win, Hg, Wg, Hout, Wout, h_bounds,
+                               h_kk, h_ksize, v_bounds, window, g0, B);
+        SD_LAUNCH_CHECK();
+        hipLaunchKernelGGL(k_window_v_u8, flat, dim3(256), 0, st, tmp, cur, Hg, Wg, Hout, Wout, v_bounds, v_kk, v_ksize, window, g0, B);
+        SD_LAUNCH_CHECK();
+    } else {
+        if (list) {
+            if (int e = resample_h_list(table, tmp, B, Hin, Win, Wg, h_bounds, h_kk, h_ksize, rpb, bpi, st)) return e;
+        } else {
+            const int64_t rows = (int64_t)B * Hin;
+            hipLaunchKernelGGL(k_resample_h, dim3(cdiv(rows * Wg, 256)), dim3(256), 0, st, packed, tmp, Hin, Win, Wg, h_bounds, h_kk, h_ksize, rows);
+            SD_LAUNCH_CHECK();
+        }
+        hipLaunchKernelGGL(k_letterbox_v_u8, flat, dim3(256), 0, st, tmp, cur, Hin, Hg, Wg, Hout, Wout, g0, g1, v_bounds, v_kk, v_ksize, f0, f1, f2, B);
+        SD_LAUNCH_CHECK();
+    }
+    const dim3 grid(cdiv(Wout, AF_TX * AF_PX), cdiv(Hout, AF_TY), B);
+    if (mosaic_geom) {
+        uint8_t* dst = next();
+        hipLaunchKernelGGL(k_mosaic_u8, grid, dim3(256), 0, st, cur, dst, Hout, Wout, mosaic_geom, mosaic_affine, f0, f1, f2);
+        SD_LAUNCH_CHECK();
+        cur = dst;
+    }
+    if (affine) {
+        uint8_t* dst = next();
+        hipLaunchKernelGGL(k_affine_u8, grid, dim3(256), 0, st, cur, dst, Hout, Wout, affine, f0, f1, f2);
+        SD_LAUNCH_CHECK();
+        cur = dst;
+    }
+    if (int e = blur_stage(cur, img_b, img_a, B, Hout, Wout, blur, st)) return e;      // cur == img_a
+    if (jitter_order) return jitter_norm(B, Hout, Wout, flips, jitter_order, jitter_factors, mean3, std3, out, img_a, lsum, st);
+    hipLaunchKernelGGL(k_u8_norm, flat, dim3(256), 0, st, img_a, out, Hout, Wout, flips, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], B);
+    SD_LAUNCH_CHECK();
+    return 0;
+}
+
+int sd_preprocess_images_blur(const uint8_t* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout, int g0, int g1,
+                              const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize,
+                              const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
+                              const double* affine, const int* mosaic_geom, const double* mosaic_affine, const int* blur, const uint8_t* fill3,
+                              const float* mean3, const float* std3, float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
+    const char* what = "sd_preprocess_images_blur";
+    if (blur)
+        return preprocess_blur(what, false, images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
+                               window, flips, jitter_order, jitter_factors, affine, mosaic_geom, mosaic_affine, blur, fill3, mean3, std3, out, workspace,
+                               workspace_bytes, (hipStream_t)stream);
+    if (geometry == SD_GEOM_WINDOW)
+        return sd_preprocess_images_window(images, B, Hin, Win, Hg, Wg, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, window, g0, g1, flips,
+                                           jitter_order, jitter_factors, affine, mosaic_geom, mosaic_affine, fill3, mean3, std3, out, workspace,
+                                           workspace_bytes, stream);
+    if (geometry == SD_GEOM_LETTERBOX)
+        return sd_preprocess_images_letterbox(images, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, flips,
+                                              jitter_order, jitter_factors, affine, mosaic_geom, mosaic_affine, fill3, mean3, std3, out, workspace,
+                                              workspace_bytes, stream);
+    SD_REQUIRE(geometry == SD_GEOM_STRETCH, SD_ERR_INVALID, "%s: unknown geometry %d", what, geometry);
+    SD_REQUIRE((jitter_order == nullptr) == (jitter_factors == nullptr), SD_ERR_INVALID,
+               "%s: jitter_order and jitter_factors go together (both null = no jitter)", what);
+    if (mosaic_geom || mosaic_affine)
+        return sd_preprocess_images_mosaic(images, B, Hin, Win, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, flips, jitter_order,
+                                           jitter_factors, affine, mosaic_geom, mosaic_affine, fill3, mean3, std3, out, workspace, workspace_bytes, stream);
+    if (affine)
+        return sd_preprocess_images_affine(images, B, Hin, Win, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, flips, jitter_order,
+                                           jitter_factors, affine, fill3, mean3, std3, out, workspace, workspace_bytes, stream);
+    if (jitter_order)
+        return sd_preprocess_images_jitter(images, B, Hin, Win, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, flips, jitter_order,
+                                           jitter_factors, mean3, std3, out, workspace, workspace_bytes, stream);
+    return sd_preprocess_images(images, B, Hin, Win, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, flips, mean3, std3, out, workspace,
+                                workspace_bytes, stream);
+}
+
+int sd_preprocess_images_list_blur(const uint8_t* const* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout,
+                                   int g0, int g1, const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk,
+                                   int v_ksize, const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
+                                   const double* affine, const int* mosaic_geom, const double* mosaic_affine, const int* blur, const uint8_t* fill3,
+                                   const float* mean3, const float* std3, float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
+    const char* what = "sd_preprocess_images_list_blur";
+    if (blur)
+        return preprocess_blur(what, true, images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
+                               window, flips, jitter_order, jitter_factors, affine, mosaic_geom, mosaic_affine, blur, fill3, mean3, std3, out, workspace,
+                               workspace_bytes, (hipStream_t)stream);
+    if (geometry == SD_GEOM_WINDOW)
+        return sd_preprocess_images_list_window(images, B, Hin, Win, Hg, Wg, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, window, g0, g1,
+                                                flips, jitter_order, jitter_factors, affine, mosaic_geom, mosaic_affine, fill3, mean3, std3, out, workspace,
+                                                workspace_bytes, stream);
+    if (geometry == SD_GEOM_LETTERBOX)
+        return sd_preprocess_images_list_letterbox(images, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, flips,
+                                                   jitter_order, jitter_factors, affine, mosaic_geom, mosaic_affine, fill3, mean3, std3, out, workspace,
+                                                   workspace_bytes, stream);
+    SD_REQUIRE(geometry == SD_GEOM_STRETCH, SD_ERR_INVALID, "%s: unknown geometry %d", what, geometry);
+    SD_REQUIRE((jitter_order == nullptr) == (jitter_factors == nullptr), SD_ERR_INVALID,
+               "%s: jitter_order and jitter_factors go together (both null = no jitter)", what);
+    if (mosaic_geom || mosaic_affine)
+        return sd_preprocess_images_list_mosaic(images, B, Hin, Win, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, flips, jitter_order,
+                                                jitter_factors, affine, mosaic_geom, mosaic_affine, fill3, mean3, std3, out, workspace, workspace_bytes,
+                                                stream);
+    if (affine)
+        return sd_preprocess_images_list_affine(images, B, Hin, Win, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, flips, jitter_order,
+                                                jitter_factors, affine, fill3, mean3, std3, out, workspace, workspace_bytes, stream);
+    if (jitter_order)
+        return sd_preprocess_images_list_jitter(images, B, Hin, Win, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, flips, jitter_order,
+                                                jitter_factors, mean3, std3, out, workspace, workspace_bytes, stream);
+    return sd_preprocess_images_list(images, B, Hin, Win, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, flips, mean3, std3, out, workspace,
+                                     workspace_bytes, stream);
 }
 
 }  // extern "C"

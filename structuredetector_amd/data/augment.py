@@ -28,6 +28,9 @@ Letterbox (`--keep_aspect`; not in the reference): the Resize keeps the source's
 pass at width wi, then one vertical pass that writes image and bars); every later stage works on the frame, the annotations follow with
 `ann.resize` to the inner image and a shift by (px, py) that drops nothing (`utils.misc.letterbox_annotation`'s rule);
 `utils.misc.unletterbox_annotation` is the way back.
+Blur (`--aug_blur R`; not in the reference): between the warp and the ColorJitter, a selected image is `Image.filter(GaussianBlur(r))`
+byte for byte -- Pillow's six rounded box-blur passes in integer arithmetic (`sd_blur_u8`; in the chain `sd_preprocess_images_blur`); the
+box radius and weights of a pass are float32 arithmetic restated on the host (`blur_box_params`).  Photometric: annotations are untouched.
 Transpose (`--aug_transpose P`; not in the reference): last, after the flips, a selected image of the assembled (square) batch has its x and
 y swapped (`sd_transpose_select`, one launch: lossless, with the flips the eight symmetries of the grid); the annotations follow with
 `utils.misc.transpose_annotation`.
@@ -275,8 +278,97 @@ def _preprocess_letterbox(fn_name, source, B, Hin, Win, out_size, flips, mean, s
     return out
 
 
+def blur_box_params(r):
+    """(R, ww, fw) of Pillow's `GaussianBlur(r)` (libImaging/BoxBlur.c: _gaussian_blur_radius, ImagingLineBoxBlur8): the whole box radius
+    and the 24-bit weights of a whole pixel and of the two edge pixels of one pass, one row of `sd_blur_u8`'s table.  Pillow computes them in
+    float32 -- every operation below rounds to float32, only `sqrt` and `floor` take doubles as in C -- and the weight of a whole pixel is a
+    float32 division truncated to uint32; double arithmetic changes bytes (r = 0.3, 0.7, 1.0).  r = 0 gives (0, 2^24, 0): a copy."""
+    f = np.float32
+    r = f(r)
+    if not 0 <= r <= 8:
+        raise ValueError(f"blur radius should be in [0, 8], not {r}")
+    s2 = f(f(r * r) / f(3))
+    ll = f(math.sqrt(12.0 * float(s2) + 1.0))
+    l = f(math.floor((float(ll) - 1.0) / 2.0))
+    a = f(f(f(2) * l + f(1)) * f(f(l * f(l + f(1))) - f(f(3) * s2)))
+    a = f(a / f(f(6) * f(s2 - f(f(l + f(1)) * f(l + f(1))))))
+    fr = f(l + a)
+    R = int(fr)
+    ww = int(f(1 << 24) / f(fr * f(2) + f(1)))
+    return R, ww, ((1 << 24) - (2 * R + 1) * ww) // 2
+
+
+def _blur_rows(blur, B, device):
+    rows = torch.as_tensor(np.asarray(blur, dtype=np.int64).astype(np.int32)).reshape(-1, 3).contiguous()
+    if rows.shape[0] != B:
+        raise L.SdError("blur must have one row (R, ww, fw) per image")
+    return rows.to(device, non_blocking=True)
+
+
+def blur_images(images: torch.Tensor, blur) -> torch.Tensor:
+    """images: (B, H, W, 3) uint8 on the GPU; blur: B rows (R, ww, fw) as `blur_box_params` makes them.  Returns a new tensor, image b =
+    `Image.filter(ImageFilter.GaussianBlur(r_b))` byte for byte (`sd_blur_u8`: the stand-alone stage of the chain)."""
+    L.require_cuda(images)
+    if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3:
+        raise L.SdError(f"blur_images expects (B, H, W, 3) uint8, got {tuple(images.shape)} {images.dtype}")
+    images = images.contiguous()
+    B, H, W, _ = images.shape
+    rows = _blur_rows(blur, B, images.device)
+    out = torch.empty_like(images)
+    lib = L.lib()
+    ws = L.workspace(lib.sd_blur_workspace_bytes(B, H, W), images.device)
+    L.check(lib.sd_blur_u8(images.data_ptr(), out.data_ptr(), B, H, W, rows.data_ptr(), ws.data_ptr(), ws.numel(), L.stream()), "sd_blur_u8")
+    return out
+
+
+GEOM_STRETCH, GEOM_WINDOW, GEOM_LETTERBOX = 0, 1, 2                  # include/sdnet_hip.h SD_GEOM_*
+
+
+def _preprocess_blur(fn_name, source, B, Hin, Win, out_size, flips, mean, std, jitter, affine, mosaic, window, letterbox, blur, dev):
+    """The blur forms of `preprocess_images` / `preprocess_image_list` (`sd_preprocess_images_blur` / `..._list_blur`): any geometry, every
+    optional stage, the blur between the warp and the jitter.  source = the address of the packed images or of the pointer table."""
+    Wout, Hout = int(out_size[0]), int(out_size[1])
+    geometry, Hg, Wg, g0, g1, org = GEOM_STRETCH, 0, 0, 0, 0, None
+    if letterbox is not None:
+        if window is not None:
+            raise L.SdError("preprocess: a letterbox and a window do not combine")
+        wi, hi, px, py = (int(v) for v in letterbox)
+        if wi <= 0 or hi <= 0:
+            raise L.SdError(f"letterbox: the inner image should be at least 1 x 1, not {wi} x {hi}")
+        geometry, Hg, Wg, g0, g1 = GEOM_LETTERBOX, hi, wi, py, px
+        hb, hk, hks = _tables.get(Win, wi, dev)
+        vb, vk, vks = _tables.get(Hin, hi, dev)
+    elif window is not None:
+        (Wc, Hc), origins = window
+        Wc, Hc = int(Wc), int(Hc)
+        if not (0 < Wout <= Wc and 0 < Hout <= Hc):
+            raise L.SdError(f"window: {Wout} x {Hout} does not fit the canvas {Wc} x {Hc}")
+        org = torch.as_tensor(np.asarray(origins, dtype=np.int32)).reshape(-1, 2).contiguous()
+        if org.shape[0] != B:
+            raise L.SdError("window must have one origin (x0, y0) per image")
+        org = org.to(dev, non_blocking=True)
+        geometry, Hg, Wg = GEOM_WINDOW, Hc, Wc
+        g1, g0 = window_extents(Win, Wc, Wout), window_extents(Hin, Hc, Hout)
+        hb, hk, hks = _tables.get(Win, Wc, dev)
+        vb, vk, vks = _tables.get(Hin, Hc, dev)
+    else:
+        hb, hk, hks = _tables.get(Win, Wout, dev)
+        vb, vk, vks = _tables.get(Hin, Hout, dev)
+    out = torch.empty((B, 3, Hout, Wout), dtype=torch.float32, device=dev)
+    fl, order, factors, rows, geom, mats = _stage_tables(B, flips, jitter, affine, mosaic, dev)
+    bl = None if blur is None else _blur_rows(blur, B, dev)          # (None: the library runs the geometry's existing entry point)
+    ptr = lambda t: t.data_ptr() if t is not None else 0
+    lib = L.lib()
+    ws = L.workspace(lib.sd_preprocess_blur_workspace_bytes(geometry, B, Hin, Win, Wg, Hout, Wout, g0), dev)
+    L.check(getattr(lib, fn_name)(source, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, hb.data_ptr(), hk.data_ptr(), hks, vb.data_ptr(),
+                                  vk.data_ptr(), vks, ptr(org), ptr(fl), ptr(order), ptr(factors), ptr(rows), ptr(geom), ptr(mats), ptr(bl),
+                                  (C.c_ubyte * 3)(*_FILL), (C.c_float * 3)(*mean), (C.c_float * 3)(*std), out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                  L.stream()), fn_name)
+    return out
+
+
 def preprocess_images(images: torch.Tensor, out_size, flips=None, mean=_MEAN, std=_STD, jitter=None, affine=None, mosaic=None,
-                      window=None, letterbox=None) -> torch.Tensor:
+                      window=None, letterbox=None, blur=None) -> torch.Tensor:
     """images: (B, Hin, Win, 3) uint8 on the GPU; out_size = (width, height); flips: (B,) uint8 (bit 0 horizontal, bit 1 vertical)
     or None; jitter: None or (order words (B,) int32, factors (B, 3) fp32) as `jitter_words` makes them; affine: None or B rows of the 6
     coefficients of `affine_inverse_matrix` at out_size (the warp runs on the resized image, in front of the jitter, fill `_FILL`); mosaic:
@@ -285,13 +377,18 @@ def preprocess_images(images: torch.Tensor, out_size, flips=None, mean=_MEAN, st
     (x0, y0)): the resize targets the canvas and only its out_size window at the origin is produced (`sd_preprocess_images_window`;
     origins are clamped into the canvas on the device), every later stage works on that window; letterbox: None or (wi, hi, px, py) as
     `letterbox_geometry` gives them: the resize targets wi x hi and the result is pasted at (px, py) into an out_size frame of `_FILL`
-    (`sd_preprocess_images_letterbox`), every later stage works on that frame (not together with `window`).
-    Returns (B, 3, height, width) fp32 = Normalize(to_tensor(flip(jitter(affine(mosaic(resize(image))))))) of transforms.py:217-226."""
+    (`sd_preprocess_images_letterbox`), every later stage works on that frame (not together with `window`); blur: None or B rows
+    (R, ww, fw) as `blur_box_params` makes them: Pillow's GaussianBlur after the warp, in front of the jitter
+    (`sd_preprocess_images_blur`, chosen only when blur is set; a row of r = 0 leaves its image as it is).
+    Returns (B, 3, height, width) fp32 = Normalize(to_tensor(flip(jitter(blur(affine(mosaic(resize(image)))))))) of transforms.py:217-226."""
     L.require_cuda(images)
     if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3:
         raise L.SdError(f"preprocess_images expects (B, H, W, 3) uint8, got {tuple(images.shape)} {images.dtype}")
     images = images.contiguous()
     B, Hin, Win, _ = images.shape
+    if blur is not None:
+        return _preprocess_blur("sd_preprocess_images_blur", images.data_ptr(), B, Hin, Win, out_size, flips, mean, std, jitter, affine, mosaic,
+                                window, letterbox, blur, images.device)
     if letterbox is not None:
         if window is not None:
             raise L.SdError("preprocess_images: a letterbox and a window do not combine")
@@ -351,7 +448,7 @@ def preprocess_images(images: torch.Tensor, out_size, flips=None, mean=_MEAN, st
 
 
 def preprocess_image_list(pointers: torch.Tensor, hin: int, win: int, out_size, flips=None, mean=_MEAN, std=_STD, jitter=None,
-                          affine=None, mosaic=None, window=None, letterbox=None) -> torch.Tensor:
+                          affine=None, mosaic=None, window=None, letterbox=None, blur=None) -> torch.Tensor:
     """`preprocess_images` over B images that are not packed together: pointers is a (B,) int64 DEVICE tensor of the device addresses of
     B (hin, win, 3) uint8 images (any byte alignment; the caller keeps them alive until the work on the current stream is done), e.g. entries
     of data/image_cache.py's DeviceImageCache.  Same arguments otherwise, same output bytes as `preprocess_images` on the stacked images."""
@@ -361,6 +458,9 @@ def preprocess_image_list(pointers: torch.Tensor, hin: int, win: int, out_size, 
     pointers = pointers.contiguous()
     dev = pointers.device
     B, Hin, Win = pointers.numel(), int(hin), int(win)
+    if blur is not None:
+        return _preprocess_blur("sd_preprocess_images_list_blur", pointers.data_ptr(), B, Hin, Win, out_size, flips, mean, std, jitter, affine,
+                                mosaic, window, letterbox, blur, dev)
     if letterbox is not None:
         if window is not None:
             raise L.SdError("preprocess_image_list: a letterbox and a window do not combine")
@@ -481,6 +581,10 @@ class ValidationAugmentation:
         """n flags (1 = the sample is transposed) or None: validation never transposes and never draws."""
         return None
 
+    def blur_draws_for(self, n):
+        """n gaussian radii (0.0 = the sample stays sharp) or None: validation never blurs and never draws."""
+        return None
+
     @staticmethod
     def size_groups(images):
         """{(hin, win): (indices into the batch, stack of those images)} of what `__call__` accepts as `images`."""
@@ -529,6 +633,7 @@ class ValidationAugmentation:
         mosaics = self.mosaic_draws_for(n, [idx for idx, _ in groups.values()])
         windows = self.window_draws_for(n)
         transposes = self.transpose_draws_for(n)
+        blurs = self.blur_draws_for(n)
         if transposes is not None and W != H:
             raise L.SdError(f"aug_transpose: a transposed sample needs a square batch, not {W} x {H}")
         if windows is not None and self.keep_aspect:
@@ -545,6 +650,8 @@ class ValidationAugmentation:
                 kw["mosaic"] = ([[*tiles[i][0][:2], *(where[s] for s in tiles[i][0][2:])] for i in idx], [tiles[i][1] for i in idx])
             if windows is not None:
                 kw["window"] = (windows[0], [windows[1][i] for i in idx])
+            if blurs is not None:                                    # photometric: the annotations do not move
+                kw["blur"] = [blur_box_params(blurs[i]) for i in idx]
             box = None
             if self.keep_aspect:                                     # one geometry per size group, at the current (multi-scale) size
                 box = kw["letterbox"] = letterbox_geometry((win, hin), (W, H))
@@ -610,6 +717,7 @@ class TrainAugmentation(ValidationAugmentation):
         self.translate = float(getattr(args, "aug_translate", 0.0))        # shift uniform in [-translate, translate] * (width, height)
         self.mosaic = float(getattr(args, "aug_mosaic", 0.0))              # per-image probability of becoming a mosaic of four
         self.transpose = float(getattr(args, "aug_transpose", 0.0))        # per-image probability of being transposed (square sizes only)
+        self.blur = float(getattr(args, "aug_blur", 0.0) or 0.0)           # gaussian radius uniform in [0, blur] pixels for a selected image
         self.train_tiles = parse_tiles(getattr(args, "train_tiles", ""), "train_tiles")   # (Tx, Ty) of the canvas the windows are cut from, () = off
         self.tile_overlap = int(getattr(args, "tile_overlap", 64))
 
@@ -683,6 +791,16 @@ class TrainAugmentation(ValidationAugmentation):
         if self.args.no_augmentation or self.transpose == 0:
             return None
         return (torch.rand(n, dtype=torch.float64) < self.transpose).to(torch.uint8).tolist()
+
+    def blur_draws_for(self, n):
+        """n gaussian radii from ONE more draw on torch's global generator, `rand(n, 2)` in float64, made after that of
+        `transpose_draws_for`: sample i is blurred when u0 < `prob`, with r = R * u1 in pixels of the current network input size (the same
+        blur at every multi-scale size), else its radius is 0.0 (a copy row of the table).  None, and no draw at all, with `--aug_blur 0`
+        or augmentation off."""
+        if self.args.no_augmentation or self.blur == 0:
+            return None
+        u = torch.rand(n, 2, dtype=torch.float64).tolist()
+        return [self.blur * u1 if u0 < self.prob else 0.0 for u0, u1 in u]
 
     def trigger_random_resize(self):
         if self.args.no_augmentation:

@@ -131,6 +131,11 @@ _FLAGS = [
                                 "image is transposed (x and y swapped: a lossless quarter turn with the flips, no resampling and no fill), "
                                 "after the flips. Needs a square network input (--width equal to --height). Not consulted by evaluate / "
                                 "detect.")),
+    (("--aug_blur",), dict(type=float, default=0.0, metavar="R", help="Training augmentation: with the flip probability's threshold "
+                           "(u < 0.5) an image is blurred by Pillow's GaussianBlur with a radius uniform in [0, R] pixels of the current "
+                           "network input size (0 <= R <= 8: the same physical blur at every multi-scale size; motion / defocus blur of "
+                           "deployment frames), after the warp and before the colour jitter; annotations are untouched. Needs a directory "
+                           "(not --synthetic). Not consulted by evaluate / detect. 0 = off.")),
 ]
 
 _POSITIVE = ["in_channels", "fpn_depth", "batch_size", "epochs", "learning_rate", "down_ratio", "max_objects", "max_parts"]
@@ -269,6 +274,20 @@ def check_aug_transpose(args):
     return p
 
 
+MAX_AUG_BLUR = 8.0                  # pixels: the gaussian radius whose box radius is SD_BLUR_MAX_RADIUS (include/sdnet_hip.h)
+
+
+def check_aug_blur(args):
+    """`--aug_blur` on a parsed namespace -> R, as `train` checks it (model/trainer.py): a radius in [0, 8]; `--synthetic` renders
+    network-input tensors and has no 8-bit image to blur, so the flag is refused there."""
+    r = float(getattr(args, "aug_blur", 0.0) or 0.0)
+    if not 0 <= r <= MAX_AUG_BLUR:                                   # (also false for nan)
+        raise ValueError(f"'aug_blur' should be in [0, {MAX_AUG_BLUR:g}] pixels (0 = off), not {r}")
+    if r > 0 and getattr(args, "synthetic", 0):
+        raise ValueError("'aug_blur' blurs source images: it needs --train_dir, not --synthetic")
+    return r
+
+
 def finalize(args):
     """Validation + derived fields (args.py:178-269) on an already parsed namespace."""
     for side in ("width", "height"):
@@ -290,6 +309,7 @@ def finalize(args):
     assert 0 <= getattr(args, "aug_translate", 0.0) <= 0.5, "'aug_translate' should be in [0, 0.5]"
     assert 0 <= getattr(args, "aug_mosaic", 0.0) <= 1, "'aug_mosaic' should be in [0, 1]"
     assert 0 <= getattr(args, "aug_transpose", 0.0) <= 1, "'aug_transpose' should be in [0, 1]"
+    assert 0 <= getattr(args, "aug_blur", 0.0) <= MAX_AUG_BLUR, "'aug_blur' should be in [0, 8]"
     args.label_nms = check_label_nms(getattr(args, "label_nms", 0))
     args.tta_scales = parse_tta_scales(getattr(args, "tta_scales", ""))
     args.tiles = parse_tiles(getattr(args, "tiles", ""))
