@@ -505,7 +505,36 @@ int sd_preprocess_images_list_blur(const uint8_t* const* images, int geometry, i
                                    const uint8_t fill3[3], const float* mean3, const float* std3, float* out, void* workspace,
                                    size_t workspace_bytes, sd_stream_t stream);
 
-/* ---- loss: src/sdnet/model/loss.py:17-64,91-117 ------------------------------------------- */
+/* Random perspective of 8-bit images (training augmentation, `train --aug_perspective`): image b becomes
+ * Image.transform((W, H), PERSPECTIVE, coeffs_b, BILINEAR, fillcolor=fill3) byte for byte.  coeffs (B, 8) fp64 on the DEVICE = a0 .. a7:
+ * with xc = x + 0.5, yc = y + 0.5 the output pixel (x, y) samples the source position
+ *     den = a6 xc + a7 yc + 1,  xin = (a0 xc + a1 yc + a2) / den,  yin = (a3 xc + a4 yc + a5) / den
+ * (every product and sum rounded on its own, left to right; two correctly rounded fp64 divisions) exactly as the affine warp samples its
+ * position: the inside test, the -0.5 shift, floor, clamped taps, the double lerp, truncation to a byte.  A position that is infinite or
+ * NaN is outside and becomes fill; where den is negative a position inside the source is sampled, as in Pillow.  A row with a6 = a7 = 0
+ * gives the bytes of the affine warp with the same six coefficients.  Nothing in a row is validated: index clamps bound every address for
+ * any table.  in and out are (B, H, W, 3) uint8 and must not overlap; fill3 is a HOST pointer.  B <= 65535. */
+int sd_perspective_u8(const uint8_t* in, uint8_t* out, int B, int H, int W, const double* coeffs, const uint8_t fill3[3], sd_stream_t stream);
+
+/* The blur forms with the perspective in the warp slot:
+ *     Resize | Window | Letterbox -> [Mosaic] -> Perspective -> [Blur] -> [ColorJitter] -> flips -> Normalize.
+ * The arguments of sd_preprocess_images_blur / _list_blur plus persp (B, 8) fp64 on the device after affine.  With persp null the call IS
+ * the blur form.  With persp set, affine must be null (SD_ERR_INVALID: the host folds the affine matrix into the homography, so an image
+ * is resampled once), fill3 is needed and blur may be null.  workspace: sd_preprocess_blur_workspace_bytes() bytes, the same layout. */
+int sd_preprocess_images_persp(const uint8_t* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout, int g0, int g1,
+                               const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize,
+                               const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
+                               const double* affine, const double* persp, const int* mosaic_geom, const double* mosaic_affine, const int* blur,
+                               const uint8_t fill3[3], const float* mean3, const float* std3, float* out, void* workspace,
+                               size_t workspace_bytes, sd_stream_t stream);
+int sd_preprocess_images_list_persp(const uint8_t* const* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout,
+                                    int g0, int g1, const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk,
+                                    int v_ksize, const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
+                                    const double* affine, const double* persp, const int* mosaic_geom, const double* mosaic_affine,
+                                    const int* blur, const uint8_t fill3[3], const float* mean3, const float* std3, float* out, void* workspace,
+                                    size_t workspace_bytes, sd_stream_t stream);
+
+/* ---- loss: src/sdnet/model/loss.py:17-64,91-117------------------------------------------- */
 
 #define SD_HM_MSE   0
 #define SD_HM_FOCAL 1

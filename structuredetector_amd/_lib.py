@@ -136,6 +136,13 @@ _SIGNATURES = {
                                   [C.POINTER(C.c_ubyte), C.POINTER(c_float), C.POINTER(c_float), c_vp, c_vp, c_size, c_vp]),
     "sd_preprocess_images_list_blur": (c_int, [c_vp] + [c_int] * 10 + [c_vp, c_vp, c_int, c_vp, c_vp, c_int] + [c_vp] * 8 +
                                        [C.POINTER(C.c_ubyte), C.POINTER(c_float), C.POINTER(c_float), c_vp, c_vp, c_size, c_vp]),
+    # random perspective of 8-bit images: in, out, B, H, W, coeffs (B, 8) fp64 device, fill3 (HOST), stream
+    "sd_perspective_u8": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, C.POINTER(C.c_ubyte), c_vp]),
+    # the blur forms with persp (B, 8) fp64 device after affine (null: the blur form; set: affine must be null)
+    "sd_preprocess_images_persp": (c_int, [c_vp] + [c_int] * 10 + [c_vp, c_vp, c_int, c_vp, c_vp, c_int] + [c_vp] * 9 +
+                                   [C.POINTER(C.c_ubyte), C.POINTER(c_float), C.POINTER(c_float), c_vp, c_vp, c_size, c_vp]),
+    "sd_preprocess_images_list_persp": (c_int, [c_vp] + [c_int] * 10 + [c_vp, c_vp, c_int, c_vp, c_vp, c_int] + [c_vp] * 9 +
+                                        [C.POINTER(C.c_ubyte), C.POINTER(c_float), C.POINTER(c_float), c_vp, c_vp, c_size, c_vp]),
     "sd_render_targets": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_float, c_vp, c_vp]),
     "sd_loss_workspace_bytes": (c_size, [c_int] * 5),
     "sd_loss_fwd": (c_int, [C.POINTER(LossDesc), c_vp, c_vp, c_size, c_vp]),

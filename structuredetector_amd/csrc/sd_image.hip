@@ -309,12 +309,10 @@ __device__ __forceinline__ void affine_row(const uint8_t* __restrict__ row, int 
     }
 }
 
-// one output pixel (x, y) of an (H, W, 3) image: Pillow's affine_transform + bilinear_filter32RGB
-__device__ __forceinline__ Rgb8 affine_pixel(const uint8_t* __restrict__ src, int H, int W, const Affine6& m, int x, int y, const Rgb8& fill) {
-    const double xc = (double)x + 0.5, yc5 = (double)y + 0.5;
-    double xin = m.m0 * xc + m.m1 * yc5 + m.m2;
-    double yin = m.m3 * xc + m.m4 * yc5 + m.m5;
-    if (!(xin >= 0.0 && xin < (double)W && yin >= 0.0 && yin < (double)H)) return fill;       // (a NaN is outside too)
+// the source position (xin, yin) of an (H, W, 3) image sampled as Pillow's bilinear_filter32RGB does; what lies outside is fill.  Shared
+// by the affine and the projective form of the source-position arithmetic below.
+__device__ __forceinline__ Rgb8 sample_bilinear(const uint8_t* __restrict__ src, int H, int W, double xin, double yin, const Rgb8& fill) {
+    if (!(xin >= 0.0 && xin < (double)W && yin >= 0.0 && yin < (double)H)) return fill;       // (a NaN or an infinity is outside too)
     xin -= 0.5; yin -= 0.5;
     const double fx = floor(xin), fy = floor(yin);
     const double dx = xin - fx, dy = yin - fy;
@@ -333,6 +331,27 @@ __device__ __forceinline__ Rgb8 affine_pixel(const uint8_t* __restrict__ src, in
         o[c] = (int)(v1 + (v2 - v1) * dy) & 255;                         // (UINT8) of a value in [0, 255]
     }
     return Rgb8{o[0], o[1], o[2]};
+}
+
+// one output pixel (x, y): Pillow's affine_transform, then the sampling
+__device__ __forceinline__ Rgb8 affine_pixel(const uint8_t* __restrict__ src, int H, int W, const Affine6& m, int x, int y, const Rgb8& fill) {
+    const double xc = (double)x + 0.5, yc5 = (double)y + 0.5;
+    const double xin = m.m0 * xc + m.m1 * yc5 + m.m2;
+    const double yin = m.m3 * xc + m.m4 * yc5 + m.m5;
+    return sample_bilinear(src, H, W, xin, yin, fill);
+}
+
+// Pillow's perspective_transform: both numerators divided by the same denominator, each quotient one correctly rounded fp64 division
+// (a reciprocal and a multiply changes bytes).  den == 0 gives an infinity (fill) or, with a zero numerator, a NaN (fill here; undefined
+// in Pillow); a negative den is sampled like any other where the position lands inside.
+struct Persp8 { double a0, a1, a2, a3, a4, a5, a6, a7; };
+
+__device__ __forceinline__ Rgb8 persp_pixel(const uint8_t* __restrict__ src, int H, int W, const Persp8& m, int x, int y, const Rgb8& fill) {
+    const double xc = (double)x + 0.5, yc5 = (double)y + 0.5;
+    const double den = m.a6 * xc + m.a7 * yc5 + 1.0;
+    const double xin = (m.a0 * xc + m.a1 * yc5 + m.a2) / den;
+    const double yin = (m.a3 * xc + m.a4 * yc5 + m.a5) / den;
+    return sample_bilinear(src, H, W, xin, yin, fill);
 }
 
 __device__ __forceinline__ Affine6 affine_of(const double* __restrict__ affine, int b) {
@@ -361,6 +380,35 @@ __global__ __launch_bounds__(256) void k_affine_u8(const uint8_t* __restrict__ i
     } else {
         for (int k = 0; k < AF_PX && x + k < W; ++k) {
             const Rgb8 c = affine_pixel(src, H, W, m, x + k, y, fill);
+            dst[3 * k] = (uint8_t)c.r; dst[3 * k + 1] = (uint8_t)c.g; dst[3 * k + 2] = (uint8_t)c.b;
+        }
+    }
+}
+
+// RandomPerspective (`train --aug_perspective`): k_affine_u8 with the projective source position; persp (B, 8) fp64 on the device, the
+// coefficients of Image.transform(size, PERSPECTIVE, ...).  Nothing in a row is validated: the inside test and the index clamps of
+// sample_bilinear bound every address for any table.  img (B, H, W, 3) u8 -> out (B, H, W, 3) u8, never in place; k_affine_u8's grid.
+__global__ __launch_bounds__(256) void k_persp_u8(const uint8_t* __restrict__ img, uint8_t* __restrict__ out, int H, int W,
+                                                   const double* __restrict__ persp, int f0, int f1, int f2) {
+    const int b = blockIdx.z;
+    const int x = (blockIdx.x * AF_TX + (threadIdx.x % AF_TX)) * AF_PX, y = blockIdx.y * AF_TY + threadIdx.x / AF_TX;
+    if (x >= W || y >= H) return;
+    const double* a = persp + 8 * (int64_t)b;
+    const Persp8 m{a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7]};
+    const Rgb8 fill{f0, f1, f2};
+    const uint8_t* src = img + (int64_t)b * H * W * 3;
+    uint8_t* dst = out + (((int64_t)b * H + y) * W + x) * 3;
+    if ((W & 3) == 0) {                                                  // four pixels = three aligned dwords
+        Rgb8 c[AF_PX];
+#pragma unroll
+        for (int k = 0; k < AF_PX; ++k) c[k] = persp_pixel(src, H, W, m, x + k, y, fill);
+        uint32_t* d = reinterpret_cast<uint32_t*>(dst);
+        d[0] = (uint32_t)c[0].r | (uint32_t)c[0].g << 8 | (uint32_t)c[0].b << 16 | (uint32_t)c[1].r << 24;
+        d[1] = (uint32_t)c[1].g | (uint32_t)c[1].b << 8 | (uint32_t)c[2].r << 16 | (uint32_t)c[2].g << 24;
+        d[2] = (uint32_t)c[2].b | (uint32_t)c[3].r << 8 | (uint32_t)c[3].g << 16 | (uint32_t)c[3].b << 24;
+    } else {
+        for (int k = 0; k < AF_PX && x + k < W; ++k) {
+            const Rgb8 c = persp_pixel(src, H, W, m, x + k, y, fill);
             dst[3 * k] = (uint8_t)c.r; dst[3 * k + 1] = (uint8_t)c.g; dst[3 * k + 2] = (uint8_t)c.b;
         }
     }
@@ -1361,13 +1409,15 @@ size_t sd_preprocess_blur_workspace_bytes(int geometry, int B, int Hin, int Win,
     return sd_preprocess_mosaic_workspace_bytes(B, Hin, Win, Hout, Wout);
 }
 
-// the blur forms proper (blur set): the checks of the geometry's entry point, its horizontal pass, its vertical pass into an 8-bit image,
-// the 8-bit stages, the blur, and the jitter or plain tail
+// the blur and perspective forms proper (blur or persp set): the checks of the geometry's entry point, its horizontal pass, its vertical
+// pass into an 8-bit image, the 8-bit stages -- the warp slot is k_affine_u8 or k_persp_u8 --, the blur unless its table is null, and the
+// jitter or plain tail
 static int preprocess_blur(const char* what, bool list, const void* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout,
                            int g0, int g1, const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize,
                            const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors, const double* affine,
-                           const int* mosaic_geom, const double* mosaic_affine, const int* blur, const uint8_t* fill3, const float* mean3,
-                           const float* std3, float* out, void* workspace, size_t workspace_bytes, hipStream_t st) {
+                           const double* persp, const int* mosaic_geom, const double* mosaic_affine, const int* blur, const uint8_t* fill3,
+                           const float* mean3, const float* std3, float* out, void* workspace, size_t workspace_bytes, hipStream_t st) {
+    const double* warp = affine ? affine : persp;                        // one warp slot: the callers refuse both together
     const uint8_t* packed = reinterpret_cast<const uint8_t*>(images);
     const uint8_t* const* table = reinterpret_cast<const uint8_t* const*>(images);
     int rpb = 0, bpi = 0;
@@ -1383,13 +1433,13 @@ static int preprocess_blur(const char* what, bool list, const void* images, int 
                    "%s: jitter_order and jitter_factors go together (both null = no jitter)", what);
         SD_REQUIRE((mosaic_geom == nullptr) == (mosaic_affine == nullptr), SD_ERR_INVALID,
                    "%s: mosaic_geom and mosaic_affine go together (both null = no mosaic)", what);
-        SD_REQUIRE(fill3 || !(affine || mosaic_geom), SD_ERR_INVALID, "%s: a warp or a mosaic needs a fill colour", what);
+        SD_REQUIRE(fill3 || !(warp || mosaic_geom), SD_ERR_INVALID, "%s: a warp or a mosaic needs a fill colour", what);
         SD_REQUIRE(workspace_bytes >= sd_preprocess_mosaic_workspace_bytes(B, Hin, Win, Hout, Wout), SD_ERR_WORKSPACE, "%s: workspace %zu < %zu", what,
                    workspace_bytes, sd_preprocess_mosaic_workspace_bytes(B, Hin, Win, Hout, Wout));
         tmp_bytes = sd_preprocess_workspace_bytes(B, Hin, Win, Wout);
     } else if (geometry == SD_GEOM_WINDOW) {
         if (int e = window_check(what, packed, B, Hin, Win, Hg, Wg, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, window, g0, g1,
-                                 jitter_order, jitter_factors, affine, mosaic_geom, mosaic_affine, fill3, mean3, std3, out, workspace, workspace_bytes))
+                                 jitter_order, jitter_factors, warp, mosaic_geom, mosaic_affine, fill3, mean3, std3, out, workspace, workspace_bytes))
             return e;
         if (list) {
             SD_REQUIRE((int64_t)g1 * 3 + 32 <= HL_LDS_BYTES, SD_ERR_INVALID,
@@ -1402,7 +1452,7 @@ static int preprocess_blur(const char* what, bool list, const void* images, int 
     } else if (geometry == SD_GEOM_LETTERBOX) {
         SD_REQUIRE(!window, SD_ERR_INVALID, "%s: a window table needs SD_GEOM_WINDOW", what);
         if (int e = letterbox_check(what, packed, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, jitter_order,
-                                    jitter_factors, affine, mosaic_geom, mosaic_affine, fill3, mean3, std3, out, workspace, workspace_bytes)) return e;
+                                    jitter_factors, warp, mosaic_geom, mosaic_affine, fill3, mean3, std3, out, workspace, workspace_bytes)) return e;
         if (list) {
             SD_REQUIRE((int64_t)Win * 3 + 32 <= HL_LDS_BYTES, SD_ERR_INVALID, "%s: source rows of %d pixels exceed the LDS staging buffer (at most %d)",
                        what, Win, (HL_LDS_BYTES - 32) / 3);
@@ -1422,7 +1472,7 @@ static int preprocess_blur(const char* what, bool list, const void* images, int 
     unsigned long long* lsum = reinterpret_cast<unsigned long long*>(img_a + frame);
     uint8_t* img_b = img_a + frame + align_up((size_t)B * 8, 256);
     if (jitter_order) SD_HIP(hipMemsetAsync(lsum, 0, (size_t)B * 8, st));
-    const int before = 1 + (mosaic_geom ? 1 : 0) + (affine ? 1 : 0);     // 8-bit images written in front of the blur; the last one is A
+    const int before = 1 + (mosaic_geom ? 1 : 0) + (warp ? 1 : 0);       // 8-bit images written in front of the blur; the last one is A
     int k = 0;
     auto next = [&]() { return ((before - 1 - k++) & 1) ? img_b : img_a; };
     uint8_t* cur = next();
@@ -1471,7 +1521,14 @@ static int preprocess_blur(const char* what, bool list, const void* images, int 
         SD_LAUNCH_CHECK();
         cur = dst;
     }
-    if (int e = blur_stage(cur, img_b, img_a, B, Hout, Wout, blur, st)) return e;      // cur == img_a
+    if (persp) {
+        uint8_t* dst = next();
+        hipLaunchKernelGGL(k_persp_u8, grid, dim3(256), 0, st, cur, dst, Hout, Wout, persp, f0, f1, f2);
+        SD_LAUNCH_CHECK();
+        cur = dst;
+    }
+    if (blur)                                                            // cur == img_a; without a blur the jitter reads it as it is
+        if (int e = blur_stage(cur, img_b, img_a, B, Hout, Wout, blur, st)) return e;
     if (jitter_order) return jitter_norm(B, Hout, Wout, flips, jitter_order, jitter_factors, mean3, std3, out, img_a, lsum, st);
     hipLaunchKernelGGL(k_u8_norm, flat, dim3(256), 0, st, img_a, out, Hout, Wout, flips, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], B);
     SD_LAUNCH_CHECK();
@@ -1486,8 +1543,8 @@ int sd_preprocess_images_blur(const uint8_t* images, int geometry, int B, int Hi
     const char* what = "sd_preprocess_images_blur";
     if (blur)
         return preprocess_blur(what, false, images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
-                               window, flips, jitter_order, jitter_factors, affine, mosaic_geom, mosaic_affine, blur, fill3, mean3, std3, out, workspace,
-                               workspace_bytes, (hipStream_t)stream);
+                               window, flips, jitter_order, jitter_factors, affine, nullptr, mosaic_geom, mosaic_affine, blur, fill3, mean3, std3, out,
+                               workspace, workspace_bytes, (hipStream_t)stream);
     if (geometry == SD_GEOM_WINDOW)
         return sd_preprocess_images_window(images, B, Hin, Win, Hg, Wg, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, window, g0, g1, flips,
                                            jitter_order, jitter_factors, affine, mosaic_geom, mosaic_affine, fill3, mean3, std3, out, workspace,
@@ -1520,8 +1577,8 @@ int sd_preprocess_images_list_blur(const uint8_t* const* images, int geometry, i
     const char* what = "sd_preprocess_images_list_blur";
     if (blur)
         return preprocess_blur(what, true, images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
-                               window, flips, jitter_order, jitter_factors, affine, mosaic_geom, mosaic_affine, blur, fill3, mean3, std3, out, workspace,
-                               workspace_bytes, (hipStream_t)stream);
+                               window, flips, jitter_order, jitter_factors, affine, nullptr, mosaic_geom, mosaic_affine, blur, fill3, mean3, std3, out,
+                               workspace, workspace_bytes, (hipStream_t)stream);
     if (geometry == SD_GEOM_WINDOW)
         return sd_preprocess_images_list_window(images, B, Hin, Win, Hg, Wg, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, window, g0, g1,
                                                 flips, jitter_order, jitter_factors, affine, mosaic_geom, mosaic_affine, fill3, mean3, std3, out, workspace,
@@ -1545,6 +1602,57 @@ int sd_preprocess_images_list_blur(const uint8_t* const* images, int geometry, i
                                                 jitter_factors, mean3, std3, out, workspace, workspace_bytes, stream);
     return sd_preprocess_images_list(images, B, Hin, Win, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, flips, mean3, std3, out, workspace,
                                      workspace_bytes, stream);
+}
+
+// ---- RandomPerspective in the warp slot of the chain (k_persp_u8), behind any geometry ----
+// persp null: the blur form, a call.  persp set: the host has folded the affine draw into the homography, so affine must be null; the
+// chain is preprocess_blur's with k_persp_u8 as the warp and the blur optional.
+int sd_perspective_u8(const uint8_t* in, uint8_t* out, int B, int H, int W, const double* coeffs, const uint8_t* fill3, sd_stream_t stream) {
+    SD_REQUIRE(in && out && coeffs && fill3, SD_ERR_INVALID, "sd_perspective_u8: null pointer");
+    SD_REQUIRE(B > 0 && H > 0 && W > 0, SD_ERR_INVALID, "sd_perspective_u8: bad shape");
+    SD_REQUIRE(B <= 65535 && H <= 65535 * AF_TY && (int64_t)B * H * W * 3 < (1ll << 40), SD_ERR_INVALID, "sd_perspective_u8: batch too large");
+    const int64_t bytes = (int64_t)B * H * W * 3;
+    SD_REQUIRE(in + bytes <= out || out + bytes <= in, SD_ERR_INVALID, "sd_perspective_u8: in place is not supported (out must not overlap in)");
+    const dim3 grid(cdiv(W, AF_TX * AF_PX), cdiv(H, AF_TY), B);
+    hipLaunchKernelGGL(k_persp_u8, grid, dim3(256), 0, (hipStream_t)stream, in, out, H, W, coeffs, (int)fill3[0], (int)fill3[1], (int)fill3[2]);
+    SD_LAUNCH_CHECK();
+    return 0;
+}
+
+int sd_preprocess_images_persp(const uint8_t* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout, int g0, int g1,
+                               const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize,
+                               const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
+                               const double* affine, const double* persp, const int* mosaic_geom, const double* mosaic_affine, const int* blur,
+                               const uint8_t* fill3, const float* mean3, const float* std3, float* out, void* workspace, size_t workspace_bytes,
+                               sd_stream_t stream) {
+    const char* what = "sd_preprocess_images_persp";
+    if (!persp)
+        return sd_preprocess_images_blur(images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
+                                         window, flips, jitter_order, jitter_factors, affine, mosaic_geom, mosaic_affine, blur, fill3, mean3, std3, out,
+                                         workspace, workspace_bytes, stream);
+    SD_REQUIRE(!affine, SD_ERR_INVALID, "%s: persp and affine do not combine (fold the affine matrix into the homography)", what);
+    SD_REQUIRE(fill3, SD_ERR_INVALID, "%s: a warp needs a fill colour", what);
+    return preprocess_blur(what, false, images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
+                           window, flips, jitter_order, jitter_factors, nullptr, persp, mosaic_geom, mosaic_affine, blur, fill3, mean3, std3, out,
+                           workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int sd_preprocess_images_list_persp(const uint8_t* const* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout,
+                                    int g0, int g1, const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk,
+                                    int v_ksize, const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
+                                    const double* affine, const double* persp, const int* mosaic_geom, const double* mosaic_affine, const int* blur,
+                                    const uint8_t* fill3, const float* mean3, const float* std3, float* out, void* workspace,
+                                    size_t workspace_bytes, sd_stream_t stream) {
+    const char* what = "sd_preprocess_images_list_persp";
+    if (!persp)
+        return sd_preprocess_images_list_blur(images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk,
+                                              v_ksize, window, flips, jitter_order, jitter_factors, affine, mosaic_geom, mosaic_affine, blur, fill3,
+                                              mean3, std3, out, workspace, workspace_bytes, stream);
+    SD_REQUIRE(!affine, SD_ERR_INVALID, "%s: persp and affine do not combine (fold the affine matrix into the homography)", what);
+    SD_REQUIRE(fill3, SD_ERR_INVALID, "%s: a warp needs a fill colour", what);
+    return preprocess_blur(what, true, images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
+                           window, flips, jitter_order, jitter_factors, nullptr, persp, mosaic_geom, mosaic_affine, blur, fill3, mean3, std3, out,
+                           workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

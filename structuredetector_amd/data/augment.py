@@ -31,6 +31,9 @@ pass at width wi, then one vertical pass that writes image and bars); every late
 Blur (`--aug_blur R`; not in the reference): between the warp and the ColorJitter, a selected image is `Image.filter(GaussianBlur(r))`
 byte for byte -- Pillow's six rounded box-blur passes in integer arithmetic (`sd_blur_u8`; in the chain `sd_preprocess_images_blur`); the
 box radius and weights of a pass are float32 arithmetic restated on the host (`blur_box_params`).  Photometric: annotations are untouched.
+Perspective (`--aug_perspective D`; not in the reference): the warp slot of the chain becomes one homography, the random affine folded into
+it on the host (`compose_affine_perspective`), byte for byte `Image.transform(size, PERSPECTIVE, coeffs, BILINEAR, fillcolor)`
+(`sd_perspective_u8`; in the chain `sd_preprocess_images_persp`); the annotations follow with `utils.misc.perspective_annotation`.
 Transpose (`--aug_transpose P`; not in the reference): last, after the flips, a selected image of the assembled (square) batch has its x and
 y swapped (`sd_transpose_select`, one launch: lossless, with the flips the eight symmetries of the grid); the annotations follow with
 `utils.misc.transpose_annotation`.
@@ -46,7 +49,7 @@ import torch
 from .. import _lib as L
 from ..utils.args import parse_tiles, tile_canvas
 from ..utils.misc import (affine_annotation, clip_annotation, hflip_annotation, letterbox_annotation, letterbox_geometry, mosaic_annotation,
-                          transpose_annotation, vflip_annotation)
+                          perspective_annotation, transpose_annotation, vflip_annotation)
 
 PRECISION_BITS = 32 - 8 - 2
 _MEAN = (0.485, 0.456, 0.406)
@@ -168,6 +171,32 @@ def affine_forward_matrix(size, angle, scale, translate):
     return [a, b, cx + tx - (a * cx + b * cy), c, d, cy + ty - (c * cx + d * cy)]
 
 
+def perspective_coeffs(src_quad, dst_quad):
+    """The 8 coefficients a0 .. a7 of the homography that takes the four `dst_quad` points to the four `src_quad` points,
+    src = ((a0 x + a1 y + a2) / den, (a3 x + a4 y + a5) / den) with den = a6 x + a7 y + 1 at dst = (x, y): what Pillow's
+    `Image.transform(size, PERSPECTIVE, coeffs, ...)` takes when dst are positions in the output and src in the source (both in the
+    continuous frame, a pixel index p being p + 0.5).  An 8 x 8 `numpy.linalg.solve` in float64, not torchvision's float32 least squares.
+    With the quads swapped it gives the forward twin, what the annotations follow (`perspective_annotation`)."""
+    a = np.zeros((8, 8), np.float64)
+    b = np.zeros(8, np.float64)
+    for k, ((sx, sy), (dx, dy)) in enumerate(zip(src_quad, dst_quad)):
+        a[2 * k] = (dx, dy, 1.0, 0.0, 0.0, 0.0, -dx * sx, -dy * sx)
+        a[2 * k + 1] = (0.0, 0.0, 0.0, dx, dy, 1.0, -dx * sy, -dy * sy)
+        b[2 * k], b[2 * k + 1] = sx, sy
+    return np.linalg.solve(a, b).tolist()
+
+
+def compose_affine_perspective(affine_inverse6, persp_inverse8):
+    """The 8 coefficients of source = A_inv(P_inv(out)): the image is affine-warped first and perspective-warped second, in ONE resample.
+    The 3 x 3 product of A_inv, extended by the row (0, 0, 1), with P_inv; its last row is P_inv's (a6, a7, 1), so nothing is
+    renormalised.  With the identity perspective the result is the affine row padded with (0, 0), with the identity affine it is the
+    perspective row, both exactly."""
+    a0, a1, a2, a3, a4, a5 = (float(v) for v in affine_inverse6)
+    p = [float(v) for v in persp_inverse8]
+    return [a0 * p[0] + a1 * p[3] + a2 * p[6], a0 * p[1] + a1 * p[4] + a2 * p[7], a0 * p[2] + a1 * p[5] + a2,
+            a3 * p[0] + a4 * p[3] + a5 * p[6], a3 * p[1] + a4 * p[4] + a5 * p[7], a3 * p[2] + a4 * p[5] + a5, p[6], p[7]]
+
+
 def mosaic_tiles(size, i, draw):
     """One image's mosaic from (W, H) = size and draw = (cx, cy, (p1, p2, p3)) -- an integer centre and the three partner images -- or
     draw = None for an image that is not selected.  Returns (geom, inverse, forward, rects):
@@ -278,6 +307,29 @@ def _preprocess_letterbox(fn_name, source, B, Hin, Win, out_size, flips, mean, s
     return out
 
 
+def _persp_rows(persp, B, device):
+    rows = torch.as_tensor(np.asarray(persp, dtype=np.float64)).reshape(-1, 8).contiguous()
+    if rows.shape[0] != B:
+        raise L.SdError("persp must have one row of 8 coefficients per image")
+    return rows.to(device, non_blocking=True)
+
+
+def perspective_images(images: torch.Tensor, persp, fill=_FILL) -> torch.Tensor:
+    """images: (B, H, W, 3) uint8 on the GPU; persp: B rows of 8 coefficients as `perspective_coeffs` makes them.  Returns a new tensor,
+    image b = `Image.transform((W, H), PERSPECTIVE, persp_b, BILINEAR, fillcolor=fill)` byte for byte (`sd_perspective_u8`: the stand-alone
+    stage of the chain)."""
+    L.require_cuda(images)
+    if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3:
+        raise L.SdError(f"perspective_images expects (B, H, W, 3) uint8, got {tuple(images.shape)} {images.dtype}")
+    images = images.contiguous()
+    B, H, W, _ = images.shape
+    rows = _persp_rows(persp, B, images.device)
+    out = torch.empty_like(images)
+    L.check(L.lib().sd_perspective_u8(images.data_ptr(), out.data_ptr(), B, H, W, rows.data_ptr(), (C.c_ubyte * 3)(*fill), L.stream()),
+            "sd_perspective_u8")
+    return out
+
+
 def blur_box_params(r):
     """(R, ww, fw) of Pillow's `GaussianBlur(r)` (libImaging/BoxBlur.c: _gaussian_blur_radius, ImagingLineBoxBlur8): the whole box radius
     and the 24-bit weights of a whole pixel and of the two edge pixels of one pass, one row of `sd_blur_u8`'s table.  Pillow computes them in
@@ -324,9 +376,12 @@ def blur_images(images: torch.Tensor, blur) -> torch.Tensor:
 GEOM_STRETCH, GEOM_WINDOW, GEOM_LETTERBOX = 0, 1, 2                  # include/sdnet_hip.h SD_GEOM_*
 
 
-def _preprocess_blur(fn_name, source, B, Hin, Win, out_size, flips, mean, std, jitter, affine, mosaic, window, letterbox, blur, dev):
+def _preprocess_blur(fn_name, source, B, Hin, Win, out_size, flips, mean, std, jitter, affine, mosaic, window, letterbox, blur, dev, persp=None):
     """The blur forms of `preprocess_images` / `preprocess_image_list` (`sd_preprocess_images_blur` / `..._list_blur`): any geometry, every
-    optional stage, the blur between the warp and the jitter.  source = the address of the packed images or of the pointer table."""
+    optional stage, the blur between the warp and the jitter.  source = the address of the packed images or of the pointer table.  With
+    `persp` the perspective forms (`sd_preprocess_images_persp` / `..._list_persp`): the same arguments plus the homography table."""
+    if persp is not None and affine is not None:
+        raise L.SdError("preprocess: persp and affine do not combine (fold the affine matrix in with compose_affine_perspective)")
     Wout, Hout = int(out_size[0]), int(out_size[1])
     geometry, Hg, Wg, g0, g1, org = GEOM_STRETCH, 0, 0, 0, 0, None
     if letterbox is not None:
@@ -358,17 +413,19 @@ def _preprocess_blur(fn_name, source, B, Hin, Win, out_size, flips, mean, std, j
     fl, order, factors, rows, geom, mats = _stage_tables(B, flips, jitter, affine, mosaic, dev)
     bl = None if blur is None else _blur_rows(blur, B, dev)          # (None: the library runs the geometry's existing entry point)
     ptr = lambda t: t.data_ptr() if t is not None else 0
+    homography = None if persp is None else _persp_rows(persp, B, dev)
+    warp = [ptr(rows), ptr(homography)] if fn_name.endswith("_persp") else [ptr(rows)]   # the perspective forms take persp after affine
     lib = L.lib()
     ws = L.workspace(lib.sd_preprocess_blur_workspace_bytes(geometry, B, Hin, Win, Wg, Hout, Wout, g0), dev)
     L.check(getattr(lib, fn_name)(source, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, hb.data_ptr(), hk.data_ptr(), hks, vb.data_ptr(),
-                                  vk.data_ptr(), vks, ptr(org), ptr(fl), ptr(order), ptr(factors), ptr(rows), ptr(geom), ptr(mats), ptr(bl),
+                                  vk.data_ptr(), vks, ptr(org), ptr(fl), ptr(order), ptr(factors), *warp, ptr(geom), ptr(mats), ptr(bl),
                                   (C.c_ubyte * 3)(*_FILL), (C.c_float * 3)(*mean), (C.c_float * 3)(*std), out.data_ptr(), ws.data_ptr(), ws.numel(),
                                   L.stream()), fn_name)
     return out
 
 
 def preprocess_images(images: torch.Tensor, out_size, flips=None, mean=_MEAN, std=_STD, jitter=None, affine=None, mosaic=None,
-                      window=None, letterbox=None, blur=None) -> torch.Tensor:
+                      window=None, letterbox=None, blur=None, persp=None) -> torch.Tensor:
     """images: (B, Hin, Win, 3) uint8 on the GPU; out_size = (width, height); flips: (B,) uint8 (bit 0 horizontal, bit 1 vertical)
     or None; jitter: None or (order words (B,) int32, factors (B, 3) fp32) as `jitter_words` makes them; affine: None or B rows of the 6
     coefficients of `affine_inverse_matrix` at out_size (the warp runs on the resized image, in front of the jitter, fill `_FILL`); mosaic:
@@ -379,13 +436,18 @@ def preprocess_images(images: torch.Tensor, out_size, flips=None, mean=_MEAN, st
     `letterbox_geometry` gives them: the resize targets wi x hi and the result is pasted at (px, py) into an out_size frame of `_FILL`
     (`sd_preprocess_images_letterbox`), every later stage works on that frame (not together with `window`); blur: None or B rows
     (R, ww, fw) as `blur_box_params` makes them: Pillow's GaussianBlur after the warp, in front of the jitter
-    (`sd_preprocess_images_blur`, chosen only when blur is set; a row of r = 0 leaves its image as it is).
+    (`sd_preprocess_images_blur`, chosen only when blur is set; a row of r = 0 leaves its image as it is); persp: None or B rows of the 8
+    coefficients of `perspective_coeffs` / `compose_affine_perspective` at out_size: the warp is that homography (`sd_preprocess_images_persp`,
+    chosen only when persp is set; not together with `affine`, which the caller folds in).
     Returns (B, 3, height, width) fp32 = Normalize(to_tensor(flip(jitter(blur(affine(mosaic(resize(image)))))))) of transforms.py:217-226."""
     L.require_cuda(images)
     if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3:
         raise L.SdError(f"preprocess_images expects (B, H, W, 3) uint8, got {tuple(images.shape)} {images.dtype}")
     images = images.contiguous()
     B, Hin, Win, _ = images.shape
+    if persp is not None:
+        return _preprocess_blur("sd_preprocess_images_persp", images.data_ptr(), B, Hin, Win, out_size, flips, mean, std, jitter, affine, mosaic,
+                                window, letterbox, blur, images.device, persp)
     if blur is not None:
         return _preprocess_blur("sd_preprocess_images_blur", images.data_ptr(), B, Hin, Win, out_size, flips, mean, std, jitter, affine, mosaic,
                                 window, letterbox, blur, images.device)
@@ -448,7 +510,7 @@ def preprocess_images(images: torch.Tensor, out_size, flips=None, mean=_MEAN, st
 
 
 def preprocess_image_list(pointers: torch.Tensor, hin: int, win: int, out_size, flips=None, mean=_MEAN, std=_STD, jitter=None,
-                          affine=None, mosaic=None, window=None, letterbox=None, blur=None) -> torch.Tensor:
+                          affine=None, mosaic=None, window=None, letterbox=None, blur=None, persp=None) -> torch.Tensor:
     """`preprocess_images` over B images that are not packed together: pointers is a (B,) int64 DEVICE tensor of the device addresses of
     B (hin, win, 3) uint8 images (any byte alignment; the caller keeps them alive until the work on the current stream is done), e.g. entries
     of data/image_cache.py's DeviceImageCache.  Same arguments otherwise, same output bytes as `preprocess_images` on the stacked images."""
@@ -458,6 +520,9 @@ def preprocess_image_list(pointers: torch.Tensor, hin: int, win: int, out_size, 
     pointers = pointers.contiguous()
     dev = pointers.device
     B, Hin, Win = pointers.numel(), int(hin), int(win)
+    if persp is not None:
+        return _preprocess_blur("sd_preprocess_images_list_persp", pointers.data_ptr(), B, Hin, Win, out_size, flips, mean, std, jitter, affine,
+                                mosaic, window, letterbox, blur, dev, persp)
     if blur is not None:
         return _preprocess_blur("sd_preprocess_images_list_blur", pointers.data_ptr(), B, Hin, Win, out_size, flips, mean, std, jitter, affine,
                                 mosaic, window, letterbox, blur, dev)
@@ -585,6 +650,10 @@ class ValidationAugmentation:
         """n gaussian radii (0.0 = the sample stays sharp) or None: validation never blurs and never draws."""
         return None
 
+    def perspective_draws_for(self, n):
+        """Per sample None or the four output corners (tl, tr, br, bl), or None for the batch: validation never warps and never draws."""
+        return None
+
     @staticmethod
     def size_groups(images):
         """{(hin, win): (indices into the batch, stack of those images)} of what `__call__` accepts as `images`."""
@@ -634,6 +703,14 @@ class ValidationAugmentation:
         windows = self.window_draws_for(n)
         transposes = self.transpose_draws_for(n)
         blurs = self.blur_draws_for(n)
+        quads = self.perspective_draws_for(n)
+        homography = forward8 = None
+        if quads is not None:                                        # the warp slot becomes one homography per image: affine, then perspective
+            frame = [(0.0, 0.0), (float(W), 0.0), (float(W), float(H)), (0.0, float(H))]
+            ident6, ident8 = [1.0, 0.0, 0.0, 0.0, 1.0, 0.0], [1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0]
+            homography = [compose_affine_perspective(ident6 if inverse is None else inverse[i],
+                                                     ident8 if quads[i] is None else perspective_coeffs(frame, quads[i])) for i in range(n)]
+            forward8 = [None if quads[i] is None else perspective_coeffs(quads[i], frame) for i in range(n)]
         if transposes is not None and W != H:
             raise L.SdError(f"aug_transpose: a transposed sample needs a square batch, not {W} x {H}")
         if windows is not None and self.keep_aspect:
@@ -642,8 +719,10 @@ class ValidationAugmentation:
         for (hin, win), (idx, stack) in groups.items():
             f = None if flips is None else [flips[i] for i in idx]
             j = None if jitter is None else ([jitter[0][i] for i in idx], [jitter[1][i] for i in idx])
-            m = None if inverse is None else [inverse[i] for i in idx]
+            m = None if inverse is None or homography is not None else [inverse[i] for i in idx]
             kw = {}
+            if homography is not None:                               # (the affine draw is folded in: `affine=` is not passed)
+                kw["persp"] = [homography[i] for i in idx]
             if mosaics is not None:                                  # the kernel's sources index this group's stack: partners come from the group
                 where = {i: k for k, i in enumerate(idx)}
                 tiles = {i: mosaic_tiles((W, H), i, mosaics[i]) for i in idx}
@@ -682,9 +761,11 @@ class ValidationAugmentation:
                         mosaic_annotation(annotations[i], [resized[s] for s in geom[2:]], forward, rects)
             for i in idx:
                 ann = annotations[i]
-                if warps is not None:                                # on the resized image, before the flips: drops what leaves the frame
-                    a, s, tx, ty = warps[i]
-                    affine_annotation(ann, affine_forward_matrix((W, H), a, s, (tx, ty)), (W, H))
+                forward6 = None if warps is None else affine_forward_matrix((W, H), warps[i][0], warps[i][1], warps[i][2:])
+                if forward8 is not None and forward8[i] is not None:  # affine, then perspective; one inside test at the end
+                    perspective_annotation(ann, forward8[i], (W, H), affine_forward=forward6)
+                elif forward6 is not None:                           # on the resized image, before the flips: drops what leaves the frame
+                    affine_annotation(ann, forward6, (W, H))
                 if flips is not None and flips[i] & 1:
                     hflip_annotation(ann, (W, H))                    # transforms.py:15 (on the resized image)
                 if flips is not None and flips[i] & 2:
@@ -718,6 +799,7 @@ class TrainAugmentation(ValidationAugmentation):
         self.mosaic = float(getattr(args, "aug_mosaic", 0.0))              # per-image probability of becoming a mosaic of four
         self.transpose = float(getattr(args, "aug_transpose", 0.0))        # per-image probability of being transposed (square sizes only)
         self.blur = float(getattr(args, "aug_blur", 0.0) or 0.0)           # gaussian radius uniform in [0, blur] pixels for a selected image
+        self.perspective = float(getattr(args, "aug_perspective", 0.0) or 0.0)   # distortion scale of a selected image's corner insets
         self.train_tiles = parse_tiles(getattr(args, "train_tiles", ""), "train_tiles")   # (Tx, Ty) of the canvas the windows are cut from, () = off
         self.tile_overlap = int(getattr(args, "tile_overlap", 64))
 
@@ -801,6 +883,23 @@ class TrainAugmentation(ValidationAugmentation):
             return None
         u = torch.rand(n, 2, dtype=torch.float64).tolist()
         return [self.blur * u1 if u0 < self.prob else 0.0 for u0, u1 in u]
+
+    def perspective_draws_for(self, n):
+        """Per sample None (not selected) or the four output corners (tl, tr, br, bl) from ONE more draw on torch's global generator,
+        `rand(n, 9)` in float64, made after that of `blur_draws_for`: sample i is warped when u0 < `prob`; its corners are inset as
+        torchvision's RandomPerspective insets them, in the continuous frame [0, W] x [0, H] of the current multi-scale size and left
+        unrounded: tl = (u1 D W/2, u2 D H/2), tr = (W - u3 D W/2, u4 D H/2), br = (W - u5 D W/2, H - u6 D H/2), bl = (u7 D W/2,
+        H - u8 D H/2).  The source quad is the frame's corners.  None, and no draw at all, with `--aug_perspective 0` or augmentation
+        off."""
+        if self.args.no_augmentation or self.perspective == 0:
+            return None
+        W, H = self.size
+        d = self.perspective
+        quads = []
+        for u0, u1, u2, u3, u4, u5, u6, u7, u8 in torch.rand(n, 9, dtype=torch.float64).tolist():
+            quads.append([(u1 * d * W / 2, u2 * d * H / 2), (W - u3 * d * W / 2, u4 * d * H / 2), (W - u5 * d * W / 2, H - u6 * d * H / 2),
+                          (u7 * d * W / 2, H - u8 * d * H / 2)] if u0 < self.prob else None)
+        return quads
 
     def trigger_random_resize(self):
         if self.args.no_augmentation:

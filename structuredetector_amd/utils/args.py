@@ -136,6 +136,13 @@ _FLAGS = [
                            "network input size (0 <= R <= 8: the same physical blur at every multi-scale size; motion / defocus blur of "
                            "deployment frames), after the warp and before the colour jitter; annotations are untouched. Needs a directory "
                            "(not --synthetic). Not consulted by evaluate / detect. 0 = off.")),
+    (("--aug_perspective",), dict(type=float, default=0.0, metavar="D", help="Training augmentation: with the flip probability's threshold "
+                                  "(u < 0.5) an image gets a random perspective warp, torchvision's RandomPerspective with distortion "
+                                  "scale D (0 <= D <= 0.9): each corner of the frame moves inwards by up to D/2 of the width and height "
+                                  "(pitch / roll / mounting tilt of the camera). Folded with --aug_rotate / --aug_scale / --aug_translate "
+                                  "into one homography, so an image is resampled once, byte for byte Pillow's Image.transform("
+                                  "PERSPECTIVE, BILINEAR); keypoints that leave the frame are dropped. Needs a directory (not "
+                                  "--synthetic). Not consulted by evaluate / detect. 0 = off.")),
 ]
 
 _POSITIVE = ["in_channels", "fpn_depth", "batch_size", "epochs", "learning_rate", "down_ratio", "max_objects", "max_parts"]
@@ -288,6 +295,20 @@ def check_aug_blur(args):
     return r
 
 
+MAX_AUG_PERSPECTIVE = 0.9           # distortion scale: at 1 two opposite corners can meet and the quadrilateral degenerates
+
+
+def check_aug_perspective(args):
+    """`--aug_perspective` on a parsed namespace -> D, as `train` checks it (model/trainer.py): a distortion scale in [0, 0.9];
+    `--synthetic` renders network-input tensors and has no 8-bit image to warp, so the flag is refused there."""
+    d = float(getattr(args, "aug_perspective", 0.0) or 0.0)
+    if not 0 <= d <= MAX_AUG_PERSPECTIVE:                            # (also false for nan)
+        raise ValueError(f"'aug_perspective' should be in [0, {MAX_AUG_PERSPECTIVE:g}] (0 = off), not {d}")
+    if d > 0 and getattr(args, "synthetic", 0):
+        raise ValueError("'aug_perspective' warps source images: it needs --train_dir, not --synthetic")
+    return d
+
+
 def finalize(args):
     """Validation + derived fields (args.py:178-269) on an already parsed namespace."""
     for side in ("width", "height"):
@@ -310,6 +331,7 @@ def finalize(args):
     assert 0 <= getattr(args, "aug_mosaic", 0.0) <= 1, "'aug_mosaic' should be in [0, 1]"
     assert 0 <= getattr(args, "aug_transpose", 0.0) <= 1, "'aug_transpose' should be in [0, 1]"
     assert 0 <= getattr(args, "aug_blur", 0.0) <= MAX_AUG_BLUR, "'aug_blur' should be in [0, 8]"
+    assert 0 <= getattr(args, "aug_perspective", 0.0) <= MAX_AUG_PERSPECTIVE, "'aug_perspective' should be in [0, 0.9]"
     args.label_nms = check_label_nms(getattr(args, "label_nms", 0))
     args.tta_scales = parse_tta_scales(getattr(args, "tta_scales", ""))
     args.tiles = parse_tiles(getattr(args, "tiles", ""))

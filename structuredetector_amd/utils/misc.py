@@ -105,6 +105,57 @@ def affine_annotation(annotation, forward_matrix, img_size):
     return annotation
 
 
+def perspective_annotation(annotation, forward8, img_size, affine_forward=None):
+    """Follow a perspective warp of the image (data/augment.py: perspective_coeffs with the quads swapped), in place: with q = p + 0.5 a
+    point moves to p' + 0.5 = ((f0 qx + f1 qy + f2) / den, (f3 qx + f4 qy + f5) / den), den = f6 qx + f7 qy + 1.  With `affine_forward`
+    (affine_forward_matrix) the point goes through that matrix first, with nothing dropped in between: the image is warped once by the
+    composed coefficients, so the inside test runs once, at the end.  The drop rule is affine_annotation's -- 0 <= x' + 0.5 < w and
+    0 <= y' + 0.5 < h -- plus den > 0: a point with den <= 0 lies on or behind the horizon of the forward map, and where it would land is
+    not where the image shows it.  An object whose anchor is dropped goes with all its parts; a dropped part is removed from its object; a
+    box becomes the axis-aligned hull of its four corners, or the whole frame when a corner has den <= 0 (the quadrilateral is then
+    unbounded; clip_annotation clips either later)."""
+    w, h = img_size
+    f0, f1, f2, f3, f4, f5, f6, f7 = forward8
+    a = affine_forward
+
+    def move(x, y):
+        xc, yc = x + 0.5, y + 0.5
+        if a is not None:
+            xc, yc = a[0] * xc + a[1] * yc + a[2], a[3] * xc + a[4] * yc + a[5]
+        den = f6 * xc + f7 * yc + 1.0
+        if not den > 0:
+            return None
+        return (f0 * xc + f1 * yc + f2) / den - 0.5, (f3 * xc + f4 * yc + f5) / den - 0.5
+
+    def inside(p):
+        return p is not None and 0 <= p[0] + 0.5 < w and 0 <= p[1] + 0.5 < h
+
+    kept = []
+    for obj in annotation.objects:
+        anchor = move(obj.x, obj.y)
+        if not inside(anchor):
+            continue
+        obj.x, obj.y = anchor
+        parts = []
+        for p in obj.parts:
+            moved = move(p.x, p.y)
+            if inside(moved):
+                p.x, p.y = moved
+                parts.append(p)
+        obj.parts = parts
+        if obj.box is not None:
+            b = obj.box
+            corners = [move(x, y) for x in (b.x_min, b.x_max) for y in (b.y_min, b.y_max)]
+            if any(c is None for c in corners):
+                b.x_min, b.x_max, b.y_min, b.y_max = 0.0, float(w - 1), 0.0, float(h - 1)
+            else:
+                xs, ys = zip(*corners)
+                b.x_min, b.x_max, b.y_min, b.y_max = min(xs), max(xs), min(ys), max(ys)
+        kept.append(obj)
+    annotation.objects = kept
+    return annotation
+
+
 def mosaic_annotation(annotation, sources, forward_matrices, rects):
     """Follow a mosaic of the image (data/augment.py: mosaic_tiles): `annotation` gets, in place, the objects of the four `sources` (the
     RESIZED annotations of the images shown in tiles 0 .. 3; they are read, never modified: every object is cloned first, so an image can
