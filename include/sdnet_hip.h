@@ -534,6 +534,40 @@ int sd_preprocess_images_list_persp(const uint8_t* const* images, int geometry, 
                                     const int* blur, const uint8_t fill3[3], const float* mean3, const float* std3, float* out, void* workspace,
                                     size_t workspace_bytes, sd_stream_t stream);
 
+/* JPEG compression of 8-bit images (training augmentation, `train --aug_jpeg`): image b becomes what Pillow's
+ * Image.save(buf, "JPEG", qtables=[ql_b, qc_b], subsampling=2) followed by Image.open(buf) gives, byte for byte: libjpeg's RGB -> YCbCr,
+ * h2v2 chroma downsampling, accurate-integer forward DCT, quantiser, dequantiser, accurate-integer inverse DCT, h2v2 "fancy" chroma
+ * upsampling and YCbCr -> RGB, all in 32-bit integers (the entropy coder is lossless and is left out; tests/jpeg_ref.py states every
+ * formula).  table (B, 129) int32 on the DEVICE: a row is [on, ql[64], qc[64]], the luminance and chrominance quantisation tables in
+ * natural (row-major) order, e.g. libjpeg's standard tables at a quality (data/augment.py jpeg_quant_tables).  A row with on == 0 copies
+ * its image.  Entries outside [1, 255] are clamped into that range; nothing in a row decides an address, so any table is memory-safe.
+ * in and out are (B, H, W, 3) uint8 with H and W multiples of 16 (whole MCUs; SD_ERR_INVALID otherwise); out may be in (in place), any
+ * other overlap is SD_ERR_INVALID.  workspace: sd_jpeg_workspace_bytes() bytes, 16-byte aligned -- the decoded Y plane at full size and
+ * the decoded Cb and Cr planes at half size.  Two launches.  B <= 65535. */
+size_t sd_jpeg_workspace_bytes(int B, int H, int W);
+int sd_jpeg_u8(const uint8_t* in, uint8_t* out, int B, int H, int W, const int* table, void* workspace, size_t workspace_bytes,
+               sd_stream_t stream);
+
+/* The perspective forms with the JPEG round trip between the blur and the jitter:
+ *     Resize | Window | Letterbox -> [Mosaic] -> [Affine | Perspective] -> [Blur] -> JPEG -> [ColorJitter] -> flips -> Normalize.
+ * The arguments of sd_preprocess_images_persp / _list_persp plus jpeg (B, 129) int32 on the device after blur, as sd_jpeg_u8's table.
+ * With jpeg null the call IS the perspective form.  With jpeg set every other table is optional, Hout and Wout must be multiples of 16
+ * and the workspace 16-byte aligned (SD_ERR_INVALID otherwise).  workspace: sd_preprocess_jpeg_workspace_bytes() bytes =
+ * sd_preprocess_blur_workspace_bytes() in that layout, then the decoded planes. */
+size_t sd_preprocess_jpeg_workspace_bytes(int geometry, int B, int Hin, int Win, int Wg, int Hout, int Wout, int g0);
+int sd_preprocess_images_jpeg(const uint8_t* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout, int g0, int g1,
+                              const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize,
+                              const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
+                              const double* affine, const double* persp, const int* mosaic_geom, const double* mosaic_affine, const int* blur,
+                              const int* jpeg, const uint8_t fill3[3], const float* mean3, const float* std3, float* out, void* workspace,
+                              size_t workspace_bytes, sd_stream_t stream);
+int sd_preprocess_images_list_jpeg(const uint8_t* const* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout,
+                                   int g0, int g1, const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk,
+                                   int v_ksize, const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
+                                   const double* affine, const double* persp, const int* mosaic_geom, const double* mosaic_affine,
+                                   const int* blur, const int* jpeg, const uint8_t fill3[3], const float* mean3, const float* std3, float* out,
+                                   void* workspace, size_t workspace_bytes, sd_stream_t stream);
+
 /* ---- loss: src/sdnet/model/loss.py:17-64,91-117------------------------------------------- */
 
 #define SD_HM_MSE   0

@@ -143,6 +143,15 @@ _SIGNATURES = {
                                    [C.POINTER(C.c_ubyte), C.POINTER(c_float), C.POINTER(c_float), c_vp, c_vp, c_size, c_vp]),
     "sd_preprocess_images_list_persp": (c_int, [c_vp] + [c_int] * 10 + [c_vp, c_vp, c_int, c_vp, c_vp, c_int] + [c_vp] * 9 +
                                         [C.POINTER(C.c_ubyte), C.POINTER(c_float), C.POINTER(c_float), c_vp, c_vp, c_size, c_vp]),
+    # JPEG round trip of 8-bit images: in, out (may be in), B, H, W (multiples of 16), table (B, 129) int32 device = on, ql[64], qc[64], workspace, ...
+    "sd_jpeg_workspace_bytes": (c_size, [c_int] * 3),
+    "sd_jpeg_u8": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_size, c_vp]),
+    # the perspective forms with jpeg (B, 129) int32 device after blur (null: the perspective form)
+    "sd_preprocess_jpeg_workspace_bytes": (c_size, [c_int] * 8),
+    "sd_preprocess_images_jpeg": (c_int, [c_vp] + [c_int] * 10 + [c_vp, c_vp, c_int, c_vp, c_vp, c_int] + [c_vp] * 10 +
+                                  [C.POINTER(C.c_ubyte), C.POINTER(c_float), C.POINTER(c_float), c_vp, c_vp, c_size, c_vp]),
+    "sd_preprocess_images_list_jpeg": (c_int, [c_vp] + [c_int] * 10 + [c_vp, c_vp, c_int, c_vp, c_vp, c_int] + [c_vp] * 10 +
+                                       [C.POINTER(C.c_ubyte), C.POINTER(c_float), C.POINTER(c_float), c_vp, c_vp, c_size, c_vp]),
     "sd_render_targets": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_float, c_vp, c_vp]),
     "sd_loss_workspace_bytes": (c_size, [c_int] * 5),
     "sd_loss_fwd": (c_int, [C.POINTER(LossDesc), c_vp, c_vp, c_size, c_vp]),

@@ -87,6 +87,12 @@ int head_wide_dgrad(const float* dy, const float* w, float* dx, int B, int HW, i
 // int32 on the device.  Shapes are the caller's to check (B and cdiv(H, 64) are grid dimensions: <= 65535).
 int blur_stage(const uint8_t* in, uint8_t* mid, uint8_t* out, int B, int H, int W, const int* blur, hipStream_t st);
 
+// JPEG round-trip stage (sd_jpeg.hip): in -> planes -> out, in and out (B, H, W, 3) u8 with H and W multiples of 16, out may be in.
+// planes: jpeg_planes_bytes() bytes, 16-byte aligned.  table (B, 129) int32 on the device.  Shapes are the caller's to check (B and
+// cdiv(H, 64) are grid dimensions: <= 65535).
+size_t jpeg_planes_bytes(int B, int H, int W);
+int jpeg_stage(const uint8_t* in, uint8_t* out, uint8_t* planes, int B, int H, int W, const int* table, hipStream_t st);
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);

@@ -34,6 +34,10 @@ box radius and weights of a pass are float32 arithmetic restated on the host (`b
 Perspective (`--aug_perspective D`; not in the reference): the warp slot of the chain becomes one homography, the random affine folded into
 it on the host (`compose_affine_perspective`), byte for byte `Image.transform(size, PERSPECTIVE, coeffs, BILINEAR, fillcolor)`
 (`sd_perspective_u8`; in the chain `sd_preprocess_images_persp`); the annotations follow with `utils.misc.perspective_annotation`.
+JPEG (`--aug_jpeg QMIN`; not in the reference): between the blur and the ColorJitter, a selected image is what Pillow's
+`save(buf, "JPEG", quality=q)` then `open(buf)` gives, byte for byte -- colour conversion, 4:2:0 chroma, the accurate-integer DCT of every
+8 x 8 block, the quantiser and the way back, all integer (`sd_jpeg_u8`; in the chain `sd_preprocess_images_jpeg`); the two quantisation
+tables of a quality come from the host (`jpeg_quant_tables`).  Photometric: annotations are untouched.
 Transpose (`--aug_transpose P`; not in the reference): last, after the flips, a selected image of the assembled (square) batch has its x and
 y swapped (`sd_transpose_select`, one launch: lossless, with the flips the eight symmetries of the grid); the annotations follow with
 `utils.misc.transpose_annotation`.
@@ -373,13 +377,69 @@ def blur_images(images: torch.Tensor, blur) -> torch.Tensor:
     return out
 
 
+# Annex K of the JPEG standard: the luminance and chrominance quantisation tables of quality 50, natural (row-major) order
+_JPEG_LUMA = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+              18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99)
+_JPEG_CHROMA = (17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99) + (99,) * 32
+
+
+def jpeg_quant_tables(q):
+    """(ql, qc) of libjpeg's `jpeg_set_quality(q, force_baseline)`, what Pillow's `save(quality=q)` writes and `Image.open().quantization`
+    returns: two lists of 64 entries in [1, 255] in natural (row-major) order, the Annex-K tables scaled by 5000 // q percent below quality 50
+    and by 200 - 2 q from there on."""
+    q = int(q)
+    if not 1 <= q <= 100:
+        raise ValueError(f"jpeg quality should be in [1, 100], not {q}")
+    s = 5000 // q if q < 50 else 200 - 2 * q
+    return tuple([min(max((v * s + 50) // 100, 1), 255) for v in base] for base in (_JPEG_LUMA, _JPEG_CHROMA))
+
+
+def jpeg_rows(qualities):
+    """One row [on, ql[64], qc[64]] of `sd_jpeg_u8`'s table per quality; quality 0 gives a copy row (on = 0, the tables all ones)."""
+    rows = []
+    for q in qualities:
+        if int(q) == 0:
+            rows.append([0] + [1] * 128)
+        else:
+            ql, qc = jpeg_quant_tables(q)
+            rows.append([1, *ql, *qc])
+    return rows
+
+
+def _jpeg_rows(rows, B, device):
+    table = torch.as_tensor(np.asarray(rows, dtype=np.int64).astype(np.int32)).reshape(-1, 129).contiguous()
+    if table.shape[0] != B:
+        raise L.SdError("jpeg must have one row (on, ql[64], qc[64]) per image")
+    return table.to(device, non_blocking=True)
+
+
+def jpeg_images(images: torch.Tensor, rows) -> torch.Tensor:
+    """images: (B, H, W, 3) uint8 on the GPU with H and W multiples of 16; rows: B rows [on, ql[64], qc[64]] as `jpeg_rows` makes them.
+    Returns a new tensor, image b = Pillow's `save(buf, "JPEG", quality=q_b)` then `open(buf)` byte for byte (`sd_jpeg_u8`: the stand-alone
+    stage of the chain)."""
+    L.require_cuda(images)
+    if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3:
+        raise L.SdError(f"jpeg_images expects (B, H, W, 3) uint8, got {tuple(images.shape)} {images.dtype}")
+    images = images.contiguous()
+    B, H, W, _ = images.shape
+    table = _jpeg_rows(rows, B, images.device)
+    out = torch.empty_like(images)
+    lib = L.lib()
+    ws = L.workspace(lib.sd_jpeg_workspace_bytes(B, H, W), images.device)
+    L.check(lib.sd_jpeg_u8(images.data_ptr(), out.data_ptr(), B, H, W, table.data_ptr(), ws.data_ptr(), ws.numel(), L.stream()), "sd_jpeg_u8")
+    return out
+
+
+JPEG_MAX_QUALITY = 95                                                # the upper end of `--aug_jpeg`'s quality range (Pillow's advised maximum)
 GEOM_STRETCH, GEOM_WINDOW, GEOM_LETTERBOX = 0, 1, 2                  # include/sdnet_hip.h SD_GEOM_*
 
 
-def _preprocess_blur(fn_name, source, B, Hin, Win, out_size, flips, mean, std, jitter, affine, mosaic, window, letterbox, blur, dev, persp=None):
+def _preprocess_blur(fn_name, source, B, Hin, Win, out_size, flips, mean, std, jitter, affine, mosaic, window, letterbox, blur, dev, persp=None,
+                     jpeg=None):
     """The blur forms of `preprocess_images` / `preprocess_image_list` (`sd_preprocess_images_blur` / `..._list_blur`): any geometry, every
     optional stage, the blur between the warp and the jitter.  source = the address of the packed images or of the pointer table.  With
-    `persp` the perspective forms (`sd_preprocess_images_persp` / `..._list_persp`): the same arguments plus the homography table."""
+    `persp` the perspective forms (`sd_preprocess_images_persp` / `..._list_persp`): the same arguments plus the homography table.  With
+    `jpeg` the JPEG forms (`sd_preprocess_images_jpeg` / `..._list_jpeg`): those arguments plus the quantisation tables after the blur's."""
     if persp is not None and affine is not None:
         raise L.SdError("preprocess: persp and affine do not combine (fold the affine matrix in with compose_affine_perspective)")
     Wout, Hout = int(out_size[0]), int(out_size[1])
@@ -414,18 +474,22 @@ def _preprocess_blur(fn_name, source, B, Hin, Win, out_size, flips, mean, std, j
     bl = None if blur is None else _blur_rows(blur, B, dev)          # (None: the library runs the geometry's existing entry point)
     ptr = lambda t: t.data_ptr() if t is not None else 0
     homography = None if persp is None else _persp_rows(persp, B, dev)
-    warp = [ptr(rows), ptr(homography)] if fn_name.endswith("_persp") else [ptr(rows)]   # the perspective forms take persp after affine
+    jp = None if jpeg is None else _jpeg_rows(jpeg, B, dev)
+    jpeg_form = fn_name.endswith("_jpeg")
+    warp = [ptr(rows), ptr(homography)] if jpeg_form or fn_name.endswith("_persp") else [ptr(rows)]   # the perspective forms take persp after affine
+    tail = [ptr(bl), ptr(jp)] if jpeg_form else [ptr(bl)]                                            # the JPEG forms take jpeg after blur
     lib = L.lib()
-    ws = L.workspace(lib.sd_preprocess_blur_workspace_bytes(geometry, B, Hin, Win, Wg, Hout, Wout, g0), dev)
+    ws_bytes = lib.sd_preprocess_jpeg_workspace_bytes if jpeg_form else lib.sd_preprocess_blur_workspace_bytes
+    ws = L.workspace(ws_bytes(geometry, B, Hin, Win, Wg, Hout, Wout, g0), dev)
     L.check(getattr(lib, fn_name)(source, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, hb.data_ptr(), hk.data_ptr(), hks, vb.data_ptr(),
-                                  vk.data_ptr(), vks, ptr(org), ptr(fl), ptr(order), ptr(factors), *warp, ptr(geom), ptr(mats), ptr(bl),
+                                  vk.data_ptr(), vks, ptr(org), ptr(fl), ptr(order), ptr(factors), *warp, ptr(geom), ptr(mats), *tail,
                                   (C.c_ubyte * 3)(*_FILL), (C.c_float * 3)(*mean), (C.c_float * 3)(*std), out.data_ptr(), ws.data_ptr(), ws.numel(),
                                   L.stream()), fn_name)
     return out
 
 
 def preprocess_images(images: torch.Tensor, out_size, flips=None, mean=_MEAN, std=_STD, jitter=None, affine=None, mosaic=None,
-                      window=None, letterbox=None, blur=None, persp=None) -> torch.Tensor:
+                      window=None, letterbox=None, blur=None, persp=None, jpeg=None) -> torch.Tensor:
     """images: (B, Hin, Win, 3) uint8 on the GPU; out_size = (width, height); flips: (B,) uint8 (bit 0 horizontal, bit 1 vertical)
     or None; jitter: None or (order words (B,) int32, factors (B, 3) fp32) as `jitter_words` makes them; affine: None or B rows of the 6
     coefficients of `affine_inverse_matrix` at out_size (the warp runs on the resized image, in front of the jitter, fill `_FILL`); mosaic:
@@ -438,13 +502,18 @@ def preprocess_images(images: torch.Tensor, out_size, flips=None, mean=_MEAN, st
     (R, ww, fw) as `blur_box_params` makes them: Pillow's GaussianBlur after the warp, in front of the jitter
     (`sd_preprocess_images_blur`, chosen only when blur is set; a row of r = 0 leaves its image as it is); persp: None or B rows of the 8
     coefficients of `perspective_coeffs` / `compose_affine_perspective` at out_size: the warp is that homography (`sd_preprocess_images_persp`,
-    chosen only when persp is set; not together with `affine`, which the caller folds in).
-    Returns (B, 3, height, width) fp32 = Normalize(to_tensor(flip(jitter(blur(affine(mosaic(resize(image)))))))) of transforms.py:217-226."""
+    chosen only when persp is set; not together with `affine`, which the caller folds in); jpeg: None or B rows [on, ql[64], qc[64]] as
+    `jpeg_rows` makes them: Pillow's JPEG round trip after the blur, in front of the jitter (`sd_preprocess_images_jpeg`, chosen only when
+    jpeg is set; height and width multiples of 16; a row of quality 0 leaves its image as it is).
+    Returns (B, 3, height, width) fp32 = Normalize(to_tensor(flip(jitter(jpeg(blur(affine(mosaic(resize(image))))))))) of transforms.py:217-226."""
     L.require_cuda(images)
     if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3:
         raise L.SdError(f"preprocess_images expects (B, H, W, 3) uint8, got {tuple(images.shape)} {images.dtype}")
     images = images.contiguous()
     B, Hin, Win, _ = images.shape
+    if jpeg is not None:
+        return _preprocess_blur("sd_preprocess_images_jpeg", images.data_ptr(), B, Hin, Win, out_size, flips, mean, std, jitter, affine, mosaic,
+                                window, letterbox, blur, images.device, persp, jpeg)
     if persp is not None:
         return _preprocess_blur("sd_preprocess_images_persp", images.data_ptr(), B, Hin, Win, out_size, flips, mean, std, jitter, affine, mosaic,
                                 window, letterbox, blur, images.device, persp)
@@ -510,7 +579,7 @@ def preprocess_images(images: torch.Tensor, out_size, flips=None, mean=_MEAN, st
 
 
 def preprocess_image_list(pointers: torch.Tensor, hin: int, win: int, out_size, flips=None, mean=_MEAN, std=_STD, jitter=None,
-                          affine=None, mosaic=None, window=None, letterbox=None, blur=None, persp=None) -> torch.Tensor:
+                          affine=None, mosaic=None, window=None, letterbox=None, blur=None, persp=None, jpeg=None) -> torch.Tensor:
     """`preprocess_images` over B images that are not packed together: pointers is a (B,) int64 DEVICE tensor of the device addresses of
     B (hin, win, 3) uint8 images (any byte alignment; the caller keeps them alive until the work on the current stream is done), e.g. entries
     of data/image_cache.py's DeviceImageCache.  Same arguments otherwise, same output bytes as `preprocess_images` on the stacked images."""
@@ -520,6 +589,9 @@ def preprocess_image_list(pointers: torch.Tensor, hin: int, win: int, out_size, 
     pointers = pointers.contiguous()
     dev = pointers.device
     B, Hin, Win = pointers.numel(), int(hin), int(win)
+    if jpeg is not None:
+        return _preprocess_blur("sd_preprocess_images_list_jpeg", pointers.data_ptr(), B, Hin, Win, out_size, flips, mean, std, jitter, affine,
+                                mosaic, window, letterbox, blur, dev, persp, jpeg)
     if persp is not None:
         return _preprocess_blur("sd_preprocess_images_list_persp", pointers.data_ptr(), B, Hin, Win, out_size, flips, mean, std, jitter, affine,
                                 mosaic, window, letterbox, blur, dev, persp)
@@ -654,6 +726,10 @@ class ValidationAugmentation:
         """Per sample None or the four output corners (tl, tr, br, bl), or None for the batch: validation never warps and never draws."""
         return None
 
+    def jpeg_draws_for(self, n):
+        """n JPEG qualities (0 = the sample is not compressed) or None: validation never compresses and never draws."""
+        return None
+
     @staticmethod
     def size_groups(images):
         """{(hin, win): (indices into the batch, stack of those images)} of what `__call__` accepts as `images`."""
@@ -704,6 +780,7 @@ class ValidationAugmentation:
         transposes = self.transpose_draws_for(n)
         blurs = self.blur_draws_for(n)
         quads = self.perspective_draws_for(n)
+        qualities = self.jpeg_draws_for(n)
         homography = forward8 = None
         if quads is not None:                                        # the warp slot becomes one homography per image: affine, then perspective
             frame = [(0.0, 0.0), (float(W), 0.0), (float(W), float(H)), (0.0, float(H))]
@@ -731,6 +808,8 @@ class ValidationAugmentation:
                 kw["window"] = (windows[0], [windows[1][i] for i in idx])
             if blurs is not None:                                    # photometric: the annotations do not move
                 kw["blur"] = [blur_box_params(blurs[i]) for i in idx]
+            if qualities is not None:                                # photometric as well
+                kw["jpeg"] = jpeg_rows(qualities[i] for i in idx)
             box = None
             if self.keep_aspect:                                     # one geometry per size group, at the current (multi-scale) size
                 box = kw["letterbox"] = letterbox_geometry((win, hin), (W, H))
@@ -800,6 +879,7 @@ class TrainAugmentation(ValidationAugmentation):
         self.transpose = float(getattr(args, "aug_transpose", 0.0))        # per-image probability of being transposed (square sizes only)
         self.blur = float(getattr(args, "aug_blur", 0.0) or 0.0)           # gaussian radius uniform in [0, blur] pixels for a selected image
         self.perspective = float(getattr(args, "aug_perspective", 0.0) or 0.0)   # distortion scale of a selected image's corner insets
+        self.jpeg = int(getattr(args, "aug_jpeg", 0) or 0)                 # a selected image is JPEG-compressed at a quality uniform in [jpeg, 95]
         self.train_tiles = parse_tiles(getattr(args, "train_tiles", ""), "train_tiles")   # (Tx, Ty) of the canvas the windows are cut from, () = off
         self.tile_overlap = int(getattr(args, "tile_overlap", 64))
 
@@ -900,6 +980,16 @@ class TrainAugmentation(ValidationAugmentation):
             quads.append([(u1 * d * W / 2, u2 * d * H / 2), (W - u3 * d * W / 2, u4 * d * H / 2), (W - u5 * d * W / 2, H - u6 * d * H / 2),
                           (u7 * d * W / 2, H - u8 * d * H / 2)] if u0 < self.prob else None)
         return quads
+
+    def jpeg_draws_for(self, n):
+        """n JPEG qualities from ONE more draw on torch's global generator, `rand(n, 2)` in float64, made after that of
+        `perspective_draws_for`: sample i is compressed when u0 < `prob`, at the quality min(95, QMIN + int(u1 (96 - QMIN))), uniform over
+        the integers of [QMIN, 95]; else its quality is 0 (a copy row of the table).  None, and no draw at all, with `--aug_jpeg 0` or
+        augmentation off."""
+        if self.args.no_augmentation or self.jpeg == 0:
+            return None
+        u = torch.rand(n, 2, dtype=torch.float64).tolist()
+        return [min(JPEG_MAX_QUALITY, self.jpeg + int(u1 * (JPEG_MAX_QUALITY + 1 - self.jpeg))) if u0 < self.prob else 0 for u0, u1 in u]
 
     def trigger_random_resize(self):
         if self.args.no_augmentation:

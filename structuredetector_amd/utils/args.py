@@ -143,6 +143,12 @@ _FLAGS = [
                                   "into one homography, so an image is resampled once, byte for byte Pillow's Image.transform("
                                   "PERSPECTIVE, BILINEAR); keypoints that leave the frame are dropped. Needs a directory (not "
                                   "--synthetic). Not consulted by evaluate / detect. 0 = off.")),
+    (("--aug_jpeg",), dict(type=int, default=0, metavar="QMIN", help="Training augmentation: with the flip probability's threshold "
+                           "(u < 0.5) an image is JPEG-compressed and decoded again at a quality uniform over the integers of [QMIN, 95] "
+                           "(5 <= QMIN <= 95), byte for byte Pillow's save(quality=q) + open(): the 8 x 8 blocking, ringing and chroma "
+                           "smearing of a camera's encoder, on the grid of the network input. After the blur and before the colour "
+                           "jitter; annotations are untouched. Needs a directory (not --synthetic). Not consulted by evaluate / detect. "
+                           "0 = off.")),
 ]
 
 _POSITIVE = ["in_channels", "fpn_depth", "batch_size", "epochs", "learning_rate", "down_ratio", "max_objects", "max_parts"]
@@ -309,6 +315,20 @@ def check_aug_perspective(args):
     return d
 
 
+MIN_AUG_JPEG, MAX_AUG_JPEG = 5, 95  # qualities: below 5 every block is its mean, above 95 Pillow advises against (tables of ones)
+
+
+def check_aug_jpeg(args):
+    """`--aug_jpeg` on a parsed namespace -> QMIN, as `train` checks it (model/trainer.py): 0 (off) or an integer in [5, 95];
+    `--synthetic` renders network-input tensors and has no 8-bit image to compress, so the flag is refused there."""
+    q = getattr(args, "aug_jpeg", 0) or 0
+    if isinstance(q, bool) or not isinstance(q, int) or not (q == 0 or MIN_AUG_JPEG <= q <= MAX_AUG_JPEG):
+        raise ValueError(f"'aug_jpeg' should be 0 (off) or an integer in [{MIN_AUG_JPEG}, {MAX_AUG_JPEG}], not {q}")
+    if q > 0 and getattr(args, "synthetic", 0):
+        raise ValueError("'aug_jpeg' compresses source images: it needs --train_dir, not --synthetic")
+    return q
+
+
 def finalize(args):
     """Validation + derived fields (args.py:178-269) on an already parsed namespace."""
     for side in ("width", "height"):
@@ -332,6 +352,7 @@ def finalize(args):
     assert 0 <= getattr(args, "aug_transpose", 0.0) <= 1, "'aug_transpose' should be in [0, 1]"
     assert 0 <= getattr(args, "aug_blur", 0.0) <= MAX_AUG_BLUR, "'aug_blur' should be in [0, 8]"
     assert 0 <= getattr(args, "aug_perspective", 0.0) <= MAX_AUG_PERSPECTIVE, "'aug_perspective' should be in [0, 0.9]"
+    assert getattr(args, "aug_jpeg", 0) == 0 or MIN_AUG_JPEG <= getattr(args, "aug_jpeg", 0) <= MAX_AUG_JPEG, "'aug_jpeg' should be 0 or in [5, 95]"
     args.label_nms = check_label_nms(getattr(args, "label_nms", 0))
     args.tta_scales = parse_tta_scales(getattr(args, "tta_scales", ""))
     args.tiles = parse_tiles(getattr(args, "tiles", ""))
