@@ -568,6 +568,42 @@ int sd_preprocess_images_list_jpeg(const uint8_t* const* images, int geometry, i
                                    const int* blur, const int* jpeg, const uint8_t fill3[3], const float* mean3, const float* std3, float* out,
                                    void* workspace, size_t workspace_bytes, sd_stream_t stream);
 
+/* Histogram tone curves of 8-bit images (training augmentation, `train --aug_equalize / --aug_autocontrast`): image b becomes what Pillow's
+ * ImageOps.equalize(img) (mode 2) or ImageOps.autocontrast(img, cutoff) (mode 1) gives, byte for byte: per channel a 256-bin histogram of
+ * the image's own pixels, a 256-entry table made from it, a look-up (tests/tone_ref.py states both tables; equalize is 32-bit unsigned
+ * integer arithmetic, autocontrast one IEEE double expression whose product and sum are rounded separately).  table (B, 4) int32 on the
+ * DEVICE: a row is [mode, cut_lo, cut_hi, 0]; cut_lo / cut_hi are the numbers of darkest / brightest pixels autocontrast ignores, Pillow's
+ * int(H * W * cutoff // 100) (data/augment.py tone_rows).  Mode 0 and every mode other than 1 and 2 copies its image.  The cuts are
+ * clamped to [0, H * W]; nothing in a row decides an address, so any table is memory-safe.  in and out are (B, H, W, 3) uint8, any
+ * H, W >= 1 with H * W < 2^31 and any byte alignment; out may be in (in place), any other overlap is SD_ERR_INVALID.  workspace:
+ * sd_tone_workspace_bytes() bytes, 16-byte aligned -- the (B, 3, 256) uint32 histograms (the tables are made in LDS by the look-up
+ * launch).  One memset and two launches; a histogram block covers SD_TONE_STRIP_PIXELS pixels of one image.  B <= 65535. */
+#define SD_TONE_STRIP_PIXELS 16384
+size_t sd_tone_workspace_bytes(int B);
+int sd_tone_u8(const uint8_t* in, uint8_t* out, int B, int H, int W, const int* table, void* workspace, size_t workspace_bytes,
+               sd_stream_t stream);
+
+/* The JPEG forms with the tone stage between the JPEG round trip and the jitter:
+ *     Resize | Window | Letterbox -> [Mosaic] -> [Affine | Perspective] -> [Blur] -> [JPEG] -> Tone -> [ColorJitter] -> flips -> Normalize.
+ * The arguments of sd_preprocess_images_jpeg / _list_jpeg plus tone (B, 4) int32 on the device after jpeg, as sd_tone_u8's table.  With
+ * tone null the call IS the JPEG form.  With tone set every other table is optional and the workspace must be 16-byte aligned
+ * (SD_ERR_INVALID otherwise); the stage has no size rule of its own (Hout and Wout must be multiples of 16 only when jpeg is set too).
+ * The histogram is that of the 8-bit frame as it stands there, fill colour and letterbox bars included.  workspace:
+ * sd_preprocess_tone_workspace_bytes() bytes = sd_preprocess_jpeg_workspace_bytes() in that layout, then sd_tone_workspace_bytes(). */
+size_t sd_preprocess_tone_workspace_bytes(int geometry, int B, int Hin, int Win, int Wg, int Hout, int Wout, int g0);
+int sd_preprocess_images_tone(const uint8_t* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout, int g0, int g1,
+                              const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize,
+                              const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
+                              const double* affine, const double* persp, const int* mosaic_geom, const double* mosaic_affine, const int* blur,
+                              const int* jpeg, const int* tone, const uint8_t fill3[3], const float* mean3, const float* std3, float* out,
+                              void* workspace, size_t workspace_bytes, sd_stream_t stream);
+int sd_preprocess_images_list_tone(const uint8_t* const* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout,
+                                   int g0, int g1, const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk,
+                                   int v_ksize, const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
+                                   const double* affine, const double* persp, const int* mosaic_geom, const double* mosaic_affine,
+                                   const int* blur, const int* jpeg, const int* tone, const uint8_t fill3[3], const float* mean3,
+                                   const float* std3, float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream);
+
 /* ---- loss: src/sdnet/model/loss.py:17-64,91-117------------------------------------------- */
 
 #define SD_HM_MSE   0

@@ -152,6 +152,15 @@ _SIGNATURES = {
                                   [C.POINTER(C.c_ubyte), C.POINTER(c_float), C.POINTER(c_float), c_vp, c_vp, c_size, c_vp]),
     "sd_preprocess_images_list_jpeg": (c_int, [c_vp] + [c_int] * 10 + [c_vp, c_vp, c_int, c_vp, c_vp, c_int] + [c_vp] * 10 +
                                        [C.POINTER(C.c_ubyte), C.POINTER(c_float), C.POINTER(c_float), c_vp, c_vp, c_size, c_vp]),
+    # tone curves of 8-bit images: in, out (may be in), B, H, W, table (B, 4) int32 device = mode (1 autocontrast, 2 equalize), cut_lo, cut_hi, 0, workspace, ...
+    "sd_tone_workspace_bytes": (c_size, [c_int]),
+    "sd_tone_u8": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_size, c_vp]),
+    # the JPEG forms with tone (B, 4) int32 device after jpeg (null: the JPEG form)
+    "sd_preprocess_tone_workspace_bytes": (c_size, [c_int] * 8),
+    "sd_preprocess_images_tone": (c_int, [c_vp] + [c_int] * 10 + [c_vp, c_vp, c_int, c_vp, c_vp, c_int] + [c_vp] * 11 +
+                                  [C.POINTER(C.c_ubyte), C.POINTER(c_float), C.POINTER(c_float), c_vp, c_vp, c_size, c_vp]),
+    "sd_preprocess_images_list_tone": (c_int, [c_vp] + [c_int] * 10 + [c_vp, c_vp, c_int, c_vp, c_vp, c_int] + [c_vp] * 11 +
+                                       [C.POINTER(C.c_ubyte), C.POINTER(c_float), C.POINTER(c_float), c_vp, c_vp, c_size, c_vp]),
     "sd_render_targets": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_float, c_vp, c_vp]),
     "sd_loss_workspace_bytes": (c_size, [c_int] * 5),
     "sd_loss_fwd": (c_int, [C.POINTER(LossDesc), c_vp, c_vp, c_size, c_vp]),

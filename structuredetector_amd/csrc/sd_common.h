@@ -93,6 +93,11 @@ int blur_stage(const uint8_t* in, uint8_t* mid, uint8_t* out, int B, int H, int 
 size_t jpeg_planes_bytes(int B, int H, int W);
 int jpeg_stage(const uint8_t* in, uint8_t* out, uint8_t* planes, int B, int H, int W, const int* table, hipStream_t st);
 
+// Histogram tone stage (sd_tone.hip): in -> out, (B, H, W, 3) u8 of any alignment, out may be in.  ws: tone_workspace_bytes() bytes,
+// 16-byte aligned.  table (B, 4) int32 on the device.  Shapes are the caller's to check (B is a grid dimension: <= 65535; H W < 2^31).
+size_t tone_workspace_bytes(int B);
+int tone_stage(const uint8_t* in, uint8_t* out, void* ws, int B, int H, int W, const int* table, hipStream_t st);
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);

@@ -1411,14 +1411,15 @@ size_t sd_preprocess_blur_workspace_bytes(int geometry, int B, int Hin, int Win,
 
 // the blur and perspective forms proper (blur or persp set): the checks of the geometry's entry point, its horizontal pass, its vertical
 // pass into an 8-bit image, the 8-bit stages -- the warp slot is k_affine_u8 or k_persp_u8 --, the blur unless its table is null, the JPEG
-// round trip unless its table is null (sd_jpeg.hip: jpeg_stage, on image A in place; its planes lie behind image B), and the jitter or
+// round trip unless its table is null (sd_jpeg.hip: jpeg_stage, on image A in place; its planes lie behind image B), the tone stage unless
+// its table is null (sd_tone.hip: tone_stage, on image A in place; its histograms and tables lie behind the planes), and the jitter or
 // plain tail
 static int preprocess_blur(const char* what, bool list, const void* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout,
                            int g0, int g1, const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize,
                            const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors, const double* affine,
                            const double* persp, const int* mosaic_geom, const double* mosaic_affine, const int* blur, const int* jpeg,
-                           const uint8_t* fill3, const float* mean3, const float* std3, float* out, void* workspace, size_t workspace_bytes,
-                           hipStream_t st) {
+                           const int* tone, const uint8_t* fill3, const float* mean3, const float* std3, float* out, void* workspace,
+                           size_t workspace_bytes, hipStream_t st) {
     const double* warp = affine ? affine : persp;                        // one warp slot: the callers refuse both together
     const uint8_t* packed = reinterpret_cast<const uint8_t*>(images);
     const uint8_t* const* table = reinterpret_cast<const uint8_t* const*>(images);
@@ -1473,6 +1474,13 @@ static int preprocess_blur(const char* what, bool list, const void* images, int 
         SD_REQUIRE(aligned16(workspace), SD_ERR_INVALID, "%s: jpeg needs a 16-byte aligned workspace", what);
         SD_REQUIRE(workspace_bytes >= planes_at + jpeg_planes_bytes(B, Hout, Wout), SD_ERR_WORKSPACE, "%s: workspace %zu < %zu", what, workspace_bytes,
                    planes_at + jpeg_planes_bytes(B, Hout, Wout));
+    }
+    const size_t tone_at = planes_at + jpeg_planes_bytes(B, Hout, Wout);                                      // a multiple of 256
+    if (tone) {
+        SD_REQUIRE((int64_t)Hout * Wout < (1ll << 31), SD_ERR_INVALID, "%s: tone needs a frame of fewer than 2^31 pixels, not %d x %d", what, Wout, Hout);
+        SD_REQUIRE(aligned16(workspace), SD_ERR_INVALID, "%s: tone needs a 16-byte aligned workspace", what);
+        SD_REQUIRE(workspace_bytes >= tone_at + tone_workspace_bytes(B), SD_ERR_WORKSPACE, "%s: workspace %zu < %zu", what, workspace_bytes,
+                   tone_at + tone_workspace_bytes(B));
     }
 
     uint8_t* tmp = reinterpret_cast<uint8_t*>(workspace);
@@ -1540,6 +1548,8 @@ static int preprocess_blur(const char* what, bool list, const void* images, int 
         if (int e = blur_stage(cur, img_b, img_a, B, Hout, Wout, blur, st)) return e;
     if (jpeg)                                                            // the last 8-bit image, in place: the second launch reads the planes only
         if (int e = jpeg_stage(img_a, img_a, tmp + planes_at, B, Hout, Wout, jpeg, st)) return e;
+    if (tone)                                                            // in place as well: every byte is read and written by one thread
+        if (int e = tone_stage(img_a, img_a, tmp + tone_at, B, Hout, Wout, tone, st)) return e;
     if (jitter_order) return jitter_norm(B, Hout, Wout, flips, jitter_order, jitter_factors, mean3, std3, out, img_a, lsum, st);
     hipLaunchKernelGGL(k_u8_norm, flat, dim3(256), 0, st, img_a, out, Hout, Wout, flips, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], B);
     SD_LAUNCH_CHECK();
@@ -1554,7 +1564,7 @@ int sd_preprocess_images_blur(const uint8_t* images, int geometry, int B, int Hi
     const char* what = "sd_preprocess_images_blur";
     if (blur)
         return preprocess_blur(what, false, images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
-                               window, flips, jitter_order, jitter_factors, affine, nullptr, mosaic_geom, mosaic_affine, blur, nullptr, fill3, mean3, std3,
+                               window, flips, jitter_order, jitter_factors, affine, nullptr, mosaic_geom, mosaic_affine, blur, nullptr, nullptr, fill3, mean3, std3,
                                out, workspace, workspace_bytes, (hipStream_t)stream);
     if (geometry == SD_GEOM_WINDOW)
         return sd_preprocess_images_window(images, B, Hin, Win, Hg, Wg, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, window, g0, g1, flips,
@@ -1588,7 +1598,7 @@ int sd_preprocess_images_list_blur(const uint8_t* const* images, int geometry, i
     const char* what = "sd_preprocess_images_list_blur";
     if (blur)
         return preprocess_blur(what, true, images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
-                               window, flips, jitter_order, jitter_factors, affine, nullptr, mosaic_geom, mosaic_affine, blur, nullptr, fill3, mean3, std3,
+                               window, flips, jitter_order, jitter_factors, affine, nullptr, mosaic_geom, mosaic_affine, blur, nullptr, nullptr, fill3, mean3, std3,
                                out, workspace, workspace_bytes, (hipStream_t)stream);
     if (geometry == SD_GEOM_WINDOW)
         return sd_preprocess_images_list_window(images, B, Hin, Win, Hg, Wg, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, window, g0, g1,
@@ -1644,7 +1654,7 @@ int sd_preprocess_images_persp(const uint8_t* images, int geometry, int B, int H
     SD_REQUIRE(!affine, SD_ERR_INVALID, "%s: persp and affine do not combine (fold the affine matrix into the homography)", what);
     SD_REQUIRE(fill3, SD_ERR_INVALID, "%s: a warp needs a fill colour", what);
     return preprocess_blur(what, false, images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
-                           window, flips, jitter_order, jitter_factors, nullptr, persp, mosaic_geom, mosaic_affine, blur, nullptr, fill3, mean3, std3, out,
+                           window, flips, jitter_order, jitter_factors, nullptr, persp, mosaic_geom, mosaic_affine, blur, nullptr, nullptr, fill3, mean3, std3, out,
                            workspace, workspace_bytes, (hipStream_t)stream);
 }
 
@@ -1662,7 +1672,7 @@ int sd_preprocess_images_list_persp(const uint8_t* const* images, int geometry, 
     SD_REQUIRE(!affine, SD_ERR_INVALID, "%s: persp and affine do not combine (fold the affine matrix into the homography)", what);
     SD_REQUIRE(fill3, SD_ERR_INVALID, "%s: a warp needs a fill colour", what);
     return preprocess_blur(what, true, images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
-                           window, flips, jitter_order, jitter_factors, nullptr, persp, mosaic_geom, mosaic_affine, blur, nullptr, fill3, mean3, std3, out,
+                           window, flips, jitter_order, jitter_factors, nullptr, persp, mosaic_geom, mosaic_affine, blur, nullptr, nullptr, fill3, mean3, std3, out,
                            workspace, workspace_bytes, (hipStream_t)stream);
 }
 
@@ -1687,7 +1697,7 @@ int sd_preprocess_images_jpeg(const uint8_t* images, int geometry, int B, int Hi
                                           std3, out, workspace, workspace_bytes, stream);
     SD_REQUIRE(!(affine && persp), SD_ERR_INVALID, "%s: persp and affine do not combine (fold the affine matrix into the homography)", what);
     return preprocess_blur(what, false, images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
-                           window, flips, jitter_order, jitter_factors, affine, persp, mosaic_geom, mosaic_affine, blur, jpeg, fill3, mean3, std3, out,
+                           window, flips, jitter_order, jitter_factors, affine, persp, mosaic_geom, mosaic_affine, blur, jpeg, nullptr, fill3, mean3, std3, out,
                            workspace, workspace_bytes, (hipStream_t)stream);
 }
 
@@ -1704,8 +1714,50 @@ int sd_preprocess_images_list_jpeg(const uint8_t* const* images, int geometry, i
                                                fill3, mean3, std3, out, workspace, workspace_bytes, stream);
     SD_REQUIRE(!(affine && persp), SD_ERR_INVALID, "%s: persp and affine do not combine (fold the affine matrix into the homography)", what);
     return preprocess_blur(what, true, images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
-                           window, flips, jitter_order, jitter_factors, affine, persp, mosaic_geom, mosaic_affine, blur, jpeg, fill3, mean3, std3, out,
+                           window, flips, jitter_order, jitter_factors, affine, persp, mosaic_geom, mosaic_affine, blur, jpeg, nullptr, fill3, mean3, std3, out,
                            workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+// ---- histogram tone curves between the JPEG round trip and the jitter (sd_tone.hip: tone_stage), behind any geometry ----
+// tone null: the JPEG form, a call.  tone set: preprocess_blur's chain with the one more stage, every other table optional;
+// workspace: the JPEG form's, then the histograms and the tables.
+size_t sd_preprocess_tone_workspace_bytes(int geometry, int B, int Hin, int Win, int Wg, int Hout, int Wout, int g0) {
+    if (B <= 0 || Hout <= 0 || Wout <= 0) return sd_preprocess_jpeg_workspace_bytes(geometry, B, Hin, Win, Wg, Hout, Wout, g0);
+    return sd_preprocess_jpeg_workspace_bytes(geometry, B, Hin, Win, Wg, Hout, Wout, g0) + tone_workspace_bytes(B);
+}
+
+int sd_preprocess_images_tone(const uint8_t* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout, int g0, int g1,
+                              const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize,
+                              const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
+                              const double* affine, const double* persp, const int* mosaic_geom, const double* mosaic_affine, const int* blur,
+                              const int* jpeg, const int* tone, const uint8_t* fill3, const float* mean3, const float* std3, float* out,
+                              void* workspace, size_t workspace_bytes, sd_stream_t stream) {
+    const char* what = "sd_preprocess_images_tone";
+    if (!tone)
+        return sd_preprocess_images_jpeg(images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
+                                         window, flips, jitter_order, jitter_factors, affine, persp, mosaic_geom, mosaic_affine, blur, jpeg, fill3,
+                                         mean3, std3, out, workspace, workspace_bytes, stream);
+    SD_REQUIRE(!(affine && persp), SD_ERR_INVALID, "%s: persp and affine do not combine (fold the affine matrix into the homography)", what);
+    return preprocess_blur(what, false, images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
+                           window, flips, jitter_order, jitter_factors, affine, persp, mosaic_geom, mosaic_affine, blur, jpeg, tone, fill3, mean3, std3,
+                           out, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int sd_preprocess_images_list_tone(const uint8_t* const* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout,
+                                   int g0, int g1, const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk,
+                                   int v_ksize, const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
+                                   const double* affine, const double* persp, const int* mosaic_geom, const double* mosaic_affine, const int* blur,
+                                   const int* jpeg, const int* tone, const uint8_t* fill3, const float* mean3, const float* std3, float* out,
+                                   void* workspace, size_t workspace_bytes, sd_stream_t stream) {
+    const char* what = "sd_preprocess_images_list_tone";
+    if (!tone)
+        return sd_preprocess_images_list_jpeg(images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk,
+                                              v_ksize, window, flips, jitter_order, jitter_factors, affine, persp, mosaic_geom, mosaic_affine, blur,
+                                              jpeg, fill3, mean3, std3, out, workspace, workspace_bytes, stream);
+    SD_REQUIRE(!(affine && persp), SD_ERR_INVALID, "%s: persp and affine do not combine (fold the affine matrix into the homography)", what);
+    return preprocess_blur(what, true, images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
+                           window, flips, jitter_order, jitter_factors, affine, persp, mosaic_geom, mosaic_affine, blur, jpeg, tone, fill3, mean3, std3,
+                           out, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -38,6 +38,10 @@ JPEG (`--aug_jpeg QMIN`; not in the reference): between the blur and the ColorJi
 `save(buf, "JPEG", quality=q)` then `open(buf)` gives, byte for byte -- colour conversion, 4:2:0 chroma, the accurate-integer DCT of every
 8 x 8 block, the quantiser and the way back, all integer (`sd_jpeg_u8`; in the chain `sd_preprocess_images_jpeg`); the two quantisation
 tables of a quality come from the host (`jpeg_quant_tables`).  Photometric: annotations are untouched.
+Tone (`--aug_equalize P` / `--aug_autocontrast P`; not in the reference): after the JPEG round trip, in front of the ColorJitter, a selected
+image is Pillow's `ImageOps.equalize(img)` or `ImageOps.autocontrast(img, cutoff)`, byte for byte -- a look-up table per channel made from
+the histogram of the 8-bit frame as it stands there, fill colour and letterbox bars included (`sd_tone_u8`; in the chain
+`sd_preprocess_images_tone`); the host only turns the cutoff into pixel counts (`tone_rows`).  Photometric: annotations are untouched.
 Transpose (`--aug_transpose P`; not in the reference): last, after the flips, a selected image of the assembled (square) batch has its x and
 y swapped (`sd_transpose_select`, one launch: lossless, with the flips the eight symmetries of the grid); the annotations follow with
 `utils.misc.transpose_annotation`.
@@ -430,16 +434,56 @@ def jpeg_images(images: torch.Tensor, rows) -> torch.Tensor:
     return out
 
 
+TONE_COPY, TONE_AUTOCONTRAST, TONE_EQUALIZE = 0, 1, 2               # the modes of `sd_tone_u8`'s table
+TONE_STRIP_PIXELS = 16384                                            # include/sdnet_hip.h SD_TONE_STRIP_PIXELS: pixels of a histogram block
+
+
+def tone_rows(draws, n_pixels):
+    """One row [mode, cut_lo, cut_hi, 0] of `sd_tone_u8`'s table per draw (mode, cutoff percent) on images of n_pixels pixels: the two cuts
+    are Pillow's `int(n * cutoff // 100)` with the cutoff a Python float, the number of darkest and of brightest pixels that
+    `ImageOps.autocontrast(img, cutoff)` ignores; 0 for the other modes."""
+    rows = []
+    for mode, cutoff in draws:
+        cut = int(int(n_pixels) * float(cutoff) // 100) if int(mode) == TONE_AUTOCONTRAST else 0
+        rows.append([int(mode), cut, cut, 0])
+    return rows
+
+
+def _tone_rows(rows, B, device):
+    table = torch.as_tensor(np.asarray(rows, dtype=np.int64).astype(np.int32)).reshape(-1, 4).contiguous()
+    if table.shape[0] != B:
+        raise L.SdError("tone must have one row (mode, cut_lo, cut_hi, 0) per image")
+    return table.to(device, non_blocking=True)
+
+
+def tone_images(images: torch.Tensor, rows) -> torch.Tensor:
+    """images: (B, H, W, 3) uint8 on the GPU, any H and W; rows: B rows [mode, cut_lo, cut_hi, 0] as `tone_rows` makes them.  Returns a
+    new tensor, image b = Pillow's `ImageOps.autocontrast` (mode 1) or `ImageOps.equalize` (mode 2) of image b byte for byte, or image b
+    itself (`sd_tone_u8`: the stand-alone stage of the chain)."""
+    L.require_cuda(images)
+    if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3:
+        raise L.SdError(f"tone_images expects (B, H, W, 3) uint8, got {tuple(images.shape)} {images.dtype}")
+    images = images.contiguous()
+    B, H, W, _ = images.shape
+    table = _tone_rows(rows, B, images.device)
+    out = torch.empty_like(images)
+    lib = L.lib()
+    ws = L.workspace(lib.sd_tone_workspace_bytes(B), images.device)
+    L.check(lib.sd_tone_u8(images.data_ptr(), out.data_ptr(), B, H, W, table.data_ptr(), ws.data_ptr(), ws.numel(), L.stream()), "sd_tone_u8")
+    return out
+
+
 JPEG_MAX_QUALITY = 95                                                # the upper end of `--aug_jpeg`'s quality range (Pillow's advised maximum)
 GEOM_STRETCH, GEOM_WINDOW, GEOM_LETTERBOX = 0, 1, 2                  # include/sdnet_hip.h SD_GEOM_*
 
 
 def _preprocess_blur(fn_name, source, B, Hin, Win, out_size, flips, mean, std, jitter, affine, mosaic, window, letterbox, blur, dev, persp=None,
-                     jpeg=None):
+                     jpeg=None, tone=None):
     """The blur forms of `preprocess_images` / `preprocess_image_list` (`sd_preprocess_images_blur` / `..._list_blur`): any geometry, every
     optional stage, the blur between the warp and the jitter.  source = the address of the packed images or of the pointer table.  With
     `persp` the perspective forms (`sd_preprocess_images_persp` / `..._list_persp`): the same arguments plus the homography table.  With
-    `jpeg` the JPEG forms (`sd_preprocess_images_jpeg` / `..._list_jpeg`): those arguments plus the quantisation tables after the blur's."""
+    `jpeg` the JPEG forms (`sd_preprocess_images_jpeg` / `..._list_jpeg`): those arguments plus the quantisation tables after the blur's.  With
+    `tone` the tone forms (`sd_preprocess_images_tone` / `..._list_tone`): those plus the tone table after the quantisation tables."""
     if persp is not None and affine is not None:
         raise L.SdError("preprocess: persp and affine do not combine (fold the affine matrix in with compose_affine_perspective)")
     Wout, Hout = int(out_size[0]), int(out_size[1])
@@ -475,11 +519,16 @@ def _preprocess_blur(fn_name, source, B, Hin, Win, out_size, flips, mean, std, j
     ptr = lambda t: t.data_ptr() if t is not None else 0
     homography = None if persp is None else _persp_rows(persp, B, dev)
     jp = None if jpeg is None else _jpeg_rows(jpeg, B, dev)
-    jpeg_form = fn_name.endswith("_jpeg")
+    tn = None if tone is None else _tone_rows(tone, B, dev)
+    tone_form = fn_name.endswith("_tone")
+    jpeg_form = tone_form or fn_name.endswith("_jpeg")
     warp = [ptr(rows), ptr(homography)] if jpeg_form or fn_name.endswith("_persp") else [ptr(rows)]   # the perspective forms take persp after affine
     tail = [ptr(bl), ptr(jp)] if jpeg_form else [ptr(bl)]                                            # the JPEG forms take jpeg after blur
+    if tone_form:
+        tail.append(ptr(tn))                                                                         # the tone forms take tone after jpeg
     lib = L.lib()
-    ws_bytes = lib.sd_preprocess_jpeg_workspace_bytes if jpeg_form else lib.sd_preprocess_blur_workspace_bytes
+    ws_bytes = (lib.sd_preprocess_tone_workspace_bytes if tone_form else
+                lib.sd_preprocess_jpeg_workspace_bytes if jpeg_form else lib.sd_preprocess_blur_workspace_bytes)
     ws = L.workspace(ws_bytes(geometry, B, Hin, Win, Wg, Hout, Wout, g0), dev)
     L.check(getattr(lib, fn_name)(source, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, hb.data_ptr(), hk.data_ptr(), hks, vb.data_ptr(),
                                   vk.data_ptr(), vks, ptr(org), ptr(fl), ptr(order), ptr(factors), *warp, ptr(geom), ptr(mats), *tail,
@@ -489,7 +538,7 @@ def _preprocess_blur(fn_name, source, B, Hin, Win, out_size, flips, mean, std, j
 
 
 def preprocess_images(images: torch.Tensor, out_size, flips=None, mean=_MEAN, std=_STD, jitter=None, affine=None, mosaic=None,
-                      window=None, letterbox=None, blur=None, persp=None, jpeg=None) -> torch.Tensor:
+                      window=None, letterbox=None, blur=None, persp=None, jpeg=None, tone=None) -> torch.Tensor:
     """images: (B, Hin, Win, 3) uint8 on the GPU; out_size = (width, height); flips: (B,) uint8 (bit 0 horizontal, bit 1 vertical)
     or None; jitter: None or (order words (B,) int32, factors (B, 3) fp32) as `jitter_words` makes them; affine: None or B rows of the 6
     coefficients of `affine_inverse_matrix` at out_size (the warp runs on the resized image, in front of the jitter, fill `_FILL`); mosaic:
@@ -504,13 +553,19 @@ def preprocess_images(images: torch.Tensor, out_size, flips=None, mean=_MEAN, st
     coefficients of `perspective_coeffs` / `compose_affine_perspective` at out_size: the warp is that homography (`sd_preprocess_images_persp`,
     chosen only when persp is set; not together with `affine`, which the caller folds in); jpeg: None or B rows [on, ql[64], qc[64]] as
     `jpeg_rows` makes them: Pillow's JPEG round trip after the blur, in front of the jitter (`sd_preprocess_images_jpeg`, chosen only when
-    jpeg is set; height and width multiples of 16; a row of quality 0 leaves its image as it is).
-    Returns (B, 3, height, width) fp32 = Normalize(to_tensor(flip(jitter(jpeg(blur(affine(mosaic(resize(image))))))))) of transforms.py:217-226."""
+    jpeg is set; height and width multiples of 16; a row of quality 0 leaves its image as it is); tone: None or B rows [mode, cut_lo, cut_hi,
+    0] as `tone_rows` makes them: Pillow's autocontrast or equalize after the JPEG round trip, in front of the jitter
+    (`sd_preprocess_images_tone`, chosen only when tone is set; any size; a row of mode 0 leaves its image as it is).
+    Returns (B, 3, height, width) fp32 = Normalize(to_tensor(flip(jitter(tone(jpeg(blur(affine(mosaic(resize(image)))))))))) of
+    transforms.py:217-226."""
     L.require_cuda(images)
     if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3:
         raise L.SdError(f"preprocess_images expects (B, H, W, 3) uint8, got {tuple(images.shape)} {images.dtype}")
     images = images.contiguous()
     B, Hin, Win, _ = images.shape
+    if tone is not None:
+        return _preprocess_blur("sd_preprocess_images_tone", images.data_ptr(), B, Hin, Win, out_size, flips, mean, std, jitter, affine, mosaic,
+                                window, letterbox, blur, images.device, persp, jpeg, tone)
     if jpeg is not None:
         return _preprocess_blur("sd_preprocess_images_jpeg", images.data_ptr(), B, Hin, Win, out_size, flips, mean, std, jitter, affine, mosaic,
                                 window, letterbox, blur, images.device, persp, jpeg)
@@ -579,7 +634,7 @@ def preprocess_images(images: torch.Tensor, out_size, flips=None, mean=_MEAN, st
 
 
 def preprocess_image_list(pointers: torch.Tensor, hin: int, win: int, out_size, flips=None, mean=_MEAN, std=_STD, jitter=None,
-                          affine=None, mosaic=None, window=None, letterbox=None, blur=None, persp=None, jpeg=None) -> torch.Tensor:
+                          affine=None, mosaic=None, window=None, letterbox=None, blur=None, persp=None, jpeg=None, tone=None) -> torch.Tensor:
     """`preprocess_images` over B images that are not packed together: pointers is a (B,) int64 DEVICE tensor of the device addresses of
     B (hin, win, 3) uint8 images (any byte alignment; the caller keeps them alive until the work on the current stream is done), e.g. entries
     of data/image_cache.py's DeviceImageCache.  Same arguments otherwise, same output bytes as `preprocess_images` on the stacked images."""
@@ -589,6 +644,9 @@ def preprocess_image_list(pointers: torch.Tensor, hin: int, win: int, out_size, 
     pointers = pointers.contiguous()
     dev = pointers.device
     B, Hin, Win = pointers.numel(), int(hin), int(win)
+    if tone is not None:
+        return _preprocess_blur("sd_preprocess_images_list_tone", pointers.data_ptr(), B, Hin, Win, out_size, flips, mean, std, jitter, affine,
+                                mosaic, window, letterbox, blur, dev, persp, jpeg, tone)
     if jpeg is not None:
         return _preprocess_blur("sd_preprocess_images_list_jpeg", pointers.data_ptr(), B, Hin, Win, out_size, flips, mean, std, jitter, affine,
                                 mosaic, window, letterbox, blur, dev, persp, jpeg)
@@ -730,6 +788,10 @@ class ValidationAugmentation:
         """n JPEG qualities (0 = the sample is not compressed) or None: validation never compresses and never draws."""
         return None
 
+    def tone_draws_for(self, n):
+        """n tone draws (mode, cutoff percent) or None: validation never changes the tone curve and never draws."""
+        return None
+
     @staticmethod
     def size_groups(images):
         """{(hin, win): (indices into the batch, stack of those images)} of what `__call__` accepts as `images`."""
@@ -781,6 +843,7 @@ class ValidationAugmentation:
         blurs = self.blur_draws_for(n)
         quads = self.perspective_draws_for(n)
         qualities = self.jpeg_draws_for(n)
+        tones = self.tone_draws_for(n)
         homography = forward8 = None
         if quads is not None:                                        # the warp slot becomes one homography per image: affine, then perspective
             frame = [(0.0, 0.0), (float(W), 0.0), (float(W), float(H)), (0.0, float(H))]
@@ -810,6 +873,8 @@ class ValidationAugmentation:
                 kw["blur"] = [blur_box_params(blurs[i]) for i in idx]
             if qualities is not None:                                # photometric as well
                 kw["jpeg"] = jpeg_rows(qualities[i] for i in idx)
+            if tones is not None:                                    # photometric as well; the cuts count pixels of the network input
+                kw["tone"] = tone_rows((tones[i] for i in idx), W * H)
             box = None
             if self.keep_aspect:                                     # one geometry per size group, at the current (multi-scale) size
                 box = kw["letterbox"] = letterbox_geometry((win, hin), (W, H))
@@ -880,6 +945,9 @@ class TrainAugmentation(ValidationAugmentation):
         self.blur = float(getattr(args, "aug_blur", 0.0) or 0.0)           # gaussian radius uniform in [0, blur] pixels for a selected image
         self.perspective = float(getattr(args, "aug_perspective", 0.0) or 0.0)   # distortion scale of a selected image's corner insets
         self.jpeg = int(getattr(args, "aug_jpeg", 0) or 0)                 # a selected image is JPEG-compressed at a quality uniform in [jpeg, 95]
+        self.equalize = float(getattr(args, "aug_equalize", 0.0) or 0.0)   # per-image probability of ImageOps.equalize
+        self.autocontrast = float(getattr(args, "aug_autocontrast", 0.0) or 0.0)   # per-image probability of ImageOps.autocontrast (when not equalized)
+        self.autocontrast_cutoff = float(getattr(args, "aug_autocontrast_cutoff", 1.0) or 0.0)   # its cutoff is uniform in [0, this] percent
         self.train_tiles = parse_tiles(getattr(args, "train_tiles", ""), "train_tiles")   # (Tx, Ty) of the canvas the windows are cut from, () = off
         self.tile_overlap = int(getattr(args, "tile_overlap", 64))
 
@@ -990,6 +1058,17 @@ class TrainAugmentation(ValidationAugmentation):
             return None
         u = torch.rand(n, 2, dtype=torch.float64).tolist()
         return [min(JPEG_MAX_QUALITY, self.jpeg + int(u1 * (JPEG_MAX_QUALITY + 1 - self.jpeg))) if u0 < self.prob else 0 for u0, u1 in u]
+
+    def tone_draws_for(self, n):
+        """n tone draws (mode, cutoff percent) from ONE more draw on torch's global generator, `rand(n, 3)` in float64, made after that of
+        `jpeg_draws_for`: sample i is equalized when u0 < `--aug_equalize`; otherwise it is autocontrasted when u1 < `--aug_autocontrast`,
+        at the cutoff u2 `--aug_autocontrast_cutoff` percent; otherwise it is left alone -- never both.  None, and no draw at all, with both
+        probabilities 0 or augmentation off."""
+        if self.args.no_augmentation or (self.equalize == 0 and self.autocontrast == 0):
+            return None
+        u = torch.rand(n, 3, dtype=torch.float64).tolist()
+        return [(TONE_EQUALIZE, 0.0) if u0 < self.equalize else
+                (TONE_AUTOCONTRAST, self.autocontrast_cutoff * u2) if u1 < self.autocontrast else (TONE_COPY, 0.0) for u0, u1, u2 in u]
 
     def trigger_random_resize(self):
         if self.args.no_augmentation:

@@ -149,6 +149,19 @@ _FLAGS = [
                            "smearing of a camera's encoder, on the grid of the network input. After the blur and before the colour "
                            "jitter; annotations are untouched. Needs a directory (not --synthetic). Not consulted by evaluate / detect. "
                            "0 = off.")),
+    (("--aug_equalize",), dict(type=float, default=0.0, metavar="P", help="Training augmentation: with probability P an image's histogram "
+                               "is equalized per channel, byte for byte Pillow's ImageOps.equalize (torchvision's RandomEqualize on a PIL "
+                               "image): a tone curve made from the image's own content, as exposure and auto-gain differences between "
+                               "cameras are. After the JPEG round trip and before the colour jitter, on the 8-bit network input (fill "
+                               "colour and letterbox bars included); annotations are untouched. Needs a directory (not --synthetic). Not "
+                               "consulted by evaluate / detect. 0 = off.")),
+    (("--aug_autocontrast",), dict(type=float, default=0.0, metavar="P", help="Training augmentation: with probability P an image that "
+                                   "--aug_equalize did not select has each channel stretched to the full range, byte for byte Pillow's "
+                                   "ImageOps.autocontrast (torchvision's RandomAutocontrast on a PIL image), ignoring a share of the "
+                                   "darkest and brightest pixels uniform in [0, --aug_autocontrast_cutoff] percent. Same place in the chain "
+                                   "and same limits as --aug_equalize. 0 = off.")),
+    (("--aug_autocontrast_cutoff",), dict(type=float, default=1.0, metavar="C", help="Upper end, in percent of the pixels at either end of "
+                                          "the histogram, of the cutoff that --aug_autocontrast draws (0 <= C <= 40).")),
 ]
 
 _POSITIVE = ["in_channels", "fpn_depth", "batch_size", "epochs", "learning_rate", "down_ratio", "max_objects", "max_parts"]
@@ -329,6 +342,27 @@ def check_aug_jpeg(args):
     return q
 
 
+MAX_AUG_AUTOCONTRAST_CUTOFF = 40.0  # percent at either end: beyond, the two cuts meet in the middle and most images are left alone
+
+
+def check_aug_tone(args):
+    """`--aug_equalize`, `--aug_autocontrast` and `--aug_autocontrast_cutoff` on a parsed namespace -> (P_eq, P_ac, C), as `train` checks
+    them (model/trainer.py): two probabilities in [0, 1] and a percentage in [0, 40] (NaN fails the range tests); `--synthetic` renders
+    network-input tensors and has no 8-bit image to take a histogram of, so a positive probability is refused there."""
+    p_eq = getattr(args, "aug_equalize", 0.0) or 0.0
+    p_ac = getattr(args, "aug_autocontrast", 0.0) or 0.0
+    cutoff = getattr(args, "aug_autocontrast_cutoff", 1.0)
+    cutoff = 0.0 if cutoff is None else cutoff
+    for name, p in (("aug_equalize", p_eq), ("aug_autocontrast", p_ac)):
+        if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0 <= p <= 1:
+            raise ValueError(f"'{name}' should be a probability in [0, 1], not {p}")
+    if isinstance(cutoff, bool) or not isinstance(cutoff, (int, float)) or not 0 <= cutoff <= MAX_AUG_AUTOCONTRAST_CUTOFF:
+        raise ValueError(f"'aug_autocontrast_cutoff' should be a percentage in [0, {MAX_AUG_AUTOCONTRAST_CUTOFF:g}], not {cutoff}")
+    if (p_eq > 0 or p_ac > 0) and getattr(args, "synthetic", 0):
+        raise ValueError("'aug_equalize' / 'aug_autocontrast' work on source images: they need --train_dir, not --synthetic")
+    return float(p_eq), float(p_ac), float(cutoff)
+
+
 def finalize(args):
     """Validation + derived fields (args.py:178-269) on an already parsed namespace."""
     for side in ("width", "height"):
@@ -353,6 +387,9 @@ def finalize(args):
     assert 0 <= getattr(args, "aug_blur", 0.0) <= MAX_AUG_BLUR, "'aug_blur' should be in [0, 8]"
     assert 0 <= getattr(args, "aug_perspective", 0.0) <= MAX_AUG_PERSPECTIVE, "'aug_perspective' should be in [0, 0.9]"
     assert getattr(args, "aug_jpeg", 0) == 0 or MIN_AUG_JPEG <= getattr(args, "aug_jpeg", 0) <= MAX_AUG_JPEG, "'aug_jpeg' should be 0 or in [5, 95]"
+    assert 0 <= getattr(args, "aug_equalize", 0.0) <= 1, "'aug_equalize' should be in [0, 1]"
+    assert 0 <= getattr(args, "aug_autocontrast", 0.0) <= 1, "'aug_autocontrast' should be in [0, 1]"
+    assert 0 <= getattr(args, "aug_autocontrast_cutoff", 1.0) <= MAX_AUG_AUTOCONTRAST_CUTOFF, "'aug_autocontrast_cutoff' should be in [0, 40]"
     args.label_nms = check_label_nms(getattr(args, "label_nms", 0))
     args.tta_scales = parse_tta_scales(getattr(args, "tta_scales", ""))
     args.tiles = parse_tiles(getattr(args, "tiles", ""))
