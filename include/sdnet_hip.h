@@ -604,6 +604,40 @@ int sd_preprocess_images_list_tone(const uint8_t* const* images, int geometry, i
                                    const int* blur, const int* jpeg, const int* tone, const uint8_t fill3[3], const float* mean3,
                                    const float* std3, float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream);
 
+/* Sensor noise on 8-bit images (training augmentation, `train --aug_noise / --aug_noise_shot`): read noise plus signal-dependent shot noise,
+ * the heteroscedastic-Gaussian sensor model per channel and pixel in the 8-bit domain (no gamma is modelled), all integer and bit-exact:
+ * with o the byte's offset inside ITS image, word = Philox4x32-10(counter (o >> 2, 0, 0, 0), key (k0, k1))[o & 3]; z = the unit normal in
+ * Q10 from the word's top 12 bits through a 2048-entry inverse-CDF half table (the other 20 bits are not used); sigma(v) = isqrt(a' + b' v)
+ * in Q8 with a' = min(a, 2^26), b' = min(b, 2^17); out = clamp(v + ((z sigma(v) + 2^17) >> 18), 0, 255) (tests/noise_ref.py restates it).
+ * table (B, 4) int32 on the DEVICE: a row is [k0, k1, a, b], a = the read-noise variance and b = the shot gain per level, both in Q16
+ * levels^2 and read as uint32 (data/augment.py noise_rows); the clamps are part of the definition and nothing in a row decides an address,
+ * so any table is memory-safe; a row with a' = b' = 0 leaves its image as it is.  The bytes depend on the image's content and its row only,
+ * not on the launch shape, the position in the batch or the base address.  in and out are (B, H, W, 3) uint8, any H, W >= 1 with
+ * H * W < 2^31 and any byte alignment; out may be in (in place), any other overlap is SD_ERR_INVALID.  One launch, no workspace.
+ * B <= 65535.  sd_noise_normal_table (host only) copies the half table H[j] = round(1024 Phi^-1((2048 + j + 0.5) / 4096)). */
+int sd_noise_normal_table(uint16_t out[2048]);
+int sd_noise_u8(const uint8_t* in, uint8_t* out, int B, int H, int W, const int* table, sd_stream_t stream);
+
+/* The tone forms with the noise stage between the blur and the JPEG round trip (optics -> sensor -> encoder):
+ *     Resize | Window | Letterbox -> [Mosaic] -> [Affine | Perspective] -> [Blur] -> Noise -> [JPEG] -> [Tone] -> [ColorJitter] -> flips -> Normalize.
+ * The arguments of sd_preprocess_images_tone / _list_tone plus noise (B, 4) int32 on the device after tone, as sd_noise_u8's table.  With
+ * noise null the call IS the tone form.  With noise set every other table is optional; the stage has no size or alignment rule of its own
+ * beyond Hout * Wout < 2^31 and needs no workspace: sd_preprocess_noise_workspace_bytes() = sd_preprocess_tone_workspace_bytes(). */
+size_t sd_preprocess_noise_workspace_bytes(int geometry, int B, int Hin, int Win, int Wg, int Hout, int Wout, int g0);
+int sd_preprocess_images_noise(const uint8_t* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout, int g0, int g1,
+                               const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize,
+                               const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
+                               const double* affine, const double* persp, const int* mosaic_geom, const double* mosaic_affine, const int* blur,
+                               const int* jpeg, const int* tone, const int* noise, const uint8_t fill3[3], const float* mean3, const float* std3,
+                               float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream);
+int sd_preprocess_images_list_noise(const uint8_t* const* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout,
+                                    int g0, int g1, const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk,
+                                    int v_ksize, const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
+                                    const double* affine, const double* persp, const int* mosaic_geom, const double* mosaic_affine,
+                                    const int* blur, const int* jpeg, const int* tone, const int* noise, const uint8_t fill3[3],
+                                    const float* mean3, const float* std3, float* out, void* workspace, size_t workspace_bytes,
+                                    sd_stream_t stream);
+
 /* ---- loss: src/sdnet/model/loss.py:17-64,91-117------------------------------------------- */
 
 #define SD_HM_MSE   0

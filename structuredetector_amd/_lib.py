@@ -161,6 +161,15 @@ _SIGNATURES = {
                                   [C.POINTER(C.c_ubyte), C.POINTER(c_float), C.POINTER(c_float), c_vp, c_vp, c_size, c_vp]),
     "sd_preprocess_images_list_tone": (c_int, [c_vp] + [c_int] * 10 + [c_vp, c_vp, c_int, c_vp, c_vp, c_int] + [c_vp] * 11 +
                                        [C.POINTER(C.c_ubyte), C.POINTER(c_float), C.POINTER(c_float), c_vp, c_vp, c_size, c_vp]),
+    # sensor noise on 8-bit images: in, out (may be in), B, H, W, table (B, 4) int32 device = k0, k1, a (read variance Q16), b (shot gain Q16), stream
+    "sd_noise_normal_table": (c_int, [c_vp]),                      # host only: the 2048 uint16 of the unit-normal half table
+    "sd_noise_u8": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp]),
+    # the tone forms with noise (B, 4) int32 device after tone (null: the tone form)
+    "sd_preprocess_noise_workspace_bytes": (c_size, [c_int] * 8),
+    "sd_preprocess_images_noise": (c_int, [c_vp] + [c_int] * 10 + [c_vp, c_vp, c_int, c_vp, c_vp, c_int] + [c_vp] * 12 +
+                                   [C.POINTER(C.c_ubyte), C.POINTER(c_float), C.POINTER(c_float), c_vp, c_vp, c_size, c_vp]),
+    "sd_preprocess_images_list_noise": (c_int, [c_vp] + [c_int] * 10 + [c_vp, c_vp, c_int, c_vp, c_vp, c_int] + [c_vp] * 12 +
+                                        [C.POINTER(C.c_ubyte), C.POINTER(c_float), C.POINTER(c_float), c_vp, c_vp, c_size, c_vp]),
     "sd_render_targets": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_float, c_vp, c_vp]),
     "sd_loss_workspace_bytes": (c_size, [c_int] * 5),
     "sd_loss_fwd": (c_int, [C.POINTER(LossDesc), c_vp, c_vp, c_size, c_vp]),

@@ -98,6 +98,10 @@ int jpeg_stage(const uint8_t* in, uint8_t* out, uint8_t* planes, int B, int H, i
 size_t tone_workspace_bytes(int B);
 int tone_stage(const uint8_t* in, uint8_t* out, void* ws, int B, int H, int W, const int* table, hipStream_t st);
 
+// Sensor noise stage (sd_noise.hip): in -> out, (B, H, W, 3) u8 of any alignment, out may be in.  No workspace.  table (B, 4) int32 on
+// the device.  Shapes are the caller's to check (B is a grid dimension: <= 65535; H W < 2^31).
+int noise_stage(const uint8_t* in, uint8_t* out, int B, int H, int W, const int* table, hipStream_t st);
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);

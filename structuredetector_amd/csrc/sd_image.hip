@@ -1410,7 +1410,8 @@ size_t sd_preprocess_blur_workspace_bytes(int geometry, int B, int Hin, int Win,
 }
 
 // the blur and perspective forms proper (blur or persp set): the checks of the geometry's entry point, its horizontal pass, its vertical
-// pass into an 8-bit image, the 8-bit stages -- the warp slot is k_affine_u8 or k_persp_u8 --, the blur unless its table is null, the JPEG
+// pass into an 8-bit image, the 8-bit stages -- the warp slot is k_affine_u8 or k_persp_u8 --, the blur unless its table is null, the sensor
+// noise unless its table is null (sd_noise.hip: noise_stage, on image A in place, no workspace), the JPEG
 // round trip unless its table is null (sd_jpeg.hip: jpeg_stage, on image A in place; its planes lie behind image B), the tone stage unless
 // its table is null (sd_tone.hip: tone_stage, on image A in place; its histograms and tables lie behind the planes), and the jitter or
 // plain tail
@@ -1418,8 +1419,8 @@ static int preprocess_blur(const char* what, bool list, const void* images, int 
                            int g0, int g1, const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize,
                            const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors, const double* affine,
                            const double* persp, const int* mosaic_geom, const double* mosaic_affine, const int* blur, const int* jpeg,
-                           const int* tone, const uint8_t* fill3, const float* mean3, const float* std3, float* out, void* workspace,
-                           size_t workspace_bytes, hipStream_t st) {
+                           const int* tone, const int* noise, const uint8_t* fill3, const float* mean3, const float* std3, float* out,
+                           void* workspace, size_t workspace_bytes, hipStream_t st) {
     const double* warp = affine ? affine : persp;                        // one warp slot: the callers refuse both together
     const uint8_t* packed = reinterpret_cast<const uint8_t*>(images);
     const uint8_t* const* table = reinterpret_cast<const uint8_t* const*>(images);
@@ -1482,6 +1483,9 @@ static int preprocess_blur(const char* what, bool list, const void* images, int 
         SD_REQUIRE(workspace_bytes >= tone_at + tone_workspace_bytes(B), SD_ERR_WORKSPACE, "%s: workspace %zu < %zu", what, workspace_bytes,
                    tone_at + tone_workspace_bytes(B));
     }
+
+    if (noise)
+        SD_REQUIRE((int64_t)Hout * Wout < (1ll << 31), SD_ERR_INVALID, "%s: noise needs a frame of fewer than 2^31 pixels, not %d x %d", what, Wout, Hout);
 
     uint8_t* tmp = reinterpret_cast<uint8_t*>(workspace);
     const size_t frame = align_up((size_t)B * Hout * Wout * 3, 256);
@@ -1546,6 +1550,8 @@ static int preprocess_blur(const char* what, bool list, const void* images, int 
     }
     if (blur)                                                            // cur == img_a; without a blur the jitter reads it as it is
         if (int e = blur_stage(cur, img_b, img_a, B, Hout, Wout, blur, st)) return e;
+    if (noise)                                                           // image A in place (with or without a blur the last stage wrote it)
+        if (int e = noise_stage(img_a, img_a, B, Hout, Wout, noise, st)) return e;
     if (jpeg)                                                            // the last 8-bit image, in place: the second launch reads the planes only
         if (int e = jpeg_stage(img_a, img_a, tmp + planes_at, B, Hout, Wout, jpeg, st)) return e;
     if (tone)                                                            // in place as well: every byte is read and written by one thread
@@ -1564,7 +1570,7 @@ int sd_preprocess_images_blur(const uint8_t* images, int geometry, int B, int Hi
     const char* what = "sd_preprocess_images_blur";
     if (blur)
         return preprocess_blur(what, false, images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
-                               window, flips, jitter_order, jitter_factors, affine, nullptr, mosaic_geom, mosaic_affine, blur, nullptr, nullptr, fill3, mean3, std3,
+                               window, flips, jitter_order, jitter_factors, affine, nullptr, mosaic_geom, mosaic_affine, blur, nullptr, nullptr, nullptr, fill3, mean3, std3,
                                out, workspace, workspace_bytes, (hipStream_t)stream);
     if (geometry == SD_GEOM_WINDOW)
         return sd_preprocess_images_window(images, B, Hin, Win, Hg, Wg, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, window, g0, g1, flips,
@@ -1598,7 +1604,7 @@ int sd_preprocess_images_list_blur(const uint8_t* const* images, int geometry, i
     const char* what = "sd_preprocess_images_list_blur";
     if (blur)
         return preprocess_blur(what, true, images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
-                               window, flips, jitter_order, jitter_factors, affine, nullptr, mosaic_geom, mosaic_affine, blur, nullptr, nullptr, fill3, mean3, std3,
+                               window, flips, jitter_order, jitter_factors, affine, nullptr, mosaic_geom, mosaic_affine, blur, nullptr, nullptr, nullptr, fill3, mean3, std3,
                                out, workspace, workspace_bytes, (hipStream_t)stream);
     if (geometry == SD_GEOM_WINDOW)
         return sd_preprocess_images_list_window(images, B, Hin, Win, Hg, Wg, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, window, g0, g1,
@@ -1654,7 +1660,7 @@ int sd_preprocess_images_persp(const uint8_t* images, int geometry, int B, int H
     SD_REQUIRE(!affine, SD_ERR_INVALID, "%s: persp and affine do not combine (fold the affine matrix into the homography)", what);
     SD_REQUIRE(fill3, SD_ERR_INVALID, "%s: a warp needs a fill colour", what);
     return preprocess_blur(what, false, images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
-                           window, flips, jitter_order, jitter_factors, nullptr, persp, mosaic_geom, mosaic_affine, blur, nullptr, nullptr, fill3, mean3, std3, out,
+                           window, flips, jitter_order, jitter_factors, nullptr, persp, mosaic_geom, mosaic_affine, blur, nullptr, nullptr, nullptr, fill3, mean3, std3, out,
                            workspace, workspace_bytes, (hipStream_t)stream);
 }
 
@@ -1672,7 +1678,7 @@ int sd_preprocess_images_list_persp(const uint8_t* const* images, int geometry, 
     SD_REQUIRE(!affine, SD_ERR_INVALID, "%s: persp and affine do not combine (fold the affine matrix into the homography)", what);
     SD_REQUIRE(fill3, SD_ERR_INVALID, "%s: a warp needs a fill colour", what);
     return preprocess_blur(what, true, images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
-                           window, flips, jitter_order, jitter_factors, nullptr, persp, mosaic_geom, mosaic_affine, blur, nullptr, nullptr, fill3, mean3, std3, out,
+                           window, flips, jitter_order, jitter_factors, nullptr, persp, mosaic_geom, mosaic_affine, blur, nullptr, nullptr, nullptr, fill3, mean3, std3, out,
                            workspace, workspace_bytes, (hipStream_t)stream);
 }
 
@@ -1697,7 +1703,7 @@ int sd_preprocess_images_jpeg(const uint8_t* images, int geometry, int B, int Hi
                                           std3, out, workspace, workspace_bytes, stream);
     SD_REQUIRE(!(affine && persp), SD_ERR_INVALID, "%s: persp and affine do not combine (fold the affine matrix into the homography)", what);
     return preprocess_blur(what, false, images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
-                           window, flips, jitter_order, jitter_factors, affine, persp, mosaic_geom, mosaic_affine, blur, jpeg, nullptr, fill3, mean3, std3, out,
+                           window, flips, jitter_order, jitter_factors, affine, persp, mosaic_geom, mosaic_affine, blur, jpeg, nullptr, nullptr, fill3, mean3, std3, out,
                            workspace, workspace_bytes, (hipStream_t)stream);
 }
 
@@ -1714,7 +1720,7 @@ int sd_preprocess_images_list_jpeg(const uint8_t* const* images, int geometry, i
                                                fill3, mean3, std3, out, workspace, workspace_bytes, stream);
     SD_REQUIRE(!(affine && persp), SD_ERR_INVALID, "%s: persp and affine do not combine (fold the affine matrix into the homography)", what);
     return preprocess_blur(what, true, images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
-                           window, flips, jitter_order, jitter_factors, affine, persp, mosaic_geom, mosaic_affine, blur, jpeg, nullptr, fill3, mean3, std3, out,
+                           window, flips, jitter_order, jitter_factors, affine, persp, mosaic_geom, mosaic_affine, blur, jpeg, nullptr, nullptr, fill3, mean3, std3, out,
                            workspace, workspace_bytes, (hipStream_t)stream);
 }
 
@@ -1739,7 +1745,7 @@ int sd_preprocess_images_tone(const uint8_t* images, int geometry, int B, int Hi
                                          mean3, std3, out, workspace, workspace_bytes, stream);
     SD_REQUIRE(!(affine && persp), SD_ERR_INVALID, "%s: persp and affine do not combine (fold the affine matrix into the homography)", what);
     return preprocess_blur(what, false, images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
-                           window, flips, jitter_order, jitter_factors, affine, persp, mosaic_geom, mosaic_affine, blur, jpeg, tone, fill3, mean3, std3,
+                           window, flips, jitter_order, jitter_factors, affine, persp, mosaic_geom, mosaic_affine, blur, jpeg, tone, nullptr, fill3, mean3, std3,
                            out, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
@@ -1756,8 +1762,49 @@ int sd_preprocess_images_list_tone(const uint8_t* const* images, int geometry, i
                                               jpeg, fill3, mean3, std3, out, workspace, workspace_bytes, stream);
     SD_REQUIRE(!(affine && persp), SD_ERR_INVALID, "%s: persp and affine do not combine (fold the affine matrix into the homography)", what);
     return preprocess_blur(what, true, images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
-                           window, flips, jitter_order, jitter_factors, affine, persp, mosaic_geom, mosaic_affine, blur, jpeg, tone, fill3, mean3, std3,
+                           window, flips, jitter_order, jitter_factors, affine, persp, mosaic_geom, mosaic_affine, blur, jpeg, tone, nullptr, fill3, mean3, std3,
                            out, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+// ---- sensor noise between the blur and the JPEG round trip (sd_noise.hip: noise_stage), behind any geometry ----
+// noise null: the tone form, a call.  noise set: preprocess_blur's chain with the one more stage, every other table optional;
+// workspace: the tone form's (the stage needs none).
+size_t sd_preprocess_noise_workspace_bytes(int geometry, int B, int Hin, int Win, int Wg, int Hout, int Wout, int g0) {
+    return sd_preprocess_tone_workspace_bytes(geometry, B, Hin, Win, Wg, Hout, Wout, g0);
+}
+
+int sd_preprocess_images_noise(const uint8_t* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout, int g0, int g1,
+                               const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize,
+                               const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
+                               const double* affine, const double* persp, const int* mosaic_geom, const double* mosaic_affine, const int* blur,
+                               const int* jpeg, const int* tone, const int* noise, const uint8_t* fill3, const float* mean3, const float* std3,
+                               float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
+    const char* what = "sd_preprocess_images_noise";
+    if (!noise)
+        return sd_preprocess_images_tone(images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
+                                         window, flips, jitter_order, jitter_factors, affine, persp, mosaic_geom, mosaic_affine, blur, jpeg, tone,
+                                         fill3, mean3, std3, out, workspace, workspace_bytes, stream);
+    SD_REQUIRE(!(affine && persp), SD_ERR_INVALID, "%s: persp and affine do not combine (fold the affine matrix into the homography)", what);
+    return preprocess_blur(what, false, images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
+                           window, flips, jitter_order, jitter_factors, affine, persp, mosaic_geom, mosaic_affine, blur, jpeg, tone, noise, fill3, mean3,
+                           std3, out, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int sd_preprocess_images_list_noise(const uint8_t* const* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout,
+                                    int g0, int g1, const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk,
+                                    int v_ksize, const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
+                                    const double* affine, const double* persp, const int* mosaic_geom, const double* mosaic_affine, const int* blur,
+                                    const int* jpeg, const int* tone, const int* noise, const uint8_t* fill3, const float* mean3, const float* std3,
+                                    float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
+    const char* what = "sd_preprocess_images_list_noise";
+    if (!noise)
+        return sd_preprocess_images_list_tone(images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk,
+                                              v_ksize, window, flips, jitter_order, jitter_factors, affine, persp, mosaic_geom, mosaic_affine, blur,
+                                              jpeg, tone, fill3, mean3, std3, out, workspace, workspace_bytes, stream);
+    SD_REQUIRE(!(affine && persp), SD_ERR_INVALID, "%s: persp and affine do not combine (fold the affine matrix into the homography)", what);
+    return preprocess_blur(what, true, images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
+                           window, flips, jitter_order, jitter_factors, affine, persp, mosaic_geom, mosaic_affine, blur, jpeg, tone, noise, fill3, mean3,
+                           std3, out, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -38,6 +38,12 @@ JPEG (`--aug_jpeg QMIN`; not in the reference): between the blur and the ColorJi
 `save(buf, "JPEG", quality=q)` then `open(buf)` gives, byte for byte -- colour conversion, 4:2:0 chroma, the accurate-integer DCT of every
 8 x 8 block, the quantiser and the way back, all integer (`sd_jpeg_u8`; in the chain `sd_preprocess_images_jpeg`); the two quantisation
 tables of a quality come from the host (`jpeg_quant_tables`).  Photometric: annotations are untouched.
+Noise (`--aug_noise R` / `--aug_noise_shot G`; not in the reference): between the blur and the JPEG round trip -- optics, sensor, encoder --
+a selected image gets read noise of a standard deviation up to R grey levels plus shot noise whose variance is up to G levels^2 per level:
+the heteroscedastic-Gaussian sensor model per channel and pixel in the 8-bit domain (no gamma is modelled), all integer and bit-exact
+(`sd_noise_u8`; in the chain `sd_preprocess_images_noise`; tests/noise_ref.py restates it).  The random numbers are made on the device by a
+counter-based generator, Philox4x32-10 keyed per image and counted by the byte's offset in its image, so the bytes depend on the image and
+its row (`noise_rows`) alone; the host draws only the two key words and the two strengths.  Photometric: annotations are untouched.
 Tone (`--aug_equalize P` / `--aug_autocontrast P`; not in the reference): after the JPEG round trip, in front of the ColorJitter, a selected
 image is Pillow's `ImageOps.equalize(img)` or `ImageOps.autocontrast(img, cutoff)`, byte for byte -- a look-up table per channel made from
 the histogram of the 8-bit frame as it stands there, fill colour and letterbox bars included (`sd_tone_u8`; in the chain
@@ -473,17 +479,49 @@ def tone_images(images: torch.Tensor, rows) -> torch.Tensor:
     return out
 
 
+def noise_rows(draws):
+    """One row [k0, k1, a, b] of `sd_noise_u8`'s table per draw (k0, k1, sigma_read, gain): the two Philox key words, the read-noise
+    variance a = round(sigma_read^2 65536) and the shot gain b = round(gain 65536), both Q16, all four as int32 bit patterns (the library
+    reads them as uint32 and clamps a to 2^26, b to 2^17)."""
+    wrap = lambda v: ((int(v) & 0xFFFFFFFF) ^ 0x80000000) - 0x80000000
+    return [[wrap(k0), wrap(k1), wrap(round(float(sigma) * float(sigma) * 65536.0)), wrap(round(float(gain) * 65536.0))]
+            for k0, k1, sigma, gain in draws]
+
+
+def _noise_rows(rows, B, device):
+    table = torch.as_tensor(np.asarray(rows, dtype=np.int64).astype(np.int32)).reshape(-1, 4).contiguous()
+    if table.shape[0] != B:
+        raise L.SdError("noise must have one row (k0, k1, a, b) per image")
+    return table.to(device, non_blocking=True)
+
+
+def noise_images(images: torch.Tensor, rows) -> torch.Tensor:
+    """images: (B, H, W, 3) uint8 on the GPU, any H and W; rows: B rows [k0, k1, a, b] as `noise_rows` makes them.  Returns a new tensor,
+    image b = image b with the sensor noise of its row, byte for byte tests/noise_ref.py's `noise_ref`, or image b itself for a row with
+    a = b = 0 (`sd_noise_u8`: the stand-alone stage of the chain)."""
+    L.require_cuda(images)
+    if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3:
+        raise L.SdError(f"noise_images expects (B, H, W, 3) uint8, got {tuple(images.shape)} {images.dtype}")
+    images = images.contiguous()
+    B, H, W, _ = images.shape
+    table = _noise_rows(rows, B, images.device)
+    out = torch.empty_like(images)
+    L.check(L.lib().sd_noise_u8(images.data_ptr(), out.data_ptr(), B, H, W, table.data_ptr(), L.stream()), "sd_noise_u8")
+    return out
+
+
 JPEG_MAX_QUALITY = 95                                                # the upper end of `--aug_jpeg`'s quality range (Pillow's advised maximum)
 GEOM_STRETCH, GEOM_WINDOW, GEOM_LETTERBOX = 0, 1, 2                  # include/sdnet_hip.h SD_GEOM_*
 
 
 def _preprocess_blur(fn_name, source, B, Hin, Win, out_size, flips, mean, std, jitter, affine, mosaic, window, letterbox, blur, dev, persp=None,
-                     jpeg=None, tone=None):
+                     jpeg=None, tone=None, noise=None):
     """The blur forms of `preprocess_images` / `preprocess_image_list` (`sd_preprocess_images_blur` / `..._list_blur`): any geometry, every
     optional stage, the blur between the warp and the jitter.  source = the address of the packed images or of the pointer table.  With
     `persp` the perspective forms (`sd_preprocess_images_persp` / `..._list_persp`): the same arguments plus the homography table.  With
     `jpeg` the JPEG forms (`sd_preprocess_images_jpeg` / `..._list_jpeg`): those arguments plus the quantisation tables after the blur's.  With
-    `tone` the tone forms (`sd_preprocess_images_tone` / `..._list_tone`): those plus the tone table after the quantisation tables."""
+    `tone` the tone forms (`sd_preprocess_images_tone` / `..._list_tone`): those plus the tone table after the quantisation tables.  With
+    `noise` the noise forms (`sd_preprocess_images_noise` / `..._list_noise`): those plus the noise table after the tone table."""
     if persp is not None and affine is not None:
         raise L.SdError("preprocess: persp and affine do not combine (fold the affine matrix in with compose_affine_perspective)")
     Wout, Hout = int(out_size[0]), int(out_size[1])
@@ -520,14 +558,18 @@ def _preprocess_blur(fn_name, source, B, Hin, Win, out_size, flips, mean, std, j
     homography = None if persp is None else _persp_rows(persp, B, dev)
     jp = None if jpeg is None else _jpeg_rows(jpeg, B, dev)
     tn = None if tone is None else _tone_rows(tone, B, dev)
-    tone_form = fn_name.endswith("_tone")
+    ns = None if noise is None else _noise_rows(noise, B, dev)
+    noise_form = fn_name.endswith("_noise")
+    tone_form = noise_form or fn_name.endswith("_tone")
     jpeg_form = tone_form or fn_name.endswith("_jpeg")
     warp = [ptr(rows), ptr(homography)] if jpeg_form or fn_name.endswith("_persp") else [ptr(rows)]   # the perspective forms take persp after affine
     tail = [ptr(bl), ptr(jp)] if jpeg_form else [ptr(bl)]                                            # the JPEG forms take jpeg after blur
     if tone_form:
         tail.append(ptr(tn))                                                                         # the tone forms take tone after jpeg
+    if noise_form:
+        tail.append(ptr(ns))                                                                         # the noise forms take noise after tone
     lib = L.lib()
-    ws_bytes = (lib.sd_preprocess_tone_workspace_bytes if tone_form else
+    ws_bytes = (lib.sd_preprocess_noise_workspace_bytes if noise_form else lib.sd_preprocess_tone_workspace_bytes if tone_form else
                 lib.sd_preprocess_jpeg_workspace_bytes if jpeg_form else lib.sd_preprocess_blur_workspace_bytes)
     ws = L.workspace(ws_bytes(geometry, B, Hin, Win, Wg, Hout, Wout, g0), dev)
     L.check(getattr(lib, fn_name)(source, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, hb.data_ptr(), hk.data_ptr(), hks, vb.data_ptr(),
@@ -538,7 +580,7 @@ def _preprocess_blur(fn_name, source, B, Hin, Win, out_size, flips, mean, std, j
 
 
 def preprocess_images(images: torch.Tensor, out_size, flips=None, mean=_MEAN, std=_STD, jitter=None, affine=None, mosaic=None,
-                      window=None, letterbox=None, blur=None, persp=None, jpeg=None, tone=None) -> torch.Tensor:
+                      window=None, letterbox=None, blur=None, persp=None, jpeg=None, tone=None, noise=None) -> torch.Tensor:
     """images: (B, Hin, Win, 3) uint8 on the GPU; out_size = (width, height); flips: (B,) uint8 (bit 0 horizontal, bit 1 vertical)
     or None; jitter: None or (order words (B,) int32, factors (B, 3) fp32) as `jitter_words` makes them; affine: None or B rows of the 6
     coefficients of `affine_inverse_matrix` at out_size (the warp runs on the resized image, in front of the jitter, fill `_FILL`); mosaic:
@@ -555,14 +597,19 @@ def preprocess_images(images: torch.Tensor, out_size, flips=None, mean=_MEAN, st
     `jpeg_rows` makes them: Pillow's JPEG round trip after the blur, in front of the jitter (`sd_preprocess_images_jpeg`, chosen only when
     jpeg is set; height and width multiples of 16; a row of quality 0 leaves its image as it is); tone: None or B rows [mode, cut_lo, cut_hi,
     0] as `tone_rows` makes them: Pillow's autocontrast or equalize after the JPEG round trip, in front of the jitter
-    (`sd_preprocess_images_tone`, chosen only when tone is set; any size; a row of mode 0 leaves its image as it is).
-    Returns (B, 3, height, width) fp32 = Normalize(to_tensor(flip(jitter(tone(jpeg(blur(affine(mosaic(resize(image)))))))))) of
+    (`sd_preprocess_images_tone`, chosen only when tone is set; any size; a row of mode 0 leaves its image as it is); noise: None or B rows
+    [k0, k1, a, b] as `noise_rows` makes them: the sensor noise after the blur, in front of the JPEG round trip
+    (`sd_preprocess_images_noise`, chosen only when noise is set; any size; a row with a = b = 0 leaves its image as it is).
+    Returns (B, 3, height, width) fp32 = Normalize(to_tensor(flip(jitter(tone(jpeg(noise(blur(affine(mosaic(resize(image))))))))))) of
     transforms.py:217-226."""
     L.require_cuda(images)
     if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3:
         raise L.SdError(f"preprocess_images expects (B, H, W, 3) uint8, got {tuple(images.shape)} {images.dtype}")
     images = images.contiguous()
     B, Hin, Win, _ = images.shape
+    if noise is not None:
+        return _preprocess_blur("sd_preprocess_images_noise", images.data_ptr(), B, Hin, Win, out_size, flips, mean, std, jitter, affine, mosaic,
+                                window, letterbox, blur, images.device, persp, jpeg, tone, noise)
     if tone is not None:
         return _preprocess_blur("sd_preprocess_images_tone", images.data_ptr(), B, Hin, Win, out_size, flips, mean, std, jitter, affine, mosaic,
                                 window, letterbox, blur, images.device, persp, jpeg, tone)
@@ -634,7 +681,7 @@ def preprocess_images(images: torch.Tensor, out_size, flips=None, mean=_MEAN, st
 
 
 def preprocess_image_list(pointers: torch.Tensor, hin: int, win: int, out_size, flips=None, mean=_MEAN, std=_STD, jitter=None,
-                          affine=None, mosaic=None, window=None, letterbox=None, blur=None, persp=None, jpeg=None, tone=None) -> torch.Tensor:
+                          affine=None, mosaic=None, window=None, letterbox=None, blur=None, persp=None, jpeg=None, tone=None, noise=None) -> torch.Tensor:
     """`preprocess_images` over B images that are not packed together: pointers is a (B,) int64 DEVICE tensor of the device addresses of
     B (hin, win, 3) uint8 images (any byte alignment; the caller keeps them alive until the work on the current stream is done), e.g. entries
     of data/image_cache.py's DeviceImageCache.  Same arguments otherwise, same output bytes as `preprocess_images` on the stacked images."""
@@ -644,6 +691,9 @@ def preprocess_image_list(pointers: torch.Tensor, hin: int, win: int, out_size, 
     pointers = pointers.contiguous()
     dev = pointers.device
     B, Hin, Win = pointers.numel(), int(hin), int(win)
+    if noise is not None:
+        return _preprocess_blur("sd_preprocess_images_list_noise", pointers.data_ptr(), B, Hin, Win, out_size, flips, mean, std, jitter, affine,
+                                mosaic, window, letterbox, blur, dev, persp, jpeg, tone, noise)
     if tone is not None:
         return _preprocess_blur("sd_preprocess_images_list_tone", pointers.data_ptr(), B, Hin, Win, out_size, flips, mean, std, jitter, affine,
                                 mosaic, window, letterbox, blur, dev, persp, jpeg, tone)
@@ -792,6 +842,10 @@ class ValidationAugmentation:
         """n tone draws (mode, cutoff percent) or None: validation never changes the tone curve and never draws."""
         return None
 
+    def noise_draws_for(self, n):
+        """n noise draws (k0, k1, sigma_read, gain) or None: validation never adds noise and never draws."""
+        return None
+
     @staticmethod
     def size_groups(images):
         """{(hin, win): (indices into the batch, stack of those images)} of what `__call__` accepts as `images`."""
@@ -844,6 +898,7 @@ class ValidationAugmentation:
         quads = self.perspective_draws_for(n)
         qualities = self.jpeg_draws_for(n)
         tones = self.tone_draws_for(n)
+        noises = self.noise_draws_for(n)
         homography = forward8 = None
         if quads is not None:                                        # the warp slot becomes one homography per image: affine, then perspective
             frame = [(0.0, 0.0), (float(W), 0.0), (float(W), float(H)), (0.0, float(H))]
@@ -875,6 +930,8 @@ class ValidationAugmentation:
                 kw["jpeg"] = jpeg_rows(qualities[i] for i in idx)
             if tones is not None:                                    # photometric as well; the cuts count pixels of the network input
                 kw["tone"] = tone_rows((tones[i] for i in idx), W * H)
+            if noises is not None:                                   # photometric as well; the key and the strengths of each sample
+                kw["noise"] = noise_rows(noises[i] for i in idx)
             box = None
             if self.keep_aspect:                                     # one geometry per size group, at the current (multi-scale) size
                 box = kw["letterbox"] = letterbox_geometry((win, hin), (W, H))
@@ -948,6 +1005,8 @@ class TrainAugmentation(ValidationAugmentation):
         self.equalize = float(getattr(args, "aug_equalize", 0.0) or 0.0)   # per-image probability of ImageOps.equalize
         self.autocontrast = float(getattr(args, "aug_autocontrast", 0.0) or 0.0)   # per-image probability of ImageOps.autocontrast (when not equalized)
         self.autocontrast_cutoff = float(getattr(args, "aug_autocontrast_cutoff", 1.0) or 0.0)   # its cutoff is uniform in [0, this] percent
+        self.noise = float(getattr(args, "aug_noise", 0.0) or 0.0)         # read noise of a selected image: sigma uniform in [0, noise] grey levels
+        self.noise_shot = float(getattr(args, "aug_noise_shot", 0.0) or 0.0)   # its shot gain: uniform in [0, noise_shot] levels^2 per level
         self.train_tiles = parse_tiles(getattr(args, "train_tiles", ""), "train_tiles")   # (Tx, Ty) of the canvas the windows are cut from, () = off
         self.tile_overlap = int(getattr(args, "tile_overlap", 64))
 
@@ -1069,6 +1128,19 @@ class TrainAugmentation(ValidationAugmentation):
         u = torch.rand(n, 3, dtype=torch.float64).tolist()
         return [(TONE_EQUALIZE, 0.0) if u0 < self.equalize else
                 (TONE_AUTOCONTRAST, self.autocontrast_cutoff * u2) if u1 < self.autocontrast else (TONE_COPY, 0.0) for u0, u1, u2 in u]
+
+    def noise_draws_for(self, n):
+        """n noise draws (k0, k1, sigma_read, gain) from TWO more draws on torch's global generator, made after that of `tone_draws_for`:
+        `rand(n, 3)` in float64 -- sample i is noised when u0 < 0.5, the flips' threshold, with sigma_read = u1 `--aug_noise` grey levels and
+        gain = u2 `--aug_noise_shot` levels^2 per level -- then `randint(0, 2^32, (n, 2))` in int64, the two Philox key words of every sample.
+        A sample that is not selected keeps its key and gets the strengths 0, 0: the identity row.  None, and no draw at all, with both flags
+        0 or augmentation off."""
+        if self.args.no_augmentation or (self.noise == 0 and self.noise_shot == 0):
+            return None
+        u = torch.rand(n, 3, dtype=torch.float64).tolist()
+        keys = torch.randint(0, 2 ** 32, (n, 2), dtype=torch.int64).tolist()
+        return [(k0, k1, u1 * self.noise, u2 * self.noise_shot) if u0 < self.prob else (k0, k1, 0.0, 0.0)
+                for (u0, u1, u2), (k0, k1) in zip(u, keys)]
 
     def trigger_random_resize(self):
         if self.args.no_augmentation:

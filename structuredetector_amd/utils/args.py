@@ -162,6 +162,16 @@ _FLAGS = [
                                    "and same limits as --aug_equalize. 0 = off.")),
     (("--aug_autocontrast_cutoff",), dict(type=float, default=1.0, metavar="C", help="Upper end, in percent of the pixels at either end of "
                                           "the histogram, of the cutoff that --aug_autocontrast draws (0 <= C <= 40).")),
+    (("--aug_noise",), dict(type=float, default=0.0, metavar="R", help="Training augmentation: with probability 0.5 an image gets sensor read "
+                            "noise, Gaussian with a standard deviation uniform in [0, R] grey levels (0 <= R <= 32), independent per pixel "
+                            "and channel, as a camera at dusk or at short exposure delivers. Made on the GPU by a counter-based generator "
+                            "(Philox4x32-10), bit-exact and reproducible from the seed. After the blur and before the JPEG round trip, on "
+                            "the 8-bit network input (no gamma is modelled); annotations are untouched. Needs a directory (not "
+                            "--synthetic). Not consulted by evaluate / detect. 0 = off.")),
+    (("--aug_noise_shot",), dict(type=float, default=0.0, metavar="G", help="Training augmentation: the signal-dependent part of the sensor "
+                                 "noise: a selected image's noise variance grows by g grey levels^2 per grey level, g uniform in [0, G] "
+                                 "(0 <= G <= 2). Either of --aug_noise and --aug_noise_shot switches the stage on; same place in the chain "
+                                 "and same limits. 0 = off.")),
 ]
 
 _POSITIVE = ["in_channels", "fpn_depth", "batch_size", "epochs", "learning_rate", "down_ratio", "max_objects", "max_parts"]
@@ -363,6 +373,24 @@ def check_aug_tone(args):
     return float(p_eq), float(p_ac), float(cutoff)
 
 
+MAX_AUG_NOISE, MAX_AUG_NOISE_SHOT = 32.0, 2.0   # grey levels; levels^2 per level: where the stage clamps a row (2^26 and 2^17 in Q16)
+
+
+def check_aug_noise(args):
+    """`--aug_noise` and `--aug_noise_shot` on a parsed namespace -> (R, G), as `train` checks them (model/trainer.py): a read-noise
+    standard deviation in [0, 32] grey levels and a shot gain in [0, 2] (NaN fails the range tests); `--synthetic` renders network-input
+    tensors and has no 8-bit image to add sensor noise to, so a positive value is refused there."""
+    r = getattr(args, "aug_noise", 0.0) or 0.0
+    g = getattr(args, "aug_noise_shot", 0.0) or 0.0
+    if isinstance(r, bool) or not isinstance(r, (int, float)) or not 0 <= r <= MAX_AUG_NOISE:
+        raise ValueError(f"'aug_noise' should be in [0, {MAX_AUG_NOISE:g}] grey levels (0 = off), not {r}")
+    if isinstance(g, bool) or not isinstance(g, (int, float)) or not 0 <= g <= MAX_AUG_NOISE_SHOT:
+        raise ValueError(f"'aug_noise_shot' should be in [0, {MAX_AUG_NOISE_SHOT:g}] (0 = off), not {g}")
+    if (r > 0 or g > 0) and getattr(args, "synthetic", 0):
+        raise ValueError("'aug_noise' / 'aug_noise_shot' work on source images: they need --train_dir, not --synthetic")
+    return float(r), float(g)
+
+
 def finalize(args):
     """Validation + derived fields (args.py:178-269) on an already parsed namespace."""
     for side in ("width", "height"):
@@ -390,6 +418,8 @@ def finalize(args):
     assert 0 <= getattr(args, "aug_equalize", 0.0) <= 1, "'aug_equalize' should be in [0, 1]"
     assert 0 <= getattr(args, "aug_autocontrast", 0.0) <= 1, "'aug_autocontrast' should be in [0, 1]"
     assert 0 <= getattr(args, "aug_autocontrast_cutoff", 1.0) <= MAX_AUG_AUTOCONTRAST_CUTOFF, "'aug_autocontrast_cutoff' should be in [0, 40]"
+    assert 0 <= getattr(args, "aug_noise", 0.0) <= MAX_AUG_NOISE, "'aug_noise' should be in [0, 32]"
+    assert 0 <= getattr(args, "aug_noise_shot", 0.0) <= MAX_AUG_NOISE_SHOT, "'aug_noise_shot' should be in [0, 2]"
     args.label_nms = check_label_nms(getattr(args, "label_nms", 0))
     args.tta_scales = parse_tta_scales(getattr(args, "tta_scales", ""))
     args.tiles = parse_tiles(getattr(args, "tiles", ""))
