@@ -335,52 +335,102 @@ int sd_render_targets(const int32_t* cx, const int32_t* cy, const int32_t* chan_
 
 /* ---- input pipeline: src/sdnet/data/transforms.py:9-35,47-60,108-118 (flips, Resize, Normalize) ------------------------ */
 
-/* Batched Resize (PIL bilinear, bit-identical bytes: Pillow's 22-bit fixed-point separable resampling, horizontal pass first)
- * + optional horizontal / vertical flip of the RESIZED image (transforms.py:217-226 order) + to_tensor + Normalize.
- * images: (B, Hin, Win, 3) u8 on the device; out: (B, 3, Hout, Wout) fp32 NCHW.  h_bounds / h_kk (Wout x {first source
- * column, count} and Wout x h_ksize fixed-point weights) and v_bounds / v_kk (per output row) are the coefficient tables of
- * Pillow's precompute_coeffs + normalize_coeffs_8bpc, computed by the host (structuredetector_amd/data/augment.py) and
- * resident on the device; flips: B bytes (bit 0 = horizontal, bit 1 = vertical) or NULL; mean3 / std3: HOST pointers to
- * three floats.  workspace: sd_preprocess_workspace_bytes() bytes (the 8-bit intermediate of the horizontal pass). */
+/* The preprocess chain, one call per batch, every image operation byte for byte Pillow's (or the stated integer definition):
+ *     Resize | Window | Letterbox -> [Mosaic] -> [Affine | Perspective] -> [Blur] -> [Noise] -> [JPEG] -> [Tone] -> [ColorJitter]
+ *     -> flips -> to_tensor -> Normalize            (transforms.py:217-226 order; out: (B, 3, Hout, Wout) fp32 NCHW)
+ * sd_preprocess_chain is the entry point for new callers; every stage in brackets is a table of the descriptor that is null when off.
+ *
+ * Source.  images: (B, Hin, Win, 3) u8 on the device, or with list != 0 a DEVICE array of B device pointers, each to one (Hin, Win, 3)
+ *   u8 image, any byte alignment, duplicates allowed (a cache of decoded images).  The list form stages source rows in LDS: Win (with a
+ *   window: g1) <= 21834, SD_ERR_INVALID beyond.  The two forms give the same bytes.
+ * Resize.  PIL bilinear: Pillow's 22-bit fixed-point separable resampling, horizontal pass first.  h_bounds / h_kk (per output column
+ *   {first source column, count} and h_ksize fixed-point weights) and v_bounds / v_kk (per output row) are the tables of Pillow's
+ *   precompute_coeffs + normalize_coeffs_8bpc, made by the host (data/augment.py) and resident on the device.  geometry:
+ *     SD_GEOM_STRETCH    tables Win -> Wout, Hin -> Hout; Hg, Wg, g0, g1 are not read and window is null.
+ *     SD_GEOM_WINDOW     crop training: image b's resize target is the (Hg, Wg) canvas (tables Win -> Wg, Hin -> Hg) of which only the
+ *                        (Hout, Wout) window at window[b] = (x0, y0) -- (B, 2) int32 on the device, clamped into the canvas by the
+ *                        kernels -- is produced: Image.resize((Wg, Hg)).crop(...).  g0 = max_rows, g1 = max_cols: HOST upper bounds of
+ *                        any window's source row / column span (data/augment.py window_extents), in [1, Hin] / [1, Win]; only those
+ *                        rows and columns are read.  A window larger than the canvas or a null table is SD_ERR_INVALID.
+ *     SD_GEOM_LETTERBOX  aspect-preserving input: the source is resized to (Hg, Wg) (tables Win -> Wg, Hin -> Hg) and pasted at
+ *                        (x0, y0) = (g1, g0) into a (Hout, Wout) frame of fill3, which is always needed; an image that does not lie
+ *                        inside the frame is SD_ERR_INVALID.  window is null.
+ *   Every later stage works on the (Hout, Wout) result; grey means and histograms include fill pixels and bars.
+ * Mosaic.  mosaic_geom (B, 6) int32 = cx, cy, s0 .. s3 and mosaic_affine (B, 4, 6) fp64, both or neither: output pixel (x, y) lies in
+ *   quadrant q = (x >= cx) + 2 (y >= cy) and takes Image.transform(AFFINE, m_q, BILINEAR, fillcolor = fill3) of resized image s_q of THIS
+ *   batch.  The kernels clamp cx, cy and s_q: any table is memory-safe.  A row (Wout, Hout, b, -, -, -) with m_0 the identity copies b.
+ * Warp.  affine (B, 6) fp64 = the inverse matrix [m0 .. m5] that maps an output pixel centre (x + 0.5, y + 0.5) to the source position
+ *   (m0 x + m1 y + m2, m3 x + m4 y + m5), Image.transform(AFFINE, ..., BILINEAR, fillcolor = fill3); or persp (B, 8) fp64 as
+ *   sd_perspective_u8's coefficients.  Not both (SD_ERR_INVALID: fold the affine matrix into the homography).  A warp or a mosaic needs
+ *   fill3 (HOST pointer to three bytes).
+ * Blur, Noise, JPEG, Tone.  blur (B, 3), noise (B, 4), jpeg (B, 129), tone (B, 4) int32 on the device: the tables of sd_blur_u8,
+ *   sd_noise_u8, sd_jpeg_u8 and sd_tone_u8 below, the same bytes.  jpeg needs Hout and Wout multiples of 16; jpeg and tone need a
+ *   16-byte aligned workspace; noise and tone need Hout * Wout < 2^31.
+ * ColorJitter.  torchvision ColorJitter on the 8-bit image (ImageEnhance.Brightness / Contrast / Color and the HSV round trip of
+ *   adjust_hue).  jitter_order (B) int32: bits 0-7 = the four op ids in application order, 2 bits each (0 brightness, 1 contrast,
+ *   2 saturation, 3 hue), bits 8-15 = the hue shift byte uint8(hue_factor * 255); jitter_factors (B, 3) fp32; both or neither.
+ * flips: B bytes (bit 0 = horizontal, bit 1 = vertical) or null.  mean3 / std3: HOST pointers to three floats.  The draws are the caller's.
+ *
+ * Launches.  H and V are the geometry's horizontal and vertical kernels; "late" = persp, blur, noise, jpeg or tone is set; with jitter
+ * a memset of the grey sums comes first.  A and B are the workspace's two 8-bit images.
+ *     none                      H, V_norm -> out             mosaic                    H, V -> B, mosaic_norm -> out
+ *     jitter                    H, V -> A, J                 mosaic + jitter           H, V -> B, mosaic -> A, J
+ *     affine                    H, V -> B, affine_norm -> out  mosaic + affine         H, V -> A, mosaic -> B, affine_norm -> out
+ *     affine + jitter           H, V -> B, affine -> A, J    mosaic + affine + jitter  H, V -> A, mosaic -> B, affine -> A, J
+ *     late: H, V, [mosaic], [affine | persp] alternating so that the last writes A, [blur A -> B -> A], [noise], [jpeg], [tone] on A in
+ *           place, then J or k_u8_norm -> out                (J = k_jitter_lsum + k_jitter_norm -> out)
+ * sd_preprocess_kernel_names prints the plan of a descriptor: the launches in order, separated by "; ", each as
+ * "<kernel> grid=XxYxZ block=256 lds=N dst=tmp|A|B|out|sums", "memset", the late stages as "blur", "noise", "jpeg", "tone", or
+ * "refused: <message>" where the chain would return an error (thread-local storage; sets sd_last_error then).
+ *
+ * workspace: [horizontal intermediate | image A | grey sums | image B | JPEG planes | tone histograms], each a multiple of 256 bytes;
+ * sd_preprocess_chain_workspace_bytes() (0 for a descriptor the chain refuses) is the end of the last region the plan uses -- the
+ * intermediate for the plain stretch, the grey sums for the stretch with jitter alone, image B otherwise (the window and letterbox
+ * geometries always reserve up to there), the planes with jpeg, the histograms (behind the planes' place) with tone.  A short workspace
+ * is SD_ERR_WORKSPACE.
+ * Limits.  B <= 65535 when jitter, a warp, a mosaic or a late stage is set (B is a grid dimension there), Hout <= 65535 * 64 with a late
+ * stage; no batch limit on the plain resize. */
+#define SD_GEOM_STRETCH   0
+#define SD_GEOM_WINDOW    1
+#define SD_GEOM_LETTERBOX 2
+typedef struct sd_preprocess_desc {
+    const void* images; int list;
+    int geometry;
+    int B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1;
+    const int *h_bounds, *h_kk; int h_ksize; const int *v_bounds, *v_kk; int v_ksize;
+    const int* window; const uint8_t* flips; const int* jitter_order; const float* jitter_factors;
+    const double *affine, *persp; const int* mosaic_geom; const double* mosaic_affine;
+    const int *blur, *noise, *jpeg, *tone;
+    const uint8_t* fill3; const float *mean3, *std3; float* out;
+} sd_preprocess_desc;
+size_t sd_preprocess_chain_workspace_bytes(const sd_preprocess_desc* d);
+int sd_preprocess_chain(const sd_preprocess_desc* d, void* workspace, size_t workspace_bytes, sd_stream_t stream);
+const char* sd_preprocess_kernel_names(const sd_preprocess_desc* d);
+
+/* The entry points from before the descriptor, kept for their callers: each is sd_preprocess_chain on the fields it names (the stages it
+ * has no argument for are off; a null table is the form below it, bit for bit), with errors under its own name.  The *_workspace_bytes
+ * functions give the chain's layout with every region of their form. */
+/* Resize -> flips -> Normalize.  workspace: the horizontal intermediate. */
 size_t sd_preprocess_workspace_bytes(int B, int Hin, int Win, int Wout);
 int sd_preprocess_images(const uint8_t* images, int B, int Hin, int Win, int Hout, int Wout,
                          const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize,
                          const uint8_t* flips, const float* mean3, const float* std3, float* out,
                          void* workspace, size_t workspace_bytes, sd_stream_t stream);
-
-/* The same with the reference's RandomColorJitter (src/sdnet/data/transforms.py:37-47: torchvision ColorJitter(0.25, 0.25, 0.15, 0.05) on the
- * RESIZED PIL image, before the flips and Normalize) applied per image on the device, byte for byte what Pillow computes
- * (ImageEnhance.Brightness / Contrast / Color and the HSV round trip of adjust_hue).  jitter_order (B) int32: bits 0-7 = the four op ids in
- * application order, 2 bits each (0 brightness, 1 contrast, 2 saturation, 3 hue), bits 8-15 = the hue shift byte uint8(hue_factor * 255);
- * jitter_factors (B, 3) fp32 = brightness, contrast, saturation factors.  The random draws stay with the caller. */
+int sd_preprocess_images_list(const uint8_t* const* images, int B, int Hin, int Win, int Hout, int Wout,
+                              const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize,
+                              const uint8_t* flips, const float* mean3, const float* std3, float* out,
+                              void* workspace, size_t workspace_bytes, sd_stream_t stream);
+/* ... with ColorJitter: both jitter tables are required.  workspace: up to the grey sums. */
 size_t sd_preprocess_jitter_workspace_bytes(int B, int Hin, int Win, int Hout, int Wout);
 int sd_preprocess_images_jitter(const uint8_t* images, int B, int Hin, int Win, int Hout, int Wout, const int* h_bounds, const int* h_kk,
                                 int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips, const int* jitter_order,
                                 const float* jitter_factors, const float* mean3, const float* std3, float* out, void* workspace,
                                 size_t workspace_bytes, sd_stream_t stream);
-
-/* The same two pipelines over B images that are not packed together (a device-resident cache of decoded images): images is a DEVICE
- * array of B device pointers, each to one (Hin, Win, 3) u8 image, any byte alignment, duplicates allowed.  Every other argument, the
- * workspace sizes (sd_preprocess_workspace_bytes / sd_preprocess_jitter_workspace_bytes) and the output bytes are those of
- * sd_preprocess_images / sd_preprocess_images_jitter on the same image bytes.  The horizontal pass stages source rows in LDS:
- * Win <= 21834 (SD_ERR_INVALID beyond). */
-int sd_preprocess_images_list(const uint8_t* const* images, int B, int Hin, int Win, int Hout, int Wout,
-                              const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize,
-                              const uint8_t* flips, const float* mean3, const float* std3, float* out,
-                              void* workspace, size_t workspace_bytes, sd_stream_t stream);
 int sd_preprocess_images_list_jitter(const uint8_t* const* images, int B, int Hin, int Win, int Hout, int Wout, const int* h_bounds,
                                      const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips,
                                      const int* jitter_order, const float* jitter_factors, const float* mean3, const float* std3, float* out,
                                      void* workspace, size_t workspace_bytes, sd_stream_t stream);
-
-/* Both pipelines with a random affine warp (rotate, scale, shift: torchvision RandomAffine on the RESIZED PIL image, in front of the
- * ColorJitter) applied per image on the device, byte for byte Pillow's Image.transform(size, AFFINE, matrix, BILINEAR, fillcolor):
- * affine (B, 6) fp64 on the DEVICE = per image the inverse matrix [m0 .. m5] that maps an output pixel centre (x + 0.5, y + 0.5) to the
- * source position (m0 x + m1 y + m2, m3 x + m4 y + m5), both in pixels of the resized (Hout, Wout) image; any finite matrix is legal, an
- * output pixel whose source position is outside the image takes fill3 (HOST pointer to three bytes, RGB).  jitter_order / jitter_factors
- * as in sd_preprocess_images_jitter, or BOTH null for the chain without ColorJitter (one of the two alone: SD_ERR_INVALID); the contrast
- * op's grey mean is taken over the warped image, fill pixels included.  workspace: sd_preprocess_affine_workspace_bytes() bytes in
- * either case.  The list form takes the pointer table of sd_preprocess_images_list (same Win limit). */
+/* ... with the affine warp: affine and fill3 are required, the jitter is optional.  workspace: up to image B. */
 size_t sd_preprocess_affine_workspace_bytes(int B, int Hin, int Win, int Hout, int Wout);
 int sd_preprocess_images_affine(const uint8_t* images, int B, int Hin, int Win, int Hout, int Wout, const int* h_bounds, const int* h_kk,
                                 int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips, const int* jitter_order,
@@ -391,16 +441,7 @@ int sd_preprocess_images_list_affine(const uint8_t* const* images, int B, int Hi
                                      const int* jitter_order, const float* jitter_factors, const double* affine, const uint8_t fill3[3],
                                      const float* mean3, const float* std3, float* out, void* workspace, size_t workspace_bytes,
                                      sd_stream_t stream);
-
-/* Both pipelines with a mosaic (four images of the batch per sample) composed on the device from the RESIZED images, in front of the
- * warp: Resize -> Mosaic -> [RandomAffine] -> [ColorJitter] -> flips -> Normalize.  mosaic_geom (B, 6) int32 on the DEVICE = per image
- * cx, cy, s0, s1, s2, s3: output pixel (x, y) lies in quadrant q = (x >= cx) + 2 (y >= cy) and takes, byte for byte,
- * Image.transform((Wout, Hout), AFFINE, m_q, BILINEAR, fillcolor = fill3) of resized image s_q at (x, y); mosaic_affine (B, 4, 6) fp64
- * on the DEVICE = the four inverse matrices m_0 .. m_3 per image, in the convention of `affine` above.  Any matrices and any centre in
- * [0, Wout] x [0, Hout] are legal; the tables cannot be checked without a sync, so the kernels clamp cx, cy to that range and s_q to
- * [0, B): any table is memory-safe.  A row (Wout, Hout, b, -, -, -) with m_0 the identity copies image b.  affine: as above, or null
- * for no warp; jitter_order / jitter_factors: both set or both null (one alone, a null table or fill3: SD_ERR_INVALID).  The contrast
- * op's grey mean is taken over the composed (and warped) image.  workspace: sd_preprocess_mosaic_workspace_bytes() bytes in every case. */
+/* ... with the mosaic: both mosaic tables and fill3 are required, the warp and the jitter are optional.  workspace: up to image B. */
 size_t sd_preprocess_mosaic_workspace_bytes(int B, int Hin, int Win, int Hout, int Wout);
 int sd_preprocess_images_mosaic(const uint8_t* images, int B, int Hin, int Win, int Hout, int Wout, const int* h_bounds, const int* h_kk,
                                 int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips, const int* jitter_order,
@@ -412,19 +453,7 @@ int sd_preprocess_images_list_mosaic(const uint8_t* const* images, int B, int Hi
                                      const int* jitter_order, const float* jitter_factors, const double* affine, const int* mosaic_geom,
                                      const double* mosaic_affine, const uint8_t fill3[3], const float* mean3, const float* std3, float* out,
                                      void* workspace, size_t workspace_bytes, sd_stream_t stream);
-
-/* Every pipeline above on a WINDOW of the resized image (crop training at the tile scale, `train --train_tiles`): image b's resize target is
- * a (Hc, Wc) canvas of which only the (Hout, Wout) window at (x0_b, y0_b) is produced -- byte for byte
- * Image.resize((Wc, Hc), BILINEAR).crop((x0, y0, x0 + Wout, y0 + Hout)) -- and everything after the resize works on that window:
- * Window -> [Mosaic] -> [RandomAffine] -> [ColorJitter] -> flips -> Normalize at (Hout, Wout).  h_bounds / h_kk and v_bounds / v_kk are
- * the tables of Win -> Wc and Hin -> Hc.  window (B, 2) int32 on the DEVICE = x0, y0 per image; it cannot be checked without a sync, so
- * the kernels clamp x0 to [0, Wc - Wout] and y0 to [0, Hc - Hout]: any table is memory-safe.  max_rows / max_cols: HOST upper bounds of
- * any window's source row span (v_bounds[y0 + Hout - 1].first + count - v_bounds[y0].first) and column span (h_bounds likewise), from the
- * host's copy of the tables (data/augment.py window_extents); only those rows and columns of the source are read, and spans are clamped
- * to them.  Every stage is optional: flips, jitter_order + jitter_factors, affine, mosaic_geom + mosaic_affine may be null (all null:
- * window + Normalize); fill3 is needed with a warp or a mosaic.  One half of a pair alone, a null window, a window larger than the
- * canvas or max_rows / max_cols outside the source: SD_ERR_INVALID.  The list form stages max_cols source pixels per row in LDS:
- * max_cols <= 21834 (SD_ERR_INVALID beyond), whatever Win is.  workspace: sd_preprocess_window_workspace_bytes() bytes in every case. */
+/* SD_GEOM_WINDOW with (Hg, Wg) = (Hc, Wc), g0 = max_rows, g1 = max_cols; every stage optional.  workspace: up to image B. */
 size_t sd_preprocess_window_workspace_bytes(int B, int max_rows, int Hout, int Wout);
 int sd_preprocess_images_window(const uint8_t* images, int B, int Hin, int Win, int Hc, int Wc, int Hout, int Wout, const int* h_bounds,
                                 const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const int* window, int max_rows,
@@ -437,18 +466,7 @@ int sd_preprocess_images_list_window(const uint8_t* const* images, int B, int Hi
                                      const double* affine, const int* mosaic_geom, const double* mosaic_affine, const uint8_t fill3[3],
                                      const float* mean3, const float* std3, float* out, void* workspace, size_t workspace_bytes,
                                      sd_stream_t stream);
-
-/* Every pipeline above behind a LETTERBOX (aspect-preserving input, `--keep_aspect`): the source is resized to (Hi, Wi) -- the largest size
- * of its aspect ratio that fits the frame, data/augment.py letterbox_geometry -- and pasted at (x0, y0) into a (Hout, Wout) frame of fill3,
- * byte for byte Image.new("RGB", (Wout, Hout), fill3).paste(Image.resize((Wi, Hi), BILINEAR), (x0, y0)), and everything after the resize
- * works on that frame: Letterbox -> [Mosaic] -> [RandomAffine] -> [ColorJitter] -> flips -> Normalize at (Hout, Wout); the contrast op's
- * grey mean is taken over the frame, bars included.  h_bounds / h_kk and v_bounds / v_kk are the tables of Win -> Wi and Hin -> Hi.  The
- * geometry is the same for the whole batch and is checked here: x0 < 0, y0 < 0, x0 + Wi > Wout or y0 + Hi > Hout is SD_ERR_INVALID.
- * Every stage is optional: flips, jitter_order + jitter_factors, affine, mosaic_geom + mosaic_affine may be null (all null: letterbox +
- * Normalize, two launches; a bar pixel is ((float)fill / 255 - mean) / std, the expressions of an image pixel); fill3 is always needed.
- * One half of a pair alone or a null fill3: SD_ERR_INVALID.  With Wi == Wout and Hi == Hout the output is that of the entry points above
- * bit for bit.  The list form takes the pointer table of sd_preprocess_images_list (same Win limit).
- * workspace: sd_preprocess_letterbox_workspace_bytes() bytes in every case. */
+/* SD_GEOM_LETTERBOX with (Hg, Wg) = (Hi, Wi), g0 = y0, g1 = x0; every stage optional.  workspace: up to image B. */
 size_t sd_preprocess_letterbox_workspace_bytes(int B, int Hin, int Wi, int Hout, int Wout);
 int sd_preprocess_images_letterbox(const uint8_t* images, int B, int Hin, int Win, int Hi, int Wi, int Hout, int Wout, int y0, int x0,
                                    const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize,
@@ -460,6 +478,76 @@ int sd_preprocess_images_list_letterbox(const uint8_t* const* images, int B, int
                                         const uint8_t* flips, const int* jitter_order, const float* jitter_factors, const double* affine,
                                         const int* mosaic_geom, const double* mosaic_affine, const uint8_t fill3[3], const float* mean3,
                                         const float* std3, float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream);
+/* Any geometry (geometry, Hg, Wg, g0, g1, window as in the descriptor), every stage optional, + blur.  workspace: up to image B. */
+size_t sd_preprocess_blur_workspace_bytes(int geometry, int B, int Hin, int Win, int Wg, int Hout, int Wout, int g0);
+int sd_preprocess_images_blur(const uint8_t* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout, int g0, int g1,
+                              const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize,
+                              const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
+                              const double* affine, const int* mosaic_geom, const double* mosaic_affine, const int* blur,
+                              const uint8_t fill3[3], const float* mean3, const float* std3, float* out, void* workspace,
+                              size_t workspace_bytes, sd_stream_t stream);
+int sd_preprocess_images_list_blur(const uint8_t* const* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout,
+                                   int g0, int g1, const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk,
+                                   int v_ksize, const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
+                                   const double* affine, const int* mosaic_geom, const double* mosaic_affine, const int* blur,
+                                   const uint8_t fill3[3], const float* mean3, const float* std3, float* out, void* workspace,
+                                   size_t workspace_bytes, sd_stream_t stream);
+/* ... + persp after affine.  workspace: sd_preprocess_blur_workspace_bytes(). */
+int sd_preprocess_images_persp(const uint8_t* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout, int g0, int g1,
+                               const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize,
+                               const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
+                               const double* affine, const double* persp, const int* mosaic_geom, const double* mosaic_affine, const int* blur,
+                               const uint8_t fill3[3], const float* mean3, const float* std3, float* out, void* workspace,
+                               size_t workspace_bytes, sd_stream_t stream);
+int sd_preprocess_images_list_persp(const uint8_t* const* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout,
+                                    int g0, int g1, const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk,
+                                    int v_ksize, const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
+                                    const double* affine, const double* persp, const int* mosaic_geom, const double* mosaic_affine,
+                                    const int* blur, const uint8_t fill3[3], const float* mean3, const float* std3, float* out, void* workspace,
+                                    size_t workspace_bytes, sd_stream_t stream);
+/* ... + jpeg after blur.  workspace: the blur forms' + the decoded planes. */
+size_t sd_preprocess_jpeg_workspace_bytes(int geometry, int B, int Hin, int Win, int Wg, int Hout, int Wout, int g0);
+int sd_preprocess_images_jpeg(const uint8_t* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout, int g0, int g1,
+                              const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize,
+                              const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
+                              const double* affine, const double* persp, const int* mosaic_geom, const double* mosaic_affine, const int* blur,
+                              const int* jpeg, const uint8_t fill3[3], const float* mean3, const float* std3, float* out, void* workspace,
+                              size_t workspace_bytes, sd_stream_t stream);
+int sd_preprocess_images_list_jpeg(const uint8_t* const* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout,
+                                   int g0, int g1, const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk,
+                                   int v_ksize, const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
+                                   const double* affine, const double* persp, const int* mosaic_geom, const double* mosaic_affine,
+                                   const int* blur, const int* jpeg, const uint8_t fill3[3], const float* mean3, const float* std3, float* out,
+                                   void* workspace, size_t workspace_bytes, sd_stream_t stream);
+/* ... + tone after jpeg.  workspace: the JPEG forms' + sd_tone_workspace_bytes(). */
+size_t sd_preprocess_tone_workspace_bytes(int geometry, int B, int Hin, int Win, int Wg, int Hout, int Wout, int g0);
+int sd_preprocess_images_tone(const uint8_t* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout, int g0, int g1,
+                              const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize,
+                              const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
+                              const double* affine, const double* persp, const int* mosaic_geom, const double* mosaic_affine, const int* blur,
+                              const int* jpeg, const int* tone, const uint8_t fill3[3], const float* mean3, const float* std3, float* out,
+                              void* workspace, size_t workspace_bytes, sd_stream_t stream);
+int sd_preprocess_images_list_tone(const uint8_t* const* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout,
+                                   int g0, int g1, const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk,
+                                   int v_ksize, const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
+                                   const double* affine, const double* persp, const int* mosaic_geom, const double* mosaic_affine,
+                                   const int* blur, const int* jpeg, const int* tone, const uint8_t fill3[3], const float* mean3,
+                                   const float* std3, float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream);
+/* ... + noise after tone (it runs between the blur and the JPEG round trip).  workspace: the tone forms' (the stage needs none). */
+size_t sd_preprocess_noise_workspace_bytes(int geometry, int B, int Hin, int Win, int Wg, int Hout, int Wout, int g0);
+int sd_preprocess_images_noise(const uint8_t* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout, int g0, int g1,
+                               const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize,
+                               const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
+                               const double* affine, const double* persp, const int* mosaic_geom, const double* mosaic_affine, const int* blur,
+                               const int* jpeg, const int* tone, const int* noise, const uint8_t fill3[3], const float* mean3, const float* std3,
+                               float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream);
+int sd_preprocess_images_list_noise(const uint8_t* const* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout,
+                                    int g0, int g1, const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk,
+                                    int v_ksize, const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
+                                    const double* affine, const double* persp, const int* mosaic_geom, const double* mosaic_affine,
+                                    const int* blur, const int* jpeg, const int* tone, const int* noise, const uint8_t fill3[3],
+                                    const float* mean3, const float* std3, float* out, void* workspace, size_t workspace_bytes,
+                                    sd_stream_t stream);
 
 /* Gaussian blur of 8-bit images (training augmentation, `train --aug_blur`): image b becomes Image.filter(ImageFilter.GaussianBlur(r_b))
  * byte for byte -- Pillow's three box-blur passes along the rows, then three along the columns, each rounded to bytes.  blur (B, 3) int32
@@ -476,35 +564,6 @@ size_t sd_blur_workspace_bytes(int B, int H, int W);
 int sd_blur_u8(const uint8_t* in, uint8_t* out, int B, int H, int W, const int* blur, void* workspace, size_t workspace_bytes,
                sd_stream_t stream);
 
-/* Every pipeline above with the blur between the warp and the jitter:
- *     Resize | Window | Letterbox -> [Mosaic] -> [RandomAffine] -> Blur -> [ColorJitter] -> flips -> Normalize;
- * the contrast op's grey mean is taken over the blurred image.  One entry point per source form, the geometry chosen by `geometry`:
- *     SD_GEOM_STRETCH    the plain resize to (Hout, Wout); Hg, Wg, g0, g1 are not read and window is null;
- *     SD_GEOM_WINDOW     sd_preprocess_images_window:    (Hg, Wg) = the canvas (Hc, Wc), g0 = max_rows, g1 = max_cols, window (B, 2);
- *     SD_GEOM_LETTERBOX  sd_preprocess_images_letterbox: (Hg, Wg) = the inner image (Hi, Wi), g0 = y0, g1 = x0, window is null;
- * tables, limits and errors are those of the entry point of that geometry.  Every stage is optional (null = off), pairs go together, and
- * fill3 is needed where that entry point needs it.  blur: as sd_blur_u8's.  With blur null the call IS the existing entry point of
- * that geometry and those stages (its output bit for bit); with blur set and no jitter the blurred bytes go through flips + Normalize
- * alone.  workspace: sd_preprocess_blur_workspace_bytes() bytes in every case -- [horizontal intermediate | 8-bit image A | grey sums |
- * 8-bit image B], the layout of the mosaic / window / letterbox forms: the 8-bit stages alternate between A and B so that the blur's
- * horizontal direction writes B and its vertical direction A, where the jitter reads. */
-#define SD_GEOM_STRETCH   0
-#define SD_GEOM_WINDOW    1
-#define SD_GEOM_LETTERBOX 2
-size_t sd_preprocess_blur_workspace_bytes(int geometry, int B, int Hin, int Win, int Wg, int Hout, int Wout, int g0);
-int sd_preprocess_images_blur(const uint8_t* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout, int g0, int g1,
-                              const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize,
-                              const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
-                              const double* affine, const int* mosaic_geom, const double* mosaic_affine, const int* blur,
-                              const uint8_t fill3[3], const float* mean3, const float* std3, float* out, void* workspace,
-                              size_t workspace_bytes, sd_stream_t stream);
-int sd_preprocess_images_list_blur(const uint8_t* const* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout,
-                                   int g0, int g1, const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk,
-                                   int v_ksize, const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
-                                   const double* affine, const int* mosaic_geom, const double* mosaic_affine, const int* blur,
-                                   const uint8_t fill3[3], const float* mean3, const float* std3, float* out, void* workspace,
-                                   size_t workspace_bytes, sd_stream_t stream);
-
 /* Random perspective of 8-bit images (training augmentation, `train --aug_perspective`): image b becomes
  * Image.transform((W, H), PERSPECTIVE, coeffs_b, BILINEAR, fillcolor=fill3) byte for byte.  coeffs (B, 8) fp64 on the DEVICE = a0 .. a7:
  * with xc = x + 0.5, yc = y + 0.5 the output pixel (x, y) samples the source position
@@ -515,24 +574,6 @@ int sd_preprocess_images_list_blur(const uint8_t* const* images, int geometry, i
  * gives the bytes of the affine warp with the same six coefficients.  Nothing in a row is validated: index clamps bound every address for
  * any table.  in and out are (B, H, W, 3) uint8 and must not overlap; fill3 is a HOST pointer.  B <= 65535. */
 int sd_perspective_u8(const uint8_t* in, uint8_t* out, int B, int H, int W, const double* coeffs, const uint8_t fill3[3], sd_stream_t stream);
-
-/* The blur forms with the perspective in the warp slot:
- *     Resize | Window | Letterbox -> [Mosaic] -> Perspective -> [Blur] -> [ColorJitter] -> flips -> Normalize.
- * The arguments of sd_preprocess_images_blur / _list_blur plus persp (B, 8) fp64 on the device after affine.  With persp null the call IS
- * the blur form.  With persp set, affine must be null (SD_ERR_INVALID: the host folds the affine matrix into the homography, so an image
- * is resampled once), fill3 is needed and blur may be null.  workspace: sd_preprocess_blur_workspace_bytes() bytes, the same layout. */
-int sd_preprocess_images_persp(const uint8_t* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout, int g0, int g1,
-                               const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize,
-                               const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
-                               const double* affine, const double* persp, const int* mosaic_geom, const double* mosaic_affine, const int* blur,
-                               const uint8_t fill3[3], const float* mean3, const float* std3, float* out, void* workspace,
-                               size_t workspace_bytes, sd_stream_t stream);
-int sd_preprocess_images_list_persp(const uint8_t* const* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout,
-                                    int g0, int g1, const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk,
-                                    int v_ksize, const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
-                                    const double* affine, const double* persp, const int* mosaic_geom, const double* mosaic_affine,
-                                    const int* blur, const uint8_t fill3[3], const float* mean3, const float* std3, float* out, void* workspace,
-                                    size_t workspace_bytes, sd_stream_t stream);
 
 /* JPEG compression of 8-bit images (training augmentation, `train --aug_jpeg`): image b becomes what Pillow's
  * Image.save(buf, "JPEG", qtables=[ql_b, qc_b], subsampling=2) followed by Image.open(buf) gives, byte for byte: libjpeg's RGB -> YCbCr,
@@ -547,26 +588,6 @@ int sd_preprocess_images_list_persp(const uint8_t* const* images, int geometry, 
 size_t sd_jpeg_workspace_bytes(int B, int H, int W);
 int sd_jpeg_u8(const uint8_t* in, uint8_t* out, int B, int H, int W, const int* table, void* workspace, size_t workspace_bytes,
                sd_stream_t stream);
-
-/* The perspective forms with the JPEG round trip between the blur and the jitter:
- *     Resize | Window | Letterbox -> [Mosaic] -> [Affine | Perspective] -> [Blur] -> JPEG -> [ColorJitter] -> flips -> Normalize.
- * The arguments of sd_preprocess_images_persp / _list_persp plus jpeg (B, 129) int32 on the device after blur, as sd_jpeg_u8's table.
- * With jpeg null the call IS the perspective form.  With jpeg set every other table is optional, Hout and Wout must be multiples of 16
- * and the workspace 16-byte aligned (SD_ERR_INVALID otherwise).  workspace: sd_preprocess_jpeg_workspace_bytes() bytes =
- * sd_preprocess_blur_workspace_bytes() in that layout, then the decoded planes. */
-size_t sd_preprocess_jpeg_workspace_bytes(int geometry, int B, int Hin, int Win, int Wg, int Hout, int Wout, int g0);
-int sd_preprocess_images_jpeg(const uint8_t* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout, int g0, int g1,
-                              const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize,
-                              const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
-                              const double* affine, const double* persp, const int* mosaic_geom, const double* mosaic_affine, const int* blur,
-                              const int* jpeg, const uint8_t fill3[3], const float* mean3, const float* std3, float* out, void* workspace,
-                              size_t workspace_bytes, sd_stream_t stream);
-int sd_preprocess_images_list_jpeg(const uint8_t* const* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout,
-                                   int g0, int g1, const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk,
-                                   int v_ksize, const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
-                                   const double* affine, const double* persp, const int* mosaic_geom, const double* mosaic_affine,
-                                   const int* blur, const int* jpeg, const uint8_t fill3[3], const float* mean3, const float* std3, float* out,
-                                   void* workspace, size_t workspace_bytes, sd_stream_t stream);
 
 /* Histogram tone curves of 8-bit images (training augmentation, `train --aug_equalize / --aug_autocontrast`): image b becomes what Pillow's
  * ImageOps.equalize(img) (mode 2) or ImageOps.autocontrast(img, cutoff) (mode 1) gives, byte for byte: per channel a 256-bin histogram of
@@ -583,27 +604,6 @@ size_t sd_tone_workspace_bytes(int B);
 int sd_tone_u8(const uint8_t* in, uint8_t* out, int B, int H, int W, const int* table, void* workspace, size_t workspace_bytes,
                sd_stream_t stream);
 
-/* The JPEG forms with the tone stage between the JPEG round trip and the jitter:
- *     Resize | Window | Letterbox -> [Mosaic] -> [Affine | Perspective] -> [Blur] -> [JPEG] -> Tone -> [ColorJitter] -> flips -> Normalize.
- * The arguments of sd_preprocess_images_jpeg / _list_jpeg plus tone (B, 4) int32 on the device after jpeg, as sd_tone_u8's table.  With
- * tone null the call IS the JPEG form.  With tone set every other table is optional and the workspace must be 16-byte aligned
- * (SD_ERR_INVALID otherwise); the stage has no size rule of its own (Hout and Wout must be multiples of 16 only when jpeg is set too).
- * The histogram is that of the 8-bit frame as it stands there, fill colour and letterbox bars included.  workspace:
- * sd_preprocess_tone_workspace_bytes() bytes = sd_preprocess_jpeg_workspace_bytes() in that layout, then sd_tone_workspace_bytes(). */
-size_t sd_preprocess_tone_workspace_bytes(int geometry, int B, int Hin, int Win, int Wg, int Hout, int Wout, int g0);
-int sd_preprocess_images_tone(const uint8_t* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout, int g0, int g1,
-                              const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize,
-                              const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
-                              const double* affine, const double* persp, const int* mosaic_geom, const double* mosaic_affine, const int* blur,
-                              const int* jpeg, const int* tone, const uint8_t fill3[3], const float* mean3, const float* std3, float* out,
-                              void* workspace, size_t workspace_bytes, sd_stream_t stream);
-int sd_preprocess_images_list_tone(const uint8_t* const* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout,
-                                   int g0, int g1, const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk,
-                                   int v_ksize, const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
-                                   const double* affine, const double* persp, const int* mosaic_geom, const double* mosaic_affine,
-                                   const int* blur, const int* jpeg, const int* tone, const uint8_t fill3[3], const float* mean3,
-                                   const float* std3, float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream);
-
 /* Sensor noise on 8-bit images (training augmentation, `train --aug_noise / --aug_noise_shot`): read noise plus signal-dependent shot noise,
  * the heteroscedastic-Gaussian sensor model per channel and pixel in the 8-bit domain (no gamma is modelled), all integer and bit-exact:
  * with o the byte's offset inside ITS image, word = Philox4x32-10(counter (o >> 2, 0, 0, 0), key (k0, k1))[o & 3]; z = the unit normal in
@@ -617,26 +617,6 @@ int sd_preprocess_images_list_tone(const uint8_t* const* images, int geometry, i
  * B <= 65535.  sd_noise_normal_table (host only) copies the half table H[j] = round(1024 Phi^-1((2048 + j + 0.5) / 4096)). */
 int sd_noise_normal_table(uint16_t out[2048]);
 int sd_noise_u8(const uint8_t* in, uint8_t* out, int B, int H, int W, const int* table, sd_stream_t stream);
-
-/* The tone forms with the noise stage between the blur and the JPEG round trip (optics -> sensor -> encoder):
- *     Resize | Window | Letterbox -> [Mosaic] -> [Affine | Perspective] -> [Blur] -> Noise -> [JPEG] -> [Tone] -> [ColorJitter] -> flips -> Normalize.
- * The arguments of sd_preprocess_images_tone / _list_tone plus noise (B, 4) int32 on the device after tone, as sd_noise_u8's table.  With
- * noise null the call IS the tone form.  With noise set every other table is optional; the stage has no size or alignment rule of its own
- * beyond Hout * Wout < 2^31 and needs no workspace: sd_preprocess_noise_workspace_bytes() = sd_preprocess_tone_workspace_bytes(). */
-size_t sd_preprocess_noise_workspace_bytes(int geometry, int B, int Hin, int Win, int Wg, int Hout, int Wout, int g0);
-int sd_preprocess_images_noise(const uint8_t* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout, int g0, int g1,
-                               const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize,
-                               const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
-                               const double* affine, const double* persp, const int* mosaic_geom, const double* mosaic_affine, const int* blur,
-                               const int* jpeg, const int* tone, const int* noise, const uint8_t fill3[3], const float* mean3, const float* std3,
-                               float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream);
-int sd_preprocess_images_list_noise(const uint8_t* const* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout,
-                                    int g0, int g1, const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk,
-                                    int v_ksize, const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
-                                    const double* affine, const double* persp, const int* mosaic_geom, const double* mosaic_affine,
-                                    const int* blur, const int* jpeg, const int* tone, const int* noise, const uint8_t fill3[3],
-                                    const float* mean3, const float* std3, float* out, void* workspace, size_t workspace_bytes,
-                                    sd_stream_t stream);
 
 /* ---- loss: src/sdnet/model/loss.py:17-64,91-117------------------------------------------- */
 

@@ -45,6 +45,16 @@ class ConvDesc(C.Structure):
     _fields_ = [(n, c_int) for n in ("B", "Hi", "Wi", "Cin", "Ho", "Wo", "Cout", "R", "S", "stride", "pad")]
 
 
+class PreprocessDesc(C.Structure):
+    """sd_preprocess_desc (include/sdnet_hip.h): a zeroed one is the packed stretch chain with every optional stage off."""
+    _fields_ = ([("images", c_vp), ("list", c_int), ("geometry", c_int)] +
+                [(n, c_int) for n in ("B", "Hin", "Win", "Hg", "Wg", "Hout", "Wout", "g0", "g1")] +
+                [("h_bounds", c_vp), ("h_kk", c_vp), ("h_ksize", c_int), ("v_bounds", c_vp), ("v_kk", c_vp), ("v_ksize", c_int)] +
+                [(n, c_vp) for n in ("window", "flips", "jitter_order", "jitter_factors", "affine", "persp", "mosaic_geom", "mosaic_affine",
+                                     "blur", "noise", "jpeg", "tone")] +
+                [("fill3", C.POINTER(C.c_ubyte)), ("mean3", C.POINTER(c_float)), ("std3", C.POINTER(c_float)), ("out", c_vp)])
+
+
 _MAP = [c_vp, c_i64, c_i64]          # pointer, batch stride, channel stride
 _PEAK_OUT = [c_vp, c_vp, c_vp, c_vp, c_vp]
 
@@ -88,6 +98,10 @@ _SIGNATURES = {
     "sd_tile_merge_nms": (c_int, _MAP + [c_int] + _MAP + [c_int, c_vp, c_vp] + [c_int] * 6 + [c_vp]),
     # cross-label anchor suppression: map, out, B, M, h, w, R, stream
     "sd_label_nms": (c_int, _MAP + [c_vp] + [c_int] * 5 + [c_vp]),
+    # the preprocess chain: descriptor, workspace, bytes, stream (data/augment.py calls this one; the forms below it are the legacy C API)
+    "sd_preprocess_chain_workspace_bytes": (c_size, [C.POINTER(PreprocessDesc)]),
+    "sd_preprocess_chain": (c_int, [C.POINTER(PreprocessDesc), c_vp, c_size, c_vp]),
+    "sd_preprocess_kernel_names": (C.c_char_p, [C.POINTER(PreprocessDesc)]),
     "sd_preprocess_workspace_bytes": (c_size, [c_int] * 4),
     "sd_preprocess_images": (c_int, [c_vp] + [c_int] * 5 + [c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp, C.POINTER(c_float), C.POINTER(c_float),
                                                 c_vp, c_vp, c_size, c_vp]),

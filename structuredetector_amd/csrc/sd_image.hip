@@ -851,789 +851,331 @@ using namespace sd;
 
 extern "C" {
 
+// ---- the legacy size queries: the chain's workspace layout (below) with the regions their forms use --------------------------------
 size_t sd_preprocess_workspace_bytes(int B, int Hin, int Win, int Wout) { return align_up((size_t)B * Hin * Wout * 3, 256); }
 
 size_t sd_preprocess_jitter_workspace_bytes(int B, int Hin, int Win, int Hout, int Wout) {
     return sd_preprocess_workspace_bytes(B, Hin, Win, Wout) + align_up((size_t)B * Hout * Wout * 3, 256) + align_up((size_t)B * 8, 256);
 }
 
-static int preprocess_check(const char* what, const uint8_t* images, int B, int Hin, int Win, int Hout, int Wout, const int* h_bounds, const int* h_kk,
-                            int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const float* mean3, const float* std3, float* out,
-                            void* workspace) {
-    SD_REQUIRE(images && out && h_bounds && h_kk && v_bounds && v_kk && mean3 && std3 && workspace, SD_ERR_INVALID, "%s: null pointer", what);
-    SD_REQUIRE(B > 0 && Hin > 0 && Win > 0 && Hout > 0 && Wout > 0 && h_ksize > 0 && v_ksize > 0, SD_ERR_INVALID, "%s: bad shape", what);
-    SD_REQUIRE((int64_t)B * std::max(Hin, Hout) * std::max(Win, Wout) * 3 < (1ll << 40), SD_ERR_INVALID, "%s: batch too large", what);
-    SD_REQUIRE(std3[0] != 0.f && std3[1] != 0.f && std3[2] != 0.f, SD_ERR_INVALID, "%s: zero std", what);
-    return 0;
-}
-
-// the launches after the horizontal pass (tmp = its 8-bit intermediate at the start of the workspace), shared by the packed and the list forms
-static int preprocess_tail(int B, int Hin, int Hout, int Wout, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips,
-                           const float* mean3, const float* std3, float* out, uint8_t* tmp, hipStream_t st) {
-    hipLaunchKernelGGL(k_resample_v_norm, dim3(cdiv((int64_t)B * Hout * Wout, 256)), dim3(256), 0, st, tmp, out, Hin, Hout, Wout, v_bounds, v_kk,
-                       v_ksize, flips, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], B);
-    SD_LAUNCH_CHECK();
-    return 0;
-}
-
-// vertical pass into an 8-bit image, and the two jitter launches on an 8-bit image: the halves of the jitter tail, shared with the affine forms
-static int resample_v_u8(int B, int Hin, int Hout, int Wout, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* tmp, uint8_t* img,
-                         hipStream_t st) {
-    hipLaunchKernelGGL(k_resample_v_u8, dim3(cdiv((int64_t)B * Hout * Wout, 256)), dim3(256), 0, st, tmp, img, Hin, Hout, Wout, v_bounds, v_kk,
-                       v_ksize, B);
-    SD_LAUNCH_CHECK();
-    return 0;
-}
-
-static int jitter_norm(int B, int Hout, int Wout, const uint8_t* flips, const int* jitter_order, const float* jitter_factors, const float* mean3,
-                       const float* std3, float* out, const uint8_t* img, unsigned long long* lsum, hipStream_t st) {
-    const int64_t npix = (int64_t)Hout * Wout;
-    hipLaunchKernelGGL(k_jitter_lsum, dim3(std::min<int64_t>(cdiv(npix, 256), 64), B), dim3(256), 0, st, img, npix, jitter_order, jitter_factors, lsum);
-    SD_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_jitter_norm, dim3(cdiv((int64_t)B * npix, 256)), dim3(256), 0, st, img, out, Hout, Wout, jitter_order, jitter_factors, lsum,
-                       flips, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], B);
-    SD_LAUNCH_CHECK();
-    return 0;
-}
-
-static int preprocess_jitter_tail(int B, int Hin, int Win, int Hout, int Wout, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips,
-                                  const int* jitter_order, const float* jitter_factors, const float* mean3, const float* std3, float* out,
-                                  uint8_t* tmp, hipStream_t st) {
-    uint8_t* img = tmp + sd_preprocess_workspace_bytes(B, Hin, Win, Wout);
-    unsigned long long* lsum = reinterpret_cast<unsigned long long*>(img + align_up((size_t)B * Hout * Wout * 3, 256));
-    if (int e = resample_v_u8(B, Hin, Hout, Wout, v_bounds, v_kk, v_ksize, tmp, img, st)) return e;
-    return jitter_norm(B, Hout, Wout, flips, jitter_order, jitter_factors, mean3, std3, out, img, lsum, st);
-}
-
-int sd_preprocess_images(const uint8_t* images, int B, int Hin, int Win, int Hout, int Wout, const int* h_bounds, const int* h_kk,
-                         int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips, const float* mean3,
-                         const float* std3, float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
-    if (int e = preprocess_check("sd_preprocess_images", images, B, Hin, Win, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, mean3, std3,
-                                 out, workspace)) return e;
-    SD_REQUIRE(workspace_bytes >= sd_preprocess_workspace_bytes(B, Hin, Win, Wout), SD_ERR_WORKSPACE, "sd_preprocess_images: workspace %zu < %zu",
-               workspace_bytes, sd_preprocess_workspace_bytes(B, Hin, Win, Wout));
-    hipStream_t st = (hipStream_t)stream;
-    uint8_t* tmp = reinterpret_cast<uint8_t*>(workspace);
-    const int64_t rows = (int64_t)B * Hin;
-    hipLaunchKernelGGL(k_resample_h, dim3(cdiv(rows * Wout, 256)), dim3(256), 0, st, images, tmp, Hin, Win, Wout, h_bounds, h_kk, h_ksize, rows);
-    SD_LAUNCH_CHECK();
-    return preprocess_tail(B, Hin, Hout, Wout, v_bounds, v_kk, v_ksize, flips, mean3, std3, out, tmp, st);
-}
-
-int sd_preprocess_images_jitter(const uint8_t* images, int B, int Hin, int Win, int Hout, int Wout, const int* h_bounds, const int* h_kk,
-                                int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips, const int* jitter_order,
-                                const float* jitter_factors, const float* mean3, const float* std3, float* out, void* workspace,
-                                size_t workspace_bytes, sd_stream_t stream) {
-    if (int e = preprocess_check("sd_preprocess_images_jitter", images, B, Hin, Win, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, mean3,
-                                 std3, out, workspace)) return e;
-    SD_REQUIRE(jitter_order && jitter_factors, SD_ERR_INVALID, "sd_preprocess_images_jitter: null jitter parameters");
-    SD_REQUIRE(B <= 65535, SD_ERR_INVALID, "sd_preprocess_images_jitter: batch %d > 65535", B);
-    SD_REQUIRE(workspace_bytes >= sd_preprocess_jitter_workspace_bytes(B, Hin, Win, Hout, Wout), SD_ERR_WORKSPACE,
-               "sd_preprocess_images_jitter: workspace %zu < %zu", workspace_bytes, sd_preprocess_jitter_workspace_bytes(B, Hin, Win, Hout, Wout));
-    hipStream_t st = (hipStream_t)stream;
-    uint8_t* tmp = reinterpret_cast<uint8_t*>(workspace);
-    uint8_t* img = tmp + sd_preprocess_workspace_bytes(B, Hin, Win, Wout);
-    SD_HIP(hipMemsetAsync(img + align_up((size_t)B * Hout * Wout * 3, 256), 0, (size_t)B * 8, st));        // lsum
-    const int64_t rows = (int64_t)B * Hin;
-    hipLaunchKernelGGL(k_resample_h, dim3(cdiv(rows * Wout, 256)), dim3(256), 0, st, images, tmp, Hin, Win, Wout, h_bounds, h_kk, h_ksize, rows);
-    SD_LAUNCH_CHECK();
-    return preprocess_jitter_tail(B, Hin, Win, Hout, Wout, v_bounds, v_kk, v_ksize, flips, jitter_order, jitter_factors, mean3, std3, out, tmp, st);
-}
-
-// ---- the same from a device table of B image pointers (k_resample_h_list for the horizontal pass) ----
-static int preprocess_list_check(const char* what, const uint8_t* const* images, int B, int Hin, int Win, int Hout, int Wout, const int* h_bounds,
-                                 const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const float* mean3,
-                                 const float* std3, float* out, void* workspace, int* rpb, int* blocks_per_image) {
-    if (int e = preprocess_check(what, reinterpret_cast<const uint8_t*>(images), B, Hin, Win, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk,
-                                 v_ksize, mean3, std3, out, workspace)) return e;
-    SD_REQUIRE((int64_t)Win * 3 + 32 <= HL_LDS_BYTES, SD_ERR_INVALID, "%s: source rows of %d pixels exceed the LDS staging buffer (at most %d)",
-               what, Win, (HL_LDS_BYTES - 32) / 3);
-    *rpb = (int)std::min<int64_t>(HL_ROWS, (HL_LDS_BYTES - 32) / ((int64_t)Win * 3));
-    *blocks_per_image = cdiv(Hin, *rpb);
-    SD_REQUIRE((int64_t)B * *blocks_per_image < (1ll << 31), SD_ERR_INVALID, "%s: batch too large", what);
-    return 0;
-}
-
-static int resample_h_list(const uint8_t* const* images, uint8_t* tmp, int B, int Hin, int Win, int Wout, const int* h_bounds, const int* h_kk,
-                           int h_ksize, int rpb, int blocks_per_image, hipStream_t st) {
-    const size_t lds = (size_t)rpb * Win * 3 + 32;
-    hipLaunchKernelGGL(k_resample_h_list, dim3((unsigned)((int64_t)B * blocks_per_image)), dim3(256), lds, st, images, tmp, Hin, Win, Wout, h_bounds,
-                       h_kk, h_ksize, rpb, blocks_per_image);
-    SD_LAUNCH_CHECK();
-    return 0;
-}
-
-int sd_preprocess_images_list(const uint8_t* const* images, int B, int Hin, int Win, int Hout, int Wout, const int* h_bounds, const int* h_kk,
-                              int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips, const float* mean3,
-                              const float* std3, float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
-    int rpb = 0, bpi = 0;
-    if (int e = preprocess_list_check("sd_preprocess_images_list", images, B, Hin, Win, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
-                                      mean3, std3, out, workspace, &rpb, &bpi)) return e;
-    SD_REQUIRE(workspace_bytes >= sd_preprocess_workspace_bytes(B, Hin, Win, Wout), SD_ERR_WORKSPACE, "sd_preprocess_images_list: workspace %zu < %zu",
-               workspace_bytes, sd_preprocess_workspace_bytes(B, Hin, Win, Wout));
-    hipStream_t st = (hipStream_t)stream;
-    uint8_t* tmp = reinterpret_cast<uint8_t*>(workspace);
-    if (int e = resample_h_list(images, tmp, B, Hin, Win, Wout, h_bounds, h_kk, h_ksize, rpb, bpi, st)) return e;
-    return preprocess_tail(B, Hin, Hout, Wout, v_bounds, v_kk, v_ksize, flips, mean3, std3, out, tmp, st);
-}
-
-int sd_preprocess_images_list_jitter(const uint8_t* const* images, int B, int Hin, int Win, int Hout, int Wout, const int* h_bounds, const int* h_kk,
-                                     int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips, const int* jitter_order,
-                                     const float* jitter_factors, const float* mean3, const float* std3, float* out, void* workspace,
-                                     size_t workspace_bytes, sd_stream_t stream) {
-    int rpb = 0, bpi = 0;
-    if (int e = preprocess_list_check("sd_preprocess_images_list_jitter", images, B, Hin, Win, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk,
-                                      v_ksize, mean3, std3, out, workspace, &rpb, &bpi)) return e;
-    SD_REQUIRE(jitter_order && jitter_factors, SD_ERR_INVALID, "sd_preprocess_images_list_jitter: null jitter parameters");
-    SD_REQUIRE(B <= 65535, SD_ERR_INVALID, "sd_preprocess_images_list_jitter: batch %d > 65535", B);
-    SD_REQUIRE(workspace_bytes >= sd_preprocess_jitter_workspace_bytes(B, Hin, Win, Hout, Wout), SD_ERR_WORKSPACE,
-               "sd_preprocess_images_list_jitter: workspace %zu < %zu", workspace_bytes, sd_preprocess_jitter_workspace_bytes(B, Hin, Win, Hout, Wout));
-    hipStream_t st = (hipStream_t)stream;
-    uint8_t* tmp = reinterpret_cast<uint8_t*>(workspace);
-    uint8_t* img = tmp + sd_preprocess_workspace_bytes(B, Hin, Win, Wout);
-    SD_HIP(hipMemsetAsync(img + align_up((size_t)B * Hout * Wout * 3, 256), 0, (size_t)B * 8, st));        // lsum
-    if (int e = resample_h_list(images, tmp, B, Hin, Win, Wout, h_bounds, h_kk, h_ksize, rpb, bpi, st)) return e;
-    return preprocess_jitter_tail(B, Hin, Win, Hout, Wout, v_bounds, v_kk, v_ksize, flips, jitter_order, jitter_factors, mean3, std3, out, tmp, st);
-}
-
-// ---- RandomAffine between the resize and the jitter / normalise (k_affine_u8, k_affine_norm) ----
-// workspace: the jitter forms' [horizontal intermediate | 8-bit image | grey sums] + a second 8-bit image.  The vertical pass writes the
-// second image, the warp reads it: with jitter into the first (where the jitter launches expect their input), without straight to `out`.
 size_t sd_preprocess_affine_workspace_bytes(int B, int Hin, int Win, int Hout, int Wout) {
     return sd_preprocess_jitter_workspace_bytes(B, Hin, Win, Hout, Wout) + align_up((size_t)B * Hout * Wout * 3, 256);
 }
 
-static int affine_check(const char* what, int B, int Hin, int Win, int Hout, int Wout, const int* jitter_order, const float* jitter_factors,
-                        const double* affine, const uint8_t* fill3, size_t workspace_bytes) {
-    SD_REQUIRE(affine && fill3, SD_ERR_INVALID, "%s: null affine matrices or fill colour", what);
-    SD_REQUIRE((jitter_order == nullptr) == (jitter_factors == nullptr), SD_ERR_INVALID,
-               "%s: jitter_order and jitter_factors go together (both null = no jitter)", what);
-    SD_REQUIRE(B <= 65535, SD_ERR_INVALID, "%s: batch %d > 65535", what, B);
-    SD_REQUIRE(workspace_bytes >= sd_preprocess_affine_workspace_bytes(B, Hin, Win, Hout, Wout), SD_ERR_WORKSPACE, "%s: workspace %zu < %zu", what,
-               workspace_bytes, sd_preprocess_affine_workspace_bytes(B, Hin, Win, Hout, Wout));
-    return 0;
-}
-
-// the launches after the vertical pass (`resized` = the 8-bit resized image), shared with the window forms
-static int affine_stages(int B, int Hout, int Wout, const uint8_t* flips, const int* jitter_order, const float* jitter_factors, const double* affine,
-                         const uint8_t* fill3, const float* mean3, const float* std3, float* out, const uint8_t* resized, uint8_t* img,
-                         unsigned long long* lsum, hipStream_t st) {
-    const dim3 grid(cdiv(Wout, AF_TX * AF_PX), cdiv(Hout, AF_TY), B);
-    if (!jitter_order) {
-        hipLaunchKernelGGL(k_affine_norm, grid, dim3(256), 0, st, resized, out, Hout, Wout, affine, (int)fill3[0], (int)fill3[1], (int)fill3[2], flips,
-                           mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
-        SD_LAUNCH_CHECK();
-        return 0;
-    }
-    hipLaunchKernelGGL(k_affine_u8, grid, dim3(256), 0, st, resized, img, Hout, Wout, affine, (int)fill3[0], (int)fill3[1], (int)fill3[2]);
-    SD_LAUNCH_CHECK();
-    return jitter_norm(B, Hout, Wout, flips, jitter_order, jitter_factors, mean3, std3, out, img, lsum, st);
-}
-
-// the launches after the horizontal pass
-static int preprocess_affine_tail(int B, int Hin, int Win, int Hout, int Wout, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips,
-                                  const int* jitter_order, const float* jitter_factors, const double* affine, const uint8_t* fill3,
-                                  const float* mean3, const float* std3, float* out, uint8_t* tmp, hipStream_t st) {
-    uint8_t* img = tmp + sd_preprocess_workspace_bytes(B, Hin, Win, Wout);
-    unsigned long long* lsum = reinterpret_cast<unsigned long long*>(img + align_up((size_t)B * Hout * Wout * 3, 256));
-    uint8_t* resized = tmp + sd_preprocess_jitter_workspace_bytes(B, Hin, Win, Hout, Wout);
-    if (int e = resample_v_u8(B, Hin, Hout, Wout, v_bounds, v_kk, v_ksize, tmp, resized, st)) return e;
-    return affine_stages(B, Hout, Wout, flips, jitter_order, jitter_factors, affine, fill3, mean3, std3, out, resized, img, lsum, st);
-}
-
-int sd_preprocess_images_affine(const uint8_t* images, int B, int Hin, int Win, int Hout, int Wout, const int* h_bounds, const int* h_kk,
-                                int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips, const int* jitter_order,
-                                const float* jitter_factors, const double* affine, const uint8_t* fill3, const float* mean3, const float* std3,
-                                float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
-    if (int e = preprocess_check("sd_preprocess_images_affine", images, B, Hin, Win, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, mean3,
-                                 std3, out, workspace)) return e;
-    if (int e = affine_check("sd_preprocess_images_affine", B, Hin, Win, Hout, Wout, jitter_order, jitter_factors, affine, fill3, workspace_bytes))
-        return e;
-    hipStream_t st = (hipStream_t)stream;
-    uint8_t* tmp = reinterpret_cast<uint8_t*>(workspace);
-    if (jitter_order) {
-        uint8_t* img = tmp + sd_preprocess_workspace_bytes(B, Hin, Win, Wout);
-        SD_HIP(hipMemsetAsync(img + align_up((size_t)B * Hout * Wout * 3, 256), 0, (size_t)B * 8, st));    // lsum
-    }
-    const int64_t rows = (int64_t)B * Hin;
-    hipLaunchKernelGGL(k_resample_h, dim3(cdiv(rows * Wout, 256)), dim3(256), 0, st, images, tmp, Hin, Win, Wout, h_bounds, h_kk, h_ksize, rows);
-    SD_LAUNCH_CHECK();
-    return preprocess_affine_tail(B, Hin, Win, Hout, Wout, v_bounds, v_kk, v_ksize, flips, jitter_order, jitter_factors, affine, fill3, mean3, std3,
-                                  out, tmp, st);
-}
-
-int sd_preprocess_images_list_affine(const uint8_t* const* images, int B, int Hin, int Win, int Hout, int Wout, const int* h_bounds,
-                                     const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips,
-                                     const int* jitter_order, const float* jitter_factors, const double* affine, const uint8_t* fill3,
-                                     const float* mean3, const float* std3, float* out, void* workspace, size_t workspace_bytes,
-                                     sd_stream_t stream) {
-    int rpb = 0, bpi = 0;
-    if (int e = preprocess_list_check("sd_preprocess_images_list_affine", images, B, Hin, Win, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk,
-                                      v_ksize, mean3, std3, out, workspace, &rpb, &bpi)) return e;
-    if (int e = affine_check("sd_preprocess_images_list_affine", B, Hin, Win, Hout, Wout, jitter_order, jitter_factors, affine, fill3,
-                             workspace_bytes)) return e;
-    hipStream_t st = (hipStream_t)stream;
-    uint8_t* tmp = reinterpret_cast<uint8_t*>(workspace);
-    if (jitter_order) {
-        uint8_t* img = tmp + sd_preprocess_workspace_bytes(B, Hin, Win, Wout);
-        SD_HIP(hipMemsetAsync(img + align_up((size_t)B * Hout * Wout * 3, 256), 0, (size_t)B * 8, st));    // lsum
-    }
-    if (int e = resample_h_list(images, tmp, B, Hin, Win, Wout, h_bounds, h_kk, h_ksize, rpb, bpi, st)) return e;
-    return preprocess_affine_tail(B, Hin, Win, Hout, Wout, v_bounds, v_kk, v_ksize, flips, jitter_order, jitter_factors, affine, fill3, mean3, std3,
-                                  out, tmp, st);
-}
-
-// ---- Mosaic between the resize and the warp / jitter / normalise (k_mosaic_u8, k_mosaic_norm) ----
-// workspace: that of the affine forms, [horizontal intermediate | 8-bit image A | grey sums | 8-bit image B].  The jitter launches read A, so
-// the 8-bit stages are laid out backwards from there: without a warp the vertical pass writes B and the mosaic A (or `out`, fused); with a
-// warp the vertical pass writes A, the mosaic B, and the warp A again (or `out`, fused) -- A's resized bytes are dead by then.
 size_t sd_preprocess_mosaic_workspace_bytes(int B, int Hin, int Win, int Hout, int Wout) {
     return sd_preprocess_affine_workspace_bytes(B, Hin, Win, Hout, Wout);
 }
 
-static int mosaic_check(const char* what, int B, int Hin, int Win, int Hout, int Wout, const int* jitter_order, const float* jitter_factors,
-                        const int* mosaic_geom, const double* mosaic_affine, const uint8_t* fill3, size_t workspace_bytes) {
-    SD_REQUIRE(mosaic_geom && mosaic_affine && fill3, SD_ERR_INVALID, "%s: null mosaic tables or fill colour", what);
-    SD_REQUIRE((jitter_order == nullptr) == (jitter_factors == nullptr), SD_ERR_INVALID,
-               "%s: jitter_order and jitter_factors go together (both null = no jitter)", what);
-    SD_REQUIRE(B <= 65535, SD_ERR_INVALID, "%s: batch %d > 65535", what, B);
-    SD_REQUIRE(workspace_bytes >= sd_preprocess_mosaic_workspace_bytes(B, Hin, Win, Hout, Wout), SD_ERR_WORKSPACE, "%s: workspace %zu < %zu", what,
-               workspace_bytes, sd_preprocess_mosaic_workspace_bytes(B, Hin, Win, Hout, Wout));
-    return 0;
-}
-
-// the launches after the vertical pass, shared with the window forms: the resized image is in A with a warp, in B without (see above)
-static int mosaic_stages(int B, int Hout, int Wout, const uint8_t* flips, const int* jitter_order, const float* jitter_factors, const double* affine,
-                         const int* mosaic_geom, const double* mosaic_affine, const uint8_t* fill3, const float* mean3, const float* std3, float* out,
-                         uint8_t* img_a, uint8_t* img_b, unsigned long long* lsum, hipStream_t st) {
-    uint8_t* resized = affine ? img_a : img_b;
-    uint8_t* mosaic = affine ? img_b : img_a;
-    const int f0 = fill3[0], f1 = fill3[1], f2 = fill3[2];
-    const dim3 grid(cdiv(Wout, AF_TX * AF_PX), cdiv(Hout, AF_TY), B);
-    if (!affine && !jitter_order) {
-        hipLaunchKernelGGL(k_mosaic_norm, grid, dim3(256), 0, st, resized, out, Hout, Wout, mosaic_geom, mosaic_affine, f0, f1, f2, flips, mean3[0],
-                           mean3[1], mean3[2], std3[0], std3[1], std3[2]);
-        SD_LAUNCH_CHECK();
-        return 0;
-    }
-    hipLaunchKernelGGL(k_mosaic_u8, grid, dim3(256), 0, st, resized, mosaic, Hout, Wout, mosaic_geom, mosaic_affine, f0, f1, f2);
-    SD_LAUNCH_CHECK();
-    if (affine && !jitter_order) {
-        hipLaunchKernelGGL(k_affine_norm, grid, dim3(256), 0, st, mosaic, out, Hout, Wout, affine, f0, f1, f2, flips, mean3[0], mean3[1], mean3[2],
-                           std3[0], std3[1], std3[2]);
-        SD_LAUNCH_CHECK();
-        return 0;
-    }
-    if (affine) {
-        hipLaunchKernelGGL(k_affine_u8, grid, dim3(256), 0, st, mosaic, img_a, Hout, Wout, affine, f0, f1, f2);
-        SD_LAUNCH_CHECK();
-    }
-    return jitter_norm(B, Hout, Wout, flips, jitter_order, jitter_factors, mean3, std3, out, img_a, lsum, st);
-}
-
-// the launches after the horizontal pass
-static int preprocess_mosaic_tail(int B, int Hin, int Win, int Hout, int Wout, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips,
-                                  const int* jitter_order, const float* jitter_factors, const double* affine, const int* mosaic_geom,
-                                  const double* mosaic_affine, const uint8_t* fill3, const float* mean3, const float* std3, float* out,
-                                  uint8_t* tmp, hipStream_t st) {
-    uint8_t* img_a = tmp + sd_preprocess_workspace_bytes(B, Hin, Win, Wout);
-    unsigned long long* lsum = reinterpret_cast<unsigned long long*>(img_a + align_up((size_t)B * Hout * Wout * 3, 256));
-    uint8_t* img_b = tmp + sd_preprocess_jitter_workspace_bytes(B, Hin, Win, Hout, Wout);
-    if (int e = resample_v_u8(B, Hin, Hout, Wout, v_bounds, v_kk, v_ksize, tmp, affine ? img_a : img_b, st)) return e;
-    return mosaic_stages(B, Hout, Wout, flips, jitter_order, jitter_factors, affine, mosaic_geom, mosaic_affine, fill3, mean3, std3, out, img_a, img_b,
-                         lsum, st);
-}
-
-int sd_preprocess_images_mosaic(const uint8_t* images, int B, int Hin, int Win, int Hout, int Wout, const int* h_bounds, const int* h_kk,
-                                int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips, const int* jitter_order,
-                                const float* jitter_factors, const double* affine, const int* mosaic_geom, const double* mosaic_affine,
-                                const uint8_t* fill3, const float* mean3, const float* std3, float* out, void* workspace, size_t workspace_bytes,
-                                sd_stream_t stream) {
-    if (int e = preprocess_check("sd_preprocess_images_mosaic", images, B, Hin, Win, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, mean3,
-                                 std3, out, workspace)) return e;
-    if (int e = mosaic_check("sd_preprocess_images_mosaic", B, Hin, Win, Hout, Wout, jitter_order, jitter_factors, mosaic_geom, mosaic_affine, fill3,
-                             workspace_bytes)) return e;
-    hipStream_t st = (hipStream_t)stream;
-    uint8_t* tmp = reinterpret_cast<uint8_t*>(workspace);
-    if (jitter_order) {
-        uint8_t* img = tmp + sd_preprocess_workspace_bytes(B, Hin, Win, Wout);
-        SD_HIP(hipMemsetAsync(img + align_up((size_t)B * Hout * Wout * 3, 256), 0, (size_t)B * 8, st));    // lsum
-    }
-    const int64_t rows = (int64_t)B * Hin;
-    hipLaunchKernelGGL(k_resample_h, dim3(cdiv(rows * Wout, 256)), dim3(256), 0, st, images, tmp, Hin, Win, Wout, h_bounds, h_kk, h_ksize, rows);
-    SD_LAUNCH_CHECK();
-    return preprocess_mosaic_tail(B, Hin, Win, Hout, Wout, v_bounds, v_kk, v_ksize, flips, jitter_order, jitter_factors, affine, mosaic_geom,
-                                  mosaic_affine, fill3, mean3, std3, out, tmp, st);
-}
-
-int sd_preprocess_images_list_mosaic(const uint8_t* const* images, int B, int Hin, int Win, int Hout, int Wout, const int* h_bounds,
-                                     const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips,
-                                     const int* jitter_order, const float* jitter_factors, const double* affine, const int* mosaic_geom,
-                                     const double* mosaic_affine, const uint8_t* fill3, const float* mean3, const float* std3, float* out,
-                                     void* workspace, size_t workspace_bytes, sd_stream_t stream) {
-    int rpb = 0, bpi = 0;
-    if (int e = preprocess_list_check("sd_preprocess_images_list_mosaic", images, B, Hin, Win, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk,
-                                      v_ksize, mean3, std3, out, workspace, &rpb, &bpi)) return e;
-    if (int e = mosaic_check("sd_preprocess_images_list_mosaic", B, Hin, Win, Hout, Wout, jitter_order, jitter_factors, mosaic_geom, mosaic_affine,
-                             fill3, workspace_bytes)) return e;
-    hipStream_t st = (hipStream_t)stream;
-    uint8_t* tmp = reinterpret_cast<uint8_t*>(workspace);
-    if (jitter_order) {
-        uint8_t* img = tmp + sd_preprocess_workspace_bytes(B, Hin, Win, Wout);
-        SD_HIP(hipMemsetAsync(img + align_up((size_t)B * Hout * Wout * 3, 256), 0, (size_t)B * 8, st));    // lsum
-    }
-    if (int e = resample_h_list(images, tmp, B, Hin, Win, Wout, h_bounds, h_kk, h_ksize, rpb, bpi, st)) return e;
-    return preprocess_mosaic_tail(B, Hin, Win, Hout, Wout, v_bounds, v_kk, v_ksize, flips, jitter_order, jitter_factors, affine, mosaic_geom,
-                                  mosaic_affine, fill3, mean3, std3, out, tmp, st);
-}
-
-// ---- Windowed resize in front of every chain above (k_window_h / k_window_h_list, k_window_v_norm / k_window_v_u8) ----
-// workspace: that of the mosaic forms with max_rows in the place of Hin, [horizontal intermediate (B, max_rows, Wout, 3) | 8-bit image A |
-// grey sums | 8-bit image B]: the windowed vertical pass writes the 8-bit window where the stage that follows expects the resized image.
 size_t sd_preprocess_window_workspace_bytes(int B, int max_rows, int Hout, int Wout) {
     return sd_preprocess_mosaic_workspace_bytes(B, max_rows, 0, Hout, Wout);
 }
 
-static int window_check(const char* what, const uint8_t* images, int B, int Hin, int Win, int Hc, int Wc, int Hout, int Wout, const int* h_bounds,
-                        const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const int* window, int max_rows, int max_cols,
-                        const int* jitter_order, const float* jitter_factors, const double* affine, const int* mosaic_geom,
-                        const double* mosaic_affine, const uint8_t* fill3, const float* mean3, const float* std3, float* out, void* workspace,
-                        size_t workspace_bytes) {
-    if (int e = preprocess_check(what, images, B, Hin, Win, Hc, Wc, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, mean3, std3, out, workspace))
-        return e;
-    SD_REQUIRE(window, SD_ERR_INVALID, "%s: null window table", what);
-    SD_REQUIRE(Hout > 0 && Wout > 0 && Hout <= Hc && Wout <= Wc, SD_ERR_INVALID, "%s: a %d x %d window does not fit a %d x %d canvas", what, Wout, Hout,
-               Wc, Hc);
-    SD_REQUIRE(max_rows > 0 && max_rows <= Hin && max_cols > 0 && max_cols <= Win, SD_ERR_INVALID,
-               "%s: max_rows %d / max_cols %d should be in [1, %d] / [1, %d] (the source)", what, max_rows, max_cols, Hin, Win);
-    SD_REQUIRE((jitter_order == nullptr) == (jitter_factors == nullptr), SD_ERR_INVALID,
-               "%s: jitter_order and jitter_factors go together (both null = no jitter)", what);
-    SD_REQUIRE((mosaic_geom == nullptr) == (mosaic_affine == nullptr), SD_ERR_INVALID,
-               "%s: mosaic_geom and mosaic_affine go together (both null = no mosaic)", what);
-    SD_REQUIRE(fill3 || !(affine || mosaic_geom), SD_ERR_INVALID, "%s: a warp or a mosaic needs a fill colour", what);
-    SD_REQUIRE(B <= 65535 || !(jitter_order || affine || mosaic_geom), SD_ERR_INVALID, "%s: batch %d > 65535", what, B);
-    SD_REQUIRE(workspace_bytes >= sd_preprocess_window_workspace_bytes(B, max_rows, Hout, Wout), SD_ERR_WORKSPACE, "%s: workspace %zu < %zu", what,
-               workspace_bytes, sd_preprocess_window_workspace_bytes(B, max_rows, Hout, Wout));
-    return 0;
-}
-
-// the launches after the horizontal pass: the windowed vertical pass, fused with Normalize when no stage follows, else into the 8-bit
-// image the existing tails resample into, and then their launches (jitter_norm, affine_stages, mosaic_stages)
-static int window_tail(int B, int Hc, int Wc, int Hout, int Wout, const int* v_bounds, const int* v_kk, int v_ksize, const int* window, int max_rows,
-                       const uint8_t* flips, const int* jitter_order, const float* jitter_factors, const double* affine, const int* mosaic_geom,
-                       const double* mosaic_affine, const uint8_t* fill3, const float* mean3, const float* std3, float* out, uint8_t* tmp,
-                       hipStream_t st) {
-    const dim3 grid(cdiv((int64_t)B * Hout * Wout, 256));
-    if (!jitter_order && !affine && !mosaic_geom) {
-        hipLaunchKernelGGL(k_window_v_norm, grid, dim3(256), 0, st, tmp, out, Hc, Wc, Hout, Wout, v_bounds, v_kk, v_ksize, window, max_rows, flips,
-                           mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], B);
-        SD_LAUNCH_CHECK();
-        return 0;
-    }
-    uint8_t* img_a = tmp + sd_preprocess_workspace_bytes(B, max_rows, 0, Wout);
-    unsigned long long* lsum = reinterpret_cast<unsigned long long*>(img_a + align_up((size_t)B * Hout * Wout * 3, 256));
-    uint8_t* img_b = tmp + sd_preprocess_jitter_workspace_bytes(B, max_rows, 0, Hout, Wout);
-    uint8_t* resized = (mosaic_geom != nullptr) == (affine != nullptr) ? img_a : img_b;    // jitter reads A, the warp B, the mosaic A with a warp, else B
-    hipLaunchKernelGGL(k_window_v_u8, grid, dim3(256), 0, st, tmp, resized, Hc, Wc, Hout, Wout, v_bounds, v_kk, v_ksize, window, max_rows, B);
-    SD_LAUNCH_CHECK();
-    if (mosaic_geom)
-        return mosaic_stages(B, Hout, Wout, flips, jitter_order, jitter_factors, affine, mosaic_geom, mosaic_affine, fill3, mean3, std3, out, img_a,
-                             img_b, lsum, st);
-    if (affine)
-        return affine_stages(B, Hout, Wout, flips, jitter_order, jitter_factors, affine, fill3, mean3, std3, out, resized, img_a, lsum, st);
-    return jitter_norm(B, Hout, Wout, flips, jitter_order, jitter_factors, mean3, std3, out, img_a, lsum, st);
-}
-
-int sd_preprocess_images_window(const uint8_t* images, int B, int Hin, int Win, int Hc, int Wc, int Hout, int Wout, const int* h_bounds,
-                                const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const int* window, int max_rows,
-                                int max_cols, const uint8_t* flips, const int* jitter_order, const float* jitter_factors, const double* affine,
-                                const int* mosaic_geom, const double* mosaic_affine, const uint8_t* fill3, const float* mean3, const float* std3,
-                                float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
-    if (int e = window_check("sd_preprocess_images_window", images, B, Hin, Win, Hc, Wc, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
-                             window, max_rows, max_cols, jitter_order, jitter_factors, affine, mosaic_geom, mosaic_affine, fill3, mean3, std3, out,
-                             workspace, workspace_bytes)) return e;
-    hipStream_t st = (hipStream_t)stream;
-    uint8_t* tmp = reinterpret_cast<uint8_t*>(workspace);
-    if (jitter_order) {
-        uint8_t* img = tmp + sd_preprocess_workspace_bytes(B, max_rows, 0, Wout);
-        SD_HIP(hipMemsetAsync(img + align_up((size_t)B * Hout * Wout * 3, 256), 0, (size_t)B * 8, st));    // lsum
-    }
-    hipLaunchKernelGGL(k_window_h, dim3(cdiv((int64_t)B * max_rows * Wout, 256)), dim3(256), 0, st, images, tmp, Hin, Win, Hc, Wc, Hout, Wout, h_bounds,
-                       h_kk, h_ksize, v_bounds, window, max_rows, B);
-    SD_LAUNCH_CHECK();
-    return window_tail(B, Hc, Wc, Hout, Wout, v_bounds, v_kk, v_ksize, window, max_rows, flips, jitter_order, jitter_factors, affine, mosaic_geom,
-                       mosaic_affine, fill3, mean3, std3, out, tmp, st);
-}
-
-int sd_preprocess_images_list_window(const uint8_t* const* images, int B, int Hin, int Win, int Hc, int Wc, int Hout, int Wout, const int* h_bounds,
-                                     const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const int* window,
-                                     int max_rows, int max_cols, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
-                                     const double* affine, const int* mosaic_geom, const double* mosaic_affine, const uint8_t* fill3,
-                                     const float* mean3, const float* std3, float* out, void* workspace, size_t workspace_bytes,
-                                     sd_stream_t stream) {
-    const char* what = "sd_preprocess_images_list_window";
-    if (int e = window_check(what, reinterpret_cast<const uint8_t*>(images), B, Hin, Win, Hc, Wc, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk,
-                             v_ksize, window, max_rows, max_cols, jitter_order, jitter_factors, affine, mosaic_geom, mosaic_affine, fill3, mean3, std3,
-                             out, workspace, workspace_bytes)) return e;
-    SD_REQUIRE((int64_t)max_cols * 3 + 32 <= HL_LDS_BYTES, SD_ERR_INVALID,
-               "%s: a column span of %d source pixels exceeds the LDS staging buffer (at most %d)", what, max_cols, (HL_LDS_BYTES - 32) / 3);
-    const int rpb = (int)std::min<int64_t>(HL_ROWS, (HL_LDS_BYTES - 32) / ((int64_t)max_cols * 3));
-    const int bpi = cdiv(max_rows, rpb);
-    SD_REQUIRE((int64_t)B * bpi < (1ll << 31), SD_ERR_INVALID, "%s: batch too large", what);
-    hipStream_t st = (hipStream_t)stream;
-    uint8_t* tmp = reinterpret_cast<uint8_t*>(workspace);
-    if (jitter_order) {
-        uint8_t* img = tmp + sd_preprocess_workspace_bytes(B, max_rows, 0, Wout);
-        SD_HIP(hipMemsetAsync(img + align_up((size_t)B * Hout * Wout * 3, 256), 0, (size_t)B * 8, st));    // lsum
-    }
-    hipLaunchKernelGGL(k_window_h_list, dim3((unsigned)((int64_t)B * bpi)), dim3(256), (size_t)rpb * max_cols * 3 + 32, st, images, tmp, Win, Hc, Wc,
-                       Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, window, max_rows, max_cols, rpb, bpi);
-    SD_LAUNCH_CHECK();
-    return window_tail(B, Hc, Wc, Hout, Wout, v_bounds, v_kk, v_ksize, window, max_rows, flips, jitter_order, jitter_factors, affine, mosaic_geom,
-                       mosaic_affine, fill3, mean3, std3, out, tmp, st);
-}
-
-// ---- Letterbox in front of every chain above (k_resample_h / k_resample_h_list at Wout = Wi, k_letterbox_v_norm / k_letterbox_v_u8) ----
-// workspace: [horizontal intermediate (B, Hin, Wi, 3) | 8-bit frame A | grey sums | 8-bit frame B], the layout of the mosaic forms with
-// the intermediate at the inner width and the 8-bit images at the frame's size.
 size_t sd_preprocess_letterbox_workspace_bytes(int B, int Hin, int Wi, int Hout, int Wout) {
     return align_up((size_t)B * Hin * Wi * 3, 256) + 2 * align_up((size_t)B * Hout * Wout * 3, 256) + align_up((size_t)B * 8, 256);
 }
 
-static int letterbox_check(const char* what, const uint8_t* images, int B, int Hin, int Win, int Hi, int Wi, int Hout, int Wout, int y0, int x0,
-                           const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize,
-                           const int* jitter_order, const float* jitter_factors, const double* affine, const int* mosaic_geom,
-                           const double* mosaic_affine, const uint8_t* fill3, const float* mean3, const float* std3, float* out, void* workspace,
-                           size_t workspace_bytes) {
-    if (int e = preprocess_check(what, images, B, Hin, Win, Hi, Wi, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, mean3, std3, out, workspace))
-        return e;
-    SD_REQUIRE(fill3, SD_ERR_INVALID, "%s: null fill colour", what);
-    SD_REQUIRE(Hout > 0 && Wout > 0 && (int64_t)B * Hout * Wout * 3 < (1ll << 40), SD_ERR_INVALID, "%s: bad frame %d x %d", what, Wout, Hout);
-    SD_REQUIRE(x0 >= 0 && y0 >= 0 && (int64_t)x0 + Wi <= Wout && (int64_t)y0 + Hi <= Hout, SD_ERR_INVALID,
-               "%s: a %d x %d image at (%d, %d) does not lie inside the %d x %d frame", what, Wi, Hi, x0, y0, Wout, Hout);
-    SD_REQUIRE((jitter_order == nullptr) == (jitter_factors == nullptr), SD_ERR_INVALID,
-               "%s: jitter_order and jitter_factors go together (both null = no jitter)", what);
-    SD_REQUIRE((mosaic_geom == nullptr) == (mosaic_affine == nullptr), SD_ERR_INVALID,
-               "%s: mosaic_geom and mosaic_affine go together (both null = no mosaic)", what);
-    SD_REQUIRE(B <= 65535 || !(jitter_order || affine || mosaic_geom), SD_ERR_INVALID, "%s: batch %d > 65535", what, B);
-    SD_REQUIRE(workspace_bytes >= sd_preprocess_letterbox_workspace_bytes(B, Hin, Wi, Hout, Wout), SD_ERR_WORKSPACE, "%s: workspace %zu < %zu", what,
-               workspace_bytes, sd_preprocess_letterbox_workspace_bytes(B, Hin, Wi, Hout, Wout));
-    return 0;
-}
-
-// the launches after the horizontal pass: the letterbox vertical pass, fused with Normalize when no stage follows, else into the 8-bit
-// frame the existing tails resample into, and then their launches (jitter_norm, affine_stages, mosaic_stages) at the frame's size
-static int letterbox_tail(int B, int Hin, int Hi, int Wi, int Hout, int Wout, int y0, int x0, const int* v_bounds, const int* v_kk, int v_ksize,
-                          const uint8_t* flips, const int* jitter_order, const float* jitter_factors, const double* affine, const int* mosaic_geom,
-                          const double* mosaic_affine, const uint8_t* fill3, const float* mean3, const float* std3, float* out, uint8_t* tmp,
-                          hipStream_t st) {
-    const dim3 grid(cdiv((int64_t)B * Hout * Wout, 256));
-    const int f0 = fill3[0], f1 = fill3[1], f2 = fill3[2];
-    if (!jitter_order && !affine && !mosaic_geom) {
-        hipLaunchKernelGGL(k_letterbox_v_norm, grid, dim3(256), 0, st, tmp, out, Hin, Hi, Wi, Hout, Wout, y0, x0, v_bounds, v_kk, v_ksize, flips, f0,
-                           f1, f2, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], B);
-        SD_LAUNCH_CHECK();
-        return 0;
-    }
-    const size_t frame = align_up((size_t)B * Hout * Wout * 3, 256);
-    uint8_t* img_a = tmp + align_up((size_t)B * Hin * Wi * 3, 256);
-    unsigned long long* lsum = reinterpret_cast<unsigned long long*>(img_a + frame);
-    uint8_t* img_b = img_a + frame + align_up((size_t)B * 8, 256);
-    uint8_t* framed = (mosaic_geom != nullptr) == (affine != nullptr) ? img_a : img_b;     // jitter reads A, the warp B, the mosaic A with a warp, else B
-    hipLaunchKernelGGL(k_letterbox_v_u8, grid, dim3(256), 0, st, tmp, framed, Hin, Hi, Wi, Hout, Wout, y0, x0, v_bounds, v_kk, v_ksize, f0, f1, f2, B);
-    SD_LAUNCH_CHECK();
-    if (mosaic_geom)
-        return mosaic_stages(B, Hout, Wout, flips, jitter_order, jitter_factors, affine, mosaic_geom, mosaic_affine, fill3, mean3, std3, out, img_a,
-                             img_b, lsum, st);
-    if (affine)
-        return affine_stages(B, Hout, Wout, flips, jitter_order, jitter_factors, affine, fill3, mean3, std3, out, framed, img_a, lsum, st);
-    return jitter_norm(B, Hout, Wout, flips, jitter_order, jitter_factors, mean3, std3, out, img_a, lsum, st);
-}
-
-static int letterbox_zero_lsum(int B, int Hin, int Wi, int Hout, int Wout, uint8_t* tmp, hipStream_t st) {
-    uint8_t* lsum = tmp + align_up((size_t)B * Hin * Wi * 3, 256) + align_up((size_t)B * Hout * Wout * 3, 256);
-    SD_HIP(hipMemsetAsync(lsum, 0, (size_t)B * 8, st));
-    return 0;
-}
-
-int sd_preprocess_images_letterbox(const uint8_t* images, int B, int Hin, int Win, int Hi, int Wi, int Hout, int Wout, int y0, int x0,
-                                   const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize,
-                                   const uint8_t* flips, const int* jitter_order, const float* jitter_factors, const double* affine,
-                                   const int* mosaic_geom, const double* mosaic_affine, const uint8_t* fill3, const float* mean3, const float* std3,
-                                   float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
-    if (int e = letterbox_check("sd_preprocess_images_letterbox", images, B, Hin, Win, Hi, Wi, Hout, Wout, y0, x0, h_bounds, h_kk, h_ksize, v_bounds,
-                                v_kk, v_ksize, jitter_order, jitter_factors, affine, mosaic_geom, mosaic_affine, fill3, mean3, std3, out, workspace,
-                                workspace_bytes)) return e;
-    hipStream_t st = (hipStream_t)stream;
-    uint8_t* tmp = reinterpret_cast<uint8_t*>(workspace);
-    if (jitter_order)
-        if (int e = letterbox_zero_lsum(B, Hin, Wi, Hout, Wout, tmp, st)) return e;
-    const int64_t rows = (int64_t)B * Hin;
-    hipLaunchKernelGGL(k_resample_h, dim3(cdiv(rows * Wi, 256)), dim3(256), 0, st, images, tmp, Hin, Win, Wi, h_bounds, h_kk, h_ksize, rows);
-    SD_LAUNCH_CHECK();
-    return letterbox_tail(B, Hin, Hi, Wi, Hout, Wout, y0, x0, v_bounds, v_kk, v_ksize, flips, jitter_order, jitter_factors, affine, mosaic_geom,
-                          mosaic_affine, fill3, mean3, std3, out, tmp, st);
-}
-
-int sd_preprocess_images_list_letterbox(const uint8_t* const* images, int B, int Hin, int Win, int Hi, int Wi, int Hout, int Wout, int y0, int x0,
-                                        const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize,
-                                        const uint8_t* flips, const int* jitter_order, const float* jitter_factors, const double* affine,
-                                        const int* mosaic_geom, const double* mosaic_affine, const uint8_t* fill3, const float* mean3,
-                                        const float* std3, float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
-    const char* what = "sd_preprocess_images_list_letterbox";
-    if (int e = letterbox_check(what, reinterpret_cast<const uint8_t*>(images), B, Hin, Win, Hi, Wi, Hout, Wout, y0, x0, h_bounds, h_kk, h_ksize,
-                                v_bounds, v_kk, v_ksize, jitter_order, jitter_factors, affine, mosaic_geom, mosaic_affine, fill3, mean3, std3, out,
-                                workspace, workspace_bytes)) return e;
-    SD_REQUIRE((int64_t)Win * 3 + 32 <= HL_LDS_BYTES, SD_ERR_INVALID, "%s: source rows of %d pixels exceed the LDS staging buffer (at most %d)",
-               what, Win, (HL_LDS_BYTES - 32) / 3);
-    const int rpb = (int)std::min<int64_t>(HL_ROWS, (HL_LDS_BYTES - 32) / ((int64_t)Win * 3));
-    const int bpi = cdiv(Hin, rpb);
-    SD_REQUIRE((int64_t)B * bpi < (1ll << 31), SD_ERR_INVALID, "%s: batch too large", what);
-    hipStream_t st = (hipStream_t)stream;
-    uint8_t* tmp = reinterpret_cast<uint8_t*>(workspace);
-    if (jitter_order)
-        if (int e = letterbox_zero_lsum(B, Hin, Wi, Hout, Wout, tmp, st)) return e;
-    if (int e = resample_h_list(images, tmp, B, Hin, Win, Wi, h_bounds, h_kk, h_ksize, rpb, bpi, st)) return e;
-    return letterbox_tail(B, Hin, Hi, Wi, Hout, Wout, y0, x0, v_bounds, v_kk, v_ksize, flips, jitter_order, jitter_factors, affine, mosaic_geom,
-                          mosaic_affine, fill3, mean3, std3, out, tmp, st);
-}
-
-// ---- Gaussian blur between the warp and the jitter, behind any geometry (sd_blur.hip: blur_stage; k_u8_norm) ----
-// workspace: [horizontal intermediate | 8-bit image A | grey sums | 8-bit image B] with the intermediate of the geometry, i.e. the layout of
-// the mosaic, window and letterbox forms.  The 8-bit stages in front of the blur -- vertical pass [, mosaic] [, warp] -- alternate between
-// A and B so that the last of them writes A: the blur's horizontal direction then writes B and its vertical direction A, where the jitter
-// launches (and k_u8_norm) read.  No stage runs in place.
 size_t sd_preprocess_blur_workspace_bytes(int geometry, int B, int Hin, int Win, int Wg, int Hout, int Wout, int g0) {
     if (geometry == SD_GEOM_WINDOW) return sd_preprocess_window_workspace_bytes(B, g0, Hout, Wout);
     if (geometry == SD_GEOM_LETTERBOX) return sd_preprocess_letterbox_workspace_bytes(B, Hin, Wg, Hout, Wout);
     return sd_preprocess_mosaic_workspace_bytes(B, Hin, Win, Hout, Wout);
 }
 
-// the blur and perspective forms proper (blur or persp set): the checks of the geometry's entry point, its horizontal pass, its vertical
-// pass into an 8-bit image, the 8-bit stages -- the warp slot is k_affine_u8 or k_persp_u8 --, the blur unless its table is null, the sensor
-// noise unless its table is null (sd_noise.hip: noise_stage, on image A in place, no workspace), the JPEG
-// round trip unless its table is null (sd_jpeg.hip: jpeg_stage, on image A in place; its planes lie behind image B), the tone stage unless
-// its table is null (sd_tone.hip: tone_stage, on image A in place; its histograms and tables lie behind the planes), and the jitter or
-// plain tail
-static int preprocess_blur(const char* what, bool list, const void* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout,
-                           int g0, int g1, const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize,
-                           const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors, const double* affine,
-                           const double* persp, const int* mosaic_geom, const double* mosaic_affine, const int* blur, const int* jpeg,
-                           const int* tone, const int* noise, const uint8_t* fill3, const float* mean3, const float* std3, float* out,
-                           void* workspace, size_t workspace_bytes, hipStream_t st) {
-    const double* warp = affine ? affine : persp;                        // one warp slot: the callers refuse both together
-    const uint8_t* packed = reinterpret_cast<const uint8_t*>(images);
-    const uint8_t* const* table = reinterpret_cast<const uint8_t* const*>(images);
-    int rpb = 0, bpi = 0;
-    size_t tmp_bytes = 0;
-    if (geometry == SD_GEOM_STRETCH) {
-        if (list) {
-            if (int e = preprocess_list_check(what, table, B, Hin, Win, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, mean3, std3, out,
-                                              workspace, &rpb, &bpi)) return e;
-        } else if (int e = preprocess_check(what, packed, B, Hin, Win, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, mean3, std3, out,
-                                            workspace)) return e;
-        SD_REQUIRE(!window, SD_ERR_INVALID, "%s: a window table needs SD_GEOM_WINDOW", what);
-        SD_REQUIRE((jitter_order == nullptr) == (jitter_factors == nullptr), SD_ERR_INVALID,
-                   "%s: jitter_order and jitter_factors go together (both null = no jitter)", what);
-        SD_REQUIRE((mosaic_geom == nullptr) == (mosaic_affine == nullptr), SD_ERR_INVALID,
-                   "%s: mosaic_geom and mosaic_affine go together (both null = no mosaic)", what);
-        SD_REQUIRE(fill3 || !(warp || mosaic_geom), SD_ERR_INVALID, "%s: a warp or a mosaic needs a fill colour", what);
-        SD_REQUIRE(workspace_bytes >= sd_preprocess_mosaic_workspace_bytes(B, Hin, Win, Hout, Wout), SD_ERR_WORKSPACE, "%s: workspace %zu < %zu", what,
-                   workspace_bytes, sd_preprocess_mosaic_workspace_bytes(B, Hin, Win, Hout, Wout));
-        tmp_bytes = sd_preprocess_workspace_bytes(B, Hin, Win, Wout);
-    } else if (geometry == SD_GEOM_WINDOW) {
-        if (int e = window_check(what, packed, B, Hin, Win, Hg, Wg, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, window, g0, g1,
-                                 jitter_order, jitter_factors, warp, mosaic_geom, mosaic_affine, fill3, mean3, std3, out, workspace, workspace_bytes))
-            return e;
-        if (list) {
-            SD_REQUIRE((int64_t)g1 * 3 + 32 <= HL_LDS_BYTES, SD_ERR_INVALID,
-                       "%s: a column span of %d source pixels exceeds the LDS staging buffer (at most %d)", what, g1, (HL_LDS_BYTES - 32) / 3);
-            rpb = (int)std::min<int64_t>(HL_ROWS, (HL_LDS_BYTES - 32) / ((int64_t)g1 * 3));
-            bpi = cdiv(g0, rpb);
-            SD_REQUIRE((int64_t)B * bpi < (1ll << 31), SD_ERR_INVALID, "%s: batch too large", what);
-        }
-        tmp_bytes = sd_preprocess_workspace_bytes(B, g0, 0, Wout);
-    } else if (geometry == SD_GEOM_LETTERBOX) {
-        SD_REQUIRE(!window, SD_ERR_INVALID, "%s: a window table needs SD_GEOM_WINDOW", what);
-        if (int e = letterbox_check(what, packed, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, jitter_order,
-                                    jitter_factors, warp, mosaic_geom, mosaic_affine, fill3, mean3, std3, out, workspace, workspace_bytes)) return e;
-        if (list) {
-            SD_REQUIRE((int64_t)Win * 3 + 32 <= HL_LDS_BYTES, SD_ERR_INVALID, "%s: source rows of %d pixels exceed the LDS staging buffer (at most %d)",
-                       what, Win, (HL_LDS_BYTES - 32) / 3);
-            rpb = (int)std::min<int64_t>(HL_ROWS, (HL_LDS_BYTES - 32) / ((int64_t)Win * 3));
-            bpi = cdiv(Hin, rpb);
-            SD_REQUIRE((int64_t)B * bpi < (1ll << 31), SD_ERR_INVALID, "%s: batch too large", what);
-        }
-        tmp_bytes = align_up((size_t)B * Hin * Wg * 3, 256);
-    } else {
-        SD_REQUIRE(false, SD_ERR_INVALID, "%s: unknown geometry %d", what, geometry);
+size_t sd_preprocess_jpeg_workspace_bytes(int geometry, int B, int Hin, int Win, int Wg, int Hout, int Wout, int g0) {
+    if (B <= 0 || Hout <= 0 || Wout <= 0) return sd_preprocess_blur_workspace_bytes(geometry, B, Hin, Win, Wg, Hout, Wout, g0);
+    return sd_preprocess_blur_workspace_bytes(geometry, B, Hin, Win, Wg, Hout, Wout, g0) + jpeg_planes_bytes(B, Hout, Wout);
+}
+
+size_t sd_preprocess_tone_workspace_bytes(int geometry, int B, int Hin, int Win, int Wg, int Hout, int Wout, int g0) {
+    if (B <= 0 || Hout <= 0 || Wout <= 0) return sd_preprocess_jpeg_workspace_bytes(geometry, B, Hin, Win, Wg, Hout, Wout, g0);
+    return sd_preprocess_jpeg_workspace_bytes(geometry, B, Hin, Win, Wg, Hout, Wout, g0) + tone_workspace_bytes(B);
+}
+
+size_t sd_preprocess_noise_workspace_bytes(int geometry, int B, int Hin, int Win, int Wg, int Hout, int Wout, int g0) {
+    return sd_preprocess_tone_workspace_bytes(geometry, B, Hin, Win, Wg, Hout, Wout, g0);
+}
+
+// ---- the preprocess chain: one descriptor (sd_preprocess_desc), one plan, one launcher ----------------------------------------------
+//     H (horizontal resize) -> V (vertical resize [+ window | letterbox paste]) -> [mosaic] -> [affine | persp] -> [blur] -> [noise]
+//     -> [jpeg] -> [tone] -> [jitter] -> flips -> Normalize
+// plan_chain is host arithmetic only: the checks, the list form's LDS staging, the workspace layout and the launches with their buffers.
+// sd_preprocess_chain and every legacy entry point run it under their own name and walk it (launch_chain); sd_preprocess_kernel_names
+// prints it; sd_preprocess_chain_workspace_bytes is its ws_bytes.
+//
+// workspace: [horizontal intermediate (tmp) | 8-bit image A | grey sums | 8-bit image B | JPEG planes | tone histograms], every region a
+// multiple of 256 bytes.  The plain stretch needs tmp only and the stretch with jitter alone up to the grey sums; every other plan
+// reserves up to B's end (the window and letterbox forms always did), the planes with jpeg, the histograms -- behind the planes' place,
+// set or not -- with tone.
+//
+// The A/B rule: the 8-bit stages in front of the blur -- V [, mosaic] [, warp] -- alternate between A and B so that the last of them
+// writes A, where the blur (A -> B -> A), the in-place stages, the jitter and k_u8_norm read.  Without a late stage (persp, blur, noise,
+// jpeg, tone) and without jitter that last stage is its kernel fused with flips + Normalize (`_norm`) and writes `out` instead.
+enum ChainOp { OP_MEMSET, OP_H, OP_V, OP_MOSAIC, OP_AFFINE, OP_PERSP, OP_BLUR, OP_NOISE, OP_JPEG, OP_TONE, OP_LSUM, OP_JITTER_NORM, OP_U8_NORM };
+enum ChainBuf { BUF_TMP, BUF_A, BUF_B, BUF_OUT, BUF_SUMS };
+struct ChainStep { ChainOp op; ChainBuf src, dst; };                     // dst == BUF_OUT on V / MOSAIC / AFFINE: the `_norm` kernel, else `_u8`
+struct ChainPlan {
+    ChainStep steps[12];
+    int n;
+    int rows, cols;              // the horizontal intermediate is (B, rows, cols, 3)
+    int span, rpb, bpi;          // list form: source pixels staged per row, source rows per block, blocks per image
+    size_t a_at, sums_at, b_at, planes_at, tone_at, ws_bytes;
+};
+struct ChainDims { dim3 grid; size_t lds; };                             // every block has 256 threads; lds: dynamic bytes
+
+static int plan_chain(const sd_preprocess_desc* desc, const char* what, ChainPlan* p) {
+    SD_REQUIRE(desc, SD_ERR_INVALID, "%s: null descriptor", what);
+    const sd_preprocess_desc& d = *desc;
+    SD_REQUIRE(d.images && d.out && d.h_bounds && d.h_kk && d.v_bounds && d.v_kk && d.mean3 && d.std3, SD_ERR_INVALID, "%s: null pointer", what);
+    SD_REQUIRE(d.geometry == SD_GEOM_STRETCH || d.geometry == SD_GEOM_WINDOW || d.geometry == SD_GEOM_LETTERBOX, SD_ERR_INVALID,
+               "%s: unknown geometry %d", what, d.geometry);
+    const bool window = d.geometry == SD_GEOM_WINDOW, letterbox = d.geometry == SD_GEOM_LETTERBOX;
+    const int B = d.B, Hin = d.Hin, Win = d.Win, Hout = d.Hout, Wout = d.Wout;
+    const int Ht = window || letterbox ? d.Hg : Hout, Wt = window || letterbox ? d.Wg : Wout;    // the resize target of the tables
+    SD_REQUIRE(B > 0 && Hin > 0 && Win > 0 && Ht > 0 && Wt > 0 && d.h_ksize > 0 && d.v_ksize > 0, SD_ERR_INVALID, "%s: bad shape", what);
+    SD_REQUIRE((int64_t)B * std::max(Hin, Ht) * std::max(Win, Wt) * 3 < (1ll << 40), SD_ERR_INVALID, "%s: batch too large", what);
+    SD_REQUIRE(d.std3[0] != 0.f && d.std3[1] != 0.f && d.std3[2] != 0.f, SD_ERR_INVALID, "%s: zero std", what);
+    SD_REQUIRE(window || !d.window, SD_ERR_INVALID, "%s: a window table needs SD_GEOM_WINDOW", what);
+    if (window) {                                                        // (Hg, Wg) = the canvas, g0 / g1 = max_rows / max_cols
+        SD_REQUIRE(d.window, SD_ERR_INVALID, "%s: null window table", what);
+        SD_REQUIRE(Hout > 0 && Wout > 0 && Hout <= d.Hg && Wout <= d.Wg, SD_ERR_INVALID, "%s: a %d x %d window does not fit a %d x %d canvas", what,
+                   Wout, Hout, d.Wg, d.Hg);
+        SD_REQUIRE(d.g0 > 0 && d.g0 <= Hin && d.g1 > 0 && d.g1 <= Win, SD_ERR_INVALID,
+                   "%s: max_rows %d / max_cols %d should be in [1, %d] / [1, %d] (the source)", what, d.g0, d.g1, Hin, Win);
     }
-    SD_REQUIRE(B <= 65535 && Hout <= 65535 * 64, SD_ERR_INVALID, "%s: batch %d > 65535 or frame too tall", what, B);
-    const size_t planes_at = sd_preprocess_blur_workspace_bytes(geometry, B, Hin, Win, Wg, Hout, Wout, g0);   // a multiple of 256
-    if (jpeg) {
-        SD_REQUIRE(Hout % 16 == 0 && Wout % 16 == 0, SD_ERR_INVALID, "%s: jpeg needs a frame of whole 16 x 16 MCUs, not %d x %d", what, Wout, Hout);
-        SD_REQUIRE(aligned16(workspace), SD_ERR_INVALID, "%s: jpeg needs a 16-byte aligned workspace", what);
-        SD_REQUIRE(workspace_bytes >= planes_at + jpeg_planes_bytes(B, Hout, Wout), SD_ERR_WORKSPACE, "%s: workspace %zu < %zu", what, workspace_bytes,
-                   planes_at + jpeg_planes_bytes(B, Hout, Wout));
+    if (letterbox) {                                                     // (Hg, Wg) = the inner image, g0 / g1 = y0 / x0
+        SD_REQUIRE(d.fill3, SD_ERR_INVALID, "%s: null fill colour", what);
+        SD_REQUIRE(Hout > 0 && Wout > 0 && (int64_t)B * Hout * Wout * 3 < (1ll << 40), SD_ERR_INVALID, "%s: bad frame %d x %d", what, Wout, Hout);
+        SD_REQUIRE(d.g1 >= 0 && d.g0 >= 0 && (int64_t)d.g1 + d.Wg <= Wout && (int64_t)d.g0 + d.Hg <= Hout, SD_ERR_INVALID,
+                   "%s: a %d x %d image at (%d, %d) does not lie inside the %d x %d frame", what, d.Wg, d.Hg, d.g1, d.g0, Wout, Hout);
     }
-    const size_t tone_at = planes_at + jpeg_planes_bytes(B, Hout, Wout);                                      // a multiple of 256
-    if (tone) {
-        SD_REQUIRE((int64_t)Hout * Wout < (1ll << 31), SD_ERR_INVALID, "%s: tone needs a frame of fewer than 2^31 pixels, not %d x %d", what, Wout, Hout);
-        SD_REQUIRE(aligned16(workspace), SD_ERR_INVALID, "%s: tone needs a 16-byte aligned workspace", what);
-        SD_REQUIRE(workspace_bytes >= tone_at + tone_workspace_bytes(B), SD_ERR_WORKSPACE, "%s: workspace %zu < %zu", what, workspace_bytes,
-                   tone_at + tone_workspace_bytes(B));
+    SD_REQUIRE(!(d.affine && d.persp), SD_ERR_INVALID, "%s: persp and affine do not combine (fold the affine matrix into the homography)", what);
+    SD_REQUIRE((d.jitter_order == nullptr) == (d.jitter_factors == nullptr), SD_ERR_INVALID,
+               "%s: jitter_order and jitter_factors go together (both null = no jitter)", what);
+    SD_REQUIRE((d.mosaic_geom == nullptr) == (d.mosaic_affine == nullptr), SD_ERR_INVALID,
+               "%s: mosaic_geom and mosaic_affine go together (both null = no mosaic)", what);
+    const bool jitter = d.jitter_order, mosaic = d.mosaic_geom, warp = d.affine || d.persp;
+    const bool late = d.persp || d.blur || d.noise || d.jpeg || d.tone;
+    SD_REQUIRE(d.fill3 || !(warp || mosaic), SD_ERR_INVALID, "%s: a warp or a mosaic needs a fill colour", what);
+    // B is a grid dimension of the jitter, warp, mosaic and late launches (the late ones also take cdiv(Hout, 64)); the resize has flat grids
+    SD_REQUIRE(B <= 65535 || !(jitter || warp || mosaic || late), SD_ERR_INVALID, "%s: batch %d > 65535", what, B);
+    SD_REQUIRE(Hout <= 65535 * 64 || !late, SD_ERR_INVALID, "%s: a frame of %d rows is too tall", what, Hout);
+    SD_REQUIRE((int64_t)Hout * Wout < (1ll << 31) || !(d.noise || d.tone), SD_ERR_INVALID,
+               "%s: noise and tone need a frame of fewer than 2^31 pixels, not %d x %d", what, Wout, Hout);
+    SD_REQUIRE(!d.jpeg || (Hout % 16 == 0 && Wout % 16 == 0), SD_ERR_INVALID, "%s: jpeg needs a frame of whole 16 x 16 MCUs, not %d x %d", what, Wout,
+               Hout);
+
+    p->rows = window ? d.g0 : Hin;
+    p->cols = letterbox ? d.Wg : Wout;
+    p->span = window ? d.g1 : Win;
+    p->rpb = p->bpi = 0;
+    if (d.list) {                                                        // a block stages rpb rows of span source pixels in LDS
+        SD_REQUIRE((int64_t)p->span * 3 + 32 <= HL_LDS_BYTES, SD_ERR_INVALID,
+                   "%s: source rows (or a window's column span) of %d pixels exceed the LDS staging buffer (at most %d)", what, p->span,
+                   (HL_LDS_BYTES - 32) / 3);
+        p->rpb = (int)std::min<int64_t>(HL_ROWS, (HL_LDS_BYTES - 32) / ((int64_t)p->span * 3));
+        p->bpi = cdiv(p->rows, p->rpb);
+        SD_REQUIRE((int64_t)B * p->bpi < (1ll << 31), SD_ERR_INVALID, "%s: batch too large", what);
     }
 
-    if (noise)
-        SD_REQUIRE((int64_t)Hout * Wout < (1ll << 31), SD_ERR_INVALID, "%s: noise needs a frame of fewer than 2^31 pixels, not %d x %d", what, Wout, Hout);
-
-    uint8_t* tmp = reinterpret_cast<uint8_t*>(workspace);
+    const int stages = 1 + (mosaic ? 1 : 0) + (warp ? 1 : 0);            // 8-bit images written in front of the blur
+    const bool fuse = !late && !jitter;
     const size_t frame = align_up((size_t)B * Hout * Wout * 3, 256);
-    uint8_t* img_a = tmp + tmp_bytes;
-    unsigned long long* lsum = reinterpret_cast<unsigned long long*>(img_a + frame);
-    uint8_t* img_b = img_a + frame + align_up((size_t)B * 8, 256);
-    if (jitter_order) SD_HIP(hipMemsetAsync(lsum, 0, (size_t)B * 8, st));
-    const int before = 1 + (mosaic_geom ? 1 : 0) + (warp ? 1 : 0);       // 8-bit images written in front of the blur; the last one is A
-    int k = 0;
-    auto next = [&]() { return ((before - 1 - k++) & 1) ? img_b : img_a; };
-    uint8_t* cur = next();
-    const dim3 flat(cdiv((int64_t)B * Hout * Wout, 256));
-    const int f0 = fill3 ? fill3[0] : 0, f1 = fill3 ? fill3[1] : 0, f2 = fill3 ? fill3[2] : 0;
-    if (geometry == SD_GEOM_STRETCH) {
-        if (list) {
-            if (int e = resample_h_list(table, tmp, B, Hin, Win, Wout, h_bounds, h_kk, h_ksize, rpb, bpi, st)) return e;
-        } else {
-            const int64_t rows = (int64_t)B * Hin;
-            hipLaunchKernelGGL(k_resample_h, dim3(cdiv(rows * Wout, 256)), dim3(256), 0, st, packed, tmp, Hin, Win, Wout, h_bounds, h_kk, h_ksize, rows);
-            SD_LAUNCH_CHECK();
-        }
-        if (int e = resample_v_u8(B, Hin, Hout, Wout, v_bounds, v_kk, v_ksize, tmp, cur, st)) return e;
-    } else if (geometry == SD_GEOM_WINDOW) {
-        if (list)
-            hipLaunchKernelGGL(k_window_h_list, dim3((unsigned)((int64_t)B * bpi)), dim3(256), (size_t)rpb * g1 * 3 + 32, st, table, tmp, Win, Hg, Wg, Hout,
-                               Wout, h_bounds, h_kk, h_ksize, v_bounds, window, g0, g1, rpb, bpi);
-        else
-            hipLaunchKernelGGL(k_window_h, dim3(cdiv((int64_t)B * g0 * Wout, 256)), dim3(256), 0, st, packed, tmp, Hin, Win, Hg, Wg, Hout, Wout, h_bounds,
-                               h_kk, h_ksize, v_bounds, window, g0, B);
-        SD_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_window_v_u8, flat, dim3(256), 0, st, tmp, cur, Hg, Wg, Hout, Wout, v_bounds, v_kk, v_ksize, window, g0, B);
-        SD_LAUNCH_CHECK();
-    } else {
-        if (list) {
-            if (int e = resample_h_list(table, tmp, B, Hin, Win, Wg, h_bounds, h_kk, h_ksize, rpb, bpi, st)) return e;
-        } else {
-            const int64_t rows = (int64_t)B * Hin;
-            hipLaunchKernelGGL(k_resample_h, dim3(cdiv(rows * Wg, 256)), dim3(256), 0, st, packed, tmp, Hin, Win, Wg, h_bounds, h_kk, h_ksize, rows);
-            SD_LAUNCH_CHECK();
-        }
-        hipLaunchKernelGGL(k_letterbox_v_u8, flat, dim3(256), 0, st, tmp, cur, Hin, Hg, Wg, Hout, Wout, g0, g1, v_bounds, v_kk, v_ksize, f0, f1, f2, B);
-        SD_LAUNCH_CHECK();
-    }
-    const dim3 grid(cdiv(Wout, AF_TX * AF_PX), cdiv(Hout, AF_TY), B);
-    if (mosaic_geom) {
-        uint8_t* dst = next();
-        hipLaunchKernelGGL(k_mosaic_u8, grid, dim3(256), 0, st, cur, dst, Hout, Wout, mosaic_geom, mosaic_affine, f0, f1, f2);
-        SD_LAUNCH_CHECK();
+    p->a_at = align_up((size_t)B * p->rows * p->cols * 3, 256);
+    p->sums_at = p->a_at + frame;
+    p->b_at = p->sums_at + align_up((size_t)B * 8, 256);
+    p->planes_at = p->b_at + frame;
+    p->tone_at = p->planes_at + jpeg_planes_bytes(B, Hout, Wout);
+    const bool tmp_only = d.geometry == SD_GEOM_STRETCH && fuse && stages == 1, to_sums = d.geometry == SD_GEOM_STRETCH && !late && stages == 1;
+    p->ws_bytes = d.tone ? p->tone_at + tone_workspace_bytes(B) : d.jpeg ? p->tone_at : tmp_only ? p->a_at : to_sums ? p->b_at : p->planes_at;
+
+    p->n = 0;
+    auto add = [&](ChainOp op, ChainBuf src, ChainBuf dst) { p->steps[p->n++] = ChainStep{op, src, dst}; };
+    if (jitter) add(OP_MEMSET, BUF_SUMS, BUF_SUMS);
+    add(OP_H, BUF_TMP, BUF_TMP);
+    const ChainOp stage[3] = {OP_V, OP_MOSAIC, d.affine ? OP_AFFINE : OP_PERSP};
+    const bool on[3] = {true, mosaic, warp};
+    ChainBuf cur = BUF_TMP;
+    for (int i = 0, left = stages; i < 3; ++i) {
+        if (!on[i]) continue;
+        --left;                                                          // stages still to come: an even number ends in A from A
+        const ChainBuf dst = fuse && left == 0 ? BUF_OUT : (left & 1) ? BUF_B : BUF_A;
+        add(stage[i], cur, dst);
         cur = dst;
     }
-    if (affine) {
-        uint8_t* dst = next();
-        hipLaunchKernelGGL(k_affine_u8, grid, dim3(256), 0, st, cur, dst, Hout, Wout, affine, f0, f1, f2);
-        SD_LAUNCH_CHECK();
-        cur = dst;
+    if (d.blur) add(OP_BLUR, BUF_A, BUF_A);                              // through B
+    if (d.noise) add(OP_NOISE, BUF_A, BUF_A);
+    if (d.jpeg) add(OP_JPEG, BUF_A, BUF_A);
+    if (d.tone) add(OP_TONE, BUF_A, BUF_A);
+    if (jitter) {
+        add(OP_LSUM, BUF_A, BUF_SUMS);
+        add(OP_JITTER_NORM, BUF_A, BUF_OUT);
+    } else if (late) {
+        add(OP_U8_NORM, BUF_A, BUF_OUT);
     }
-    if (persp) {
-        uint8_t* dst = next();
-        hipLaunchKernelGGL(k_persp_u8, grid, dim3(256), 0, st, cur, dst, Hout, Wout, persp, f0, f1, f2);
-        SD_LAUNCH_CHECK();
-        cur = dst;
-    }
-    if (blur)                                                            // cur == img_a; without a blur the jitter reads it as it is
-        if (int e = blur_stage(cur, img_b, img_a, B, Hout, Wout, blur, st)) return e;
-    if (noise)                                                           // image A in place (with or without a blur the last stage wrote it)
-        if (int e = noise_stage(img_a, img_a, B, Hout, Wout, noise, st)) return e;
-    if (jpeg)                                                            // the last 8-bit image, in place: the second launch reads the planes only
-        if (int e = jpeg_stage(img_a, img_a, tmp + planes_at, B, Hout, Wout, jpeg, st)) return e;
-    if (tone)                                                            // in place as well: every byte is read and written by one thread
-        if (int e = tone_stage(img_a, img_a, tmp + tone_at, B, Hout, Wout, tone, st)) return e;
-    if (jitter_order) return jitter_norm(B, Hout, Wout, flips, jitter_order, jitter_factors, mean3, std3, out, img_a, lsum, st);
-    hipLaunchKernelGGL(k_u8_norm, flat, dim3(256), 0, st, img_a, out, Hout, Wout, flips, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], B);
-    SD_LAUNCH_CHECK();
     return 0;
 }
 
-int sd_preprocess_images_blur(const uint8_t* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout, int g0, int g1,
-                              const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize,
-                              const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
-                              const double* affine, const int* mosaic_geom, const double* mosaic_affine, const int* blur, const uint8_t* fill3,
-                              const float* mean3, const float* std3, float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
-    const char* what = "sd_preprocess_images_blur";
-    if (blur)
-        return preprocess_blur(what, false, images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
-                               window, flips, jitter_order, jitter_factors, affine, nullptr, mosaic_geom, mosaic_affine, blur, nullptr, nullptr, nullptr, fill3, mean3, std3,
-                               out, workspace, workspace_bytes, (hipStream_t)stream);
-    if (geometry == SD_GEOM_WINDOW)
-        return sd_preprocess_images_window(images, B, Hin, Win, Hg, Wg, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, window, g0, g1, flips,
-                                           jitter_order, jitter_factors, affine, mosaic_geom, mosaic_affine, fill3, mean3, std3, out, workspace,
-                                           workspace_bytes, stream);
-    if (geometry == SD_GEOM_LETTERBOX)
-        return sd_preprocess_images_letterbox(images, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, flips,
-                                              jitter_order, jitter_factors, affine, mosaic_geom, mosaic_affine, fill3, mean3, std3, out, workspace,
-                                              workspace_bytes, stream);
-    SD_REQUIRE(geometry == SD_GEOM_STRETCH, SD_ERR_INVALID, "%s: unknown geometry %d", what, geometry);
-    SD_REQUIRE((jitter_order == nullptr) == (jitter_factors == nullptr), SD_ERR_INVALID,
-               "%s: jitter_order and jitter_factors go together (both null = no jitter)", what);
-    if (mosaic_geom || mosaic_affine)
-        return sd_preprocess_images_mosaic(images, B, Hin, Win, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, flips, jitter_order,
-                                           jitter_factors, affine, mosaic_geom, mosaic_affine, fill3, mean3, std3, out, workspace, workspace_bytes, stream);
-    if (affine)
-        return sd_preprocess_images_affine(images, B, Hin, Win, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, flips, jitter_order,
-                                           jitter_factors, affine, fill3, mean3, std3, out, workspace, workspace_bytes, stream);
-    if (jitter_order)
-        return sd_preprocess_images_jitter(images, B, Hin, Win, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, flips, jitter_order,
-                                           jitter_factors, mean3, std3, out, workspace, workspace_bytes, stream);
-    return sd_preprocess_images(images, B, Hin, Win, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, flips, mean3, std3, out, workspace,
-                                workspace_bytes, stream);
+static ChainDims chain_dims(const sd_preprocess_desc& d, const ChainPlan& p, ChainOp op) {
+    const int64_t npix = (int64_t)d.Hout * d.Wout;
+    switch (op) {
+    case OP_H:
+        if (d.list) return {dim3((unsigned)((int64_t)d.B * p.bpi)), (size_t)p.rpb * p.span * 3 + 32};
+        return {dim3(cdiv((int64_t)d.B * p.rows * p.cols, 256)), 0};
+    case OP_MOSAIC: case OP_AFFINE: case OP_PERSP: return {dim3(cdiv(d.Wout, AF_TX * AF_PX), cdiv(d.Hout, AF_TY), d.B), 0};
+    case OP_LSUM: return {dim3(std::min<int64_t>(cdiv(npix, 256), 64), d.B), 0};
+    default: return {dim3(cdiv((int64_t)d.B * npix, 256)), 0};
+    }
 }
 
-int sd_preprocess_images_list_blur(const uint8_t* const* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout,
-                                   int g0, int g1, const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk,
-                                   int v_ksize, const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
-                                   const double* affine, const int* mosaic_geom, const double* mosaic_affine, const int* blur, const uint8_t* fill3,
-                                   const float* mean3, const float* std3, float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
-    const char* what = "sd_preprocess_images_list_blur";
-    if (blur)
-        return preprocess_blur(what, true, images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
-                               window, flips, jitter_order, jitter_factors, affine, nullptr, mosaic_geom, mosaic_affine, blur, nullptr, nullptr, nullptr, fill3, mean3, std3,
-                               out, workspace, workspace_bytes, (hipStream_t)stream);
-    if (geometry == SD_GEOM_WINDOW)
-        return sd_preprocess_images_list_window(images, B, Hin, Win, Hg, Wg, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, window, g0, g1,
-                                                flips, jitter_order, jitter_factors, affine, mosaic_geom, mosaic_affine, fill3, mean3, std3, out, workspace,
-                                                workspace_bytes, stream);
-    if (geometry == SD_GEOM_LETTERBOX)
-        return sd_preprocess_images_list_letterbox(images, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, flips,
-                                                   jitter_order, jitter_factors, affine, mosaic_geom, mosaic_affine, fill3, mean3, std3, out, workspace,
-                                                   workspace_bytes, stream);
-    SD_REQUIRE(geometry == SD_GEOM_STRETCH, SD_ERR_INVALID, "%s: unknown geometry %d", what, geometry);
-    SD_REQUIRE((jitter_order == nullptr) == (jitter_factors == nullptr), SD_ERR_INVALID,
-               "%s: jitter_order and jitter_factors go together (both null = no jitter)", what);
-    if (mosaic_geom || mosaic_affine)
-        return sd_preprocess_images_list_mosaic(images, B, Hin, Win, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, flips, jitter_order,
-                                                jitter_factors, affine, mosaic_geom, mosaic_affine, fill3, mean3, std3, out, workspace, workspace_bytes,
-                                                stream);
-    if (affine)
-        return sd_preprocess_images_list_affine(images, B, Hin, Win, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, flips, jitter_order,
-                                                jitter_factors, affine, fill3, mean3, std3, out, workspace, workspace_bytes, stream);
-    if (jitter_order)
-        return sd_preprocess_images_list_jitter(images, B, Hin, Win, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, flips, jitter_order,
-                                                jitter_factors, mean3, std3, out, workspace, workspace_bytes, stream);
-    return sd_preprocess_images_list(images, B, Hin, Win, Hout, Wout, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize, flips, mean3, std3, out, workspace,
-                                     workspace_bytes, stream);
+// the name of a step's kernel, or of a late stage (its launches belong to its own file), or "memset"
+static const char* chain_name(const sd_preprocess_desc& d, const ChainStep& s) {
+    const bool window = d.geometry == SD_GEOM_WINDOW, fused = s.dst == BUF_OUT;
+    switch (s.op) {
+    case OP_MEMSET: return "memset";
+    case OP_H: return window ? (d.list ? "k_window_h_list" : "k_window_h") : (d.list ? "k_resample_h_list" : "k_resample_h");
+    case OP_V:
+        if (window) return fused ? "k_window_v_norm" : "k_window_v_u8";
+        if (d.geometry == SD_GEOM_LETTERBOX) return fused ? "k_letterbox_v_norm" : "k_letterbox_v_u8";
+        return fused ? "k_resample_v_norm" : "k_resample_v_u8";
+    case OP_MOSAIC: return fused ? "k_mosaic_norm" : "k_mosaic_u8";
+    case OP_AFFINE: return fused ? "k_affine_norm" : "k_affine_u8";
+    case OP_PERSP: return "k_persp_u8";
+    case OP_BLUR: return "blur";
+    case OP_NOISE: return "noise";
+    case OP_JPEG: return "jpeg";
+    case OP_TONE: return "tone";
+    case OP_LSUM: return "k_jitter_lsum";
+    case OP_JITTER_NORM: return "k_jitter_norm";
+    case OP_U8_NORM: return "k_u8_norm";
+    }
+    return "?";
 }
 
-// ---- RandomPerspective in the warp slot of the chain (k_persp_u8), behind any geometry ----
-// persp null: the blur form, a call.  persp set: the host has folded the affine draw into the homography, so affine must be null; the
-// chain is preprocess_blur's with k_persp_u8 as the warp and the blur optional.
+static int launch_chain(const sd_preprocess_desc& d, const ChainPlan& p, uint8_t* ws, hipStream_t st) {
+    uint8_t* const buf[] = {ws, ws + p.a_at, ws + p.b_at, nullptr, ws + p.sums_at};
+    unsigned long long* sums = reinterpret_cast<unsigned long long*>(ws + p.sums_at);
+    const uint8_t* packed = reinterpret_cast<const uint8_t*>(d.images);
+    const uint8_t* const* table = reinterpret_cast<const uint8_t* const*>(d.images);
+    const int B = d.B, Hin = d.Hin, Win = d.Win, Hg = d.Hg, Wg = d.Wg, Hout = d.Hout, Wout = d.Wout, g0 = d.g0, g1 = d.g1;
+    const int f0 = d.fill3 ? d.fill3[0] : 0, f1 = d.fill3 ? d.fill3[1] : 0, f2 = d.fill3 ? d.fill3[2] : 0;
+    const float m0 = d.mean3[0], m1 = d.mean3[1], m2 = d.mean3[2], s0 = d.std3[0], s1 = d.std3[1], s2 = d.std3[2];
+    const dim3 block(256);
+    for (int i = 0; i < p.n; ++i) {
+        const ChainStep& s = p.steps[i];
+        const ChainDims l = chain_dims(d, p, s.op);
+        const uint8_t* src = buf[s.src];
+        uint8_t* dst = buf[s.dst];
+        const bool fused = s.dst == BUF_OUT;
+        switch (s.op) {
+        case OP_MEMSET: SD_HIP(hipMemsetAsync(sums, 0, (size_t)B * 8, st)); continue;
+        case OP_H:
+            if (d.geometry == SD_GEOM_WINDOW) {
+                if (d.list)
+                    hipLaunchKernelGGL(k_window_h_list, l.grid, block, l.lds, st, table, dst, Win, Hg, Wg, Hout, Wout, d.h_bounds, d.h_kk, d.h_ksize,
+                                       d.v_bounds, d.window, g0, g1, p.rpb, p.bpi);
+                else
+                    hipLaunchKernelGGL(k_window_h, l.grid, block, 0, st, packed, dst, Hin, Win, Hg, Wg, Hout, Wout, d.h_bounds, d.h_kk, d.h_ksize,
+                                       d.v_bounds, d.window, g0, B);
+            } else if (d.list) {
+                hipLaunchKernelGGL(k_resample_h_list, l.grid, block, l.lds, st, table, dst, Hin, Win, p.cols, d.h_bounds, d.h_kk, d.h_ksize, p.rpb, p.bpi);
+            } else {
+                hipLaunchKernelGGL(k_resample_h, l.grid, block, 0, st, packed, dst, Hin, Win, p.cols, d.h_bounds, d.h_kk, d.h_ksize, (int64_t)B * Hin);
+            }
+            break;
+        case OP_V:
+            if (d.geometry == SD_GEOM_WINDOW) {
+                if (fused)
+                    hipLaunchKernelGGL(k_window_v_norm, l.grid, block, 0, st, src, d.out, Hg, Wg, Hout, Wout, d.v_bounds, d.v_kk, d.v_ksize, d.window, g0,
+                                       d.flips, m0, m1, m2, s0, s1, s2, B);
+                else
+                    hipLaunchKernelGGL(k_window_v_u8, l.grid, block, 0, st, src, dst, Hg, Wg, Hout, Wout, d.v_bounds, d.v_kk, d.v_ksize, d.window, g0, B);
+            } else if (d.geometry == SD_GEOM_LETTERBOX) {
+                if (fused)
+                    hipLaunchKernelGGL(k_letterbox_v_norm, l.grid, block, 0, st, src, d.out, Hin, Hg, Wg, Hout, Wout, g0, g1, d.v_bounds, d.v_kk,
+                                       d.v_ksize, d.flips, f0, f1, f2, m0, m1, m2, s0, s1, s2, B);
+                else
+                    hipLaunchKernelGGL(k_letterbox_v_u8, l.grid, block, 0, st, src, dst, Hin, Hg, Wg, Hout, Wout, g0, g1, d.v_bounds, d.v_kk, d.v_ksize,
+                                       f0, f1, f2, B);
+            } else if (fused) {
+                hipLaunchKernelGGL(k_resample_v_norm, l.grid, block, 0, st, src, d.out, Hin, Hout, Wout, d.v_bounds, d.v_kk, d.v_ksize, d.flips, m0, m1,
+                                   m2, s0, s1, s2, B);
+            } else {
+                hipLaunchKernelGGL(k_resample_v_u8, l.grid, block, 0, st, src, dst, Hin, Hout, Wout, d.v_bounds, d.v_kk, d.v_ksize, B);
+            }
+            break;
+        case OP_MOSAIC:
+            if (fused)
+                hipLaunchKernelGGL(k_mosaic_norm, l.grid, block, 0, st, src, d.out, Hout, Wout, d.mosaic_geom, d.mosaic_affine, f0, f1, f2, d.flips, m0,
+                                   m1, m2, s0, s1, s2);
+            else
+                hipLaunchKernelGGL(k_mosaic_u8, l.grid, block, 0, st, src, dst, Hout, Wout, d.mosaic_geom, d.mosaic_affine, f0, f1, f2);
+            break;
+        case OP_AFFINE:
+            if (fused)
+                hipLaunchKernelGGL(k_affine_norm, l.grid, block, 0, st, src, d.out, Hout, Wout, d.affine, f0, f1, f2, d.flips, m0, m1, m2, s0, s1, s2);
+            else
+                hipLaunchKernelGGL(k_affine_u8, l.grid, block, 0, st, src, dst, Hout, Wout, d.affine, f0, f1, f2);
+            break;
+        case OP_PERSP: hipLaunchKernelGGL(k_persp_u8, l.grid, block, 0, st, src, dst, Hout, Wout, d.persp, f0, f1, f2); break;
+        case OP_BLUR: if (int e = blur_stage(src, buf[BUF_B], dst, B, Hout, Wout, d.blur, st)) return e; continue;
+        case OP_NOISE: if (int e = noise_stage(src, dst, B, Hout, Wout, d.noise, st)) return e; continue;
+        case OP_JPEG: if (int e = jpeg_stage(src, dst, ws + p.planes_at, B, Hout, Wout, d.jpeg, st)) return e; continue;
+        case OP_TONE: if (int e = tone_stage(src, dst, ws + p.tone_at, B, Hout, Wout, d.tone, st)) return e; continue;
+        case OP_LSUM:
+            hipLaunchKernelGGL(k_jitter_lsum, l.grid, block, 0, st, src, (int64_t)Hout * Wout, d.jitter_order, d.jitter_factors, sums);
+            break;
+        case OP_JITTER_NORM:
+            hipLaunchKernelGGL(k_jitter_norm, l.grid, block, 0, st, src, d.out, Hout, Wout, d.jitter_order, d.jitter_factors, sums, d.flips, m0, m1, m2,
+                               s0, s1, s2, B);
+            break;
+        case OP_U8_NORM: hipLaunchKernelGGL(k_u8_norm, l.grid, block, 0, st, src, d.out, Hout, Wout, d.flips, m0, m1, m2, s0, s1, s2, B); break;
+        }
+        SD_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+// plan + the checks of the workspace + launcher, under the caller's name
+static int run_chain(const char* what, const sd_preprocess_desc* d, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
+    ChainPlan p;
+    if (int e = plan_chain(d, what, &p)) return e;
+    SD_REQUIRE(workspace, SD_ERR_INVALID, "%s: null pointer (workspace)", what);
+    SD_REQUIRE(aligned16(workspace) || !(d->jpeg || d->tone), SD_ERR_INVALID, "%s: jpeg and tone need a 16-byte aligned workspace", what);
+    SD_REQUIRE(workspace_bytes >= p.ws_bytes, SD_ERR_WORKSPACE, "%s: workspace %zu < %zu", what, workspace_bytes, p.ws_bytes);
+    return launch_chain(*d, p, reinterpret_cast<uint8_t*>(workspace), (hipStream_t)stream);
+}
+
+size_t sd_preprocess_chain_workspace_bytes(const sd_preprocess_desc* d) {
+    ChainPlan p;
+    return plan_chain(d, "sd_preprocess_chain_workspace_bytes", &p) ? 0 : p.ws_bytes;
+}
+
+int sd_preprocess_chain(const sd_preprocess_desc* d, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
+    return run_chain("sd_preprocess_chain", d, workspace, workspace_bytes, stream);
+}
+
+const char* sd_preprocess_kernel_names(const sd_preprocess_desc* d) {
+    static thread_local char line[1536];
+    static const char* const buffers[] = {"tmp", "A", "B", "out", "sums"};
+    ChainPlan p;
+    if (plan_chain(d, "sd_preprocess_kernel_names", &p)) {
+        snprintf(line, sizeof(line), "refused: %s", sd_last_error());
+        return line;
+    }
+    int at = 0;
+    for (int i = 0; i < p.n && (size_t)at < sizeof(line); ++i) {
+        const ChainStep& s = p.steps[i];
+        const char* sep = i ? "; " : "";
+        if (s.op == OP_MEMSET || (s.op >= OP_BLUR && s.op <= OP_TONE)) {
+            at += snprintf(line + at, sizeof(line) - at, "%s%s", sep, chain_name(*d, s));
+            continue;
+        }
+        const ChainDims l = chain_dims(*d, p, s.op);
+        at += snprintf(line + at, sizeof(line) - at, "%s%s grid=%ux%ux%u block=256 lds=%zu dst=%s", sep, chain_name(*d, s), l.grid.x, l.grid.y,
+                       l.grid.z, l.lds, buffers[s.dst]);
+    }
+    return line;
+}
+
 int sd_perspective_u8(const uint8_t* in, uint8_t* out, int B, int H, int W, const double* coeffs, const uint8_t* fill3, sd_stream_t stream) {
     SD_REQUIRE(in && out && coeffs && fill3, SD_ERR_INVALID, "sd_perspective_u8: null pointer");
     SD_REQUIRE(B > 0 && H > 0 && W > 0, SD_ERR_INVALID, "sd_perspective_u8: bad shape");
@@ -1646,22 +1188,156 @@ int sd_perspective_u8(const uint8_t* in, uint8_t* out, int B, int H, int W, cons
     return 0;
 }
 
+// ---- the legacy entry points: each fills a descriptor and runs the chain under its own name -----------------------------------------
+// Their arguments carry the names of the descriptor's fields, so the macros below copy them by name; a form has no slot for the stages
+// that came after it, which stay null.  What a form asks beyond the chain (the table it is named after) is checked in its body.
+#define SD_DESC_RESIZE(LIST)                                                                                                               \
+    sd_preprocess_desc d = {};                                                                                                             \
+    d.images = images; d.list = LIST; d.B = B; d.Hin = Hin; d.Win = Win; d.Hout = Hout; d.Wout = Wout; d.h_bounds = h_bounds; d.h_kk = h_kk; \
+    d.h_ksize = h_ksize; d.v_bounds = v_bounds; d.v_kk = v_kk; d.v_ksize = v_ksize; d.flips = flips; d.mean3 = mean3; d.std3 = std3; d.out = out
+#define SD_DESC_JITTER d.jitter_order = jitter_order; d.jitter_factors = jitter_factors
+#define SD_DESC_STAGES SD_DESC_JITTER; d.affine = affine; d.mosaic_geom = mosaic_geom; d.mosaic_affine = mosaic_affine; d.fill3 = fill3
+#define SD_DESC_GEOMETRY d.geometry = geometry; d.Hg = Hg; d.Wg = Wg; d.g0 = g0; d.g1 = g1; d.window = window
+#define SD_RUN_CHAIN return run_chain(__func__, &d, workspace, workspace_bytes, stream)
+
+int sd_preprocess_images(const uint8_t* images, int B, int Hin, int Win, int Hout, int Wout, const int* h_bounds, const int* h_kk,
+                         int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips, const float* mean3,
+                         const float* std3, float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
+    SD_DESC_RESIZE(0);
+    SD_RUN_CHAIN;
+}
+
+int sd_preprocess_images_list(const uint8_t* const* images, int B, int Hin, int Win, int Hout, int Wout, const int* h_bounds, const int* h_kk,
+                              int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips, const float* mean3,
+                              const float* std3, float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
+    SD_DESC_RESIZE(1);
+    SD_RUN_CHAIN;
+}
+
+int sd_preprocess_images_jitter(const uint8_t* images, int B, int Hin, int Win, int Hout, int Wout, const int* h_bounds, const int* h_kk,
+                                int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips, const int* jitter_order,
+                                const float* jitter_factors, const float* mean3, const float* std3, float* out, void* workspace,
+                                size_t workspace_bytes, sd_stream_t stream) {
+    SD_DESC_RESIZE(0); SD_DESC_JITTER;
+    SD_REQUIRE(jitter_order && jitter_factors, SD_ERR_INVALID, "%s: null jitter parameters", __func__);
+    SD_RUN_CHAIN;
+}
+
+int sd_preprocess_images_list_jitter(const uint8_t* const* images, int B, int Hin, int Win, int Hout, int Wout, const int* h_bounds, const int* h_kk,
+                                     int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips, const int* jitter_order,
+                                     const float* jitter_factors, const float* mean3, const float* std3, float* out, void* workspace,
+                                     size_t workspace_bytes, sd_stream_t stream) {
+    SD_DESC_RESIZE(1); SD_DESC_JITTER;
+    SD_REQUIRE(jitter_order && jitter_factors, SD_ERR_INVALID, "%s: null jitter parameters", __func__);
+    SD_RUN_CHAIN;
+}
+
+int sd_preprocess_images_affine(const uint8_t* images, int B, int Hin, int Win, int Hout, int Wout, const int* h_bounds, const int* h_kk,
+                                int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips, const int* jitter_order,
+                                const float* jitter_factors, const double* affine, const uint8_t* fill3, const float* mean3, const float* std3,
+                                float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
+    SD_DESC_RESIZE(0); SD_DESC_JITTER; d.affine = affine; d.fill3 = fill3;
+    SD_REQUIRE(affine && fill3, SD_ERR_INVALID, "%s: null affine matrices or fill colour", __func__);
+    SD_RUN_CHAIN;
+}
+
+int sd_preprocess_images_list_affine(const uint8_t* const* images, int B, int Hin, int Win, int Hout, int Wout, const int* h_bounds,
+                                     const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips,
+                                     const int* jitter_order, const float* jitter_factors, const double* affine, const uint8_t* fill3,
+                                     const float* mean3, const float* std3, float* out, void* workspace, size_t workspace_bytes,
+                                     sd_stream_t stream) {
+    SD_DESC_RESIZE(1); SD_DESC_JITTER; d.affine = affine; d.fill3 = fill3;
+    SD_REQUIRE(affine && fill3, SD_ERR_INVALID, "%s: null affine matrices or fill colour", __func__);
+    SD_RUN_CHAIN;
+}
+
+int sd_preprocess_images_mosaic(const uint8_t* images, int B, int Hin, int Win, int Hout, int Wout, const int* h_bounds, const int* h_kk,
+                                int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips, const int* jitter_order,
+                                const float* jitter_factors, const double* affine, const int* mosaic_geom, const double* mosaic_affine,
+                                const uint8_t* fill3, const float* mean3, const float* std3, float* out, void* workspace, size_t workspace_bytes,
+                                sd_stream_t stream) {
+    SD_DESC_RESIZE(0); SD_DESC_STAGES;
+    SD_REQUIRE(mosaic_geom && mosaic_affine && fill3, SD_ERR_INVALID, "%s: null mosaic tables or fill colour", __func__);
+    SD_RUN_CHAIN;
+}
+
+int sd_preprocess_images_list_mosaic(const uint8_t* const* images, int B, int Hin, int Win, int Hout, int Wout, const int* h_bounds,
+                                     const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const uint8_t* flips,
+                                     const int* jitter_order, const float* jitter_factors, const double* affine, const int* mosaic_geom,
+                                     const double* mosaic_affine, const uint8_t* fill3, const float* mean3, const float* std3, float* out,
+                                     void* workspace, size_t workspace_bytes, sd_stream_t stream) {
+    SD_DESC_RESIZE(1); SD_DESC_STAGES;
+    SD_REQUIRE(mosaic_geom && mosaic_affine && fill3, SD_ERR_INVALID, "%s: null mosaic tables or fill colour", __func__);
+    SD_RUN_CHAIN;
+}
+
+int sd_preprocess_images_window(const uint8_t* images, int B, int Hin, int Win, int Hc, int Wc, int Hout, int Wout, const int* h_bounds,
+                                const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const int* window, int max_rows,
+                                int max_cols, const uint8_t* flips, const int* jitter_order, const float* jitter_factors, const double* affine,
+                                const int* mosaic_geom, const double* mosaic_affine, const uint8_t* fill3, const float* mean3, const float* std3,
+                                float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
+    SD_DESC_RESIZE(0); SD_DESC_STAGES;
+    d.geometry = SD_GEOM_WINDOW; d.Hg = Hc; d.Wg = Wc; d.g0 = max_rows; d.g1 = max_cols; d.window = window;
+    SD_RUN_CHAIN;
+}
+
+int sd_preprocess_images_list_window(const uint8_t* const* images, int B, int Hin, int Win, int Hc, int Wc, int Hout, int Wout, const int* h_bounds,
+                                     const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, const int* window,
+                                     int max_rows, int max_cols, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
+                                     const double* affine, const int* mosaic_geom, const double* mosaic_affine, const uint8_t* fill3,
+                                     const float* mean3, const float* std3, float* out, void* workspace, size_t workspace_bytes,
+                                     sd_stream_t stream) {
+    SD_DESC_RESIZE(1); SD_DESC_STAGES;
+    d.geometry = SD_GEOM_WINDOW; d.Hg = Hc; d.Wg = Wc; d.g0 = max_rows; d.g1 = max_cols; d.window = window;
+    SD_RUN_CHAIN;
+}
+
+int sd_preprocess_images_letterbox(const uint8_t* images, int B, int Hin, int Win, int Hi, int Wi, int Hout, int Wout, int y0, int x0,
+                                   const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize,
+                                   const uint8_t* flips, const int* jitter_order, const float* jitter_factors, const double* affine,
+                                   const int* mosaic_geom, const double* mosaic_affine, const uint8_t* fill3, const float* mean3, const float* std3,
+                                   float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
+    SD_DESC_RESIZE(0); SD_DESC_STAGES;
+    d.geometry = SD_GEOM_LETTERBOX; d.Hg = Hi; d.Wg = Wi; d.g0 = y0; d.g1 = x0;
+    SD_RUN_CHAIN;
+}
+
+int sd_preprocess_images_list_letterbox(const uint8_t* const* images, int B, int Hin, int Win, int Hi, int Wi, int Hout, int Wout, int y0, int x0,
+                                        const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize,
+                                        const uint8_t* flips, const int* jitter_order, const float* jitter_factors, const double* affine,
+                                        const int* mosaic_geom, const double* mosaic_affine, const uint8_t* fill3, const float* mean3,
+                                        const float* std3, float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
+    SD_DESC_RESIZE(1); SD_DESC_STAGES;
+    d.geometry = SD_GEOM_LETTERBOX; d.Hg = Hi; d.Wg = Wi; d.g0 = y0; d.g1 = x0;
+    SD_RUN_CHAIN;
+}
+
+int sd_preprocess_images_blur(const uint8_t* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout, int g0, int g1,
+                              const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize,
+                              const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
+                              const double* affine, const int* mosaic_geom, const double* mosaic_affine, const int* blur, const uint8_t* fill3,
+                              const float* mean3, const float* std3, float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
+    SD_DESC_RESIZE(0); SD_DESC_GEOMETRY; SD_DESC_STAGES; d.blur = blur;
+    SD_RUN_CHAIN;
+}
+
+int sd_preprocess_images_list_blur(const uint8_t* const* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout,
+                                   int g0, int g1, const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk,
+                                   int v_ksize, const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
+                                   const double* affine, const int* mosaic_geom, const double* mosaic_affine, const int* blur, const uint8_t* fill3,
+                                   const float* mean3, const float* std3, float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
+    SD_DESC_RESIZE(1); SD_DESC_GEOMETRY; SD_DESC_STAGES; d.blur = blur;
+    SD_RUN_CHAIN;
+}
+
 int sd_preprocess_images_persp(const uint8_t* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout, int g0, int g1,
                                const int* h_bounds, const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize,
                                const int* window, const uint8_t* flips, const int* jitter_order, const float* jitter_factors,
                                const double* affine, const double* persp, const int* mosaic_geom, const double* mosaic_affine, const int* blur,
                                const uint8_t* fill3, const float* mean3, const float* std3, float* out, void* workspace, size_t workspace_bytes,
                                sd_stream_t stream) {
-    const char* what = "sd_preprocess_images_persp";
-    if (!persp)
-        return sd_preprocess_images_blur(images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
-                                         window, flips, jitter_order, jitter_factors, affine, mosaic_geom, mosaic_affine, blur, fill3, mean3, std3, out,
-                                         workspace, workspace_bytes, stream);
-    SD_REQUIRE(!affine, SD_ERR_INVALID, "%s: persp and affine do not combine (fold the affine matrix into the homography)", what);
-    SD_REQUIRE(fill3, SD_ERR_INVALID, "%s: a warp needs a fill colour", what);
-    return preprocess_blur(what, false, images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
-                           window, flips, jitter_order, jitter_factors, nullptr, persp, mosaic_geom, mosaic_affine, blur, nullptr, nullptr, nullptr, fill3, mean3, std3, out,
-                           workspace, workspace_bytes, (hipStream_t)stream);
+    SD_DESC_RESIZE(0); SD_DESC_GEOMETRY; SD_DESC_STAGES; d.persp = persp; d.blur = blur;
+    SD_RUN_CHAIN;
 }
 
 int sd_preprocess_images_list_persp(const uint8_t* const* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout,
@@ -1670,24 +1346,8 @@ int sd_preprocess_images_list_persp(const uint8_t* const* images, int geometry, 
                                     const double* affine, const double* persp, const int* mosaic_geom, const double* mosaic_affine, const int* blur,
                                     const uint8_t* fill3, const float* mean3, const float* std3, float* out, void* workspace,
                                     size_t workspace_bytes, sd_stream_t stream) {
-    const char* what = "sd_preprocess_images_list_persp";
-    if (!persp)
-        return sd_preprocess_images_list_blur(images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk,
-                                              v_ksize, window, flips, jitter_order, jitter_factors, affine, mosaic_geom, mosaic_affine, blur, fill3,
-                                              mean3, std3, out, workspace, workspace_bytes, stream);
-    SD_REQUIRE(!affine, SD_ERR_INVALID, "%s: persp and affine do not combine (fold the affine matrix into the homography)", what);
-    SD_REQUIRE(fill3, SD_ERR_INVALID, "%s: a warp needs a fill colour", what);
-    return preprocess_blur(what, true, images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
-                           window, flips, jitter_order, jitter_factors, nullptr, persp, mosaic_geom, mosaic_affine, blur, nullptr, nullptr, nullptr, fill3, mean3, std3, out,
-                           workspace, workspace_bytes, (hipStream_t)stream);
-}
-
-// ---- JPEG round trip between the blur and the jitter (sd_jpeg.hip: jpeg_stage), behind any geometry ----
-// jpeg null: the perspective form, a call.  jpeg set: preprocess_blur's chain with the one more stage, every other table optional;
-// workspace: the blur form's, then the decoded planes.
-size_t sd_preprocess_jpeg_workspace_bytes(int geometry, int B, int Hin, int Win, int Wg, int Hout, int Wout, int g0) {
-    if (B <= 0 || Hout <= 0 || Wout <= 0) return sd_preprocess_blur_workspace_bytes(geometry, B, Hin, Win, Wg, Hout, Wout, g0);
-    return sd_preprocess_blur_workspace_bytes(geometry, B, Hin, Win, Wg, Hout, Wout, g0) + jpeg_planes_bytes(B, Hout, Wout);
+    SD_DESC_RESIZE(1); SD_DESC_GEOMETRY; SD_DESC_STAGES; d.persp = persp; d.blur = blur;
+    SD_RUN_CHAIN;
 }
 
 int sd_preprocess_images_jpeg(const uint8_t* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout, int g0, int g1,
@@ -1696,15 +1356,8 @@ int sd_preprocess_images_jpeg(const uint8_t* images, int geometry, int B, int Hi
                               const double* affine, const double* persp, const int* mosaic_geom, const double* mosaic_affine, const int* blur,
                               const int* jpeg, const uint8_t* fill3, const float* mean3, const float* std3, float* out, void* workspace,
                               size_t workspace_bytes, sd_stream_t stream) {
-    const char* what = "sd_preprocess_images_jpeg";
-    if (!jpeg)
-        return sd_preprocess_images_persp(images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
-                                          window, flips, jitter_order, jitter_factors, affine, persp, mosaic_geom, mosaic_affine, blur, fill3, mean3,
-                                          std3, out, workspace, workspace_bytes, stream);
-    SD_REQUIRE(!(affine && persp), SD_ERR_INVALID, "%s: persp and affine do not combine (fold the affine matrix into the homography)", what);
-    return preprocess_blur(what, false, images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
-                           window, flips, jitter_order, jitter_factors, affine, persp, mosaic_geom, mosaic_affine, blur, jpeg, nullptr, nullptr, fill3, mean3, std3, out,
-                           workspace, workspace_bytes, (hipStream_t)stream);
+    SD_DESC_RESIZE(0); SD_DESC_GEOMETRY; SD_DESC_STAGES; d.persp = persp; d.blur = blur; d.jpeg = jpeg;
+    SD_RUN_CHAIN;
 }
 
 int sd_preprocess_images_list_jpeg(const uint8_t* const* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout,
@@ -1713,23 +1366,8 @@ int sd_preprocess_images_list_jpeg(const uint8_t* const* images, int geometry, i
                                    const double* affine, const double* persp, const int* mosaic_geom, const double* mosaic_affine, const int* blur,
                                    const int* jpeg, const uint8_t* fill3, const float* mean3, const float* std3, float* out, void* workspace,
                                    size_t workspace_bytes, sd_stream_t stream) {
-    const char* what = "sd_preprocess_images_list_jpeg";
-    if (!jpeg)
-        return sd_preprocess_images_list_persp(images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk,
-                                               v_ksize, window, flips, jitter_order, jitter_factors, affine, persp, mosaic_geom, mosaic_affine, blur,
-                                               fill3, mean3, std3, out, workspace, workspace_bytes, stream);
-    SD_REQUIRE(!(affine && persp), SD_ERR_INVALID, "%s: persp and affine do not combine (fold the affine matrix into the homography)", what);
-    return preprocess_blur(what, true, images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
-                           window, flips, jitter_order, jitter_factors, affine, persp, mosaic_geom, mosaic_affine, blur, jpeg, nullptr, nullptr, fill3, mean3, std3, out,
-                           workspace, workspace_bytes, (hipStream_t)stream);
-}
-
-// ---- histogram tone curves between the JPEG round trip and the jitter (sd_tone.hip: tone_stage), behind any geometry ----
-// tone null: the JPEG form, a call.  tone set: preprocess_blur's chain with the one more stage, every other table optional;
-// workspace: the JPEG form's, then the histograms and the tables.
-size_t sd_preprocess_tone_workspace_bytes(int geometry, int B, int Hin, int Win, int Wg, int Hout, int Wout, int g0) {
-    if (B <= 0 || Hout <= 0 || Wout <= 0) return sd_preprocess_jpeg_workspace_bytes(geometry, B, Hin, Win, Wg, Hout, Wout, g0);
-    return sd_preprocess_jpeg_workspace_bytes(geometry, B, Hin, Win, Wg, Hout, Wout, g0) + tone_workspace_bytes(B);
+    SD_DESC_RESIZE(1); SD_DESC_GEOMETRY; SD_DESC_STAGES; d.persp = persp; d.blur = blur; d.jpeg = jpeg;
+    SD_RUN_CHAIN;
 }
 
 int sd_preprocess_images_tone(const uint8_t* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout, int g0, int g1,
@@ -1738,15 +1376,8 @@ int sd_preprocess_images_tone(const uint8_t* images, int geometry, int B, int Hi
                               const double* affine, const double* persp, const int* mosaic_geom, const double* mosaic_affine, const int* blur,
                               const int* jpeg, const int* tone, const uint8_t* fill3, const float* mean3, const float* std3, float* out,
                               void* workspace, size_t workspace_bytes, sd_stream_t stream) {
-    const char* what = "sd_preprocess_images_tone";
-    if (!tone)
-        return sd_preprocess_images_jpeg(images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
-                                         window, flips, jitter_order, jitter_factors, affine, persp, mosaic_geom, mosaic_affine, blur, jpeg, fill3,
-                                         mean3, std3, out, workspace, workspace_bytes, stream);
-    SD_REQUIRE(!(affine && persp), SD_ERR_INVALID, "%s: persp and affine do not combine (fold the affine matrix into the homography)", what);
-    return preprocess_blur(what, false, images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
-                           window, flips, jitter_order, jitter_factors, affine, persp, mosaic_geom, mosaic_affine, blur, jpeg, tone, nullptr, fill3, mean3, std3,
-                           out, workspace, workspace_bytes, (hipStream_t)stream);
+    SD_DESC_RESIZE(0); SD_DESC_GEOMETRY; SD_DESC_STAGES; d.persp = persp; d.blur = blur; d.jpeg = jpeg; d.tone = tone;
+    SD_RUN_CHAIN;
 }
 
 int sd_preprocess_images_list_tone(const uint8_t* const* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout,
@@ -1755,22 +1386,8 @@ int sd_preprocess_images_list_tone(const uint8_t* const* images, int geometry, i
                                    const double* affine, const double* persp, const int* mosaic_geom, const double* mosaic_affine, const int* blur,
                                    const int* jpeg, const int* tone, const uint8_t* fill3, const float* mean3, const float* std3, float* out,
                                    void* workspace, size_t workspace_bytes, sd_stream_t stream) {
-    const char* what = "sd_preprocess_images_list_tone";
-    if (!tone)
-        return sd_preprocess_images_list_jpeg(images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk,
-                                              v_ksize, window, flips, jitter_order, jitter_factors, affine, persp, mosaic_geom, mosaic_affine, blur,
-                                              jpeg, fill3, mean3, std3, out, workspace, workspace_bytes, stream);
-    SD_REQUIRE(!(affine && persp), SD_ERR_INVALID, "%s: persp and affine do not combine (fold the affine matrix into the homography)", what);
-    return preprocess_blur(what, true, images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
-                           window, flips, jitter_order, jitter_factors, affine, persp, mosaic_geom, mosaic_affine, blur, jpeg, tone, nullptr, fill3, mean3, std3,
-                           out, workspace, workspace_bytes, (hipStream_t)stream);
-}
-
-// ---- sensor noise between the blur and the JPEG round trip (sd_noise.hip: noise_stage), behind any geometry ----
-// noise null: the tone form, a call.  noise set: preprocess_blur's chain with the one more stage, every other table optional;
-// workspace: the tone form's (the stage needs none).
-size_t sd_preprocess_noise_workspace_bytes(int geometry, int B, int Hin, int Win, int Wg, int Hout, int Wout, int g0) {
-    return sd_preprocess_tone_workspace_bytes(geometry, B, Hin, Win, Wg, Hout, Wout, g0);
+    SD_DESC_RESIZE(1); SD_DESC_GEOMETRY; SD_DESC_STAGES; d.persp = persp; d.blur = blur; d.jpeg = jpeg; d.tone = tone;
+    SD_RUN_CHAIN;
 }
 
 int sd_preprocess_images_noise(const uint8_t* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout, int g0, int g1,
@@ -1779,15 +1396,8 @@ int sd_preprocess_images_noise(const uint8_t* images, int geometry, int B, int H
                                const double* affine, const double* persp, const int* mosaic_geom, const double* mosaic_affine, const int* blur,
                                const int* jpeg, const int* tone, const int* noise, const uint8_t* fill3, const float* mean3, const float* std3,
                                float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
-    const char* what = "sd_preprocess_images_noise";
-    if (!noise)
-        return sd_preprocess_images_tone(images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
-                                         window, flips, jitter_order, jitter_factors, affine, persp, mosaic_geom, mosaic_affine, blur, jpeg, tone,
-                                         fill3, mean3, std3, out, workspace, workspace_bytes, stream);
-    SD_REQUIRE(!(affine && persp), SD_ERR_INVALID, "%s: persp and affine do not combine (fold the affine matrix into the homography)", what);
-    return preprocess_blur(what, false, images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
-                           window, flips, jitter_order, jitter_factors, affine, persp, mosaic_geom, mosaic_affine, blur, jpeg, tone, noise, fill3, mean3,
-                           std3, out, workspace, workspace_bytes, (hipStream_t)stream);
+    SD_DESC_RESIZE(0); SD_DESC_GEOMETRY; SD_DESC_STAGES; d.persp = persp; d.blur = blur; d.jpeg = jpeg; d.tone = tone; d.noise = noise;
+    SD_RUN_CHAIN;
 }
 
 int sd_preprocess_images_list_noise(const uint8_t* const* images, int geometry, int B, int Hin, int Win, int Hg, int Wg, int Hout, int Wout,
@@ -1796,15 +1406,9 @@ int sd_preprocess_images_list_noise(const uint8_t* const* images, int geometry, 
                                     const double* affine, const double* persp, const int* mosaic_geom, const double* mosaic_affine, const int* blur,
                                     const int* jpeg, const int* tone, const int* noise, const uint8_t* fill3, const float* mean3, const float* std3,
                                     float* out, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
-    const char* what = "sd_preprocess_images_list_noise";
-    if (!noise)
-        return sd_preprocess_images_list_tone(images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk,
-                                              v_ksize, window, flips, jitter_order, jitter_factors, affine, persp, mosaic_geom, mosaic_affine, blur,
-                                              jpeg, tone, fill3, mean3, std3, out, workspace, workspace_bytes, stream);
-    SD_REQUIRE(!(affine && persp), SD_ERR_INVALID, "%s: persp and affine do not combine (fold the affine matrix into the homography)", what);
-    return preprocess_blur(what, true, images, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, h_bounds, h_kk, h_ksize, v_bounds, v_kk, v_ksize,
-                           window, flips, jitter_order, jitter_factors, affine, persp, mosaic_geom, mosaic_affine, blur, jpeg, tone, noise, fill3, mean3,
-                           std3, out, workspace, workspace_bytes, (hipStream_t)stream);
+    SD_DESC_RESIZE(1); SD_DESC_GEOMETRY; SD_DESC_STAGES; d.persp = persp; d.blur = blur; d.jpeg = jpeg; d.tone = tone; d.noise = noise;
+    SD_RUN_CHAIN;
 }
 
 }  // extern "C"
+

@@ -254,72 +254,26 @@ def _affine_rows(affine, B, device):
     return rows.to(device, non_blocking=True)
 
 
-def _stage_tables(B, flips, jitter, affine, mosaic, dev):
-    """The device tables of the optional stages, each None when its stage is off: flips (B,) uint8, jitter order (B,) int32 and factors
-    (B, 3) fp32, affine rows (B, 6) fp64, mosaic geometry (B, 6) int32 and matrices (B, 24) fp64."""
-    fl = order = factors = rows = geom = mats = None
-    if flips is not None:
-        fl = torch.as_tensor(flips, dtype=torch.uint8).to(dev, non_blocking=True)
-        if fl.numel() != B:
-            raise L.SdError("flips must have one entry per image")
-    if jitter is not None:
-        order = torch.as_tensor(jitter[0], dtype=torch.int32).to(dev, non_blocking=True)
-        factors = torch.as_tensor(jitter[1], dtype=torch.float32).reshape(-1, 3).contiguous().to(dev, non_blocking=True)
-        if order.numel() != B or factors.shape[0] != B:
-            raise L.SdError("jitter parameters must have one row per image")
-    if affine is not None:
-        rows = _affine_rows(affine, B, dev)
-    if mosaic is not None:
-        geom, mats = _mosaic_tables(mosaic, B, dev)
-    return fl, order, factors, rows, geom, mats
+def _flip_table(flips, B, device):
+    table = torch.as_tensor(flips, dtype=torch.uint8).to(device, non_blocking=True)
+    if table.numel() != B:
+        raise L.SdError("flips must have one entry per image")
+    return table
 
 
-def _preprocess_window(fn_name, source, B, Hin, Win, out_size, flips, mean, std, jitter, affine, mosaic, window, dev):
-    """The window forms of `preprocess_images` / `preprocess_image_list`: source = the address of the packed images or of the pointer
-    table; window = ((Wc, Hc), B origins (x0, y0))."""
-    (Wc, Hc), origins = window
-    Wc, Hc = int(Wc), int(Hc)
-    Wout, Hout = int(out_size[0]), int(out_size[1])
-    if not (0 < Wout <= Wc and 0 < Hout <= Hc):
-        raise L.SdError(f"window: {Wout} x {Hout} does not fit the canvas {Wc} x {Hc}")
-    org = torch.as_tensor(np.asarray(origins, dtype=np.int32)).reshape(-1, 2).contiguous()
-    if org.shape[0] != B:
+def _jitter_tables(jitter, B, device):
+    order = torch.as_tensor(jitter[0], dtype=torch.int32).to(device, non_blocking=True)
+    factors = torch.as_tensor(jitter[1], dtype=torch.float32).reshape(-1, 3).contiguous().to(device, non_blocking=True)
+    if order.numel() != B or factors.shape[0] != B:
+        raise L.SdError("jitter parameters must have one row per image")
+    return order, factors
+
+
+def _window_origins(origins, B, device):
+    table = torch.as_tensor(np.asarray(origins, dtype=np.int32)).reshape(-1, 2).contiguous()
+    if table.shape[0] != B:
         raise L.SdError("window must have one origin (x0, y0) per image")
-    org = org.to(dev, non_blocking=True)
-    hb, hk, hks = _tables.get(Win, Wc, dev)
-    vb, vk, vks = _tables.get(Hin, Hc, dev)
-    max_cols, max_rows = window_extents(Win, Wc, Wout), window_extents(Hin, Hc, Hout)
-    out = torch.empty((B, 3, Hout, Wout), dtype=torch.float32, device=dev)
-    fl, order, factors, rows, geom, mats = _stage_tables(B, flips, jitter, affine, mosaic, dev)
-    ptr = lambda t: t.data_ptr() if t is not None else 0
-    lib = L.lib()
-    ws = L.workspace(lib.sd_preprocess_window_workspace_bytes(B, max_rows, Hout, Wout), dev)
-    L.check(getattr(lib, fn_name)(source, B, Hin, Win, Hc, Wc, Hout, Wout, hb.data_ptr(), hk.data_ptr(), hks, vb.data_ptr(), vk.data_ptr(), vks,
-                                  org.data_ptr(), max_rows, max_cols, ptr(fl), ptr(order), ptr(factors), ptr(rows), ptr(geom), ptr(mats),
-                                  (C.c_ubyte * 3)(*_FILL), (C.c_float * 3)(*mean), (C.c_float * 3)(*std), out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                  L.stream()), fn_name)
-    return out
-
-
-def _preprocess_letterbox(fn_name, source, B, Hin, Win, out_size, flips, mean, std, jitter, affine, mosaic, letterbox, dev):
-    """The letterbox forms of `preprocess_images` / `preprocess_image_list`: source = the address of the packed images or of the pointer
-    table; letterbox = (wi, hi, px, py) as `letterbox_geometry` gives them (the library checks that the image lies inside the frame)."""
-    wi, hi, px, py = (int(v) for v in letterbox)
-    Wout, Hout = int(out_size[0]), int(out_size[1])
-    if wi <= 0 or hi <= 0:
-        raise L.SdError(f"letterbox: the inner image should be at least 1 x 1, not {wi} x {hi}")
-    hb, hk, hks = _tables.get(Win, wi, dev)
-    vb, vk, vks = _tables.get(Hin, hi, dev)
-    out = torch.empty((B, 3, Hout, Wout), dtype=torch.float32, device=dev)
-    fl, order, factors, rows, geom, mats = _stage_tables(B, flips, jitter, affine, mosaic, dev)
-    ptr = lambda t: t.data_ptr() if t is not None else 0
-    lib = L.lib()
-    ws = L.workspace(lib.sd_preprocess_letterbox_workspace_bytes(B, Hin, wi, Hout, Wout), dev)
-    L.check(getattr(lib, fn_name)(source, B, Hin, Win, hi, wi, Hout, Wout, py, px, hb.data_ptr(), hk.data_ptr(), hks, vb.data_ptr(), vk.data_ptr(),
-                                  vks, ptr(fl), ptr(order), ptr(factors), ptr(rows), ptr(geom), ptr(mats), (C.c_ubyte * 3)(*_FILL),
-                                  (C.c_float * 3)(*mean), (C.c_float * 3)(*std), out.data_ptr(), ws.data_ptr(), ws.numel(), L.stream()), fn_name)
-    return out
-
+    return table.to(device, non_blocking=True)
 
 def _persp_rows(persp, B, device):
     rows = torch.as_tensor(np.asarray(persp, dtype=np.float64)).reshape(-1, 8).contiguous()
@@ -514,68 +468,67 @@ JPEG_MAX_QUALITY = 95                                                # the upper
 GEOM_STRETCH, GEOM_WINDOW, GEOM_LETTERBOX = 0, 1, 2                  # include/sdnet_hip.h SD_GEOM_*
 
 
-def _preprocess_blur(fn_name, source, B, Hin, Win, out_size, flips, mean, std, jitter, affine, mosaic, window, letterbox, blur, dev, persp=None,
-                     jpeg=None, tone=None, noise=None):
-    """The blur forms of `preprocess_images` / `preprocess_image_list` (`sd_preprocess_images_blur` / `..._list_blur`): any geometry, every
-    optional stage, the blur between the warp and the jitter.  source = the address of the packed images or of the pointer table.  With
-    `persp` the perspective forms (`sd_preprocess_images_persp` / `..._list_persp`): the same arguments plus the homography table.  With
-    `jpeg` the JPEG forms (`sd_preprocess_images_jpeg` / `..._list_jpeg`): those arguments plus the quantisation tables after the blur's.  With
-    `tone` the tone forms (`sd_preprocess_images_tone` / `..._list_tone`): those plus the tone table after the quantisation tables.  With
-    `noise` the noise forms (`sd_preprocess_images_noise` / `..._list_noise`): those plus the noise table after the tone table."""
+def _chain_desc(source, is_list, B, Hin, Win, out_size, flips, mean, std, jitter, affine, mosaic, window, letterbox, blur, persp, jpeg, tone,
+                noise, dev):
+    """The descriptor of one `sd_preprocess_chain` call (include/sdnet_hip.h sd_preprocess_desc): source = the address of the packed images
+    or, with is_list, of the pointer table; every other argument as `preprocess_images` takes it.  Each optional table is uploaded once,
+    the geometry (coefficient tables, `window_extents`, the letterbox tuple) resolved once.  Returns (descriptor, out, the device tensors
+    the descriptor points into)."""
     if persp is not None and affine is not None:
         raise L.SdError("preprocess: persp and affine do not combine (fold the affine matrix in with compose_affine_perspective)")
+    if letterbox is not None and window is not None:
+        raise L.SdError("preprocess: a letterbox and a window do not combine")
     Wout, Hout = int(out_size[0]), int(out_size[1])
-    geometry, Hg, Wg, g0, g1, org = GEOM_STRETCH, 0, 0, 0, 0, None
+    d = L.PreprocessDesc(images=source, list=int(is_list), geometry=GEOM_STRETCH, B=B, Hin=Hin, Win=Win, Hout=Hout, Wout=Wout)
+    Wt, Ht, org = Wout, Hout, None                                   # the resize target of the coefficient tables
     if letterbox is not None:
-        if window is not None:
-            raise L.SdError("preprocess: a letterbox and a window do not combine")
         wi, hi, px, py = (int(v) for v in letterbox)
         if wi <= 0 or hi <= 0:
             raise L.SdError(f"letterbox: the inner image should be at least 1 x 1, not {wi} x {hi}")
-        geometry, Hg, Wg, g0, g1 = GEOM_LETTERBOX, hi, wi, py, px
-        hb, hk, hks = _tables.get(Win, wi, dev)
-        vb, vk, vks = _tables.get(Hin, hi, dev)
+        d.geometry, d.Hg, d.Wg, d.g0, d.g1 = GEOM_LETTERBOX, hi, wi, py, px      # (the library checks that the image lies inside the frame)
+        Wt, Ht = wi, hi
     elif window is not None:
         (Wc, Hc), origins = window
-        Wc, Hc = int(Wc), int(Hc)
-        if not (0 < Wout <= Wc and 0 < Hout <= Hc):
-            raise L.SdError(f"window: {Wout} x {Hout} does not fit the canvas {Wc} x {Hc}")
-        org = torch.as_tensor(np.asarray(origins, dtype=np.int32)).reshape(-1, 2).contiguous()
-        if org.shape[0] != B:
-            raise L.SdError("window must have one origin (x0, y0) per image")
-        org = org.to(dev, non_blocking=True)
-        geometry, Hg, Wg = GEOM_WINDOW, Hc, Wc
-        g1, g0 = window_extents(Win, Wc, Wout), window_extents(Hin, Hc, Hout)
-        hb, hk, hks = _tables.get(Win, Wc, dev)
-        vb, vk, vks = _tables.get(Hin, Hc, dev)
-    else:
-        hb, hk, hks = _tables.get(Win, Wout, dev)
-        vb, vk, vks = _tables.get(Hin, Hout, dev)
+        Wt, Ht = int(Wc), int(Hc)
+        if not (0 < Wout <= Wt and 0 < Hout <= Ht):
+            raise L.SdError(f"window: {Wout} x {Hout} does not fit the canvas {Wt} x {Ht}")
+        org = _window_origins(origins, B, dev)
+        d.geometry, d.Hg, d.Wg, d.window = GEOM_WINDOW, Ht, Wt, org.data_ptr()
+        d.g0, d.g1 = window_extents(Hin, Ht, Hout), window_extents(Win, Wt, Wout)   # (the LDS limit of the list form binds g1, the column span)
+    hb, hk, d.h_ksize = _tables.get(Win, Wt, dev)
+    vb, vk, d.v_ksize = _tables.get(Hin, Ht, dev)
+    d.h_bounds, d.h_kk, d.v_bounds, d.v_kk = hb.data_ptr(), hk.data_ptr(), vb.data_ptr(), vk.data_ptr()
     out = torch.empty((B, 3, Hout, Wout), dtype=torch.float32, device=dev)
-    fl, order, factors, rows, geom, mats = _stage_tables(B, flips, jitter, affine, mosaic, dev)
-    bl = None if blur is None else _blur_rows(blur, B, dev)          # (None: the library runs the geometry's existing entry point)
-    ptr = lambda t: t.data_ptr() if t is not None else 0
-    homography = None if persp is None else _persp_rows(persp, B, dev)
-    jp = None if jpeg is None else _jpeg_rows(jpeg, B, dev)
-    tn = None if tone is None else _tone_rows(tone, B, dev)
-    ns = None if noise is None else _noise_rows(noise, B, dev)
-    noise_form = fn_name.endswith("_noise")
-    tone_form = noise_form or fn_name.endswith("_tone")
-    jpeg_form = tone_form or fn_name.endswith("_jpeg")
-    warp = [ptr(rows), ptr(homography)] if jpeg_form or fn_name.endswith("_persp") else [ptr(rows)]   # the perspective forms take persp after affine
-    tail = [ptr(bl), ptr(jp)] if jpeg_form else [ptr(bl)]                                            # the JPEG forms take jpeg after blur
-    if tone_form:
-        tail.append(ptr(tn))                                                                         # the tone forms take tone after jpeg
-    if noise_form:
-        tail.append(ptr(ns))                                                                         # the noise forms take noise after tone
+    d.out, d.fill3, d.mean3, d.std3 = out.data_ptr(), (C.c_ubyte * 3)(*_FILL), (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
+    keep = [org, hb, hk, vb, vk]
+
+    def table(field, tensor):
+        setattr(d, field, tensor.data_ptr())
+        keep.append(tensor)
+    if flips is not None:
+        table("flips", _flip_table(flips, B, dev))
+    if jitter is not None:
+        order, factors = _jitter_tables(jitter, B, dev)
+        table("jitter_order", order); table("jitter_factors", factors)
+    if mosaic is not None:
+        geom, mats = _mosaic_tables(mosaic, B, dev)
+        table("mosaic_geom", geom); table("mosaic_affine", mats)
+    for field, rows, upload in (("affine", affine, _affine_rows), ("persp", persp, _persp_rows), ("blur", blur, _blur_rows),
+                                ("noise", noise, _noise_rows), ("jpeg", jpeg, _jpeg_rows), ("tone", tone, _tone_rows)):
+        if rows is not None:
+            table(field, upload(rows, B, dev))
+    return d, out, keep
+
+
+def _preprocess(source, is_list, B, Hin, Win, out_size, flips, mean, std, jitter, affine, mosaic, window, letterbox, blur, persp, jpeg, tone,
+                noise, dev):
+    """The one call site of the chain: `preprocess_images` (packed) and `preprocess_image_list` (is_list) after their argument checks."""
+    d, out, keep = _chain_desc(source, is_list, B, Hin, Win, out_size, flips, mean, std, jitter, affine, mosaic, window, letterbox, blur, persp,
+                               jpeg, tone, noise, dev)
     lib = L.lib()
-    ws_bytes = (lib.sd_preprocess_noise_workspace_bytes if noise_form else lib.sd_preprocess_tone_workspace_bytes if tone_form else
-                lib.sd_preprocess_jpeg_workspace_bytes if jpeg_form else lib.sd_preprocess_blur_workspace_bytes)
-    ws = L.workspace(ws_bytes(geometry, B, Hin, Win, Wg, Hout, Wout, g0), dev)
-    L.check(getattr(lib, fn_name)(source, geometry, B, Hin, Win, Hg, Wg, Hout, Wout, g0, g1, hb.data_ptr(), hk.data_ptr(), hks, vb.data_ptr(),
-                                  vk.data_ptr(), vks, ptr(org), ptr(fl), ptr(order), ptr(factors), *warp, ptr(geom), ptr(mats), *tail,
-                                  (C.c_ubyte * 3)(*_FILL), (C.c_float * 3)(*mean), (C.c_float * 3)(*std), out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                  L.stream()), fn_name)
+    ws = L.workspace(lib.sd_preprocess_chain_workspace_bytes(C.byref(d)), dev)   # (0 for a descriptor the call below refuses)
+    L.check(lib.sd_preprocess_chain(C.byref(d), ws.data_ptr(), ws.numel(), L.stream()), "sd_preprocess_chain")
+    del keep
     return out
 
 
@@ -607,77 +560,8 @@ def preprocess_images(images: torch.Tensor, out_size, flips=None, mean=_MEAN, st
         raise L.SdError(f"preprocess_images expects (B, H, W, 3) uint8, got {tuple(images.shape)} {images.dtype}")
     images = images.contiguous()
     B, Hin, Win, _ = images.shape
-    if noise is not None:
-        return _preprocess_blur("sd_preprocess_images_noise", images.data_ptr(), B, Hin, Win, out_size, flips, mean, std, jitter, affine, mosaic,
-                                window, letterbox, blur, images.device, persp, jpeg, tone, noise)
-    if tone is not None:
-        return _preprocess_blur("sd_preprocess_images_tone", images.data_ptr(), B, Hin, Win, out_size, flips, mean, std, jitter, affine, mosaic,
-                                window, letterbox, blur, images.device, persp, jpeg, tone)
-    if jpeg is not None:
-        return _preprocess_blur("sd_preprocess_images_jpeg", images.data_ptr(), B, Hin, Win, out_size, flips, mean, std, jitter, affine, mosaic,
-                                window, letterbox, blur, images.device, persp, jpeg)
-    if persp is not None:
-        return _preprocess_blur("sd_preprocess_images_persp", images.data_ptr(), B, Hin, Win, out_size, flips, mean, std, jitter, affine, mosaic,
-                                window, letterbox, blur, images.device, persp)
-    if blur is not None:
-        return _preprocess_blur("sd_preprocess_images_blur", images.data_ptr(), B, Hin, Win, out_size, flips, mean, std, jitter, affine, mosaic,
-                                window, letterbox, blur, images.device)
-    if letterbox is not None:
-        if window is not None:
-            raise L.SdError("preprocess_images: a letterbox and a window do not combine")
-        return _preprocess_letterbox("sd_preprocess_images_letterbox", images.data_ptr(), B, Hin, Win, out_size, flips, mean, std, jitter, affine,
-                                     mosaic, letterbox, images.device)
-    if window is not None:
-        return _preprocess_window("sd_preprocess_images_window", images.data_ptr(), B, Hin, Win, out_size, flips, mean, std, jitter, affine, mosaic,
-                                  window, images.device)
-    Wout, Hout = int(out_size[0]), int(out_size[1])
-    hb, hk, hks = _tables.get(Win, Wout, images.device)
-    vb, vk, vks = _tables.get(Hin, Hout, images.device)
-    out = torch.empty((B, 3, Hout, Wout), dtype=torch.float32, device=images.device)
-    lib = L.lib()
-    fl = None
-    if flips is not None:
-        fl = torch.as_tensor(flips, dtype=torch.uint8).to(images.device, non_blocking=True)
-        if fl.numel() != B:
-            raise L.SdError("flips must have one entry per image")
-    m3, s3 = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
-    order = factors = None
-    if jitter is not None:
-        order = torch.as_tensor(jitter[0], dtype=torch.int32).to(images.device, non_blocking=True)
-        factors = torch.as_tensor(jitter[1], dtype=torch.float32).reshape(-1, 3).contiguous().to(images.device, non_blocking=True)
-        if order.numel() != B or factors.shape[0] != B:
-            raise L.SdError("jitter parameters must have one row per image")
-    if mosaic is not None:
-        geom, mats = _mosaic_tables(mosaic, B, images.device)
-        rows = None if affine is None else _affine_rows(affine, B, images.device)
-        ws = L.workspace(lib.sd_preprocess_mosaic_workspace_bytes(B, Hin, Win, Hout, Wout), images.device)
-        L.check(lib.sd_preprocess_images_mosaic(images.data_ptr(), B, Hin, Win, Hout, Wout, hb.data_ptr(), hk.data_ptr(), hks, vb.data_ptr(),
-                                                vk.data_ptr(), vks, fl.data_ptr() if fl is not None else 0,
-                                                order.data_ptr() if order is not None else 0, factors.data_ptr() if factors is not None else 0,
-                                                rows.data_ptr() if rows is not None else 0, geom.data_ptr(), mats.data_ptr(),
-                                                (C.c_ubyte * 3)(*_FILL), m3, s3, out.data_ptr(), ws.data_ptr(), ws.numel(), L.stream()),
-                "sd_preprocess_images_mosaic")
-        return out
-    if affine is not None:
-        rows = _affine_rows(affine, B, images.device)
-        ws = L.workspace(lib.sd_preprocess_affine_workspace_bytes(B, Hin, Win, Hout, Wout), images.device)
-        L.check(lib.sd_preprocess_images_affine(images.data_ptr(), B, Hin, Win, Hout, Wout, hb.data_ptr(), hk.data_ptr(), hks, vb.data_ptr(),
-                                                vk.data_ptr(), vks, fl.data_ptr() if fl is not None else 0,
-                                                order.data_ptr() if order is not None else 0, factors.data_ptr() if factors is not None else 0,
-                                                rows.data_ptr(), (C.c_ubyte * 3)(*_FILL), m3, s3, out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                L.stream()), "sd_preprocess_images_affine")
-        return out
-    if jitter is not None:
-        ws = L.workspace(lib.sd_preprocess_jitter_workspace_bytes(B, Hin, Win, Hout, Wout), images.device)
-        L.check(lib.sd_preprocess_images_jitter(images.data_ptr(), B, Hin, Win, Hout, Wout, hb.data_ptr(), hk.data_ptr(), hks, vb.data_ptr(),
-                                                vk.data_ptr(), vks, fl.data_ptr() if fl is not None else 0, order.data_ptr(), factors.data_ptr(),
-                                                m3, s3, out.data_ptr(), ws.data_ptr(), ws.numel(), L.stream()), "sd_preprocess_images_jitter")
-        return out
-    ws = L.workspace(lib.sd_preprocess_workspace_bytes(B, Hin, Win, Wout), images.device)
-    L.check(lib.sd_preprocess_images(images.data_ptr(), B, Hin, Win, Hout, Wout, hb.data_ptr(), hk.data_ptr(), hks, vb.data_ptr(),
-                                     vk.data_ptr(), vks, fl.data_ptr() if fl is not None else 0, m3, s3, out.data_ptr(), ws.data_ptr(),
-                                     ws.numel(), L.stream()), "sd_preprocess_images")
-    return out
+    return _preprocess(images.data_ptr(), False, B, Hin, Win, out_size, flips, mean, std, jitter, affine, mosaic, window, letterbox, blur, persp,
+                       jpeg, tone, noise, images.device)
 
 
 def preprocess_image_list(pointers: torch.Tensor, hin: int, win: int, out_size, flips=None, mean=_MEAN, std=_STD, jitter=None,
@@ -689,81 +573,8 @@ def preprocess_image_list(pointers: torch.Tensor, hin: int, win: int, out_size, 
     if pointers.dtype != torch.int64 or pointers.dim() != 1 or pointers.numel() == 0:
         raise L.SdError(f"preprocess_image_list expects a non-empty (B,) int64 pointer table, got {tuple(pointers.shape)} {pointers.dtype}")
     pointers = pointers.contiguous()
-    dev = pointers.device
-    B, Hin, Win = pointers.numel(), int(hin), int(win)
-    if noise is not None:
-        return _preprocess_blur("sd_preprocess_images_list_noise", pointers.data_ptr(), B, Hin, Win, out_size, flips, mean, std, jitter, affine,
-                                mosaic, window, letterbox, blur, dev, persp, jpeg, tone, noise)
-    if tone is not None:
-        return _preprocess_blur("sd_preprocess_images_list_tone", pointers.data_ptr(), B, Hin, Win, out_size, flips, mean, std, jitter, affine,
-                                mosaic, window, letterbox, blur, dev, persp, jpeg, tone)
-    if jpeg is not None:
-        return _preprocess_blur("sd_preprocess_images_list_jpeg", pointers.data_ptr(), B, Hin, Win, out_size, flips, mean, std, jitter, affine,
-                                mosaic, window, letterbox, blur, dev, persp, jpeg)
-    if persp is not None:
-        return _preprocess_blur("sd_preprocess_images_list_persp", pointers.data_ptr(), B, Hin, Win, out_size, flips, mean, std, jitter, affine,
-                                mosaic, window, letterbox, blur, dev, persp)
-    if blur is not None:
-        return _preprocess_blur("sd_preprocess_images_list_blur", pointers.data_ptr(), B, Hin, Win, out_size, flips, mean, std, jitter, affine,
-                                mosaic, window, letterbox, blur, dev)
-    if letterbox is not None:
-        if window is not None:
-            raise L.SdError("preprocess_image_list: a letterbox and a window do not combine")
-        return _preprocess_letterbox("sd_preprocess_images_list_letterbox", pointers.data_ptr(), B, Hin, Win, out_size, flips, mean, std, jitter,
-                                     affine, mosaic, letterbox, dev)
-    if window is not None:                                           # (the LDS limit of the list form then binds the window's column span)
-        return _preprocess_window("sd_preprocess_images_list_window", pointers.data_ptr(), B, Hin, Win, out_size, flips, mean, std, jitter, affine,
-                                  mosaic, window, dev)
-    Wout, Hout = int(out_size[0]), int(out_size[1])
-    hb, hk, hks = _tables.get(Win, Wout, dev)
-    vb, vk, vks = _tables.get(Hin, Hout, dev)
-    out = torch.empty((B, 3, Hout, Wout), dtype=torch.float32, device=dev)
-    lib = L.lib()
-    fl = None
-    if flips is not None:
-        fl = torch.as_tensor(flips, dtype=torch.uint8).to(dev, non_blocking=True)
-        if fl.numel() != B:
-            raise L.SdError("flips must have one entry per image")
-    m3, s3 = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
-    order = factors = None
-    if jitter is not None:
-        order = torch.as_tensor(jitter[0], dtype=torch.int32).to(dev, non_blocking=True)
-        factors = torch.as_tensor(jitter[1], dtype=torch.float32).reshape(-1, 3).contiguous().to(dev, non_blocking=True)
-        if order.numel() != B or factors.shape[0] != B:
-            raise L.SdError("jitter parameters must have one row per image")
-    if mosaic is not None:
-        geom, mats = _mosaic_tables(mosaic, B, dev)
-        rows = None if affine is None else _affine_rows(affine, B, dev)
-        ws = L.workspace(lib.sd_preprocess_mosaic_workspace_bytes(B, Hin, Win, Hout, Wout), dev)
-        L.check(lib.sd_preprocess_images_list_mosaic(pointers.data_ptr(), B, Hin, Win, Hout, Wout, hb.data_ptr(), hk.data_ptr(), hks, vb.data_ptr(),
-                                                     vk.data_ptr(), vks, fl.data_ptr() if fl is not None else 0,
-                                                     order.data_ptr() if order is not None else 0,
-                                                     factors.data_ptr() if factors is not None else 0,
-                                                     rows.data_ptr() if rows is not None else 0, geom.data_ptr(), mats.data_ptr(),
-                                                     (C.c_ubyte * 3)(*_FILL), m3, s3, out.data_ptr(), ws.data_ptr(), ws.numel(), L.stream()),
-                "sd_preprocess_images_list_mosaic")
-        return out
-    if affine is not None:
-        rows = _affine_rows(affine, B, dev)
-        ws = L.workspace(lib.sd_preprocess_affine_workspace_bytes(B, Hin, Win, Hout, Wout), dev)
-        L.check(lib.sd_preprocess_images_list_affine(pointers.data_ptr(), B, Hin, Win, Hout, Wout, hb.data_ptr(), hk.data_ptr(), hks, vb.data_ptr(),
-                                                     vk.data_ptr(), vks, fl.data_ptr() if fl is not None else 0,
-                                                     order.data_ptr() if order is not None else 0,
-                                                     factors.data_ptr() if factors is not None else 0, rows.data_ptr(),
-                                                     (C.c_ubyte * 3)(*_FILL), m3, s3, out.data_ptr(), ws.data_ptr(), ws.numel(), L.stream()),
-                "sd_preprocess_images_list_affine")
-        return out
-    if jitter is not None:
-        ws = L.workspace(lib.sd_preprocess_jitter_workspace_bytes(B, Hin, Win, Hout, Wout), dev)
-        L.check(lib.sd_preprocess_images_list_jitter(pointers.data_ptr(), B, Hin, Win, Hout, Wout, hb.data_ptr(), hk.data_ptr(), hks, vb.data_ptr(),
-                                                     vk.data_ptr(), vks, fl.data_ptr() if fl is not None else 0, order.data_ptr(), factors.data_ptr(),
-                                                     m3, s3, out.data_ptr(), ws.data_ptr(), ws.numel(), L.stream()), "sd_preprocess_images_list_jitter")
-        return out
-    ws = L.workspace(lib.sd_preprocess_workspace_bytes(B, Hin, Win, Wout), dev)
-    L.check(lib.sd_preprocess_images_list(pointers.data_ptr(), B, Hin, Win, Hout, Wout, hb.data_ptr(), hk.data_ptr(), hks, vb.data_ptr(),
-                                          vk.data_ptr(), vks, fl.data_ptr() if fl is not None else 0, m3, s3, out.data_ptr(), ws.data_ptr(),
-                                          ws.numel(), L.stream()), "sd_preprocess_images_list")
-    return out
+    return _preprocess(pointers.data_ptr(), True, pointers.numel(), int(hin), int(win), out_size, flips, mean, std, jitter, affine, mosaic, window,
+                       letterbox, blur, persp, jpeg, tone, noise, pointers.device)
 
 
 def transpose_select(batch: torch.Tensor, select) -> torch.Tensor:

@@ -614,3 +614,51 @@ def head_problem(case, regime="round"):
            "dw": torch.einsum("bohw,bchw->oc", dyd, xd), "dw_bound": torch.einsum("bohw,bchw->oc", dyd.abs(), xd.abs()),
            "db": dyd.sum((0, 2, 3)), "db_bound": dyd.abs().sum((0, 2, 3))}
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# the legacy preprocess entry points of the C API, called by name with positional arguments
+# ---------------------------------------------------------------------------------------------
+def call_legacy_preprocess_form(fn_name, source, B, Hin, Win, out_size, flips, mean, std, jitter, affine, mosaic, window, letterbox, blur, dev,
+                                persp=None, jpeg=None, tone=None, noise=None):
+    """Calls the legacy entry point `fn_name` (`sd_preprocess_images[_list][_jitter | _affine | _mosaic | _window | _letterbox | _blur |
+    _persp | _jpeg | _tone | _noise]`) the way a C caller does: positional arguments in the order of include/sdnet_hip.h and a workspace of
+    the form's own size query.  source = the address of the packed images or of the pointer table; the tables are those data/augment.py
+    uploads for the same arguments.  A stage the form has no argument for must be None."""
+    from structuredetector_amd import _lib as L
+    from structuredetector_amd.data.augment import _chain_desc
+    lib = L.lib()
+    form = fn_name.replace("sd_preprocess_images", "").replace("_list", "").lstrip("_")      # "" = the plain resize
+    forms = ["", "jitter", "affine", "mosaic", "window", "letterbox", "blur", "persp", "jpeg", "tone", "noise"]
+    late = forms.index(form) - forms.index("blur")                                          # >= 0: the forms that take a geometry
+    d, out, keep = _chain_desc(source, "_list" in fn_name, B, Hin, Win, out_size, flips, mean, std, jitter, affine, mosaic, window, letterbox, blur,
+                               persp, jpeg, tone, noise, dev)
+    given = dict(jitter=jitter, affine=affine, mosaic=mosaic, window=window, letterbox=letterbox, blur=blur, persp=persp, jpeg=jpeg, tone=tone,
+                 noise=noise)
+    takes = {"": (), "jitter": ("jitter",), "affine": ("jitter", "affine"), "mosaic": ("jitter", "affine", "mosaic"),
+             "window": ("jitter", "affine", "mosaic", "window"), "letterbox": ("jitter", "affine", "mosaic", "letterbox")}
+    takes = takes.get(form, ("jitter", "affine", "mosaic", "window", "letterbox") + tuple(forms[6:7 + max(late, 0)]))
+    assert all(v is None or k in takes for k, v in given.items()), f"{fn_name} has no argument for {[k for k, v in given.items() if v is not None]}"
+    tables = [d.h_bounds, d.h_kk, d.h_ksize, d.v_bounds, d.v_kk, d.v_ksize]
+    jit, mos, end = [d.jitter_order, d.jitter_factors], [d.mosaic_geom, d.mosaic_affine], [d.mean3, d.std3, d.out]
+    if late >= 0:
+        args = [source, d.geometry, B, Hin, Win, d.Hg, d.Wg, d.Hout, d.Wout, d.g0, d.g1, *tables, d.window, d.flips, *jit, d.affine]
+        args += ([d.persp] if late >= 1 else []) + mos + [d.blur] + [d.jpeg, d.tone, d.noise][:max(late - 1, 0)] + [d.fill3]
+        size = {0: lib.sd_preprocess_blur_workspace_bytes, 1: lib.sd_preprocess_blur_workspace_bytes, 2: lib.sd_preprocess_jpeg_workspace_bytes,
+                3: lib.sd_preprocess_tone_workspace_bytes, 4: lib.sd_preprocess_noise_workspace_bytes}[late]
+        nbytes = size(d.geometry, B, Hin, Win, d.Wg, d.Hout, d.Wout, d.g0)
+    elif form == "window":
+        args = [source, B, Hin, Win, d.Hg, d.Wg, d.Hout, d.Wout, *tables, d.window, d.g0, d.g1, d.flips, *jit, d.affine, *mos, d.fill3]
+        nbytes = lib.sd_preprocess_window_workspace_bytes(B, d.g0, d.Hout, d.Wout)
+    elif form == "letterbox":
+        args = [source, B, Hin, Win, d.Hg, d.Wg, d.Hout, d.Wout, d.g0, d.g1, *tables, d.flips, *jit, d.affine, *mos, d.fill3]
+        nbytes = lib.sd_preprocess_letterbox_workspace_bytes(B, Hin, d.Wg, d.Hout, d.Wout)
+    else:
+        stages = {"": [], "jitter": jit, "affine": jit + [d.affine, d.fill3], "mosaic": jit + [d.affine] + mos + [d.fill3]}[form]
+        args = [source, B, Hin, Win, d.Hout, d.Wout, *tables, d.flips, *stages]
+        nbytes = (lib.sd_preprocess_workspace_bytes(B, Hin, Win, d.Wout) if form == "" else
+                  getattr(lib, f"sd_preprocess_{form}_workspace_bytes")(B, Hin, Win, d.Hout, d.Wout))
+    ws = L.workspace(nbytes, dev)
+    L.check(getattr(lib, fn_name)(*args, *end, ws.data_ptr(), ws.numel(), L.stream()), fn_name)
+    del keep
+    return out

@@ -152,7 +152,8 @@ def test_chain_forms_equal_the_hand_composition(geometry):
 @pytest.mark.parametrize("geometry", ["stretch", "window", "letterbox"])
 def test_a_null_table_is_the_existing_entry_point_bit_for_bit(geometry):
     from structuredetector_amd.data import preprocess_image_list, preprocess_images
-    from structuredetector_amd.data.augment import _MEAN, _STD, _preprocess_blur
+    from structuredetector_amd.data.augment import _MEAN, _STD
+    from tests.helpers import call_legacy_preprocess_form as _preprocess_blur
     x = torch.tensor(_sources(), device=DEV)
     arena, table = _table()
     geom = _geometry(geometry)

@@ -233,7 +233,8 @@ def test_chain_forms_equal_the_hand_composition(geometry):
 @pytest.mark.parametrize("geometry", ["stretch", "window", "letterbox"])
 def test_a_null_table_is_the_perspective_form_bit_for_bit(geometry):
     from structuredetector_amd.data import blur_box_params, preprocess_image_list, preprocess_images
-    from structuredetector_amd.data.augment import _MEAN, _STD, _preprocess_blur
+    from structuredetector_amd.data.augment import _MEAN, _STD
+    from tests.helpers import call_legacy_preprocess_form as _preprocess_blur
     from tests.test_gpu_blur import NB, OUT, RADII, SRC, _geometry, _sources, _stage_sets, _table
     x = torch.tensor(_sources(), device=DEV)
     arena, table = _table()

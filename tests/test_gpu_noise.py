@@ -235,7 +235,8 @@ def test_the_chain_has_no_size_rule_of_its_own():
 @pytest.mark.parametrize("geometry", ["stretch", "window", "letterbox"])
 def test_a_null_table_is_the_tone_form_bit_for_bit(geometry):
     from structuredetector_amd.data import blur_box_params, preprocess_image_list, preprocess_images
-    from structuredetector_amd.data.augment import _MEAN, _STD, _preprocess_blur
+    from structuredetector_amd.data.augment import _MEAN, _STD
+    from tests.helpers import call_legacy_preprocess_form as _preprocess_blur
     from tests.test_gpu_blur import NB, OUT, RADII, SRC, _geometry, _sources, _stage_sets, _table
     x = torch.tensor(_sources(), device=DEV)
     arena, table = _table()

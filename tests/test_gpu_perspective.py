@@ -202,7 +202,8 @@ def test_chain_forms_equal_the_hand_composition_on_pil_images(geometry, src, siz
 @pytest.mark.parametrize("geometry", ["stretch", "window", "letterbox"])
 def test_a_null_table_is_the_blur_form_bit_for_bit(geometry):
     from structuredetector_amd.data import blur_box_params, preprocess_images
-    from structuredetector_amd.data.augment import _MEAN, _STD, _preprocess_blur, affine_inverse_matrix
+    from structuredetector_amd.data.augment import _MEAN, _STD, affine_inverse_matrix
+    from tests.helpers import call_legacy_preprocess_form as _preprocess_blur
     src, size = (33, 47), (70, 33)
     imgs = np.random.default_rng(3).integers(0, 256, (B, src[0], src[1], 3), dtype=np.uint8)
     x = torch.tensor(imgs, device=DEV)
