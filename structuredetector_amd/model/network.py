@@ -20,6 +20,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import warnings
+from typing import NamedTuple
 
 import torch
 import torch.nn as nn
@@ -135,9 +136,42 @@ def _ptr(t):
     return 0 if t is None else t.data_ptr()
 
 
+def _flops(d):
+    return 2.0 * d.B * d.Ho * d.Wo * d.Cout * d.Cin * d.R * d.S
+
+
+# ReLU-mask mode of the BatchNorm backward kernels: no ReLU / mask from the saved output y / mask recomputed from x / y holds the
+# mask bytes of sd_bn_apply (residual layers)
+RELU_NONE, RELU_FROM_Y, RELU_FROM_X, RELU_MASK_BYTES = 0, 1, 2, 3
+
+
+def _mask_ptr(y, relu):
+    """the `y` pointer a ReLU-mask mode reads (the other two modes take none)"""
+    return _ptr(y) if relu in (RELU_FROM_Y, RELU_MASK_BYTES) else 0
+
+
+# what the training forward leaves on the tape for the backward; positional order is part of the contract (tests unpack them)
+class StemRec(NamedTuple):
+    d: object; s0: object; mean: object; invstd: object; pidx: object
+
+
+class BlockRec(NamedTuple):
+    blk: object; xin: object; hw: tuple; d1: object; c1: object; a1: object; m1: object; i1: object; d2: object; c2: object; m2: object
+    i2: object; out: object; dd: object; cd: object; md: object; idd: object; mask: object
+
+
+class FpnRec(NamedTuple):
+    fpn: object; shortcut: object; hw: tuple; dl: object; t: object; dc: object; c: object; mean: object; invstd: object; out: object
+
+
+class LateralGrad(NamedTuple):
+    """deferred data-gradient of an FPN lateral 1x1: joins the trunk's own gradient of the same tensor"""
+    dy: object; conv: object; d: object
+
+
 class _Engine:
     """Explicit forward / backward schedules over the C ABI.  Tensors named *_nhwc are
-    (B, H, W, C) contiguous; `tape` keeps what the backward needs."""
+    (B, H, W, C) contiguous; `tape` keeps what the backward needs (StemRec, BlockRec and FpnRec records)."""
 
     def __init__(self, net: "Network"):
         self.net = net
@@ -164,26 +198,41 @@ class _Engine:
         self.fuse_head = True              # bf16 inference: the 1x1 head in the epilogue of the last FPN conv where it takes the two-group kernel (False: A/B, tests)
         self.small_batch_kernel = True     # eval forward: sd_conv2d_fwd_sb where the 128-row tile grid cannot fill the chip (False: A/B)
 
-    def _kname(self, d, which):
-        """device kernel the C ABI will launch for this conv (profiling label; same names as the rocprofv3 kernel trace)"""
+    def _tic(self, d, which, bf16=False, name=None):
+        """Opens the `prof` record of a conv launch (None while `prof` is off).  The label is the device kernel the C ABI will launch
+        for pass `which` of this conv (same names as the rocprofv3 kernel trace), or `name` where the caller knows it."""
         if self.prof is None:
-            return ""
-        if self.prof_shapes is not None:
-            self.prof_shapes.append((d.B, d.Hi, d.Wi, d.Cin, d.Cout, d.R, d.stride, d.Ho, d.Wo))
-        return self.lib.sd_conv2d_kernel_name(C.byref(d), which).decode()
-
-    def _timed(self, kind, flops, fn, phase="fwd"):
-        if self.prof is None:
-            return fn()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            return None
+        if name is None:
+            if self.prof_shapes is not None:
+                self.prof_shapes.append((d.B, d.Hi, d.Wi, d.Cin, d.Cout, d.R, d.stride, d.Ho, d.Wo))
+            name = self.lib.sd_conv2d_kernel_name(C.byref(d), which).decode()
+        e0 = torch.cuda.Event(enable_timing=True)
         e0.record()           # torch's current stream == the stream handed to the C ABI (L.stream())
-        fn()
-        e1.record()
-        self.prof.append((kind, flops, e0, e1, phase))
+        return ("bf16:" + name if bf16 else name), e0
+
+    def _toc(self, t, d, phase="fwd"):
+        if t is not None:
+            e1 = torch.cuda.Event(enable_timing=True)
+            e1.record()
+            self.prof.append((t[0], _flops(d), t[1], e1, phase))
 
     # ---- helpers -------------------------------------------------------------------------
     def _ws(self, nbytes, dev):
         return L.workspace(max(int(nbytes), 256), dev)
+
+    def _fn(self, name, bf16):
+        """the fp32 / bf16 pair of an entry point: the bf16 one carries the suffix"""
+        return getattr(self.lib, name + "_bf16" if bf16 else name)
+
+    @staticmethod
+    def _running(bn, update):
+        """running-statistics pointer pair of a statistics launch (0, 0: leave them alone)"""
+        return (bn.running_mean.data_ptr(), bn.running_var.data_ptr()) if update else (0, 0)
+
+    @staticmethod
+    def _w32(conv):
+        return conv.weight
 
     # ---- mixed precision (`--amp`, trainer.py:115-121): bf16 activations / conv weights, fp32 accumulation and master weights ----
     def _to_bf16(self, t):
@@ -208,89 +257,70 @@ class _Engine:
         off, n = self.net._flat_off[id(conv.weight)]
         return self.net.flat_params_bf16[off:off + n]                 # physical [Cout][R][S][Cin] order; off % 8 == 0 (32-byte slots): 16-byte aligned
 
-    def _conv_sb(self, x, w, y, d, scale, shift, res, res_up2, relu, bf16):
-        """Small-batch inference conv: one launch, split-K combined inside it (sd_conv2d_fwd_sb); the arrival tickets live in a
-        zeroed per-stream state buffer that every launch leaves zero."""
-        nws = self.lib.sd_conv2d_fwd_sb_workspace_bytes(C.byref(d), bf16)
-        ws = self._ws(nws, x.device) if nws else None
-        st = L.zero_state(self.lib.sd_conv2d_fwd_sb_state_bytes(C.byref(d), bf16), x.device) if nws else None
-        L.check(self.lib.sd_conv2d_fwd_sb(x.data_ptr(), w.data_ptr(), y.data_ptr(), C.byref(d), _ptr(scale), _ptr(shift), _ptr(res), int(res_up2),
-                                          int(relu), bf16, _ptr(ws), ws.numel() if nws else 0, _ptr(st), st.numel() if nws else 0, L.stream()),
-                "sd_conv2d_fwd_sb")
-
-    def conv(self, x, conv, B, Hi, Wi, scale=None, shift=None, res=None, res_up2=False, relu=False, amp=False, sb=False):
+    def conv(self, how, x, conv, B, Hi, Wi, scale=None, shift=None, res=None, res_up2=False, relu=False):
+        """The conv forward launch of every schedule.  how = (weight source, entry point, its workspace query or None: no split-K
+        workspace, kernel-name pass 0 = fp32 / 16 = bf16, try the small-batch kernel first, give the launch a `prof` record).
+        Small-batch kernel (sd_conv2d_fwd_sb): one launch, split-K combined inside it; the arrival tickets live in a zeroed per-stream
+        state buffer that every launch leaves zero."""
+        weight, fwd, ws_bytes, which, sb, timed = how
+        lib, bf16 = self.lib, int(which == 16)
         d = _desc(B, Hi, Wi, conv)
-        if amp:
-            y = torch.empty((B, d.Ho, d.Wo, conv.cout), dtype=torch.bfloat16, device=x.device)
-            flops = 2.0 * B * d.Ho * d.Wo * conv.cout * conv.cin * conv.k * conv.k
-            self._timed("bf16:" + self._kname(d, 16), flops, lambda: L.check(
-                self.lib.sd_conv2d_fwd_bf16(x.data_ptr(), self._w16(conv).data_ptr(), y.data_ptr(), C.byref(d), _ptr(scale), _ptr(shift),
-                                            _ptr(res), int(res_up2), int(relu), 0, 0, L.stream()), "sd_conv2d_fwd_bf16"))
-            return y, d
-        y = torch.empty((B, d.Ho, d.Wo, conv.cout), dtype=torch.float32, device=x.device)
-        flops = 2.0 * B * d.Ho * d.Wo * conv.cout * conv.cin * conv.k * conv.k
-        if sb and self.small_batch_kernel and self.lib.sd_conv2d_fwd_sb_supported(C.byref(d), 0):
-            self._timed("k_conv_fwd_sb<false>" if self.prof is not None else "", flops,
-                        lambda: self._conv_sb(x, conv.weight, y, d, scale, shift, res, res_up2, relu, 0))
-            return y, d
-        nws = self.lib.sd_conv2d_fwd_workspace_bytes(C.byref(d))          # > 0 only for small batches (split-K)
-        ws = self._ws(nws, x.device) if nws else None
-        self._timed(self._kname(d, 0), flops, lambda: L.check(
-            self.lib.sd_conv2d_fwd(x.data_ptr(), conv.weight.data_ptr(), y.data_ptr(), C.byref(d), _ptr(scale), _ptr(shift),
-                                   _ptr(res), int(res_up2), int(relu), _ptr(ws), ws.numel() if nws else 0, L.stream()),
-            "sd_conv2d_fwd"))
+        y = torch.empty((B, d.Ho, d.Wo, conv.cout), dtype=torch.bfloat16 if bf16 else torch.float32, device=x.device)
+        if sb and self.small_batch_kernel and lib.sd_conv2d_fwd_sb_supported(C.byref(d), bf16):
+            w = weight(conv)
+            nws = lib.sd_conv2d_fwd_sb_workspace_bytes(C.byref(d), bf16)
+            ws = self._ws(nws, x.device) if nws else None
+            st = L.zero_state(lib.sd_conv2d_fwd_sb_state_bytes(C.byref(d), bf16), x.device) if nws else None
+            t = self._tic(d, which, name="k_conv_fwd_sb<false>") if timed else None          # (only fp32 schedules are timed)
+            L.check(lib.sd_conv2d_fwd_sb(x.data_ptr(), w.data_ptr(), y.data_ptr(), C.byref(d), _ptr(scale), _ptr(shift), _ptr(res), int(res_up2),
+                                         int(relu), bf16, _ptr(ws), ws.numel() if nws else 0, _ptr(st), st.numel() if nws else 0, L.stream()),
+                    "sd_conv2d_fwd_sb")
+        else:
+            nws = ws_bytes(C.byref(d)) if ws_bytes is not None else 0          # > 0 only for small batches (split-K)
+            ws = self._ws(nws, x.device) if nws else None
+            w = weight(conv)
+            t = self._tic(d, which, bf16) if timed else None
+            L.check(fwd(x.data_ptr(), w.data_ptr(), y.data_ptr(), C.byref(d), _ptr(scale), _ptr(shift), _ptr(res), int(res_up2), int(relu),
+                        _ptr(ws), ws.numel() if nws else 0, L.stream()), "sd_conv2d_fwd")
+        if t is not None:
+            self._toc(t, d)
         return y, d
 
     def conv_stats(self, x, conv, B, Hi, Wi, bn: BNParams, update_running=True, amp=False, sync=None):
         """Training forward of conv -> BatchNorm: the conv launch also produces the batch statistics of its output
         (sd_conv2d_fwd_bn_stats), so bn_train(..., stats=...) only has the apply pass left.  `sync` (a BnStatsExchange): the same
         launch stops after the first half of the statistics finish, the fp64 sums are exchanged, the second half finishes."""
+        lib = self.lib
         d = _desc(B, Hi, Wi, conv)
         y = torch.empty((B, d.Ho, d.Wo, conv.cout), dtype=torch.bfloat16 if amp else torch.float32, device=x.device)
         mean = torch.empty(conv.cout, dtype=torch.float32, device=x.device)
         invstd = torch.empty_like(mean)
-        flops = 2.0 * B * d.Ho * d.Wo * conv.cout * conv.cin * conv.k * conv.k
         if sync is not None:
             sums = sync.take(conv.cout)
             if sync.log is not None:
-                fused = self.lib.sd_conv2d_fwd_bn_stats_rows(C.byref(d), int(amp)) > 0
+                fused = lib.sd_conv2d_fwd_bn_stats_rows(C.byref(d), int(amp)) > 0
                 sync.log.append(("sd_conv2d_fwd_bf16_bn_sums" if amp else "sd_conv2d_fwd_bn_sums") + ("" if fused else ":two-pass"))
-            if amp:
-                ws = self._ws(self.lib.sd_conv2d_fwd_bf16_bn_stats_workspace_bytes(C.byref(d)), x.device)
-                self._timed("bf16:" + self._kname(d, 16), flops, lambda: L.check(
-                    self.lib.sd_conv2d_fwd_bf16_bn_sums(x.data_ptr(), self._w16(conv).data_ptr(), y.data_ptr(), C.byref(d), sums.data_ptr(),
-                                                        ws.data_ptr(), ws.numel(), L.stream()), "sd_conv2d_fwd_bf16_bn_sums"))
-            else:
-                ws = self._ws(self.lib.sd_conv2d_fwd_bn_stats_workspace_bytes(C.byref(d)), x.device)
-                self._timed(self._kname(d, 0), flops, lambda: L.check(
-                    self.lib.sd_conv2d_fwd_bn_sums(x.data_ptr(), conv.weight.data_ptr(), y.data_ptr(), C.byref(d), sums.data_ptr(),
-                                                   ws.data_ptr(), ws.numel(), L.stream()), "sd_conv2d_fwd_bn_sums"))
-            self._stats_from_sums(sync, sums, bn, mean, invstd, update_running)
-            return y, d, (mean, invstd)
+            tail = (sums.data_ptr(),)
+        else:
+            tail = (BN_EPS, BN_MOMENTUM, *self._running(bn, update_running), mean.data_ptr(), invstd.data_ptr())
         if amp:
-            ws = self._ws(self.lib.sd_conv2d_fwd_bf16_bn_stats_workspace_bytes(C.byref(d)), x.device)
-            self._timed("bf16:" + self._kname(d, 16), flops, lambda: L.check(
-                self.lib.sd_conv2d_fwd_bf16_bn_stats(x.data_ptr(), self._w16(conv).data_ptr(), y.data_ptr(), C.byref(d), BN_EPS, BN_MOMENTUM,
-                                                     bn.running_mean.data_ptr() if update_running else 0,
-                                                     bn.running_var.data_ptr() if update_running else 0,
-                                                     mean.data_ptr(), invstd.data_ptr(), ws.data_ptr(), ws.numel(), L.stream()),
-                "sd_conv2d_fwd_bf16_bn_stats"))
-            return y, d, (mean, invstd)
-        ws = self._ws(self.lib.sd_conv2d_fwd_bn_stats_workspace_bytes(C.byref(d)), x.device)
-        self._timed(self._kname(d, 0), flops, lambda: L.check(
-            self.lib.sd_conv2d_fwd_bn_stats(x.data_ptr(), conv.weight.data_ptr(), y.data_ptr(), C.byref(d), BN_EPS, BN_MOMENTUM,
-                                            bn.running_mean.data_ptr() if update_running else 0,
-                                            bn.running_var.data_ptr() if update_running else 0,
-                                            mean.data_ptr(), invstd.data_ptr(), ws.data_ptr(), ws.numel(), L.stream()),
-            "sd_conv2d_fwd_bn_stats"))
+            fwd = lib.sd_conv2d_fwd_bf16_bn_stats if sync is None else lib.sd_conv2d_fwd_bf16_bn_sums
+            w, ws_bytes = self._w16(conv), lib.sd_conv2d_fwd_bf16_bn_stats_workspace_bytes
+        else:
+            fwd = lib.sd_conv2d_fwd_bn_stats if sync is None else lib.sd_conv2d_fwd_bn_sums
+            w, ws_bytes = conv.weight, lib.sd_conv2d_fwd_bn_stats_workspace_bytes
+        ws = self._ws(ws_bytes(C.byref(d)), x.device)
+        t = self._tic(d, 16 if amp else 0, amp)
+        L.check(fwd(x.data_ptr(), w.data_ptr(), y.data_ptr(), C.byref(d), *tail, ws.data_ptr(), ws.numel(), L.stream()), "sd_conv2d_fwd_bn_stats")
+        self._toc(t, d)
+        if sync is not None:
+            self._stats_from_sums(sync, sums, bn, mean, invstd, update_running)
         return y, d, (mean, invstd)
 
     def _stats_from_sums(self, sync, sums, bn: BNParams, mean, invstd, update_running=True):
         """Synchronized BatchNorm, forward: all-reduce the layer's fp64 [S0, S1, n], then mean / invstd / running statistics from it."""
         sync.reduce(sums)
-        L.check(self.lib.sd_bn_stats_from_sums(sums.data_ptr(), bn.c, BN_EPS, BN_MOMENTUM,
-                                               bn.running_mean.data_ptr() if update_running else 0,
-                                               bn.running_var.data_ptr() if update_running else 0,
+        L.check(self.lib.sd_bn_stats_from_sums(sums.data_ptr(), bn.c, BN_EPS, BN_MOMENTUM, *self._running(bn, update_running),
                                                mean.data_ptr(), invstd.data_ptr(), L.stream()), "sd_bn_stats_from_sums")
 
     def _means_from_sums(self, sync, sums, Cc, device):
@@ -302,31 +332,27 @@ class _Engine:
 
     def bn_train(self, x, bn: BNParams, res=None, relu=True, update_running=True, stats=None, want_mask=False, sync=None):
         Mrows, Cc = x.numel() // x.shape[-1], x.shape[-1]
+        bf16 = x.dtype == torch.bfloat16
         if stats is not None:
             mean, invstd = stats
-        elif sync is not None:
-            mean = torch.empty(Cc, dtype=torch.float32, device=x.device)
-            invstd = torch.empty_like(mean)
-            sums = sync.take(Cc)
-            sync.record("sd_bn_train_sums")
-            ws = self._ws(self.lib.sd_col_reduce_workspace_bytes(Mrows, Cc), x.device)
-            train_sums = self.lib.sd_bn_train_sums_bf16 if x.dtype == torch.bfloat16 else self.lib.sd_bn_train_sums
-            L.check(train_sums(x.data_ptr(), Mrows, Cc, sums.data_ptr(), ws.data_ptr(), ws.numel(), L.stream()), "sd_bn_train_sums")
-            self._stats_from_sums(sync, sums, bn, mean, invstd, update_running)
         else:
             mean = torch.empty(Cc, dtype=torch.float32, device=x.device)
             invstd = torch.empty_like(mean)
             ws = self._ws(self.lib.sd_col_reduce_workspace_bytes(Mrows, Cc), x.device)
-            L.check(self.lib.sd_bn_train_stats(x.data_ptr(), Mrows, Cc, BN_EPS, BN_MOMENTUM,
-                                               bn.running_mean.data_ptr() if update_running else 0,
-                                               bn.running_var.data_ptr() if update_running else 0,
-                                               mean.data_ptr(), invstd.data_ptr(), ws.data_ptr(), ws.numel(), L.stream()), "sd_bn_train_stats")
+            if sync is not None:
+                sums = sync.take(Cc)
+                sync.record("sd_bn_train_sums")
+                L.check(self._fn("sd_bn_train_sums", bf16)(x.data_ptr(), Mrows, Cc, sums.data_ptr(), ws.data_ptr(), ws.numel(), L.stream()),
+                        "sd_bn_train_sums")
+                self._stats_from_sums(sync, sums, bn, mean, invstd, update_running)
+            else:
+                L.check(self.lib.sd_bn_train_stats(x.data_ptr(), Mrows, Cc, BN_EPS, BN_MOMENTUM, *self._running(bn, update_running),
+                                                   mean.data_ptr(), invstd.data_ptr(), ws.data_ptr(), ws.numel(), L.stream()), "sd_bn_train_stats")
         y = torch.empty_like(x)
         # residual layers: the backward needs the ReLU mask of y; one byte per four elements instead of re-reading y twice
         mask = torch.empty(x.numel() // 4, dtype=torch.uint8, device=x.device) if want_mask else None
-        apply = self.lib.sd_bn_apply_bf16 if x.dtype == torch.bfloat16 else self.lib.sd_bn_apply
-        L.check(apply(x.data_ptr(), y.data_ptr(), Mrows, Cc, mean.data_ptr(), invstd.data_ptr(), bn.weight.data_ptr(),
-                      bn.bias.data_ptr(), _ptr(res), int(relu), _ptr(mask), L.stream()), "sd_bn_apply")
+        L.check(self._fn("sd_bn_apply", bf16)(x.data_ptr(), y.data_ptr(), Mrows, Cc, mean.data_ptr(), invstd.data_ptr(), bn.weight.data_ptr(),
+                                              bn.bias.data_ptr(), _ptr(res), int(relu), _ptr(mask), L.stream()), "sd_bn_apply")
         if update_running:
             self._nbt.append(bn.num_batches_tracked)
         return (y, mean, invstd, mask) if want_mask else (y, mean, invstd)
@@ -343,12 +369,8 @@ class _Engine:
         return scale, shift
 
     # ---- forward -------------------------------------------------------------------------
-    def forward(self, x, training, tape=None, amp=False):
-        net, lib = self.net, self.lib
-        if amp:
-            if not training:
-                raise L.SdError("amp=True is the mixed-precision TRAINING forward; inference uses forward_bf16")
-            self.refresh_bf16_weights()
+    @staticmethod
+    def _input(x):
         if x.dim() != 4 or x.shape[1] != 3:
             raise L.SdError(f"Network expects (B, 3, H, W) input, got {tuple(x.shape)}")
         L.require_cuda(x)
@@ -356,89 +378,79 @@ class _Engine:
         B, _, H, W = x.shape
         if H % 32 or W % 32:
             raise L.SdError("input height/width must be multiples of 32 (args.py:181-186)")
+        return x, B, H, W
+
+    def forward(self, x, training, tape=None, amp=False):
+        """training=False: the fp32 eval schedule (_eval).  training=True: the training forward, recording `tape` for backward();
+        amp: the mixed-precision step."""
+        if not training:
+            if amp:
+                raise L.SdError("amp=True is the mixed-precision TRAINING forward; inference uses forward_bf16")
+            return self._eval(x, False)
+        net, lib = self.net, self.lib
+        if amp:
+            self.refresh_bf16_weights()
+        x, B, H, W = self._input(x)
         rec = tape is not None
         # synchronized BatchNorm (TrainStep(sync_bn=True)): every batch-statistics finish goes through the exchange on the tape
-        sx = tape.get("bn_sync") if (rec and training) else None
+        sx = tape.get("bn_sync") if rec else None
         if sx is not None:
             sx.begin("fwd")
+        how = (self._w16, lib.sd_conv2d_fwd_bf16, None, 16, False, True) if amp \
+            else (self._w32, lib.sd_conv2d_fwd, lib.sd_conv2d_fwd_workspace_bytes, 0, False, True)
+        act = torch.bfloat16 if amp else torch.float32
 
         # stem: conv7x7/2 + BN + ReLU + maxpool3x3/2 (network.py:43-45)
         T.push("fwd:stem")
         stem, bn0 = net.adpater[0], net.adpater[1]
         d0 = _desc(B, H, W, stem)
-        # mixed precision: the stem's conv output and pooled map are bf16 too (even maps: the quad form of the tail's backward); BatchNorm
-        # statistics / arithmetic stay fp32
-        amp_stem = bool(amp and training and d0.Ho % 2 == 0 and d0.Wo % 2 == 0)
-        s0 = torch.empty((B, d0.Ho, d0.Wo, 64), dtype=torch.bfloat16 if amp_stem else torch.float32, device=x.device)
-        wss = self._ws(lib.sd_conv2d_stem_fwd_workspace_bytes(C.byref(d0)), x.device)
+        # mixed precision: the stem's conv output and pooled map are bf16 too (H % 32 == 0 makes the stem map even: the quad form of the
+        # tail's backward always applies); BatchNorm statistics / arithmetic stay fp32
+        s0 = torch.empty((B, d0.Ho, d0.Wo, 64), dtype=act, device=x.device)
+        self._ws(lib.sd_conv2d_stem_fwd_workspace_bytes(C.byref(d0)), x.device)         # the shared workspace is at least the eval stem's
         Hp, Wp = (d0.Ho + 2 - 3) // 2 + 1, (d0.Wo + 2 - 3) // 2 + 1
-        p1 = torch.empty((B, Hp, Wp, 64), dtype=torch.bfloat16 if amp_stem else torch.float32, device=x.device)
+        p1 = torch.empty((B, Hp, Wp, 64), dtype=act, device=x.device)
         pidx = torch.empty((B, Hp, Wp, 64), dtype=torch.uint8, device=x.device)
-        if training:
-            # BatchNorm + ReLU + max-pool in one pass over the conv output: the full-resolution activation (1 GB at bs=64,
-            # 512x512) is neither written nor read back; the backward recomputes what it needs from s0 and the pool indices
-            m0 = torch.empty(64, dtype=torch.float32, device=x.device)
-            i0 = torch.empty_like(m0)
-            ws = self._ws(lib.sd_conv2d_stem_fwd_bn_stats_workspace_bytes(C.byref(d0)), x.device)
-            if sx is None:
-                stem_fwd = (lib.sd_conv2d_stem_fwd_bn_stats_bf16 if amp_stem else lib.sd_conv2d_stem_fwd_bn_stats_bf16mm) if amp \
-                    else lib.sd_conv2d_stem_fwd_bn_stats                                                           # amp: product on the bf16 MFMA
-                L.check(stem_fwd(x.data_ptr(), stem.weight.data_ptr(), s0.data_ptr(), C.byref(d0), BN_EPS, BN_MOMENTUM,
-                                 bn0.running_mean.data_ptr(), bn0.running_var.data_ptr(), m0.data_ptr(), i0.data_ptr(),
-                                 ws.data_ptr(), ws.numel(), L.stream()), "sd_conv2d_stem_fwd_bn_stats")
-            else:
-                sums = sx.take(64)
-                stem_sums = (lib.sd_conv2d_stem_fwd_bn_sums_bf16 if amp_stem else lib.sd_conv2d_stem_fwd_bn_sums_bf16mm) if amp \
-                    else lib.sd_conv2d_stem_fwd_bn_sums
-                sx.record("sd_conv2d_stem_fwd_bn_sums")
-                L.check(stem_sums(x.data_ptr(), stem.weight.data_ptr(), s0.data_ptr(), C.byref(d0), sums.data_ptr(), ws.data_ptr(), ws.numel(),
-                                  L.stream()), "sd_conv2d_stem_fwd_bn_sums")
-                self._stats_from_sums(sx, sums, bn0, m0, i0)
-            self._nbt.append(bn0.num_batches_tracked)
-            pool_fwd = lib.sd_bn_relu_maxpool_fwd_bf16 if amp_stem else lib.sd_bn_relu_maxpool_fwd
-            L.check(pool_fwd(s0.data_ptr(), B, d0.Ho, d0.Wo, 64, m0.data_ptr(), i0.data_ptr(), bn0.weight.data_ptr(),
-                             bn0.bias.data_ptr(), p1.data_ptr(), pidx.data_ptr(), L.stream()), "sd_bn_relu_maxpool_fwd")
+        # BatchNorm + ReLU + max-pool in one pass over the conv output: the full-resolution activation (1 GB at bs=64,
+        # 512x512) is neither written nor read back; the backward recomputes what it needs from s0 and the pool indices
+        m0 = torch.empty(64, dtype=torch.float32, device=x.device)
+        i0 = torch.empty_like(m0)
+        ws = self._ws(lib.sd_conv2d_stem_fwd_bn_stats_workspace_bytes(C.byref(d0)), x.device)
+        if sx is None:                                                            # amp: product on the bf16 MFMA
+            L.check(self._fn("sd_conv2d_stem_fwd_bn_stats", amp)(
+                x.data_ptr(), stem.weight.data_ptr(), s0.data_ptr(), C.byref(d0), BN_EPS, BN_MOMENTUM, *self._running(bn0, True),
+                m0.data_ptr(), i0.data_ptr(), ws.data_ptr(), ws.numel(), L.stream()), "sd_conv2d_stem_fwd_bn_stats")
         else:
-            sc, sh = self.bn_fold(bn0)
-            L.check(lib.sd_conv2d_stem_fwd(x.data_ptr(), stem.weight.data_ptr(), s0.data_ptr(), C.byref(d0), sc.data_ptr(), sh.data_ptr(), 1, 0,
-                                           wss.data_ptr(), wss.numel(), L.stream()), "stem")
-            m0 = i0 = None
-            L.check(lib.sd_maxpool3x3s2_fwd(s0.data_ptr(), p1.data_ptr(), pidx.data_ptr(), B, d0.Ho, d0.Wo, 64, L.stream()), "maxpool")
+            sums = sx.take(64)
+            sx.record("sd_conv2d_stem_fwd_bn_sums")
+            L.check(self._fn("sd_conv2d_stem_fwd_bn_sums", amp)(x.data_ptr(), stem.weight.data_ptr(), s0.data_ptr(), C.byref(d0), sums.data_ptr(),
+                                                                ws.data_ptr(), ws.numel(), L.stream()), "sd_conv2d_stem_fwd_bn_sums")
+            self._stats_from_sums(sx, sums, bn0, m0, i0)
+        self._nbt.append(bn0.num_batches_tracked)
+        L.check(self._fn("sd_bn_relu_maxpool_fwd", amp)(s0.data_ptr(), B, d0.Ho, d0.Wo, 64, m0.data_ptr(), i0.data_ptr(), bn0.weight.data_ptr(),
+                                                        bn0.bias.data_ptr(), p1.data_ptr(), pidx.data_ptr(), L.stream()), "sd_bn_relu_maxpool_fwd")
         if rec:
-            tape["x"], tape["stem"], tape["amp"] = x, (d0, s0, m0, i0, pidx), bool(amp)
-        if amp and not amp_stem:
-            p1 = self._to_bf16(p1)          # (odd maps: fp32 stem tail) everything behind the max-pool is bf16
-
+            tape["x"], tape["stem"], tape["amp"] = x, StemRec(d0, s0, m0, i0, pidx), bool(amp)
         T.pop()
+
         # trunk (network.py:47-50)
         feats, cur, Hc, Wc = [], p1, Hp, Wp
         blocks_tape = []
         for li, layer in enumerate((net.down1, net.down2, net.down3, net.down4), start=1):
             T.push(f"fwd:down{li}")
             for blk in layer:
-                if training:
-                    c1, d1, st1 = self.conv_stats(cur, blk.conv1, B, Hc, Wc, blk.bn1, amp=amp, sync=sx)
-                    a1, m1, i1 = self.bn_train(c1, blk.bn1, stats=st1)
-                    c2, d2, st2 = self.conv_stats(a1, blk.conv2, B, d1.Ho, d1.Wo, blk.bn2, amp=amp, sync=sx)
-                    if blk.downsample is not None:
-                        cd, dd, std_ = self.conv_stats(cur, blk.downsample[0], B, Hc, Wc, blk.downsample[1], amp=amp, sync=sx)
-                        idt, md, idd = self.bn_train(cd, blk.downsample[1], relu=False, stats=std_)
-                    else:
-                        cd = dd = md = idd = None
-                        idt = cur
-                    out, m2, i2, msk = self.bn_train(c2, blk.bn2, res=idt, relu=True, stats=st2, want_mask=True)
-                    if rec:
-                        blocks_tape.append((blk, cur, (Hc, Wc), d1, c1, a1, m1, i1, d2, c2, m2, i2, out, dd, cd, md, idd, msk))
+                c1, d1, st1 = self.conv_stats(cur, blk.conv1, B, Hc, Wc, blk.bn1, amp=amp, sync=sx)
+                a1, m1, i1 = self.bn_train(c1, blk.bn1, stats=st1)
+                c2, d2, st2 = self.conv_stats(a1, blk.conv2, B, d1.Ho, d1.Wo, blk.bn2, amp=amp, sync=sx)
+                if blk.downsample is not None:
+                    cd, dd, std_ = self.conv_stats(cur, blk.downsample[0], B, Hc, Wc, blk.downsample[1], amp=amp, sync=sx)
+                    idt, md, idd = self.bn_train(cd, blk.downsample[1], relu=False, stats=std_)
                 else:
-                    s1, h1 = self.bn_fold(blk.bn1)
-                    a1, d1 = self.conv(cur, blk.conv1, B, Hc, Wc, scale=s1, shift=h1, relu=True, sb=True)
-                    if blk.downsample is not None:
-                        sd_, hd = self.bn_fold(blk.downsample[1])
-                        idt, _ = self.conv(cur, blk.downsample[0], B, Hc, Wc, scale=sd_, shift=hd, sb=True)
-                    else:
-                        idt = cur
-                    s2, h2 = self.bn_fold(blk.bn2)
-                    out, _ = self.conv(a1, blk.conv2, B, d1.Ho, d1.Wo, scale=s2, shift=h2, res=idt, relu=True, sb=True)
+                    cd = dd = md = idd = None
+                    idt = cur
+                out, m2, i2, msk = self.bn_train(c2, blk.bn2, res=idt, relu=True, stats=st2, want_mask=True)
+                if rec:
+                    blocks_tape.append(BlockRec(blk, cur, (Hc, Wc), d1, c1, a1, m1, i1, d2, c2, m2, i2, out, dd, cd, md, idd, msk))
                 cur, Hc, Wc = out, d1.Ho, d1.Wo
             feats.append((cur, Hc, Wc))
             T.pop()
@@ -446,34 +458,117 @@ class _Engine:
 
         # FPN (network.py:52-55,6-19): lateral 1x1 (+bias) with the x2-upsampled coarser map added in the epilogue
         T.push("fwd:fpn")
-        f, _ = self.conv(p5, net.up1, B, H5, W5, shift=net.up1.bias, amp=amp, sb=not training)
+        f, _ = self.conv(how, p5, net.up1, B, H5, W5, shift=net.up1.bias)
         fpn_tape = []
         for fpn, (sc_t, Hs, Ws) in ((net.up2, (p4, H4, W4)), (net.up3, (p3, H3, W3)), (net.up4, (p2, H2, W2))):
-            t, dl = self.conv(sc_t, fpn.lateral, B, Hs, Ws, shift=fpn.lateral.bias, res=f, res_up2=True, amp=amp, sb=not training)
-            if training:
-                c, dc, stf = self.conv_stats(t, fpn.conv[0], B, Hs, Ws, fpn.conv[1], amp=amp, sync=sx)
-                fn, mf, if_ = self.bn_train(c, fpn.conv[1], stats=stf)
-                if rec:
-                    fpn_tape.append((fpn, sc_t, (Hs, Ws), dl, t, dc, c, mf, if_, fn))
-            else:
-                sf, hf = self.bn_fold(fpn.conv[1])
-                fn, _ = self.conv(t, fpn.conv[0], B, Hs, Ws, scale=sf, shift=hf, relu=True, sb=True)
-            f = fn
+            t, dl = self.conv(how, sc_t, fpn.lateral, B, Hs, Ws, shift=fpn.lateral.bias, res=f, res_up2=True)
+            c, dc, stf = self.conv_stats(t, fpn.conv[0], B, Hs, Ws, fpn.conv[1], amp=amp, sync=sx)
+            f, mf, if_ = self.bn_train(c, fpn.conv[1], stats=stf)
+            if rec:
+                fpn_tape.append(FpnRec(fpn, sc_t, (Hs, Ws), dl, t, dc, c, mf, if_, f))
         T.pop()
 
-        # head (network.py:57): NHWC -> NCHW
+        # head (network.py:57): NHWC -> NCHW (the head's output and the loss stay fp32)
         T.push("fwd:head")
         hc = net.head.conv
         out = torch.empty((B, hc.cout, H2, W2), dtype=torch.float32, device=x.device)
-        head_fwd = lib.sd_head_fwd_bf16 if amp else lib.sd_head_fwd       # (the head's output and the loss stay fp32)
-        L.check(head_fwd(f.data_ptr(), hc.weight.data_ptr(), hc.bias.data_ptr(), out.data_ptr(), B, H2 * W2, hc.cin, hc.cout,
-                         L.stream()), "sd_head_fwd")
+        L.check(self._fn("sd_head_fwd", amp)(f.data_ptr(), hc.weight.data_ptr(), hc.bias.data_ptr(), out.data_ptr(), B, H2 * W2, hc.cin, hc.cout,
+                                             L.stream()), "sd_head_fwd")
         T.pop()
         if rec:
             tape.update(blocks=blocks_tape, fpn=fpn_tape, p5=(p5, H5, W5), f1=f, B=B, hw=(H2, W2))
-        if self._nbt:
-            torch._foreach_add_(self._nbt, 1)
-            self._nbt = []
+        torch._foreach_add_(self._nbt, 1)
+        self._nbt = []
+        return out
+
+    def forward_bf16(self, x):
+        """Eval-mode forward with bf16 activations / weights and fp32 accumulation; BN folded into fp32 epilogues.
+        The stem reads the fp32 image with fp32 weights and stores bf16; the head returns fp32 NCHW."""
+        return self._eval(x, True)
+
+    def _eval(self, x, bf16):
+        """The eval schedule, fp32 or with a bf16 backbone (BASELINE stress config: "bf16 backbone + fp32 decode"): BatchNorm folded
+        into the conv epilogues.  bf16 only: stem + max-pool in one launch, the head in the epilogue of the last FPN conv."""
+        net, lib = self.net, self.lib
+        x, B, H, W = self._input(x)
+        how = (self._w_bf16, lib.sd_conv2d_fwd_bf16, lib.sd_conv2d_fwd_bf16_workspace_bytes, 16, True, False) if bf16 \
+            else (self._w32, lib.sd_conv2d_fwd, lib.sd_conv2d_fwd_workspace_bytes, 0, True, True)
+        act = torch.bfloat16 if bf16 else torch.float32
+
+        # stem: conv7x7/2 + BN + ReLU + maxpool3x3/2 (network.py:43-45)
+        T.push("fwd:stem")
+        stem, bn0 = net.adpater[0], net.adpater[1]
+        d0 = _desc(B, H, W, stem)
+        Hc, Wc = (d0.Ho + 2 - 3) // 2 + 1, (d0.Wo + 2 - 3) // 2 + 1
+        cur = torch.empty((B, Hc, Wc, 64), dtype=act, device=x.device)
+        one_launch = bf16 and stem.k == 7 and stem.stride == 2 and stem.pad == 3 and d0.Wo <= 4096
+        if not one_launch:
+            a0 = torch.empty((B, d0.Ho, d0.Wo, 64), dtype=act, device=x.device)
+            wss = self._ws(lib.sd_conv2d_stem_fwd_workspace_bytes(C.byref(d0)), x.device)
+        sc, sh = self.bn_fold(bn0)
+        if one_launch:
+            # conv1 -> bn1 -> relu -> maxpool in one launch: the (B, H/2, W/2, 64) activation is never written
+            L.check(lib.sd_stem_bn_relu_maxpool_fwd_bf16(x.data_ptr(), stem.weight.data_ptr(), sc.data_ptr(), sh.data_ptr(), cur.data_ptr(),
+                                                         C.byref(d0), L.stream()), "stem+maxpool")
+        else:
+            L.check(lib.sd_conv2d_stem_fwd(x.data_ptr(), stem.weight.data_ptr(), a0.data_ptr(), C.byref(d0), sc.data_ptr(), sh.data_ptr(), 1, int(bf16),
+                                           wss.data_ptr(), wss.numel(), L.stream()), "stem")
+            if bf16:
+                L.check(lib.sd_maxpool3x3s2_fwd_bf16(a0.data_ptr(), cur.data_ptr(), B, d0.Ho, d0.Wo, 64, L.stream()), "maxpool")
+            else:
+                pidx = torch.empty((B, Hc, Wc, 64), dtype=torch.uint8, device=x.device)
+                L.check(lib.sd_maxpool3x3s2_fwd(a0.data_ptr(), cur.data_ptr(), pidx.data_ptr(), B, d0.Ho, d0.Wo, 64, L.stream()), "maxpool")
+        T.pop()
+
+        # trunk (network.py:47-50)
+        feats = []
+        for li, layer in enumerate((net.down1, net.down2, net.down3, net.down4), start=1):
+            T.push(f"fwd:down{li}")
+            for blk in layer:
+                s1, h1 = self.bn_fold(blk.bn1)
+                a1, d1 = self.conv(how, cur, blk.conv1, B, Hc, Wc, scale=s1, shift=h1, relu=True)
+                if blk.downsample is not None:
+                    sd_, hd = self.bn_fold(blk.downsample[1])
+                    idt, _ = self.conv(how, cur, blk.downsample[0], B, Hc, Wc, scale=sd_, shift=hd)
+                else:
+                    idt = cur
+                s2, h2 = self.bn_fold(blk.bn2)
+                cur, _ = self.conv(how, a1, blk.conv2, B, d1.Ho, d1.Wo, scale=s2, shift=h2, res=idt, relu=True)
+                Hc, Wc = d1.Ho, d1.Wo
+            feats.append((cur, Hc, Wc))
+            T.pop()
+        (p2, H2, W2), (p3, H3, W3), (p4, H4, W4), (p5, H5, W5) = feats
+
+        # FPN (network.py:52-55,6-19): lateral 1x1 (+bias) with the x2-upsampled coarser map added in the epilogue
+        T.push("fwd:fpn")
+        f, _ = self.conv(how, p5, net.up1, B, H5, W5, shift=net.up1.bias)
+        hc = net.head.conv
+        out = torch.empty((B, hc.cout, H2, W2), dtype=torch.float32, device=x.device)
+        for fpn, (sc_t, Hs, Ws) in ((net.up2, (p4, H4, W4)), (net.up3, (p3, H3, W3)), (net.up4, (p2, H2, W2))):
+            t, _ = self.conv(how, sc_t, fpn.lateral, B, Hs, Ws, shift=fpn.lateral.bias, res=f, res_up2=True)
+            sf, hf = self.bn_fold(fpn.conv[1])
+            if bf16 and fpn is net.up4 and self.fuse_head and self._head_fusable(B, Hs, Ws, fpn.conv[0], hc):
+                # network.py:17-18 + 22-29 in one launch where the conv takes the two-group kernel: the FPN output is never stored
+                dl = _desc(B, Hs, Ws, fpn.conv[0])
+                rc = lib.sd_conv2d_fwd_bf16_head(t.data_ptr(), self._w_bf16(fpn.conv[0]).data_ptr(), C.byref(dl), sf.data_ptr(), hf.data_ptr(), 1,
+                                                 self._head_prepared(hc).data_ptr(), hc.cout, out.data_ptr(), L.stream())
+                if rc == 0:
+                    T.pop()
+                    return out
+                if rc > 0:
+                    L.check(rc, "sd_conv2d_fwd_bf16_head")
+                # rc < 0 = "geometry not served" BEFORE any launch: the remembered answer was taken under other thread-local dispatch
+                # options (`conv_pp_min_tiles`, `conv_pp_strips`, `conv_fwd_split_k` change what the two-group kernel takes).  Forget
+                # it and run conv + head as two launches.
+                self._head_ok.pop((B, Hs, Ws, hc.cout), None)
+            f, _ = self.conv(how, t, fpn.conv[0], B, Hs, Ws, scale=sf, shift=hf, relu=True)
+        T.pop()
+
+        # head (network.py:57): NHWC -> NCHW, fp32
+        T.push("fwd:head")
+        L.check(self._fn("sd_head_fwd", bf16)(f.data_ptr(), hc.weight.data_ptr(), hc.bias.data_ptr(), out.data_ptr(), B, H2 * W2, hc.cin, hc.cout,
+                                              L.stream()), "sd_head_fwd")
+        T.pop()
         return out
 
     # ---- bf16 backbone, inference only (BASELINE stress config: "bf16 backbone + fp32 decode") -------------
@@ -507,82 +602,6 @@ class _Engine:
             self.net._folded[key] = buf
         return buf
 
-    def conv_bf16(self, x, conv, B, Hi, Wi, scale=None, shift=None, res=None, res_up2=False, relu=False):
-        d = _desc(B, Hi, Wi, conv)
-        y = torch.empty((B, d.Ho, d.Wo, conv.cout), dtype=torch.bfloat16, device=x.device)
-        if self.small_batch_kernel and self.lib.sd_conv2d_fwd_sb_supported(C.byref(d), 1):
-            self._conv_sb(x, self._w_bf16(conv), y, d, scale, shift, res, res_up2, relu, 1)
-            return y, d
-        nws = self.lib.sd_conv2d_fwd_bf16_workspace_bytes(C.byref(d))
-        ws = self._ws(nws, x.device) if nws else None
-        L.check(self.lib.sd_conv2d_fwd_bf16(x.data_ptr(), self._w_bf16(conv).data_ptr(), y.data_ptr(), C.byref(d), _ptr(scale), _ptr(shift),
-                                            _ptr(res), int(res_up2), int(relu), _ptr(ws), ws.numel() if nws else 0, L.stream()),
-                "sd_conv2d_fwd_bf16")
-        return y, d
-
-    def forward_bf16(self, x):
-        """Eval-mode forward with bf16 activations / weights and fp32 accumulation; BN folded into fp32 epilogues.
-        The stem reads the fp32 image with fp32 weights and stores bf16; the head returns fp32 NCHW."""
-        net, lib = self.net, self.lib
-        L.require_cuda(x)
-        x = x.contiguous().float()
-        B, _, H, W = x.shape
-        if x.dim() != 4 or x.shape[1] != 3 or H % 32 or W % 32:
-            raise L.SdError("Network expects (B, 3, H, W) input with H, W multiples of 32")
-        stem, bn0 = net.adpater[0], net.adpater[1]
-        d0 = _desc(B, H, W, stem)
-        sc, sh = self.bn_fold(bn0)
-        Hc, Wc = (d0.Ho + 2 - 3) // 2 + 1, (d0.Wo + 2 - 3) // 2 + 1
-        cur = torch.empty((B, Hc, Wc, 64), dtype=torch.bfloat16, device=x.device)
-        if stem.k == 7 and stem.stride == 2 and stem.pad == 3 and d0.Wo <= 4096:
-            # conv1 -> bn1 -> relu -> maxpool in one launch: the (B, H/2, W/2, 64) activation is never written
-            L.check(lib.sd_stem_bn_relu_maxpool_fwd_bf16(x.data_ptr(), stem.weight.data_ptr(), sc.data_ptr(), sh.data_ptr(), cur.data_ptr(),
-                                                         C.byref(d0), L.stream()), "stem+maxpool")
-        else:
-            a0 = torch.empty((B, d0.Ho, d0.Wo, 64), dtype=torch.bfloat16, device=x.device)
-            wss = self._ws(lib.sd_conv2d_stem_fwd_workspace_bytes(C.byref(d0)), x.device)
-            L.check(lib.sd_conv2d_stem_fwd(x.data_ptr(), stem.weight.data_ptr(), a0.data_ptr(), C.byref(d0), sc.data_ptr(), sh.data_ptr(), 1, 1,
-                                           wss.data_ptr(), wss.numel(), L.stream()), "stem")
-            L.check(lib.sd_maxpool3x3s2_fwd_bf16(a0.data_ptr(), cur.data_ptr(), B, d0.Ho, d0.Wo, 64, L.stream()), "maxpool")
-        feats = []
-        for layer in (net.down1, net.down2, net.down3, net.down4):
-            for blk in layer:
-                s1, h1 = self.bn_fold(blk.bn1)
-                a1, d1 = self.conv_bf16(cur, blk.conv1, B, Hc, Wc, scale=s1, shift=h1, relu=True)
-                if blk.downsample is not None:
-                    sd_, hd = self.bn_fold(blk.downsample[1])
-                    idt, _ = self.conv_bf16(cur, blk.downsample[0], B, Hc, Wc, scale=sd_, shift=hd)
-                else:
-                    idt = cur
-                s2, h2 = self.bn_fold(blk.bn2)
-                cur, _ = self.conv_bf16(a1, blk.conv2, B, d1.Ho, d1.Wo, scale=s2, shift=h2, res=idt, relu=True)
-                Hc, Wc = d1.Ho, d1.Wo
-            feats.append((cur, Hc, Wc))
-        (p2, H2, W2), (p3, H3, W3), (p4, H4, W4), (p5, H5, W5) = feats
-        f, _ = self.conv_bf16(p5, net.up1, B, H5, W5, shift=net.up1.bias)
-        hc = net.head.conv
-        out = torch.empty((B, hc.cout, H2, W2), dtype=torch.float32, device=x.device)
-        for fpn, (sc_t, Hs, Ws) in ((net.up2, (p4, H4, W4)), (net.up3, (p3, H3, W3)), (net.up4, (p2, H2, W2))):
-            t, _ = self.conv_bf16(sc_t, fpn.lateral, B, Hs, Ws, shift=fpn.lateral.bias, res=f, res_up2=True)
-            sf, hf = self.bn_fold(fpn.conv[1])
-            if fpn is net.up4 and self.fuse_head and self._head_fusable(B, Hs, Ws, fpn.conv[0], hc):
-                # network.py:17-18 + 22-29 in one launch where the conv takes the two-group kernel: the FPN output is never stored
-                dl = _desc(B, Hs, Ws, fpn.conv[0])
-                rc = lib.sd_conv2d_fwd_bf16_head(t.data_ptr(), self._w_bf16(fpn.conv[0]).data_ptr(), C.byref(dl), sf.data_ptr(), hf.data_ptr(), 1,
-                                                 self._head_prepared(hc).data_ptr(), hc.cout, out.data_ptr(), L.stream())
-                if rc == 0:
-                    return out
-                if rc > 0:
-                    L.check(rc, "sd_conv2d_fwd_bf16_head")
-                # rc < 0 = "geometry not served" BEFORE any launch: the remembered answer was taken under other thread-local dispatch
-                # options (`conv_pp_min_tiles`, `conv_pp_strips`, `conv_fwd_split_k` change what the two-group kernel takes).  Forget
-                # it and run conv + head as two launches.
-                self._head_ok.pop((B, Hs, Ws, hc.cout), None)
-            f, _ = self.conv_bf16(t, fpn.conv[0], B, Hs, Ws, scale=sf, shift=hf, relu=True)
-        L.check(lib.sd_head_fwd_bf16(f.data_ptr(), hc.weight.data_ptr(), hc.bias.data_ptr(), out.data_ptr(), B, H2 * W2, hc.cin, hc.cout,
-                                     L.stream()), "sd_head_fwd_bf16")
-        return out
-
     # ---- backward ------------------------------------------------------------------------
     def _transpose_all(self, amp):
         """Every data-gradient conv's weights [Cout][taps][Cin] -> [Cin][taps][Cout] in ONE launch at the start of a backward pass
@@ -613,55 +632,44 @@ class _Engine:
             off, n = self._wt_plan[3][id(conv)]
             return self._wt_flat[self._wt_valid][off:off + n]
         wt = torch.empty(conv.cin * conv.k * conv.k * conv.cout, dtype=torch.bfloat16 if amp else torch.float32, device=conv.weight.device)
-        transpose = self.lib.sd_conv2d_transpose_weights_bf16 if amp else self.lib.sd_conv2d_transpose_weights
-        L.check(transpose(conv.weight.data_ptr(), wt.data_ptr(), conv.cout, conv.k * conv.k, conv.cin, L.stream()), "transpose_weights")
+        L.check(self._fn("sd_conv2d_transpose_weights", amp)(conv.weight.data_ptr(), wt.data_ptr(), conv.cout, conv.k * conv.k, conv.cin, L.stream()),
+                "transpose_weights")
         return wt
 
     def _dgrad(self, dy, conv, d, res=None, bn_next=None, res_half=False, sync=None):
-        """dx = dgrad(dy) [+ res].  bn_next = (x, y, relu, bn, mean, invstd) of the BatchNorm whose output gradient dx is:
-        the launch then also does that BatchNorm's backward reduction (sd_conv2d_dgrad_bn_reduce) and the per-channel means
-        come back for _bn_bwd(..., means=...), which only has the apply pass left."""
-        amp = dy.dtype == torch.bfloat16
+        """dx = dgrad(dy) [+ res] -> (dx, None).  bn_next = (x, y, relu, bn, mean, invstd) of the BatchNorm whose output gradient dx is:
+        the launch then also does that BatchNorm's backward reduction (sd_conv2d_dgrad_bn_reduce) and returns (dx, the per-channel
+        means) for _bn_bwd(..., means=...), which only has the apply pass left."""
+        lib, amp = self.lib, dy.dtype == torch.bfloat16
         dx = torch.empty((d.B, d.Hi, d.Wi, conv.cin), dtype=dy.dtype, device=dy.device)
         wt = self._wt(conv, amp)
-        flops = 2.0 * d.B * d.Ho * d.Wo * conv.cout * conv.cin * conv.k * conv.k
-        if amp:
-            assert bn_next is None, "fuse_bn_bwd is an fp32-path experiment"
-            mode = 2 if res_half else (1 if res is not None else 0)
-            self._timed("bf16:" + self._kname(d, 17), flops, lambda: L.check(
-                self.lib.sd_conv2d_dgrad_bf16(dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), C.byref(d), _ptr(res), mode, L.stream()),
-                "sd_conv2d_dgrad_bf16"), phase="dgrad")
-            return dx
+        head = (dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), C.byref(d))
         if bn_next is None:
-            if res_half:
-                fn = lambda: L.check(self.lib.sd_conv2d_dgrad_half_res(dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), C.byref(d), res.data_ptr(),
-                                                                       L.stream()), "sd_conv2d_dgrad_half_res")
+            t = self._tic(d, 17 if amp else 1, amp)
+            if amp:
+                L.check(lib.sd_conv2d_dgrad_bf16(*head, _ptr(res), 2 if res_half else (1 if res is not None else 0), L.stream()), "sd_conv2d_dgrad_bf16")
+            elif res_half:
+                L.check(lib.sd_conv2d_dgrad_half_res(*head, res.data_ptr(), L.stream()), "sd_conv2d_dgrad_half_res")
             else:
-                fn = lambda: L.check(self.lib.sd_conv2d_dgrad(dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), C.byref(d), _ptr(res), L.stream()),
-                                     "sd_conv2d_dgrad")
-            self._timed(self._kname(d, 1), flops, fn, phase="dgrad")
-            return dx
-        assert not res_half
+                L.check(lib.sd_conv2d_dgrad(*head, _ptr(res), L.stream()), "sd_conv2d_dgrad")
+            self._toc(t, d, "dgrad")
+            return dx, None
+        assert not amp and not res_half, "fuse_bn_bwd is an fp32-path experiment"
         x, y, relu, bn, mean, invstd = bn_next
-        ws = self._ws(self.lib.sd_conv2d_dgrad_bn_reduce_workspace_bytes(C.byref(d)), dy.device)
+        ws = self._ws(lib.sd_conv2d_dgrad_bn_reduce_workspace_bytes(C.byref(d)), dy.device)
         if sync is not None:            # synchronized BatchNorm: the epilogue's sums are exchanged before the means are formed
-            sums = sync.take(conv.cin)
+            out = sync.take(conv.cin)
             sync.record("sd_conv2d_dgrad_bn_reduce_sums")
-            self._timed(self._kname(d, 1), flops, lambda: L.check(
-                self.lib.sd_conv2d_dgrad_bn_reduce_sums(dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), C.byref(d), _ptr(res), x.data_ptr(),
-                                                        _ptr(y) if int(relu) in (1, 3) else 0, int(relu), mean.data_ptr(), invstd.data_ptr(),
-                                                        bn.weight.data_ptr(), bn.bias.data_ptr(), self.net.grad_of(bn.weight).data_ptr(),
-                                                        self.net.grad_of(bn.bias).data_ptr(), 0, sums.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                        L.stream()), "sd_conv2d_dgrad_bn_reduce_sums"), phase="dgrad")
-            return dx, self._means_from_sums(sync, sums, conv.cin, dy.device)
-        means = torch.empty(2 * conv.cin, dtype=torch.float32, device=dy.device)
-        self._timed(self._kname(d, 1), flops, lambda: L.check(
-            self.lib.sd_conv2d_dgrad_bn_reduce(dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), C.byref(d), _ptr(res), x.data_ptr(),
-                                               _ptr(y) if int(relu) in (1, 3) else 0, int(relu), mean.data_ptr(), invstd.data_ptr(),
-                                               bn.weight.data_ptr(), bn.bias.data_ptr(), self.net.grad_of(bn.weight).data_ptr(),
-                                               self.net.grad_of(bn.bias).data_ptr(), 0, means.data_ptr(), ws.data_ptr(), ws.numel(),
-                                               L.stream()), "sd_conv2d_dgrad_bn_reduce"), phase="dgrad")
-        return dx, means
+            reduce = lib.sd_conv2d_dgrad_bn_reduce_sums
+        else:
+            out = torch.empty(2 * conv.cin, dtype=torch.float32, device=dy.device)
+            reduce = lib.sd_conv2d_dgrad_bn_reduce
+        t = self._tic(d, 1)
+        L.check(reduce(*head, _ptr(res), x.data_ptr(), _mask_ptr(y, relu), relu, mean.data_ptr(), invstd.data_ptr(), bn.weight.data_ptr(),
+                       bn.bias.data_ptr(), self.net.grad_of(bn.weight).data_ptr(), self.net.grad_of(bn.bias).data_ptr(), 0, out.data_ptr(),
+                       ws.data_ptr(), ws.numel(), L.stream()), "sd_conv2d_dgrad_bn_reduce")
+        self._toc(t, d, "dgrad")
+        return dx, (out if sync is None else self._means_from_sums(sync, out, conv.cin, dy.device))
 
     def _side_stream(self):
         if self._side is None:
@@ -685,60 +693,42 @@ class _Engine:
 
     def _wgrad_now(self, dy, x, conv, d):
         g = self.net.grad_of(conv.weight)
-        flops = 2.0 * d.B * d.Ho * d.Wo * conv.cout * conv.cin * conv.k * conv.k
-        if dy.dtype == torch.bfloat16:
-            # mixed precision: bf16 operands, fp32 accumulation, fp32 gradient (3x3 / stride 1 layers on the bf16 MFMA through
-            # transposed LDS reads; the strided and 1x1 convs widen their operands in the workspace and take the fp32 kernels)
-            ws = self._ws(self.lib.sd_conv2d_wgrad_bf16_workspace_bytes(C.byref(d)), dy.device)
-            self._timed("bf16:" + self._kname(d, 2), flops, lambda: L.check(
-                self.lib.sd_conv2d_wgrad_bf16(dy.data_ptr(), x.data_ptr(), g.data_ptr(), C.byref(d), 0, ws.data_ptr(), ws.numel(), L.stream()),
-                "sd_conv2d_wgrad_bf16"), phase="wgrad")
-            return
-        nbytes = self.lib.sd_conv2d_wgrad_workspace_bytes(C.byref(d))
-        ws = self._ws(nbytes, dy.device)
-        self._timed(self._kname(d, 2), flops, lambda: L.check(
-            self.lib.sd_conv2d_wgrad(dy.data_ptr(), x.data_ptr(), g.data_ptr(), C.byref(d), 0, ws.data_ptr(), ws.numel(), L.stream()),
-            "sd_conv2d_wgrad"), phase="wgrad")
+        # mixed precision: bf16 operands, fp32 accumulation, fp32 gradient (3x3 / stride 1 layers on the bf16 MFMA through
+        # transposed LDS reads; the strided and 1x1 convs widen their operands in the workspace and take the fp32 kernels)
+        bf16 = dy.dtype == torch.bfloat16
+        ws_bytes = self.lib.sd_conv2d_wgrad_bf16_workspace_bytes if bf16 else self.lib.sd_conv2d_wgrad_workspace_bytes
+        ws = self._ws(ws_bytes(C.byref(d)), dy.device)
+        t = self._tic(d, 2, bf16)
+        L.check(self._fn("sd_conv2d_wgrad", bf16)(dy.data_ptr(), x.data_ptr(), g.data_ptr(), C.byref(d), 0, ws.data_ptr(), ws.numel(), L.stream()),
+                "sd_conv2d_wgrad")
+        self._toc(t, d, "wgrad")
 
     def _bias_grad(self, dy, conv):
         Mrows, Cc = dy.numel() // dy.shape[-1], dy.shape[-1]
         ws = self._ws(self.lib.sd_col_reduce_workspace_bytes(Mrows, Cc), dy.device)
-        col_sum = self.lib.sd_col_sum_bf16 if dy.dtype == torch.bfloat16 else self.lib.sd_col_sum
-        L.check(col_sum(dy.data_ptr(), Mrows, Cc, self.net.grad_of(conv.bias).data_ptr(), 0, ws.data_ptr(), ws.numel(), L.stream()),
-                "sd_col_sum")
+        L.check(self._fn("sd_col_sum", dy.dtype == torch.bfloat16)(dy.data_ptr(), Mrows, Cc, self.net.grad_of(conv.bias).data_ptr(), 0,
+                                                                   ws.data_ptr(), ws.numel(), L.stream()), "sd_col_sum")
 
     def _bn_bwd(self, dy, x, y, relu, bn, mean, invstd, want_g=False, means=None, sync=None):
+        """BatchNorm backward: dx (and the ReLU-masked dy as `g` on request); dgamma / dbeta into the flat gradients.  means: the reduction
+        was done by the data-gradient launch that produced dy, only the apply half is left.  sync: reduce half, exchange, apply half."""
+        lib, bf16 = self.lib, x.dtype == torch.bfloat16
         Mrows, Cc = x.numel() // x.shape[-1], x.shape[-1]
         dx = torch.empty_like(x)
         g = torch.empty_like(x) if want_g else None
-        if means is None and sync is not None:
-            # synchronized BatchNorm: the reduce half (dgamma / dbeta from the local sums), the exchange, the means, then the apply half
+        head = (dy.data_ptr(), x.data_ptr(), _mask_ptr(y, relu), relu, Mrows, Cc, mean.data_ptr(), invstd.data_ptr(), bn.weight.data_ptr(),
+                bn.bias.data_ptr())
+        if means is None:
+            grads = (self.net.grad_of(bn.weight).data_ptr(), self.net.grad_of(bn.bias).data_ptr(), 0)
+            ws = self._ws(lib.sd_col_reduce_workspace_bytes(Mrows, Cc), x.device)
+            if sync is None:
+                L.check(self._fn("sd_bn_bwd", bf16)(*head, dx.data_ptr(), _ptr(g), *grads, ws.data_ptr(), ws.numel(), L.stream()), "sd_bn_bwd")
+                return dx, g
             sums = sync.take(Cc)
-            bf16 = x.dtype == torch.bfloat16
             sync.record("sd_bn_bwd_reduce_bf16" if bf16 else "sd_bn_bwd_reduce")
-            ws = self._ws(self.lib.sd_col_reduce_workspace_bytes(Mrows, Cc), x.device)
-            reduce = self.lib.sd_bn_bwd_reduce_bf16 if bf16 else self.lib.sd_bn_bwd_reduce
-            L.check(reduce(dy.data_ptr(), x.data_ptr(), _ptr(y) if int(relu) in (1, 3) else 0, int(relu), Mrows, Cc, mean.data_ptr(),
-                           invstd.data_ptr(), bn.weight.data_ptr(), bn.bias.data_ptr(), self.net.grad_of(bn.weight).data_ptr(),
-                           self.net.grad_of(bn.bias).data_ptr(), 0, sums.data_ptr(), ws.data_ptr(), ws.numel(), L.stream()), "sd_bn_bwd_reduce")
+            L.check(self._fn("sd_bn_bwd_reduce", bf16)(*head, *grads, sums.data_ptr(), ws.data_ptr(), ws.numel(), L.stream()), "sd_bn_bwd_reduce")
             means = self._means_from_sums(sync, sums, Cc, x.device)
-            apply = self.lib.sd_bn_bwd_apply_bf16 if bf16 else self.lib.sd_bn_bwd_apply
-            L.check(apply(dy.data_ptr(), x.data_ptr(), _ptr(y) if int(relu) in (1, 3) else 0, int(relu), Mrows, Cc, mean.data_ptr(),
-                          invstd.data_ptr(), bn.weight.data_ptr(), bn.bias.data_ptr(), means.data_ptr(), dx.data_ptr(), _ptr(g), L.stream()),
-                    "sd_bn_bwd_apply")
-            return dx, g
-        if means is not None:       # reduction (and dgamma / dbeta) already done by the data-gradient launch that produced dy
-            L.check(self.lib.sd_bn_bwd_apply(dy.data_ptr(), x.data_ptr(), _ptr(y) if int(relu) in (1, 3) else 0, int(relu), Mrows, Cc,
-                                             mean.data_ptr(), invstd.data_ptr(), bn.weight.data_ptr(), bn.bias.data_ptr(), means.data_ptr(),
-                                             dx.data_ptr(), _ptr(g), L.stream()), "sd_bn_bwd_apply")
-            return dx, g
-        ws = self._ws(self.lib.sd_col_reduce_workspace_bytes(Mrows, Cc), x.device)
-        # relu: False/0 = none, True/1 = mask from y, 3 = y holds the mask bytes of sd_bn_apply (residual layers), 2 = mask recomputed from x
-        bn_bwd = self.lib.sd_bn_bwd_bf16 if x.dtype == torch.bfloat16 else self.lib.sd_bn_bwd
-        L.check(bn_bwd(dy.data_ptr(), x.data_ptr(), _ptr(y) if int(relu) in (1, 3) else 0, int(relu), Mrows, Cc, mean.data_ptr(),
-                                   invstd.data_ptr(), bn.weight.data_ptr(), bn.bias.data_ptr(), dx.data_ptr(), _ptr(g),
-                                   self.net.grad_of(bn.weight).data_ptr(),
-                                   self.net.grad_of(bn.bias).data_ptr(), 0, ws.data_ptr(), ws.numel(), L.stream()), "sd_bn_bwd")
+        L.check(self._fn("sd_bn_bwd_apply", bf16)(*head, means.data_ptr(), dx.data_ptr(), _ptr(g), L.stream()), "sd_bn_bwd_apply")
         return dx, g
 
     def backward(self, tape, dhead, on_stage=None):
@@ -759,36 +749,30 @@ class _Engine:
         T.push("bwd:fpn_head")
         self._transpose_all(amp)
         ws = self._ws(lib.sd_head_bwd_workspace_bytes(B, H2 * W2, hc.cin, hc.cout), dhead.device)
-        if amp and hc.cin in (64, 128) and hc.cout <= 8:
-            # bf16 FPN output in, bf16 gradient out (fp32 arithmetic, fp32 weight / bias gradients): no fp32 copies of the two maps
-            f1 = tape["f1"]
-            df = torch.empty_like(f1)
-            L.check(lib.sd_head_bwd_bf16(dhead.data_ptr(), f1.data_ptr(), hc.weight.data_ptr(), df.data_ptr(), net.grad_of(hc.weight).data_ptr(),
-                                         net.grad_of(hc.bias).data_ptr(), B, H2 * W2, hc.cin, hc.cout, 0, ws.data_ptr(), ws.numel(), L.stream()),
-                    "sd_head_bwd_bf16")
-        else:
-            f1 = self._to_f32(tape["f1"]) if amp else tape["f1"]      # wide heads: fp32 kernels on widened copies
-            df = torch.empty_like(f1)
-            L.check(lib.sd_head_bwd(dhead.data_ptr(), f1.data_ptr(), hc.weight.data_ptr(), df.data_ptr(), net.grad_of(hc.weight).data_ptr(),
-                                    net.grad_of(hc.bias).data_ptr(), B, H2 * W2, hc.cin, hc.cout, 0, ws.data_ptr(), ws.numel(), L.stream()),
-                    "sd_head_bwd")
-            if amp:
-                df = self._to_bf16(df)
+        # amp, narrow heads: bf16 FPN output in, bf16 gradient out (fp32 arithmetic, fp32 weight / bias gradients): no fp32 copies of the two
+        # maps.  amp, wide heads: the fp32 kernels on widened copies
+        widen = amp and not (hc.cin in (64, 128) and hc.cout <= 8)
+        f1 = self._to_f32(tape["f1"]) if widen else tape["f1"]
+        df = torch.empty_like(f1)
+        L.check(self._fn("sd_head_bwd", amp and not widen)(
+            dhead.data_ptr(), f1.data_ptr(), hc.weight.data_ptr(), df.data_ptr(), net.grad_of(hc.weight).data_ptr(),
+            net.grad_of(hc.bias).data_ptr(), B, H2 * W2, hc.cin, hc.cout, 0, ws.data_ptr(), ws.numel(), L.stream()), "sd_head_bwd")
+        if widen:
+            df = self._to_bf16(df)
 
         # FPN, finest level first.  The lateral 1x1 data-gradients are deferred until the trunk's own
         # gradient for that tensor exists, so the sum of the two is the dgrad kernel's residual epilogue.
         lateral_grad = {}
-        for (fpn, sc_t, (Hs, Ws), dl, t, dc, c, mf, if_, fn) in reversed(tape["fpn"]):
-            dcv, _ = self._bn_bwd(df, c, fn, 2, fpn.conv[1], mf, if_, sync=sx)
-            dt = self._dgrad(dcv, fpn.conv[0], dc)
-            self._wgrad(dcv, t, fpn.conv[0], dc)
-            self._wgrad(dt, sc_t, fpn.lateral, dl)
+        for r in reversed(tape["fpn"]):
+            fpn, (Hs, Ws) = r.fpn, r.hw
+            dcv, _ = self._bn_bwd(df, r.c, r.out, RELU_FROM_X, fpn.conv[1], r.mean, r.invstd, sync=sx)
+            dt, _ = self._dgrad(dcv, fpn.conv[0], r.dc)
+            self._wgrad(dcv, r.t, fpn.conv[0], r.dc)
+            self._wgrad(dt, r.shortcut, fpn.lateral, r.dl)
             self._bias_grad(dt, fpn.lateral)
-            lateral_grad[sc_t.data_ptr()] = (dt, fpn.lateral, dl)
-            dfp = torch.empty((B, Hs // 2, Ws // 2, fpn.lateral.cout), dtype=dt.dtype, device=dt.device)
-            up2_bwd = lib.sd_upsample2x_bwd_bf16 if amp else lib.sd_upsample2x_bwd
-            L.check(up2_bwd(dt.data_ptr(), 0, dfp.data_ptr(), B, Hs // 2, Ws // 2, fpn.lateral.cout, L.stream()), "up2_bwd")
-            df = dfp
+            lateral_grad[r.shortcut.data_ptr()] = LateralGrad(dt, fpn.lateral, r.dl)
+            df = torch.empty((B, Hs // 2, Ws // 2, fpn.lateral.cout), dtype=dt.dtype, device=dt.device)
+            L.check(self._fn("sd_upsample2x_bwd", amp)(dt.data_ptr(), 0, df.data_ptr(), B, Hs // 2, Ws // 2, fpn.lateral.cout, L.stream()), "up2_bwd")
         p5, H5, W5 = tape["p5"]
         d5 = _desc(B, H5, W5, net.up1)
         self._wgrad(df, p5, net.up1, d5)
@@ -797,17 +781,15 @@ class _Engine:
         # BatchNorm's backward reduction in its epilogue (bn_next); `mcur` / `ma1` carry the per-channel means to the apply pass.
         blocks = tape["blocks"]
 
-        def bn2_of(i):          # bn_next tuple of block i's second BatchNorm (mask from the saved output: residual layer)
+        def bn2_of(i):          # bn_next tuple of block i's second BatchNorm (mask from the saved mask bytes: residual layer)
             if i < 0 or not self.fuse_bn_bwd:
                 return None
-            b = blocks[i]       # (blk, xin, (Hc, Wc), d1, c1, a1, m1, i1, d2, c2, m2, i2, out, dd, cd, md, idd, relu mask bytes)
-            return (b[9], b[17], 3, b[0].bn2, b[10], b[11])
+            b = blocks[i]
+            return (b.c2, b.mask, RELU_MASK_BYTES, b.blk.bn2, b.m2, b.i2)
 
         last = len(blocks) - 1
-        has_lateral = blocks[last][12].data_ptr() in lateral_grad
-        nxt = None if has_lateral else bn2_of(last)
-        r = self._dgrad(df, net.up1, d5, bn_next=nxt, sync=sx)
-        dcur, mcur = r if nxt is not None else (r, None)
+        has_lateral = blocks[last].out.data_ptr() in lateral_grad
+        dcur, mcur = self._dgrad(df, net.up1, d5, bn_next=None if has_lateral else bn2_of(last), sync=sx)
         T.pop()
         if on_stage:
             self._join_side()
@@ -817,22 +799,20 @@ class _Engine:
         first_of = {id(net.down4[0]): "down4", id(net.down3[0]): "down3", id(net.down2[0]): "down2"}
         T.push("bwd:down4")
         for bi in range(last, -1, -1):
-            (blk, xin, (Hc, Wc), d1, c1, a1, m1, i1, d2, c2, m2, i2, out, dd, cd, md, idd, msk) = blocks[bi]
-            extra = lateral_grad.pop(out.data_ptr(), None)
+            b = blocks[bi]
+            blk, xin, (Hc, Wc) = b.blk, b.xin, b.hw
+            extra = lateral_grad.pop(b.out.data_ptr(), None)
             if extra is not None:                       # `out` also feeds an FPN lateral conv: this launch completes d(out)
-                nxt = bn2_of(bi)
-                r = self._dgrad(extra[0], extra[1], extra[2], res=dcur, bn_next=nxt, sync=sx)
-                dcur, mcur = r if nxt is not None else (r, None)
-            dc2, g = self._bn_bwd(dcur, c2, msk, 3, blk.bn2, m2, i2, want_g=True, means=mcur, sync=sx)
-            nxt = (c1, None, 2, blk.bn1, m1, i1) if self.fuse_bn_bwd else None
-            r = self._dgrad(dc2, blk.conv2, d2, bn_next=nxt, sync=sx)
-            da1, ma1 = r if nxt is not None else (r, None)
-            self._wgrad(dc2, a1, blk.conv2, d2)
-            dc1, _ = self._bn_bwd(da1, c1, a1, 2, blk.bn1, m1, i1, means=ma1, sync=sx)
+                dcur, mcur = self._dgrad(extra.dy, extra.conv, extra.d, res=dcur, bn_next=bn2_of(bi), sync=sx)
+            dc2, g = self._bn_bwd(dcur, b.c2, b.mask, RELU_MASK_BYTES, blk.bn2, b.m2, b.i2, want_g=True, means=mcur, sync=sx)
+            nxt = (b.c1, None, RELU_FROM_X, blk.bn1, b.m1, b.i1) if self.fuse_bn_bwd else None
+            da1, ma1 = self._dgrad(dc2, blk.conv2, b.d2, bn_next=nxt, sync=sx)
+            self._wgrad(dc2, b.a1, blk.conv2, b.d2)
+            dc1, _ = self._bn_bwd(da1, b.c1, b.a1, RELU_FROM_X, blk.bn1, b.m1, b.i1, means=ma1, sync=sx)
             half = False
             if blk.downsample is not None:
-                dcd, _ = self._bn_bwd(g, cd, None, False, blk.downsample[1], md, idd, sync=sx)
-                ds = blk.downsample[0]
+                dcd, _ = self._bn_bwd(g, b.cd, None, RELU_NONE, blk.downsample[1], b.md, b.idd, sync=sx)
+                ds, dd = blk.downsample[0], b.dd
                 half = ds.k == 1 and ds.stride == 2 and ds.pad == 0 and Hc % 2 == 0 and Wc % 2 == 0 and not self.fuse_bn_bwd
                 if half:
                     # 1x1 / stride 2: the gradient lives on the even pixels only -> stride-1 data-gradient on the small map,
@@ -840,18 +820,17 @@ class _Engine:
                     dsm = L.ConvDesc()
                     dsm.B, dsm.Hi, dsm.Wi, dsm.Cin, dsm.Cout, dsm.R, dsm.S, dsm.stride, dsm.pad = B, dd.Ho, dd.Wo, ds.cin, ds.cout, 1, 1, 1, 0
                     dsm.Ho, dsm.Wo = dd.Ho, dd.Wo
-                    skip = self._dgrad(dcd, ds, dsm)
+                    skip, _ = self._dgrad(dcd, ds, dsm)
                 else:
-                    skip = self._dgrad(dcd, ds, dd)
+                    skip, _ = self._dgrad(dcd, ds, dd)
                 self._wgrad(dcd, xin, ds, dd)
             else:
                 skip = g
             # d(xin) = d(out of the previous block), complete unless that tensor also feeds an FPN lateral (handled above)
-            prev_lateral = bi > 0 and blocks[bi - 1][12].data_ptr() in lateral_grad
+            prev_lateral = bi > 0 and blocks[bi - 1].out.data_ptr() in lateral_grad
             nxt = None if (bi == 0 or prev_lateral) else bn2_of(bi - 1)
-            r = self._dgrad(dc1, blk.conv1, d1, res=skip, bn_next=nxt, res_half=half, sync=sx)
-            dcur, mcur = r if nxt is not None else (r, None)
-            self._wgrad(dc1, xin, blk.conv1, d1)
+            dcur, mcur = self._dgrad(dc1, blk.conv1, b.d1, res=skip, bn_next=nxt, res_half=half, sync=sx)
+            self._wgrad(dc1, xin, blk.conv1, b.d1)
             if id(blk) in first_of:                                         # the first block of a layer closes that layer's range
                 T.pop()
                 if on_stage:
@@ -859,36 +838,32 @@ class _Engine:
                     on_stage(first_of[id(blk)])
                 T.push("bwd:" + {"down4": "down3", "down3": "down2", "down2": "down1_stem"}[first_of[id(blk)]])
 
-        # stem
+        # stem (H % 32 == 0 made its map even: under mixed precision the conv output and the pooled gradient are bf16, as autocast's conv1
+        # backward sees them)
+        stem, bn0 = net.adpater[0], net.adpater[1]
         d0, s0, m0, i0, pidx = tape["stem"]
-        bn0 = net.adpater[1]
-        amp_stem = s0.dtype == torch.bfloat16       # bf16 conv output / pooled gradient in, bf16 gradient out (as autocast's conv1 backward sees it)
-        if amp and not amp_stem:
-            dcur = self._to_f32(dcur)
-        ring = amp_stem and self.stem_ring and d0.Wi % 4 == 0          # the row-ring weight gradient fetches the image in aligned groups of four columns
+        ring = amp and self.stem_ring and d0.Wi % 4 == 0          # the row-ring weight gradient fetches the image in aligned groups of four columns
+        # amp: the products on the bf16 MFMA (autocast: conv1 in bf16); ring: a bf16 stem gradient for the row-ring weight-gradient kernel
+        pool_bwd, pool_reduce, pool_apply, stem_wgrad = {
+            (False, False): (lib.sd_maxpool_bn_relu_bwd, lib.sd_maxpool_bn_relu_bwd_reduce, lib.sd_maxpool_bn_relu_bwd_apply, lib.sd_conv2d_stem_wgrad),
+            (True, False): (lib.sd_maxpool_bn_relu_bwd_bf16, lib.sd_maxpool_bn_relu_bwd_reduce_bf16, lib.sd_maxpool_bn_relu_bwd_apply_bf16,
+                            lib.sd_conv2d_stem_wgrad_bf16mm),
+            (True, True): (lib.sd_maxpool_bn_relu_bwd_bf16_dx16, lib.sd_maxpool_bn_relu_bwd_reduce_bf16, lib.sd_maxpool_bn_relu_bwd_apply_bf16_dx16,
+                           lib.sd_conv2d_stem_wgrad_bf16)}[amp, ring]
         ds0 = torch.empty(s0.shape, dtype=torch.bfloat16 if ring else torch.float32, device=s0.device)
         ws = self._ws(lib.sd_col_reduce_workspace_bytes(B * d0.Ho * d0.Wo, 64), s0.device)
+        head = (dcur.data_ptr(), pidx.data_ptr(), s0.data_ptr(), B, d0.Ho, d0.Wo, 64, m0.data_ptr(), i0.data_ptr(), bn0.weight.data_ptr(),
+                bn0.bias.data_ptr())
+        grads = (net.grad_of(bn0.weight).data_ptr(), net.grad_of(bn0.bias).data_ptr(), 0)
         if sx is None:
-            pool_bwd = lib.sd_maxpool_bn_relu_bwd_bf16_dx16 if ring else (lib.sd_maxpool_bn_relu_bwd_bf16 if amp_stem else lib.sd_maxpool_bn_relu_bwd)
-            L.check(pool_bwd(dcur.data_ptr(), pidx.data_ptr(), s0.data_ptr(), B, d0.Ho, d0.Wo, 64, m0.data_ptr(), i0.data_ptr(),
-                             bn0.weight.data_ptr(), bn0.bias.data_ptr(), ds0.data_ptr(), net.grad_of(bn0.weight).data_ptr(),
-                             net.grad_of(bn0.bias).data_ptr(), 0, ws.data_ptr(), ws.numel(), L.stream()), "sd_maxpool_bn_relu_bwd")
+            L.check(pool_bwd(*head, ds0.data_ptr(), *grads, ws.data_ptr(), ws.numel(), L.stream()), "sd_maxpool_bn_relu_bwd")
         else:                                         # synchronized BatchNorm: reduce half, exchange, means, apply half
             sums = sx.take(64)
             sx.record("sd_maxpool_bn_relu_bwd_reduce")
-            pool_reduce = lib.sd_maxpool_bn_relu_bwd_reduce_bf16 if amp_stem else lib.sd_maxpool_bn_relu_bwd_reduce
-            L.check(pool_reduce(dcur.data_ptr(), pidx.data_ptr(), s0.data_ptr(), B, d0.Ho, d0.Wo, 64, m0.data_ptr(), i0.data_ptr(),
-                                bn0.weight.data_ptr(), bn0.bias.data_ptr(), net.grad_of(bn0.weight).data_ptr(), net.grad_of(bn0.bias).data_ptr(), 0,
-                                sums.data_ptr(), ws.data_ptr(), ws.numel(), L.stream()), "sd_maxpool_bn_relu_bwd_reduce")
+            L.check(pool_reduce(*head, *grads, sums.data_ptr(), ws.data_ptr(), ws.numel(), L.stream()), "sd_maxpool_bn_relu_bwd_reduce")
             means = self._means_from_sums(sx, sums, 64, s0.device)
-            pool_apply = lib.sd_maxpool_bn_relu_bwd_apply_bf16_dx16 if ring else (lib.sd_maxpool_bn_relu_bwd_apply_bf16 if amp_stem
-                                                                                  else lib.sd_maxpool_bn_relu_bwd_apply)
-            L.check(pool_apply(dcur.data_ptr(), pidx.data_ptr(), s0.data_ptr(), B, d0.Ho, d0.Wo, 64, m0.data_ptr(), i0.data_ptr(),
-                               bn0.weight.data_ptr(), bn0.bias.data_ptr(), means.data_ptr(), ds0.data_ptr(), L.stream()), "sd_maxpool_bn_relu_bwd_apply")
-        stem = net.adpater[0]
+            L.check(pool_apply(*head, means.data_ptr(), ds0.data_ptr(), L.stream()), "sd_maxpool_bn_relu_bwd_apply")
         ws = self._ws(lib.sd_conv2d_stem_wgrad_workspace_bytes(C.byref(d0)), ds0.device)
-        # amp: product on the bf16 MFMA (autocast: conv1 in bf16); a bf16 stem gives a bf16 gradient (row-ring kernel)
-        stem_wgrad = lib.sd_conv2d_stem_wgrad_bf16 if ring else (lib.sd_conv2d_stem_wgrad_bf16mm if amp else lib.sd_conv2d_stem_wgrad)
         L.check(stem_wgrad(ds0.data_ptr(), tape["x"].data_ptr(), net.grad_of(stem.weight).data_ptr(), C.byref(d0), 0,
                            ws.data_ptr(), ws.numel(), L.stream()), "sd_conv2d_stem_wgrad")
         self._join_side()

@@ -662,3 +662,38 @@ def call_legacy_preprocess_form(fn_name, source, B, Hin, Win, out_size, flips, m
     L.check(getattr(lib, fn_name)(*args, *end, ws.data_ptr(), ws.numel(), L.stream()), fn_name)
     del keep
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# launch trace of the network engine (tests/test_gpu_engine_trace.py, tools/engine_trace.py)
+# ---------------------------------------------------------------------------------------------
+def _trace_arg(a):
+    """A `byref(struct)` as the struct's field tuple, a float as itself, an int below 2^20 as itself, anything else as 0 / "p" (null or not)."""
+    obj = getattr(a, "_obj", None)
+    if obj is not None and hasattr(obj, "_fields_"):
+        return tuple(getattr(obj, f) for f, _ in obj._fields_)
+    if isinstance(a, float):
+        return a
+    if isinstance(a, int):
+        return int(a) if a < 2 ** 20 else "p"
+    return "p" if a else 0
+
+
+class LaunchRecorder:
+    """Stand-in for `_Engine.lib`: every attribute is the real library's function behind a wrapper that first notes
+    (symbol, canonical arguments) in `calls`.  Entry point, geometry, flags, modes, the null-ness of every buffer and the order."""
+
+    def __init__(self, lib):
+        self._lib, self.calls = lib, []
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+
+        def call(*args):
+            self.calls.append((name, tuple(_trace_arg(a) for a in args)))
+            return fn(*args)
+        self.__dict__[name] = call
+        return call
+
+    def lines(self):
+        return [f"{name}({', '.join(repr(a) for a in args)})" for name, args in self.calls]
