@@ -56,12 +56,13 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+from collections import namedtuple
 
 import numpy as np
 import torch
 
 from .. import _lib as L
-from ..utils.args import parse_tiles, tile_canvas
+from ..utils.args import AUG_FLAGS, aug_flag, parse_tiles, tile_canvas
 from ..utils.misc import (affine_annotation, clip_annotation, hflip_annotation, letterbox_annotation, letterbox_geometry, mosaic_annotation,
                           perspective_annotation, transpose_annotation, vflip_annotation)
 
@@ -239,63 +240,61 @@ def mosaic_tiles(size, i, draw):
     return [cx, cy, i, *partners], inverse, forward, rects
 
 
-def _mosaic_tables(mosaic, B, device):
-    geom = torch.as_tensor(np.asarray(mosaic[0], dtype=np.int32)).reshape(-1, 6).contiguous()
-    mats = torch.as_tensor(np.asarray(mosaic[1], dtype=np.float64)).reshape(-1, 24).contiguous()
-    if geom.shape[0] != B or mats.shape[0] != B:
-        raise L.SdError("mosaic must have one geometry row of 6 integers and four matrices of 6 coefficients per image")
-    return geom.to(device, non_blocking=True), mats.to(device, non_blocking=True)
+# field of the chain's descriptor: (numpy dtype path, row width, message) of its per-image host table.  The integer tables of the late stages
+# go through int64 first, so a value past 2^31 wraps to the int32 bit pattern the library reads as uint32 instead of being refused.
+_I32, _WRAP32, _F64 = (np.int32,), (np.int64, np.int32), (np.float64,)
+_UPLOADS = {
+    "flips": ((np.uint8,), 1, "flips must have one entry per image"),
+    "jitter_order": (_I32, 1, "jitter parameters must have one row per image"),
+    "jitter_factors": ((np.float32,), 3, "jitter parameters must have one row per image"),
+    "mosaic_geom": (_I32, 6, "mosaic must have one geometry row of 6 integers and four matrices of 6 coefficients per image"),
+    "mosaic_affine": (_F64, 24, "mosaic must have one geometry row of 6 integers and four matrices of 6 coefficients per image"),
+    "window": (_I32, 2, "window must have one origin (x0, y0) per image"),
+    "affine": (_F64, 6, "affine must have one row of 6 coefficients per image"),
+    "persp": (_F64, 8, "persp must have one row of 8 coefficients per image"),
+    "blur": (_WRAP32, 3, "blur must have one row (R, ww, fw) per image"),
+    "noise": (_WRAP32, 4, "noise must have one row (k0, k1, a, b) per image"),
+    "jpeg": (_WRAP32, 129, "jpeg must have one row (on, ql[64], qc[64]) per image"),
+    "tone": (_WRAP32, 4, "tone must have one row (mode, cut_lo, cut_hi, 0) per image"),
+}
 
 
-def _affine_rows(affine, B, device):
-    rows = torch.as_tensor(np.asarray(affine, dtype=np.float64)).reshape(-1, 6).contiguous()
-    if rows.shape[0] != B:
-        raise L.SdError("affine must have one row of 6 coefficients per image")
-    return rows.to(device, non_blocking=True)
-
-
-def _flip_table(flips, B, device):
-    table = torch.as_tensor(flips, dtype=torch.uint8).to(device, non_blocking=True)
-    if table.numel() != B:
-        raise L.SdError("flips must have one entry per image")
-    return table
-
-
-def _jitter_tables(jitter, B, device):
-    order = torch.as_tensor(jitter[0], dtype=torch.int32).to(device, non_blocking=True)
-    factors = torch.as_tensor(jitter[1], dtype=torch.float32).reshape(-1, 3).contiguous().to(device, non_blocking=True)
-    if order.numel() != B or factors.shape[0] != B:
-        raise L.SdError("jitter parameters must have one row per image")
-    return order, factors
-
-
-def _window_origins(origins, B, device):
-    table = torch.as_tensor(np.asarray(origins, dtype=np.int32)).reshape(-1, 2).contiguous()
+def _upload(field, rows, B, device):
+    """The host table `rows` of `field` (_UPLOADS) as a contiguous device tensor of B rows."""
+    path, width, message = _UPLOADS[field]
+    table = np.asarray(rows.cpu() if isinstance(rows, torch.Tensor) else rows, dtype=path[0])
+    for dtype in path[1:]:
+        table = table.astype(dtype)
+    table = torch.as_tensor(np.ascontiguousarray(table.reshape(-1, width) if width > 1 else table.reshape(-1)))
     if table.shape[0] != B:
-        raise L.SdError("window must have one origin (x0, y0) per image")
+        raise L.SdError(message)
     return table.to(device, non_blocking=True)
 
-def _persp_rows(persp, B, device):
-    rows = torch.as_tensor(np.asarray(persp, dtype=np.float64)).reshape(-1, 8).contiguous()
-    if rows.shape[0] != B:
-        raise L.SdError("persp must have one row of 8 coefficients per image")
-    return rows.to(device, non_blocking=True)
+
+def _run_stage(name, images, rows, field=None, workspace=None, extra=()):
+    """The shared body of the stand-alone stages `<name>_images`: images (B, H, W, 3) uint8 on the GPU and the B rows of the chain's table
+    `field` (default: name) -> a new tensor from `sd_<name>_u8`, called with `extra` behind the table and, when workspace(lib, B, H, W)
+    gives a size, that workspace."""
+    L.require_cuda(images)
+    if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3:
+        raise L.SdError(f"{name}_images expects (B, H, W, 3) uint8, got {tuple(images.shape)} {images.dtype}")
+    images = images.contiguous()
+    B, H, W, _ = images.shape
+    table = _upload(field or name, rows, B, images.device)
+    out = torch.empty_like(images)
+    lib = L.lib()
+    if workspace is not None:
+        ws = L.workspace(workspace(lib, B, H, W), images.device)
+        extra = (*extra, ws.data_ptr(), ws.numel())
+    L.check(getattr(lib, f"sd_{name}_u8")(images.data_ptr(), out.data_ptr(), B, H, W, table.data_ptr(), *extra, L.stream()), f"sd_{name}_u8")
+    return out
 
 
 def perspective_images(images: torch.Tensor, persp, fill=_FILL) -> torch.Tensor:
     """images: (B, H, W, 3) uint8 on the GPU; persp: B rows of 8 coefficients as `perspective_coeffs` makes them.  Returns a new tensor,
     image b = `Image.transform((W, H), PERSPECTIVE, persp_b, BILINEAR, fillcolor=fill)` byte for byte (`sd_perspective_u8`: the stand-alone
     stage of the chain)."""
-    L.require_cuda(images)
-    if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3:
-        raise L.SdError(f"perspective_images expects (B, H, W, 3) uint8, got {tuple(images.shape)} {images.dtype}")
-    images = images.contiguous()
-    B, H, W, _ = images.shape
-    rows = _persp_rows(persp, B, images.device)
-    out = torch.empty_like(images)
-    L.check(L.lib().sd_perspective_u8(images.data_ptr(), out.data_ptr(), B, H, W, rows.data_ptr(), (C.c_ubyte * 3)(*fill), L.stream()),
-            "sd_perspective_u8")
-    return out
+    return _run_stage("perspective", images, persp, field="persp", extra=((C.c_ubyte * 3)(*fill),))
 
 
 def blur_box_params(r):
@@ -318,27 +317,10 @@ def blur_box_params(r):
     return R, ww, ((1 << 24) - (2 * R + 1) * ww) // 2
 
 
-def _blur_rows(blur, B, device):
-    rows = torch.as_tensor(np.asarray(blur, dtype=np.int64).astype(np.int32)).reshape(-1, 3).contiguous()
-    if rows.shape[0] != B:
-        raise L.SdError("blur must have one row (R, ww, fw) per image")
-    return rows.to(device, non_blocking=True)
-
-
 def blur_images(images: torch.Tensor, blur) -> torch.Tensor:
     """images: (B, H, W, 3) uint8 on the GPU; blur: B rows (R, ww, fw) as `blur_box_params` makes them.  Returns a new tensor, image b =
     `Image.filter(ImageFilter.GaussianBlur(r_b))` byte for byte (`sd_blur_u8`: the stand-alone stage of the chain)."""
-    L.require_cuda(images)
-    if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3:
-        raise L.SdError(f"blur_images expects (B, H, W, 3) uint8, got {tuple(images.shape)} {images.dtype}")
-    images = images.contiguous()
-    B, H, W, _ = images.shape
-    rows = _blur_rows(blur, B, images.device)
-    out = torch.empty_like(images)
-    lib = L.lib()
-    ws = L.workspace(lib.sd_blur_workspace_bytes(B, H, W), images.device)
-    L.check(lib.sd_blur_u8(images.data_ptr(), out.data_ptr(), B, H, W, rows.data_ptr(), ws.data_ptr(), ws.numel(), L.stream()), "sd_blur_u8")
-    return out
+    return _run_stage("blur", images, blur, workspace=lambda lib, B, H, W: lib.sd_blur_workspace_bytes(B, H, W))
 
 
 # Annex K of the JPEG standard: the luminance and chrominance quantisation tables of quality 50, natural (row-major) order
@@ -370,28 +352,11 @@ def jpeg_rows(qualities):
     return rows
 
 
-def _jpeg_rows(rows, B, device):
-    table = torch.as_tensor(np.asarray(rows, dtype=np.int64).astype(np.int32)).reshape(-1, 129).contiguous()
-    if table.shape[0] != B:
-        raise L.SdError("jpeg must have one row (on, ql[64], qc[64]) per image")
-    return table.to(device, non_blocking=True)
-
-
 def jpeg_images(images: torch.Tensor, rows) -> torch.Tensor:
     """images: (B, H, W, 3) uint8 on the GPU with H and W multiples of 16; rows: B rows [on, ql[64], qc[64]] as `jpeg_rows` makes them.
     Returns a new tensor, image b = Pillow's `save(buf, "JPEG", quality=q_b)` then `open(buf)` byte for byte (`sd_jpeg_u8`: the stand-alone
     stage of the chain)."""
-    L.require_cuda(images)
-    if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3:
-        raise L.SdError(f"jpeg_images expects (B, H, W, 3) uint8, got {tuple(images.shape)} {images.dtype}")
-    images = images.contiguous()
-    B, H, W, _ = images.shape
-    table = _jpeg_rows(rows, B, images.device)
-    out = torch.empty_like(images)
-    lib = L.lib()
-    ws = L.workspace(lib.sd_jpeg_workspace_bytes(B, H, W), images.device)
-    L.check(lib.sd_jpeg_u8(images.data_ptr(), out.data_ptr(), B, H, W, table.data_ptr(), ws.data_ptr(), ws.numel(), L.stream()), "sd_jpeg_u8")
-    return out
+    return _run_stage("jpeg", images, rows, workspace=lambda lib, B, H, W: lib.sd_jpeg_workspace_bytes(B, H, W))
 
 
 TONE_COPY, TONE_AUTOCONTRAST, TONE_EQUALIZE = 0, 1, 2               # the modes of `sd_tone_u8`'s table
@@ -409,28 +374,11 @@ def tone_rows(draws, n_pixels):
     return rows
 
 
-def _tone_rows(rows, B, device):
-    table = torch.as_tensor(np.asarray(rows, dtype=np.int64).astype(np.int32)).reshape(-1, 4).contiguous()
-    if table.shape[0] != B:
-        raise L.SdError("tone must have one row (mode, cut_lo, cut_hi, 0) per image")
-    return table.to(device, non_blocking=True)
-
-
 def tone_images(images: torch.Tensor, rows) -> torch.Tensor:
     """images: (B, H, W, 3) uint8 on the GPU, any H and W; rows: B rows [mode, cut_lo, cut_hi, 0] as `tone_rows` makes them.  Returns a
     new tensor, image b = Pillow's `ImageOps.autocontrast` (mode 1) or `ImageOps.equalize` (mode 2) of image b byte for byte, or image b
     itself (`sd_tone_u8`: the stand-alone stage of the chain)."""
-    L.require_cuda(images)
-    if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3:
-        raise L.SdError(f"tone_images expects (B, H, W, 3) uint8, got {tuple(images.shape)} {images.dtype}")
-    images = images.contiguous()
-    B, H, W, _ = images.shape
-    table = _tone_rows(rows, B, images.device)
-    out = torch.empty_like(images)
-    lib = L.lib()
-    ws = L.workspace(lib.sd_tone_workspace_bytes(B), images.device)
-    L.check(lib.sd_tone_u8(images.data_ptr(), out.data_ptr(), B, H, W, table.data_ptr(), ws.data_ptr(), ws.numel(), L.stream()), "sd_tone_u8")
-    return out
+    return _run_stage("tone", images, rows, workspace=lambda lib, B, H, W: lib.sd_tone_workspace_bytes(B))
 
 
 def noise_rows(draws):
@@ -442,26 +390,11 @@ def noise_rows(draws):
             for k0, k1, sigma, gain in draws]
 
 
-def _noise_rows(rows, B, device):
-    table = torch.as_tensor(np.asarray(rows, dtype=np.int64).astype(np.int32)).reshape(-1, 4).contiguous()
-    if table.shape[0] != B:
-        raise L.SdError("noise must have one row (k0, k1, a, b) per image")
-    return table.to(device, non_blocking=True)
-
-
 def noise_images(images: torch.Tensor, rows) -> torch.Tensor:
     """images: (B, H, W, 3) uint8 on the GPU, any H and W; rows: B rows [k0, k1, a, b] as `noise_rows` makes them.  Returns a new tensor,
     image b = image b with the sensor noise of its row, byte for byte tests/noise_ref.py's `noise_ref`, or image b itself for a row with
     a = b = 0 (`sd_noise_u8`: the stand-alone stage of the chain)."""
-    L.require_cuda(images)
-    if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3:
-        raise L.SdError(f"noise_images expects (B, H, W, 3) uint8, got {tuple(images.shape)} {images.dtype}")
-    images = images.contiguous()
-    B, H, W, _ = images.shape
-    table = _noise_rows(rows, B, images.device)
-    out = torch.empty_like(images)
-    L.check(L.lib().sd_noise_u8(images.data_ptr(), out.data_ptr(), B, H, W, table.data_ptr(), L.stream()), "sd_noise_u8")
-    return out
+    return _run_stage("noise", images, rows)
 
 
 JPEG_MAX_QUALITY = 95                                                # the upper end of `--aug_jpeg`'s quality range (Pillow's advised maximum)
@@ -492,7 +425,7 @@ def _chain_desc(source, is_list, B, Hin, Win, out_size, flips, mean, std, jitter
         Wt, Ht = int(Wc), int(Hc)
         if not (0 < Wout <= Wt and 0 < Hout <= Ht):
             raise L.SdError(f"window: {Wout} x {Hout} does not fit the canvas {Wt} x {Ht}")
-        org = _window_origins(origins, B, dev)
+        org = _upload("window", origins, B, dev)
         d.geometry, d.Hg, d.Wg, d.window = GEOM_WINDOW, Ht, Wt, org.data_ptr()
         d.g0, d.g1 = window_extents(Hin, Ht, Hout), window_extents(Win, Wt, Wout)   # (the LDS limit of the list form binds g1, the column span)
     hb, hk, d.h_ksize = _tables.get(Win, Wt, dev)
@@ -502,21 +435,12 @@ def _chain_desc(source, is_list, B, Hin, Win, out_size, flips, mean, std, jitter
     d.out, d.fill3, d.mean3, d.std3 = out.data_ptr(), (C.c_ubyte * 3)(*_FILL), (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
     keep = [org, hb, hk, vb, vk]
 
-    def table(field, tensor):
-        setattr(d, field, tensor.data_ptr())
-        keep.append(tensor)
-    if flips is not None:
-        table("flips", _flip_table(flips, B, dev))
-    if jitter is not None:
-        order, factors = _jitter_tables(jitter, B, dev)
-        table("jitter_order", order); table("jitter_factors", factors)
-    if mosaic is not None:
-        geom, mats = _mosaic_tables(mosaic, B, dev)
-        table("mosaic_geom", geom); table("mosaic_affine", mats)
-    for field, rows, upload in (("affine", affine, _affine_rows), ("persp", persp, _persp_rows), ("blur", blur, _blur_rows),
-                                ("noise", noise, _noise_rows), ("jpeg", jpeg, _jpeg_rows), ("tone", tone, _tone_rows)):
+    given = dict(flips=flips, jitter_order=jitter and jitter[0], jitter_factors=jitter and jitter[1], mosaic_geom=mosaic and mosaic[0],
+                 mosaic_affine=mosaic and mosaic[1], affine=affine, persp=persp, blur=blur, noise=noise, jpeg=jpeg, tone=tone)
+    for field, rows in given.items():
         if rows is not None:
-            table(field, upload(rows, B, dev))
+            keep.append(_upload(field, rows, B, dev))
+            setattr(d, field, keep[-1].data_ptr())
     return d, out, keep
 
 
@@ -608,6 +532,16 @@ class _Objects:
         self.objects = list(objects)
 
 
+# The draw steps of one batch, in the order in which they consume torch's global generator: the only place that order is written
+# (`draw_all` runs them, `Draws` names their answers).  A step that is off draws nothing and answers None.
+DRAW_STEPS = ("draws_for", "affine_draws_for", "mosaic_draws_for", "window_draws_for", "transpose_draws_for", "blur_draws_for",
+              "perspective_draws_for", "jpeg_draws_for", "tone_draws_for", "noise_draws_for")
+Draws = namedtuple("Draws", ["base" if step == "draws_for" else step[:-len("_draws_for")] for step in DRAW_STEPS])     # base = (flips, jitter)
+# One batch's draws and what is derived from them once: the affine matrices (source <- output and its forward twin), with a perspective draw
+# the homographies they are folded into (then `inverse` is not passed on) and the perspective's forward twins, and the mosaic tiles.
+_Plan = namedtuple("_Plan", "draws inverse forward6 homography forward8 tiles")
+
+
 class ValidationAugmentation:
     """transforms.py:255-261 for a batch: Resize((width, height)) + Normalize (+ the clip Encode applies, transforms.py:154).  With
     `--keep_aspect` the Resize is a letterbox, its geometry computed per size group at the current size (`letterbox_geometry`)."""
@@ -621,41 +555,13 @@ class ValidationAugmentation:
         """(flips, jitter) for n samples: validation draws nothing."""
         return None, None
 
-    def affine_draws_for(self, n):
-        """(angle, scale, tx, ty) per sample, or None: validation never warps and never draws."""
+    def _no_draw(self, n, groups=None):
+        """Every other step of DRAW_STEPS (set below the class): validation has none of these stages and never draws."""
         return None
 
-    def mosaic_draws_for(self, n, groups):
-        """Per sample None or (cx, cy, partners), or None for the batch: validation never composes and never draws."""
-        return None
-
-    def window_draws_for(self, n):
-        """((Wc, Hc), n origins (x0, y0)) or None: validation always shows the whole frame and never draws."""
-        return None
-
-    def transpose_draws_for(self, n):
-        """n flags (1 = the sample is transposed) or None: validation never transposes and never draws."""
-        return None
-
-    def blur_draws_for(self, n):
-        """n gaussian radii (0.0 = the sample stays sharp) or None: validation never blurs and never draws."""
-        return None
-
-    def perspective_draws_for(self, n):
-        """Per sample None or the four output corners (tl, tr, br, bl), or None for the batch: validation never warps and never draws."""
-        return None
-
-    def jpeg_draws_for(self, n):
-        """n JPEG qualities (0 = the sample is not compressed) or None: validation never compresses and never draws."""
-        return None
-
-    def tone_draws_for(self, n):
-        """n tone draws (mode, cutoff percent) or None: validation never changes the tone curve and never draws."""
-        return None
-
-    def noise_draws_for(self, n):
-        """n noise draws (k0, k1, sigma_read, gain) or None: validation never adds noise and never draws."""
-        return None
+    def draw_all(self, n, groups):
+        """The draws of a batch of n samples, every step of DRAW_STEPS in that order; groups = the index lists of its size groups."""
+        return Draws(*(getattr(self, step)(n, groups) if step == "mosaic_draws_for" else getattr(self, step)(n) for step in DRAW_STEPS))
 
     @staticmethod
     def size_groups(images):
@@ -670,124 +576,136 @@ class ValidationAugmentation:
             by_size.setdefault(tuple(t.shape[:2]), []).append((i, t))
         return {k: ([i for i, _ in v], torch.stack([t for _, t in v])) for k, v in by_size.items()}
 
+    def _resample(self, groups, size, tables, then=None):
+        """One chain call per size group at `size` with the keyword tables `tables(idx, (win, hin))` gives, packed or by pointer list, and
+        the results scattered to the samples' places: the (B, 3, height, width) tensor.  `then(idx, (win, hin))` runs behind each group's
+        call: host work there is hidden behind the device's (the next group's first upload waits for this group's kernels)."""
+        dev = self.args.device
+        out = None
+        for (hin, win), (idx, stack) in groups.items():
+            if hasattr(stack, "pointers"):                           # data/image_cache.py ImageList: cached / uploaded images by address
+                res = preprocess_image_list(stack.pointers, hin, win, size, **tables(idx, (win, hin)))
+            else:
+                res = preprocess_images(stack.to(dev, non_blocking=True), size, **tables(idx, (win, hin)))
+            if len(groups) == 1:
+                out = res
+            else:
+                if out is None:
+                    out = torch.empty((sum(len(i) for i, _ in groups.values()), 3, size[1], size[0]), dtype=torch.float32, device=dev)
+                out[torch.as_tensor(idx, device=dev)] = res
+            if then is not None:
+                then(idx, (win, hin))
+        return out
+
     def images_at(self, images, size):
         """The Resize + Normalize of `__call__` at another `size` = (width, height), from the same SOURCE images: the
         (B, 3, height, width) tensor only.  No annotation is touched (`__call__` edits them in place, once) and nothing is drawn: this
         is the plain validation transform, what the multi-scale test (model/tta.py ScaleTta) runs at its extra sizes."""
-        dev = self.args.device
-        W, H = size
-        groups = self.size_groups(images)
-        out = None
-        for (hin, win), (idx, stack) in groups.items():
-            box = letterbox_geometry((win, hin), (W, H)) if self.keep_aspect else None
-            if hasattr(stack, "pointers"):
-                res = preprocess_image_list(stack.pointers, hin, win, (W, H), letterbox=box)
-            else:
-                res = preprocess_images(stack.to(dev, non_blocking=True), (W, H), letterbox=box)
-            if len(groups) == 1:
-                return res
-            if out is None:
-                out = torch.empty((sum(len(i) for i, _ in groups.values()), 3, H, W), dtype=torch.float32, device=dev)
-            out[torch.as_tensor(idx, device=dev)] = res
-        return out
+        return self._resample(self.size_groups(images), tuple(size),
+                              lambda idx, src: dict(letterbox=letterbox_geometry(src, tuple(size))) if self.keep_aspect else {})
+
+    def _plan(self, n, groups):
+        """The draws of one batch and what follows from them once per batch (_Plan), after the two refusals."""
+        W, H = self.size
+        d = self.draw_all(n, groups)
+        inverse = forward6 = homography = forward8 = tiles = None
+        if d.affine is not None:
+            inverse = [affine_inverse_matrix((W, H), a, s, (tx, ty)) for a, s, tx, ty in d.affine]
+            forward6 = [affine_forward_matrix((W, H), a, s, (tx, ty)) for a, s, tx, ty in d.affine]
+        if d.perspective is not None:                                # the warp slot becomes one homography per image: affine, then perspective
+            frame = [(0.0, 0.0), (float(W), 0.0), (float(W), float(H)), (0.0, float(H))]
+            ident6, ident8 = [1.0, 0.0, 0.0, 0.0, 1.0, 0.0], [1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0]
+            homography = [compose_affine_perspective(ident6 if inverse is None else inverse[i], ident8 if quad is None else perspective_coeffs(frame, quad))
+                          for i, quad in enumerate(d.perspective)]
+            forward8 = [None if quad is None else perspective_coeffs(quad, frame) for quad in d.perspective]
+        if d.mosaic is not None:
+            tiles = [mosaic_tiles((W, H), i, draw) for i, draw in enumerate(d.mosaic)]
+        if d.transpose is not None and W != H:
+            raise L.SdError(f"aug_transpose: a transposed sample needs a square batch, not {W} x {H}")
+        if d.window is not None and self.keep_aspect:
+            raise L.SdError("keep_aspect does not combine with train_tiles: a window is cut from the stretched canvas")
+        return _Plan(d, inverse, forward6, homography, forward8, tiles)
+
+    def _group_tables(self, plan, idx, src):
+        """The keyword tables of one size group's chain call: the rows of its samples `idx`, in the group's order."""
+        W, H = self.size
+        d = plan.draws
+        pick = lambda rows: [rows[i] for i in idx]
+        kw = {}
+        if d.base[0] is not None:
+            kw["flips"] = pick(d.base[0])
+        if d.base[1] is not None:
+            kw["jitter"] = (pick(d.base[1][0]), pick(d.base[1][1]))
+        if plan.homography is not None:                              # (the affine draw is folded in: `affine=` is not passed)
+            kw["persp"] = pick(plan.homography)
+        elif plan.inverse is not None:
+            kw["affine"] = pick(plan.inverse)
+        if plan.tiles is not None:                                   # the kernel's sources index this group's stack: partners come from the group
+            where = {i: k for k, i in enumerate(idx)}
+            kw["mosaic"] = ([[*plan.tiles[i][0][:2], *(where[s] for s in plan.tiles[i][0][2:])] for i in idx], [plan.tiles[i][1] for i in idx])
+        if d.window is not None:
+            kw["window"] = (d.window[0], pick(d.window[1]))
+        for stage, rows_of in (("blur", lambda radii: [blur_box_params(r) for r in radii]), ("jpeg", jpeg_rows),
+                               ("tone", lambda draws: tone_rows(draws, W * H)), ("noise", noise_rows)):
+            if getattr(d, stage) is not None:                        # photometric: the annotations do not move; the cuts count pixels of the input
+                kw[stage] = rows_of(pick(getattr(d, stage)))
+        if self.keep_aspect:                                         # one geometry per size group, at the current (multi-scale) size
+            kw["letterbox"] = letterbox_geometry(src, (W, H))
+        return kw
+
+    def _move_annotations(self, plan, annotations, idx, src):
+        """The annotations of one size group (source size `src`) through what its images went through, in the images' order: 1 resize or
+        letterbox or window, 2 mosaic, 3 affine or affine + perspective, 4 hflip, 5 vflip, 6 transpose, 7 clip."""
+        W, H = self.size
+        d = plan.draws
+        for i in idx:
+            ann = annotations[i]
+            ann.img_size = ann.img_size or src
+            if self.keep_aspect:                                     # 1: to the inner image, then to its place in the frame: nothing leaves it
+                letterbox_annotation(ann, src, (W, H))
+            elif d.window is None:
+                ann.resize(src, (W, H))                              # transforms.py:58
+            else:                                                    # to the canvas, then into the window: what leaves it is dropped
+                x0, y0 = d.window[1][i]
+                ann.resize(src, d.window[0])
+                affine_annotation(ann, [1.0, 0.0, -float(x0), 0.0, 1.0, -float(y0)], (W, H))
+        if plan.tiles is not None:                                   # 2: an image is itself and maybe someone's partner: compose from the
+            resized = {i: _Objects(annotations[i].objects) for i in idx}      # resized objects of the whole group, as they were
+            for i in idx:
+                if d.mosaic[i] is not None:
+                    geom, _, forward, rects = plan.tiles[i]
+                    mosaic_annotation(annotations[i], [resized[s] for s in geom[2:]], forward, rects)
+        flips, transposes, affine, persp = d.base[0], d.transpose, plan.forward6, plan.forward8
+        for i in idx:
+            ann = annotations[i]
+            forward6 = None if affine is None else affine[i]
+            if persp is not None and persp[i] is not None:           # 3: affine, then perspective; one inside test at the end
+                perspective_annotation(ann, persp[i], (W, H), affine_forward=forward6)
+            elif forward6 is not None:                               # on the resized image, before the flips: drops what leaves the frame
+                affine_annotation(ann, forward6, (W, H))
+            if flips is not None and flips[i] & 1:
+                hflip_annotation(ann, (W, H))                        # 4: transforms.py:15 (on the resized image)
+            if flips is not None and flips[i] & 2:
+                vflip_annotation(ann, (W, H))                        # 5: transforms.py:28
+            if transposes is not None and transposes[i]:
+                transpose_annotation(ann, (W, H))                    # 6: last, like the image's
+            clip_annotation(ann, (W, H))                             # 7: transforms.py:154
 
     def __call__(self, images, annotations):
         """images: list of (H, W, 3) uint8 arrays / tensors (any sizes) or one (B, H, W, 3) tensor; annotations: list of
         ImageAnnotation in ORIGINAL image pixels (modified in place like the reference's Resize / flips / Encode clip do on their
         copies).  Returns ((B, 3, height, width) fp32 device tensor, annotations in network-input pixels)."""
-        dev = self.args.device
-        W, H = self.size
         groups = self.size_groups(images)
-        n = sum(len(idx) for idx, _ in groups.values())
-        flips, jitter = self.draws_for(n)
-        warps = self.affine_draws_for(n)
-        inverse = None if warps is None else [affine_inverse_matrix((W, H), a, s, (tx, ty)) for a, s, tx, ty in warps]
-        mosaics = self.mosaic_draws_for(n, [idx for idx, _ in groups.values()])
-        windows = self.window_draws_for(n)
-        transposes = self.transpose_draws_for(n)
-        blurs = self.blur_draws_for(n)
-        quads = self.perspective_draws_for(n)
-        qualities = self.jpeg_draws_for(n)
-        tones = self.tone_draws_for(n)
-        noises = self.noise_draws_for(n)
-        homography = forward8 = None
-        if quads is not None:                                        # the warp slot becomes one homography per image: affine, then perspective
-            frame = [(0.0, 0.0), (float(W), 0.0), (float(W), float(H)), (0.0, float(H))]
-            ident6, ident8 = [1.0, 0.0, 0.0, 0.0, 1.0, 0.0], [1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0]
-            homography = [compose_affine_perspective(ident6 if inverse is None else inverse[i],
-                                                     ident8 if quads[i] is None else perspective_coeffs(frame, quads[i])) for i in range(n)]
-            forward8 = [None if quads[i] is None else perspective_coeffs(quads[i], frame) for i in range(n)]
-        if transposes is not None and W != H:
-            raise L.SdError(f"aug_transpose: a transposed sample needs a square batch, not {W} x {H}")
-        if windows is not None and self.keep_aspect:
-            raise L.SdError("keep_aspect does not combine with train_tiles: a window is cut from the stretched canvas")
-        out = torch.empty((n, 3, H, W), dtype=torch.float32, device=dev)
-        for (hin, win), (idx, stack) in groups.items():
-            f = None if flips is None else [flips[i] for i in idx]
-            j = None if jitter is None else ([jitter[0][i] for i in idx], [jitter[1][i] for i in idx])
-            m = None if inverse is None or homography is not None else [inverse[i] for i in idx]
-            kw = {}
-            if homography is not None:                               # (the affine draw is folded in: `affine=` is not passed)
-                kw["persp"] = [homography[i] for i in idx]
-            if mosaics is not None:                                  # the kernel's sources index this group's stack: partners come from the group
-                where = {i: k for k, i in enumerate(idx)}
-                tiles = {i: mosaic_tiles((W, H), i, mosaics[i]) for i in idx}
-                kw["mosaic"] = ([[*tiles[i][0][:2], *(where[s] for s in tiles[i][0][2:])] for i in idx], [tiles[i][1] for i in idx])
-            if windows is not None:
-                kw["window"] = (windows[0], [windows[1][i] for i in idx])
-            if blurs is not None:                                    # photometric: the annotations do not move
-                kw["blur"] = [blur_box_params(blurs[i]) for i in idx]
-            if qualities is not None:                                # photometric as well
-                kw["jpeg"] = jpeg_rows(qualities[i] for i in idx)
-            if tones is not None:                                    # photometric as well; the cuts count pixels of the network input
-                kw["tone"] = tone_rows((tones[i] for i in idx), W * H)
-            if noises is not None:                                   # photometric as well; the key and the strengths of each sample
-                kw["noise"] = noise_rows(noises[i] for i in idx)
-            box = None
-            if self.keep_aspect:                                     # one geometry per size group, at the current (multi-scale) size
-                box = kw["letterbox"] = letterbox_geometry((win, hin), (W, H))
-            if hasattr(stack, "pointers"):                           # data/image_cache.py ImageList: cached / uploaded images by address
-                res = preprocess_image_list(stack.pointers, hin, win, (W, H), f, jitter=j, affine=m, **kw)
-            else:
-                res = preprocess_images(stack.to(dev, non_blocking=True), (W, H), f, jitter=j, affine=m, **kw)
-            if len(groups) == 1:
-                out = res
-            else:
-                out[torch.as_tensor(idx, device=dev)] = res
-            for i in idx:
-                ann = annotations[i]
-                ann.img_size = ann.img_size or (win, hin)
-                if box is not None:                                  # to the inner image, then to its place in the frame: nothing leaves it
-                    letterbox_annotation(ann, (win, hin), (W, H))
-                elif windows is None:
-                    ann.resize((win, hin), (W, H))                   # transforms.py:58
-                else:                                                # to the canvas, then into the window: what leaves it is dropped
-                    x0, y0 = windows[1][i]
-                    ann.resize((win, hin), windows[0])
-                    affine_annotation(ann, [1.0, 0.0, -float(x0), 0.0, 1.0, -float(y0)], (W, H))
-            if mosaics is not None:                                  # an image is itself and maybe someone's partner: compose from the
-                resized = {i: _Objects(annotations[i].objects) for i in idx}      # resized objects of the whole group, as they were
-                for i in idx:
-                    if mosaics[i] is not None:
-                        geom, _, forward, rects = tiles[i]
-                        mosaic_annotation(annotations[i], [resized[s] for s in geom[2:]], forward, rects)
-            for i in idx:
-                ann = annotations[i]
-                forward6 = None if warps is None else affine_forward_matrix((W, H), warps[i][0], warps[i][1], warps[i][2:])
-                if forward8 is not None and forward8[i] is not None:  # affine, then perspective; one inside test at the end
-                    perspective_annotation(ann, forward8[i], (W, H), affine_forward=forward6)
-                elif forward6 is not None:                           # on the resized image, before the flips: drops what leaves the frame
-                    affine_annotation(ann, forward6, (W, H))
-                if flips is not None and flips[i] & 1:
-                    hflip_annotation(ann, (W, H))                    # transforms.py:15 (on the resized image)
-                if flips is not None and flips[i] & 2:
-                    vflip_annotation(ann, (W, H))                    # transforms.py:28
-                if transposes is not None and transposes[i]:
-                    transpose_annotation(ann, (W, H))                # last, like the image's
-                clip_annotation(ann, (W, H))                         # transforms.py:154
-        if transposes is not None:                                   # one launch over the assembled batch, after the flips
-            out = transpose_select(out, transposes)
+        plan = self._plan(sum(len(idx) for idx, _ in groups.values()), [idx for idx, _ in groups.values()])
+        out = self._resample(groups, tuple(self.size), lambda idx, src: self._group_tables(plan, idx, src),
+                             then=lambda idx, src: self._move_annotations(plan, annotations, idx, src))
+        if plan.draws.transpose is not None:                         # one launch over the assembled batch, after the flips
+            out = transpose_select(out, plan.draws.transpose)
         return out, annotations
+
+
+for _step in DRAW_STEPS[1:]:
+    setattr(ValidationAugmentation, _step, ValidationAugmentation._no_draw)
 
 
 class TrainAugmentation(ValidationAugmentation):
@@ -797,7 +715,8 @@ class TrainAugmentation(ValidationAugmentation):
     factors uniform in [1 - x, 1 + x], hue in [-x, x]), `randn < prob` for each flip (transforms.py:14,27: a normal, not a uniform,
     draw: the flip probability is Phi(0.5) = 0.69), `torch.randint` for the multi-scale ratio -- from torch's global generator (the
     reference draws them inside DataLoader worker processes with per-worker seeds: its stream is not reproducible across worker counts,
-    so the distributions, not a draw order, are what there is to match)."""
+    so the distributions, not a draw order, are what there is to match).  The order in which one batch's steps consume the generator
+    is DRAW_STEPS; every attribute a step reads (rotate .. noise_shot) is its `--aug_*` flag of utils/args.py AUG_FLAGS."""
 
     ratios = (0.75, 0.8125, 0.875, 0.9375, 1, 1.0625, 1.125, 1.1875, 1.25)
     brightness, contrast, saturation, hue = 0.25, 0.25, 0.15, 0.05            # transforms.py:38
@@ -805,19 +724,8 @@ class TrainAugmentation(ValidationAugmentation):
     def __init__(self, args, prob=0.5):
         super().__init__(args)
         self.prob = prob
-        self.rotate = float(getattr(args, "aug_rotate", 0.0))              # degrees: angle uniform in [-rotate, rotate]
-        self.scale = float(getattr(args, "aug_scale", 0.0))                # scale uniform in [1 - scale, 1 + scale]
-        self.translate = float(getattr(args, "aug_translate", 0.0))        # shift uniform in [-translate, translate] * (width, height)
-        self.mosaic = float(getattr(args, "aug_mosaic", 0.0))              # per-image probability of becoming a mosaic of four
-        self.transpose = float(getattr(args, "aug_transpose", 0.0))        # per-image probability of being transposed (square sizes only)
-        self.blur = float(getattr(args, "aug_blur", 0.0) or 0.0)           # gaussian radius uniform in [0, blur] pixels for a selected image
-        self.perspective = float(getattr(args, "aug_perspective", 0.0) or 0.0)   # distortion scale of a selected image's corner insets
-        self.jpeg = int(getattr(args, "aug_jpeg", 0) or 0)                 # a selected image is JPEG-compressed at a quality uniform in [jpeg, 95]
-        self.equalize = float(getattr(args, "aug_equalize", 0.0) or 0.0)   # per-image probability of ImageOps.equalize
-        self.autocontrast = float(getattr(args, "aug_autocontrast", 0.0) or 0.0)   # per-image probability of ImageOps.autocontrast (when not equalized)
-        self.autocontrast_cutoff = float(getattr(args, "aug_autocontrast_cutoff", 1.0) or 0.0)   # its cutoff is uniform in [0, this] percent
-        self.noise = float(getattr(args, "aug_noise", 0.0) or 0.0)         # read noise of a selected image: sigma uniform in [0, noise] grey levels
-        self.noise_shot = float(getattr(args, "aug_noise_shot", 0.0) or 0.0)   # its shot gain: uniform in [0, noise_shot] levels^2 per level
+        for name, row in AUG_FLAGS.items():                          # rotate, scale, translate, mosaic, transpose, blur, perspective, jpeg, equalize,
+            setattr(self, name[4:], type(row.default)(aug_flag(args, name)))    # autocontrast(_cutoff), noise(_shot): what the `*_draws_for` below read
         self.train_tiles = parse_tiles(getattr(args, "train_tiles", ""), "train_tiles")   # (Tx, Ty) of the canvas the windows are cut from, () = off
         self.tile_overlap = int(getattr(args, "tile_overlap", 64))
 
@@ -843,8 +751,8 @@ class TrainAugmentation(ValidationAugmentation):
         return flip_bits, (words, factors)
 
     def affine_draws_for(self, n):
-        """(angle, scale, tx, ty) of n samples (torchvision RandomAffine.get_params' distributions, the shift left unrounded) from ONE more
-        draw on torch's global generator, made after those of `draws_for`; None, and no draw at all, when the three ranges are 0 or
+        """(angle, scale, tx, ty) of n samples (torchvision RandomAffine.get_params' distributions, the shift left unrounded) from ONE draw
+        on torch's global generator; None, and no draw at all, when the three ranges are 0 or
         augmentation is off.  The shift range follows the current multi-scale size."""
         if self.args.no_augmentation or (self.rotate == 0 and self.scale == 0 and self.translate == 0):
             return None
@@ -855,8 +763,8 @@ class TrainAugmentation(ValidationAugmentation):
         return [tuple(r) for r in (lo + (hi - lo) * u).tolist()]
 
     def mosaic_draws_for(self, n, groups):
-        """Per sample None (not selected) or (cx, cy, (p1, p2, p3)) from ONE more draw on torch's global generator, `rand(n, 6)` in float64,
-        made after that of `affine_draws_for`: columns select (u < P), cx uniform over the integers of [W/4, 3W/4], cy over [H/4, 3H/4],
+        """Per sample None (not selected) or (cx, cy, (p1, p2, p3)) from ONE draw on torch's global generator, `rand(n, 6)` in float64:
+        columns select (u < P), cx uniform over the integers of [W/4, 3W/4], cy over [H/4, 3H/4],
         and three partners.  groups = the index lists of the batch's size groups: partner k of image i is `idx[int(u * len(idx))]` of its
         own group idx (with replacement, i itself allowed: the device composes from the resized images of one group).  None, and no draw
         at all, with `--aug_mosaic 0` or augmentation off.  The centre follows the current multi-scale size."""
@@ -874,7 +782,7 @@ class TrainAugmentation(ValidationAugmentation):
 
     def window_draws_for(self, n):
         """((Wc, Hc), n origins (x0, y0)) with `--train_tiles`: the canvas `tile_canvas` gives for the current multi-scale size and, from ONE
-        more draw on torch's global generator, `rand(n, 2)` in float64, made after that of `mosaic_draws_for`, x0 = int(u (Wc - W + 1)) and
+        draw on torch's global generator, `rand(n, 2)` in float64, x0 = int(u (Wc - W + 1)) and
         y0 = int(u (Hc - H + 1)): uniform over the windows of the canvas.  None, and no draw at all, with the flag off.  The flag selects
         the pixel scale the network is trained at, not a perturbation of a sample, and a fixed window would hide most of every frame for
         good: the windows are drawn under `--no_augmentation` too."""
@@ -886,15 +794,13 @@ class TrainAugmentation(ValidationAugmentation):
         return (Wc, Hc), [(int(ux * (Wc - W + 1)), int(uy * (Hc - H + 1))) for ux, uy in u]
 
     def transpose_draws_for(self, n):
-        """n flags (1 where u < P) from ONE more draw on torch's global generator, `rand(n)` in float64, made after that of
-        `window_draws_for`; None, and no draw at all, with `--aug_transpose 0` or augmentation off."""
+        """n flags (1 where u < P) from ONE draw on torch's global generator, `rand(n)` in float64; None, and no draw at all, with `--aug_transpose 0` or augmentation off."""
         if self.args.no_augmentation or self.transpose == 0:
             return None
         return (torch.rand(n, dtype=torch.float64) < self.transpose).to(torch.uint8).tolist()
 
     def blur_draws_for(self, n):
-        """n gaussian radii from ONE more draw on torch's global generator, `rand(n, 2)` in float64, made after that of
-        `transpose_draws_for`: sample i is blurred when u0 < `prob`, with r = R * u1 in pixels of the current network input size (the same
+        """n gaussian radii from ONE draw on torch's global generator, `rand(n, 2)` in float64: sample i is blurred when u0 < `prob`, with r = R * u1 in pixels of the current network input size (the same
         blur at every multi-scale size), else its radius is 0.0 (a copy row of the table).  None, and no draw at all, with `--aug_blur 0`
         or augmentation off."""
         if self.args.no_augmentation or self.blur == 0:
@@ -903,8 +809,8 @@ class TrainAugmentation(ValidationAugmentation):
         return [self.blur * u1 if u0 < self.prob else 0.0 for u0, u1 in u]
 
     def perspective_draws_for(self, n):
-        """Per sample None (not selected) or the four output corners (tl, tr, br, bl) from ONE more draw on torch's global generator,
-        `rand(n, 9)` in float64, made after that of `blur_draws_for`: sample i is warped when u0 < `prob`; its corners are inset as
+        """Per sample None (not selected) or the four output corners (tl, tr, br, bl) from ONE draw on torch's global generator,
+        `rand(n, 9)` in float64: sample i is warped when u0 < `prob`; its corners are inset as
         torchvision's RandomPerspective insets them, in the continuous frame [0, W] x [0, H] of the current multi-scale size and left
         unrounded: tl = (u1 D W/2, u2 D H/2), tr = (W - u3 D W/2, u4 D H/2), br = (W - u5 D W/2, H - u6 D H/2), bl = (u7 D W/2,
         H - u8 D H/2).  The source quad is the frame's corners.  None, and no draw at all, with `--aug_perspective 0` or augmentation
@@ -920,8 +826,7 @@ class TrainAugmentation(ValidationAugmentation):
         return quads
 
     def jpeg_draws_for(self, n):
-        """n JPEG qualities from ONE more draw on torch's global generator, `rand(n, 2)` in float64, made after that of
-        `perspective_draws_for`: sample i is compressed when u0 < `prob`, at the quality min(95, QMIN + int(u1 (96 - QMIN))), uniform over
+        """n JPEG qualities from ONE draw on torch's global generator, `rand(n, 2)` in float64: sample i is compressed when u0 < `prob`, at the quality min(95, QMIN + int(u1 (96 - QMIN))), uniform over
         the integers of [QMIN, 95]; else its quality is 0 (a copy row of the table).  None, and no draw at all, with `--aug_jpeg 0` or
         augmentation off."""
         if self.args.no_augmentation or self.jpeg == 0:
@@ -930,8 +835,7 @@ class TrainAugmentation(ValidationAugmentation):
         return [min(JPEG_MAX_QUALITY, self.jpeg + int(u1 * (JPEG_MAX_QUALITY + 1 - self.jpeg))) if u0 < self.prob else 0 for u0, u1 in u]
 
     def tone_draws_for(self, n):
-        """n tone draws (mode, cutoff percent) from ONE more draw on torch's global generator, `rand(n, 3)` in float64, made after that of
-        `jpeg_draws_for`: sample i is equalized when u0 < `--aug_equalize`; otherwise it is autocontrasted when u1 < `--aug_autocontrast`,
+        """n tone draws (mode, cutoff percent) from ONE draw on torch's global generator, `rand(n, 3)` in float64: sample i is equalized when u0 < `--aug_equalize`; otherwise it is autocontrasted when u1 < `--aug_autocontrast`,
         at the cutoff u2 `--aug_autocontrast_cutoff` percent; otherwise it is left alone -- never both.  None, and no draw at all, with both
         probabilities 0 or augmentation off."""
         if self.args.no_augmentation or (self.equalize == 0 and self.autocontrast == 0):
@@ -941,7 +845,7 @@ class TrainAugmentation(ValidationAugmentation):
                 (TONE_AUTOCONTRAST, self.autocontrast_cutoff * u2) if u1 < self.autocontrast else (TONE_COPY, 0.0) for u0, u1, u2 in u]
 
     def noise_draws_for(self, n):
-        """n noise draws (k0, k1, sigma_read, gain) from TWO more draws on torch's global generator, made after that of `tone_draws_for`:
+        """n noise draws (k0, k1, sigma_read, gain) from TWO draws on torch's global generator:
         `rand(n, 3)` in float64 -- sample i is noised when u0 < 0.5, the flips' threshold, with sigma_read = u1 `--aug_noise` grey levels and
         gain = u2 `--aug_noise_shot` levels^2 per level -- then `randint(0, 2^32, (n, 2))` in int64, the two Philox key words of every sample.
         A sample that is not selected keeps its key and gets the strengths 0, 0: the identity row.  None, and no draw at all, with both flags

@@ -474,18 +474,10 @@ class Trainer:
         import numpy as np
 
         from ..data import CropDataset, Encode
-        from ..utils.args import (check_aug_blur, check_aug_jpeg, check_aug_noise, check_aug_perspective, check_aug_tone, check_aug_transpose,
-                                  check_keep_aspect, check_train_tiles)
+        from ..utils.args import check_train
         from .network import Network
         self.args = args
-        check_train_tiles(args)                                        # --train_tiles: refused with --synthetic, overlap against the smallest size
-        check_keep_aspect(args, training=True)                         # --keep_aspect: refused with --train_tiles / --synthetic
-        check_aug_transpose(args)                                      # --aug_transpose: square network inputs only
-        check_aug_blur(args)                                           # --aug_blur: a radius in [0, 8], refused with --synthetic
-        check_aug_perspective(args)                                    # --aug_perspective: a distortion in [0, 0.9], refused with --synthetic
-        check_aug_jpeg(args)                                           # --aug_jpeg: 0 or a quality in [5, 95], refused with --synthetic
-        check_aug_tone(args)                                           # --aug_equalize / --aug_autocontrast: probabilities, refused with --synthetic
-        check_aug_noise(args)                                          # --aug_noise / --aug_noise_shot: [0, 32] levels and [0, 2], refused with --synthetic
+        check_train(args)                                              # --train_tiles, --keep_aspect, --aug_*: ranges, square inputs, --synthetic
         if getattr(args, "use_amp", False) and not BF16_TRAINING:
             # the reference autocasts the training forward under --amp (trainer.py:115-121); silently training in fp32 under the
             # same flag would be a different experiment with the same name

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import argparse
 import json
+from collections import namedtuple
 from multiprocessing import cpu_count
 from pathlib import Path
 
@@ -109,14 +110,14 @@ _FLAGS = [
                            "--max_parts. Not consulted by train / detect.")),
     (("--save_csv_pr",), dict(dest="csv_pr_path", type=Path, default=None, metavar="PATH", help="evaluate --pr_curve: write the curves here, "
                               "one row per group, label and threshold: tp, ndet, npos, precision, recall, F1, mean accuracy.")),
-    (("--aug_rotate",), dict(type=float, default=0.0, metavar="DEG", help="Training augmentation: rotate every image about its centre by an "
+    (("--aug_rotate",), dict(metavar="DEG", help="Training augmentation: rotate every image about its centre by an "
                              "angle uniform in [-DEG, DEG] (0 .. 180; what leaves the frame is dropped from the annotation, what the image does "
                              "not cover is filled with the ImageNet mean; 0 = off). Not consulted by evaluate / detect.")),
-    (("--aug_scale",), dict(type=float, default=0.0, metavar="S", help="Training augmentation: zoom every image about its centre by a factor "
+    (("--aug_scale",), dict(metavar="S", help="Training augmentation: zoom every image about its centre by a factor "
                             "uniform in [1 - S, 1 + S] (0 <= S < 1; 0 = off). Not consulted by evaluate / detect.")),
-    (("--aug_translate",), dict(type=float, default=0.0, metavar="T", help="Training augmentation: shift every image by a fraction of its width "
+    (("--aug_translate",), dict(metavar="T", help="Training augmentation: shift every image by a fraction of its width "
                                 "and height uniform in [-T, T] (0 .. 0.5; 0 = off). Not consulted by evaluate / detect.")),
-    (("--aug_mosaic",), dict(type=float, default=0.0, metavar="P", help="Training augmentation: with probability P (0 .. 1; 0 = off) an image "
+    (("--aug_mosaic",), dict(metavar="P", help="Training augmentation: with probability P (0 .. 1; 0 = off) an image "
                              "becomes a mosaic of itself and three other images of its batch at half scale around a random centre. A mosaic "
                              "carries up to four images' objects: raise --max_objects / --max_parts accordingly (what exceeds them is "
                              "truncated by the target encoder as always). Not consulted by evaluate / detect.")),
@@ -127,48 +128,48 @@ _FLAGS = [
                               "original-image pixels. Train and evaluate a model with the same setting. Does not combine with --tiles / "
                               "--tta_scales / --train_tiles (their other sizes would letterbox with different roundings) or --synthetic. "
                               "Off = the stretched input.")),
-    (("--aug_transpose",), dict(type=float, default=0.0, metavar="P", help="Training augmentation: with probability P (0 .. 1; 0 = off) an "
+    (("--aug_transpose",), dict(metavar="P", help="Training augmentation: with probability P (0 .. 1; 0 = off) an "
                                 "image is transposed (x and y swapped: a lossless quarter turn with the flips, no resampling and no fill), "
                                 "after the flips. Needs a square network input (--width equal to --height). Not consulted by evaluate / "
                                 "detect.")),
-    (("--aug_blur",), dict(type=float, default=0.0, metavar="R", help="Training augmentation: with the flip probability's threshold "
+    (("--aug_blur",), dict(metavar="R", help="Training augmentation: with the flip probability's threshold "
                            "(u < 0.5) an image is blurred by Pillow's GaussianBlur with a radius uniform in [0, R] pixels of the current "
                            "network input size (0 <= R <= 8: the same physical blur at every multi-scale size; motion / defocus blur of "
                            "deployment frames), after the warp and before the colour jitter; annotations are untouched. Needs a directory "
                            "(not --synthetic). Not consulted by evaluate / detect. 0 = off.")),
-    (("--aug_perspective",), dict(type=float, default=0.0, metavar="D", help="Training augmentation: with the flip probability's threshold "
+    (("--aug_perspective",), dict(metavar="D", help="Training augmentation: with the flip probability's threshold "
                                   "(u < 0.5) an image gets a random perspective warp, torchvision's RandomPerspective with distortion "
                                   "scale D (0 <= D <= 0.9): each corner of the frame moves inwards by up to D/2 of the width and height "
                                   "(pitch / roll / mounting tilt of the camera). Folded with --aug_rotate / --aug_scale / --aug_translate "
                                   "into one homography, so an image is resampled once, byte for byte Pillow's Image.transform("
                                   "PERSPECTIVE, BILINEAR); keypoints that leave the frame are dropped. Needs a directory (not "
                                   "--synthetic). Not consulted by evaluate / detect. 0 = off.")),
-    (("--aug_jpeg",), dict(type=int, default=0, metavar="QMIN", help="Training augmentation: with the flip probability's threshold "
+    (("--aug_jpeg",), dict(metavar="QMIN", help="Training augmentation: with the flip probability's threshold "
                            "(u < 0.5) an image is JPEG-compressed and decoded again at a quality uniform over the integers of [QMIN, 95] "
                            "(5 <= QMIN <= 95), byte for byte Pillow's save(quality=q) + open(): the 8 x 8 blocking, ringing and chroma "
                            "smearing of a camera's encoder, on the grid of the network input. After the blur and before the colour "
                            "jitter; annotations are untouched. Needs a directory (not --synthetic). Not consulted by evaluate / detect. "
                            "0 = off.")),
-    (("--aug_equalize",), dict(type=float, default=0.0, metavar="P", help="Training augmentation: with probability P an image's histogram "
+    (("--aug_equalize",), dict(metavar="P", help="Training augmentation: with probability P an image's histogram "
                                "is equalized per channel, byte for byte Pillow's ImageOps.equalize (torchvision's RandomEqualize on a PIL "
                                "image): a tone curve made from the image's own content, as exposure and auto-gain differences between "
                                "cameras are. After the JPEG round trip and before the colour jitter, on the 8-bit network input (fill "
                                "colour and letterbox bars included); annotations are untouched. Needs a directory (not --synthetic). Not "
                                "consulted by evaluate / detect. 0 = off.")),
-    (("--aug_autocontrast",), dict(type=float, default=0.0, metavar="P", help="Training augmentation: with probability P an image that "
+    (("--aug_autocontrast",), dict(metavar="P", help="Training augmentation: with probability P an image that "
                                    "--aug_equalize did not select has each channel stretched to the full range, byte for byte Pillow's "
                                    "ImageOps.autocontrast (torchvision's RandomAutocontrast on a PIL image), ignoring a share of the "
                                    "darkest and brightest pixels uniform in [0, --aug_autocontrast_cutoff] percent. Same place in the chain "
                                    "and same limits as --aug_equalize. 0 = off.")),
-    (("--aug_autocontrast_cutoff",), dict(type=float, default=1.0, metavar="C", help="Upper end, in percent of the pixels at either end of "
+    (("--aug_autocontrast_cutoff",), dict(metavar="C", help="Upper end, in percent of the pixels at either end of "
                                           "the histogram, of the cutoff that --aug_autocontrast draws (0 <= C <= 40).")),
-    (("--aug_noise",), dict(type=float, default=0.0, metavar="R", help="Training augmentation: with probability 0.5 an image gets sensor read "
+    (("--aug_noise",), dict(metavar="R", help="Training augmentation: with probability 0.5 an image gets sensor read "
                             "noise, Gaussian with a standard deviation uniform in [0, R] grey levels (0 <= R <= 32), independent per pixel "
                             "and channel, as a camera at dusk or at short exposure delivers. Made on the GPU by a counter-based generator "
                             "(Philox4x32-10), bit-exact and reproducible from the seed. After the blur and before the JPEG round trip, on "
                             "the 8-bit network input (no gamma is modelled); annotations are untouched. Needs a directory (not "
                             "--synthetic). Not consulted by evaluate / detect. 0 = off.")),
-    (("--aug_noise_shot",), dict(type=float, default=0.0, metavar="G", help="Training augmentation: the signal-dependent part of the sensor "
+    (("--aug_noise_shot",), dict(metavar="G", help="Training augmentation: the signal-dependent part of the sensor "
                                  "noise: a selected image's noise variance grows by g grey levels^2 per grey level, g uniform in [0, G] "
                                  "(0 <= G <= 2). Either of --aug_noise and --aug_noise_shot switches the stage on; same place in the chain "
                                  "and same limits. 0 = off.")),
@@ -303,7 +304,7 @@ def check_label_nms(radius):
 def check_aug_transpose(args):
     """`--aug_transpose` on a parsed namespace -> P, as `train` checks it (model/trainer.py): a batch has ONE shape, so a transposed sample
     needs width == height (the per-epoch multi-scale rule and the `--train_tiles` windows keep a square square)."""
-    p = float(getattr(args, "aug_transpose", 0.0) or 0.0)
+    p = float(aug_flag(args, "aug_transpose"))
     if p > 0 and args.width != args.height:
         raise ValueError(f"'aug_transpose' transposes samples inside a batch of one shape: it needs a square network input, not "
                          f"{args.width} x {args.height}")
@@ -311,84 +312,87 @@ def check_aug_transpose(args):
 
 
 MAX_AUG_BLUR = 8.0                  # pixels: the gaussian radius whose box radius is SD_BLUR_MAX_RADIUS (include/sdnet_hip.h)
-
-
-def check_aug_blur(args):
-    """`--aug_blur` on a parsed namespace -> R, as `train` checks it (model/trainer.py): a radius in [0, 8]; `--synthetic` renders
-    network-input tensors and has no 8-bit image to blur, so the flag is refused there."""
-    r = float(getattr(args, "aug_blur", 0.0) or 0.0)
-    if not 0 <= r <= MAX_AUG_BLUR:                                   # (also false for nan)
-        raise ValueError(f"'aug_blur' should be in [0, {MAX_AUG_BLUR:g}] pixels (0 = off), not {r}")
-    if r > 0 and getattr(args, "synthetic", 0):
-        raise ValueError("'aug_blur' blurs source images: it needs --train_dir, not --synthetic")
-    return r
-
-
 MAX_AUG_PERSPECTIVE = 0.9           # distortion scale: at 1 two opposite corners can meet and the quadrilateral degenerates
-
-
-def check_aug_perspective(args):
-    """`--aug_perspective` on a parsed namespace -> D, as `train` checks it (model/trainer.py): a distortion scale in [0, 0.9];
-    `--synthetic` renders network-input tensors and has no 8-bit image to warp, so the flag is refused there."""
-    d = float(getattr(args, "aug_perspective", 0.0) or 0.0)
-    if not 0 <= d <= MAX_AUG_PERSPECTIVE:                            # (also false for nan)
-        raise ValueError(f"'aug_perspective' should be in [0, {MAX_AUG_PERSPECTIVE:g}] (0 = off), not {d}")
-    if d > 0 and getattr(args, "synthetic", 0):
-        raise ValueError("'aug_perspective' warps source images: it needs --train_dir, not --synthetic")
-    return d
-
-
 MIN_AUG_JPEG, MAX_AUG_JPEG = 5, 95  # qualities: below 5 every block is its mean, above 95 Pillow advises against (tables of ones)
-
-
-def check_aug_jpeg(args):
-    """`--aug_jpeg` on a parsed namespace -> QMIN, as `train` checks it (model/trainer.py): 0 (off) or an integer in [5, 95];
-    `--synthetic` renders network-input tensors and has no 8-bit image to compress, so the flag is refused there."""
-    q = getattr(args, "aug_jpeg", 0) or 0
-    if isinstance(q, bool) or not isinstance(q, int) or not (q == 0 or MIN_AUG_JPEG <= q <= MAX_AUG_JPEG):
-        raise ValueError(f"'aug_jpeg' should be 0 (off) or an integer in [{MIN_AUG_JPEG}, {MAX_AUG_JPEG}], not {q}")
-    if q > 0 and getattr(args, "synthetic", 0):
-        raise ValueError("'aug_jpeg' compresses source images: it needs --train_dir, not --synthetic")
-    return q
-
-
 MAX_AUG_AUTOCONTRAST_CUTOFF = 40.0  # percent at either end: beyond, the two cuts meet in the middle and most images are left alone
-
-
-def check_aug_tone(args):
-    """`--aug_equalize`, `--aug_autocontrast` and `--aug_autocontrast_cutoff` on a parsed namespace -> (P_eq, P_ac, C), as `train` checks
-    them (model/trainer.py): two probabilities in [0, 1] and a percentage in [0, 40] (NaN fails the range tests); `--synthetic` renders
-    network-input tensors and has no 8-bit image to take a histogram of, so a positive probability is refused there."""
-    p_eq = getattr(args, "aug_equalize", 0.0) or 0.0
-    p_ac = getattr(args, "aug_autocontrast", 0.0) or 0.0
-    cutoff = getattr(args, "aug_autocontrast_cutoff", 1.0)
-    cutoff = 0.0 if cutoff is None else cutoff
-    for name, p in (("aug_equalize", p_eq), ("aug_autocontrast", p_ac)):
-        if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0 <= p <= 1:
-            raise ValueError(f"'{name}' should be a probability in [0, 1], not {p}")
-    if isinstance(cutoff, bool) or not isinstance(cutoff, (int, float)) or not 0 <= cutoff <= MAX_AUG_AUTOCONTRAST_CUTOFF:
-        raise ValueError(f"'aug_autocontrast_cutoff' should be a percentage in [0, {MAX_AUG_AUTOCONTRAST_CUTOFF:g}], not {cutoff}")
-    if (p_eq > 0 or p_ac > 0) and getattr(args, "synthetic", 0):
-        raise ValueError("'aug_equalize' / 'aug_autocontrast' work on source images: they need --train_dir, not --synthetic")
-    return float(p_eq), float(p_ac), float(cutoff)
-
-
 MAX_AUG_NOISE, MAX_AUG_NOISE_SHOT = 32.0, 2.0   # grey levels; levels^2 per level: where the stage clamps a row (2^26 and 2^17 in Q16)
 
 
-def check_aug_noise(args):
-    """`--aug_noise` and `--aug_noise_shot` on a parsed namespace -> (R, G), as `train` checks them (model/trainer.py): a read-noise
-    standard deviation in [0, 32] grey levels and a shot gain in [0, 2] (NaN fails the range tests); `--synthetic` renders network-input
-    tensors and has no 8-bit image to add sensor noise to, so a positive value is refused there."""
-    r = getattr(args, "aug_noise", 0.0) or 0.0
-    g = getattr(args, "aug_noise_shot", 0.0) or 0.0
-    if isinstance(r, bool) or not isinstance(r, (int, float)) or not 0 <= r <= MAX_AUG_NOISE:
-        raise ValueError(f"'aug_noise' should be in [0, {MAX_AUG_NOISE:g}] grey levels (0 = off), not {r}")
-    if isinstance(g, bool) or not isinstance(g, (int, float)) or not 0 <= g <= MAX_AUG_NOISE_SHOT:
-        raise ValueError(f"'aug_noise_shot' should be in [0, {MAX_AUG_NOISE_SHOT:g}] (0 = off), not {g}")
-    if (r > 0 or g > 0) and getattr(args, "synthetic", 0):
-        raise ValueError("'aug_noise' / 'aug_noise_shot' work on source images: they need --train_dir, not --synthetic")
-    return float(r), float(g)
+# One training-augmentation flag: its default (what a Namespace from before the flag gives; the parser's default and type), its range
+# [lo, hi] (open_hi: [lo, hi[; with lo > 0 the value 0 = off is accepted too), integer: an int is required, source: None or the verb of the
+# refusal when the value is positive under --synthetic (the stage works on 8-bit source images and a rendered scene has none), text: what
+# `check_aug` says the value should be, coerce: the value goes through float() instead of being refused when it is no number.
+AugFlag = namedtuple("AugFlag", "name default lo hi open_hi integer source text coerce", defaults=(False, False, None, "in {range}", False))
+
+# the table behind the parser's defaults, `finalize`'s asserts (in this order), `check_aug` and `TrainAugmentation`'s attributes (name[4:])
+AUG_FLAGS = {f.name: f for f in (
+    AugFlag("aug_rotate", 0.0, 0, 180),
+    AugFlag("aug_scale", 0.0, 0, 1, open_hi=True),
+    AugFlag("aug_translate", 0.0, 0, 0.5),
+    AugFlag("aug_mosaic", 0.0, 0, 1),
+    AugFlag("aug_transpose", 0.0, 0, 1),
+    AugFlag("aug_blur", 0.0, 0, MAX_AUG_BLUR, source="blurs", text="in {range} pixels (0 = off)", coerce=True),
+    AugFlag("aug_perspective", 0.0, 0, MAX_AUG_PERSPECTIVE, source="warps", text="in {range} (0 = off)", coerce=True),
+    AugFlag("aug_jpeg", 0, MIN_AUG_JPEG, MAX_AUG_JPEG, integer=True, source="compresses", text="0 (off) or an integer in {range}"),
+    AugFlag("aug_equalize", 0.0, 0, 1, source="work on", text="a probability in {range}"),
+    AugFlag("aug_autocontrast", 0.0, 0, 1, source="work on", text="a probability in {range}"),
+    AugFlag("aug_autocontrast_cutoff", 1.0, 0, MAX_AUG_AUTOCONTRAST_CUTOFF, text="a percentage in {range}"),
+    AugFlag("aug_noise", 0.0, 0, MAX_AUG_NOISE, source="work on", text="in {range} grey levels (0 = off)"),
+    AugFlag("aug_noise_shot", 0.0, 0, MAX_AUG_NOISE_SHOT, source="work on", text="in {range} (0 = off)"),
+)}
+
+
+def _aug_range(row):
+    return f"[{row.lo:g}, {row.hi:g}{'[' if row.open_hi else ']'}"
+
+
+def _aug_holds(row, v):
+    """v lies in the row's range (false for nan)."""
+    return bool(row.lo > 0 and v == 0) or (row.lo <= v < row.hi if row.open_hi else row.lo <= v <= row.hi)
+
+
+def aug_flag(args, name):
+    """The value of one flag of AUG_FLAGS on a namespace, unchecked: a namespace from before the flag gives its default; None, and for a
+    flag whose default is 0 (= off) anything false, reads as 0."""
+    row = AUG_FLAGS[name]
+    v = getattr(args, name, row.default)
+    return type(row.default)(0) if v is None or (not v and not row.default) else v
+
+
+def check_aug(args, *names):
+    """The flags `names` of AUG_FLAGS on a parsed namespace -> their values, as `train` checks them: each in its range and of its type (NaN
+    fails the range test), then, under `--synthetic`, none of those that need source images positive."""
+    rows = [AUG_FLAGS[n] for n in names]
+    values = []
+    for row in rows:
+        v = aug_flag(args, row.name)
+        if row.coerce:
+            v = float(v)
+        if isinstance(v, bool) or not isinstance(v, int if row.integer else (int, float)) or not _aug_holds(row, v):
+            raise ValueError(f"'{row.name}' should be {row.text.format(range=_aug_range(row))}, not {v}")
+        values.append(v if row.integer else float(v))
+    needy = [row for row in rows if row.source]
+    if getattr(args, "synthetic", 0) and any(v > 0 for row, v in zip(rows, values) if row.source):
+        raise ValueError(f"{' / '.join(repr(row.name) for row in needy)} {needy[0].source} source images: "
+                         f"{'it needs' if len(needy) == 1 else 'they need'} --train_dir, not --synthetic")
+    return tuple(values)
+
+
+# the checks of `train` by stage: the values in their ranges, a positive one refused with --synthetic (model/trainer.py calls `check_train`)
+def check_aug_blur(args): return check_aug(args, "aug_blur")[0]                                  # noqa: E704  -> R, a radius in pixels
+def check_aug_perspective(args): return check_aug(args, "aug_perspective")[0]                    # noqa: E704  -> D, a distortion scale
+def check_aug_jpeg(args): return check_aug(args, "aug_jpeg")[0]                                  # noqa: E704  -> QMIN, 0 = off
+def check_aug_tone(args): return check_aug(args, "aug_equalize", "aug_autocontrast", "aug_autocontrast_cutoff")   # noqa: E704  -> (P_eq, P_ac, C)
+def check_aug_noise(args): return check_aug(args, "aug_noise", "aug_noise_shot")                 # noqa: E704  -> (R, G)
+
+
+def check_train(args):
+    """Everything `train` checks on a parsed namespace before it builds anything (model/trainer.py; `evaluate` and `detect` consult none of
+    these flags): `--train_tiles`, `--keep_aspect`, `--aug_transpose`, then the ranges and the `--synthetic` refusals of AUG_FLAGS."""
+    check_train_tiles(args)
+    check_keep_aspect(args, training=True)
+    for check in (check_aug_transpose, check_aug_blur, check_aug_perspective, check_aug_jpeg, check_aug_tone, check_aug_noise):
+        check(args)
 
 
 def finalize(args):
@@ -407,19 +411,8 @@ def finalize(args):
     for k in ("weight_decay", "clip_grad_norm", "ema_decay"):
         assert getattr(args, k, 0.0) >= 0, f"'{k}' should be greater than or equal to 0"
     assert getattr(args, "ema_decay", 0.0) < 1, "'ema_decay' should be less than 1"
-    assert 0 <= getattr(args, "aug_rotate", 0.0) <= 180, "'aug_rotate' should be in [0, 180]"
-    assert 0 <= getattr(args, "aug_scale", 0.0) < 1, "'aug_scale' should be in [0, 1["
-    assert 0 <= getattr(args, "aug_translate", 0.0) <= 0.5, "'aug_translate' should be in [0, 0.5]"
-    assert 0 <= getattr(args, "aug_mosaic", 0.0) <= 1, "'aug_mosaic' should be in [0, 1]"
-    assert 0 <= getattr(args, "aug_transpose", 0.0) <= 1, "'aug_transpose' should be in [0, 1]"
-    assert 0 <= getattr(args, "aug_blur", 0.0) <= MAX_AUG_BLUR, "'aug_blur' should be in [0, 8]"
-    assert 0 <= getattr(args, "aug_perspective", 0.0) <= MAX_AUG_PERSPECTIVE, "'aug_perspective' should be in [0, 0.9]"
-    assert getattr(args, "aug_jpeg", 0) == 0 or MIN_AUG_JPEG <= getattr(args, "aug_jpeg", 0) <= MAX_AUG_JPEG, "'aug_jpeg' should be 0 or in [5, 95]"
-    assert 0 <= getattr(args, "aug_equalize", 0.0) <= 1, "'aug_equalize' should be in [0, 1]"
-    assert 0 <= getattr(args, "aug_autocontrast", 0.0) <= 1, "'aug_autocontrast' should be in [0, 1]"
-    assert 0 <= getattr(args, "aug_autocontrast_cutoff", 1.0) <= MAX_AUG_AUTOCONTRAST_CUTOFF, "'aug_autocontrast_cutoff' should be in [0, 40]"
-    assert 0 <= getattr(args, "aug_noise", 0.0) <= MAX_AUG_NOISE, "'aug_noise' should be in [0, 32]"
-    assert 0 <= getattr(args, "aug_noise_shot", 0.0) <= MAX_AUG_NOISE_SHOT, "'aug_noise_shot' should be in [0, 2]"
+    for row in AUG_FLAGS.values():
+        assert _aug_holds(row, getattr(args, row.name, row.default)), f"'{row.name}' should be {'0 or ' if row.lo > 0 else ''}in {_aug_range(row)}"
     args.label_nms = check_label_nms(getattr(args, "label_nms", 0))
     args.tta_scales = parse_tta_scales(getattr(args, "tta_scales", ""))
     args.tiles = parse_tiles(getattr(args, "tiles", ""))
@@ -457,6 +450,9 @@ class Arguments:
     def __init__(self):
         self.parser = argparse.ArgumentParser(formatter_class=argparse.ArgumentDefaultsHelpFormatter)
         for flags, kw in _FLAGS:
+            row = AUG_FLAGS.get(flags[0][2:])
+            if row is not None:                                      # the augmentation flags take type and default from their table
+                kw = dict(kw, type=type(row.default), default=row.default)
             self.parser.add_argument(*flags, **kw)
 
     def parse(self, argv=None):

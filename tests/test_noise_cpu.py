@@ -217,16 +217,22 @@ def test_the_draws_come_after_the_tone_draw_and_change_no_earlier_one():
     assert seen[0] == seen[1] == seen[2] and torch.equal(ends[0], ends[1]) and not torch.equal(ends[0], ends[2])
 
 
-def test_the_call_makes_the_draws_in_that_order():
-    """`ValidationAugmentation.__call__` asks for the noise draws last: the source names the draw functions in the order of the test above."""
-    import inspect
-
-    from structuredetector_amd.data import ValidationAugmentation
-    src = inspect.getsource(ValidationAugmentation.__call__)
-    order = [src.index(f"self.{name}(n") for name in ("draws_for", "affine_draws_for", "mosaic_draws_for", "window_draws_for", "transpose_draws_for",
-                                                      "blur_draws_for", "perspective_draws_for", "jpeg_draws_for", "tone_draws_for",
-                                                      "noise_draws_for")]
-    assert order == sorted(order)
+def test_the_call_makes_the_draws_in_that_order(monkeypatch):
+    """`ValidationAugmentation.__call__` asks for the noise draws last: DRAW_STEPS, the one place the order is written, names the draw
+    functions in the order of the test above, and the call runs whatever is bound to those names, in that order, once each."""
+    from structuredetector_amd.data import augment as A
+    from structuredetector_amd.utils import ImageAnnotation
+    names = ("draws_for", "affine_draws_for", "mosaic_draws_for", "window_draws_for", "transpose_draws_for", "blur_draws_for",
+             "perspective_draws_for", "jpeg_draws_for", "tone_draws_for", "noise_draws_for")
+    assert A.DRAW_STEPS == names
+    aug, asked = A.TrainAugmentation(Namespace(**_COMMON, aug_noise=6.0)), []
+    for name in names:
+        real = getattr(aug, name)
+        setattr(aug, name, lambda *a, name=name, real=real: asked.append(name) or real(*a))
+    monkeypatch.setattr(A, "preprocess_images", lambda images, size, **kw: torch.zeros(images.shape[0], 3, size[1], size[0]))
+    monkeypatch.setattr(A, "transpose_select", lambda batch, select: batch)
+    out, _ = aug([np.zeros((40, 56, 3), np.uint8)] * 4, [ImageAnnotation(f"/i{i}.png") for i in range(4)])
+    assert asked == list(names) and out.shape == (4, 3, 128, 128)
 
 
 NAMES = ["sd_noise_normal_table", "sd_noise_u8", "sd_preprocess_noise_workspace_bytes", "sd_preprocess_images_noise",

@@ -35,7 +35,7 @@ opt = ap.parse_args()
 
 sys.path.insert(0, str(ROOT))
 from structuredetector_amd import _lib as L  # noqa: E402
-from structuredetector_amd.data.augment import (_FILL, _MEAN, _STD, _affine_rows, _flip_table, _jitter_tables, _tables, affine_inverse_matrix, compose_affine_perspective,  # noqa: E402
+from structuredetector_amd.data.augment import (_FILL, _MEAN, _STD, _tables, _upload, affine_inverse_matrix, compose_affine_perspective,  # noqa: E402
                                                 jitter_words, perspective_coeffs)
 
 dev = torch.device("cuda", torch.cuda.current_device())
@@ -127,8 +127,8 @@ def chain_call(handle, name, x, rows6=None, rows8=None):
     Bn, Hin, Win, _ = x.shape
     hb, hk, hks = _tables.get(Win, Wout, dev)
     vb, vk, vks = _tables.get(Hin, Hout, dev)
-    fl, (order, fac) = _flip_table(flips, Bn, dev), _jitter_tables(jitter, Bn, dev)
-    rows = None if rows6 is None else _affine_rows(rows6, Bn, dev)
+    fl, order, fac = _upload("flips", flips, Bn, dev), _upload("jitter_order", jitter[0], Bn, dev), _upload("jitter_factors", jitter[1], Bn, dev)
+    rows = None if rows6 is None else _upload("affine", rows6, Bn, dev)
     homography = None if rows8 is None else torch.tensor(np.asarray(rows8), device=dev)
     out = torch.empty((Bn, 3, Hout, Wout), dtype=torch.float32, device=dev)
     ws = torch.empty(lib.sd_preprocess_blur_workspace_bytes(0, Bn, Hin, Win, 0, Hout, Wout, 0), dtype=torch.uint8, device=dev)
