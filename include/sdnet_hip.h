@@ -982,6 +982,43 @@ int sd_optim_step(float* param, const float* grad, float* exp_avg, float* exp_av
                   const uint8_t* decay_mask, float max_norm, const void* partials, int npartials, float* ema,
                   float ema_decay, void* status, sd_stream_t stream);
 
+/* What a call of the BatchNorm / pool / head / optimizer entry points above launches (host only; no pointer is read).  The descriptor names
+ * the call: `op`, `form` (0 fp32, 1 bf16, 2 bf16 with a bf16 dx -- the stem tail's _dx16; SD_NN_CAST: 0 = to bf16, 1 = to fp32), the shape
+ * (the map ops take B, H, W; the head B and H = HW; every other op M -- the optimizer and the casts their n), C, Co, relu, rows (the
+ * caller-provided-rows forms) and `flags`: bit k (k < 4) = pointer k of the op's kernel choice is 16-byte aligned, in the order
+ *     bn_apply: x, y, residual        bn_bwd / bn_bwd_apply: dy, x, dx, g_out (bn_bwd_reduce: dy, x)        bn_relu_maxpool_fwd: x, y_pool, idx
+ *     head_fwd: x, w, y               head_bwd: x, dy
+ * SD_NN_SCRATCH = scratch given, SD_NN_SUMS = the split form that stops at the fp64 sums (sd_bn_train_sums, sd_bn_stats_sums, sd_bn_bwd_sums,
+ * sd_bn_bwd_reduce, sd_maxpool_bn_relu_bwd_reduce), SD_NN_DECAY / _CLIP / _EMA = the options of sd_optim_step.  pool_fwd_pair: the option
+ * of that name as the call would see it.
+ * sd_nn_kernel_names prints the launches in order, separated by "; ", each as "<kernel as rocprofv3 prints it, without sd::> grid=X block=256
+ * lds=N" (N: dynamic bytes), a wide head's own kernels as "head_wide_fwd" / "head_wide_wgrad" / "head_wide_dgrad" (their grids need the
+ * device).  Reducing ops append " | rpb=.. nb=.. slab=.. rows=.. partial_at=.. means_at=.. fold_at=.. ws_bytes=.." (slab 0 = no fold; rows =
+ * what the finish reads; offsets in floats), the caller-provided-rows forms " | slab=.. rows=..", the head backward and sd_grad_sumsq
+ * " | ws_bytes=..".  "refused: <message>" for an unknown op and where one of the layer's shared shape checkers refuses the call: C (and M) of
+ * the BatchNorm / column-sum / stem-tail family, relu outside 0..3, the map checks of the pool and upsample entry points, a bf16 stem tail on
+ * an odd map, n % 4 != 0 of the casts and the optimizer.  The checks an entry point states for itself are not asked -- the head's limits on
+ * C and Co (the query prints the launches of the form the descriptor names), rows <= 0, null pointers, workspace sizes.  A refusal sets
+ * sd_last_error() of the calling thread, as the entry point's own would; an answered query leaves it alone.  The answer is made from the
+ * plans, launch shapes and predicates the launchers themselves run.  Thread-local storage, valid until the next call on the thread. */
+enum { SD_NN_BN_TRAIN_STATS, SD_NN_BN_FINALIZE_STATS, SD_NN_BN_STATS_FROM_SUMS, SD_NN_BN_APPLY, SD_NN_BN_FOLD, SD_NN_BN_BWD, SD_NN_BN_BWD_REDUCE,
+       SD_NN_BN_BWD_FINALIZE, SD_NN_BN_BWD_MEANS_FROM_SUMS, SD_NN_BN_BWD_APPLY, SD_NN_COL_SUM, SD_NN_MAXPOOL_FWD, SD_NN_MAXPOOL_BWD,
+       SD_NN_BN_RELU_MAXPOOL_FWD, SD_NN_STEM_BWD, SD_NN_STEM_BWD_REDUCE, SD_NN_STEM_BWD_APPLY, SD_NN_UPSAMPLE_BWD, SD_NN_CAST, SD_NN_HEAD_FWD,
+       SD_NN_HEAD_BWD, SD_NN_ADAM, SD_NN_GRAD_SUMSQ, SD_NN_OPTIM };
+#define SD_NN_SCRATCH (1u << 8)
+#define SD_NN_SUMS (1u << 9)
+#define SD_NN_DECAY (1u << 10)
+#define SD_NN_CLIP (1u << 11)
+#define SD_NN_EMA (1u << 12)
+typedef struct {
+    int op, form, B, H, W;
+    int64_t M;
+    int C, Co, relu, rows;
+    unsigned flags;
+    int pool_fwd_pair;
+} sd_nn_call_desc;
+const char* sd_nn_kernel_names(const sd_nn_call_desc* d);
+
 /* ---- gradient exchange (the reference's step, trainer.py:113-124, is single-device) -------------------
  * Thin wrapper over RCCL, one communicator per process (= per GPU).  librccl.so.1 is dlopen()ed on first use (the copy a
  * PyTorch-ROCm process has already loaded is reused), so libsdnet_hip.so has no link-time dependency on it.

@@ -55,6 +55,12 @@ class PreprocessDesc(C.Structure):
                 [("fill3", C.POINTER(C.c_ubyte)), ("mean3", C.POINTER(c_float)), ("std3", C.POINTER(c_float)), ("out", c_vp)])
 
 
+class NnCallDesc(C.Structure):
+    """sd_nn_call_desc (include/sdnet_hip.h): names one call of the BatchNorm / pool / head / optimizer entry points for sd_nn_kernel_names."""
+    _fields_ = ([(n, c_int) for n in ("op", "form", "B", "H", "W")] + [("M", c_i64)] + [(n, c_int) for n in ("C", "Co", "relu", "rows")] +
+                [("flags", C.c_uint), ("pool_fwd_pair", c_int)])
+
+
 _MAP = [c_vp, c_i64, c_i64]          # pointer, batch stride, channel stride
 _PEAK_OUT = [c_vp, c_vp, c_vp, c_vp, c_vp]
 
@@ -247,6 +253,7 @@ _SIGNATURES = {
     "sd_grad_sumsq": (c_int, [c_vp, c_i64, c_vp, c_size, c_vp]),
     "sd_optim_step": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_float, c_float, c_float, c_float, c_float, c_float, c_vp, c_float, c_vp, c_int,
                               c_vp, c_float, c_vp, c_vp]),
+    "sd_nn_kernel_names": (C.c_char_p, [C.POINTER(NnCallDesc)]),
     "sd_conv2d_kernel_name": (C.c_char_p, [c_vp, c_int]),
     "sd_set_option": (c_int, [C.c_char_p, c_int]),
     "sd_decode_set_option": (c_int, [C.c_char_p, c_int]),

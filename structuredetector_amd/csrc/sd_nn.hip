@@ -1629,13 +1629,43 @@ __global__ __launch_bounds__(256) void k_col_reduce_bwd_bf16x8(const uint16_t* _
 static inline int ew_grid(int64_t n4) { return (int)std::min<int64_t>(cdiv(n4, 256), 256 * 16); }
 
 }  // namespace sd
+#include <cstdarg>                                    // (va_list: the formatter of sd_nn_kernel_names)
 
 using namespace sd;
+
+// ==== host layer: checks (one checker per argument family, the entry point's name passed as `what`), a plan (plain structs, no HIP call, no
+// allocation), the launches the plan names.  sd_nn_kernel_names at the end prints the same plans; nothing else here formats a string. =========
 
 static thread_local int g_pool_pair = 1;              // sd_set_option("pool_fwd_pair", 0): one window per thread in sd_bn_relu_maxpool_fwd[_bf16] (A/B)
 namespace sd { void sd_nn_set_pool_pair(int v) { g_pool_pair = v; } }  // (called by sd_set_option in sd_conv.hip)
 
-extern "C" {
+// the last launch of an entry point: 256 threads per block, check, `return 0` (the macro leaves the function)
+#define SD_RETURN_LAUNCH(kernel, grid, lds, st, ...) \
+    do { hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds, st, __VA_ARGS__); SD_LAUNCH_CHECK(); return 0; } while (0)
+
+// ---- launch shapes: what a launcher hands hipLaunchKernelGGL and sd_nn_kernel_names prints (n: the count the kernel is told, where it takes one)
+struct Launch { int grid; size_t lds; int64_t n; };
+static Launch ew_launch(int64_t n) { return {ew_grid(n), 0, n}; }                                     // grid-stride pass over n groups of elements
+static Launch bn_ew_launch(bool wide, int64_t M, int C) { return ew_launch(M * C / (wide ? 8 : 4)); }   // [M][C] in groups of 4, the bf16 x8 kernels of 8
+static Launch map_launch(int B, int H, int W, int C, int elems) {                                        // one thread per `elems` channels of a (B, H, W, C) map
+    const int64_t n = (int64_t)B * H * W * C / elems;
+    return {cdiv(n, 256), 0, n};
+}
+static Launch pool_fwd_launch(bool pair, int elems, int B, int Ho, int Wo, int C) { return map_launch(B, Ho, Wo, C, pair ? 2 * elems : 4); }
+static Launch stem_apply_launch(bool quad, int B, int Hi, int Wi, int C) { return map_launch(B, Hi, Wi, C, quad ? 16 : 4); }   // a quad: 2 x 2 pixels x 4 channels
+static Launch chan_launch(int C, int per_block) { return {cdiv(C, per_block), 0, C}; }                 // per channel: 4 a block (the finish), 256 (the tails)
+static Launch head_dgrad_launch(int64_t M, int C, int Co) { return {cdiv(M, 64), (size_t)Co * C * sizeof(float), M}; }
+
+// ---- the plan of a column reduction.  Workspace, in floats: [nb partial rows][2][C] | mean(g) (C), mean(g * xhat) (C) of the backward | the
+// slab sums of the two-level finish -----------------------------------------------------------------------------------------------------------
+enum RowsRule { ROWS_BN, ROWS_STEM_TAIL };
+struct FoldPlan { int slab, rows; };                 // slab == 0: no k_rows_fold launch; rows: the rows the finish kernel reads
+struct ColReducePlan {
+    int rpb, nb;
+    FoldPlan fold;
+    size_t partial_at, means_at, fold_at;            // float offsets into the workspace
+    size_t ws_bytes;
+};
 
 // rows per reduction block: 256 for the big maps, fewer for the deep layers so that the pass still spreads over >= 1024 blocks
 // (layer4, M = 16384 at bs=64: 64 blocks of 256 rows read at 0.8 TB/s, 1024 blocks of 16 rows at HBM rate)
@@ -1647,172 +1677,402 @@ static int red_rows(int64_t M) {
 
 static int fold_rows(int rows) { return rows > 2048 ? cdiv(rows, std::max(16, rows / 128)) : 0; }      // (<= 2048 rows: one finalize launch is faster)
 
-// [nb partial rows][2][C] + the two per-channel means of the backward + the slab sums of the two-level finish
-size_t sd_col_reduce_workspace_bytes(int64_t M, int C) {
-    const int nb = cdiv(M, red_rows(M));
-    return align_up(((size_t)nb + fold_rows(nb)) * 2 * C * sizeof(float) + 2 * (size_t)C * sizeof(float), 256);
+// Many partial rows: they are folded in coalesced slabs first (a column-slice finalize touches every row from every block), into `scratch`.
+static FoldPlan plan_fold(int rows, int C, bool scratch) {
+    if (!scratch || fold_rows(rows) == 0 || 2 * C > 1024) return {0, rows};
+    const int slab = std::max(16, rows / 128);
+    return {slab, cdiv(rows, slab)};
 }
 
-// Many partial rows: fold them in coalesced slabs first (a column-slice finalize touches every row from every block); returns
-// the rows the finalize kernel then reads (possibly moved to `scratch`).
-static const float* fold_partials(const float* partial, int& rows, int C, float* scratch, hipStream_t st) {
-    if (!scratch || fold_rows(rows) == 0 || 2 * C > 1024) return partial;
-    const int slab = std::max(16, rows / 128), nb2 = cdiv(rows, slab);
-    hipLaunchKernelGGL(k_rows_fold, dim3(nb2), dim3(256), 0, st, partial, rows, 2 * C, slab, scratch);
-    rows = nb2;
+// ROWS_STEM_TAIL: the stem tail's kernels take RED_ROWS_PER_BLOCK rows per block whatever M is, while its callers size the workspace with
+// sd_col_reduce_workspace_bytes, i.e. by the BatchNorm rule.  That is never the smaller size: red_rows(M) <= RED_ROWS_PER_BLOCK, so the stem
+// tail has at most as many partial rows as the BatchNorm rule, and the two differ only for M / 256 < 1024, where neither has rows to fold.
+static ColReducePlan plan_col_reduce(int64_t M, int C, RowsRule rule) {
+    ColReducePlan p;
+    const int nb_bn = cdiv(M, red_rows(M));
+    p.rpb = rule == ROWS_STEM_TAIL ? RED_ROWS_PER_BLOCK : red_rows(M);
+    p.nb = cdiv(M, p.rpb);
+    p.fold = plan_fold(p.nb, C, true);
+    p.partial_at = 0;
+    p.means_at = (size_t)p.nb * 2 * C;
+    p.fold_at = p.means_at + 2 * (size_t)C;
+    p.ws_bytes = align_up(((size_t)nb_bn + fold_rows(nb_bn)) * 2 * C * sizeof(float) + 2 * (size_t)C * sizeof(float), 256);
+    return p;
+}
+
+static const float* launch_fold(const float* partial, int rows, int C, const FoldPlan& f, float* scratch, hipStream_t st) {
+    if (!f.slab) return partial;
+    hipLaunchKernelGGL(k_rows_fold, dim3(f.rows), dim3(256), 0, st, partial, rows, 2 * C, f.slab, scratch);
     return scratch;
 }
 
+// The finish of partial rows [rows][2][C], sums in fp64.  MODE 0: a = mean, b = invstd, c / d = running mean / variance; MODE 1: a = dgamma,
+// b = dbeta (+= when accumulate), c / d = mean(g), mean(g * xhat); MODE 2: a = the plain column sums (+=).  With `sums` (synchronized BatchNorm)
+// phase 1 only: [S0, S1, n] in fp64 and, MODE 1, dgamma / dbeta from the local sums; the rest then comes from sd_bn_*_from_sums.
+template <int MODE>
+static void col_finish(const float* fin, int rows, int64_t M, int C, float eps, float momentum, float* a, float* b, float* c, float* d, int accumulate,
+                       double* sums, hipStream_t st) {
+    float* const none = nullptr;
+    if constexpr (MODE != 2) {
+        if (sums) {
+            hipLaunchKernelGGL(k_col_sums<MODE>, dim3(chan_launch(C, 4).grid), dim3(256), 0, st, fin, rows, C, (double)M, MODE ? a : none, MODE ? b : none, accumulate, sums);
+            return;
+        }
+    }
+    hipLaunchKernelGGL(k_col_finalize<MODE>, dim3(chan_launch(C, 4).grid), dim3(256), 0, st, fin, rows, C, (double)M, eps, momentum, a, b, MODE == 0 ? c : none,
+                       MODE == 0 ? d : none, MODE == 1 ? c : none, MODE == 1 ? d : none, accumulate);
+}
+
+// ---- checkers: one per argument family ------------------------------------------------------------------------------------------------------
 static int check_mc(const char* what, int64_t M, int C) {
     SD_REQUIRE(M > 0 && C > 0 && C % 4 == 0 && C <= 1024 && (C / 4) <= 256 && 256 % (C / 4) == 0, SD_ERR_INVALID,
                "%s: needs M > 0 and C in {4..1024} with C/4 dividing 256 (got M=%lld C=%d)", what, (long long)M, C);
     return 0;
 }
-
-}  // extern "C"
-
-// the forward finish of partial rows [rows][2][C]: k_col_finalize<0> (one launch), or with `sums` phase 1 of the split finish only
-// (k_col_sums<0>: [S0, S1, n] in fp64; mean / invstd / running statistics then come from sd_bn_stats_from_sums)
-static void bn_stats_finish(const float* fin, int rows, int64_t M, int C, float eps, float momentum, float* running_mean, float* running_var,
-                            float* mean, float* invstd, double* sums, hipStream_t st) {
-    if (sums)
-        hipLaunchKernelGGL(k_col_sums<0>, dim3(cdiv(C, 4)), dim3(256), 0, st, fin, rows, C, (double)M, (float*)nullptr, (float*)nullptr, 0, sums);
-    else
-        hipLaunchKernelGGL(k_col_finalize<0>, dim3(cdiv(C, 4)), dim3(256), 0, st, fin, rows, C, (double)M, eps, momentum,
-                           mean, invstd, running_mean, running_var, (float*)nullptr, (float*)nullptr, 0);
+// the ReLU form of a BatchNorm backward and the pointers it needs: y for the mask from y (1) or the mask bytes (3), beta to recompute it (2)
+static int check_relu(const char* what, int relu, const void* y, const void* beta) {
+    SD_REQUIRE(relu >= 0 && relu <= 3, SD_ERR_INVALID, "%s: relu must be 0 (none), 1 (mask from y), 2 (mask recomputed from x) or 3 (mask bytes)", what);
+    SD_REQUIRE(((relu != 1 && relu != 3) || y) && (relu != 2 || beta), SD_ERR_INVALID, "%s: null pointer", what);
+    return 0;
+}
+static int check_sums(const char* what, const double* sums) {
+    SD_REQUIRE((reinterpret_cast<uintptr_t>(sums) & 7u) == 0, SD_ERR_ALIGN, "%s: the fp64 sums must be 8-byte aligned", what);
+    return 0;
+}
+static int check_map(const char* what, bool pointers, int B, int H, int W, int C, int cmul) {
+    SD_REQUIRE(pointers && B > 0 && H > 0 && W > 0 && C > 0 && C % cmul == 0, SD_ERR_INVALID, "%s: bad arguments", what);
+    return 0;
+}
+// only the fp32 form of the stem tail's backward has pixel kernels for odd maps
+static int check_stem_quad(const char* what, bool quad, bool f32) {
+    SD_REQUIRE(quad || f32, SD_ERR_INVALID, "%s: the bf16 form needs even Hi, Wi", what);
+    return 0;
 }
 
-// the backward finish: k_col_finalize<1> (dgamma / dbeta and the two means), or with `sums` phase 1 only (dgamma / dbeta from the local
-// sums + [S0, S1, n]; the means then come from sd_bn_bwd_means_from_sums)
-static void bn_bwd_finish(const float* fin, int rows, int64_t M, int C, float* dgamma, float* dbeta, int accumulate, float* mg, float* mgx,
-                          double* sums, hipStream_t st) {
-    if (sums)
-        hipLaunchKernelGGL(k_col_sums<1>, dim3(cdiv(C, 4)), dim3(256), 0, st, fin, rows, C, (double)M, dgamma, dbeta, accumulate, sums);
-    else
-        hipLaunchKernelGGL(k_col_finalize<1>, dim3(cdiv(C, 4)), dim3(256), 0, st, fin, rows, C, (double)M, 0.f, 0.f, dgamma, dbeta,
-                           (float*)nullptr, (float*)nullptr, mg, mgx, accumulate);
+// ---- predicates: one per kernel choice ------------------------------------------------------------------------------------------------------
+// The bf16 x8 kernels of the BatchNorm backward: one choice for the reduce and the apply pass, so that the fused and the split forms reduce
+// in the same order.  The reduce-only form has no dx / g_out and passes null (aligned16(nullptr) is true): buffers from one allocator make
+// the same choice in both forms.
+static bool bn_bwd_wide(int C, int relu, const void* dy, const void* x, const void* dx, const void* g_out) {
+    return C % 8 == 0 && relu != 1 && aligned16(dy) && aligned16(x) && aligned16(dx) && aligned16(g_out);
+}
+static bool bn_apply_wide(int C, const void* x, const void* y, const void* residual) { return C % 8 == 0 && aligned16(x) && aligned16(y) && aligned16(residual); }
+// two windows per thread in the stem tail's forward (`option`: pool_fwd_pair; elems channels per thread: 4 fp32, 8 bf16; idx: a byte per channel)
+static bool pool_fwd_pair(int option, int elems, int Wo, int C, const void* x, const void* y_pool, const void* idx) {
+    return option && Wo % 2 == 0 && C % elems == 0 && aligned16(x) && aligned16(y_pool) && (reinterpret_cast<uintptr_t>(idx) & (uintptr_t)(elems - 1)) == 0;
+}
+static bool stem_bwd_quad(int Hi, int Wi) { return Hi % 2 == 0 && Wi % 2 == 0; }        // even maps: 2x2 quads share their four windows
+// the C = 128 pipelines of the head (the default FPN depth): wave-private LDS-DMA rings
+static bool head_fwd_f32_c128(int64_t M, int HW, int C, int Co, const void* x, const void* w, const void* y) {
+    return C == 128 && Co <= 16 && HW % 16 == 0 && M < (1ll << 31) && aligned16(x) && aligned16(w) && aligned16(y);
+}
+static bool head_fwd_bf16_c128(int HW, int C, const void* x, const void* y) { return C == 128 && HW % 4 == 0 && aligned16(x) && aligned16(y); }
+static bool head_wgrad_f32_c128(int64_t M, int HW, int C, int Co, const void* x, const void* dy) {
+    return C == 128 && Co <= 16 && HW % 16 == 0 && M < (1ll << 31) && aligned16(x) && aligned16(dy);
 }
 
-static bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
+static inline int pool_out(int n) { return (n + 2 - 3) / 2 + 1; }
+template <typename... Ts> constexpr bool all_f32 = (std::is_same<Ts, float>::value && ...);
+template <typename T> constexpr bool is_bf16 = std::is_same<T, uint16_t>::value;
 
-template <typename T>
-static int bn_train_stats_any(const char* what, const T* x, int64_t M, int C, float eps, float momentum, float* running_mean, float* running_var,
-                              float* mean, float* invstd, double* sums, void* workspace, size_t workspace_bytes, hipStream_t st) {
+// ---- BatchNorm and column sums --------------------------------------------------------------------------------------------------------------
+// a whole-tensor reduction of x [M][C] through the workspace.  MODE 0: the statistics (sd_bn_train_stats / _sums); 2: sd_col_sum (a = out)
+template <int MODE, typename T>
+static int col_reduce_any(const char* what, const T* x, int64_t M, int C, float eps, float momentum, float* a, float* b, float* c, float* d, double* sums,
+                          int accumulate, void* workspace, size_t workspace_bytes, hipStream_t st) {
     if (int e = check_mc(what, M, C)) return e;
-    SD_REQUIRE(x && (sums || (mean && invstd)) && workspace, SD_ERR_INVALID, "%s: null pointer", what);
-    SD_REQUIRE(aligned8(sums), SD_ERR_ALIGN, "%s: the fp64 sums must be 8-byte aligned", what);
-    SD_REQUIRE(workspace_bytes >= sd_col_reduce_workspace_bytes(M, C), SD_ERR_WORKSPACE, "%s: workspace too small", what);
-    const int rpb = red_rows(M), nb = cdiv(M, rpb);
-    hipLaunchKernelGGL((k_col_reduce<0, T>), dim3(nb), dim3(256), 0, st, x, (const T*)nullptr, (const T*)nullptr, (const float*)nullptr,
-                       (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, 0, M, C, (float*)workspace, rpb);
+    SD_REQUIRE(x && (MODE == 2 ? a != nullptr : (sums || (a && b))) && workspace, SD_ERR_INVALID, "%s: null pointer", what);
+    if (int e = check_sums(what, sums)) return e;
+    const ColReducePlan p = plan_col_reduce(M, C, ROWS_BN);
+    SD_REQUIRE(workspace_bytes >= p.ws_bytes, SD_ERR_WORKSPACE, "%s: workspace too small", what);
+    float* ws = (float*)workspace;
+    hipLaunchKernelGGL((k_col_reduce<MODE, T>), dim3(p.nb), dim3(256), 0, st, x, (const T*)nullptr, (const T*)nullptr, (const float*)nullptr,
+                       (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, 0, M, C, ws + p.partial_at, p.rpb);
     SD_LAUNCH_CHECK();
-    int rows = nb;
-    const float* fin = fold_partials((const float*)workspace, rows, C, (float*)workspace + ((size_t)nb + 1) * 2 * C, st);
-    bn_stats_finish(fin, rows, M, C, eps, momentum, running_mean, running_var, mean, invstd, sums, st);
+    const float* fin = launch_fold(ws + p.partial_at, p.nb, C, p.fold, ws + p.fold_at, st);
+    col_finish<MODE>(fin, p.fold.rows, M, C, eps, momentum, a, b, c, d, accumulate, sums, st);
     SD_LAUNCH_CHECK();
     return 0;
 }
 
-// the reduction half of sd_bn_bwd[_bf16]: partial rows of (sum g, sum g * xhat) into the workspace, then the finish (the two means at
-// workspace + nb * 2C, or with `sums` phase 1 into the caller's fp64 buffer).  `wide`: the bf16 x8 kernels (the caller's choice, so
-// that the fused and the split forms reduce in the same order).
+// The reduction half of sd_bn_bwd[_bf16]: partial rows of (sum g, sum g * xhat) into the workspace, then the finish (the two means at the
+// plan's means_at, or with `sums` phase 1 into the caller's fp64 buffer).  `wide`: bn_bwd_wide, the caller's choice.  `plan_out`: where a fused
+// form finds the means.
 template <typename T>
 static int bn_bwd_reduce_any(const char* what, const T* dy, const T* x, const void* y, int relu, int64_t M, int C, const float* mean,
                              const float* invstd, const float* gamma, const float* beta, float* dgamma, float* dbeta, int accumulate,
-                             double* sums, bool wide, void* workspace, size_t workspace_bytes, hipStream_t st) {
+                             double* sums, bool wide, void* workspace, size_t workspace_bytes, hipStream_t st, ColReducePlan* plan_out = nullptr) {
     if (int e = check_mc(what, M, C)) return e;
-    SD_REQUIRE(relu >= 0 && relu <= 3, SD_ERR_INVALID, "%s: relu must be 0 (none), 1 (mask from y), 2 (mask recomputed from x) or 3 (mask bytes)", what);
-    SD_REQUIRE(dy && x && mean && invstd && gamma && dgamma && dbeta && workspace && ((relu != 1 && relu != 3) || y) && (relu != 2 || beta),
-               SD_ERR_INVALID, "%s: null pointer", what);
-    SD_REQUIRE(aligned8(sums), SD_ERR_ALIGN, "%s: the fp64 sums must be 8-byte aligned", what);
-    SD_REQUIRE(workspace_bytes >= sd_col_reduce_workspace_bytes(M, C), SD_ERR_WORKSPACE, "%s: workspace too small", what);
-    const int rpb = red_rows(M), nb = cdiv(M, rpb);
-    float* partial = (float*)workspace;
-    float* mg = partial + (size_t)nb * 2 * C;
-    float* mgx = mg + C;
-    if constexpr (std::is_same<T, uint16_t>::value) {
-        if (wide) hipLaunchKernelGGL(k_col_reduce_bwd_bf16x8, dim3(nb), dim3(256), 0, st, dy, x, (const uint8_t*)y, mean, invstd, gamma, beta, relu,
-                                     M, C, partial, rpb);
-        else hipLaunchKernelGGL((k_col_reduce<1, uint16_t>), dim3(nb), dim3(256), 0, st, dy, x, (const uint16_t*)y, mean, invstd, gamma, beta,
-                                relu, M, C, partial, rpb);
-    } else {
-        hipLaunchKernelGGL(k_col_reduce<1>, dim3(nb), dim3(256), 0, st, dy, x, (const float*)y, mean, invstd, gamma, beta, relu, M, C, partial, rpb);
+    if (int e = check_relu(what, relu, y, beta)) return e;
+    SD_REQUIRE(dy && x && mean && invstd && gamma && dgamma && dbeta && workspace, SD_ERR_INVALID, "%s: null pointer", what);
+    if (int e = check_sums(what, sums)) return e;
+    const ColReducePlan p = plan_col_reduce(M, C, ROWS_BN);
+    SD_REQUIRE(workspace_bytes >= p.ws_bytes, SD_ERR_WORKSPACE, "%s: workspace too small", what);
+    float* ws = (float*)workspace;
+    float* partial = ws + p.partial_at;
+    if (is_bf16<T> && wide)
+        hipLaunchKernelGGL(k_col_reduce_bwd_bf16x8, dim3(p.nb), dim3(256), 0, st, (const uint16_t*)dy, (const uint16_t*)x, (const uint8_t*)y, mean, invstd,
+                           gamma, beta, relu, M, C, partial, p.rpb);
+    else
+        hipLaunchKernelGGL((k_col_reduce<1, T>), dim3(p.nb), dim3(256), 0, st, dy, x, (const T*)y, mean, invstd, gamma, beta, relu, M, C, partial, p.rpb);
+    SD_LAUNCH_CHECK();
+    const float* fin = launch_fold(partial, p.nb, C, p.fold, ws + p.fold_at, st);
+    col_finish<1>(fin, p.fold.rows, M, C, 0.f, 0.f, dgamma, dbeta, ws + p.means_at, ws + p.means_at + C, accumulate, sums, st);
+    SD_LAUNCH_CHECK();
+    if (plan_out) *plan_out = p;
+    return 0;
+}
+
+// the apply pass of the BatchNorm backward (means = [mean(g) (C), mean(g * xhat) (C)])
+template <typename T>
+static int bn_bwd_apply_launch(const T* dy, const T* x, const void* y, int relu, int64_t M, int C, const float* mean, const float* invstd,
+                               const float* gamma, const float* beta, const float* means, T* dx, T* g_out, bool wide, hipStream_t st) {
+    const Launch l = bn_ew_launch(is_bf16<T> && wide, M, C);
+    if (is_bf16<T> && wide)
+        SD_RETURN_LAUNCH(k_bn_bwd_apply_bf16x8, l.grid, 0, st, (const uint16_t*)dy, (const uint16_t*)x, (const uint8_t*)y, relu, l.n, C, mean, invstd, gamma,
+                      beta, means, means + C, (uint16_t*)dx, (uint16_t*)g_out);
+    SD_RETURN_LAUNCH(k_bn_bwd_apply<T>, l.grid, 0, st, dy, x, (const T*)y, relu, l.n, C, mean, invstd, gamma, beta, means, means + C, dx, g_out);
+}
+
+template <typename T>
+static int bn_bwd_any(const char* what, const T* dy, const T* x, const void* y, int relu, int64_t M, int C, const float* mean, const float* invstd,
+                      const float* gamma, const float* beta, T* dx, T* g_out, float* dgamma, float* dbeta, int accumulate, void* workspace,
+                      size_t workspace_bytes, hipStream_t st) {
+    SD_REQUIRE(dx, SD_ERR_INVALID, "%s: null pointer", what);
+    const bool wide = is_bf16<T> && bn_bwd_wide(C, relu, dy, x, dx, g_out);
+    ColReducePlan p;
+    if (int e = bn_bwd_reduce_any<T>(what, dy, x, y, relu, M, C, mean, invstd, gamma, beta, dgamma, dbeta, accumulate, nullptr, wide, workspace,
+                                     workspace_bytes, st, &p)) return e;
+    return bn_bwd_apply_launch<T>(dy, x, y, relu, M, C, mean, invstd, gamma, beta, (const float*)workspace + p.means_at, dx, g_out, wide, st);
+}
+
+template <typename T>
+static int bn_bwd_apply_any(const char* what, const T* dy, const T* x, const void* y, int relu, int64_t M, int C, const float* mean,
+                            const float* invstd, const float* gamma, const float* beta, const float* means, T* dx, T* g_out, hipStream_t st) {
+    if (int e = check_mc(what, M, C)) return e;
+    if (int e = check_relu(what, relu, y, beta)) return e;
+    SD_REQUIRE(dy && x && mean && invstd && gamma && means && dx, SD_ERR_INVALID, "%s: null pointer", what);
+    return bn_bwd_apply_launch<T>(dy, x, y, relu, M, C, mean, invstd, gamma, beta, means, dx, g_out, is_bf16<T> && bn_bwd_wide(C, relu, dy, x, dx, g_out), st);
+}
+
+// The finish on caller-provided partial rows [rows][2][C] (one per conv tile: up to 8192), MODE and a..d as col_finish.  `split`: phase 1 of
+// synchronized BatchNorm into `sums` -- same rows, scratch and summation order as the one-launch form.
+template <int MODE>
+static int rows_finish_any(const char* what, bool split, const float* partial, int rows, int64_t M, int C, float eps, float momentum, float* a, float* b,
+                           float* c, float* d, int accumulate, double* sums, float* scratch, hipStream_t st) {
+    if (int e = check_mc(what, M, C)) return e;
+    const bool outputs = split ? sums && (MODE == 0 || (a && b)) : a && b && (MODE == 0 || c);
+    SD_REQUIRE(partial && outputs && rows > 0, SD_ERR_INVALID,
+               split ? "%s: bad arguments (null pointer or rows <= 0)" : "%s: bad arguments", what);
+    if (int e = check_sums(what, sums)) return e;
+    const FoldPlan f = plan_fold(rows, C, scratch != nullptr);
+    const float* fin = launch_fold(partial, rows, C, f, scratch, st);
+    SD_LAUNCH_CHECK();
+    col_finish<MODE>(fin, f.rows, M, C, eps, momentum, a, b, c, d, accumulate, sums, st);
+    SD_LAUNCH_CHECK();
+    return 0;
+}
+
+template <typename T>
+static int bn_apply_any(const char* what, const T* x, T* y, int64_t M, int C, const float* mean, const float* invstd, const float* gamma,
+                        const float* beta, const T* residual, int relu, uint8_t* relu_mask_out, hipStream_t st) {
+    if (int e = check_mc(what, M, C)) return e;
+    SD_REQUIRE(x && y && mean && invstd && gamma && beta, SD_ERR_INVALID, "%s: null pointer", what);
+    const bool wide = is_bf16<T> && bn_apply_wide(C, x, y, residual);
+    const Launch l = bn_ew_launch(wide, M, C);
+    if (wide)
+        SD_RETURN_LAUNCH(k_bn_apply_bf16x8, l.grid, 0, st, (const uint16_t*)x, (uint16_t*)y, l.n, C, mean, invstd, gamma, beta, (const uint16_t*)residual, relu,
+                      relu_mask_out);
+    SD_RETURN_LAUNCH(k_bn_apply<T>, l.grid, 0, st, x, y, l.n, C, mean, invstd, gamma, beta, residual, relu, relu_mask_out);
+}
+
+// ---- pooling, the stem tail, upsample -------------------------------------------------------------------------------------------------------
+template <typename T>
+static int bn_relu_maxpool_fwd_any(const char* what, const T* x, int B, int Hi, int Wi, int C, const float* mean, const float* invstd,
+                                   const float* gamma, const float* beta, T* y_pool, uint8_t* idx, hipStream_t st) {
+    if (int e = check_map(what, x && mean && invstd && gamma && beta && y_pool && idx, B, Hi, Wi, C, 4)) return e;
+    constexpr int ELEMS = is_bf16<T> ? 8 : 4;
+    const int Ho = pool_out(Hi), Wo = pool_out(Wi);
+    const bool pair = pool_fwd_pair(g_pool_pair, ELEMS, Wo, C, x, y_pool, idx);
+    const Launch l = pool_fwd_launch(pair, ELEMS, B, Ho, Wo, C);
+    if (pair) SD_RETURN_LAUNCH((k_bn_relu_maxpool_fwd_pair<T, T, ELEMS>), l.grid, 0, st, x, mean, invstd, gamma, beta, y_pool, idx, B, Hi, Wi, Ho, Wo, C);
+    SD_RETURN_LAUNCH((k_bn_relu_maxpool_fwd<T, T>), l.grid, 0, st, x, mean, invstd, gamma, beta, y_pool, idx, B, Hi, Wi, Ho, Wo, C);
+}
+
+// The stem tail's backward (max-pool -> ReLU -> BatchNorm): reduce, finish, apply.  Split forms for synchronized BatchNorm: `sums` -> stop
+// after phase 1 (dgamma / dbeta from the local sums, [S0, S1, n] in fp64); the apply pass alone takes the means.  `fused`: called by the fused
+// form, which has checked the map already.
+template <typename XT>
+static int stem_bwd_reduce_any(const char* what, bool fused, const XT* dpool, const uint8_t* idx, const XT* x, int B, int Hi, int Wi, int C,
+                               const float* mean, const float* invstd, const float* gamma, const float* beta, float* dgamma, float* dbeta,
+                               int accumulate, double* sums, void* workspace, size_t workspace_bytes, hipStream_t st, ColReducePlan* plan_out = nullptr) {
+    const int64_t M = (int64_t)B * Hi * Wi;
+    if (int e = check_mc(what, M, C)) return e;
+    SD_REQUIRE(dpool && idx && x && mean && invstd && gamma && beta && dgamma && dbeta && workspace, SD_ERR_INVALID, "%s: null pointer", what);
+    if (int e = check_sums(what, sums)) return e;
+    const ColReducePlan p = plan_col_reduce(M, C, ROWS_STEM_TAIL);
+    SD_REQUIRE(workspace_bytes >= p.ws_bytes, SD_ERR_WORKSPACE, "%s: workspace too small", what);
+    const bool quad = stem_bwd_quad(Hi, Wi);
+    if (!fused) if (int e = check_stem_quad(what, quad, all_f32<XT>)) return e;
+    const int Ho = pool_out(Hi), Wo = pool_out(Wi);
+    float* ws = (float*)workspace;
+    float* partial = ws + p.partial_at;
+    if (quad) hipLaunchKernelGGL((k_pool_bn_bwd_reduce_quad<XT, XT>), dim3(p.nb), dim3(256), 0, st, dpool, idx, x, mean, invstd, gamma, beta, Hi, Wi, Ho, Wo, M / 4, C, partial);
+    else if constexpr (all_f32<XT>) hipLaunchKernelGGL(k_pool_bn_bwd_reduce, dim3(p.nb), dim3(256), 0, st, dpool, idx, x, mean, invstd, gamma, beta, Hi, Wi, Ho, Wo, M, C, partial);
+    SD_LAUNCH_CHECK();
+    const float* fin = launch_fold(partial, p.nb, C, p.fold, ws + p.fold_at, st);
+    col_finish<1>(fin, p.fold.rows, M, C, 0.f, 0.f, dgamma, dbeta, ws + p.means_at, ws + p.means_at + C, accumulate, sums, st);
+    SD_LAUNCH_CHECK();
+    if (plan_out) *plan_out = p;
+    return 0;
+}
+
+template <typename XT, typename DT>
+static int stem_bwd_apply_launch(const XT* dpool, const uint8_t* idx, const XT* x, int B, int Hi, int Wi, int C, const float* mean, const float* invstd,
+                                 const float* gamma, const float* beta, const float* means, DT* dx, hipStream_t st) {
+    const int Ho = pool_out(Hi), Wo = pool_out(Wi);
+    const bool quad = stem_bwd_quad(Hi, Wi);
+    const Launch l = stem_apply_launch(quad, B, Hi, Wi, C);
+    if (quad)
+        SD_RETURN_LAUNCH((k_pool_bn_bwd_apply_quad<XT, XT, DT>), l.grid, 0, st, dpool, idx, x, mean, invstd, gamma, beta, means, means + C, Hi, Wi, Ho, Wo, l.n,
+                      C, dx);
+    if constexpr (all_f32<XT, DT>)
+        SD_RETURN_LAUNCH(k_pool_bn_bwd_apply, l.grid, 0, st, dpool, idx, x, mean, invstd, gamma, beta, means, means + C, Hi, Wi, Ho, Wo, l.n, C, dx);
+    return 0;                                        // (a bf16 form on an odd map: refused by check_stem_quad before it gets here)
+}
+
+template <typename XT, typename DT>
+static int stem_bwd_apply_any(const char* what, const XT* dpool, const uint8_t* idx, const XT* x, int B, int Hi, int Wi, int C, const float* mean,
+                              const float* invstd, const float* gamma, const float* beta, const float* means, DT* dx, hipStream_t st) {
+    if (int e = check_mc(what, (int64_t)B * Hi * Wi, C)) return e;
+    SD_REQUIRE(dpool && idx && x && mean && invstd && gamma && beta && means && dx, SD_ERR_INVALID, "%s: null pointer", what);
+    if (int e = check_stem_quad(what, stem_bwd_quad(Hi, Wi), all_f32<XT, DT>)) return e;
+    return stem_bwd_apply_launch<XT, DT>(dpool, idx, x, B, Hi, Wi, C, mean, invstd, gamma, beta, means, dx, st);
+}
+
+template <typename XT, typename DT>
+static int stem_bwd_any(const char* what, const XT* dpool, const uint8_t* idx, const XT* x, int B, int Hi, int Wi, int C, const float* mean,
+                        const float* invstd, const float* gamma, const float* beta, DT* dx, float* dgamma, float* dbeta, int accumulate,
+                        void* workspace, size_t workspace_bytes, hipStream_t st) {
+    SD_REQUIRE(dx, SD_ERR_INVALID, "%s: null pointer", what);
+    if (int e = check_stem_quad(what, stem_bwd_quad(Hi, Wi), all_f32<XT, DT>)) return e;
+    ColReducePlan p;
+    if (int e = stem_bwd_reduce_any<XT>(what, true, dpool, idx, x, B, Hi, Wi, C, mean, invstd, gamma, beta, dgamma, dbeta, accumulate, nullptr, workspace,
+                                        workspace_bytes, st, &p)) return e;
+    return stem_bwd_apply_launch<XT, DT>(dpool, idx, x, B, Hi, Wi, C, mean, invstd, gamma, beta, (const float*)workspace + p.means_at, dx, st);
+}
+
+template <typename T>
+static int upsample2x_bwd_any(const char* what, const T* dy, const T* add, T* dx, int B, int H, int W, int C, hipStream_t st) {
+    if (int e = check_map(what, dy && dx, B, H, W, C, 4)) return e;
+    SD_RETURN_LAUNCH(k_up2_bwd<T>, map_launch(B, H, W, C, 4).grid, 0, st, dy, add, dx, B, H, W, C);
+}
+
+// ---- the narrow head (Co <= HEAD_NARROW_MAX_CO; wider ones: sd_head_wide.hip) ---------------------------------------------------------------
+struct HeadLaunch { bool c128; int grid, rows; size_t lds; };             // rows: tiles of the forward, partial rows of the weight gradient
+
+static HeadLaunch plan_head_fwd(bool bf16, int64_t M, int HW, int C, int Co, const void* x, const void* w, const void* y) {
+    if (bf16 && head_fwd_bf16_c128(HW, C, x, y)) {                         // wave-private LDS-DMA + bf16 MFMA pipeline
+        const int ntiles = cdiv(M, 64);
+        return {true, std::max(1, std::min(cdiv(ntiles, 4), 1024)), ntiles, 0};
     }
-    SD_LAUNCH_CHECK();
-    int rows = nb;
-    const float* fin = fold_partials(partial, rows, C, mgx + C, st);
-    bn_bwd_finish(fin, rows, M, C, dgamma, dbeta, accumulate, mg, mgx, sums, st);
-    SD_LAUNCH_CHECK();
-    return 0;
+    if (!bf16 && head_fwd_f32_c128(M, HW, C, Co, x, w, y)) {
+        const int ntiles = (int)(M / 16);
+        return {true, std::min(cdiv(ntiles, 4), 256), ntiles, (size_t)4 * HF_NST * 2048 * sizeof(float)};
+    }
+    return {false, cdiv(M, 64), 0, ((size_t)64 * (C + 4) + (size_t)Co * C) * sizeof(float)};
 }
 
-// the apply pass of sd_bn_bwd_bf16 (means = [mean(g) (C), mean(g * xhat) (C)])
-static int bn_bwd_apply_bf16(const void* dy, const void* x, const void* y, int relu, int64_t M, int C, const float* mean, const float* invstd,
-                             const float* gamma, const float* beta, const float* means, void* dx, void* g_out, bool wide, hipStream_t st) {
-    const int64_t n4 = M * C / 4;
-    if (wide) hipLaunchKernelGGL(k_bn_bwd_apply_bf16x8, dim3(ew_grid(n4 / 2)), dim3(256), 0, st, (const uint16_t*)dy, (const uint16_t*)x, (const uint8_t*)y,
-                                 relu, n4 / 2, C, mean, invstd, gamma, beta, means, means + C, (uint16_t*)dx, (uint16_t*)g_out);
-    else hipLaunchKernelGGL(k_bn_bwd_apply<uint16_t>, dim3(ew_grid(n4)), dim3(256), 0, st, (const uint16_t*)dy, (const uint16_t*)x, (const uint16_t*)y,
-                            relu, n4, C, mean, invstd, gamma, beta, means, means + C, (uint16_t*)dx, (uint16_t*)g_out);
-    SD_LAUNCH_CHECK();
-    return 0;
+// partial rows of the head weight gradient: one per block of k_head_wgrad[_bf16] (HEAD_WG_PIX pixels), or one per WAVE of k_head_wgrad_f32_c128
+// (up to 1024 waves = one block of four waves per CU, each wave on tiles of 16 pixels)
+static HeadLaunch plan_head_wgrad(bool c128, int64_t M) {
+    if (!c128) return {false, cdiv(M, HEAD_WG_PIX), cdiv(M, HEAD_WG_PIX), 0};
+    const int rows = (int)std::min<int64_t>(1024, (cdiv(M, 16) + 3) / 4 * 4);
+    return {true, rows / 4, rows, (size_t)4 * HF_NST * HWG_STAGE * sizeof(float)};
 }
 
+static inline int head_fin_grid(int C, int Co) { return cdiv(Co * C + Co, 8); }
+static void head_wgrad_fin(const float* partial, int rows, int C, int Co, float* dw, float* dbias, int accumulate, hipStream_t st) {
+    hipLaunchKernelGGL(k_head_wgrad_fin, dim3(head_fin_grid(C, Co)), dim3(256), 0, st, partial, rows, Co * C + Co, dw, dbias, Co * C, accumulate);
+}
+
+// the dynamic LDS of a C = 128 pipeline is above the default limit: raised once per process, at the kernel's first launch
+#define SD_RAISE_LDS_ONCE(kernel, bytes)                                                                                                               \
+    static const hipError_t attr_once = hipFuncSetAttribute(reinterpret_cast<const void*>(&kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes)); \
+    SD_HIP(attr_once)
+
+// ---- the optimizer --------------------------------------------------------------------------------------------------------------------------
+static int adam_launch(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n4, float lr, float beta1, float beta2, float eps,
+                       double bc1, double bc2, float grad_scale, hipStream_t st) {
+    SD_RETURN_LAUNCH(k_adam, ew_launch(n4).grid, 0, st, param, grad, exp_avg, exp_avg_sq, n4, lr, beta1, beta2, eps, (float)bc1, (float)sqrt(bc2), grad_scale);
+}
+
+static inline int sumsq_blocks(int64_t n) { return n > 0 ? (int)std::min<int64_t>(cdiv(n / 4, 256), SUMSQ_MAX_BLOCKS) : 0; }
+
+// ==== the C ABI.  The fp32 and bf16 forms of an entry point are one template body behind two exported names: FORMS stamps the export (NAME,
+// element type T, and V = the element type the C prototype shows: float, or void for bf16) ====================================================
 extern "C" {
 
-int sd_bn_train_stats(const float* x, int64_t M, int C, float eps, float momentum, float* running_mean, float* running_var,
-                      float* mean, float* invstd, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
-    return bn_train_stats_any<float>("sd_bn_train_stats", x, M, C, eps, momentum, running_mean, running_var, mean, invstd, nullptr, workspace,
-                                     workspace_bytes, (hipStream_t)stream);
-}
-
-int sd_bn_train_stats_bf16(const void* x, int64_t M, int C, float eps, float momentum, float* running_mean, float* running_var,
-                           float* mean, float* invstd, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
-    return bn_train_stats_any<uint16_t>("sd_bn_train_stats_bf16", (const uint16_t*)x, M, C, eps, momentum, running_mean, running_var, mean, invstd,
-                                        nullptr, workspace, workspace_bytes, (hipStream_t)stream);
-}
-
-int sd_bn_train_sums(const float* x, int64_t M, int C, double* sums, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
-    SD_REQUIRE(sums, SD_ERR_INVALID, "sd_bn_train_sums: null sums");
-    return bn_train_stats_any<float>("sd_bn_train_sums", x, M, C, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr, sums, workspace, workspace_bytes,
-                                     (hipStream_t)stream);
-}
-
-int sd_bn_train_sums_bf16(const void* x, int64_t M, int C, double* sums, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
-    SD_REQUIRE(sums, SD_ERR_INVALID, "sd_bn_train_sums_bf16: null sums");
-    return bn_train_stats_any<uint16_t>("sd_bn_train_sums_bf16", (const uint16_t*)x, M, C, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr, sums,
-                                        workspace, workspace_bytes, (hipStream_t)stream);
-}
-
+size_t sd_col_reduce_workspace_bytes(int64_t M, int C) { return plan_col_reduce(M, C, ROWS_BN).ws_bytes; }
 // rows of `scratch` the two-level finish of `rows` partial rows needs (0 = single level)
 int sd_bn_finalize_scratch_rows(int rows) { return fold_rows(rows); }
 
+#define FORMS(NAME, T, V)                                                                                                                               \
+    int NAME(const V* x, int64_t M, int C, float eps, float momentum, float* running_mean, float* running_var, float* mean, float* invstd, void* workspace, \
+             size_t workspace_bytes, sd_stream_t stream) {                                                                                              \
+        return col_reduce_any<0, T>(#NAME, (const T*)x, M, C, eps, momentum, mean, invstd, running_mean, running_var, nullptr, 0, workspace, workspace_bytes, \
+                                    (hipStream_t)stream);                                                                                               \
+    }
+FORMS(sd_bn_train_stats, float, float)
+FORMS(sd_bn_train_stats_bf16, uint16_t, void)
+#undef FORMS
+
+// synchronized BatchNorm: the statistics up to sums = [S0 = sum x (C), S1 = sum x^2 (C), n = M] in fp64 (sd_bn_stats_from_sums finishes)
+#define FORMS(NAME, T, V)                                                                                                                          \
+    int NAME(const V* x, int64_t M, int C, double* sums, void* workspace, size_t workspace_bytes, sd_stream_t stream) {                            \
+        SD_REQUIRE(sums, SD_ERR_INVALID, #NAME ": null sums");                                                                                     \
+        return col_reduce_any<0, T>(#NAME, (const T*)x, M, C, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr, sums, 0, workspace, workspace_bytes,  \
+                                    (hipStream_t)stream);                                                                                          \
+    }
+FORMS(sd_bn_train_sums, float, float)
+FORMS(sd_bn_train_sums_bf16, uint16_t, void)
+#undef FORMS
+
+#define FORMS(NAME, T, V)                                                                                                                           \
+    int NAME(const V* x, int64_t M, int C, float* out, int accumulate, void* workspace, size_t workspace_bytes, sd_stream_t stream) {              \
+        return col_reduce_any<2, T>(#NAME, (const T*)x, M, C, 0.f, 0.f, out, nullptr, nullptr, nullptr, nullptr, accumulate, workspace, workspace_bytes, \
+                                    (hipStream_t)stream);                                                                                           \
+    }
+FORMS(sd_col_sum, float, float)
+FORMS(sd_col_sum_bf16, uint16_t, void)
+#undef FORMS
+
 int sd_bn_finalize_stats(const float* partial, int rows, int64_t M, int C, float eps, float momentum, float* running_mean,
                          float* running_var, float* mean, float* invstd, float* scratch, sd_stream_t stream) {
-    if (int e = check_mc("sd_bn_finalize_stats", M, C)) return e;
-    SD_REQUIRE(partial && mean && invstd && rows > 0, SD_ERR_INVALID, "sd_bn_finalize_stats: bad arguments");
-    hipStream_t st = (hipStream_t)stream;
-    // Many partial rows (one per conv tile: up to 8192): a column-slice finalize would touch every row from every block, so
-    // the rows are first folded in coalesced slabs (full 2C-float rows per block), then the few slab sums are finished.
-    partial = fold_partials(partial, rows, C, scratch, st);
-    SD_LAUNCH_CHECK();
-    bn_stats_finish(partial, rows, M, C, eps, momentum, running_mean, running_var, mean, invstd, nullptr, st);
-    SD_LAUNCH_CHECK();
-    return 0;
+    return rows_finish_any<0>("sd_bn_finalize_stats", false, partial, rows, M, C, eps, momentum, mean, invstd, running_mean, running_var, 0, nullptr,
+                              scratch, (hipStream_t)stream);
 }
 
-// synchronized BatchNorm, forward: phase 1 of sd_bn_finalize_stats (same partial rows, same scratch, same summation order) into
-// sums = [S0 = sum x (C), S1 = sum x^2 (C), n = M] in fp64; after any all-reduce of `sums`, sd_bn_stats_from_sums finishes
+// synchronized BatchNorm, forward: phase 1 of sd_bn_finalize_stats; after any all-reduce of `sums`, sd_bn_stats_from_sums finishes
 int sd_bn_stats_sums(const float* partial, int rows, int64_t M, int C, double* sums, float* scratch, sd_stream_t stream) {
-    if (int e = check_mc("sd_bn_stats_sums", M, C)) return e;
-    SD_REQUIRE(partial && sums && rows > 0, SD_ERR_INVALID, "sd_bn_stats_sums: bad arguments (null pointer or rows <= 0)");
-    SD_REQUIRE(aligned8(sums), SD_ERR_ALIGN, "sd_bn_stats_sums: the fp64 sums must be 8-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    partial = fold_partials(partial, rows, C, scratch, st);
-    SD_LAUNCH_CHECK();
-    bn_stats_finish(partial, rows, M, C, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr, sums, st);
-    SD_LAUNCH_CHECK();
-    return 0;
+    return rows_finish_any<0>("sd_bn_stats_sums", true, partial, rows, M, C, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr, 0, sums, scratch,
+                              (hipStream_t)stream);
+}
+
+// second half of the reduction of sd_bn_bwd on caller-provided partial rows (sum g, sum g * xhat): dgamma / dbeta (+=) and
+// means_out = [mean(g) (C), mean(g * xhat) (C)] for sd_bn_bwd_apply
+int sd_bn_bwd_finalize(const float* partial, int rows, int64_t M, int C, float* dgamma, float* dbeta, int accumulate, float* means_out,
+                       float* scratch, sd_stream_t stream) {
+    return rows_finish_any<1>("sd_bn_bwd_finalize", false, partial, rows, M, C, 0.f, 0.f, dgamma, dbeta, means_out, means_out ? means_out + C : nullptr,
+                              accumulate, nullptr, scratch, (hipStream_t)stream);
+}
+
+// synchronized BatchNorm, backward: phase 1 of sd_bn_bwd_finalize -- dgamma / dbeta (+=) from the local sums and
+// sums = [sum g (C), sum g * xhat (C), n = M] in fp64
+int sd_bn_bwd_sums(const float* partial, int rows, int64_t M, int C, float* dgamma, float* dbeta, int accumulate, double* sums, float* scratch,
+                   sd_stream_t stream) {
+    return rows_finish_any<1>("sd_bn_bwd_sums", true, partial, rows, M, C, 0.f, 0.f, dgamma, dbeta, nullptr, nullptr, accumulate, sums, scratch,
+                              (hipStream_t)stream);
 }
 
 // phase 2: mean, invstd (biased variance) and the running statistics (unbiased with n = sums[2C]) from [S0, S1, n]
@@ -1821,416 +2081,146 @@ int sd_bn_stats_from_sums(const double* sums, int C, float eps, float momentum, 
     if (int e = check_mc("sd_bn_stats_from_sums", 1, C)) return e;
     SD_REQUIRE(sums && mean && invstd && (running_mean != nullptr) == (running_var != nullptr), SD_ERR_INVALID,
                "sd_bn_stats_from_sums: null pointer (running_mean and running_var are both given or both null)");
-    SD_REQUIRE(aligned8(sums), SD_ERR_ALIGN, "sd_bn_stats_from_sums: the fp64 sums must be 8-byte aligned");
-    hipLaunchKernelGGL(k_bn_stats_from_sums, dim3(cdiv(C, 256)), dim3(256), 0, (hipStream_t)stream, sums, C, eps, momentum, mean, invstd,
-                       running_mean, running_var);
-    SD_LAUNCH_CHECK();
-    return 0;
-}
-
-int sd_bn_apply(const float* x, float* y, int64_t M, int C, const float* mean, const float* invstd, const float* gamma, const float* beta,
-                const float* residual, int relu, uint8_t* relu_mask_out, sd_stream_t stream) {
-    if (int e = check_mc("sd_bn_apply", M, C)) return e;
-    SD_REQUIRE(x && y && mean && invstd && gamma && beta, SD_ERR_INVALID, "sd_bn_apply: null pointer");
-    const int64_t n4 = M * C / 4;
-    hipLaunchKernelGGL(k_bn_apply<float>, dim3(ew_grid(n4)), dim3(256), 0, (hipStream_t)stream, x, y, n4, C, mean, invstd, gamma, beta, residual, relu,
-                       relu_mask_out);
-    SD_LAUNCH_CHECK();
-    return 0;
-}
-
-int sd_bn_fold(const float* gamma, const float* beta, const float* running_mean, const float* running_var, float eps, int C, float* scale,
-               float* shift, sd_stream_t stream) {
-    SD_REQUIRE(gamma && beta && running_mean && running_var && scale && shift && C > 0, SD_ERR_INVALID, "sd_bn_fold: bad arguments");
-    hipLaunchKernelGGL(k_bn_fold, dim3(cdiv(C, 256)), dim3(256), 0, (hipStream_t)stream, gamma, beta, running_mean, running_var, eps, C, scale, shift);
-    SD_LAUNCH_CHECK();
-    return 0;
-}
-
-int sd_bn_bwd(const float* dy, const float* x, const float* y, int relu, int64_t M, int C, const float* mean, const float* invstd,
-              const float* gamma, const float* beta, float* dx, float* g_out, float* dgamma, float* dbeta, int accumulate, void* workspace,
-              size_t workspace_bytes, sd_stream_t stream) {
-    SD_REQUIRE(dx, SD_ERR_INVALID, "sd_bn_bwd: null pointer");
-    if (int e = bn_bwd_reduce_any<float>("sd_bn_bwd", dy, x, y, relu, M, C, mean, invstd, gamma, beta, dgamma, dbeta, accumulate, nullptr, false,
-                                         workspace, workspace_bytes, (hipStream_t)stream)) return e;
-    const int nb = cdiv(M, red_rows(M));
-    const float* mg = (const float*)workspace + (size_t)nb * 2 * C;
-    const int64_t n4 = M * C / 4;
-    hipLaunchKernelGGL(k_bn_bwd_apply<float>, dim3(ew_grid(n4)), dim3(256), 0, (hipStream_t)stream, dy, x, y, relu, n4, C, mean, invstd, gamma, beta,
-                       mg, mg + C, dx, g_out);
-    SD_LAUNCH_CHECK();
-    return 0;
-}
-
-// synchronized BatchNorm, backward: the reduce half of sd_bn_bwd alone -- dgamma / dbeta (+=) from the local sums and
-// sums = [sum g (C), sum g * xhat (C), n = M] in fp64; after any all-reduce of `sums`, sd_bn_bwd_means_from_sums + sd_bn_bwd_apply
-int sd_bn_bwd_reduce(const float* dy, const float* x, const float* y, int relu, int64_t M, int C, const float* mean, const float* invstd,
-                     const float* gamma, const float* beta, float* dgamma, float* dbeta, int accumulate, double* sums, void* workspace,
-                     size_t workspace_bytes, sd_stream_t stream) {
-    SD_REQUIRE(sums, SD_ERR_INVALID, "sd_bn_bwd_reduce: null pointer");
-    return bn_bwd_reduce_any<float>("sd_bn_bwd_reduce", dy, x, y, relu, M, C, mean, invstd, gamma, beta, dgamma, dbeta, accumulate, sums, false,
-                                    workspace, workspace_bytes, (hipStream_t)stream);
-}
-
-// second half of the reduction of sd_bn_bwd on caller-provided partial rows [rows][2][C] (sum g, sum g * xhat):
-// dgamma / dbeta (+=) and means_out = [mean(g) (C), mean(g * xhat) (C)] for sd_bn_bwd_apply
-int sd_bn_bwd_finalize(const float* partial, int rows, int64_t M, int C, float* dgamma, float* dbeta, int accumulate, float* means_out,
-                       float* scratch, sd_stream_t stream) {
-    if (int e = check_mc("sd_bn_bwd_finalize", M, C)) return e;
-    SD_REQUIRE(partial && dgamma && dbeta && means_out && rows > 0, SD_ERR_INVALID, "sd_bn_bwd_finalize: bad arguments");
-    hipStream_t st = (hipStream_t)stream;
-    const float* fin = fold_partials(partial, rows, C, scratch, st);
-    SD_LAUNCH_CHECK();
-    bn_bwd_finish(fin, rows, M, C, dgamma, dbeta, accumulate, means_out, means_out + C, nullptr, st);
-    SD_LAUNCH_CHECK();
-    return 0;
-}
-
-// synchronized BatchNorm, backward: phase 1 of sd_bn_bwd_finalize -- dgamma / dbeta (+=) from the local sums and
-// sums = [sum g (C), sum g * xhat (C), n = M] in fp64 (same partial rows, scratch and summation order)
-int sd_bn_bwd_sums(const float* partial, int rows, int64_t M, int C, float* dgamma, float* dbeta, int accumulate, double* sums, float* scratch,
-                   sd_stream_t stream) {
-    if (int e = check_mc("sd_bn_bwd_sums", M, C)) return e;
-    SD_REQUIRE(partial && dgamma && dbeta && sums && rows > 0, SD_ERR_INVALID, "sd_bn_bwd_sums: bad arguments (null pointer or rows <= 0)");
-    SD_REQUIRE(aligned8(sums), SD_ERR_ALIGN, "sd_bn_bwd_sums: the fp64 sums must be 8-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    const float* fin = fold_partials(partial, rows, C, scratch, st);
-    SD_LAUNCH_CHECK();
-    bn_bwd_finish(fin, rows, M, C, dgamma, dbeta, accumulate, nullptr, nullptr, sums, st);
-    SD_LAUNCH_CHECK();
-    return 0;
+    if (int e = check_sums("sd_bn_stats_from_sums", sums)) return e;
+    SD_RETURN_LAUNCH(k_bn_stats_from_sums, chan_launch(C, 256).grid, 0, (hipStream_t)stream, sums, C, eps, momentum, mean, invstd, running_mean, running_var);
 }
 
 // phase 2: means_out = [S0 / n (C), S1 / n (C)] with n = sums[2C], what sd_bn_bwd_apply[_bf16] / sd_maxpool_bn_relu_bwd_apply* consume
 int sd_bn_bwd_means_from_sums(const double* sums, int C, float* means_out, sd_stream_t stream) {
     if (int e = check_mc("sd_bn_bwd_means_from_sums", 1, C)) return e;
     SD_REQUIRE(sums && means_out, SD_ERR_INVALID, "sd_bn_bwd_means_from_sums: null pointer");
-    SD_REQUIRE(aligned8(sums), SD_ERR_ALIGN, "sd_bn_bwd_means_from_sums: the fp64 sums must be 8-byte aligned");
-    hipLaunchKernelGGL(k_bn_bwd_means_from_sums, dim3(cdiv(C, 256)), dim3(256), 0, (hipStream_t)stream, sums, C, means_out);
-    SD_LAUNCH_CHECK();
-    return 0;
+    if (int e = check_sums("sd_bn_bwd_means_from_sums", sums)) return e;
+    SD_RETURN_LAUNCH(k_bn_bwd_means_from_sums, chan_launch(C, 256).grid, 0, (hipStream_t)stream, sums, C, means_out);
 }
 
-// apply pass of sd_bn_bwd with the two per-channel means already known (sd_conv2d_dgrad_bn_reduce / sd_bn_bwd_finalize)
-int sd_bn_bwd_apply(const float* dy, const float* x, const float* y, int relu, int64_t M, int C, const float* mean, const float* invstd,
-                    const float* gamma, const float* beta, const float* means, float* dx, float* g_out, sd_stream_t stream) {
-    if (int e = check_mc("sd_bn_bwd_apply", M, C)) return e;
-    SD_REQUIRE(relu >= 0 && relu <= 3, SD_ERR_INVALID, "sd_bn_bwd_apply: relu must be 0 (none), 1 (mask from y), 2 (mask recomputed from x) or 3 (mask bytes)");
-    SD_REQUIRE(dy && x && mean && invstd && gamma && means && dx && ((relu != 1 && relu != 3) || y) && (relu != 2 || beta), SD_ERR_INVALID,
-               "sd_bn_bwd_apply: null pointer");
-    const int64_t n4 = M * C / 4;
-    hipLaunchKernelGGL(k_bn_bwd_apply<float>, dim3(ew_grid(n4)), dim3(256), 0, (hipStream_t)stream, dy, x, y, relu, n4, C, mean, invstd, gamma, beta,
-                       means, means + C, dx, g_out);
-    SD_LAUNCH_CHECK();
-    return 0;
+// bf16 activations (mixed-precision training): the same kernels with 2-byte loads / stores, all arithmetic in fp32
+#define FORMS(NAME, T, V)                                                                                                                          \
+    int NAME(const V* x, V* y, int64_t M, int C, const float* mean, const float* invstd, const float* gamma, const float* beta, const V* residual, \
+             int relu, uint8_t* relu_mask_out, sd_stream_t stream) {                                                                               \
+        return bn_apply_any<T>(#NAME, (const T*)x, (T*)y, M, C, mean, invstd, gamma, beta, (const T*)residual, relu, relu_mask_out, (hipStream_t)stream); \
+    }
+FORMS(sd_bn_apply, float, float)
+FORMS(sd_bn_apply_bf16, uint16_t, void)
+#undef FORMS
+
+int sd_bn_fold(const float* gamma, const float* beta, const float* running_mean, const float* running_var, float eps, int C, float* scale,
+               float* shift, sd_stream_t stream) {
+    SD_REQUIRE(gamma && beta && running_mean && running_var && scale && shift && C > 0, SD_ERR_INVALID, "sd_bn_fold: bad arguments");
+    SD_RETURN_LAUNCH(k_bn_fold, chan_launch(C, 256).grid, 0, (hipStream_t)stream, gamma, beta, running_mean, running_var, eps, C, scale, shift);
 }
 
-int sd_col_sum(const float* x, int64_t M, int C, float* out, int accumulate, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
-    if (int e = check_mc("sd_col_sum", M, C)) return e;
-    SD_REQUIRE(x && out && workspace, SD_ERR_INVALID, "sd_col_sum: null pointer");
-    SD_REQUIRE(workspace_bytes >= sd_col_reduce_workspace_bytes(M, C), SD_ERR_WORKSPACE, "sd_col_sum: workspace too small");
-    const int rpb = red_rows(M), nb = cdiv(M, rpb);
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_col_reduce<2>, dim3(nb), dim3(256), 0, st, x, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr,
-                       (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, 0, M, C, (float*)workspace, rpb);
-    SD_LAUNCH_CHECK();
-    int rows = nb;
-    const float* fin = fold_partials((const float*)workspace, rows, C, (float*)workspace + ((size_t)nb + 1) * 2 * C, st);
-    hipLaunchKernelGGL(k_col_finalize<2>, dim3(cdiv(C, 4)), dim3(256), 0, st, fin, rows, C, (double)M, 0.f, 0.f, out,
-                       (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr, accumulate);
-    SD_LAUNCH_CHECK();
-    return 0;
-}
+#define FORMS(NAME, T, V)                                                                                                                            \
+    int NAME(const V* dy, const V* x, const V* y, int relu, int64_t M, int C, const float* mean, const float* invstd, const float* gamma,            \
+             const float* beta, V* dx, V* g_out, float* dgamma, float* dbeta, int accumulate, void* workspace, size_t workspace_bytes, sd_stream_t stream) { \
+        return bn_bwd_any<T>(#NAME, (const T*)dy, (const T*)x, y, relu, M, C, mean, invstd, gamma, beta, (T*)dx, (T*)g_out, dgamma, dbeta, accumulate, \
+                             workspace, workspace_bytes, (hipStream_t)stream);                                                                       \
+    }
+FORMS(sd_bn_bwd, float, float)
+FORMS(sd_bn_bwd_bf16, uint16_t, void)
+#undef FORMS
+
+// synchronized BatchNorm, backward: the reduce half of sd_bn_bwd alone -- dgamma / dbeta (+=) from the local sums and
+// sums = [sum g (C), sum g * xhat (C), n = M] in fp64; after any all-reduce of `sums`, sd_bn_bwd_means_from_sums + sd_bn_bwd_apply
+#define FORMS(NAME, T, V)                                                                                                                             \
+    int NAME(const V* dy, const V* x, const V* y, int relu, int64_t M, int C, const float* mean, const float* invstd, const float* gamma,             \
+             const float* beta, float* dgamma, float* dbeta, int accumulate, double* sums, void* workspace, size_t workspace_bytes, sd_stream_t stream) { \
+        SD_REQUIRE(sums, SD_ERR_INVALID, #NAME ": null pointer");                                                                                     \
+        return bn_bwd_reduce_any<T>(#NAME, (const T*)dy, (const T*)x, y, relu, M, C, mean, invstd, gamma, beta, dgamma, dbeta, accumulate, sums,      \
+                                    is_bf16<T> && bn_bwd_wide(C, relu, dy, x, nullptr, nullptr), workspace, workspace_bytes, (hipStream_t)stream);    \
+    }
+FORMS(sd_bn_bwd_reduce, float, float)
+FORMS(sd_bn_bwd_reduce_bf16, uint16_t, void)
+#undef FORMS
+
+// apply pass of sd_bn_bwd with the two per-channel means already known (sd_conv2d_dgrad_bn_reduce / sd_bn_bwd_finalize / ..._from_sums)
+#define FORMS(NAME, T, V)                                                                                                                          \
+    int NAME(const V* dy, const V* x, const V* y, int relu, int64_t M, int C, const float* mean, const float* invstd, const float* gamma,          \
+             const float* beta, const float* means, V* dx, V* g_out, sd_stream_t stream) {                                                         \
+        return bn_bwd_apply_any<T>(#NAME, (const T*)dy, (const T*)x, y, relu, M, C, mean, invstd, gamma, beta, means, (T*)dx, (T*)g_out, (hipStream_t)stream); \
+    }
+FORMS(sd_bn_bwd_apply, float, float)
+FORMS(sd_bn_bwd_apply_bf16, uint16_t, void)
+#undef FORMS
 
 int sd_maxpool3x3s2_fwd(const float* x, float* y, uint8_t* idx, int B, int Hi, int Wi, int C, sd_stream_t stream) {
-    SD_REQUIRE(x && y && idx && B > 0 && Hi > 0 && Wi > 0 && C > 0 && C % 4 == 0, SD_ERR_INVALID, "sd_maxpool3x3s2_fwd: bad arguments");
-    const int Ho = (Hi + 2 - 3) / 2 + 1, Wo = (Wi + 2 - 3) / 2 + 1;
-    const int64_t n4 = (int64_t)B * Ho * Wo * C / 4;
-    hipLaunchKernelGGL(k_maxpool_fwd, dim3(cdiv(n4, 256)), dim3(256), 0, (hipStream_t)stream, x, y, idx, B, Hi, Wi, Ho, Wo, C);
-    SD_LAUNCH_CHECK();
-    return 0;
+    if (int e = check_map("sd_maxpool3x3s2_fwd", x && y && idx, B, Hi, Wi, C, 4)) return e;
+    const int Ho = pool_out(Hi), Wo = pool_out(Wi);
+    SD_RETURN_LAUNCH(k_maxpool_fwd, map_launch(B, Ho, Wo, C, 4).grid, 0, (hipStream_t)stream, x, y, idx, B, Hi, Wi, Ho, Wo, C);
+}
+
+int sd_maxpool3x3s2_fwd_bf16(const void* x, void* y, int B, int Hi, int Wi, int C, sd_stream_t stream) {
+    if (int e = check_map("sd_maxpool3x3s2_fwd_bf16", x && y, B, Hi, Wi, C, 8)) return e;
+    const int Ho = pool_out(Hi), Wo = pool_out(Wi);
+    SD_RETURN_LAUNCH(k_maxpool_fwd_bf16, map_launch(B, Ho, Wo, C, 8).grid, 0, (hipStream_t)stream, (const uint16_t*)x, (uint16_t*)y, B, Hi, Wi, Ho, Wo, C);
 }
 
 int sd_maxpool3x3s2_bwd(const float* dy, const uint8_t* idx, float* dx, int B, int Hi, int Wi, int C, sd_stream_t stream) {
-    SD_REQUIRE(dy && dx && idx && B > 0 && Hi > 0 && Wi > 0 && C > 0 && C % 4 == 0, SD_ERR_INVALID, "sd_maxpool3x3s2_bwd: bad arguments");
-    const int Ho = (Hi + 2 - 3) / 2 + 1, Wo = (Wi + 2 - 3) / 2 + 1;
-    const int64_t n4 = (int64_t)B * Hi * Wi * C / 4;
-    hipLaunchKernelGGL(k_maxpool_bwd, dim3(cdiv(n4, 256)), dim3(256), 0, (hipStream_t)stream, dy, idx, dx, B, Hi, Wi, Ho, Wo, C);
-    SD_LAUNCH_CHECK();
-    return 0;
+    if (int e = check_map("sd_maxpool3x3s2_bwd", dy && dx && idx, B, Hi, Wi, C, 4)) return e;
+    SD_RETURN_LAUNCH(k_maxpool_bwd, map_launch(B, Hi, Wi, C, 4).grid, 0, (hipStream_t)stream, dy, idx, dx, B, Hi, Wi, pool_out(Hi), pool_out(Wi), C);
 }
 
-int sd_bn_relu_maxpool_fwd(const float* x, int B, int Hi, int Wi, int C, const float* mean, const float* invstd, const float* gamma,
-                           const float* beta, float* y_pool, uint8_t* idx, sd_stream_t stream) {
-    SD_REQUIRE(x && mean && invstd && gamma && beta && y_pool && idx && B > 0 && Hi > 0 && Wi > 0 && C > 0 && C % 4 == 0, SD_ERR_INVALID,
-               "sd_bn_relu_maxpool_fwd: bad arguments");
-    const int Ho = (Hi + 2 - 3) / 2 + 1, Wo = (Wi + 2 - 3) / 2 + 1;
-    const int64_t n4 = (int64_t)B * Ho * Wo * C / 4;
-    if (g_pool_pair && Wo % 2 == 0 && aligned16(x) && aligned16(y_pool) && (reinterpret_cast<uintptr_t>(idx) & 3u) == 0)
-        hipLaunchKernelGGL((k_bn_relu_maxpool_fwd_pair<float, float, 4>), dim3(cdiv(n4 / 2, 256)), dim3(256), 0, (hipStream_t)stream, x, mean, invstd, gamma, beta,
-                           y_pool, idx, B, Hi, Wi, Ho, Wo, C);
-    else
-    hipLaunchKernelGGL((k_bn_relu_maxpool_fwd<float, float>), dim3(cdiv(n4, 256)), dim3(256), 0, (hipStream_t)stream, x, mean, invstd, gamma, beta, y_pool, idx,
-                       B, Hi, Wi, Ho, Wo, C);
-    SD_LAUNCH_CHECK();
-    return 0;
-}
+#define FORMS(NAME, T, V)                                                                                                                     \
+    int NAME(const V* x, int B, int Hi, int Wi, int C, const float* mean, const float* invstd, const float* gamma, const float* beta, V* y_pool, \
+             uint8_t* idx, sd_stream_t stream) {                                                                                              \
+        return bn_relu_maxpool_fwd_any<T>(#NAME, (const T*)x, B, Hi, Wi, C, mean, invstd, gamma, beta, (T*)y_pool, idx, (hipStream_t)stream); \
+    }
+FORMS(sd_bn_relu_maxpool_fwd, float, float)
+FORMS(sd_bn_relu_maxpool_fwd_bf16, uint16_t, void)
+#undef FORMS
 
-int sd_bn_relu_maxpool_fwd_bf16(const void* x_bf16, int B, int Hi, int Wi, int C, const float* mean, const float* invstd, const float* gamma,
-                                const float* beta, void* y_pool_bf16, uint8_t* idx, sd_stream_t stream) {
-    SD_REQUIRE(x_bf16 && mean && invstd && gamma && beta && y_pool_bf16 && idx && B > 0 && Hi > 0 && Wi > 0 && C > 0 && C % 4 == 0, SD_ERR_INVALID,
-               "sd_bn_relu_maxpool_fwd_bf16: bad arguments");
-    const int Ho = (Hi + 2 - 3) / 2 + 1, Wo = (Wi + 2 - 3) / 2 + 1;
-    const int64_t n4 = (int64_t)B * Ho * Wo * C / 4;
-    if (g_pool_pair && Wo % 2 == 0 && C % 8 == 0 && aligned16(x_bf16) && aligned16(y_pool_bf16) && (reinterpret_cast<uintptr_t>(idx) & 7u) == 0)
-        hipLaunchKernelGGL((k_bn_relu_maxpool_fwd_pair<uint16_t, uint16_t, 8>), dim3(cdiv(n4 / 4, 256)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x_bf16,
-                           mean, invstd, gamma, beta, (uint16_t*)y_pool_bf16, idx, B, Hi, Wi, Ho, Wo, C);
-    else
-    hipLaunchKernelGGL((k_bn_relu_maxpool_fwd<uint16_t, uint16_t>), dim3(cdiv(n4, 256)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x_bf16, mean,
-                       invstd, gamma, beta, (uint16_t*)y_pool_bf16, idx, B, Hi, Wi, Ho, Wo, C);
-    SD_LAUNCH_CHECK();
-    return 0;
-}
+// the stem tail's backward: fp32; bf16 pooled gradient and conv output with an fp32 dx; the same with a bf16 dx (what sd_conv2d_stem_wgrad_bf16
+// reads: under autocast the stem conv's output gradient is bf16).  T / V: the inputs, DT / DV: dx
+#define FORMS(NAME, T, V, DT, DV)                                                                                                                    \
+    int NAME(const V* dpool, const uint8_t* idx, const V* x, int B, int Hi, int Wi, int C, const float* mean, const float* invstd, const float* gamma, \
+             const float* beta, DV* dx, float* dgamma, float* dbeta, int accumulate, void* workspace, size_t workspace_bytes, sd_stream_t stream) {  \
+        return stem_bwd_any<T, DT>(#NAME, (const T*)dpool, idx, (const T*)x, B, Hi, Wi, C, mean, invstd, gamma, beta, (DT*)dx, dgamma, dbeta, accumulate, \
+                                   workspace, workspace_bytes, (hipStream_t)stream);                                                                 \
+    }
+FORMS(sd_maxpool_bn_relu_bwd, float, float, float, float)
+FORMS(sd_maxpool_bn_relu_bwd_bf16, uint16_t, void, float, float)
+FORMS(sd_maxpool_bn_relu_bwd_bf16_dx16, uint16_t, void, uint16_t, void)
+#undef FORMS
 
-extern "C++" {
-// The stem tail's backward (max-pool -> ReLU -> BatchNorm): reduce, finish, apply.  Split forms for synchronized BatchNorm:
-// `sums` -> stop after phase 1 (dgamma / dbeta from the local sums, [S0, S1, n] in fp64); `means` -> the apply pass alone.
-template <typename XT, typename PT>
-static int maxpool_bn_relu_bwd_reduce_any(const char* what, const PT* dpool, const uint8_t* idx, const XT* x, int B, int Hi, int Wi, int C,
-                                          const float* mean, const float* invstd, const float* gamma, const float* beta, float* dgamma,
-                                          float* dbeta, int accumulate, double* sums, void* workspace, size_t workspace_bytes, hipStream_t st) {
-    const int64_t M = (int64_t)B * Hi * Wi;
-    if (int e = check_mc(what, M, C)) return e;
-    SD_REQUIRE(dpool && idx && x && mean && invstd && gamma && beta && dgamma && dbeta && workspace, SD_ERR_INVALID, "%s: null pointer", what);
-    SD_REQUIRE(aligned8(sums), SD_ERR_ALIGN, "%s: the fp64 sums must be 8-byte aligned", what);
-    SD_REQUIRE(workspace_bytes >= sd_col_reduce_workspace_bytes(M, C), SD_ERR_WORKSPACE, "%s: workspace too small", what);
-    const int Ho = (Hi + 2 - 3) / 2 + 1, Wo = (Wi + 2 - 3) / 2 + 1;
-    const int nb = cdiv(M, RED_ROWS_PER_BLOCK);
-    float* partial = (float*)workspace;
-    float* mg = partial + (size_t)nb * 2 * C;
-    float* mgx = mg + C;
-    const bool quad = Hi % 2 == 0 && Wi % 2 == 0;        // even maps: 2x2 quads share their four windows
-    constexpr bool F32 = std::is_same<XT, float>::value && std::is_same<PT, float>::value;
-    SD_REQUIRE(quad || F32, SD_ERR_INVALID, "%s: the bf16 form needs even Hi, Wi", what);
-    if (quad) hipLaunchKernelGGL((k_pool_bn_bwd_reduce_quad<XT, PT>), dim3(nb), dim3(256), 0, st, dpool, idx, x, mean, invstd, gamma, beta, Hi, Wi, Ho, Wo, M / 4, C, partial);
-    else if constexpr (F32) hipLaunchKernelGGL(k_pool_bn_bwd_reduce, dim3(nb), dim3(256), 0, st, dpool, idx, x, mean, invstd, gamma, beta, Hi, Wi, Ho, Wo, M, C, partial);
-    SD_LAUNCH_CHECK();
-    int rows = nb;
-    const float* fin = fold_partials(partial, rows, C, mgx + C, st);
-    bn_bwd_finish(fin, rows, M, C, dgamma, dbeta, accumulate, mg, mgx, sums, st);
-    SD_LAUNCH_CHECK();
-    return 0;
-}
+// synchronized BatchNorm: its reduce half (dgamma / dbeta += local sums; [S0, S1, n] fp64 into `sums`) ...
+#define FORMS(NAME, T, V)                                                                                                                            \
+    int NAME(const V* dpool, const uint8_t* idx, const V* x, int B, int Hi, int Wi, int C, const float* mean, const float* invstd, const float* gamma, \
+             const float* beta, float* dgamma, float* dbeta, int accumulate, double* sums, void* workspace, size_t workspace_bytes, sd_stream_t stream) { \
+        SD_REQUIRE(sums, SD_ERR_INVALID, #NAME ": null pointer");                                                                                    \
+        return stem_bwd_reduce_any<T>(#NAME, false, (const T*)dpool, idx, (const T*)x, B, Hi, Wi, C, mean, invstd, gamma, beta, dgamma, dbeta, accumulate, \
+                                      sums, workspace, workspace_bytes, (hipStream_t)stream);                                                        \
+    }
+FORMS(sd_maxpool_bn_relu_bwd_reduce, float, float)
+FORMS(sd_maxpool_bn_relu_bwd_reduce_bf16, uint16_t, void)
+#undef FORMS
 
-template <typename XT, typename PT, typename DT>
-static int maxpool_bn_relu_bwd_apply_any(const char* what, const PT* dpool, const uint8_t* idx, const XT* x, int B, int Hi, int Wi, int C,
-                                         const float* mean, const float* invstd, const float* gamma, const float* beta, const float* means, DT* dx,
-                                         hipStream_t st) {
-    const int64_t M = (int64_t)B * Hi * Wi;
-    if (int e = check_mc(what, M, C)) return e;
-    SD_REQUIRE(dpool && idx && x && mean && invstd && gamma && beta && means && dx, SD_ERR_INVALID, "%s: null pointer", what);
-    const int Ho = (Hi + 2 - 3) / 2 + 1, Wo = (Wi + 2 - 3) / 2 + 1;
-    const bool quad = Hi % 2 == 0 && Wi % 2 == 0;
-    constexpr bool F32 = std::is_same<XT, float>::value && std::is_same<PT, float>::value && std::is_same<DT, float>::value;
-    SD_REQUIRE(quad || F32, SD_ERR_INVALID, "%s: the bf16 form needs even Hi, Wi", what);
-    const int64_t n4 = M * C / 4;
-    if (quad) hipLaunchKernelGGL((k_pool_bn_bwd_apply_quad<XT, PT, DT>), dim3(cdiv(n4 / 4, 256)), dim3(256), 0, st, dpool, idx, x, mean, invstd, gamma, beta,
-                                 means, means + C, Hi, Wi, Ho, Wo, n4 / 4, C, dx);
-    else if constexpr (F32) hipLaunchKernelGGL(k_pool_bn_bwd_apply, dim3(cdiv(n4, 256)), dim3(256), 0, st, dpool, idx, x, mean, invstd, gamma, beta, means,
-                                               means + C, Hi, Wi, Ho, Wo, n4, C, dx);
-    SD_LAUNCH_CHECK();
-    return 0;
-}
+// ... and the apply pass from the two means of sd_bn_bwd_means_from_sums
+#define FORMS(NAME, T, V, DT, DV)                                                                                                                    \
+    int NAME(const V* dpool, const uint8_t* idx, const V* x, int B, int Hi, int Wi, int C, const float* mean, const float* invstd, const float* gamma, \
+             const float* beta, const float* means, DV* dx, sd_stream_t stream) {                                                                    \
+        return stem_bwd_apply_any<T, DT>(#NAME, (const T*)dpool, idx, (const T*)x, B, Hi, Wi, C, mean, invstd, gamma, beta, means, (DT*)dx, (hipStream_t)stream); \
+    }
+FORMS(sd_maxpool_bn_relu_bwd_apply, float, float, float, float)
+FORMS(sd_maxpool_bn_relu_bwd_apply_bf16, uint16_t, void, float, float)
+FORMS(sd_maxpool_bn_relu_bwd_apply_bf16_dx16, uint16_t, void, uint16_t, void)
+#undef FORMS
 
-template <typename XT, typename PT, typename DT = float>
-static int maxpool_bn_relu_bwd_any(const char* what, const PT* dpool, const uint8_t* idx, const XT* x, int B, int Hi, int Wi, int C, const float* mean,
-                                   const float* invstd, const float* gamma, const float* beta, DT* dx, float* dgamma, float* dbeta, int accumulate,
-                                   void* workspace, size_t workspace_bytes, sd_stream_t stream) {
-    SD_REQUIRE(dx, SD_ERR_INVALID, "%s: null pointer", what);
-    constexpr bool F32 = std::is_same<XT, float>::value && std::is_same<PT, float>::value && std::is_same<DT, float>::value;
-    SD_REQUIRE((Hi % 2 == 0 && Wi % 2 == 0) || F32, SD_ERR_INVALID, "%s: the bf16 form needs even Hi, Wi", what);
-    hipStream_t st = (hipStream_t)stream;
-    if (int e = maxpool_bn_relu_bwd_reduce_any<XT, PT>(what, dpool, idx, x, B, Hi, Wi, C, mean, invstd, gamma, beta, dgamma, dbeta, accumulate, nullptr,
-                                                       workspace, workspace_bytes, st)) return e;
-    const int nb = cdiv((int64_t)B * Hi * Wi, RED_ROWS_PER_BLOCK);
-    const float* mg = (const float*)workspace + (size_t)nb * 2 * C;
-    return maxpool_bn_relu_bwd_apply_any<XT, PT, DT>(what, dpool, idx, x, B, Hi, Wi, C, mean, invstd, gamma, beta, mg, dx, st);
-}
-}  // extern "C++"
-
-int sd_maxpool_bn_relu_bwd(const float* dpool, const uint8_t* idx, const float* x, int B, int Hi, int Wi, int C, const float* mean,
-                           const float* invstd, const float* gamma, const float* beta, float* dx, float* dgamma, float* dbeta, int accumulate,
-                           void* workspace, size_t workspace_bytes, sd_stream_t stream) {
-    return maxpool_bn_relu_bwd_any<float, float>("sd_maxpool_bn_relu_bwd", dpool, idx, x, B, Hi, Wi, C, mean, invstd, gamma, beta, dx, dgamma, dbeta,
-                                                 accumulate, workspace, workspace_bytes, stream);
-}
-
-int sd_maxpool_bn_relu_bwd_bf16(const void* dpool_bf16, const uint8_t* idx, const void* x_bf16, int B, int Hi, int Wi, int C, const float* mean,
-                                const float* invstd, const float* gamma, const float* beta, float* dx, float* dgamma, float* dbeta, int accumulate,
-                                void* workspace, size_t workspace_bytes, sd_stream_t stream) {
-    return maxpool_bn_relu_bwd_any<uint16_t, uint16_t>("sd_maxpool_bn_relu_bwd_bf16", (const uint16_t*)dpool_bf16, idx, (const uint16_t*)x_bf16, B, Hi, Wi, C,
-                                                       mean, invstd, gamma, beta, dx, dgamma, dbeta, accumulate, workspace, workspace_bytes, stream);
-}
-
-// the same with a bf16 input gradient out (what sd_conv2d_stem_wgrad_bf16 reads: under autocast the stem conv's output gradient is bf16)
-int sd_maxpool_bn_relu_bwd_bf16_dx16(const void* dpool_bf16, const uint8_t* idx, const void* x_bf16, int B, int Hi, int Wi, int C, const float* mean,
-                                     const float* invstd, const float* gamma, const float* beta, void* dx_bf16, float* dgamma, float* dbeta, int accumulate,
-                                     void* workspace, size_t workspace_bytes, sd_stream_t stream) {
-    return maxpool_bn_relu_bwd_any<uint16_t, uint16_t, uint16_t>("sd_maxpool_bn_relu_bwd_bf16_dx16", (const uint16_t*)dpool_bf16, idx, (const uint16_t*)x_bf16,
-                                                                 B, Hi, Wi, C, mean, invstd, gamma, beta, (uint16_t*)dx_bf16, dgamma, dbeta, accumulate,
-                                                                 workspace, workspace_bytes, stream);
-}
-
-// synchronized BatchNorm: the reduce half of sd_maxpool_bn_relu_bwd (dgamma / dbeta += local sums; [S0, S1, n] fp64 into `sums`) ...
-int sd_maxpool_bn_relu_bwd_reduce(const float* dpool, const uint8_t* idx, const float* x, int B, int Hi, int Wi, int C, const float* mean,
-                                  const float* invstd, const float* gamma, const float* beta, float* dgamma, float* dbeta, int accumulate, double* sums,
-                                  void* workspace, size_t workspace_bytes, sd_stream_t stream) {
-    SD_REQUIRE(sums, SD_ERR_INVALID, "sd_maxpool_bn_relu_bwd_reduce: null pointer");
-    return maxpool_bn_relu_bwd_reduce_any<float, float>("sd_maxpool_bn_relu_bwd_reduce", dpool, idx, x, B, Hi, Wi, C, mean, invstd, gamma, beta, dgamma,
-                                                        dbeta, accumulate, sums, workspace, workspace_bytes, (hipStream_t)stream);
-}
-
-// ... of its two bf16 forms (bf16 pooled gradient and conv output) ...
-int sd_maxpool_bn_relu_bwd_reduce_bf16(const void* dpool_bf16, const uint8_t* idx, const void* x_bf16, int B, int Hi, int Wi, int C, const float* mean,
-                                       const float* invstd, const float* gamma, const float* beta, float* dgamma, float* dbeta, int accumulate,
-                                       double* sums, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
-    SD_REQUIRE(sums, SD_ERR_INVALID, "sd_maxpool_bn_relu_bwd_reduce_bf16: null pointer");
-    return maxpool_bn_relu_bwd_reduce_any<uint16_t, uint16_t>("sd_maxpool_bn_relu_bwd_reduce_bf16", (const uint16_t*)dpool_bf16, idx, (const uint16_t*)x_bf16,
-                                                              B, Hi, Wi, C, mean, invstd, gamma, beta, dgamma, dbeta, accumulate, sums, workspace,
-                                                              workspace_bytes, (hipStream_t)stream);
-}
-
-// ... and the apply pass from the two means of sd_bn_bwd_means_from_sums: fp32, bf16 in / fp32 dx, bf16 in / bf16 dx
-int sd_maxpool_bn_relu_bwd_apply(const float* dpool, const uint8_t* idx, const float* x, int B, int Hi, int Wi, int C, const float* mean,
-                                 const float* invstd, const float* gamma, const float* beta, const float* means, float* dx, sd_stream_t stream) {
-    return maxpool_bn_relu_bwd_apply_any<float, float, float>("sd_maxpool_bn_relu_bwd_apply", dpool, idx, x, B, Hi, Wi, C, mean, invstd, gamma, beta,
-                                                              means, dx, (hipStream_t)stream);
-}
-
-int sd_maxpool_bn_relu_bwd_apply_bf16(const void* dpool_bf16, const uint8_t* idx, const void* x_bf16, int B, int Hi, int Wi, int C, const float* mean,
-                                      const float* invstd, const float* gamma, const float* beta, const float* means, float* dx, sd_stream_t stream) {
-    return maxpool_bn_relu_bwd_apply_any<uint16_t, uint16_t, float>("sd_maxpool_bn_relu_bwd_apply_bf16", (const uint16_t*)dpool_bf16, idx,
-                                                                    (const uint16_t*)x_bf16, B, Hi, Wi, C, mean, invstd, gamma, beta, means, dx,
-                                                                    (hipStream_t)stream);
-}
-
-int sd_maxpool_bn_relu_bwd_apply_bf16_dx16(const void* dpool_bf16, const uint8_t* idx, const void* x_bf16, int B, int Hi, int Wi, int C,
-                                           const float* mean, const float* invstd, const float* gamma, const float* beta, const float* means,
-                                           void* dx_bf16, sd_stream_t stream) {
-    return maxpool_bn_relu_bwd_apply_any<uint16_t, uint16_t, uint16_t>("sd_maxpool_bn_relu_bwd_apply_bf16_dx16", (const uint16_t*)dpool_bf16, idx,
-                                                                       (const uint16_t*)x_bf16, B, Hi, Wi, C, mean, invstd, gamma, beta, means,
-                                                                       (uint16_t*)dx_bf16, (hipStream_t)stream);
-}
-
-int sd_upsample2x_bwd(const float* dy, const float* add, float* dx, int B, int H, int W, int C, sd_stream_t stream) {
-    SD_REQUIRE(dy && dx && B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, SD_ERR_INVALID, "sd_upsample2x_bwd: bad arguments");
-    const int64_t n4 = (int64_t)B * H * W * C / 4;
-    hipLaunchKernelGGL(k_up2_bwd<float>, dim3(cdiv(n4, 256)), dim3(256), 0, (hipStream_t)stream, dy, add, dx, B, H, W, C);
-    SD_LAUNCH_CHECK();
-    return 0;
-}
+#define FORMS(NAME, T, V)                                                                                                  \
+    int NAME(const V* dy, const V* add, V* dx, int B, int H, int W, int C, sd_stream_t stream) {                          \
+        return upsample2x_bwd_any<T>(#NAME, (const T*)dy, (const T*)add, (T*)dx, B, H, W, C, (hipStream_t)stream);        \
+    }
+FORMS(sd_upsample2x_bwd, float, float)
+FORMS(sd_upsample2x_bwd_bf16, uint16_t, void)
+#undef FORMS
 
 int sd_cast_f32_to_bf16(const float* x, void* y, int64_t n, sd_stream_t stream) {
     SD_REQUIRE(x && y && n > 0 && n % 4 == 0 && aligned16(x), SD_ERR_INVALID, "sd_cast_f32_to_bf16: bad arguments (n %% 4 == 0, 16-byte aligned source)");
-    hipLaunchKernelGGL(k_cast_bf16, dim3(ew_grid(n / 4)), dim3(256), 0, (hipStream_t)stream, x, (uint16_t*)y, n / 4);
-    SD_LAUNCH_CHECK();
-    return 0;
+    SD_RETURN_LAUNCH(k_cast_bf16, ew_launch(n / 4).grid, 0, (hipStream_t)stream, x, (uint16_t*)y, n / 4);
 }
 
 int sd_cast_bf16_to_f32(const void* x, float* y, int64_t n, sd_stream_t stream) {
     SD_REQUIRE(x && y && n > 0 && n % 4 == 0 && aligned16(y) && (reinterpret_cast<uintptr_t>(x) & 7u) == 0, SD_ERR_INVALID,
                "sd_cast_bf16_to_f32: bad arguments (n %% 4 == 0, 8-byte aligned source, 16-byte aligned destination)");
-    hipLaunchKernelGGL(k_cast_f32, dim3(ew_grid(n / 4)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x, y, n / 4);
-    SD_LAUNCH_CHECK();
-    return 0;
-}
-
-// ---- bf16 activations (mixed-precision training): the same kernels with 2-byte loads / stores, all arithmetic in fp32 --------
-int sd_bn_apply_bf16(const void* x, void* y, int64_t M, int C, const float* mean, const float* invstd, const float* gamma, const float* beta,
-                     const void* residual, int relu, uint8_t* relu_mask_out, sd_stream_t stream) {
-    if (int e = check_mc("sd_bn_apply_bf16", M, C)) return e;
-    SD_REQUIRE(x && y && mean && invstd && gamma && beta, SD_ERR_INVALID, "sd_bn_apply_bf16: null pointer");
-    const int64_t n4 = M * C / 4;
-    if (C % 8 == 0 && aligned16(x) && aligned16(y) && aligned16(residual)) {
-        hipLaunchKernelGGL(k_bn_apply_bf16x8, dim3(ew_grid(n4 / 2)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x, (uint16_t*)y, n4 / 2, C, mean,
-                           invstd, gamma, beta, (const uint16_t*)residual, relu, relu_mask_out);
-        SD_LAUNCH_CHECK();
-        return 0;
-    }
-    hipLaunchKernelGGL(k_bn_apply<uint16_t>, dim3(ew_grid(n4)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x, (uint16_t*)y, n4, C, mean,
-                       invstd, gamma, beta, (const uint16_t*)residual, relu, relu_mask_out);
-    SD_LAUNCH_CHECK();
-    return 0;
-}
-
-int sd_bn_bwd_bf16(const void* dy, const void* x, const void* y, int relu, int64_t M, int C, const float* mean, const float* invstd,
-                   const float* gamma, const float* beta, void* dx, void* g_out, float* dgamma, float* dbeta, int accumulate, void* workspace,
-                   size_t workspace_bytes, sd_stream_t stream) {
-    SD_REQUIRE(dx, SD_ERR_INVALID, "sd_bn_bwd_bf16: null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    const bool wide = C % 8 == 0 && relu != 1 && aligned16(dy) && aligned16(x) && aligned16(dx) && aligned16(g_out);
-    if (int e = bn_bwd_reduce_any<uint16_t>("sd_bn_bwd_bf16", (const uint16_t*)dy, (const uint16_t*)x, y, relu, M, C, mean, invstd, gamma, beta,
-                                            dgamma, dbeta, accumulate, nullptr, wide, workspace, workspace_bytes, st)) return e;
-    const int nb = cdiv(M, red_rows(M));
-    const float* mg = (const float*)workspace + (size_t)nb * 2 * C;
-    return bn_bwd_apply_bf16(dy, x, y, relu, M, C, mean, invstd, gamma, beta, mg, dx, g_out, wide, st);
-}
-
-// the reduce half of sd_bn_bwd_bf16 (see sd_bn_bwd_reduce); the x8 kernel is chosen from dy / x alone (sd_bn_bwd_bf16 also asks for
-// 16-byte aligned dx / g_out: buffers from one allocator make the same choice in both forms)
-int sd_bn_bwd_reduce_bf16(const void* dy, const void* x, const void* y, int relu, int64_t M, int C, const float* mean, const float* invstd,
-                          const float* gamma, const float* beta, float* dgamma, float* dbeta, int accumulate, double* sums, void* workspace,
-                          size_t workspace_bytes, sd_stream_t stream) {
-    SD_REQUIRE(sums, SD_ERR_INVALID, "sd_bn_bwd_reduce_bf16: null pointer");
-    const bool wide = C % 8 == 0 && relu != 1 && aligned16(dy) && aligned16(x);
-    return bn_bwd_reduce_any<uint16_t>("sd_bn_bwd_reduce_bf16", (const uint16_t*)dy, (const uint16_t*)x, y, relu, M, C, mean, invstd, gamma, beta,
-                                       dgamma, dbeta, accumulate, sums, wide, workspace, workspace_bytes, (hipStream_t)stream);
-}
-
-// apply pass of sd_bn_bwd_bf16 with the two per-channel means known (sd_bn_bwd_means_from_sums)
-int sd_bn_bwd_apply_bf16(const void* dy, const void* x, const void* y, int relu, int64_t M, int C, const float* mean, const float* invstd,
-                         const float* gamma, const float* beta, const float* means, void* dx, void* g_out, sd_stream_t stream) {
-    if (int e = check_mc("sd_bn_bwd_apply_bf16", M, C)) return e;
-    SD_REQUIRE(relu >= 0 && relu <= 3, SD_ERR_INVALID, "sd_bn_bwd_apply_bf16: relu must be 0 (none), 1 (mask from y), 2 (mask recomputed from x) or 3 (mask bytes)");
-    SD_REQUIRE(dy && x && mean && invstd && gamma && means && dx && ((relu != 1 && relu != 3) || y) && (relu != 2 || beta), SD_ERR_INVALID,
-               "sd_bn_bwd_apply_bf16: null pointer");
-    const bool wide = C % 8 == 0 && relu != 1 && aligned16(dy) && aligned16(x) && aligned16(dx) && aligned16(g_out);
-    return bn_bwd_apply_bf16(dy, x, y, relu, M, C, mean, invstd, gamma, beta, means, dx, g_out, wide, (hipStream_t)stream);
-}
-
-int sd_col_sum_bf16(const void* x, int64_t M, int C, float* out, int accumulate, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
-    if (int e = check_mc("sd_col_sum_bf16", M, C)) return e;
-    SD_REQUIRE(x && out && workspace, SD_ERR_INVALID, "sd_col_sum_bf16: null pointer");
-    SD_REQUIRE(workspace_bytes >= sd_col_reduce_workspace_bytes(M, C), SD_ERR_WORKSPACE, "sd_col_sum_bf16: workspace too small");
-    const int rpb = red_rows(M), nb = cdiv(M, rpb);
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL((k_col_reduce<2, uint16_t>), dim3(nb), dim3(256), 0, st, (const uint16_t*)x, (const uint16_t*)nullptr, (const uint16_t*)nullptr,
-                       (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, 0, M, C, (float*)workspace, rpb);
-    SD_LAUNCH_CHECK();
-    int rows = nb;
-    const float* fin = fold_partials((const float*)workspace, rows, C, (float*)workspace + ((size_t)nb + 1) * 2 * C, st);
-    hipLaunchKernelGGL(k_col_finalize<2>, dim3(cdiv(C, 4)), dim3(256), 0, st, fin, rows, C, (double)M, 0.f, 0.f, out,
-                       (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr, accumulate);
-    SD_LAUNCH_CHECK();
-    return 0;
-}
-
-int sd_upsample2x_bwd_bf16(const void* dy, const void* add, void* dx, int B, int H, int W, int C, sd_stream_t stream) {
-    SD_REQUIRE(dy && dx && B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, SD_ERR_INVALID, "sd_upsample2x_bwd_bf16: bad arguments");
-    const int64_t n4 = (int64_t)B * H * W * C / 4;
-    hipLaunchKernelGGL(k_up2_bwd<uint16_t>, dim3(cdiv(n4, 256)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)dy, (const uint16_t*)add,
-                       (uint16_t*)dx, B, H, W, C);
-    SD_LAUNCH_CHECK();
-    return 0;
-}
-
-int sd_maxpool3x3s2_fwd_bf16(const void* x, void* y, int B, int Hi, int Wi, int C, sd_stream_t stream) {
-    SD_REQUIRE(x && y && B > 0 && Hi > 0 && Wi > 0 && C > 0 && C % 8 == 0, SD_ERR_INVALID, "sd_maxpool3x3s2_fwd_bf16: bad arguments");
-    const int Ho = (Hi + 2 - 3) / 2 + 1, Wo = (Wi + 2 - 3) / 2 + 1;
-    const int64_t n8 = (int64_t)B * Ho * Wo * C / 8;
-    hipLaunchKernelGGL(k_maxpool_fwd_bf16, dim3(cdiv(n8, 256)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x, (uint16_t*)y, B, Hi, Wi, Ho, Wo, C);
-    SD_LAUNCH_CHECK();
-    return 0;
+    SD_RETURN_LAUNCH(k_cast_f32, ew_launch(n / 4).grid, 0, (hipStream_t)stream, (const uint16_t*)x, y, n / 4);
 }
 
 int sd_head_fwd_bf16(const void* x, const float* w, const float* bias, float* y, int B, int HW, int C, int Co, sd_stream_t stream) {
@@ -2238,17 +2228,10 @@ int sd_head_fwd_bf16(const void* x, const float* w, const float* bias, float* y,
     if (Co > HEAD_NARROW_MAX_CO) return head_wide_fwd_bf16(x, w, bias, y, B, HW, C, Co, (hipStream_t)stream);    // sd_head_wide.hip
     SD_REQUIRE(C % 8 == 0 && C <= 512 && Co > 0 && Co <= HEAD_NARROW_MAX_CO, SD_ERR_INVALID, "sd_head_fwd_bf16: needs C %% 8 == 0, C <= 512, Co <= %d", HEAD_NARROW_MAX_CO);
     const int64_t M = (int64_t)B * HW;
-    if (C == 128 && HW % 4 == 0 && aligned16(x) && aligned16(y)) {       // wave-private LDS-DMA + bf16 MFMA pipeline (the default FPN depth)
-        const int ntiles = (int)cdiv(M, 64), blocks = std::max(1, std::min(cdiv(ntiles, 4), 1024));
-        if (Co <= 16) hipLaunchKernelGGL(k_head_fwd_bf16_c128<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x, w, bias, y, M, HW, Co, ntiles);
-        else hipLaunchKernelGGL(k_head_fwd_bf16_c128<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x, w, bias, y, M, HW, Co, ntiles);
-        SD_LAUNCH_CHECK();
-        return 0;
-    }
-    const size_t lds = ((size_t)64 * (C + 4) + (size_t)Co * C) * sizeof(float);
-    hipLaunchKernelGGL(k_head_fwd_bf16, dim3(cdiv(M, 64)), dim3(256), lds, (hipStream_t)stream, (const uint16_t*)x, w, bias, y, M, HW, C, Co);
-    SD_LAUNCH_CHECK();
-    return 0;
+    const HeadLaunch l = plan_head_fwd(true, M, HW, C, Co, x, w, y);
+    if (l.c128 && Co <= 16) SD_RETURN_LAUNCH(k_head_fwd_bf16_c128<false>, l.grid, 0, (hipStream_t)stream, (const uint16_t*)x, w, bias, y, M, HW, Co, l.rows);
+    if (l.c128) SD_RETURN_LAUNCH(k_head_fwd_bf16_c128<true>, l.grid, 0, (hipStream_t)stream, (const uint16_t*)x, w, bias, y, M, HW, Co, l.rows);
+    SD_RETURN_LAUNCH(k_head_fwd_bf16, l.grid, l.lds, (hipStream_t)stream, (const uint16_t*)x, w, bias, y, M, HW, C, Co);
 }
 
 int sd_head_fwd(const float* x, const float* w, const float* bias, float* y, int B, int HW, int C, int Co, sd_stream_t stream) {
@@ -2256,70 +2239,52 @@ int sd_head_fwd(const float* x, const float* w, const float* bias, float* y, int
     if (Co > HEAD_NARROW_MAX_CO) return head_wide_fwd(x, w, bias, y, B, HW, C, Co, (hipStream_t)stream);              // sd_head_wide.hip
     SD_REQUIRE(C % 4 == 0 && C <= 512 && Co > 0 && Co <= HEAD_NARROW_MAX_CO, SD_ERR_INVALID, "sd_head_fwd: needs C %% 4 == 0, C <= 512, Co <= %d", HEAD_NARROW_MAX_CO);
     const int64_t M = (int64_t)B * HW;
-    if (C == 128 && Co <= 16 && HW % 16 == 0 && M < (1ll << 31) && aligned16(x) && aligned16(w) && aligned16(y)) {
-        const int ntiles = (int)(M / 16);
-        const size_t lds_b = (size_t)4 * HF_NST * 2048 * sizeof(float);
-        static const hipError_t attr_once = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_head_fwd_f32_c128), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b);
-        SD_HIP(attr_once);
-        hipLaunchKernelGGL(k_head_fwd_f32_c128, dim3(std::min(cdiv(ntiles, 4), 256)), dim3(256), lds_b, (hipStream_t)stream, x, w, bias, y, HW, Co, ntiles);
-        SD_LAUNCH_CHECK();
-        return 0;
+    const HeadLaunch l = plan_head_fwd(false, M, HW, C, Co, x, w, y);
+    if (l.c128) {
+        SD_RAISE_LDS_ONCE(k_head_fwd_f32_c128, l.lds);
+        SD_RETURN_LAUNCH(k_head_fwd_f32_c128, l.grid, l.lds, (hipStream_t)stream, x, w, bias, y, HW, Co, l.rows);
     }
-    const size_t lds = ((size_t)64 * (C + 4) + (size_t)Co * C) * sizeof(float);
-    hipLaunchKernelGGL(k_head_fwd, dim3(cdiv(M, 64)), dim3(256), lds, (hipStream_t)stream, x, w, bias, y, M, HW, C, Co);
-    SD_LAUNCH_CHECK();
-    return 0;
+    SD_RETURN_LAUNCH(k_head_fwd, l.grid, l.lds, (hipStream_t)stream, x, w, bias, y, M, HW, C, Co);
 }
 
-// partial rows of the head weight gradient: one per block of k_head_wgrad (1024 pixels), or one per WAVE of k_head_wgrad_f32_c128
-// (up to 1024 waves = one block of four waves per CU, each wave on tiles of 16 pixels)
-static int head_wgrad_wave_rows(int64_t M) { return (int)std::min<int64_t>(1024, (cdiv(M, 16) + 3) / 4 * 4); }
+// the narrow head sizes for the larger of its two weight-gradient kernels: the pointers that choose between them are not known here
 size_t sd_head_bwd_workspace_bytes(int B, int HW, int C, int Co) {
     const int64_t M = (int64_t)B * HW;
     if (Co > HEAD_NARROW_MAX_CO) return head_wide_bwd_workspace_bytes(M, C, Co);
-    return align_up((size_t)std::max<int64_t>(cdiv(M, HEAD_WG_PIX), head_wgrad_wave_rows(M)) * (Co * C + Co) * sizeof(float), 256);
+    return align_up((size_t)std::max(plan_head_wgrad(false, M).rows, plan_head_wgrad(true, M).rows) * (Co * C + Co) * sizeof(float), 256);
 }
 
 int sd_head_bwd(const float* dy, const float* x, const float* w, float* dx, float* dw, float* dbias, int B, int HW, int C, int Co,
                 int accumulate, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
     SD_REQUIRE(dy && x && w && dx && dw && dbias && workspace && B > 0 && HW > 0, SD_ERR_INVALID, "sd_head_bwd: bad arguments");
+    const int64_t M = (int64_t)B * HW;
+    hipStream_t st = (hipStream_t)stream;
     if (Co > HEAD_NARROW_MAX_CO) {                                             // GEMM kernels of sd_head_wide.hip
-        const int64_t P = (int64_t)B * HW;
-        if (int e = head_wide_check("sd_head_bwd", P, C, Co)) return e;
+        if (int e = head_wide_check("sd_head_bwd", M, C, Co)) return e;
         SD_REQUIRE(workspace_bytes >= sd_head_bwd_workspace_bytes(B, HW, C, Co), SD_ERR_WORKSPACE, "sd_head_bwd: workspace too small");
-        hipStream_t st = (hipStream_t)stream;
         int rows = 0;
         if (int e = head_wide_wgrad(dy, x, (float*)workspace, B, HW, C, Co, st, rows)) return e;
-        const int n = Co * C + Co;
-        hipLaunchKernelGGL(k_head_wgrad_fin, dim3(cdiv(n, 8)), dim3(256), 0, st, (const float*)workspace, rows, n, dw, dbias, Co * C, accumulate);
+        head_wgrad_fin((const float*)workspace, rows, C, Co, dw, dbias, accumulate, st);
         SD_LAUNCH_CHECK();
         return head_wide_dgrad(dy, w, dx, B, HW, C, Co, st);
     }
     SD_REQUIRE(C % 4 == 0 && C <= 256 && (256 % C == 0) && (64 % (256 / C) == 0) && ((64 / (256 / C)) % 8 == 0) && Co > 0 && Co <= HEAD_NARROW_MAX_CO,
                SD_ERR_INVALID, "sd_head_bwd: needs C in {64, 128, 256} and Co <= %d", HEAD_NARROW_MAX_CO);
     SD_REQUIRE(workspace_bytes >= sd_head_bwd_workspace_bytes(B, HW, C, Co), SD_ERR_WORKSPACE, "sd_head_bwd: workspace too small");
-    const int64_t M = (int64_t)B * HW;
-    hipStream_t st = (hipStream_t)stream;
     // weight gradient first: it streams x while HBM is quiet; behind the data-gradient it shared the memory system with the write-back
     // of that kernel's 537 MB (144 us instead of ~105)
-    int nb = cdiv(M, HEAD_WG_PIX);
-    if (C == 128 && Co <= 16 && HW % 16 == 0 && M < (1ll << 31) && aligned16(x) && aligned16(dy)) {
-        nb = head_wgrad_wave_rows(M);                                          // one partial row per wave
-        const int blocks = nb / 4;
-        const size_t lds_b = (size_t)4 * HF_NST * HWG_STAGE * sizeof(float);
-        static const hipError_t attr_once = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_head_wgrad_f32_c128), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b);
-        SD_HIP(attr_once);
-        hipLaunchKernelGGL(k_head_wgrad_f32_c128, dim3(blocks), dim3(256), lds_b, st, dy, x, (float*)workspace, HW, Co, (int)(M / 16));
+    const HeadLaunch l = plan_head_wgrad(head_wgrad_f32_c128(M, HW, C, Co, x, dy), M);
+    if (l.c128) {
+        SD_RAISE_LDS_ONCE(k_head_wgrad_f32_c128, l.lds);
+        hipLaunchKernelGGL(k_head_wgrad_f32_c128, dim3(l.grid), dim3(256), l.lds, st, dy, x, (float*)workspace, HW, Co, (int)(M / 16));
     } else {
-        hipLaunchKernelGGL(k_head_wgrad, dim3(nb), dim3(256), 0, st, dy, x, (float*)workspace, M, HW, C, Co);
+        hipLaunchKernelGGL(k_head_wgrad, dim3(l.grid), dim3(256), 0, st, dy, x, (float*)workspace, M, HW, C, Co);
     }
     SD_LAUNCH_CHECK();
-    const int n = Co * C + Co;
-    hipLaunchKernelGGL(k_head_wgrad_fin, dim3(cdiv(n, 8)), dim3(256), 0, st, (const float*)workspace, nb, n, dw, dbias, Co * C, accumulate);
+    head_wgrad_fin((const float*)workspace, l.rows, C, Co, dw, dbias, accumulate, st);
     SD_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_head_dgrad<float>, dim3(cdiv(M, 64)), dim3(256), (size_t)Co * C * sizeof(float), st, dy, w, dx, M, HW, C, Co);
-    SD_LAUNCH_CHECK();
-    return 0;
+    const Launch dg = head_dgrad_launch(M, C, Co);
+    SD_RETURN_LAUNCH(k_head_dgrad<float>, dg.grid, dg.lds, st, dy, w, dx, M, HW, C, Co);
 }
 
 int sd_head_bwd_bf16(const float* dy, const void* x_bf16, const float* w, void* dx_bf16, float* dw, float* dbias, int B, int HW, int C, int Co,
@@ -2330,13 +2295,13 @@ int sd_head_bwd_bf16(const float* dy, const void* x_bf16, const float* w, void* 
     SD_REQUIRE(workspace_bytes >= sd_head_bwd_workspace_bytes(B, HW, C, Co), SD_ERR_WORKSPACE, "sd_head_bwd_bf16: workspace too small");
     const int64_t M = (int64_t)B * HW;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_head_dgrad<uint16_t>, dim3(cdiv(M, 64)), dim3(256), (size_t)Co * C * sizeof(float), st, dy, w, (uint16_t*)dx_bf16, M, HW, C, Co);
+    const Launch dg = head_dgrad_launch(M, C, Co);
+    hipLaunchKernelGGL(k_head_dgrad<uint16_t>, dim3(dg.grid), dim3(256), dg.lds, st, dy, w, (uint16_t*)dx_bf16, M, HW, C, Co);
     SD_LAUNCH_CHECK();
-    const int nb = cdiv(M, HEAD_WG_PIX);
-    hipLaunchKernelGGL(k_head_wgrad_bf16<8>, dim3(nb), dim3(256), 0, st, dy, (const uint16_t*)x_bf16, (float*)workspace, M, HW, C, Co);
+    const HeadLaunch l = plan_head_wgrad(false, M);
+    hipLaunchKernelGGL(k_head_wgrad_bf16<8>, dim3(l.grid), dim3(256), 0, st, dy, (const uint16_t*)x_bf16, (float*)workspace, M, HW, C, Co);
     SD_LAUNCH_CHECK();
-    const int n = Co * C + Co;
-    hipLaunchKernelGGL(k_head_wgrad_fin, dim3(cdiv(n, 8)), dim3(256), 0, st, (const float*)workspace, nb, n, dw, dbias, Co * C, accumulate);
+    head_wgrad_fin((const float*)workspace, l.rows, C, Co, dw, dbias, accumulate, st);
     SD_LAUNCH_CHECK();
     return 0;
 }
@@ -2345,14 +2310,9 @@ int sd_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg
                  float eps, float grad_scale, sd_stream_t stream) {
     SD_REQUIRE(param && grad && exp_avg && exp_avg_sq && n > 0 && n % 4 == 0 && step >= 1, SD_ERR_INVALID, "sd_adam_step: bad arguments (n %% 4 == 0, step >= 1)");
     SD_REQUIRE(aligned16(param) && aligned16(grad) && aligned16(exp_avg) && aligned16(exp_avg_sq), SD_ERR_ALIGN, "sd_adam_step: pointers must be 16-byte aligned");
-    const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-    hipLaunchKernelGGL(k_adam, dim3(ew_grid(n / 4)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n / 4, lr, beta1, beta2, eps,
-                       (float)bc1, (float)sqrt(bc2), grad_scale);
-    SD_LAUNCH_CHECK();
-    return 0;
+    return adam_launch(param, grad, exp_avg, exp_avg_sq, n / 4, lr, beta1, beta2, eps, 1.0 - pow((double)beta1, step), 1.0 - pow((double)beta2, step),
+                       grad_scale, (hipStream_t)stream);
 }
-
-static inline int sumsq_blocks(int64_t n) { return n > 0 ? (int)std::min<int64_t>(cdiv(n / 4, 256), SUMSQ_MAX_BLOCKS) : 0; }
 
 size_t sd_grad_sumsq_workspace_bytes(int64_t n) { return (size_t)sumsq_blocks(n) * sizeof(double); }
 
@@ -2361,9 +2321,7 @@ int sd_grad_sumsq(const float* grad, int64_t n, void* workspace, size_t workspac
     SD_REQUIRE(aligned16(grad) && (reinterpret_cast<uintptr_t>(workspace) & 7u) == 0, SD_ERR_ALIGN,
                "sd_grad_sumsq: grad must be 16-byte aligned, the workspace 8-byte aligned");
     SD_REQUIRE(workspace_bytes >= sd_grad_sumsq_workspace_bytes(n), SD_ERR_WORKSPACE, "sd_grad_sumsq: workspace too small");
-    hipLaunchKernelGGL(k_grad_sumsq, dim3(sumsq_blocks(n)), dim3(256), 0, (hipStream_t)stream, grad, n / 4, (double*)workspace);
-    SD_LAUNCH_CHECK();
-    return 0;
+    SD_RETURN_LAUNCH(k_grad_sumsq, sumsq_blocks(n), 0, (hipStream_t)stream, grad, n / 4, (double*)workspace);
 }
 
 int sd_optim_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, int step, float lr, float beta1, float beta2,
@@ -2386,23 +2344,162 @@ int sd_optim_step(float* param, const float* grad, float* exp_avg, float* exp_av
     }
     const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
     const int64_t n4 = n / 4;
-    hipStream_t st = (hipStream_t)stream;
-    if (!decay && !clip && !avg) {                                             // every option off: sd_adam_step's own launch
-        hipLaunchKernelGGL(k_adam, dim3(ew_grid(n4)), dim3(256), 0, st, param, grad, exp_avg, exp_avg_sq, n4, lr, beta1, beta2, eps, (float)bc1,
-                           (float)sqrt(bc2), grad_scale);
-        SD_LAUNCH_CHECK();
-        return 0;
-    }
+    if (!decay && !clip && !avg)                                               // every option off: sd_adam_step's own launch
+        return adam_launch(param, grad, exp_avg, exp_avg_sq, n4, lr, beta1, beta2, eps, bc1, bc2, grad_scale, (hipStream_t)stream);
     using kernel_t = decltype(&k_optim<true, true, true>);
     static const kernel_t variants[8] = {nullptr,                      k_optim<true, false, false>, k_optim<false, true, false>,
                                          k_optim<true, true, false>,   k_optim<false, false, true>, k_optim<true, false, true>,
                                          k_optim<false, true, true>,   k_optim<true, true, true>};
     const float decay_mul = (float)(1.0 - (double)lr * (double)weight_decay);
-    hipLaunchKernelGGL(variants[(int)decay | (int)clip << 1 | (int)avg << 2], dim3(ew_grid(n4)), dim3(256), 0, st, param, grad, exp_avg, exp_avg_sq, n4,
-                       lr, beta1, beta2, eps, (float)bc1, (float)sqrt(bc2), grad_scale, decay_mul, decay_mask, max_norm, (const double*)partials,
-                       npartials, ema, ema_decay, (uint32_t*)status);
-    SD_LAUNCH_CHECK();
+    SD_RETURN_LAUNCH(variants[(int)decay | (int)clip << 1 | (int)avg << 2], ew_launch(n4).grid, 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n4, lr, beta1,
+                  beta2, eps, (float)bc1, (float)sqrt(bc2), grad_scale, decay_mul, decay_mask, max_norm, (const double*)partials, npartials, ema, ema_decay,
+                  (uint32_t*)status);
+}
+
+// ---- sd_nn_kernel_names: the plans above, printed (host only; the one place of this layer that formats) -------------------------------------
+namespace {
+struct Names {
+    char* buf; size_t cap, at;
+    void put(const char* fmt, ...) __attribute__((format(printf, 2, 3))) {
+        va_list ap;
+        va_start(ap, fmt);
+        if (at < cap) at += vsnprintf(buf + at, cap - at, fmt, ap);
+        va_end(ap);
+    }
+    void add(const char* name, int64_t grid, size_t lds = 0) { put("%s%s grid=%lld block=256 lds=%zu", at ? "; " : "", name, (long long)grid, lds); }
+    void add(const char* name, const Launch& l) { add(name, l.grid, l.lds); }
+    void reduce(const char* kernel, int nb, const FoldPlan& f, int mode, bool sums, int C) {      // the launches of every reducing op
+        char fin[32];
+        snprintf(fin, sizeof(fin), sums ? "k_col_sums<%d>" : "k_col_finalize<%d>", mode);
+        if (kernel) add(kernel, nb);
+        if (f.slab) add("k_rows_fold", f.rows);
+        add(fin, chan_launch(C, 4));
+    }
+    void plan(const ColReducePlan& p) {
+        put(" | rpb=%d nb=%d slab=%d rows=%d partial_at=%zu means_at=%zu fold_at=%zu ws_bytes=%zu", p.rpb, p.nb, p.fold.slab, p.fold.rows, p.partial_at,
+            p.means_at, p.fold_at, p.ws_bytes);
+    }
+};
+}  // namespace
+
+// the shapes the entry points refuse, by their checkers
+static int check_desc(const char* what, const sd_nn_call_desc& d, int64_t M) {
+    switch (d.op) {
+    case SD_NN_BN_STATS_FROM_SUMS: case SD_NN_BN_BWD_MEANS_FROM_SUMS: return check_mc(what, 1, d.C);
+    case SD_NN_BN_TRAIN_STATS: case SD_NN_BN_FINALIZE_STATS: case SD_NN_BN_APPLY: case SD_NN_BN_BWD_FINALIZE: case SD_NN_COL_SUM: return check_mc(what, M, d.C);
+    case SD_NN_BN_BWD: case SD_NN_BN_BWD_REDUCE: case SD_NN_BN_BWD_APPLY:
+        if (int e = check_mc(what, M, d.C)) return e;
+        return check_relu(what, d.relu, what, what);
+    case SD_NN_MAXPOOL_FWD: case SD_NN_MAXPOOL_BWD: case SD_NN_BN_RELU_MAXPOOL_FWD: case SD_NN_UPSAMPLE_BWD:
+        return check_map(what, true, d.B, d.H, d.W, d.C, d.op == SD_NN_MAXPOOL_FWD && d.form ? 8 : 4);
+    case SD_NN_STEM_BWD: case SD_NN_STEM_BWD_REDUCE: case SD_NN_STEM_BWD_APPLY:
+        if (int e = check_stem_quad(what, stem_bwd_quad(d.H, d.W), !d.form)) return e;
+        return check_mc(what, M, d.C);
+    case SD_NN_CAST: case SD_NN_ADAM: case SD_NN_GRAD_SUMSQ: case SD_NN_OPTIM:
+        SD_REQUIRE(M > 0 && M % 4 == 0, SD_ERR_INVALID, "%s: needs n > 0 and n %% 4 == 0 (got %lld)", what, (long long)M);
+        return 0;
+    case SD_NN_BN_FOLD: case SD_NN_HEAD_FWD: case SD_NN_HEAD_BWD: return 0;
+    }
+    SD_REQUIRE(false, SD_ERR_INVALID, "%s: unknown op %d", what, d.op);
     return 0;
+}
+
+const char* sd_nn_kernel_names(const sd_nn_call_desc* d) {
+    static thread_local char line[1024];
+    static const sd_nn_call_desc none = {-1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    if (!d) d = &none;
+    Names out{line, sizeof(line), 0};
+    line[0] = 0;
+    char name[128];
+#define NAME(...) (snprintf(name, sizeof(name), __VA_ARGS__), name)
+    // a stand-in for pointer k of the op's kernel choice: only its alignment is ever looked at
+    const auto ptr = [&](int k) { return reinterpret_cast<const void*>((uintptr_t)((d->flags >> k & 1u) ? 0x1000 : 0x1001)); };
+    const int op = d->op, C = d->C, Co = d->Co, Ho = pool_out(d->H), Wo = pool_out(d->W);
+    const bool bf = d->form != 0, sums = (d->flags & SD_NN_SUMS) != 0, map_op = op >= SD_NN_MAXPOOL_FWD && op <= SD_NN_UPSAMPLE_BWD;
+    const bool head = op == SD_NN_HEAD_FWD || op == SD_NN_HEAD_BWD, wide_head = head && Co > HEAD_NARROW_MAX_CO;
+    const char *T = bf ? "unsigned short" : "float", *DT = d->form == 2 ? "unsigned short" : "float";
+    const int64_t M = map_op ? (int64_t)d->B * d->H * d->W : head ? (int64_t)d->B * d->H : d->M;
+    const bool quad = stem_bwd_quad(d->H, d->W), stem = op >= SD_NN_STEM_BWD && op <= SD_NN_STEM_BWD_APPLY;
+    if (check_desc("sd_nn_kernel_names", *d, M)) {
+        snprintf(line, sizeof(line), "refused: %s", sd_last_error());
+        return line;
+    }
+    const ColReducePlan p = plan_col_reduce(M, C, stem ? ROWS_STEM_TAIL : ROWS_BN);
+    switch (op) {
+    case SD_NN_BN_TRAIN_STATS: case SD_NN_COL_SUM:
+        out.reduce(NAME("k_col_reduce<%d, %s>", op == SD_NN_COL_SUM ? 2 : 0, T), p.nb, p.fold, op == SD_NN_COL_SUM ? 2 : 0, sums, C);
+        out.plan(p);
+        break;
+    case SD_NN_BN_FINALIZE_STATS: case SD_NN_BN_BWD_FINALIZE: {
+        const FoldPlan f = plan_fold(d->rows, C, (d->flags & SD_NN_SCRATCH) != 0);
+        out.reduce(nullptr, 0, f, op == SD_NN_BN_BWD_FINALIZE, sums, C);
+        out.put(" | slab=%d rows=%d", f.slab, f.rows);
+        break;
+    }
+    case SD_NN_BN_STATS_FROM_SUMS: out.add("k_bn_stats_from_sums", chan_launch(C, 256)); break;
+    case SD_NN_BN_BWD_MEANS_FROM_SUMS: out.add("k_bn_bwd_means_from_sums", chan_launch(C, 256)); break;
+    case SD_NN_BN_FOLD: out.add("k_bn_fold", chan_launch(C, 256)); break;
+    case SD_NN_BN_APPLY:
+    {
+        const bool wide = bf && bn_apply_wide(C, ptr(0), ptr(1), ptr(2));
+        out.add(wide ? "k_bn_apply_bf16x8" : NAME("k_bn_apply<%s>", T), bn_ew_launch(wide, M, C));
+        break;
+    }
+    case SD_NN_BN_BWD: case SD_NN_BN_BWD_REDUCE: case SD_NN_BN_BWD_APPLY: {
+        const bool reduce_only = op == SD_NN_BN_BWD_REDUCE;
+        const bool wide = bf && bn_bwd_wide(C, d->relu, ptr(0), ptr(1), reduce_only ? nullptr : ptr(2), reduce_only ? nullptr : ptr(3));
+        if (op != SD_NN_BN_BWD_APPLY) out.reduce(wide ? "k_col_reduce_bwd_bf16x8" : NAME("k_col_reduce<1, %s>", T), p.nb, p.fold, 1, sums, C);
+        if (!reduce_only) out.add(wide ? "k_bn_bwd_apply_bf16x8" : NAME("k_bn_bwd_apply<%s>", T), bn_ew_launch(wide, M, C));
+        if (op != SD_NN_BN_BWD_APPLY) out.plan(p);
+        break;
+    }
+    case SD_NN_MAXPOOL_FWD: out.add(bf ? "k_maxpool_fwd_bf16" : "k_maxpool_fwd", map_launch(d->B, Ho, Wo, C, bf ? 8 : 4)); break;
+    case SD_NN_MAXPOOL_BWD: out.add("k_maxpool_bwd", map_launch(d->B, d->H, d->W, C, 4)); break;
+    case SD_NN_BN_RELU_MAXPOOL_FWD: {
+        const int elems = bf ? 8 : 4;
+        const bool pair = pool_fwd_pair(d->pool_fwd_pair, elems, Wo, C, ptr(0), ptr(1), ptr(2));
+        out.add(pair ? NAME("k_bn_relu_maxpool_fwd_pair<%s, %s, %d>", T, T, elems) : NAME("k_bn_relu_maxpool_fwd<%s, %s>", T, T), pool_fwd_launch(pair, elems, d->B, Ho, Wo, C));
+        break;
+    }
+    case SD_NN_STEM_BWD: case SD_NN_STEM_BWD_REDUCE: case SD_NN_STEM_BWD_APPLY:
+        if (op != SD_NN_STEM_BWD_APPLY) out.reduce(quad ? NAME("k_pool_bn_bwd_reduce_quad<%s, %s>", T, T) : "k_pool_bn_bwd_reduce", p.nb, p.fold, 1, sums, C);
+        if (op != SD_NN_STEM_BWD_REDUCE) out.add(quad ? NAME("k_pool_bn_bwd_apply_quad<%s, %s, %s>", T, T, DT) : "k_pool_bn_bwd_apply", stem_apply_launch(quad, d->B, d->H, d->W, C));
+        if (op != SD_NN_STEM_BWD_APPLY) out.plan(p);
+        break;
+    case SD_NN_UPSAMPLE_BWD: out.add(NAME("k_up2_bwd<%s>", T), map_launch(d->B, d->H, d->W, C, 4)); break;
+    case SD_NN_CAST: out.add(bf ? "k_cast_f32" : "k_cast_bf16", ew_launch(M / 4)); break;
+    case SD_NN_HEAD_FWD: {
+        const HeadLaunch l = plan_head_fwd(bf, M, d->H, C, Co, ptr(0), ptr(1), ptr(2));
+        if (wide_head) out.put(bf ? "head_wide_fwd_bf16" : "head_wide_fwd");
+        else if (bf) out.add(l.c128 ? (Co <= 16 ? "k_head_fwd_bf16_c128<false>" : "k_head_fwd_bf16_c128<true>") : "k_head_fwd_bf16", l.grid, l.lds);
+        else out.add(l.c128 ? "k_head_fwd_f32_c128" : "k_head_fwd", l.grid, l.lds);
+        break;
+    }
+    case SD_NN_HEAD_BWD: {
+        const HeadLaunch l = plan_head_wgrad(!bf && head_wgrad_f32_c128(M, d->H, C, Co, ptr(0), ptr(1)), M);
+        if (wide_head) out.put("head_wide_wgrad");
+        else if (bf) { out.add("k_head_dgrad<unsigned short>", head_dgrad_launch(M, C, Co)); out.add("k_head_wgrad_bf16<8>", l.grid); }
+        else out.add(l.c128 ? "k_head_wgrad_f32_c128" : "k_head_wgrad", l.grid, l.lds);
+        out.add("k_head_wgrad_fin", head_fin_grid(C, Co));
+        if (wide_head) out.put("; head_wide_dgrad");
+        else if (!bf) out.add("k_head_dgrad<float>", head_dgrad_launch(M, C, Co));
+        out.put(" | ws_bytes=%zu", sd_head_bwd_workspace_bytes(d->B, d->H, C, Co));
+        break;
+    }
+    case SD_NN_ADAM: out.add("k_adam", ew_launch(M / 4)); break;
+    case SD_NN_GRAD_SUMSQ:
+        out.add("k_grad_sumsq", sumsq_blocks(M));
+        out.put(" | ws_bytes=%zu", sd_grad_sumsq_workspace_bytes(M));
+        break;
+    case SD_NN_OPTIM: {
+        const bool decay = d->flags & SD_NN_DECAY, clip = d->flags & SD_NN_CLIP, avg = d->flags & SD_NN_EMA;
+        static const char* const tf[2] = {"false", "true"};
+        out.add(decay || clip || avg ? NAME("k_optim<%s, %s, %s>", tf[decay], tf[clip], tf[avg]) : "k_adam", ew_launch(M / 4));
+        break;
+    }
+    }
+#undef NAME
+    return line;
 }
 
 }  // extern "C"
