@@ -1004,7 +1004,11 @@ int sd_optim_step(float* param, const float* grad, float* exp_avg, float* exp_av
 enum { SD_NN_BN_TRAIN_STATS, SD_NN_BN_FINALIZE_STATS, SD_NN_BN_STATS_FROM_SUMS, SD_NN_BN_APPLY, SD_NN_BN_FOLD, SD_NN_BN_BWD, SD_NN_BN_BWD_REDUCE,
        SD_NN_BN_BWD_FINALIZE, SD_NN_BN_BWD_MEANS_FROM_SUMS, SD_NN_BN_BWD_APPLY, SD_NN_COL_SUM, SD_NN_MAXPOOL_FWD, SD_NN_MAXPOOL_BWD,
        SD_NN_BN_RELU_MAXPOOL_FWD, SD_NN_STEM_BWD, SD_NN_STEM_BWD_REDUCE, SD_NN_STEM_BWD_APPLY, SD_NN_UPSAMPLE_BWD, SD_NN_CAST, SD_NN_HEAD_FWD,
-       SD_NN_HEAD_BWD, SD_NN_ADAM, SD_NN_GRAD_SUMSQ, SD_NN_OPTIM };
+       SD_NN_HEAD_BWD, SD_NN_ADAM, SD_NN_GRAD_SUMSQ, SD_NN_OPTIM,
+       /* ops 0 .. 23 are the ones of the recorded call trace (tests/golden/nn_call_trace.json), and 24, the first id behind them, is the
+        * one tests/test_nn_plan_cpu.py asks about as an unknown op: it stays unused, ops added since follow from 25.  bn_frozen_bwd (sd_frozen_bn_bwd[_bf16]): M, C, form; flag bits: dy, y, dx, g_out
+        * (a pointer the call leaves NULL counts as aligned) */
+       SD_NN_BN_FROZEN_BWD = 25 };
 #define SD_NN_SCRATCH (1u << 8)
 #define SD_NN_SUMS (1u << 9)
 #define SD_NN_DECAY (1u << 10)
@@ -1113,6 +1117,18 @@ int sd_maxpool_bn_relu_bwd_apply_bf16(const void* dpool_bf16, const uint8_t* idx
 int sd_maxpool_bn_relu_bwd_apply_bf16_dx16(const void* dpool_bf16, const uint8_t* idx, const void* x_bf16, int B, int Hi, int Wi, int C,
                                            const float* mean, const float* invstd, const float* gamma, const float* beta, const float* means,
                                            void* dx_bf16, sd_stream_t stream);
+
+/* ---- frozen BatchNorm, backward (fine-tuning: `Network.freeze`) ----------------------------------------------------
+ * A BatchNorm that normalises with its stored statistics is the per-channel affine y = x * scale[c] + shift[c] (sd_bn_fold), so its
+ * backward has no reduction:  g = (y == NULL || y[i] > 0) ? dy[i] : +0;  g_out[i] = g;  dx[i] = g * scale[i % C]  (one fp32 multiply;
+ * the bf16 form: g_out = dy's bits or +0, dx = round-to-nearest-even(float(g) * scale[c])).  y: the layer's ReLU output or NULL (no ReLU);
+ * g_out: NULL or the masked gradient (what the skip path of a residual block takes).  A pure function of its inputs: one launch, no
+ * workspace, no atomics, grid-stride over any M.  C as the BatchNorm family (C % 4 == 0 ...), M >= 1; dx and g_out must not alias
+ * dy, y or each other (SD_ERR_INVALID).  16-byte loads and stores where every pointer given is 16-byte aligned (the bf16 form: and
+ * C % 8 == 0), element-wise ones otherwise.  Named sd_frozen_bn_* (not sd_bn_frozen_*): the sd_bn_* names are the entry points of the
+ * recorded call trace (tests/golden/nn_call_trace.json), which this one came after. */
+int sd_frozen_bn_bwd(const float* dy, const float* y, const float* scale, int64_t M, int C, float* dx, float* g_out, sd_stream_t stream);
+int sd_frozen_bn_bwd_bf16(const void* dy, const void* y, const float* scale, int64_t M, int C, void* dx, void* g_out, sd_stream_t stream);
 
 /* ---- profiler ranges (no reference counterpart: SURVEY.md section 5 lists tracing as absent from the reference) ----
  * roctx ranges on the calling thread, for `rocprofv3 --marker-trace`.  Active only when the environment holds SDNET_ROCTX=1 at the

@@ -298,6 +298,9 @@ _SIGNATURES = {
     "sd_maxpool_bn_relu_bwd_apply": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int] + [c_vp] * 7),
     "sd_maxpool_bn_relu_bwd_apply_bf16": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int] + [c_vp] * 7),
     "sd_maxpool_bn_relu_bwd_apply_bf16_dx16": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int] + [c_vp] * 7),
+    # frozen BatchNorm, backward: dy, y (or null), scale, M, C, dx, g_out (or null), stream
+    "sd_frozen_bn_bwd": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp]),
+    "sd_frozen_bn_bwd_bf16": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp]),
     "sd_allreduce_unique_id": (c_int, [c_vp]),
     "sd_allreduce_init": (c_int, [c_vp, c_int, c_int, C.POINTER(c_vp)]),
     "sd_allreduce_run": (c_int, [c_vp, c_vp, c_i64, c_vp]),

@@ -1626,6 +1626,79 @@ __global__ __launch_bounds__(256) void k_col_reduce_bwd_bf16x8(const uint16_t* _
     }
 }
 
+// ---- frozen BatchNorm, backward (sd_frozen_bn_bwd): g = dy * [y > 0] (y null: no ReLU), dx = g * scale[c], optionally g_out = g.  The layer
+// is the per-channel affine of sd_bn_fold, so there is nothing to reduce: one streaming pass, dy (and y) in, dx (and g) out.  The vector
+// kernels take a float4 / 8 bf16 per thread and step: the grid stride is a multiple of 256 and the column count (C/4, C/8) divides 256, so a
+// thread never leaves its column and keeps its scales in registers.  The element-wise kernel (a misaligned pointer, bf16 with C % 8 != 0)
+// stages the scales in LDS.
+__global__ __launch_bounds__(256) void k_bn_frozen_bwd_f32x4(const float* __restrict__ dy, const float* __restrict__ y, const float* __restrict__ scale,
+                                                              int64_t n4, int C, float* __restrict__ dx, float* __restrict__ g_out) {
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    const int64_t i0 = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int c0 = 4 * (int)(i0 % (C >> 2));
+    const float s0 = scale[c0], s1 = scale[c0 + 1], s2 = scale[c0 + 2], s3 = scale[c0 + 3];
+    for (int64_t i = i0; i < n4; i += stride) {
+        float4 g = ld4(dy, i);
+        if (y) {
+            const float4 yy = ld4(y, i);
+            g.x = yy.x > 0.f ? g.x : 0.f; g.y = yy.y > 0.f ? g.y : 0.f; g.z = yy.z > 0.f ? g.z : 0.f; g.w = yy.w > 0.f ? g.w : 0.f;
+        }
+        st4(dx, i, make_float4(g.x * s0, g.y * s1, g.z * s2, g.w * s3));
+        if (g_out) st4(g_out, i, g);
+    }
+}
+
+// two bf16 of a dword: the gradient where the ReLU output is positive (its own bits), +0 elsewhere / times their scales, rounded to nearest even
+__device__ __forceinline__ uint32_t frozen_mask2(uint32_t d, uint32_t y) {
+    return (bf16_to_f32((uint16_t)(y & 0xffffu)) > 0.f ? (d & 0xffffu) : 0u) | (bf16_to_f32((uint16_t)(y >> 16)) > 0.f ? (d & 0xffff0000u) : 0u);
+}
+__device__ __forceinline__ uint32_t frozen_scale2(uint32_t g, float s0, float s1) {
+    return (uint32_t)f32_to_bf16(bf16_to_f32((uint16_t)(g & 0xffffu)) * s0) | ((uint32_t)f32_to_bf16(bf16_to_f32((uint16_t)(g >> 16)) * s1) << 16);
+}
+
+__global__ __launch_bounds__(256) void k_bn_frozen_bwd_bf16x8(const uint16_t* __restrict__ dy, const uint16_t* __restrict__ y, const float* __restrict__ scale,
+                                                               int64_t n8, int C, uint16_t* __restrict__ dx, uint16_t* __restrict__ g_out) {
+    typedef unsigned sd_u32x4_nt __attribute__((ext_vector_type(4)));               // (read once: non-temporal, see ld4 in sd_common.h)
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    const int64_t i0 = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int c0 = 8 * (int)(i0 % (C >> 3));
+    float s[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) s[j] = scale[c0 + j];
+    for (int64_t i = i0; i < n8; i += stride) {
+        const sd_u32x4_nt d = __builtin_nontemporal_load(reinterpret_cast<const sd_u32x4_nt*>(dy) + i);
+        uint4 g = make_uint4(d[0], d[1], d[2], d[3]);
+        if (y) {
+            const sd_u32x4_nt m = __builtin_nontemporal_load(reinterpret_cast<const sd_u32x4_nt*>(y) + i);
+            g = make_uint4(frozen_mask2(g.x, m[0]), frozen_mask2(g.y, m[1]), frozen_mask2(g.z, m[2]), frozen_mask2(g.w, m[3]));
+        }
+        reinterpret_cast<uint4*>(dx)[i] = make_uint4(frozen_scale2(g.x, s[0], s[1]), frozen_scale2(g.y, s[2], s[3]), frozen_scale2(g.z, s[4], s[5]),
+                                                     frozen_scale2(g.w, s[6], s[7]));
+        if (g_out) reinterpret_cast<uint4*>(g_out)[i] = g;
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_bn_frozen_bwd_ew(const T* __restrict__ dy, const T* __restrict__ y, const float* __restrict__ scale, int64_t n,
+                                                           int C, T* __restrict__ dx, T* __restrict__ g_out) {
+    __shared__ float s[1024];                                                       // C <= 1024 (check_mc)
+    for (int c = threadIdx.x; c < C; c += 256) s[c] = scale[c];
+    __syncthreads();
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+        const float sc = s[(int)(i % C)];
+        if constexpr (std::is_same<T, float>::value) {
+            const float g = (!y || y[i] > 0.f) ? dy[i] : 0.f;
+            dx[i] = g * sc;
+            if (g_out) g_out[i] = g;
+        } else {
+            const uint16_t g = (!y || bf16_to_f32(y[i]) > 0.f) ? dy[i] : (uint16_t)0;
+            dx[i] = f32_to_bf16(bf16_to_f32(g) * sc);
+            if (g_out) g_out[i] = g;
+        }
+    }
+}
+
 static inline int ew_grid(int64_t n4) { return (int)std::min<int64_t>(cdiv(n4, 256), 256 * 16); }
 
 }  // namespace sd
@@ -1853,6 +1926,30 @@ static int bn_bwd_apply_any(const char* what, const T* dy, const T* x, const voi
     if (int e = check_relu(what, relu, y, beta)) return e;
     SD_REQUIRE(dy && x && mean && invstd && gamma && means && dx, SD_ERR_INVALID, "%s: null pointer", what);
     return bn_bwd_apply_launch<T>(dy, x, y, relu, M, C, mean, invstd, gamma, beta, means, dx, g_out, is_bf16<T> && bn_bwd_wide(C, relu, dy, x, dx, g_out), st);
+}
+
+// frozen BatchNorm, backward: the vector kernel where every pointer given is 16-byte aligned (null counts as aligned; bf16: and C % 8 == 0)
+static bool frozen_bwd_wide(bool bf16, int C, const void* dy, const void* y, const void* dx, const void* g_out) {
+    return (!bf16 || C % 8 == 0) && aligned16(dy) && aligned16(y) && aligned16(dx) && aligned16(g_out);
+}
+static Launch frozen_bwd_launch(bool bf16, bool wide, int64_t M, int C) { return ew_launch(wide ? M * C / (bf16 ? 8 : 4) : M * C); }
+static bool ranges_meet(const void* a, const void* b, size_t bytes) {                 // two buffers of `bytes` each share a byte (null: no buffer)
+    const uintptr_t p = reinterpret_cast<uintptr_t>(a), q = reinterpret_cast<uintptr_t>(b);
+    return a && b && p < q + bytes && q < p + bytes;
+}
+
+template <typename T>
+static int bn_frozen_bwd_any(const char* what, const T* dy, const T* y, const float* scale, int64_t M, int C, T* dx, T* g_out, hipStream_t st) {
+    if (int e = check_mc(what, M, C)) return e;
+    SD_REQUIRE(dy && scale && dx, SD_ERR_INVALID, "%s: null pointer", what);
+    const size_t bytes = (size_t)M * C * sizeof(T);
+    SD_REQUIRE(!ranges_meet(dx, dy, bytes) && !ranges_meet(dx, y, bytes) && !ranges_meet(g_out, dy, bytes) && !ranges_meet(g_out, y, bytes) &&
+               !ranges_meet(dx, g_out, bytes), SD_ERR_INVALID, "%s: dx and g_out must not alias dy, y or each other", what);
+    const bool wide = frozen_bwd_wide(is_bf16<T>, C, dy, y, dx, g_out);
+    const Launch l = frozen_bwd_launch(is_bf16<T>, wide, M, C);
+    if (!wide) SD_RETURN_LAUNCH(k_bn_frozen_bwd_ew<T>, l.grid, 0, st, dy, y, scale, l.n, C, dx, g_out);
+    if constexpr (is_bf16<T>) SD_RETURN_LAUNCH(k_bn_frozen_bwd_bf16x8, l.grid, 0, st, dy, y, scale, l.n, C, dx, g_out);
+    else SD_RETURN_LAUNCH(k_bn_frozen_bwd_f32x4, l.grid, 0, st, dy, y, scale, l.n, C, dx, g_out);
 }
 
 // The finish on caller-provided partial rows [rows][2][C] (one per conv tile: up to 8192), MODE and a..d as col_finish.  `split`: phase 1 of
@@ -2142,6 +2239,15 @@ FORMS(sd_bn_bwd_apply, float, float)
 FORMS(sd_bn_bwd_apply_bf16, uint16_t, void)
 #undef FORMS
 
+// backward of a BatchNorm that normalises with its stored statistics (scale: sd_bn_fold's): no reduction, one pass
+#define FORMS(NAME, T, V)                                                                                                              \
+    int NAME(const V* dy, const V* y, const float* scale, int64_t M, int C, V* dx, V* g_out, sd_stream_t stream) {                    \
+        return bn_frozen_bwd_any<T>(#NAME, (const T*)dy, (const T*)y, scale, M, C, (T*)dx, (T*)g_out, (hipStream_t)stream);            \
+    }
+FORMS(sd_frozen_bn_bwd, float, float)
+FORMS(sd_frozen_bn_bwd_bf16, uint16_t, void)
+#undef FORMS
+
 int sd_maxpool3x3s2_fwd(const float* x, float* y, uint8_t* idx, int B, int Hi, int Wi, int C, sd_stream_t stream) {
     if (int e = check_map("sd_maxpool3x3s2_fwd", x && y && idx, B, Hi, Wi, C, 4)) return e;
     const int Ho = pool_out(Hi), Wo = pool_out(Wi);
@@ -2386,7 +2492,8 @@ struct Names {
 static int check_desc(const char* what, const sd_nn_call_desc& d, int64_t M) {
     switch (d.op) {
     case SD_NN_BN_STATS_FROM_SUMS: case SD_NN_BN_BWD_MEANS_FROM_SUMS: return check_mc(what, 1, d.C);
-    case SD_NN_BN_TRAIN_STATS: case SD_NN_BN_FINALIZE_STATS: case SD_NN_BN_APPLY: case SD_NN_BN_BWD_FINALIZE: case SD_NN_COL_SUM: return check_mc(what, M, d.C);
+    case SD_NN_BN_TRAIN_STATS: case SD_NN_BN_FINALIZE_STATS: case SD_NN_BN_APPLY: case SD_NN_BN_BWD_FINALIZE: case SD_NN_COL_SUM: case SD_NN_BN_FROZEN_BWD:
+        return check_mc(what, M, d.C);
     case SD_NN_BN_BWD: case SD_NN_BN_BWD_REDUCE: case SD_NN_BN_BWD_APPLY:
         if (int e = check_mc(what, M, d.C)) return e;
         return check_relu(what, d.relu, what, what);
@@ -2451,6 +2558,11 @@ const char* sd_nn_kernel_names(const sd_nn_call_desc* d) {
         if (op != SD_NN_BN_BWD_APPLY) out.reduce(wide ? "k_col_reduce_bwd_bf16x8" : NAME("k_col_reduce<1, %s>", T), p.nb, p.fold, 1, sums, C);
         if (!reduce_only) out.add(wide ? "k_bn_bwd_apply_bf16x8" : NAME("k_bn_bwd_apply<%s>", T), bn_ew_launch(wide, M, C));
         if (op != SD_NN_BN_BWD_APPLY) out.plan(p);
+        break;
+    }
+    case SD_NN_BN_FROZEN_BWD: {
+        const bool wide = frozen_bwd_wide(bf, C, ptr(0), ptr(1), ptr(2), ptr(3));
+        out.add(!wide ? NAME("k_bn_frozen_bwd_ew<%s>", T) : bf ? "k_bn_frozen_bwd_bf16x8" : "k_bn_frozen_bwd_f32x4", frozen_bwd_launch(bf, wide, M, C));
         break;
     }
     case SD_NN_MAXPOOL_FWD: out.add(bf ? "k_maxpool_fwd_bf16" : "k_maxpool_fwd", map_launch(d->B, Ho, Wo, C, bf ? 8 : 4)); break;

@@ -30,6 +30,7 @@ from ..utils import trace as T
 
 BN_EPS = 1e-5
 BN_MOMENTUM = 0.1
+FREEZE_STAGES = ("adpater", "down1", "down2", "down3", "down4")     # `Network.freeze(stages=N)`: the first N, in the order of parameters()
 
 
 # ------------------------------------------------------------------------------------------
@@ -158,6 +159,12 @@ class StemRec(NamedTuple):
 class BlockRec(NamedTuple):
     blk: object; xin: object; hw: tuple; d1: object; c1: object; a1: object; m1: object; i1: object; d2: object; c2: object; m2: object
     i2: object; out: object; dd: object; cd: object; md: object; idd: object; mask: object
+
+
+class FrozenBnRec(NamedTuple):
+    """a trainable block whose BatchNorms are frozen (`Network.freeze(bn=True)`): the eval schedule's three launches, no statistics;
+    scales = the folded (conv1, conv2, downsample or None) BatchNorm scales its backward multiplies by"""
+    blk: object; xin: object; hw: tuple; d1: object; a1: object; d2: object; out: object; dd: object; idt: object; scales: tuple
 
 
 class FpnRec(NamedTuple):
@@ -388,6 +395,10 @@ class _Engine:
                 raise L.SdError("amp=True is the mixed-precision TRAINING forward; inference uses forward_bf16")
             return self._eval(x, False)
         net, lib = self.net, self.lib
+        nf, fbn = net.frozen_stages, net.frozen_bn            # `Network.freeze`: the first nf of FREEZE_STAGES / the trainable trunk's BatchNorms
+        if nf and self.fuse_bn_bwd:
+            raise L.SdError("fuse_bn_bwd does not combine with Network.freeze: its data-gradient epilogues reduce for BatchNorms that a "
+                            "freeze takes out of the backward; switch one of them off")
         if amp:
             self.refresh_bf16_weights()
         x, B, H, W = self._input(x)
@@ -398,40 +409,16 @@ class _Engine:
             sx.begin("fwd")
         how = (self._w16, lib.sd_conv2d_fwd_bf16, None, 16, False, True) if amp \
             else (self._w32, lib.sd_conv2d_fwd, lib.sd_conv2d_fwd_workspace_bytes, 0, False, True)
-        act = torch.bfloat16 if amp else torch.float32
 
-        # stem: conv7x7/2 + BN + ReLU + maxpool3x3/2 (network.py:43-45)
-        T.push("fwd:stem")
-        stem, bn0 = net.adpater[0], net.adpater[1]
-        d0 = _desc(B, H, W, stem)
-        # mixed precision: the stem's conv output and pooled map are bf16 too (H % 32 == 0 makes the stem map even: the quad form of the
-        # tail's backward always applies); BatchNorm statistics / arithmetic stay fp32
-        s0 = torch.empty((B, d0.Ho, d0.Wo, 64), dtype=act, device=x.device)
-        self._ws(lib.sd_conv2d_stem_fwd_workspace_bytes(C.byref(d0)), x.device)         # the shared workspace is at least the eval stem's
-        Hp, Wp = (d0.Ho + 2 - 3) // 2 + 1, (d0.Wo + 2 - 3) // 2 + 1
-        p1 = torch.empty((B, Hp, Wp, 64), dtype=act, device=x.device)
-        pidx = torch.empty((B, Hp, Wp, 64), dtype=torch.uint8, device=x.device)
-        # BatchNorm + ReLU + max-pool in one pass over the conv output: the full-resolution activation (1 GB at bs=64,
-        # 512x512) is neither written nor read back; the backward recomputes what it needs from s0 and the pool indices
-        m0 = torch.empty(64, dtype=torch.float32, device=x.device)
-        i0 = torch.empty_like(m0)
-        ws = self._ws(lib.sd_conv2d_stem_fwd_bn_stats_workspace_bytes(C.byref(d0)), x.device)
-        if sx is None:                                                            # amp: product on the bf16 MFMA
-            L.check(self._fn("sd_conv2d_stem_fwd_bn_stats", amp)(
-                x.data_ptr(), stem.weight.data_ptr(), s0.data_ptr(), C.byref(d0), BN_EPS, BN_MOMENTUM, *self._running(bn0, True),
-                m0.data_ptr(), i0.data_ptr(), ws.data_ptr(), ws.numel(), L.stream()), "sd_conv2d_stem_fwd_bn_stats")
+        if nf:
+            # frozen stages make the launches of the eval schedule (BatchNorm folded, running statistics read and not written, bf16 form
+            # under mixed precision) and leave nothing on the tape
+            frozen_how = self._eval_how(amp)
+            p1, Hp, Wp = self._eval_stem(x, B, H, W, amp)
+            if rec:
+                tape["x"], tape["stem"], tape["amp"] = None, None, bool(amp)
         else:
-            sums = sx.take(64)
-            sx.record("sd_conv2d_stem_fwd_bn_sums")
-            L.check(self._fn("sd_conv2d_stem_fwd_bn_sums", amp)(x.data_ptr(), stem.weight.data_ptr(), s0.data_ptr(), C.byref(d0), sums.data_ptr(),
-                                                                ws.data_ptr(), ws.numel(), L.stream()), "sd_conv2d_stem_fwd_bn_sums")
-            self._stats_from_sums(sx, sums, bn0, m0, i0)
-        self._nbt.append(bn0.num_batches_tracked)
-        L.check(self._fn("sd_bn_relu_maxpool_fwd", amp)(s0.data_ptr(), B, d0.Ho, d0.Wo, 64, m0.data_ptr(), i0.data_ptr(), bn0.weight.data_ptr(),
-                                                        bn0.bias.data_ptr(), p1.data_ptr(), pidx.data_ptr(), L.stream()), "sd_bn_relu_maxpool_fwd")
-        if rec:
-            tape["x"], tape["stem"], tape["amp"] = x, StemRec(d0, s0, m0, i0, pidx), bool(amp)
-        T.pop()
+            p1, Hp, Wp = self._train_stem(x, B, H, W, amp, sx, tape)
 
         # trunk (network.py:47-50)
         feats, cur, Hc, Wc = [], p1, Hp, Wp
@@ -439,6 +426,16 @@ class _Engine:
         for li, layer in enumerate((net.down1, net.down2, net.down3, net.down4), start=1):
             T.push(f"fwd:down{li}")
             for blk in layer:
+                if li < nf:
+                    cur, Hc, Wc = self._eval_block(frozen_how, blk, cur, B, Hc, Wc)[:3]
+                    continue
+                if fbn:
+                    # frozen BatchNorm in a trainable block: the same three launches through the training `how` (this step's weights)
+                    out, Ho, Wo, a1, d1, d2, idt, dd, scales = self._eval_block(how, blk, cur, B, Hc, Wc)
+                    if rec:
+                        blocks_tape.append(FrozenBnRec(blk, cur, (Hc, Wc), d1, a1, d2, out, dd, idt if dd is not None else None, scales))
+                    cur, Hc, Wc = out, Ho, Wo
+                    continue
                 c1, d1, st1 = self.conv_stats(cur, blk.conv1, B, Hc, Wc, blk.bn1, amp=amp, sync=sx)
                 a1, m1, i1 = self.bn_train(c1, blk.bn1, stats=st1)
                 c2, d2, st2 = self.conv_stats(a1, blk.conv2, B, d1.Ho, d1.Wo, blk.bn2, amp=amp, sync=sx)
@@ -477,25 +474,65 @@ class _Engine:
         T.pop()
         if rec:
             tape.update(blocks=blocks_tape, fpn=fpn_tape, p5=(p5, H5, W5), f1=f, B=B, hw=(H2, W2))
-        torch._foreach_add_(self._nbt, 1)
+        if self._nbt:
+            torch._foreach_add_(self._nbt, 1)
         self._nbt = []
         return out
+
+    def _train_stem(self, x, B, H, W, amp, sx, tape):
+        """Training stem: conv7x7/2 with batch statistics, then BatchNorm + ReLU + max-pool in one pass -> (pooled map, Hp, Wp)."""
+        net, lib = self.net, self.lib
+        rec = tape is not None
+        act = torch.bfloat16 if amp else torch.float32
+        # stem: conv7x7/2 + BN + ReLU + maxpool3x3/2 (network.py:43-45)
+        T.push("fwd:stem")
+        stem, bn0 = net.adpater[0], net.adpater[1]
+        d0 = _desc(B, H, W, stem)
+        # mixed precision: the stem's conv output and pooled map are bf16 too (H % 32 == 0 makes the stem map even: the quad form of the
+        # tail's backward always applies); BatchNorm statistics / arithmetic stay fp32
+        s0 = torch.empty((B, d0.Ho, d0.Wo, 64), dtype=act, device=x.device)
+        self._ws(lib.sd_conv2d_stem_fwd_workspace_bytes(C.byref(d0)), x.device)         # the shared workspace is at least the eval stem's
+        Hp, Wp = (d0.Ho + 2 - 3) // 2 + 1, (d0.Wo + 2 - 3) // 2 + 1
+        p1 = torch.empty((B, Hp, Wp, 64), dtype=act, device=x.device)
+        pidx = torch.empty((B, Hp, Wp, 64), dtype=torch.uint8, device=x.device)
+        # BatchNorm + ReLU + max-pool in one pass over the conv output: the full-resolution activation (1 GB at bs=64,
+        # 512x512) is neither written nor read back; the backward recomputes what it needs from s0 and the pool indices
+        m0 = torch.empty(64, dtype=torch.float32, device=x.device)
+        i0 = torch.empty_like(m0)
+        ws = self._ws(lib.sd_conv2d_stem_fwd_bn_stats_workspace_bytes(C.byref(d0)), x.device)
+        if sx is None:                                                            # amp: product on the bf16 MFMA
+            L.check(self._fn("sd_conv2d_stem_fwd_bn_stats", amp)(
+                x.data_ptr(), stem.weight.data_ptr(), s0.data_ptr(), C.byref(d0), BN_EPS, BN_MOMENTUM, *self._running(bn0, True),
+                m0.data_ptr(), i0.data_ptr(), ws.data_ptr(), ws.numel(), L.stream()), "sd_conv2d_stem_fwd_bn_stats")
+        else:
+            sums = sx.take(64)
+            sx.record("sd_conv2d_stem_fwd_bn_sums")
+            L.check(self._fn("sd_conv2d_stem_fwd_bn_sums", amp)(x.data_ptr(), stem.weight.data_ptr(), s0.data_ptr(), C.byref(d0), sums.data_ptr(),
+                                                                ws.data_ptr(), ws.numel(), L.stream()), "sd_conv2d_stem_fwd_bn_sums")
+            self._stats_from_sums(sx, sums, bn0, m0, i0)
+        self._nbt.append(bn0.num_batches_tracked)
+        L.check(self._fn("sd_bn_relu_maxpool_fwd", amp)(s0.data_ptr(), B, d0.Ho, d0.Wo, 64, m0.data_ptr(), i0.data_ptr(), bn0.weight.data_ptr(),
+                                                        bn0.bias.data_ptr(), p1.data_ptr(), pidx.data_ptr(), L.stream()), "sd_bn_relu_maxpool_fwd")
+        if rec:
+            tape["x"], tape["stem"], tape["amp"] = x, StemRec(d0, s0, m0, i0, pidx), bool(amp)
+        T.pop()
+        return p1, Hp, Wp
 
     def forward_bf16(self, x):
         """Eval-mode forward with bf16 activations / weights and fp32 accumulation; BN folded into fp32 epilogues.
         The stem reads the fp32 image with fp32 weights and stores bf16; the head returns fp32 NCHW."""
         return self._eval(x, True)
 
-    def _eval(self, x, bf16):
-        """The eval schedule, fp32 or with a bf16 backbone (BASELINE stress config: "bf16 backbone + fp32 decode"): BatchNorm folded
-        into the conv epilogues.  bf16 only: stem + max-pool in one launch, the head in the epilogue of the last FPN conv."""
-        net, lib = self.net, self.lib
-        x, B, H, W = self._input(x)
-        how = (self._w_bf16, lib.sd_conv2d_fwd_bf16, lib.sd_conv2d_fwd_bf16_workspace_bytes, 16, True, False) if bf16 \
+    def _eval_how(self, bf16):
+        """the `how` of `conv` for the eval schedule (and for the frozen stages of a training forward)"""
+        lib = self.lib
+        return (self._w_bf16, lib.sd_conv2d_fwd_bf16, lib.sd_conv2d_fwd_bf16_workspace_bytes, 16, True, False) if bf16 \
             else (self._w32, lib.sd_conv2d_fwd, lib.sd_conv2d_fwd_workspace_bytes, 0, True, True)
-        act = torch.bfloat16 if bf16 else torch.float32
 
-        # stem: conv7x7/2 + BN + ReLU + maxpool3x3/2 (network.py:43-45)
+    def _eval_stem(self, x, B, H, W, bf16):
+        """Stem of the eval schedule, BatchNorm folded: conv7x7/2 + BN + ReLU + maxpool3x3/2 (network.py:43-45) -> (pooled map, Hc, Wc)."""
+        net, lib = self.net, self.lib
+        act = torch.bfloat16 if bf16 else torch.float32
         T.push("fwd:stem")
         stem, bn0 = net.adpater[0], net.adpater[1]
         d0 = _desc(B, H, W, stem)
@@ -519,22 +556,37 @@ class _Engine:
                 pidx = torch.empty((B, Hc, Wc, 64), dtype=torch.uint8, device=x.device)
                 L.check(lib.sd_maxpool3x3s2_fwd(a0.data_ptr(), cur.data_ptr(), pidx.data_ptr(), B, d0.Ho, d0.Wo, 64, L.stream()), "maxpool")
         T.pop()
+        return cur, Hc, Wc
+
+    def _eval_block(self, how, blk, cur, B, Hc, Wc):
+        """A BasicBlock with its BatchNorms folded into the conv epilogues: three `conv` launches (two without a downsample) ->
+        (out, Ho, Wo, a1, d1, d2, idt, dd, (scale1, scale2, downsample scale or None)); the eval schedule keeps the first three."""
+        s1, h1 = self.bn_fold(blk.bn1)
+        a1, d1 = self.conv(how, cur, blk.conv1, B, Hc, Wc, scale=s1, shift=h1, relu=True)
+        if blk.downsample is not None:
+            sd_, hd = self.bn_fold(blk.downsample[1])
+            idt, dd = self.conv(how, cur, blk.downsample[0], B, Hc, Wc, scale=sd_, shift=hd)
+        else:
+            idt, dd, sd_ = cur, None, None
+        s2, h2 = self.bn_fold(blk.bn2)
+        out, d2 = self.conv(how, a1, blk.conv2, B, d1.Ho, d1.Wo, scale=s2, shift=h2, res=idt, relu=True)
+        return out, d1.Ho, d1.Wo, a1, d1, d2, idt, dd, (s1, s2, sd_)
+
+    def _eval(self, x, bf16):
+        """The eval schedule, fp32 or with a bf16 backbone (BASELINE stress config: "bf16 backbone + fp32 decode"): BatchNorm folded
+        into the conv epilogues.  bf16 only: stem + max-pool in one launch, the head in the epilogue of the last FPN conv."""
+        net, lib = self.net, self.lib
+        x, B, H, W = self._input(x)
+        how = self._eval_how(bf16)
+
+        cur, Hc, Wc = self._eval_stem(x, B, H, W, bf16)
 
         # trunk (network.py:47-50)
         feats = []
         for li, layer in enumerate((net.down1, net.down2, net.down3, net.down4), start=1):
             T.push(f"fwd:down{li}")
             for blk in layer:
-                s1, h1 = self.bn_fold(blk.bn1)
-                a1, d1 = self.conv(how, cur, blk.conv1, B, Hc, Wc, scale=s1, shift=h1, relu=True)
-                if blk.downsample is not None:
-                    sd_, hd = self.bn_fold(blk.downsample[1])
-                    idt, _ = self.conv(how, cur, blk.downsample[0], B, Hc, Wc, scale=sd_, shift=hd)
-                else:
-                    idt = cur
-                s2, h2 = self.bn_fold(blk.bn2)
-                cur, _ = self.conv(how, a1, blk.conv2, B, d1.Ho, d1.Wo, scale=s2, shift=h2, res=idt, relu=True)
-                Hc, Wc = d1.Ho, d1.Wo
+                cur, Hc, Wc = self._eval_block(how, blk, cur, B, Hc, Wc)[:3]
             feats.append((cur, Hc, Wc))
             T.pop()
         (p2, H2, W2), (p3, H3, W3), (p4, H4, W4), (p5, H5, W5) = feats
@@ -731,11 +783,28 @@ class _Engine:
         L.check(self._fn("sd_bn_bwd_apply", bf16)(*head, means.data_ptr(), dx.data_ptr(), _ptr(g), L.stream()), "sd_bn_bwd_apply")
         return dx, g
 
+    def _frozen_bwd(self, dy, y, scale, want_g=False):
+        """Backward of a frozen BatchNorm (+ ReLU where `y`, its output, is given): dx = g * scale with g = dy * [y > 0]; (dx, g on request)."""
+        Mrows, Cc = dy.numel() // dy.shape[-1], dy.shape[-1]
+        dx = torch.empty_like(dy)
+        g = torch.empty_like(dy) if want_g else None
+        L.check(self._fn("sd_frozen_bn_bwd", dy.dtype == torch.bfloat16)(dy.data_ptr(), _ptr(y), scale.data_ptr(), Mrows, Cc, dx.data_ptr(), _ptr(g),
+                                                                         L.stream()), "sd_frozen_bn_bwd")
+        return dx, g
+
     def backward(self, tape, dhead, on_stage=None):
         """Writes every parameter gradient into `net.flat_grads` (overwriting, not accumulating).
         on_stage(name) is called after the gradients of a parameter group are complete, in the order
-        'fpn_head', 'down4', 'down3', 'down2', 'down1_stem' (bucketed all-reduce hook)."""
+        'fpn_head', 'down4', 'down3', 'down2', 'down1_stem' (bucketed all-reduce hook).
+        With `Network.freeze(stages=N)` the tape holds the trainable blocks only: the block loop ends at the first of them, which launches
+        its weight-gradients but no data-gradient (its input is frozen output); lateral data-gradients into frozen output are dropped, the
+        stem tail and the stem weight-gradient are not launched, and with N = 5 neither is up1's data-gradient.  Frozen slots of
+        `flat_grads` are never written (`freeze` zeroed them); on_stage is still called for all five names in the same order, the frozen
+        ones directly after the last trainable one."""
         net, lib = self.net, self.lib
+        nf = net.frozen_stages
+        if nf and self.fuse_bn_bwd:
+            raise L.SdError("fuse_bn_bwd does not combine with Network.freeze; switch one of them off")
         B = tape["B"]
         H2, W2 = tape["hw"]
         dhead = dhead.contiguous().float()
@@ -788,8 +857,10 @@ class _Engine:
             return (b.c2, b.mask, RELU_MASK_BYTES, b.blk.bn2, b.m2, b.i2)
 
         last = len(blocks) - 1
-        has_lateral = blocks[last].out.data_ptr() in lateral_grad
-        dcur, mcur = self._dgrad(df, net.up1, d5, bn_next=None if has_lateral else bn2_of(last), sync=sx)
+        dcur = mcur = None
+        if blocks:                                              # (all five stages frozen: p5 is frozen output, nothing takes its gradient)
+            has_lateral = blocks[last].out.data_ptr() in lateral_grad
+            dcur, mcur = self._dgrad(df, net.up1, d5, bn_next=None if has_lateral else bn2_of(last), sync=sx)
         T.pop()
         if on_stage:
             self._join_side()
@@ -797,24 +868,39 @@ class _Engine:
 
         # trunk, last block first
         first_of = {id(net.down4[0]): "down4", id(net.down3[0]): "down3", id(net.down2[0]): "down2"}
+        stage = "down4"                                         # the parameter group whose range is open
         T.push("bwd:down4")
         for bi in range(last, -1, -1):
             b = blocks[bi]
             blk, xin, (Hc, Wc) = b.blk, b.xin, b.hw
+            frozen_bn = isinstance(b, FrozenBnRec)
+            inner = not (nf and bi == 0)                        # False: the first trainable block behind frozen stages -- d(xin) has no taker
             extra = lateral_grad.pop(b.out.data_ptr(), None)
             if extra is not None:                       # `out` also feeds an FPN lateral conv: this launch completes d(out)
                 dcur, mcur = self._dgrad(extra.dy, extra.conv, extra.d, res=dcur, bn_next=bn2_of(bi), sync=sx)
-            dc2, g = self._bn_bwd(dcur, b.c2, b.mask, RELU_MASK_BYTES, blk.bn2, b.m2, b.i2, want_g=True, means=mcur, sync=sx)
-            nxt = (b.c1, None, RELU_FROM_X, blk.bn1, b.m1, b.i1) if self.fuse_bn_bwd else None
-            da1, ma1 = self._dgrad(dc2, blk.conv2, b.d2, bn_next=nxt, sync=sx)
-            self._wgrad(dc2, b.a1, blk.conv2, b.d2)
-            dc1, _ = self._bn_bwd(da1, b.c1, b.a1, RELU_FROM_X, blk.bn1, b.m1, b.i1, means=ma1, sync=sx)
+            if frozen_bn:
+                s1, s2, sd_ = b.scales
+                dc2, g = self._frozen_bwd(dcur, b.out, s2, want_g=True)
+                da1, _ = self._dgrad(dc2, blk.conv2, b.d2)
+                self._wgrad(dc2, b.a1, blk.conv2, b.d2)
+                dc1, _ = self._frozen_bwd(da1, b.a1, s1)
+            else:
+                dc2, g = self._bn_bwd(dcur, b.c2, b.mask, RELU_MASK_BYTES, blk.bn2, b.m2, b.i2, want_g=True, means=mcur, sync=sx)
+                nxt = (b.c1, None, RELU_FROM_X, blk.bn1, b.m1, b.i1) if self.fuse_bn_bwd else None
+                da1, ma1 = self._dgrad(dc2, blk.conv2, b.d2, bn_next=nxt, sync=sx)
+                self._wgrad(dc2, b.a1, blk.conv2, b.d2)
+                dc1, _ = self._bn_bwd(da1, b.c1, b.a1, RELU_FROM_X, blk.bn1, b.m1, b.i1, means=ma1, sync=sx)
             half = False
             if blk.downsample is not None:
-                dcd, _ = self._bn_bwd(g, b.cd, None, RELU_NONE, blk.downsample[1], b.md, b.idd, sync=sx)
+                if frozen_bn:
+                    dcd, _ = self._frozen_bwd(g, None, sd_)
+                else:
+                    dcd, _ = self._bn_bwd(g, b.cd, None, RELU_NONE, blk.downsample[1], b.md, b.idd, sync=sx)
                 ds, dd = blk.downsample[0], b.dd
                 half = ds.k == 1 and ds.stride == 2 and ds.pad == 0 and Hc % 2 == 0 and Wc % 2 == 0 and not self.fuse_bn_bwd
-                if half:
+                if not inner:
+                    skip = None
+                elif half:
                     # 1x1 / stride 2: the gradient lives on the even pixels only -> stride-1 data-gradient on the small map,
                     # joined by conv1's data-gradient epilogue (no zero-filled full-size tensor)
                     dsm = L.ConvDesc()
@@ -826,17 +912,32 @@ class _Engine:
                 self._wgrad(dcd, xin, ds, dd)
             else:
                 skip = g
-            # d(xin) = d(out of the previous block), complete unless that tensor also feeds an FPN lateral (handled above)
-            prev_lateral = bi > 0 and blocks[bi - 1].out.data_ptr() in lateral_grad
-            nxt = None if (bi == 0 or prev_lateral) else bn2_of(bi - 1)
-            dcur, mcur = self._dgrad(dc1, blk.conv1, b.d1, res=skip, bn_next=nxt, res_half=half, sync=sx)
+            if inner:
+                # d(xin) = d(out of the previous block), complete unless that tensor also feeds an FPN lateral (handled above)
+                prev_lateral = bi > 0 and blocks[bi - 1].out.data_ptr() in lateral_grad
+                nxt = None if (bi == 0 or prev_lateral) else bn2_of(bi - 1)
+                dcur, mcur = self._dgrad(dc1, blk.conv1, b.d1, res=skip, bn_next=nxt, res_half=half, sync=sx)
             self._wgrad(dc1, xin, blk.conv1, b.d1)
             if id(blk) in first_of:                                         # the first block of a layer closes that layer's range
                 T.pop()
                 if on_stage:
                     self._join_side()
                     on_stage(first_of[id(blk)])
-                T.push("bwd:" + {"down4": "down3", "down3": "down2", "down2": "down1_stem"}[first_of[id(blk)]])
+                stage = {"down4": "down3", "down3": "down2", "down2": "down1_stem"}[first_of[id(blk)]]
+                T.push("bwd:" + stage)
+
+        lateral_grad.clear()                                    # what is left points into frozen output: dropped on purpose
+        if nf:
+            # frozen stages: no stem tail, no stem weight-gradient; the open range closes and the remaining (frozen, all-zero) parameter
+            # groups are reported in today's order, so that the bucket plans of the exchange stay as they are
+            self._join_side()
+            self._wt_valid = None
+            T.pop()
+            if on_stage:
+                names = ("down4", "down3", "down2", "down1_stem")
+                for name in names[names.index(stage):]:
+                    on_stage(name)
+            return
 
         # stem (H % 32 == 0 made its map even: under mixed precision the conv output and the pooled gradient are bf16, as autocast's conv1
         # backward sees them)
@@ -888,7 +989,7 @@ class _NetFn(torch.autograd.Function):
         net = ctx.net
         net._engine.backward(ctx.tape, dhead)
         ctx.tape = None
-        return (None, None) + tuple(net.grad_of(p) for p in net._flat_order)
+        return (None, None) + tuple(None if id(p) in net._frozen_ids else net.grad_of(p) for p in net._flat_order)
 
 
 class Network(nn.Module):
@@ -944,6 +1045,7 @@ class Network(nn.Module):
         self._flat_order, self._flat_off = [], {}
         self._folded = {}        # eval-mode (scale, shift) per BN, valid until the parameters can have changed
         self._engine = None
+        self.frozen_stages, self.frozen_bn, self._frozen_ids = 0, False, frozenset()      # fine-tuning: `freeze`
 
     # ---- init / flat storage -------------------------------------------------------------
     def reset_parameters(self, seed=0):
@@ -994,7 +1096,52 @@ class Network(nn.Module):
                 self._flat_off[id(p)] = (off, n)
         self.flat_params, self.flat_grads, self.flat_params_bf16 = flat, grads, None
         self._folded = {}
-        self._engine = _Engine(self)
+        self._engine = _Engine(self)                         # (a freeze survives: the parameters are the same objects, the new gradients are zero)
+
+    # ---- fine-tuning: frozen trunk stages, frozen BatchNorm ------------------------------------
+    def freeze(self, stages=0, bn=False):
+        """Fine-tuning (`train --freeze_stages N [--freeze_bn]`), callable before or after `.to(device)`; `freeze(0)` undoes it.
+        stages = N: the first N of FREEZE_STAGES (stem, down1 .. down4), as Detectron2's FREEZE_AT -- their convolution weights and
+        BatchNorm weight / bias get no gradient and never change (`requires_grad = False`), their BatchNorms normalise with the running
+        statistics and write neither those nor `num_batches_tracked`; the training forward runs them on the eval schedule and the backward
+        does not visit them.  bn = True (needs N >= 1): the BatchNorms of the trunk blocks that still train are FrozenBatchNorm2d --
+        running statistics used and not written, weight / bias fixed, the convolutions around them train; the FPN's BatchNorms keep batch
+        statistics.  Eval-mode forwards and the state_dict keys are unchanged.  The frozen slots of `flat_grads` are zeroed here and
+        never written afterwards: the frozen stages are the prefix `frozen_range()` of the flat buffers."""
+        if isinstance(stages, bool) or not isinstance(stages, int) or not 0 <= stages <= len(FREEZE_STAGES):
+            raise ValueError(f"freeze: stages should be an integer in [0, {len(FREEZE_STAGES)}], not {stages!r}")
+        if bn and stages == 0:
+            raise ValueError("freeze: bn=True needs stages >= 1 (a frozen stem BatchNorm behind a trainable stem is not built)")
+        self.frozen_stages, self.frozen_bn = int(stages), bool(bn)
+        self._folded = {}                                    # a layer frozen now may have trained since its fold / bf16 copy was cached
+        self._mark_frozen()
+        return self
+
+    def _frozen_parameters(self):
+        """the parameters a freeze fixes: everything of the frozen stages, and under `frozen_bn` the BatchNorm weight / bias of the rest of the trunk"""
+        out = []
+        for k, name in enumerate(FREEZE_STAGES):
+            stage = getattr(self, name)
+            if k < self.frozen_stages:
+                out += list(stage.parameters())
+            elif self.frozen_bn:
+                out += [p for m in stage.modules() if isinstance(m, BNParams) for p in m.parameters()]
+        return out
+
+    def _mark_frozen(self):
+        frozen = self._frozen_parameters()
+        self._frozen_ids = frozenset(id(p) for p in frozen)
+        for p in self.parameters():
+            p.requires_grad_(id(p) not in self._frozen_ids)
+        if self.flat_grads is not None:
+            for p in frozen:
+                off, n = self._flat_off[id(p)]
+                self.flat_grads[off:off + n].zero_()
+
+    def frozen_range(self):
+        """(0, off): the flat-buffer element range of the frozen stages -- a prefix, because FREEZE_STAGES is the order of parameters();
+        off is the start of the first trainable stage's first slot (slots as `_build_flat` lays them out: 8 floats each)."""
+        return 0, sum((p.numel() + 7) // 8 * 8 for name in FREEZE_STAGES[:self.frozen_stages] for p in getattr(self, name).parameters())
 
     def grad_of(self, p):
         off, n = self._flat_off[id(p)]

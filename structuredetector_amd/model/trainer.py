@@ -89,6 +89,14 @@ class SimExchange:
 
 
 class TrainStep:
+    """One optimizer step on the flat buffers.  Fine-tuning: the net's `freeze` setting is read HERE, at construction (freeze first, then
+    build the step).  The optimizer then works on the suffix `flat[off:]` behind the frozen stages (`Network.frozen_range()`): parameter,
+    gradient, both moments and the EMA are offset by `off`, the decay mask by off / 4 bytes, n = total - off (slots are 32-byte aligned, so
+    every alignment rule holds) -- the prefix is never written by decay, update or average.  Frozen BatchNorm weight / bias INSIDE the
+    suffix (`freeze(bn=True)`) stay fixed because their gradient and their moments are zero, which makes the Adam update exactly zero and
+    leaves them undecayed (the mask covers convolution weights only): `Network.freeze` zeroes those slots of `flat_grads` and the backward
+    never writes them; their `exp_avg` / `exp_avg_sq` slots are zeroed at construction and again after `load_state_dict`."""
+
     def __init__(self, net, args, lr=None, betas=(0.9, 0.999), eps=1e-8, process_group=None, exchange=None, sync_bn=False,
                  weight_decay=0.0, clip_grad_norm=0.0, ema_decay=0.0):
         if net.flat_params is None:
@@ -101,6 +109,9 @@ class TrainStep:
         self.betas, self.eps = betas, eps
         self.exp_avg = torch.zeros_like(net.flat_params)
         self.exp_avg_sq = torch.zeros_like(net.flat_params)
+        self.frozen = (int(getattr(net, "frozen_stages", 0)), bool(getattr(net, "frozen_bn", False)))
+        self.frozen_off = net.frozen_range()[1] if self.frozen[0] else 0          # the optimizer's range starts behind the frozen stages
+        self._zero_frozen_moments()
         self.step_count = 0
         self.pg = process_group
         self.world = dist.get_world_size(process_group) if (dist.is_available() and dist.is_initialized()) else 1
@@ -137,6 +148,14 @@ class TrainStep:
         self._status.view(torch.float32)[1] = 1.0
         self._configure_optim()
 
+    def _zero_frozen_moments(self):
+        """Both moments of every frozen slot (`Network.freeze`) to zero: with a zero gradient the update of such a slot is exactly zero."""
+        net = self.net
+        for p in net._frozen_parameters() if self.frozen[0] else ():
+            off, n = net._flat_off[id(p)]
+            self.exp_avg[off:off + n].zero_()
+            self.exp_avg_sq[off:off + n].zero_()
+
     # ---- AdamW decay / global-norm clipping / weight EMA ----------------------------------------------------------------------
     def _configure_optim(self):
         """Buffers of the options that are on: the decay mask, the partials of the norm, the EMA copy (kept if it already exists)."""
@@ -144,7 +163,7 @@ class TrainStep:
         if self.weight_decay > 0 and self.decay_mask is None:
             self.decay_mask = self.build_decay_mask(net)
         if self.clip_grad_norm > 0 and self._partials is None:
-            self._partials = torch.empty(L.lib().sd_grad_sumsq_workspace_bytes(net.flat_grads.numel()) // 8, dtype=torch.float64,
+            self._partials = torch.empty(L.lib().sd_grad_sumsq_workspace_bytes(net.flat_grads.numel() - self.frozen_off) // 8, dtype=torch.float64,
                                          device=net.flat_params.device)
         if self.ema_decay > 0 and self.ema is None:
             self.ema = net.flat_params.detach().clone()
@@ -190,15 +209,17 @@ class TrainStep:
     def _optim_step(self):
         """sd_grad_sumsq (only with clipping) + sd_optim_step on the step's stream; nothing is read back."""
         net, lib, st = self.net, L.lib(), L.stream()
-        n = net.flat_params.numel()
+        off = self.frozen_off                        # floats; 4 bytes each, one mask byte per four
+        n = net.flat_params.numel() - off
         clip = self.clip_grad_norm > 0
         if clip:
-            L.check(lib.sd_grad_sumsq(net.flat_grads.data_ptr(), n, self._partials.data_ptr(), self._partials.numel() * 8, st), "sd_grad_sumsq")
-        L.check(lib.sd_optim_step(net.flat_params.data_ptr(), net.flat_grads.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), n,
+            L.check(lib.sd_grad_sumsq(net.flat_grads.data_ptr() + 4 * off, n, self._partials.data_ptr(), self._partials.numel() * 8, st), "sd_grad_sumsq")
+        L.check(lib.sd_optim_step(net.flat_params.data_ptr() + 4 * off, net.flat_grads.data_ptr() + 4 * off, self.exp_avg.data_ptr() + 4 * off,
+                                  self.exp_avg_sq.data_ptr() + 4 * off, n,
                                   self.step_count, self.lr, self.betas[0], self.betas[1], self.eps, 1.0 / self.world, self.weight_decay,
-                                  self.decay_mask.data_ptr() if self.decay_mask is not None else None, self.clip_grad_norm,
+                                  self.decay_mask.data_ptr() + off // 4 if self.decay_mask is not None else None, self.clip_grad_norm,
                                   self._partials.data_ptr() if clip else None, self._partials.numel() if clip else 0,
-                                  self.ema.data_ptr() if self.ema is not None else None,
+                                  self.ema.data_ptr() + 4 * off if self.ema is not None else None,
                                   self.ema_decay_at(self.step_count) if self.ema is not None else 0.0, self._status.data_ptr(), st), "sd_optim_step")
 
     @contextmanager
@@ -249,6 +270,7 @@ class TrainStep:
         if self.ema is not None:
             self.ema.copy_(state["ema"] if state.get("ema") is not None else self.net.flat_params)
         self._status[2] = int(state.get("skipped_steps", 0))
+        self._zero_frozen_moments()                  # (a state written under another freeze setting may hold moments for slots frozen now)
 
     def sync_parameters(self):
         """Identical initial weights on every rank (rank 0's)."""
@@ -408,8 +430,9 @@ class TrainStep:
         self.step_count += 1
         T.push("adam")
         if self.plain_adam:
-            L.check(L.lib().sd_adam_step(net.flat_params.data_ptr(), net.flat_grads.data_ptr(), self.exp_avg.data_ptr(),
-                                         self.exp_avg_sq.data_ptr(), net.flat_params.numel(), self.step_count, self.lr, self.betas[0],
+            off = 4 * self.frozen_off                 # bytes: the frozen stages' prefix is not the optimizer's
+            L.check(L.lib().sd_adam_step(net.flat_params.data_ptr() + off, net.flat_grads.data_ptr() + off, self.exp_avg.data_ptr() + off,
+                                         self.exp_avg_sq.data_ptr() + off, net.flat_params.numel() - self.frozen_off, self.step_count, self.lr, self.betas[0],
                                          self.betas[1], self.eps, 1.0 / self.world, L.stream()), "sd_adam_step")
         else:
             self._optim_step()
@@ -474,10 +497,11 @@ class Trainer:
         import numpy as np
 
         from ..data import CropDataset, Encode
-        from ..utils.args import check_train
+        from ..utils.args import check_freeze, check_train
         from .network import Network
         self.args = args
         check_train(args)                                              # --train_tiles, --keep_aspect, --aug_*: ranges, square inputs, --synthetic
+        self.freeze = check_freeze(args)                               # --freeze_stages N, --freeze_bn
         if getattr(args, "use_amp", False) and not BF16_TRAINING:
             # the reference autocasts the training forward under --amp (trainer.py:115-121); silently training in fp32 under the
             # same flag would be a different experiment with the same name
@@ -489,6 +513,7 @@ class Trainer:
         if args.pretrained_model:
             self.net.load_state_dict(torch.load(args.pretrained_model, map_location="cpu", weights_only=True))
         self.net.to(args.device).train()
+        self.net.freeze(*self.freeze)                                  # before the step is built: TrainStep reads the setting
         self.step = TrainStep(self.net, args, **train_step_kwargs(args))
         self.step.sync_parameters()
         self.scheduler = StepLR(self.step, args.lr_step)
@@ -665,7 +690,8 @@ class Trainer:
                     "optimizer": self.step.state_dict(), "scheduler": self.scheduler.state_dict(), "epoch": self.epoch,
                     "best": {k: getattr(self, k) for k in ("best_loss", "best_csi", "best_classif", "best_kp_reg")},
                     "augment_size": tuple(int(v) for v in self.augment.size), "torch_rng": torch.get_rng_state(),
-                    "numpy_rng": self.rng.bit_generator.state, "save_dir": str(self.save_dir), "global_step": int(self.global_step)}, path)
+                    "numpy_rng": self.rng.bit_generator.state, "save_dir": str(self.save_dir), "global_step": int(self.global_step),
+                    "freeze_stages": int(self.freeze[0]), "freeze_bn": bool(self.freeze[1])}, path)
 
     def load_resume(self, path):
         from pathlib import Path
@@ -687,6 +713,10 @@ class Trainer:
             self.rng.bit_generator.state = state["numpy_rng"]
             self.save_dir = Path(state["save_dir"])     # model_best_* and resume.pth of one run stay in one directory
         self.global_step = int(state.get("global_step", 0))
+        was = (int(state.get("freeze_stages", 0)), bool(state.get("freeze_bn", False)))
+        if was != tuple(self.freeze) and self.rank == 0:       # the freeze belongs to the command line: a run may thaw stages when it resumes
+            print("resume: the checkpoint was written with --freeze_stages %d%s, this run continues with --freeze_stages %d%s (the command "
+                  "line wins)" % (was[0], " --freeze_bn" if was[1] else "", self.freeze[0], " --freeze_bn" if self.freeze[1] else ""), flush=True)
 
     def scalar_writer(self):
         """The run's scalar log (rank 0), created on first use: TensorBoard when importable, always `<dir>/scalars.jsonl` (utils/scalars.py)."""
@@ -725,6 +755,10 @@ class Trainer:
         if self.rank == 0 and not self.step.plain_adam:
             print(f"optimizer: weight decay {self.step.weight_decay:g} (convolution weights), gradient clipping at norm "
                   f"{self.step.clip_grad_norm:g}, weight EMA {self.step.ema_decay:g} (0 = off)", flush=True)
+        if self.rank == 0 and self.freeze[0]:
+            from .network import FREEZE_STAGES
+            print(f"frozen trunk stages: {', '.join(FREEZE_STAGES[:self.freeze[0]])} (no gradient, BatchNorm on the stored statistics)"
+                  + ("; frozen BatchNorm in the trainable trunk stages" if self.freeze[1] else ""), flush=True)
         if self.rank == 0 and self.step.sync_bn:
             print(f"synchronized BatchNorm: on (statistics over the global batch of {self.step.world} rank(s) x {self.args.batch_size})", flush=True)
         if self.rank == 0 and self.augment.train_tiles:

@@ -173,6 +173,14 @@ _FLAGS = [
                                  "noise: a selected image's noise variance grows by g grey levels^2 per grey level, g uniform in [0, G] "
                                  "(0 <= G <= 2). Either of --aug_noise and --aug_noise_shot switches the stage on; same place in the chain "
                                  "and same limits. 0 = off.")),
+    (("--freeze_stages",), dict(type=int, default=0, metavar="N", help="Fine-tuning: keep the first N trunk stages (stem, down1, down2, "
+                                "down3, down4; 0 .. 5) as they were loaded: their convolution and BatchNorm parameters get no gradient and "
+                                "never change, their BatchNorms normalise with the stored running statistics and do not update them "
+                                "(Detectron2's FREEZE_AT). Their backward is not run. Not consulted by evaluate / detect. 0 = off.")),
+    (("--freeze_bn",), dict(action="store_true", help="Fine-tuning: the BatchNorms of the trunk stages that still train use their stored "
+                            "running statistics and keep their weight / bias (FrozenBatchNorm2d in the backbone); the convolutions around "
+                            "them train, the three FPN BatchNorms keep batch statistics. Needs --freeze_stages >= 1. Not consulted by "
+                            "evaluate / detect.")),
 ]
 
 _POSITIVE = ["in_channels", "fpn_depth", "batch_size", "epochs", "learning_rate", "down_ratio", "max_objects", "max_parts"]
@@ -393,6 +401,25 @@ def check_train(args):
     check_keep_aspect(args, training=True)
     for check in (check_aug_transpose, check_aug_blur, check_aug_perspective, check_aug_jpeg, check_aug_tone, check_aug_noise):
         check(args)
+
+
+MAX_FREEZE_STAGES = 5               # stem, down1 .. down4 (model/network.py FREEZE_STAGES)
+
+
+def check_freeze(args):
+    """`--freeze_stages` / `--freeze_bn` on a parsed namespace -> (N, frozen BatchNorm), as `train` checks them (model/trainer.py;
+    `evaluate`, `detect` and `Predictor` never look at the flags).  A namespace from before the flags gives (0, False).  N is an integer in
+    0 .. 5; `--freeze_bn` needs N >= 1: with the stem frozen no trainable convolution sits in front of a frozen stem BatchNorm, whose
+    backward (through the fused BatchNorm + ReLU + max-pool tail) is not built."""
+    n, bn = getattr(args, "freeze_stages", 0), getattr(args, "freeze_bn", False)
+    n = 0 if n is None else n
+    if isinstance(n, bool) or not isinstance(n, int):
+        raise ValueError(f"'freeze_stages' should be an integer number of trunk stages, not {n!r}")
+    if not 0 <= n <= MAX_FREEZE_STAGES:
+        raise ValueError(f"'freeze_stages' should be in [0, {MAX_FREEZE_STAGES}] (0 = off), not {n}")
+    if bn and n == 0:
+        raise ValueError("'freeze_bn' needs --freeze_stages >= 1: a frozen stem BatchNorm behind a trainable stem is not built")
+    return n, bool(bn)
 
 
 def finalize(args):
