@@ -982,6 +982,28 @@ int sd_optim_step(float* param, const float* grad, float* exp_avg, float* exp_av
                   const uint8_t* decay_mask, float max_norm, const void* partials, int npartials, float* ema,
                   float ema_decay, void* status, sd_stream_t stream);
 
+/* sd_optim_step with a learning rate and a weight decay per parameter GROUP (fine-tuning: a lower rate on the pretrained trunk, layer-wise
+ * rate decay) -- still one update launch over the whole flat buffer.  sd_optim_step's arguments, with the decay mask replaced by
+ *   group_ids (device, required): one byte per group of four floats (n / 4 bytes), laid out like decay_mask -- a group of four never
+ *     straddles two tensors.  The kernel uses id & 15: a stray byte cannot read outside the table, it names a row; the ids are not scanned;
+ *   lr_mul, wd_mul (HOST arrays of ngroups floats, 1 <= ngroups <= SD_OPTIM_MAX_GROUPS, every entry finite and >= 0): read during the call
+ *     and handed to the kernel by value in its arguments -- no device table, no upload, no lifetime rule.  Group k steps with
+ *     lr_k = lr * lr_mul[k] (one float multiply) and is decayed by p *= (float)(1 - (double)lr_k * weight_decay * wd_mul[k]) before the
+ *     update; wd_mul[k] == 0 or weight_decay == 0: group k is not decayed.  Rows k >= ngroups are 0 / 0: such a group does not move.
+ *     lr_mul[k] == 0 is torch's lr = 0 group: moments and EMA still update, the parameter does not move.
+ * Everything else is sd_optim_step's update in its operation order: a table [1, 1] / [0, 1] over ids equal to a 0 / 1 decay mask gives
+ * sd_optim_step's bits.  Clipping (the GLOBAL norm over all groups, from the same sd_grad_sumsq partials; a non-finite norm skips the step
+ * for every group), EMA and the status block behave exactly as there.  One kernel per (clipping, EMA) combination; decay is decided per
+ * group from the table.
+ * Errors: sd_optim_step's, and SD_ERR_INVALID for a null group_ids / lr_mul / wd_mul, ngroups outside 1 .. 16, a negative or non-finite
+ * multiplier. */
+#define SD_OPTIM_MAX_GROUPS 16
+int sd_optim_groups_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, int step,
+                         float lr, float beta1, float beta2, float eps, float grad_scale, float weight_decay,
+                         const uint8_t* group_ids, const float* lr_mul, const float* wd_mul, int ngroups,
+                         float max_norm, const void* partials, int npartials, float* ema, float ema_decay,
+                         void* status, sd_stream_t stream);
+
 /* What a call of the BatchNorm / pool / head / optimizer entry points above launches (host only; no pointer is read).  The descriptor names
  * the call: `op`, `form` (0 fp32, 1 bf16, 2 bf16 with a bf16 dx -- the stem tail's _dx16; SD_NN_CAST: 0 = to bf16, 1 = to fp32), the shape
  * (the map ops take B, H, W; the head B and H = HW; every other op M -- the optimizer and the casts their n), C, Co, relu, rows (the
@@ -989,7 +1011,7 @@ int sd_optim_step(float* param, const float* grad, float* exp_avg, float* exp_av
  *     bn_apply: x, y, residual        bn_bwd / bn_bwd_apply: dy, x, dx, g_out (bn_bwd_reduce: dy, x)        bn_relu_maxpool_fwd: x, y_pool, idx
  *     head_fwd: x, w, y               head_bwd: x, dy
  * SD_NN_SCRATCH = scratch given, SD_NN_SUMS = the split form that stops at the fp64 sums (sd_bn_train_sums, sd_bn_stats_sums, sd_bn_bwd_sums,
- * sd_bn_bwd_reduce, sd_maxpool_bn_relu_bwd_reduce), SD_NN_DECAY / _CLIP / _EMA = the options of sd_optim_step.  pool_fwd_pair: the option
+ * sd_bn_bwd_reduce, sd_maxpool_bn_relu_bwd_reduce), SD_NN_DECAY / _CLIP / _EMA = the options of sd_optim_step (_CLIP / _EMA: of sd_optim_groups_step too).  pool_fwd_pair: the option
  * of that name as the call would see it.
  * sd_nn_kernel_names prints the launches in order, separated by "; ", each as "<kernel as rocprofv3 prints it, without sd::> grid=X block=256
  * lds=N" (N: dynamic bytes), a wide head's own kernels as "head_wide_fwd" / "head_wide_wgrad" / "head_wide_dgrad" (their grids need the
@@ -1008,7 +1030,10 @@ enum { SD_NN_BN_TRAIN_STATS, SD_NN_BN_FINALIZE_STATS, SD_NN_BN_STATS_FROM_SUMS, 
        /* ops 0 .. 23 are the ones of the recorded call trace (tests/golden/nn_call_trace.json), and 24, the first id behind them, is the
         * one tests/test_nn_plan_cpu.py asks about as an unknown op: it stays unused, ops added since follow from 25.  bn_frozen_bwd (sd_frozen_bn_bwd[_bf16]): M, C, form; flag bits: dy, y, dx, g_out
         * (a pointer the call leaves NULL counts as aligned) */
-       SD_NN_BN_FROZEN_BWD = 25 };
+       SD_NN_BN_FROZEN_BWD = 25,
+       /* sd_optim_groups_step: n in M; flags SD_NN_CLIP / SD_NN_EMA.  Prints the step's launches: k_grad_sumsq (with SD_NN_CLIP: the
+        * sd_grad_sumsq call that feeds it), then k_optim_groups<clip, ema> */
+       SD_NN_OPTIM_GROUPS = 26 };
 #define SD_NN_SCRATCH (1u << 8)
 #define SD_NN_SUMS (1u << 9)
 #define SD_NN_DECAY (1u << 10)

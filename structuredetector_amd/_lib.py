@@ -253,6 +253,9 @@ _SIGNATURES = {
     "sd_grad_sumsq": (c_int, [c_vp, c_i64, c_vp, c_size, c_vp]),
     "sd_optim_step": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_float, c_float, c_float, c_float, c_float, c_float, c_vp, c_float, c_vp, c_int,
                               c_vp, c_float, c_vp, c_vp]),
+    # the same with per-group rates: ... weight_decay, group_ids (DEVICE bytes), lr_mul, wd_mul (HOST floats), ngroups, max_norm, ... as above
+    "sd_optim_groups_step": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_float, c_float, c_float, c_float, c_float, c_float, c_vp,
+                                     C.POINTER(c_float), C.POINTER(c_float), c_int, c_float, c_vp, c_int, c_vp, c_float, c_vp, c_vp]),
     "sd_nn_kernel_names": (C.c_char_p, [C.POINTER(NnCallDesc)]),
     "sd_conv2d_kernel_name": (C.c_char_p, [c_vp, c_int]),
     "sd_set_option": (c_int, [C.c_char_p, c_int]),

@@ -1255,6 +1255,81 @@ __global__ __launch_bounds__(256) void k_optim(float* __restrict__ p, const floa
     }
 }
 
+// The same pass with a learning rate and a decay per parameter group (sd_optim_groups_step): one id byte per group of four floats, laid
+// out like k_optim's mask, names a row of a table of SD_OPTIM_MAX_GROUPS rows that arrives by value in the kernel arguments (SGPRs).
+// Every lane keeps row (lane & 15) of it in two registers, and a group's row is fetched from lane (id & 15) by a wave shuffle (two
+// ds_bpermute a float4) -- registers only: no table in memory, so no load that depends on the id byte -- and everything behind the pick
+// is k_optim's body in k_optim's order.  `decay_bits` bit k: group k is decayed at all (the multiply by
+// decay_mul stays behind a condition, as in k_optim, so that both kernels round alike); a row past ngroups is lr 0 / no decay.
+struct OptimGroupTable {
+    float step[SD_OPTIM_MAX_GROUPS];           // lr_k / bc1 with lr_k = lr * lr_mul[k]: k_optim's `lr / bc1`, the same fp32 division done on the host
+    float decay_mul[SD_OPTIM_MAX_GROUPS];      // 1 - lr_k * weight_decay * wd_mul[k]
+};
+
+template <bool CLIP, bool EMA>
+__global__ __launch_bounds__(256) void k_optim_groups(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                       float* __restrict__ v, int64_t n4, const OptimGroupTable tab, uint32_t decay_bits, float b1,
+                                                       float b2, float eps, float bc2_sqrt, float gscale,
+                                                       const uint8_t* __restrict__ ids, float max_norm, const double* __restrict__ partial,
+                                                       int npartial, float* __restrict__ ema, float ema_decay, uint32_t* __restrict__ status) {
+    float coef = 1.f;
+    if (CLIP) {                                                                // k_optim's finish of the partials, word for word
+        __shared__ double red[4];
+        double s = 0.0;
+        for (int k = threadIdx.x; k < npartial; k += 256) s += partial[k];
+        s = block_sum_256(s, red);
+        const float norm = (float)(fabs((double)gscale) * sqrt(s));
+        const bool finite = (__float_as_uint(norm) & 0x7f800000u) != 0x7f800000u;
+        coef = finite ? fminf(1.f, max_norm / (norm + 1e-6f)) : 0.f;
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            status[0] = __float_as_uint(norm);
+            status[1] = __float_as_uint(coef);
+            if (!finite) status[2] = status[2] + 1u;
+        }
+        if (!finite) return;                                                   // skipped for every group
+    }
+    // the table, once per thread: lane l of a wave keeps row l & 15 in two registers
+    const uint32_t lane = threadIdx.x & 63u, row = lane & (SD_OPTIM_MAX_GROUPS - 1u);
+    float row_step = tab.step[0], row_decay_mul = tab.decay_mul[0];
+#pragma unroll
+    for (uint32_t q = 1; q < SD_OPTIM_MAX_GROUPS; ++q) {
+        row_step = row == q ? tab.step[q] : row_step;
+        row_decay_mul = row == q ? tab.decay_mul[q] : row_decay_mul;
+    }
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    // the loop runs per WAVE (its bound is the wave's first group), so that the whole wave is live at the shuffles: a lane past the end
+    // takes part in them and skips the rest
+    for (int64_t base = (int64_t)blockIdx.x * 256 + (threadIdx.x - lane); base < n4; base += stride) {
+        const int64_t i = base + lane;
+        const bool live = i < n4;
+        const uint32_t k = live ? ids[i] & (SD_OPTIM_MAX_GROUPS - 1u) : 0u;    // a stray byte names a row of the table, never memory
+        const float step = __shfl(row_step, (int)k), decay_mul = __shfl(row_decay_mul, (int)k);   // lane k (< 16) holds row k
+        if (!live) continue;
+        float4 pp = reinterpret_cast<float4*>(p)[i];
+        const float4 gg = reinterpret_cast<const float4*>(g)[i];
+        float4 mm = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
+        float4 ee = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (EMA) ee = reinterpret_cast<float4*>(ema)[i];
+        const bool decay = (decay_bits >> k & 1u) != 0;
+        float* P = &pp.x; const float* G = &gg.x; float* Mo = &mm.x; float* V = &vv.x; float* E = &ee.x;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float gr = G[j] * gscale;
+            if (CLIP) gr *= coef;
+            if (decay) P[j] *= decay_mul;
+            Mo[j] = b1 * Mo[j] + (1.f - b1) * gr;
+            V[j] = b2 * V[j] + (1.f - b2) * gr * gr;
+            const float denom = sqrtf(V[j]) / bc2_sqrt + eps;
+            P[j] -= step * (Mo[j] / denom);
+            if (EMA) E[j] = ema_decay * E[j] + (1.f - ema_decay) * P[j];
+        }
+        reinterpret_cast<float4*>(p)[i] = pp;
+        reinterpret_cast<float4*>(m)[i] = mm;
+        reinterpret_cast<float4*>(v)[i] = vv;
+        if (EMA) reinterpret_cast<float4*>(ema)[i] = ee;
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // bf16 backbone (inference): weight cast, max-pool and head reading bf16 NHWC activations
 // ------------------------------------------------------------------------------------------
@@ -2462,6 +2537,55 @@ int sd_optim_step(float* param, const float* grad, float* exp_avg, float* exp_av
                   (uint32_t*)status);
 }
 
+int sd_optim_groups_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, int step, float lr, float beta1, float beta2,
+                         float eps, float grad_scale, float weight_decay, const uint8_t* group_ids, const float* lr_mul, const float* wd_mul,
+                         int ngroups, float max_norm, const void* partials, int npartials, float* ema, float ema_decay, void* status,
+                         sd_stream_t stream) {
+    SD_REQUIRE(param && grad && exp_avg && exp_avg_sq && n > 0 && n % 4 == 0 && step >= 1, SD_ERR_INVALID,
+               "sd_optim_groups_step: bad arguments (n %% 4 == 0, step >= 1)");
+    SD_REQUIRE(group_ids && lr_mul && wd_mul, SD_ERR_INVALID, "sd_optim_groups_step: needs group_ids (device, n / 4 bytes) and the host arrays lr_mul and wd_mul");
+    SD_REQUIRE(ngroups >= 1 && ngroups <= SD_OPTIM_MAX_GROUPS, SD_ERR_INVALID, "sd_optim_groups_step: ngroups must be in [1, %d] (got %d)",
+               SD_OPTIM_MAX_GROUPS, ngroups);
+    SD_REQUIRE(aligned16(param) && aligned16(grad) && aligned16(exp_avg) && aligned16(exp_avg_sq) && aligned16(ema), SD_ERR_ALIGN,
+               "sd_optim_groups_step: pointers must be 16-byte aligned");
+    SD_REQUIRE(weight_decay >= 0.f, SD_ERR_INVALID, "sd_optim_groups_step: weight_decay must be >= 0 (got %g)", (double)weight_decay);
+    SD_REQUIRE(max_norm >= 0.f, SD_ERR_INVALID, "sd_optim_groups_step: max_norm must be >= 0 (got %g; 0 = no clipping)", (double)max_norm);
+    SD_REQUIRE(ema_decay >= 0.f && ema_decay < 1.f, SD_ERR_INVALID, "sd_optim_groups_step: ema_decay must be in [0, 1) (got %g)", (double)ema_decay);
+    for (int k = 0; k < ngroups; ++k) {
+        SD_REQUIRE(std::isfinite(lr_mul[k]) && lr_mul[k] >= 0.f, SD_ERR_INVALID, "sd_optim_groups_step: lr_mul[%d] must be finite and >= 0 (got %g)", k,
+                   (double)lr_mul[k]);
+        SD_REQUIRE(std::isfinite(wd_mul[k]) && wd_mul[k] >= 0.f, SD_ERR_INVALID, "sd_optim_groups_step: wd_mul[%d] must be finite and >= 0 (got %g)", k,
+                   (double)wd_mul[k]);
+    }
+    const bool clip = max_norm > 0.f, avg = ema != nullptr;
+    if (clip) {
+        SD_REQUIRE(partials && npartials > 0 && status, SD_ERR_INVALID,
+                   "sd_optim_groups_step: max_norm > 0 needs the partials of sd_grad_sumsq (pointer and count) and the status block");
+        SD_REQUIRE(npartials == sumsq_blocks(n), SD_ERR_INVALID, "sd_optim_groups_step: %d partials, sd_grad_sumsq writes %d for n = %lld "
+                   "(sd_grad_sumsq_workspace_bytes(n) / 8)", npartials, sumsq_blocks(n), (long long)n);
+        SD_REQUIRE((reinterpret_cast<uintptr_t>(partials) & 7u) == 0 && (reinterpret_cast<uintptr_t>(status) & 3u) == 0, SD_ERR_ALIGN,
+                   "sd_optim_groups_step: partials must be 8-byte aligned, the status block 4-byte aligned");
+    }
+    const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
+    OptimGroupTable tab;
+    uint32_t decay_bits = 0;
+    for (int k = 0; k < SD_OPTIM_MAX_GROUPS; ++k) {                            // rows past ngroups: a group that does not move
+        const float lr_k = k < ngroups ? lr * lr_mul[k] : 0.f;
+        const bool decay = k < ngroups && weight_decay > 0.f && wd_mul[k] > 0.f;
+        // k_optim divides `lr / bc1` in fp32 on the device; this is the same division on the host.  The two agree bit for bit because both
+        // are IEEE correctly rounded: hipcc's default for fp32 division (this file is built without fast-math or a relaxed-division flag).
+        tab.step[k] = lr_k / (float)bc1;
+        tab.decay_mul[k] = decay ? (float)(1.0 - (double)lr_k * (double)weight_decay * (double)wd_mul[k]) : 1.f;
+        decay_bits |= (uint32_t)decay << k;
+    }
+    using kernel_t = decltype(&k_optim_groups<true, true>);
+    static const kernel_t variants[4] = {k_optim_groups<false, false>, k_optim_groups<true, false>, k_optim_groups<false, true>, k_optim_groups<true, true>};
+    const int64_t n4 = n / 4;
+    SD_RETURN_LAUNCH(variants[(int)clip | (int)avg << 1], ew_launch(n4).grid, 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n4, tab, decay_bits,
+                     beta1, beta2, eps, (float)sqrt(bc2), grad_scale, group_ids, max_norm, (const double*)partials, npartials, ema, ema_decay,
+                     (uint32_t*)status);
+}
+
 // ---- sd_nn_kernel_names: the plans above, printed (host only; the one place of this layer that formats) -------------------------------------
 namespace {
 struct Names {
@@ -2502,7 +2626,7 @@ static int check_desc(const char* what, const sd_nn_call_desc& d, int64_t M) {
     case SD_NN_STEM_BWD: case SD_NN_STEM_BWD_REDUCE: case SD_NN_STEM_BWD_APPLY:
         if (int e = check_stem_quad(what, stem_bwd_quad(d.H, d.W), !d.form)) return e;
         return check_mc(what, M, d.C);
-    case SD_NN_CAST: case SD_NN_ADAM: case SD_NN_GRAD_SUMSQ: case SD_NN_OPTIM:
+    case SD_NN_CAST: case SD_NN_ADAM: case SD_NN_GRAD_SUMSQ: case SD_NN_OPTIM: case SD_NN_OPTIM_GROUPS:
         SD_REQUIRE(M > 0 && M % 4 == 0, SD_ERR_INVALID, "%s: needs n > 0 and n %% 4 == 0 (got %lld)", what, (long long)M);
         return 0;
     case SD_NN_BN_FOLD: case SD_NN_HEAD_FWD: case SD_NN_HEAD_BWD: return 0;
@@ -2607,6 +2731,13 @@ const char* sd_nn_kernel_names(const sd_nn_call_desc* d) {
         const bool decay = d->flags & SD_NN_DECAY, clip = d->flags & SD_NN_CLIP, avg = d->flags & SD_NN_EMA;
         static const char* const tf[2] = {"false", "true"};
         out.add(decay || clip || avg ? NAME("k_optim<%s, %s, %s>", tf[decay], tf[clip], tf[avg]) : "k_adam", ew_launch(M / 4));
+        break;
+    }
+    case SD_NN_OPTIM_GROUPS: {                                                 // the step's two calls: sd_grad_sumsq (with clipping), sd_optim_groups_step
+        const bool clip = d->flags & SD_NN_CLIP, avg = d->flags & SD_NN_EMA;
+        static const char* const tf[2] = {"false", "true"};
+        if (clip) out.add("k_grad_sumsq", sumsq_blocks(M));
+        out.add(NAME("k_optim_groups<%s, %s>", tf[clip], tf[avg]), ew_launch(M / 4));
         break;
     }
     }

@@ -31,6 +31,7 @@ from ..utils import trace as T
 BN_EPS = 1e-5
 BN_MOMENTUM = 0.1
 FREEZE_STAGES = ("adpater", "down1", "down2", "down3", "down4")     # `Network.freeze(stages=N)`: the first N, in the order of parameters()
+OPTIM_STAGES = FREEZE_STAGES + ("fpn", "head")                      # `Network.optim_groups()`: the trunk, then up1 .. up4, then the head
 
 
 # ------------------------------------------------------------------------------------------
@@ -1142,6 +1143,29 @@ class Network(nn.Module):
         """(0, off): the flat-buffer element range of the frozen stages -- a prefix, because FREEZE_STAGES is the order of parameters();
         off is the start of the first trainable stage's first slot (slots as `_build_flat` lays them out: 8 floats each)."""
         return 0, sum((p.numel() + 7) // 8 * 8 for name in FREEZE_STAGES[:self.frozen_stages] for p in getattr(self, name).parameters())
+
+    def optim_groups(self):
+        """Parameter groups of the optimizer for per-stage learning rates (`TrainStep(lr_mults=...)`, sd_optim_groups_step):
+        (ids, groups).  `groups[k]` = (stage, decayed) for group id k: the stages of OPTIM_STAGES in flat-buffer order, each split into
+        its 4-D tensors (convolution weights: decayed, what `TrainStep.build_decay_mask` flags) and the rest (biases, BatchNorm weight /
+        bias) -- 14 groups, id = 2 * stage index + decayed.  `ids`: a uint8 host tensor with one byte per group of four floats of the flat
+        buffer (`flat_params.numel() // 4`; the layout of `_build_flat`, so it can be asked for before `.to(device)`); the padding of a
+        32-byte slot carries the id of its tensor."""
+        groups = [(stage, decayed) for stage in OPTIM_STAGES for decayed in (False, True)]
+        stage_of = {}
+        for k, stage in enumerate(OPTIM_STAGES):
+            for name in (("up1", "up2", "up3", "up4") if stage == "fpn" else (stage,)):
+                for p in getattr(self, name).parameters():
+                    stage_of[id(p)] = k
+        params = list(self.parameters())
+        ids = torch.zeros(sum((p.numel() + 7) // 8 * 8 for p in params) // 4, dtype=torch.uint8)
+        off = 0
+        for p in params:                                     # `_build_flat`: registration order, 8-float slots
+            slot = (p.numel() + 7) // 8 * 8
+            ids[off // 4:(off + slot) // 4] = 2 * stage_of[id(p)] + int(p.dim() == 4)
+            off += slot
+        assert self.flat_params is None or ids.numel() * 4 == self.flat_params.numel()
+        return ids, groups
 
     def grad_of(self, p):
         off, n = self._flat_off[id(p)]

@@ -98,12 +98,13 @@ class TrainStep:
     never writes them; their `exp_avg` / `exp_avg_sq` slots are zeroed at construction and again after `load_state_dict`."""
 
     def __init__(self, net, args, lr=None, betas=(0.9, 0.999), eps=1e-8, process_group=None, exchange=None, sync_bn=False,
-                 weight_decay=0.0, clip_grad_norm=0.0, ema_decay=0.0):
+                 weight_decay=0.0, clip_grad_norm=0.0, ema_decay=0.0, lr_mults=None):
         if net.flat_params is None:
             raise L.SdError("move the Network to the GPU before building TrainStep")
         if weight_decay < 0 or clip_grad_norm < 0 or not 0 <= ema_decay < 1:
             raise ValueError(f"weight_decay and clip_grad_norm must be >= 0 and ema_decay in [0, 1), got {weight_decay!r}, {clip_grad_norm!r}, "
                              f"{ema_decay!r}")
+        self.lr_mults = self.check_lr_mults(lr_mults)
         self.net, self.args = net, args
         self.lr = float(lr if lr is not None else getattr(args, "learning_rate", 1e-3))
         self.betas, self.eps = betas, eps
@@ -143,7 +144,7 @@ class TrainStep:
         # large-batch options of the optimizer (sd_optim_step): all zero = the plain sd_adam_step launch.  The status block
         # ([0] float norm, [1] float clip coefficient, [2] int32 skipped steps) lives on the device and is never read by the step.
         self.weight_decay, self.clip_grad_norm, self.ema_decay = float(weight_decay), float(clip_grad_norm), float(ema_decay)
-        self.decay_mask = self.ema = self._partials = None
+        self.decay_mask = self.ema = self._partials = self.group_ids = None
         self._status = torch.zeros(4, dtype=torch.int32, device=net.flat_params.device)
         self._status.view(torch.float32)[1] = 1.0
         self._configure_optim()
@@ -160,7 +161,15 @@ class TrainStep:
     def _configure_optim(self):
         """Buffers of the options that are on: the decay mask, the partials of the norm, the EMA copy (kept if it already exists)."""
         net = self.net
-        if self.weight_decay > 0 and self.decay_mask is None:
+        if self.lr_mults is not None and self.group_ids is None:
+            # per-stage rates (sd_optim_groups_step): the byte map on the device, the two tables on the host (they travel by value with
+            # every launch).  The map carries the decay bit too, so the mask is not built.
+            import ctypes as C
+            ids, groups = net.optim_groups()
+            self.group_ids, self.groups = ids.to(net.flat_params.device), groups
+            self._lr_mul = (C.c_float * len(groups))(*(self.lr_mults[stage] for stage, _ in groups))
+            self._wd_mul = (C.c_float * len(groups))(*(float(decayed) for _, decayed in groups))
+        if self.weight_decay > 0 and self.decay_mask is None and self.lr_mults is None:
             self.decay_mask = self.build_decay_mask(net)
         if self.clip_grad_norm > 0 and self._partials is None:
             self._partials = torch.empty(L.lib().sd_grad_sumsq_workspace_bytes(net.flat_grads.numel() - self.frozen_off) // 8, dtype=torch.float64,
@@ -182,6 +191,21 @@ class TrainStep:
                 assert off % 4 == 0 and n % 4 == 0, "a convolution weight must fill whole 16-byte groups"
                 mask[off // 4:(off + n) // 4] = 1
         return mask.to(net.flat_params.device)
+
+    @staticmethod
+    def check_lr_mults(lr_mults):
+        """`lr_mults` (None = off, or {stage of OPTIM_STAGES: multiplier}) -> None or the dict over every stage; a stage left out gets 1."""
+        if lr_mults is None:
+            return None
+        from .network import OPTIM_STAGES
+        unknown = sorted(set(lr_mults) - set(OPTIM_STAGES))
+        if unknown:
+            raise ValueError(f"lr_mults: unknown stage(s) {unknown}; the stages are {', '.join(OPTIM_STAGES)}")
+        out = {stage: float(lr_mults.get(stage, 1.0)) for stage in OPTIM_STAGES}
+        for stage, v in out.items():
+            if not 0 <= v < float("inf"):                    # (false for nan)
+                raise ValueError(f"lr_mults[{stage!r}] must be finite and >= 0, got {v!r}")
+        return out
 
     @property
     def plain_adam(self):
@@ -207,13 +231,23 @@ class TrainStep:
         return min(self.ema_decay, (1.0 + t) / (10.0 + t))
 
     def _optim_step(self):
-        """sd_grad_sumsq (only with clipping) + sd_optim_step on the step's stream; nothing is read back."""
+        """sd_grad_sumsq (only with clipping) + sd_optim_step (with `lr_mults`: sd_optim_groups_step) on the step's stream; nothing is read back."""
         net, lib, st = self.net, L.lib(), L.stream()
         off = self.frozen_off                        # floats; 4 bytes each, one mask byte per four
         n = net.flat_params.numel() - off
         clip = self.clip_grad_norm > 0
         if clip:
             L.check(lib.sd_grad_sumsq(net.flat_grads.data_ptr() + 4 * off, n, self._partials.data_ptr(), self._partials.numel() * 8, st), "sd_grad_sumsq")
+        if self.lr_mults is not None:                # per-stage rates: the same single launch, rate and decay looked up per 16-byte group
+            L.check(lib.sd_optim_groups_step(net.flat_params.data_ptr() + 4 * off, net.flat_grads.data_ptr() + 4 * off, self.exp_avg.data_ptr() + 4 * off,
+                                             self.exp_avg_sq.data_ptr() + 4 * off, n,
+                                             self.step_count, self.lr, self.betas[0], self.betas[1], self.eps, 1.0 / self.world, self.weight_decay,
+                                             self.group_ids.data_ptr() + off // 4, self._lr_mul, self._wd_mul, len(self.groups), self.clip_grad_norm,
+                                             self._partials.data_ptr() if clip else None, self._partials.numel() if clip else 0,
+                                             self.ema.data_ptr() + 4 * off if self.ema is not None else None,
+                                             self.ema_decay_at(self.step_count) if self.ema is not None else 0.0, self._status.data_ptr(), st),
+                    "sd_optim_groups_step")
+            return
         L.check(lib.sd_optim_step(net.flat_params.data_ptr() + 4 * off, net.flat_grads.data_ptr() + 4 * off, self.exp_avg.data_ptr() + 4 * off,
                                   self.exp_avg_sq.data_ptr() + 4 * off, n,
                                   self.step_count, self.lr, self.betas[0], self.betas[1], self.eps, 1.0 / self.world, self.weight_decay,
@@ -429,8 +463,8 @@ class TrainStep:
         T.pop()
         self.step_count += 1
         T.push("adam")
-        if self.plain_adam:
-            off = 4 * self.frozen_off                 # bytes: the frozen stages' prefix is not the optimizer's
+        if self.plain_adam and self.lr_mults is None:
+            off = 4 * self.frozen_off                # bytes: the frozen stages' prefix is not the optimizer's
             L.check(L.lib().sd_adam_step(net.flat_params.data_ptr() + off, net.flat_grads.data_ptr() + off, self.exp_avg.data_ptr() + off,
                                          self.exp_avg_sq.data_ptr() + off, net.flat_params.numel() - self.frozen_off, self.step_count, self.lr, self.betas[0],
                                          self.betas[1], self.eps, 1.0 / self.world, L.stream()), "sd_adam_step")
@@ -448,25 +482,91 @@ def train_step_kwargs(args):
     for name in ("weight_decay", "clip_grad_norm", "ema_decay"):          # optimizer options: passed when set (TrainStep's defaults are "off")
         if getattr(args, name, 0.0):
             kw[name] = float(getattr(args, name))
+    from ..utils.args import check_lr, stage_lr_mults
+    lr = check_lr(args)
+    mults = stage_lr_mults(lr.backbone_lr_mult, lr.lr_layer_decay)        # --backbone_lr_mult / --lr_layer_decay: None when both are 1
+    if mults is not None:
+        kw["lr_mults"] = mults
     return kw
 
 
-class StepLR:
-    """torch.optim.lr_scheduler.StepLR(step_size, gamma=0.1) over TrainStep.lr (trainer.py:54-56)."""
+class LRSchedule:
+    """The scalar learning rate of every optimizer step, written to `TrainStep.lr` (a kernel argument: nothing synchronises).
+    schedule "step": torch.optim.lr_scheduler.StepLR(step_size, gamma=0.1) over the epochs (trainer.py:54-56),
+    base * gamma ** (epoch // step_size), moved by `step()` once per epoch.  "cosine": with i = `TrainStep.step_count` before the step,
+    N = warmup_steps, T = total_steps: min_lr + (base - min_lr) * 0.5 * (1 + cos(pi * (i - N) / (T - N))) for N <= i < T, min_lr from T on.
+    Warm-up, either schedule: the value is multiplied by (i + 1) / N while i < N (the cosine term is `base` there).  Python floats.
+    Without warm-up and with "step" (`per_step` False) the rate changes in `step()` only, to StepLR's values, bit for bit; otherwise the
+    loop calls `apply()` before every optimizer step.  The curve is a function of `step_count`, which the optimizer state carries: a
+    resumed run continues on it."""
 
-    def __init__(self, step: TrainStep, step_size: int, gamma: float = 0.1):
+    NEW_KEYS = ("schedule", "warmup_steps", "total_steps", "min_lr")
+
+    def __init__(self, step: TrainStep, step_size: int, gamma: float = 0.1, schedule: str = "step", warmup_steps: int = 0, total_steps: int = 0,
+                 min_lr: float = 0.0):
         self.step_obj, self.step_size, self.gamma, self.epoch, self.base = step, max(int(step_size), 1), gamma, 0, step.lr
+        if schedule not in ("step", "cosine"):
+            raise ValueError(f"schedule must be 'step' or 'cosine', got {schedule!r}")
+        self.schedule, self.warmup_steps, self.total_steps, self.min_lr = schedule, int(warmup_steps), int(total_steps), float(min_lr)
+        if self.per_step and not 0 <= self.warmup_steps < self.total_steps:
+            raise ValueError(f"the warm-up ({self.warmup_steps} steps) must be shorter than the run ({self.total_steps} optimizer steps)")
+
+    @property
+    def per_step(self):
+        return self.schedule != "step" or self.warmup_steps > 0
+
+    def lr_at(self, i):
+        """The rate of the optimizer step that finds `step_count` == i."""
+        import math
+        n, t = self.warmup_steps, self.total_steps
+        if self.schedule == "step":
+            value = self.base * self.gamma ** (self.epoch // self.step_size)
+        elif i < n:
+            value = self.base
+        elif i < t:
+            value = self.min_lr + (self.base - self.min_lr) * 0.5 * (1 + math.cos(math.pi * (i - n) / (t - n)))
+        else:
+            value = self.min_lr
+        return value * ((i + 1) / n) if i < n else value
+
+    def _set(self):
+        # (per epoch the step schedule needs the epoch alone: `step_count` is read only where a per-step schedule is on)
+        self.step_obj.lr = self.lr_at(self.step_obj.step_count if self.per_step else 0)
+
+    def apply(self):
+        """Before an optimizer step: its rate into `TrainStep.lr`; returns it."""
+        self.step_obj.lr = self.lr_at(self.step_obj.step_count)
+        return self.step_obj.lr
 
     def step(self):
         self.epoch += 1
-        self.step_obj.lr = self.base * self.gamma ** (self.epoch // self.step_size)
+        self._set()
+
+    def describe(self):
+        text = f"StepLR every {self.step_size} epoch(s)" if self.schedule == "step" else \
+            f"cosine from {self.base:g} to {self.min_lr:g} over {self.total_steps} optimizer steps"
+        return text + (f", linear warm-up over the first {self.warmup_steps} steps" if self.warmup_steps else "")
 
     def state_dict(self):
-        return {"epoch": self.epoch, "base": self.base, "step_size": self.step_size, "gamma": self.gamma}
+        return {"epoch": self.epoch, "base": self.base, "step_size": self.step_size, "gamma": self.gamma, "schedule": self.schedule,
+                "warmup_steps": self.warmup_steps, "total_steps": self.total_steps, "min_lr": self.min_lr}
 
     def load_state_dict(self, state):
+        """A state from before the schedule options (today's four keys) stands for schedule "step" without warm-up.  The options belong
+        to the command line AND to the curve a run is on: a state whose schedule, warm-up, total or min_lr differ from this object's is
+        refused (the total only where a per-step schedule uses it)."""
+        was = (state.get("schedule", "step"), int(state.get("warmup_steps", 0)), float(state.get("min_lr", 0.0)))
+        now = (self.schedule, self.warmup_steps, self.min_lr)
+        total = int(state.get("total_steps", self.total_steps))
+        if was != now or (self.per_step and total != self.total_steps):
+            raise ValueError("resume: the checkpoint was written with --lr_schedule %s --warmup_steps %d --min_lr %g over %d optimizer steps, the "
+                             "command line gives --lr_schedule %s --warmup_steps %d --min_lr %g over %d: continue with the checkpoint's values "
+                             "(same --epochs / --steps / --batch_size)" % (was + (total,) + now + (self.total_steps,)))
         self.epoch, self.base, self.step_size, self.gamma = int(state["epoch"]), float(state["base"]), int(state["step_size"]), float(state["gamma"])
-        self.step_obj.lr = self.base * self.gamma ** (self.epoch // self.step_size)
+        self._set()
+
+
+StepLR = LRSchedule          # (the name this class had while it held the step schedule only)
 
 
 def shard_indices(n, batch, rank, world, seed):
@@ -497,11 +597,12 @@ class Trainer:
         import numpy as np
 
         from ..data import CropDataset, Encode
-        from ..utils.args import check_freeze, check_train
+        from ..utils.args import check_freeze, check_lr, check_train
         from .network import Network
         self.args = args
         check_train(args)                                              # --train_tiles, --keep_aspect, --aug_*: ranges, square inputs, --synthetic
         self.freeze = check_freeze(args)                               # --freeze_stages N, --freeze_bn
+        self.lr_options = check_lr(args)                               # --lr_schedule, --warmup_steps, --min_lr, --backbone_lr_mult, --lr_layer_decay
         if getattr(args, "use_amp", False) and not BF16_TRAINING:
             # the reference autocasts the training forward under --amp (trainer.py:115-121); silently training in fp32 under the
             # same flag would be a different experiment with the same name
@@ -516,12 +617,20 @@ class Trainer:
         self.net.freeze(*self.freeze)                                  # before the step is built: TrainStep reads the setting
         self.step = TrainStep(self.net, args, **train_step_kwargs(args))
         self.step.sync_parameters()
-        self.scheduler = StepLR(self.step, args.lr_step)
         self.encode = Encode(args)
         self.rng = np.random.default_rng(926354916 + self.rank)
         # directory data: decode on the host (PIL), resize + flips + normalisation for the whole batch on the GPU
         from ..data.augment import TrainAugmentation
         self.dataset = None if args.synthetic else CropDataset(args, args.train_dir, raw=True)
+        # --lr_schedule / --warmup_steps / --min_lr over the optimizer steps of the run: epochs x steps per epoch of this world size, as
+        # `batches()` counts them, or --steps when that is set and smaller
+        lr = self.lr_options
+        total = args.epochs * self.steps_per_epoch()
+        total = min(total, args.steps) if args.steps else total
+        if (lr.schedule != "step" or lr.warmup_steps) and lr.warmup_steps >= total:
+            raise ValueError(f"'warmup_steps' ({lr.warmup_steps}) should be less than the optimizer steps of the run ({total}: --epochs x steps per "
+                             "epoch, or --steps)")
+        self.scheduler = LRSchedule(self.step, args.lr_step, schedule=lr.schedule, warmup_steps=lr.warmup_steps, total_steps=total, min_lr=lr.min_lr)
         self.augment = TrainAugmentation(args)
         self.save_dir = Path("trainings") / f"{datetime.now():%Y-%m-%d_%H-%M-%S}"
         self.best_loss = float("inf")
@@ -539,6 +648,13 @@ class Trainer:
         self._writer = None
         if getattr(args, "resume", None):
             self.load_resume(args.resume)
+
+    def steps_per_epoch(self):
+        """Optimizer steps of one epoch on this world size, as `batches()` yields them (whole global batches: drop_last)."""
+        a, world = self.args, self.step.world
+        if a.synthetic:
+            return max(a.synthetic // (a.batch_size * world), 1)
+        return len(self.dataset) // (a.batch_size * world)
 
     def batches(self):
         a, B = self.args, self.args.batch_size
@@ -691,7 +807,8 @@ class Trainer:
                     "best": {k: getattr(self, k) for k in ("best_loss", "best_csi", "best_classif", "best_kp_reg")},
                     "augment_size": tuple(int(v) for v in self.augment.size), "torch_rng": torch.get_rng_state(),
                     "numpy_rng": self.rng.bit_generator.state, "save_dir": str(self.save_dir), "global_step": int(self.global_step),
-                    "freeze_stages": int(self.freeze[0]), "freeze_bn": bool(self.freeze[1])}, path)
+                    "freeze_stages": int(self.freeze[0]), "freeze_bn": bool(self.freeze[1]),
+                    "lr_mults": None if self.step.lr_mults is None else dict(self.step.lr_mults)}, path)
 
     def load_resume(self, path):
         from pathlib import Path
@@ -703,6 +820,12 @@ class Trainer:
         if kept != asked and self.rank == 0:            # the options belong to the run: the file's win over the command line's, and say so
             print("resume: optimizer options come from the checkpoint -- weight_decay %g, clip_grad_norm %g, ema_decay %g (the command line "
                   "asked for %g, %g, %g); a checkpoint written without them continues with all three off" % (kept + asked), flush=True)
+        was, now = state.get("lr_mults"), self.step.lr_mults
+        if was != now and self.rank == 0:               # the per-stage multipliers belong to the command line too, as the freeze does
+            def show(mults):
+                return "none" if mults is None else ", ".join(f"{stage} {v:g}" for stage, v in mults.items())
+            print(f"resume: the checkpoint was written with the per-stage learning-rate multipliers {show(was)}, this run continues with "
+                  f"{show(now)} (--backbone_lr_mult / --lr_layer_decay: the command line wins)", flush=True)
         self.scheduler.load_state_dict(state["scheduler"])
         self.start_epoch = int(state["epoch"]) + 1
         for k, v in state["best"].items():
@@ -751,7 +874,14 @@ class Trainer:
                   f"{st['refused']} left on the host path (budget {a.cache_images:g} GB)", flush=True)
 
     def _train(self):
-        steps = 0
+        per_step = self.scheduler.per_step
+        # --steps bounds this call's optimizer steps; under a per-step schedule, whose length it sets, the steps of the run (a resumed
+        # run then ends where the uninterrupted one does)
+        steps = self.step.step_count if per_step else 0
+        if self.rank == 0 and (per_step or self.step.lr_mults is not None):
+            mults = self.step.lr_mults
+            print(f"learning rate: {self.scheduler.describe()}" + ("" if mults is None else "; per-stage multipliers " +
+                  ", ".join(f"{stage} {v:g}" for stage, v in mults.items())), flush=True)
         if self.rank == 0 and not self.step.plain_adam:
             print(f"optimizer: weight decay {self.step.weight_decay:g} (convolution weights), gradient clipping at norm "
                   f"{self.step.clip_grad_norm:g}, weight EMA {self.step.ema_decay:g} (0 = off)", flush=True)
@@ -768,18 +898,22 @@ class Trainer:
         if self.cache is not None:
             self.prefill_cache()
         for epoch in range(self.start_epoch, self.args.epochs):
+            if self.args.steps and steps >= self.args.steps:           # (a resumed run whose bound was reached before it was saved: no step more)
+                break
             self.epoch = epoch
-            per_step, norms = [], []
+            losses, norms, rates = [], [], []
             clipping = self.step.clip_grad_norm > 0
             for images, targets in self.batches():
-                per_step.append(self.step(images, targets).clone())    # (total, hm, offset, embedding) on the device: no host sync in the loop
+                if per_step:
+                    rates.append(self.scheduler.apply())               # this step's rate: a host value handed to the launch, no sync
+                losses.append(self.step(images, targets).clone())      # (total, hm, offset, embedding) on the device: no host sync in the loop
                 if clipping:
                     norms.append(self.step.grad_norm.clone())          # the status block's norm of this step, read with the losses below
                 steps += 1
                 if self.args.steps and steps >= self.args.steps:
                     break
-            n = len(per_step)
-            rows = torch.stack(per_step).tolist() if n else []         # one host sync per epoch
+            n = len(losses)
+            rows = torch.stack(losses).tolist() if n else []           # one host sync per epoch
             norms = torch.stack(norms).tolist() if norms else []
             skipped = int(self.step.skipped_steps) if clipping else 0
             mean = [sum(r[k] for r in rows) / max(n, 1) for k in range(4)]
@@ -791,8 +925,11 @@ class Trainer:
                     writer.add_scalars("Loss/Train", dict(hm_loss=r[1], offset_loss=r[2], embedding_loss=r[3]), self.global_step)
                     if clipping:
                         writer.add_scalar("Gradient norm", norms[k], self.global_step)
+                    if per_step:                                       # warm-up / cosine: the rate of every step
+                        writer.add_scalar("Learning rate", rates[k], self.global_step)
                     self.global_step += self.args.batch_size
-                writer.add_scalar("Learning rate", self.step.lr, self.global_step)
+                if not per_step:
+                    writer.add_scalar("Learning rate", self.step.lr, self.global_step)
                 if clipping:
                     writer.add_scalar("Skipped steps", skipped, self.global_step)
                 writer.flush()

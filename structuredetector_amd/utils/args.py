@@ -181,6 +181,20 @@ _FLAGS = [
                             "running statistics and keep their weight / bias (FrozenBatchNorm2d in the backbone); the convolutions around "
                             "them train, the three FPN BatchNorms keep batch statistics. Needs --freeze_stages >= 1. Not consulted by "
                             "evaluate / detect.")),
+    (("--lr_schedule",), dict(type=str, default="step", choices=["step", "cosine"], help="Learning-rate schedule of train. step: the rate is "
+                              "divided by 10 every epochs / --lr_step epochs (the reference's StepLR). cosine: it follows half a cosine "
+                              "from --learning_rate to --min_lr over the optimizer steps of the run (epochs x steps per epoch, or --steps), "
+                              "set before every step; --lr_step is then ignored. Not consulted by evaluate / detect.")),
+    (("--warmup_steps",), dict(type=int, default=0, metavar="N", help="Linear warm-up, with either schedule: optimizer step i (from 0) of "
+                               "the first N runs at (i + 1) / N of the scheduled rate (under cosine the cosine starts after the warm-up). "
+                               "Must be less than the steps of the run. 0 = off.")),
+    (("--min_lr",), dict(type=float, default=0.0, help="Rate at which --lr_schedule cosine ends (0 .. --learning_rate).")),
+    (("--backbone_lr_mult",), dict(type=float, default=1.0, metavar="M", help="Fine-tuning: the pretrained trunk (stem, down1 .. down4) trains "
+                                   "at M times the learning rate of the FPN and the head (0 .. 10; Detectron2 / MMDetection's backbone "
+                                   "lr_mult), in the same single optimizer launch. A stage under --freeze_stages stays frozen. 1 = off.")),
+    (("--lr_layer_decay",), dict(type=float, default=1.0, metavar="D", help="Fine-tuning: layer-wise learning-rate decay over the trunk: "
+                                 "stage s (0 = stem .. 4 = down4) trains at M * D ** (5 - s) times the rate of the FPN and the head "
+                                 "(0 < D <= 1; M = --backbone_lr_mult). 1 = off.")),
 ]
 
 _POSITIVE = ["in_channels", "fpn_depth", "batch_size", "epochs", "learning_rate", "down_ratio", "max_objects", "max_parts"]
@@ -420,6 +434,46 @@ def check_freeze(args):
     if bn and n == 0:
         raise ValueError("'freeze_bn' needs --freeze_stages >= 1: a frozen stem BatchNorm behind a trainable stem is not built")
     return n, bool(bn)
+
+
+LrOptions = namedtuple("LrOptions", "schedule warmup_steps min_lr backbone_lr_mult lr_layer_decay")
+LR_SCHEDULES = ("step", "cosine")
+MAX_BACKBONE_LR_MULT = 10.0
+
+
+def check_lr(args):
+    """`--lr_schedule`, `--warmup_steps`, `--min_lr`, `--backbone_lr_mult`, `--lr_layer_decay` on a parsed namespace -> LrOptions, as
+    `train` checks them (model/trainer.py; `evaluate`, `detect` and `Predictor` never look at the flags).  A namespace from before the
+    flags gives the defaults (all off).  Every range test is false for NaN."""
+    schedule = getattr(args, "lr_schedule", "step") or "step"
+    if schedule not in LR_SCHEDULES:
+        raise ValueError(f"'lr_schedule' should be one of {', '.join(LR_SCHEDULES)}, not {schedule!r}")
+    n = getattr(args, "warmup_steps", 0)
+    n = 0 if n is None else n
+    if isinstance(n, bool) or not isinstance(n, int) or n < 0:
+        raise ValueError(f"'warmup_steps' should be an integer number of optimizer steps >= 0, not {n!r}")
+    base = float(getattr(args, "learning_rate", 1e-3))
+    min_lr = float(getattr(args, "min_lr", 0.0) or 0.0)
+    if not 0 <= min_lr <= base:
+        raise ValueError(f"'min_lr' should be in [0, {base:g}] (0 to --learning_rate), not {min_lr}")
+    mult = getattr(args, "backbone_lr_mult", 1.0)
+    mult = 1.0 if mult is None else float(mult)
+    if not 0 <= mult <= MAX_BACKBONE_LR_MULT:
+        raise ValueError(f"'backbone_lr_mult' should be in [0, {MAX_BACKBONE_LR_MULT:g}] (1 = off), not {mult}")
+    decay = getattr(args, "lr_layer_decay", 1.0)
+    decay = 1.0 if decay is None else float(decay)
+    if not 0 < decay <= 1:
+        raise ValueError(f"'lr_layer_decay' should be in ]0, 1] (1 = off), not {decay}")
+    return LrOptions(schedule, int(n), min_lr, mult, decay)
+
+
+def stage_lr_mults(mult, decay):
+    """{stage: multiplier} for `TrainStep(lr_mults=...)` from `--backbone_lr_mult` M and `--lr_layer_decay` D: trunk stage s (0 = stem ..
+    4 = down4) gets M * D ** (5 - s), the FPN and the head 1; None when M = D = 1 (off: the step's launches are those without the flags)."""
+    if mult == 1.0 and decay == 1.0:
+        return None
+    names = ("adpater", "down1", "down2", "down3", "down4")            # model/network.py FREEZE_STAGES
+    return dict({name: mult * decay ** (5 - s) for s, name in enumerate(names)}, fpn=1.0, head=1.0)
 
 
 def finalize(args):
