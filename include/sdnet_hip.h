@@ -1004,6 +1004,16 @@ int sd_optim_groups_step(float* param, const float* grad, float* exp_avg, float*
                          float max_norm, const void* partials, int npartials, float* ema, float ema_decay,
                          void* status, sd_stream_t stream);
 
+/* Gradient accumulation (`train --accum_steps K`): one streaming launch that folds a micro-batch's gradient into a running sum.
+ *   overwrite = 0: dst[i] = dst[i] + src[i] -- one fp32 add per element, no FMA, no rescaling: the bits of torch's `dst += src`;
+ *   overwrite = 1: dst[i] = src[i] (the first micro-batch of a group: no zero-fill pass before it).
+ * In place on dst, on the caller's stream; no workspace, no atomics.  The mean is taken later, by the optimizer's grad_scale
+ * (1 / (k * world) for a group of k micro-batches).  n floats, n % 4 == 0; n == 0 succeeds without a launch (and reads no pointer).  dst and
+ * src may be the same range; any other overlap is refused.
+ * Errors: SD_ERR_INVALID for n < 0, n % 4 != 0, a null pointer with n > 0, overwrite outside 0 / 1, partially overlapping ranges;
+ * SD_ERR_ALIGN for a pointer that is not 16-byte aligned. */
+int sd_grad_accum(float* dst, const float* src, int64_t n, int overwrite, sd_stream_t stream);
+
 /* What a call of the BatchNorm / pool / head / optimizer entry points above launches (host only; no pointer is read).  The descriptor names
  * the call: `op`, `form` (0 fp32, 1 bf16, 2 bf16 with a bf16 dx -- the stem tail's _dx16; SD_NN_CAST: 0 = to bf16, 1 = to fp32), the shape
  * (the map ops take B, H, W; the head B and H = HW; every other op M -- the optimizer and the casts their n), C, Co, relu, rows (the
@@ -1019,7 +1029,7 @@ int sd_optim_groups_step(float* param, const float* grad, float* exp_avg, float*
  * what the finish reads; offsets in floats), the caller-provided-rows forms " | slab=.. rows=..", the head backward and sd_grad_sumsq
  * " | ws_bytes=..".  "refused: <message>" for an unknown op and where one of the layer's shared shape checkers refuses the call: C (and M) of
  * the BatchNorm / column-sum / stem-tail family, relu outside 0..3, the map checks of the pool and upsample entry points, a bf16 stem tail on
- * an odd map, n % 4 != 0 of the casts and the optimizer.  The checks an entry point states for itself are not asked -- the head's limits on
+ * an odd map, n % 4 != 0 of the casts, the optimizer and sd_grad_accum (and its form outside 0 / 1).  The checks an entry point states for itself are not asked -- the head's limits on
  * C and Co (the query prints the launches of the form the descriptor names), rows <= 0, null pointers, workspace sizes.  A refusal sets
  * sd_last_error() of the calling thread, as the entry point's own would; an answered query leaves it alone.  The answer is made from the
  * plans, launch shapes and predicates the launchers themselves run.  Thread-local storage, valid until the next call on the thread. */
@@ -1033,7 +1043,10 @@ enum { SD_NN_BN_TRAIN_STATS, SD_NN_BN_FINALIZE_STATS, SD_NN_BN_STATS_FROM_SUMS, 
        SD_NN_BN_FROZEN_BWD = 25,
        /* sd_optim_groups_step: n in M; flags SD_NN_CLIP / SD_NN_EMA.  Prints the step's launches: k_grad_sumsq (with SD_NN_CLIP: the
         * sd_grad_sumsq call that feeds it), then k_optim_groups<clip, ema> */
-       SD_NN_OPTIM_GROUPS = 26 };
+       SD_NN_OPTIM_GROUPS = 26,
+       /* sd_grad_accum: n in M; form 0 = add (k_grad_accum<false>), 1 = overwrite (k_grad_accum<true>); n == 0: no launch, an empty answer.
+        * 27 is skipped as 24 is: tests/test_optim_groups_cpu.py asks about both as unknown ops, so they stay unused */
+       SD_NN_GRAD_ACCUM = 28 };
 #define SD_NN_SCRATCH (1u << 8)
 #define SD_NN_SUMS (1u << 9)
 #define SD_NN_DECAY (1u << 10)

@@ -256,6 +256,8 @@ _SIGNATURES = {
     # the same with per-group rates: ... weight_decay, group_ids (DEVICE bytes), lr_mul, wd_mul (HOST floats), ngroups, max_norm, ... as above
     "sd_optim_groups_step": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_float, c_float, c_float, c_float, c_float, c_float, c_vp,
                                      C.POINTER(c_float), C.POINTER(c_float), c_int, c_float, c_vp, c_int, c_vp, c_float, c_vp, c_vp]),
+    # gradient accumulation: dst, src, n floats, overwrite (0: dst += src, 1: dst = src), stream
+    "sd_grad_accum": (c_int, [c_vp, c_vp, c_i64, c_int, c_vp]),
     "sd_nn_kernel_names": (C.c_char_p, [C.POINTER(NnCallDesc)]),
     "sd_conv2d_kernel_name": (C.c_char_p, [c_vp, c_int]),
     "sd_set_option": (c_int, [C.c_char_p, c_int]),

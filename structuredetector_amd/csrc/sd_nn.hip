@@ -1330,6 +1330,22 @@ __global__ __launch_bounds__(256) void k_optim_groups(float* __restrict__ p, con
     }
 }
 
+// Gradient accumulation (sd_grad_accum): dst += src, or dst = src for the first micro-batch of a group (no zero-fill pass before it).
+// One fp32 add per element, written as four separate adds so that nothing can contract them; a streaming pass of 12 (8) bytes per float.
+// dst and src may be the SAME range (the entry point refuses any other overlap), so neither pointer is __restrict__.
+template <bool OVERWRITE>
+__global__ __launch_bounds__(256) void k_grad_accum(float* dst, const float* src, int64_t n4) {
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+        float4 s = reinterpret_cast<const float4*>(src)[i];
+        if (!OVERWRITE) {
+            const float4 d = reinterpret_cast<const float4*>(dst)[i];
+            s.x = d.x + s.x; s.y = d.y + s.y; s.z = d.z + s.z; s.w = d.w + s.w;
+        }
+        reinterpret_cast<float4*>(dst)[i] = s;
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // bf16 backbone (inference): weight cast, max-pool and head reading bf16 NHWC activations
 // ------------------------------------------------------------------------------------------
@@ -2586,6 +2602,26 @@ int sd_optim_groups_step(float* param, const float* grad, float* exp_avg, float*
                      (uint32_t*)status);
 }
 
+// the count and the mode of sd_grad_accum (shared with sd_nn_kernel_names)
+static int check_grad_accum(const char* what, int64_t n, int overwrite) {
+    SD_REQUIRE(n >= 0 && n % 4 == 0, SD_ERR_INVALID, "%s: needs n >= 0 and n %% 4 == 0 (got %lld)", what, (long long)n);
+    SD_REQUIRE(overwrite == 0 || overwrite == 1, SD_ERR_INVALID, "%s: overwrite must be 0 (add) or 1 (copy), got %d", what, overwrite);
+    return 0;
+}
+
+int sd_grad_accum(float* dst, const float* src, int64_t n, int overwrite, sd_stream_t stream) {
+    if (int e = check_grad_accum("sd_grad_accum", n, overwrite)) return e;
+    if (n == 0) return 0;                                                     // an empty range (a stage that is frozen whole): no launch
+    SD_REQUIRE(dst && src, SD_ERR_INVALID, "sd_grad_accum: null pointer");
+    SD_REQUIRE(aligned16(dst) && aligned16(src), SD_ERR_ALIGN, "sd_grad_accum: pointers must be 16-byte aligned");
+    const uintptr_t d = reinterpret_cast<uintptr_t>(dst), s = reinterpret_cast<uintptr_t>(src), bytes = (uintptr_t)n * sizeof(float);
+    SD_REQUIRE(d == s || d + bytes <= s || s + bytes <= d, SD_ERR_INVALID,
+               "sd_grad_accum: dst and src overlap without being the same range (in place on dst: every group of four is read, then written)");
+    const Launch l = ew_launch(n / 4);
+    if (overwrite) SD_RETURN_LAUNCH(k_grad_accum<true>, l.grid, 0, (hipStream_t)stream, dst, src, l.n);
+    SD_RETURN_LAUNCH(k_grad_accum<false>, l.grid, 0, (hipStream_t)stream, dst, src, l.n);
+}
+
 // ---- sd_nn_kernel_names: the plans above, printed (host only; the one place of this layer that formats) -------------------------------------
 namespace {
 struct Names {
@@ -2629,6 +2665,7 @@ static int check_desc(const char* what, const sd_nn_call_desc& d, int64_t M) {
     case SD_NN_CAST: case SD_NN_ADAM: case SD_NN_GRAD_SUMSQ: case SD_NN_OPTIM: case SD_NN_OPTIM_GROUPS:
         SD_REQUIRE(M > 0 && M % 4 == 0, SD_ERR_INVALID, "%s: needs n > 0 and n %% 4 == 0 (got %lld)", what, (long long)M);
         return 0;
+    case SD_NN_GRAD_ACCUM: return check_grad_accum(what, M, d.form);
     case SD_NN_BN_FOLD: case SD_NN_HEAD_FWD: case SD_NN_HEAD_BWD: return 0;
     }
     SD_REQUIRE(false, SD_ERR_INVALID, "%s: unknown op %d", what, d.op);
@@ -2740,6 +2777,9 @@ const char* sd_nn_kernel_names(const sd_nn_call_desc* d) {
         out.add(NAME("k_optim_groups<%s, %s>", tf[clip], tf[avg]), ew_launch(M / 4));
         break;
     }
+    case SD_NN_GRAD_ACCUM:                                                     // n == 0: no launch, an empty answer
+        if (M > 0) out.add(bf ? "k_grad_accum<true>" : "k_grad_accum<false>", ew_launch(M / 4));
+        break;
     }
 #undef NAME
     return line;

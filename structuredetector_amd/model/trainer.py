@@ -9,6 +9,8 @@ RCCL (`torch.distributed` backend "nccl") in five buckets that follow the backwa
 backward kernels; the mean is applied inside the fused Adam launch (grad_scale = 1/world).
 BatchNorm statistics are rank-local by default; `sync_bn=True` (`train --sync_bn`) computes them over the global batch
 (model/sync_bn.py) through the same process group as the gradient buckets.
+`accum_steps=K` (`train --accum_steps K`) makes one optimizer step of K consecutive batches: `sd_grad_accum` folds each bucket into an
+accumulator as the backward completes it, and the exchange and the optimizer run once per K calls (grad_scale = 1/(K world)).
 """
 from __future__ import annotations
 
@@ -95,12 +97,27 @@ class TrainStep:
     every alignment rule holds) -- the prefix is never written by decay, update or average.  Frozen BatchNorm weight / bias INSIDE the
     suffix (`freeze(bn=True)`) stay fixed because their gradient and their moments are zero, which makes the Adam update exactly zero and
     leaves them undecayed (the mask covers convolution weights only): `Network.freeze` zeroes those slots of `flat_grads` and the backward
-    never writes them; their `exp_avg` / `exp_avg_sq` slots are zeroed at construction and again after `load_state_dict`."""
+    never writes them; their `exp_avg` / `exp_avg_sq` slots are zeroed at construction and again after `load_state_dict`.
+
+    Gradient accumulation (`accum_steps=K`, `train --accum_steps K`, 1 .. 64; torch's accumulation loop): a call is one MICRO-step -- a
+    normal training forward (batch statistics of that batch, one momentum update of the running statistics, `sync_bn` all-reduces as
+    always), that batch's loss with its own normalisation, and the plain backward into `flat_grads`.  As each of the five parameter
+    groups completes, one `sd_grad_accum` launch on the step's stream folds it into `grad_acc` (micro-step 1 overwrites, 2 .. K - 1
+    add); on micro-step K the launch adds `grad_acc` into `flat_grads` instead, and only then does that group's gradient exchange start.
+    `flat_grads` then holds (((g1 + g2) + ...) + gK) in fp32, the gradients are exchanged once per optimizer step, and the optimizer
+    runs with grad_scale = 1 / (K * world): the mean of the micro-batch gradients (not the gradient of one large batch: every
+    micro-loss divides by its own batch's counts).  `updated` tells whether the call ran the optimizer; `step_count` counts optimizer
+    steps.  `flush()` ends a partial group (the end of an epoch) with the mean over what it holds.  With K = 1 nothing of this exists:
+    no buffer, no launch, the step as it always was.  Neither buffer is read or written below `frozen_off`."""
+
+    MAX_ACCUM_STEPS = 64
 
     def __init__(self, net, args, lr=None, betas=(0.9, 0.999), eps=1e-8, process_group=None, exchange=None, sync_bn=False,
-                 weight_decay=0.0, clip_grad_norm=0.0, ema_decay=0.0, lr_mults=None):
+                 weight_decay=0.0, clip_grad_norm=0.0, ema_decay=0.0, lr_mults=None, accum_steps=1):
         if net.flat_params is None:
             raise L.SdError("move the Network to the GPU before building TrainStep")
+        if isinstance(accum_steps, bool) or not isinstance(accum_steps, int) or not 1 <= accum_steps <= self.MAX_ACCUM_STEPS:
+            raise ValueError(f"accum_steps must be an integer in [1, {self.MAX_ACCUM_STEPS}], got {accum_steps!r}")
         if weight_decay < 0 or clip_grad_norm < 0 or not 0 <= ema_decay < 1:
             raise ValueError(f"weight_decay and clip_grad_norm must be >= 0 and ema_decay in [0, 1), got {weight_decay!r}, {clip_grad_norm!r}, "
                              f"{ema_decay!r}")
@@ -114,6 +131,11 @@ class TrainStep:
         self.frozen_off = net.frozen_range()[1] if self.frozen[0] else 0          # the optimizer's range starts behind the frozen stages
         self._zero_frozen_moments()
         self.step_count = 0
+        # gradient accumulation: the running sum of the group's micro-batch gradients (only with K > 1), the micro-steps taken in the
+        # current group, and whether the last call ran the optimizer
+        self.accum_steps = accum_steps
+        self.grad_acc = torch.zeros_like(net.flat_grads) if accum_steps > 1 else None
+        self.micro, self.updated = 0, False
         self.pg = process_group
         self.world = dist.get_world_size(process_group) if (dist.is_available() and dist.is_initialized()) else 1
         exchange = exchange or os.environ.get("SDNET_EXCHANGE", "torch")
@@ -230,7 +252,7 @@ class TrainStep:
         """Decay of update number t (1-based): min(ema_decay, (1 + t) / (10 + t)) -- the average follows the weights closely at first."""
         return min(self.ema_decay, (1.0 + t) / (10.0 + t))
 
-    def _optim_step(self):
+    def _optim_step(self, grad_scale):
         """sd_grad_sumsq (only with clipping) + sd_optim_step (with `lr_mults`: sd_optim_groups_step) on the step's stream; nothing is read back."""
         net, lib, st = self.net, L.lib(), L.stream()
         off = self.frozen_off                        # floats; 4 bytes each, one mask byte per four
@@ -241,7 +263,7 @@ class TrainStep:
         if self.lr_mults is not None:                # per-stage rates: the same single launch, rate and decay looked up per 16-byte group
             L.check(lib.sd_optim_groups_step(net.flat_params.data_ptr() + 4 * off, net.flat_grads.data_ptr() + 4 * off, self.exp_avg.data_ptr() + 4 * off,
                                              self.exp_avg_sq.data_ptr() + 4 * off, n,
-                                             self.step_count, self.lr, self.betas[0], self.betas[1], self.eps, 1.0 / self.world, self.weight_decay,
+                                             self.step_count, self.lr, self.betas[0], self.betas[1], self.eps, grad_scale, self.weight_decay,
                                              self.group_ids.data_ptr() + off // 4, self._lr_mul, self._wd_mul, len(self.groups), self.clip_grad_norm,
                                              self._partials.data_ptr() if clip else None, self._partials.numel() if clip else 0,
                                              self.ema.data_ptr() + 4 * off if self.ema is not None else None,
@@ -250,7 +272,7 @@ class TrainStep:
             return
         L.check(lib.sd_optim_step(net.flat_params.data_ptr() + 4 * off, net.flat_grads.data_ptr() + 4 * off, self.exp_avg.data_ptr() + 4 * off,
                                   self.exp_avg_sq.data_ptr() + 4 * off, n,
-                                  self.step_count, self.lr, self.betas[0], self.betas[1], self.eps, 1.0 / self.world, self.weight_decay,
+                                  self.step_count, self.lr, self.betas[0], self.betas[1], self.eps, grad_scale, self.weight_decay,
                                   self.decay_mask.data_ptr() + off // 4 if self.decay_mask is not None else None, self.clip_grad_norm,
                                   self._partials.data_ptr() if clip else None, self._partials.numel() if clip else 0,
                                   self.ema.data_ptr() + 4 * off if self.ema is not None else None,
@@ -431,10 +453,56 @@ class TrainStep:
         net.flat_grads.zero_()
         return out
 
-    def __call__(self, images, targets):
-        """One optimizer step; returns the loss vector [total, hm, offset, embedding] as a device tensor."""
+    def _accumulate(self, dst, src, name, overwrite):
+        """One `sd_grad_accum` launch over stage `name`'s range behind the frozen prefix, on the step's stream: dst (+)= src."""
+        lo, hi = self.ranges[name]
+        lo = max(lo, self.frozen_off)
+        if hi <= lo:                                     # a stage that is frozen whole: nothing of it is read or written
+            return
+        T.push("accum:" + name)
+        L.check(L.lib().sd_grad_accum(dst.data_ptr() + 4 * lo, src.data_ptr() + 4 * lo, hi - lo, int(overwrite), L.stream()), "sd_grad_accum")
+        T.pop()
+
+    def _accum_hook(self, exchange, last):
+        """on_stage of a micro-step under accumulation.  Not the last of its group: the stage's gradient goes into `grad_acc` (the first
+        micro-step overwrites, so the buffer is never zero-filled) and nothing else runs.  The last: `grad_acc` is added into
+        `flat_grads`, then the stage's exchange hook (if there is an exchange) starts -- every exchange orders its own stream behind
+        the stream this launch is on (torch's binding and both side-stream exchanges wait for the current stream when they are
+        called), so the all-reduce reads the total."""
+        net, acc, first = self.net, self.grad_acc, self.micro == 0
+
+        def on_stage(name):
+            if not last:
+                self._accumulate(acc, net.flat_grads, name, first)
+                return
+            self._accumulate(net.flat_grads, acc, name, False)
+            if exchange is not None:
+                exchange(name)
+        return on_stage
+
+    def _update(self, k):
+        """The optimizer launch on `flat_grads` = the sum over k micro-batches (and, after the exchange, over the ranks): one more
+        optimizer step, on the mean."""
         net = self.net
-        T.push("step")
+        grad_scale = 1.0 / (k * self.world)
+        self.step_count += 1
+        T.push("adam")
+        if self.plain_adam and self.lr_mults is None:
+            off = 4 * self.frozen_off                # bytes: the frozen stages' prefix is not the optimizer's
+            L.check(L.lib().sd_adam_step(net.flat_params.data_ptr() + off, net.flat_grads.data_ptr() + off, self.exp_avg.data_ptr() + off,
+                                         self.exp_avg_sq.data_ptr() + off, net.flat_params.numel() - self.frozen_off, self.step_count, self.lr, self.betas[0],
+                                         self.betas[1], self.eps, grad_scale, L.stream()), "sd_adam_step")
+        else:
+            self._optim_step(grad_scale)
+        T.pop()
+
+    def __call__(self, images, targets):
+        """One batch in, that batch's loss vector [total, hm, offset, embedding] out, as a device tensor.  Without accumulation this is
+        one optimizer step; with `accum_steps` = K it is one micro-step, and every K-th call runs the optimizer (`self.updated`)."""
+        net = self.net
+        accumulate = self.accum_steps > 1
+        last = self.micro + 1 >= self.accum_steps                  # this call completes its group (always, without accumulation)
+        T.push("step" if last else "accum")
         T.push("forward")
         if self.bn_sync is None:
             head, tape = net.forward_train(images, amp=self.amp)
@@ -447,7 +515,7 @@ class TrainStep:
         desc, keep, out8 = loss_forward(head, targets, cfg)
         dhead = loss_backward(desc, out8, self.one, tuple(head.shape))
         T.pop()
-        on_stage, finish = self._exchange_hooks()
+        on_stage, finish = self._exchange_hooks() if last else (None, None)      # gradients travel once per optimizer step
         if on_stage is not None and T.enabled():
             launch = on_stage
 
@@ -455,25 +523,44 @@ class TrainStep:
                 T.push("bucket:" + name)
                 launch(name)
                 T.pop()
+        if accumulate:
+            on_stage = self._accum_hook(on_stage, last)
         T.push("backward")
         net.backward_from(tape, dhead, on_stage)
         T.pop()
-        T.push("exchange:join")
-        finish()
-        T.pop()
-        self.step_count += 1
-        T.push("adam")
-        if self.plain_adam and self.lr_mults is None:
-            off = 4 * self.frozen_off                # bytes: the frozen stages' prefix is not the optimizer's
-            L.check(L.lib().sd_adam_step(net.flat_params.data_ptr() + off, net.flat_grads.data_ptr() + off, self.exp_avg.data_ptr() + off,
-                                         self.exp_avg_sq.data_ptr() + off, net.flat_params.numel() - self.frozen_off, self.step_count, self.lr, self.betas[0],
-                                         self.betas[1], self.eps, 1.0 / self.world, L.stream()), "sd_adam_step")
-        else:
-            self._optim_step()
-        T.pop()
+        self.micro += 1
+        if last:
+            T.push("exchange:join")
+            finish()
+            T.pop()
+            self._update(self.micro)
+            self.micro = 0
+        self.updated = last
         T.pop()
         self.stats.update(out8[1], out8[2], out8[3])
         return out8[:4]
+
+    def flush(self):
+        """Ends a partial group (0 < `micro` < K: the batches of an epoch ran out) with what it holds: `flat_grads` takes the sum from
+        `grad_acc`, the gradients are exchanged and the optimizer runs on the mean over `micro` micro-batches.  Nothing happens, and
+        nothing is launched, at `micro` == 0.  Under data parallelism every rank must call it at the same point (it exchanges).
+        Returns whether an optimizer step ran."""
+        if self.micro == 0:
+            return False
+        T.push("step")
+        on_stage, finish = self._exchange_hooks()
+        for name in self.STAGES:                                   # the order in which a backward would have completed them
+            self._accumulate(self.net.flat_grads, self.grad_acc, name, True)
+            if on_stage is not None:
+                on_stage(name)
+        T.push("exchange:join")
+        finish()
+        T.pop()
+        self._update(self.micro)
+        self.micro = 0
+        self.updated = True
+        T.pop()
+        return True
 
 
 def train_step_kwargs(args):
@@ -482,11 +569,14 @@ def train_step_kwargs(args):
     for name in ("weight_decay", "clip_grad_norm", "ema_decay"):          # optimizer options: passed when set (TrainStep's defaults are "off")
         if getattr(args, name, 0.0):
             kw[name] = float(getattr(args, name))
-    from ..utils.args import check_lr, stage_lr_mults
+    from ..utils.args import check_accum, check_lr, stage_lr_mults
     lr = check_lr(args)
     mults = stage_lr_mults(lr.backbone_lr_mult, lr.lr_layer_decay)        # --backbone_lr_mult / --lr_layer_decay: None when both are 1
     if mults is not None:
         kw["lr_mults"] = mults
+    accum = check_accum(args)                                             # --accum_steps: passed when > 1
+    if accum > 1:
+        kw["accum_steps"] = accum
     return kw
 
 
@@ -625,8 +715,8 @@ class Trainer:
         # --lr_schedule / --warmup_steps / --min_lr over the optimizer steps of the run: epochs x steps per epoch of this world size, as
         # `batches()` counts them, or --steps when that is set and smaller
         lr = self.lr_options
-        total = args.epochs * self.steps_per_epoch()
-        total = min(total, args.steps) if args.steps else total
+        from ..utils.args import run_updates
+        total = run_updates(args.epochs, self.batches_per_epoch(), self.step.accum_steps, args.steps)
         if (lr.schedule != "step" or lr.warmup_steps) and lr.warmup_steps >= total:
             raise ValueError(f"'warmup_steps' ({lr.warmup_steps}) should be less than the optimizer steps of the run ({total}: --epochs x steps per "
                              "epoch, or --steps)")
@@ -649,12 +739,17 @@ class Trainer:
         if getattr(args, "resume", None):
             self.load_resume(args.resume)
 
-    def steps_per_epoch(self):
-        """Optimizer steps of one epoch on this world size, as `batches()` yields them (whole global batches: drop_last)."""
+    def batches_per_epoch(self):
+        """Batches of one epoch on this world size, as `batches()` yields them (whole global batches: drop_last)."""
         a, world = self.args, self.step.world
         if a.synthetic:
             return max(a.synthetic // (a.batch_size * world), 1)
         return len(self.dataset) // (a.batch_size * world)
+
+    def steps_per_epoch(self):
+        """Optimizer steps of one epoch: its batches, or with `--accum_steps K` ceil(batches / K) (the last group is flushed)."""
+        from ..utils.args import updates_per_epoch
+        return updates_per_epoch(self.batches_per_epoch(), self.step.accum_steps)
 
     def batches(self):
         a, B = self.args, self.args.batch_size
@@ -885,6 +980,11 @@ class Trainer:
         if self.rank == 0 and not self.step.plain_adam:
             print(f"optimizer: weight decay {self.step.weight_decay:g} (convolution weights), gradient clipping at norm "
                   f"{self.step.clip_grad_norm:g}, weight EMA {self.step.ema_decay:g} (0 = off)", flush=True)
+        if self.rank == 0 and self.step.accum_steps > 1:
+            k, b, world = self.step.accum_steps, self.args.batch_size, self.step.world
+            print(f"gradient accumulation: {k} batches per optimizer step, effective batch {k * b * world} ({k} x {b} x {world} rank(s)); "
+                  "--steps, warm-up and schedule count optimizer steps; BatchNorm statistics are per micro-batch -- consider --freeze_bn "
+                  "or --sync_bn for small batches", flush=True)
         if self.rank == 0 and self.freeze[0]:
             from .network import FREEZE_STAGES
             print(f"frozen trunk stages: {', '.join(FREEZE_STAGES[:self.freeze[0]])} (no gradient, BatchNorm on the stored statistics)"
@@ -901,17 +1001,34 @@ class Trainer:
             if self.args.steps and steps >= self.args.steps:           # (a resumed run whose bound was reached before it was saved: no step more)
                 break
             self.epoch = epoch
-            losses, norms, rates = [], [], []
+            losses, norms, rates, sizes = [], [], [], []               # one entry per optimizer step
             clipping = self.step.clip_grad_norm > 0
+            group, micro, rate = None, 0, None                         # the open accumulation group: its loss sum (device), its batches, its rate
+
+            def close_group():
+                # the optimizer just ran: the group's mean loss (a device value, like the norm: read with the epoch's one copy below)
+                losses.append(group if micro == 1 else group / micro)
+                if per_step:
+                    rates.append(rate)
+                if clipping:
+                    norms.append(self.step.grad_norm.clone())          # the status block's norm of this step
+                sizes.append(micro)
+
             for images, targets in self.batches():
                 if per_step:
-                    rates.append(self.scheduler.apply())               # this step's rate: a host value handed to the launch, no sync
-                losses.append(self.step(images, targets).clone())      # (total, hm, offset, embedding) on the device: no host sync in the loop
-                if clipping:
-                    norms.append(self.step.grad_norm.clone())          # the status block's norm of this step, read with the losses below
+                    rate = self.scheduler.apply()                      # a function of step_count: the same value for every batch of a group; no sync
+                loss = self.step(images, targets)                      # (total, hm, offset, embedding) on the device: no host sync in the loop
+                group = loss.clone() if group is None else group + loss
+                micro += 1
+                if self.step.updated:
+                    close_group()
+                    group, micro = None, 0
+                    steps += 1
+                    if self.args.steps and steps >= self.args.steps:
+                        break
+            if self.step.flush():                                      # --accum_steps: the epoch's last, partial group -- an epoch ends at an update
+                close_group()
                 steps += 1
-                if self.args.steps and steps >= self.args.steps:
-                    break
             n = len(losses)
             rows = torch.stack(losses).tolist() if n else []           # one host sync per epoch
             norms = torch.stack(norms).tolist() if norms else []
@@ -927,14 +1044,14 @@ class Trainer:
                         writer.add_scalar("Gradient norm", norms[k], self.global_step)
                     if per_step:                                       # warm-up / cosine: the rate of every step
                         writer.add_scalar("Learning rate", rates[k], self.global_step)
-                    self.global_step += self.args.batch_size
+                    self.global_step += self.args.batch_size * sizes[k]        # images of the step: its batches (one without --accum_steps)
                 if not per_step:
                     writer.add_scalar("Learning rate", self.step.lr, self.global_step)
                 if clipping:
                     writer.add_scalar("Skipped steps", skipped, self.global_step)
                 writer.flush()
                 print(f"epoch {epoch}: total {mean[0]:.5f} hm {mean[1]:.5f} offset {mean[2]:.5f} embedding {mean[3]:.5f} "
-                      f"lr {self.step.lr:g} ({n} steps)", flush=True)
+                      f"lr {self.step.lr:g} ({n} steps" + (f", {sum(sizes)} batches)" if self.step.accum_steps > 1 else ")"), flush=True)
             if epoch % 2 == 0:                                         # trainer.py:98-99
                 self.valid()
             self.scheduler.step()

@@ -195,6 +195,11 @@ _FLAGS = [
     (("--lr_layer_decay",), dict(type=float, default=1.0, metavar="D", help="Fine-tuning: layer-wise learning-rate decay over the trunk: "
                                  "stage s (0 = stem .. 4 = down4) trains at M * D ** (5 - s) times the rate of the FPN and the head "
                                  "(0 < D <= 1; M = --backbone_lr_mult). 1 = off.")),
+    (("--accum_steps",), dict(type=int, default=1, metavar="K", help="Gradient accumulation of train: one optimizer step uses the mean "
+                              "gradient of K consecutive batches on each rank (1 .. 64), so the effective batch is K x --batch_size x ranks. "
+                              "--steps, --warmup_steps, the cosine length and the EMA count optimizer steps, not batches. BatchNorm statistics "
+                              "stay per batch (consider --freeze_bn or --sync_bn for small batches). Not consulted by evaluate / detect. "
+                              "1 = off.")),
 ]
 
 _POSITIVE = ["in_channels", "fpn_depth", "batch_size", "epochs", "learning_rate", "down_ratio", "max_objects", "max_parts"]
@@ -474,6 +479,34 @@ def stage_lr_mults(mult, decay):
         return None
     names = ("adpater", "down1", "down2", "down3", "down4")            # model/network.py FREEZE_STAGES
     return dict({name: mult * decay ** (5 - s) for s, name in enumerate(names)}, fpn=1.0, head=1.0)
+
+
+MAX_ACCUM_STEPS = 64
+
+
+def check_accum(args):
+    """`--accum_steps` on a parsed namespace -> K, the batches per optimizer step, as `train` checks it (model/trainer.py; `evaluate`,
+    `detect` and `Predictor` never look at the flag).  A namespace from before the flag gives 1 (off).  K is an integer in 1 .. 64."""
+    k = getattr(args, "accum_steps", 1)
+    k = 1 if k is None else k
+    if isinstance(k, bool) or not isinstance(k, int):
+        raise ValueError(f"'accum_steps' should be an integer number of batches per optimizer step, not {k!r}")
+    if not 1 <= k <= MAX_ACCUM_STEPS:
+        raise ValueError(f"'accum_steps' should be in [1, {MAX_ACCUM_STEPS}] (1 = off), not {k}")
+    return k
+
+
+def updates_per_epoch(batches, accum_steps):
+    """Optimizer steps of an epoch of `batches` batches under `--accum_steps K`: ceil(batches / K) -- the last group of an epoch is
+    flushed with the batches it has (`TrainStep.flush`), so every epoch ends at an update boundary."""
+    return -(-int(batches) // int(accum_steps))
+
+
+def run_updates(epochs, batches, accum_steps=1, steps=0):
+    """Optimizer steps of a whole run, the length of the cosine schedule: epochs x `updates_per_epoch`, or `--steps` (which counts
+    optimizer steps too) when that is set and smaller."""
+    total = int(epochs) * updates_per_epoch(batches, accum_steps)
+    return min(total, int(steps)) if steps else total
 
 
 def finalize(args):
