@@ -1004,6 +1004,60 @@ int sd_optim_groups_step(float* param, const float* grad, float* exp_avg, float*
                          float max_norm, const void* partials, int npartials, float* ema, float ema_decay,
                          void* status, sd_stream_t stream);
 
+/* The other two update rules over the same flat buffers (`train --optimizer sgd|lamb`; no reference counterpart, no accuracy claim: the
+ * deliverable is the update rule).  Both take the GROUPS form of sd_optim_groups_step: group_ids (device, one byte per group of four floats,
+ * id & 15), the HOST tables lr_mul / wd_mul by value (ngroups entries; a uniform table = no per-stage rates), grad_scale, max_norm +
+ * partials / npartials from sd_grad_sumsq (the GLOBAL norm; a non-finite norm skips the whole step: no launch of the step writes anything
+ * but status[0..2], and status[2] goes up by one), ema / ema_decay, status -- same meaning, same refusals and codes.  Group k steps with
+ * lr_k = lr * lr_mul[k] and wd_k = weight_decay * wd_mul[k] (one float multiply each).
+ *
+ * sd_sgd_step: torch.optim.SGD with dampening 0, one launch (sd_optim_groups_step's traffic minus one moment buffer), per element
+ *     d = grad * grad_scale * clip_coef;  if wd_k > 0: d += wd_k * p
+ *     if momentum > 0: buf = momentum * buf + d;  d = nesterov ? d + momentum * buf : buf
+ *     p -= lr_k * d;  ema = ema_decay * ema + (1 - ema_decay) * p_new
+ *   The decay is COUPLED L2 (it enters the gradient, and through it the momentum), as in torch.optim.SGD -- not AdamW's decoupled decay of
+ *   sd_optim_step.  A zero buffer at step 1 gives torch's buf = d.  momentum == 0: the buffer is neither read nor written and may be NULL.
+ *   Errors, beyond the groups form's: SD_ERR_INVALID for momentum outside [0, 1), nesterov outside 0 / 1 or with momentum == 0, a null
+ *   buffer with momentum > 0.
+ *
+ * sd_lamb_step: LAMB (You et al. 2020, Alg. 2), two launches, per parameter SLOT s and its groups k
+ *     g = grad * grad_scale * clip_coef;  m = beta1 * m + (1 - beta1) * g;  v = beta2 * v + (1 - beta2) * g * g
+ *     u = (m / (1 - beta1^t)) / (sqrt(v) / sqrt(1 - beta2^t) + eps) + wd_k * p
+ *     phi_s = adapt_s and |p_s| > 0 and |u_s| > 0 and both finite ? |p_s| / |u_s| : 1      (L2 norms over the slot, p BEFORE the update)
+ *     p -= lr_k * phi_s * u;  ema as above
+ *   Which slots adapt is the table's bit, set by the caller; `Network.optim_slots()` sets it for 4-D tensors (convolution weights) whatever
+ *   weight_decay is, and leaves biases and BatchNorm weight / bias at phi = 1.  (apex FusedLAMB ties the exclusion to weight_decay == 0
+ *   instead: there a run without decay adapts nothing unless use_nvlamb is set.)  lr_mul[k] == 0: moments and EMA update, p does not move.
+ *   The slot table is static per network: sd_lamb_table_build (host only, no HIP call) lays it out from the slot ranges -- the slots must
+ *   tile [0, n) in order, each a positive multiple of 8 floats -- and reports its size and the block count; with table == NULL it only
+ *   reports.  The caller uploads the table once (16-byte aligned) and hands it to every step with nslots and nblocks.  Layout (int32):
+ *   [nslots][4] = {lo / 4, hi / 4, first block, block count | adapt << 30}, then [nblocks] slot indices.  A slot of f floats gets
+ *   min(ceil(f / SD_LAMB_BLOCK_FLOATS), SD_LAMB_MAX_SLOT_BLOCKS) blocks; no block works on two slots.  The kernels clamp every value they
+ *   read from the table into [0, n / 4) and [0, nblocks): a wrong table gives wrong numbers, never an access outside the buffers.
+ *   Pass 1 (k_lamb_moments) writes m, v and one fp64 (sum p^2, sum u^2) pair per block into the workspace (sd_lamb_workspace_bytes(nblocks),
+ *   8-byte aligned, every pair written: earlier contents do not matter); pass 2 (k_lamb_apply): every block finishes its slot's pairs itself,
+ *   recomputes u from the stored m, v and p, and applies.  Both norms are fp64 sums in a fixed order (per thread in index order, lanes by
+ *   shuffle, waves in order, a slot's blocks in block order), no atomics: the same inputs give the same bits on every run and every rank.
+ *   Errors, beyond the groups form's: SD_ERR_INVALID for step < 1, null moments / table / workspace, nslots outside [1, SD_LAMB_MAX_SLOTS],
+ *   nblocks outside [nslots, SD_LAMB_MAX_SLOT_BLOCKS * nslots], n >= 2^33; SD_ERR_ALIGN; SD_ERR_WORKSPACE for a workspace (or, in the
+ *   builder, a table) that is too small.  sd_lamb_table_build: SD_ERR_INVALID for null arrays, a slot count out of range, slots that do
+ *   not tile [0, n). */
+#define SD_LAMB_BLOCK_FLOATS 4096
+#define SD_LAMB_MAX_SLOT_BLOCKS 128
+#define SD_LAMB_MAX_SLOTS 65536
+int sd_sgd_step(float* param, const float* grad, float* momentum_buf, int64_t n, float lr, float momentum, int nesterov,
+                float grad_scale, float weight_decay, const uint8_t* group_ids, const float* lr_mul, const float* wd_mul,
+                int ngroups, float max_norm, const void* partials, int npartials, float* ema, float ema_decay,
+                void* status, sd_stream_t stream);
+size_t sd_lamb_workspace_bytes(int nblocks);
+int sd_lamb_table_build(const int64_t* slot_lo, const int64_t* slot_hi, const uint8_t* adapt, int nslots, int64_t n,
+                        void* table, size_t table_bytes, size_t* bytes_needed, int* nblocks);
+int sd_lamb_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, int step,
+                 float lr, float beta1, float beta2, float eps, float grad_scale, float weight_decay,
+                 const uint8_t* group_ids, const float* lr_mul, const float* wd_mul, int ngroups,
+                 float max_norm, const void* partials, int npartials, float* ema, float ema_decay, void* status,
+                 const void* table, int nslots, int nblocks, void* workspace, size_t workspace_bytes, sd_stream_t stream);
+
 /* Gradient accumulation (`train --accum_steps K`): one streaming launch that folds a micro-batch's gradient into a running sum.
  *   overwrite = 0: dst[i] = dst[i] + src[i] -- one fp32 add per element, no FMA, no rescaling: the bits of torch's `dst += src`;
  *   overwrite = 1: dst[i] = src[i] (the first micro-batch of a group: no zero-fill pass before it).
@@ -1021,7 +1075,7 @@ int sd_grad_accum(float* dst, const float* src, int64_t n, int overwrite, sd_str
  *     bn_apply: x, y, residual        bn_bwd / bn_bwd_apply: dy, x, dx, g_out (bn_bwd_reduce: dy, x)        bn_relu_maxpool_fwd: x, y_pool, idx
  *     head_fwd: x, w, y               head_bwd: x, dy
  * SD_NN_SCRATCH = scratch given, SD_NN_SUMS = the split form that stops at the fp64 sums (sd_bn_train_sums, sd_bn_stats_sums, sd_bn_bwd_sums,
- * sd_bn_bwd_reduce, sd_maxpool_bn_relu_bwd_reduce), SD_NN_DECAY / _CLIP / _EMA = the options of sd_optim_step (_CLIP / _EMA: of sd_optim_groups_step too).  pool_fwd_pair: the option
+ * sd_bn_bwd_reduce, sd_maxpool_bn_relu_bwd_reduce), SD_NN_DECAY / _CLIP / _EMA = the options of sd_optim_step (_CLIP / _EMA: of sd_optim_groups_step, sd_sgd_step and sd_lamb_step too).  pool_fwd_pair: the option
  * of that name as the call would see it.
  * sd_nn_kernel_names prints the launches in order, separated by "; ", each as "<kernel as rocprofv3 prints it, without sd::> grid=X block=256
  * lds=N" (N: dynamic bytes), a wide head's own kernels as "head_wide_fwd" / "head_wide_wgrad" / "head_wide_dgrad" (their grids need the
@@ -1046,7 +1100,13 @@ enum { SD_NN_BN_TRAIN_STATS, SD_NN_BN_FINALIZE_STATS, SD_NN_BN_STATS_FROM_SUMS, 
        SD_NN_OPTIM_GROUPS = 26,
        /* sd_grad_accum: n in M; form 0 = add (k_grad_accum<false>), 1 = overwrite (k_grad_accum<true>); n == 0: no launch, an empty answer.
         * 27 is skipped as 24 is: tests/test_optim_groups_cpu.py asks about both as unknown ops, so they stay unused */
-       SD_NN_GRAD_ACCUM = 28 };
+       SD_NN_GRAD_ACCUM = 28,
+       /* 29 is skipped as 24 and 27 are (tests/test_accum_cpu.py asks about it as an unknown op).  The step's calls of the two other
+        * optimizers, n in M, flags SD_NN_CLIP / SD_NN_EMA as for SD_NN_OPTIM_GROUPS; both print k_grad_sumsq first with SD_NN_CLIP.
+        * sd_sgd_step: form 0 = no momentum, 1 = momentum, 2 = Nesterov; k_sgd<form, clip, ema> on sd_adam_step's grid.
+        * sd_lamb_step: the grid depends on the slot table, so the query takes sd_lamb_table_build's block count in `rows` (rows < 1 is
+        * refused): k_lamb_moments<clip> and k_lamb_apply<clip, ema>, both grid = rows, then " | ws_bytes=.." (sd_lamb_workspace_bytes(rows)) */
+       SD_NN_SGD = 30, SD_NN_LAMB = 31 };
 #define SD_NN_SCRATCH (1u << 8)
 #define SD_NN_SUMS (1u << 9)
 #define SD_NN_DECAY (1u << 10)

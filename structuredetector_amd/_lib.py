@@ -256,6 +256,17 @@ _SIGNATURES = {
     # the same with per-group rates: ... weight_decay, group_ids (DEVICE bytes), lr_mul, wd_mul (HOST floats), ngroups, max_norm, ... as above
     "sd_optim_groups_step": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_float, c_float, c_float, c_float, c_float, c_float, c_vp,
                                      C.POINTER(c_float), C.POINTER(c_float), c_int, c_float, c_vp, c_int, c_vp, c_float, c_vp, c_vp]),
+    # SGD with momentum: param, grad, momentum_buf, n, lr, momentum, nesterov, grad_scale, weight_decay, then the groups form as above
+    "sd_sgd_step": (c_int, [c_vp, c_vp, c_vp, c_i64, c_float, c_float, c_int, c_float, c_float, c_vp, C.POINTER(c_float), C.POINTER(c_float), c_int,
+                            c_float, c_vp, c_int, c_vp, c_float, c_vp, c_vp]),
+    # LAMB: sd_optim_groups_step's arguments, then table (DEVICE), nslots, nblocks, workspace, workspace_bytes, stream; the table's host builder:
+    # slot_lo, slot_hi (HOST int64), adapt (HOST bytes), nslots, n, table (HOST, or null = size query), table_bytes, &bytes_needed, &nblocks
+    "sd_lamb_workspace_bytes": (c_size, [c_int]),
+    "sd_lamb_table_build": (c_int, [C.POINTER(c_i64), C.POINTER(c_i64), C.POINTER(C.c_ubyte), c_int, c_i64, c_vp, c_size, C.POINTER(c_size),
+                                    C.POINTER(c_int)]),
+    "sd_lamb_step": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_float, c_float, c_float, c_float, c_float, c_float, c_vp,
+                             C.POINTER(c_float), C.POINTER(c_float), c_int, c_float, c_vp, c_int, c_vp, c_float, c_vp, c_vp, c_int, c_int, c_vp, c_size,
+                             c_vp]),
     # gradient accumulation: dst, src, n floats, overwrite (0: dst += src, 1: dst = src), stream
     "sd_grad_accum": (c_int, [c_vp, c_vp, c_i64, c_int, c_vp]),
     "sd_nn_kernel_names": (C.c_char_p, [C.POINTER(NnCallDesc)]),

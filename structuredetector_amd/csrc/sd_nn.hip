@@ -1330,6 +1330,217 @@ __global__ __launch_bounds__(256) void k_optim_groups(float* __restrict__ p, con
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// The other two update rules over the same flat buffers, both in the groups form (id byte per group of four, rates and decays by value):
+// SGD with momentum (sd_sgd_step, torch.optim.SGD with dampening 0) and LAMB (sd_lamb_step, You et al. 2020, Alg. 2).
+// ------------------------------------------------------------------------------------------
+// k_optim's finish of the sd_grad_sumsq partials: the norm, the coefficient, and whether the step runs at all.  `writer`: this thread
+// records them in the status block (one thread of one launch of a step).
+__device__ __forceinline__ float clip_coef_256(const double* __restrict__ partial, int npartial, float gscale, float max_norm, double* red4,
+                                               uint32_t* __restrict__ status, bool writer, bool& finite) {
+    double s = 0.0;
+    for (int k = threadIdx.x; k < npartial; k += 256) s += partial[k];
+    s = block_sum_256(s, red4);
+    const float norm = (float)(fabs((double)gscale) * sqrt(s));
+    finite = (__float_as_uint(norm) & 0x7f800000u) != 0x7f800000u;
+    const float coef = finite ? fminf(1.f, max_norm / (norm + 1e-6f)) : 0.f;
+    if (writer) {
+        status[0] = __float_as_uint(norm);
+        status[1] = __float_as_uint(coef);
+        if (!finite) status[2] = status[2] + 1u;
+    }
+    return coef;
+}
+
+struct SgdGroupTable {
+    float lr[SD_OPTIM_MAX_GROUPS];             // lr * lr_mul[k]
+    float wd[SD_OPTIM_MAX_GROUPS];             // weight_decay * wd_mul[k]; 0: the group is not decayed
+};
+
+// SGD: k_optim_groups's pass (the table in registers, picked by a wave shuffle) with one state buffer, or none.
+// MOM 0: no momentum, `buf` is never touched; 1: momentum; 2: Nesterov momentum.
+template <int MOM, bool CLIP, bool EMA>
+__global__ __launch_bounds__(256) void k_sgd(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, int64_t n4,
+                                              const SgdGroupTable tab, float momentum, float gscale, const uint8_t* __restrict__ ids,
+                                              float max_norm, const double* __restrict__ partial, int npartial, float* __restrict__ ema,
+                                              float ema_decay, uint32_t* __restrict__ status) {
+    float coef = 1.f;
+    if (CLIP) {
+        __shared__ double red[4];
+        bool finite;
+        coef = clip_coef_256(partial, npartial, gscale, max_norm, red, status, blockIdx.x == 0 && threadIdx.x == 0, finite);
+        if (!finite) return;                                                   // skipped for every group: nothing is written
+    }
+    const uint32_t lane = threadIdx.x & 63u, row = lane & (SD_OPTIM_MAX_GROUPS - 1u);
+    float row_lr = tab.lr[0], row_wd = tab.wd[0];
+#pragma unroll
+    for (uint32_t q = 1; q < SD_OPTIM_MAX_GROUPS; ++q) {
+        row_lr = row == q ? tab.lr[q] : row_lr;
+        row_wd = row == q ? tab.wd[q] : row_wd;
+    }
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t base = (int64_t)blockIdx.x * 256 + (threadIdx.x - lane); base < n4; base += stride) {     // per wave, as in k_optim_groups
+        const int64_t i = base + lane;
+        const bool live = i < n4;
+        const uint32_t k = live ? ids[i] & (SD_OPTIM_MAX_GROUPS - 1u) : 0u;
+        const float lr = __shfl(row_lr, (int)k), wd = __shfl(row_wd, (int)k);
+        if (!live) continue;
+        float4 pp = reinterpret_cast<float4*>(p)[i];
+        const float4 gg = reinterpret_cast<const float4*>(g)[i];
+        float4 bb = make_float4(0.f, 0.f, 0.f, 0.f), ee = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (MOM) bb = reinterpret_cast<float4*>(buf)[i];
+        if (EMA) ee = reinterpret_cast<float4*>(ema)[i];
+        float* P = &pp.x; const float* G = &gg.x; float* Bu = &bb.x; float* E = &ee.x;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float d = G[j] * gscale;
+            if (CLIP) d *= coef;
+            if (wd > 0.f) d += wd * P[j];                            // coupled L2: grad.add(param, alpha=weight_decay)
+            if (MOM) {
+                Bu[j] = momentum * Bu[j] + d;                        // buf.mul_(momentum).add_(grad); a zero buffer at step 1: buf = grad
+                d = MOM == 2 ? d + momentum * Bu[j] : Bu[j];
+            }
+            P[j] -= lr * d;
+            if (EMA) E[j] = ema_decay * E[j] + (1.f - ema_decay) * P[j];
+        }
+        reinterpret_cast<float4*>(p)[i] = pp;
+        if (MOM) reinterpret_cast<float4*>(buf)[i] = bb;
+        if (EMA) reinterpret_cast<float4*>(ema)[i] = ee;
+    }
+}
+
+// LAMB.  The slot table (sd_lamb_table_build; int32, on the device): [nslots] rows {lo4, hi4, first block, block count | adapt << 30} in
+// float4 units, then [nblocks] slot indices, one per block.  A block works on ONE slot: block b of a slot's nb blocks takes the float4s
+// lo4 + (r * nb + b) * 1024 + [0, 1024) for r = 0, 1, .. (one "sweep" of the slot per r), a thread its four of each 1024 in index order.
+// Every value read from the table is clamped before it is used as an index: a wrong table gives wrong numbers inside [0, n4) and
+// inside the workspace, never an access outside them.
+constexpr int LAMB_BLOCK_F4 = SD_LAMB_BLOCK_FLOATS / 4;
+static_assert(LAMB_BLOCK_F4 == 4 * 256 && SD_LAMB_MAX_SLOT_BLOCKS <= 256, "k_lamb_*: four float4 a thread and a sweep, a slot's partials in one read a thread");
+
+struct LambSlot { int64_t lo4, hi4; int first, nb, bi; bool adapt; };
+
+__device__ __forceinline__ LambSlot lamb_slot(const int32_t* __restrict__ table, int nslots, int nblocks, int64_t n4) {
+    const int s = min(max(table[4 * (int64_t)nslots + blockIdx.x], 0), nslots - 1);
+    const int4 e = reinterpret_cast<const int4*>(table)[s];
+    LambSlot o;
+    o.lo4 = min((int64_t)max(e.x, 0), n4);
+    o.hi4 = min(max((int64_t)e.y, o.lo4), n4);
+    o.first = min(max(e.z, 0), nblocks - 1);
+    o.nb = min(min(max(e.w & 0xffff, 1), SD_LAMB_MAX_SLOT_BLOCKS), nblocks - o.first);
+    o.bi = min(max((int)blockIdx.x - o.first, 0), o.nb - 1);
+    o.adapt = (e.w >> 30 & 1) != 0;
+    return o;
+}
+
+// u of one element from the moments as they are stored; no multiply-add is left to contraction, so that both passes get the same bits
+__device__ __forceinline__ float lamb_u(float m, float v, float p, float bc1, float bc2_sqrt, float eps, float wd) {
+    const float u = (m / bc1) / (sqrtf(v) / bc2_sqrt + eps);
+    return wd > 0.f ? __builtin_fmaf(wd, p, u) : u;
+}
+
+// pass 1: the moments, and this block's fp64 (sum p^2, sum u^2) into workspace[2 * block], [2 * block + 1]
+template <bool CLIP>
+__global__ __launch_bounds__(256) void k_lamb_moments(const float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                       float* __restrict__ v, int64_t n4, const SgdGroupTable tab, float b1, float b2, float eps,
+                                                       float bc1, float bc2_sqrt, float gscale, const uint8_t* __restrict__ ids, float max_norm,
+                                                       const double* __restrict__ partial, int npartial, uint32_t* __restrict__ status,
+                                                       const int32_t* __restrict__ table, int nslots, int nblocks, double* __restrict__ ws) {
+    __shared__ double red[4], red_p[4], red_u[4];
+    __shared__ float s_wd[SD_OPTIM_MAX_GROUPS];
+    float coef = 1.f;
+    if (CLIP) {
+        bool finite;
+        coef = clip_coef_256(partial, npartial, gscale, max_norm, red, status, blockIdx.x == 0 && threadIdx.x == 0, finite);
+        if (!finite) return;
+    }
+    if (threadIdx.x < SD_OPTIM_MAX_GROUPS) s_wd[threadIdx.x] = tab.wd[threadIdx.x];
+    __syncthreads();
+    const LambSlot sl = lamb_slot(table, nslots, nblocks, n4);
+    double sp = 0.0, su = 0.0;
+    for (int64_t base = sl.lo4 + (int64_t)sl.bi * LAMB_BLOCK_F4; base < sl.hi4; base += (int64_t)sl.nb * LAMB_BLOCK_F4) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int64_t i = base + q * 256 + threadIdx.x;
+            if (i >= sl.hi4) continue;
+            const float4 pp = reinterpret_cast<const float4*>(p)[i], gg = reinterpret_cast<const float4*>(g)[i];
+            float4 mm = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
+            const float wd = s_wd[ids[i] & (SD_OPTIM_MAX_GROUPS - 1u)];
+            const float* P = &pp.x; const float* G = &gg.x; float* Mo = &mm.x; float* V = &vv.x;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float gr = G[j] * gscale;
+                if (CLIP) gr *= coef;
+                Mo[j] = b1 * Mo[j] + (1.f - b1) * gr;
+                V[j] = b2 * V[j] + (1.f - b2) * gr * gr;
+                const float u = lamb_u(Mo[j], V[j], P[j], bc1, bc2_sqrt, eps, wd);
+                sp += (double)P[j] * P[j];
+                su += (double)u * u;
+            }
+            reinterpret_cast<float4*>(m)[i] = mm;
+            reinterpret_cast<float4*>(v)[i] = vv;
+        }
+    }
+    sp = block_sum_256(sp, red_p);
+    su = block_sum_256(su, red_u);
+    if (threadIdx.x == 0) {
+        ws[2 * (int64_t)blockIdx.x] = sp;
+        ws[2 * (int64_t)blockIdx.x + 1] = su;
+    }
+}
+
+// pass 2: every block finishes its slot's partials itself (at most SD_LAMB_MAX_SLOT_BLOCKS pairs, in block order), recomputes u from the
+// stored moments and the parameter it is about to change, and applies p -= lr_k * phi * u
+template <bool CLIP, bool EMA>
+__global__ __launch_bounds__(256) void k_lamb_apply(float* __restrict__ p, const float* __restrict__ m, const float* __restrict__ v, int64_t n4,
+                                                     const SgdGroupTable tab, float eps, float bc1, float bc2_sqrt, float gscale,
+                                                     const uint8_t* __restrict__ ids, float max_norm, const double* __restrict__ partial,
+                                                     int npartial, float* __restrict__ ema, float ema_decay, const int32_t* __restrict__ table,
+                                                     int nslots, int nblocks, const double* __restrict__ ws) {
+    __shared__ double red[4], red_p[4], red_u[4];
+    __shared__ float s_lr[SD_OPTIM_MAX_GROUPS], s_wd[SD_OPTIM_MAX_GROUPS];
+    if (CLIP) {
+        bool finite;
+        clip_coef_256(partial, npartial, gscale, max_norm, red, nullptr, false, finite);   // pass 1 recorded the status; the same partials, the same verdict
+        if (!finite) return;
+    }
+    if (threadIdx.x < SD_OPTIM_MAX_GROUPS) {
+        s_lr[threadIdx.x] = tab.lr[threadIdx.x];
+        s_wd[threadIdx.x] = tab.wd[threadIdx.x];
+    }
+    const LambSlot sl = lamb_slot(table, nslots, nblocks, n4);
+    double sp = 0.0, su = 0.0;
+    for (int k = threadIdx.x; k < sl.nb; k += 256) {
+        sp += ws[2 * (int64_t)(sl.first + k)];
+        su += ws[2 * (int64_t)(sl.first + k) + 1];
+    }
+    sp = block_sum_256(sp, red_p);                                             // (its barrier also publishes s_lr / s_wd)
+    su = block_sum_256(su, red_u);
+    const double norm_p = sqrt(sp), norm_u = sqrt(su);
+    const bool trust = sl.adapt && norm_p > 0.0 && norm_u > 0.0 && norm_p < HUGE_VAL && norm_u < HUGE_VAL;   // (false for nan)
+    const float phi = trust ? (float)(norm_p / norm_u) : 1.f;
+    for (int64_t base = sl.lo4 + (int64_t)sl.bi * LAMB_BLOCK_F4; base < sl.hi4; base += (int64_t)sl.nb * LAMB_BLOCK_F4) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int64_t i = base + q * 256 + threadIdx.x;
+            if (i >= sl.hi4) continue;
+            float4 pp = reinterpret_cast<float4*>(p)[i];
+            const float4 mm = reinterpret_cast<const float4*>(m)[i], vv = reinterpret_cast<const float4*>(v)[i];
+            float4 ee = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (EMA) ee = reinterpret_cast<float4*>(ema)[i];
+            const uint32_t k = ids[i] & (SD_OPTIM_MAX_GROUPS - 1u);
+            const float step = s_lr[k] * phi, wd = s_wd[k];
+            float* P = &pp.x; const float* Mo = &mm.x; const float* V = &vv.x; float* E = &ee.x;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                P[j] -= step * lamb_u(Mo[j], V[j], P[j], bc1, bc2_sqrt, eps, wd);
+                if (EMA) E[j] = ema_decay * E[j] + (1.f - ema_decay) * P[j];
+            }
+            reinterpret_cast<float4*>(p)[i] = pp;
+            if (EMA) reinterpret_cast<float4*>(ema)[i] = ee;
+        }
+    }
+}
+
 // Gradient accumulation (sd_grad_accum): dst += src, or dst = src for the first micro-batch of a group (no zero-fill pass before it).
 // One fp32 add per element, written as four separate adds so that nothing can contract them; a streaming pass of 12 (8) bytes per float.
 // dst and src may be the SAME range (the entry point refuses any other overlap), so neither pointer is __restrict__.
@@ -2602,6 +2813,137 @@ int sd_optim_groups_step(float* param, const float* grad, float* exp_avg, float*
                      (uint32_t*)status);
 }
 
+// ---- sd_sgd_step / sd_lamb_step: the groups form's checks, said once for both (sd_optim_groups_step's refusals and codes) ----------------
+static int check_groups_form(const char* what, const void* param, const void* grad, int64_t n, float weight_decay, const uint8_t* group_ids,
+                             const float* lr_mul, const float* wd_mul, int ngroups, float max_norm, const void* partials, int npartials,
+                             const void* ema, float ema_decay, const void* status) {
+    SD_REQUIRE(param && grad && n > 0 && n % 4 == 0, SD_ERR_INVALID, "%s: bad arguments (null param / grad, n > 0, n %% 4 == 0)", what);
+    SD_REQUIRE(group_ids && lr_mul && wd_mul, SD_ERR_INVALID, "%s: needs group_ids (device, n / 4 bytes) and the host arrays lr_mul and wd_mul", what);
+    SD_REQUIRE(ngroups >= 1 && ngroups <= SD_OPTIM_MAX_GROUPS, SD_ERR_INVALID, "%s: ngroups must be in [1, %d] (got %d)", what, SD_OPTIM_MAX_GROUPS, ngroups);
+    SD_REQUIRE(aligned16(param) && aligned16(grad) && aligned16(ema), SD_ERR_ALIGN, "%s: pointers must be 16-byte aligned", what);
+    SD_REQUIRE(weight_decay >= 0.f && std::isfinite(weight_decay), SD_ERR_INVALID, "%s: weight_decay must be finite and >= 0 (got %g)", what, (double)weight_decay);
+    SD_REQUIRE(max_norm >= 0.f, SD_ERR_INVALID, "%s: max_norm must be >= 0 (got %g; 0 = no clipping)", what, (double)max_norm);
+    SD_REQUIRE(ema_decay >= 0.f && ema_decay < 1.f, SD_ERR_INVALID, "%s: ema_decay must be in [0, 1) (got %g)", what, (double)ema_decay);
+    for (int k = 0; k < ngroups; ++k) {
+        SD_REQUIRE(std::isfinite(lr_mul[k]) && lr_mul[k] >= 0.f, SD_ERR_INVALID, "%s: lr_mul[%d] must be finite and >= 0 (got %g)", what, k, (double)lr_mul[k]);
+        SD_REQUIRE(std::isfinite(wd_mul[k]) && wd_mul[k] >= 0.f, SD_ERR_INVALID, "%s: wd_mul[%d] must be finite and >= 0 (got %g)", what, k, (double)wd_mul[k]);
+    }
+    if (max_norm > 0.f) {
+        SD_REQUIRE(partials && npartials > 0 && status, SD_ERR_INVALID,
+                   "%s: max_norm > 0 needs the partials of sd_grad_sumsq (pointer and count) and the status block", what);
+        SD_REQUIRE(npartials == sumsq_blocks(n), SD_ERR_INVALID, "%s: %d partials, sd_grad_sumsq writes %d for n = %lld "
+                   "(sd_grad_sumsq_workspace_bytes(n) / 8)", what, npartials, sumsq_blocks(n), (long long)n);
+        SD_REQUIRE((reinterpret_cast<uintptr_t>(partials) & 7u) == 0 && (reinterpret_cast<uintptr_t>(status) & 3u) == 0, SD_ERR_ALIGN,
+                   "%s: partials must be 8-byte aligned, the status block 4-byte aligned", what);
+    }
+    return 0;
+}
+
+// lr_k = lr * lr_mul[k], wd_k = weight_decay * wd_mul[k] (one fp32 multiply each); rows past ngroups: a group that does not move
+static SgdGroupTable rate_table(float lr, float weight_decay, const float* lr_mul, const float* wd_mul, int ngroups) {
+    SgdGroupTable tab;
+    for (int k = 0; k < SD_OPTIM_MAX_GROUPS; ++k) {
+        tab.lr[k] = k < ngroups ? lr * lr_mul[k] : 0.f;
+        tab.wd[k] = k < ngroups ? weight_decay * wd_mul[k] : 0.f;
+    }
+    return tab;
+}
+
+int sd_sgd_step(float* param, const float* grad, float* momentum_buf, int64_t n, float lr, float momentum, int nesterov, float grad_scale,
+                float weight_decay, const uint8_t* group_ids, const float* lr_mul, const float* wd_mul, int ngroups, float max_norm,
+                const void* partials, int npartials, float* ema, float ema_decay, void* status, sd_stream_t stream) {
+    if (int e = check_groups_form("sd_sgd_step", param, grad, n, weight_decay, group_ids, lr_mul, wd_mul, ngroups, max_norm, partials, npartials, ema,
+                                  ema_decay, status)) return e;
+    SD_REQUIRE(momentum >= 0.f && momentum < 1.f, SD_ERR_INVALID, "sd_sgd_step: momentum must be in [0, 1) (got %g)", (double)momentum);
+    SD_REQUIRE(nesterov == 0 || nesterov == 1, SD_ERR_INVALID, "sd_sgd_step: nesterov must be 0 or 1 (got %d)", nesterov);
+    SD_REQUIRE(!nesterov || momentum > 0.f, SD_ERR_INVALID, "sd_sgd_step: nesterov needs momentum > 0");
+    SD_REQUIRE(momentum == 0.f || momentum_buf, SD_ERR_INVALID, "sd_sgd_step: momentum > 0 needs the momentum buffer (bad arguments)");
+    SD_REQUIRE(aligned16(momentum_buf), SD_ERR_ALIGN, "sd_sgd_step: pointers must be 16-byte aligned");
+    const SgdGroupTable tab = rate_table(lr, weight_decay, lr_mul, wd_mul, ngroups);
+    const bool clip = max_norm > 0.f, avg = ema != nullptr;
+    const int64_t n4 = n / 4;
+    const int mom = momentum == 0.f ? 0 : nesterov ? 2 : 1;                    // one kernel per (momentum kind, clipping, EMA)
+    using kernel_t = decltype(&k_sgd<0, true, true>);
+    static const kernel_t variants[12] = {k_sgd<0, false, false>, k_sgd<0, true, false>, k_sgd<0, false, true>, k_sgd<0, true, true>,
+                                          k_sgd<1, false, false>, k_sgd<1, true, false>, k_sgd<1, false, true>, k_sgd<1, true, true>,
+                                          k_sgd<2, false, false>, k_sgd<2, true, false>, k_sgd<2, false, true>, k_sgd<2, true, true>};
+    SD_RETURN_LAUNCH(variants[4 * mom | (int)clip | (int)avg << 1], ew_launch(n4).grid, 0, (hipStream_t)stream, param, grad, mom ? momentum_buf : nullptr, n4,
+                     tab, momentum, grad_scale, group_ids, max_norm, (const double*)partials, npartials, ema, ema_decay, (uint32_t*)status);
+}
+
+// ---- LAMB's slot table (host only) -------------------------------------------------------------------------------------------------------
+static int lamb_slot_blocks(int64_t floats) { return (int)std::min<int64_t>(cdiv(floats, SD_LAMB_BLOCK_FLOATS), SD_LAMB_MAX_SLOT_BLOCKS); }
+
+size_t sd_lamb_workspace_bytes(int nblocks) { return nblocks > 0 ? (size_t)nblocks * 2 * sizeof(double) : 0; }
+
+int sd_lamb_table_build(const int64_t* slot_lo, const int64_t* slot_hi, const uint8_t* adapt, int nslots, int64_t n, void* table, size_t table_bytes,
+                        size_t* bytes_needed, int* nblocks) {
+    SD_REQUIRE(slot_lo && slot_hi && adapt, SD_ERR_INVALID, "sd_lamb_table_build: needs the host arrays slot_lo, slot_hi and adapt");
+    SD_REQUIRE(nslots >= 1 && nslots <= SD_LAMB_MAX_SLOTS, SD_ERR_INVALID, "sd_lamb_table_build: nslots must be in [1, %d] (got %d)", SD_LAMB_MAX_SLOTS, nslots);
+    SD_REQUIRE(n > 0 && n % 8 == 0 && n / 4 <= INT32_MAX, SD_ERR_INVALID, "sd_lamb_table_build: n must be a positive multiple of 8 below 2^33 (got %lld)",
+               (long long)n);
+    int64_t at = 0, blocks = 0;
+    for (int s = 0; s < nslots; ++s) {
+        SD_REQUIRE(slot_lo[s] == at && slot_hi[s] > slot_lo[s] && slot_hi[s] <= n && slot_hi[s] % 8 == 0, SD_ERR_INVALID,
+                   "sd_lamb_table_build: slot %d is [%lld, %lld): the slots must tile [0, n) in order, each a positive multiple of 8 floats "
+                   "(expected it to start at %lld; n = %lld)", s, (long long)slot_lo[s], (long long)slot_hi[s], (long long)at, (long long)n);
+        at = slot_hi[s];
+        blocks += lamb_slot_blocks(slot_hi[s] - slot_lo[s]);
+    }
+    SD_REQUIRE(at == n, SD_ERR_INVALID, "sd_lamb_table_build: the slots end at %lld, the buffer at n = %lld", (long long)at, (long long)n);
+    const size_t need = ((size_t)nslots * 4 + (size_t)blocks) * sizeof(int32_t);
+    if (bytes_needed) *bytes_needed = need;
+    if (nblocks) *nblocks = (int)blocks;
+    if (!table) return 0;                                                      // the size query
+    SD_REQUIRE(table_bytes >= need, SD_ERR_WORKSPACE, "sd_lamb_table_build: the table needs %zu bytes (got %zu)", need, table_bytes);
+    int32_t* rows = (int32_t*)table;
+    int32_t* owner = rows + 4 * (size_t)nslots;
+    int first = 0;
+    for (int s = 0; s < nslots; ++s) {
+        const int nb = lamb_slot_blocks(slot_hi[s] - slot_lo[s]);
+        rows[4 * s] = (int32_t)(slot_lo[s] / 4);
+        rows[4 * s + 1] = (int32_t)(slot_hi[s] / 4);
+        rows[4 * s + 2] = first;
+        rows[4 * s + 3] = nb | (adapt[s] ? 1 << 30 : 0);
+        for (int b = 0; b < nb; ++b) owner[first + b] = s;
+        first += nb;
+    }
+    return 0;
+}
+
+int sd_lamb_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, int step, float lr, float beta1, float beta2,
+                 float eps, float grad_scale, float weight_decay, const uint8_t* group_ids, const float* lr_mul, const float* wd_mul, int ngroups,
+                 float max_norm, const void* partials, int npartials, float* ema, float ema_decay, void* status, const void* table, int nslots,
+                 int nblocks, void* workspace, size_t workspace_bytes, sd_stream_t stream) {
+    if (int e = check_groups_form("sd_lamb_step", param, grad, n, weight_decay, group_ids, lr_mul, wd_mul, ngroups, max_norm, partials, npartials, ema,
+                                  ema_decay, status)) return e;
+    SD_REQUIRE(exp_avg && exp_avg_sq && step >= 1, SD_ERR_INVALID, "sd_lamb_step: bad arguments (null exp_avg / exp_avg_sq, step >= 1)");
+    SD_REQUIRE(aligned16(exp_avg) && aligned16(exp_avg_sq), SD_ERR_ALIGN, "sd_lamb_step: pointers must be 16-byte aligned");
+    SD_REQUIRE(n / 4 <= INT32_MAX, SD_ERR_INVALID, "sd_lamb_step: n must be below 2^33 (got %lld)", (long long)n);
+    SD_REQUIRE(table && workspace, SD_ERR_INVALID, "sd_lamb_step: needs the slot table (device, from sd_lamb_table_build) and the workspace");
+    SD_REQUIRE(nslots >= 1 && nslots <= SD_LAMB_MAX_SLOTS, SD_ERR_INVALID, "sd_lamb_step: nslots must be in [1, %d] (got %d)", SD_LAMB_MAX_SLOTS, nslots);
+    SD_REQUIRE(nblocks >= nslots && (int64_t)nblocks <= (int64_t)nslots * SD_LAMB_MAX_SLOT_BLOCKS, SD_ERR_INVALID,
+               "sd_lamb_step: nblocks must be in [nslots, %d * nslots] (got %d for %d slots)", SD_LAMB_MAX_SLOT_BLOCKS, nblocks, nslots);
+    SD_REQUIRE(aligned16(table) && (reinterpret_cast<uintptr_t>(workspace) & 7u) == 0, SD_ERR_ALIGN,
+               "sd_lamb_step: the table must be 16-byte aligned, the workspace 8-byte aligned");
+    SD_REQUIRE(workspace_bytes >= sd_lamb_workspace_bytes(nblocks), SD_ERR_WORKSPACE, "sd_lamb_step: workspace too small (%zu bytes, %d blocks need %zu)",
+               workspace_bytes, nblocks, sd_lamb_workspace_bytes(nblocks));
+    const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
+    const SgdGroupTable tab = rate_table(lr, weight_decay, lr_mul, wd_mul, ngroups);
+    const bool clip = max_norm > 0.f, avg = ema != nullptr;
+    const int64_t n4 = n / 4;
+    const hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(clip ? k_lamb_moments<true> : k_lamb_moments<false>, dim3(nblocks), dim3(256), 0, st, param, grad, exp_avg, exp_avg_sq, n4, tab, beta1,
+                       beta2, eps, (float)bc1, (float)sqrt(bc2), grad_scale, group_ids, max_norm, (const double*)partials, npartials, (uint32_t*)status,
+                       (const int32_t*)table, nslots, nblocks, (double*)workspace);
+    SD_LAUNCH_CHECK();
+    using kernel_t = decltype(&k_lamb_apply<true, true>);
+    static const kernel_t variants[4] = {k_lamb_apply<false, false>, k_lamb_apply<true, false>, k_lamb_apply<false, true>, k_lamb_apply<true, true>};
+    SD_RETURN_LAUNCH(variants[(int)clip | (int)avg << 1], nblocks, 0, st, param, exp_avg, exp_avg_sq, n4, tab, eps, (float)bc1, (float)sqrt(bc2), grad_scale,
+                     group_ids, max_norm, (const double*)partials, npartials, ema, ema_decay, (const int32_t*)table, nslots, nblocks,
+                     (const double*)workspace);
+}
+
 // the count and the mode of sd_grad_accum (shared with sd_nn_kernel_names)
 static int check_grad_accum(const char* what, int64_t n, int overwrite) {
     SD_REQUIRE(n >= 0 && n % 4 == 0, SD_ERR_INVALID, "%s: needs n >= 0 and n %% 4 == 0 (got %lld)", what, (long long)n);
@@ -2662,8 +3004,11 @@ static int check_desc(const char* what, const sd_nn_call_desc& d, int64_t M) {
     case SD_NN_STEM_BWD: case SD_NN_STEM_BWD_REDUCE: case SD_NN_STEM_BWD_APPLY:
         if (int e = check_stem_quad(what, stem_bwd_quad(d.H, d.W), !d.form)) return e;
         return check_mc(what, M, d.C);
-    case SD_NN_CAST: case SD_NN_ADAM: case SD_NN_GRAD_SUMSQ: case SD_NN_OPTIM: case SD_NN_OPTIM_GROUPS:
+    case SD_NN_CAST: case SD_NN_ADAM: case SD_NN_GRAD_SUMSQ: case SD_NN_OPTIM: case SD_NN_OPTIM_GROUPS: case SD_NN_SGD: case SD_NN_LAMB:
         SD_REQUIRE(M > 0 && M % 4 == 0, SD_ERR_INVALID, "%s: needs n > 0 and n %% 4 == 0 (got %lld)", what, (long long)M);
+        SD_REQUIRE(d.op != SD_NN_SGD || (d.form >= 0 && d.form <= 2), SD_ERR_INVALID, "%s: sgd's form must be 0 (no momentum), 1 (momentum) or 2 (nesterov), got %d",
+                   what, d.form);
+        SD_REQUIRE(d.op != SD_NN_LAMB || d.rows >= 1, SD_ERR_INVALID, "%s: lamb needs the block count of sd_lamb_table_build in rows (got %d)", what, d.rows);
         return 0;
     case SD_NN_GRAD_ACCUM: return check_grad_accum(what, M, d.form);
     case SD_NN_BN_FOLD: case SD_NN_HEAD_FWD: case SD_NN_HEAD_BWD: return 0;
@@ -2775,6 +3120,22 @@ const char* sd_nn_kernel_names(const sd_nn_call_desc* d) {
         static const char* const tf[2] = {"false", "true"};
         if (clip) out.add("k_grad_sumsq", sumsq_blocks(M));
         out.add(NAME("k_optim_groups<%s, %s>", tf[clip], tf[avg]), ew_launch(M / 4));
+        break;
+    }
+    case SD_NN_SGD: {                                                          // sd_grad_sumsq (with clipping), sd_sgd_step; form = momentum kind
+        const bool clip = d->flags & SD_NN_CLIP, avg = d->flags & SD_NN_EMA;
+        static const char* const tf[2] = {"false", "true"};
+        if (clip) out.add("k_grad_sumsq", sumsq_blocks(M));
+        out.add(NAME("k_sgd<%d, %s, %s>", d->form, tf[clip], tf[avg]), ew_launch(M / 4));
+        break;
+    }
+    case SD_NN_LAMB: {                                                         // sd_grad_sumsq (with clipping), sd_lamb_step's two passes; rows = its nblocks
+        const bool clip = d->flags & SD_NN_CLIP, avg = d->flags & SD_NN_EMA;
+        static const char* const tf[2] = {"false", "true"};
+        if (clip) out.add("k_grad_sumsq", sumsq_blocks(M));
+        out.add(NAME("k_lamb_moments<%s>", tf[clip]), d->rows);
+        out.add(NAME("k_lamb_apply<%s, %s>", tf[clip], tf[avg]), d->rows);
+        out.put(" | ws_bytes=%zu", sd_lamb_workspace_bytes(d->rows));
         break;
     }
     case SD_NN_GRAD_ACCUM:                                                     // n == 0: no launch, an empty answer

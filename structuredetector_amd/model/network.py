@@ -1167,6 +1167,20 @@ class Network(nn.Module):
         assert self.flat_params is None or ids.numel() * 4 == self.flat_params.numel()
         return ids, groups
 
+    def optim_slots(self):
+        """The slot table of the layer-wise optimizer (`TrainStep(optimizer="lamb")`, sd_lamb_step): one (lo, hi, adapt) per parameter,
+        in flat-buffer order.  [lo, hi) is the parameter's 8-float slot in floats (the layout of `_build_flat`, padding included, so it
+        can be asked for before `.to(device)`); the slots tile the buffer like the ids of `optim_groups()`.  adapt: the slot's step is
+        scaled by its trust ratio -- True for 4-D tensors (convolution weights, the tensors `optim_groups()` marks as decayed), False
+        for biases and BatchNorm weight / bias."""
+        slots, off = [], 0
+        for p in self.parameters():                          # `_build_flat`: registration order, 8-float slots
+            hi = off + (p.numel() + 7) // 8 * 8
+            slots.append((off, hi, p.dim() == 4))
+            off = hi
+        assert self.flat_params is None or off == self.flat_params.numel()
+        return slots
+
     def grad_of(self, p):
         off, n = self._flat_off[id(p)]
         g = self.flat_grads[off:off + n]

@@ -108,12 +108,20 @@ class TrainStep:
     runs with grad_scale = 1 / (K * world): the mean of the micro-batch gradients (not the gradient of one large batch: every
     micro-loss divides by its own batch's counts).  `updated` tells whether the call ran the optimizer; `step_count` counts optimizer
     steps.  `flush()` ends a partial group (the end of an epoch) with the mean over what it holds.  With K = 1 nothing of this exists:
-    no buffer, no launch, the step as it always was.  Neither buffer is read or written below `frozen_off`."""
+    no buffer, no launch, the step as it always was.  Neither buffer is read or written below `frozen_off`.
+
+    `optimizer` picks the update rule ("adam", the default and the step as it always was; "sgd": torch.optim.SGD with `momentum` and
+    `nesterov`, dampening 0, sd_sgd_step; "lamb": LAMB with the trust ratio on convolution weights, sd_lamb_step).  The two new rules
+    always run in the groups form -- `Network.optim_groups()` ids, a uniform rate table when `lr_mults` is None -- and take every
+    option above unchanged.  Under sgd `weight_decay` is COUPLED L2 (it enters the gradient and the momentum), `exp_avg` is the momentum
+    buffer and `exp_avg_sq` is None; lamb keeps both moments and adds the network's slot table (`Network.optim_slots()`, uploaded once)
+    and a few KB of fp64 partials.  No accuracy is claimed for either: the update rules are tested, not trained models."""
 
     MAX_ACCUM_STEPS = 64
+    OPTIMIZERS = ("adam", "sgd", "lamb")
 
     def __init__(self, net, args, lr=None, betas=(0.9, 0.999), eps=1e-8, process_group=None, exchange=None, sync_bn=False,
-                 weight_decay=0.0, clip_grad_norm=0.0, ema_decay=0.0, lr_mults=None, accum_steps=1):
+                 weight_decay=0.0, clip_grad_norm=0.0, ema_decay=0.0, lr_mults=None, accum_steps=1, optimizer="adam", momentum=0.9, nesterov=False):
         if net.flat_params is None:
             raise L.SdError("move the Network to the GPU before building TrainStep")
         if isinstance(accum_steps, bool) or not isinstance(accum_steps, int) or not 1 <= accum_steps <= self.MAX_ACCUM_STEPS:
@@ -121,12 +129,19 @@ class TrainStep:
         if weight_decay < 0 or clip_grad_norm < 0 or not 0 <= ema_decay < 1:
             raise ValueError(f"weight_decay and clip_grad_norm must be >= 0 and ema_decay in [0, 1), got {weight_decay!r}, {clip_grad_norm!r}, "
                              f"{ema_decay!r}")
+        if optimizer not in self.OPTIMIZERS:
+            raise ValueError(f"optimizer must be one of {', '.join(self.OPTIMIZERS)}, got {optimizer!r}")
+        if not 0 <= momentum < 1:                            # (false for nan)
+            raise ValueError(f"momentum must be in [0, 1), got {momentum!r}")
+        if optimizer == "sgd" and nesterov and momentum == 0:
+            raise ValueError("nesterov needs momentum > 0")
+        self.optimizer, self.momentum, self.nesterov = optimizer, float(momentum), bool(nesterov)
         self.lr_mults = self.check_lr_mults(lr_mults)
         self.net, self.args = net, args
         self.lr = float(lr if lr is not None else getattr(args, "learning_rate", 1e-3))
         self.betas, self.eps = betas, eps
         self.exp_avg = torch.zeros_like(net.flat_params)
-        self.exp_avg_sq = torch.zeros_like(net.flat_params)
+        self.exp_avg_sq = torch.zeros_like(net.flat_params) if optimizer != "sgd" else None      # sgd: one state buffer (the momentum)
         self.frozen = (int(getattr(net, "frozen_stages", 0)), bool(getattr(net, "frozen_bn", False)))
         self.frozen_off = net.frozen_range()[1] if self.frozen[0] else 0          # the optimizer's range starts behind the frozen stages
         self._zero_frozen_moments()
@@ -166,7 +181,7 @@ class TrainStep:
         # large-batch options of the optimizer (sd_optim_step): all zero = the plain sd_adam_step launch.  The status block
         # ([0] float norm, [1] float clip coefficient, [2] int32 skipped steps) lives on the device and is never read by the step.
         self.weight_decay, self.clip_grad_norm, self.ema_decay = float(weight_decay), float(clip_grad_norm), float(ema_decay)
-        self.decay_mask = self.ema = self._partials = self.group_ids = None
+        self.decay_mask = self.ema = self._partials = self.group_ids = self._lamb = None
         self._status = torch.zeros(4, dtype=torch.int32, device=net.flat_params.device)
         self._status.view(torch.float32)[1] = 1.0
         self._configure_optim()
@@ -177,21 +192,24 @@ class TrainStep:
         for p in net._frozen_parameters() if self.frozen[0] else ():
             off, n = net._flat_off[id(p)]
             self.exp_avg[off:off + n].zero_()
-            self.exp_avg_sq[off:off + n].zero_()
+            if self.exp_avg_sq is not None:
+                self.exp_avg_sq[off:off + n].zero_()
 
     # ---- AdamW decay / global-norm clipping / weight EMA ----------------------------------------------------------------------
     def _configure_optim(self):
         """Buffers of the options that are on: the decay mask, the partials of the norm, the EMA copy (kept if it already exists)."""
         net = self.net
-        if self.lr_mults is not None and self.group_ids is None:
+        if (self.lr_mults is not None or self.optimizer != "adam") and self.group_ids is None:
             # per-stage rates (sd_optim_groups_step): the byte map on the device, the two tables on the host (they travel by value with
             # every launch).  The map carries the decay bit too, so the mask is not built.
             import ctypes as C
             ids, groups = net.optim_groups()
             self.group_ids, self.groups = ids.to(net.flat_params.device), groups
-            self._lr_mul = (C.c_float * len(groups))(*(self.lr_mults[stage] for stage, _ in groups))
+            self._lr_mul = (C.c_float * len(groups))(*(self.lr_mults[stage] if self.lr_mults is not None else 1.0 for stage, _ in groups))
             self._wd_mul = (C.c_float * len(groups))(*(float(decayed) for _, decayed in groups))
-        if self.weight_decay > 0 and self.decay_mask is None and self.lr_mults is None:
+        if self.optimizer == "lamb" and self._lamb is None:
+            self._lamb = self._build_lamb_table()
+        if self.weight_decay > 0 and self.decay_mask is None and self.group_ids is None:
             self.decay_mask = self.build_decay_mask(net)
         if self.clip_grad_norm > 0 and self._partials is None:
             self._partials = torch.empty(L.lib().sd_grad_sumsq_workspace_bytes(net.flat_grads.numel() - self.frozen_off) // 8, dtype=torch.float64,
@@ -200,6 +218,24 @@ class TrainStep:
             self.ema = net.flat_params.detach().clone()
         if self.ema_decay == 0:
             self.ema = None
+
+    def _build_lamb_table(self):
+        """sd_lamb_step's static part: the slot table of the range behind the frozen prefix (`Network.optim_slots()`, shifted by
+        `frozen_off`), laid out on the host by sd_lamb_table_build and uploaded once, and the workspace of its per-block partials.
+        Returns (table, nslots, nblocks, workspace)."""
+        import ctypes as C
+        net, lib, off = self.net, L.lib(), self.frozen_off
+        slots = [(lo - off, hi - off, adapt) for lo, hi, adapt in net.optim_slots() if lo >= off]
+        count, n = len(slots), net.flat_params.numel() - off
+        lo = (C.c_int64 * count)(*(s[0] for s in slots))
+        hi = (C.c_int64 * count)(*(s[1] for s in slots))
+        adapt = (C.c_ubyte * count)(*(int(s[2]) for s in slots))
+        need, nblocks = C.c_size_t(), C.c_int()
+        L.check(lib.sd_lamb_table_build(lo, hi, adapt, count, n, None, 0, C.byref(need), C.byref(nblocks)), "sd_lamb_table_build")
+        host = torch.zeros(need.value // 4, dtype=torch.int32)
+        L.check(lib.sd_lamb_table_build(lo, hi, adapt, count, n, host.data_ptr(), need.value, None, None), "sd_lamb_table_build")
+        dev = net.flat_params.device
+        return host.to(dev), count, nblocks.value, torch.empty(lib.sd_lamb_workspace_bytes(nblocks.value) // 8, dtype=torch.float64, device=dev)
 
     @staticmethod
     def build_decay_mask(net):
@@ -260,6 +296,20 @@ class TrainStep:
         clip = self.clip_grad_norm > 0
         if clip:
             L.check(lib.sd_grad_sumsq(net.flat_grads.data_ptr() + 4 * off, n, self._partials.data_ptr(), self._partials.numel() * 8, st), "sd_grad_sumsq")
+        if self.optimizer != "adam":                 # sgd / lamb: always the groups form; the same tail of arguments for both
+            tail = (grad_scale, self.weight_decay, self.group_ids.data_ptr() + off // 4, self._lr_mul, self._wd_mul, len(self.groups), self.clip_grad_norm,
+                    self._partials.data_ptr() if clip else None, self._partials.numel() if clip else 0,
+                    self.ema.data_ptr() + 4 * off if self.ema is not None else None,
+                    self.ema_decay_at(self.step_count) if self.ema is not None else 0.0, self._status.data_ptr())
+            if self.optimizer == "sgd":
+                L.check(lib.sd_sgd_step(net.flat_params.data_ptr() + 4 * off, net.flat_grads.data_ptr() + 4 * off, self.exp_avg.data_ptr() + 4 * off, n,
+                                        self.lr, self.momentum, int(self.nesterov), *tail, st), "sd_sgd_step")
+                return
+            table, nslots, nblocks, ws = self._lamb
+            L.check(lib.sd_lamb_step(net.flat_params.data_ptr() + 4 * off, net.flat_grads.data_ptr() + 4 * off, self.exp_avg.data_ptr() + 4 * off,
+                                     self.exp_avg_sq.data_ptr() + 4 * off, n, self.step_count, self.lr, self.betas[0], self.betas[1], self.eps, *tail,
+                                     table.data_ptr(), nslots, nblocks, ws.data_ptr(), ws.numel() * 8, st), "sd_lamb_step")
+            return
         if self.lr_mults is not None:                # per-stage rates: the same single launch, rate and decay looked up per 16-byte group
             L.check(lib.sd_optim_groups_step(net.flat_params.data_ptr() + 4 * off, net.flat_grads.data_ptr() + 4 * off, self.exp_avg.data_ptr() + 4 * off,
                                              self.exp_avg_sq.data_ptr() + 4 * off, n,
@@ -303,20 +353,31 @@ class TrainStep:
     def state_dict(self):
         """Optimizer state of the flat-buffer Adam: both moment buffers, the step count (bias correction) and the learning rate.
         Tensors are copies on the host; `Network.state_dict()` carries the weights and BatchNorm buffers."""
-        state = {"exp_avg": self.exp_avg.detach().cpu().clone(), "exp_avg_sq": self.exp_avg_sq.detach().cpu().clone(),
+        state = {"exp_avg": self.exp_avg.detach().cpu().clone(), "exp_avg_sq": None if self.exp_avg_sq is None else self.exp_avg_sq.detach().cpu().clone(),
                  "step_count": int(self.step_count), "lr": float(self.lr), "betas": tuple(self.betas), "eps": float(self.eps),
                  "flat_numel": int(self.net.flat_params.numel())}
         if not self.plain_adam:          # (one host read of the skip counter: state_dict is a checkpoint, not the step)
             state.update(weight_decay=self.weight_decay, clip_grad_norm=self.clip_grad_norm, ema_decay=self.ema_decay,
                          skipped_steps=int(self.skipped_steps), ema=None if self.ema is None else self.ema.detach().cpu().clone())
+        if self.optimizer != "adam":     # (a state without the key is Adam's: files from before the choice existed)
+            state.update(optimizer=self.optimizer, momentum=self.momentum, nesterov=self.nesterov)
+            if self.exp_avg_sq is None:
+                del state["exp_avg_sq"]
         return state
 
     def load_state_dict(self, state):
         if int(state["flat_numel"]) != self.net.flat_params.numel():
             raise L.SdError(f"optimizer state is for a flat parameter buffer of {state['flat_numel']} floats, this network has "
                             f"{self.net.flat_params.numel()} (different labels / parts / fpn_depth?)")
+        kind = state.get("optimizer", "adam")
+        if kind != self.optimizer:
+            raise L.SdError(f"optimizer state was written by optimizer {kind!r}, this step was built with optimizer {self.optimizer!r}: the moment "
+                            "buffers of one rule mean nothing to another (resume with the run's --optimizer, or start from the weights alone)")
         self.exp_avg.copy_(state["exp_avg"])
-        self.exp_avg_sq.copy_(state["exp_avg_sq"])
+        if self.exp_avg_sq is not None:
+            self.exp_avg_sq.copy_(state["exp_avg_sq"])
+        if kind == "sgd":                            # the momentum travels with the run, like the options below
+            self.momentum, self.nesterov = float(state.get("momentum", self.momentum)), bool(state.get("nesterov", self.nesterov))
         self.step_count, self.lr = int(state["step_count"]), float(state["lr"])
         self.betas, self.eps = tuple(state["betas"]), float(state["eps"])
         # the options travel with the run; a file written without them (or before they existed) loads with all three off
@@ -487,7 +548,7 @@ class TrainStep:
         grad_scale = 1.0 / (k * self.world)
         self.step_count += 1
         T.push("adam")
-        if self.plain_adam and self.lr_mults is None:
+        if self.plain_adam and self.lr_mults is None and self.optimizer == "adam":
             off = 4 * self.frozen_off                # bytes: the frozen stages' prefix is not the optimizer's
             L.check(L.lib().sd_adam_step(net.flat_params.data_ptr() + off, net.flat_grads.data_ptr() + off, self.exp_avg.data_ptr() + off,
                                          self.exp_avg_sq.data_ptr() + off, net.flat_params.numel() - self.frozen_off, self.step_count, self.lr, self.betas[0],
@@ -569,7 +630,10 @@ def train_step_kwargs(args):
     for name in ("weight_decay", "clip_grad_norm", "ema_decay"):          # optimizer options: passed when set (TrainStep's defaults are "off")
         if getattr(args, name, 0.0):
             kw[name] = float(getattr(args, name))
-    from ..utils.args import check_accum, check_lr, stage_lr_mults
+    from ..utils.args import check_accum, check_lr, check_optimizer, stage_lr_mults
+    kind = check_optimizer(args)                                          # --optimizer / --momentum / --nesterov: passed when not adam
+    if kind.optimizer != "adam":
+        kw.update(optimizer=kind.optimizer, momentum=kind.momentum, nesterov=kind.nesterov)
     lr = check_lr(args)
     mults = stage_lr_mults(lr.backbone_lr_mult, lr.lr_layer_decay)        # --backbone_lr_mult / --lr_layer_decay: None when both are 1
     if mults is not None:
@@ -980,6 +1044,10 @@ class Trainer:
         if self.rank == 0 and not self.step.plain_adam:
             print(f"optimizer: weight decay {self.step.weight_decay:g} (convolution weights), gradient clipping at norm "
                   f"{self.step.clip_grad_norm:g}, weight EMA {self.step.ema_decay:g} (0 = off)", flush=True)
+        if self.rank == 0 and self.step.optimizer != "adam":
+            s = self.step
+            print("update rule: " + (f"SGD, momentum {s.momentum:g}{' (Nesterov)' if s.nesterov else ''}; --weight_decay is coupled L2" if s.optimizer == "sgd"
+                                     else "LAMB, trust ratio on convolution weights; biases and BatchNorm parameters step without it"), flush=True)
         if self.rank == 0 and self.step.accum_steps > 1:
             k, b, world = self.step.accum_steps, self.args.batch_size, self.step.world
             print(f"gradient accumulation: {k} batches per optimizer step, effective batch {k * b * world} ({k} x {b} x {world} rank(s)); "

@@ -30,7 +30,8 @@ _FLAGS = [
     (("--batch_size", "-b"), dict(type=int, default=8, help="Batch size for training.")),
     (("--epochs", "-e"), dict(type=int, default=100, help="The number of epochs to train.")),
     (("--no_augmentation", "-a"), dict(action="store_true", help="Disable training augmentations.")),
-    (("--learning_rate", "-l"), dict(type=float, default=1e-3, help="The learning rate for training.")),
+    (("--learning_rate", "-l"), dict(type=float, default=1e-3, help="The learning rate for training. The default is Adam's: "
+                                     "--optimizer sgd usually wants a rate 10 to 100 times larger.")),
     (("--lr_step",), dict(type=int, default=3, help="Number of divisions by 10 of the learning rate (0 = off).")),
     (("--down_ratio", "-g"), dict(type=float, default=4.0, help="Downsampling ratio of the network.")),
     (("--hm_loss_fn", "-f"), dict(type=str, default="mse", help="Heatmap loss: 'focal' or 'mse'.")),
@@ -62,7 +63,8 @@ _FLAGS = [
     (("--cache_images",), dict(type=float, default=0.0, help="GB of device memory for decoded training / validation images, kept across "
                                "epochs (decoded once before epoch 1; images beyond the budget are decoded every epoch; 0 = off).")),
     (("--weight_decay",), dict(type=float, default=0.0, help="Decoupled weight decay (torch.optim.AdamW) on the convolution weights; biases "
-                               "and BatchNorm parameters are not decayed (0 = off: plain Adam).")),
+                               "and BatchNorm parameters are not decayed (0 = off: plain Adam). Under --optimizer sgd it is coupled L2 "
+                               "(torch.optim.SGD: added to the gradient, so it passes through the momentum); under lamb it is added to the update.")),
     (("--clip_grad_norm",), dict(type=float, default=0.0, help="Clip the global norm of the (averaged) gradient to this value "
                                  "(torch.nn.utils.clip_grad_norm_); a step whose gradient norm is not finite is skipped -- this guard against inf / nan gradients (--amp) exists only with clipping on (0 = off).")),
     (("--ema_decay",), dict(type=float, default=0.0, help="Exponential moving average of the weights with this decay, warmed up as "
@@ -200,6 +202,14 @@ _FLAGS = [
                               "--steps, --warmup_steps, the cosine length and the EMA count optimizer steps, not batches. BatchNorm statistics "
                               "stay per batch (consider --freeze_bn or --sync_bn for small batches). Not consulted by evaluate / detect. "
                               "1 = off.")),
+    (("--optimizer",), dict(type=str, default="adam", choices=["adam", "sgd", "lamb"], help="Update rule of train. adam: Adam / AdamW, as always. "
+                            "sgd: torch.optim.SGD with --momentum (dampening 0; the usual fine-tuning optimizer). lamb: LAMB (You et al. 2020) -- "
+                            "Adam's update scaled per convolution weight by |w| / |update|, for the large effective batches of --accum_steps and "
+                            "many ranks; biases and BatchNorm parameters step without the ratio. Every other training flag works with all three; "
+                            "a run resumes with the optimizer it was started with. Not consulted by evaluate / detect.")),
+    (("--momentum",), dict(type=float, default=0.9, metavar="M", help="Momentum of --optimizer sgd, in [0, 1) (0 = plain SGD, no state buffer "
+                           "is read or written); read by sgd only.")),
+    (("--nesterov",), dict(action="store_true", help="Nesterov momentum for --optimizer sgd (needs --momentum > 0).")),
 ]
 
 _POSITIVE = ["in_channels", "fpn_depth", "batch_size", "epochs", "learning_rate", "down_ratio", "max_objects", "max_parts"]
@@ -494,6 +504,28 @@ def check_accum(args):
     if not 1 <= k <= MAX_ACCUM_STEPS:
         raise ValueError(f"'accum_steps' should be in [1, {MAX_ACCUM_STEPS}] (1 = off), not {k}")
     return k
+
+
+OPTIMIZERS = ("adam", "sgd", "lamb")
+OptimizerOptions = namedtuple("OptimizerOptions", "optimizer momentum nesterov")
+
+
+def check_optimizer(args):
+    """`--optimizer` / `--momentum` / `--nesterov` on a parsed namespace -> OptimizerOptions, as `train` checks them (model/trainer.py;
+    `evaluate`, `detect` and `Predictor` never look at the flags).  A namespace from before the flags gives ("adam", 0.9, False).
+    momentum is in [0, 1) (nan is refused) and is read by sgd only; nesterov under sgd needs momentum > 0."""
+    kind = getattr(args, "optimizer", "adam")
+    kind = "adam" if kind is None else kind
+    if kind not in OPTIMIZERS:
+        raise ValueError(f"'optimizer' should be one of {', '.join(OPTIMIZERS)}, not {kind!r}")
+    momentum = getattr(args, "momentum", 0.9)
+    momentum = 0.9 if momentum is None else momentum
+    if isinstance(momentum, bool) or not isinstance(momentum, (int, float)) or not 0 <= momentum < 1:       # (false for nan)
+        raise ValueError(f"'momentum' should be in [0, 1), not {momentum!r}")
+    nesterov = bool(getattr(args, "nesterov", False))
+    if kind == "sgd" and nesterov and momentum == 0:
+        raise ValueError("'nesterov' needs a 'momentum' greater than 0")
+    return OptimizerOptions(kind, float(momentum), nesterov)
 
 
 def updates_per_epoch(batches, accum_steps):
